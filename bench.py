@@ -31,6 +31,10 @@ algorithmic bytes (12 row elements per cell-step for 2-piece = 24 B with 16-bit 
 box's host cores, at all cores and at one.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c1|c4|c5] [--pairs P]
+
+`--steps K` timed steps (K >= 1) after W untimed ones; `ms_per_step` = the timed region / K.  `--dump-outputs DIR` writes
+what the last timed step returned (awv_align_pairs' per-pair results, float64, at most 64 MB) as DIR/<field>.npy; the
+inputs are seeded, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -48,6 +52,11 @@ HBM_PEAK_GBPS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s
 PAIRS_PER_GPU = 65280   # config 2's pair count: the per-GPU share of the default multi-GPU workload
 N_SIMDS = 1024          # 256 CUs x 4
 CLOCK_HZ_NOMINAL = 2.4e9  # only when the in-kernel clock stamps are unavailable
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs: all ranks' files together
+# --dump-outputs: the per-pair fields of awv_align_pairs' results (cigar_off is left out: an offset into the CIGAR arena,
+# which the timed path keeps on the device and never hands to the caller)
+DUMP_FIELDS = ("status", "penalty", "score", "cigar_len", "num_matches", "num_mismatches", "num_ins", "num_del", "q_end", "t_end")
+DUMP_SAMPLE_SEED = 20240611
 
 
 def usable_cores():
@@ -89,6 +98,26 @@ def self_launch(n, argv):
     raise SystemExit(p.returncode if p.returncode or line else 1)
 
 
+def dump_outputs(out_dir, res, rank, world):
+    """Writes the last timed step's results, field by field, as out_dir/<field>.npy (float64: every field is a 32-bit
+    integer, so the values are exact) plus pair_index.npy, the rows of this rank's pair list they belong to.  Above the
+    byte budget a fixed, seeded sample of the rows is written (the same rows on every run with the same arguments).  With
+    several ranks each writes its own shard's files, suffixed _rank<r>.  Returns (rows written, rows)."""
+    import numpy as np
+    n = len(res)
+    budget = (DUMP_BYTES_MAX // max(world, 1) - 4096) // (8 * (len(DUMP_FIELDS) + 1))  # rows this rank may write (4 KB: .npy headers)
+    if n <= budget:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=budget, replace=False))
+    suffix = "_rank%d" % rank if world > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pair_index%s.npy" % suffix), idx.astype(np.float64))
+    for f in DUMP_FIELDS:
+        np.save(os.path.join(out_dir, "%s%s.npy" % (f, suffix)), res[f][idx].astype(np.float64))
+    return len(idx), n
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -107,7 +136,12 @@ def main():
                     help="plumbing check without a GPU: ranks rendezvous over gloo, shard the job, reduce counters and print the line's launch fields")
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="debug: all ranks share GPU 0 and synchronise over gloo (multi-rank plumbing on a 1-GPU box)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the per-pair results of the last timed step as DIR/<field>.npy (float64; "
+                         "a fixed, seeded sample of the pairs when all of them would exceed %d MB)" % (DUMP_BYTES_MAX >> 20))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
@@ -213,6 +247,7 @@ def main():
         cig_bytes += int(res["cigar_len"].sum())
     barrier()
     elapsed = time.perf_counter() - t0
+    dumped = dump_outputs(args.dump_outputs, res, rank, world) if args.dump_outputs else None
     if (res["status"] != 0).any():
         raise SystemExit("bench: %d pairs did not complete" % int((res["status"] != 0).sum()))
 
@@ -312,6 +347,8 @@ def main():
         "kernel_ms_max_over_mean": (max(per_rank_kernel_ms) / (sum(per_rank_kernel_ms) / len(per_rank_kernel_ms))) if per_rank_kernel_ms else None,
         "roofline": roof,
     }
+    if dumped:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "pairs": dumped[0], "of": dumped[1], "fields": list(DUMP_FIELDS)}
 
     if world == 1 and not args.no_paf:
         # secondary figures (never `value`): the whole boundary end to end -- sequences on the host ->

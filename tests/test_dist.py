@@ -6,8 +6,18 @@ import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def host(hip_lib):
+    """The host library (the cost-balanced partition behind shard_pairs with lengths), built if stale."""
+    from allwave_amd import build, host as H
+    build.build_host()
+    H.load()
+    return H
 
 
 def run_world(world, tmp_path):
@@ -46,7 +56,7 @@ def test_two_ranks_equal_one(tmp_path):
     assert two["lines"] == one["lines"] and len(one["lines"]) == one["n"]
 
 
-def test_bench_launches_its_own_ranks():
+def test_bench_launches_its_own_ranks(host):
     """A bare `python bench.py --gpus 2` (no WORLD_SIZE in the environment: the shape of the driver's
     command) starts two ranks itself and relays rank 0's line; --launch-check runs the launcher, the
     gloo rendezvous, the shard arithmetic and the reductions of the real run without a GPU."""
@@ -63,7 +73,7 @@ def test_bench_launches_its_own_ranks():
     assert bad.returncode != 0 and b"WORLD_SIZE=3" in bad.stderr
 
 
-def test_cost_balanced_shards_config5():
+def test_cost_balanced_shards_config5(host):
     """Config 5's pair list (512 prefixes of 1-50 kbp, -p tree:3:1:0.1): per-pair cost spans orders of
     magnitude.  The LPT partition keeps max/mean predicted shard cost <= 1.05 for N = 8, every pair
     lands on exactly one rank, and equal-cost lists come out strided."""

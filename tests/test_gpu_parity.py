@@ -11,6 +11,15 @@ import pytest
 from util import DEFAULT_2P, EDIT, PENALTY_SETS, mutate, rand_seq, random_pair, rle
 
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def host(hip_lib):
+    """The host library (the planner's sparsifiers), built if stale."""
+    from allwave_amd import build, host as H
+    build.build_host()
+    H.load()
+    return H
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
@@ -514,7 +523,7 @@ def test_config4_shaped_budgeted_rows(oracle):
         e.close()
 
 
-def test_config5_shaped_sparsified_mixed_lengths(engine, oracle):
+def test_config5_shaped_sparsified_mixed_lengths(engine, oracle, host):
     """BASELINE config 5's shape, scaled down: prefixes of 1-9 kbp of a common root at 10 %, the pair
     list from the host planner's tree sparsifier (-p tree:3:1:0.1); bit-exact against the oracle."""
     from allwave_amd import host as H, synth
@@ -525,7 +534,7 @@ def test_config5_shaped_sparsified_mixed_lengths(engine, oracle):
     check_against_oracle(engine, oracle, seqs, pairs, DEFAULT_2P)
 
 
-def test_config5_real_lengths(oracle):
+def test_config5_real_lengths(oracle, host):
     """BASELINE configs[4] (config 5) at its REAL lengths: 512 prefixes of 1-50 kbp of a common root at
     10 %, pair list from the planner's `-p tree:3:1:0.1` (iterator.rs:30-50 -> knn_graph.rs); eight
     pairs of that list -- the shortest query against the longest target it meets, the longest against
