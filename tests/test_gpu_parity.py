@@ -8,7 +8,7 @@ import random
 import numpy as np
 import pytest
 
-from util import DEFAULT_2P, EDIT, PENALTY_SETS, mutate, rand_seq, random_pair, rle
+from util import DEFAULT_2P, EDIT, PENALTY_SETS, check_against_oracle, mutate, rand_seq, random_pair, rle
 
 pytestmark = pytest.mark.gpu
 
@@ -21,24 +21,6 @@ def host(hip_lib):
     H.load()
     return H
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def check_against_oracle(engine, oracle, seqs, pairs, scores):
-    engine.set_sequences(seqs)
-    res, cigs = engine.align_pairs(scores, pairs)
-    al = oracle.Aligner(scores)
-    for i, p in enumerate(pairs):
-        a, b = p[0], p[1]
-        pen, ops = al.align(seqs[a], seqs[b])
-        assert res["status"][i] == 0, (scores, i)
-        assert res["penalty"][i] == pen and res["score"][i] == -pen, (scores, i, len(seqs[a]), len(seqs[b]))
-        assert cigs[i] == ops, (scores, i, rle(cigs[i])[:60], rle(ops)[:60])
-        c = {k: ops.count(k.encode()) for k in "MXID"}
-        assert (res["num_matches"][i], res["num_mismatches"][i], res["num_ins"][i], res["num_del"][i]) == \
-               (c["M"], c["X"], c["I"], c["D"])
-        # parse_cigar_lengths of /root/reference/src/alignment.rs:320-344
-        assert res["q_end"][i] == c["M"] + c["X"] + c["D"] == len(seqs[a])
-        assert res["t_end"][i] == c["M"] + c["X"] + c["I"] == len(seqs[b])
 
 
 def test_golden_fixtures(engine):

@@ -10,8 +10,11 @@ import json
 import os
 import random
 
+import statistics
+
 import pytest
 
+import repeats
 from util import DEFAULT_2P, EDIT, PENALTY_SETS, mutate, rand_seq, random_pair, rle
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -198,3 +201,42 @@ def test_pin_files_are_what_the_oracle_gives():
     assert len(rows) == len(doc["cases"])
     for r, c in zip(rows, doc["cases"]):
         assert r == [c["name"], ",".join(map(str, c["scores"])), c["pattern"], c["text"], str(c["penalty"]), c["cigar"]]
+
+
+@pytest.mark.parametrize("family", sorted(repeats.SMALL))
+@pytest.mark.parametrize("scores", PENALTY_SETS)
+def test_repeat_families_optimal_and_valid(oracle, scores, family):
+    """Repeat-rich pairs (tests/repeats.py), where co-optimal alignments are many and tie-breaking decides the CIGAR: the
+    penalty is the Gotoh optimum, the CIGAR is valid and re-scores to it, BiWFA and plain WFA agree on it, and the mode with
+    the kernel's shortcuts (exact overlap pre-filter, known-optimum stop) gives the same bytes as the plain search."""
+    rng = random.Random("%s/%s" % (family, scores))
+    gen = repeats.SMALL[family]
+    al, fast = oracle.Aligner(scores), oracle.Aligner(scores)
+    fast.set_fast_overlap(True)
+    for it in range(8):
+        s, t = gen(rng)
+        pen, ops = al.align(s, t)
+        pen_u, ops_u = al.align_unidirectional(s, t)
+        g = oracle.gotoh_penalty(s, t, scores)
+        assert oracle.cigar_check(ops, s, t, scores) == (0, g), (family, it, len(s), len(t))
+        assert oracle.cigar_check(ops_u, s, t, scores) == (0, g), (family, it, len(s), len(t))
+        assert pen == pen_u == g, (family, it, len(s), len(t))
+        assert fast.align(s, t) == (pen, ops), (family, it, len(s), len(t))
+
+
+def test_repeat_families_are_tie_heavy(oracle):
+    """The repeat families must keep the tie-breaking busy: two optimal alignments of a pair -- the oracle's, and the one of
+    the reversed pair reversed back -- differ on a median number of DP cells at least 4x that of the random inputs the rest
+    of the suite uses (random_pair, and plain 5 % pairs of 1.5 kbp, whichever is larger).  Fails if the generators turn
+    bland."""
+    al = oracle.Aligner(DEFAULT_2P)
+    rng = random.Random(4096)
+    rep = [repeats.tie_cells(al, *repeats.SMALL[f](rng)) for f in sorted(repeats.SMALL) for _ in range(10)]
+    rnd = [repeats.tie_cells(al, *random_pair(rng, 1500)) for _ in range(60)]
+    five = []
+    for _ in range(60):
+        s = rand_seq(rng, 1500)
+        five.append(repeats.tie_cells(al, s, mutate(s, 0.05, rng)))
+    base = max(statistics.median(rnd), statistics.median(five))
+    assert base > 0
+    assert statistics.median(rep) >= 4 * base, (statistics.median(rep), statistics.median(rnd), statistics.median(five))
