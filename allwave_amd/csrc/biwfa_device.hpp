@@ -60,7 +60,11 @@ static_assert(AWV_WG == 128, "direction split = two waves per pair");
 #else
 constexpr bool DIRSPLIT = false;
 #endif
-constexpr int MAX_RING = 128;
+// Accepted penalties: scope = max(x, o1+e1, o2+e2) + 1 <= MAX_SCOPE (engine.hip check_penalties).  The ring of score rows is
+// the power of two >= scope + 2 + multi_T * chain_max - 1 (align_core), so it reaches MAX_RING = 256 rows: e.g. (0,5,121,1),
+// (0,125,3,1) or (0,5,8,2,124,1).  Nothing on the device is sized by it; the ring arena and the LDS row metadata follow kp.ring.
+constexpr int MAX_SCOPE = 126;
+constexpr int MAX_RING = 256;
 constexpr int NCOMP = 5;
 constexpr int32_t OFF_NULL = INT32_MIN / 2;
 constexpr int32_t NULLISH = INT32_MIN / 4;    // any value below is a NULL(+n)
@@ -1400,6 +1404,7 @@ constexpr int CHAIN_MAX32 = AWV_CHAIN_MAX32;  // 32-bit rows: a sweep's M rows a
 constexpr int TMAX32 = AWV_TMAX32;  // steps per sweep with 32-bit rows (their M sources are loaded one step ahead, not all up front)
 constexpr int MSTEPS = 16;  // most steps one pass can cover (a lane table entry per step and per source)
 static_assert(TMAX >= 2 && TMAX <= 8 && TMAX * CHAIN_MAX <= MSTEPS - 1, "pass length");
+static_assert(MAX_SCOPE + 2 + TMAX * CHAIN_MAX - 1 <= MAX_RING, "the deepest ring an accepted penalty set can need");
 
 struct MultiPlan {
   int Tn;                    // steps in this pass = TMAX-step sweeps * nh (the last sweep may be shorter only when nh == 1)

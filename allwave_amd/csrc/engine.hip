@@ -256,7 +256,7 @@ int check_penalties(const awv_penalties* p, awv::DevPenalties& d) {
   int scope = std::max(d.x, d.o1 + d.e1);
   if (d.two_piece) scope = std::max(scope, d.o2 + d.e2);
   d.scope = scope + 1;
-  if (d.scope + 2 > awv::MAX_RING) return fail(AWV_ERR_PENALTIES, "penalties too large: max(x, o+e) must be < 126");
+  if (d.scope > awv::MAX_SCOPE) return fail(AWV_ERR_PENALTIES, "penalties too large: max(x, o1+e1, o2+e2) must be < 126");
   return AWV_OK;
 }
 
@@ -337,6 +337,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
     chain_max = std::max(1, std::min(awv::CHAIN_MAX, (dp.o2 + dp.e2) / awv::TMAX));
   int ring = 4;
   while (ring < dp.scope + 2 + (multi_T > 0 ? multi_T * chain_max - 1 : 0)) ring *= 2;
+  if (ring > awv::MAX_RING) return fail(AWV_ERR_PENALTIES, "ring of " + std::to_string(ring) + " rows exceeds MAX_RING");  // (unreachable: MAX_SCOPE)
   const int64_t max_batch = e->cfg.max_batch_pairs > 0 ? e->cfg.max_batch_pairs : (int64_t)1 << 20;
   uint64_t max_arena = e->cfg.max_arena_bytes > 0 ? (uint64_t)e->cfg.max_arena_bytes : (uint64_t)8 << 30;
   // Experiment knobs read from the environment exist only in a -DAWV_DEBUG_KNOBS build; the product library's
@@ -460,13 +461,49 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
     // row metadata (AWV_WIDE16: only the shorter length < 32760)
     const bool narrow = width != 1, wide_meta = width == 2;
     if (hq.empty()) return AWV_OK;
+    // 16-bit wavefront rows whenever every offset fits (halves the HBM/L2 traffic of the rings): the caller
+    // groups pairs by row width, so one long sequence no longer drags a whole batch to 32-bit rows
+    const size_t esz = narrow ? 2 : 4;
+    // Row offsets inside a workgroup's ring arena are 32-bit and its buffer descriptor holds at most 2^31 - 1 bytes
+    // (row_off, make_rsrc in biwfa_device.hpp): a row past 2 GiB would read 0 and lose its writes.  So no attempt, the first
+    // or a re-run, uses rows wider than wc_2g columns: with 32-bit rows 838,656 at ring 64, 419,328 at ring 128 and 209,664
+    // at ring 256; with 16-bit rows 1,677,568 at ring 64 and 838,656 at ring 128.
+    const int wc_2g = (int)(((size_t)INT32_MAX / ((size_t)2 * NCOMP * ring * esz)) & ~(size_t)255);
+    {
+      // A pair whose length difference alone cannot fit such rows ends CAPACITY here, before any launch (the kernel would
+      // find out only after a long search).  The two searches meet on one diagonal, and a row of wc columns reaches at
+      // most half + COL_PAD - 2 diagonals beyond its search's origin on either side: find_breakpoint clips its diagonal
+      // range to half = (wc - 2 COL_PAD - 9 - 256) / 2 on each side, and the capacity test of compute_row keeps 257 / 262
+      // columns at the row's ends.  So the searches span at most 2 half + 2 COL_PAD diagonals between them.
+      const long long span = 2 * (((long long)wc_2g - 2 * COL_PAD - 9 - 256) / 2) + 2 * COL_PAD;
+      if (amap.empty()) {
+        amap.resize(hq.size());
+        for (size_t i = 0; i < hq.size(); ++i) amap[i] = (int64_t)i;
+      }
+      size_t k = 0;
+      g_maxsum = g_maxlen = 0;
+      for (size_t i = 0; i < hq.size(); ++i) {
+        const int ql = s.len[hq[i]], tl = s.len[ht[i]];
+        if (ql > 0 && tl > 0 && std::llabs((long long)ql - tl) > span) {
+          awv_result r{};
+          r.status = AWV_ST_CAPACITY;
+          r.cigar_off = hoff[i];
+          hres[(size_t)amap[i]] = r;
+          continue;
+        }
+        amap[k] = amap[i];
+        hq[k] = hq[i]; ht[k] = ht[i]; hrc[k] = hrc[i]; hoff[k] = hoff[i];
+        g_maxsum = std::max(g_maxsum, ql + tl);
+        g_maxlen = std::max(g_maxlen, std::max(ql, tl));
+        ++k;
+      }
+      hq.resize(k); ht.resize(k); hrc.resize(k); hoff.resize(k); amap.resize(k);
+      if (k == 0) return AWV_OK;
+    }
     const int wg = waves == 1 ? AWV_THRU_WG : 64 * waves;
     const int nslots_g = e->cfg.workgroups > 0 ? std::max(1, e->cfg.workgroups / (wg / 64)) : (WAVES_PER_SIMD * 256 / wg) * e->num_cus;
     const int wcap_full = ((g_maxsum + 9 + 256 + 2 * COL_PAD) + 255) & ~255;
     const int nslots_want = (int)std::min<int64_t>(nslots_g, (int64_t)hq.size());
-    // 16-bit wavefront rows whenever every offset fits (halves the HBM/L2 traffic of the rings): the caller
-    // groups pairs by row width, so one long sequence no longer drags a whole batch to 32-bit rows
-    const size_t esz = narrow ? 2 : 4;
     // dynamic LDS = ring metadata (16-bit entries with 16-bit rows) + staging of the 2-bit packed
     // sequences: what the largest pair needs, within 160 KB / (16 waves per CU) per workgroup;
     // sub-problems that do not fit read global memory instead
@@ -504,6 +541,8 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
     }
     // (diagnostic / test hook: a narrower first attempt, so that the CAPACITY re-run path can be exercised on short sequences)
     if (e->cfg.first_row_cols > 0) wcap = std::min(wcap, std::max(2048, (e->cfg.first_row_cols + 255) & ~255));
+    wcap = std::min(wcap, wc_2g);
+    const int wc_last = std::min(wcap_full, wc_2g);  // the widest rows a re-run may use
     // ---- attempts: the whole batch at row capacity `wcap`, then only the pairs that outgrew it
     std::vector<awv_result> tres;
     float ms = 0;
@@ -673,7 +712,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       for (int64_t i = 0; i < m; ++i) {
         const int64_t bi = amap.empty() ? i : amap[(size_t)i];
         hres[(size_t)bi] = tres[(size_t)i];
-        if (tres[(size_t)i].status == AWV_ST_CAPACITY && wc < wcap_full && !(e->cfg.flags & AWV_F_NO_RERUN)) again.push_back(i);
+        if (tres[(size_t)i].status == AWV_ST_CAPACITY && wc < wc_last && !(e->cfg.flags & AWV_F_NO_RERUN)) again.push_back(i);
       }
       if (again.empty()) break;
       std::vector<int32_t> q2, t2, rc2;
@@ -687,7 +726,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
         map2.push_back(amap.empty() ? i : amap[(size_t)i]);
       }
       hq.swap(q2); ht.swap(t2); hrc.swap(rc2); hoff.swap(off2); amap.swap(map2);
-      wc = (int)std::min<long long>(wcap_full, 4LL * wc);
+      wc = (int)std::min<long long>(wc_last, 4LL * wc);
     }
     return AWV_OK;
     };

@@ -59,6 +59,13 @@ extern "C" {
 /* per-pair status (awv_result.status) */
 #define AWV_ST_COMPLETED 0
 #define AWV_ST_CAPACITY 1        /* an internal capacity bound was hit (wavefront width / history) */
+/* One bound behind AWV_ST_CAPACITY is fixed: a workgroup's ring of wavefront rows (2 directions x 5 components x `ring` rows of
+ * `wc` columns) is addressed with 32-bit offsets and must stay below 2 GiB, so rows hold at most
+ * ((2^31 - 1) / (10 * ring * bytes per cell)) & ~255 columns -- with 32-bit cells (a sequence of 32,760 bases or more)
+ * 838,656 at ring 64 (the default scores), 419,328 at ring 128 and 209,664 at ring 256 (ring: the power of two
+ * >= max(x, o1+e1, o2+e2) + 3, plus up to 14 with multi-step passes).  A pair whose length difference alone cannot fit such
+ * rows comes back AWV_ST_CAPACITY without being run; a pair whose wavefronts outgrow them (long, very divergent sequences)
+ * comes back AWV_ST_CAPACITY after its last re-run. */
 #define AWV_ST_INTERNAL 2        /* invariant violated (would be a bug) */
 #define AWV_ST_MAX_STEPS 3       /* step guard tripped */
 
