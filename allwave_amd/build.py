@@ -172,7 +172,7 @@ def build_host(force=False, verbose=False):
     # both depend on the ABI header (AllPairIterator embeds an awv_stats: a header-only change must rebuild the library
     # AND the driver, or the two disagree on the object's layout); liballwave_hip itself is linked dynamically
     cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + HOST_DIR,
-           "-o", HOST_LIB] + cpps + ["-L" + PKG, "-lallwave_hip", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath-link,/opt/rocm/lib"]
+           "-o", HOST_LIB] + cpps + ["-L" + PKG, "-lallwave_hip", "-ldl", "-Wl,-rpath,$ORIGIN", "-Wl,-rpath-link,/opt/rocm/lib"]
     _build_one(HOST_LIB, srcs + [ABI_HEADER], cmd, force, verbose)
     cli_src = os.path.join(HOST_DIR, "main.cpp")
     if os.path.exists(cli_src):

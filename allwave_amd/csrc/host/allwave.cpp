@@ -12,6 +12,9 @@
 #include <memory>
 #include <mutex>
 #include <chrono>
+#include <condition_variable>
+#include <dlfcn.h>
+#include <link.h>
 #include <thread>
 
 namespace allwave {
@@ -196,43 +199,65 @@ std::string alignment_to_paf(const AlignmentResult& r, const std::vector<Sequenc
 
 // ---- iterator.rs ----------------------------------------------------------------------------
 namespace {
-// One engine per device and process, created on first use and kept (like the reference's cached
+// One engine per (device, slot) and process, created on first use and kept (like the reference's cached
 // per-thread aligners, alignment.rs:11-22): its HBM arenas are tens of GB, and allocating them right
-// after a free can take the driver seconds.  A holder owns the device's engine for its lifetime.
+// after a free can take the driver seconds.  Slot 0 is the engine every one-device run uses; a run over
+// several slots (with_devices) takes slots 0, 1, ... of each device it names.  A holder owns its slot's
+// engine for its lifetime.  Lock order: a slot's mutex, then the table's (never the other way round).
 std::atomic<int> g_engine_flags{0};  // awv_engine_config.flags of engines created from now on (set_engine_flags)
 std::atomic<int> g_engine_first_row_cols{0};  // awv_engine_config.first_row_cols, likewise (diagnostic / test hook)
+constexpr int64_t kDefaultScratch = (int64_t)160 << 30;  // the engine's default max_scratch_bytes
+struct EngineSlot {
+  awv_engine* e = nullptr;
+  std::unique_ptr<std::mutex> mu{new std::mutex()};  // one run at a time per slot
+};
 struct EngineTable {
-  std::mutex mu;  // guards the table
-  std::map<int, std::pair<awv_engine*, std::unique_ptr<std::mutex>>> engines;
+  std::mutex mu;  // guards the table (entries are never erased: slot mutexes stay put)
+  std::map<std::pair<int, int>, EngineSlot> engines;  // (device, slot)
+  // slots per device of the widest run that created engines there: those engines get max_scratch_bytes = 160 GiB / k
+  // (kept until release_engines)
+  std::map<int, int> scratch_split;
 };
 EngineTable& engine_table() {
   static EngineTable t;
   return t;
 }
+std::mutex* slot_mutex(int device, int slot) {
+  EngineTable& tb = engine_table();
+  std::lock_guard<std::mutex> g(tb.mu);
+  return tb.engines[{device, slot}].mu.get();
+}
+// the slot's engine, created if need be; the caller holds the slot's mutex, so nobody else creates or destroys this slot's
+// engine meanwhile, and the creation itself runs outside the table's lock (slots of different devices start in parallel).
+// `slots_on_device`: how many slots of this device the calling run uses
+awv_engine* slot_engine(int device, int slot, int slots_on_device) {
+  EngineTable& tb = engine_table();
+  EngineSlot* es;
+  awv_engine_config cfg{};
+  {
+    std::lock_guard<std::mutex> g(tb.mu);
+    es = &tb.engines[{device, slot}];
+    if (es->e) return es->e;
+    cfg.device = device;
+    cfg.flags = g_engine_flags.load();
+    cfg.first_row_cols = g_engine_first_row_cols.load();
+    auto sp = tb.scratch_split.find(device);
+    const int k = std::max(slots_on_device, sp == tb.scratch_split.end() ? 1 : sp->second);
+    if (k > 1) {
+      tb.scratch_split[device] = k;
+      cfg.max_scratch_bytes = kDefaultScratch / k;
+    }
+  }
+  awv_engine* e = nullptr;
+  if (awv_engine_create(&cfg, &e) != AWV_OK) throw AlignmentError(std::string("engine: ") + awv_last_error());
+  std::lock_guard<std::mutex> g(tb.mu);
+  es->e = e;
+  return e;
+}
 struct EngineHolder {
   awv_engine* e = nullptr;
   std::unique_lock<std::mutex> lock;
-  explicit EngineHolder(int device) {
-    EngineTable& tb = engine_table();
-    std::mutex* dev_mu;
-    {
-      std::lock_guard<std::mutex> g(tb.mu);
-      auto& slot = tb.engines[device];
-      if (!slot.second) slot.second.reset(new std::mutex());
-      dev_mu = slot.second.get();
-    }
-    lock = std::unique_lock<std::mutex>(*dev_mu);  // one run at a time per device
-    std::lock_guard<std::mutex> g(tb.mu);
-    auto& slot = tb.engines[device];
-    if (!slot.first) {
-      awv_engine_config cfg{};
-      cfg.device = device;
-      cfg.flags = g_engine_flags.load();
-      cfg.first_row_cols = g_engine_first_row_cols.load();
-      if (awv_engine_create(&cfg, &slot.first) != AWV_OK) throw AlignmentError(std::string("engine: ") + awv_last_error());
-    }
-    e = slot.first;
-  }
+  explicit EngineHolder(int device) : lock(*slot_mutex(device, 0)) { e = slot_engine(device, 0, 1); }
 };
 
 void upload(awv_engine* e, const std::vector<Sequence>& seqs) {
@@ -305,18 +330,59 @@ AllPairIterator AllPairIterator::with_options(const std::vector<Sequence>& seque
 
 AllPairIterator& AllPairIterator::with_orientation_params(AlignmentParams p) { orientation_params_ = std::move(p); return *this; }
 AllPairIterator& AllPairIterator::with_orientation(Orientation o) { orientation_ = o; return *this; }
-AllPairIterator& AllPairIterator::with_device(int device) { device_ = device; return *this; }
+AllPairIterator& AllPairIterator::with_device(int device) { devices_.assign(1, device); return *this; }
+AllPairIterator& AllPairIterator::with_devices(std::vector<int> devices) {
+  if (devices.empty()) throw std::invalid_argument("with_devices: the device list is empty");
+  devices_ = std::move(devices);
+  return *this;
+}
+AllPairIterator& AllPairIterator::with_min_batch_pairs(size_t n) { min_batch_pairs_ = std::max<size_t>(1, n); return *this; }
 void set_engine_flags(int flags) { g_engine_flags.store(flags); }
 void set_engine_first_row_cols(int cols) { g_engine_first_row_cols.store(cols); }
 void release_engines() {
   EngineTable& tb = engine_table();
-  std::lock_guard<std::mutex> g(tb.mu);
-  for (auto& kv : tb.engines) {
-    std::lock_guard<std::mutex> busy(*kv.second.second);  // (waits for a run in flight on that device)
-    if (kv.second.first) awv_engine_destroy(kv.second.first);
-    kv.second.first = nullptr;
+  std::vector<std::pair<EngineSlot*, std::mutex*>> slots;
+  {
+    std::lock_guard<std::mutex> g(tb.mu);
+    for (auto& kv : tb.engines) slots.emplace_back(&kv.second, kv.second.mu.get());
   }
+  for (auto& sm : slots) {
+    std::lock_guard<std::mutex> busy(*sm.second);  // (waits for a run in flight on that slot)
+    awv_engine* e;
+    {
+      std::lock_guard<std::mutex> g(tb.mu);
+      e = sm.first->e;
+      sm.first->e = nullptr;
+    }
+    if (e) awv_engine_destroy(e);
+  }
+  std::lock_guard<std::mutex> g(tb.mu);
+  tb.scratch_split.clear();
 }
+int visible_device_count() {
+  // the HIP runtime is found among the objects already loaded (liballwave_hip links it): no path or version of it is assumed
+  std::string path;
+  dl_iterate_phdr([](dl_phdr_info* info, size_t, void* p) -> int {
+    if (info->dlpi_name && strstr(info->dlpi_name, "libamdhip64")) {
+      *(std::string*)p = info->dlpi_name;
+      return 1;
+    }
+    return 0;
+  }, &path);
+  void* h = path.empty() ? nullptr : dlopen(path.c_str(), RTLD_NOW | RTLD_NOLOAD);
+  if (!h) throw AlignmentError("no HIP device available (the HIP runtime is not loaded)");
+  typedef int (*CountFn)(int*);           // hipGetDeviceCount; hipError_t: hipSuccess = 0
+  typedef const char* (*ErrFn)(int);      // hipGetErrorString
+  CountFn count = (CountFn)dlsym(h, "hipGetDeviceCount");
+  ErrFn err_str = (ErrFn)dlsym(h, "hipGetErrorString");
+  int n = 0;
+  const int rc = count ? count(&n) : -1;
+  const std::string why = rc == 0 ? "no device" : (err_str && rc > 0 ? err_str(rc) : "hipGetDeviceCount failed");
+  dlclose(h);
+  if (rc != 0 || n <= 0) throw AlignmentError("no HIP device available (" + why + ")");
+  return n;
+}
+
 AllPairIterator& AllPairIterator::with_shard(size_t rank, size_t world) {
   // cost-balanced shards (planner::assign_shards_lpt): every process derives the same partition and
   // keeps its own part, in list order; equal-cost lists (config 2 / 3) come out strided
@@ -336,7 +402,8 @@ AllPairIterator& AllPairIterator::with_shard(size_t rank, size_t world) {
 AllPairIterator AllPairIterator::with_sparsification(SparsificationStrategy strategy) const {  // iterator.rs:101-110
   AllPairIterator it = with_options(sequences_, params_, exclude_self_, orientation_ == Orientation::Mash, std::move(strategy));
   if (orientation_ == Orientation::ForwardOnly) it.orientation_ = Orientation::ForwardOnly;  // (this build's extension survives)
-  it.device_ = device_;
+  it.devices_ = devices_;
+  it.min_batch_pairs_ = min_batch_pairs_;
   it.threads_ = threads_;
   it.next_chunk_ = next_chunk_;
   return it;
@@ -352,10 +419,11 @@ std::optional<AlignmentResult> AllPairIterator::next() {  // iterator.rs:151-171
     if (next_pos_ >= pairs_.size()) return std::nullopt;
     const size_t first = next_pos_, cnt = std::min(next_chunk_, pairs_.size() - first);
     next_buf_.resize(cnt);
-    run_range(first, cnt, [&](int64_t bf, int64_t bn, const awv_result* res, const uint8_t* arena, const std::vector<uint8_t>& rev) {
-      for (int64_t i = 0; i < bn; ++i) {
-        const auto& pr = pairs_[first + (size_t)(bf + i)];
-        next_buf_[(size_t)(bf + i)] = make_result(pr.first, pr.second, rev[(size_t)(bf + i)] != 0, res[i], arena, true);
+    run_range(first, cnt, [&](const Batch& b) {  // (every entry has its own slot of next_buf_: no lock)
+      for (int64_t i = 0; i < b.n; ++i) {
+        const size_t k = b.pair(i);
+        const auto& pr = pairs_[first + k];
+        next_buf_[k] = make_result(pr.first, pr.second, b.is_rev(i), b.res[i], b.arena, true);
       }
     });
     next_pos_ += cnt;
@@ -364,20 +432,24 @@ std::optional<AlignmentResult> AllPairIterator::next() {  // iterator.rs:151-171
 }
 
 void AllPairParallelIterator::for_each_with_callback(const Callback& cb) {
-  const int want = threads_ > 0 ? threads_ : (it_.threads_ > 0 ? it_.threads_ : planner::host_threads());
-  it_.run([&](int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena, const std::vector<uint8_t>& rev) {
+  // the threads are shared out among the slots, whose batches are consumed at the same time
+  const int want = std::max<int>(1, (threads_ > 0 ? threads_ : (it_.threads_ > 0 ? it_.threads_ : planner::host_threads())) /
+                                        (int)it_.devices_.size());
+  // the first error wins (iterator.rs:236-242); the other workers, on every slot, stop at their next pair
+  std::mutex mu;
+  std::exception_ptr err;
+  std::atomic<bool> stop{false};
+  it_.run([&](const AllPairIterator::Batch& b) {
+    const int64_t cnt = b.n;
     const int T = (int)std::max<int64_t>(1, std::min<int64_t>(want, cnt));
-    std::mutex mu;
-    std::exception_ptr err;  // the first error wins (iterator.rs:236-242); the other workers stop at their next pair
-    std::atomic<bool> stop{false};
     std::atomic<int64_t> cursor{0};
     auto work = [&]() {
       for (;;) {
         const int64_t i = cursor.fetch_add(1);
         if (i >= cnt || stop.load()) return;
-        const auto& pr = it_.pairs_[(size_t)(first + i)];
+        const auto& pr = it_.pairs_[b.pair(i)];
         try {
-          cb(make_result(pr.first, pr.second, rev[(size_t)(first + i)] != 0, res[i], arena, true));
+          cb(make_result(pr.first, pr.second, b.is_rev(i), b.res[i], b.arena, true));
         } catch (...) {
           std::lock_guard<std::mutex> g(mu);
           if (!err) err = std::current_exception();
@@ -390,16 +462,18 @@ void AllPairParallelIterator::for_each_with_callback(const Callback& cb) {
     for (int t = 1; t < T; ++t) th.emplace_back(work);
     work();
     for (auto& x : th) x.join();
+    std::lock_guard<std::mutex> g(mu);
     if (err) std::rethrow_exception(err);
   });
 }
 
 std::vector<AlignmentResult> AllPairParallelIterator::collect() {
   std::vector<AlignmentResult> out(it_.pairs_.size());
-  it_.run([&](int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena, const std::vector<uint8_t>& rev) {
-    for (int64_t i = 0; i < cnt; ++i) {
-      const auto& pr = it_.pairs_[(size_t)(first + i)];
-      out[(size_t)(first + i)] = make_result(pr.first, pr.second, rev[(size_t)(first + i)] != 0, res[i], arena, true);
+  it_.run([&](const AllPairIterator::Batch& b) {  // (every pair has its own slot of `out`: no lock)
+    for (int64_t i = 0; i < b.n; ++i) {
+      const size_t k = b.pair(i);
+      const auto& pr = it_.pairs_[k];
+      out[k] = make_result(pr.first, pr.second, b.is_rev(i), b.res[i], b.arena, true);
     }
   });
   return out;
@@ -411,9 +485,68 @@ void process_alignments_with_callback(const std::vector<Sequence>& sequences, Al
   aligner.for_each_with_callback(callback);
 }
 
-void AllPairIterator::run_range(size_t range_first, size_t range_count,
-                                const std::function<void(int64_t, int64_t, const awv_result*, const uint8_t*,
-                                                         const std::vector<uint8_t>&)>& batch_cb) {
+void process_alignments_with_callback(const std::vector<Sequence>& sequences, AlignmentParams params,
+                                      SparsificationStrategy sparsification, const Callback& callback,
+                                      const std::vector<int>& devices) {
+  AllPairIterator aligner = AllPairIterator::with_options(sequences, std::move(params), true, true, std::move(sparsification));
+  aligner.with_devices(devices);
+  aligner.for_each_with_callback(callback);
+}
+
+namespace {
+// determine_orientation_wfa (alignment.rs:157-175) for the pairs (q, t) of ap[0, n): align forward and reverse-complement
+// with the orientation params, compare #X+#I+#D; forward wins ties; a failed alignment counts as usize::MAX
+void orient_wfa(awv_engine* e, const awv_penalties& open, const awv_pair* ap, int64_t n, uint8_t* is_rev) {
+  std::vector<awv_pair> op((size_t)2 * n);
+  for (int64_t i = 0; i < n; ++i) {
+    op[2 * i] = awv_pair{ap[i].q_idx, ap[i].t_idx, 0};
+    op[2 * i + 1] = awv_pair{ap[i].q_idx, ap[i].t_idx, 1};
+  }
+  std::vector<awv_result> orr((size_t)2 * n);
+  if (awv_align_pairs(e, &open, op.data(), 2 * n, orr.data(), nullptr, nullptr) != AWV_OK)
+    throw AlignmentError(std::string("orientation pass: ") + awv_last_error());
+  for (int64_t i = 0; i < n; ++i) {
+    auto dist = [](const awv_result& r) -> uint64_t {
+      return r.status == AWV_ST_COMPLETED ? (uint64_t)r.num_mismatches + (uint64_t)r.num_ins + (uint64_t)r.num_del : UINT64_MAX;
+    };
+    is_rev[i] = dist(orr[2 * i]) <= dist(orr[2 * i + 1]) ? 0 : 1;
+  }
+}
+
+// counters of several engine calls: summed, except the clock rate (a property of the device) and scratch_bytes (what is
+// allocated now: summed over slots, the last call's within one)
+void add_stats(awv_stats& acc, const awv_stats& x, bool same_engine) {
+  acc.kernel_ms += x.kernel_ms;
+  acc.h2d_ms += x.h2d_ms;
+  acc.d2h_ms += x.d2h_ms;
+  acc.launches += x.launches;
+  acc.cell_steps += x.cell_steps;
+  acc.extend_steps += x.extend_steps;
+  acc.n_breakpoints += x.n_breakpoints;
+  acc.n_base += x.n_base;
+  acc.overlap_scans += x.overlap_scans;
+  acc.aligned_bp += x.aligned_bp;
+  acc.pairs_completed += x.pairs_completed;
+  acc.scratch_bytes = same_engine ? x.scratch_bytes : acc.scratch_bytes + x.scratch_bytes;
+  for (int i = 0; i < 14; ++i) acc.prof[i] += x.prof[i];
+  acc.restarts += x.restarts;
+  acc.multi_cell_steps += x.multi_cell_steps;
+  for (int i = 0; i < 4; ++i) acc.windows[i] += x.windows[i];
+  acc.clock_cycles += x.clock_cycles;
+  acc.clock_ticks += x.clock_ticks;
+  if (!acc.clock_tick_khz) acc.clock_tick_khz = x.clock_tick_khz;
+  acc.deep_cell_steps += x.deep_cell_steps;
+}
+}  // namespace
+
+void AllPairIterator::run_range(size_t range_first, size_t range_count, const BatchCb& batch_cb) {
+  if (devices_.size() > 1) {
+    if (range_first > pairs_.size() || range_count > pairs_.size() - range_first) throw AlignmentError("pair range out of bounds");
+    const std::vector<std::pair<size_t, size_t>> slice(pairs_.begin() + (ptrdiff_t)range_first,
+                                                       pairs_.begin() + (ptrdiff_t)(range_first + range_count));
+    run_slots(slice, batch_cb);
+    return;
+  }
 #ifdef AWV_DEBUG_KNOBS
   const bool timing = getenv("AWH_TIMING") != nullptr;  // diagnostic: stage times on stderr
 #else
@@ -423,7 +556,7 @@ void AllPairIterator::run_range(size_t range_first, size_t range_count,
   auto lap = [&](const char* what) {
     if (timing) fprintf(stderr, "[awh] %-18s %.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count());
   };
-  EngineHolder eh(device_);
+  EngineHolder eh(devices_[0]);
   lap("engine created");
   upload(eh.e, sequences_);
   lap("sequences uploaded");
@@ -440,26 +573,10 @@ void AllPairIterator::run_range(size_t range_first, size_t range_count,
   if (orientation_ == Orientation::Mash) {
     is_rev = planner::orient_pairs_mash(sequences_, plist, host_thr);  // alignment.rs:69-94 (host threads: the CLI's -t)
   } else if (orientation_ == Orientation::Wfa) {
-    // determine_orientation_wfa (alignment.rs:157-175): align forward and reverse-complement with the
-    // orientation params, compare #X+#I+#D; forward wins ties; a failed alignment counts as usize::MAX
-    std::vector<awv_pair> op((size_t)2 * n);
-    for (int64_t i = 0; i < n; ++i) {
-      op[2 * i] = awv_pair{(int32_t)plist[i].first, (int32_t)plist[i].second, 0};
-      op[2 * i + 1] = awv_pair{(int32_t)plist[i].first, (int32_t)plist[i].second, 1};
-    }
-    std::vector<awv_result> orr((size_t)2 * n);
-    const awv_penalties open = to_penalties(orientation_params_);
-    if (awv_align_pairs(eh.e, &open, op.data(), 2 * n, orr.data(), nullptr, nullptr) != AWV_OK)
-      throw AlignmentError(std::string("orientation pass: ") + awv_last_error());
-    for (int64_t i = 0; i < n; ++i) {
-      auto dist = [](const awv_result& r) -> uint64_t {
-        return r.status == AWV_ST_COMPLETED ? (uint64_t)r.num_mismatches + (uint64_t)r.num_ins + (uint64_t)r.num_del : UINT64_MAX;
-      };
-      is_rev[i] = dist(orr[2 * i]) <= dist(orr[2 * i + 1]) ? 0 : 1;
-    }
+    for (int64_t i = 0; i < n; ++i) ap[i] = awv_pair{(int32_t)plist[i].first, (int32_t)plist[i].second, 0};
+    orient_wfa(eh.e, to_penalties(orientation_params_), ap.data(), n, is_rev.data());
   }
   for (int64_t i = 0; i < n; ++i) ap[i] = awv_pair{(int32_t)plist[i].first, (int32_t)plist[i].second, is_rev[i]};
-  using BatchCb = std::function<void(int64_t, int64_t, const awv_result*, const uint8_t*, const std::vector<uint8_t>&)>;
   struct Ctx {
     const BatchCb* cb;
     const std::vector<uint8_t>* rev;
@@ -468,7 +585,7 @@ void AllPairIterator::run_range(size_t range_first, size_t range_count,
   auto sink = [](void* user, int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena) -> int {
     Ctx* c = (Ctx*)user;
     try {
-      (*c->cb)(first, cnt, res, arena, *c->rev);
+      (*c->cb)(Batch{first, cnt, res, arena, c->rev->data(), nullptr});
     } catch (...) {
       c->err = std::current_exception();  // first error wins and aborts (iterator.rs:220-251)
       return 1;
@@ -480,22 +597,164 @@ void AllPairIterator::run_range(size_t range_first, size_t range_count,
   const int rc = awv_align_pairs(eh.e, &pen, ap.data(), n, nullptr, sink, &ctx);
   lap("aligned + sunk");
   awv_engine_stats(eh.e, &stats_);
+  slot_stats_.assign(1, stats_);
   if (ctx.err) std::rethrow_exception(ctx.err);
   if (rc != AWV_OK) throw AlignmentError(std::string("align_pairs: ") + awv_last_error());
 }
 
+// Several slots: planner::device_batches over the predicted costs, one submitter thread per slot.  Every slot creates its
+// engine and uploads the sequences; only when all have done so (a failure there ends the run before any launch) does slot
+// s take batch s, and then the next batch from one cursor each time its previous call returns.  Per batch: WFA orientation
+// on the slot's own engine (mash orientation is computed once for the whole list, up front), then one awv_align_pairs
+// call.  The first error -- an engine's or a batch callback's -- wins: the other slots take no new batch and stop at their
+// next sink call; it is rethrown here once every thread has ended.
+void AllPairIterator::run_slots(const std::vector<std::pair<size_t, size_t>>& plist, const BatchCb& batch_cb) {
+  const size_t S = devices_.size();
+  const int64_t n = (int64_t)plist.size();
+  std::vector<double> cost((size_t)n);
+  for (int64_t i = 0; i < n; ++i)
+    cost[i] = planner::predicted_pair_cost(sequences_[plist[i].first].seq.size(), sequences_[plist[i].second].seq.size(), params_);
+  const std::vector<std::vector<size_t>> batches = planner::device_batches(cost, S, min_batch_pairs_);
+  std::vector<uint8_t> mash_rev;
+  if (orientation_ == Orientation::Mash)
+    mash_rev = planner::orient_pairs_mash(sequences_, plist, threads_ > 0 ? threads_ : planner::host_threads());
+  // slot number of every entry on its device, and how many slots each device has in this run
+  std::map<int, int> per_device;
+  std::vector<int> slot_no(S);
+  for (size_t s = 0; s < S; ++s) slot_no[s] = per_device[devices_[s]]++;
+  // the slots' mutexes, taken here in (device, slot) order: two runs over the same slots cannot deadlock
+  std::vector<std::pair<std::pair<int, int>, size_t>> order;
+  for (size_t s = 0; s < S; ++s) order.push_back({{devices_[s], slot_no[s]}, s});
+  std::sort(order.begin(), order.end());
+  std::vector<std::unique_lock<std::mutex>> locks;
+  for (const auto& o : order) locks.emplace_back(*slot_mutex(o.first.first, o.first.second));
+
+  std::mutex mu;  // guards err and the start barrier
+  std::condition_variable cv;
+  size_t ready = 0;
+  bool aborted = false;  // a submitter thread could not be started: nobody waits for the whole set at the barrier
+  std::exception_ptr err;
+  std::atomic<bool> stop{false};
+  std::atomic<size_t> cursor{S};
+  auto fail = [&](std::exception_ptr e) {
+    std::lock_guard<std::mutex> g(mu);
+    if (!err) err = e;
+    stop.store(true);
+  };
+  const std::function<void(std::exception_ptr)> fail_fn = fail;
+  std::vector<awv_stats> st(S, awv_stats{});
+  const awv_penalties pen = to_penalties(params_), open = to_penalties(orientation_params_);
+  auto worker = [&](size_t s) {
+    awv_engine* e = nullptr;
+    try {
+      e = slot_engine(devices_[s], slot_no[s], per_device.at(devices_[s]));
+      upload(e, sequences_);
+    } catch (...) {
+      fail(std::current_exception());
+    }
+    {
+      std::unique_lock<std::mutex> g(mu);
+      if (++ready == S) cv.notify_all();
+      else cv.wait(g, [&] { return ready == S || aborted; });
+    }
+    if (stop.load()) return;
+    try {
+      for (size_t b = s; b < batches.size() && !stop.load(); b = cursor.fetch_add(1)) {
+        const std::vector<size_t>& idx = batches[b];
+        const int64_t m = (int64_t)idx.size();
+        if (m == 0) continue;
+        std::vector<awv_pair> ap((size_t)m);
+        std::vector<uint8_t> rev((size_t)m, 0);
+        for (int64_t i = 0; i < m; ++i) ap[i] = awv_pair{(int32_t)plist[idx[i]].first, (int32_t)plist[idx[i]].second, 0};
+        if (orientation_ == Orientation::Mash) {
+          for (int64_t i = 0; i < m; ++i) rev[i] = mash_rev[idx[i]];
+        } else if (orientation_ == Orientation::Wfa) {
+          orient_wfa(e, open, ap.data(), m, rev.data());
+        }
+        for (int64_t i = 0; i < m; ++i) ap[i].q_revcomp = rev[i];
+        struct Ctx {
+          const BatchCb* cb;
+          const uint8_t* rev;
+          const size_t* idx;
+          std::atomic<bool>* stop;
+          const std::function<void(std::exception_ptr)>* fail;
+          bool failed;
+        } ctx{&batch_cb, rev.data(), idx.data(), &stop, &fail_fn, false};
+        auto sink = [](void* user, int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena) -> int {
+          Ctx* c = (Ctx*)user;
+          if (c->stop->load()) return 1;  // another slot failed: stop here, report nothing
+          try {
+            (*c->cb)(Batch{first, cnt, res, arena, c->rev, c->idx});
+          } catch (...) {
+            (*c->fail)(std::current_exception());  // recorded now, and every slot stops at its next sink call
+            c->failed = true;
+            return 1;
+          }
+          return 0;
+        };
+        const int rc = awv_align_pairs(e, &pen, ap.data(), m, nullptr, sink, &ctx);
+        awv_stats x{};
+        awv_engine_stats(e, &x);
+        add_stats(st[s], x, true);
+        if (ctx.failed) return;  // (the error is already recorded)
+        if (rc != AWV_OK) {
+          if (rc == AWV_ERR_SINK && stop.load()) return;  // stopped by another slot's error, which is the one reported
+          throw AlignmentError(std::string("align_pairs: ") + awv_last_error());
+        }
+      }
+    } catch (...) {
+      fail(std::current_exception());
+    }
+  };
+  std::vector<std::thread> th;
+  try {
+    for (size_t s = 1; s < S; ++s) th.emplace_back(worker, s);
+  } catch (...) {
+    fail(std::current_exception());
+    std::lock_guard<std::mutex> g(mu);
+    aborted = true;
+    cv.notify_all();
+  }
+  if (th.size() == S - 1) worker(0);
+  for (auto& t : th) t.join();
+  locks.clear();
+  slot_stats_ = st;
+  stats_ = awv_stats{};
+  for (const auto& x : st) add_stats(stats_, x, false);
+  if (err) std::rethrow_exception(err);
+}
+
 void AllPairIterator::for_each_with_callback(const Callback& cb) {
-  run([&](int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena, const std::vector<uint8_t>& rev) {
-    for (int64_t i = 0; i < cnt; ++i) {
-      const auto& pr = pairs_[(size_t)(first + i)];
-      cb(make_result(pr.first, pr.second, rev[(size_t)(first + i)] != 0, res[i], arena, true));
+  // the callback's calls never overlap (several slots deliver batches at once), and none follows its first error: a
+  // batch that gets the lock after it rethrows that same error (so whichever slot reports first, the error is the same)
+  std::mutex mu;
+  std::exception_ptr first;
+  run([&](const Batch& b) {
+    std::lock_guard<std::mutex> g(mu);
+    if (first) std::rethrow_exception(first);
+    try {
+      for (int64_t i = 0; i < b.n; ++i) {
+        const auto& pr = pairs_[b.pair(i)];
+        cb(make_result(pr.first, pr.second, b.is_rev(i), b.res[i], b.arena, true));
+      }
+    } catch (...) {
+      first = std::current_exception();
+      throw;
     }
   });
 }
 
 void AllPairIterator::for_each_paf_batch(const std::function<void(const std::string&)>& sink, int format_threads) {
-  run([&](int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena, const std::vector<uint8_t>& rev) {
-    const int T = (int)std::max<int64_t>(1, std::min<int64_t>(format_threads, cnt / 64 + 1));
+  // sink calls never overlap (several slots deliver batches at once) and none follows its first error; formatting runs
+  // outside the lock, on the format threads shared out among the slots
+  std::mutex mu;
+  std::exception_ptr first;
+  const int per_slot = std::max(1, format_threads / (int)devices_.size());
+  run([&](const Batch& b) {
+    const int64_t cnt = b.n;
+    const awv_result* res = b.res;
+    const uint8_t* arena = b.arena;
+    const int T = (int)std::max<int64_t>(1, std::min<int64_t>(per_slot, cnt / 64 + 1));
     std::vector<std::string> parts((size_t)T);
     std::vector<std::thread> th;
     for (int t = 0; t < T; ++t) {
@@ -504,8 +763,8 @@ void AllPairIterator::for_each_paf_batch(const std::function<void(const std::str
         std::string& out = parts[(size_t)t];
         out.reserve((size_t)(hi - lo) * 4096);
         for (int64_t i = lo; i < hi; ++i) {
-          const auto& pr = pairs_[(size_t)(first + i)];
-          const AlignmentResult a = make_result(pr.first, pr.second, rev[(size_t)(first + i)] != 0, res[i], arena, false);
+          const auto& pr = pairs_[b.pair(i)];
+          const AlignmentResult a = make_result(pr.first, pr.second, b.is_rev(i), res[i], arena, false);
           const bool ok = res[i].status == AWV_ST_COMPLETED;
           append_paf(out, a, ok ? arena + res[i].cigar_off : nullptr, ok ? res[i].cigar_len : 0, sequences_);
           out.push_back('\n');
@@ -516,7 +775,14 @@ void AllPairIterator::for_each_paf_batch(const std::function<void(const std::str
 #ifdef AWV_DEBUG_KNOBS
     if (getenv("AWH_TIMING")) fprintf(stderr, "[awh] formatted %lld pairs on %d threads\n", (long long)cnt, T);
 #endif
-    for (const auto& p : parts) sink(p);
+    std::lock_guard<std::mutex> g(mu);
+    if (first) std::rethrow_exception(first);
+    try {
+      for (const auto& p : parts) sink(p);
+    } catch (...) {
+      first = std::current_exception();
+      throw;
+    }
   });
 }
 

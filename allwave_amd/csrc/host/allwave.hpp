@@ -89,9 +89,12 @@ using Callback = std::function<void(AlignmentResult&&)>;  // may throw: first er
 // (an engine lives for the rest of the process once created).
 void set_engine_flags(int flags);
 void set_engine_first_row_cols(int cols);  // awv_engine_config.first_row_cols, likewise (diagnostic / test hook)
-// destroys the per-device engines this library holds (their HBM arenas are freed; the next run creates fresh ones with the
-// flags then in force)
+// destroys the engines this library holds, one per (device, slot) (their HBM arenas are freed; the next run creates fresh
+// ones with the flags then in force) and forgets the scratch split of devices that ran several slots
 void release_engines();
+// number of HIP devices visible to this process, asked of the HIP runtime liballwave_hip has loaded; throws AlignmentError
+// when there is none
+int visible_device_count();
 
 class AllPairParallelIterator;
 
@@ -115,36 +118,62 @@ class AllPairIterator {  // iterator.rs:12-171
   // process-wide planner::host_threads())
   AllPairIterator& with_threads(int host_threads);
   AllPairIterator& with_orientation(Orientation o);
-  AllPairIterator& with_device(int device);
-  // keep pairs rank, rank + world, ... of the planned list (one process per GPU: every pair lands on
-  // exactly one rank, per-rank cost stays even for a row-major all-pairs list)
+  AllPairIterator& with_device(int device);  // = with_devices({device})
+  // Aligns the pair list on several engines at once, one "slot" per entry: an ordinal may appear more than once, and each
+  // occurrence is an engine of its own (stream, arenas; the slots of one device split its default scratch budget).  With
+  // two or more slots the list is cut into planner::device_batches, handed out from one cursor to one submitter thread per
+  // slot; with one slot every entry point runs exactly as with_device.
+  AllPairIterator& with_devices(std::vector<int> devices);
+  // pairs per batch at the least when several slots share the list (default 16,384: 4 x the engine's pairs in flight)
+  AllPairIterator& with_min_batch_pairs(size_t pairs);
+  const std::vector<int>& devices() const { return devices_; }
+  // keep this process's part of a cost-balanced partition of the planned list into `world` shards
+  // (planner::assign_shards_lpt: every process derives the same partition, each keeps its pairs in list
+  // order; one process per GPU, or per group of GPUs with with_devices)
   AllPairIterator& with_shard(size_t rank, size_t world);
   size_t pair_count() const { return pairs_.size(); }
   const std::vector<std::pair<size_t, size_t>>& get_pairs() const { return pairs_; }
-  // iterator.rs:127-137,206-253: streams results (order unspecified in the reference for T>1;
-  // here batches arrive in pair order)
+  // iterator.rs:127-137,206-253: streams results (order unspecified in the reference for T>1; here
+  // batches arrive in pair order on one slot, in no fixed order on several).  Calls never overlap.
   void for_each_with_callback(const Callback& cb);
   // formats every record with alignment_to_paf on a small thread pool and hands whole batches to
-  // `sink` (replaces the single unbuffered writer thread of src/main.rs:347-367)
+  // `sink` (replaces the single unbuffered writer thread of src/main.rs:347-367); sink calls never overlap
   void for_each_paf_batch(const std::function<void(const std::string&)>& sink, int format_threads = 8);
+  // counters of the last run, summed over its slots (kernel_ms: summed kernel time, not wall time)
   awv_stats last_stats() const { return stats_; }
+  // the same, one entry per slot, in with_devices order
+  const std::vector<awv_stats>& last_slot_stats() const { return slot_stats_; }
 
  private:
   friend class AllPairParallelIterator;
-  void run(const std::function<void(int64_t first, int64_t n, const awv_result* res, const uint8_t* arena,
-                                    const std::vector<uint8_t>& is_rev)>& batch_cb) { run_range(0, pairs_.size(), batch_cb); }
-  // pairs_[first, first + count) through one orientation pass + one awv_align_pairs call; batch indices are relative to `first`
-  void run_range(size_t first, size_t count,
-                 const std::function<void(int64_t first, int64_t n, const awv_result* res, const uint8_t* arena,
-                                          const std::vector<uint8_t>& is_rev)>& batch_cb);
+  // One engine call's results, handed to a run's batch callback: results res[0, n) belong to entries first .. first + n - 1
+  // of the call's pair array, whose pair-list index is pair(i) (relative to the run's range) and orientation is_rev(i).
+  struct Batch {
+    int64_t first, n;
+    const awv_result* res;
+    const uint8_t* arena;
+    const uint8_t* rev;  // per entry of the call's pair array
+    const size_t* idx;   // pair-list index per entry; nullptr: the entry's own position
+    size_t pair(int64_t i) const { return idx ? idx[first + i] : (size_t)(first + i); }
+    bool is_rev(int64_t i) const { return rev[first + i] != 0; }
+  };
+  using BatchCb = std::function<void(const Batch&)>;
+  // With several slots, batch callbacks of different slots run concurrently: consumers that call user code serialise it.
+  void run(const BatchCb& batch_cb) { run_range(0, pairs_.size(), batch_cb); }
+  // pairs_[first, first + count) through one orientation pass + one awv_align_pairs call (one slot), or through
+  // run_slots (several); batch indices are relative to `first`
+  void run_range(size_t first, size_t count, const BatchCb& batch_cb);
+  void run_slots(const std::vector<std::pair<size_t, size_t>>& plist, const BatchCb& batch_cb);
   const std::vector<Sequence>& sequences_;
   AlignmentParams params_, orientation_params_;
   bool exclude_self_ = true;
   Orientation orientation_ = Orientation::Wfa;
-  int device_ = 0;
+  std::vector<int> devices_{0};
+  size_t min_batch_pairs_ = 16384;
   int threads_ = 0;
   std::vector<std::pair<size_t, size_t>> pairs_;
   awv_stats stats_{};
+  std::vector<awv_stats> slot_stats_;
   // sequential iteration (next): position in the pair list and the buffered results of the running chunk
   size_t next_pos_ = 0, next_chunk_ = 16384;
   std::vector<AlignmentResult> next_buf_;
@@ -161,6 +190,8 @@ class AllPairParallelIterator {
   AllPairParallelIterator& with_threads(int threads) { threads_ = threads; return *this; }
   void for_each_with_callback(const Callback& cb);   // iterator.rs:206-253
   std::vector<AlignmentResult> collect();           // rayon's collect() on the parallel iterator: results in pair-list order
+  awv_stats last_stats() const { return it_.last_stats(); }
+  const std::vector<awv_stats>& last_slot_stats() const { return it_.last_slot_stats(); }
  private:
   friend class AllPairIterator;
   explicit AllPairParallelIterator(const AllPairIterator& it) : it_(it) {}
@@ -172,6 +203,10 @@ class AllPairParallelIterator {
 // .for_each_with_callback(callback); the callback may throw (first error aborts and is rethrown)
 void process_alignments_with_callback(const std::vector<Sequence>& sequences, AlignmentParams params,
                                       SparsificationStrategy sparsification, const Callback& callback);
+// the same on the engines `devices` names (AllPairIterator::with_devices; the callback's calls never overlap)
+void process_alignments_with_callback(const std::vector<Sequence>& sequences, AlignmentParams params,
+                                      SparsificationStrategy sparsification, const Callback& callback,
+                                      const std::vector<int>& devices);
 
 namespace wfa {  // src/wfa.rs
 struct Penalties { int32_t mismatch, gap_opening1, gap_extension1, gap_opening2, gap_extension2; };

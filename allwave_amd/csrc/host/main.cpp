@@ -2,7 +2,8 @@
 // the MI355X engine.  FASTA in (plain, or .gz/BGZF through zlib), PAF out.  SURVEY.md 8f-1.
 //   -i/--input  -o/--output  -s/--scores  -x/--preset  -t/--threads  -p/--sparsification
 //   --no-progress  --mash-matrix  --wfa-orientation  -k/--keep-prefixes  -e/--exclude-prefixes
-// Extensions: --device N (GPU ordinal), --forward-only (skip orientation: all '+').
+// Extensions: --device N (GPU ordinal), --devices LIST (several GPUs, or engines, in this one process),
+// --shard R/N (this process's part of the pair list), --forward-only (skip orientation: all '+').
 // -t sets the host threads used for PAF formatting / sketching (alignment itself runs on the GPU).
 #include <zlib.h>
 
@@ -26,6 +27,9 @@ struct Args {
   bool have_output = false, have_scores = false, have_preset = false, no_progress = false, mash_matrix = false;
   bool wfa_orientation = false, forward_only = false, have_keep = false, have_exclude = false;
   int threads = 1, device = 0;
+  bool have_device = false;
+  std::string devices;  // --devices LIST (empty: --device)
+  bool have_devices = false;
   long shard_rank = 0, shard_world = 1;  // --shard R/N: this process aligns pairs R, R+N, ... (one process per GPU)
 };
 
@@ -107,6 +111,50 @@ std::vector<std::string> split_trim(const std::string& s) {
   return out;
 }
 
+// --devices LIST: comma-separated ordinals and ranges A-B (A <= B), e.g. 0,1,2 / 0-7 / 0,0; `all` = every visible device.
+// Returns false with a message on a malformed list (before any device is opened).
+bool parse_devices(const std::string& list, std::vector<int>& out, std::string& msg) {
+  out.clear();
+  if (list == "all") {
+    try {
+      const int n = std::min(256, visible_device_count());
+      for (int d = 0; d < n; ++d) out.push_back(d);
+    } catch (const std::exception& e) {
+      msg = std::string("--devices all: ") + e.what();
+      return false;
+    }
+    return true;
+  }
+  auto ordinal = [](const std::string& t, int& v) {
+    if (t.empty() || t.size() > 6 || t.find_first_not_of("0123456789") != std::string::npos) return false;
+    v = atoi(t.c_str());
+    return true;
+  };
+  for (const std::string& tok : split_trim(list)) {
+    const size_t dash = tok.find('-');
+    int a = 0, b = 0;
+    if (dash == std::string::npos ? !ordinal(tok, a) : !(ordinal(tok.substr(0, dash), a) && ordinal(tok.substr(dash + 1), b))) {
+      msg = "--devices: '" + tok + "' is not a device ordinal or range A-B (LIST: e.g. 0,1,2 or 0-7 or 0,0 or all)";
+      return false;
+    }
+    if (dash == std::string::npos) b = a;
+    if (a > b) {
+      msg = "--devices: empty range '" + tok + "' (A-B needs A <= B)";
+      return false;
+    }
+    if (b - a >= 256 || out.size() + (size_t)(b - a) >= 256) {  // (one engine and one submitter thread per entry)
+      msg = "--devices: more than 256 entries";
+      return false;
+    }
+    for (int d = a; d <= b; ++d) out.push_back(d);
+  }
+  if (out.empty()) {
+    msg = "--devices: the device list is empty (LIST: e.g. 0,1,2 or 0-7 or 0,0 or all)";
+    return false;
+  }
+  return true;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -129,7 +177,8 @@ int main(int argc, char** argv) {
     else if (k == "--forward-only") a.forward_only = true;
     else if (k == "-k" || k == "--keep-prefixes") { a.keep = val(); a.have_keep = true; }
     else if (k == "-e" || k == "--exclude-prefixes") { a.exclude = val(); a.have_exclude = true; }
-    else if (k == "--device") a.device = atoi(val().c_str());
+    else if (k == "--device") { a.device = atoi(val().c_str()); a.have_device = true; }
+    else if (k == "--devices") { a.devices = val(); a.have_devices = true; }
     else if (k == "--shard") {
       const std::string v = val();
       char* end = nullptr;
@@ -141,13 +190,22 @@ int main(int argc, char** argv) {
     }
     else if (k == "-h" || k == "--help") {
       std::cout << "usage: allwave_hip -i in.fa [-o out.paf] [-s m,x,o,e[,o2,e2] | -x ANI] [-p none|auto|random:f|giant:p|tree:n:f:r[:k]]\n"
-                   "                   [-t threads] [--wfa-orientation|--forward-only] [-k prefixes | -e prefixes] [--mash-matrix] [--device N] [--shard R/N]\n";
+                   "                   [-t threads] [--wfa-orientation|--forward-only] [-k prefixes | -e prefixes] [--mash-matrix]\n"
+                   "                   [--device N | --devices LIST] [--shard R/N]\n"
+                   "  --devices LIST   align on several devices in this process: ordinals and ranges, e.g. 0,1,2 / 0-7 / all;\n"
+                   "                   an ordinal may repeat (0,0: two engines on device 0); -t is shared out among them\n";
       return 0;
     } else die("unexpected argument: " + k);
   }
   if (a.input.empty()) die("the following required arguments were not provided: --input <INPUT>");
   if (a.have_scores && a.have_preset) die("the argument '--scores' cannot be used with '--preset'");
   if (a.have_keep && a.have_exclude) die("the argument '--keep-prefixes' cannot be used with '--exclude-prefixes'");
+  if (a.have_device && a.have_devices) die("the argument '--device' cannot be used with '--devices'", 1);
+  std::vector<int> devices(1, a.device);
+  if (a.have_devices) {
+    std::string msg;
+    if (!parse_devices(a.devices, devices, msg)) die(msg, 1);
+  }
 
   SparsificationStrategy strategy;
   try { strategy = SparsificationStrategy::parse(a.sparsification); } catch (const std::exception& e) { die(e.what(), 1); }
@@ -189,7 +247,7 @@ int main(int argc, char** argv) {
   try {
     AllPairIterator it = AllPairIterator::with_options(sequences, params, true, !a.wfa_orientation, strategy);
     if (a.forward_only) it.with_orientation(Orientation::ForwardOnly);
-    it.with_device(a.device);
+    it.with_devices(devices);
     it.with_shard((size_t)a.shard_rank, (size_t)a.shard_world);
     const size_t total = it.pair_count();
     // a short-lived process with little work: taking the ring arena as it comes beats choosing the

@@ -266,5 +266,14 @@ std::vector<uint32_t> assign_shards_lpt(const std::vector<double>& cost, size_t 
   return shard;
 }
 
+std::vector<std::vector<size_t>> device_batches(const std::vector<double>& cost, size_t slots, size_t min_batch_pairs) {
+  const size_t n = cost.size(), m = std::max<size_t>(1, min_batch_pairs);
+  const size_t nb = std::max<size_t>(1, std::min(4 * std::max<size_t>(1, slots), (n + m - 1) / m));
+  const std::vector<uint32_t> batch = assign_shards_lpt(cost, nb);
+  std::vector<std::vector<size_t>> out(nb);
+  for (size_t i = 0; i < n; ++i) out[batch[i]].push_back(i);
+  return out;
+}
+
 }  // namespace planner
 }  // namespace allwave

@@ -57,6 +57,12 @@ double predicted_pair_cost(size_t qlen, size_t tlen, const AlignmentParams& para
 // shard of every pair; deterministic, so every process derives the same partition.  A list whose
 // pairs all cost the same degenerates to the strided shard r, r + world, ...
 std::vector<uint32_t> assign_shards_lpt(const std::vector<double>& cost, size_t world);
+// Batches of one in-process multi-device run (AllPairIterator::with_devices): B = min(4 * slots,
+// ceil(n / min_batch_pairs)) batches, at least 1, cut by assign_shards_lpt(cost, B) so that every batch
+// mixes large and small pairs; each batch lists its pair indices in list order.  Deterministic.  At run
+// time the batches are handed out in index order, each slot taking the next one when its previous call
+// returns, so the final balance follows measured speed rather than the prediction alone.
+std::vector<std::vector<size_t>> device_batches(const std::vector<double>& cost, size_t slots, size_t min_batch_pairs);
 
 }  // namespace planner
 }  // namespace allwave
