@@ -27,10 +27,15 @@ over per cell-step; the kernel's duration is measured live (HIP events on the en
 algorithmic bytes (12 row elements per cell-step for 2-piece = 24 B with 16-bit rows / 48 B with 32-bit rows,
 7 elements for 1-piece, + CIGAR bytes) are reported beside it (`algorithmic_GBps`,
 `traffic_over_algorithmic`): since round 2 the kernel keeps rows in registers and moves fewer bytes than that.
-`cpu_baseline` is the CPU restatement (oracle/, kind "port") on a bounded sample of the same pairs on this
-box's host cores, at all cores and at one.
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line: `value`,
+`ms_per_step`, the launch counters and `roofline` (computed from this run's counters and the committed profile).
+`--full` adds the figures that take runs of their own after the timed region (N = 1 only): `paf_end_to_end`,
+`paf_end_to_end_mash` and `paf_lines_per_s` (the whole boundary end to end, through the C++ host mirror), and
+`cpu_baseline` / `cpu_baseline_t1` -- the CPU restatement (oracle/, kind "port") on a bounded sample of the same
+pairs on this box's host cores, at all cores and at one -- with `parity`, the GPU's results on that sample checked
+against it.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c1|c4|c5] [--pairs P]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c1|c4|c5] [--pairs P] [--full]
 
 `--steps K` timed steps (K >= 1) after W untimed ones; `ms_per_step` = the timed region / K.  `--dump-outputs DIR` writes
 what the last timed step returned (awv_align_pairs' per-pair results, float64, at most 64 MB) as DIR/<field>.npy; the
@@ -129,9 +134,12 @@ def main():
     ap.add_argument("--pairs", type=int, default=0,
                     help="length of the pair-list prefix (whole job, before sharding); default: all of c1/c2, N x 65,280 of c3")
     ap.add_argument("--workgroups", type=int, default=0)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample duration (all cores)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-paf", action="store_true", help="skip the end-to-end PAF formatting figures")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the end-to-end PAF figures and the CPU baseline with its parity check "
+                         "(one GPU only; off by default: a plain run does only what `value` needs)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: target CPU-baseline sample duration (all cores)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity check")
+    ap.add_argument("--no-paf", action="store_true", help="with --full: skip the end-to-end PAF formatting figures")
     ap.add_argument("--launch-check", action="store_true",
                     help="plumbing check without a GPU: ranks rendezvous over gloo, shard the job, reduce counters and print the line's launch fields")
     ap.add_argument("--rehearse-one-gpu", action="store_true",
@@ -350,7 +358,7 @@ def main():
     if dumped:
         out["dumped_outputs"] = {"dir": args.dump_outputs, "pairs": dumped[0], "of": dumped[1], "fields": list(DUMP_FIELDS)}
 
-    if world == 1 and not args.no_paf:
+    if world == 1 and args.full and not args.no_paf:
         # secondary figures (never `value`): the whole boundary end to end -- sequences on the host ->
         # upload -> [orientation] -> align -> CIGARs over PCIe -> alignment_to_paf text (C++ host mirror)
         # into a counting sink, repeated --steps times.  "forward": no orientation pass (what `value`
@@ -380,7 +388,7 @@ def main():
         out["paf_lines_per_s"] = out["paf_end_to_end_mash"]["lines_per_s"]
         out["paf_lines_per_s_what"] = "paf_end_to_end_mash.lines_per_s (end to end incl. PCIe and host formatting; not part of `value`)"
 
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import oracle as O  # the reported CPU baseline (kind "port"), never the product
         cores = usable_cores()
         probe = pairs[:min(len(pairs), 4 * cores)]

@@ -12,5 +12,5 @@ timeout -k 10 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv 
 echo "pmc FETCH_SIZE done"
 timeout -k 10 200 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/cal_write -- $R/scratch/bin/fetchcal > $O/cal_write.log 2>&1 || { tail -5 $O/cal_write.log; exit 1; }
 echo "pmc WRITE_SIZE done"
-cd $R && timeout -k 10 400 python bench.py --no-cpu-baseline > $O/bench_r02_base.json 2> $O/bench_r02_base.err || { tail -5 $O/bench_r02_base.err; exit 1; }
+cd $R && timeout -k 10 400 python bench.py --full --no-cpu-baseline > $O/bench_r02_base.json 2> $O/bench_r02_base.err || { tail -5 $O/bench_r02_base.err; exit 1; }
 cut -c1-600 $O/bench_r02_base.json

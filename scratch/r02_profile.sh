@@ -4,7 +4,7 @@
 # Summarise afterwards (here): python scratch/summarize_pmc.py <tag> r02
 set -o pipefail
 R=$GRAFT_REPO_ROOT; T=${1:-v}; O=$R/gpurun_out
-cd $R && timeout -k 10 600 python bench.py > $O/bench_$T.json 2> $O/bench_$T.err || { tail -5 $O/bench_$T.err; exit 1; }
+cd $R && timeout -k 10 600 python bench.py --full > $O/bench_$T.json 2> $O/bench_$T.err || { tail -5 $O/bench_$T.err; exit 1; }
 cd /tmp; export TMPDIR=/tmp
 CMD="python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-paf"
 rm -rf $O/prof_$T
