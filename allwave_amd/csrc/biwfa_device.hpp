@@ -99,7 +99,7 @@ constexpr int STATIC_LDS_RESERVE = 1024;
 constexpr int COL_PAD = 576;  // columns of slack either side of a row: whole-wave vector loads stay inside it
 
 // per-pair status (allwave_hip.h AWV_ST_*)
-constexpr int ST_OK = 0, ST_CAPACITY = 1, ST_INTERNAL = 2, ST_MAX_STEPS = 3;
+constexpr int ST_OK = 0, ST_CAPACITY = 1, ST_INTERNAL = 2, ST_MAX_STEPS = 3, ST_ABOVE_BOUND = 4;
 
 struct DevPenalties {
   int x, o1, e1, o2, e2, two_piece, scope;  // scope = max(x, o1+e1, o2+e2) + 1  (A.3)
@@ -172,6 +172,11 @@ struct KParams {
   DevResult* results;
   unsigned long long* work_counter;
   unsigned long long* stats;
+  // score-only launches (awv_score_pairs): the top-level search's breakpoint score is the pair's penalty -- no sub-problems,
+  // no CIGAR (cigar / cigar_off are not read).  max_penalty: INT_MAX = no bound; else a pair whose penalty is proved above it
+  // ends ST_ABOVE_BOUND with penalty max_penalty + 1
+  int score_only;
+  int max_penalty;
 };
 
 struct RowMeta { int lo, hi; };
@@ -252,6 +257,9 @@ struct PassCtx {
   unsigned long long Pw, Tw;
   int multi_T, lds_seq_bytes, pb_abs, tb_abs;
   int deep_passes;
+  // score-only bound (KParams::max_penalty; INT_MAX = none) and the score from which the far-apart passes plan no further pass:
+  // with both directions there, every breakpoint still to be found costs more than the bound (find_breakpoint)
+  int max_penalty, score_cap;
 };
 struct PhaseResult {
   int why, sc, fmax, rmax, npass;
@@ -2143,7 +2151,7 @@ __device__ __forceinline__ int compute_rows_multi(const KParams& kp, Shared& sh,
 // Inputs beyond the few scalars come from LDS (Shared::pctx), results go back through Shared::pres.
 typedef __attribute__((address_space(3))) Shared* lds_shared_ptr;
 typedef __attribute__((address_space(3))) unsigned char* lds_bytes_ptr;
-constexpr int MP_MARGIN = 0, MP_DISCARD = 1, MP_MET = 2, MP_ERROR = 3, MP_DEEP_MET = 4;
+constexpr int MP_MARGIN = 0, MP_DISCARD = 1, MP_MET = 2, MP_ERROR = 3, MP_DEEP_MET = 4, MP_BOUND = 5;
 template <bool P2, typename OffT, int E1, int E2>
 __device__ __attribute__((noinline)) void deep_phase(unsigned sh_addr, unsigned dyn_addr, int s0_v, int fmax_v, int rmax_v, int Tn_v, int pass_v,
                                                      int far_npass_v, unsigned far_cells_lo, unsigned far_cells_hi);
@@ -2222,6 +2230,7 @@ __device__ __attribute__((noinline)) void multi_phase(unsigned sh_addr, unsigned
   const bool long_reads = (uni(deep_v) & 0x400) != 0;  // a 16-bit search of a launch with 32-bit rows: those reads' margin factor
   const int chain_cap = CHAIN ? min(max(uni(pc.chain_max), 1), sizeof(OffT) == 2 ? CHAIN_MAX : (lds_chain ? 3 : CHAIN_MAX32)) : 1;
   for (;;) {
+    if (sc >= uni(pc.score_cap)) { why = MP_BOUND; break; }  // (score-only bound: no pass from this score on, no deep_phase)
     // Start keeping every I/D row well before the furthest points can meet: the margin is several times what
     // the two searches advance while `scope` more rows (and one more pass) are computed.  The longest chain
     // whose own length still fits in front of that margin is taken.
@@ -2370,6 +2379,7 @@ __device__ __attribute__((noinline)) void deep_phase(unsigned sh_addr, unsigned 
   unsigned long long cells = 0;
   unsigned ext_iters = 0;
   for (;;) {
+    if (sc >= uni(pc.score_cap)) { why = MP_BOUND; break; }  // (score-only bound; sf = sr = sc here: no pass has met)
     const int aslot = pass % 3;
     int nc0 = 0, nc1 = 0;
 #pragma nounroll
@@ -2663,8 +2673,10 @@ struct Emit {
   int cnt[4];  // M X I D
 };
 __device__ __forceinline__ void emit_run(Emit& em, uint8_t op, int len) {
-  uint8_t* p = em.cig + em.n;
-  for (int i = cold_tid(); i < len; i += WG) p[i] = op;
+  if (em.cig != nullptr) {  // (score-only launches have no CIGAR arena: the counts alone)
+    uint8_t* p = em.cig + em.n;
+    for (int i = cold_tid(); i < len; i += WG) p[i] = op;
+  }
   em.n += len;
   em.cnt[0] += op == 'M' ? len : 0;
   em.cnt[1] += op == 'X' ? len : 0;
@@ -2919,7 +2931,7 @@ __device__ __forceinline__ int base_align(const KParams& kp, Shared& sh, const L
 // ---------------------------------------------------------------------------------------------
 // BiWFA breakpoint search (A.6)
 // ---------------------------------------------------------------------------------------------
-constexpr int BP_OK = 0, BP_END_REACHED = 100, BP_RESTART = 101;
+constexpr int BP_OK = 0, BP_END_REACHED = 100, BP_RESTART = 101, BP_ABOVE_BOUND = 102;
 
 template <bool P2, typename OffT>
 __device__ __forceinline__ void bialign_overlap(const KParams& kp, Shared& sh, const Lds<OffT>& lds, const SubCtx& cx, void* ring_mem, rsrc_t ring_rs, int d0, int s0,
@@ -3178,6 +3190,10 @@ __device__ __forceinline__ int find_breakpoint(const KParams& kp, Shared& sh, co
     pc.kmin[0] = cx.kmin[0]; pc.kmin[1] = cx.kmin[1];
     pc.wcols = cx.wcols;
     pc.seq_mode = cx.seq_mode; pc.p_w0 = cx.p_w0; pc.t_w0 = cx.t_w0; pc.p_bit = cx.p_bit; pc.t_bit = cx.t_bit;
+    // both directions at score s: every breakpoint still to be found costs at least 2 s - (scope - 1) - gap_opening (the
+    // inequality of the bound, below), so from the first s at which that exceeds the bound phase 1 plans no further pass
+    const long long gap_open_max = P2 ? max(pn.o1, pn.o2) : pn.o1;
+    pc.score_cap = kp.max_penalty == INT_MAX ? INT_MAX : (int)min((long long)INT_MAX, ((long long)kp.max_penalty + pn.scope - 1 + gap_open_max) / 2 + 1);
     sh.ext_multi = 0;
   }
   // score-0 wavefronts (wavefront_unialign_init by begin component)
@@ -3220,6 +3236,13 @@ __device__ __forceinline__ int find_breakpoint(const KParams& kp, Shared& sh, co
   const long long max_steps = ((long long)pn.o1 + pn.o2 + 2LL * (pn.e1 + pn.e2) + pn.x) * ((long long)plen + tlen + 4) + 1024;
   long long steps = 0;
   int rc = BP_OK;
+  // Score-only bound B (kp.max_penalty, INT_MAX = none).  Every breakpoint the search can still find pairs a score >= sc[0] of
+  // one side with one >= sc[1] - (scope - 1) of the other, minus at most one gap open -- the inequality phase 2's termination
+  // tests rely on.  So the search starts as if a breakpoint of score B + 1 were known: phase 2 then accepts only breakpoints
+  // <= B and ends as soon as none can remain, and phase 1 (which finds none) ends once both sides stand at pctx.score_cap.
+  // A breakpoint <= B, once found, lets the search run to its normal end (exact).  (Bound values are read back from LDS
+  // where they are needed: nothing extra stays live in the step loop.)
+  if (kp.max_penalty != INT_MAX) bp.score = kp.max_penalty + 1;
   const int gap_opening = P2 ? max(pn.o1, pn.o2) : pn.o1;
   bool last_fwd = false;
   // A sub-problem handed down by a parent's breakpoint has a known optimal score: its share of the
@@ -3357,6 +3380,7 @@ __device__ __forceinline__ int find_breakpoint(const KParams& kp, Shared& sh, co
       ++sc[1];
       rmax = max(rmax, uni(lds.bi_A[1 * kp.ring + (sc[1] & rmask)]));
       last_fwd = false;
+      if (sc[1] >= uni(sh.pctx.score_cap)) { rc = BP_ABOVE_BOUND; break; }  // (sc[0] == sc[1]: every breakpoint left is above the bound)
     } else {
       // phase 2: until no better overlap is possible
       if (last_fwd) {
@@ -3392,6 +3416,7 @@ __device__ __forceinline__ int find_breakpoint(const KParams& kp, Shared& sh, co
   }
   atomicAdd(&lstats[STAT_EXTEND], (unsigned long long)ext_iters);
   if (!DIRSPLIT && tid == 0) lstats[STAT_EXTEND] += sh.ext_multi;
+  if (rc == BP_OK && bp.score > uni(sh.pctx.max_penalty)) rc = BP_ABOVE_BOUND;  // (the bound's phase 2 found no breakpoint <= B)
   __syncthreads();  // LDS metadata is rewritten by the next sub-problem
   if (rc == BP_OK && bp.score == INT_MAX) rc = ST_INTERNAL;
   return rc;
@@ -3427,6 +3452,7 @@ __device__ __attribute__((noinline)) int find_breakpoint_fn(unsigned sh_addr, un
   kp.chain_max = uni(pc.chain_max);
   kp.multi_T = uni(pc.multi_T);
   kp.deep_passes = uni(pc.deep_passes);
+  kp.max_penalty = uni(pc.max_penalty);
   kp.ring_slot_stride = (size_t)uni64(pc.ring_bytes);
   SubCtx cx;
   cx.plen = uni(pc.plen);
@@ -3521,7 +3547,7 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
     }
     const unsigned long long tt0 = PROF_NOW();
     Emit em;
-    em.cig = kp.cigar + kp.cigar_off[pair];
+    em.cig = kp.score_only ? nullptr : kp.cigar + kp.cigar_off[pair];
     em.n = 0;
     em.cnt[0] = em.cnt[1] = em.cnt[2] = em.cnt[3] = 0;
     int status = ST_OK;
@@ -3590,6 +3616,7 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
             pc.chain_max = kp.chain_max;
             pc.multi_T = kp.multi_T;
             pc.deep_passes = kp.deep_passes;
+            pc.max_penalty = kp.max_penalty;
             pc.plen = plen; pc.tlen = tlen;
             pc.seq_mode = cx.seq_mode; pc.p_w0 = cx.p_w0; pc.t_w0 = cx.t_w0; pc.p_bit = cx.p_bit; pc.t_bit = cx.t_bit;
             pc.pb_abs = cx.pb_abs; pc.tb_abs = cx.tb_abs;
@@ -3617,6 +3644,7 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
           if (tid == 0) lstats[STAT_RESTARTS] += 1;
         }
         if (rc == BP_END_REACHED) do_base = true;  // wavefront_bialign_exception -> plain WFA
+        else if (rc == BP_ABOVE_BOUND) { status = ST_ABOVE_BOUND; break; }
         else if (rc != BP_OK) { status = rc; break; }
       }
       if (do_base) {
@@ -3626,6 +3654,10 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
         if (top) penalty = pen_b;
         top = false;
         continue;
+      }
+      if (kp.score_only) {  // the top level's breakpoint score is the penalty: no sub-problems, no CIGAR
+        penalty = bp.score;
+        break;
       }
       const int bh = bp.off_f, bv = bp.off_f - bp.kf;
       if (bh < 0 || bh > tlen || bv < 0 || bv > plen || sp + 2 > STACK_CAP) { status = ST_INTERNAL; break; }
@@ -3639,13 +3671,15 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
       top = false;
       __syncthreads();
     }
+    // (score-only: the closed-form and base-case penalties are exact too; any penalty above the bound reports as such)
+    if (status == ST_OK && penalty > kp.max_penalty) status = ST_ABOVE_BOUND;
     if (tid == 0) {
       DevResult r;
       r.status = status;
-      r.penalty = status == ST_OK ? penalty : 0;
+      r.penalty = status == ST_OK ? penalty : status == ST_ABOVE_BOUND ? kp.max_penalty + 1 : 0;
       r.score = -r.penalty;
-      r.cigar_len = status == ST_OK ? (uint32_t)em.n : 0u;
-      r.cigar_off = kp.cigar_off[pair];
+      r.cigar_len = status == ST_OK && !kp.score_only ? (uint32_t)em.n : 0u;
+      r.cigar_off = kp.score_only ? 0 : kp.cigar_off[pair];
       r.num_matches = em.cnt[0];
       r.num_mismatches = em.cnt[1];
       r.num_ins = em.cnt[2];

@@ -44,6 +44,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -309,8 +310,10 @@ long long worst_case_penalty(const awv::DevPenalties& d, long long n) {
   return std::min(2 * gap(n), n * (long long)d.x + gap(n));
 }
 
+// score_only: awv_score_pairs -- the top-level search's score only, no CIGAR arena (so max_arena_bytes does not cut batches);
+// max_penalty: that call's bound (INT_MAX = none)
 int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
-               awv_result* out, awv_sink sink, void* user) {
+               awv_result* out, awv_sink sink, void* user, bool score_only = false, int max_penalty = INT_MAX) {
   using namespace awv;
   if (npairs < 0 || (npairs > 0 && !pairs)) return fail(AWV_ERR_ARG, "align_pairs: null pairs");
   DevPenalties dp{};
@@ -404,7 +407,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
     while (first + n < npairs && n < max_batch) {
       const awv_pair& p = pairs[first + n];
       const int ql = s.len[p.q_idx], tl = s.len[p.t_idx];
-      const uint64_t need = ((uint64_t)ql + (uint64_t)tl + 7) & ~(uint64_t)7;
+      const uint64_t need = score_only ? 0 : ((uint64_t)ql + (uint64_t)tl + 7) & ~(uint64_t)7;
       if (n > 0 && arena + need > max_arena) break;
       hq.push_back(p.q_idx);
       ht.push_back(p.t_idx);
@@ -652,6 +655,8 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       kp.results = e->d_results.p;
       kp.work_counter = e->d_counters.p;
       kp.stats = e->d_counters.p + 1;
+      kp.score_only = score_only ? 1 : 0;
+      kp.max_penalty = score_only ? max_penalty : INT_MAX;
       HIP_TRY(hipEventRecord(e->ev0, e->stream));
       auto launch = [&](auto kern, const auto& kparams) -> int {
         HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
@@ -690,7 +695,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipEventRecord(e->ev1, e->stream));
       // while the kernel runs: get the host CIGAR buffer's pages in place (0.2 s for config 2's 670 MB)
-      if (sink && !(e->cfg.flags & AWV_F_KEEP_ON_DEVICE) && e->h_cigar.size() < (size_t)arena + 64) e->h_cigar.resize((size_t)arena + 64);
+      if (sink && !score_only && !(e->cfg.flags & AWV_F_KEEP_ON_DEVICE) && e->h_cigar.size() < (size_t)arena + 64) e->h_cigar.resize((size_t)arena + 64);
       HIP_TRY(hipEventSynchronize(e->ev1));
       HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
       kernel_ms += ms;
@@ -818,7 +823,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       for (int g = NG - 1; g >= 0; --g)
         if (int rcg = run_group(std::move(q[g]), std::move(t[g]), std::move(rc[g]), std::move(off[g]), std::move(map[g]), waves_of[g / 3], g % 3, gsum[g], glen[g], false)) return rcg;
     }
-    const bool want_cigar = sink && !(e->cfg.flags & AWV_F_KEEP_ON_DEVICE);
+    const bool want_cigar = sink && !score_only && !(e->cfg.flags & AWV_F_KEEP_ON_DEVICE);
     lap("results on host");
     if (want_cigar) {
       e->h_cigar.resize((size_t)arena + 64);
@@ -971,6 +976,30 @@ int awv_align_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pai
   if (!e) return fail(AWV_ERR_ARG, "null engine");
   if (e->seqs.n == 0 && npairs > 0) return fail(AWV_ERR_STATE, "align_pairs before set_sequences");
   AWV_GUARDED(return align_core(e, e->seqs, pen, pairs, npairs, out, sink, user);)
+}
+
+int awv_score_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, int32_t max_penalty,
+                    awv_score_result* out) {
+  if (!e) {  // (without a GPU there is no engine to pass: say so, as awv_engine_create does)
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(AWV_ERR_NO_DEVICE, "no HIP device available: liballwave_hip has no CPU fallback");
+    return fail(AWV_ERR_ARG, "null engine");
+  }
+  if (!out) return fail(AWV_ERR_ARG, "score_pairs: null out");
+  if (npairs < 0) return fail(AWV_ERR_ARG, "score_pairs: npairs < 0");
+  if (e->seqs.n == 0 && npairs > 0) return fail(AWV_ERR_STATE, "score_pairs before set_sequences");
+  // (a bound of 2^30 or more cannot be met by any pair the engine accepts: it is no bound)
+  const int bound = max_penalty < 0 || max_penalty >= (1 << 30) ? INT_MAX : max_penalty;
+  AWV_GUARDED(
+    std::vector<awv_result> res((size_t)npairs);
+    const int rc = align_core(e, e->seqs, pen, pairs, npairs, res.data(), nullptr, nullptr, true, bound);
+    if (rc != AWV_OK) return rc;
+    for (int64_t i = 0; i < npairs; ++i) {
+      out[i].status = res[(size_t)i].status;
+      out[i].penalty = res[(size_t)i].penalty;
+    }
+    return AWV_OK;
+  )
 }
 
 namespace {

@@ -539,6 +539,20 @@ void add_stats(awv_stats& acc, const awv_stats& x, bool same_engine) {
 }
 }  // namespace
 
+int AllPairIterator::engine_call(awv_engine* e, const awv_penalties& pen, const awv_pair* ap, int64_t n, awv_sink sink, void* user) const {
+  if (!score_only_) return awv_align_pairs(e, &pen, ap, n, nullptr, sink, user);
+  std::vector<awv_score_result> sr((size_t)n);
+  const int rc = awv_score_pairs(e, &pen, ap, n, max_penalty_, sr.data());
+  if (rc != AWV_OK || n == 0) return rc;
+  std::vector<awv_result> res((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    res[(size_t)i].status = sr[(size_t)i].status;
+    res[(size_t)i].penalty = sr[(size_t)i].penalty;
+    res[(size_t)i].score = -sr[(size_t)i].penalty;
+  }
+  return sink(user, 0, n, res.data(), nullptr) == 0 ? AWV_OK : AWV_ERR_SINK;
+}
+
 void AllPairIterator::run_range(size_t range_first, size_t range_count, const BatchCb& batch_cb) {
   if (devices_.size() > 1) {
     if (range_first > pairs_.size() || range_count > pairs_.size() - range_first) throw AlignmentError("pair range out of bounds");
@@ -594,7 +608,7 @@ void AllPairIterator::run_range(size_t range_first, size_t range_count, const Ba
   };
   const awv_penalties pen = to_penalties(params_);
   lap("pairs oriented");
-  const int rc = awv_align_pairs(eh.e, &pen, ap.data(), n, nullptr, sink, &ctx);
+  const int rc = engine_call(eh.e, pen, ap.data(), n, sink, &ctx);
   lap("aligned + sunk");
   awv_engine_stats(eh.e, &stats_);
   slot_stats_.assign(1, stats_);
@@ -692,7 +706,7 @@ void AllPairIterator::run_slots(const std::vector<std::pair<size_t, size_t>>& pl
           }
           return 0;
         };
-        const int rc = awv_align_pairs(e, &pen, ap.data(), m, nullptr, sink, &ctx);
+        const int rc = engine_call(e, pen, ap.data(), m, sink, &ctx);
         awv_stats x{};
         awv_engine_stats(e, &x);
         add_stats(st[s], x, true);
@@ -784,6 +798,29 @@ void AllPairIterator::for_each_paf_batch(const std::function<void(const std::str
       throw;
     }
   });
+}
+
+std::vector<PairScore> AllPairIterator::scores(std::optional<int> max_penalty) {
+  if (max_penalty && *max_penalty < 0) throw std::invalid_argument("scores: max_penalty must be >= 0");
+  std::vector<PairScore> out(pairs_.size());
+  struct Mode {  // the iterator is back in alignment mode however this call ends
+    AllPairIterator* it;
+    ~Mode() { it->score_only_ = false; it->max_penalty_ = -1; }
+  } mode{this};
+  score_only_ = true;
+  max_penalty_ = max_penalty ? *max_penalty : -1;
+  run([&](const Batch& b) {  // (every entry has its own slot of `out`: no lock)
+    for (int64_t i = 0; i < b.n; ++i) {
+      const size_t k = b.pair(i);
+      PairScore& p = out[k];
+      p.query_idx = pairs_[k].first;
+      p.target_idx = pairs_[k].second;
+      p.is_reverse = b.is_rev(i);
+      p.status = b.res[i].status;
+      p.penalty = b.res[i].penalty;
+    }
+  });
+  return out;
 }
 
 // ---- wfa.rs ---------------------------------------------------------------------------------

@@ -83,6 +83,16 @@ enum class Orientation {
   Mash          // determine_orientation_mash (alignment.rs:69-154), hoisted to per-sequence sketches
 };
 
+// One pair's score-only result (AllPairIterator::scores): the optimal penalty without a CIGAR, WFA2's
+// AlignmentScope::ComputeScore.  status: AWV_ST_*; penalty: exact when AWV_ST_COMPLETED, max_penalty + 1 when
+// AWV_ST_ABOVE_BOUND, 0 on failure.
+struct PairScore {
+  size_t query_idx = 0, target_idx = 0;
+  bool is_reverse = false;
+  int32_t penalty = 0;
+  int32_t status = AWV_ST_COMPLETED;
+};
+
 using Callback = std::function<void(AlignmentResult&&)>;  // may throw: first error aborts the run
 
 // awv_engine_config.flags (AWV_F_*) for the per-device engines this library creates from now on
@@ -139,6 +149,11 @@ class AllPairIterator {  // iterator.rs:12-171
   // formats every record with alignment_to_paf on a small thread pool and hands whole batches to
   // `sink` (replaces the single unbuffered writer thread of src/main.rs:347-367); sink calls never overlap
   void for_each_paf_batch(const std::function<void(const std::string&)>& sink, int format_threads = 8);
+  // Score-only consumer (awv_score_pairs): one PairScore per planned pair, in pair-list order, through the same orientation,
+  // sparsification, shard and device settings as the alignment consumers (WFA orientation still aligns both strands in full
+  // to choose one; the final alignment is scored only).  max_penalty: a bound -- pairs proved above it come back
+  // AWV_ST_ABOVE_BOUND, and their search stops there.
+  std::vector<PairScore> scores(std::optional<int> max_penalty = std::nullopt);
   // counters of the last run, summed over its slots (kernel_ms: summed kernel time, not wall time)
   awv_stats last_stats() const { return stats_; }
   // the same, one entry per slot, in with_devices order
@@ -164,6 +179,11 @@ class AllPairIterator {  // iterator.rs:12-171
   // run_slots (several); batch indices are relative to `first`
   void run_range(size_t first, size_t count, const BatchCb& batch_cb);
   void run_slots(const std::vector<std::pair<size_t, size_t>>& plist, const BatchCb& batch_cb);
+  // the engine call of a run: awv_align_pairs, or awv_score_pairs while score_only_ (one sink call, results carry status and
+  // penalty, no arena)
+  int engine_call(awv_engine* e, const awv_penalties& pen, const awv_pair* ap, int64_t n, awv_sink sink, void* user) const;
+  bool score_only_ = false;
+  int32_t max_penalty_ = -1;
   const std::vector<Sequence>& sequences_;
   AlignmentParams params_, orientation_params_;
   bool exclude_self_ = true;

@@ -251,6 +251,37 @@ int awh_iterate_devices(int n, const char* const* ids, const uint8_t* bytes, con
                       min_batch_pairs, shard_rank, shard_world, 0, slot_stats, out, out_len, n_records, late_calls, err, cap);
 }
 
+// AllPairIterator::scores over the pair list AllPairIterator::with_options(..., exclude_self = true, mash orientation when
+// orientation == 2, sparsification) plans, oriented by `orientation` (0 forward, 1 WFA, 2 mash), on the engines
+// `devices[0, n_devices)` names, on shard `shard_rank` of `shard_world` (world <= 1: the whole list).  max_penalty < 0: no
+// bound.  out = malloc'ed int64 records of five (query_idx, target_idx, is_reverse, penalty, status), one per planned pair in
+// pair-list order; st (nullable) receives last_stats().
+int awh_all_pairs_scores(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores,
+                         const char* sparsification, int orientation, const int32_t* devices, int n_devices, int64_t shard_rank,
+                         int64_t shard_world, int64_t max_penalty, int64_t** out, size_t* npairs, awv_stats* st, char* err, size_t cap) {
+  try {
+    if (!devices || n_devices < 1) throw std::invalid_argument("awh_all_pairs_scores: empty device list");
+    const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
+    AllPairIterator it = AllPairIterator::with_options(seqs, parse_scores(scores), true, orientation == 2,
+                                                      SparsificationStrategy::parse(sparsification ? sparsification : "none"));
+    it.with_orientation(orientation == 0 ? Orientation::ForwardOnly : orientation == 1 ? Orientation::Wfa : Orientation::Mash);
+    it.with_devices(std::vector<int>(devices, devices + n_devices));
+    if (shard_world > 1) it.with_shard((size_t)shard_rank, (size_t)shard_world);
+    if (max_penalty > INT32_MAX) max_penalty = -1;  // (no pair can score that much: no bound)
+    const std::vector<PairScore> r = it.scores(max_penalty >= 0 ? std::optional<int>((int)max_penalty) : std::nullopt);
+    *out = (int64_t*)malloc(sizeof(int64_t) * 5 * (r.size() + 1));
+    if (!*out) throw std::bad_alloc();
+    for (size_t i = 0; i < r.size(); ++i) {
+      int64_t* o = *out + 5 * i;
+      o[0] = (int64_t)r[i].query_idx; o[1] = (int64_t)r[i].target_idx; o[2] = r[i].is_reverse ? 1 : 0;
+      o[3] = r[i].penalty; o[4] = r[i].status;
+    }
+    *npairs = r.size();
+    if (st) *st = it.last_stats();
+    return 0;
+  } catch (const std::exception& e) { set_err(err, cap, e.what()); return -1; }
+}
+
 // End-to-end measurement: sequences -> GPU alignment -> D2H -> PAF text into a counting sink.
 int awh_all_pairs_paf_count(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores,
                             int orientation, int device, int format_threads, uint64_t* out_bytes, uint64_t* out_lines,

@@ -3,7 +3,8 @@
 //   -i/--input  -o/--output  -s/--scores  -x/--preset  -t/--threads  -p/--sparsification
 //   --no-progress  --mash-matrix  --wfa-orientation  -k/--keep-prefixes  -e/--exclude-prefixes
 // Extensions: --device N (GPU ordinal), --devices LIST (several GPUs, or engines, in this one process),
-// --shard R/N (this process's part of the pair list), --forward-only (skip orientation: all '+').
+// --shard R/N (this process's part of the pair list), --forward-only (skip orientation: all '+'),
+// --score-only (penalties instead of PAF: WFA2's ComputeScore scope) with an optional --max-penalty N bound.
 // -t sets the host threads used for PAF formatting / sketching (alignment itself runs on the GPU).
 #include <zlib.h>
 
@@ -31,6 +32,9 @@ struct Args {
   std::string devices;  // --devices LIST (empty: --device)
   bool have_devices = false;
   long shard_rank = 0, shard_world = 1;  // --shard R/N: this process aligns pairs R, R+N, ... (one process per GPU)
+  bool score_only = false;  // --score-only: one line `qname qlen tname tlen strand penalty` per pair instead of PAF
+  long max_penalty = -1;    // --max-penalty N (with --score-only): pairs whose penalty exceeds N are left out
+  bool have_max_penalty = false;
 };
 
 [[noreturn]] void die(const std::string& m, int code = 2) {
@@ -179,6 +183,14 @@ int main(int argc, char** argv) {
     else if (k == "-e" || k == "--exclude-prefixes") { a.exclude = val(); a.have_exclude = true; }
     else if (k == "--device") { a.device = atoi(val().c_str()); a.have_device = true; }
     else if (k == "--devices") { a.devices = val(); a.have_devices = true; }
+    else if (k == "--score-only") a.score_only = true;
+    else if (k == "--max-penalty") {
+      const std::string v = val();
+      char* end = nullptr;
+      a.max_penalty = strtol(v.c_str(), &end, 10);
+      if (v.empty() || !end || *end != 0 || a.max_penalty < 0 || a.max_penalty > INT32_MAX) die("--max-penalty expects a penalty N >= 0");
+      a.have_max_penalty = true;
+    }
     else if (k == "--shard") {
       const std::string v = val();
       char* end = nullptr;
@@ -191,12 +203,16 @@ int main(int argc, char** argv) {
     else if (k == "-h" || k == "--help") {
       std::cout << "usage: allwave_hip -i in.fa [-o out.paf] [-s m,x,o,e[,o2,e2] | -x ANI] [-p none|auto|random:f|giant:p|tree:n:f:r[:k]]\n"
                    "                   [-t threads] [--wfa-orientation|--forward-only] [-k prefixes | -e prefixes] [--mash-matrix]\n"
-                   "                   [--device N | --devices LIST] [--shard R/N]\n"
+                   "                   [--device N | --devices LIST] [--shard R/N] [--score-only [--max-penalty N]]\n"
                    "  --devices LIST   align on several devices in this process: ordinals and ranges, e.g. 0,1,2 / 0-7 / all;\n"
-                   "                   an ordinal may repeat (0,0: two engines on device 0); -t is shared out among them\n";
+                   "                   an ordinal may repeat (0,0: two engines on device 0); -t is shared out among them\n"
+                   "  --score-only     no PAF: one tab-separated line per pair, `qname qlen tname tlen strand penalty`, in pair-list\n"
+                   "                   order (the optimal penalty without a CIGAR; `*` for a pair that failed)\n"
+                   "  --max-penalty N  with --score-only: stop searching a pair once its penalty is proved above N and leave it out\n";
       return 0;
     } else die("unexpected argument: " + k);
   }
+  if (a.have_max_penalty && !a.score_only) die("the argument '--max-penalty' requires '--score-only'");
   if (a.input.empty()) die("the following required arguments were not provided: --input <INPUT>");
   if (a.have_scores && a.have_preset) die("the argument '--scores' cannot be used with '--preset'");
   if (a.have_keep && a.have_exclude) die("the argument '--keep-prefixes' cannot be used with '--exclude-prefixes'");
@@ -261,21 +277,41 @@ int main(int argc, char** argv) {
     std::ostream& out = a.have_output ? (std::ostream&)fout : (std::ostream&)std::cout;
     const auto t0 = std::chrono::steady_clock::now();
     size_t done = 0;
-    it.for_each_paf_batch([&](const std::string& chunk) {
-      out.write(chunk.data(), (std::streamsize)chunk.size());
-      // a short write (disk full, closed pipe) must not pass for a complete PAF: the reference propagates
-      // the writer's error (main.rs:355 `writeln!(..)?`, joined at :451-453); throwing here makes the
-      // engine stop with AWV_ERR_SINK before any further batch
-      if (!out) throw std::runtime_error("write error on the PAF output");
-      for (char c : chunk) done += c == '\n';
-    }, a.threads);
+    if (a.score_only) {
+      const std::vector<PairScore> sc = it.scores(a.have_max_penalty ? std::optional<int>((int)a.max_penalty) : std::nullopt);
+      std::string buf;
+      for (const PairScore& p : sc) {
+        ++done;
+        if (p.status == AWV_ST_ABOVE_BOUND) continue;
+        const Sequence& q = sequences[p.query_idx];
+        const Sequence& t = sequences[p.target_idx];
+        buf += q.id + '\t' + std::to_string(q.seq.size()) + '\t' + t.id + '\t' + std::to_string(t.seq.size()) + '\t' +
+               (p.is_reverse ? '-' : '+') + '\t' + (p.status == AWV_ST_COMPLETED ? std::to_string(p.penalty) : std::string("*")) + '\n';
+        if (buf.size() >= (1u << 20)) {
+          out.write(buf.data(), (std::streamsize)buf.size());
+          if (!out) throw std::runtime_error("write error on the score output");
+          buf.clear();
+        }
+      }
+      out.write(buf.data(), (std::streamsize)buf.size());
+      if (!out) throw std::runtime_error("write error on the score output");
+    } else {
+      it.for_each_paf_batch([&](const std::string& chunk) {
+        out.write(chunk.data(), (std::streamsize)chunk.size());
+        // a short write (disk full, closed pipe) must not pass for a complete PAF: the reference propagates
+        // the writer's error (main.rs:355 `writeln!(..)?`, joined at :451-453); throwing here makes the
+        // engine stop with AWV_ERR_SINK before any further batch
+        if (!out) throw std::runtime_error("write error on the PAF output");
+        for (char c : chunk) done += c == '\n';
+      }, a.threads);
+    }
     out.flush();
     if (!out) die("write error on the PAF output (flush)", 1);
     if (a.have_output) {
       fout.close();
       if (fout.fail()) die("write error on the PAF output (close)", 1);
     }
-    if (done != total) die("internal: wrote " + std::to_string(done) + " of " + std::to_string(total) + " PAF lines", 1);
+    if (done != total) die("internal: wrote " + std::to_string(done) + " of " + std::to_string(total) + (a.score_only ? " pairs" : " PAF lines"), 1);
     if (!a.no_progress) {
       const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       char buf[160];

@@ -13,7 +13,11 @@ LIB_PATH = os.environ.get("AWV_HIP_LIB") or os.path.join(_HERE, "liballwave_hip.
 
 AWV_OK = 0
 AWV_ERR_NO_DEVICE = -1
+AWV_ERR_ARG = -3
 AWV_ERR_SINK = -7
+AWV_ST_COMPLETED = 0
+AWV_ST_CAPACITY = 1
+AWV_ST_ABOVE_BOUND = 4
 AWV_F_KEEP_ON_DEVICE = 1
 AWV_F_FORCE_INT32 = 2
 AWV_F_NO_PACKED_SEQ = 4
@@ -28,7 +32,7 @@ AWV_F_NO_RERUN = 1024
 
 #: every symbol include/allwave_hip.h declares
 EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine_destroy",
-           "awv_engine_set_sequences", "awv_align_pairs", "awv_align_one", "awv_engine_stats")
+           "awv_engine_set_sequences", "awv_align_pairs", "awv_align_one", "awv_score_pairs", "awv_engine_stats")
 
 
 class EngineConfig(C.Structure):
@@ -68,6 +72,8 @@ PAIR_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4")]
 RESULT_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4"), ("score", "<i4"), ("cigar_len", "<u4"),
                          ("cigar_off", "<u8"), ("num_matches", "<i4"), ("num_mismatches", "<i4"),
                          ("num_ins", "<i4"), ("num_del", "<i4"), ("q_end", "<i4"), ("t_end", "<i4")])
+#: awv_score_result
+SCORE_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4")])
 
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p)
 
@@ -91,6 +97,7 @@ def load():
                                       SINK_FN, C.c_void_p]
         L.awv_align_one.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_char_p, C.c_int32, C.c_char_p, C.c_int32,
                                     C.c_void_p, C.c_void_p, C.c_size_t]
+        L.awv_score_pairs.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         L.awv_engine_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
         _LIB = L
     return _LIB
@@ -140,10 +147,8 @@ class Engine:
             raise EngineError(rc, "awv_engine_set_sequences")
         self.nseq = n
 
-    def align_pairs(self, scores, pairs, want_cigars=True):
-        """pairs: int array [n,2] (q,t) or [n,3] (q,t,revcomp), or a PAIR_DTYPE array.
-        Returns (results structured array, list of op-byte strings or None)."""
-        pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+    @staticmethod
+    def _pair_array(pairs):
         if not (isinstance(pairs, np.ndarray) and pairs.dtype == PAIR_DTYPE):
             a = np.asarray(pairs, dtype=np.int32)
             a = a.reshape(len(a), -1) if len(a) else np.zeros((0, 2), dtype=np.int32)
@@ -153,7 +158,13 @@ class Engine:
                 if a.shape[1] > 2:
                     p["q_revcomp"] = a[:, 2]
             pairs = p
-        pairs = np.ascontiguousarray(pairs)
+        return np.ascontiguousarray(pairs)
+
+    def align_pairs(self, scores, pairs, want_cigars=True):
+        """pairs: int array [n,2] (q,t) or [n,3] (q,t,revcomp), or a PAIR_DTYPE array.
+        Returns (results structured array, list of op-byte strings or None)."""
+        pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+        pairs = self._pair_array(pairs)
         res = np.zeros(len(pairs), dtype=RESULT_DTYPE)
         cigars = [None] * len(pairs) if want_cigars else None
 
@@ -171,6 +182,21 @@ class Engine:
         if rc != AWV_OK:
             raise EngineError(rc, "awv_align_pairs")
         return res, cigars
+
+    def score_pairs(self, scores, pairs, max_penalty=None):
+        """Score-only alignment (awv_score_pairs): the optimal penalty of every pair, no CIGAR.  pairs as for align_pairs.
+        max_penalty: None = no bound; else pairs whose penalty exceeds it come back AWV_ST_ABOVE_BOUND with penalty
+        max_penalty + 1.  Returns a SCORE_DTYPE structured array (status, penalty)."""
+        pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+        pairs = self._pair_array(pairs)
+        bound = -1 if max_penalty is None else int(max_penalty)
+        if max_penalty is not None and bound < 0:
+            raise ValueError("max_penalty must be >= 0 (None: no bound)")
+        out = np.zeros(max(len(pairs), 1), dtype=SCORE_DTYPE)[:len(pairs)]  # (out is required, also for an empty list)
+        rc = load().awv_score_pairs(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), bound, out.ctypes.data)
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_score_pairs")
+        return out
 
     def align_one(self, scores, pattern, text):
         """Mirror of wf.align + wf.score + wf.cigar (alignment.rs:231-236). Returns (result, op_bytes)."""

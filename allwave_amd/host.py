@@ -214,6 +214,41 @@ def all_pairs_paf_count(ids, seqs, scores, orientation="forward", device=0, form
     return nb.value, nl.value, secs.value, st, list(slot), (ck.value if checksum else None)
 
 
+PAIR_SCORE_DTYPE = np.dtype([("query_idx", "<i8"), ("target_idx", "<i8"), ("is_reverse", "<i8"), ("penalty", "<i8"),
+                             ("status", "<i8")])
+
+
+def all_pairs_scores(ids, seqs, scores, orientation="mash", sparsification="none", devices=None, max_penalty=None, shard=None,
+                     with_stats=False):
+    """Score-only all-vs-all (AllPairIterator::scores): the optimal penalty of every planned pair without a CIGAR, in
+    pair-list order, as a PAIR_SCORE_DTYPE array (query_idx, target_idx, is_reverse, penalty, status -- ffi.AWV_ST_*).
+    The pair list is AllPairIterator::with_options(..., exclude_self=True, mash orientation, sparsification)'s; the strand of
+    each pair comes from `orientation` ("mash", "wfa": two full alignments per pair, or "forward").  `devices`: a list of
+    ordinals (one engine per entry, repeats allowed; None = device 0), `shard` = (rank, world) keeps that shard of the list.
+    max_penalty: None = no bound; else pairs proved above it come back AWV_ST_ABOVE_BOUND with penalty max_penalty + 1.
+    with_stats: returns (array, ffi.Stats) -- last_stats(), summed over the slots."""
+    if max_penalty is not None and int(max_penalty) < 0:
+        raise ValueError("max_penalty must be >= 0 (None: no bound)")
+    cids, data, offs = _seq_args(ids, seqs)
+    devs, nd = _device_args([0] if devices is None else devices)
+    rank, world = shard if shard is not None else (0, 1)
+    out = C.c_void_p()
+    n = C.c_size_t(0)
+    st = ffi.Stats()
+    e = _err()
+    rc = load().awh_all_pairs_scores(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), scores.encode(),
+                                     sparsification.encode(), ORIENT[orientation], devs, nd, C.c_int64(int(rank)), C.c_int64(int(world)),
+                                     C.c_int64(-1 if max_penalty is None else int(max_penalty)), C.byref(out), C.byref(n),
+                                     C.byref(st), e, _CAP)
+    if rc != 0:
+        raise HostError(e.value.decode())
+    k = n.value
+    raw = np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_int64)), shape=(max(k, 1) * 5,))[:5 * k].copy()
+    load().awh_free(out)
+    res = raw.view(PAIR_SCORE_DTYPE)
+    return (res, st) if with_stats else res
+
+
 def align_sequences(pattern, text, penalties, mode, device=0):
     """wfa.rs:178-258. penalties = (mismatch, o1, e1, o2, e2); mode in {"edit","affine","affine2p"}.
     Returns dict(score, cigar, matches, mismatches, insertions, deletions, alignment_length)."""

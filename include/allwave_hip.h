@@ -12,6 +12,8 @@
  *     src/alignment.rs:279-287, src/wfa.rs:208-216
  *   set_alignment_scope(Alignment) / set_alignment_span(End2End) /      fixed behaviour of the engine
  *   set_heuristic(None)   src/alignment.rs:226-228, src/wfa.rs:221-223  (end-to-end, exact, with CIGAR)
+ *   set_alignment_scope(ComputeScore) + wf.align + wf.score()            awv_score_pairs (exact penalty, no
+ *                                                                        CIGAR; optional penalty bound)
  *   wf.align(query, target) -> AlignmentStatus   src/alignment.rs:231   awv_align_pairs / awv_align_one
  *   wf.score()                                   src/alignment.rs:235   awv_result.score (= -penalty)
  *   wf.cigar() -> &[u8]                          src/alignment.rs:236   CIGAR arena + awv_result.cigar_off/len
@@ -68,6 +70,7 @@ extern "C" {
  * comes back AWV_ST_CAPACITY after its last re-run. */
 #define AWV_ST_INTERNAL 2        /* invariant violated (would be a bug) */
 #define AWV_ST_MAX_STEPS 3       /* step guard tripped */
+#define AWV_ST_ABOVE_BOUND 4     /* score-only calls: the penalty exceeds max_penalty */
 
 typedef struct awv_engine awv_engine;
 
@@ -191,6 +194,17 @@ int awv_align_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pai
 int awv_align_one(awv_engine* e, const awv_penalties* pen, const uint8_t* pattern, int32_t plen,
                   const uint8_t* text, int32_t tlen, awv_result* result, uint8_t* cigar_buf,
                   size_t cigar_cap);
+
+/* Score-only alignment (WFA2's AlignmentScope::ComputeScore): the optimal end-to-end penalty of pairs[0..npairs), no CIGAR.
+ * Runs the top-level BiWFA breakpoint search only (its breakpoint score is the penalty); needs no CIGAR arena, so
+ * max_arena_bytes never splits the call.  max_penalty >= 0 bounds the search: a pair whose penalty is proved above it stops
+ * there and comes back AWV_ST_ABOVE_BOUND; max_penalty < 0 means no bound.  awv_engine_stats reports the call. */
+typedef struct {
+  int32_t status;  /* AWV_ST_* */
+  int32_t penalty; /* exact when COMPLETED; max_penalty + 1 when ABOVE_BOUND; 0 on failure */
+} awv_score_result;
+int awv_score_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
+                    int32_t max_penalty /* < 0: no bound */, awv_score_result* out /* required */);
 
 int awv_engine_stats(const awv_engine* e, awv_stats* out);
 
