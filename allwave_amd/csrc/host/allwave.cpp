@@ -201,9 +201,9 @@ std::string alignment_to_paf(const AlignmentResult& r, const std::vector<Sequenc
 namespace {
 // One engine per (device, slot) and process, created on first use and kept (like the reference's cached
 // per-thread aligners, alignment.rs:11-22): its HBM arenas are tens of GB, and allocating them right
-// after a free can take the driver seconds.  Slot 0 is the engine every one-device run uses; a run over
-// several slots (with_devices) takes slots 0, 1, ... of each device it names.  A holder owns its slot's
-// engine for its lifetime.  Lock order: a slot's mutex, then the table's (never the other way round).
+// after a free can take the driver seconds.  A run takes slots 0, 1, ... of each device it names (one slot:
+// slot 0) and owns their engines under their mutexes.  Lock order: a slot's mutex, then the table's (never
+// the other way round).
 std::atomic<int> g_engine_flags{0};  // awv_engine_config.flags of engines created from now on (set_engine_flags)
 std::atomic<int> g_engine_first_row_cols{0};  // awv_engine_config.first_row_cols, likewise (diagnostic / test hook)
 constexpr int64_t kDefaultScratch = (int64_t)160 << 30;  // the engine's default max_scratch_bytes
@@ -254,12 +254,6 @@ awv_engine* slot_engine(int device, int slot, int slots_on_device) {
   es->e = e;
   return e;
 }
-struct EngineHolder {
-  awv_engine* e = nullptr;
-  std::unique_lock<std::mutex> lock;
-  explicit EngineHolder(int device) : lock(*slot_mutex(device, 0)) { e = slot_engine(device, 0, 1); }
-};
-
 void upload(awv_engine* e, const std::vector<Sequence>& seqs) {
   std::vector<uint64_t> offs(seqs.size() + 1, 0);
   for (size_t i = 0; i < seqs.size(); ++i) offs[i + 1] = offs[i] + seqs[i].seq.size();
@@ -268,6 +262,14 @@ void upload(awv_engine* e, const std::vector<Sequence>& seqs) {
     if (!seqs[i].seq.empty()) memcpy(cat.data() + offs[i], seqs[i].seq.data(), seqs[i].seq.size());
   if (awv_engine_set_sequences(e, (int32_t)seqs.size(), cat.data(), offs.data()) != AWV_OK)
     throw AlignmentError(std::string("set_sequences: ") + awv_last_error());
+}
+
+// planner::predicted_pair_cost of pairs[0, n)
+std::vector<double> pair_costs(const std::vector<Sequence>& seqs, const std::pair<size_t, size_t>* pairs, size_t n,
+                               const AlignmentParams& params) {
+  std::vector<double> cost(n);
+  for (size_t i = 0; i < n; ++i) cost[i] = planner::predicted_pair_cost(seqs[pairs[i].first].seq.size(), seqs[pairs[i].second].seq.size(), params);
+  return cost;
 }
 
 // align_pair's result mapping (alignment.rs:42-65, 239-253)
@@ -387,10 +389,7 @@ AllPairIterator& AllPairIterator::with_shard(size_t rank, size_t world) {
   // cost-balanced shards (planner::assign_shards_lpt): every process derives the same partition and
   // keeps its own part, in list order; equal-cost lists (config 2 / 3) come out strided
   if (world <= 1) return *this;
-  std::vector<double> cost(pairs_.size());
-  for (size_t i = 0; i < pairs_.size(); ++i)
-    cost[i] = planner::predicted_pair_cost(sequences_[pairs_[i].first].seq.size(), sequences_[pairs_[i].second].seq.size(), params_);
-  const std::vector<uint32_t> shard = planner::assign_shards_lpt(cost, world);
+  const std::vector<uint32_t> shard = planner::assign_shards_lpt(pair_costs(sequences_, pairs_.data(), pairs_.size(), params_), world);
   std::vector<std::pair<size_t, size_t>> mine;
   mine.reserve(pairs_.size() / world + 1);
   for (size_t i = 0; i < pairs_.size(); ++i)
@@ -414,18 +413,19 @@ AllPairParallelIterator AllPairIterator::into_par_iter() const { return AllPairP
 
 std::optional<AlignmentResult> AllPairIterator::next() {  // iterator.rs:151-171
   if (next_buf_pos_ >= next_buf_.size()) {
-    next_buf_.clear();
-    next_buf_pos_ = 0;
     if (next_pos_ >= pairs_.size()) return std::nullopt;
     const size_t first = next_pos_, cnt = std::min(next_chunk_, pairs_.size() - first);
-    next_buf_.resize(cnt);
-    run_range(first, cnt, [&](const Batch& b) {  // (every entry has its own slot of next_buf_: no lock)
+    std::vector<AlignmentResult> buf(cnt);
+    run(first, cnt, [&](const Batch& b) {  // (every entry has its own slot of buf: no lock)
       for (int64_t i = 0; i < b.n; ++i) {
         const size_t k = b.pair(i);
         const auto& pr = pairs_[first + k];
-        next_buf_[k] = make_result(pr.first, pr.second, b.is_rev(i), b.res[i], b.arena, true);
+        buf[k] = make_result(pr.first, pr.second, b.is_rev(i), b.res[i], b.arena, true);
       }
     });
+    // (only a run that returned moves the position on: after an error the next call runs the same chunk again)
+    next_buf_ = std::move(buf);
+    next_buf_pos_ = 0;
     next_pos_ += cnt;
   }
   return std::move(next_buf_[next_buf_pos_++]);
@@ -481,8 +481,7 @@ std::vector<AlignmentResult> AllPairParallelIterator::collect() {
 
 void process_alignments_with_callback(const std::vector<Sequence>& sequences, AlignmentParams params,
                                       SparsificationStrategy sparsification, const Callback& callback) {  // lib.rs:57-68
-  AllPairIterator aligner = AllPairIterator::with_options(sequences, std::move(params), true, true, std::move(sparsification));
-  aligner.for_each_with_callback(callback);
+  process_alignments_with_callback(sequences, std::move(params), std::move(sparsification), callback, {0});
 }
 
 void process_alignments_with_callback(const std::vector<Sequence>& sequences, AlignmentParams params,
@@ -537,12 +536,14 @@ void add_stats(awv_stats& acc, const awv_stats& x, bool same_engine) {
   if (!acc.clock_tick_khz) acc.clock_tick_khz = x.clock_tick_khz;
   acc.deep_cell_steps += x.deep_cell_steps;
 }
-}  // namespace
 
-int AllPairIterator::engine_call(awv_engine* e, const awv_penalties& pen, const awv_pair* ap, int64_t n, awv_sink sink, void* user) const {
-  if (!score_only_) return awv_align_pairs(e, &pen, ap, n, nullptr, sink, user);
+// one batch's engine call: awv_align_pairs, or awv_score_pairs under max_penalty (< 0: no bound) with its results handed
+// to the sink in one call (status and penalty, no arena)
+int engine_call(awv_engine* e, bool score_only, int32_t max_penalty, const awv_penalties& pen, const awv_pair* ap, int64_t n,
+                awv_sink sink, void* user) {
+  if (!score_only) return awv_align_pairs(e, &pen, ap, n, nullptr, sink, user);
   std::vector<awv_score_result> sr((size_t)n);
-  const int rc = awv_score_pairs(e, &pen, ap, n, max_penalty_, sr.data());
+  const int rc = awv_score_pairs(e, &pen, ap, n, max_penalty, sr.data());
   if (rc != AWV_OK || n == 0) return rc;
   std::vector<awv_result> res((size_t)n);
   for (int64_t i = 0; i < n; ++i) {
@@ -552,17 +553,21 @@ int AllPairIterator::engine_call(awv_engine* e, const awv_penalties& pen, const 
   }
   return sink(user, 0, n, res.data(), nullptr) == 0 ? AWV_OK : AWV_ERR_SINK;
 }
+}  // namespace
 
-void AllPairIterator::run_range(size_t range_first, size_t range_count, const BatchCb& batch_cb) {
-  if (devices_.size() > 1) {
-    if (range_first > pairs_.size() || range_count > pairs_.size() - range_first) throw AlignmentError("pair range out of bounds");
-    const std::vector<std::pair<size_t, size_t>> slice(pairs_.begin() + (ptrdiff_t)range_first,
-                                                       pairs_.begin() + (ptrdiff_t)(range_first + range_count));
-    run_slots(slice, batch_cb);
-    return;
-  }
+// The run's pairs go to its slots in batches.  One slot: one batch, the whole range in list order, on the calling thread.
+// Several slots: planner::device_batches over the predicted costs, one submitter thread per slot.  Every slot creates its
+// engine and uploads the sequences; only when all have done so (a failure there ends the run before any launch) does slot
+// s take batch s, and then the next batch from one cursor each time its previous call returns.  Per batch: WFA orientation
+// on the slot's own engine (mash orientation is computed once for the whole range, up front), then one engine call.  The
+// first error -- an engine's or a batch callback's -- wins: the other slots take no new batch and stop at their next sink
+// call; it is rethrown here once every thread has ended.
+void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, EngineCall call) {
+  if (first > pairs_.size() || count > pairs_.size() - first) throw AlignmentError("pair range out of bounds");
+  const std::pair<size_t, size_t>* plist = pairs_.data() + first;
+  const size_t S = devices_.size();
 #ifdef AWV_DEBUG_KNOBS
-  const bool timing = getenv("AWH_TIMING") != nullptr;  // diagnostic: stage times on stderr
+  const bool timing = S == 1 && getenv("AWH_TIMING") != nullptr;  // diagnostic: a one-slot run's stage times on stderr
 #else
   const bool timing = false;
 #endif
@@ -570,68 +575,13 @@ void AllPairIterator::run_range(size_t range_first, size_t range_count, const Ba
   auto lap = [&](const char* what) {
     if (timing) fprintf(stderr, "[awh] %-18s %.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count());
   };
-  EngineHolder eh(devices_[0]);
-  lap("engine created");
-  upload(eh.e, sequences_);
-  lap("sequences uploaded");
-  if (range_first > pairs_.size() || range_count > pairs_.size() - range_first) throw AlignmentError("pair range out of bounds");
-  // (a sub-range -- sequential next() -- works on its own copy of the slice; the whole list is used in place)
-  const bool whole = range_first == 0 && range_count == pairs_.size();
-  std::vector<std::pair<size_t, size_t>> slice;
-  if (!whole) slice.assign(pairs_.begin() + (ptrdiff_t)range_first, pairs_.begin() + (ptrdiff_t)(range_first + range_count));
-  const std::vector<std::pair<size_t, size_t>>& plist = whole ? pairs_ : slice;
-  const int64_t n = (int64_t)plist.size();
-  const int host_thr = threads_ > 0 ? threads_ : planner::host_threads();
-  std::vector<uint8_t> is_rev((size_t)n, 0);
-  std::vector<awv_pair> ap((size_t)n);
-  if (orientation_ == Orientation::Mash) {
-    is_rev = planner::orient_pairs_mash(sequences_, plist, host_thr);  // alignment.rs:69-94 (host threads: the CLI's -t)
-  } else if (orientation_ == Orientation::Wfa) {
-    for (int64_t i = 0; i < n; ++i) ap[i] = awv_pair{(int32_t)plist[i].first, (int32_t)plist[i].second, 0};
-    orient_wfa(eh.e, to_penalties(orientation_params_), ap.data(), n, is_rev.data());
-  }
-  for (int64_t i = 0; i < n; ++i) ap[i] = awv_pair{(int32_t)plist[i].first, (int32_t)plist[i].second, is_rev[i]};
-  struct Ctx {
-    const BatchCb* cb;
-    const std::vector<uint8_t>* rev;
-    std::exception_ptr err;
-  } ctx{&batch_cb, &is_rev, nullptr};
-  auto sink = [](void* user, int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena) -> int {
-    Ctx* c = (Ctx*)user;
-    try {
-      (*c->cb)(Batch{first, cnt, res, arena, c->rev->data(), nullptr});
-    } catch (...) {
-      c->err = std::current_exception();  // first error wins and aborts (iterator.rs:220-251)
-      return 1;
-    }
-    return 0;
-  };
-  const awv_penalties pen = to_penalties(params_);
-  lap("pairs oriented");
-  const int rc = engine_call(eh.e, pen, ap.data(), n, sink, &ctx);
-  lap("aligned + sunk");
-  awv_engine_stats(eh.e, &stats_);
-  slot_stats_.assign(1, stats_);
-  if (ctx.err) std::rethrow_exception(ctx.err);
-  if (rc != AWV_OK) throw AlignmentError(std::string("align_pairs: ") + awv_last_error());
-}
-
-// Several slots: planner::device_batches over the predicted costs, one submitter thread per slot.  Every slot creates its
-// engine and uploads the sequences; only when all have done so (a failure there ends the run before any launch) does slot
-// s take batch s, and then the next batch from one cursor each time its previous call returns.  Per batch: WFA orientation
-// on the slot's own engine (mash orientation is computed once for the whole list, up front), then one awv_align_pairs
-// call.  The first error -- an engine's or a batch callback's -- wins: the other slots take no new batch and stop at their
-// next sink call; it is rethrown here once every thread has ended.
-void AllPairIterator::run_slots(const std::vector<std::pair<size_t, size_t>>& plist, const BatchCb& batch_cb) {
-  const size_t S = devices_.size();
-  const int64_t n = (int64_t)plist.size();
-  std::vector<double> cost((size_t)n);
-  for (int64_t i = 0; i < n; ++i)
-    cost[i] = planner::predicted_pair_cost(sequences_[plist[i].first].seq.size(), sequences_[plist[i].second].seq.size(), params_);
-  const std::vector<std::vector<size_t>> batches = planner::device_batches(cost, S, min_batch_pairs_);
+  // pair indices (relative to `first`) of each batch; one slot's single batch needs none (Batch::idx == nullptr)
+  const std::vector<std::vector<size_t>> batches =
+      S > 1 ? planner::device_batches(pair_costs(sequences_, plist, count, params_), S, min_batch_pairs_)
+            : std::vector<std::vector<size_t>>(1);
   std::vector<uint8_t> mash_rev;
-  if (orientation_ == Orientation::Mash)
-    mash_rev = planner::orient_pairs_mash(sequences_, plist, threads_ > 0 ? threads_ : planner::host_threads());
+  if (orientation_ == Orientation::Mash)  // alignment.rs:69-94 (host threads: the CLI's -t)
+    mash_rev = planner::orient_pairs_mash(sequences_, plist, count, threads_ > 0 ? threads_ : planner::host_threads());
   // slot number of every entry on its device, and how many slots each device has in this run
   std::map<int, int> per_device;
   std::vector<int> slot_no(S);
@@ -662,7 +612,9 @@ void AllPairIterator::run_slots(const std::vector<std::pair<size_t, size_t>>& pl
     awv_engine* e = nullptr;
     try {
       e = slot_engine(devices_[s], slot_no[s], per_device.at(devices_[s]));
+      lap("engine created");
       upload(e, sequences_);
+      lap("sequences uploaded");
     } catch (...) {
       fail(std::current_exception());
     }
@@ -674,18 +626,19 @@ void AllPairIterator::run_slots(const std::vector<std::pair<size_t, size_t>>& pl
     if (stop.load()) return;
     try {
       for (size_t b = s; b < batches.size() && !stop.load(); b = cursor.fetch_add(1)) {
-        const std::vector<size_t>& idx = batches[b];
-        const int64_t m = (int64_t)idx.size();
-        if (m == 0) continue;
+        const size_t* idx = S > 1 ? batches[b].data() : nullptr;
+        const int64_t m = (int64_t)(S > 1 ? batches[b].size() : count);
+        auto at = [&](int64_t i) { return idx ? idx[i] : (size_t)i; };
         std::vector<awv_pair> ap((size_t)m);
         std::vector<uint8_t> rev((size_t)m, 0);
-        for (int64_t i = 0; i < m; ++i) ap[i] = awv_pair{(int32_t)plist[idx[i]].first, (int32_t)plist[idx[i]].second, 0};
+        for (int64_t i = 0; i < m; ++i) ap[i] = awv_pair{(int32_t)plist[at(i)].first, (int32_t)plist[at(i)].second, 0};
         if (orientation_ == Orientation::Mash) {
-          for (int64_t i = 0; i < m; ++i) rev[i] = mash_rev[idx[i]];
+          for (int64_t i = 0; i < m; ++i) rev[i] = mash_rev[at(i)];
         } else if (orientation_ == Orientation::Wfa) {
           orient_wfa(e, open, ap.data(), m, rev.data());
         }
         for (int64_t i = 0; i < m; ++i) ap[i].q_revcomp = rev[i];
+        lap("pairs oriented");
         struct Ctx {
           const BatchCb* cb;
           const uint8_t* rev;
@@ -693,7 +646,7 @@ void AllPairIterator::run_slots(const std::vector<std::pair<size_t, size_t>>& pl
           std::atomic<bool>* stop;
           const std::function<void(std::exception_ptr)>* fail;
           bool failed;
-        } ctx{&batch_cb, rev.data(), idx.data(), &stop, &fail_fn, false};
+        } ctx{&batch_cb, rev.data(), idx, &stop, &fail_fn, false};
         auto sink = [](void* user, int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena) -> int {
           Ctx* c = (Ctx*)user;
           if (c->stop->load()) return 1;  // another slot failed: stop here, report nothing
@@ -706,7 +659,8 @@ void AllPairIterator::run_slots(const std::vector<std::pair<size_t, size_t>>& pl
           }
           return 0;
         };
-        const int rc = engine_call(e, pen, ap.data(), m, sink, &ctx);
+        const int rc = engine_call(e, call.score_only, call.max_penalty, pen, ap.data(), m, sink, &ctx);
+        lap("aligned + sunk");
         awv_stats x{};
         awv_engine_stats(e, &x);
         add_stats(st[s], x, true);
@@ -803,12 +757,6 @@ void AllPairIterator::for_each_paf_batch(const std::function<void(const std::str
 std::vector<PairScore> AllPairIterator::scores(std::optional<int> max_penalty) {
   if (max_penalty && *max_penalty < 0) throw std::invalid_argument("scores: max_penalty must be >= 0");
   std::vector<PairScore> out(pairs_.size());
-  struct Mode {  // the iterator is back in alignment mode however this call ends
-    AllPairIterator* it;
-    ~Mode() { it->score_only_ = false; it->max_penalty_ = -1; }
-  } mode{this};
-  score_only_ = true;
-  max_penalty_ = max_penalty ? *max_penalty : -1;
   run([&](const Batch& b) {  // (every entry has its own slot of `out`: no lock)
     for (int64_t i = 0; i < b.n; ++i) {
       const size_t k = b.pair(i);
@@ -819,7 +767,7 @@ std::vector<PairScore> AllPairIterator::scores(std::optional<int> max_penalty) {
       p.status = b.res[i].status;
       p.penalty = b.res[i].penalty;
     }
-  });
+  }, EngineCall{true, max_penalty ? *max_penalty : -1});
   return out;
 }
 
@@ -873,10 +821,11 @@ AlignmentResult align_sequences(const std::vector<uint8_t>& pattern, const std::
       q.gap_open2 = p.gap_opening2; q.gap_ext2 = p.gap_extension2; q.two_piece = 1;
       break;
   }
-  EngineHolder eh(device);
+  std::lock_guard<std::mutex> slot(*slot_mutex(device, 0));
+  awv_engine* e = slot_engine(device, 0, 1);
   std::vector<uint8_t> cig(pattern.size() + text.size() + 1);
   awv_result r{};
-  if (awv_align_one(eh.e, &q, pattern.data(), (int32_t)pattern.size(), text.data(), (int32_t)text.size(), &r,
+  if (awv_align_one(e, &q, pattern.data(), (int32_t)pattern.size(), text.data(), (int32_t)text.size(), &r,
                     cig.data(), cig.size()) != AWV_OK)
     throw AlignmentError(std::string("Alignment failed: ") + awv_last_error());
   if (r.status != AWV_ST_COMPLETED) throw AlignmentError("Alignment failed with status: " + std::to_string(r.status));

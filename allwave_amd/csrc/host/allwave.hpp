@@ -132,7 +132,7 @@ class AllPairIterator {  // iterator.rs:12-171
   // Aligns the pair list on several engines at once, one "slot" per entry: an ordinal may appear more than once, and each
   // occurrence is an engine of its own (stream, arenas; the slots of one device split its default scratch budget).  With
   // two or more slots the list is cut into planner::device_batches, handed out from one cursor to one submitter thread per
-  // slot; with one slot every entry point runs exactly as with_device.
+  // slot; one slot aligns the list in one batch on the calling thread.
   AllPairIterator& with_devices(std::vector<int> devices);
   // pairs per batch at the least when several slots share the list (default 16,384: 4 x the engine's pairs in flight)
   AllPairIterator& with_min_batch_pairs(size_t pairs);
@@ -173,17 +173,18 @@ class AllPairIterator {  // iterator.rs:12-171
     bool is_rev(int64_t i) const { return rev[first + i] != 0; }
   };
   using BatchCb = std::function<void(const Batch&)>;
-  // With several slots, batch callbacks of different slots run concurrently: consumers that call user code serialise it.
-  void run(const BatchCb& batch_cb) { run_range(0, pairs_.size(), batch_cb); }
-  // pairs_[first, first + count) through one orientation pass + one awv_align_pairs call (one slot), or through
-  // run_slots (several); batch indices are relative to `first`
-  void run_range(size_t first, size_t count, const BatchCb& batch_cb);
-  void run_slots(const std::vector<std::pair<size_t, size_t>>& plist, const BatchCb& batch_cb);
-  // the engine call of a run: awv_align_pairs, or awv_score_pairs while score_only_ (one sink call, results carry status and
-  // penalty, no arena)
-  int engine_call(awv_engine* e, const awv_penalties& pen, const awv_pair* ap, int64_t n, awv_sink sink, void* user) const;
-  bool score_only_ = false;
-  int32_t max_penalty_ = -1;
+  // The engine call a run makes per batch: awv_align_pairs, or awv_score_pairs under max_penalty (< 0: no bound; one sink
+  // call per batch, results carry status and penalty, no arena).
+  struct EngineCall {
+    bool score_only;
+    int32_t max_penalty;
+  };
+  // pairs_[first, first + count) on the with_devices slots; batch indices are relative to `first`.  Per batch: orientation,
+  // one engine call, the batch callback, the counters.  One slot: one batch, the whole range in list order, on the calling
+  // thread.  With several slots, batch callbacks of different slots run concurrently: consumers that call user code
+  // serialise it.
+  void run(size_t first, size_t count, const BatchCb& batch_cb, EngineCall call = {false, -1});
+  void run(const BatchCb& batch_cb, EngineCall call = {false, -1}) { run(0, pairs_.size(), batch_cb, call); }
   const std::vector<Sequence>& sequences_;
   AlignmentParams params_, orientation_params_;
   bool exclude_self_ = true;
@@ -220,7 +221,8 @@ class AllPairParallelIterator {
 };
 
 // lib.rs:57-68: AllPairIterator::with_options(sequences, params, exclude_self = true, mash orientation = true, sparsification)
-// .for_each_with_callback(callback); the callback may throw (first error aborts and is rethrown)
+// .for_each_with_callback(callback) on device 0 (the overload below with devices {0}); the callback may throw (first error
+// aborts and is rethrown)
 void process_alignments_with_callback(const std::vector<Sequence>& sequences, AlignmentParams params,
                                       SparsificationStrategy sparsification, const Callback& callback);
 // the same on the engines `devices` names (AllPairIterator::with_devices; the callback's calls never overlap)

@@ -24,110 +24,6 @@ std::vector<Sequence> make_seqs(int n, const char* const* ids, const uint8_t* by
   return s;
 }
 
-// awh_iterate / awh_iterate_devices: devices == nullptr is the one-device hook, exactly as before
-int iterate_impl(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores,
-                 const char* sparsification, int orientation, int mode, int threads, int chunk, int resparsify, long fail_at,
-                 const int32_t* devices, int n_devices, int64_t min_batch_pairs, int64_t shard_rank, int64_t shard_world, int device,
-                 awv_stats* slot_stats, char** out, size_t* out_len, size_t* n_records, size_t* late_calls, char* err, size_t cap) {
-  size_t seen = 0, late = 0;
-  bool thrown = false;
-  try {
-    const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
-    const SparsificationStrategy strat = SparsificationStrategy::parse(sparsification ? sparsification : "none");
-    const Orientation orient = orientation == 0 ? Orientation::ForwardOnly : orientation == 1 ? Orientation::Wfa : Orientation::Mash;
-    std::mutex mu;
-    std::string all;
-    auto record = [&](AlignmentResult&& r) {
-      std::string line = alignment_to_paf(r, seqs);
-      std::lock_guard<std::mutex> g(mu);
-      if (fail_at >= 0 && (long)seen == fail_at) {
-        // (the multi-device hook tells a later failure from the first one, and counts the calls that follow the first)
-        if (devices && thrown) throw std::runtime_error("callback failed again, call " + std::to_string(++late) + " after the first failure");
-        thrown = true;
-        throw std::runtime_error("callback failed at record " + std::to_string(seen));
-      }
-      ++seen;
-      all += line;
-      all.push_back('\n');
-    };
-    const std::vector<int> devs(devices, devices + (devices ? n_devices : 0));
-    std::vector<awv_stats> st;
-    if (mode == 4 && !devices) {
-      process_alignments_with_callback(seqs, parse_scores(scores), strat, record);
-    } else if (mode == 4 && min_batch_pairs <= 0) {
-      process_alignments_with_callback(seqs, parse_scores(scores), strat, record, devs);
-    } else if (mode == 4) {  // what that overload does, with the batch size of the call
-      AllPairIterator it = AllPairIterator::with_options(seqs, parse_scores(scores), true, true, strat);
-      it.with_devices(devs).with_min_batch_pairs((size_t)min_batch_pairs);
-      it.for_each_with_callback(record);
-      st = it.last_slot_stats();
-    } else {
-      AllPairIterator it0 = AllPairIterator::with_options(seqs, parse_scores(scores), true, orientation == 2,
-                                                         resparsify ? SparsificationStrategy{} : strat);
-      it0.with_orientation(orient);
-      if (shard_world > 1) it0.with_shard((size_t)shard_rank, (size_t)shard_world);
-      if (devices) it0.with_devices(devs);
-      else it0.with_device(device);
-      if (min_batch_pairs > 0) it0.with_min_batch_pairs((size_t)min_batch_pairs);
-      if (chunk > 0) it0.with_next_chunk((size_t)chunk);
-      AllPairIterator it = resparsify ? it0.with_sparsification(strat).with_shard((size_t)shard_rank, (size_t)shard_world) : it0;
-      if (mode == 0) { it.for_each_with_callback(record); st = it.last_slot_stats(); }
-      else if (mode == 1) { while (auto r = it.next()) record(std::move(*r)); st = it.last_slot_stats(); }
-      else if (mode == 2) { auto par = it.into_par_iter(); par.with_threads(threads).for_each_with_callback(record); st = par.last_slot_stats(); }
-      else if (mode == 3) { auto par = it.into_par_iter(); for (auto& r : par.collect()) record(std::move(r)); st = par.last_slot_stats(); }
-      else throw std::invalid_argument("awh_iterate: unknown mode");
-    }
-    if (slot_stats)
-      for (int k = 0; k < n_devices; ++k) slot_stats[k] = (size_t)k < st.size() ? st[(size_t)k] : awv_stats{};
-    *out = (char*)malloc(all.size() + 1);
-    memcpy(*out, all.c_str(), all.size() + 1);
-    *out_len = all.size();
-    *n_records = seen;
-    return 0;
-  } catch (const std::exception& e) {
-    set_err(err, cap, e.what());
-    if (devices) {  // (the multi-device hook: records that arrived before the error, calls after it)
-      *n_records = seen;
-      if (late_calls) *late_calls = late;
-    }
-    return -1;
-  }
-}
-
-int paf_count_impl(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores, int orientation,
-                   const char* sparsification, const std::vector<int>& devices, int64_t min_batch_pairs, int format_threads,
-                   uint64_t* out_bytes, uint64_t* out_lines, uint64_t* out_checksum, double* secs, awv_stats* st, awv_stats* slot_stats,
-                   char* err, size_t cap) {
-  try {
-    const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
-    AllPairIterator it = sparsification ? AllPairIterator::with_options(seqs, parse_scores(scores), true, false,
-                                                                       SparsificationStrategy::parse(sparsification))
-                                        : AllPairIterator(seqs, parse_scores(scores));
-    it.with_orientation(orientation == 0 ? Orientation::ForwardOnly : orientation == 1 ? Orientation::Wfa : Orientation::Mash).with_devices(devices);
-    if (min_batch_pairs > 0) it.with_min_batch_pairs((size_t)min_batch_pairs);
-    it.with_threads(format_threads);  // this call's sketching / orientation threads: carried by the iterator, not a process-wide setting
-    uint64_t nb = 0, nl = 0, sum = 0;
-    const auto t0 = std::chrono::steady_clock::now();
-    it.for_each_paf_batch([&](const std::string& s) {
-      nb += s.size();
-      for (char c : s) nl += c == '\n';
-      if (out_checksum) {  // order-independent: the sum of every line's FNV-1a 64-bit hash
-        uint64_t h = 14695981039346656037ull;
-        for (char c : s) {
-          if (c == '\n') { sum += h; h = 14695981039346656037ull; }
-          else { h ^= (uint8_t)c; h *= 1099511628211ull; }
-        }
-      }
-    }, format_threads);
-    *secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    *out_bytes = nb;
-    *out_lines = nl;
-    if (out_checksum) *out_checksum = sum;
-    if (st) *st = it.last_stats();
-    if (slot_stats) for (size_t k = 0; k < devices.size(); ++k) slot_stats[k] = it.last_slot_stats()[k];
-    return 0;
-  } catch (const std::exception& e) { set_err(err, cap, e.what()); return -1; }
-}
 }  // namespace
 
 extern "C" {
@@ -185,8 +81,8 @@ int awh_format_paf(const char* qid, size_t qlen, const char* tid, size_t tlen, s
   return (int)s.size();
 }
 
-// awh_all_pairs_paf on the engines `devices[0, n_devices)` names (min_batch_pairs <= 0: the default; slot_stats: nullable,
-// n_devices entries).  With one device this is awh_all_pairs_paf.
+// AllPairIterator + alignment_to_paf per record on the engines `devices[0, n_devices)` names (min_batch_pairs <= 0: the
+// default; slot_stats: nullable, n_devices entries); out = the PAF lines
 int awh_all_pairs_paf_devices(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores,
                               const char* sparsification, int orientation, int exclude_self, const int32_t* devices, int n_devices,
                               int64_t min_batch_pairs, awv_stats* slot_stats, char** out, size_t* out_len, char* err, size_t cap) {
@@ -211,46 +107,84 @@ int awh_all_pairs_paf_devices(int n, const char* const* ids, const uint8_t* byte
   } catch (const std::exception& e) { set_err(err, cap, e.what()); return -1; }
 }
 
-int awh_all_pairs_paf(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores,
-                      const char* sparsification, int orientation, int exclude_self, int device, char** out, size_t* out_len,
-                      char* err, size_t cap) {
-  const int32_t dev = device;
-  return awh_all_pairs_paf_devices(n, ids, bytes, offs, scores, sparsification, orientation, exclude_self, &dev, 1, 0, nullptr, out,
-                                   out_len, err, cap);
-}
-
-// Every consumer of the pair list the reference offers, one per `mode` (tests/test_host_api.py):
+// Every consumer of the pair list the reference offers, one per `mode` (tests/test_host_api.py), on the engines
+// `devices[0, n_devices)` names (AllPairIterator::with_devices; an ordinal may repeat):
 //   0  AllPairIterator::for_each_with_callback                 iterator.rs:127-137
 //   1  the sequential `impl Iterator` (next() until the end)    iterator.rs:151-171
 //   2  into_par_iter().for_each_with_callback on `threads`      iterator.rs:113-125,206-253
 //   3  into_par_iter().collect()                                iterator.rs:182-203 (rayon collect)
 //   4  process_alignments_with_callback                         lib.rs:57-68 (mash orientation, exclude_self)
-// `resparsify`: plan with -p none first, then call with_sparsification(strategy) (iterator.rs:101-110).
-// `fail_at` >= 0: the callback throws at its fail_at-th record; the call must fail with that message (first error wins).
-// out = PAF lines in the order the records arrived.
-int awh_iterate(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores,
-                const char* sparsification, int orientation, int mode, int threads, int chunk, int resparsify, long fail_at,
-                int device, char** out, size_t* out_len, size_t* n_records, char* err, size_t cap) {
-  return iterate_impl(n, ids, bytes, offs, scores, sparsification, orientation, mode, threads, chunk, resparsify, fail_at, nullptr, 0, 0, 0, 1,
-                      device, nullptr, out, out_len, n_records, nullptr, err, cap);
-}
-
-// awh_iterate on the engines `devices[0, n_devices)` names (AllPairIterator::with_devices; an ordinal may repeat), with
-// batches of at least `min_batch_pairs` pairs (<= 0: the default), on shard `shard_rank` of `shard_world` (world <= 1: the
-// whole list; not in mode 4).  slot_stats (nullable, n_devices entries) receives last_slot_stats() -- zeros in mode 4
-// without min_batch_pairs, where process_alignments_with_callback owns the iterator.  On failure n_records still receives
-// the number of records that arrived and late_calls (nullable) how many callback calls followed the first failure; with
-// fail_at, the first failure's message is "callback failed at record <fail_at>" and later ones say "failed again".
+// `resparsify`: plan with -p none first, then call with_sparsification(strategy) (iterator.rs:101-110).  Batches of at
+// least `min_batch_pairs` pairs (<= 0: the default), on shard `shard_rank` of `shard_world` (world <= 1: the whole list; not
+// in mode 4).  out = PAF lines in the order the records arrived.  slot_stats (nullable, n_devices entries) receives
+// last_slot_stats() -- zeros in mode 4 without min_batch_pairs, where process_alignments_with_callback owns the iterator.
+// `fail_at` >= 0: the callback throws at its fail_at-th record; the call must fail with that message (first error wins),
+// "callback failed at record <fail_at>", and callback calls after it say "failed again".  On failure n_records still
+// receives the number of records that arrived and late_calls (nullable) how many callback calls followed the first failure.
 int awh_iterate_devices(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores,
                         const char* sparsification, int orientation, int mode, int threads, int chunk, int resparsify, long fail_at,
                         const int32_t* devices, int n_devices, int64_t min_batch_pairs, int64_t shard_rank, int64_t shard_world,
                         awv_stats* slot_stats, char** out, size_t* out_len, size_t* n_records, size_t* late_calls, char* err,
                         size_t cap) {
   if (!devices || n_devices < 1) { set_err(err, cap, "awh_iterate_devices: empty device list"); return -1; }
-  return iterate_impl(n, ids, bytes, offs, scores, sparsification, orientation, mode, threads, chunk, resparsify, fail_at, devices, n_devices,
-                      min_batch_pairs, shard_rank, shard_world, 0, slot_stats, out, out_len, n_records, late_calls, err, cap);
+  size_t seen = 0, late = 0;
+  bool thrown = false;
+  try {
+    const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
+    const SparsificationStrategy strat = SparsificationStrategy::parse(sparsification ? sparsification : "none");
+    const Orientation orient = orientation == 0 ? Orientation::ForwardOnly : orientation == 1 ? Orientation::Wfa : Orientation::Mash;
+    std::mutex mu;
+    std::string all;
+    auto record = [&](AlignmentResult&& r) {
+      std::string line = alignment_to_paf(r, seqs);
+      std::lock_guard<std::mutex> g(mu);
+      if (fail_at >= 0 && (long)seen == fail_at) {
+        // (a later failure is told from the first one, and the calls that follow the first are counted)
+        if (thrown) throw std::runtime_error("callback failed again, call " + std::to_string(++late) + " after the first failure");
+        thrown = true;
+        throw std::runtime_error("callback failed at record " + std::to_string(seen));
+      }
+      ++seen;
+      all += line;
+      all.push_back('\n');
+    };
+    const std::vector<int> devs(devices, devices + n_devices);
+    std::vector<awv_stats> st;
+    if (mode == 4 && min_batch_pairs <= 0) {
+      process_alignments_with_callback(seqs, parse_scores(scores), strat, record, devs);
+    } else if (mode == 4) {  // what that overload does, with the batch size of the call
+      AllPairIterator it = AllPairIterator::with_options(seqs, parse_scores(scores), true, true, strat);
+      it.with_devices(devs).with_min_batch_pairs((size_t)min_batch_pairs);
+      it.for_each_with_callback(record);
+      st = it.last_slot_stats();
+    } else {
+      AllPairIterator it0 = AllPairIterator::with_options(seqs, parse_scores(scores), true, orientation == 2,
+                                                         resparsify ? SparsificationStrategy{} : strat);
+      it0.with_orientation(orient).with_devices(devs);
+      if (shard_world > 1) it0.with_shard((size_t)shard_rank, (size_t)shard_world);
+      if (min_batch_pairs > 0) it0.with_min_batch_pairs((size_t)min_batch_pairs);
+      if (chunk > 0) it0.with_next_chunk((size_t)chunk);
+      AllPairIterator it = resparsify ? it0.with_sparsification(strat).with_shard((size_t)shard_rank, (size_t)shard_world) : it0;
+      if (mode == 0) { it.for_each_with_callback(record); st = it.last_slot_stats(); }
+      else if (mode == 1) { while (auto r = it.next()) record(std::move(*r)); st = it.last_slot_stats(); }
+      else if (mode == 2) { auto par = it.into_par_iter(); par.with_threads(threads).for_each_with_callback(record); st = par.last_slot_stats(); }
+      else if (mode == 3) { auto par = it.into_par_iter(); for (auto& r : par.collect()) record(std::move(r)); st = par.last_slot_stats(); }
+      else throw std::invalid_argument("awh_iterate_devices: unknown mode");
+    }
+    if (slot_stats)
+      for (int k = 0; k < n_devices; ++k) slot_stats[k] = (size_t)k < st.size() ? st[(size_t)k] : awv_stats{};
+    *out = (char*)malloc(all.size() + 1);
+    memcpy(*out, all.c_str(), all.size() + 1);
+    *out_len = all.size();
+    *n_records = seen;
+    return 0;
+  } catch (const std::exception& e) {
+    set_err(err, cap, e.what());
+    *n_records = seen;
+    if (late_calls) *late_calls = late;
+    return -1;
+  }
 }
-
 // AllPairIterator::scores over the pair list AllPairIterator::with_options(..., exclude_self = true, mash orientation when
 // orientation == 2, sparsification) plans, oriented by `orientation` (0 forward, 1 WFA, 2 mash), on the engines
 // `devices[0, n_devices)` names, on shard `shard_rank` of `shard_world` (world <= 1: the whole list).  max_penalty < 0: no
@@ -282,25 +216,45 @@ int awh_all_pairs_scores(int n, const char* const* ids, const uint8_t* bytes, co
   } catch (const std::exception& e) { set_err(err, cap, e.what()); return -1; }
 }
 
-// End-to-end measurement: sequences -> GPU alignment -> D2H -> PAF text into a counting sink.
-int awh_all_pairs_paf_count(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores,
-                            int orientation, int device, int format_threads, uint64_t* out_bytes, uint64_t* out_lines,
-                            double* secs, awv_stats* st, char* err, size_t cap) {
-  return paf_count_impl(n, ids, bytes, offs, scores, orientation, nullptr, std::vector<int>(1, device), 0, format_threads, out_bytes,
-                        out_lines, nullptr, secs, st, nullptr, err, cap);
-}
-
-// awh_all_pairs_paf_count on the engines `devices[0, n_devices)` names (min_batch_pairs <= 0: the default) over the pair
-// list `sparsification` plans (nullable: every pair, as awh_all_pairs_paf_count); slot_stats (nullable, n_devices entries)
-// receives last_slot_stats(), st (nullable) their sum, out_checksum (nullable) the sum of the lines' FNV-1a hashes (the
-// same for the same lines in any order)
+// End-to-end measurement: sequences -> GPU alignment -> D2H -> PAF text into a counting sink, on the engines
+// `devices[0, n_devices)` names (min_batch_pairs <= 0: the default), over the pair list `sparsification` plans (nullable:
+// every pair, AllPairIterator::new); slot_stats (nullable, n_devices entries) receives last_slot_stats(), st (nullable)
+// their sum, out_checksum (nullable) the sum of the lines' FNV-1a hashes (the same for the same lines in any order)
 int awh_all_pairs_paf_count_devices(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores,
                                     int orientation, const char* sparsification, const int32_t* devices, int n_devices,
                                     int64_t min_batch_pairs, int format_threads, uint64_t* out_bytes, uint64_t* out_lines,
                                     uint64_t* out_checksum, double* secs, awv_stats* st, awv_stats* slot_stats, char* err, size_t cap) {
   if (!devices || n_devices < 1) { set_err(err, cap, "awh_all_pairs_paf_count_devices: empty device list"); return -1; }
-  return paf_count_impl(n, ids, bytes, offs, scores, orientation, sparsification, std::vector<int>(devices, devices + n_devices),
-                        min_batch_pairs, format_threads, out_bytes, out_lines, out_checksum, secs, st, slot_stats, err, cap);
+  try {
+    const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
+    AllPairIterator it = sparsification ? AllPairIterator::with_options(seqs, parse_scores(scores), true, false,
+                                                                       SparsificationStrategy::parse(sparsification))
+                                        : AllPairIterator(seqs, parse_scores(scores));
+    it.with_orientation(orientation == 0 ? Orientation::ForwardOnly : orientation == 1 ? Orientation::Wfa : Orientation::Mash)
+        .with_devices(std::vector<int>(devices, devices + n_devices));
+    if (min_batch_pairs > 0) it.with_min_batch_pairs((size_t)min_batch_pairs);
+    it.with_threads(format_threads);  // this call's sketching / orientation threads: carried by the iterator, not a process-wide setting
+    uint64_t nb = 0, nl = 0, sum = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    it.for_each_paf_batch([&](const std::string& s) {
+      nb += s.size();
+      for (char c : s) nl += c == '\n';
+      if (out_checksum) {  // order-independent: the sum of every line's FNV-1a 64-bit hash
+        uint64_t h = 14695981039346656037ull;
+        for (char c : s) {
+          if (c == '\n') { sum += h; h = 14695981039346656037ull; }
+          else { h ^= (uint8_t)c; h *= 1099511628211ull; }
+        }
+      }
+    }, format_threads);
+    *secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    *out_bytes = nb;
+    *out_lines = nl;
+    if (out_checksum) *out_checksum = sum;
+    if (st) *st = it.last_stats();
+    if (slot_stats) for (int k = 0; k < n_devices; ++k) slot_stats[k] = it.last_slot_stats()[(size_t)k];
+    return 0;
+  } catch (const std::exception& e) { set_err(err, cap, e.what()); return -1; }
 }
 int awh_align_sequences(const uint8_t* pattern, size_t plen, const uint8_t* text, size_t tlen, const int32_t pen[5], int mode,
                         int device, int32_t* score, char* cigar, size_t ccap, uint64_t counts[5], char* err, size_t cap) {
@@ -369,7 +323,7 @@ int awh_orient_mash(int n, const char* const* ids, const uint8_t* bytes, const u
   const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
   std::vector<std::pair<size_t, size_t>> p(npairs);
   for (size_t i = 0; i < npairs; ++i) p[i] = {(size_t)pairs[2 * i], (size_t)pairs[2 * i + 1]};
-  const auto r = planner::orient_pairs_mash(seqs, p, 8);
+  const auto r = planner::orient_pairs_mash(seqs, p.data(), p.size(), 8);
   memcpy(is_rev, r.data(), npairs);
   return 0;
 }

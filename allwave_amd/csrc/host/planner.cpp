@@ -130,16 +130,16 @@ static void parallel_for(size_t n, int threads, F f) {
   for (auto& x : th) x.join();
 }
 
-std::vector<uint8_t> orient_pairs_mash(const std::vector<Sequence>& seqs,
-                                       const std::vector<std::pair<size_t, size_t>>& pairs, int threads) {
+std::vector<uint8_t> orient_pairs_mash(const std::vector<Sequence>& seqs, const std::pair<size_t, size_t>* pairs, size_t npairs,
+                                       int threads) {
   constexpr size_t K = 15, S = 1000;  // alignment.rs:70-75
   std::vector<std::vector<uint64_t>> fwd(seqs.size()), rev(seqs.size());
   parallel_for(seqs.size(), threads, [&](size_t i) {
     fwd[i] = sketch_sequence_stranded(seqs[i].seq, K, S);
     rev[i] = sketch_sequence_stranded(reverse_complement(seqs[i].seq), K, S);
   });
-  std::vector<uint8_t> is_rev(pairs.size(), 0);
-  parallel_for(pairs.size(), threads, [&](size_t p) {
+  std::vector<uint8_t> is_rev(npairs, 0);
+  parallel_for(npairs, threads, [&](size_t p) {
     const size_t q = pairs[p].first, t = pairs[p].second;
     const double jf = jaccard(fwd[q], fwd[t]), jr = jaccard(rev[q], fwd[t]);
     is_rev[p] = jf >= jr ? 0 : 1;  // forward wins ties (alignment.rs:89)

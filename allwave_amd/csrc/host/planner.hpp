@@ -30,9 +30,9 @@ double jaccard(const std::vector<uint64_t>& a, const std::vector<uint64_t>& b); 
 double mash_distance(double jaccard, size_t k);                                   // mash.rs:59-74
 
 // alignment.rs:69-94 hoisted to per-sequence sketches (identical results, 2 sketches per sequence
-// instead of 3 per pair): is_reverse[i] for pairs[i]
-std::vector<uint8_t> orient_pairs_mash(const std::vector<Sequence>& seqs,
-                                       const std::vector<std::pair<size_t, size_t>>& pairs, int threads);
+// instead of 3 per pair): is_reverse[i] for pairs[i], i < npairs
+std::vector<uint8_t> orient_pairs_mash(const std::vector<Sequence>& seqs, const std::pair<size_t, size_t>* pairs, size_t npairs,
+                                       int threads);
 
 // host threads used by sketching / orientation when the caller does not say (the CLI's -t; default 8)
 void set_host_threads(int threads);

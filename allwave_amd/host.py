@@ -118,21 +118,16 @@ def _device_args(devices):
 def all_pairs_paf(ids, seqs, scores, orientation="wfa", exclude_self=True, device=0, sparsification="none", devices=None,
                   min_batch_pairs=0):
     """AllPairIterator + alignment_to_paf per record; returns the list of PAF lines.  `devices`: a list of ordinals (one
-    engine per entry, repeats allowed) to spread the pair list over in this call; None = `device` alone, as before.
+    engine per entry, repeats allowed) to spread the pair list over in this call; None = [device].
     `min_batch_pairs` > 0 overrides the smallest batch of a multi-device run (default 16,384)."""
     cids, data, offs = _seq_args(ids, seqs)
+    devs, nd = _device_args([device] if devices is None else devices)
     out = C.c_void_p()
     n = C.c_size_t(0)
     e = _err()
-    if devices is None:
-        rc = load().awh_all_pairs_paf(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
-                                      scores.encode(), sparsification.encode(), ORIENT[orientation], int(exclude_self),
-                                      device, C.byref(out), C.byref(n), e, _CAP)
-    else:
-        devs, nd = _device_args(devices)
-        rc = load().awh_all_pairs_paf_devices(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
-                                              scores.encode(), sparsification.encode(), ORIENT[orientation], int(exclude_self),
-                                              devs, nd, C.c_int64(int(min_batch_pairs)), None, C.byref(out), C.byref(n), e, _CAP)
+    rc = load().awh_all_pairs_paf_devices(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
+                                          scores.encode(), sparsification.encode(), ORIENT[orientation], int(exclude_self),
+                                          devs, nd, C.c_int64(int(min_batch_pairs)), None, C.byref(out), C.byref(n), e, _CAP)
     if rc != 0:
         raise HostError(e.value.decode())
     txt = C.string_at(out, n.value).decode()
@@ -147,70 +142,59 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
             resparsify=False, fail_at=-1, device=0, devices=None, min_batch_pairs=0, shard=None, with_stats=False):
     """Every consumer of the pair list (iterator.rs:101-253, lib.rs:57-68) through one hook; returns the PAF lines in arrival
     order.  `fail_at` >= 0 makes the callback throw at that record: HostError carries its message.
-    `devices`: a list of ordinals (one engine per entry, repeats allowed) to spread the pair list over; None = `device`
-    alone, through the one-device hook as before.  `min_batch_pairs` > 0 overrides the smallest batch of a multi-device
-    run, `shard` = (rank, world) keeps that shard of the list (with_shard; devices only, not "process_alignments").
-    with_stats (devices only): returns (lines, [ffi.Stats per slot]) -- last_slot_stats(); all zeros for
-    "process_alignments" without min_batch_pairs.  With devices, a HostError carries `.records`: how many records
-    arrived before the error, and `.late_calls`: how many callback calls followed the first failure (with fail_at, each of
-    those fails with a message of its own: "callback failed again, ...")."""
+    `devices`: a list of ordinals (one engine per entry, repeats allowed) to spread the pair list over; None = [device].
+    `min_batch_pairs` > 0 overrides the smallest batch of a multi-device run, `shard` = (rank, world) keeps that shard of
+    the list (with_shard; not "process_alignments").  with_stats: returns (lines, [ffi.Stats per slot]) --
+    last_slot_stats(); all zeros for "process_alignments" without min_batch_pairs.  A HostError carries `.records`: how
+    many records arrived before the error, and `.late_calls`: how many callback calls followed the first failure (with
+    fail_at, each of those fails with a message of its own: "callback failed again, ...")."""
     cids, data, offs = _seq_args(ids, seqs)
+    devs, nd = _device_args([device] if devices is None else devices)
+    st = (ffi.Stats * nd)()
+    rank, world = shard if shard is not None else (0, 1)
     out = C.c_void_p()
     n, nrec, late = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
     e = _err()
-    if devices is None:
-        rc = load().awh_iterate(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), scores.encode(),
-                                sparsification.encode(), ORIENT[orientation], ITER_MODES[mode], int(threads), int(chunk), int(bool(resparsify)),
-                                C.c_long(int(fail_at)), device, C.byref(out), C.byref(n), C.byref(nrec), e, _CAP)
-        st = None
-    else:
-        devs, nd = _device_args(devices)
-        st = (ffi.Stats * nd)()
-        rank, world = shard if shard is not None else (0, 1)
-        rc = load().awh_iterate_devices(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), scores.encode(),
-                                        sparsification.encode(), ORIENT[orientation], ITER_MODES[mode], int(threads), int(chunk),
-                                        int(bool(resparsify)), C.c_long(int(fail_at)), devs, nd, C.c_int64(int(min_batch_pairs)),
-                                        C.c_int64(int(rank)), C.c_int64(int(world)), st, C.byref(out), C.byref(n), C.byref(nrec),
-                                        C.byref(late), e, _CAP)
+    rc = load().awh_iterate_devices(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), scores.encode(),
+                                    sparsification.encode(), ORIENT[orientation], ITER_MODES[mode], int(threads), int(chunk),
+                                    int(bool(resparsify)), C.c_long(int(fail_at)), devs, nd, C.c_int64(int(min_batch_pairs)),
+                                    C.c_int64(int(rank)), C.c_int64(int(world)), st, C.byref(out), C.byref(n), C.byref(nrec),
+                                    C.byref(late), e, _CAP)
     if rc != 0:
         err = HostError(e.value.decode())
-        err.records = nrec.value if devices is not None else None
-        err.late_calls = late.value if devices is not None else None
+        err.records = nrec.value
+        err.late_calls = late.value
         raise err
     txt = C.string_at(out, n.value).decode()
     load().awh_free(out)
     if with_stats:
-        return txt.splitlines(), (list(st) if st is not None else None)
+        return txt.splitlines(), list(st)
     return txt.splitlines()
 
 
 def all_pairs_paf_count(ids, seqs, scores, orientation="forward", device=0, format_threads=8, devices=None, min_batch_pairs=0,
                         sparsification=None, checksum=False):
-    """End to end: upload -> align -> D2H -> format into a counting sink. Returns (bytes, lines, secs, ffi.Stats).
-    `devices`: a list of ordinals (one engine per entry, repeats allowed); the Stats are then summed over the slots, and
-    the result gains a fifth element, each slot's Stats (last_slot_stats()), and a sixth, the sum of the lines' FNV-1a
-    hashes when `checksum` (order-independent; else None).  With devices, `sparsification` plans the pair list (default:
-    every pair).  None = `device` alone, as before."""
+    """End to end: upload -> align -> D2H -> format into a counting sink. Returns (bytes, lines, secs, ffi.Stats) for
+    every pair on `device`.  `devices`: a list of ordinals (one engine per entry, repeats allowed); the Stats are then
+    summed over the slots, and the result gains a fifth element, each slot's Stats (last_slot_stats()), and a sixth, the
+    sum of the lines' FNV-1a hashes when `checksum` (order-independent; else None).  With devices, `sparsification` plans
+    the pair list (default: every pair)."""
+    one = devices is None
     cids, data, offs = _seq_args(ids, seqs)
-    nb, nl, secs = C.c_uint64(0), C.c_uint64(0), C.c_double(0)
+    devs, nd = _device_args([device] if one else devices)
+    nb, nl, secs, ck = C.c_uint64(0), C.c_uint64(0), C.c_double(0), C.c_uint64(0)
     st = ffi.Stats()
-    e = _err()
-    if devices is None:
-        rc = load().awh_all_pairs_paf_count(len(ids), cids, data.ctypes.data_as(C.c_void_p),
-                                            offs.ctypes.data_as(C.c_void_p), scores.encode(), ORIENT[orientation], device,
-                                            format_threads, C.byref(nb), C.byref(nl), C.byref(secs), C.byref(st), e, _CAP)
-        if rc != 0:
-            raise HostError(e.value.decode())
-        return nb.value, nl.value, secs.value, st
-    devs, nd = _device_args(devices)
     slot = (ffi.Stats * nd)()
-    ck = C.c_uint64(0)
+    e = _err()
     rc = load().awh_all_pairs_paf_count_devices(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
-                                                scores.encode(), ORIENT[orientation], sparsification.encode() if sparsification else None,
+                                                scores.encode(), ORIENT[orientation],
+                                                sparsification.encode() if sparsification and not one else None,
                                                 devs, nd, C.c_int64(int(min_batch_pairs)), format_threads, C.byref(nb), C.byref(nl),
                                                 C.byref(ck) if checksum else None, C.byref(secs), C.byref(st), slot, e, _CAP)
     if rc != 0:
         raise HostError(e.value.decode())
+    if one:
+        return nb.value, nl.value, secs.value, st
     return nb.value, nl.value, secs.value, st, list(slot), (ck.value if checksum else None)
 
 

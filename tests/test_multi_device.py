@@ -116,8 +116,8 @@ def test_empty_device_list_is_refused(host):
 
 def test_no_gpu_multi_slot_fails_promptly(host):
     """On a box without a GPU every slot's engine creation fails: the first error crosses the submitter threads and is
-    raised once, promptly, with the engine's no-device message -- in a child process, so that a hang would end at its
-    time limit instead of stopping the suite."""
+    raised once, promptly, with the engine's no-device message; the one-device form (devices=None) fails the same way --
+    in a child process, so that a hang would end at its time limit instead of stopping the suite."""
     import torch
     if torch.cuda.is_available():
         pytest.skip("GPU present")
@@ -125,14 +125,14 @@ def test_no_gpu_multi_slot_fails_promptly(host):
         "import sys, time; sys.path.insert(0, %r)\n"
         "from allwave_amd import host as H\n"
         "t = time.time()\n"
-        "for mode in ('for_each', 'next', 'par_for_each', 'par_collect', 'process_alignments'):\n"
-        "    try:\n"
-        "        H.iterate(['a', 'b', 'c'], [b'ACGT' * 9, b'ACGA' * 9, b'TTGA' * 9], '0,5,8,2,24,1', mode=mode, chunk=2,\n"
-        "                  devices=[0, 0], min_batch_pairs=1)\n"
-        "        print('no error', mode); sys.exit(1)\n"
-        "    except H.HostError as e:\n"
-        "        assert 'no HIP device' in str(e) and 'no CPU fallback' in str(e), str(e)\n"
-        "        assert e.records == 0, e.records\n"
+        "for kw in (dict(devices=[0, 0], min_batch_pairs=1), dict(devices=None)):\n"
+        "    for mode in ('for_each', 'next', 'par_for_each', 'par_collect', 'process_alignments'):\n"
+        "        try:\n"
+        "            H.iterate(['a', 'b', 'c'], [b'ACGT' * 9, b'ACGA' * 9, b'TTGA' * 9], '0,5,8,2,24,1', mode=mode, chunk=2, **kw)\n"
+        "            print('no error', mode, kw); sys.exit(1)\n"
+        "        except H.HostError as e:\n"
+        "            assert 'no HIP device' in str(e) and 'no CPU fallback' in str(e), (kw, str(e))\n"
+        "            assert e.records == 0, (kw, e.records)\n"
         "print('ok %%.3f' %% (time.time() - t))\n") % ROOT
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
@@ -195,7 +195,7 @@ def _assert_slots_worked(stats, npairs):
 
 @pytest.mark.gpu
 def test_two_slots_every_consumer(host, oracle):
-    """devices=[0, 0] with one-pair batches: each consumer of awh_iterate gives the one-device output and the oracle's --
+    """devices=[0, 0] with one-pair batches: each consumer of host.iterate gives the one-device output and the oracle's --
     the same list for the ordered consumers (par_collect, next), the same lines otherwise; both slots align pairs."""
     ids, seqs = _mixed_list(11)
     sc = "0,5,8,2,24,1"
