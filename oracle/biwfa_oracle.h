@@ -87,9 +87,21 @@ int awo_align_unidirectional(awo_aligner_t* a, const uint8_t* pattern, int plen,
                              const uint8_t* text, int tlen, uint8_t* cigar_out, int cigar_cap,
                              int* cigar_len, int* penalty, awo_stats_t* stats);
 
-/* ---- oracle/gotoh.c : independent full-DP optimum (score only, O(plen*tlen)) ---- */
+/* ---- oracle/gotoh.c : independent full-DP optimum (score only, O(plen*tlen)), and its banded form ---- */
 int64_t awo_gotoh_penalty(const uint8_t* pattern, int plen, const uint8_t* text, int tlen,
                           const awo_penalties_t* pen);
+/* The same DP on the diagonals k = j - i that an alignment of cost <= bound can visit: the exact optimum when it is
+ * <= bound, else bound + 1.  O(min(plen, tlen) * band) time, O(band) memory; affordable at 20-150 kbp when the bound is
+ * near the optimum of a low-divergence pair.  Negative on allocation failure. */
+int64_t awo_gotoh_penalty_banded(const uint8_t* pattern, int plen, const uint8_t* text, int tlen,
+                                 const awo_penalties_t* pen, int64_t bound);
+/* The band awo_gotoh_penalty_banded uses, [*lo, *hi] in k = j - i: [min(0, dl) - m, max(0, dl) + m] for dl = tlen - plen
+ * and the largest m with g(|dl| + 2m) <= bound, clipped to the matrix.  Returns -1 (no band) when bound < 0 or the
+ * forced gap alone costs more than bound. */
+int awo_gotoh_band(int plen, int tlen, const awo_penalties_t* pen, int64_t bound, int64_t* lo, int64_t* hi);
+/* The DP restricted to the diagonals lo <= j - i <= hi: the cheapest path inside them (>= 2^50 when none). */
+int64_t awo_gotoh_penalty_band(const uint8_t* pattern, int plen, const uint8_t* text, int tlen,
+                               const awo_penalties_t* pen, int64_t lo, int64_t hi);
 
 /* ---- oracle/cigar_check.c : restates wfa.rs:105-176 + validation_simple.rs:73-161 ---- */
 /* Returns 0 when the op bytes consume exactly both sequences, every 'M' column really

@@ -71,6 +71,13 @@ def lib():
         L.awo_align_unidirectional.argtypes = sig
         L.awo_gotoh_penalty.restype = C.c_int64
         L.awo_gotoh_penalty.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(Penalties)]
+        L.awo_gotoh_penalty_banded.restype = C.c_int64
+        L.awo_gotoh_penalty_banded.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(Penalties), C.c_int64]
+        L.awo_gotoh_penalty_band.restype = C.c_int64
+        L.awo_gotoh_penalty_band.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(Penalties), C.c_int64,
+                                             C.c_int64]
+        L.awo_gotoh_band.argtypes = [C.c_int, C.c_int, C.POINTER(Penalties), C.c_int64, C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int64)]
         L.awo_cigar_check.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.c_int,
                                       C.POINTER(Penalties), C.POINTER(C.c_int64)]
         for fn in (L.awo_all_pairs, L.awo_all_pairs_fast):
@@ -126,6 +133,59 @@ def gotoh_penalty(pattern, text, scores):
     pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
     pattern, text = bytes(pattern), bytes(text)
     return lib().awo_gotoh_penalty(pattern, len(pattern), text, len(text), C.byref(pen))
+
+
+NO_BOUND = (1 << 62)
+
+
+def gotoh_penalty_banded(pattern, text, scores, bound=None):
+    """The Gotoh DP on the diagonals an alignment of cost <= bound can visit (oracle/gotoh.c): the optimum when it is
+    <= bound, else bound + 1.  bound=None: no bound (the band still never exceeds what some alignment of the pair costs)."""
+    pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+    pattern, text = bytes(pattern), bytes(text)
+    r = lib().awo_gotoh_penalty_banded(pattern, len(pattern), text, len(text), C.byref(pen),
+                                       NO_BOUND if bound is None else int(bound))
+    if r < 0 and (bound is None or bound >= 0):
+        raise MemoryError("banded Gotoh DP: allocation failed")
+    return r
+
+
+def gotoh_band(plen, tlen, scores, bound):
+    """(lo, hi): the diagonals k = j - i that gotoh_penalty_banded searches for this bound; None if the forced gap alone
+    costs more."""
+    pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+    lo, hi = C.c_int64(0), C.c_int64(0)
+    if lib().awo_gotoh_band(int(plen), int(tlen), C.byref(pen), int(bound), C.byref(lo), C.byref(hi)) != 0:
+        return None
+    return lo.value, hi.value
+
+
+def gotoh_penalty_band(pattern, text, scores, lo, hi):
+    """The cheapest alignment whose path stays on diagonals lo <= j - i <= hi (>= 2**50 when there is none)."""
+    pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+    pattern, text = bytes(pattern), bytes(text)
+    return lib().awo_gotoh_penalty_band(pattern, len(pattern), text, len(text), C.byref(pen), int(lo), int(hi))
+
+
+_POOL = None
+
+
+def dp_pool():
+    """A thread pool for gotoh_penalty_banded calls (ctypes releases the GIL for the call, so they run in parallel):
+    at most 16 threads, and never more than the CPUs this process may run on."""
+    global _POOL
+    if _POOL is None:
+        from concurrent.futures import ThreadPoolExecutor
+        lib()
+        _POOL = ThreadPoolExecutor(max_workers=min(16, len(os.sched_getaffinity(0))))
+    return _POOL
+
+
+def gotoh_penalty_banded_many(jobs):
+    """Runs gotoh_penalty_banded(pattern, text, scores, bound) for every tuple of jobs on dp_pool(); returns a future
+    per job, in order."""
+    pool = dp_pool()
+    return [pool.submit(gotoh_penalty_banded, *job) for job in jobs]
 
 
 def cigar_check(cigar, pattern, text, scores):

@@ -159,6 +159,12 @@ REJECTED = [(n, s) for n, s in PENALTY_SPACE if not derive(s).accepted]
 BY_NAME = dict(PENALTY_SPACE)
 
 
+# one representative per derived class: ring 4, T = 2, the usual 2-piece sets with and without chained sweeps, inverted,
+# crossing, equal pieces, ring 128 at scope 125, ring 256 with one sweep and with three chained, and sb = 4000
+FLAVOUR_SETS = ("edit_unit", "affine_T2_e2", "default_2p", "2p_chain2", "2p_inverted", "2p_crossing", "2p_equal",
+                "scope125", "ring256_scope123_e1", "ring256_2p_chain3", "sb4000")
+
+
 def scaled(scores, k):
     """Every score times k (match stays 0): every alignment's penalty is k times what it was."""
     return tuple(int(v) * k for v in scores)

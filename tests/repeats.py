@@ -156,6 +156,14 @@ SMALL = {
 }
 
 
+# (generator, seed): pairs on which breakpoint searches met inside a multi-step pass and were run again step by step
+# (awv_stats.restarts), found by a per-pair scan of 300 seeded repeat pairs on an MI355X -- restarts came up on about half
+# of the tandem, copy-number and microsatellite pairs and on nearly every long-exact-block pair
+RESTART_CASES = (("tandem", lambda rng: tandem(rng, total=(3000, 12000)), "restart/tandem/1"),
+                 ("exact_blocks", lambda rng: exact_blocks(rng), "restart/exact_blocks/0"),
+                 ("microsatellite", lambda rng: microsatellite(rng), "restart/microsatellite/48"))
+
+
 def path_cells(ops):
     """The DP cells (i, j) an alignment's path visits; ops are the oracle's op bytes (M/X consume both
     sequences, D the pattern, I the text)."""

@@ -14,6 +14,7 @@ import pytest
 
 import penalty_space as PS
 import repeats as R
+from long_pairs import row_width_pairs
 from util import check_against_oracle, mutate, rand_seq, random_pair
 
 pytestmark = pytest.mark.gpu
@@ -91,10 +92,7 @@ def test_parity_at_every_accepted_set(engine, oracle, request, name):
         e.close()
 
 
-# one representative per derived class: ring 4, T = 2, the usual 2-piece sets with and without chained sweeps, inverted,
-# crossing, equal pieces, ring 128 at scope 125, ring 256 with one sweep and with three chained, and sb = 4000
-FLAVOUR_SETS = ("edit_unit", "affine_T2_e2", "default_2p", "2p_chain2", "2p_inverted", "2p_crossing", "2p_equal",
-                "scope125", "ring256_scope123_e1", "ring256_2p_chain3", "sb4000")
+FLAVOUR_SETS = PS.FLAVOUR_SETS
 
 
 def flavour_inputs(name):
@@ -127,29 +125,13 @@ def test_flavour_matrix(oracle, flavour):
         e.close()
 
 
-def long_inputs():
-    """A 32-bit-row pair (both >= 32760), a wide16 pair (shorter < 32760, longer >= 32760) and a sixteen-wave pair
-    (length difference >= 16384), both orders of each."""
-    rng = random.Random("gpu-penalties/long")
-    a = rand_seq(rng, 33500)
-    b = mutate(a, 0.003, rng)
-    c = rand_seq(rng, 36000)
-    d = mutate(c[9000:12000], 0.01, rng)
-    g = rand_seq(rng, 3000)
-    h = mutate(g[:1500] + rand_seq(rng, 16500) + g[1500:], 0.003, rng)
-    assert min(len(a), len(b)) >= 32760 and min(len(c), len(d)) < 32760 <= max(len(c), len(d))
-    assert abs(len(g) - len(h)) >= 16384
-    seqs = [a, b, c, d, g, h]
-    return seqs, [(0, 1), (1, 0), (2, 3), (3, 2), (4, 5), (5, 4)]
-
-
 @pytest.mark.parametrize("name", FLAVOUR_SETS)
 def test_long_pairs_on_every_row_width(oracle, name):
     """32-bit rows, wide16 rows and the sixteen-wave flavour at each representative set (the engine's own routing), and the
     32-bit pair under one wave per pair: equal to the oracle."""
     from allwave_amd import ffi
     scores = PS.BY_NAME[name]
-    seqs, pairs = long_inputs()
+    seqs, pairs = row_width_pairs()
     e = _engine(0)
     try:
         check_cached(e, oracle, "long", seqs, pairs, scores)

@@ -125,12 +125,7 @@ def test_repeat_paths_reached(oracle):
         e.close()
 
 
-# (generator, seed): pairs on which breakpoint searches met inside a multi-step pass and were run again step by step
-# (awv_stats.restarts), found by a per-pair scan of 300 seeded repeat pairs on an MI355X -- restarts came up on about half
-# of the tandem, copy-number and microsatellite pairs and on nearly every long-exact-block pair
-RESTART_CASES = (("tandem", lambda rng: R.tandem(rng, total=(3000, 12000)), "restart/tandem/1"),
-                 ("exact_blocks", lambda rng: R.exact_blocks(rng), "restart/exact_blocks/0"),
-                 ("microsatellite", lambda rng: R.microsatellite(rng), "restart/microsatellite/48"))
+RESTART_CASES = R.RESTART_CASES
 
 
 @pytest.mark.parametrize("case", RESTART_CASES, ids=[c[0] for c in RESTART_CASES])
