@@ -45,8 +45,9 @@ HIP_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950"]
 # "iterative-maxocc": 1779-1785 ms against 1719-1737 ms).  Not for engine.hip: there it spills a lane
 # vector inside a pass loop of the 16-bit min(h, v) kernels (scratch/spill_audit.py).
 HIP_FLAGS_AWV = HIP_FLAGS + ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
-HIP_UNITS = (("engine.hip", HIP_FLAGS), ("kernels_awv.hip", HIP_FLAGS_AWV))
-HIP_SOURCES = [os.path.join(CSRC, f) for f in ("engine.hip", "kernels_awv.hip", "kernels_awv.hpp", "biwfa_device.hpp")] + [ABI_HEADER]
+HIP_UNITS = (("engine.hip", HIP_FLAGS), ("kernels_awv.hip", HIP_FLAGS_AWV), ("planner.hip", HIP_FLAGS))
+HIP_SOURCES = [os.path.join(CSRC, f) for f in ("engine.hip", "kernels_awv.hip", "kernels_awv.hpp", "biwfa_device.hpp", "planner.hip",
+                                               "planner_device.hpp")] + [ABI_HEADER]
 
 
 def _host_sources():
@@ -117,7 +118,7 @@ def build_hip(force=False, verbose=False):
     tmp = tempfile.mkdtemp(prefix="awv_build_%d_" % os.getpid())
     try:
         objs, procs = [], []
-        for (unit, _), cmd in zip(HIP_UNITS, compile_cmds):  # the two translation units compile side by side
+        for (unit, _), cmd in zip(HIP_UNITS, compile_cmds):  # the translation units compile side by side
             obj = os.path.join(tmp, unit.replace(".hip", ".o"))
             full = cmd + ["-o", obj]
             if verbose:

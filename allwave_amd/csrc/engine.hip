@@ -7,6 +7,7 @@
 #include "allwave_hip.h"
 // the device code, once per workgroup size: awv:: one wave per pair (throughput), awvw:: four waves per pair,
 // awvx:: sixteen waves per pair (one pair per CU: the few pairs a large length difference makes enormous)
+#include "planner_device.hpp"  // (the sketches and scratch of device pair planning, planner.hip)
 #include "kernels_awv.hpp"  // (AWV_THRU_WG; the awv:: kernels themselves are instantiated in kernels_awv.hip -- here only the types)
 #define AWV_NS awv
 #define AWV_WG AWV_THRU_WG
@@ -160,6 +161,7 @@ struct awv_engine {
   DevBuf<unsigned long long> d_counters;  // [0] work cursor, [1..] stats
   std::vector<uint8_t> h_cigar;
   awv_stats stats{};
+  awp::PlanState* plan = nullptr;  // planner.hip: sketches of `seqs` and planning scratch (released with a new set)
 };
 
 namespace {
@@ -936,6 +938,8 @@ int awv_engine_create(const awv_engine_config* cfg, awv_engine** out) {
 void awv_engine_destroy(awv_engine* e) {
   if (!e) return;
   (void)hipSetDevice(e->device);
+  awp::plan_state_release(e->plan);
+  e->plan = nullptr;
   e->seqs.release();
   e->ring_mem.release();
   e->hist_mem.release();
@@ -968,6 +972,8 @@ void awv_engine_destroy(awv_engine* e) {
 
 int awv_engine_set_sequences(awv_engine* e, int32_t n, const uint8_t* concat_bytes, const uint64_t* offsets) {
   if (!e) return fail(AWV_ERR_ARG, "null engine");
+  awp::plan_state_release(e->plan);  // (sketches of the previous set are stale)
+  e->plan = nullptr;
   AWV_GUARDED(return upload_seqset(e, e->seqs, n, concat_bytes, offsets);)
 }
 
@@ -1067,3 +1073,20 @@ int awv_engine_stats(const awv_engine* e, awv_stats* out) {
 }
 
 }  // extern "C"
+
+// ---- what planner.hip reads of an engine (planner_device.hpp) ----
+int awv_internal_view(awv_engine* e, awp::EngineView* v) {
+  if (!e || !v) return fail(AWV_ERR_ARG, "null engine");
+  v->device = e->device;
+  v->stream = e->stream;
+  v->n = e->seqs.n;
+  v->fwd = e->seqs.d_seq[0].p;
+  v->rc = e->seqs.d_seq[2].p;
+  v->off = e->seqs.d_off.p;
+  v->len = e->seqs.d_len.p;
+  v->len_host = e->seqs.len.data();
+  if (e->seqs.n == 0) return fail(AWV_ERR_STATE, "no sequence set: call awv_engine_set_sequences first");
+  return AWV_OK;
+}
+awp::PlanState*& awv_internal_plan(awv_engine* e) { return e->plan; }
+int awv_internal_fail(int code, const std::string& msg) { return fail(code, msg); }

@@ -293,11 +293,45 @@ AlignmentResult make_result(size_t qi, size_t ti, bool is_rev, const awv_result&
 }  // namespace
 
 AllPairIterator::AllPairIterator(const std::vector<Sequence>& sequences, AlignmentParams params)
+    : AllPairIterator(sequences, std::move(params), true) {}
+
+AllPairIterator::AllPairIterator(const std::vector<Sequence>& sequences, AlignmentParams params, bool enumerate)
     : sequences_(sequences), params_(std::move(params)), orientation_params_(AlignmentParams::edit_distance()) {
+  if (!enumerate) return;
   const size_t n = sequences.size();
   for (size_t i = 0; i < n; ++i)
     for (size_t j = 0; j < n; ++j)
       if (i != j) pairs_.emplace_back(i, j);  // iterator.rs:38-43 row-major, i != j
+}
+
+AllPairIterator AllPairIterator::with_options(const std::vector<Sequence>& sequences, AlignmentParams params, bool exclude_self,
+                                              bool use_mash_orientation, SparsificationStrategy s, int plan_device) {
+  if (plan_device < 0 || s.kind == SparsificationStrategy::None) {
+    AllPairIterator it = with_options(sequences, std::move(params), exclude_self, use_mash_orientation, std::move(s));
+    return it.with_plan_device(plan_device);
+  }
+  // the same lists as below, planned on the device without enumerating all N^2 pairs on the host first
+  AllPairIterator it(sequences, std::move(params), false);
+  it.exclude_self_ = exclude_self;
+  it.plan_device_ = plan_device;
+  const size_t n = sequences.size();
+  switch (s.kind) {
+    case SparsificationStrategy::None: break;
+    case SparsificationStrategy::Random:
+      it.pairs_ = planner::apply_random_sparsification(sequences, s.value, exclude_self, plan_device);
+      break;
+    case SparsificationStrategy::Auto:
+      it.pairs_ = planner::apply_random_sparsification(sequences, planner::compute_connectivity_probability(n, 0.95), exclude_self, plan_device);
+      break;
+    case SparsificationStrategy::Connectivity:
+      it.pairs_ = planner::apply_random_sparsification(sequences, planner::compute_connectivity_probability(n, s.value), exclude_self, plan_device);
+      break;
+    case SparsificationStrategy::TreeSampling:
+      it.pairs_ = planner::extract_tree_pairs(sequences, s.k_nearest, s.k_farthest, s.random_fraction, s.kmer_size.value_or(15), plan_device);
+      break;
+  }
+  it.orientation_ = use_mash_orientation ? Orientation::Mash : Orientation::Wfa;
+  return it;
 }
 
 AllPairIterator AllPairIterator::with_options(const std::vector<Sequence>& sequences, AlignmentParams params,
@@ -330,6 +364,7 @@ AllPairIterator AllPairIterator::with_options(const std::vector<Sequence>& seque
   return it;
 }
 
+AllPairIterator& AllPairIterator::with_plan_device(int plan_device) { plan_device_ = plan_device < 0 ? -1 : plan_device; return *this; }
 AllPairIterator& AllPairIterator::with_orientation_params(AlignmentParams p) { orientation_params_ = std::move(p); return *this; }
 AllPairIterator& AllPairIterator::with_orientation(Orientation o) { orientation_ = o; return *this; }
 AllPairIterator& AllPairIterator::with_device(int device) { devices_.assign(1, device); return *this; }
@@ -399,7 +434,7 @@ AllPairIterator& AllPairIterator::with_shard(size_t rank, size_t world) {
 }
 
 AllPairIterator AllPairIterator::with_sparsification(SparsificationStrategy strategy) const {  // iterator.rs:101-110
-  AllPairIterator it = with_options(sequences_, params_, exclude_self_, orientation_ == Orientation::Mash, std::move(strategy));
+  AllPairIterator it = with_options(sequences_, params_, exclude_self_, orientation_ == Orientation::Mash, std::move(strategy), plan_device_);
   if (orientation_ == Orientation::ForwardOnly) it.orientation_ = Orientation::ForwardOnly;  // (this build's extension survives)
   it.devices_ = devices_;
   it.min_batch_pairs_ = min_batch_pairs_;
@@ -581,7 +616,7 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
             : std::vector<std::vector<size_t>>(1);
   std::vector<uint8_t> mash_rev;
   if (orientation_ == Orientation::Mash)  // alignment.rs:69-94 (host threads: the CLI's -t)
-    mash_rev = planner::orient_pairs_mash(sequences_, plist, count, threads_ > 0 ? threads_ : planner::host_threads());
+    mash_rev = planner::orient_pairs_mash(sequences_, plist, count, threads_ > 0 ? threads_ : planner::host_threads(), plan_device_);
   // slot number of every entry on its device, and how many slots each device has in this run
   std::map<int, int> per_device;
   std::vector<int> slot_no(S);

@@ -113,6 +113,13 @@ class AllPairIterator {  // iterator.rs:12-171
   AllPairIterator(const std::vector<Sequence>& sequences, AlignmentParams params);  // ::new
   static AllPairIterator with_options(const std::vector<Sequence>& sequences, AlignmentParams params,
                                       bool exclude_self, bool use_mash_orientation, SparsificationStrategy s);
+  // the same, the pair list planned on the HIP device `plan_device` (planner.hpp's device variants: the same list, byte for byte;
+  // AlignmentError without that device); plan_device < 0: on the host, as above.  The plan device also runs mash orientation.
+  static AllPairIterator with_options(const std::vector<Sequence>& sequences, AlignmentParams params, bool exclude_self,
+                                      bool use_mash_orientation, SparsificationStrategy s, int plan_device);
+  // the device mash orientation and with_sparsification plan on from now on (< 0: the host, the default); the current list stays
+  AllPairIterator& with_plan_device(int plan_device);
+  int plan_device() const { return plan_device_; }
   AllPairIterator& with_orientation_params(AlignmentParams p);
   // iterator.rs:101-110: a NEW iterator over the same sequences / params / exclude_self / orientation choice with the pair
   // list planned again under `strategy` -- through with_options, exactly like the reference, so the orientation params go
@@ -185,8 +192,10 @@ class AllPairIterator {  // iterator.rs:12-171
   // serialise it.
   void run(size_t first, size_t count, const BatchCb& batch_cb, EngineCall call = {false, -1});
   void run(const BatchCb& batch_cb, EngineCall call = {false, -1}) { run(0, pairs_.size(), batch_cb, call); }
+  AllPairIterator(const std::vector<Sequence>& sequences, AlignmentParams params, bool enumerate);  // enumerate = false: no pairs
   const std::vector<Sequence>& sequences_;
   AlignmentParams params_, orientation_params_;
+  int plan_device_ = -1;
   bool exclude_self_ = true;
   Orientation orientation_ = Orientation::Wfa;
   std::vector<int> devices_{0};

@@ -328,6 +328,77 @@ int awh_orient_mash(int n, const char* const* ids, const uint8_t* bytes, const u
   return 0;
 }
 
+// ---- device planning (planner.hpp's device variants; they fail without a GPU: -1 and the message in err) ----
+// awh_mash_matrix on `device`
+int awh_mash_matrix_gpu(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, int k, int device, double* out,
+                        char* err, size_t cap) {
+  try {
+    const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
+    const auto m = planner::compute_distance_matrix(seqs, (size_t)k, 1000, device);
+    for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) out[i * n + j] = m[i][j];
+    return 0;
+  } catch (const std::exception& e) { set_err(err, cap, e.what()); return -1; }
+}
+
+// awh_plan_pairs with the list planned on `device` (AllPairIterator::with_options(..., plan_device))
+int awh_plan_pairs_gpu(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* sparsification,
+                       int exclude_self, int device, int64_t** out, size_t* npairs, char* err, size_t cap) {
+  try {
+    const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
+    const bool resparsify = (exclude_self & 2) != 0;
+    AllPairIterator it0 = AllPairIterator::with_options(seqs, AlignmentParams{}, (exclude_self & 1) != 0, false,
+                                                       resparsify ? SparsificationStrategy{} : SparsificationStrategy::parse(sparsification),
+                                                       device);
+    AllPairIterator it = resparsify ? it0.with_sparsification(SparsificationStrategy::parse(sparsification)) : it0;
+    const auto& p = it.get_pairs();
+    *out = (int64_t*)malloc(sizeof(int64_t) * 2 * (p.size() + 1));
+    for (size_t i = 0; i < p.size(); ++i) { (*out)[2 * i] = (int64_t)p[i].first; (*out)[2 * i + 1] = (int64_t)p[i].second; }
+    *npairs = p.size();
+    return 0;
+  } catch (const std::invalid_argument& e) { set_err(err, cap, e.what()); return -1;  // (a bad -p string)
+  } catch (const std::exception& e) { set_err(err, cap, e.what()); return -2; }     // (the device)
+}
+
+// awh_orient_mash on `device`
+int awh_orient_mash_gpu(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const int64_t* pairs, size_t npairs,
+                        int device, uint8_t* is_rev, char* err, size_t cap) {
+  try {
+    const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
+    std::vector<std::pair<size_t, size_t>> p(npairs);
+    for (size_t i = 0; i < npairs; ++i) p[i] = {(size_t)pairs[2 * i], (size_t)pairs[2 * i + 1]};
+    const auto r = planner::orient_pairs_mash(seqs, p.data(), p.size(), 8, device);
+    if (npairs) memcpy(is_rev, r.data(), npairs);
+    return 0;
+  } catch (const std::exception& e) { set_err(err, cap, e.what()); return -1; }
+}
+
+// sketches of every sequence (planner::sketch_all; kind 0 canonical, 1 forward, 2 reverse complement; device < 0: the host
+// code): offsets_out = malloc'ed n + 1 offsets, hashes_out = malloc'ed hashes
+int awh_sketch(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, int k, int s, int kind, int device,
+               uint64_t** offsets_out, uint64_t** hashes_out, char* err, size_t cap) {
+  try {
+    if (kind < 0 || kind > 2) throw std::invalid_argument("sketch: kind must be 0, 1 or 2");
+    if (k < 0 || s < 0) throw std::invalid_argument("sketch: k and s must be >= 0");
+    const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
+    const auto sk = planner::sketch_all(seqs, (planner::SketchKind)kind, (size_t)k, (size_t)s, device);
+    *offsets_out = (uint64_t*)malloc(sizeof(uint64_t) * ((size_t)n + 1));
+    (*offsets_out)[0] = 0;
+    for (int i = 0; i < n; ++i) (*offsets_out)[i + 1] = (*offsets_out)[i] + sk[i].size();
+    *hashes_out = (uint64_t*)malloc(sizeof(uint64_t) * ((*offsets_out)[n] + 1));
+    for (int i = 0; i < n; ++i)
+      if (!sk[i].empty()) memcpy(*hashes_out + (*offsets_out)[i], sk[i].data(), sk[i].size() * sizeof(uint64_t));
+    return 0;
+  } catch (const std::exception& e) { set_err(err, cap, e.what()); return -1; }
+}
+
+// planner::keep_threshold: keep iff keep_all or h < the returned threshold
+uint64_t awh_keep_threshold(double fraction, int* keep_all) {
+  bool all = false;
+  const uint64_t t = planner::keep_threshold(fraction, &all);
+  *keep_all = all ? 1 : 0;
+  return t;
+}
+
 // shard of every pair under the cost-balanced (LPT) partition AllPairIterator::with_shard uses; cost_out (nullable)
 // receives the predicted costs
 int awh_shard_pairs(const int64_t* pairs, size_t npairs, const int64_t* lens, size_t nseq, const char* scores, size_t world, uint32_t* shard_out,

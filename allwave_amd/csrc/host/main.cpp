@@ -35,6 +35,7 @@ struct Args {
   bool score_only = false;  // --score-only: one line `qname qlen tname tlen strand penalty` per pair instead of PAF
   long max_penalty = -1;    // --max-penalty N (with --score-only): pairs whose penalty exceeds N are left out
   bool have_max_penalty = false;
+  int plan_device = -1;     // --plan-device N: plan the pair list, the mash matrix and mash orientation on device N
 };
 
 [[noreturn]] void die(const std::string& m, int code = 2) {
@@ -184,6 +185,11 @@ int main(int argc, char** argv) {
     else if (k == "--device") { a.device = atoi(val().c_str()); a.have_device = true; }
     else if (k == "--devices") { a.devices = val(); a.have_devices = true; }
     else if (k == "--score-only") a.score_only = true;
+    else if (k == "--plan-device") {
+      const std::string v = val();
+      if (v.empty() || v.size() > 6 || v.find_first_not_of("0123456789") != std::string::npos) die("--plan-device expects a device ordinal N >= 0");
+      a.plan_device = atoi(v.c_str());
+    }
     else if (k == "--max-penalty") {
       const std::string v = val();
       char* end = nullptr;
@@ -203,12 +209,14 @@ int main(int argc, char** argv) {
     else if (k == "-h" || k == "--help") {
       std::cout << "usage: allwave_hip -i in.fa [-o out.paf] [-s m,x,o,e[,o2,e2] | -x ANI] [-p none|auto|random:f|giant:p|tree:n:f:r[:k]]\n"
                    "                   [-t threads] [--wfa-orientation|--forward-only] [-k prefixes | -e prefixes] [--mash-matrix]\n"
-                   "                   [--device N | --devices LIST] [--shard R/N] [--score-only [--max-penalty N]]\n"
+                   "                   [--device N | --devices LIST] [--shard R/N] [--score-only [--max-penalty N]] [--plan-device N]\n"
                    "  --devices LIST   align on several devices in this process: ordinals and ranges, e.g. 0,1,2 / 0-7 / all;\n"
                    "                   an ordinal may repeat (0,0: two engines on device 0); -t is shared out among them\n"
                    "  --score-only     no PAF: one tab-separated line per pair, `qname qlen tname tlen strand penalty`, in pair-list\n"
                    "                   order (the optimal penalty without a CIGAR; `*` for a pair that failed)\n"
-                   "  --max-penalty N  with --score-only: stop searching a pair once its penalty is proved above N and leave it out\n";
+                   "  --max-penalty N  with --score-only: stop searching a pair once its penalty is proved above N and leave it out\n"
+                   "  --plan-device N  plan on device N: --mash-matrix, the -p pair list and mash orientation (the same output as\n"
+                   "                   the host planner; with --shard every rank plans the whole list on its own plan device)\n";
       return 0;
     } else die("unexpected argument: " + k);
   }
@@ -248,7 +256,19 @@ int main(int argc, char** argv) {
   planner::set_host_threads(a.threads);  // -t: sketching, mash orientation, PAF formatting
   if (a.mash_matrix) {  // main.rs:281-293
     const size_t k = strategy.kind == SparsificationStrategy::TreeSampling && strategy.kmer_size ? *strategy.kmer_size : 15;
-    std::cout << planner::format_distance_matrix(sequences, planner::compute_distance_matrix(sequences, k, 1000));
+    if (a.plan_device < 0) {
+      std::cout << planner::format_distance_matrix(sequences, planner::compute_distance_matrix(sequences, k, 1000));
+      return 0;
+    }
+    try {  // streamed a block of rows at a time
+      planner::write_distance_matrix(sequences, k, 1000, a.plan_device, [](const std::string& block) {
+        std::cout.write(block.data(), (std::streamsize)block.size());
+        if (!std::cout) throw std::runtime_error("write error on the matrix output");
+      });
+      std::cout.flush();
+    } catch (const std::exception& e) {
+      die(e.what(), 1);
+    }
     return 0;
   }
 
@@ -261,7 +281,7 @@ int main(int argc, char** argv) {
   try { params = parse_scores(scores); } catch (const std::exception& e) { die(e.what(), 1); }
 
   try {
-    AllPairIterator it = AllPairIterator::with_options(sequences, params, true, !a.wfa_orientation, strategy);
+    AllPairIterator it = AllPairIterator::with_options(sequences, params, true, !a.wfa_orientation, strategy, a.plan_device);
     if (a.forward_only) it.with_orientation(Orientation::ForwardOnly);
     it.with_devices(devices);
     it.with_shard((size_t)a.shard_rank, (size_t)a.shard_world);

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <queue>
 #include <cmath>
 #include <cstdio>
@@ -161,16 +162,22 @@ std::vector<std::vector<double>> compute_distance_matrix(const std::vector<Seque
   return m;
 }
 
-std::string format_distance_matrix(const std::vector<Sequence>& seqs, const std::vector<std::vector<double>>& m) {
+static std::string matrix_header(const std::vector<Sequence>& seqs) {
   std::string out = "sequence";  // mash.rs:168-184
   for (const auto& s : seqs) { out += "\t"; out += s.id; }
   out += "\n";
+  return out;
+}
+static void append_matrix_row(std::string& out, const std::string& id, const double* d, size_t n) {
   char buf[64];
-  for (size_t i = 0; i < m.size(); ++i) {
-    out += seqs[i].id;
-    for (double d : m[i]) { snprintf(buf, sizeof(buf), "\t%.6f", d); out += buf; }
-    out += "\n";
-  }
+  out += id;
+  for (size_t j = 0; j < n; ++j) { snprintf(buf, sizeof(buf), "\t%.6f", d[j]); out += buf; }
+  out += "\n";
+}
+
+std::string format_distance_matrix(const std::vector<Sequence>& seqs, const std::vector<std::vector<double>>& m) {
+  std::string out = matrix_header(seqs);
+  for (size_t i = 0; i < m.size(); ++i) append_matrix_row(out, seqs[i].id, m[i].data(), m[i].size());
   return out;
 }
 
@@ -227,6 +234,243 @@ std::vector<std::pair<size_t, size_t>> extract_tree_pairs(const std::vector<Sequ
   return all;
 }
 
+
+// ---- device planning ------------------------------------------------------------------------------------------------------
+namespace {
+// one engine on the planning device for the duration of a call (no alignment arenas: it only sketches and hashes)
+struct PlanEngine {
+  awv_engine* e = nullptr;
+  explicit PlanEngine(int device) {
+    awv_engine_config cfg{};
+    cfg.device = device;
+    if (awv_engine_create(&cfg, &e) != AWV_OK)
+      throw AlignmentError("plan device " + std::to_string(device) + ": " + awv_last_error());
+  }
+  ~PlanEngine() { awv_engine_destroy(e); }
+  PlanEngine(const PlanEngine&) = delete;
+  PlanEngine& operator=(const PlanEngine&) = delete;
+  static void check(int rc, const char* what) {
+    if (rc != AWV_OK) throw AlignmentError(std::string(what) + ": " + awv_last_error());
+  }
+  void upload(const std::vector<Sequence>& seqs) {
+    if (seqs.size() > (size_t)INT32_MAX) throw AlignmentError("device planning: more than 2^31 - 1 sequences");
+    std::vector<uint64_t> offs(seqs.size() + 1, 0);
+    for (size_t i = 0; i < seqs.size(); ++i) offs[i + 1] = offs[i] + seqs[i].seq.size();
+    std::vector<uint8_t> cat(offs.back() + 1);
+    for (size_t i = 0; i < seqs.size(); ++i)
+      if (!seqs[i].seq.empty()) memcpy(cat.data() + offs[i], seqs[i].seq.data(), seqs[i].seq.size());
+    check(awv_engine_set_sequences(e, (int32_t)seqs.size(), cat.data(), offs.data()), "awv_engine_set_sequences");
+  }
+  std::vector<uint32_t> sketch(SketchKind kind, size_t k, size_t s, size_t n) {
+    std::vector<uint32_t> sizes(n);
+    check(awv_sketch(e, (int32_t)kind, (int32_t)k, (int32_t)s, sizes.data()), "awv_sketch");
+    return sizes;
+  }
+  // bitmap rows of `words` 32-bit words: bit (i, j) set when the pair passes keep_pair(fraction)
+  void keep_bits(const std::vector<Sequence>& seqs, double fraction, bool include_diag, std::vector<uint32_t>& bitmap) {
+    std::vector<uint64_t> offs(seqs.size() + 1, 0);
+    std::string ids;
+    for (size_t i = 0; i < seqs.size(); ++i) { ids += seqs[i].id; offs[i + 1] = ids.size(); }
+    bool all = false;
+    const uint64_t t = keep_threshold(fraction, &all);
+    check(awv_keep_pairs(e, (int32_t)seqs.size(), (const uint8_t*)ids.data(), offs.data(), t, all ? 1 : 0, include_diag ? 1 : 0,
+                         bitmap.data()),
+          "awv_keep_pairs");
+  }
+};
+
+inline double jaccard_counts(size_t inter, size_t a, size_t b) {  // jaccard() from the counts (the same arithmetic)
+  const size_t uni = a + b - inter;
+  return uni == 0 ? 0.0 : (double)inter / (double)uni;
+}
+inline bool device_sketch_ok(size_t k, size_t s) { return k >= 1 && k <= AWV_PLAN_MAX_K && s >= 1 && s <= AWV_PLAN_MAX_S; }
+
+// rows of counts at a time: at most 16 M entries (32 MiB) per block
+inline size_t row_block(size_t n) { return std::max<size_t>(1, std::min<size_t>(n, ((size_t)16 << 20) / std::max<size_t>(n, 1))); }
+
+// the set bits of an n x n bitmap, row-major
+std::vector<std::pair<size_t, size_t>> bitmap_pairs(const std::vector<uint32_t>& bitmap, size_t n) {
+  const size_t words = (n + 31) / 32;
+  size_t total = 0;
+  for (uint32_t w : bitmap) total += (size_t)__builtin_popcount(w);
+  std::vector<std::pair<size_t, size_t>> out;
+  out.reserve(total);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t w = 0; w < words; ++w)
+      for (uint32_t x = bitmap[i * words + w]; x; x &= x - 1) out.emplace_back(i, 32 * w + (size_t)__builtin_ctz(x));
+  return out;
+}
+}  // namespace
+
+std::vector<std::vector<uint64_t>> sketch_all(const std::vector<Sequence>& seqs, SketchKind kind, size_t k, size_t sketch_size,
+                                              int device) {
+  const size_t n = seqs.size();
+  std::vector<std::vector<uint64_t>> out(n);
+  auto host = [&]() {
+    parallel_for(n, host_threads(), [&](size_t i) {
+      out[i] = kind == SketchKind::Canonical ? sketch_sequence_canonical(seqs[i].seq, k, sketch_size)
+               : kind == SketchKind::Forward ? sketch_sequence_stranded(seqs[i].seq, k, sketch_size)
+                                             : sketch_sequence_stranded(reverse_complement(seqs[i].seq), k, sketch_size);
+    });
+    return out;
+  };
+  if (device < 0) return host();
+  PlanEngine pe(device);
+  if (!device_sketch_ok(k, sketch_size)) return host();
+  if (n == 0) return out;
+  pe.upload(seqs);
+  pe.sketch(kind, k, sketch_size, n);
+  std::vector<uint64_t> offs(n + 1);
+  PlanEngine::check(awv_sketch_copy(pe.e, (int32_t)kind, offs.data(), nullptr), "awv_sketch_copy");
+  std::vector<uint64_t> all(offs[n] + 1);
+  PlanEngine::check(awv_sketch_copy(pe.e, (int32_t)kind, nullptr, all.data()), "awv_sketch_copy");
+  for (size_t i = 0; i < n; ++i) out[i].assign(all.begin() + (ptrdiff_t)offs[i], all.begin() + (ptrdiff_t)offs[i + 1]);
+  return out;
+}
+
+uint64_t keep_threshold(double fraction, bool* keep_all) {
+  // keep_pair's predicate, the same expression: monotone in h, so {h : kept} = [0, T) for the least h it rejects
+  auto kept = [&](uint64_t h) { return (double)h / (double)UINT64_MAX < fraction; };
+  *keep_all = kept(UINT64_MAX);
+  if (*keep_all) return UINT64_MAX;
+  uint64_t lo = 0, hi = UINT64_MAX;  // kept(hi) is false
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (kept(mid)) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+static void distance_rows(PlanEngine& pe, const std::vector<uint32_t>& sz, size_t k, size_t n,
+                          const std::function<void(size_t row0, size_t nrows, const std::vector<double>& d)>& take) {
+  const size_t R = row_block(n);
+  std::vector<uint16_t> inter(R * n);
+  std::vector<double> d(R * n);
+  for (size_t r0 = 0; r0 < n; r0 += R) {
+    const size_t nr = std::min(R, n - r0);
+    PlanEngine::check(awv_sketch_rows(pe.e, AWV_SK_CANONICAL, (int32_t)r0, (int32_t)nr, inter.data()), "awv_sketch_rows");
+    for (size_t r = 0; r < nr; ++r) {
+      const size_t i = r0 + r;
+      for (size_t j = 0; j < n; ++j)
+        d[r * n + j] = j == i ? 0.0 : mash_distance(jaccard_counts(inter[r * n + j], sz[i], sz[j]), k);
+    }
+    take(r0, nr, d);
+  }
+}
+
+std::vector<std::vector<double>> compute_distance_matrix(const std::vector<Sequence>& seqs, size_t k, size_t sketch_size, int device) {
+  if (device < 0) return compute_distance_matrix(seqs, k, sketch_size);
+  PlanEngine pe(device);
+  if (!device_sketch_ok(k, sketch_size)) return compute_distance_matrix(seqs, k, sketch_size);
+  const size_t n = seqs.size();
+  std::vector<std::vector<double>> m(n, std::vector<double>(n, 0.0));
+  if (n == 0) return m;
+  pe.upload(seqs);
+  const std::vector<uint32_t> sz = pe.sketch(SketchKind::Canonical, k, sketch_size, n);
+  distance_rows(pe, sz, k, n, [&](size_t r0, size_t nr, const std::vector<double>& d) {
+    for (size_t r = 0; r < nr; ++r) std::copy(d.begin() + (ptrdiff_t)(r * n), d.begin() + (ptrdiff_t)((r + 1) * n), m[r0 + r].begin());
+  });
+  return m;
+}
+
+void write_distance_matrix(const std::vector<Sequence>& seqs, size_t k, size_t sketch_size, int device,
+                           const std::function<void(const std::string&)>& sink) {
+  if (device < 0) { sink(format_distance_matrix(seqs, compute_distance_matrix(seqs, k, sketch_size))); return; }
+  PlanEngine pe(device);
+  if (!device_sketch_ok(k, sketch_size)) { sink(format_distance_matrix(seqs, compute_distance_matrix(seqs, k, sketch_size))); return; }
+  const size_t n = seqs.size();
+  sink(matrix_header(seqs));
+  if (n == 0) return;
+  pe.upload(seqs);
+  const std::vector<uint32_t> sz = pe.sketch(SketchKind::Canonical, k, sketch_size, n);
+  std::vector<std::string> text;
+  distance_rows(pe, sz, k, n, [&](size_t r0, size_t nr, const std::vector<double>& d) {
+    text.assign(nr, std::string());  // (formatting is most of the host's work: spread over the host threads)
+    parallel_for(nr, host_threads(), [&](size_t r) { append_matrix_row(text[r], seqs[r0 + r].id, d.data() + r * n, n); });
+    std::string block;
+    for (const std::string& t : text) block += t;
+    sink(block);
+  });
+}
+
+std::vector<std::pair<size_t, size_t>> apply_random_sparsification(const std::vector<Sequence>& seqs, double keep_fraction,
+                                                                   bool exclude_self, int device) {
+  const size_t n = seqs.size();
+  if (device < 0) {
+    std::vector<std::pair<size_t, size_t>> all;
+    for (size_t i = 0; i < n; ++i)
+      for (size_t j = 0; j < n; ++j)
+        if (!exclude_self || i != j) all.emplace_back(i, j);
+    return apply_random_sparsification(std::move(all), keep_fraction, seqs);
+  }
+  PlanEngine pe(device);
+  if (n == 0) return {};
+  std::vector<uint32_t> bitmap(n * ((n + 31) / 32), 0);
+  pe.keep_bits(seqs, keep_fraction, !exclude_self, bitmap);
+  return bitmap_pairs(bitmap, n);
+}
+
+std::vector<std::pair<size_t, size_t>> extract_tree_pairs(const std::vector<Sequence>& seqs, size_t k_nearest, size_t k_farthest,
+                                                          double random_fraction, size_t kmer_size, int device) {
+  if (device < 0) return extract_tree_pairs(seqs, k_nearest, k_farthest, random_fraction, kmer_size);
+  PlanEngine pe(device);
+  const size_t n = seqs.size();
+  if (n < 2) return {};
+  // the integer ranking puts J = 0 (distance 1.0) behind every J > 0: it equals the host's order when the smallest
+  // positive Jaccard of two sketches of <= 1,000 hashes, 1 / 1,999, is still nearer than 1.0 (k >= 7)
+  const bool ranked_ok = device_sketch_ok(kmer_size, 1000) && mash_distance(1.0 / 1999.0, kmer_size) < 1.0;
+  if (k_nearest > AWV_PLAN_MAX_KNN || k_farthest > AWV_PLAN_MAX_KNN || ((k_nearest || k_farthest) && !ranked_ok))
+    return extract_tree_pairs(seqs, k_nearest, k_farthest, random_fraction, kmer_size);
+  const size_t words = (n + 31) / 32;
+  std::vector<uint32_t> bitmap(n * words, 0);
+  if (random_fraction > 0.0) pe.keep_bits(seqs, random_fraction, false, bitmap);
+  if (k_nearest > 0 || k_farthest > 0) {
+    pe.upload(seqs);
+    pe.sketch(SketchKind::Canonical, kmer_size, 1000, n);
+    std::vector<int32_t> nearest(n * k_nearest + 1), farthest(n * k_farthest + 1);
+    PlanEngine::check(awv_sketch_knn(pe.e, AWV_SK_CANONICAL, (int32_t)k_nearest, (int32_t)k_farthest, nearest.data(), farthest.data()),
+                      "awv_sketch_knn");
+    auto mark = [&](const std::vector<int32_t>& v, size_t k) {
+      for (size_t i = 0; i < n; ++i)
+        for (size_t t = 0; t < k; ++t) {
+          const int32_t j = v[i * k + t];
+          if (j >= 0 && (size_t)j < n) bitmap[i * words + (size_t)j / 32] |= 1u << (j & 31);
+        }
+    };
+    mark(nearest, k_nearest);
+    mark(farthest, k_farthest);
+  }
+  return bitmap_pairs(bitmap, n);
+}
+
+std::vector<uint8_t> orient_pairs_mash(const std::vector<Sequence>& seqs, const std::pair<size_t, size_t>* pairs, size_t npairs,
+                                       int threads, int device) {
+  if (device < 0) return orient_pairs_mash(seqs, pairs, npairs, threads);
+  constexpr size_t K = 15, S = 1000;  // alignment.rs:70-75
+  PlanEngine pe(device);
+  std::vector<uint8_t> is_rev(npairs, 0);
+  if (npairs == 0) return is_rev;
+  const size_t n = seqs.size();
+  std::vector<int32_t> q(npairs), t(npairs);
+  for (size_t p = 0; p < npairs; ++p) {
+    if (pairs[p].first >= n || pairs[p].second >= n) throw AlignmentError("orient_pairs_mash: sequence index out of range");
+    q[p] = (int32_t)pairs[p].first;
+    t[p] = (int32_t)pairs[p].second;
+  }
+  pe.upload(seqs);
+  const std::vector<uint32_t> sf = pe.sketch(SketchKind::Forward, K, S, n), sr = pe.sketch(SketchKind::RevComp, K, S, n);
+  std::vector<uint16_t> cf(npairs), cr(npairs);
+  PlanEngine::check(awv_sketch_pair_counts(pe.e, AWV_SK_FORWARD, AWV_SK_FORWARD, q.data(), t.data(), (int64_t)npairs, cf.data()),
+                    "awv_sketch_pair_counts");
+  PlanEngine::check(awv_sketch_pair_counts(pe.e, AWV_SK_REVCOMP, AWV_SK_FORWARD, q.data(), t.data(), (int64_t)npairs, cr.data()),
+                    "awv_sketch_pair_counts");
+  parallel_for(npairs, threads, [&](size_t p) {
+    const double jf = jaccard_counts(cf[p], sf[q[p]], sf[t[p]]), jr = jaccard_counts(cr[p], sr[q[p]], sf[t[p]]);
+    is_rev[p] = jf >= jr ? 0 : 1;  // forward wins ties (alignment.rs:89)
+  });
+  return is_rev;
+}
 
 double predicted_pair_cost(size_t qlen, size_t tlen, const AlignmentParams& params) {
   const double lo = (double)std::min(qlen, tlen), g = (double)(qlen > tlen ? qlen - tlen : tlen - qlen);

@@ -8,6 +8,7 @@
 #pragma once
 
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -46,6 +47,31 @@ std::vector<std::pair<size_t, size_t>> apply_random_sparsification(std::vector<s
 std::vector<std::pair<size_t, size_t>> build_knn_graph(const std::vector<std::vector<double>>& d, size_t k, bool farthest);
 std::vector<std::pair<size_t, size_t>> extract_tree_pairs(const std::vector<Sequence>& seqs, size_t k_nearest,
                                                           size_t k_farthest, double random_fraction, size_t kmer_size);
+
+// ---- device planning (csrc/planner.hip through awv_sketch* / awv_keep_pairs) ----------------------------------------------
+// Each variant below gives the same result, byte for byte, as the host function of the same name, on the HIP device
+// `device`.  Without a usable device they throw AlignmentError: there is no silent host fallback.  Outside the device limits
+// (k outside [1, 64], a sketch size outside [1, 4096], k_nearest or k_farthest above 64) they run the host code on the host.
+// Distances are computed here from the device's integer intersection counts with jaccard/mash_distance's own arithmetic;
+// kNN ranking and the keep test run on the device in exact integer arithmetic.
+enum class SketchKind { Canonical = AWV_SK_CANONICAL, Forward = AWV_SK_FORWARD, RevComp = AWV_SK_REVCOMP };
+// sketch of every sequence: canonical, stranded forward, or stranded of reverse_complement(seq); device < 0: on the host
+std::vector<std::vector<uint64_t>> sketch_all(const std::vector<Sequence>& seqs, SketchKind kind, size_t k, size_t sketch_size,
+                                              int device);
+// keep_pair's `(double)h / (double)UINT64_MAX < fraction` as an integer test: keep iff *keep_all or h < the returned T
+uint64_t keep_threshold(double fraction, bool* keep_all);
+std::vector<std::vector<double>> compute_distance_matrix(const std::vector<Sequence>& seqs, size_t k, size_t sketch_size, int device);
+// format_distance_matrix(seqs, compute_distance_matrix(seqs, k, sketch_size, device)), handed to `sink` a block of rows at a
+// time (never holds the N x N matrix)
+void write_distance_matrix(const std::vector<Sequence>& seqs, size_t k, size_t sketch_size, int device,
+                           const std::function<void(const std::string&)>& sink);
+// the pair list iterator.rs:38-46 enumerates (row-major; i != j when exclude_self) through apply_random_sparsification
+std::vector<std::pair<size_t, size_t>> apply_random_sparsification(const std::vector<Sequence>& seqs, double keep_fraction,
+                                                                   bool exclude_self, int device);
+std::vector<std::pair<size_t, size_t>> extract_tree_pairs(const std::vector<Sequence>& seqs, size_t k_nearest, size_t k_farthest,
+                                                          double random_fraction, size_t kmer_size, int device);
+std::vector<uint8_t> orient_pairs_mash(const std::vector<Sequence>& seqs, const std::pair<size_t, size_t>* pairs, size_t npairs,
+                                       int threads, int device);
 
 // ---- multi-GPU shards (what rayon's work stealing does for the reference, iterator.rs:222-233)
 // Predicted cost of one pair: cell-steps grow with the square of the optimal penalty, estimated from

@@ -1,0 +1,35 @@
+// planner_device.hpp -- what planner.hip (device pair planning) needs of an engine, and what engine.hip keeps for it.
+// The engine owns the resident sequence set; planner.hip owns the sketches built from it (one set per kind) and the
+// scratch of its kernels, released with the engine and whenever a new sequence set is handed over.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+struct awv_engine;
+
+namespace awp {
+
+struct PlanState;                   // planner.hip
+void plan_state_release(PlanState* p);  // frees its device buffers and the object itself (nullptr: nothing)
+
+// the engine's resident sequences: forward and reverse-complement copies in the engine's padded layout
+struct EngineView {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int32_t n = 0;
+  const uint8_t* fwd = nullptr;     // device
+  const uint8_t* rc = nullptr;      // device (host reverse_complement: non-ACGT -> 'N')
+  const uint64_t* off = nullptr;    // device, n + 1
+  const int32_t* len = nullptr;     // device, n
+  const int32_t* len_host = nullptr;  // host, n
+};
+
+}  // namespace awp
+
+// engine.hip
+int awv_internal_view(awv_engine* e, awp::EngineView* v);  // AWV_ERR_STATE without a sequence set
+awp::PlanState*& awv_internal_plan(awv_engine* e);
+int awv_internal_fail(int code, const std::string& msg);   // records awv_last_error(), returns code

@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("AWV_HIP_LIB") or os.path.join(_HERE, "liballwave_hip.
 AWV_OK = 0
 AWV_ERR_NO_DEVICE = -1
 AWV_ERR_ARG = -3
+AWV_ERR_STATE = -6
 AWV_ERR_SINK = -7
 AWV_ST_COMPLETED = 0
 AWV_ST_CAPACITY = 1
@@ -29,10 +30,15 @@ AWV_F_NO_CHAIN = 128
 AWV_F_NO_WIDE16 = 256
 AWV_F_NO_DEEP = 512
 AWV_F_NO_RERUN = 1024
+#: sketch kinds of device pair planning (awv_sketch)
+AWV_SK_CANONICAL = 0
+AWV_SK_FORWARD = 1
+AWV_SK_REVCOMP = 2
 
 #: every symbol include/allwave_hip.h declares
 EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine_destroy",
-           "awv_engine_set_sequences", "awv_align_pairs", "awv_align_one", "awv_score_pairs", "awv_engine_stats")
+           "awv_engine_set_sequences", "awv_align_pairs", "awv_align_one", "awv_score_pairs", "awv_engine_stats",
+           "awv_sketch", "awv_sketch_copy", "awv_sketch_pair_counts", "awv_sketch_rows", "awv_sketch_knn", "awv_keep_pairs")
 
 
 class EngineConfig(C.Structure):

@@ -286,17 +286,25 @@ def _pairs_out(out, n):
     return [tuple(int(v) for v in r) for r in a]
 
 
-def plan_pairs(ids, seqs, sparsification, exclude_self=True, resparsify=False):
+def plan_pairs(ids, seqs, sparsification, exclude_self=True, resparsify=False, device=None):
     """Pair list AllPairIterator::with_options would align (iterator.rs:30-92); resparsify: planned with `-p none` first and
-    then through with_sparsification (iterator.rs:101-110)."""
+    then through with_sparsification (iterator.rs:101-110).  device: a HIP ordinal to plan on (the same list; HostError
+    without that device), None: the host planner."""
     cids, data, offs = _seq_args(ids, seqs)
     out = C.c_void_p()
     n = C.c_size_t(0)
     e = _err()
-    rc = load().awh_plan_pairs(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
-                               sparsification.encode(), int(bool(exclude_self)) | (2 if resparsify else 0), C.byref(out), C.byref(n), e, _CAP)
-    if rc != 0:
-        raise ValueError(e.value.decode())
+    flags = int(bool(exclude_self)) | (2 if resparsify else 0)
+    if device is None:
+        rc = load().awh_plan_pairs(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
+                                   sparsification.encode(), flags, C.byref(out), C.byref(n), e, _CAP)
+        if rc != 0:
+            raise ValueError(e.value.decode())
+    else:
+        rc = load().awh_plan_pairs_gpu(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
+                                       sparsification.encode(), flags, int(device), C.byref(out), C.byref(n), e, _CAP)
+        if rc != 0:
+            raise (ValueError if rc == -1 else HostError)(e.value.decode())
     return _pairs_out(out, n.value)
 
 
@@ -341,18 +349,66 @@ def knn_graph(dist, k, farthest=False):
     return _pairs_out(out, n.value)
 
 
-def mash_matrix(ids, seqs, k=15):
+def mash_matrix(ids, seqs, k=15, device=None):
+    """Mash distance matrix (mash.rs:135-166, sketch size 1,000); device: a HIP ordinal to sketch and intersect on (the same
+    doubles, bit for bit; HostError without that device), None: the host planner."""
     cids, data, offs = _seq_args(ids, seqs)
     out = np.zeros((len(ids), len(ids)), dtype=np.float64)
-    load().awh_mash_matrix(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), int(k),
-                           out.ctypes.data_as(C.c_void_p))
+    if device is None:
+        load().awh_mash_matrix(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), int(k),
+                               out.ctypes.data_as(C.c_void_p))
+        return out
+    e = _err()
+    if load().awh_mash_matrix_gpu(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), int(k), int(device),
+                                  out.ctypes.data_as(C.c_void_p), e, _CAP) != 0:
+        raise HostError(e.value.decode())
     return out
 
 
-def orient_mash(ids, seqs, pairs):
+def orient_mash(ids, seqs, pairs, device=None):
+    """Mash orientation of every pair (alignment.rs:69-94): True = reverse.  device: a HIP ordinal (HostError without it)."""
     cids, data, offs = _seq_args(ids, seqs)
     p = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
-    out = np.zeros(len(p), dtype=np.uint8)
-    load().awh_orient_mash(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
-                           p.ctypes.data_as(C.c_void_p), C.c_size_t(len(p)), out.ctypes.data_as(C.c_void_p))
-    return [bool(x) for x in out]
+    out = np.zeros(max(len(p), 1), dtype=np.uint8)
+    if device is None:
+        load().awh_orient_mash(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
+                               p.ctypes.data_as(C.c_void_p), C.c_size_t(len(p)), out.ctypes.data_as(C.c_void_p))
+    else:
+        e = _err()
+        if load().awh_orient_mash_gpu(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
+                                      p.ctypes.data_as(C.c_void_p), C.c_size_t(len(p)), int(device), out.ctypes.data_as(C.c_void_p),
+                                      e, _CAP) != 0:
+            raise HostError(e.value.decode())
+    return [bool(x) for x in out[:len(p)]]
+
+
+SKETCH_KINDS = {"canonical": 0, "forward": 1, "revcomp": 2}
+
+
+def sketch(ids, seqs, k, s, kind="canonical", device=None):
+    """Sketch of every sequence as a list of sorted hash lists: kind "canonical" (mash.rs:78-107), "forward" (stranded,
+    alignment.rs:96-122) or "revcomp" (stranded, of reverse_complement(seq)).  device: a HIP ordinal (the engine's
+    awv_sketch; HostError without it), None: the host code."""
+    cids, data, offs = _seq_args(ids, seqs)
+    po, ph = C.c_void_p(), C.c_void_p()
+    e = _err()
+    L = load()
+    if L.awh_sketch(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), int(k), int(s), SKETCH_KINDS[kind],
+                    -1 if device is None else int(device), C.byref(po), C.byref(ph), e, _CAP) != 0:
+        raise HostError(e.value.decode())
+    n = len(ids)
+    o = np.ctypeslib.as_array(C.cast(po, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+    h = np.ctypeslib.as_array(C.cast(ph, C.POINTER(C.c_uint64)), shape=(int(o[n]) + 1,))[:int(o[n])].copy()
+    L.awh_free(po)
+    L.awh_free(ph)
+    return [h[o[i]:o[i + 1]].tolist() for i in range(n)]
+
+
+def keep_threshold(fraction):
+    """(threshold, keep_all) of the hashed keep test: keep_pair's `h / u64::MAX < fraction` holds iff keep_all or h < threshold."""
+    L = load()
+    L.awh_keep_threshold.restype = C.c_uint64
+    L.awh_keep_threshold.argtypes = [C.c_double, C.POINTER(C.c_int)]
+    a = C.c_int(0)
+    t = L.awh_keep_threshold(float(fraction), C.byref(a))
+    return int(t), bool(a.value)

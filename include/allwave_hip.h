@@ -208,6 +208,37 @@ int awv_score_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pai
 
 int awv_engine_stats(const awv_engine* e, awv_stats* out);
 
+/* ---- device pair planning (csrc/planner.hip) -------------------------------------------------------------------------
+ * Integer work over the engine's resident sequence set, on its device and stream; results equal the host planner's
+ * (csrc/host/planner.cpp) bit for bit.  Every call but awv_keep_pairs needs a sequence set (else AWV_ERR_STATE); a new set
+ * drops the sketches of the old one.  A null engine: AWV_ERR_NO_DEVICE without a GPU, else AWV_ERR_ARG. */
+#define AWV_SK_CANONICAL 0 /* min(hash(k-mer), hash(upper-cased reverse complement)) of the forward copy (mash.rs) */
+#define AWV_SK_FORWARD 1   /* stranded, forward copy (alignment.rs:96-122) */
+#define AWV_SK_REVCOMP 2   /* stranded, reverse-complement copy */
+#define AWV_PLAN_MAX_K 64
+#define AWV_PLAN_MAX_S 4096
+#define AWV_PLAN_MAX_KNN 64
+
+/* Builds and keeps the sketch set of `kind`: per sequence the distinct hashes among the s smallest k-mer hashes (duplicates
+ * counted; k-mers with a non-ACGT byte skipped), 1 <= k <= 64, 1 <= s <= 4096.  sizes (nullable): n entries. */
+int awv_sketch(awv_engine* e, int32_t kind, int32_t k, int32_t s, uint32_t* sizes);
+/* Copies the kept sketch set of `kind` out: offsets[n + 1] (nullable) and the ascending hashes, offsets[n] of them (nullable). */
+int awv_sketch_copy(awv_engine* e, int32_t kind, uint64_t* offsets, uint64_t* hashes);
+/* inter[p] = |sketch_a(a[p]) n sketch_b(b[p])| for p < npairs (sketches of kinds kind_a, kind_b). */
+int awv_sketch_pair_counts(awv_engine* e, int32_t kind_a, int32_t kind_b, const int32_t* a, const int32_t* b, int64_t npairs,
+                           uint16_t* inter);
+/* inter[r * n + j] = |S(row0 + r) n S(j)| for r < nrows, j < n (one kind against itself). */
+int awv_sketch_rows(awv_engine* e, int32_t kind, int32_t row0, int32_t nrows, uint16_t* inter);
+/* Per row i: the k_nearest columns j != i of largest Jaccard and the k_farthest of smallest, ties to the smaller j, in that
+ * order (nearest[i * k_nearest + t], farthest[i * k_farthest + t]; -1 past n - 1 columns).  Jaccards are compared exactly
+ * (inter_a * uni_b against inter_b * uni_a; uni = 0 counts as 0).  0 <= k_nearest, k_farthest <= 64. */
+int awv_sketch_knn(awv_engine* e, int32_t kind, int32_t k_nearest, int32_t k_farthest, int32_t* nearest, int32_t* farthest);
+/* The hashed keep test of the sparsifiers (iterator.rs:261-281): bit j & 31 of bitmap[i * ((n + 31) / 32) + j / 32] is set
+ * when keep_all or DefaultHasher("id_i:id_j") < threshold, for i != j (and i == j with include_diag).  The ids: n strings,
+ * id_bytes[id_offsets[i], id_offsets[i + 1]).  Reads no sequence: the engine needs no sequence set for it. */
+int awv_keep_pairs(awv_engine* e, int32_t n, const uint8_t* id_bytes, const uint64_t* id_offsets, uint64_t threshold,
+                   int32_t keep_all, int32_t include_diag, uint32_t* bitmap);
+
 #ifdef __cplusplus
 }
 #endif
