@@ -177,6 +177,9 @@ struct KParams {
   // ends ST_ABOVE_BOUND with penalty max_penalty + 1
   int score_only;
   int max_penalty;
+  // score-only launches with a bound per pair (awv_score_pairs_bounded): nullable; when present pair i's bound is
+  // pair_max_penalty[i] (INT_MAX = none) and max_penalty is not read
+  const int32_t* pair_max_penalty;
 };
 
 struct RowMeta { int lo, hi; };
@@ -3616,7 +3619,7 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
             pc.chain_max = kp.chain_max;
             pc.multi_T = kp.multi_T;
             pc.deep_passes = kp.deep_passes;
-            pc.max_penalty = kp.max_penalty;
+            pc.max_penalty = kp.pair_max_penalty ? kp.pair_max_penalty[pair] : kp.max_penalty;
             pc.plen = plen; pc.tlen = tlen;
             pc.seq_mode = cx.seq_mode; pc.p_w0 = cx.p_w0; pc.t_w0 = cx.t_w0; pc.p_bit = cx.p_bit; pc.t_bit = cx.t_bit;
             pc.pb_abs = cx.pb_abs; pc.tb_abs = cx.tb_abs;
@@ -3672,11 +3675,12 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
       __syncthreads();
     }
     // (score-only: the closed-form and base-case penalties are exact too; any penalty above the bound reports as such)
-    if (status == ST_OK && penalty > kp.max_penalty) status = ST_ABOVE_BOUND;
+    const int pair_bound = kp.pair_max_penalty ? kp.pair_max_penalty[pair] : kp.max_penalty;
+    if (status == ST_OK && penalty > pair_bound) status = ST_ABOVE_BOUND;
     if (tid == 0) {
       DevResult r;
       r.status = status;
-      r.penalty = status == ST_OK ? penalty : status == ST_ABOVE_BOUND ? kp.max_penalty + 1 : 0;
+      r.penalty = status == ST_OK ? penalty : status == ST_ABOVE_BOUND ? pair_bound + 1 : 0;
       r.score = -r.penalty;
       r.cigar_len = status == ST_OK && !kp.score_only ? (uint32_t)em.n : 0u;
       r.cigar_off = kp.score_only ? 0 : kp.cigar_off[pair];

@@ -155,6 +155,7 @@ struct awv_engine {
   DevBuf<uint32_t> ev_mem;
   // per-launch buffers
   DevBuf<int32_t> d_pair_q, d_pair_t, d_pair_rc;
+  DevBuf<int32_t> d_pair_bound;  // score-only launches with a bound per pair
   DevBuf<uint64_t> d_cigar_off;
   DevBuf<awv::DevResult> d_results;
   DevBuf<uint8_t> d_cigar;
@@ -313,9 +314,10 @@ long long worst_case_penalty(const awv::DevPenalties& d, long long n) {
 }
 
 // score_only: awv_score_pairs -- the top-level search's score only, no CIGAR arena (so max_arena_bytes does not cut batches);
-// max_penalty: that call's bound (INT_MAX = none)
+// max_penalty: that call's bound (INT_MAX = none); pair_bound (nullable, score_only): pair i's own bound instead (INT_MAX = none)
 int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
-               awv_result* out, awv_sink sink, void* user, bool score_only = false, int max_penalty = INT_MAX) {
+               awv_result* out, awv_sink sink, void* user, bool score_only = false, int max_penalty = INT_MAX,
+               const int32_t* pair_bound = nullptr) {
   using namespace awv;
   if (npairs < 0 || (npairs > 0 && !pairs)) return fail(AWV_ERR_ARG, "align_pairs: null pairs");
   DevPenalties dp{};
@@ -376,7 +378,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
   auto lap = [&](const char* what) {
     if (timing) fprintf(stderr, "[awv] %-22s %.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - tl0).count());
   };
-  std::vector<int32_t> hq, ht, hrc;
+  std::vector<int32_t> hq, ht, hrc, hbound;
   std::vector<uint64_t> hoff;
   std::vector<awv_result> hres;
   int64_t first = 0;
@@ -613,6 +615,12 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       HIP_TRY(hipMemcpyAsync(e->d_pair_t.p, ht.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
       HIP_TRY(hipMemcpyAsync(e->d_pair_rc.p, hrc.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
       HIP_TRY(hipMemcpyAsync(e->d_cigar_off.p, hoff.data(), (size_t)m * 8, hipMemcpyHostToDevice, e->stream));
+      if (pair_bound) {  // (amap: dispatch index -> batch index, kept through the sort, the groups and the re-runs)
+        hbound.resize((size_t)m);
+        for (int64_t i = 0; i < m; ++i) hbound[(size_t)i] = pair_bound[first + amap[(size_t)i]];
+        if (int rc = e->d_pair_bound.reserve((size_t)m)) return rc;
+        HIP_TRY(hipMemcpyAsync(e->d_pair_bound.p, hbound.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
+      }
       HIP_TRY(hipMemsetAsync(e->d_counters.p, 0, (1 + STAT_N) * sizeof(unsigned long long), e->stream));
       HIP_TRY(hipEventRecord(e->ev1, e->stream));
       HIP_TRY(hipEventSynchronize(e->ev1));
@@ -659,6 +667,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       kp.stats = e->d_counters.p + 1;
       kp.score_only = score_only ? 1 : 0;
       kp.max_penalty = score_only ? max_penalty : INT_MAX;
+      kp.pair_max_penalty = score_only && pair_bound ? e->d_pair_bound.p : nullptr;
       HIP_TRY(hipEventRecord(e->ev0, e->stream));
       auto launch = [&](auto kern, const auto& kparams) -> int {
         HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
@@ -947,6 +956,7 @@ void awv_engine_destroy(awv_engine* e) {
   e->d_pair_q.release();
   e->d_pair_t.release();
   e->d_pair_rc.release();
+  e->d_pair_bound.release();
   e->d_cigar_off.release();
   e->d_results.release();
   e->d_cigar.release();
@@ -984,8 +994,10 @@ int awv_align_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pai
   AWV_GUARDED(return align_core(e, e->seqs, pen, pairs, npairs, out, sink, user);)
 }
 
-int awv_score_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, int32_t max_penalty,
-                    awv_score_result* out) {
+namespace {
+// awv_score_pairs / awv_score_pairs_bounded: one bound for the call (pair_bound == nullptr), or one per pair
+int score_core(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, int32_t max_penalty,
+               const int32_t* pair_bound, awv_score_result* out) {
   if (!e) {  // (without a GPU there is no engine to pass: say so, as awv_engine_create does)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(AWV_ERR_NO_DEVICE, "no HIP device available: liballwave_hip has no CPU fallback");
@@ -995,10 +1007,16 @@ int awv_score_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pai
   if (npairs < 0) return fail(AWV_ERR_ARG, "score_pairs: npairs < 0");
   if (e->seqs.n == 0 && npairs > 0) return fail(AWV_ERR_STATE, "score_pairs before set_sequences");
   // (a bound of 2^30 or more cannot be met by any pair the engine accepts: it is no bound)
-  const int bound = max_penalty < 0 || max_penalty >= (1 << 30) ? INT_MAX : max_penalty;
+  auto norm = [](int32_t b) { return b < 0 || b >= (1 << 30) ? INT_MAX : b; };
   AWV_GUARDED(
     std::vector<awv_result> res((size_t)npairs);
-    const int rc = align_core(e, e->seqs, pen, pairs, npairs, res.data(), nullptr, nullptr, true, bound);
+    std::vector<int32_t> pb;
+    if (pair_bound) {
+      pb.resize((size_t)npairs);
+      for (int64_t i = 0; i < npairs; ++i) pb[(size_t)i] = norm(pair_bound[i]);
+    }
+    const int rc = align_core(e, e->seqs, pen, pairs, npairs, res.data(), nullptr, nullptr, true, norm(max_penalty),
+                              pair_bound ? pb.data() : nullptr);
     if (rc != AWV_OK) return rc;
     for (int64_t i = 0; i < npairs; ++i) {
       out[i].status = res[(size_t)i].status;
@@ -1006,6 +1024,18 @@ int awv_score_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pai
     }
     return AWV_OK;
   )
+}
+}  // namespace
+
+int awv_score_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, int32_t max_penalty,
+                    awv_score_result* out) {
+  return score_core(e, pen, pairs, npairs, max_penalty, nullptr, out);
+}
+
+int awv_score_pairs_bounded(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
+                            const int32_t* max_penalty, awv_score_result* out) {
+  if (e && npairs > 0 && !max_penalty) return fail(AWV_ERR_ARG, "score_pairs_bounded: null max_penalty");
+  return score_core(e, pen, pairs, npairs, -1, max_penalty, out);
 }
 
 namespace {
@@ -1090,3 +1120,5 @@ int awv_internal_view(awv_engine* e, awp::EngineView* v) {
 }
 awp::PlanState*& awv_internal_plan(awv_engine* e) { return e->plan; }
 int awv_internal_fail(int code, const std::string& msg) { return fail(code, msg); }
+// ---- what orient.hip needs beyond that (orient_device.hpp): the stats of a call made of several engine calls
+void awv_internal_set_stats(awv_engine* e, const awv_stats* st) { e->stats = *st; }

@@ -367,6 +367,7 @@ AllPairIterator AllPairIterator::with_options(const std::vector<Sequence>& seque
 AllPairIterator& AllPairIterator::with_plan_device(int plan_device) { plan_device_ = plan_device < 0 ? -1 : plan_device; return *this; }
 AllPairIterator& AllPairIterator::with_orientation_params(AlignmentParams p) { orientation_params_ = std::move(p); return *this; }
 AllPairIterator& AllPairIterator::with_orientation(Orientation o) { orientation_ = o; return *this; }
+AllPairIterator& AllPairIterator::with_full_wfa_orientation(bool full) { full_wfa_orientation_ = full; return *this; }
 AllPairIterator& AllPairIterator::with_device(int device) { devices_.assign(1, device); return *this; }
 AllPairIterator& AllPairIterator::with_devices(std::vector<int> devices) {
   if (devices.empty()) throw std::invalid_argument("with_devices: the device list is empty");
@@ -440,6 +441,7 @@ AllPairIterator AllPairIterator::with_sparsification(SparsificationStrategy stra
   it.min_batch_pairs_ = min_batch_pairs_;
   it.threads_ = threads_;
   it.next_chunk_ = next_chunk_;
+  it.full_wfa_orientation_ = full_wfa_orientation_;
   return it;
 }
 AllPairIterator& AllPairIterator::with_next_chunk(size_t n) { next_chunk_ = std::max<size_t>(1, n); return *this; }
@@ -528,23 +530,15 @@ void process_alignments_with_callback(const std::vector<Sequence>& sequences, Al
 }
 
 namespace {
-// determine_orientation_wfa (alignment.rs:157-175) for the pairs (q, t) of ap[0, n): align forward and reverse-complement
-// with the orientation params, compare #X+#I+#D; forward wins ties; a failed alignment counts as usize::MAX
-void orient_wfa(awv_engine* e, const awv_penalties& open, const awv_pair* ap, int64_t n, uint8_t* is_rev) {
-  std::vector<awv_pair> op((size_t)2 * n);
-  for (int64_t i = 0; i < n; ++i) {
-    op[2 * i] = awv_pair{ap[i].q_idx, ap[i].t_idx, 0};
-    op[2 * i + 1] = awv_pair{ap[i].q_idx, ap[i].t_idx, 1};
-  }
-  std::vector<awv_result> orr((size_t)2 * n);
-  if (awv_align_pairs(e, &open, op.data(), 2 * n, orr.data(), nullptr, nullptr) != AWV_OK)
+// determine_orientation_wfa (alignment.rs:157-175) for the pairs (q, t) of ap[0, n): forward unless the reverse-complement
+// alignment under the orientation params has fewer #X+#I+#D; forward wins ties; a failed alignment counts as usize::MAX.
+// awv_orient_pairs decides from bounded strand scores wherever those prove the comparison and aligns both strands in full
+// only where they do not; `full`: both strands in full for every pair (AWV_ORIENT_FULL)
+void orient_wfa(awv_engine* e, const awv_penalties& open, const awv_pair* ap, int64_t n, bool full, uint8_t* is_rev) {
+  std::vector<awv_orient_result> orr((size_t)n);
+  if (awv_orient_pairs(e, &open, ap, n, full ? AWV_ORIENT_FULL : 0, orr.data()) != AWV_OK)
     throw AlignmentError(std::string("orientation pass: ") + awv_last_error());
-  for (int64_t i = 0; i < n; ++i) {
-    auto dist = [](const awv_result& r) -> uint64_t {
-      return r.status == AWV_ST_COMPLETED ? (uint64_t)r.num_mismatches + (uint64_t)r.num_ins + (uint64_t)r.num_del : UINT64_MAX;
-    };
-    is_rev[i] = dist(orr[2 * i]) <= dist(orr[2 * i + 1]) ? 0 : 1;
-  }
+  for (int64_t i = 0; i < n; ++i) is_rev[i] = orr[(size_t)i].is_reverse ? 1 : 0;
 }
 
 // counters of several engine calls: summed, except the clock rate (a property of the device) and scratch_bytes (what is
@@ -670,7 +664,7 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
         if (orientation_ == Orientation::Mash) {
           for (int64_t i = 0; i < m; ++i) rev[i] = mash_rev[at(i)];
         } else if (orientation_ == Orientation::Wfa) {
-          orient_wfa(e, open, ap.data(), m, rev.data());
+          orient_wfa(e, open, ap.data(), m, full_wfa_orientation_, rev.data());
         }
         for (int64_t i = 0; i < m; ++i) ap[i].q_revcomp = rev[i];
         lap("pairs oriented");

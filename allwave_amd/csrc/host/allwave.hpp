@@ -135,6 +135,10 @@ class AllPairIterator {  // iterator.rs:12-171
   // process-wide planner::host_threads())
   AllPairIterator& with_threads(int host_threads);
   AllPairIterator& with_orientation(Orientation o);
+  // WFA orientation (awv_orient_pairs) decides a pair from bounded strand scores wherever those prove which strand has
+  // fewer edits, and aligns both strands in full only where they do not; true: both strands in full for every pair, the
+  // reference's method (AWV_ORIENT_FULL).  The strands chosen are the same.
+  AllPairIterator& with_full_wfa_orientation(bool full);
   AllPairIterator& with_device(int device);  // = with_devices({device})
   // Aligns the pair list on several engines at once, one "slot" per entry: an ordinal may appear more than once, and each
   // occurrence is an engine of its own (stream, arenas; the slots of one device split its default scratch budget).  With
@@ -157,8 +161,8 @@ class AllPairIterator {  // iterator.rs:12-171
   // `sink` (replaces the single unbuffered writer thread of src/main.rs:347-367); sink calls never overlap
   void for_each_paf_batch(const std::function<void(const std::string&)>& sink, int format_threads = 8);
   // Score-only consumer (awv_score_pairs): one PairScore per planned pair, in pair-list order, through the same orientation,
-  // sparsification, shard and device settings as the alignment consumers (WFA orientation still aligns both strands in full
-  // to choose one; the final alignment is scored only).  max_penalty: a bound -- pairs proved above it come back
+  // sparsification, shard and device settings as the alignment consumers (the final alignment is scored only; WFA orientation
+  // is awv_orient_pairs: bounded strand scores, full alignments only for the pairs those leave open).  max_penalty: a bound -- pairs proved above it come back
   // AWV_ST_ABOVE_BOUND, and their search stops there.
   std::vector<PairScore> scores(std::optional<int> max_penalty = std::nullopt);
   // counters of the last run, summed over its slots (kernel_ms: summed kernel time, not wall time)
@@ -198,6 +202,7 @@ class AllPairIterator {  // iterator.rs:12-171
   int plan_device_ = -1;
   bool exclude_self_ = true;
   Orientation orientation_ = Orientation::Wfa;
+  bool full_wfa_orientation_ = false;
   std::vector<int> devices_{0};
   size_t min_batch_pairs_ = 16384;
   int threads_ = 0;

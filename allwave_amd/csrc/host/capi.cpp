@@ -90,7 +90,8 @@ int awh_all_pairs_paf_devices(int n, const char* const* ids, const uint8_t* byte
     const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
     AllPairIterator it = AllPairIterator::with_options(seqs, parse_scores(scores), exclude_self != 0, orientation == 2,
                                                       SparsificationStrategy::parse(sparsification ? sparsification : "none"));
-    it.with_orientation(orientation == 0 ? Orientation::ForwardOnly : orientation == 1 ? Orientation::Wfa : Orientation::Mash);
+    it.with_orientation(orientation == 0 ? Orientation::ForwardOnly : (orientation == 1 || orientation == 3) ? Orientation::Wfa : Orientation::Mash);
+    it.with_full_wfa_orientation(orientation == 3);
     if (!devices || n_devices < 1) throw std::invalid_argument("awh_all_pairs_paf: empty device list");
     it.with_devices(std::vector<int>(devices, devices + n_devices));
     if (min_batch_pairs > 0) it.with_min_batch_pairs((size_t)min_batch_pairs);
@@ -132,7 +133,7 @@ int awh_iterate_devices(int n, const char* const* ids, const uint8_t* bytes, con
   try {
     const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
     const SparsificationStrategy strat = SparsificationStrategy::parse(sparsification ? sparsification : "none");
-    const Orientation orient = orientation == 0 ? Orientation::ForwardOnly : orientation == 1 ? Orientation::Wfa : Orientation::Mash;
+    const Orientation orient = orientation == 0 ? Orientation::ForwardOnly : (orientation == 1 || orientation == 3) ? Orientation::Wfa : Orientation::Mash;
     std::mutex mu;
     std::string all;
     auto record = [&](AlignmentResult&& r) {
@@ -161,6 +162,7 @@ int awh_iterate_devices(int n, const char* const* ids, const uint8_t* bytes, con
       AllPairIterator it0 = AllPairIterator::with_options(seqs, parse_scores(scores), true, orientation == 2,
                                                          resparsify ? SparsificationStrategy{} : strat);
       it0.with_orientation(orient).with_devices(devs);
+      it0.with_full_wfa_orientation(orientation == 3);
       if (shard_world > 1) it0.with_shard((size_t)shard_rank, (size_t)shard_world);
       if (min_batch_pairs > 0) it0.with_min_batch_pairs((size_t)min_batch_pairs);
       if (chunk > 0) it0.with_next_chunk((size_t)chunk);
@@ -186,7 +188,7 @@ int awh_iterate_devices(int n, const char* const* ids, const uint8_t* bytes, con
   }
 }
 // AllPairIterator::scores over the pair list AllPairIterator::with_options(..., exclude_self = true, mash orientation when
-// orientation == 2, sparsification) plans, oriented by `orientation` (0 forward, 1 WFA, 2 mash), on the engines
+// orientation == 2, sparsification) plans, oriented by `orientation` (0 forward, 1 WFA, 2 mash, 3 WFA by two full alignments per pair: with_full_wfa_orientation -- in every hook here), on the engines
 // `devices[0, n_devices)` names, on shard `shard_rank` of `shard_world` (world <= 1: the whole list).  max_penalty < 0: no
 // bound.  out = malloc'ed int64 records of five (query_idx, target_idx, is_reverse, penalty, status), one per planned pair in
 // pair-list order; st (nullable) receives last_stats().
@@ -198,7 +200,8 @@ int awh_all_pairs_scores(int n, const char* const* ids, const uint8_t* bytes, co
     const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
     AllPairIterator it = AllPairIterator::with_options(seqs, parse_scores(scores), true, orientation == 2,
                                                       SparsificationStrategy::parse(sparsification ? sparsification : "none"));
-    it.with_orientation(orientation == 0 ? Orientation::ForwardOnly : orientation == 1 ? Orientation::Wfa : Orientation::Mash);
+    it.with_orientation(orientation == 0 ? Orientation::ForwardOnly : (orientation == 1 || orientation == 3) ? Orientation::Wfa : Orientation::Mash);
+    it.with_full_wfa_orientation(orientation == 3);
     it.with_devices(std::vector<int>(devices, devices + n_devices));
     if (shard_world > 1) it.with_shard((size_t)shard_rank, (size_t)shard_world);
     if (max_penalty > INT32_MAX) max_penalty = -1;  // (no pair can score that much: no bound)
@@ -230,8 +233,9 @@ int awh_all_pairs_paf_count_devices(int n, const char* const* ids, const uint8_t
     AllPairIterator it = sparsification ? AllPairIterator::with_options(seqs, parse_scores(scores), true, false,
                                                                        SparsificationStrategy::parse(sparsification))
                                         : AllPairIterator(seqs, parse_scores(scores));
-    it.with_orientation(orientation == 0 ? Orientation::ForwardOnly : orientation == 1 ? Orientation::Wfa : Orientation::Mash)
+    it.with_orientation(orientation == 0 ? Orientation::ForwardOnly : (orientation == 1 || orientation == 3) ? Orientation::Wfa : Orientation::Mash)
         .with_devices(std::vector<int>(devices, devices + n_devices));
+    it.with_full_wfa_orientation(orientation == 3);
     if (min_batch_pairs > 0) it.with_min_batch_pairs((size_t)min_batch_pairs);
     it.with_threads(format_threads);  // this call's sketching / orientation threads: carried by the iterator, not a process-wide setting
     uint64_t nb = 0, nl = 0, sum = 0;

@@ -4,6 +4,7 @@
 //   --no-progress  --mash-matrix  --wfa-orientation  -k/--keep-prefixes  -e/--exclude-prefixes
 // Extensions: --device N (GPU ordinal), --devices LIST (several GPUs, or engines, in this one process),
 // --shard R/N (this process's part of the pair list), --forward-only (skip orientation: all '+'),
+// --wfa-orientation-full (WFA orientation by two full alignments per pair, the reference's method, instead of bounded scores),
 // --score-only (penalties instead of PAF: WFA2's ComputeScore scope) with an optional --max-penalty N bound.
 // -t sets the host threads used for PAF formatting / sketching (alignment itself runs on the GPU).
 #include <zlib.h>
@@ -26,7 +27,7 @@ namespace {
 struct Args {
   std::string input, output, scores = "0,5,8,2,24,1", preset, sparsification = "giant:0.99", keep, exclude;
   bool have_output = false, have_scores = false, have_preset = false, no_progress = false, mash_matrix = false;
-  bool wfa_orientation = false, forward_only = false, have_keep = false, have_exclude = false;
+  bool wfa_orientation = false, wfa_orientation_full = false, forward_only = false, have_keep = false, have_exclude = false;
   int threads = 1, device = 0;
   bool have_device = false;
   std::string devices;  // --devices LIST (empty: --device)
@@ -179,6 +180,7 @@ int main(int argc, char** argv) {
     else if (k == "--no-progress") a.no_progress = true;
     else if (k == "--mash-matrix") a.mash_matrix = true;
     else if (k == "--wfa-orientation") a.wfa_orientation = true;
+    else if (k == "--wfa-orientation-full") a.wfa_orientation = a.wfa_orientation_full = true;
     else if (k == "--forward-only") a.forward_only = true;
     else if (k == "-k" || k == "--keep-prefixes") { a.keep = val(); a.have_keep = true; }
     else if (k == "-e" || k == "--exclude-prefixes") { a.exclude = val(); a.have_exclude = true; }
@@ -208,7 +210,7 @@ int main(int argc, char** argv) {
     }
     else if (k == "-h" || k == "--help") {
       std::cout << "usage: allwave_hip -i in.fa [-o out.paf] [-s m,x,o,e[,o2,e2] | -x ANI] [-p none|auto|random:f|giant:p|tree:n:f:r[:k]]\n"
-                   "                   [-t threads] [--wfa-orientation|--forward-only] [-k prefixes | -e prefixes] [--mash-matrix]\n"
+                   "                   [-t threads] [--wfa-orientation|--wfa-orientation-full|--forward-only] [-k prefixes | -e prefixes] [--mash-matrix]\n"
                    "                   [--device N | --devices LIST] [--shard R/N] [--score-only [--max-penalty N]] [--plan-device N]\n"
                    "  --devices LIST   align on several devices in this process: ordinals and ranges, e.g. 0,1,2 / 0-7 / all;\n"
                    "                   an ordinal may repeat (0,0: two engines on device 0); -t is shared out among them\n"
@@ -283,6 +285,7 @@ int main(int argc, char** argv) {
   try {
     AllPairIterator it = AllPairIterator::with_options(sequences, params, true, !a.wfa_orientation, strategy, a.plan_device);
     if (a.forward_only) it.with_orientation(Orientation::ForwardOnly);
+    it.with_full_wfa_orientation(a.wfa_orientation_full);
     it.with_devices(devices);
     it.with_shard((size_t)a.shard_rank, (size_t)a.shard_world);
     const size_t total = it.pair_count();

@@ -30,6 +30,16 @@ AWV_F_NO_CHAIN = 128
 AWV_F_NO_WIDE16 = 256
 AWV_F_NO_DEEP = 512
 AWV_F_NO_RERUN = 1024
+#: WFA orientation (awv_orient_pairs / awv_orient_decide)
+AWV_ORIENT_FORWARD = 0
+AWV_ORIENT_REVERSE = 1
+AWV_ORIENT_UNDECIDED = 2
+AWV_ORIENT_BY_BOUND = 0
+AWV_ORIENT_BY_EDITS = 1
+AWV_ORIENT_FULL = 1
+AWV_ORIENT_SKIP_RATIO = 8
+AWV_ORIENT_NO_EDITS = 2 ** 64 - 1
+AWV_ORIENT_HI_NONE = 2 ** 31 - 1
 #: sketch kinds of device pair planning (awv_sketch)
 AWV_SK_CANONICAL = 0
 AWV_SK_FORWARD = 1
@@ -38,6 +48,7 @@ AWV_SK_REVCOMP = 2
 #: every symbol include/allwave_hip.h declares
 EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine_destroy",
            "awv_engine_set_sequences", "awv_align_pairs", "awv_align_one", "awv_score_pairs", "awv_engine_stats",
+           "awv_score_pairs_bounded", "awv_orient_pairs", "awv_orient_decide", "awv_orient_settling_bound",
            "awv_sketch", "awv_sketch_copy", "awv_sketch_pair_counts", "awv_sketch_rows", "awv_sketch_knn", "awv_keep_pairs")
 
 
@@ -81,6 +92,10 @@ RESULT_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4"), ("score", "<i4")
 #: awv_score_result
 SCORE_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4")])
 
+#: awv_orient_result
+ORIENT_DTYPE = np.dtype([("is_reverse", "<i4"), ("how", "<i4"), ("lo_f", "<i4"), ("hi_f", "<i4"), ("lo_r", "<i4"), ("hi_r", "<i4"),
+                         ("edits_f", "<u8"), ("edits_r", "<u8"), ("rounds", "<i4"), ("reserved", "<i4")])
+
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p)
 
 _LIB = None
@@ -105,6 +120,11 @@ def load():
                                     C.c_void_p, C.c_void_p, C.c_size_t]
         L.awv_score_pairs.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         L.awv_engine_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
+        L.awv_score_pairs_bounded.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.awv_orient_pairs.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+        L.awv_orient_decide.argtypes = [C.POINTER(Penalties), C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        L.awv_orient_settling_bound.argtypes = [C.POINTER(Penalties), C.c_int32, C.c_int32]
+        L.awv_orient_settling_bound.restype = C.c_int32
         _LIB = L
     return _LIB
 
@@ -192,9 +212,20 @@ class Engine:
     def score_pairs(self, scores, pairs, max_penalty=None):
         """Score-only alignment (awv_score_pairs): the optimal penalty of every pair, no CIGAR.  pairs as for align_pairs.
         max_penalty: None = no bound; else pairs whose penalty exceeds it come back AWV_ST_ABOVE_BOUND with penalty
-        max_penalty + 1.  Returns a SCORE_DTYPE structured array (status, penalty)."""
+        max_penalty + 1; an array or a list: one bound per pair (awv_score_pairs_bounded; a negative entry: no bound for
+        that pair).  Returns a SCORE_DTYPE structured array (status, penalty)."""
         pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
         pairs = self._pair_array(pairs)
+        if max_penalty is not None and np.ndim(max_penalty) > 0:
+            bounds = np.ascontiguousarray(max_penalty, dtype=np.int32)
+            if bounds.shape != (len(pairs),):
+                raise ValueError("max_penalty: need one bound per pair")
+            out = np.zeros(max(len(pairs), 1), dtype=SCORE_DTYPE)[:len(pairs)]
+            bounds = bounds if len(bounds) else np.zeros(1, dtype=np.int32)
+            rc = load().awv_score_pairs_bounded(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), bounds.ctypes.data, out.ctypes.data)
+            if rc != AWV_OK:
+                raise EngineError(rc, "awv_score_pairs_bounded")
+            return out
         bound = -1 if max_penalty is None else int(max_penalty)
         if max_penalty is not None and bound < 0:
             raise ValueError("max_penalty must be >= 0 (None: no bound)")
@@ -202,6 +233,19 @@ class Engine:
         rc = load().awv_score_pairs(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), bound, out.ctypes.data)
         if rc != AWV_OK:
             raise EngineError(rc, "awv_score_pairs")
+        return out
+
+    def orient_pairs(self, scores, pairs, full=False):
+        """WFA orientation (awv_orient_pairs) under the orientation penalties `scores`: per pair whether the query is to be
+        reverse-complemented, decided from bounded strand scores where those prove it (how == AWV_ORIENT_BY_BOUND) and from
+        the edit counts of two full alignments where they do not (AWV_ORIENT_BY_EDITS); full=True: two full alignments for
+        every pair.  pairs as for align_pairs (a third column is ignored).  Returns an ORIENT_DTYPE structured array."""
+        pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+        pairs = self._pair_array(pairs)
+        out = np.zeros(max(len(pairs), 1), dtype=ORIENT_DTYPE)[:len(pairs)]
+        rc = load().awv_orient_pairs(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), AWV_ORIENT_FULL if full else 0, out.ctypes.data)
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_orient_pairs")
         return out
 
     def align_one(self, scores, pattern, text):
@@ -223,3 +267,23 @@ class Engine:
         if rc != AWV_OK:
             raise EngineError(rc, "awv_engine_stats")
         return st
+
+
+def orient_decide(scores, lo_f, hi_f, lo_r, hi_r):
+    """awv_orient_decide: AWV_ORIENT_FORWARD / _REVERSE / _UNDECIDED from the strands' proved penalty intervals (hi =
+    AWV_ORIENT_HI_NONE: bounded only below).  Needs no device."""
+    pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+    rc = load().awv_orient_decide(C.byref(pen), int(lo_f), int(hi_f), int(lo_r), int(hi_r))
+    if rc < 0:
+        raise EngineError(rc, "awv_orient_decide")
+    return rc
+
+
+def orient_settling_bound(scores, known_is_reverse, penalty):
+    """awv_orient_settling_bound: the bound the other strand is searched under once one strand's penalty is known
+    (-1: the known penalty settles the pair alone; AWV_ORIENT_HI_NONE: no bound).  Needs no device."""
+    pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+    b = load().awv_orient_settling_bound(C.byref(pen), 1 if known_is_reverse else 0, int(penalty))
+    if b < -1:
+        raise EngineError(AWV_ERR_ARG, "awv_orient_settling_bound")
+    return b

@@ -99,6 +99,13 @@ def set_engine_config(flags=0, first_row_cols=0, release=True):
 ORIENT = {"forward": 0, "wfa": 1, "mash": 2}
 
 
+def _orient_code(orientation, orientation_full):
+    """the hooks' orientation argument: 3 = WFA orientation by two full alignments per pair (with_full_wfa_orientation)"""
+    if orientation_full and orientation != "wfa":
+        raise ValueError("orientation_full needs orientation='wfa'")
+    return 3 if orientation_full else ORIENT[orientation]
+
+
 def _seq_args(ids, seqs):
     offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
     offs[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
@@ -116,17 +123,18 @@ def _device_args(devices):
 
 
 def all_pairs_paf(ids, seqs, scores, orientation="wfa", exclude_self=True, device=0, sparsification="none", devices=None,
-                  min_batch_pairs=0):
+                  min_batch_pairs=0, orientation_full=False):
     """AllPairIterator + alignment_to_paf per record; returns the list of PAF lines.  `devices`: a list of ordinals (one
     engine per entry, repeats allowed) to spread the pair list over in this call; None = [device].
-    `min_batch_pairs` > 0 overrides the smallest batch of a multi-device run (default 16,384)."""
+    `min_batch_pairs` > 0 overrides the smallest batch of a multi-device run (default 16,384).  orientation_full: WFA
+    orientation by two full alignments for every pair (the reference's method; the same strands) instead of bounded scores."""
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if devices is None else devices)
     out = C.c_void_p()
     n = C.c_size_t(0)
     e = _err()
     rc = load().awh_all_pairs_paf_devices(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
-                                          scores.encode(), sparsification.encode(), ORIENT[orientation], int(exclude_self),
+                                          scores.encode(), sparsification.encode(), _orient_code(orientation, orientation_full), int(exclude_self),
                                           devs, nd, C.c_int64(int(min_batch_pairs)), None, C.byref(out), C.byref(n), e, _CAP)
     if rc != 0:
         raise HostError(e.value.decode())
@@ -139,7 +147,8 @@ ITER_MODES = {"for_each": 0, "next": 1, "par_for_each": 2, "par_collect": 3, "pr
 
 
 def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientation="forward", threads=4, chunk=0,
-            resparsify=False, fail_at=-1, device=0, devices=None, min_batch_pairs=0, shard=None, with_stats=False):
+            resparsify=False, fail_at=-1, device=0, devices=None, min_batch_pairs=0, shard=None, with_stats=False,
+            orientation_full=False):
     """Every consumer of the pair list (iterator.rs:101-253, lib.rs:57-68) through one hook; returns the PAF lines in arrival
     order.  `fail_at` >= 0 makes the callback throw at that record: HostError carries its message.
     `devices`: a list of ordinals (one engine per entry, repeats allowed) to spread the pair list over; None = [device].
@@ -147,7 +156,8 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
     the list (with_shard; not "process_alignments").  with_stats: returns (lines, [ffi.Stats per slot]) --
     last_slot_stats(); all zeros for "process_alignments" without min_batch_pairs.  A HostError carries `.records`: how
     many records arrived before the error, and `.late_calls`: how many callback calls followed the first failure (with
-    fail_at, each of those fails with a message of its own: "callback failed again, ...")."""
+    fail_at, each of those fails with a message of its own: "callback failed again, ...").  orientation_full: WFA
+    orientation by two full alignments for every pair instead of bounded scores (the same strands)."""
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if devices is None else devices)
     st = (ffi.Stats * nd)()
@@ -156,7 +166,7 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
     n, nrec, late = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
     e = _err()
     rc = load().awh_iterate_devices(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), scores.encode(),
-                                    sparsification.encode(), ORIENT[orientation], ITER_MODES[mode], int(threads), int(chunk),
+                                    sparsification.encode(), _orient_code(orientation, orientation_full), ITER_MODES[mode], int(threads), int(chunk),
                                     int(bool(resparsify)), C.c_long(int(fail_at)), devs, nd, C.c_int64(int(min_batch_pairs)),
                                     C.c_int64(int(rank)), C.c_int64(int(world)), st, C.byref(out), C.byref(n), C.byref(nrec),
                                     C.byref(late), e, _CAP)
@@ -203,11 +213,12 @@ PAIR_SCORE_DTYPE = np.dtype([("query_idx", "<i8"), ("target_idx", "<i8"), ("is_r
 
 
 def all_pairs_scores(ids, seqs, scores, orientation="mash", sparsification="none", devices=None, max_penalty=None, shard=None,
-                     with_stats=False):
+                     with_stats=False, orientation_full=False):
     """Score-only all-vs-all (AllPairIterator::scores): the optimal penalty of every planned pair without a CIGAR, in
     pair-list order, as a PAIR_SCORE_DTYPE array (query_idx, target_idx, is_reverse, penalty, status -- ffi.AWV_ST_*).
     The pair list is AllPairIterator::with_options(..., exclude_self=True, mash orientation, sparsification)'s; the strand of
-    each pair comes from `orientation` ("mash", "wfa": two full alignments per pair, or "forward").  `devices`: a list of
+    each pair comes from `orientation` ("mash", "wfa": bounded strand scores, two full alignments only for the pairs those
+    leave open -- or for every pair with orientation_full -- or "forward").  `devices`: a list of
     ordinals (one engine per entry, repeats allowed; None = device 0), `shard` = (rank, world) keeps that shard of the list.
     max_penalty: None = no bound; else pairs proved above it come back AWV_ST_ABOVE_BOUND with penalty max_penalty + 1.
     with_stats: returns (array, ffi.Stats) -- last_stats(), summed over the slots."""
@@ -221,7 +232,7 @@ def all_pairs_scores(ids, seqs, scores, orientation="mash", sparsification="none
     st = ffi.Stats()
     e = _err()
     rc = load().awh_all_pairs_scores(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), scores.encode(),
-                                     sparsification.encode(), ORIENT[orientation], devs, nd, C.c_int64(int(rank)), C.c_int64(int(world)),
+                                     sparsification.encode(), _orient_code(orientation, orientation_full), devs, nd, C.c_int64(int(rank)), C.c_int64(int(world)),
                                      C.c_int64(-1 if max_penalty is None else int(max_penalty)), C.byref(out), C.byref(n),
                                      C.byref(st), e, _CAP)
     if rc != 0:
@@ -380,6 +391,22 @@ def orient_mash(ids, seqs, pairs, device=None):
                                       e, _CAP) != 0:
             raise HostError(e.value.decode())
     return [bool(x) for x in out[:len(p)]]
+
+
+def orient_wfa(ids, seqs, pairs, scores="0,1,1,1", full=False, device=0):
+    """WFA orientation of every pair (alignment.rs:157-175) under the orientation penalties `scores` on `device`: True =
+    reverse.  Decided from bounded strand scores where those prove which strand has fewer edits, from two full alignments
+    where they do not; full=True: two full alignments for every pair (the same answers)."""
+    p = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+    eng = ffi.Engine(device=int(device))
+    try:
+        eng.set_sequences([s if isinstance(s, (bytes, bytearray)) else str(s).encode() for s in seqs])
+        r = eng.orient_pairs(parse_scores(scores), p.astype(np.int32), full=full)
+    except ffi.EngineError as err:
+        raise HostError(str(err))
+    finally:
+        eng.close()
+    return [bool(x) for x in r["is_reverse"]]
 
 
 SKETCH_KINDS = {"canonical": 0, "forward": 1, "revcomp": 2}

@@ -14,6 +14,7 @@
  *   set_heuristic(None)   src/alignment.rs:226-228, src/wfa.rs:221-223  (end-to-end, exact, with CIGAR)
  *   set_alignment_scope(ComputeScore) + wf.align + wf.score()            awv_score_pairs (exact penalty, no
  *                                                                        CIGAR; optional penalty bound)
+ *   determine_orientation_wfa                  src/alignment.rs:157-175  awv_orient_pairs
  *   wf.align(query, target) -> AlignmentStatus   src/alignment.rs:231   awv_align_pairs / awv_align_one
  *   wf.score()                                   src/alignment.rs:235   awv_result.score (= -penalty)
  *   wf.cigar() -> &[u8]                          src/alignment.rs:236   CIGAR arena + awv_result.cigar_off/len
@@ -205,6 +206,59 @@ typedef struct {
 } awv_score_result;
 int awv_score_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
                     int32_t max_penalty /* < 0: no bound */, awv_score_result* out /* required */);
+
+/* The same with a bound per pair: max_penalty[i] >= 0 bounds pair i (AWV_ST_ABOVE_BOUND with penalty max_penalty[i] + 1 when its
+ * penalty is proved above it), max_penalty[i] < 0 leaves pair i unbounded.  awv_score_pairs is the one-bound case. */
+int awv_score_pairs_bounded(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
+                            const int32_t* max_penalty /* per pair, < 0: none */, awv_score_result* out /* required */);
+
+/* ---- WFA orientation (determine_orientation_wfa, src/alignment.rs:157-175) ----------------------------------------------
+ * The reference aligns a pair on both strands under the orientation penalties `pen` and takes forward iff
+ * E_f <= E_r, E = #X + #I + #D of the strand's CIGAR.  With P a strand's optimal penalty, every edit column of ANY optimal
+ * CIGAR adds at least cmin = min(x, e1[, e2]) and at most cmax = max(x, o1 + e1) (2-piece: max(x, min(o1 + e1, o2 + e2))), so
+ *     ceil(P / cmax) <= E <= floor(P / cmin).
+ * Hence forward is certain when floor(P_f / cmin) <= ceil(L_r / cmax) for any proved lower bound L_r <= P_r, and reverse is
+ * certain when floor(P_r / cmin) < ceil(L_f / cmax).  awv_orient_pairs decides every pair it can from bounded score-only
+ * searches (a race of a few rounds over a shrinking list of strands; the losing strand's search stops at the bound that
+ * settles the pair) and runs the two full alignments only for the pairs the rule leaves open ("ambiguous").  The strands
+ * are the reference's in either case.
+ * The race is skipped -- every pair goes the full way -- when cmax >= 8 * cmin (AWV_ORIENT_SKIP_RATIO): the rule then
+ * settles next to nothing, and the losing strand would be searched almost to its end anyway.  A single pair leaves the race
+ * for the full alignments as soon as the bound that would settle it exceeds W = G + x * min(plen, tlen) / 2, G the cheapest
+ * gap of |plen - tlen| columns: about what an unrelated strand costs, so that search would complete instead of settling
+ * (very unequal lengths -- before round 0 --, very divergent pairs).  A cost estimate only: the answer is the same. */
+#define AWV_ORIENT_FORWARD 0
+#define AWV_ORIENT_REVERSE 1
+#define AWV_ORIENT_UNDECIDED 2
+#define AWV_ORIENT_SKIP_RATIO 8
+#define AWV_ORIENT_BY_BOUND 0 /* awv_orient_result.how: from the proved penalty intervals */
+#define AWV_ORIENT_BY_EDITS 1 /* from the edit counts of two full alignments */
+#define AWV_ORIENT_FULL 1     /* flags: two full alignments for every pair (the reference's method; yardstick and opt-out) */
+#define AWV_ORIENT_NO_EDITS UINT64_MAX /* edits of a strand that was not aligned in full, or whose alignment failed */
+
+typedef struct {
+  int32_t is_reverse;   /* 1: reverse-complement the query */
+  int32_t how;          /* AWV_ORIENT_BY_BOUND / AWV_ORIENT_BY_EDITS */
+  int32_t lo_f, hi_f;   /* proved interval of the forward strand's penalty; hi = INT32_MAX when only bounded below */
+  int32_t lo_r, hi_r;   /* the reverse-complement strand's */
+  uint64_t edits_f;     /* BY_EDITS: #X + #I + #D of the full alignments (AWV_ORIENT_NO_EDITS: failed); BY_BOUND: NO_EDITS */
+  uint64_t edits_r;
+  int32_t rounds;       /* score-only rounds the pair took part in (0: race skipped) */
+  int32_t reserved;
+} awv_orient_result;
+
+/* Orients pairs[0..npairs) (q_revcomp is ignored).  flags: 0 or AWV_ORIENT_FULL.  awv_engine_stats afterwards reports the
+ * whole call: launches, kernel time, cell-steps ... summed over the race's rounds and the full-alignment tail. */
+int awv_orient_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, int32_t flags,
+                     awv_orient_result* out /* required */);
+/* The rule alone, on the host (needs no device): AWV_ORIENT_FORWARD / _REVERSE / _UNDECIDED from proved penalty intervals
+ * [lo, hi] of the two strands (hi = INT32_MAX: unknown above); AWV_ERR_PENALTIES / AWV_ERR_ARG (< 0) on bad input.  The
+ * race's device kernel applies this very function (csrc/orient_device.hpp). */
+int awv_orient_decide(const awv_penalties* pen, int32_t lo_f, int32_t hi_f, int32_t lo_r, int32_t hi_r);
+/* The bound the race gives the other strand's search once one strand's penalty is known: the smallest B >= 0 such that
+ * "the other strand's penalty exceeds B" (a lower bound of B + 1) settles the pair; -1 when the known penalty settles
+ * it alone (INT32_MAX: no bound; INT32_MIN: bad input).  known_is_reverse: which strand `penalty` belongs to. */
+int32_t awv_orient_settling_bound(const awv_penalties* pen, int32_t known_is_reverse, int32_t penalty);
 
 int awv_engine_stats(const awv_engine* e, awv_stats* out);
 
