@@ -2831,37 +2831,41 @@ __device__ __forceinline__ int base_align(const KParams& kp, Shared& sh, const L
       }
       total += n;
     };
+    // Candidate `ms` of a state at score s on diagonal kk -- 0: M by a mismatch; 1 / 2: I1 opened / extended; 3 / 4: D1; 5 / 6: I2;
+    // 7 / 8: D2 -- is read from row (comp, cs) at diagonal ck.
+    auto cand_desc = [&](int ms, int s, int kk, int& comp, int& cs, int& ck, int& add, int& type) {
+      const bool open = (ms & 1) != 0, two = ms >= 5, ins = ms == 1 || ms == 2 || ms == 5 || ms == 6;
+      comp = (ms == 0 || open) ? C_M : ms == 2 ? C_I1 : ms == 4 ? C_D1 : ms == 6 ? C_I2 : C_D2;
+      cs = ms == 0 ? s - pn.x : s - (two ? pn.e2 : pn.e1) - (open ? (two ? pn.o2 : pn.o1) : 0);
+      ck = ms == 0 ? kk : ins ? kk - 1 : kk + 1;
+      add = (ms == 0 || ins) ? 1 : 0;
+      type = ms == 0 ? BT_M : ms == 1 ? BT_I1_OPEN : ms == 2 ? BT_I1_EXT : ms == 3 ? BT_D1_OPEN : ms == 4 ? BT_D1_EXT
+           : ms == 5 ? BT_I2_OPEN : ms == 6 ? BT_I2_EXT : ms == 7 ? BT_D2_OPEN : BT_D2_EXT;
+    };
+    // lane j's candidate of the current state as one of those nine (M: all of them, five without the second piece; a gap
+    // component: lane 0 = extended, lane 1 = opened); -1: none
+    auto slot_ms = [&](int mat, int j) {
+      if (mat == C_M) return j <= (P2 ? 8 : 4) ? j : -1;
+      const int ext = mat == C_I1 ? 2 : mat == C_D1 ? 4 : mat == C_I2 ? 6 : 8;
+      return j == 0 ? ext : j == 1 ? ext - 1 : -1;
+    };
     int guard = 0;
     while (v > 0 && h > 0 && sc > 0) {
       if (++guard > 4 * (plen + tlen) + 16) { err = ST_INTERNAL; break; }
       const int mismatch = sc - pn.x, gap_open1 = sc - pn.o1 - pn.e1, gap_extend1 = sc - pn.e1;
       const int gap_open2 = sc - pn.o2 - pn.e2, gap_extend2 = sc - pn.e2;
+      // One fetch for all lanes: which row and diagonal a lane reads is arithmetic on its lane number, so the (up to nine)
+      // candidates of a step are ONE pair of vector loads and one wait.  (A branch per lane -- a switch over the lane number with
+      // a fetch in every case -- runs its cases one after the other, each waiting for its own loads: up to nine memory round trips
+      // in series per edit)
       int cand = -1;
-      if (matrix == C_M) {
-        switch (lane) {
-          case 0: cand = bt_fetch(kp, base_meta, hist, kmin, score, C_M, mismatch, k, 1, BT_M); break;
-          case 1: cand = bt_fetch(kp, base_meta, hist, kmin, score, C_M, gap_open1, k - 1, 1, BT_I1_OPEN); break;
-          case 2: cand = bt_fetch(kp, base_meta, hist, kmin, score, C_I1, gap_extend1, k - 1, 1, BT_I1_EXT); break;
-          case 3: cand = bt_fetch(kp, base_meta, hist, kmin, score, C_M, gap_open1, k + 1, 0, BT_D1_OPEN); break;
-          case 4: cand = bt_fetch(kp, base_meta, hist, kmin, score, C_D1, gap_extend1, k + 1, 0, BT_D1_EXT); break;
-          case 5: if (P2) cand = bt_fetch(kp, base_meta, hist, kmin, score, C_M, gap_open2, k - 1, 1, BT_I2_OPEN); break;
-          case 6: if (P2) cand = bt_fetch(kp, base_meta, hist, kmin, score, C_I2, gap_extend2, k - 1, 1, BT_I2_EXT); break;
-          case 7: if (P2) cand = bt_fetch(kp, base_meta, hist, kmin, score, C_M, gap_open2, k + 1, 0, BT_D2_OPEN); break;
-          case 8: if (P2) cand = bt_fetch(kp, base_meta, hist, kmin, score, C_D2, gap_extend2, k + 1, 0, BT_D2_EXT); break;
-          default: break;
+      {
+        const int ms = lane < 9 ? slot_ms(matrix, lane) : -1;
+        if (ms >= 0) {
+          int comp, cs, ck, add, type;
+          cand_desc(ms, sc, k, comp, cs, ck, add, type);
+          cand = bt_fetch(kp, base_meta, hist, kmin, score, comp, cs, ck, add, type);
         }
-      } else if (matrix == C_I1) {
-        if (lane == 0) cand = bt_fetch(kp, base_meta, hist, kmin, score, C_I1, gap_extend1, k - 1, 1, BT_I1_EXT);
-        if (lane == 1) cand = bt_fetch(kp, base_meta, hist, kmin, score, C_M, gap_open1, k - 1, 1, BT_I1_OPEN);
-      } else if (matrix == C_I2) {
-        if (lane == 0) cand = bt_fetch(kp, base_meta, hist, kmin, score, C_I2, gap_extend2, k - 1, 1, BT_I2_EXT);
-        if (lane == 1) cand = bt_fetch(kp, base_meta, hist, kmin, score, C_M, gap_open2, k - 1, 1, BT_I2_OPEN);
-      } else if (matrix == C_D1) {
-        if (lane == 0) cand = bt_fetch(kp, base_meta, hist, kmin, score, C_D1, gap_extend1, k + 1, 0, BT_D1_EXT);
-        if (lane == 1) cand = bt_fetch(kp, base_meta, hist, kmin, score, C_M, gap_open1, k + 1, 0, BT_D1_OPEN);
-      } else {
-        if (lane == 0) cand = bt_fetch(kp, base_meta, hist, kmin, score, C_D2, gap_extend2, k + 1, 0, BT_D2_EXT);
-        if (lane == 1) cand = bt_fetch(kp, base_meta, hist, kmin, score, C_M, gap_open2, k + 1, 0, BT_D2_OPEN);
       }
       // max over lanes 0..15 on the DPP network (row_shr 1, 2, 4, 8 leave it in lane 15; lanes 9.. hold -1)
       cand = max(cand, __builtin_amdgcn_update_dpp(-1, cand, 0x111, 0xf, 0xf, false));
