@@ -45,9 +45,10 @@ HIP_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950"]
 # "iterative-maxocc": 1779-1785 ms against 1719-1737 ms).  Not for engine.hip: there it spills a lane
 # vector inside a pass loop of the 16-bit min(h, v) kernels (scratch/spill_audit.py).
 HIP_FLAGS_AWV = HIP_FLAGS + ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
-HIP_UNITS = (("engine.hip", HIP_FLAGS), ("kernels_awv.hip", HIP_FLAGS_AWV), ("planner.hip", HIP_FLAGS), ("orient.hip", HIP_FLAGS))
+HIP_UNITS = (("engine.hip", HIP_FLAGS), ("kernels_awv.hip", HIP_FLAGS_AWV), ("planner.hip", HIP_FLAGS), ("orient.hip", HIP_FLAGS),
+             ("verify.hip", HIP_FLAGS))
 HIP_SOURCES = [os.path.join(CSRC, f) for f in ("engine.hip", "kernels_awv.hip", "kernels_awv.hpp", "biwfa_device.hpp", "planner.hip",
-                                               "planner_device.hpp", "orient.hip", "orient_device.hpp")] + [ABI_HEADER]
+                                               "planner_device.hpp", "orient.hip", "orient_device.hpp", "verify.hip", "verify_device.hpp")] + [ABI_HEADER]
 
 
 def _host_sources():

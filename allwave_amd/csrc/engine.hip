@@ -8,6 +8,7 @@
 // the device code, once per workgroup size: awv:: one wave per pair (throughput), awvw:: four waves per pair,
 // awvx:: sixteen waves per pair (one pair per CU: the few pairs a large length difference makes enormous)
 #include "planner_device.hpp"  // (the sketches and scratch of device pair planning, planner.hip)
+#include "verify_device.hpp"   // (the per-batch check of awv_align_pairs_verified, verify.hip)
 #include "kernels_awv.hpp"  // (AWV_THRU_WG; the awv:: kernels themselves are instantiated in kernels_awv.hip -- here only the types)
 #define AWV_NS awv
 #define AWV_WG AWV_THRU_WG
@@ -163,6 +164,7 @@ struct awv_engine {
   std::vector<uint8_t> h_cigar;
   awv_stats stats{};
   awp::PlanState* plan = nullptr;  // planner.hip: sketches of `seqs` and planning scratch (released with a new set)
+  awvf::State* verify = nullptr;   // verify.hip: buffers and stats of the verify launches
 };
 
 namespace {
@@ -179,7 +181,7 @@ int upload_seqset(awv_engine* e, SeqSet& s, int32_t n, const uint8_t* bytes, con
     if (l > (uint64_t)(INT32_MAX / 4)) return fail(AWV_ERR_ARG, "set_sequences: sequence too long");
     s.off[i] = run;
     s.len[i] = (int32_t)l;
-    run += l + 8;  // extend reads 8 bytes at a time: keep over-reads inside the allocation
+    run += l + awp::SEQ_PAD_BYTES;  // extend reads 8 bytes at a time: keep over-reads inside the allocation
   }
   s.off[n] = run;
   s.total = run + 64;
@@ -246,11 +248,18 @@ int upload_seqset(awv_engine* e, SeqSet& s, int32_t n, const uint8_t* bytes, con
   return AWV_OK;
 }
 
-int check_penalties(const awv_penalties* p, awv::DevPenalties& d) {
+// what makes a penalty set meaningful at all (the verify check re-scores under any such set: awv_internal_check_penalties)
+int check_penalty_signs(const awv_penalties* p) {
   if (!p) return fail(AWV_ERR_ARG, "penalties: null");
   if (p->match != 0) return fail(AWV_ERR_PENALTIES, "match score must be 0 (WFA2 penalty transformation is out of scope)");
   if (p->mismatch <= 0 || p->gap_open1 < 0 || p->gap_ext1 <= 0) return fail(AWV_ERR_PENALTIES, "need x > 0, o >= 0, e > 0");
   if (p->two_piece && (p->gap_open2 < 0 || p->gap_ext2 <= 0)) return fail(AWV_ERR_PENALTIES, "need o2 >= 0, e2 > 0");
+  return AWV_OK;
+}
+
+// and what the alignment kernels can run: the score ring holds max(x, o1 + e1, o2 + e2) + 1 rows
+int check_penalties(const awv_penalties* p, awv::DevPenalties& d) {
+  if (int rc = check_penalty_signs(p)) return rc;
   d.x = p->mismatch;
   d.o1 = p->gap_open1;
   d.e1 = p->gap_ext1;
@@ -315,9 +324,11 @@ long long worst_case_penalty(const awv::DevPenalties& d, long long n) {
 
 // score_only: awv_score_pairs -- the top-level search's score only, no CIGAR arena (so max_arena_bytes does not cut batches);
 // max_penalty: that call's bound (INT_MAX = none); pair_bound (nullable, score_only): pair i's own bound instead (INT_MAX = none)
+// vout (nullable; awv_align_pairs_verified, on the engine's own sequence set): every batch's records and op bytes are checked
+// on the device before the batch's CIGARs are copied back
 int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
                awv_result* out, awv_sink sink, void* user, bool score_only = false, int max_penalty = INT_MAX,
-               const int32_t* pair_bound = nullptr) {
+               const int32_t* pair_bound = nullptr, awv_verify_result* vout = nullptr) {
   using namespace awv;
   if (npairs < 0 || (npairs > 0 && !pairs)) return fail(AWV_ERR_ARG, "align_pairs: null pairs");
   DevPenalties dp{};
@@ -836,6 +847,10 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
     }
     const bool want_cigar = sink && !score_only && !(e->cfg.flags & AWV_F_KEEP_ON_DEVICE);
     lap("results on host");
+    if (vout) {  // the groups of a batch overwrite d_results: the batch's records, as gathered in hres, go up once for the check
+      if (int rc = awvf::verify_batch(e, pen, pairs + first, n, hres.data(), e->d_cigar.p, arena, vout + first)) return rc;
+      lap("batch verified");
+    }
     if (want_cigar) {
       e->h_cigar.resize((size_t)arena + 64);
       lap("host cigar buffer");
@@ -949,6 +964,8 @@ void awv_engine_destroy(awv_engine* e) {
   (void)hipSetDevice(e->device);
   awp::plan_state_release(e->plan);
   e->plan = nullptr;
+  awvf::state_release(e->verify);
+  e->verify = nullptr;
   e->seqs.release();
   e->ring_mem.release();
   e->hist_mem.release();
@@ -992,6 +1009,15 @@ int awv_align_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pai
   if (!e) return fail(AWV_ERR_ARG, "null engine");
   if (e->seqs.n == 0 && npairs > 0) return fail(AWV_ERR_STATE, "align_pairs before set_sequences");
   AWV_GUARDED(return align_core(e, e->seqs, pen, pairs, npairs, out, sink, user);)
+}
+
+int awv_align_pairs_verified(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, awv_result* out,
+                             awv_verify_result* vout, awv_sink sink, void* user) {
+  if (!e) return fail(AWV_ERR_ARG, "null engine");
+  if (!vout) return fail(AWV_ERR_ARG, "align_pairs_verified: null vout");
+  if (e->seqs.n == 0 && npairs > 0) return fail(AWV_ERR_STATE, "align_pairs before set_sequences");
+  awvf::stats_reset(e->verify);  // the call's batches add to them (a call without pairs launches nothing: its stats are empty)
+  AWV_GUARDED(return align_core(e, e->seqs, pen, pairs, npairs, out, sink, user, false, INT_MAX, nullptr, vout);)
 }
 
 namespace {
@@ -1119,6 +1145,10 @@ int awv_internal_view(awv_engine* e, awp::EngineView* v) {
   return AWV_OK;
 }
 awp::PlanState*& awv_internal_plan(awv_engine* e) { return e->plan; }
+// ---- what verify.hip keeps in an engine, and the arena budget awv_verify_cigars splits its call by (verify_device.hpp) ----
+awvf::State*& awv_internal_verify(awv_engine* e) { return e->verify; }
+uint64_t awv_internal_max_arena(const awv_engine* e) { return e->cfg.max_arena_bytes > 0 ? (uint64_t)e->cfg.max_arena_bytes : (uint64_t)8 << 30; }
 int awv_internal_fail(int code, const std::string& msg) { return fail(code, msg); }
+int awv_internal_check_penalties(const awv_penalties* pen) { return check_penalty_signs(pen); }
 // ---- what orient.hip needs beyond that (orient_device.hpp): the stats of a call made of several engine calls
 void awv_internal_set_stats(awv_engine* e, const awv_stats* st) { e->stats = *st; }

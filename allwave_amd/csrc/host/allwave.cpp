@@ -442,8 +442,10 @@ AllPairIterator AllPairIterator::with_sparsification(SparsificationStrategy stra
   it.threads_ = threads_;
   it.next_chunk_ = next_chunk_;
   it.full_wfa_orientation_ = full_wfa_orientation_;
+  it.verify_ = verify_;
   return it;
 }
+AllPairIterator& AllPairIterator::with_verify(bool on) { verify_ = on; return *this; }
 AllPairIterator& AllPairIterator::with_next_chunk(size_t n) { next_chunk_ = std::max<size_t>(1, n); return *this; }
 AllPairIterator& AllPairIterator::with_threads(int t) { threads_ = t; return *this; }
 AllPairParallelIterator AllPairIterator::into_par_iter() const { return AllPairParallelIterator(*this); }
@@ -566,10 +568,11 @@ void add_stats(awv_stats& acc, const awv_stats& x, bool same_engine) {
   acc.deep_cell_steps += x.deep_cell_steps;
 }
 
-// one batch's engine call: awv_align_pairs, or awv_score_pairs under max_penalty (< 0: no bound) with its results handed
-// to the sink in one call (status and penalty, no arena)
+// one batch's engine call: awv_align_pairs (awv_align_pairs_verified when `vout` is given), or awv_score_pairs under
+// max_penalty (< 0: no bound) with its results handed to the sink in one call (status and penalty, no arena)
 int engine_call(awv_engine* e, bool score_only, int32_t max_penalty, const awv_penalties& pen, const awv_pair* ap, int64_t n,
-                awv_sink sink, void* user) {
+                awv_sink sink, void* user, awv_verify_result* vout) {
+  if (!score_only && vout) return awv_align_pairs_verified(e, &pen, ap, n, nullptr, vout, sink, user);
   if (!score_only) return awv_align_pairs(e, &pen, ap, n, nullptr, sink, user);
   std::vector<awv_score_result> sr((size_t)n);
   const int rc = awv_score_pairs(e, &pen, ap, n, max_penalty, sr.data());
@@ -636,6 +639,9 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   };
   const std::function<void(std::exception_ptr)> fail_fn = fail;
   std::vector<awv_stats> st(S, awv_stats{});
+  const bool verify = verify_ && !call.score_only;
+  std::vector<awv_verify_stats> vst(S, awv_verify_stats{});  // per slot: written by its submitter thread only
+  std::vector<std::vector<VerifyFailure>> vfail(S);
   const awv_penalties pen = to_penalties(params_), open = to_penalties(orientation_params_);
   auto worker = [&](size_t s) {
     awv_engine* e = nullptr;
@@ -688,11 +694,21 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
           }
           return 0;
         };
-        const int rc = engine_call(e, call.score_only, call.max_penalty, pen, ap.data(), m, sink, &ctx);
+        std::vector<awv_verify_result> vr(verify ? (size_t)m : 0);
+        const int rc = engine_call(e, call.score_only, call.max_penalty, pen, ap.data(), m, sink, &ctx, verify ? vr.data() : nullptr);
         lap("aligned + sunk");
         awv_stats x{};
         awv_engine_stats(e, &x);
         add_stats(st[s], x, true);
+        if (verify && rc == AWV_OK) {
+          awv_verify_stats vx{};
+          awv_engine_verify_stats(e, &vx);
+          vst[s].kernel_ms += vx.kernel_ms;
+          vst[s].pairs += vx.pairs;
+          vst[s].failed += vx.failed;
+          vst[s].columns += vx.columns;
+          append_verify_failures(vfail[s], vr.data(), m, first, idx, plist, rev.data());
+        }
         if (ctx.failed) return;  // (the error is already recorded)
         if (rc != AWV_OK) {
           if (rc == AWV_ERR_SINK && stop.load()) return;  // stopped by another slot's error, which is the one reported
@@ -718,6 +734,18 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   slot_stats_ = st;
   stats_ = awv_stats{};
   for (const auto& x : st) add_stats(stats_, x, false);
+  if (first == 0) {  // a run from the list's start begins anew; a later range (next()'s chunks) adds to it
+    verify_failures_.clear();
+    verify_stats_ = awv_verify_stats{};
+  }
+  for (size_t s = 0; s < S; ++s) {
+    verify_stats_.kernel_ms += vst[s].kernel_ms;
+    verify_stats_.pairs += vst[s].pairs;
+    verify_stats_.failed += vst[s].failed;
+    verify_stats_.columns += vst[s].columns;
+    verify_failures_.insert(verify_failures_.end(), vfail[s].begin(), vfail[s].end());
+  }
+  sort_verify_failures(verify_failures_);
   if (err) std::rethrow_exception(err);
 }
 
@@ -797,6 +825,203 @@ std::vector<PairScore> AllPairIterator::scores(std::optional<int> max_penalty) {
       p.penalty = b.res[i].penalty;
     }
   }, EngineCall{true, max_penalty ? *max_penalty : -1});
+  return out;
+}
+
+// ---- verification ---------------------------------------------------------------------------
+const char* verify_code_name(int32_t code) {
+  static const char* const names[] = {"ok", "skipped", "bad_op", "overrun", "m_differs", "x_equal", "short", "counts", "penalty"};
+  return code >= 0 && code <= AWV_VF_PENALTY ? names[code] : "unknown";
+}
+
+void append_verify_failures(std::vector<VerifyFailure>& out, const awv_verify_result* vr, int64_t m, size_t first, const size_t* idx,
+                            const std::pair<size_t, size_t>* plist, const uint8_t* rev) {
+  for (int64_t i = 0; i < m; ++i) {
+    if (vr[i].code == AWV_VF_OK || vr[i].code == AWV_VF_SKIPPED) continue;
+    const size_t k = idx ? idx[i] : (size_t)i;
+    out.push_back(VerifyFailure{first + k, plist[k].first, plist[k].second, rev[i] != 0, vr[i].code, vr[i].column, vr[i].penalty});
+  }
+}
+
+void sort_verify_failures(std::vector<VerifyFailure>& f) {
+  std::sort(f.begin(), f.end(), [](const VerifyFailure& a, const VerifyFailure& b) { return a.index < b.index; });
+}
+
+int report_verify_failures(const std::vector<VerifyFailure>& vf, const std::vector<Sequence>& sequences, std::string& out, size_t limit) {
+  for (size_t i = 0; i < vf.size() && i < limit; ++i)
+    out += "verify: pair " + std::to_string(vf[i].index) + " " + sequences[vf[i].query_idx].id + " " + sequences[vf[i].target_idx].id + " " +
+           (vf[i].is_reverse ? '-' : '+') + " " + verify_code_name(vf[i].code) + " column " + std::to_string(vf[i].column) + " penalty " +
+           std::to_string(vf[i].penalty) + "\n";
+  if (vf.size() > limit) out += "verify: ... and " + std::to_string(vf.size() - limit) + " more\n";
+  return vf.empty() ? 0 : 4;
+}
+
+bool cigar_string_to_bytes(const std::string& cg, std::vector<uint8_t>& ops) {
+  ops.clear();
+  size_t i = 0;
+  while (i < cg.size()) {
+    uint64_t len = 0;
+    size_t d = 0;
+    while (i < cg.size() && cg[i] >= '0' && cg[i] <= '9' && d < 10) {
+      len = len * 10 + (uint64_t)(cg[i] - '0');
+      ++i;
+      ++d;
+    }
+    if (d == 0 || len == 0 || i >= cg.size() || ops.size() + len > (uint64_t)INT32_MAX) return false;
+    uint8_t op;
+    switch (cg[i++]) {  // append_cigar's mapping undone
+      case '=': op = 'M'; break;
+      case 'X': op = 'X'; break;
+      case 'D': op = 'I'; break;
+      case 'I': op = 'D'; break;
+      default: return false;
+    }
+    ops.insert(ops.end(), (size_t)len, op);
+  }
+  return true;
+}
+
+namespace {
+bool parse_size(const std::string& s, size_t& v) {
+  if (s.empty() || s.size() > 18 || s.find_first_not_of("0123456789") != std::string::npos) return false;
+  v = (size_t)strtoull(s.c_str(), nullptr, 10);
+  return true;
+}
+}  // namespace
+
+PafCheckReport check_paf(const std::vector<Sequence>& sequences, const std::string& paf_text, const AlignmentParams& params,
+                         bool optimal, int device) {
+  PafCheckReport rep;
+  std::map<std::string, size_t> by_name;
+  for (size_t i = 0; i < sequences.size(); ++i) by_name.emplace(sequences[i].id, i);  // (the first of equal names)
+  struct Entry {
+    size_t failure;  // index into `pending`
+    size_t col10, col11, qspan, tspan;
+  };
+  // every non-empty line gets a slot of `pending` (cls empty: nothing found so far); the device-checked ones also an Entry
+  std::vector<PafCheckFailure> pending;
+  std::vector<Entry> entries;
+  std::vector<awv_pair> ap;
+  std::vector<awv_result> recs;
+  std::vector<uint8_t> arena, ops;
+  size_t pos = 0, line_no = 0;
+  while (pos < paf_text.size()) {
+    size_t nl = paf_text.find('\n', pos);
+    if (nl == std::string::npos) nl = paf_text.size();
+    std::string line = paf_text.substr(pos, nl - pos);
+    pos = nl + 1;
+    ++line_no;
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    if (line.empty()) continue;
+    ++rep.lines;
+    std::vector<std::string> f;
+    for (size_t b = 0;;) {
+      const size_t e = line.find('\t', b);
+      f.push_back(line.substr(b, e == std::string::npos ? std::string::npos : e - b));
+      if (e == std::string::npos) break;
+      b = e + 1;
+    }
+    PafCheckFailure pf;
+    pf.line = line_no;
+    if (f.size() > 0) pf.qname = f[0];
+    if (f.size() > 5) pf.tname = f[5];
+    if (f.size() > 4 && f[4].size() == 1) pf.strand = f[4][0];
+    const std::string* cg = nullptr;
+    for (size_t k = 12; k < f.size(); ++k)
+      if (f[k].compare(0, 5, "cg:Z:") == 0) cg = &f[k];
+    size_t qlen, qs, qe, tlen, ts, te, c10, c11;
+    if (f.size() < 12 || !cg || (pf.strand != '+' && pf.strand != '-') || !parse_size(f[1], qlen) || !parse_size(f[2], qs) ||
+        !parse_size(f[3], qe) || !parse_size(f[6], tlen) || !parse_size(f[7], ts) || !parse_size(f[8], te) || !parse_size(f[9], c10) ||
+        !parse_size(f[10], c11)) {
+      pf.cls = "bad_line";
+      pending.push_back(pf);
+      continue;
+    }
+    const auto qi = by_name.find(pf.qname), ti = by_name.find(pf.tname);
+    if (qi == by_name.end() || ti == by_name.end()) {
+      pf.cls = "unknown_name";
+    } else if (qlen != sequences[qi->second].seq.size() || tlen != sequences[ti->second].seq.size()) {
+      pf.cls = "length_mismatch";
+    } else if (cg->size() == 5 && qs == 0 && qe == 0 && ts == 0 && te == 0) {
+      ++rep.skipped;  // the empty record a failed pair leaves
+      continue;
+    } else if (qs != 0 || ts != 0 || qe != qlen || te != tlen) {
+      pf.cls = "not_end_to_end";
+    } else if (!cigar_string_to_bytes(cg->substr(5), ops)) {
+      pf.cls = "bad_cigar";
+    }
+    if (!pf.cls.empty()) {
+      pending.push_back(pf);
+      continue;
+    }
+    awv_result r{};
+    r.status = AWV_ST_COMPLETED;
+    r.cigar_off = arena.size();
+    r.cigar_len = (uint32_t)ops.size();
+    int64_t nx = 0, ni = 0, nd = 0;
+    for (uint8_t op : ops) {
+      nx += op == 'X';
+      ni += op == 'I';
+      nd += op == 'D';
+    }
+    r.num_matches = (int32_t)std::min<size_t>(c10, INT32_MAX);  // the line's claim; the other counts are the string's own
+    r.num_mismatches = (int32_t)nx;
+    r.num_ins = (int32_t)ni;
+    r.num_del = (int32_t)nd;
+    r.q_end = (int32_t)qe;
+    r.t_end = (int32_t)te;
+    arena.insert(arena.end(), ops.begin(), ops.end());
+    ap.push_back(awv_pair{(int32_t)qi->second, (int32_t)ti->second, pf.strand == '-' ? 1 : 0});
+    recs.push_back(r);
+    entries.push_back(Entry{pending.size(), c10, c11, qe - qs, te - ts});
+    pending.push_back(pf);
+  }
+  rep.checked = entries.size();
+  if (!entries.empty()) {
+    const awv_penalties pen = to_penalties(params);
+    std::unique_lock<std::mutex> lock(*slot_mutex(device, 0));
+    awv_engine* e = slot_engine(device, 0, 1);
+    upload(e, sequences);
+    std::vector<awv_verify_result> vr(entries.size());
+    arena.resize(arena.size() + 16);  // (never an empty arena)
+    if (awv_verify_cigars(e, &pen, ap.data(), (int64_t)ap.size(), recs.data(), arena.data(), arena.size(), vr.data()) != AWV_OK)
+      throw AlignmentError(std::string("verify_cigars: ") + awv_last_error());
+    awv_engine_verify_stats(e, &rep.stats);
+    std::vector<awv_score_result> sr;
+    if (optimal) {
+      sr.resize(entries.size());
+      if (awv_score_pairs(e, &pen, ap.data(), (int64_t)ap.size(), -1, sr.data()) != AWV_OK)
+        throw AlignmentError(std::string("score_pairs: ") + awv_last_error());
+    }
+    for (size_t k = 0; k < entries.size(); ++k) {
+      PafCheckFailure& pf = pending[entries[k].failure];
+      const awv_verify_result& v = vr[k];
+      pf.column = v.column;
+      pf.penalty = v.penalty;
+      // (the record carries no penalty: AWV_VF_PENALTY, the last check in order, means every other one passed)
+      const bool valid = v.code == AWV_VF_OK || v.code == AWV_VF_PENALTY;
+      if (!valid) pf.cls = verify_code_name(v.code);
+      else if (entries[k].col11 != std::max(entries[k].qspan, entries[k].tspan)) pf.cls = "counts";
+      if (optimal && valid && sr[k].status == AWV_ST_COMPLETED) {
+        pf.optimum = sr[k].penalty;
+        if (pf.cls.empty() && v.penalty > pf.optimum) pf.cls = "not_optimal";
+        if (pf.cls.empty() && v.penalty < pf.optimum) pf.cls = "below_optimum";
+      }
+    }
+  }
+  for (auto& pf : pending)
+    if (!pf.cls.empty()) rep.failures.push_back(std::move(pf));
+  return rep;
+}
+
+std::string format_paf_check(const PafCheckReport& r) {
+  std::string out;
+  for (const PafCheckFailure& f : r.failures) {
+    out += std::to_string(f.line) + '\t' + f.qname + '\t' + f.tname + '\t' + f.strand + '\t' + f.cls + '\t' + std::to_string(f.column) +
+           '\t' + std::to_string(f.penalty);
+    if (f.optimum >= 0) out += '\t' + std::to_string(f.optimum);
+    out.push_back('\n');
+  }
   return out;
 }
 

@@ -9,6 +9,7 @@
 //   cigar_bytes_to_string, reverse_complement, align_pair's result mapping       src/alignment.rs:25-66,178-190,347-376
 //   AllPairIterator (-p none enumeration, WFA orientation, callback streaming)   src/iterator.rs:12-253
 //   wfa::align_sequences / validate_cigar_alignment                              src/wfa.rs:105-258
+// This build's own: on-device verification of the alignments a run produces (with_verify) and of a PAF file (check_paf).
 // Pair planning (mash orientation, sparsifiers, kNN/tree pairs) lives in planner.hpp; the CLI in main.cpp.
 #pragma once
 
@@ -95,6 +96,25 @@ struct PairScore {
 
 using Callback = std::function<void(AlignmentResult&&)>;  // may throw: first error aborts the run
 
+// One pair whose alignment did not pass the on-device check (AllPairIterator::with_verify): code = AWV_VF_*, column and
+// penalty as in awv_verify_result.
+struct VerifyFailure {
+  size_t index = 0;  // in the pair list
+  size_t query_idx = 0, target_idx = 0;
+  bool is_reverse = false;
+  int32_t code = 0;
+  int64_t column = -1, penalty = -1;
+};
+// What run() does with one engine call's verify results vr[0, m): entry i of the call is entry k = idx ? idx[i] : i of the
+// run's range plist (pair-list index first + k), on strand rev[i]; every code other than OK / SKIPPED is appended.
+void append_verify_failures(std::vector<VerifyFailure>& out, const awv_verify_result* vr, int64_t m, size_t first, const size_t* idx,
+                            const std::pair<size_t, size_t>* plist, const uint8_t* rev);
+void sort_verify_failures(std::vector<VerifyFailure>& f);  // by pair-list index (the slots' lists, merged)
+// `--verify`'s report: up to `limit` lines `verify: pair <index> <qname> <tname> <strand> <class> column <c> penalty <p>`
+// appended to `out`; returns the exit status, 4 when there is a failure, else 0
+int report_verify_failures(const std::vector<VerifyFailure>& vf, const std::vector<Sequence>& sequences, std::string& out, size_t limit = 20);
+const char* verify_code_name(int32_t code);  // "ok", "skipped", "bad_op", "overrun", "m_differs", "x_equal", "short", "counts", "penalty"
+
 // awv_engine_config.flags (AWV_F_*) for the per-device engines this library creates from now on
 // (an engine lives for the rest of the process once created).
 void set_engine_flags(int flags);
@@ -139,6 +159,16 @@ class AllPairIterator {  // iterator.rs:12-171
   // fewer edits, and aligns both strands in full only where they do not; true: both strands in full for every pair, the
   // reference's method (AWV_ORIENT_FULL).  The strands chosen are the same.
   AllPairIterator& with_full_wfa_orientation(bool full);
+  // Every alignment consumer (for_each_with_callback, for_each_paf_batch, next, into_par_iter, collect) goes through
+  // awv_align_pairs_verified: each batch's records and op bytes are checked on the device before they are copied back.  The
+  // results handed out are the same; what failed is listed by verify_failures().  scores() ignores the setting, and the
+  // strand alignments inside WFA orientation are not checked: only the final ones are.
+  AllPairIterator& with_verify(bool on);
+  bool verify() const { return verify_; }
+  // of the last run (next(): of the chunks since the list's start): the failed pairs sorted by pair-list index, and the
+  // verify counters summed over the slots (kernel_ms: summed kernel time)
+  const std::vector<VerifyFailure>& verify_failures() const { return verify_failures_; }
+  awv_verify_stats last_verify_stats() const { return verify_stats_; }
   AllPairIterator& with_device(int device);  // = with_devices({device})
   // Aligns the pair list on several engines at once, one "slot" per entry: an ordinal may appear more than once, and each
   // occurrence is an engine of its own (stream, arenas; the slots of one device split its default scratch budget).  With
@@ -203,6 +233,9 @@ class AllPairIterator {  // iterator.rs:12-171
   bool exclude_self_ = true;
   Orientation orientation_ = Orientation::Wfa;
   bool full_wfa_orientation_ = false;
+  bool verify_ = false;
+  std::vector<VerifyFailure> verify_failures_;
+  awv_verify_stats verify_stats_{};
   std::vector<int> devices_{0};
   size_t min_batch_pairs_ = 16384;
   int threads_ = 0;
@@ -227,6 +260,8 @@ class AllPairParallelIterator {
   std::vector<AlignmentResult> collect();           // rayon's collect() on the parallel iterator: results in pair-list order
   awv_stats last_stats() const { return it_.last_stats(); }
   const std::vector<awv_stats>& last_slot_stats() const { return it_.last_slot_stats(); }
+  const std::vector<VerifyFailure>& verify_failures() const { return it_.verify_failures(); }
+  awv_verify_stats last_verify_stats() const { return it_.last_verify_stats(); }
  private:
   friend class AllPairIterator;
   explicit AllPairParallelIterator(const AllPairIterator& it) : it_(it) {}
@@ -243,6 +278,36 @@ void process_alignments_with_callback(const std::vector<Sequence>& sequences, Al
 void process_alignments_with_callback(const std::vector<Sequence>& sequences, AlignmentParams params,
                                       SparsificationStrategy sparsification, const Callback& callback,
                                       const std::vector<int>& devices);
+
+// ---- checking a PAF file against the sequences, on the device (nothing is aligned) ----
+// the op bytes of a PAF cg string, cigar_bytes_to_string undone ('=' -> M, X -> X, D -> I, I -> D); false when the string
+// is not <count><op>... over those four letters with counts >= 1
+bool cigar_string_to_bytes(const std::string& cg, std::vector<uint8_t>& ops);
+
+struct PafCheckFailure {
+  size_t line = 0;  // 1-based line of the PAF text
+  std::string qname, tname;
+  char strand = '?';
+  // host-side: "bad_line", "unknown_name", "length_mismatch", "not_end_to_end", "bad_cigar"; from the device check:
+  // "bad_op", "overrun", "m_differs", "x_equal", "short", "counts"; with `optimal`: "not_optimal", "below_optimum"
+  std::string cls;
+  int64_t column = -1, penalty = -1;  // as in awv_verify_result
+  int64_t optimum = -1;               // with `optimal`, for lines whose op string is valid: the optimal penalty (-1: none)
+};
+struct PafCheckReport {
+  size_t lines = 0, checked = 0, skipped = 0;  // non-empty lines; lines that went through the device check; empty records
+  std::vector<PafCheckFailure> failures;       // in line order
+  awv_verify_stats stats{};
+};
+// Every line of `paf_text` (12 columns and a cg:Z: tag, as alignment_to_paf writes them) against `sequences` under `params`:
+// names, lengths and end-to-end coordinates on the host, the op string and the counts (column 10 = #M, column 11 = the
+// longer span) through awv_verify_cigars on `device`.  A line carries no penalty: the re-scored one is reported and never
+// compared.  optimal: awv_score_pairs on the same (pair, strand) list as well; an op string that costs more than the
+// optimum is "not_optimal", one that costs less "below_optimum" (a finding against the engine, not the PAF).
+PafCheckReport check_paf(const std::vector<Sequence>& sequences, const std::string& paf_text, const AlignmentParams& params,
+                         bool optimal, int device = 0);
+// one tab-separated line per failure: line qname tname strand class column penalty [optimum]
+std::string format_paf_check(const PafCheckReport& r);
 
 namespace wfa {  // src/wfa.rs
 struct Penalties { int32_t mismatch, gap_opening1, gap_extension1, gap_opening2, gap_extension2; };

@@ -15,6 +15,15 @@ namespace {
 void set_err(char* err, size_t cap, const std::string& m) {
   if (err && cap) snprintf(err, cap, "%s", m.c_str());
 }
+// On-device verification: the alignment hooks below take `verify` (AllPairIterator::with_verify) and leave their verify
+// counters and failures here, per calling thread, for awh_last_verify.
+thread_local awv_verify_stats g_verify_stats{};
+thread_local std::vector<VerifyFailure> g_verify_failures;
+void keep_verify(const awv_verify_stats& st, const std::vector<VerifyFailure>& f) {
+  g_verify_stats = st;
+  g_verify_failures = f;
+}
+
 std::vector<Sequence> make_seqs(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs) {
   std::vector<Sequence> s((size_t)n);
   for (int i = 0; i < n; ++i) {
@@ -85,7 +94,8 @@ int awh_format_paf(const char* qid, size_t qlen, const char* tid, size_t tlen, s
 // default; slot_stats: nullable, n_devices entries); out = the PAF lines
 int awh_all_pairs_paf_devices(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores,
                               const char* sparsification, int orientation, int exclude_self, const int32_t* devices, int n_devices,
-                              int64_t min_batch_pairs, awv_stats* slot_stats, char** out, size_t* out_len, char* err, size_t cap) {
+                              int64_t min_batch_pairs, int verify, awv_stats* slot_stats, char** out, size_t* out_len, char* err,
+                              size_t cap) {
   try {
     const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
     AllPairIterator it = AllPairIterator::with_options(seqs, parse_scores(scores), exclude_self != 0, orientation == 2,
@@ -95,11 +105,13 @@ int awh_all_pairs_paf_devices(int n, const char* const* ids, const uint8_t* byte
     if (!devices || n_devices < 1) throw std::invalid_argument("awh_all_pairs_paf: empty device list");
     it.with_devices(std::vector<int>(devices, devices + n_devices));
     if (min_batch_pairs > 0) it.with_min_batch_pairs((size_t)min_batch_pairs);
+    it.with_verify(verify != 0);
     std::string all;
     it.for_each_with_callback([&](AlignmentResult&& r) {  // the reference's own per-record path
       all += alignment_to_paf(r, seqs);
       all.push_back('\n');
     });
+    keep_verify(it.last_verify_stats(), it.verify_failures());
     if (slot_stats) for (int k = 0; k < n_devices; ++k) slot_stats[k] = it.last_slot_stats()[(size_t)k];
     *out = (char*)malloc(all.size() + 1);
     memcpy(*out, all.c_str(), all.size() + 1);
@@ -125,8 +137,8 @@ int awh_all_pairs_paf_devices(int n, const char* const* ids, const uint8_t* byte
 int awh_iterate_devices(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores,
                         const char* sparsification, int orientation, int mode, int threads, int chunk, int resparsify, long fail_at,
                         const int32_t* devices, int n_devices, int64_t min_batch_pairs, int64_t shard_rank, int64_t shard_world,
-                        awv_stats* slot_stats, char** out, size_t* out_len, size_t* n_records, size_t* late_calls, char* err,
-                        size_t cap) {
+                        int verify_on, awv_stats* slot_stats, char** out, size_t* out_len, size_t* n_records, size_t* late_calls,
+                        char* err, size_t cap) {
   if (!devices || n_devices < 1) { set_err(err, cap, "awh_iterate_devices: empty device list"); return -1; }
   size_t seen = 0, late = 0;
   bool thrown = false;
@@ -151,13 +163,16 @@ int awh_iterate_devices(int n, const char* const* ids, const uint8_t* bytes, con
     };
     const std::vector<int> devs(devices, devices + n_devices);
     std::vector<awv_stats> st;
-    if (mode == 4 && min_batch_pairs <= 0) {
+    const bool verify = verify_on != 0;
+    if (mode == 4 && min_batch_pairs <= 0 && !verify) {
       process_alignments_with_callback(seqs, parse_scores(scores), strat, record, devs);
-    } else if (mode == 4) {  // what that overload does, with the batch size of the call
+    } else if (mode == 4) {  // what that overload does, with the batch size of the call and the check
       AllPairIterator it = AllPairIterator::with_options(seqs, parse_scores(scores), true, true, strat);
-      it.with_devices(devs).with_min_batch_pairs((size_t)min_batch_pairs);
+      it.with_devices(devs).with_verify(verify);
+      if (min_batch_pairs > 0) it.with_min_batch_pairs((size_t)min_batch_pairs);
       it.for_each_with_callback(record);
       st = it.last_slot_stats();
+      keep_verify(it.last_verify_stats(), it.verify_failures());
     } else {
       AllPairIterator it0 = AllPairIterator::with_options(seqs, parse_scores(scores), true, orientation == 2,
                                                          resparsify ? SparsificationStrategy{} : strat);
@@ -166,11 +181,12 @@ int awh_iterate_devices(int n, const char* const* ids, const uint8_t* bytes, con
       if (shard_world > 1) it0.with_shard((size_t)shard_rank, (size_t)shard_world);
       if (min_batch_pairs > 0) it0.with_min_batch_pairs((size_t)min_batch_pairs);
       if (chunk > 0) it0.with_next_chunk((size_t)chunk);
+      it0.with_verify(verify);
       AllPairIterator it = resparsify ? it0.with_sparsification(strat).with_shard((size_t)shard_rank, (size_t)shard_world) : it0;
-      if (mode == 0) { it.for_each_with_callback(record); st = it.last_slot_stats(); }
-      else if (mode == 1) { while (auto r = it.next()) record(std::move(*r)); st = it.last_slot_stats(); }
-      else if (mode == 2) { auto par = it.into_par_iter(); par.with_threads(threads).for_each_with_callback(record); st = par.last_slot_stats(); }
-      else if (mode == 3) { auto par = it.into_par_iter(); for (auto& r : par.collect()) record(std::move(r)); st = par.last_slot_stats(); }
+      if (mode == 0) { it.for_each_with_callback(record); st = it.last_slot_stats(); keep_verify(it.last_verify_stats(), it.verify_failures()); }
+      else if (mode == 1) { while (auto r = it.next()) record(std::move(*r)); st = it.last_slot_stats(); keep_verify(it.last_verify_stats(), it.verify_failures()); }
+      else if (mode == 2) { auto par = it.into_par_iter(); par.with_threads(threads).for_each_with_callback(record); st = par.last_slot_stats(); keep_verify(par.last_verify_stats(), par.verify_failures()); }
+      else if (mode == 3) { auto par = it.into_par_iter(); for (auto& r : par.collect()) record(std::move(r)); st = par.last_slot_stats(); keep_verify(par.last_verify_stats(), par.verify_failures()); }
       else throw std::invalid_argument("awh_iterate_devices: unknown mode");
     }
     if (slot_stats)
@@ -225,7 +241,7 @@ int awh_all_pairs_scores(int n, const char* const* ids, const uint8_t* bytes, co
 // their sum, out_checksum (nullable) the sum of the lines' FNV-1a hashes (the same for the same lines in any order)
 int awh_all_pairs_paf_count_devices(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores,
                                     int orientation, const char* sparsification, const int32_t* devices, int n_devices,
-                                    int64_t min_batch_pairs, int format_threads, uint64_t* out_bytes, uint64_t* out_lines,
+                                    int64_t min_batch_pairs, int format_threads, int verify, uint64_t* out_bytes, uint64_t* out_lines,
                                     uint64_t* out_checksum, double* secs, awv_stats* st, awv_stats* slot_stats, char* err, size_t cap) {
   if (!devices || n_devices < 1) { set_err(err, cap, "awh_all_pairs_paf_count_devices: empty device list"); return -1; }
   try {
@@ -238,6 +254,7 @@ int awh_all_pairs_paf_count_devices(int n, const char* const* ids, const uint8_t
     it.with_full_wfa_orientation(orientation == 3);
     if (min_batch_pairs > 0) it.with_min_batch_pairs((size_t)min_batch_pairs);
     it.with_threads(format_threads);  // this call's sketching / orientation threads: carried by the iterator, not a process-wide setting
+    it.with_verify(verify != 0);
     uint64_t nb = 0, nl = 0, sum = 0;
     const auto t0 = std::chrono::steady_clock::now();
     it.for_each_paf_batch([&](const std::string& s) {
@@ -255,6 +272,7 @@ int awh_all_pairs_paf_count_devices(int n, const char* const* ids, const uint8_t
     *out_bytes = nb;
     *out_lines = nl;
     if (out_checksum) *out_checksum = sum;
+    keep_verify(it.last_verify_stats(), it.verify_failures());
     if (st) *st = it.last_stats();
     if (slot_stats) for (int k = 0; k < n_devices; ++k) slot_stats[k] = it.last_slot_stats()[(size_t)k];
     return 0;
@@ -442,6 +460,85 @@ void awh_set_engine_config(int flags, int first_row_cols, int release) {
   if (release) release_engines();
   set_engine_flags(flags);
   set_engine_first_row_cols(first_row_cols);
+}
+
+// ---- on-device verification ----
+// The path a failed check takes above the engine, without an engine: verify results (code, column, penalty per entry) of
+// `calls` engine calls -- call c covers entries [cuts[c], cuts[c + 1]) of the arrays, each entry naming its place idx[i] in
+// the run's range of `npairs` pairs (q, t) that starts at pair-list index `first` -- go through append_verify_failures one
+// call at a time, in the order given (as slots finish in any order), then sort_verify_failures; the result is left for
+// awh_last_verify, and report (cap bytes) receives report_verify_failures' lines.  Returns its exit status.
+int awh_verify_failure_path(int n, const char* const* ids, const int64_t* pairs, size_t npairs, size_t first, const int64_t* idx,
+                            const uint8_t* rev, const int32_t* code, const int64_t* column, const int64_t* penalty,
+                            const size_t* cuts, size_t calls, char* report, size_t cap) {
+  std::vector<Sequence> seqs((size_t)n);
+  for (int i = 0; i < n; ++i) seqs[(size_t)i].id = ids[i];
+  std::vector<std::pair<size_t, size_t>> plist(npairs);
+  for (size_t i = 0; i < npairs; ++i) plist[i] = {(size_t)pairs[2 * i], (size_t)pairs[2 * i + 1]};
+  std::vector<VerifyFailure> all;
+  awv_verify_stats st{};
+  for (size_t c = 0; c < calls; ++c) {
+    const size_t lo = cuts[c], hi = cuts[c + 1];
+    std::vector<awv_verify_result> vr(hi - lo);
+    std::vector<size_t> ix(hi - lo);
+    for (size_t i = lo; i < hi; ++i) {
+      vr[i - lo] = awv_verify_result{code[i], 0, column[i], penalty[i]};
+      ix[i - lo] = (size_t)idx[i];
+      st.failed += code[i] != AWV_VF_OK && code[i] != AWV_VF_SKIPPED;
+    }
+    st.pairs += hi - lo;
+    append_verify_failures(all, vr.data(), (int64_t)(hi - lo), first, ix.data(), plist.data(), rev + lo);
+  }
+  sort_verify_failures(all);
+  keep_verify(st, all);
+  std::string text;
+  const int status = report_verify_failures(all, seqs, text);
+  snprintf(report, cap, "%s", text.c_str());
+  return status;
+}
+
+// what the calling thread's last alignment hook left: last_verify_stats() and verify_failures() as malloc'ed int64 records of seven (pair-list
+// index, query_idx, target_idx, is_reverse, code, column, penalty)
+int awh_last_verify(awv_verify_stats* st, int64_t** out, size_t* n) {
+  *st = g_verify_stats;
+  *out = (int64_t*)malloc(sizeof(int64_t) * 7 * (g_verify_failures.size() + 1));
+  if (!*out) return -1;
+  for (size_t i = 0; i < g_verify_failures.size(); ++i) {
+    const VerifyFailure& f = g_verify_failures[i];
+    int64_t* o = *out + 7 * i;
+    o[0] = (int64_t)f.index; o[1] = (int64_t)f.query_idx; o[2] = (int64_t)f.target_idx; o[3] = f.is_reverse ? 1 : 0;
+    o[4] = f.code; o[5] = f.column; o[6] = f.penalty;
+  }
+  *n = g_verify_failures.size();
+  return 0;
+}
+
+// cigar_string_to_bytes: the op bytes of a cg string into out[0, cap); returns their number, -1 for a malformed string, -2
+// when cap is too small
+long awh_cigar_string_to_bytes(const char* cg, uint8_t* out, size_t cap) {
+  std::vector<uint8_t> ops;
+  if (!cigar_string_to_bytes(cg, ops)) return -1;
+  if (ops.size() > cap) return -2;
+  if (!ops.empty()) memcpy(out, ops.data(), ops.size());
+  return (long)ops.size();
+}
+
+// check_paf on `device`: out = format_paf_check's lines (malloc'ed), counts = {lines, checked, skipped, failures}
+int awh_check_paf(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores, const char* paf,
+                  size_t paf_len, int optimal, int device, char** out, size_t* out_len, uint64_t counts[4], awv_verify_stats* st,
+                  char* err, size_t cap) {
+  try {
+    const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
+    const PafCheckReport r = check_paf(seqs, std::string(paf, paf_len), parse_scores(scores), optimal != 0, device);
+    const std::string txt = format_paf_check(r);
+    *out = (char*)malloc(txt.size() + 1);
+    if (!*out) throw std::bad_alloc();
+    memcpy(*out, txt.c_str(), txt.size() + 1);
+    *out_len = txt.size();
+    counts[0] = r.lines; counts[1] = r.checked; counts[2] = r.skipped; counts[3] = r.failures.size();
+    if (st) *st = r.stats;
+    return 0;
+  } catch (const std::exception& e) { set_err(err, cap, e.what()); return -1; }
 }
 
 void awh_free(void* p) { free(p); }

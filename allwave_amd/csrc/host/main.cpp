@@ -5,7 +5,9 @@
 // Extensions: --device N (GPU ordinal), --devices LIST (several GPUs, or engines, in this one process),
 // --shard R/N (this process's part of the pair list), --forward-only (skip orientation: all '+'),
 // --wfa-orientation-full (WFA orientation by two full alignments per pair, the reference's method, instead of bounded scores),
-// --score-only (penalties instead of PAF: WFA2's ComputeScore scope) with an optional --max-penalty N bound.
+// --score-only (penalties instead of PAF: WFA2's ComputeScore scope) with an optional --max-penalty N bound,
+// --verify (check every alignment on the device before it is written; exit status 4 when one fails),
+// --check-paf FILE [--check-optimal] (check an existing PAF against the FASTA on the device; nothing is aligned).
 // -t sets the host threads used for PAF formatting / sketching (alignment itself runs on the GPU).
 #include <zlib.h>
 
@@ -37,6 +39,9 @@ struct Args {
   long max_penalty = -1;    // --max-penalty N (with --score-only): pairs whose penalty exceeds N are left out
   bool have_max_penalty = false;
   int plan_device = -1;     // --plan-device N: plan the pair list, the mash matrix and mash orientation on device N
+  bool verify = false;      // --verify: awv_align_pairs_verified; `verified N pairs, F failed, K ms` on the summary line
+  std::string check_paf;    // --check-paf FILE: check that PAF against the input instead of aligning
+  bool have_check_paf = false, check_optimal = false;
 };
 
 [[noreturn]] void die(const std::string& m, int code = 2) {
@@ -187,6 +192,9 @@ int main(int argc, char** argv) {
     else if (k == "--device") { a.device = atoi(val().c_str()); a.have_device = true; }
     else if (k == "--devices") { a.devices = val(); a.have_devices = true; }
     else if (k == "--score-only") a.score_only = true;
+    else if (k == "--verify") a.verify = true;
+    else if (k == "--check-paf") { a.check_paf = val(); a.have_check_paf = true; }
+    else if (k == "--check-optimal") a.check_optimal = true;
     else if (k == "--plan-device") {
       const std::string v = val();
       if (v.empty() || v.size() > 6 || v.find_first_not_of("0123456789") != std::string::npos) die("--plan-device expects a device ordinal N >= 0");
@@ -211,7 +219,13 @@ int main(int argc, char** argv) {
     else if (k == "-h" || k == "--help") {
       std::cout << "usage: allwave_hip -i in.fa [-o out.paf] [-s m,x,o,e[,o2,e2] | -x ANI] [-p none|auto|random:f|giant:p|tree:n:f:r[:k]]\n"
                    "                   [-t threads] [--wfa-orientation|--wfa-orientation-full|--forward-only] [-k prefixes | -e prefixes] [--mash-matrix]\n"
-                   "                   [--device N | --devices LIST] [--shard R/N] [--score-only [--max-penalty N]] [--plan-device N]\n"
+                   "                   [--device N | --devices LIST] [--shard R/N] [--score-only [--max-penalty N]] [--plan-device N] [--verify]\n"
+                   "       allwave_hip -i in.fa --check-paf FILE [-s scores | -x ANI] [--check-optimal] [--device N]\n"
+                   "  --verify         check every alignment on the device before it is written (columns, counts, penalty); the summary\n"
+                   "                   line gains `verified N pairs, F failed, K ms`, failures go to stderr, exit status 4 if any\n"
+                   "  --check-paf FILE align nothing: check every line of FILE (12 columns + cg:Z:) against in.fa on the device; one line\n"
+                   "                   `line qname tname strand class column penalty [optimum]` per failing PAF line, exit status 0 or 4\n"
+                   "  --check-optimal  with --check-paf: also compare each op string's penalty with the optimal one (score-only alignment)\n"
                    "  --devices LIST   align on several devices in this process: ordinals and ranges, e.g. 0,1,2 / 0-7 / all;\n"
                    "                   an ordinal may repeat (0,0: two engines on device 0); -t is shared out among them\n"
                    "  --score-only     no PAF: one tab-separated line per pair, `qname qlen tname tlen strand penalty`, in pair-list\n"
@@ -223,6 +237,11 @@ int main(int argc, char** argv) {
     } else die("unexpected argument: " + k);
   }
   if (a.have_max_penalty && !a.score_only) die("the argument '--max-penalty' requires '--score-only'");
+  if (a.check_optimal && !a.have_check_paf) die("the argument '--check-optimal' requires '--check-paf'");
+  if (a.verify && a.score_only) die("the argument '--verify' cannot be used with '--score-only'");
+  if (a.verify && a.mash_matrix) die("the argument '--verify' cannot be used with '--mash-matrix'");
+  if (a.have_check_paf && (a.verify || a.score_only || a.mash_matrix || a.have_output || a.have_devices))
+    die("the argument '--check-paf' cannot be used with '--verify', '--score-only', '--mash-matrix', '--output' or '--devices'");
   if (a.input.empty()) die("the following required arguments were not provided: --input <INPUT>");
   if (a.have_scores && a.have_preset) die("the argument '--scores' cannot be used with '--preset'");
   if (a.have_keep && a.have_exclude) die("the argument '--keep-prefixes' cannot be used with '--exclude-prefixes'");
@@ -282,8 +301,30 @@ int main(int argc, char** argv) {
   AlignmentParams params;
   try { params = parse_scores(scores); } catch (const std::exception& e) { die(e.what(), 1); }
 
+  if (a.have_check_paf) {
+    try {
+      std::ifstream fin(a.check_paf, std::ios::binary);
+      if (!fin) die("cannot open " + a.check_paf, 1);
+      std::stringstream ss;
+      ss << fin.rdbuf();
+      set_engine_flags(AWV_F_NO_ARENA_PROBE);
+      const PafCheckReport r = check_paf(sequences, ss.str(), params, a.check_optimal, a.device);
+      std::cout << format_paf_check(r);
+      std::cout.flush();
+      char buf[200];
+      snprintf(buf, sizeof(buf), "checked %zu of %zu PAF lines (%zu empty records skipped), %zu failed, %.2f ms", r.checked, r.lines,
+               r.skipped, r.failures.size(), r.stats.kernel_ms);
+      std::cerr << buf << "\n";
+      return r.failures.empty() ? 0 : 4;
+    } catch (const std::exception& e) {
+      die(e.what(), 1);
+    }
+  }
+
+  int verify_status = 0;
   try {
     AllPairIterator it = AllPairIterator::with_options(sequences, params, true, !a.wfa_orientation, strategy, a.plan_device);
+    it.with_verify(a.verify);
     if (a.forward_only) it.with_orientation(Orientation::ForwardOnly);
     it.with_full_wfa_orientation(a.wfa_orientation_full);
     it.with_devices(devices);
@@ -337,12 +378,25 @@ int main(int argc, char** argv) {
     if (done != total) die("internal: wrote " + std::to_string(done) + " of " + std::to_string(total) + (a.score_only ? " pairs" : " PAF lines"), 1);
     if (!a.no_progress) {
       const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      char buf[160];
-      snprintf(buf, sizeof(buf), "[%.1fs] %zu/%zu (100.0%%) %.1f alignments/sec", secs, done, total, done / std::max(secs, 1e-9));
+      char buf[320];
+      int w = snprintf(buf, sizeof(buf), "[%.1fs] %zu/%zu (100.0%%) %.1f alignments/sec", secs, done, total, done / std::max(secs, 1e-9));
+      if (a.verify) {
+        const awv_verify_stats vs = it.last_verify_stats();
+        snprintf(buf + w, sizeof(buf) - (size_t)w, ", verified %llu pairs, %zu failed, %.2f ms", (unsigned long long)vs.pairs,
+                 it.verify_failures().size(), vs.kernel_ms);
+      }
       std::cerr << buf << "\n";
+    }
+    if (a.verify) {
+      const auto& vf = it.verify_failures();
+      if (a.no_progress)
+        std::cerr << "verified " << it.last_verify_stats().pairs << " pairs, " << vf.size() << " failed, " << it.last_verify_stats().kernel_ms << " ms\n";
+      std::string report;
+      verify_status = report_verify_failures(vf, sequences, report);
+      std::cerr << report;
     }
   } catch (const std::exception& e) {
     die(e.what(), 1);
   }
-  return 0;
+  return verify_status;
 }

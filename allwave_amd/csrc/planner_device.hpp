@@ -8,12 +8,18 @@
 #include <cstdint>
 #include <string>
 
+#include "allwave_hip.h"
+
 struct awv_engine;
 
 namespace awp {
 
 struct PlanState;                   // planner.hip
 void plan_state_release(PlanState* p);  // frees its device buffers and the object itself (nullptr: nothing)
+
+// zero bytes behind every sequence of the padded layout (engine.hip, upload_seqset): the extension kernels read 8 bytes at
+// a time, and verify.hip reads whole dwords that start inside a sequence
+constexpr int SEQ_PAD_BYTES = 8;
 
 // the engine's resident sequences: forward and reverse-complement copies in the engine's padded layout
 struct EngineView {
@@ -33,3 +39,4 @@ struct EngineView {
 int awv_internal_view(awv_engine* e, awp::EngineView* v);  // AWV_ERR_STATE without a sequence set
 awp::PlanState*& awv_internal_plan(awv_engine* e);
 int awv_internal_fail(int code, const std::string& msg);   // records awv_last_error(), returns code
+int awv_internal_check_penalties(const awv_penalties* pen);  // the engine's sign rules for a penalty set (not the ring's size limit): AWV_OK or awv_align_pairs' error

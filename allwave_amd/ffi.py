@@ -40,6 +40,16 @@ AWV_ORIENT_FULL = 1
 AWV_ORIENT_SKIP_RATIO = 8
 AWV_ORIENT_NO_EDITS = 2 ** 64 - 1
 AWV_ORIENT_HI_NONE = 2 ** 31 - 1
+#: verification (awv_verify_result.code), in order of precedence
+AWV_VF_OK = 0
+AWV_VF_SKIPPED = 1
+AWV_VF_BAD_OP = 2
+AWV_VF_OVERRUN = 3
+AWV_VF_M_DIFFERS = 4
+AWV_VF_X_EQUAL = 5
+AWV_VF_SHORT = 6
+AWV_VF_COUNTS = 7
+AWV_VF_PENALTY = 8
 #: sketch kinds of device pair planning (awv_sketch)
 AWV_SK_CANONICAL = 0
 AWV_SK_FORWARD = 1
@@ -49,7 +59,8 @@ AWV_SK_REVCOMP = 2
 EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine_destroy",
            "awv_engine_set_sequences", "awv_align_pairs", "awv_align_one", "awv_score_pairs", "awv_engine_stats",
            "awv_score_pairs_bounded", "awv_orient_pairs", "awv_orient_decide", "awv_orient_settling_bound",
-           "awv_sketch", "awv_sketch_copy", "awv_sketch_pair_counts", "awv_sketch_rows", "awv_sketch_knn", "awv_keep_pairs")
+           "awv_sketch", "awv_sketch_copy", "awv_sketch_pair_counts", "awv_sketch_rows", "awv_sketch_knn", "awv_keep_pairs",
+           "awv_align_pairs_verified", "awv_verify_cigars", "awv_verify_one_host", "awv_engine_verify_stats")
 
 
 class EngineConfig(C.Structure):
@@ -85,10 +96,16 @@ class Stats(C.Structure):
                 ("deep_cell_steps", C.c_uint64)]
 
 
+class VerifyStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("pairs", C.c_uint64), ("failed", C.c_uint64), ("columns", C.c_uint64)]
+
+
 PAIR_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4")])
 RESULT_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4"), ("score", "<i4"), ("cigar_len", "<u4"),
                          ("cigar_off", "<u8"), ("num_matches", "<i4"), ("num_mismatches", "<i4"),
                          ("num_ins", "<i4"), ("num_del", "<i4"), ("q_end", "<i4"), ("t_end", "<i4")])
+#: awv_verify_result
+VERIFY_DTYPE = np.dtype([("code", "<i4"), ("reserved", "<i4"), ("column", "<i8"), ("penalty", "<i8")])
 #: awv_score_result
 SCORE_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4")])
 
@@ -125,6 +142,13 @@ def load():
         L.awv_orient_decide.argtypes = [C.POINTER(Penalties), C.c_int32, C.c_int32, C.c_int32, C.c_int32]
         L.awv_orient_settling_bound.argtypes = [C.POINTER(Penalties), C.c_int32, C.c_int32]
         L.awv_orient_settling_bound.restype = C.c_int32
+        L.awv_align_pairs_verified.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                               SINK_FN, C.c_void_p]
+        L.awv_verify_cigars.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                        C.c_void_p]
+        L.awv_verify_one_host.argtypes = [C.POINTER(Penalties), C.c_char_p, C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, C.c_int64,
+                                          C.c_void_p, C.c_void_p]
+        L.awv_engine_verify_stats.argtypes = [C.c_void_p, C.POINTER(VerifyStats)]
         _LIB = L
     return _LIB
 
@@ -186,9 +210,10 @@ class Engine:
             pairs = p
         return np.ascontiguousarray(pairs)
 
-    def align_pairs(self, scores, pairs, want_cigars=True):
+    def align_pairs(self, scores, pairs, want_cigars=True, verify=False):
         """pairs: int array [n,2] (q,t) or [n,3] (q,t,revcomp), or a PAIR_DTYPE array.
-        Returns (results structured array, list of op-byte strings or None)."""
+        Returns (results structured array, list of op-byte strings or None); verify=True: every finished pair is checked on
+        the device (awv_align_pairs_verified) and a VERIFY_DTYPE array comes back as a third value."""
         pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
         pairs = self._pair_array(pairs)
         res = np.zeros(len(pairs), dtype=RESULT_DTYPE)
@@ -204,10 +229,44 @@ class Engine:
             return 0
 
         cb = SINK_FN(_sink) if want_cigars else SINK_FN()
+        if verify:
+            vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)]  # (vout is required, also for an empty list)
+            rc = load().awv_align_pairs_verified(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), res.ctypes.data,
+                                                 vres.ctypes.data, cb, None)
+            if rc != AWV_OK:
+                raise EngineError(rc, "awv_align_pairs_verified")
+            return res, cigars, vres
         rc = load().awv_align_pairs(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), res.ctypes.data, cb, None)
         if rc != AWV_OK:
             raise EngineError(rc, "awv_align_pairs")
         return res, cigars
+
+    def verify_cigars(self, scores, pairs, results, arena):
+        """awv_verify_cigars: checks caller-supplied records (a RESULT_DTYPE array whose cigar_off / cigar_len point into
+        `arena`, bytes or a uint8 array) against the resident sequences on the device.  Returns a VERIFY_DTYPE array."""
+        pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+        pairs = self._pair_array(pairs)
+        results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+        if results.shape != (len(pairs),):
+            raise ValueError("results: need one record per pair")
+        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
+        nbytes = int(arena.size)
+        if nbytes == 0:
+            arena = np.zeros(1, dtype=np.uint8)
+        vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)]
+        rc = load().awv_verify_cigars(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), results.ctypes.data, arena.ctypes.data,
+                                      nbytes, vres.ctypes.data)
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_verify_cigars")
+        return vres
+
+    def verify_stats(self):
+        """awv_engine_verify_stats: kernel_ms, pairs, failed, columns of the last verifying call."""
+        st = VerifyStats()
+        rc = load().awv_engine_verify_stats(self._h, C.byref(st))
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_engine_verify_stats")
+        return st
 
     def score_pairs(self, scores, pairs, max_penalty=None):
         """Score-only alignment (awv_score_pairs): the optimal penalty of every pair, no CIGAR.  pairs as for align_pairs.
@@ -267,6 +326,21 @@ class Engine:
         if rc != AWV_OK:
             raise EngineError(rc, "awv_engine_stats")
         return st
+
+
+def verify_one_host(scores, pattern, text, cigar, claimed):
+    """awv_verify_one_host: the verification contract on the host (needs no device; the yardstick the kernel is tested
+    against).  claimed: one RESULT_DTYPE record.  Returns one VERIFY_DTYPE record."""
+    pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+    pattern, text, cigar = bytes(pattern), bytes(text), bytes(cigar)
+    rec = np.zeros(1, dtype=RESULT_DTYPE)
+    rec[0] = tuple(claimed) if isinstance(claimed, (list, tuple)) else claimed
+    out = np.zeros(1, dtype=VERIFY_DTYPE)
+    rc = load().awv_verify_one_host(C.byref(pen), pattern, len(pattern), text, len(text), cigar, len(cigar), rec.ctypes.data,
+                                    out.ctypes.data)
+    if rc != AWV_OK:
+        raise EngineError(rc, "awv_verify_one_host")
+    return out[0]
 
 
 def orient_decide(scores, lo_f, hi_f, lo_r, hi_r):

@@ -98,6 +98,98 @@ def set_engine_config(flags=0, first_row_cols=0, release=True):
 
 ORIENT = {"forward": 0, "wfa": 1, "mash": 2}
 
+VERIFY_CODES = ("ok", "skipped", "bad_op", "overrun", "m_differs", "x_equal", "short", "counts", "penalty")  # ffi.AWV_VF_*
+
+
+def last_verify():
+    """What this thread's last all_pairs_paf / iterate / all_pairs_paf_count call left (zeros and no failures without verify=True):
+    dict(pairs, failed, columns, kernel_ms -- last_verify_stats(), summed over the slots -- and failures: verify_failures(),
+    one dict(index, query_idx, target_idx, is_reverse, code, class, column, penalty) per failed pair, by pair-list index)."""
+    st = ffi.VerifyStats()
+    out = C.c_void_p()
+    n = C.c_size_t(0)
+    if load().awh_last_verify(C.byref(st), C.byref(out), C.byref(n)) != 0:
+        raise HostError("out of memory")
+    k = n.value
+    raw = np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_int64)), shape=(max(k, 1) * 7,))[:7 * k].reshape(k, 7).copy()
+    load().awh_free(out)
+    fails = [dict(index=int(r[0]), query_idx=int(r[1]), target_idx=int(r[2]), is_reverse=bool(r[3]), code=int(r[4]),
+                  **{"class": VERIFY_CODES[int(r[4])] if 0 <= int(r[4]) < len(VERIFY_CODES) else "unknown"},
+                  column=int(r[5]), penalty=int(r[6])) for r in raw]
+    return dict(pairs=int(st.pairs), failed=int(st.failed), columns=int(st.columns), kernel_ms=float(st.kernel_ms), failures=fails)
+
+
+def verify_failure_path(ids, pairs, first, calls):
+    """The way a failed check travels above the engine, without an engine (append_verify_failures per engine call,
+    sort_verify_failures, report_verify_failures, the record packing of last_verify()).  pairs: the run's range of (q, t)
+    pairs, which starts at pair-list index `first`; calls: one list per engine call, in the order the calls finish, of
+    (place in the range, is_reverse, code, column, penalty) per entry.  Returns (exit status, report text); last_verify()
+    then holds the failures."""
+    p = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+    flat = [e for c in calls for e in c]
+    cuts = np.zeros(len(calls) + 1, dtype=np.uint64)
+    cuts[1:] = np.cumsum([len(c) for c in calls], dtype=np.uint64)
+    idx = np.array([e[0] for e in flat] + [0], dtype=np.int64)
+    rev = np.array([1 if e[1] else 0 for e in flat] + [0], dtype=np.uint8)
+    code = np.array([e[2] for e in flat] + [0], dtype=np.int32)
+    col = np.array([e[3] for e in flat] + [0], dtype=np.int64)
+    pen = np.array([e[4] for e in flat] + [0], dtype=np.int64)
+    cids = (C.c_char_p * len(ids))(*[i.encode() for i in ids])
+    buf = C.create_string_buffer(1 << 16)
+    rc = load().awh_verify_failure_path(len(ids), cids, p.ctypes.data_as(C.c_void_p), C.c_size_t(len(p)), C.c_size_t(int(first)),
+                                        idx.ctypes.data_as(C.c_void_p), rev.ctypes.data_as(C.c_void_p), code.ctypes.data_as(C.c_void_p),
+                                        col.ctypes.data_as(C.c_void_p), pen.ctypes.data_as(C.c_void_p), cuts.ctypes.data_as(C.c_void_p),
+                                        C.c_size_t(len(calls)), buf, C.c_size_t(len(buf)))
+    return rc, buf.value.decode()
+
+
+def cigar_string_to_bytes(cg):
+    """The op bytes of a PAF cg string: cigar_bytes_to_string undone ('=' -> M, X -> X, D -> I, I -> D).  ValueError for a
+    string that is not <count><op>... over those letters."""
+    cg = cg.encode() if isinstance(cg, str) else bytes(cg)
+    cap = 16
+    num = b""
+    for ch in cg:  # (an upper bound of the op bytes: the sum of the counts)
+        if 48 <= ch <= 57:
+            num += bytes([ch])
+        else:
+            cap += int(num or b"0")
+            num = b""
+    if cap > (1 << 31):
+        raise ValueError("malformed cg string")
+    buf = C.create_string_buffer(cap)
+    L = load()
+    L.awh_cigar_string_to_bytes.restype = C.c_long
+    n = L.awh_cigar_string_to_bytes(cg, buf, C.c_size_t(cap))
+    if n < 0:
+        raise ValueError("malformed cg string")
+    return buf.raw[:n]
+
+
+def check_paf(ids, seqs, paf_text, scores, optimal=False, device=0):
+    """Checks every line of a PAF (12 columns + cg:Z:) against the sequences on `device`; nothing is aligned (check_paf in
+    allwave.hpp).  Returns dict(lines, checked, skipped, kernel_ms, failures): one dict(line, qname, tname, strand, class, column,
+    penalty, optimum) per failing line, in line order; `class` as listed there; optimum is None unless `optimal` found one."""
+    cids, data, offs = _seq_args(ids, seqs)
+    txt = paf_text.encode() if isinstance(paf_text, str) else bytes(paf_text)
+    out = C.c_void_p()
+    n = C.c_size_t(0)
+    counts = (C.c_uint64 * 4)()
+    st = ffi.VerifyStats()
+    e = _err()
+    rc = load().awh_check_paf(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), scores.encode(), txt,
+                              C.c_size_t(len(txt)), int(bool(optimal)), int(device), C.byref(out), C.byref(n), counts, C.byref(st), e, _CAP)
+    if rc != 0:
+        raise HostError(e.value.decode())
+    lines = C.string_at(out, n.value).decode().splitlines()
+    load().awh_free(out)
+    fails = []
+    for ln in lines:
+        f = ln.split("\t")
+        fails.append({"line": int(f[0]), "qname": f[1], "tname": f[2], "strand": f[3], "class": f[4], "column": int(f[5]),
+                      "penalty": int(f[6]), "optimum": int(f[7]) if len(f) > 7 else None})
+    return dict(lines=int(counts[0]), checked=int(counts[1]), skipped=int(counts[2]), kernel_ms=float(st.kernel_ms), failures=fails)
+
 
 def _orient_code(orientation, orientation_full):
     """the hooks' orientation argument: 3 = WFA orientation by two full alignments per pair (with_full_wfa_orientation)"""
@@ -123,11 +215,12 @@ def _device_args(devices):
 
 
 def all_pairs_paf(ids, seqs, scores, orientation="wfa", exclude_self=True, device=0, sparsification="none", devices=None,
-                  min_batch_pairs=0, orientation_full=False):
+                  min_batch_pairs=0, orientation_full=False, verify=False):
     """AllPairIterator + alignment_to_paf per record; returns the list of PAF lines.  `devices`: a list of ordinals (one
     engine per entry, repeats allowed) to spread the pair list over in this call; None = [device].
     `min_batch_pairs` > 0 overrides the smallest batch of a multi-device run (default 16,384).  orientation_full: WFA
-    orientation by two full alignments for every pair (the reference's method; the same strands) instead of bounded scores."""
+    orientation by two full alignments for every pair (the reference's method; the same strands) instead of bounded scores.
+    verify: every alignment is checked on the device (with_verify); the lines are the same, last_verify() tells the outcome."""
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if devices is None else devices)
     out = C.c_void_p()
@@ -135,7 +228,7 @@ def all_pairs_paf(ids, seqs, scores, orientation="wfa", exclude_self=True, devic
     e = _err()
     rc = load().awh_all_pairs_paf_devices(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
                                           scores.encode(), sparsification.encode(), _orient_code(orientation, orientation_full), int(exclude_self),
-                                          devs, nd, C.c_int64(int(min_batch_pairs)), None, C.byref(out), C.byref(n), e, _CAP)
+                                          devs, nd, C.c_int64(int(min_batch_pairs)), int(bool(verify)), None, C.byref(out), C.byref(n), e, _CAP)
     if rc != 0:
         raise HostError(e.value.decode())
     txt = C.string_at(out, n.value).decode()
@@ -148,7 +241,7 @@ ITER_MODES = {"for_each": 0, "next": 1, "par_for_each": 2, "par_collect": 3, "pr
 
 def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientation="forward", threads=4, chunk=0,
             resparsify=False, fail_at=-1, device=0, devices=None, min_batch_pairs=0, shard=None, with_stats=False,
-            orientation_full=False):
+            orientation_full=False, verify=False):
     """Every consumer of the pair list (iterator.rs:101-253, lib.rs:57-68) through one hook; returns the PAF lines in arrival
     order.  `fail_at` >= 0 makes the callback throw at that record: HostError carries its message.
     `devices`: a list of ordinals (one engine per entry, repeats allowed) to spread the pair list over; None = [device].
@@ -157,7 +250,8 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
     last_slot_stats(); all zeros for "process_alignments" without min_batch_pairs.  A HostError carries `.records`: how
     many records arrived before the error, and `.late_calls`: how many callback calls followed the first failure (with
     fail_at, each of those fails with a message of its own: "callback failed again, ...").  orientation_full: WFA
-    orientation by two full alignments for every pair instead of bounded scores (the same strands)."""
+    orientation by two full alignments for every pair instead of bounded scores (the same strands).  verify: with_verify on the
+    iterator, whichever consumer `mode` names; last_verify() tells the outcome."""
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if devices is None else devices)
     st = (ffi.Stats * nd)()
@@ -168,7 +262,7 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
     rc = load().awh_iterate_devices(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), scores.encode(),
                                     sparsification.encode(), _orient_code(orientation, orientation_full), ITER_MODES[mode], int(threads), int(chunk),
                                     int(bool(resparsify)), C.c_long(int(fail_at)), devs, nd, C.c_int64(int(min_batch_pairs)),
-                                    C.c_int64(int(rank)), C.c_int64(int(world)), st, C.byref(out), C.byref(n), C.byref(nrec),
+                                    C.c_int64(int(rank)), C.c_int64(int(world)), int(bool(verify)), st, C.byref(out), C.byref(n), C.byref(nrec),
                                     C.byref(late), e, _CAP)
     if rc != 0:
         err = HostError(e.value.decode())
@@ -183,12 +277,12 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
 
 
 def all_pairs_paf_count(ids, seqs, scores, orientation="forward", device=0, format_threads=8, devices=None, min_batch_pairs=0,
-                        sparsification=None, checksum=False):
+                        sparsification=None, checksum=False, verify=False):
     """End to end: upload -> align -> D2H -> format into a counting sink. Returns (bytes, lines, secs, ffi.Stats) for
     every pair on `device`.  `devices`: a list of ordinals (one engine per entry, repeats allowed); the Stats are then
     summed over the slots, and the result gains a fifth element, each slot's Stats (last_slot_stats()), and a sixth, the
     sum of the lines' FNV-1a hashes when `checksum` (order-independent; else None).  With devices, `sparsification` plans
-    the pair list (default: every pair)."""
+    the pair list (default: every pair).  verify: with_verify on the iterator; last_verify() tells the outcome."""
     one = devices is None
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if one else devices)
@@ -199,7 +293,7 @@ def all_pairs_paf_count(ids, seqs, scores, orientation="forward", device=0, form
     rc = load().awh_all_pairs_paf_count_devices(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
                                                 scores.encode(), ORIENT[orientation],
                                                 sparsification.encode() if sparsification and not one else None,
-                                                devs, nd, C.c_int64(int(min_batch_pairs)), format_threads, C.byref(nb), C.byref(nl),
+                                                devs, nd, C.c_int64(int(min_batch_pairs)), format_threads, int(bool(verify)), C.byref(nb), C.byref(nl),
                                                 C.byref(ck) if checksum else None, C.byref(secs), C.byref(st), slot, e, _CAP)
     if rc != 0:
         raise HostError(e.value.decode())

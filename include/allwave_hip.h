@@ -262,6 +262,57 @@ int32_t awv_orient_settling_bound(const awv_penalties* pen, int32_t known_is_rev
 
 int awv_engine_stats(const awv_engine* e, awv_stats* out);
 
+/* ---- verification on the device (csrc/verify.hip, csrc/verify_device.hpp) ---------------------------------------------
+ * What the reference's validators check (validation.rs verify_cigar_alignment, validation_simple.rs, wfa.rs
+ * validate_cigar_alignment), plus the penalty: an op string is verified against its pair when every column is what it
+ * says, both sequences are consumed end to end, and the record's counts and penalty are the op string's.  The pattern is
+ * the query, or its reverse complement when q_revcomp is set; bytes compare verbatim; 'I' consumes the text, 'D' the
+ * pattern.  Re-scoring: each 'X' adds x; a maximal run of L equal gap ops adds o1 + L e1 (2-piece: min(o1 + L e1,
+ * o2 + L e2)); an 'I' run followed directly by a 'D' run is two runs.
+ * The code is the FIRST failure in this order: */
+#define AWV_VF_OK 0        /* verified */
+#define AWV_VF_SKIPPED 1   /* status is not AWV_ST_COMPLETED: nothing to check */
+/* column-level, the smallest column wins; within one column in this order: */
+#define AWV_VF_BAD_OP 2    /* the byte is not one of M, X, I, D */
+#define AWV_VF_OVERRUN 3   /* the column needs a base beyond the end of either sequence */
+#define AWV_VF_M_DIFFERS 4 /* an 'M' column whose bytes differ */
+#define AWV_VF_X_EQUAL 5   /* an 'X' column whose bytes are equal */
+/* on the whole string, after every column has passed: */
+#define AWV_VF_SHORT 6     /* the ops end before both sequences are consumed */
+#define AWV_VF_COUNTS 7    /* cigar_len, num_matches, num_mismatches, num_ins, num_del, q_end or t_end is not the op string's */
+#define AWV_VF_PENALTY 8   /* the re-scored penalty differs from `penalty`, or score != -penalty */
+
+typedef struct {
+  int32_t code;     /* AWV_VF_* */
+  int32_t reserved;
+  int64_t column;   /* index of the offending op byte for column-level codes, else -1 */
+  int64_t penalty;  /* the op string re-scored under pen when every column-level check passed, else -1 */
+} awv_verify_result; /* 24 bytes */
+
+typedef struct {
+  double kernel_ms;  /* HIP-event time of the verify launches of the last verifying call */
+  uint64_t pairs;    /* pairs handed to the check (skipped ones included) */
+  uint64_t failed;   /* of them: code other than AWV_VF_OK / AWV_VF_SKIPPED */
+  uint64_t columns;  /* op bytes looked at: min(cigar_len, pattern + text length + 1) of every pair not skipped, failed ones included */
+} awv_verify_stats;
+
+/* awv_align_pairs, and every batch's finished pairs checked on the device, on the engine's stream, before the batch's CIGARs
+ * are copied back (pairs re-run after AWV_ST_CAPACITY included; also under AWV_F_KEEP_ON_DEVICE).  vout[i] belongs to
+ * pairs[i].  Results and CIGARs are those of awv_align_pairs; a failed check is reported, never repaired. */
+int awv_align_pairs_verified(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, awv_result* out,
+                             awv_verify_result* vout /* required */, awv_sink sink, void* user);
+/* The same check on records and op bytes the caller supplies, against the resident sequence set: results[i] claims that
+ * cigar_arena[results[i].cigar_off, + cigar_len) aligns pairs[i].  The arena goes up in pieces of at most max_arena_bytes.
+ * A completed record whose op bytes lie outside the arena: AWV_ERR_ARG (nothing is read on the device). */
+int awv_verify_cigars(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const awv_result* results,
+                      const uint8_t* cigar_arena, uint64_t arena_bytes, awv_verify_result* vout /* required */);
+/* The contract alone, on the host (needs no device): the yardstick the kernel is tested against, not a fallback -- no
+ * product path calls it.  cigar: n op bytes; claimed: the record. */
+int awv_verify_one_host(const awv_penalties* pen, const uint8_t* pattern, int32_t plen, const uint8_t* text, int32_t tlen,
+                        const uint8_t* cigar, int64_t n, const awv_result* claimed, awv_verify_result* out);
+/* The last verifying call (awv_align_pairs_verified / awv_verify_cigars) of this engine. */
+int awv_engine_verify_stats(const awv_engine* e, awv_verify_stats* out);
+
 /* ---- device pair planning (csrc/planner.hip) -------------------------------------------------------------------------
  * Integer work over the engine's resident sequence set, on its device and stream; results equal the host planner's
  * (csrc/host/planner.cpp) bit for bit.  Every call but awv_keep_pairs needs a sequence set (else AWV_ERR_STATE); a new set
