@@ -23,7 +23,7 @@
 //   * long sequences (32-bit rows): three chained sweeps with the middle sweep's rows in LDS wherever the
 //     sub-problem is too long for its packed sequences to be staged there; such a sub-problem probes the 2-bit
 //     words where they lie in HBM (seq_mode 2), and every sub-problem that has become short enough is searched
-//     with 16-bit rows inside the same launch (AWV_SUB16);
+//     with 16-bit rows inside the same launch (kp.sub16);
 //   * the far-apart phase (multi_phase, which tail-calls deep_phase), the base case's passes (base_phase), the
 //     breakpoint search (find_breakpoint_fn) and the trimmed-hull search (trim_pass_fn) are real functions with
 //     register files of their own; their inputs travel through LDS (Shared::pctx); the passes' planning
@@ -52,14 +52,6 @@
 namespace AWV_NS {
 
 constexpr int WG = AWV_WG;  // threads per workgroup = per sequence pair (64 or 256)
-// Direction split (two waves per pair): in the breakpoint search wave 0 computes the forward rows and
-// wave 1 the reverse rows of a fused pass, each over all of its row's windows.
-#ifdef AWV_DIRSPLIT
-constexpr bool DIRSPLIT = true;
-static_assert(AWV_WG == 128, "direction split = two waves per pair");
-#else
-constexpr bool DIRSPLIT = false;
-#endif
 // Accepted penalties: scope = max(x, o1+e1, o2+e2) + 1 <= MAX_SCOPE (engine.hip check_penalties).  The ring of score rows is
 // the power of two >= scope + 2 + multi_T * chain_max - 1 (align_core), so it reaches MAX_RING = 256 rows: e.g. (0,5,121,1),
 // (0,125,3,1) or (0,5,8,2,124,1).  Nothing on the device is sized by it; the ring arena and the LDS row metadata follow kp.ring.
@@ -84,10 +76,7 @@ enum { C_M = 0, C_I1 = 1, C_I2 = 2, C_D1 = 3, C_D2 = 4 };
 constexpr int FALLBACK_MIN_SCORE = 250;
 constexpr int FALLBACK_MIN_LENGTH = 100;
 constexpr int STACK_CAP = 48;
-// 1: inside a launch with 32-bit rows, sub-problems of which both lengths are below SUB16_MAX_LEN are searched with 16-bit rows
-#ifndef AWV_SUB16
-#define AWV_SUB16 1
-#endif
+// inside a launch with 32-bit rows, sub-problems of which both lengths are below SUB16_MAX_LEN are searched with 16-bit rows (kp.sub16)
 constexpr int SUB16_MAX_LEN = 32760;  // (the engine's own limit for 16-bit rows: engine.hip)
 // Occupancy target: waves per SIMD (the register budget the kernel is compiled for) and the static
 // LDS the kernel declares; the engine sizes the dynamic LDS so that WAVES_PER_SIMD * 4 waves fit a CU.
@@ -154,7 +143,7 @@ struct KParams {
   int chain_max;   // sweeps a multi-step pass may chain (1: none; > 1 needs x == TMAX and o1 + e1 == 2 TMAX, ring >= scope + 2 + TMAX * chain_max - 1)
   int multi_T;     // steps per multi-step pass (0: off): <= min(TMAX, x, o1+e1, o2+e2, ring - scope - 1), e1/e2 among the instantiated depths
   int deep_passes; // 1: the margin zone of phase 1 runs in passes that store every I/D row (deep_phase); 0: step by step there (round 2)
-  int sub16;       // 32-bit launches: 1 = sub-problems whose lengths fit 16-bit rows are searched with 16-bit rows (AWV_SUB16)
+  int sub16;       // 32-bit launches: 1 = sub-problems whose lengths fit 16-bit rows are searched with 16-bit rows
   int wcap;        // columns per ring row
   void* ring_mem;
   size_t ring_slot_stride;  // bytes per workgroup slot
@@ -521,42 +510,8 @@ __device__ __forceinline__ int packed_first_count(const uint32_t* seq, const Sub
 #ifndef AWV_MIN_PASS_LEN
 #define AWV_MIN_PASS_LEN 1024
 #endif
-// 1: plan_multi plans a pass's steps without an LDS round trip per step (I/D metadata forwarded in scalar registers, M rows
-// fetched an iteration ahead); 0: one plan_step per score
-#ifndef AWV_PLAN_PIPELINED
-#define AWV_PLAN_PIPELINED 1
-#endif
-// 1: the first sweep's x- and (o1 + e1)-lag sources are loaded straight into the chain registers (compute_rows_multi, ALIAS)
-#ifndef AWV_CHAIN_ALIAS
-#define AWV_CHAIN_ALIAS 1
-#endif
-// 1: 32-bit rows (long sequences): the (o1 + e1)-lag M rows of a chained pass's later sweeps live in LDS -- a lane vector is four
-// registers there and a second set of chain registers does not fit; the staging region of the packed sequences is free whenever
-// the sub-problem is too long to be staged (the top BiWFA levels of 100 kbp reads), and five scores x 64 lanes x 16 B per wave
-// fit it.  Passes then chain three sweeps (15 scores) instead of two: 52 row vectors per 15 scores move through HBM instead of 70.
-#ifndef AWV_LDS_CHAIN
-#define AWV_LDS_CHAIN 1
-#endif
-// 1: the last sweep of a window issues the NEXT window's first-sweep loads, step by step, into the chain registers its own
-// steps have just finished with (compute_rows_multi, XPREF; needs AWV_TAP_PREFETCH)
-#ifndef AWV_WINDOW_PREFETCH
-#define AWV_WINDOW_PREFETCH 0  // bit-exact, measured twice on config 2: -1.0 % and 0.0 % (1795 -> 1777 / 1797 ms): a window's first burst is not where the waves wait; off
-#endif
-// 1: chained sweeps load their (o2 + e2)-lag M rows one sweep ahead (compute_rows_multi, PREF)
-#ifndef AWV_TAP_PREFETCH
-#define AWV_TAP_PREFETCH 1
-#endif
 #ifndef AWV_PROBE_BATCH
 #define AWV_PROBE_BATCH 2  // cells per batch of LDS reads: 0 = the compiler's own order, 2, 4 (config 2, same box: 1645 / 1629 / 1660 ms)
-#endif
-// experiment (off): wave priority raised while a window issues its row loads (1) and also while a step issues its probe reads (2)
-#ifndef AWV_SETPRIO
-#define AWV_SETPRIO 0
-#endif
-#if AWV_SETPRIO
-#define AWV_PRIO(n) __builtin_amdgcn_s_setprio(n)
-#else
-#define AWV_PRIO(n) ((void)0)
 #endif
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 template <int DIR, int NB>
@@ -629,9 +584,6 @@ __device__ __forceinline__ int extend_lcp_packed(const uint32_t* seq, const SubC
 // holding the sub-problem's first base (p_bit / t_bit = its position in that word, as in LDS); the raw pointers are not kept.
 // The engine pads the packed arrays with two words in front (reverse probes of a sequence's first bases read up to two words
 // below its first) and four behind; what a probe reads outside the sub-problem is cut off by the remaining length.
-#ifndef AWV_GLOBAL_PACKED
-#define AWV_GLOBAL_PACKED 1
-#endif
 typedef unsigned int u32x3_t __attribute__((ext_vector_type(3)));
 typedef u32x2_t __attribute__((aligned(4))) u32x2_a4;
 typedef u32x3_t __attribute__((aligned(4))) u32x3_a4;
@@ -703,11 +655,9 @@ __device__ __forceinline__ void stage_sequences(const KParams& kp, const Lds<Off
   cx.t_w0 = cx.p_w0 + npw + 3 + 2;
   const int total_words = cx.t_w0 + ntw + 3;
   if (total_words * 4 > kp.lds_seq_bytes) {
-    if (AWV_GLOBAL_PACKED) {
-      cx.seq_mode = 2;
-      cx.P[0] = cx.P[1] = (gseq_t)(cx.Pw + pw_first);
-      cx.T[0] = cx.T[1] = (gseq_t)(cx.Tw + tw_first);
-    }
+    cx.seq_mode = 2;
+    cx.P[0] = cx.P[1] = (gseq_t)(cx.Pw + pw_first);
+    cx.T[0] = cx.T[1] = (gseq_t)(cx.Tw + tw_first);
     return;
   }
   cx.seq_mode = 1;
@@ -749,9 +699,9 @@ __device__ __forceinline__ void hull_add(RowMeta& h, const RowMeta& s, int dlo, 
   h.hi = max(h.hi, s.hi + dhi);
 }
 
-// SCALAR: the hull arithmetic spelled out for the scalar unit (the passes' planning loop, plan_multi); the step-by-step loop of
-// find_breakpoint_fn keeps the compiler's own selection -- there the extra scalar registers spill (425 spill instructions against 73)
-template <bool P2, bool BASE, typename OffT, bool SCALAR = false>
+// One score's plan for the step-by-step loops.  The hull arithmetic is left to the compiler's own selection: spelled out for
+// the scalar unit as in plan_multi, the extra scalar registers spill in find_breakpoint_fn (425 spill instructions against 73).
+template <bool P2, bool BASE, typename OffT>
 __device__ __forceinline__ void plan_step(const KParams& kp, const Lds<OffT>& lds, int dir, int score, StepPlan& pl) {
   const DevPenalties& pn = kp.pen;
   // The nine metadata entries are fetched by nine lanes in one LDS round trip and handed out with
@@ -792,36 +742,6 @@ __device__ __forceinline__ void plan_step(const KParams& kp, const Lds<OffT>& ld
   // repairs in trim_pass): a cell of I (D) is non-NULL iff its left (right) source cell is, M iff
   // any source is (A.3).  They are written to the row metadata right away -- the slot of the new
   // score is not read by anyone during this step -- so nothing but lo/hi outlives the barrier.
-  if constexpr (SCALAR) {
-    // (on the scalar unit by construction -- s_min / s_max / s_add above; an empty source row {K_BIG, -K_BIG} drops out of the
-    // minima / maxima by itself and leaves lo > hi behind where nothing feeds a component)
-    int plo[NCOMP], phi[NCOMP];
-    plo[C_I1] = s_add(s_min(pl.src[1].lo, pl.src[2].lo), 1);
-    phi[C_I1] = s_add(s_max(pl.src[1].hi, pl.src[2].hi), 1);
-    plo[C_D1] = s_add(s_min(pl.src[1].lo, pl.src[3].lo), -1);
-    phi[C_D1] = s_add(s_max(pl.src[1].hi, pl.src[3].hi), -1);
-    plo[C_I2] = plo[C_D2] = K_BIG;
-    phi[C_I2] = phi[C_D2] = -K_BIG;
-    int mlo = s_min(pl.src[0].lo, s_min(plo[C_I1], plo[C_D1])), mhi = s_max(pl.src[0].hi, s_max(phi[C_I1], phi[C_D1]));
-    if (P2) {
-      plo[C_I2] = s_add(s_min(pl.src[4].lo, pl.src[5].lo), 1);
-      phi[C_I2] = s_add(s_max(pl.src[4].hi, pl.src[5].hi), 1);
-      plo[C_D2] = s_add(s_min(pl.src[4].lo, pl.src[6].lo), -1);
-      phi[C_D2] = s_add(s_max(pl.src[4].hi, pl.src[6].hi), -1);
-      mlo = s_min(mlo, s_min(plo[C_I2], plo[C_D2]));
-      mhi = s_max(mhi, s_max(phi[C_I2], phi[C_D2]));
-    }
-    plo[C_M] = mlo;
-    phi[C_M] = mhi;
-    pl.lo = mlo;
-    pl.hi = mhi;
-  #pragma unroll
-    for (int c = 0; c < NCOMP; ++c) {
-      meta_store_scalar(&lds.ring_meta[(dir * NCOMP + c) * kp.ring + (score & (kp.ring - 1))], plo[c], phi[c]);
-      if (BASE && (threadIdx.x & 63) == 0) lds.meta_log[score * NCOMP + c] = plo[c] > phi[c] ? ROW_EMPTY : RowMeta{plo[c], phi[c]};  // history for the backtrace
-    }
-    return;
-  }
   RowMeta pred[NCOMP];
 #pragma unroll
   for (int c = 0; c < NCOMP; ++c) pred[c] = ROW_EMPTY;
@@ -884,11 +804,11 @@ __device__ __forceinline__ RawVec<int32_t> shift_from_right(const RawVec<int32_t
 
 // extend (A.4) of N = 4 * steps M cells of one lane (cell i lies on diagonal k0 + i % 4; m[i] < 0: NULL, left
 // alone): the first probe (16 bases) of all N cells is issued together -- one LDS round trip for the lot,
-// invalid cells probe offset 0, always readable -- then the few longer runs continue in a loop each
-// PERCELL: the rare longer runs branch per cell on the lanes' condition itself instead of through a per-lane bit mask
-// (fewer vector instructions; used by the multi-step passes -- in the step-by-step loop, whose register file is full,
-// the grouped form keeps the allocation it has)
-template <typename OffT, int N, bool PERCELL = false>
+// invalid cells probe offset 0, always readable -- then the few longer runs continue in a loop each, picked through a
+// per-lane bit mask.  The step-by-step form (compute_row, through extend_cells with N = 4); the passes have extend_cells_lean.
+// (The general N and the wrapper stay: written as one function of four cells, the step-by-step kernels come out of the
+// compiler with another instruction schedule.)
+template <typename OffT, int N>
 __device__ __forceinline__ void extend_cells_n(const Lds<OffT>& lds, const SubCtx& cx, int dir, int k0, int32_t (&m)[N], unsigned& ext_iters) {
   static_assert(N % 4 == 0 && N <= 32, "whole lane vectors");
   const gseq_t Pp = dir ? cx.P[1] : cx.P[0];  // (selects: `dir` may be a run-time value, SubCtx lives in registers)
@@ -920,20 +840,6 @@ __device__ __forceinline__ void extend_cells_n(const Lds<OffT>& lds, const SubCt
     } else {
 #pragma unroll
       for (int j = 0; j < N; ++j) nn[j] = packed_first_count<1>(seq, cx, vv[j], hh[j]);
-    }
-    if (PERCELL) {
-      ext_iters += N;
-#pragma unroll
-      for (int j = 0; j < N; ++j) {
-        const bool more = nn[j] == PROBE_FIRST && rr[j] > PROBE_FIRST;
-        m[j] += min(nn[j], rr[j]);  // rr == 0 for NULL cells: unchanged
-        if (more) {
-          const int v = wenc_of<OffT>() ? m[j] + max(-(k0 + (j & 3)), 0) : m[j] - (k0 + (j & 3));
-          const int h = wenc_of<OffT>() ? m[j] + max(k0 + (j & 3), 0) : m[j];
-          m[j] += dir == 0 ? extend_lcp_packed<0>(seq, cx, v, h, ext_iters) : extend_lcp_packed<1>(seq, cx, v, h, ext_iters);
-        }
-      }
-      return;
     }
 #pragma unroll
     for (int j = 0; j < N; ++j) {
@@ -988,21 +894,10 @@ __device__ __forceinline__ void extend_cells(const Lds<OffT>& lds, const SubCtx&
 // of diagonal k0 + j as the recurrences leave it (any value; NULLs are negative), ok[j] says whether it is a cell of the
 // wavefront (inside the step's hull and inside the matrix: hmin <= cand <= hmaxv[j], the largest offset inside the matrix on
 // that diagonal).  The remaining length is hmaxv[j] - cand (= min(plen - v, tlen - h)), cells that are not ok probe position 0
-// and come back OFF_NULL: 23 vector instructions per cell where bounds test + extend_cells_n took 34.
-#ifndef AWV_LEAN_EXT
-#define AWV_LEAN_EXT 1
-#endif
-// 1: a search's passes start at score 0 (sources of negative scores are empty rows to plan_multi); 0: round 2's rule, step by
-// step until `scope` - 1 rows exist
-#ifndef AWV_EARLY_PASSES
-#define AWV_EARLY_PASSES 1
-#endif
-// 1: cells that are not part of the wavefront probe wherever their candidate value points instead of position 0 -- an LDS read
-// outside the workgroup's allocation returns 0 on gfx950 (scratch/src/ldsoob.hip: every address tried, no fault), a raw-byte
-// probe cannot do that (global memory): packed probes only
-#ifndef AWV_OOB_PROBES
-#define AWV_OOB_PROBES 0  // measured: 1686 ms against 1673 ms on config 2 (the scattered addresses cost more than the two selects per cell save)
-#endif
+// and come back OFF_NULL: 23 vector instructions per cell where a separate bounds test + extend_cells_n took 34.
+// (Letting such cells probe wherever their candidate value points -- an LDS read outside the workgroup's allocation returns 0 on
+// gfx950, scratch/src/ldsoob.hip -- was measured and dropped: 1686 ms against 1673 ms on config 2, the scattered addresses cost
+// more than the two selects per cell save.)
 // NBATCH: cells whose first-probe LDS reads go out together (packed_first_counts4; 0: the compiler's own order) -- chosen per
 // instantiation by the caller: only where the registers are there (no spill inside the window loop, scratch/spill_audit.py)
 template <typename OffT, int NBATCH>
@@ -1010,27 +905,24 @@ __device__ __forceinline__ void extend_cells_lean(const Lds<OffT>& lds, const Su
                                                   const int (&hmaxv)[4], int32_t (&m)[4], unsigned& ext_iters) {
   const uint32_t* seq = lds.seq;
   int rr[4], vv[4], hh[4], nn[4];
-  // positions of the probes: PROBE_ANYWHERE -- the cell's candidate value as it is (cells that are not ok read somewhere, possibly
-  // outside the LDS allocation, and their count is dropped); otherwise such cells probe position (0, 0)
-  auto positions = [&](bool anywhere) {
+  // positions of the probes: cells that are not ok probe position (0, 0)
+  auto positions = [&]() {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int k = k0 + j;
-      const bool use = anywhere || ok[j];
       if constexpr (wenc_of<OffT>()) {  // cand holds w = min(h, v): v = w + max(-k, 0), h = w + max(k, 0)
-        vv[j] = use ? cand[j] + max(-k, 0) : 0;
-        hh[j] = use ? cand[j] + max(k, 0) : 0;
+        vv[j] = ok[j] ? cand[j] + max(-k, 0) : 0;
+        hh[j] = ok[j] ? cand[j] + max(k, 0) : 0;
       } else {
-        vv[j] = use ? cand[j] - k : 0;
-        hh[j] = use ? cand[j] : 0;
+        vv[j] = ok[j] ? cand[j] - k : 0;
+        hh[j] = ok[j] ? cand[j] : 0;
       }
     }
   };
 #pragma unroll
   for (int j = 0; j < 4; ++j) rr[j] = hmaxv[j] - cand[j];
   if (cx.seq_mode == 1) {
-    positions(AWV_OOB_PROBES != 0);
-    if (AWV_SETPRIO >= 2) AWV_PRIO(2);
+    positions();
     if constexpr (NBATCH != 0) {
       if (dir == 0) packed_first_counts4<0, NBATCH ? NBATCH : 4>(seq, cx, vv, hh, nn);
       else packed_first_counts4<1, NBATCH ? NBATCH : 4>(seq, cx, vv, hh, nn);
@@ -1041,7 +933,6 @@ __device__ __forceinline__ void extend_cells_lean(const Lds<OffT>& lds, const Su
 #pragma unroll
       for (int j = 0; j < 4; ++j) nn[j] = packed_first_count<1>(seq, cx, vv[j], hh[j]);
     }
-    if (AWV_SETPRIO >= 2) AWV_PRIO(0);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int t = min(nn[j], rr[j]);
@@ -1057,7 +948,7 @@ __device__ __forceinline__ void extend_cells_lean(const Lds<OffT>& lds, const Su
     }
     return;
   }
-  positions(false);
+  positions();
   if (cx.seq_mode == 2) {  // packed words from global memory (too long for the LDS staging)
     if (dir == 0) gw_first_counts4<0>(cx, vv, hh, nn);
     else gw_first_counts4<1>(cx, vv, hh, nn);
@@ -1108,7 +999,7 @@ template <bool P2, bool BASE, typename OffT>
 __device__ __forceinline__ int compute_row(const KParams& kp, Shared& sh, const Lds<OffT>& lds, const SubCtx& cx, rsrc_t rs,
                                            int dir, int score, const StepPlan& pl, bool dirty, Acc& acc, unsigned& ext_iters) {
   static_assert(WG % 64 == 0, "whole waves");
-  constexpr int NWAVES = (DIRSPLIT && !BASE) ? 1 : WG / 64;  // a row's windows are dealt round-robin to the workgroup's waves (direction split: a row belongs to one wave)
+  constexpr int NWAVES = WG / 64;  // a row's windows are dealt round-robin to the workgroup's waves
   constexpr int VEC = OffTraits<OffT>::VEC;
   static_assert(VEC == 4, "lane vectors are 4 diagonals wide");
   constexpr int WSPAN = 64 * VEC;
@@ -1464,12 +1355,11 @@ __device__ __forceinline__ void plan_multi(const KParams& kp, const Lds<OffT>& l
   mp.lds_chain = 0;
   mp.vslo = 1;
   mp.vshi = 0;
-#if AWV_PLAN_PIPELINED
   // The predicted metadata of the pass's steps, one after the other (step t's I/D rows feed step t + 1 / t + 2), without an LDS
   // round trip per step: the I/D rows of the last e1 / e2 scores travel in scalar registers (queues like compute_rows_multi's),
   // and the three M rows a step reads -- x, o1 + e1 and o2 + e2 scores back, all written at least two iterations ago -- are
-  // fetched one iteration ahead by lanes 0..2.  (plan_step did one dependent LDS round trip per score: 15 in a row per pass and
-  // direction, a quarter of a narrow sub-problem's pass.)  All arithmetic on the scalar unit (s_min / s_max / s_add).
+  // fetched one iteration ahead by lanes 0..2.  (One plan_step per score is one dependent LDS round trip per score: 15 in a row per
+  // pass and direction, a quarter of a narrow sub-problem's pass.)  All arithmetic on the scalar unit (s_min / s_max / s_add).
   {
     typedef typename MetaTraits<OffT>::Stored MetaStored;
     const int rmask = kp.ring - 1;
@@ -1546,17 +1436,6 @@ __device__ __forceinline__ void plan_multi(const KParams& kp, const Lds<OffT>& l
       cur = nxt;
     }
   }
-#else
-  for (int t = 0; t < Tn; ++t) {  // (uniform) the predicted metadata of step t is in LDS before step t + 1 is planned
-    StepPlan pl;
-    plan_step<P2, BASE, OffT, true>(kp, lds, dir, s0 + 1 + t, pl);
-    if (lane == t) { mp.vslo = pl.lo; mp.vshi = pl.hi; }
-    if (pl.lo <= pl.hi) {
-      mp.lo_min = min(mp.lo_min, pl.lo);
-      mp.hi_max = max(mp.hi_max, pl.hi);
-    }
-  }
-#endif
   // every source row's stored extent = the hull of the step that wrote it (its M row's metadata), fetched by
   // lane r in one LDS round trip.  Score 0 is special -- the search's origin: one cell in the begin
   // component's row, nothing stored for the others -- so there the component's own range counts; rows
@@ -1662,14 +1541,18 @@ __device__ __forceinline__ int compute_rows_multi(const KParams& kp, Shared& sh,
     return o;
   };
   int nwin = 0;
-  // (declared out here: with XPREF these registers carry the next window's first-sweep sources across the window loop)
-  constexpr bool ALIAS = CHAIN && W16 && (AWV_CHAIN_ALIAS != 0);
-  constexpr bool PREF = ALIAS && P2 && (AWV_TAP_PREFETCH != 0);
-  constexpr bool XPREF = PREF && (AWV_WINDOW_PREFETCH != 0);
+  constexpr bool ALIAS = CHAIN && W16;  // the first sweep's x- and (o1 + e1)-lag sources are loaded straight into the chain registers
+  constexpr bool PREF = ALIAS && P2;     // chained sweeps load their (o2 + e2)-lag M rows one sweep ahead
+  // (A window's last sweep issuing the NEXT window's first-sweep loads into the chain registers its steps have finished with was
+  // built, bit-exact, and dropped: -1.0 % and 0.0 % in two runs on config 2 (1795 -> 1777 / 1797 ms) -- a window's first burst is
+  // not where the waves wait.)
   V Mp1[CHAIN ? TM : 1], Mp2[CHAIN && (ALIAS || CH >= 3) ? TM : 1];
   V tapO[PREF ? TM : 1], tapN[PREF ? TM : 1];
-  bool pre_loaded = false;  // (uniform) XPREF: the previous window has issued this window's first-sweep loads
-  constexpr bool LCH = CHAIN && !W16 && (AWV_LDS_CHAIN != 0);
+  // 32-bit rows (long sequences): the (o1 + e1)-lag M rows of a chained pass's later sweeps live in LDS -- a lane vector is four
+  // registers there and a second set of chain registers does not fit; the staging region of the packed sequences is free whenever
+  // the sub-problem is too long to be staged (the top BiWFA levels of 100 kbp reads), and five scores x 64 lanes x 16 B per wave
+  // fit it.  Passes then chain three sweeps (15 scores) instead of two: 52 row vectors per 15 scores move through HBM instead of 70.
+  constexpr bool LCH = CHAIN && !W16;
   const bool lds_chain = LCH && mp.lds_chain != 0;  // (uniform)
   typedef unsigned int u32x4l __attribute__((ext_vector_type(4)));
   // this wave's slots: [step of the sweep][lane], 16 B each (the region is 16-byte aligned: Lds::seq starts at a 16-byte multiple)
@@ -1677,7 +1560,6 @@ __device__ __forceinline__ int compute_rows_multi(const KParams& kp, Shared& sh,
   for (int cb = (colLoMin & ~(VEC - 1)) - halo * VEC + (NWAVES > 1 ? (int)(threadIdx.x >> 6) * stride : 0); cb + halo * VEC <= colHiMax;
        cb += stride * NWAVES) {
     ++nwin;
-    const bool has_next = XPREF && cb + stride * NWAVES + halo * VEC <= colHiMax;  // (uniform) this wave has another window in this pass
     const int c0 = cb + lane * VEC;
     const int k0 = c0 + kmin;
     const int voff = c0 * ESZ;
@@ -1691,7 +1573,6 @@ __device__ __forceinline__ int compute_rows_multi(const KParams& kp, Shared& sh,
       for (int r = 0; r < NW; ++r) v.w[r] = keep ? v.w[r] : nullw;
     };
     const unsigned long long tm0 = PROF_NOW();
-    AWV_PRIO(3);
     // ---- the I/D rows the pass begins with
     V qI1[E1], qD1[E1], qI2[E2], qD2[E2];
 #pragma unroll
@@ -1718,22 +1599,20 @@ __device__ __forceinline__ int compute_rows_multi(const KParams& kp, Shared& sh,
     // 5- and 10-back rows without a select per step, a second copy of the sweep's results or a separate set of load registers
     // (30 registers less than keeping taps, Mp1 / Mp2 and the new rows apart; the (o1 + e1)-lag rows of the second sweep are the
     // first sweep's x-lag rows -- no load for them either).
-    if (!(XPREF && pre_loaded)) {
 #pragma unroll
-      for (int t = 0; t < (CHAIN ? TM : 1); ++t) Mp1[t] = V{};
+    for (int t = 0; t < (CHAIN ? TM : 1); ++t) Mp1[t] = V{};
 #pragma unroll
-      for (int t = 0; t < (CHAIN && (ALIAS || CH >= 3) ? TM : 1); ++t) Mp2[t] = V{};
-    }
-    // ALIAS + AWV_TAP_PREFETCH: the one source a chained sweep still loads -- the (o2 + e2)-lag M rows, 25 scores back, written
+    for (int t = 0; t < (CHAIN && (ALIAS || CH >= 3) ? TM : 1); ++t) Mp2[t] = V{};
+    // PREF: the one source a chained sweep still loads -- the (o2 + e2)-lag M rows, 25 scores back, written
     // by earlier passes whatever the sweep -- is loaded a whole sweep ahead: sweep h computes from tapO while tapN (sweep h + 1's)
     // is in flight, so only a window's first sweep waits for memory.
 #pragma unroll
     for (int t = 0; t < (PREF ? TM : 1); ++t) {
-      if (!(XPREF && pre_loaded)) tapO[t] = V{};
+      tapO[t] = V{};
       tapN[t] = V{};
     }
     if constexpr (PREF) {
-      if (load_on && !(XPREF && pre_loaded)) {
+      if (load_on) {
 #pragma unroll
         for (int t = 0; t < TM; ++t)
           if (t < min(TM, Tn)) tapO[t] = buf_load_raw<OffT>(rs, voff, row_off<BASE, OffT>(kp, dir, C_M, s0 + 1 + t - pn.o2 - pn.e2));
@@ -1760,7 +1639,6 @@ __device__ __forceinline__ int compute_rows_multi(const KParams& kp, Shared& sh,
       const int sb = s0 + h * TM;   // this sweep covers scores sb + 1 .. sb + TM
       const int tb = h * TM;        // its first step index within the pass
       const int tn = min(TM, Tn - tb);
-      AWV_PRIO(3);
       const bool own0 = CHAIN && h >= 1, own1 = CHAIN && (ALIAS || lds_chain ? h >= 1 : (CH >= 3 && h >= 2));  // (uniform) M sources 0 / 1 come from registers (or, 32-bit rows, from LDS)
       // ---- 16-bit rows: all row loads of the sweep, back to back (one memory round trip per sweep).  32-bit rows (a lane
       // vector is four registers; TM x NT of them do not fit): the M sources of a step are loaded one step ahead -- `cur`
@@ -1793,7 +1671,7 @@ __device__ __forceinline__ int compute_rows_multi(const KParams& kp, Shared& sh,
           for (int t = 0; t < TM; ++t) {
             if (t < tn) {
               if constexpr (ALIAS) {
-                if (!own0 && !(XPREF && pre_loaded)) {  // (own0 = own1 here: the first sweep only; with XPREF the previous window may have issued them)
+                if (!own0) {  // (own0 = own1 here: the first sweep only)
                   Mp1[t] = buf_load_raw<OffT>(rs, voff, row_off<BASE, OffT>(kp, dir, C_M, sb + 1 + t - pn.x));
                   Mp2[t] = buf_load_raw<OffT>(rs, voff, row_off<BASE, OffT>(kp, dir, C_M, sb + 1 + t - pn.o1 - pn.e1));
                 }
@@ -1808,7 +1686,6 @@ __device__ __forceinline__ int compute_rows_multi(const KParams& kp, Shared& sh,
           }
         }
       }
-      AWV_PRIO(0);
       if (!interior) {
         if (h == 0) {
 #pragma unroll
@@ -1879,11 +1756,8 @@ __device__ __forceinline__ int compute_rows_multi(const KParams& kp, Shared& sh,
             if (CH >= 3 && own1 && !lds_chain) cO1 = Mp2[CH >= 3 ? t : 0];
           }
           V nI1{}, nD1{}, nI2{}, nD2{};
-          int32_t m[VEC];
-#if AWV_LEAN_EXT
-          int32_t cand[VEC];
+          int32_t m[VEC], cand[VEC];
           bool okc[VEC];
-#endif
           if constexpr (W16) {
             // max first, neighbour shift after: max(O[k-1], I[k-1]) = (max(O, I))[k-1] -- one shift per gap kind instead of two
             auto pkmax = [&](const V& a, const V& b) {
@@ -1921,12 +1795,8 @@ __device__ __forceinline__ int compute_rows_multi(const KParams& kp, Shared& sh,
                 lane_oob |= lane_on && mm > hmax;
                 // (h < k, i.e. a negative pattern position, never occurs in a real wavefront; the halo lanes' stale values
                 // -- which are extended like any other now that chained sweeps read them back -- may hold anything)
-#if AWV_LEAN_EXT
                 cand[2 * r + e] = mm;
                 okc[2 * r + e] = in_hull && mm <= hmax && mm >= hminv[2 * r + e];
-#else
-                m[2 * r + e] = (mm > hmax || mm < hminv[2 * r + e] || !in_hull) ? OFF_NULL : mm;
-#endif
               }
             }
           } else {
@@ -1957,12 +1827,8 @@ __device__ __forceinline__ int compute_rows_multi(const KParams& kp, Shared& sh,
               const int32_t mm = max(del, max((int32_t)cMx.w[j] + 1, ins));
               const int hmax = hmaxv[j];
               lane_oob |= lane_on && mm > hmax;
-#if AWV_LEAN_EXT
               cand[j] = mm;
               okc[j] = in_hull && mm <= hmax && mm >= hminv[j];
-#else
-              m[j] = (mm > hmax || mm < hminv[j] || !in_hull) ? OFF_NULL : mm;
-#endif
             }
           }
           if (DEEP && lane_on) {  // this score's I/D rows (canonical form), whole lane vectors over the step's hull
@@ -1989,15 +1855,11 @@ __device__ __forceinline__ int compute_rows_multi(const KParams& kp, Shared& sh,
           PROF_DRAIN();
           PROF_ADD_L(STAT_T_CR_ALU, tm1);
           const unsigned long long tm2 = PROF_NOW();
-#if AWV_LEAN_EXT
           // (batched probe reads where the window loop has the registers for them: the base case, and the chained far-apart passes
           // when they do not spend those registers on loading a sweep ahead -- which pays more: config 2, same box, 1645 ms batched /
           // 1615 ms a sweep ahead / 1632 ms both (two spills); the deep passes' 15 source vectors and the 32-bit rows' four-word lane
           // vectors leave no room: the compiler's one-read-at-a-time order there)
           extend_cells_lean<OffT, (W16 && !WE && WG == 64 && ((ALIAS && !PREF) || BASE)) ? AWV_PROBE_BATCH : 0>(lds, cx, dir, k0, cand, okc, hmaxv, m, ext_iters);
-#else
-          extend_cells_n<OffT, 4, true>(lds, cx, dir, k0, m, ext_iters);
-#endif
           PROF_DRAIN();
           PROF_ADD_L(STAT_T_CR_EXTEND, tm2);
           const unsigned long long tm3 = PROF_NOW();
@@ -2033,24 +1895,9 @@ __device__ __forceinline__ int compute_rows_multi(const KParams& kp, Shared& sh,
               }
             }
             if (lane_on) st(row_off<BASE, OffT>(kp, dir, C_M, sb + 1 + t), voff, mv);
-            if constexpr (CHAIN && W16) {  // in place: this step has read its entries already (without ALIAS: only what the next sweeps take from registers)
-              if (XPREF && has_next && h == nh - 1) {
-                // the window's last sweep: nobody reads this step's chain registers again -- they take the NEXT window's first-sweep
-                // sources of the same step (its loads are then a whole sweep old when that window starts)
-                const int voff_n = voff + stride * NWAVES * ESZ, c0_n = c0 + stride * NWAVES;
-                const bool load_on_n = c0_n + (halo + 2) * VEC > colLoMin && c0_n - (halo + 1) * VEC <= colHiMax;
-                Mp1[t] = V{};
-                Mp2[XPREF ? t : 0] = V{};
-                tapO[XPREF ? t : 0] = V{};
-                if (load_on_n) {
-                  Mp1[t] = buf_load_raw<OffT>(rs, voff_n, row_off<BASE, OffT>(kp, dir, C_M, s0 + 1 + t - pn.x));
-                  Mp2[XPREF ? t : 0] = buf_load_raw<OffT>(rs, voff_n, row_off<BASE, OffT>(kp, dir, C_M, s0 + 1 + t - pn.o1 - pn.e1));
-                  tapO[XPREF ? t : 0] = buf_load_raw<OffT>(rs, voff_n, row_off<BASE, OffT>(kp, dir, C_M, s0 + 1 + t - pn.o2 - pn.e2));
-                }
-              } else {
-                if constexpr (ALIAS || CH >= 3) Mp2[ALIAS || CH >= 3 ? t : 0] = Mp1[t];
-                Mp1[t] = mv;
-              }
+            if constexpr (ALIAS) {  // in place: this step has read its entries already
+              Mp2[t] = Mp1[t];
+              Mp1[t] = mv;
             }
             if constexpr (CHAIN && !W16) {  // in place: this step has read its entries already (the registers of a second copy are not there)
               if (CH >= 3) Mp2[CH >= 3 ? t : 0] = Mp1[t];
@@ -2083,13 +1930,10 @@ __device__ __forceinline__ int compute_rows_multi(const KParams& kp, Shared& sh,
         }
       }
       if constexpr (PREF) {
-        if (!(XPREF && has_next && h == nh - 1)) {
 #pragma unroll
-          for (int t = 0; t < TM; ++t) tapO[t] = tapN[t];
-        }
+        for (int t = 0; t < TM; ++t) tapO[t] = tapN[t];
       }
     }
-    pre_loaded = has_next;
     if constexpr (!BASE && !DEEPP && !WE) lane_maxak = max(lane_maxak, win_maxak - k0);
     // ---- the pass's last e1 / e2 I/D rows (canonical form, whole lane vectors over their step's hull)
     if (!DEEP) {
@@ -2226,8 +2070,8 @@ __device__ __attribute__((noinline)) void multi_phase(unsigned sh_addr, unsigned
   int nsteps = 0, npass = 0, why = MP_MARGIN;
   unsigned long long cells = 0;
   unsigned ext_iters = 0;
-  // 32-bit rows: a third chained sweep when the staging region of the packed sequences can hold the chain rows (AWV_LDS_CHAIN)
-  const bool lds_chain = CHAIN && sizeof(OffT) == 4 && (AWV_LDS_CHAIN != 0) && cx.seq_mode != 1 &&
+  // 32-bit rows: a third chained sweep when the staging region of the packed sequences can hold the chain rows (compute_rows_multi, LCH)
+  const bool lds_chain = CHAIN && sizeof(OffT) == 4 && cx.seq_mode != 1 &&
                          uni(pc.lds_seq_bytes) >= (WG / 64) * TMAX32 * 64 * 16;
   const int margin_shift = (uni(deep_v) >> 8) & 3;  // a restarted search: the margin times four (find_breakpoint)
   const bool long_reads = (uni(deep_v) & 0x400) != 0;  // a 16-bit search of a launch with 32-bit rows: those reads' margin factor
@@ -2735,7 +2579,6 @@ __device__ __forceinline__ int base_align(const KParams& kp, Shared& sh, const L
     acc_reset(sh.acc[1][0]);
     acc_reset(sh.acc[2][0]);
   }
-  constexpr bool MULTI_BUILD = !DIRSPLIT;
   const unsigned sh_addr = (unsigned)(uintptr_t)&sh, dyn_addr = (unsigned)(uintptr_t)lds.ring_meta;  // LDS addresses
   if (tid == 0) {  // what base_phase / trim_pass_fn read back (uniform; the barrier below publishes it)
     PassCtx& pc = sh.pctx;
@@ -2764,7 +2607,7 @@ __device__ __forceinline__ int base_align(const KParams& kp, Shared& sh, const L
   unsigned long long cells = 0;
   int pass = 0;
   bool dirty = false;  // some row of this sub-problem was trimmed: later steps mask element by element
-  bool multi_open = MULTI_BUILD && kp.multi_T > 0;  // multi-step passes (base_phase) until one is discarded or the capacity bound is near
+  bool multi_open = kp.multi_T > 0;  // multi-step passes (base_phase) until one is discarded or the capacity bound is near
   const unsigned long long tb0 = PROF_NOW();
   for (;;) {
     // termination (wavefront_termination_end2end): end component reaches (plen, tlen)
@@ -2773,11 +2616,9 @@ __device__ __forceinline__ int base_align(const KParams& kp, Shared& sh, const L
       const int32_t v = uni(off_load1<OffT>(hist + ((size_t)score * NCOMP + ce) * (size_t)kp.wb_cap + (k_end - kmin), k_end));
       if (v >= tlen) break;
     }
-    if (MULTI_BUILD && multi_open && !dirty) {
-      if constexpr (MULTI_BUILD) {
-        if (P2 || pn.e1 == 1) base_phase<P2, OffT, P2 ? 2 : 1, 1>(sh_addr, dyn_addr, score, kp.multi_T, pass);
-        else base_phase<P2, OffT, 2, 1>(sh_addr, dyn_addr, score, kp.multi_T, pass);
-      }
+    if (multi_open && !dirty) {
+      if (P2 || pn.e1 == 1) base_phase<P2, OffT, P2 ? 2 : 1, 1>(sh_addr, dyn_addr, score, kp.multi_T, pass);
+      else base_phase<P2, OffT, 2, 1>(sh_addr, dyn_addr, score, kp.multi_T, pass);
       const int why = uni(sh.pres.why);
       if (why == MP_ERROR) return uni(sh.error);
       score = uni(sh.pres.sc);
@@ -2814,7 +2655,7 @@ __device__ __forceinline__ int base_align(const KParams& kp, Shared& sh, const L
     lstats[STAT_BASE] += 1;
   }
   atomicAdd(&lstats[STAT_EXTEND], (unsigned long long)ext_iters);
-  if (MULTI_BUILD && tid == 0) lstats[STAT_EXTEND] += sh.ext_multi;
+  if (tid == 0) lstats[STAT_EXTEND] += sh.ext_multi;
   // ---- backtrace by wave 0 (candidates fetched by lanes 0..8, packed (offset<<4)|type, max wins)
   if (tid < 64) {
     int matrix = ce, sc = score, k = k_end, offset = tlen;
@@ -3018,7 +2859,7 @@ __device__ __forceinline__ void bialign_overlap(const KParams& kp, Shared& sh, c
     // One wave per pair: the gate loads of up to four chunks are in flight together (a candidate's
     // range is a few chunks and nearly all of them fail the gate), so a candidate costs one memory
     // round trip instead of one per chunk.
-    const bool pregated = m_gate && (WG == 64 || DIRSPLIT) && chhi - chlo < 64;
+    const bool pregated = m_gate && WG == 64 && chhi - chlo < 64;
     uint64_t gate_pass = ~0ull;  // bit (ch - chlo): the chunk passed the gate
     if (pregated) {
       gate_pass = 0;
@@ -3263,13 +3104,12 @@ __device__ __forceinline__ int find_breakpoint(const KParams& kp, Shared& sh, co
   bool dirty[2] = {false, false};  // per direction: some row was trimmed, later steps mask element by element
   // Multi-step passes (compute_rows_multi) while the searches are far apart; step by step -- every I/D
   // row kept, as the overlap search needs them -- from a safe margin before they can meet.
-  constexpr bool MULTI_BUILD = !DIRSPLIT;
   // attempt 0: the margins of multi_phase; 1 (the furthest points met inside a far-apart pass): once more with four times the
   // margin; 2 (again): step by step throughout
   const bool force_single = (attempt & 0xff) >= AWV_RESTART_ATTEMPTS - 1;
   // (bits 8, 9 = log2 of the margin's multiplier, bit 10 = the margin factor of long reads although the rows are 16-bit)
   const int deep_arg = kp.deep_passes | ((attempt & 0xff) == 1 && !force_single ? 0x200 : 0) | ((attempt & 0x100) ? 0x400 : 0);
-  const int multi_T = (MULTI_BUILD && !force_single && plen + tlen > AWV_MIN_PASS_LEN) ? kp.multi_T : 0;  // 0: step by step throughout
+  const int multi_T = (!force_single && plen + tlen > AWV_MIN_PASS_LEN) ? kp.multi_T : 0;  // 0: step by step throughout
   bool deep_on = multi_T == 0;     // every step stores its I/D rows
   int deep_since[2] = {deep_on ? 0 : INT_MAX, deep_on ? 0 : INT_MAX};  // first score from which all I/D rows are in HBM
   // the overlap search of (d0, s0) against d1 reads the I/D rows of s0 and of scores s1 - scope + 1 .. s1
@@ -3287,20 +3127,18 @@ __device__ __forceinline__ int find_breakpoint(const KParams& kp, Shared& sh, co
       int plo[2] = {1, 1}, phi[2] = {0, 0};
       bool need[2];
       const unsigned long long tp0 = PROF_NOW();
-      if (MULTI_BUILD && !deep_on && (dirty[0] || dirty[1])) {
+      if (!deep_on && (dirty[0] || dirty[1])) {
         deep_on = true;
         deep_since[0] = comp[0] + 1;
         deep_since[1] = comp[1] + 1;
       }
-      if (MULTI_BUILD && !deep_on && phase == 1 && comp[0] == sc[0] && comp[1] == sc[1] && sc[0] == sc[1] &&
-          (AWV_EARLY_PASSES || sc[0] + 1 - (pn.scope - 1) >= 1)) {
-        // ---- the far-apart phase: all multi-step passes of this search in one call (multi_phase)
-        if constexpr (MULTI_BUILD) {
-          // (chained sweeps only where the scores allow them: 2-piece with x = TMAX and o1 + e1 = 2 TMAX, the default set)
-          if (P2) multi_phase<P2, OffT, 2, 1, P2>(sh_addr, dyn_addr, sc[0], fmax, rmax, multi_T, pass, deep_arg);
-          else if (pn.e1 == 1) multi_phase<P2, OffT, 1, 1, false>(sh_addr, dyn_addr, sc[0], fmax, rmax, multi_T, pass, deep_arg);
-          else multi_phase<P2, OffT, 2, 1, false>(sh_addr, dyn_addr, sc[0], fmax, rmax, multi_T, pass, deep_arg);
-        }
+      if (!deep_on && phase == 1 && comp[0] == sc[0] && comp[1] == sc[1] && sc[0] == sc[1]) {
+        // ---- the far-apart phase: all multi-step passes of this search in one call (multi_phase), from score 0 on (sources
+        // of negative scores are empty rows to plan_multi)
+        // (chained sweeps only where the scores allow them: 2-piece with x = TMAX and o1 + e1 = 2 TMAX, the default set)
+        if (P2) multi_phase<P2, OffT, 2, 1, P2>(sh_addr, dyn_addr, sc[0], fmax, rmax, multi_T, pass, deep_arg);
+        else if (pn.e1 == 1) multi_phase<P2, OffT, 1, 1, false>(sh_addr, dyn_addr, sc[0], fmax, rmax, multi_T, pass, deep_arg);
+        else multi_phase<P2, OffT, 2, 1, false>(sh_addr, dyn_addr, sc[0], fmax, rmax, multi_T, pass, deep_arg);
         PROF_ADD(STAT_T_BI_COMPUTE, tp0);
         const int why = uni(sh.pres.why);
         if (why == MP_ERROR) { rc = uni(sh.error); break; }
@@ -3331,7 +3169,7 @@ __device__ __forceinline__ int find_breakpoint(const KParams& kp, Shared& sh, co
 #pragma unroll
       for (int dir = 0; dir < 2; ++dir) {  // unrolled: every per-direction array keeps constant indices
         need[dir] = comp[dir] == sc[dir];
-        if (need[dir] && (!DIRSPLIT || uni((int)(threadIdx.x >> 6)) == dir)) {
+        if (need[dir]) {
           StepPlan pl;
           plan_step<P2, false, OffT>(kp, lds, dir, sc[dir] + 1, pl);
           cells += compute_row<P2, false, OffT>(kp, sh, lds, cx, ring_rs, dir, sc[dir] + 1, pl, dirty[dir], a[dir], ext_iters);
@@ -3362,10 +3200,6 @@ __device__ __forceinline__ int find_breakpoint(const KParams& kp, Shared& sh, co
         dirty[0] = dirty[0] || trim0;
         dirty[1] = dirty[1] || trim1;
         if (trim0 || trim1) {
-          if (DIRSPLIT) {  // the other wave planned that row: its hull is the M row's predicted metadata
-            if (trim0) { const RowMeta mm = get_meta(kp, lds, 0, C_M, sc[0] + 1); plo[0] = mm.lo; phi[0] = mm.hi; }
-            if (trim1) { const RowMeta mm = get_meta(kp, lds, 1, C_M, sc[1] + 1); plo[1] = mm.lo; phi[1] = mm.hi; }
-          }
           if (trim0) trim_pass_fn<P2, false, OffT>(sh_addr, 0, sc[0] + 1, plo[0], phi[0], pass % 3);
           if (trim1) trim_pass_fn<P2, false, OffT>(sh_addr, 1, sc[1] + 1, plo[1], phi[1], pass % 3);
           __syncthreads();
@@ -3412,17 +3246,14 @@ __device__ __forceinline__ int find_breakpoint(const KParams& kp, Shared& sh, co
     }
     if (++steps > max_steps) { rc = ST_MAX_STEPS; break; }
   }
-  if (DIRSPLIT) {
-    if ((tid & 63) == 0) atomicAdd(&lstats[STAT_CELLS], cells);
-    if (tid == 0) lstats[STAT_BREAKPOINTS] += 1;
-  } else if (tid == 0) {
+  if (tid == 0) {
     lstats[STAT_CELLS] += cells;
     lstats[STAT_MULTI_CELLS] += multi_cells;
     lstats[STAT_DEEP_CELLS] += deep_cells;
     lstats[STAT_BREAKPOINTS] += 1;
   }
   atomicAdd(&lstats[STAT_EXTEND], (unsigned long long)ext_iters);
-  if (!DIRSPLIT && tid == 0) lstats[STAT_EXTEND] += sh.ext_multi;
+  if (tid == 0) lstats[STAT_EXTEND] += sh.ext_multi;
   if (rc == BP_OK && bp.score > uni(sh.pctx.max_penalty)) rc = BP_ABOVE_BOUND;  // (the bound's phase 2 found no breakpoint <= B)
   __syncthreads();  // LDS metadata is rewritten by the next sub-problem
   if (rc == BP_OK && bp.score == INT_MAX) rc = ST_INTERNAL;
@@ -3629,10 +3460,10 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
             pc.pb_abs = cx.pb_abs; pc.tb_abs = cx.tb_abs;
           }
           __syncthreads();
-          // A launch with 32-bit rows searches the sub-problems that have become short enough with 16-bit rows (AWV_SUB16): the
+          // A launch with 32-bit rows searches the sub-problems that have become short enough with 16-bit rows (kp.sub16): the
           // same ring arena at half the bytes per row, packed arithmetic, the 16-bit metadata layout inside the same LDS region --
           // a search leaves nothing behind but its breakpoint.  (The base case stays with the launch's row width.)
-          if constexpr (AWV_SUB16 && sizeof(OffT) == 4 && !WENC) {
+          if constexpr (sizeof(OffT) == 4 && !WENC) {
             if (kp.sub16 != 0 && max(plen, tlen) < SUB16_MAX_LEN)
               rc = uni(find_breakpoint_fn<P2, int16_t>((unsigned)(uintptr_t)&sh, (unsigned)(uintptr_t)lds.ring_meta, (unsigned)(uintptr_t)lstats,
                                                        t.cb, t.ce, t.score_remaining, t.known, attempt | 0x100));  // (0x100: the long reads' margin)

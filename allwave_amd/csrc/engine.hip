@@ -9,16 +9,12 @@
 // awvx:: sixteen waves per pair (one pair per CU: the few pairs a large length difference makes enormous)
 #include "planner_device.hpp"  // (the sketches and scratch of device pair planning, planner.hip)
 #include "verify_device.hpp"   // (the per-batch check of awv_align_pairs_verified, verify.hip)
-#include "kernels_awv.hpp"  // (AWV_THRU_WG; the awv:: kernels themselves are instantiated in kernels_awv.hip -- here only the types)
+#include "kernels_awv.hpp"  // (the awv:: kernels themselves are instantiated in kernels_awv.hip -- here only the types)
 #define AWV_NS awv
-#define AWV_WG AWV_THRU_WG
-#if AWV_THRU_WG == 128
-#define AWV_DIRSPLIT 1
-#endif
+#define AWV_WG 64
 #include "biwfa_device.hpp"
 #undef AWV_NS
 #undef AWV_WG
-#undef AWV_DIRSPLIT
 #define AWV_NS awvw
 #define AWV_WG 256
 #include "biwfa_device.hpp"
@@ -518,7 +514,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       hq.resize(k); ht.resize(k); hrc.resize(k); hoff.resize(k); amap.resize(k);
       if (k == 0) return AWV_OK;
     }
-    const int wg = waves == 1 ? AWV_THRU_WG : 64 * waves;
+    const int wg = 64 * waves;
     const int nslots_g = e->cfg.workgroups > 0 ? std::max(1, e->cfg.workgroups / (wg / 64)) : (WAVES_PER_SIMD * 256 / wg) * e->num_cus;
     const int wcap_full = ((g_maxsum + 9 + 256 + 2 * COL_PAD) + 255) & ~255;
     const int nslots_want = (int)std::min<int64_t>(nslots_g, (int64_t)hq.size());
@@ -657,7 +653,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       kp.deep_passes = (kp.multi_T > 0 && !(e->cfg.flags & AWV_F_NO_DEEP)) ? 1 : 0;
       kp.sub16 = (e->cfg.flags & AWV_F_FORCE_INT32) ? 0 : 1;  // (the pin means 32-bit rows throughout)
       // (32-bit rows: two sweeps chained through registers, a third when the kernel finds room for its chain rows in LDS -- the
-      // kernel caps what it is offered: biwfa_device.hpp, AWV_LDS_CHAIN)
+      // kernel caps what it is offered: biwfa_device.hpp, multi_phase's lds_chain)
       kp.chain_max = narrow ? chain_max : (awv::TMAX32 == awv::TMAX ? std::min(chain_max, 3) : 1);
       kp.wcap = wc;
       kp.ring_mem = e->ring_mem.p;
@@ -794,7 +790,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       // One-wave pairs that cannot fill the machine even once, next to pairs that go four waves anyway, are bound by their
       // most expensive pair on a single wave while most of the machine idles: when their costs are uneven they go four
       // waves too (config 5: 3,315 such pairs, 2.9 s at 61 % of the CUs busy).  (Pairs come in descending cost order.)
-      if (!never_wide && n_one > 0 && n_four > 0 && n_one <= (int64_t)(WAVES_PER_SIMD * 256 / AWV_THRU_WG) * e->num_cus) {
+      if (!never_wide && n_one > 0 && n_four > 0 && n_one <= (int64_t)(WAVES_PER_SIMD * 256 / 64) * e->num_cus) {
         auto cost_of = [&](int64_t i) {
           const int64_t ql = s.len[hq[(size_t)i]], tl = s.len[ht[(size_t)i]];
           return (uint64_t)(ql + tl + 4 * std::llabs(ql - tl));
@@ -831,7 +827,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
           demand[g] = {0, g};
           if (q[g].empty()) continue;
           const int wv = waves_of[g / 3];
-          const int wgx = wv == 1 ? AWV_THRU_WG : 64 * wv;
+          const int wgx = 64 * wv;
           const int64_t slots = std::min<int64_t>((WAVES_PER_SIMD * 256 / wgx) * e->num_cus, (int64_t)q[g].size());
           demand[g].first = (size_t)slots * (size_t)gsum[g] * ((g % 3) == 1 ? 4 : 2);
         }

@@ -4,10 +4,7 @@
 // loop (not allowed) -- so the option is given to this file only (allwave_amd/build.py).
 #include "kernels_awv.hpp"
 #define AWV_NS awv
-#define AWV_WG AWV_THRU_WG
-#if AWV_THRU_WG == 128
-#define AWV_DIRSPLIT 1
-#endif
+#define AWV_WG 64
 #include "biwfa_device.hpp"
 
 namespace {
@@ -15,7 +12,7 @@ template <typename K>
 int launch(K kern, unsigned grid, size_t dyn_lds, hipStream_t stream, const awv::KParams& kp) {
   const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(AWV_THRU_WG), dyn_lds, stream, kp);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(AWV_WG), dyn_lds, stream, kp);
   return (int)hipSuccess;
 }
 }  // namespace

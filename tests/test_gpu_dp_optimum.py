@@ -280,9 +280,9 @@ def test_wide16_rows(dpc):
 
 def test_lds_chain_and_sub16(dpc):
     """70 kbp at 2-3 % (the inputs of test_unstaged_long_pairs_chain_through_lds): 32-bit rows, four waves, top levels too
-    long to stage, the middle sweep of chained passes kept in LDS (AWV_LDS_CHAIN), and the same with chaining off; and the
+    long to stage, the middle sweep of chained passes kept in LDS (compute_rows_multi's LCH), and the same with chaining off; and the
     150 kbp pair at 1.5 % of test_packed_probes_of_unstaged_sub_problems, whose sub-problems below 32,760 bases are searched
-    with 16-bit rows inside the 32-bit launch (AWV_SUB16)."""
+    with 16-bit rows inside the 32-bit launch (kp.sub16)."""
     rng = random.Random(1234)
     a = rand_seq(rng, 70000)
     seqs = [a, mutate(a, 0.02, rng), mutate(a, 0.03, rng)]

@@ -342,7 +342,7 @@ def test_long_sequences_use_32bit_rows(engine, oracle):
 def test_unstaged_long_pairs_chain_through_lds(oracle):
     """70 kbp at 2 %: 32-bit rows, four waves per pair, and a top BiWFA level too long for the LDS staging of the packed sequences
     (140 k bases against the 32 KB region) -- the regime in which the far-apart passes chain three sweeps with the middle
-    sweep's rows kept in that region (AWV_LDS_CHAIN, biwfa_device.hpp).  Against the oracle, and against the same engine with
+    sweep's rows kept in that region (compute_rows_multi's LCH, biwfa_device.hpp).  Against the oracle, and against the same engine with
     chaining off (AWV_F_NO_CHAIN)."""
     from allwave_amd import ffi
     rng = random.Random(1234)
@@ -372,7 +372,7 @@ def test_packed_probes_of_unstaged_sub_problems(oracle):
     front of the packed array), reverse-complemented queries, one wave per pair (a 6 KB staging region: 20 kbp pairs are
     unstaged there) and four, 16- and 32-bit rows -- against the oracle and against the raw-byte probes (AWV_F_NO_PACKED_SEQ).
     A pair with a non-ACGT base keeps the raw bytes.  The 150 kbp pair is also the case of a launch with 32-bit rows whose
-    sub-problems below 32,760 bases are searched with 16-bit rows (AWV_SUB16); AWV_F_FORCE_INT32 pins 32-bit rows throughout."""
+    sub-problems below 32,760 bases are searched with 16-bit rows (kp.sub16); AWV_F_FORCE_INT32 pins 32-bit rows throughout."""
     from allwave_amd import ffi
     rng = random.Random(777)
     comp = {65: 84, 84: 65, 67: 71, 71: 67}
