@@ -43,6 +43,8 @@
 #include <stdint.h>
 #include <limits.h>
 
+#include "range_span.hpp"
+
 #ifndef AWV_NS
 #define AWV_NS awv
 #endif
@@ -3331,8 +3333,14 @@ __device__ __attribute__((noinline)) int find_breakpoint_fn(unsigned sh_addr, un
 // ---------------------------------------------------------------------------------------------
 // The kernel: persistent workgroups, one pair at a time, DFS over the BiWFA recursion
 // ---------------------------------------------------------------------------------------------
-template <bool P2, typename OffT>
-__global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams kp) {
+// A range launch (awv_align_ranges / awv_score_ranges) is an instantiation of its own with a second argument, `const
+// awvr::Span* pair_span`: pair i aligns the rectangle pair_span[i] of its two sequences instead of the whole of them -- the
+// top-level task is that rectangle, everything below it is a BiWFA sub-problem as ever.  Whole-pair launches keep the
+// one-argument kernel and its parameter block as they were, so they run the code they always ran, register for register.
+template <bool P2, typename OffT, typename... PairSpan>
+__global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams kp, PairSpan... pair_span_arg) {
+  constexpr bool RANGES = sizeof...(PairSpan) > 0;
+  static_assert(sizeof...(PairSpan) <= 1, "one optional argument: const awvr::Span*");
   __shared__ Shared sh;
   __shared__ unsigned long long lstats[STAT_N];
   static_assert(sizeof(Shared) + sizeof(unsigned long long) * STAT_N <= STATIC_LDS_RESERVE, "static LDS reserve");
@@ -3391,7 +3399,15 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
     int status = ST_OK;
     int penalty = -1;
     int sp = 0;
-    if (tid == 0) {
+    if constexpr (RANGES) {
+      // the top-level task is the rectangle the launch names (plenT / tlenT stay the full lengths: the reversed copies are
+      // addressed from the far end)
+      if (tid == 0) {
+        const awvr::Span top = (pair_span_arg, ...)[pair];
+        const bool min_length = max(top.pe - top.pb, top.te - top.tb) <= FALLBACK_MIN_LENGTH;
+        stack[0] = Task{top.pb, top.pe, top.tb, top.te, C_M, C_M, min_length ? 0 : INT_MAX, INT_MAX};
+      }
+    } else if (tid == 0) {
       const bool min_length = max(plenT, tlenT) <= FALLBACK_MIN_LENGTH;
       stack[0] = Task{0, plenT, 0, tlenT, C_M, C_M, min_length ? 0 : INT_MAX, INT_MAX};
     }
@@ -3530,7 +3546,8 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
       lstats[STAT_WIN_SINGLE] += sh.win_single; lstats[STAT_WIN_MULTI] += sh.win_multi; lstats[STAT_WIN_BASE] += sh.win_base; lstats[STAT_WIN_BASE_MULTI] += sh.win_base_multi;
       sh.win_single = sh.win_multi = sh.win_base = sh.win_base_multi = 0;
       if (status == ST_OK) {
-        lstats[STAT_ALIGNED_BP] += (unsigned long long)plenT;
+        if constexpr (RANGES) lstats[STAT_ALIGNED_BP] += (unsigned long long)((pair_span_arg, ...)[pair].pe - (pair_span_arg, ...)[pair].pb);
+        else lstats[STAT_ALIGNED_BP] += (unsigned long long)plenT;
         lstats[STAT_PAIRS] += 1;
       }
     }

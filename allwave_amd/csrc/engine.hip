@@ -153,6 +153,7 @@ struct awv_engine {
   // per-launch buffers
   DevBuf<int32_t> d_pair_q, d_pair_t, d_pair_rc;
   DevBuf<int32_t> d_pair_bound;  // score-only launches with a bound per pair
+  DevBuf<awvr::Span> d_pair_span;  // range launches: the rectangle of every pair
   DevBuf<uint64_t> d_cigar_off;
   DevBuf<awv::DevResult> d_results;
   DevBuf<uint8_t> d_cigar;
@@ -322,9 +323,11 @@ long long worst_case_penalty(const awv::DevPenalties& d, long long n) {
 // max_penalty: that call's bound (INT_MAX = none); pair_bound (nullable, score_only): pair i's own bound instead (INT_MAX = none)
 // vout (nullable; awv_align_pairs_verified, on the engine's own sequence set): every batch's records and op bytes are checked
 // on the device before the batch's CIGARs are copied back
+// spans (nullable; the awv_*_ranges calls): pair i aligns the rectangle spans[i] of its two sequences, in pattern / text
+// coordinates and already validated, instead of the whole of them -- every length below is then the rectangle's
 int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
                awv_result* out, awv_sink sink, void* user, bool score_only = false, int max_penalty = INT_MAX,
-               const int32_t* pair_bound = nullptr, awv_verify_result* vout = nullptr) {
+               const int32_t* pair_bound = nullptr, awv_verify_result* vout = nullptr, const awvr::Span* spans = nullptr) {
   using namespace awv;
   if (npairs < 0 || (npairs > 0 && !pairs)) return fail(AWV_ERR_ARG, "align_pairs: null pairs");
   DevPenalties dp{};
@@ -385,7 +388,19 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
   auto lap = [&](const char* what) {
     if (timing) fprintf(stderr, "[awv] %-22s %.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - tl0).count());
   };
+  // the (pattern, text) lengths pair gi of the call is aligned over: what cost order, kernel flavour, row width, row capacity and
+  // the CIGAR arena are decided by
+  auto pair_lens = [&](int64_t gi, int& ql, int& tl) {
+    if (spans) {
+      ql = spans[gi].pe - spans[gi].pb;
+      tl = spans[gi].te - spans[gi].tb;
+    } else {
+      ql = s.len[pairs[gi].q_idx];
+      tl = s.len[pairs[gi].t_idx];
+    }
+  };
   std::vector<int32_t> hq, ht, hrc, hbound;
+  std::vector<awvr::Span> hspan;
   std::vector<uint64_t> hoff;
   std::vector<awv_result> hres;
   int64_t first = 0;
@@ -417,7 +432,8 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
     hq.clear(); ht.clear(); hrc.clear(); hoff.clear();
     while (first + n < npairs && n < max_batch) {
       const awv_pair& p = pairs[first + n];
-      const int ql = s.len[p.q_idx], tl = s.len[p.t_idx];
+      int ql, tl;
+      pair_lens(first + n, ql, tl);
       const uint64_t need = score_only ? 0 : ((uint64_t)ql + (uint64_t)tl + 7) & ~(uint64_t)7;
       if (n > 0 && arena + need > max_arena) break;
       hq.push_back(p.q_idx);
@@ -441,8 +457,9 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       bool uniform = true;
       for (int64_t i = 0; i < n; ++i) {
         order[(size_t)i] = i;
-        const int64_t ql = s.len[hq[(size_t)i]], tl = s.len[ht[(size_t)i]];
-        cost[(size_t)i] = (uint64_t)(ql + tl + 4 * std::llabs(ql - tl));
+        int ql, tl;
+        pair_lens(first + i, ql, tl);
+        cost[(size_t)i] = (uint64_t)((int64_t)ql + tl + 4 * std::llabs((int64_t)ql - tl));
         uniform = uniform && cost[(size_t)i] == cost[0];
       }
       if (!uniform) {
@@ -497,7 +514,8 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       size_t k = 0;
       g_maxsum = g_maxlen = 0;
       for (size_t i = 0; i < hq.size(); ++i) {
-        const int ql = s.len[hq[i]], tl = s.len[ht[i]];
+        int ql, tl;
+        pair_lens(first + amap[i], ql, tl);
         if (ql > 0 && tl > 0 && std::llabs((long long)ql - tl) > span) {
           awv_result r{};
           r.status = AWV_ST_CAPACITY;
@@ -543,7 +561,11 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
     // tens of GB is the largest fixed cost of a call) and only unusually divergent pairs are re-run.
     // (a length difference forces a gap that long: the rows must span it in both directions)
     int g_maxdelta = 0;
-    for (size_t i = 0; i < hq.size(); ++i) g_maxdelta = std::max(g_maxdelta, std::abs(s.len[hq[i]] - s.len[ht[i]]));
+    for (size_t i = 0; i < hq.size(); ++i) {
+      int ql, tl;
+      pair_lens(first + amap[i], ql, tl);
+      g_maxdelta = std::max(g_maxdelta, std::abs(ql - tl));
+    }
     int wcap = std::min(wcap_full, std::max(std::max(8192, (wcap_full / 2 + 255) & ~255), (2 * g_maxdelta + 4096 + 255) & ~255));
     if (per_slot(wcap) * (size_t)nslots_want > budget) {
       const size_t fixed = hist_stride + EV_EXTRA * sizeof(uint32_t);
@@ -628,6 +650,12 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
         if (int rc = e->d_pair_bound.reserve((size_t)m)) return rc;
         HIP_TRY(hipMemcpyAsync(e->d_pair_bound.p, hbound.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
       }
+      if (spans) {
+        hspan.resize((size_t)m);
+        for (int64_t i = 0; i < m; ++i) hspan[(size_t)i] = spans[first + amap[(size_t)i]];
+        if (int rc = e->d_pair_span.reserve((size_t)m)) return rc;
+        HIP_TRY(hipMemcpyAsync(e->d_pair_span.p, hspan.data(), (size_t)m * sizeof(awvr::Span), hipMemcpyHostToDevice, e->stream));
+      }
       HIP_TRY(hipMemsetAsync(e->d_counters.p, 0, (1 + STAT_N) * sizeof(unsigned long long), e->stream));
       HIP_TRY(hipEventRecord(e->ev1, e->stream));
       HIP_TRY(hipEventSynchronize(e->ev1));
@@ -675,39 +703,46 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       kp.score_only = score_only ? 1 : 0;
       kp.max_penalty = score_only ? max_penalty : INT_MAX;
       kp.pair_max_penalty = score_only && pair_bound ? e->d_pair_bound.p : nullptr;
+      const awvr::Span* const d_span = spans ? e->d_pair_span.p : nullptr;  // (range launches: the kernels' two-argument instantiations)
+      const bool ranged = spans != nullptr;
       HIP_TRY(hipEventRecord(e->ev0, e->stream));
       auto launch = [&](auto kern, const auto& kparams) -> int {
         HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
         hipLaunchKernelGGL(kern, dim3(nslots), dim3(wg), dyn_lds, e->stream, kparams);
         return AWV_OK;
       };
+      auto launch_ranges = [&](auto kern, const auto& kparams) -> int {
+        HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
+        hipLaunchKernelGGL(kern, dim3(nslots), dim3(wg), dyn_lds, e->stream, kparams, d_span);
+        return AWV_OK;
+      };
       int lrc;
       static_assert(sizeof(awvw::KParams) == sizeof(awv::KParams) && sizeof(awvx::KParams) == sizeof(awv::KParams),
                     "same parameter block for every workgroup size");
       if (waves == 1) {
-        HIP_TRY((hipError_t)awv_launch_one_wave(dp.two_piece, narrow ? 1 : 0, (unsigned)nslots, dyn_lds, e->stream, &kp));
+        HIP_TRY((hipError_t)awv_launch_one_wave(dp.two_piece, narrow ? 1 : 0, d_span, (unsigned)nslots, dyn_lds, e->stream, &kp));
         lrc = AWV_OK;
       } else if (wide_meta) {
         static_assert(sizeof(awvw_m::KParams) == sizeof(awv::KParams) && sizeof(awvx_m::KParams) == sizeof(awv::KParams), "same parameter block");
         if (waves == 4) {
           awvw_m::KParams kw;
           std::memcpy(&kw, &kp, sizeof(kw));
-          lrc = dp.two_piece ? launch(awvw_m::biwfa_align_kernel<true, int16_t>, kw) : launch(awvw_m::biwfa_align_kernel<false, int16_t>, kw);
+          lrc = dp.two_piece ? (ranged ? launch_ranges(awvw_m::biwfa_align_kernel<true, int16_t, const awvr::Span*>, kw) : launch(awvw_m::biwfa_align_kernel<true, int16_t>, kw)) : (ranged ? launch_ranges(awvw_m::biwfa_align_kernel<false, int16_t, const awvr::Span*>, kw) : launch(awvw_m::biwfa_align_kernel<false, int16_t>, kw));
         } else {
           awvx_m::KParams kx;
           std::memcpy(&kx, &kp, sizeof(kx));
-          lrc = dp.two_piece ? launch(awvx_m::biwfa_align_kernel<true, int16_t>, kx) : launch(awvx_m::biwfa_align_kernel<false, int16_t>, kx);
+          lrc = dp.two_piece ? (ranged ? launch_ranges(awvx_m::biwfa_align_kernel<true, int16_t, const awvr::Span*>, kx) : launch(awvx_m::biwfa_align_kernel<true, int16_t>, kx)) : (ranged ? launch_ranges(awvx_m::biwfa_align_kernel<false, int16_t, const awvr::Span*>, kx) : launch(awvx_m::biwfa_align_kernel<false, int16_t>, kx));
         }
       } else if (waves == 4) {
         awvw::KParams kw;
         std::memcpy(&kw, &kp, sizeof(kw));
-        if (dp.two_piece) lrc = narrow ? launch(awvw::biwfa_align_kernel<true, int16_t>, kw) : launch(awvw::biwfa_align_kernel<true, int32_t>, kw);
-        else lrc = narrow ? launch(awvw::biwfa_align_kernel<false, int16_t>, kw) : launch(awvw::biwfa_align_kernel<false, int32_t>, kw);
+        if (dp.two_piece) lrc = narrow ? (ranged ? launch_ranges(awvw::biwfa_align_kernel<true, int16_t, const awvr::Span*>, kw) : launch(awvw::biwfa_align_kernel<true, int16_t>, kw)) : (ranged ? launch_ranges(awvw::biwfa_align_kernel<true, int32_t, const awvr::Span*>, kw) : launch(awvw::biwfa_align_kernel<true, int32_t>, kw));
+        else lrc = narrow ? (ranged ? launch_ranges(awvw::biwfa_align_kernel<false, int16_t, const awvr::Span*>, kw) : launch(awvw::biwfa_align_kernel<false, int16_t>, kw)) : (ranged ? launch_ranges(awvw::biwfa_align_kernel<false, int32_t, const awvr::Span*>, kw) : launch(awvw::biwfa_align_kernel<false, int32_t>, kw));
       } else {
         awvx::KParams kx;
         std::memcpy(&kx, &kp, sizeof(kx));
-        if (dp.two_piece) lrc = narrow ? launch(awvx::biwfa_align_kernel<true, int16_t>, kx) : launch(awvx::biwfa_align_kernel<true, int32_t>, kx);
-        else lrc = narrow ? launch(awvx::biwfa_align_kernel<false, int16_t>, kx) : launch(awvx::biwfa_align_kernel<false, int32_t>, kx);
+        if (dp.two_piece) lrc = narrow ? (ranged ? launch_ranges(awvx::biwfa_align_kernel<true, int16_t, const awvr::Span*>, kx) : launch(awvx::biwfa_align_kernel<true, int16_t>, kx)) : (ranged ? launch_ranges(awvx::biwfa_align_kernel<true, int32_t, const awvr::Span*>, kx) : launch(awvx::biwfa_align_kernel<true, int32_t>, kx));
+        else lrc = narrow ? (ranged ? launch_ranges(awvx::biwfa_align_kernel<false, int16_t, const awvr::Span*>, kx) : launch(awvx::biwfa_align_kernel<false, int16_t>, kx)) : (ranged ? launch_ranges(awvx::biwfa_align_kernel<false, int32_t, const awvr::Span*>, kx) : launch(awvx::biwfa_align_kernel<false, int32_t>, kx));
       }
       if (lrc != AWV_OK) return lrc;
       HIP_TRY(hipGetLastError());
@@ -768,15 +803,22 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       std::vector<int64_t> map[NG];
       int gsum[NG] = {0}, glen[NG] = {0};
       // sixteen waves per pair only pay while such pairs are too few to fill the machine four waves at a time
+      // (dispatch index -> the pair's index in the call)
+      auto lens_at = [&](int64_t i, int& ql, int& tl) { pair_lens(first + (amap.empty() ? i : amap[(size_t)i]), ql, tl); };
       int64_t n_huge = 0;
-      for (int64_t i = 0; i < n; ++i) n_huge += std::abs(s.len[hq[(size_t)i]] - s.len[ht[(size_t)i]]) >= 16384;
+      for (int64_t i = 0; i < n; ++i) {
+        int ql, tl;
+        lens_at(i, ql, tl);
+        n_huge += std::abs(ql - tl) >= 16384;
+      }
       const bool use_sixteen = !never_wide && !(e->cfg.flags & AWV_F_FOUR_WAVES) && n_huge > 0 && n_huge <= (int64_t)e->num_cus;
       const bool force32 = (e->cfg.flags & AWV_F_FORCE_INT32) != 0;
       const bool no_wide16 = (e->cfg.flags & AWV_F_NO_WIDE16) != 0;
       std::vector<uint8_t> fl((size_t)n);
       int64_t n_one = 0, n_four = 0;
       for (int64_t i = 0; i < n; ++i) {
-        const int ql = s.len[hq[(size_t)i]], tl = s.len[ht[(size_t)i]];
+        int ql, tl;
+        lens_at(i, ql, tl);
         const int dl = std::abs(ql - tl);
         int f = (all_wide || (!never_wide && (dl >= 4096 || std::max(ql, tl) >= 32760))) ? 1 : 0;
         if (use_sixteen && dl >= 16384) f = 2;  // a forced gap that long: rows hundreds of windows wide
@@ -792,8 +834,9 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       // waves too (config 5: 3,315 such pairs, 2.9 s at 61 % of the CUs busy).  (Pairs come in descending cost order.)
       if (!never_wide && n_one > 0 && n_four > 0 && n_one <= (int64_t)(WAVES_PER_SIMD * 256 / 64) * e->num_cus) {
         auto cost_of = [&](int64_t i) {
-          const int64_t ql = s.len[hq[(size_t)i]], tl = s.len[ht[(size_t)i]];
-          return (uint64_t)(ql + tl + 4 * std::llabs(ql - tl));
+          int ql, tl;
+          lens_at(i, ql, tl);
+          return (uint64_t)((int64_t)ql + tl + 4 * std::llabs((int64_t)ql - tl));
         };
         int64_t first_one = -1, seen = 0, median_one = -1;
         for (int64_t i = 0; i < n && median_one < 0; ++i) {
@@ -806,7 +849,8 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
             if (fl[(size_t)i] == 0) fl[(size_t)i] = 1;
       }
       for (int64_t i = 0; i < n; ++i) {
-        const int ql = s.len[hq[(size_t)i]], tl = s.len[ht[(size_t)i]];
+        int ql, tl;
+        lens_at(i, ql, tl);
         const int f = fl[(size_t)i];
         // row width: every stored value must fit 16 bits -- text offsets (both lengths short), or min(h, v) when only
         // the shorter sequence is (the kernels for that exist in the four- and sixteen-wave flavours)
@@ -844,7 +888,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
     const bool want_cigar = sink && !score_only && !(e->cfg.flags & AWV_F_KEEP_ON_DEVICE);
     lap("results on host");
     if (vout) {  // the groups of a batch overwrite d_results: the batch's records, as gathered in hres, go up once for the check
-      if (int rc = awvf::verify_batch(e, pen, pairs + first, n, hres.data(), e->d_cigar.p, arena, vout + first)) return rc;
+      if (int rc = awvf::verify_batch(e, pen, pairs + first, n, hres.data(), e->d_cigar.p, arena, vout + first, spans ? spans + first : nullptr)) return rc;
       lap("batch verified");
     }
     if (want_cigar) {
@@ -970,6 +1014,7 @@ void awv_engine_destroy(awv_engine* e) {
   e->d_pair_t.release();
   e->d_pair_rc.release();
   e->d_pair_bound.release();
+  e->d_pair_span.release();
   e->d_cigar_off.release();
   e->d_results.release();
   e->d_cigar.release();
@@ -1019,7 +1064,7 @@ int awv_align_pairs_verified(awv_engine* e, const awv_penalties* pen, const awv_
 namespace {
 // awv_score_pairs / awv_score_pairs_bounded: one bound for the call (pair_bound == nullptr), or one per pair
 int score_core(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, int32_t max_penalty,
-               const int32_t* pair_bound, awv_score_result* out) {
+               const int32_t* pair_bound, awv_score_result* out, const awvr::Span* spans = nullptr) {
   if (!e) {  // (without a GPU there is no engine to pass: say so, as awv_engine_create does)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(AWV_ERR_NO_DEVICE, "no HIP device available: liballwave_hip has no CPU fallback");
@@ -1038,7 +1083,7 @@ int score_core(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, i
       for (int64_t i = 0; i < npairs; ++i) pb[(size_t)i] = norm(pair_bound[i]);
     }
     const int rc = align_core(e, e->seqs, pen, pairs, npairs, res.data(), nullptr, nullptr, true, norm(max_penalty),
-                              pair_bound ? pb.data() : nullptr);
+                              pair_bound ? pb.data() : nullptr, nullptr, spans);
     if (rc != AWV_OK) return rc;
     for (int64_t i = 0; i < npairs; ++i) {
       out[i].status = res[(size_t)i].status;
@@ -1058,6 +1103,58 @@ int awv_score_pairs_bounded(awv_engine* e, const awv_penalties* pen, const awv_p
                             const int32_t* max_penalty, awv_score_result* out) {
   if (e && npairs > 0 && !max_penalty) return fail(AWV_ERR_ARG, "score_pairs_bounded: null max_penalty");
   return score_core(e, pen, pairs, npairs, -1, max_penalty, out);
+}
+
+// ---- ranges: the same calls over sub-intervals of the resident sequences.  Each range becomes the pair and the rectangle
+// (pattern / text coordinates) align_core works on; nothing is launched when one of them is invalid.
+namespace {
+int split_ranges(const SeqSet& s, const awv_range_pair* ranges, int64_t n, std::vector<awv_pair>& pairs, std::vector<awvr::Span>& spans,
+                 const char* who) {
+  pairs.resize((size_t)n);
+  spans.resize((size_t)n);
+  for (int64_t i = 0; i < n; ++i)
+    if (!awvr::split_range(s.len.data(), s.n, ranges[i], pairs[(size_t)i], spans[(size_t)i]))
+      return fail(AWV_ERR_ARG, std::string(who) + ": range " + std::to_string(i) + " names a sequence index or an interval out of range");
+  return AWV_OK;
+}
+int align_ranges_core(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, awv_result* out,
+                      awv_verify_result* vout, awv_sink sink, void* user) {
+  if (n < 0 || (n > 0 && !ranges)) return fail(AWV_ERR_ARG, "align_ranges: null ranges");
+  if (e->seqs.n == 0 && n > 0) return fail(AWV_ERR_STATE, "align_ranges before set_sequences");
+  std::vector<awv_pair> pairs;
+  std::vector<awvr::Span> spans;
+  if (int rc = split_ranges(e->seqs, ranges, n, pairs, spans, "align_ranges")) return rc;
+  if (vout) awvf::stats_reset(e->verify);
+  if (n == 0) return align_core(e, e->seqs, pen, nullptr, 0, out, sink, user);
+  return align_core(e, e->seqs, pen, pairs.data(), n, out, sink, user, false, INT_MAX, nullptr, vout, spans.data());
+}
+}  // namespace
+
+int awv_align_ranges(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, awv_result* out,
+                     awv_sink sink, void* user) {
+  if (!e) return fail(AWV_ERR_ARG, "null engine");
+  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, out, nullptr, sink, user);)
+}
+
+int awv_align_ranges_verified(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, awv_result* out,
+                              awv_verify_result* vout, awv_sink sink, void* user) {
+  if (!e) return fail(AWV_ERR_ARG, "null engine");
+  if (!vout) return fail(AWV_ERR_ARG, "align_ranges_verified: null vout");
+  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, out, vout, sink, user);)
+}
+
+int awv_score_ranges(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const int32_t* max_penalty,
+                     awv_score_result* out) {
+  if (!e) return score_core(nullptr, pen, nullptr, 0, -1, nullptr, out);  // (says which: no device, or a null engine)
+  if (!out) return fail(AWV_ERR_ARG, "score_ranges: null out");
+  if (n < 0 || (n > 0 && !ranges)) return fail(AWV_ERR_ARG, "score_ranges: null ranges");
+  if (e->seqs.n == 0 && n > 0) return fail(AWV_ERR_STATE, "score_ranges before set_sequences");
+  AWV_GUARDED(
+    std::vector<awv_pair> pairs;
+    std::vector<awvr::Span> spans;
+    if (int rc = split_ranges(e->seqs, ranges, n, pairs, spans, "score_ranges")) return rc;
+    return score_core(e, pen, pairs.data(), n, -1, max_penalty, out, spans.data());
+  )
 }
 
 namespace {

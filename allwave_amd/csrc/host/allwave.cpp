@@ -264,11 +264,13 @@ void upload(awv_engine* e, const std::vector<Sequence>& seqs) {
     throw AlignmentError(std::string("set_sequences: ") + awv_last_error());
 }
 
-// planner::predicted_pair_cost of pairs[0, n)
+// planner::predicted_pair_cost of pairs[0, n) (ranges, nullable: entry i is that interval pair -- its lengths count)
 std::vector<double> pair_costs(const std::vector<Sequence>& seqs, const std::pair<size_t, size_t>* pairs, size_t n,
-                               const AlignmentParams& params) {
+                               const AlignmentParams& params, const AlignmentRange* ranges = nullptr) {
   std::vector<double> cost(n);
-  for (size_t i = 0; i < n; ++i) cost[i] = planner::predicted_pair_cost(seqs[pairs[i].first].seq.size(), seqs[pairs[i].second].seq.size(), params);
+  for (size_t i = 0; i < n; ++i)
+    cost[i] = ranges ? planner::predicted_pair_cost(ranges[i].query_end - ranges[i].query_start, ranges[i].target_end - ranges[i].target_start, params)
+                     : planner::predicted_pair_cost(seqs[pairs[i].first].seq.size(), seqs[pairs[i].second].seq.size(), params);
   return cost;
 }
 
@@ -291,6 +293,45 @@ AlignmentResult make_result(size_t qi, size_t ti, bool is_rev, const awv_result&
   return a;
 }
 }  // namespace
+
+AlignmentResult range_alignment_result(const AlignmentRange& g, const awv_result& r, const uint8_t* arena, bool copy_cigar) {
+  AlignmentResult a = make_result(g.query_idx, g.target_idx, g.is_reverse, r, arena, copy_cigar);
+  a.query_start = g.query_start;
+  a.query_end += g.query_start;
+  a.target_start = g.target_start;
+  a.target_end += g.target_start;
+  return a;
+}
+
+AlignmentResult AllPairIterator::result_at(size_t k, bool is_rev, const awv_result& r, const uint8_t* arena, bool copy_cigar) const {
+  if (ranges_) return range_alignment_result((*ranges_)[k], r, arena, copy_cigar);
+  return make_result(pairs_[k].first, pairs_[k].second, is_rev, r, arena, copy_cigar);
+}
+
+AllPairIterator AllPairIterator::for_ranges(const std::vector<Sequence>& sequences, std::vector<AlignmentRange> ranges, AlignmentParams params) {
+  AllPairIterator it(sequences, std::move(params), false);
+  it.pairs_.reserve(ranges.size());
+  for (size_t k = 0; k < ranges.size(); ++k) {
+    const AlignmentRange& g = ranges[k];
+    if (g.query_idx >= sequences.size() || g.target_idx >= sequences.size() || g.query_start > g.query_end ||
+        g.query_end > sequences[g.query_idx].seq.size() || g.target_start > g.target_end || g.target_end > sequences[g.target_idx].seq.size())
+      throw std::invalid_argument("for_ranges: range " + std::to_string(k) + " names a sequence index or an interval out of range");
+    it.pairs_.emplace_back(g.query_idx, g.target_idx);
+  }
+  it.orientation_ = Orientation::ForwardOnly;  // (the strand is each range's own)
+  it.ranges_ = std::make_shared<const std::vector<AlignmentRange>>(std::move(ranges));
+  return it;
+}
+
+void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
+                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
+                  awv_verify_stats* verify_stats) {
+  AllPairIterator it = AllPairIterator::for_ranges(sequences, ranges, std::move(params));
+  it.with_devices(devices).with_verify(verify);
+  it.for_each_with_callback(callback);
+  if (failures) *failures = it.verify_failures();
+  if (verify_stats) *verify_stats = it.last_verify_stats();
+}
 
 AllPairIterator::AllPairIterator(const std::vector<Sequence>& sequences, AlignmentParams params)
     : AllPairIterator(sequences, std::move(params), true) {}
@@ -425,6 +466,7 @@ AllPairIterator& AllPairIterator::with_shard(size_t rank, size_t world) {
   // cost-balanced shards (planner::assign_shards_lpt): every process derives the same partition and
   // keeps its own part, in list order; equal-cost lists (config 2 / 3) come out strided
   if (world <= 1) return *this;
+  if (ranges_) throw std::invalid_argument("with_shard: not for a range list");
   const std::vector<uint32_t> shard = planner::assign_shards_lpt(pair_costs(sequences_, pairs_.data(), pairs_.size(), params_), world);
   std::vector<std::pair<size_t, size_t>> mine;
   mine.reserve(pairs_.size() / world + 1);
@@ -435,6 +477,7 @@ AllPairIterator& AllPairIterator::with_shard(size_t rank, size_t world) {
 }
 
 AllPairIterator AllPairIterator::with_sparsification(SparsificationStrategy strategy) const {  // iterator.rs:101-110
+  if (ranges_) throw std::invalid_argument("with_sparsification: not for a range list");
   AllPairIterator it = with_options(sequences_, params_, exclude_self_, orientation_ == Orientation::Mash, std::move(strategy), plan_device_);
   if (orientation_ == Orientation::ForwardOnly) it.orientation_ = Orientation::ForwardOnly;  // (this build's extension survives)
   it.devices_ = devices_;
@@ -458,8 +501,7 @@ std::optional<AlignmentResult> AllPairIterator::next() {  // iterator.rs:151-171
     run(first, cnt, [&](const Batch& b) {  // (every entry has its own slot of buf: no lock)
       for (int64_t i = 0; i < b.n; ++i) {
         const size_t k = b.pair(i);
-        const auto& pr = pairs_[first + k];
-        buf[k] = make_result(pr.first, pr.second, b.is_rev(i), b.res[i], b.arena, true);
+        buf[k] = result_at(first + k, b.is_rev(i), b.res[i], b.arena, true);
       }
     });
     // (only a run that returned moves the position on: after an error the next call runs the same chunk again)
@@ -486,9 +528,8 @@ void AllPairParallelIterator::for_each_with_callback(const Callback& cb) {
       for (;;) {
         const int64_t i = cursor.fetch_add(1);
         if (i >= cnt || stop.load()) return;
-        const auto& pr = it_.pairs_[b.pair(i)];
         try {
-          cb(make_result(pr.first, pr.second, b.is_rev(i), b.res[i], b.arena, true));
+          cb(it_.result_at(b.pair(i), b.is_rev(i), b.res[i], b.arena, true));
         } catch (...) {
           std::lock_guard<std::mutex> g(mu);
           if (!err) err = std::current_exception();
@@ -511,8 +552,7 @@ std::vector<AlignmentResult> AllPairParallelIterator::collect() {
   it_.run([&](const AllPairIterator::Batch& b) {  // (every pair has its own slot of `out`: no lock)
     for (int64_t i = 0; i < b.n; ++i) {
       const size_t k = b.pair(i);
-      const auto& pr = it_.pairs_[k];
-      out[k] = make_result(pr.first, pr.second, b.is_rev(i), b.res[i], b.arena, true);
+      out[k] = it_.result_at(k, b.is_rev(i), b.res[i], b.arena, true);
     }
   });
   return out;
@@ -570,12 +610,16 @@ void add_stats(awv_stats& acc, const awv_stats& x, bool same_engine) {
 
 // one batch's engine call: awv_align_pairs (awv_align_pairs_verified when `vout` is given), or awv_score_pairs under
 // max_penalty (< 0: no bound) with its results handed to the sink in one call (status and penalty, no arena)
+// rp (nullable): the batch is these n interval pairs -- the same three calls on ranges, `ap` is not read
 int engine_call(awv_engine* e, bool score_only, int32_t max_penalty, const awv_penalties& pen, const awv_pair* ap, int64_t n,
-                awv_sink sink, void* user, awv_verify_result* vout) {
+                awv_sink sink, void* user, awv_verify_result* vout, const awv_range_pair* rp = nullptr) {
+  if (rp && !score_only) return vout ? awv_align_ranges_verified(e, &pen, rp, n, nullptr, vout, sink, user) : awv_align_ranges(e, &pen, rp, n, nullptr, sink, user);
   if (!score_only && vout) return awv_align_pairs_verified(e, &pen, ap, n, nullptr, vout, sink, user);
   if (!score_only) return awv_align_pairs(e, &pen, ap, n, nullptr, sink, user);
   std::vector<awv_score_result> sr((size_t)n);
-  const int rc = awv_score_pairs(e, &pen, ap, n, max_penalty, sr.data());
+  std::vector<int32_t> bounds(rp && max_penalty >= 0 ? (size_t)n : 0, max_penalty);
+  const int rc = rp ? awv_score_ranges(e, &pen, rp, n, bounds.empty() ? nullptr : bounds.data(), sr.data())
+                    : awv_score_pairs(e, &pen, ap, n, max_penalty, sr.data());
   if (rc != AWV_OK || n == 0) return rc;
   std::vector<awv_result> res((size_t)n);
   for (int64_t i = 0; i < n; ++i) {
@@ -609,10 +653,10 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   };
   // pair indices (relative to `first`) of each batch; one slot's single batch needs none (Batch::idx == nullptr)
   const std::vector<std::vector<size_t>> batches =
-      S > 1 ? planner::device_batches(pair_costs(sequences_, plist, count, params_), S, min_batch_pairs_)
+      S > 1 ? planner::device_batches(pair_costs(sequences_, plist, count, params_, ranges_ ? ranges_->data() + first : nullptr), S, min_batch_pairs_)
             : std::vector<std::vector<size_t>>(1);
   std::vector<uint8_t> mash_rev;
-  if (orientation_ == Orientation::Mash)  // alignment.rs:69-94 (host threads: the CLI's -t)
+  if (orientation_ == Orientation::Mash && !ranges_)  // alignment.rs:69-94 (host threads: the CLI's -t)
     mash_rev = planner::orient_pairs_mash(sequences_, plist, count, threads_ > 0 ? threads_ : planner::host_threads(), plan_device_);
   // slot number of every entry on its device, and how many slots each device has in this run
   std::map<int, int> per_device;
@@ -667,7 +711,14 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
         std::vector<awv_pair> ap((size_t)m);
         std::vector<uint8_t> rev((size_t)m, 0);
         for (int64_t i = 0; i < m; ++i) ap[i] = awv_pair{(int32_t)plist[at(i)].first, (int32_t)plist[at(i)].second, 0};
-        if (orientation_ == Orientation::Mash) {
+        std::vector<awv_range_pair> rp(ranges_ ? (size_t)m : 0);
+        if (ranges_) {
+          for (int64_t i = 0; i < m; ++i) {
+            const AlignmentRange& g = (*ranges_)[first + at(i)];
+            rev[i] = g.is_reverse ? 1 : 0;
+            rp[i] = awv_range_pair{ap[i].q_idx, ap[i].t_idx, rev[i], (int32_t)g.query_start, (int32_t)g.query_end, (int32_t)g.target_start, (int32_t)g.target_end};
+          }
+        } else if (orientation_ == Orientation::Mash) {
           for (int64_t i = 0; i < m; ++i) rev[i] = mash_rev[at(i)];
         } else if (orientation_ == Orientation::Wfa) {
           orient_wfa(e, open, ap.data(), m, full_wfa_orientation_, rev.data());
@@ -695,7 +746,8 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
           return 0;
         };
         std::vector<awv_verify_result> vr(verify ? (size_t)m : 0);
-        const int rc = engine_call(e, call.score_only, call.max_penalty, pen, ap.data(), m, sink, &ctx, verify ? vr.data() : nullptr);
+        const int rc = engine_call(e, call.score_only, call.max_penalty, pen, ap.data(), m, sink, &ctx, verify ? vr.data() : nullptr,
+                                   ranges_ ? rp.data() : nullptr);
         lap("aligned + sunk");
         awv_stats x{};
         awv_engine_stats(e, &x);
@@ -758,10 +810,7 @@ void AllPairIterator::for_each_with_callback(const Callback& cb) {
     std::lock_guard<std::mutex> g(mu);
     if (first) std::rethrow_exception(first);
     try {
-      for (int64_t i = 0; i < b.n; ++i) {
-        const auto& pr = pairs_[b.pair(i)];
-        cb(make_result(pr.first, pr.second, b.is_rev(i), b.res[i], b.arena, true));
-      }
+      for (int64_t i = 0; i < b.n; ++i) cb(result_at(b.pair(i), b.is_rev(i), b.res[i], b.arena, true));
     } catch (...) {
       first = std::current_exception();
       throw;
@@ -788,8 +837,7 @@ void AllPairIterator::for_each_paf_batch(const std::function<void(const std::str
         std::string& out = parts[(size_t)t];
         out.reserve((size_t)(hi - lo) * 4096);
         for (int64_t i = lo; i < hi; ++i) {
-          const auto& pr = pairs_[b.pair(i)];
-          const AlignmentResult a = make_result(pr.first, pr.second, b.is_rev(i), res[i], arena, false);
+          const AlignmentResult a = result_at(b.pair(i), b.is_rev(i), res[i], arena, false);
           const bool ok = res[i].status == AWV_ST_COMPLETED;
           append_paf(out, a, ok ? arena + res[i].cigar_off : nullptr, ok ? res[i].cigar_len : 0, sequences_);
           out.push_back('\n');
@@ -889,8 +937,56 @@ bool parse_size(const std::string& s, size_t& v) {
 }
 }  // namespace
 
+namespace {
+std::vector<std::string> split_tabs(const std::string& line) {
+  std::vector<std::string> f;
+  for (size_t b = 0;;) {
+    const size_t e = line.find('\t', b);
+    f.push_back(line.substr(b, e == std::string::npos ? std::string::npos : e - b));
+    if (e == std::string::npos) break;
+    b = e + 1;
+  }
+  return f;
+}
+}  // namespace
+
+PafRanges parse_paf_ranges(const std::vector<Sequence>& sequences, const std::string& paf_text) {
+  PafRanges out;
+  std::map<std::string, size_t> by_name;
+  for (size_t i = 0; i < sequences.size(); ++i) by_name.emplace(sequences[i].id, i);  // (the first of equal names)
+  size_t pos = 0, line_no = 0;
+  while (pos < paf_text.size()) {
+    size_t nl = paf_text.find('\n', pos);
+    if (nl == std::string::npos) nl = paf_text.size();
+    std::string line = paf_text.substr(pos, nl - pos);
+    pos = nl + 1;
+    ++line_no;
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    if (line.empty()) continue;
+    const std::vector<std::string> f = split_tabs(line);
+    PafRangeLine pl;
+    pl.line = line_no;
+    size_t qlen, qs, qe, tlen, ts, te;
+    if (f.size() < 9 || f[4].size() != 1 || (f[4][0] != '+' && f[4][0] != '-') || !parse_size(f[1], qlen) || !parse_size(f[2], qs) ||
+        !parse_size(f[3], qe) || !parse_size(f[6], tlen) || !parse_size(f[7], ts) || !parse_size(f[8], te)) {
+      pl.cls = "bad_line";
+    } else {
+      const auto qi = by_name.find(f[0]), ti = by_name.find(f[5]);
+      if (qi == by_name.end() || ti == by_name.end()) pl.cls = "unknown_name";
+      else if (qlen != sequences[qi->second].seq.size() || tlen != sequences[ti->second].seq.size()) pl.cls = "length_mismatch";
+      else if (qs > qe || qe > qlen || ts > te || te > tlen) pl.cls = "bad_line";  // (numbers that cannot be an interval of the sequence)
+      else {
+        pl.index = out.ranges.size();
+        out.ranges.push_back(AlignmentRange{qi->second, ti->second, f[4][0] == '-', qs, qe, ts, te});
+      }
+    }
+    out.lines.push_back(std::move(pl));
+  }
+  return out;
+}
+
 PafCheckReport check_paf(const std::vector<Sequence>& sequences, const std::string& paf_text, const AlignmentParams& params,
-                         bool optimal, int device) {
+                         bool optimal, int device, bool partial) {
   PafCheckReport rep;
   std::map<std::string, size_t> by_name;
   for (size_t i = 0; i < sequences.size(); ++i) by_name.emplace(sequences[i].id, i);  // (the first of equal names)
@@ -902,6 +998,7 @@ PafCheckReport check_paf(const std::vector<Sequence>& sequences, const std::stri
   std::vector<PafCheckFailure> pending;
   std::vector<Entry> entries;
   std::vector<awv_pair> ap;
+  std::vector<awv_range_pair> rp;  // `partial`: the same entries as interval pairs
   std::vector<awv_result> recs;
   std::vector<uint8_t> arena, ops;
   size_t pos = 0, line_no = 0;
@@ -914,13 +1011,7 @@ PafCheckReport check_paf(const std::vector<Sequence>& sequences, const std::stri
     if (!line.empty() && line.back() == '\r') line.pop_back();
     if (line.empty()) continue;
     ++rep.lines;
-    std::vector<std::string> f;
-    for (size_t b = 0;;) {
-      const size_t e = line.find('\t', b);
-      f.push_back(line.substr(b, e == std::string::npos ? std::string::npos : e - b));
-      if (e == std::string::npos) break;
-      b = e + 1;
-    }
+    const std::vector<std::string> f = split_tabs(line);
     PafCheckFailure pf;
     pf.line = line_no;
     if (f.size() > 0) pf.qname = f[0];
@@ -945,7 +1036,7 @@ PafCheckReport check_paf(const std::vector<Sequence>& sequences, const std::stri
     } else if (cg->size() == 5 && qs == 0 && qe == 0 && ts == 0 && te == 0) {
       ++rep.skipped;  // the empty record a failed pair leaves
       continue;
-    } else if (qs != 0 || ts != 0 || qe != qlen || te != tlen) {
+    } else if ((qs != 0 || ts != 0 || qe != qlen || te != tlen) && !(partial && qs <= qe && qe <= qlen && ts <= te && te <= tlen)) {
       pf.cls = "not_end_to_end";
     } else if (!cigar_string_to_bytes(cg->substr(5), ops)) {
       pf.cls = "bad_cigar";
@@ -968,10 +1059,11 @@ PafCheckReport check_paf(const std::vector<Sequence>& sequences, const std::stri
     r.num_mismatches = (int32_t)nx;
     r.num_ins = (int32_t)ni;
     r.num_del = (int32_t)nd;
-    r.q_end = (int32_t)qe;
-    r.t_end = (int32_t)te;
+    r.q_end = (int32_t)(qe - qs);  // (consumed lengths: the whole sequences' for an end-to-end line)
+    r.t_end = (int32_t)(te - ts);
     arena.insert(arena.end(), ops.begin(), ops.end());
     ap.push_back(awv_pair{(int32_t)qi->second, (int32_t)ti->second, pf.strand == '-' ? 1 : 0});
+    if (partial) rp.push_back(awv_range_pair{ap.back().q_idx, ap.back().t_idx, ap.back().q_revcomp, (int32_t)qs, (int32_t)qe, (int32_t)ts, (int32_t)te});
     recs.push_back(r);
     entries.push_back(Entry{pending.size(), c10, c11, qe - qs, te - ts});
     pending.push_back(pf);
@@ -984,13 +1076,15 @@ PafCheckReport check_paf(const std::vector<Sequence>& sequences, const std::stri
     upload(e, sequences);
     std::vector<awv_verify_result> vr(entries.size());
     arena.resize(arena.size() + 16);  // (never an empty arena)
-    if (awv_verify_cigars(e, &pen, ap.data(), (int64_t)ap.size(), recs.data(), arena.data(), arena.size(), vr.data()) != AWV_OK)
+    if ((partial ? awv_verify_ranges(e, &pen, rp.data(), (int64_t)rp.size(), recs.data(), arena.data(), arena.size(), vr.data())
+                 : awv_verify_cigars(e, &pen, ap.data(), (int64_t)ap.size(), recs.data(), arena.data(), arena.size(), vr.data())) != AWV_OK)
       throw AlignmentError(std::string("verify_cigars: ") + awv_last_error());
     awv_engine_verify_stats(e, &rep.stats);
     std::vector<awv_score_result> sr;
     if (optimal) {
       sr.resize(entries.size());
-      if (awv_score_pairs(e, &pen, ap.data(), (int64_t)ap.size(), -1, sr.data()) != AWV_OK)
+      if ((partial ? awv_score_ranges(e, &pen, rp.data(), (int64_t)rp.size(), nullptr, sr.data())
+                   : awv_score_pairs(e, &pen, ap.data(), (int64_t)ap.size(), -1, sr.data())) != AWV_OK)
         throw AlignmentError(std::string("score_pairs: ") + awv_last_error());
     }
     for (size_t k = 0; k < entries.size(); ++k) {

@@ -15,6 +15,7 @@
 
 #include <cstdint>
 #include <functional>
+#include <memory>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -96,6 +97,16 @@ struct PairScore {
 
 using Callback = std::function<void(AlignmentResult&&)>;  // may throw: first error aborts the run
 
+// One interval pair to align globally (awv_range_pair): query[query_start, query_end) -- on the query's FORWARD strand, as PAF
+// writes it, also when is_reverse -- against target[target_start, target_end).  Its AlignmentResult carries these coordinates
+// (a failed range: query_start twice and target_start twice, an empty CIGAR), so alignment_to_paf prints columns 3-4 and 8-9
+// as the interval and columns 2 and 7 as the full lengths.
+struct AlignmentRange {
+  size_t query_idx = 0, target_idx = 0;
+  bool is_reverse = false;
+  size_t query_start = 0, query_end = 0, target_start = 0, target_end = 0;
+};
+
 // One pair whose alignment did not pass the on-device check (AllPairIterator::with_verify): code = AWV_VF_*, column and
 // penalty as in awv_verify_result.
 struct VerifyFailure {
@@ -137,6 +148,11 @@ class AllPairIterator {  // iterator.rs:12-171
   // AlignmentError without that device); plan_device < 0: on the host, as above.  The plan device also runs mash orientation.
   static AllPairIterator with_options(const std::vector<Sequence>& sequences, AlignmentParams params, bool exclude_self,
                                       bool use_mash_orientation, SparsificationStrategy s, int plan_device);
+  // An iterator over a list of interval pairs instead of a planned pair list: entry k aligns ranges[k] (awv_align_ranges; the
+  // strand is the range's own, no orientation pass runs).  Every consumer, with_devices, with_verify, with_min_batch_pairs and
+  // scores() work as on a pair list -- the same slots and batches; with_shard and with_sparsification do not apply.
+  // std::invalid_argument for an index or an interval out of range.
+  static AllPairIterator for_ranges(const std::vector<Sequence>& sequences, std::vector<AlignmentRange> ranges, AlignmentParams params);
   // the device mash orientation and with_sparsification plan on from now on (< 0: the host, the default); the current list stays
   AllPairIterator& with_plan_device(int plan_device);
   int plan_device() const { return plan_device_; }
@@ -226,6 +242,9 @@ class AllPairIterator {  // iterator.rs:12-171
   // serialise it.
   void run(size_t first, size_t count, const BatchCb& batch_cb, EngineCall call = {false, -1});
   void run(const BatchCb& batch_cb, EngineCall call = {false, -1}) { run(0, pairs_.size(), batch_cb, call); }
+  // align_pair's result mapping for entry k of the pair list (a range list: in the range's coordinates)
+  AlignmentResult result_at(size_t k, bool is_rev, const awv_result& r, const uint8_t* arena, bool copy_cigar) const;
+  std::shared_ptr<const std::vector<AlignmentRange>> ranges_;  // for_ranges: entry k of pairs_ is this interval pair
   AllPairIterator(const std::vector<Sequence>& sequences, AlignmentParams params, bool enumerate);  // enumerate = false: no pairs
   const std::vector<Sequence>& sequences_;
   AlignmentParams params_, orientation_params_;
@@ -279,6 +298,31 @@ void process_alignments_with_callback(const std::vector<Sequence>& sequences, Al
                                       SparsificationStrategy sparsification, const Callback& callback,
                                       const std::vector<int>& devices);
 
+// A range's engine record as an AlignmentResult in the sequences' coordinates: the record's q_end / t_end are consumed
+// lengths, so the interval's starts are added (a failed record: the starts twice, score i32::MAX, no CIGAR).
+AlignmentResult range_alignment_result(const AlignmentRange& range, const awv_result& r, const uint8_t* arena, bool copy_cigar);
+
+// The interval pairs `ranges` aligned globally under `params` on the engines `devices` names (AllPairIterator::for_ranges +
+// for_each_with_callback: the callback's calls never overlap; on one slot they come in list order).  verify: every finished
+// range is checked on the device (awv_align_ranges_verified); failures (nullable) receives what failed, index = list index.
+void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
+                  const Callback& callback, const std::vector<int>& devices = {0}, bool verify = false,
+                  std::vector<VerifyFailure>* failures = nullptr, awv_verify_stats* verify_stats = nullptr);
+
+// ---- mappings in, alignments out: the interval pairs a PAF file names (columns 1-9 of each line) ----
+struct PafRangeLine {
+  size_t line = 0;   // 1-based line of the text
+  std::string cls;   // empty: ranges[index] is this line's interval pair; else "bad_line", "unknown_name", "length_mismatch"
+  size_t index = 0;
+};
+struct PafRanges {
+  std::vector<AlignmentRange> ranges;  // of the good lines, in line order
+  std::vector<PafRangeLine> lines;     // every non-empty line
+};
+// Names are resolved as check_paf resolves them (the first of equal names).  "bad_line": fewer than 9 columns, a strand other
+// than + / -, a number that does not parse, or an interval that is not 0 <= start <= end <= length.
+PafRanges parse_paf_ranges(const std::vector<Sequence>& sequences, const std::string& paf_text);
+
 // ---- checking a PAF file against the sequences, on the device (nothing is aligned) ----
 // the op bytes of a PAF cg string, cigar_bytes_to_string undone ('=' -> M, X -> X, D -> I, I -> D); false when the string
 // is not <count><op>... over those four letters with counts >= 1
@@ -304,8 +348,10 @@ struct PafCheckReport {
 // longer span) through awv_verify_cigars on `device`.  A line carries no penalty: the re-scored one is reported and never
 // compared.  optimal: awv_score_pairs on the same (pair, strand) list as well; an op string that costs more than the
 // optimum is "not_optimal", one that costs less "below_optimum" (a finding against the engine, not the PAF).
+// partial: a line whose coordinates are a proper interval (0 <= start <= end <= length on both sequences) is checked as the
+// global alignment of that interval pair (awv_verify_ranges; `optimal`: awv_score_ranges) instead of being "not_end_to_end".
 PafCheckReport check_paf(const std::vector<Sequence>& sequences, const std::string& paf_text, const AlignmentParams& params,
-                         bool optimal, int device = 0);
+                         bool optimal, int device = 0, bool partial = false);
 // one tab-separated line per failure: line qname tname strand class column penalty [optimum]
 std::string format_paf_check(const PafCheckReport& r);
 

@@ -525,11 +525,11 @@ long awh_cigar_string_to_bytes(const char* cg, uint8_t* out, size_t cap) {
 
 // check_paf on `device`: out = format_paf_check's lines (malloc'ed), counts = {lines, checked, skipped, failures}
 int awh_check_paf(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores, const char* paf,
-                  size_t paf_len, int optimal, int device, char** out, size_t* out_len, uint64_t counts[4], awv_verify_stats* st,
+                  size_t paf_len, int optimal, int partial, int device, char** out, size_t* out_len, uint64_t counts[4], awv_verify_stats* st,
                   char* err, size_t cap) {
   try {
     const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
-    const PafCheckReport r = check_paf(seqs, std::string(paf, paf_len), parse_scores(scores), optimal != 0, device);
+    const PafCheckReport r = check_paf(seqs, std::string(paf, paf_len), parse_scores(scores), optimal != 0, device, partial != 0);
     const std::string txt = format_paf_check(r);
     *out = (char*)malloc(txt.size() + 1);
     if (!*out) throw std::bad_alloc();
@@ -539,6 +539,82 @@ int awh_check_paf(int n, const char* const* ids, const uint8_t* bytes, const uin
     if (st) *st = r.stats;
     return 0;
   } catch (const std::exception& e) { set_err(err, cap, e.what()); return -1; }
+}
+
+// ---- ranges ----
+// allwave::align_ranges + alignment_to_paf per record: ranges = nr records of seven int64 (query_idx, target_idx, is_reverse,
+// query_start, query_end, target_start, target_end), on the engines `devices[0, n_devices)` names; out = the PAF lines in
+// list order (malloc'ed).  The verify counters and failures are left for awh_last_verify.
+int awh_align_ranges_paf(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores, const int64_t* ranges,
+                         size_t nr, const int32_t* devices, int n_devices, int verify, char** out, size_t* out_len, char* err, size_t cap) {
+  try {
+    if (!devices || n_devices < 1) throw std::invalid_argument("awh_align_ranges_paf: empty device list");
+    const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
+    std::vector<AlignmentRange> rg(nr);
+    for (size_t i = 0; i < nr; ++i) {
+      const int64_t* r = ranges + 7 * i;
+      for (int k = 0; k < 7; ++k)
+        if (r[k] < 0) throw std::invalid_argument("awh_align_ranges_paf: negative field in range " + std::to_string(i));
+      rg[i] = AlignmentRange{(size_t)r[0], (size_t)r[1], r[2] != 0, (size_t)r[3], (size_t)r[4], (size_t)r[5], (size_t)r[6]};
+    }
+    AllPairIterator it = AllPairIterator::for_ranges(seqs, rg, parse_scores(scores));
+    it.with_devices(std::vector<int>(devices, devices + n_devices)).with_verify(verify != 0);
+    AllPairParallelIterator par = it.into_par_iter();
+    const std::vector<AlignmentResult> res = par.collect();  // (in list order, on any number of slots)
+    keep_verify(par.last_verify_stats(), par.verify_failures());
+    std::string all;
+    for (const AlignmentResult& r : res) {
+      all += alignment_to_paf(r, seqs);
+      all.push_back('\n');
+    }
+    *out = (char*)malloc(all.size() + 1);
+    if (!*out) throw std::bad_alloc();
+    memcpy(*out, all.c_str(), all.size() + 1);
+    *out_len = all.size();
+    return 0;
+  } catch (const std::exception& e) { set_err(err, cap, e.what()); return -1; }
+}
+
+// The PAF line of one range's engine record (range_alignment_result + alignment_to_paf; needs no device): range = the seven
+// fields of awh_align_ranges_paf, rec = one awv_result whose cigar_off / cigar_len point into `arena`
+int awh_range_record_paf(const char* qid, size_t qlen, const char* tid, size_t tlen, const int64_t range[7], const awv_result* rec,
+                         const uint8_t* arena, char* out, size_t cap) {
+  std::vector<Sequence> seqs(2);
+  seqs[0].id = qid; seqs[0].seq.assign(qlen, 'A');
+  seqs[1].id = tid; seqs[1].seq.assign(tlen, 'A');
+  const AlignmentRange g{(size_t)range[0], (size_t)range[1], range[2] != 0, (size_t)range[3], (size_t)range[4], (size_t)range[5], (size_t)range[6]};
+  const std::string s = alignment_to_paf(range_alignment_result(g, *rec, arena, true), seqs);
+  if (s.size() + 1 > cap) return -1;
+  memcpy(out, s.c_str(), s.size() + 1);
+  return (int)s.size();
+}
+
+// parse_paf_ranges: out = malloc'ed int64 records of nine per non-empty line (line, class index into "", bad_line, unknown_name,
+// length_mismatch; then the range's seven fields, zeros for a bad line)
+int awh_parse_paf_ranges(int n, const char* const* ids, const int64_t* lens, const char* paf, size_t paf_len, int64_t** out, size_t* nlines) {
+  std::vector<Sequence> seqs((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    seqs[(size_t)i].id = ids[i];
+    seqs[(size_t)i].seq.assign((size_t)lens[i], 'A');
+  }
+  const PafRanges pr = parse_paf_ranges(seqs, std::string(paf, paf_len));
+  static const char* const classes[] = {"", "bad_line", "unknown_name", "length_mismatch"};
+  *out = (int64_t*)malloc(sizeof(int64_t) * 9 * (pr.lines.size() + 1));
+  if (!*out) return -1;
+  for (size_t i = 0; i < pr.lines.size(); ++i) {
+    int64_t* o = *out + 9 * i;
+    memset(o, 0, 9 * sizeof(int64_t));
+    o[0] = (int64_t)pr.lines[i].line;
+    for (int c = 0; c < 4; ++c)
+      if (pr.lines[i].cls == classes[c]) o[1] = c;
+    if (pr.lines[i].cls.empty()) {
+      const AlignmentRange& g = pr.ranges[pr.lines[i].index];
+      o[2] = (int64_t)g.query_idx; o[3] = (int64_t)g.target_idx; o[4] = g.is_reverse ? 1 : 0;
+      o[5] = (int64_t)g.query_start; o[6] = (int64_t)g.query_end; o[7] = (int64_t)g.target_start; o[8] = (int64_t)g.target_end;
+    }
+  }
+  *nlines = pr.lines.size();
+  return 0;
 }
 
 void awh_free(void* p) { free(p); }

@@ -7,7 +7,8 @@
 // --wfa-orientation-full (WFA orientation by two full alignments per pair, the reference's method, instead of bounded scores),
 // --score-only (penalties instead of PAF: WFA2's ComputeScore scope) with an optional --max-penalty N bound,
 // --verify (check every alignment on the device before it is written; exit status 4 when one fails),
-// --check-paf FILE [--check-optimal] (check an existing PAF against the FASTA on the device; nothing is aligned).
+// --check-paf FILE [--check-optimal] [--partial] (check an existing PAF against the FASTA on the device; nothing is aligned),
+// --align-paf FILE (align the interval pairs columns 1-9 of each line of FILE name, globally: mappings in, PAF with cg:Z: out).
 // -t sets the host threads used for PAF formatting / sketching (alignment itself runs on the GPU).
 #include <zlib.h>
 
@@ -42,6 +43,9 @@ struct Args {
   bool verify = false;      // --verify: awv_align_pairs_verified; `verified N pairs, F failed, K ms` on the summary line
   std::string check_paf;    // --check-paf FILE: check that PAF against the input instead of aligning
   bool have_check_paf = false, check_optimal = false;
+  bool partial = false;     // --partial (with --check-paf): lines over a proper interval are checked as that interval pair
+  std::string align_paf;    // --align-paf FILE: align the interval pairs that PAF names instead of a planned pair list
+  bool have_align_paf = false, have_sparsification = false, have_shard = false;
 };
 
 [[noreturn]] void die(const std::string& m, int code = 2) {
@@ -181,7 +185,7 @@ int main(int argc, char** argv) {
     else if (k == "-s" || k == "--scores") { a.scores = val(); a.have_scores = true; }
     else if (k == "-x" || k == "--preset") { a.preset = val(); a.have_preset = true; }
     else if (k == "-t" || k == "--threads") a.threads = std::max(1, atoi(val().c_str()));
-    else if (k == "-p" || k == "--sparsification") a.sparsification = val();
+    else if (k == "-p" || k == "--sparsification") { a.sparsification = val(); a.have_sparsification = true; }
     else if (k == "--no-progress") a.no_progress = true;
     else if (k == "--mash-matrix") a.mash_matrix = true;
     else if (k == "--wfa-orientation") a.wfa_orientation = true;
@@ -195,6 +199,8 @@ int main(int argc, char** argv) {
     else if (k == "--verify") a.verify = true;
     else if (k == "--check-paf") { a.check_paf = val(); a.have_check_paf = true; }
     else if (k == "--check-optimal") a.check_optimal = true;
+    else if (k == "--partial") a.partial = true;
+    else if (k == "--align-paf") { a.align_paf = val(); a.have_align_paf = true; }
     else if (k == "--plan-device") {
       const std::string v = val();
       if (v.empty() || v.size() > 6 || v.find_first_not_of("0123456789") != std::string::npos) die("--plan-device expects a device ordinal N >= 0");
@@ -210,6 +216,7 @@ int main(int argc, char** argv) {
     else if (k == "--shard") {
       const std::string v = val();
       char* end = nullptr;
+      a.have_shard = true;
       a.shard_rank = strtol(v.c_str(), &end, 10);
       if (!end || *end != '/') die("--shard expects R/N, e.g. 3/8");
       const char* w = end + 1;
@@ -220,12 +227,19 @@ int main(int argc, char** argv) {
       std::cout << "usage: allwave_hip -i in.fa [-o out.paf] [-s m,x,o,e[,o2,e2] | -x ANI] [-p none|auto|random:f|giant:p|tree:n:f:r[:k]]\n"
                    "                   [-t threads] [--wfa-orientation|--wfa-orientation-full|--forward-only] [-k prefixes | -e prefixes] [--mash-matrix]\n"
                    "                   [--device N | --devices LIST] [--shard R/N] [--score-only [--max-penalty N]] [--plan-device N] [--verify]\n"
-                   "       allwave_hip -i in.fa --check-paf FILE [-s scores | -x ANI] [--check-optimal] [--device N]\n"
+                   "       allwave_hip -i in.fa --check-paf FILE [-s scores | -x ANI] [--check-optimal] [--partial] [--device N]\n"
+                   "       allwave_hip -i in.fa --align-paf FILE [-s scores | -x ANI] [-o out.paf] [--verify] [--score-only] [--device N | --devices LIST]\n"
                    "  --verify         check every alignment on the device before it is written (columns, counts, penalty); the summary\n"
                    "                   line gains `verified N pairs, F failed, K ms`, failures go to stderr, exit status 4 if any\n"
                    "  --check-paf FILE align nothing: check every line of FILE (12 columns + cg:Z:) against in.fa on the device; one line\n"
                    "                   `line qname tname strand class column penalty [optimum]` per failing PAF line, exit status 0 or 4\n"
                    "  --check-optimal  with --check-paf: also compare each op string's penalty with the optimal one (score-only alignment)\n"
+                   "  --partial        with --check-paf: a line whose coordinates are a proper interval of both sequences is checked as the\n"
+                   "                   global alignment of that interval pair instead of being reported `not_end_to_end`\n"
+                   "  --align-paf FILE align the interval pairs FILE names (columns 1-9 of each line: names, lengths, intervals, strand; the\n"
+                   "                   query interval on its forward strand) globally; one PAF line per input line, in input order; a bad\n"
+                   "                   line is reported on stderr as `line class` and gives no output line (--score-only: the nine columns\n"
+                   "                   and the penalty)\n"
                    "  --devices LIST   align on several devices in this process: ordinals and ranges, e.g. 0,1,2 / 0-7 / all;\n"
                    "                   an ordinal may repeat (0,0: two engines on device 0); -t is shared out among them\n"
                    "  --score-only     no PAF: one tab-separated line per pair, `qname qlen tname tlen strand penalty`, in pair-list\n"
@@ -242,6 +256,11 @@ int main(int argc, char** argv) {
   if (a.verify && a.mash_matrix) die("the argument '--verify' cannot be used with '--mash-matrix'");
   if (a.have_check_paf && (a.verify || a.score_only || a.mash_matrix || a.have_output || a.have_devices))
     die("the argument '--check-paf' cannot be used with '--verify', '--score-only', '--mash-matrix', '--output' or '--devices'");
+  if (a.partial && !a.have_check_paf) die("the argument '--partial' requires '--check-paf'");
+  if (a.have_align_paf && (a.have_sparsification || a.wfa_orientation || a.forward_only || a.have_shard || a.mash_matrix || a.have_check_paf ||
+                           a.plan_device >= 0))
+    die("the argument '--align-paf' cannot be used with '--sparsification', '--wfa-orientation', '--wfa-orientation-full', '--forward-only', "
+        "'--shard', '--mash-matrix', '--plan-device' or '--check-paf'");
   if (a.input.empty()) die("the following required arguments were not provided: --input <INPUT>");
   if (a.have_scores && a.have_preset) die("the argument '--scores' cannot be used with '--preset'");
   if (a.have_keep && a.have_exclude) die("the argument '--keep-prefixes' cannot be used with '--exclude-prefixes'");
@@ -308,7 +327,7 @@ int main(int argc, char** argv) {
       std::stringstream ss;
       ss << fin.rdbuf();
       set_engine_flags(AWV_F_NO_ARENA_PROBE);
-      const PafCheckReport r = check_paf(sequences, ss.str(), params, a.check_optimal, a.device);
+      const PafCheckReport r = check_paf(sequences, ss.str(), params, a.check_optimal, a.device, a.partial);
       std::cout << format_paf_check(r);
       std::cout.flush();
       char buf[200];
@@ -323,7 +342,24 @@ int main(int argc, char** argv) {
 
   int verify_status = 0;
   try {
-    AllPairIterator it = AllPairIterator::with_options(sequences, params, true, !a.wfa_orientation, strategy, a.plan_device);
+    // --align-paf: the list is the file's interval pairs (bad lines reported here, counted below, and left out)
+    std::vector<AlignmentRange> ranges;
+    size_t bad_lines = 0;
+    if (a.have_align_paf) {
+      std::ifstream fin(a.align_paf, std::ios::binary);
+      if (!fin) die("cannot open " + a.align_paf, 1);
+      std::stringstream ss;
+      ss << fin.rdbuf();
+      PafRanges pr = parse_paf_ranges(sequences, ss.str());
+      for (const PafRangeLine& l : pr.lines)
+        if (!l.cls.empty()) {
+          std::cerr << l.line << ' ' << l.cls << "\n";
+          ++bad_lines;
+        }
+      ranges = std::move(pr.ranges);
+    }
+    AllPairIterator it = a.have_align_paf ? AllPairIterator::for_ranges(sequences, ranges, params)
+                                          : AllPairIterator::with_options(sequences, params, true, !a.wfa_orientation, strategy, a.plan_device);
     it.with_verify(a.verify);
     if (a.forward_only) it.with_orientation(Orientation::ForwardOnly);
     it.with_full_wfa_orientation(a.wfa_orientation_full);
@@ -349,8 +385,15 @@ int main(int argc, char** argv) {
         if (p.status == AWV_ST_ABOVE_BOUND) continue;
         const Sequence& q = sequences[p.query_idx];
         const Sequence& t = sequences[p.target_idx];
+        const std::string pen_s = p.status == AWV_ST_COMPLETED ? std::to_string(p.penalty) : std::string("*");
+        if (a.have_align_paf) {  // the mapping's nine columns, then the penalty
+          const AlignmentRange& g = ranges[done - 1];
+          buf += q.id + '\t' + std::to_string(q.seq.size()) + '\t' + std::to_string(g.query_start) + '\t' + std::to_string(g.query_end) + '\t' +
+                 (g.is_reverse ? '-' : '+') + '\t' + t.id + '\t' + std::to_string(t.seq.size()) + '\t' + std::to_string(g.target_start) + '\t' +
+                 std::to_string(g.target_end) + '\t' + pen_s + '\n';
+        } else
         buf += q.id + '\t' + std::to_string(q.seq.size()) + '\t' + t.id + '\t' + std::to_string(t.seq.size()) + '\t' +
-               (p.is_reverse ? '-' : '+') + '\t' + (p.status == AWV_ST_COMPLETED ? std::to_string(p.penalty) : std::string("*")) + '\n';
+               (p.is_reverse ? '-' : '+') + '\t' + pen_s + '\n';
         if (buf.size() >= (1u << 20)) {
           out.write(buf.data(), (std::streamsize)buf.size());
           if (!out) throw std::runtime_error("write error on the score output");
@@ -380,6 +423,7 @@ int main(int argc, char** argv) {
       const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       char buf[320];
       int w = snprintf(buf, sizeof(buf), "[%.1fs] %zu/%zu (100.0%%) %.1f alignments/sec", secs, done, total, done / std::max(secs, 1e-9));
+      if (a.have_align_paf && w > 0 && (size_t)w < sizeof(buf)) w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", %zu bad lines", bad_lines);
       if (a.verify) {
         const awv_verify_stats vs = it.last_verify_stats();
         snprintf(buf + w, sizeof(buf) - (size_t)w, ", verified %llu pairs, %zu failed, %.2f ms", (unsigned long long)vs.pairs,

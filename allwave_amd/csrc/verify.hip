@@ -38,6 +38,7 @@ struct KParams {
   const uint64_t* seq_off;
   const int32_t* seq_len;
   const awv_pair* pairs;
+  const Span* spans;          // nullable (range calls): pair i's pattern / text are these intervals of its sequences
   const awv_result* results;  // cigar_off relative to `arena`
   const int32_t* order;       // dispatch slot -> pair
   const uint8_t* arena;       // 16-byte aligned, readable up to the 16-byte boundary behind every op string
@@ -129,9 +130,16 @@ __global__ __launch_bounds__(64) void awv_verify_kernel(KParams kp) {
       continue;
     }
     const awv_pair pr = kp.pairs[pair];
-    const int plen = kp.seq_len[pr.q_idx], tlen = kp.seq_len[pr.t_idx];
+    int plen = kp.seq_len[pr.q_idx], tlen = kp.seq_len[pr.t_idx];
     const uint8_t* pattern = (pr.q_revcomp ? kp.rc : kp.fwd) + kp.seq_off[pr.q_idx];
     const uint8_t* text = kp.fwd + kp.seq_off[pr.t_idx];
+    if (kp.spans) {  // (validated on the host: inside the sequences)
+      const Span sp = kp.spans[pair];
+      pattern += sp.pb;
+      text += sp.tb;
+      plen = sp.pe - sp.pb;
+      tlen = sp.te - sp.tb;
+    }
     // every passing column consumes a base: an op string longer than plen + tlen fails within its first plen + tlen + 1 columns
     const long long n_claimed = (long long)claimed.cigar_len;
     const int n = (int)min(n_claimed, (long long)plen + tlen + 1);
@@ -272,6 +280,7 @@ struct Buf {
 
 struct State {
   Buf<awv_pair> d_pairs;
+  Buf<Span> d_spans;
   Buf<awv_result> d_results;
   Buf<int32_t> d_order;
   Buf<awv_verify_result> d_out;
@@ -282,6 +291,7 @@ struct State {
   awv_verify_stats stats{};
   void release() {
     d_pairs.release();
+    d_spans.release();
     d_results.release();
     d_order.release();
     d_out.release();
@@ -352,7 +362,7 @@ int open_state(awv_engine* e, awp::EngineView& v, State*& st) {
 // One launch over n pairs whose op bytes are on the device already.  Every index and every op string's place in the arena
 // is checked here, on the host: the kernel reads what the records say.
 int launch(const awp::EngineView& v, State* st, const awv_penalties& pen, const awv_pair* pairs, int64_t n, const awv_result* results,
-           const uint8_t* d_arena, uint64_t arena_bytes, awv_verify_result* vout) {
+           const uint8_t* d_arena, uint64_t arena_bytes, awv_verify_result* vout, const Span* spans = nullptr) {
   if (n == 0) return AWV_OK;
   if (n > INT32_MAX) return awv_internal_fail(AWV_ERR_ARG, "verify: more than 2^31 - 1 pairs in one launch");
   for (int64_t i = 0; i < n; ++i) {
@@ -372,6 +382,10 @@ int launch(const awp::EngineView& v, State* st, const awv_penalties& pen, const 
   VF_TRY(st->d_out.reserve((size_t)n));
   VF_TRY(st->d_counters.reserve(4));
   VF_TRY(hipMemcpyAsync(st->d_pairs.p, pairs, (size_t)n * sizeof(awv_pair), hipMemcpyHostToDevice, v.stream));
+  if (spans) {
+    VF_TRY(st->d_spans.reserve((size_t)n));
+    VF_TRY(hipMemcpyAsync(st->d_spans.p, spans, (size_t)n * sizeof(Span), hipMemcpyHostToDevice, v.stream));
+  }
   VF_TRY(hipMemcpyAsync(st->d_results.p, results, (size_t)n * sizeof(awv_result), hipMemcpyHostToDevice, v.stream));
   VF_TRY(hipMemcpyAsync(st->d_order.p, order.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
   VF_TRY(hipMemsetAsync(st->d_counters.p, 0, 4 * sizeof(unsigned long long), v.stream));
@@ -381,6 +395,7 @@ int launch(const awp::EngineView& v, State* st, const awv_penalties& pen, const 
   kp.seq_off = v.off;
   kp.seq_len = v.len;
   kp.pairs = st->d_pairs.p;
+  kp.spans = spans ? st->d_spans.p : nullptr;
   kp.results = st->d_results.p;
   kp.order = st->d_order.p;
   kp.arena = d_arena;
@@ -406,14 +421,26 @@ int launch(const awp::EngineView& v, State* st, const awv_penalties& pen, const 
   return AWV_OK;
 }
 
+// ranges (nullable; awv_verify_ranges): the call is on ranges[0..npairs) -- `pairs` is not read
 int verify_cigars_core(awv_engine* e, const awv_penalties* pen_in, const awv_pair* pairs, int64_t npairs, const awv_result* results,
-                       const uint8_t* cigar_arena, uint64_t arena_bytes, uint64_t max_arena, awv_verify_result* vout) {
+                       const uint8_t* cigar_arena, uint64_t arena_bytes, uint64_t max_arena, awv_verify_result* vout,
+                       const awv_range_pair* ranges = nullptr) {
   awv_penalties pen;
   if (int rc = check_penalties(pen_in, pen)) return rc;
   awp::EngineView v;
   State* st = nullptr;
   if (int rc = open_state(e, v, st)) return rc;
   st->stats = awv_verify_stats{};
+  std::vector<awv_pair> rpairs;
+  std::vector<Span> spans;
+  if (ranges) {
+    rpairs.resize((size_t)npairs);
+    spans.resize((size_t)npairs);
+    for (int64_t i = 0; i < npairs; ++i)
+      if (!awvr::split_range(v.len_host, v.n, ranges[i], rpairs[(size_t)i], spans[(size_t)i]))
+        return awv_internal_fail(AWV_ERR_ARG, "verify_ranges: range " + std::to_string(i) + " names a sequence index or an interval out of range");
+    pairs = rpairs.data();
+  }
   // before anything goes up: every completed record's op bytes lie inside the caller's arena
   for (int64_t i = 0; i < npairs; ++i)
     if (results[i].status == AWV_ST_COMPLETED &&
@@ -443,7 +470,7 @@ int verify_cigars_core(awv_engine* e, const awv_penalties* pen_in, const awv_pai
     }
     VF_TRY(st->d_arena.reserve((size_t)bytes + 64));
     if (bytes) VF_TRY(hipMemcpyAsync(st->d_arena.p, stage.data(), (size_t)bytes, hipMemcpyHostToDevice, v.stream));
-    if (int rc = launch(v, st, pen, pairs + first, n, recs.data(), st->d_arena.p, bytes, vout + first)) return rc;
+    if (int rc = launch(v, st, pen, pairs + first, n, recs.data(), st->d_arena.p, bytes, vout + first, ranges ? spans.data() + first : nullptr)) return rc;
     first += n;
   }
   return AWV_OK;
@@ -459,13 +486,13 @@ int null_engine() {
 }  // namespace
 
 int verify_batch(awv_engine* e, const awv_penalties* pen_in, const awv_pair* pairs, int64_t n, const awv_result* results,
-                 const uint8_t* d_arena, uint64_t arena_bytes, awv_verify_result* vout) {
+                 const uint8_t* d_arena, uint64_t arena_bytes, awv_verify_result* vout, const Span* spans) {
   awv_penalties pen;
   if (int rc = check_penalties(pen_in, pen)) return rc;
   awp::EngineView v;
   State* st = nullptr;
   if (int rc = open_state(e, v, st)) return rc;
-  return launch(v, st, pen, pairs, n, results, d_arena, arena_bytes, vout);
+  return launch(v, st, pen, pairs, n, results, d_arena, arena_bytes, vout, spans);
 }
 
 }  // namespace awvf
@@ -478,6 +505,14 @@ int awv_verify_cigars(awv_engine* e, const awv_penalties* pen, const awv_pair* p
   if (npairs < 0 || (npairs > 0 && (!pairs || !results || !vout))) return awv_internal_fail(AWV_ERR_ARG, "verify_cigars: null argument");
   if (arena_bytes > 0 && !cigar_arena) return awv_internal_fail(AWV_ERR_ARG, "verify_cigars: null arena");
   VF_GUARDED(return awvf::verify_cigars_core(e, pen, pairs, npairs, results, cigar_arena, arena_bytes, awv_internal_max_arena(e), vout);)
+}
+
+int awv_verify_ranges(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const awv_result* results,
+                      const uint8_t* cigar_arena, uint64_t arena_bytes, awv_verify_result* vout) {
+  if (!e) return awvf::null_engine();
+  if (n < 0 || (n > 0 && (!ranges || !results || !vout))) return awv_internal_fail(AWV_ERR_ARG, "verify_ranges: null argument");
+  if (arena_bytes > 0 && !cigar_arena) return awv_internal_fail(AWV_ERR_ARG, "verify_ranges: null arena");
+  VF_GUARDED(return awvf::verify_cigars_core(e, pen, nullptr, n, results, cigar_arena, arena_bytes, awv_internal_max_arena(e), vout, ranges);)
 }
 
 int awv_verify_one_host(const awv_penalties* pen, const uint8_t* pattern, int32_t plen, const uint8_t* text, int32_t tlen,

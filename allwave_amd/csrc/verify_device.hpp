@@ -13,6 +13,7 @@
 #include <cstdint>
 
 #include "allwave_hip.h"
+#include "range_span.hpp"
 
 struct awv_engine;
 
@@ -98,15 +99,17 @@ __host__ __device__ inline awv_verify_result verify_one(const awv_penalties& pen
   return make_result(whole_code(claimed, n, plen, tlen, q, t, nx, penalty), -1, penalty);
 }
 
+using awvr::Span;  // (range_span.hpp: the rectangle of a range call's pair)
+
 struct State;                    // verify.hip: the verify launches' device buffers, events and the last call's stats
 void state_release(State* s);    // frees them and the object itself (nullptr: nothing)
 void stats_reset(State* s);      // (nullptr: nothing)
 
 // engine.hip's hook: checks one batch of awv_align_pairs_verified on the engine's stream.  `pairs`, `results`, `vout`: the
 // batch's n entries (host); `d_arena`: the batch's CIGAR arena on the device, `arena_bytes` of it.  Adds to the stats the
-// caller reset at the start of its call (stats_reset).
+// caller reset at the start of its call (stats_reset).  `spans` (nullable): the batch's rectangles of a range call.
 int verify_batch(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t n, const awv_result* results,
-                 const uint8_t* d_arena, uint64_t arena_bytes, awv_verify_result* vout);
+                 const uint8_t* d_arena, uint64_t arena_bytes, awv_verify_result* vout, const Span* spans = nullptr);
 
 }  // namespace awvf
 

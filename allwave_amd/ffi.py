@@ -60,7 +60,8 @@ EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine
            "awv_engine_set_sequences", "awv_align_pairs", "awv_align_one", "awv_score_pairs", "awv_engine_stats",
            "awv_score_pairs_bounded", "awv_orient_pairs", "awv_orient_decide", "awv_orient_settling_bound",
            "awv_sketch", "awv_sketch_copy", "awv_sketch_pair_counts", "awv_sketch_rows", "awv_sketch_knn", "awv_keep_pairs",
-           "awv_align_pairs_verified", "awv_verify_cigars", "awv_verify_one_host", "awv_engine_verify_stats")
+           "awv_align_pairs_verified", "awv_verify_cigars", "awv_verify_one_host", "awv_engine_verify_stats",
+           "awv_align_ranges", "awv_align_ranges_verified", "awv_score_ranges", "awv_verify_ranges")
 
 
 class EngineConfig(C.Structure):
@@ -101,6 +102,9 @@ class VerifyStats(C.Structure):
 
 
 PAIR_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4")])
+#: awv_range_pair: the query interval on the query's forward strand (PAF convention), also with q_revcomp
+RANGE_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4"), ("q_beg", "<i4"), ("q_end", "<i4"),
+                        ("t_beg", "<i4"), ("t_end", "<i4")])
 RESULT_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4"), ("score", "<i4"), ("cigar_len", "<u4"),
                          ("cigar_off", "<u8"), ("num_matches", "<i4"), ("num_mismatches", "<i4"),
                          ("num_ins", "<i4"), ("num_del", "<i4"), ("q_end", "<i4"), ("t_end", "<i4")])
@@ -149,6 +153,10 @@ def load():
         L.awv_verify_one_host.argtypes = [C.POINTER(Penalties), C.c_char_p, C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, C.c_int64,
                                           C.c_void_p, C.c_void_p]
         L.awv_engine_verify_stats.argtypes = [C.c_void_p, C.POINTER(VerifyStats)]
+        L.awv_align_ranges.argtypes = L.awv_align_pairs.argtypes
+        L.awv_align_ranges_verified.argtypes = L.awv_align_pairs_verified.argtypes
+        L.awv_score_ranges.argtypes = L.awv_score_pairs_bounded.argtypes
+        L.awv_verify_ranges.argtypes = L.awv_verify_cigars.argtypes
         _LIB = L
     return _LIB
 
@@ -210,12 +218,52 @@ class Engine:
             pairs = p
         return np.ascontiguousarray(pairs)
 
+    @staticmethod
+    def _range_array(ranges):
+        if not (isinstance(ranges, np.ndarray) and ranges.dtype == RANGE_DTYPE):
+            a = np.asarray(ranges, dtype=np.int32)
+            a = a.reshape(len(a), 7) if len(a) else np.zeros((0, 7), dtype=np.int32)
+            r = np.zeros(len(a), dtype=RANGE_DTYPE)
+            for k, name in enumerate(RANGE_DTYPE.names):
+                r[name] = a[:, k]
+            ranges = r
+        return np.ascontiguousarray(ranges)
+
+    def align_ranges(self, scores, ranges, want_cigars=True, verify=False):
+        """align_pairs on interval pairs (awv_align_ranges / awv_align_ranges_verified).  ranges: int array [n,7] (q_idx, t_idx,
+        q_revcomp, q_beg, q_end, t_beg, t_end) or a RANGE_DTYPE array; the query interval is on the query's forward strand.
+        The records' q_end / t_end are consumed lengths, relative to the range."""
+        return self._align("awv_align_ranges", scores, self._range_array(ranges), want_cigars, verify)
+
+    def score_ranges(self, scores, ranges, max_penalty=None):
+        """score_pairs on interval pairs (awv_score_ranges).  max_penalty: None, or one bound per range (negative: none)."""
+        pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+        ranges = self._range_array(ranges)
+        bounds = None
+        if max_penalty is not None:
+            bounds = np.ascontiguousarray(np.broadcast_to(np.asarray(max_penalty, dtype=np.int32), (len(ranges),)))
+            bounds = bounds if len(bounds) else np.zeros(1, dtype=np.int32)
+        out = np.zeros(max(len(ranges), 1), dtype=SCORE_DTYPE)[:len(ranges)]
+        rc = load().awv_score_ranges(self._h, C.byref(pen), ranges.ctypes.data, len(ranges), None if bounds is None else bounds.ctypes.data,
+                                     out.ctypes.data)
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_score_ranges")
+        return out
+
+    def verify_ranges(self, scores, ranges, results, arena):
+        """verify_cigars on interval pairs (awv_verify_ranges)."""
+        return self._verify("awv_verify_ranges", scores, self._range_array(ranges), results, arena)
+
     def align_pairs(self, scores, pairs, want_cigars=True, verify=False):
         """pairs: int array [n,2] (q,t) or [n,3] (q,t,revcomp), or a PAIR_DTYPE array.
         Returns (results structured array, list of op-byte strings or None); verify=True: every finished pair is checked on
         the device (awv_align_pairs_verified) and a VERIFY_DTYPE array comes back as a third value."""
+        return self._align("awv_align_pairs", scores, self._pair_array(pairs), want_cigars, verify)
+
+    def _align(self, fn, scores, pairs, want_cigars, verify):
+        """awv_align_pairs / awv_align_ranges (`fn`; verify: its _verified variant) on a contiguous PAIR_DTYPE / RANGE_DTYPE array."""
         pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
-        pairs = self._pair_array(pairs)
+        fn_v = fn + "_verified"
         res = np.zeros(len(pairs), dtype=RESULT_DTYPE)
         cigars = [None] * len(pairs) if want_cigars else None
 
@@ -231,21 +279,23 @@ class Engine:
         cb = SINK_FN(_sink) if want_cigars else SINK_FN()
         if verify:
             vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)]  # (vout is required, also for an empty list)
-            rc = load().awv_align_pairs_verified(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), res.ctypes.data,
-                                                 vres.ctypes.data, cb, None)
+            rc = getattr(load(), fn_v)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), res.ctypes.data, vres.ctypes.data, cb, None)
             if rc != AWV_OK:
-                raise EngineError(rc, "awv_align_pairs_verified")
+                raise EngineError(rc, fn_v)
             return res, cigars, vres
-        rc = load().awv_align_pairs(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), res.ctypes.data, cb, None)
+        rc = getattr(load(), fn)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), res.ctypes.data, cb, None)
         if rc != AWV_OK:
-            raise EngineError(rc, "awv_align_pairs")
+            raise EngineError(rc, fn)
         return res, cigars
 
     def verify_cigars(self, scores, pairs, results, arena):
         """awv_verify_cigars: checks caller-supplied records (a RESULT_DTYPE array whose cigar_off / cigar_len point into
         `arena`, bytes or a uint8 array) against the resident sequences on the device.  Returns a VERIFY_DTYPE array."""
+        return self._verify("awv_verify_cigars", scores, self._pair_array(pairs), results, arena)
+
+    def _verify(self, fn, scores, pairs, results, arena):
+        """awv_verify_cigars / awv_verify_ranges (`fn`) on a contiguous PAIR_DTYPE / RANGE_DTYPE array."""
         pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
-        pairs = self._pair_array(pairs)
         results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
         if results.shape != (len(pairs),):
             raise ValueError("results: need one record per pair")
@@ -254,10 +304,10 @@ class Engine:
         if nbytes == 0:
             arena = np.zeros(1, dtype=np.uint8)
         vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)]
-        rc = load().awv_verify_cigars(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), results.ctypes.data, arena.ctypes.data,
-                                      nbytes, vres.ctypes.data)
+        rc = getattr(load(), fn)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), results.ctypes.data, arena.ctypes.data, nbytes,
+                                 vres.ctypes.data)
         if rc != AWV_OK:
-            raise EngineError(rc, "awv_verify_cigars")
+            raise EngineError(rc, fn)
         return vres
 
     def verify_stats(self):

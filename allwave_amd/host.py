@@ -166,9 +166,10 @@ def cigar_string_to_bytes(cg):
     return buf.raw[:n]
 
 
-def check_paf(ids, seqs, paf_text, scores, optimal=False, device=0):
+def check_paf(ids, seqs, paf_text, scores, optimal=False, device=0, partial=False):
     """Checks every line of a PAF (12 columns + cg:Z:) against the sequences on `device`; nothing is aligned (check_paf in
-    allwave.hpp).  Returns dict(lines, checked, skipped, kernel_ms, failures): one dict(line, qname, tname, strand, class, column,
+    allwave.hpp).  partial: a line over a proper interval of both sequences is checked as the global alignment of that interval
+    pair instead of being reported not_end_to_end.  Returns dict(lines, checked, skipped, kernel_ms, failures): one dict(line, qname, tname, strand, class, column,
     penalty, optimum) per failing line, in line order; `class` as listed there; optimum is None unless `optimal` found one."""
     cids, data, offs = _seq_args(ids, seqs)
     txt = paf_text.encode() if isinstance(paf_text, str) else bytes(paf_text)
@@ -178,7 +179,7 @@ def check_paf(ids, seqs, paf_text, scores, optimal=False, device=0):
     st = ffi.VerifyStats()
     e = _err()
     rc = load().awh_check_paf(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), scores.encode(), txt,
-                              C.c_size_t(len(txt)), int(bool(optimal)), int(device), C.byref(out), C.byref(n), counts, C.byref(st), e, _CAP)
+                              C.c_size_t(len(txt)), int(bool(optimal)), int(bool(partial)), int(device), C.byref(out), C.byref(n), counts, C.byref(st), e, _CAP)
     if rc != 0:
         raise HostError(e.value.decode())
     lines = C.string_at(out, n.value).decode().splitlines()
@@ -189,6 +190,64 @@ def check_paf(ids, seqs, paf_text, scores, optimal=False, device=0):
         fails.append({"line": int(f[0]), "qname": f[1], "tname": f[2], "strand": f[3], "class": f[4], "column": int(f[5]),
                       "penalty": int(f[6]), "optimum": int(f[7]) if len(f) > 7 else None})
     return dict(lines=int(counts[0]), checked=int(counts[1]), skipped=int(counts[2]), kernel_ms=float(st.kernel_ms), failures=fails)
+
+
+def align_ranges(ids, seqs, ranges, scores, devices=None, device=0, verify=False):
+    """allwave::align_ranges + alignment_to_paf: the interval pairs `ranges` -- rows (query_idx, target_idx, is_reverse,
+    query_start, query_end, target_start, target_end), the query interval on its forward strand -- aligned globally on the
+    engines `devices` names (default: [device]).  Returns the PAF lines in list order: columns 3-4 and 8-9 are the interval,
+    2 and 7 the full lengths; a failed range prints its starts twice and an empty cg.  verify=True: every range is checked on
+    the device; last_verify() then holds the counters and the failures (index = list index)."""
+    cids, data, offs = _seq_args(ids, seqs)
+    r = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1, 7))
+    devs, nd = _device_args([device] if devices is None else devices)
+    out = C.c_void_p()
+    n = C.c_size_t(0)
+    e = _err()
+    rbuf = r if len(r) else np.zeros((1, 7), dtype=np.int64)
+    rc = load().awh_align_ranges_paf(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), scores.encode(),
+                                     rbuf.ctypes.data_as(C.c_void_p), C.c_size_t(len(r)), devs, nd, int(bool(verify)), C.byref(out),
+                                     C.byref(n), e, _CAP)
+    if rc != 0:
+        raise HostError(e.value.decode())
+    lines = C.string_at(out, n.value).decode().splitlines()
+    load().awh_free(out)
+    return lines
+
+
+def range_record_paf(qid, qlen, tid, tlen, rng, record, ops=b""):
+    """The PAF line of one range's engine record (range_alignment_result + alignment_to_paf; needs no device).  rng: (0, 1,
+    is_reverse, query_start, query_end, target_start, target_end); record: one ffi.RESULT_DTYPE record whose op bytes are `ops`."""
+    rec = np.zeros(1, dtype=ffi.RESULT_DTYPE)
+    rec[0] = record
+    rec["cigar_off"], rec["cigar_len"] = 0, len(ops)
+    r = np.ascontiguousarray(rng, dtype=np.int64)
+    arena = bytes(ops) + b"\0"
+    buf = C.create_string_buffer(4 * len(ops) + 512)
+    n = load().awh_range_record_paf(qid.encode(), C.c_size_t(qlen), tid.encode(), C.c_size_t(tlen), r.ctypes.data_as(C.c_void_p),
+                                    rec.ctypes.data_as(C.c_void_p), arena, buf, C.c_size_t(len(buf)))
+    if n < 0:
+        raise HostError("buffer")
+    return buf.value.decode()
+
+
+PAF_RANGE_CLASSES = ("", "bad_line", "unknown_name", "length_mismatch")
+
+
+def parse_paf_ranges(ids, lengths, paf_text):
+    """parse_paf_ranges (what --align-paf reads of a mapping file: columns 1-9): one (line, class, range) per non-empty line;
+    class "" and the range's seven fields for a good line, else one of PAF_RANGE_CLASSES and None.  Needs no device."""
+    txt = paf_text.encode() if isinstance(paf_text, str) else bytes(paf_text)
+    cids = (C.c_char_p * len(ids))(*[i.encode() for i in ids])
+    lens = np.ascontiguousarray(lengths, dtype=np.int64)
+    out = C.c_void_p()
+    n = C.c_size_t(0)
+    if load().awh_parse_paf_ranges(len(ids), cids, lens.ctypes.data_as(C.c_void_p), txt, C.c_size_t(len(txt)), C.byref(out), C.byref(n)) != 0:
+        raise HostError("out of memory")
+    k = n.value
+    raw = np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_int64)), shape=(max(k, 1) * 9,))[:9 * k].reshape(k, 9).copy()
+    load().awh_free(out)
+    return [(int(r[0]), PAF_RANGE_CLASSES[int(r[1])], tuple(int(v) for v in r[2:]) if r[1] == 0 else None) for r in raw]
 
 
 def _orient_code(orientation, orientation_full):

@@ -313,6 +313,37 @@ int awv_verify_one_host(const awv_penalties* pen, const uint8_t* pattern, int32_
 /* The last verifying call (awv_align_pairs_verified / awv_verify_cigars) of this engine. */
 int awv_engine_verify_stats(const awv_engine* e, awv_verify_stats* out);
 
+/* ---- ranges: sub-intervals of resident sequences ---------------------------------------------------------------------------
+ * An awv_pair aligns two whole sequences; an awv_range_pair aligns query[q_beg, q_end) against target[t_beg, t_end), globally
+ * (end to end over the two intervals), without the caller cutting and uploading substrings.  Coordinates follow PAF: the
+ * query interval is given on the query's FORWARD strand whatever q_revcomp says; with q_revcomp the pattern is
+ * reverse_complement(query[q_beg, q_end)), which the engine finds at [L - q_end, L - q_beg) of its resident
+ * reverse-complement copy (L the query's length).  Empty intervals are legal: the result is one run of 'I' or 'D', or an
+ * empty CIGAR with penalty 0.  The calls below follow the contracts of their whole-sequence counterparts in every other
+ * respect (results, sinks, batches, statuses, stats -- aligned_bp sums the query intervals' lengths).
+ * awv_result is unchanged: q_end / t_end stay the consumed lengths (#M + #X + #D, #M + #X + #I), so they are RELATIVE TO THE
+ * RANGE -- the interval's length for a completed record -- not positions in the sequences.
+ * AWV_ERR_ARG, before anything is launched, for an index out of range or an interval with beg < 0, beg > end or end > length.
+ * The kernels take the packed (2-bit) path when the two SEQUENCES are pure upper-case ACGT, as for whole pairs: an 'N' outside
+ * a range sends it down the raw-byte path, with equal results. */
+typedef struct {
+  int32_t q_idx, t_idx, q_revcomp;
+  int32_t q_beg, q_end;   /* [q_beg, q_end) on the query's FORWARD strand (PAF convention) */
+  int32_t t_beg, t_end;   /* [t_beg, t_end) on the target */
+} awv_range_pair;         /* 28 bytes */
+
+/* awv_align_pairs / awv_align_pairs_verified on ranges. */
+int awv_align_ranges(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, awv_result* out,
+                     awv_sink sink, void* user);
+int awv_align_ranges_verified(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, awv_result* out,
+                              awv_verify_result* vout /* required */, awv_sink sink, void* user);
+/* awv_score_pairs_bounded on ranges; max_penalty == NULL: no bound for any range. */
+int awv_score_ranges(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n,
+                     const int32_t* max_penalty /* per range, nullable; < 0: none */, awv_score_result* out /* required */);
+/* awv_verify_cigars on ranges: results[i] claims that its op bytes align ranges[i] end to end over the two intervals. */
+int awv_verify_ranges(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const awv_result* results,
+                      const uint8_t* cigar_arena, uint64_t arena_bytes, awv_verify_result* vout /* required */);
+
 /* ---- device pair planning (csrc/planner.hip) -------------------------------------------------------------------------
  * Integer work over the engine's resident sequence set, on its device and stream; results equal the host planner's
  * (csrc/host/planner.cpp) bit for bit.  Every call but awv_keep_pairs needs a sequence set (else AWV_ERR_STATE); a new set
