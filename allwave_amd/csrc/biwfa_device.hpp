@@ -3292,7 +3292,10 @@ __device__ __attribute__((noinline)) int find_breakpoint_fn(unsigned sh_addr, un
   kp.chain_max = uni(pc.chain_max);
   kp.multi_T = uni(pc.multi_T);
   kp.deep_passes = uni(pc.deep_passes);
-  kp.max_penalty = uni(pc.max_penalty);
+  // The bound is the pair's: only its top-level search carries it.  The top-level task is the one that arrives without a score
+  // handed down (score_remaining == INT_MAX: a child's is its share of the parent's breakpoint score).  A sub-problem's penalty
+  // never exceeds the pair's, and a bound left on it would only change its pass planning.
+  kp.max_penalty = score_remaining == INT_MAX ? uni(pc.max_penalty) : INT_MAX;
   kp.ring_slot_stride = (size_t)uni64(pc.ring_bytes);
   SubCtx cx;
   cx.plen = uni(pc.plen);
@@ -3525,9 +3528,12 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
       top = false;
       __syncthreads();
     }
-    // (score-only: the closed-form and base-case penalties are exact too; any penalty above the bound reports as such)
+    // (the closed-form and base-case penalties are exact too; any penalty above the bound reports as such)
     const int pair_bound = kp.pair_max_penalty ? kp.pair_max_penalty[pair] : kp.max_penalty;
-    if (status == ST_OK && penalty > pair_bound) status = ST_ABOVE_BOUND;
+    if (status == ST_OK && penalty > pair_bound) {  // (a base-case top level has emitted its ops and counts by now: the record reports none)
+      status = ST_ABOVE_BOUND;
+      em.cnt[0] = em.cnt[1] = em.cnt[2] = em.cnt[3] = 0;
+    }
     if (tid == 0) {
       DevResult r;
       r.status = status;

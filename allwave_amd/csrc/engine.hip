@@ -43,6 +43,7 @@
 #include <algorithm>
 #include <chrono>
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -320,7 +321,8 @@ long long worst_case_penalty(const awv::DevPenalties& d, long long n) {
 }
 
 // score_only: awv_score_pairs -- the top-level search's score only, no CIGAR arena (so max_arena_bytes does not cut batches);
-// max_penalty: that call's bound (INT_MAX = none); pair_bound (nullable, score_only): pair i's own bound instead (INT_MAX = none)
+// max_penalty: that call's bound (INT_MAX = none); pair_bound (nullable): pair i's own bound instead (INT_MAX = none).  A full
+// alignment may carry bounds too (awv_align_pairs_bounded): they stop the pair's top-level search, nothing below it
 // vout (nullable; awv_align_pairs_verified, on the engine's own sequence set): every batch's records and op bytes are checked
 // on the device before the batch's CIGARs are copied back
 // spans (nullable; the awv_*_ranges calls): pair i aligns the rectangle spans[i] of its two sequences, in pattern / text
@@ -701,8 +703,8 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       kp.work_counter = e->d_counters.p;
       kp.stats = e->d_counters.p + 1;
       kp.score_only = score_only ? 1 : 0;
-      kp.max_penalty = score_only ? max_penalty : INT_MAX;
-      kp.pair_max_penalty = score_only && pair_bound ? e->d_pair_bound.p : nullptr;
+      kp.max_penalty = max_penalty;
+      kp.pair_max_penalty = pair_bound ? e->d_pair_bound.p : nullptr;
       const awvr::Span* const d_span = spans ? e->d_pair_span.p : nullptr;  // (range launches: the kernels' two-argument instantiations)
       const bool ranged = spans != nullptr;
       HIP_TRY(hipEventRecord(e->ev0, e->stream));
@@ -1062,6 +1064,9 @@ int awv_align_pairs_verified(awv_engine* e, const awv_penalties* pen, const awv_
 }
 
 namespace {
+// (a bound of 2^30 or more cannot be met by any pair the engine accepts: it is no bound)
+int32_t norm_bound(int32_t b) { return b < 0 || b >= (1 << 30) ? INT_MAX : b; }
+
 // awv_score_pairs / awv_score_pairs_bounded: one bound for the call (pair_bound == nullptr), or one per pair
 int score_core(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, int32_t max_penalty,
                const int32_t* pair_bound, awv_score_result* out, const awvr::Span* spans = nullptr) {
@@ -1073,8 +1078,7 @@ int score_core(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, i
   if (!out) return fail(AWV_ERR_ARG, "score_pairs: null out");
   if (npairs < 0) return fail(AWV_ERR_ARG, "score_pairs: npairs < 0");
   if (e->seqs.n == 0 && npairs > 0) return fail(AWV_ERR_STATE, "score_pairs before set_sequences");
-  // (a bound of 2^30 or more cannot be met by any pair the engine accepts: it is no bound)
-  auto norm = [](int32_t b) { return b < 0 || b >= (1 << 30) ? INT_MAX : b; };
+  auto norm = norm_bound;
   AWV_GUARDED(
     std::vector<awv_result> res((size_t)npairs);
     std::vector<int32_t> pb;
@@ -1118,7 +1122,7 @@ int split_ranges(const SeqSet& s, const awv_range_pair* ranges, int64_t n, std::
   return AWV_OK;
 }
 int align_ranges_core(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, awv_result* out,
-                      awv_verify_result* vout, awv_sink sink, void* user) {
+                      awv_verify_result* vout, awv_sink sink, void* user, const int32_t* max_penalty = nullptr) {
   if (n < 0 || (n > 0 && !ranges)) return fail(AWV_ERR_ARG, "align_ranges: null ranges");
   if (e->seqs.n == 0 && n > 0) return fail(AWV_ERR_STATE, "align_ranges before set_sequences");
   std::vector<awv_pair> pairs;
@@ -1126,9 +1130,50 @@ int align_ranges_core(awv_engine* e, const awv_penalties* pen, const awv_range_p
   if (int rc = split_ranges(e->seqs, ranges, n, pairs, spans, "align_ranges")) return rc;
   if (vout) awvf::stats_reset(e->verify);
   if (n == 0) return align_core(e, e->seqs, pen, nullptr, 0, out, sink, user);
-  return align_core(e, e->seqs, pen, pairs.data(), n, out, sink, user, false, INT_MAX, nullptr, vout, spans.data());
+  std::vector<int32_t> pb;
+  if (max_penalty) {
+    pb.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) pb[(size_t)i] = norm_bound(max_penalty[i]);
+  }
+  return align_core(e, e->seqs, pen, pairs.data(), n, out, sink, user, false, INT_MAX, max_penalty ? pb.data() : nullptr, vout, spans.data());
 }
 }  // namespace
+
+int awv_align_pairs_bounded(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const int32_t* max_penalty,
+                            awv_result* out, awv_verify_result* vout, awv_sink sink, void* user) {
+  if (!e) return fail(AWV_ERR_ARG, "null engine");
+  if (npairs > 0 && !max_penalty) return fail(AWV_ERR_ARG, "align_pairs_bounded: null max_penalty");
+  if (e->seqs.n == 0 && npairs > 0) return fail(AWV_ERR_STATE, "align_pairs before set_sequences");
+  if (vout) awvf::stats_reset(e->verify);
+  AWV_GUARDED(
+    std::vector<int32_t> pb((size_t)std::max<int64_t>(npairs, 0));
+    for (int64_t i = 0; i < npairs; ++i) pb[(size_t)i] = norm_bound(max_penalty[i]);
+    return align_core(e, e->seqs, pen, pairs, npairs, out, sink, user, false, INT_MAX, npairs > 0 ? pb.data() : nullptr, vout);
+  )
+}
+
+int awv_align_ranges_bounded(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const int32_t* max_penalty,
+                             awv_result* out, awv_verify_result* vout, awv_sink sink, void* user) {
+  if (!e) return fail(AWV_ERR_ARG, "null engine");
+  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, out, vout, sink, user, max_penalty);)
+}
+
+int32_t awv_divergence_bound(const awv_penalties* pen, int32_t plen, int32_t tlen, double d) {
+  if (check_penalty_signs(pen) != AWV_OK) return INT32_MIN;
+  if (!(d >= 0.0) || plen < 0 || tlen < 0) {  // (NaN fails the comparison too)
+    (void)fail(AWV_ERR_ARG, "divergence_bound: need d >= 0 and lengths >= 0");
+    return INT32_MIN;
+  }
+  if (d >= 1.0) return -1;
+  // E <= d (plen + tlen) / (2 - d) edit columns (columns = plen + #I = tlen + #D), each at most cmax; one more absorbs the
+  // rounding of the quotient -- the bound only has to err upwards, an exact filter on the counts follows it
+  long long gap1 = (long long)pen->gap_open1 + pen->gap_ext1;
+  if (pen->two_piece) gap1 = std::min(gap1, (long long)pen->gap_open2 + pen->gap_ext2);
+  const long long cmax = std::max<long long>(pen->mismatch, gap1);
+  const double edits = std::floor(d * ((double)plen + (double)tlen) / (2.0 - d));
+  const double B = (double)cmax * (edits + 1.0);
+  return B > (double)INT32_MAX ? -1 : (int32_t)B;
+}
 
 int awv_align_ranges(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, awv_result* out,
                      awv_sink sink, void* user) {

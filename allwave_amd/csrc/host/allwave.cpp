@@ -333,6 +333,20 @@ void align_ranges(const std::vector<Sequence>& sequences, const std::vector<Alig
   if (verify_stats) *verify_stats = it.last_verify_stats();
 }
 
+void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
+                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
+                  awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
+                  BoundStats* bound_stats) {
+  AllPairIterator it = AllPairIterator::for_ranges(sequences, ranges, std::move(params));
+  it.with_devices(devices).with_verify(verify);
+  if (max_penalty) it.with_max_penalty(*max_penalty);
+  if (max_divergence) it.with_max_divergence(*max_divergence);
+  it.for_each_with_callback(callback);
+  if (failures) *failures = it.verify_failures();
+  if (verify_stats) *verify_stats = it.last_verify_stats();
+  if (bound_stats) *bound_stats = it.last_bound_stats();
+}
+
 AllPairIterator::AllPairIterator(const std::vector<Sequence>& sequences, AlignmentParams params)
     : AllPairIterator(sequences, std::move(params), true) {}
 
@@ -486,9 +500,21 @@ AllPairIterator AllPairIterator::with_sparsification(SparsificationStrategy stra
   it.next_chunk_ = next_chunk_;
   it.full_wfa_orientation_ = full_wfa_orientation_;
   it.verify_ = verify_;
+  it.max_penalty_ = max_penalty_;
+  it.max_divergence_ = max_divergence_;
   return it;
 }
 AllPairIterator& AllPairIterator::with_verify(bool on) { verify_ = on; return *this; }
+AllPairIterator& AllPairIterator::with_max_penalty(int max_penalty) {
+  if (max_penalty < 0) throw std::invalid_argument("with_max_penalty: max_penalty must be >= 0");
+  max_penalty_ = max_penalty;
+  return *this;
+}
+AllPairIterator& AllPairIterator::with_max_divergence(double max_divergence) {
+  if (!(max_divergence >= 0.0 && max_divergence < 1.0)) throw std::invalid_argument("with_max_divergence: need 0 <= max_divergence < 1");
+  max_divergence_ = max_divergence;
+  return *this;
+}
 AllPairIterator& AllPairIterator::with_next_chunk(size_t n) { next_chunk_ = std::max<size_t>(1, n); return *this; }
 AllPairIterator& AllPairIterator::with_threads(int t) { threads_ = t; return *this; }
 AllPairParallelIterator AllPairIterator::into_par_iter() const { return AllPairParallelIterator(*this); }
@@ -498,16 +524,28 @@ std::optional<AlignmentResult> AllPairIterator::next() {  // iterator.rs:151-171
     if (next_pos_ >= pairs_.size()) return std::nullopt;
     const size_t first = next_pos_, cnt = std::min(next_chunk_, pairs_.size() - first);
     std::vector<AlignmentResult> buf(cnt);
+    std::vector<uint8_t> have(cnt, 0);  // (a pair above a bound is not delivered: its slot stays empty and is skipped)
     run(first, cnt, [&](const Batch& b) {  // (every entry has its own slot of buf: no lock)
       for (int64_t i = 0; i < b.n; ++i) {
         const size_t k = b.pair(i);
         buf[k] = result_at(first + k, b.is_rev(i), b.res[i], b.arena, true);
+        have[k] = 1;
       }
     });
+    if (bounded()) {
+      size_t w = 0;
+      for (size_t k = 0; k < cnt; ++k)
+        if (have[k]) {
+          if (w != k) buf[w] = std::move(buf[k]);
+          ++w;
+        }
+      buf.resize(w);
+    }
     // (only a run that returned moves the position on: after an error the next call runs the same chunk again)
     next_buf_ = std::move(buf);
     next_buf_pos_ = 0;
     next_pos_ += cnt;
+    if (next_buf_.empty()) return next();  // (a chunk of dropped pairs only: on to the next one)
   }
   return std::move(next_buf_[next_buf_pos_++]);
 }
@@ -549,12 +587,23 @@ void AllPairParallelIterator::for_each_with_callback(const Callback& cb) {
 
 std::vector<AlignmentResult> AllPairParallelIterator::collect() {
   std::vector<AlignmentResult> out(it_.pairs_.size());
+  std::vector<uint8_t> have(it_.pairs_.size(), 0);
   it_.run([&](const AllPairIterator::Batch& b) {  // (every pair has its own slot of `out`: no lock)
     for (int64_t i = 0; i < b.n; ++i) {
       const size_t k = b.pair(i);
       out[k] = it_.result_at(k, b.is_rev(i), b.res[i], b.arena, true);
+      have[k] = 1;
     }
   });
+  if (it_.bounded()) {  // (pairs above a bound are not delivered: the kept ones, in pair-list order)
+    size_t w = 0;
+    for (size_t k = 0; k < out.size(); ++k)
+      if (have[k]) {
+        if (w != k) out[w] = std::move(out[k]);
+        ++w;
+      }
+    out.resize(w);
+  }
   return out;
 }
 
@@ -611,8 +660,12 @@ void add_stats(awv_stats& acc, const awv_stats& x, bool same_engine) {
 // one batch's engine call: awv_align_pairs (awv_align_pairs_verified when `vout` is given), or awv_score_pairs under
 // max_penalty (< 0: no bound) with its results handed to the sink in one call (status and penalty, no arena)
 // rp (nullable): the batch is these n interval pairs -- the same three calls on ranges, `ap` is not read
+// bounds (nullable, alignment calls only): one penalty bound per entry (< 0: none) -- the *_bounded entry points
 int engine_call(awv_engine* e, bool score_only, int32_t max_penalty, const awv_penalties& pen, const awv_pair* ap, int64_t n,
-                awv_sink sink, void* user, awv_verify_result* vout, const awv_range_pair* rp = nullptr) {
+                awv_sink sink, void* user, awv_verify_result* vout, const awv_range_pair* rp = nullptr, const int32_t* align_bounds = nullptr) {
+  if (align_bounds && !score_only)
+    return rp ? awv_align_ranges_bounded(e, &pen, rp, n, align_bounds, nullptr, vout, sink, user)
+              : awv_align_pairs_bounded(e, &pen, ap, n, align_bounds, nullptr, vout, sink, user);
   if (rp && !score_only) return vout ? awv_align_ranges_verified(e, &pen, rp, n, nullptr, vout, sink, user) : awv_align_ranges(e, &pen, rp, n, nullptr, sink, user);
   if (!score_only && vout) return awv_align_pairs_verified(e, &pen, ap, n, nullptr, vout, sink, user);
   if (!score_only) return awv_align_pairs(e, &pen, ap, n, nullptr, sink, user);
@@ -687,6 +740,12 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   std::vector<awv_verify_stats> vst(S, awv_verify_stats{});  // per slot: written by its submitter thread only
   std::vector<std::vector<VerifyFailure>> vfail(S);
   const awv_penalties pen = to_penalties(params_), open = to_penalties(orientation_params_);
+  // bounds on the final alignments (with_max_penalty / with_max_divergence): per batch one penalty bound per entry, and the
+  // pairs above a bound taken out of what the batch callback sees
+  const bool bounded_run = bounded() && !call.score_only;
+  const std::optional<double> div = divergence_bound();
+  if (bounded_run && div && !(*div >= 0.0 && *div < 1.0)) throw std::invalid_argument("max_divergence: need 0 <= max_divergence < 1");
+  std::vector<BoundStats> bst(S);  // per slot: written by its sink calls (which never overlap) and its submitter thread
   auto worker = [&](size_t s) {
     awv_engine* e = nullptr;
     try {
@@ -732,11 +791,61 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
           std::atomic<bool>* stop;
           const std::function<void(std::exception_ptr)>* fail;
           bool failed;
-        } ctx{&batch_cb, rev.data(), idx, &stop, &fail_fn, false};
+          const uint8_t* by_div;  // bounded runs: per entry, whether its penalty bound is the one derived from the divergence
+          double div;             // the divergence bound (< 0: none)
+          BoundStats* bst;
+        } ctx{&batch_cb, rev.data(), idx, &stop, &fail_fn, false, nullptr, -1.0, nullptr};
+        // one penalty bound per entry: the smaller of with_max_penalty's and the one the divergence bound implies
+        std::vector<int32_t> bounds;
+        std::vector<uint8_t> by_div;
+        if (bounded_run) {
+          bounds.assign((size_t)m, max_penalty_ ? (int32_t)*max_penalty_ : -1);
+          by_div.assign((size_t)m, 0);
+          if (div) {
+            for (int64_t i = 0; i < m; ++i) {
+              const int32_t ql = ranges_ ? rp[i].q_end - rp[i].q_beg : (int32_t)sequences_[plist[at(i)].first].seq.size();
+              const int32_t tl = ranges_ ? rp[i].t_end - rp[i].t_beg : (int32_t)sequences_[plist[at(i)].second].seq.size();
+              const int32_t db = awv_divergence_bound(&pen, ql, tl, *div);
+              if (db == INT32_MIN) throw AlignmentError(std::string("max_divergence: ") + awv_last_error());
+              if (db >= 0 && (bounds[(size_t)i] < 0 || db < bounds[(size_t)i])) {
+                bounds[(size_t)i] = db;
+                by_div[(size_t)i] = 1;
+              }
+            }
+          }
+          ctx.by_div = by_div.data();
+          ctx.div = div ? *div : -1.0;
+          ctx.bst = &bst[s];
+          bst[s].pairs += (uint64_t)m;
+        }
         auto sink = [](void* user, int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena) -> int {
           Ctx* c = (Ctx*)user;
           if (c->stop->load()) return 1;  // another slot failed: stop here, report nothing
           try {
+            if (c->bst) {  // a bounded run: the batch callback sees the kept entries only
+              std::vector<awv_result> kres;
+              std::vector<uint8_t> krev;
+              std::vector<size_t> kidx;
+              for (int64_t i = 0; i < cnt; ++i) {
+                const awv_result& r = res[i];
+                if (r.status == AWV_ST_ABOVE_BOUND) {
+                  ++(c->by_div[first + i] ? c->bst->above_divergence : c->bst->above_penalty);
+                  continue;
+                }
+                if (r.status == AWV_ST_COMPLETED && c->div >= 0.0) {  // the exact filter, on the record's counts
+                  const double edits = (double)r.num_mismatches + (double)r.num_ins + (double)r.num_del;
+                  if (!(edits <= c->div * (edits + (double)r.num_matches))) {
+                    ++c->bst->above_divergence;
+                    continue;
+                  }
+                }
+                kres.push_back(r);
+                krev.push_back(c->rev[first + i]);
+                kidx.push_back(c->idx ? c->idx[first + i] : (size_t)(first + i));
+              }
+              (*c->cb)(Batch{0, (int64_t)kres.size(), kres.data(), arena, krev.data(), kidx.data()});
+              return 0;
+            }
             (*c->cb)(Batch{first, cnt, res, arena, c->rev, c->idx});
           } catch (...) {
             (*c->fail)(std::current_exception());  // recorded now, and every slot stops at its next sink call
@@ -747,7 +856,7 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
         };
         std::vector<awv_verify_result> vr(verify ? (size_t)m : 0);
         const int rc = engine_call(e, call.score_only, call.max_penalty, pen, ap.data(), m, sink, &ctx, verify ? vr.data() : nullptr,
-                                   ranges_ ? rp.data() : nullptr);
+                                   ranges_ ? rp.data() : nullptr, bounded_run ? bounds.data() : call.align_bounds);
         lap("aligned + sunk");
         awv_stats x{};
         awv_engine_stats(e, &x);
@@ -789,8 +898,12 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   if (first == 0) {  // a run from the list's start begins anew; a later range (next()'s chunks) adds to it
     verify_failures_.clear();
     verify_stats_ = awv_verify_stats{};
+    bound_stats_ = BoundStats{};
   }
   for (size_t s = 0; s < S; ++s) {
+    bound_stats_.pairs += bst[s].pairs;
+    bound_stats_.above_penalty += bst[s].above_penalty;
+    bound_stats_.above_divergence += bst[s].above_divergence;
     verify_stats_.kernel_ms += vst[s].kernel_ms;
     verify_stats_.pairs += vst[s].pairs;
     verify_stats_.failed += vst[s].failed;
@@ -872,7 +985,7 @@ std::vector<PairScore> AllPairIterator::scores(std::optional<int> max_penalty) {
       p.status = b.res[i].status;
       p.penalty = b.res[i].penalty;
     }
-  }, EngineCall{true, max_penalty ? *max_penalty : -1});
+  }, EngineCall{true, max_penalty ? *max_penalty : -1, nullptr});
   return out;
 }
 

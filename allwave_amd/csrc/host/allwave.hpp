@@ -95,6 +95,13 @@ struct PairScore {
   int32_t status = AWV_ST_COMPLETED;
 };
 
+// What the bounds of a run left out (AllPairIterator::with_max_penalty / with_max_divergence): pairs aligned under a bound,
+// and of them the ones dropped because their penalty is above the penalty bound, or their divergence above the divergence
+// bound (abandoned by the penalty bound derived from it, or completed and filtered on the record's counts).
+struct BoundStats {
+  uint64_t pairs = 0, above_penalty = 0, above_divergence = 0;
+};
+
 using Callback = std::function<void(AlignmentResult&&)>;  // may throw: first error aborts the run
 
 // One interval pair to align globally (awv_range_pair): query[query_start, query_end) -- on the query's FORWARD strand, as PAF
@@ -181,6 +188,19 @@ class AllPairIterator {  // iterator.rs:12-171
   // strand alignments inside WFA orientation are not checked: only the final ones are.
   AllPairIterator& with_verify(bool on);
   bool verify() const { return verify_; }
+  // Bounds on the final alignments (awv_align_pairs_bounded / awv_align_ranges_bounded).  A pair above a bound reaches no
+  // alignment consumer -- no callback, no next() item, no PAF line (unlike a failed pair, which still gives the reference's
+  // "empty" result); last_bound_stats() counts what was left out.  Orientation runs first, under its own penalties, untouched;
+  // scores() ignores both.
+  //   with_max_penalty(B), B >= 0: a pair whose optimal penalty exceeds B is abandoned inside its top-level search.
+  //   with_max_divergence(d), 0 <= d < 1: keeps the pairs whose alignment has (#X + #I + #D) <= d * columns.  Each pair is
+  //   searched under awv_divergence_bound(pen, plen, tlen, d) (a range: its rectangle's lengths), and a completed pair is
+  //   kept iff (double)E <= d * (double)columns on its record's counts.  AlignmentParams::max_divergence of the alignment
+  //   params means the same; the setter wins.  With both bounds the smaller penalty bound applies.
+  AllPairIterator& with_max_penalty(int max_penalty);
+  AllPairIterator& with_max_divergence(double max_divergence);
+  // of the last run (next(): of the chunks since the list's start), summed over the slots
+  BoundStats last_bound_stats() const { return bound_stats_; }
   // of the last run (next(): of the chunks since the list's start): the failed pairs sorted by pair-list index, and the
   // verify counters summed over the slots (kernel_ms: summed kernel time)
   const std::vector<VerifyFailure>& verify_failures() const { return verify_failures_; }
@@ -231,17 +251,20 @@ class AllPairIterator {  // iterator.rs:12-171
   };
   using BatchCb = std::function<void(const Batch&)>;
   // The engine call a run makes per batch: awv_align_pairs, or awv_score_pairs under max_penalty (< 0: no bound; one sink
-  // call per batch, results carry status and penalty, no arena).
+  // call per batch, results carry status and penalty, no arena).  align_bounds (nullable, alignment calls): one bound per
+  // entry of the batch (< 0: none) -- the call is then awv_align_pairs_bounded / awv_align_ranges_bounded; run() fills it in
+  // per batch from with_max_penalty / with_max_divergence.
   struct EngineCall {
     bool score_only;
     int32_t max_penalty;
+    const int32_t* align_bounds;
   };
   // pairs_[first, first + count) on the with_devices slots; batch indices are relative to `first`.  Per batch: orientation,
   // one engine call, the batch callback, the counters.  One slot: one batch, the whole range in list order, on the calling
   // thread.  With several slots, batch callbacks of different slots run concurrently: consumers that call user code
   // serialise it.
-  void run(size_t first, size_t count, const BatchCb& batch_cb, EngineCall call = {false, -1});
-  void run(const BatchCb& batch_cb, EngineCall call = {false, -1}) { run(0, pairs_.size(), batch_cb, call); }
+  void run(size_t first, size_t count, const BatchCb& batch_cb, EngineCall call = {false, -1, nullptr});
+  void run(const BatchCb& batch_cb, EngineCall call = {false, -1, nullptr}) { run(0, pairs_.size(), batch_cb, call); }
   // align_pair's result mapping for entry k of the pair list (a range list: in the range's coordinates)
   AlignmentResult result_at(size_t k, bool is_rev, const awv_result& r, const uint8_t* arena, bool copy_cigar) const;
   std::shared_ptr<const std::vector<AlignmentRange>> ranges_;  // for_ranges: entry k of pairs_ is this interval pair
@@ -253,6 +276,11 @@ class AllPairIterator {  // iterator.rs:12-171
   Orientation orientation_ = Orientation::Wfa;
   bool full_wfa_orientation_ = false;
   bool verify_ = false;
+  std::optional<int> max_penalty_;
+  std::optional<double> max_divergence_;
+  std::optional<double> divergence_bound() const { return max_divergence_ ? max_divergence_ : params_.max_divergence; }
+  bool bounded() const { return max_penalty_.has_value() || divergence_bound().has_value(); }
+  BoundStats bound_stats_{};
   std::vector<VerifyFailure> verify_failures_;
   awv_verify_stats verify_stats_{};
   std::vector<int> devices_{0};
@@ -281,6 +309,7 @@ class AllPairParallelIterator {
   const std::vector<awv_stats>& last_slot_stats() const { return it_.last_slot_stats(); }
   const std::vector<VerifyFailure>& verify_failures() const { return it_.verify_failures(); }
   awv_verify_stats last_verify_stats() const { return it_.last_verify_stats(); }
+  BoundStats last_bound_stats() const { return it_.last_bound_stats(); }
  private:
   friend class AllPairIterator;
   explicit AllPairParallelIterator(const AllPairIterator& it) : it_(it) {}
@@ -308,6 +337,12 @@ AlignmentResult range_alignment_result(const AlignmentRange& range, const awv_re
 void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
                   const Callback& callback, const std::vector<int>& devices = {0}, bool verify = false,
                   std::vector<VerifyFailure>* failures = nullptr, awv_verify_stats* verify_stats = nullptr);
+// the same under bounds (AllPairIterator::with_max_penalty / with_max_divergence; std::nullopt: none): a range above a bound
+// gives no callback; bound_stats (nullable) receives what was left out
+void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
+                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
+                  awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
+                  BoundStats* bound_stats = nullptr);
 
 // ---- mappings in, alignments out: the interval pairs a PAF file names (columns 1-9 of each line) ----
 struct PafRangeLine {

@@ -1,6 +1,8 @@
 // capi.cpp -- extern "C" hooks over the C++ host mirror so the Python tests and bench.py can drive
 // it through ctypes (plain pointers and sizes only).
+#include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,6 +24,28 @@ thread_local std::vector<VerifyFailure> g_verify_failures;
 void keep_verify(const awv_verify_stats& st, const std::vector<VerifyFailure>& f) {
   g_verify_stats = st;
   g_verify_failures = f;
+}
+
+// Bounds on the final alignments: awh_set_bounds leaves them here, per calling thread, for the NEXT alignment hook of that
+// thread, which takes them (they hold for that one call) and leaves its last_bound_stats() for awh_last_bounds.
+thread_local int64_t g_next_max_penalty = -1;
+thread_local double g_next_max_divergence = -1.0;
+thread_local BoundStats g_bound_stats{};
+struct Bounds {
+  int64_t max_penalty;
+  double max_divergence;
+  void apply(AllPairIterator& it) const {
+    if (max_penalty >= 0) it.with_max_penalty((int)std::min<int64_t>(max_penalty, INT32_MAX));
+    if (max_divergence >= 0.0) it.with_max_divergence(max_divergence);
+  }
+  bool any() const { return max_penalty >= 0 || max_divergence >= 0.0; }
+};
+Bounds take_bounds() {
+  const Bounds b{g_next_max_penalty, g_next_max_divergence};
+  g_next_max_penalty = -1;
+  g_next_max_divergence = -1.0;
+  g_bound_stats = BoundStats{};
+  return b;
 }
 
 std::vector<Sequence> make_seqs(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs) {
@@ -96,6 +120,7 @@ int awh_all_pairs_paf_devices(int n, const char* const* ids, const uint8_t* byte
                               const char* sparsification, int orientation, int exclude_self, const int32_t* devices, int n_devices,
                               int64_t min_batch_pairs, int verify, awv_stats* slot_stats, char** out, size_t* out_len, char* err,
                               size_t cap) {
+  const Bounds bounds = take_bounds();
   try {
     const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
     AllPairIterator it = AllPairIterator::with_options(seqs, parse_scores(scores), exclude_self != 0, orientation == 2,
@@ -106,12 +131,14 @@ int awh_all_pairs_paf_devices(int n, const char* const* ids, const uint8_t* byte
     it.with_devices(std::vector<int>(devices, devices + n_devices));
     if (min_batch_pairs > 0) it.with_min_batch_pairs((size_t)min_batch_pairs);
     it.with_verify(verify != 0);
+    bounds.apply(it);
     std::string all;
     it.for_each_with_callback([&](AlignmentResult&& r) {  // the reference's own per-record path
       all += alignment_to_paf(r, seqs);
       all.push_back('\n');
     });
     keep_verify(it.last_verify_stats(), it.verify_failures());
+    g_bound_stats = it.last_bound_stats();
     if (slot_stats) for (int k = 0; k < n_devices; ++k) slot_stats[k] = it.last_slot_stats()[(size_t)k];
     *out = (char*)malloc(all.size() + 1);
     memcpy(*out, all.c_str(), all.size() + 1);
@@ -139,6 +166,7 @@ int awh_iterate_devices(int n, const char* const* ids, const uint8_t* bytes, con
                         const int32_t* devices, int n_devices, int64_t min_batch_pairs, int64_t shard_rank, int64_t shard_world,
                         int verify_on, awv_stats* slot_stats, char** out, size_t* out_len, size_t* n_records, size_t* late_calls,
                         char* err, size_t cap) {
+  const Bounds bounds = take_bounds();
   if (!devices || n_devices < 1) { set_err(err, cap, "awh_iterate_devices: empty device list"); return -1; }
   size_t seen = 0, late = 0;
   bool thrown = false;
@@ -164,15 +192,17 @@ int awh_iterate_devices(int n, const char* const* ids, const uint8_t* bytes, con
     const std::vector<int> devs(devices, devices + n_devices);
     std::vector<awv_stats> st;
     const bool verify = verify_on != 0;
-    if (mode == 4 && min_batch_pairs <= 0 && !verify) {
+    if (mode == 4 && min_batch_pairs <= 0 && !verify && !bounds.any()) {
       process_alignments_with_callback(seqs, parse_scores(scores), strat, record, devs);
     } else if (mode == 4) {  // what that overload does, with the batch size of the call and the check
       AllPairIterator it = AllPairIterator::with_options(seqs, parse_scores(scores), true, true, strat);
       it.with_devices(devs).with_verify(verify);
+      bounds.apply(it);
       if (min_batch_pairs > 0) it.with_min_batch_pairs((size_t)min_batch_pairs);
       it.for_each_with_callback(record);
       st = it.last_slot_stats();
       keep_verify(it.last_verify_stats(), it.verify_failures());
+      g_bound_stats = it.last_bound_stats();
     } else {
       AllPairIterator it0 = AllPairIterator::with_options(seqs, parse_scores(scores), true, orientation == 2,
                                                          resparsify ? SparsificationStrategy{} : strat);
@@ -182,11 +212,12 @@ int awh_iterate_devices(int n, const char* const* ids, const uint8_t* bytes, con
       if (min_batch_pairs > 0) it0.with_min_batch_pairs((size_t)min_batch_pairs);
       if (chunk > 0) it0.with_next_chunk((size_t)chunk);
       it0.with_verify(verify);
+      bounds.apply(it0);
       AllPairIterator it = resparsify ? it0.with_sparsification(strat).with_shard((size_t)shard_rank, (size_t)shard_world) : it0;
-      if (mode == 0) { it.for_each_with_callback(record); st = it.last_slot_stats(); keep_verify(it.last_verify_stats(), it.verify_failures()); }
-      else if (mode == 1) { while (auto r = it.next()) record(std::move(*r)); st = it.last_slot_stats(); keep_verify(it.last_verify_stats(), it.verify_failures()); }
-      else if (mode == 2) { auto par = it.into_par_iter(); par.with_threads(threads).for_each_with_callback(record); st = par.last_slot_stats(); keep_verify(par.last_verify_stats(), par.verify_failures()); }
-      else if (mode == 3) { auto par = it.into_par_iter(); for (auto& r : par.collect()) record(std::move(r)); st = par.last_slot_stats(); keep_verify(par.last_verify_stats(), par.verify_failures()); }
+      if (mode == 0) { it.for_each_with_callback(record); st = it.last_slot_stats(); keep_verify(it.last_verify_stats(), it.verify_failures()); g_bound_stats = it.last_bound_stats(); }
+      else if (mode == 1) { while (auto r = it.next()) record(std::move(*r)); st = it.last_slot_stats(); keep_verify(it.last_verify_stats(), it.verify_failures()); g_bound_stats = it.last_bound_stats(); }
+      else if (mode == 2) { auto par = it.into_par_iter(); par.with_threads(threads).for_each_with_callback(record); st = par.last_slot_stats(); keep_verify(par.last_verify_stats(), par.verify_failures()); g_bound_stats = par.last_bound_stats(); }
+      else if (mode == 3) { auto par = it.into_par_iter(); for (auto& r : par.collect()) record(std::move(r)); st = par.last_slot_stats(); keep_verify(par.last_verify_stats(), par.verify_failures()); g_bound_stats = par.last_bound_stats(); }
       else throw std::invalid_argument("awh_iterate_devices: unknown mode");
     }
     if (slot_stats)
@@ -243,6 +274,7 @@ int awh_all_pairs_paf_count_devices(int n, const char* const* ids, const uint8_t
                                     int orientation, const char* sparsification, const int32_t* devices, int n_devices,
                                     int64_t min_batch_pairs, int format_threads, int verify, uint64_t* out_bytes, uint64_t* out_lines,
                                     uint64_t* out_checksum, double* secs, awv_stats* st, awv_stats* slot_stats, char* err, size_t cap) {
+  const Bounds bounds = take_bounds();
   if (!devices || n_devices < 1) { set_err(err, cap, "awh_all_pairs_paf_count_devices: empty device list"); return -1; }
   try {
     const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
@@ -255,6 +287,7 @@ int awh_all_pairs_paf_count_devices(int n, const char* const* ids, const uint8_t
     if (min_batch_pairs > 0) it.with_min_batch_pairs((size_t)min_batch_pairs);
     it.with_threads(format_threads);  // this call's sketching / orientation threads: carried by the iterator, not a process-wide setting
     it.with_verify(verify != 0);
+    bounds.apply(it);
     uint64_t nb = 0, nl = 0, sum = 0;
     const auto t0 = std::chrono::steady_clock::now();
     it.for_each_paf_batch([&](const std::string& s) {
@@ -273,6 +306,7 @@ int awh_all_pairs_paf_count_devices(int n, const char* const* ids, const uint8_t
     *out_lines = nl;
     if (out_checksum) *out_checksum = sum;
     keep_verify(it.last_verify_stats(), it.verify_failures());
+    g_bound_stats = it.last_bound_stats();
     if (st) *st = it.last_stats();
     if (slot_stats) for (int k = 0; k < n_devices; ++k) slot_stats[k] = it.last_slot_stats()[(size_t)k];
     return 0;
@@ -547,6 +581,7 @@ int awh_check_paf(int n, const char* const* ids, const uint8_t* bytes, const uin
 // list order (malloc'ed).  The verify counters and failures are left for awh_last_verify.
 int awh_align_ranges_paf(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores, const int64_t* ranges,
                          size_t nr, const int32_t* devices, int n_devices, int verify, char** out, size_t* out_len, char* err, size_t cap) {
+  const Bounds bounds = take_bounds();
   try {
     if (!devices || n_devices < 1) throw std::invalid_argument("awh_align_ranges_paf: empty device list");
     const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
@@ -559,9 +594,11 @@ int awh_align_ranges_paf(int n, const char* const* ids, const uint8_t* bytes, co
     }
     AllPairIterator it = AllPairIterator::for_ranges(seqs, rg, parse_scores(scores));
     it.with_devices(std::vector<int>(devices, devices + n_devices)).with_verify(verify != 0);
+    bounds.apply(it);
     AllPairParallelIterator par = it.into_par_iter();
     const std::vector<AlignmentResult> res = par.collect();  // (in list order, on any number of slots)
     keep_verify(par.last_verify_stats(), par.verify_failures());
+    g_bound_stats = par.last_bound_stats();
     std::string all;
     for (const AlignmentResult& r : res) {
       all += alignment_to_paf(r, seqs);
@@ -615,6 +652,21 @@ int awh_parse_paf_ranges(int n, const char* const* ids, const int64_t* lens, con
   }
   *nlines = pr.lines.size();
   return 0;
+}
+
+// ---- bounds on the final alignments ----
+// The calling thread's NEXT alignment hook (awh_all_pairs_paf_devices, awh_iterate_devices, awh_all_pairs_paf_count_devices,
+// awh_align_ranges_paf) runs under AllPairIterator::with_max_penalty(max_penalty) (< 0: none) and
+// with_max_divergence(max_divergence) (< 0: none); the hooks after it run unbounded again.
+void awh_set_bounds(int64_t max_penalty, double max_divergence) {
+  g_next_max_penalty = max_penalty;
+  g_next_max_divergence = max_divergence;
+}
+// last_bound_stats() of the calling thread's last alignment hook: {pairs, above_penalty, above_divergence}
+void awh_last_bounds(uint64_t out[3]) {
+  out[0] = g_bound_stats.pairs;
+  out[1] = g_bound_stats.above_penalty;
+  out[2] = g_bound_stats.above_divergence;
 }
 
 void awh_free(void* p) { free(p); }

@@ -6,6 +6,7 @@
 // --shard R/N (this process's part of the pair list), --forward-only (skip orientation: all '+'),
 // --wfa-orientation-full (WFA orientation by two full alignments per pair, the reference's method, instead of bounded scores),
 // --score-only (penalties instead of PAF: WFA2's ComputeScore scope) with an optional --max-penalty N bound,
+// --max-align-penalty N / --max-divergence D (full alignments under a bound: pairs above it are abandoned early and left out),
 // --verify (check every alignment on the device before it is written; exit status 4 when one fails),
 // --check-paf FILE [--check-optimal] [--partial] (check an existing PAF against the FASTA on the device; nothing is aligned),
 // --align-paf FILE (align the interval pairs columns 1-9 of each line of FILE name, globally: mappings in, PAF with cg:Z: out).
@@ -39,6 +40,9 @@ struct Args {
   bool score_only = false;  // --score-only: one line `qname qlen tname tlen strand penalty` per pair instead of PAF
   long max_penalty = -1;    // --max-penalty N (with --score-only): pairs whose penalty exceeds N are left out
   bool have_max_penalty = false;
+  long max_align_penalty = -1;  // --max-align-penalty N: alignments whose penalty exceeds N are abandoned and left out
+  double max_divergence = -1.0; // --max-divergence D: alignments with (#X + #I + #D) > D * columns are left out
+  bool have_max_align_penalty = false, have_max_divergence = false;
   int plan_device = -1;     // --plan-device N: plan the pair list, the mash matrix and mash orientation on device N
   bool verify = false;      // --verify: awv_align_pairs_verified; `verified N pairs, F failed, K ms` on the summary line
   std::string check_paf;    // --check-paf FILE: check that PAF against the input instead of aligning
@@ -213,6 +217,23 @@ int main(int argc, char** argv) {
       if (v.empty() || !end || *end != 0 || a.max_penalty < 0 || a.max_penalty > INT32_MAX) die("--max-penalty expects a penalty N >= 0");
       a.have_max_penalty = true;
     }
+    else if (k == "--max-align-penalty") {
+      const std::string v = val();
+      char* end = nullptr;
+      a.max_align_penalty = strtol(v.c_str(), &end, 10);
+      if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || !end || *end != 0 || a.max_align_penalty > INT32_MAX)
+        die("--max-align-penalty expects a penalty N >= 0");
+      a.have_max_align_penalty = true;
+    }
+    else if (k == "--max-divergence") {
+      const std::string v = val();
+      char* end = nullptr;
+      a.max_divergence = strtod(v.c_str(), &end);
+      if (v.empty() || v.find_first_not_of("0123456789.eE+-") != std::string::npos || !end || *end != 0 ||
+          !(a.max_divergence >= 0.0 && a.max_divergence < 1.0))
+        die("--max-divergence expects a divergence D with 0 <= D < 1");
+      a.have_max_divergence = true;
+    }
     else if (k == "--shard") {
       const std::string v = val();
       char* end = nullptr;
@@ -227,8 +248,10 @@ int main(int argc, char** argv) {
       std::cout << "usage: allwave_hip -i in.fa [-o out.paf] [-s m,x,o,e[,o2,e2] | -x ANI] [-p none|auto|random:f|giant:p|tree:n:f:r[:k]]\n"
                    "                   [-t threads] [--wfa-orientation|--wfa-orientation-full|--forward-only] [-k prefixes | -e prefixes] [--mash-matrix]\n"
                    "                   [--device N | --devices LIST] [--shard R/N] [--score-only [--max-penalty N]] [--plan-device N] [--verify]\n"
+                   "                   [--max-align-penalty N] [--max-divergence D]\n"
                    "       allwave_hip -i in.fa --check-paf FILE [-s scores | -x ANI] [--check-optimal] [--partial] [--device N]\n"
                    "       allwave_hip -i in.fa --align-paf FILE [-s scores | -x ANI] [-o out.paf] [--verify] [--score-only] [--device N | --devices LIST]\n"
+                   "                   [--max-align-penalty N] [--max-divergence D]\n"
                    "  --verify         check every alignment on the device before it is written (columns, counts, penalty); the summary\n"
                    "                   line gains `verified N pairs, F failed, K ms`, failures go to stderr, exit status 4 if any\n"
                    "  --check-paf FILE align nothing: check every line of FILE (12 columns + cg:Z:) against in.fa on the device; one line\n"
@@ -245,12 +268,26 @@ int main(int argc, char** argv) {
                    "  --score-only     no PAF: one tab-separated line per pair, `qname qlen tname tlen strand penalty`, in pair-list\n"
                    "                   order (the optimal penalty without a CIGAR; `*` for a pair that failed)\n"
                    "  --max-penalty N  with --score-only: stop searching a pair once its penalty is proved above N and leave it out\n"
+                   "  --max-align-penalty N  full alignments under a penalty bound: a pair whose optimal penalty is proved above N is\n"
+                   "                   abandoned inside its top-level search and gets no PAF line; the PAF is the unbounded one minus those\n"
+                   "                   lines, and the summary line gains `A pairs above the bound`\n"
+                   "  --max-divergence D  0 <= D < 1: keep the alignments with (#X + #I + #D) <= D * columns; every pair is searched under\n"
+                   "                   the penalty bound no such alignment can exceed, completed pairs are filtered on their counts\n"
                    "  --plan-device N  plan on device N: --mash-matrix, the -p pair list and mash orientation (the same output as\n"
                    "                   the host planner; with --shard every rank plans the whole list on its own plan device)\n";
       return 0;
     } else die("unexpected argument: " + k);
   }
   if (a.have_max_penalty && !a.score_only) die("the argument '--max-penalty' requires '--score-only'");
+  auto bound_flag_alone = [&](bool have, const char* flag) {  // (before any device is opened)
+    if (!have) return;
+    const std::string f = std::string("the argument '") + flag + "' cannot be used with ";
+    if (a.score_only) die(f + "'--score-only' (which has '--max-penalty')");
+    if (a.have_check_paf) die(f + "'--check-paf'");
+    if (a.mash_matrix) die(f + "'--mash-matrix'");
+  };
+  bound_flag_alone(a.have_max_align_penalty, "--max-align-penalty");
+  bound_flag_alone(a.have_max_divergence, "--max-divergence");
   if (a.check_optimal && !a.have_check_paf) die("the argument '--check-optimal' requires '--check-paf'");
   if (a.verify && a.score_only) die("the argument '--verify' cannot be used with '--score-only'");
   if (a.verify && a.mash_matrix) die("the argument '--verify' cannot be used with '--mash-matrix'");
@@ -361,6 +398,9 @@ int main(int argc, char** argv) {
     AllPairIterator it = a.have_align_paf ? AllPairIterator::for_ranges(sequences, ranges, params)
                                           : AllPairIterator::with_options(sequences, params, true, !a.wfa_orientation, strategy, a.plan_device);
     it.with_verify(a.verify);
+    if (a.have_max_align_penalty) it.with_max_penalty((int)a.max_align_penalty);
+    if (a.have_max_divergence) it.with_max_divergence(a.max_divergence);
+    const bool bounded = a.have_max_align_penalty || a.have_max_divergence;
     if (a.forward_only) it.with_orientation(Orientation::ForwardOnly);
     it.with_full_wfa_orientation(a.wfa_orientation_full);
     it.with_devices(devices);
@@ -418,12 +458,15 @@ int main(int argc, char** argv) {
       fout.close();
       if (fout.fail()) die("write error on the PAF output (close)", 1);
     }
-    if (done != total) die("internal: wrote " + std::to_string(done) + " of " + std::to_string(total) + (a.score_only ? " pairs" : " PAF lines"), 1);
+    const BoundStats bs = it.last_bound_stats();
+    const size_t above = (size_t)(bs.above_penalty + bs.above_divergence);  // (pairs above a bound get no line)
+    if (done + above != total) die("internal: wrote " + std::to_string(done) + " of " + std::to_string(total) + (a.score_only ? " pairs" : " PAF lines"), 1);
     if (!a.no_progress) {
       const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       char buf[320];
       int w = snprintf(buf, sizeof(buf), "[%.1fs] %zu/%zu (100.0%%) %.1f alignments/sec", secs, done, total, done / std::max(secs, 1e-9));
       if (a.have_align_paf && w > 0 && (size_t)w < sizeof(buf)) w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", %zu bad lines", bad_lines);
+      if (bounded && w > 0 && (size_t)w < sizeof(buf)) w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", %zu pairs above the bound", above);
       if (a.verify) {
         const awv_verify_stats vs = it.last_verify_stats();
         snprintf(buf + w, sizeof(buf) - (size_t)w, ", verified %llu pairs, %zu failed, %.2f ms", (unsigned long long)vs.pairs,

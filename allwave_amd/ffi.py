@@ -61,7 +61,8 @@ EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine
            "awv_score_pairs_bounded", "awv_orient_pairs", "awv_orient_decide", "awv_orient_settling_bound",
            "awv_sketch", "awv_sketch_copy", "awv_sketch_pair_counts", "awv_sketch_rows", "awv_sketch_knn", "awv_keep_pairs",
            "awv_align_pairs_verified", "awv_verify_cigars", "awv_verify_one_host", "awv_engine_verify_stats",
-           "awv_align_ranges", "awv_align_ranges_verified", "awv_score_ranges", "awv_verify_ranges")
+           "awv_align_ranges", "awv_align_ranges_verified", "awv_score_ranges", "awv_verify_ranges",
+           "awv_align_pairs_bounded", "awv_align_ranges_bounded", "awv_divergence_bound")
 
 
 class EngineConfig(C.Structure):
@@ -157,6 +158,11 @@ def load():
         L.awv_align_ranges_verified.argtypes = L.awv_align_pairs_verified.argtypes
         L.awv_score_ranges.argtypes = L.awv_score_pairs_bounded.argtypes
         L.awv_verify_ranges.argtypes = L.awv_verify_cigars.argtypes
+        L.awv_align_pairs_bounded.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              SINK_FN, C.c_void_p]
+        L.awv_align_ranges_bounded.argtypes = L.awv_align_pairs_bounded.argtypes
+        L.awv_divergence_bound.argtypes = [C.POINTER(Penalties), C.c_int32, C.c_int32, C.c_double]
+        L.awv_divergence_bound.restype = C.c_int32
         _LIB = L
     return _LIB
 
@@ -229,11 +235,12 @@ class Engine:
             ranges = r
         return np.ascontiguousarray(ranges)
 
-    def align_ranges(self, scores, ranges, want_cigars=True, verify=False):
+    def align_ranges(self, scores, ranges, want_cigars=True, verify=False, max_penalty=None):
         """align_pairs on interval pairs (awv_align_ranges / awv_align_ranges_verified).  ranges: int array [n,7] (q_idx, t_idx,
         q_revcomp, q_beg, q_end, t_beg, t_end) or a RANGE_DTYPE array; the query interval is on the query's forward strand.
-        The records' q_end / t_end are consumed lengths, relative to the range."""
-        return self._align("awv_align_ranges", scores, self._range_array(ranges), want_cigars, verify)
+        The records' q_end / t_end are consumed lengths, relative to the range.  max_penalty: as for align_pairs
+        (awv_align_ranges_bounded)."""
+        return self._align("awv_align_ranges", scores, self._range_array(ranges), want_cigars, verify, max_penalty)
 
     def score_ranges(self, scores, ranges, max_penalty=None):
         """score_pairs on interval pairs (awv_score_ranges).  max_penalty: None, or one bound per range (negative: none)."""
@@ -254,15 +261,28 @@ class Engine:
         """verify_cigars on interval pairs (awv_verify_ranges)."""
         return self._verify("awv_verify_ranges", scores, self._range_array(ranges), results, arena)
 
-    def align_pairs(self, scores, pairs, want_cigars=True, verify=False):
+    def align_pairs(self, scores, pairs, want_cigars=True, verify=False, max_penalty=None):
         """pairs: int array [n,2] (q,t) or [n,3] (q,t,revcomp), or a PAIR_DTYPE array.
         Returns (results structured array, list of op-byte strings or None); verify=True: every finished pair is checked on
-        the device (awv_align_pairs_verified) and a VERIFY_DTYPE array comes back as a third value."""
-        return self._align("awv_align_pairs", scores, self._pair_array(pairs), want_cigars, verify)
+        the device (awv_align_pairs_verified) and a VERIFY_DTYPE array comes back as a third value.
+        max_penalty: None = no bound; an int >= 0: one bound for every pair; an array or a list: one bound per pair, a
+        negative entry leaving that pair unbounded (awv_align_pairs_bounded).  A pair proved above its bound comes back
+        AWV_ST_ABOVE_BOUND with penalty bound + 1, no CIGAR (None in the list) and zero counts."""
+        return self._align("awv_align_pairs", scores, self._pair_array(pairs), want_cigars, verify, max_penalty)
 
-    def _align(self, fn, scores, pairs, want_cigars, verify):
-        """awv_align_pairs / awv_align_ranges (`fn`; verify: its _verified variant) on a contiguous PAIR_DTYPE / RANGE_DTYPE array."""
+    def _align(self, fn, scores, pairs, want_cigars, verify, max_penalty=None):
+        """awv_align_pairs / awv_align_ranges (`fn`; verify: its _verified variant; max_penalty: its _bounded variant) on a
+        contiguous PAIR_DTYPE / RANGE_DTYPE array."""
         pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+        bounds = None
+        if max_penalty is not None:
+            if np.ndim(max_penalty) == 0 and int(max_penalty) < 0:
+                raise ValueError("max_penalty must be >= 0 (None: no bound)")
+            bounds = np.ascontiguousarray(np.broadcast_to(np.asarray(max_penalty, dtype=np.int32), (len(pairs),))) \
+                if np.ndim(max_penalty) == 0 else np.ascontiguousarray(max_penalty, dtype=np.int32)
+            if bounds.shape != (len(pairs),):
+                raise ValueError("max_penalty: need one bound per pair")
+            bounds = bounds if len(bounds) else np.zeros(1, dtype=np.int32)
         fn_v = fn + "_verified"
         res = np.zeros(len(pairs), dtype=RESULT_DTYPE)
         cigars = [None] * len(pairs) if want_cigars else None
@@ -277,6 +297,14 @@ class Engine:
             return 0
 
         cb = SINK_FN(_sink) if want_cigars else SINK_FN()
+        if bounds is not None:
+            fn_b = fn + "_bounded"
+            vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)] if verify else None
+            rc = getattr(load(), fn_b)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), bounds.ctypes.data, res.ctypes.data,
+                                       vres.ctypes.data if verify else None, cb, None)
+            if rc != AWV_OK:
+                raise EngineError(rc, fn_b)
+            return (res, cigars, vres) if verify else (res, cigars)
         if verify:
             vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)]  # (vout is required, also for an empty list)
             rc = getattr(load(), fn_v)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), res.ctypes.data, vres.ctypes.data, cb, None)
@@ -391,6 +419,16 @@ def verify_one_host(scores, pattern, text, cigar, claimed):
     if rc != AWV_OK:
         raise EngineError(rc, "awv_verify_one_host")
     return out[0]
+
+
+def divergence_bound(scores, plen, tlen, d):
+    """awv_divergence_bound: the penalty no alignment of divergence <= d of a plen x tlen pair can exceed, divergence =
+    (#X + #I + #D) / columns.  -1: no bound (d >= 1, or it would pass INT32_MAX).  Needs no device."""
+    pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+    b = load().awv_divergence_bound(C.byref(pen), int(plen), int(tlen), float(d))
+    if b < -1:
+        raise EngineError(AWV_ERR_ARG, "awv_divergence_bound")
+    return b
 
 
 def orient_decide(scores, lo_f, hi_f, lo_r, hi_r):

@@ -119,6 +119,25 @@ def last_verify():
     return dict(pairs=int(st.pairs), failed=int(st.failed), columns=int(st.columns), kernel_ms=float(st.kernel_ms), failures=fails)
 
 
+def _set_bounds(max_penalty, max_divergence):
+    """awh_set_bounds: the bounds of this thread's next alignment hook (None: none); that hook takes them."""
+    if max_penalty is not None and int(max_penalty) < 0:
+        raise ValueError("max_penalty must be >= 0 (None: no bound)")
+    if max_divergence is not None and not 0.0 <= float(max_divergence) < 1.0:
+        raise ValueError("max_divergence must be in [0, 1) (None: no bound)")
+    load().awh_set_bounds(C.c_int64(-1 if max_penalty is None else int(max_penalty)),
+                          C.c_double(-1.0 if max_divergence is None else float(max_divergence)))
+
+
+def last_bounds():
+    """last_bound_stats() of this thread's last all_pairs_paf / iterate / all_pairs_paf_count / align_ranges call:
+    dict(pairs, above_penalty, above_divergence) -- pairs aligned under a bound, and of them the ones left out because their
+    penalty is above max_penalty or their divergence above max_divergence (zeros for a call without bounds)."""
+    out = (C.c_uint64 * 3)()
+    load().awh_last_bounds(out)
+    return dict(pairs=int(out[0]), above_penalty=int(out[1]), above_divergence=int(out[2]))
+
+
 def verify_failure_path(ids, pairs, first, calls):
     """The way a failed check travels above the engine, without an engine (append_verify_failures per engine call,
     sort_verify_failures, report_verify_failures, the record packing of last_verify()).  pairs: the run's range of (q, t)
@@ -192,12 +211,14 @@ def check_paf(ids, seqs, paf_text, scores, optimal=False, device=0, partial=Fals
     return dict(lines=int(counts[0]), checked=int(counts[1]), skipped=int(counts[2]), kernel_ms=float(st.kernel_ms), failures=fails)
 
 
-def align_ranges(ids, seqs, ranges, scores, devices=None, device=0, verify=False):
+def align_ranges(ids, seqs, ranges, scores, devices=None, device=0, verify=False, max_penalty=None, max_divergence=None):
     """allwave::align_ranges + alignment_to_paf: the interval pairs `ranges` -- rows (query_idx, target_idx, is_reverse,
     query_start, query_end, target_start, target_end), the query interval on its forward strand -- aligned globally on the
     engines `devices` names (default: [device]).  Returns the PAF lines in list order: columns 3-4 and 8-9 are the interval,
     2 and 7 the full lengths; a failed range prints its starts twice and an empty cg.  verify=True: every range is checked on
-    the device; last_verify() then holds the counters and the failures (index = list index)."""
+    the device; last_verify() then holds the counters and the failures (index = list index).  max_penalty / max_divergence: as
+    for all_pairs_paf (the divergence bound's penalty bound comes from the rectangle's lengths); a range above a bound gives
+    no line."""
     cids, data, offs = _seq_args(ids, seqs)
     r = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1, 7))
     devs, nd = _device_args([device] if devices is None else devices)
@@ -205,6 +226,7 @@ def align_ranges(ids, seqs, ranges, scores, devices=None, device=0, verify=False
     n = C.c_size_t(0)
     e = _err()
     rbuf = r if len(r) else np.zeros((1, 7), dtype=np.int64)
+    _set_bounds(max_penalty, max_divergence)
     rc = load().awh_align_ranges_paf(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), scores.encode(),
                                      rbuf.ctypes.data_as(C.c_void_p), C.c_size_t(len(r)), devs, nd, int(bool(verify)), C.byref(out),
                                      C.byref(n), e, _CAP)
@@ -274,17 +296,22 @@ def _device_args(devices):
 
 
 def all_pairs_paf(ids, seqs, scores, orientation="wfa", exclude_self=True, device=0, sparsification="none", devices=None,
-                  min_batch_pairs=0, orientation_full=False, verify=False):
+                  min_batch_pairs=0, orientation_full=False, verify=False, max_penalty=None, max_divergence=None):
     """AllPairIterator + alignment_to_paf per record; returns the list of PAF lines.  `devices`: a list of ordinals (one
     engine per entry, repeats allowed) to spread the pair list over in this call; None = [device].
     `min_batch_pairs` > 0 overrides the smallest batch of a multi-device run (default 16,384).  orientation_full: WFA
     orientation by two full alignments for every pair (the reference's method; the same strands) instead of bounded scores.
-    verify: every alignment is checked on the device (with_verify); the lines are the same, last_verify() tells the outcome."""
+    verify: every alignment is checked on the device (with_verify); the lines are the same, last_verify() tells the outcome.
+    max_penalty (an int >= 0) / max_divergence (0 <= d < 1): bounds on the final alignments (with_max_penalty /
+    with_max_divergence) -- a pair whose penalty exceeds max_penalty, or whose alignment has (#X + #I + #D) > d * columns,
+    is abandoned early where that can be proved and gives no line; the other lines are the unbounded call's; last_bounds()
+    counts what was left out."""
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if devices is None else devices)
     out = C.c_void_p()
     n = C.c_size_t(0)
     e = _err()
+    _set_bounds(max_penalty, max_divergence)
     rc = load().awh_all_pairs_paf_devices(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
                                           scores.encode(), sparsification.encode(), _orient_code(orientation, orientation_full), int(exclude_self),
                                           devs, nd, C.c_int64(int(min_batch_pairs)), int(bool(verify)), None, C.byref(out), C.byref(n), e, _CAP)
@@ -300,7 +327,7 @@ ITER_MODES = {"for_each": 0, "next": 1, "par_for_each": 2, "par_collect": 3, "pr
 
 def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientation="forward", threads=4, chunk=0,
             resparsify=False, fail_at=-1, device=0, devices=None, min_batch_pairs=0, shard=None, with_stats=False,
-            orientation_full=False, verify=False):
+            orientation_full=False, verify=False, max_penalty=None, max_divergence=None):
     """Every consumer of the pair list (iterator.rs:101-253, lib.rs:57-68) through one hook; returns the PAF lines in arrival
     order.  `fail_at` >= 0 makes the callback throw at that record: HostError carries its message.
     `devices`: a list of ordinals (one engine per entry, repeats allowed) to spread the pair list over; None = [device].
@@ -310,9 +337,11 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
     many records arrived before the error, and `.late_calls`: how many callback calls followed the first failure (with
     fail_at, each of those fails with a message of its own: "callback failed again, ...").  orientation_full: WFA
     orientation by two full alignments for every pair instead of bounded scores (the same strands).  verify: with_verify on the
-    iterator, whichever consumer `mode` names; last_verify() tells the outcome."""
+    iterator, whichever consumer `mode` names; last_verify() tells the outcome.  max_penalty / max_divergence: as for
+    all_pairs_paf -- no consumer is handed a pair above a bound."""
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if devices is None else devices)
+    _set_bounds(max_penalty, max_divergence)
     st = (ffi.Stats * nd)()
     rank, world = shard if shard is not None else (0, 1)
     out = C.c_void_p()
@@ -336,15 +365,17 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
 
 
 def all_pairs_paf_count(ids, seqs, scores, orientation="forward", device=0, format_threads=8, devices=None, min_batch_pairs=0,
-                        sparsification=None, checksum=False, verify=False):
+                        sparsification=None, checksum=False, verify=False, max_penalty=None, max_divergence=None):
     """End to end: upload -> align -> D2H -> format into a counting sink. Returns (bytes, lines, secs, ffi.Stats) for
     every pair on `device`.  `devices`: a list of ordinals (one engine per entry, repeats allowed); the Stats are then
     summed over the slots, and the result gains a fifth element, each slot's Stats (last_slot_stats()), and a sixth, the
     sum of the lines' FNV-1a hashes when `checksum` (order-independent; else None).  With devices, `sparsification` plans
-    the pair list (default: every pair).  verify: with_verify on the iterator; last_verify() tells the outcome."""
+    the pair list (default: every pair).  verify: with_verify on the iterator; last_verify() tells the outcome.
+    max_penalty / max_divergence: as for all_pairs_paf (the lines counted are the kept pairs')."""
     one = devices is None
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if one else devices)
+    _set_bounds(max_penalty, max_divergence)
     nb, nl, secs, ck = C.c_uint64(0), C.c_uint64(0), C.c_double(0), C.c_uint64(0)
     st = ffi.Stats()
     slot = (ffi.Stats * nd)()

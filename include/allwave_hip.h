@@ -71,7 +71,7 @@ extern "C" {
  * comes back AWV_ST_CAPACITY after its last re-run. */
 #define AWV_ST_INTERNAL 2        /* invariant violated (would be a bug) */
 #define AWV_ST_MAX_STEPS 3       /* step guard tripped */
-#define AWV_ST_ABOVE_BOUND 4     /* score-only calls: the penalty exceeds max_penalty */
+#define AWV_ST_ABOVE_BOUND 4     /* score-only and bounded calls: the penalty exceeds max_penalty */
 
 typedef struct awv_engine awv_engine;
 
@@ -343,6 +343,33 @@ int awv_score_ranges(awv_engine* e, const awv_penalties* pen, const awv_range_pa
 /* awv_verify_cigars on ranges: results[i] claims that its op bytes align ranges[i] end to end over the two intervals. */
 int awv_verify_ranges(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const awv_result* results,
                       const uint8_t* cigar_arena, uint64_t arena_bytes, awv_verify_result* vout /* required */);
+
+/* ---- full alignments under a penalty bound ------------------------------------------------------------------------------
+ * awv_align_pairs with a bound per pair: max_penalty[i] >= 0 bounds pair i, max_penalty[i] < 0 leaves it unbounded.  A pair
+ * whose penalty is proved above its bound is abandoned inside its top-level breakpoint search -- no sub-problem is searched,
+ * no CIGAR is written -- and comes back AWV_ST_ABOVE_BOUND with penalty max_penalty[i] + 1, cigar_len 0, all four counts and
+ * q_end / t_end 0.  The bound confines the top-level search only: every sub-problem runs as in awv_align_pairs.
+ * The contract:
+ *   - for every pair, status and penalty are what awv_score_pairs_bounded reports under the same bounds;
+ *   - for every AWV_ST_COMPLETED pair, the whole record and the op bytes are awv_align_pairs's, byte for byte.
+ * vout (nullable): non-null gives awv_align_pairs_verified's check; an AWV_ST_ABOVE_BOUND record verifies as AWV_VF_SKIPPED.
+ * Arena slots, batching, sinks and stats are awv_align_pairs's. */
+int awv_align_pairs_bounded(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
+                            const int32_t* max_penalty /* per pair, required; < 0: none */, awv_result* out,
+                            awv_verify_result* vout /* nullable */, awv_sink sink, void* user);
+/* The same on ranges; max_penalty == NULL: no bound for any range (as in awv_score_ranges). */
+int awv_align_ranges_bounded(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n,
+                             const int32_t* max_penalty /* per range, nullable; < 0: none */, awv_result* out,
+                             awv_verify_result* vout /* nullable */, awv_sink sink, void* user);
+/* The penalty bound that no alignment of divergence <= d can exceed, on the host (needs no device).  Divergence of an
+ * alignment = E / columns, E = #X + #I + #D, columns = #M + #X + #I + #D.  From columns = plen + #I = tlen + #D follows
+ * E <= d (plen + tlen) / (2 - d), and every edit column costs at most cmax (as above: max(x, o1 + e1), 2-piece:
+ * max(x, min(o1 + e1, o2 + e2))), so
+ *     B = cmax * (floor(d (plen + tlen) / (2 - d)) + 1)
+ * (the + 1 absorbs floating-point rounding; an exact filter on the counts follows anyway).  A penalty above B proves that no
+ * alignment of the pair, optimal or not, has divergence <= d.  Returns -1 ("no bound") when d >= 1 or B would pass
+ * INT32_MAX; INT32_MIN for d < 0, NaN, negative lengths or bad penalties. */
+int32_t awv_divergence_bound(const awv_penalties* pen, int32_t plen, int32_t tlen, double d);
 
 /* ---- device pair planning (csrc/planner.hip) -------------------------------------------------------------------------
  * Integer work over the engine's resident sequence set, on its device and stream; results equal the host planner's
