@@ -9,6 +9,7 @@
 // awvx:: sixteen waves per pair (one pair per CU: the few pairs a large length difference makes enormous)
 #include "planner_device.hpp"  // (the sketches and scratch of device pair planning, planner.hip)
 #include "verify_device.hpp"   // (the per-batch check of awv_align_pairs_verified, verify.hip)
+#include "clip_device.hpp"     // (the per-batch clip of awv_align_pairs_clipped, clip.hip)
 #include "kernels_awv.hpp"  // (the awv:: kernels themselves are instantiated in kernels_awv.hip -- here only the types)
 #define AWV_NS awv
 #define AWV_WG 64
@@ -163,6 +164,7 @@ struct awv_engine {
   awv_stats stats{};
   awp::PlanState* plan = nullptr;  // planner.hip: sketches of `seqs` and planning scratch (released with a new set)
   awvf::State* verify = nullptr;   // verify.hip: buffers and stats of the verify launches
+  awvc::State* clip = nullptr;     // clip.hip: buffers and stats of the clip launches
 };
 
 namespace {
@@ -327,9 +329,12 @@ long long worst_case_penalty(const awv::DevPenalties& d, long long n) {
 // on the device before the batch's CIGARs are copied back
 // spans (nullable; the awv_*_ranges calls): pair i aligns the rectangle spans[i] of its two sequences, in pattern / text
 // coordinates and already validated, instead of the whole of them -- every length below is then the rectangle's
+// cout (nullable; awv_align_pairs_clipped): every batch's op strings are clipped on the device under match_bonus, after the
+// check and before the batch's CIGARs are copied back
 int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
                awv_result* out, awv_sink sink, void* user, bool score_only = false, int max_penalty = INT_MAX,
-               const int32_t* pair_bound = nullptr, awv_verify_result* vout = nullptr, const awvr::Span* spans = nullptr) {
+               const int32_t* pair_bound = nullptr, awv_verify_result* vout = nullptr, const awvr::Span* spans = nullptr,
+               awv_clip_result* cout = nullptr, int32_t match_bonus = 0) {
   using namespace awv;
   if (npairs < 0 || (npairs > 0 && !pairs)) return fail(AWV_ERR_ARG, "align_pairs: null pairs");
   DevPenalties dp{};
@@ -893,6 +898,10 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       if (int rc = awvf::verify_batch(e, pen, pairs + first, n, hres.data(), e->d_cigar.p, arena, vout + first, spans ? spans + first : nullptr)) return rc;
       lap("batch verified");
     }
+    if (cout) {
+      if (int rc = awvc::clip_batch(e, pen, match_bonus, n, hres.data(), e->d_cigar.p, arena, cout + first)) return rc;
+      lap("batch clipped");
+    }
     if (want_cigar) {
       e->h_cigar.resize((size_t)arena + 64);
       lap("host cigar buffer");
@@ -1008,6 +1017,8 @@ void awv_engine_destroy(awv_engine* e) {
   e->plan = nullptr;
   awvf::state_release(e->verify);
   e->verify = nullptr;
+  awvc::state_release(e->clip);
+  e->clip = nullptr;
   e->seqs.release();
   e->ring_mem.release();
   e->hist_mem.release();
@@ -1122,7 +1133,8 @@ int split_ranges(const SeqSet& s, const awv_range_pair* ranges, int64_t n, std::
   return AWV_OK;
 }
 int align_ranges_core(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, awv_result* out,
-                      awv_verify_result* vout, awv_sink sink, void* user, const int32_t* max_penalty = nullptr) {
+                      awv_verify_result* vout, awv_sink sink, void* user, const int32_t* max_penalty = nullptr,
+                      awv_clip_result* cout = nullptr, int32_t match_bonus = 0) {
   if (n < 0 || (n > 0 && !ranges)) return fail(AWV_ERR_ARG, "align_ranges: null ranges");
   if (e->seqs.n == 0 && n > 0) return fail(AWV_ERR_STATE, "align_ranges before set_sequences");
   std::vector<awv_pair> pairs;
@@ -1135,9 +1147,42 @@ int align_ranges_core(awv_engine* e, const awv_penalties* pen, const awv_range_p
     pb.resize((size_t)n);
     for (int64_t i = 0; i < n; ++i) pb[(size_t)i] = norm_bound(max_penalty[i]);
   }
-  return align_core(e, e->seqs, pen, pairs.data(), n, out, sink, user, false, INT_MAX, max_penalty ? pb.data() : nullptr, vout, spans.data());
+  return align_core(e, e->seqs, pen, pairs.data(), n, out, sink, user, false, INT_MAX, max_penalty ? pb.data() : nullptr, vout, spans.data(),
+                    cout, match_bonus);
+}
+// what every clipping call refuses before anything is launched
+int check_clip_args(const awv_clip_result* cout, int32_t match_bonus) {
+  if (!cout) return fail(AWV_ERR_ARG, "align_clipped: null cout");
+  if (match_bonus < 1 || match_bonus > AWV_CLIP_MAX_BONUS) return fail(AWV_ERR_ARG, "align_clipped: match_bonus must be in [1, 32767]");
+  return AWV_OK;
 }
 }  // namespace
+
+int awv_align_pairs_clipped(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const int32_t* max_penalty,
+                            int32_t match_bonus, awv_result* out, awv_verify_result* vout, awv_clip_result* cout, awv_sink sink, void* user) {
+  if (!e) return fail(AWV_ERR_ARG, "null engine");
+  if (int rc = check_clip_args(cout, match_bonus)) return rc;
+  if (e->seqs.n == 0 && npairs > 0) return fail(AWV_ERR_STATE, "align_pairs before set_sequences");
+  if (vout) awvf::stats_reset(e->verify);
+  awvc::stats_reset(e->clip);
+  AWV_GUARDED(
+    std::vector<int32_t> pb;
+    if (max_penalty) {
+      pb.resize((size_t)std::max<int64_t>(npairs, 0));
+      for (int64_t i = 0; i < npairs; ++i) pb[(size_t)i] = norm_bound(max_penalty[i]);
+    }
+    return align_core(e, e->seqs, pen, pairs, npairs, out, sink, user, false, INT_MAX, max_penalty && npairs > 0 ? pb.data() : nullptr, vout,
+                      nullptr, cout, match_bonus);
+  )
+}
+
+int awv_align_ranges_clipped(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const int32_t* max_penalty,
+                             int32_t match_bonus, awv_result* out, awv_verify_result* vout, awv_clip_result* cout, awv_sink sink, void* user) {
+  if (!e) return fail(AWV_ERR_ARG, "null engine");
+  if (int rc = check_clip_args(cout, match_bonus)) return rc;
+  awvc::stats_reset(e->clip);
+  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, out, vout, sink, user, max_penalty, cout, match_bonus);)
+}
 
 int awv_align_pairs_bounded(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const int32_t* max_penalty,
                             awv_result* out, awv_verify_result* vout, awv_sink sink, void* user) {
@@ -1269,8 +1314,7 @@ int awv_engine_stats(const awv_engine* e, awv_stats* out) {
 }  // extern "C"
 
 // ---- what planner.hip reads of an engine (planner_device.hpp) ----
-int awv_internal_view(awv_engine* e, awp::EngineView* v) {
-  if (!e || !v) return fail(AWV_ERR_ARG, "null engine");
+void awv_internal_device_view(awv_engine* e, awp::EngineView* v) {
   v->device = e->device;
   v->stream = e->stream;
   v->n = e->seqs.n;
@@ -1279,12 +1323,17 @@ int awv_internal_view(awv_engine* e, awp::EngineView* v) {
   v->off = e->seqs.d_off.p;
   v->len = e->seqs.d_len.p;
   v->len_host = e->seqs.len.data();
+}
+int awv_internal_view(awv_engine* e, awp::EngineView* v) {
+  if (!e || !v) return fail(AWV_ERR_ARG, "null engine");
+  awv_internal_device_view(e, v);
   if (e->seqs.n == 0) return fail(AWV_ERR_STATE, "no sequence set: call awv_engine_set_sequences first");
   return AWV_OK;
 }
 awp::PlanState*& awv_internal_plan(awv_engine* e) { return e->plan; }
 // ---- what verify.hip keeps in an engine, and the arena budget awv_verify_cigars splits its call by (verify_device.hpp) ----
 awvf::State*& awv_internal_verify(awv_engine* e) { return e->verify; }
+awvc::State*& awv_internal_clip(awv_engine* e) { return e->clip; }
 uint64_t awv_internal_max_arena(const awv_engine* e) { return e->cfg.max_arena_bytes > 0 ? (uint64_t)e->cfg.max_arena_bytes : (uint64_t)8 << 30; }
 int awv_internal_fail(int code, const std::string& msg) { return fail(code, msg); }
 int awv_internal_check_penalties(const awv_penalties* pen) { return check_penalty_signs(pen); }

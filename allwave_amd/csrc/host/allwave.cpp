@@ -303,7 +303,25 @@ AlignmentResult range_alignment_result(const AlignmentRange& g, const awv_result
   return a;
 }
 
-AlignmentResult AllPairIterator::result_at(size_t k, bool is_rev, const awv_result& r, const uint8_t* arena, bool copy_cigar) const {
+AlignmentResult AllPairIterator::result_at(size_t k, bool is_rev, const awv_result& r, const uint8_t* arena, bool copy_cigar,
+                                           const awv_clip_result* cl) const {
+  if (cl && cl->code == AWV_CL_OK && r.status == AWV_ST_COMPLETED) {  // r describes the segment: q_end / t_end are the bases it consumes
+    const size_t qi = pairs_[k].first, ti = pairs_[k].second;
+    const size_t qb = ranges_ ? (*ranges_)[k].query_start : 0, qe = ranges_ ? (*ranges_)[k].query_end : sequences_[qi].seq.size();
+    const size_t tb = ranges_ ? (*ranges_)[k].target_start : 0;
+    AlignmentResult a = make_result(qi, ti, ranges_ ? (*ranges_)[k].is_reverse : is_rev, r, arena, copy_cigar);
+    const size_t q_len = a.query_end, t_len = a.target_end;
+    if (a.is_reverse) {
+      a.query_end = qe - (size_t)cl->q_skip;
+      a.query_start = a.query_end - q_len;
+    } else {
+      a.query_start = qb + (size_t)cl->q_skip;
+      a.query_end = a.query_start + q_len;
+    }
+    a.target_start = tb + (size_t)cl->t_skip;
+    a.target_end = a.target_start + t_len;
+    return a;
+  }
   if (ranges_) return range_alignment_result((*ranges_)[k], r, arena, copy_cigar);
   return make_result(pairs_[k].first, pairs_[k].second, is_rev, r, arena, copy_cigar);
 }
@@ -345,6 +363,21 @@ void align_ranges(const std::vector<Sequence>& sequences, const std::vector<Alig
   if (failures) *failures = it.verify_failures();
   if (verify_stats) *verify_stats = it.last_verify_stats();
   if (bound_stats) *bound_stats = it.last_bound_stats();
+}
+
+void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
+                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
+                  awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
+                  BoundStats* bound_stats, int clip_match_bonus, int64_t clip_min_score, ClipStats* clip_stats) {
+  AllPairIterator it = AllPairIterator::for_ranges(sequences, ranges, std::move(params));
+  it.with_devices(devices).with_verify(verify).with_clip(clip_match_bonus, clip_min_score);
+  if (max_penalty) it.with_max_penalty(*max_penalty);
+  if (max_divergence) it.with_max_divergence(*max_divergence);
+  it.for_each_with_callback(callback);
+  if (failures) *failures = it.verify_failures();
+  if (verify_stats) *verify_stats = it.last_verify_stats();
+  if (bound_stats) *bound_stats = it.last_bound_stats();
+  if (clip_stats) *clip_stats = it.last_clip_stats();
 }
 
 AllPairIterator::AllPairIterator(const std::vector<Sequence>& sequences, AlignmentParams params)
@@ -502,9 +535,18 @@ AllPairIterator AllPairIterator::with_sparsification(SparsificationStrategy stra
   it.verify_ = verify_;
   it.max_penalty_ = max_penalty_;
   it.max_divergence_ = max_divergence_;
+  it.clip_bonus_ = clip_bonus_;
+  it.clip_min_score_ = clip_min_score_;
   return it;
 }
 AllPairIterator& AllPairIterator::with_verify(bool on) { verify_ = on; return *this; }
+AllPairIterator& AllPairIterator::with_clip(int match_bonus, int64_t min_score) {
+  if (match_bonus < 1 || match_bonus > AWV_CLIP_MAX_BONUS) throw std::invalid_argument("with_clip: match_bonus must be in [1, 32767]");
+  if (min_score < 1) throw std::invalid_argument("with_clip: min_score must be >= 1");
+  clip_bonus_ = match_bonus;
+  clip_min_score_ = min_score;
+  return *this;
+}
 AllPairIterator& AllPairIterator::with_max_penalty(int max_penalty) {
   if (max_penalty < 0) throw std::invalid_argument("with_max_penalty: max_penalty must be >= 0");
   max_penalty_ = max_penalty;
@@ -528,11 +570,11 @@ std::optional<AlignmentResult> AllPairIterator::next() {  // iterator.rs:151-171
     run(first, cnt, [&](const Batch& b) {  // (every entry has its own slot of buf: no lock)
       for (int64_t i = 0; i < b.n; ++i) {
         const size_t k = b.pair(i);
-        buf[k] = result_at(first + k, b.is_rev(i), b.res[i], b.arena, true);
+        buf[k] = result_at(first + k, b.is_rev(i), b.res[i], b.arena, true, b.clip_at(i));
         have[k] = 1;
       }
     });
-    if (bounded()) {
+    if (drops_pairs()) {
       size_t w = 0;
       for (size_t k = 0; k < cnt; ++k)
         if (have[k]) {
@@ -567,7 +609,7 @@ void AllPairParallelIterator::for_each_with_callback(const Callback& cb) {
         const int64_t i = cursor.fetch_add(1);
         if (i >= cnt || stop.load()) return;
         try {
-          cb(it_.result_at(b.pair(i), b.is_rev(i), b.res[i], b.arena, true));
+          cb(it_.result_at(b.pair(i), b.is_rev(i), b.res[i], b.arena, true, b.clip_at(i)));
         } catch (...) {
           std::lock_guard<std::mutex> g(mu);
           if (!err) err = std::current_exception();
@@ -591,11 +633,11 @@ std::vector<AlignmentResult> AllPairParallelIterator::collect() {
   it_.run([&](const AllPairIterator::Batch& b) {  // (every pair has its own slot of `out`: no lock)
     for (int64_t i = 0; i < b.n; ++i) {
       const size_t k = b.pair(i);
-      out[k] = it_.result_at(k, b.is_rev(i), b.res[i], b.arena, true);
+      out[k] = it_.result_at(k, b.is_rev(i), b.res[i], b.arena, true, b.clip_at(i));
       have[k] = 1;
     }
   });
-  if (it_.bounded()) {  // (pairs above a bound are not delivered: the kept ones, in pair-list order)
+  if (it_.drops_pairs()) {  // (pairs above a bound or without a clip are not delivered: the kept ones, in pair-list order)
     size_t w = 0;
     for (size_t k = 0; k < out.size(); ++k)
       if (have[k]) {
@@ -661,8 +703,13 @@ void add_stats(awv_stats& acc, const awv_stats& x, bool same_engine) {
 // max_penalty (< 0: no bound) with its results handed to the sink in one call (status and penalty, no arena)
 // rp (nullable): the batch is these n interval pairs -- the same three calls on ranges, `ap` is not read
 // bounds (nullable, alignment calls only): one penalty bound per entry (< 0: none) -- the *_bounded entry points
+// cout (nullable, alignment calls only): the *_clipped entry points under clip_bonus, which take bounds and vout as well
 int engine_call(awv_engine* e, bool score_only, int32_t max_penalty, const awv_penalties& pen, const awv_pair* ap, int64_t n,
-                awv_sink sink, void* user, awv_verify_result* vout, const awv_range_pair* rp = nullptr, const int32_t* align_bounds = nullptr) {
+                awv_sink sink, void* user, awv_verify_result* vout, const awv_range_pair* rp = nullptr, const int32_t* align_bounds = nullptr,
+                int clip_bonus = 0, awv_clip_result* cout = nullptr) {
+  if (cout && !score_only)
+    return rp ? awv_align_ranges_clipped(e, &pen, rp, n, align_bounds, clip_bonus, nullptr, vout, cout, sink, user)
+              : awv_align_pairs_clipped(e, &pen, ap, n, align_bounds, clip_bonus, nullptr, vout, cout, sink, user);
   if (align_bounds && !score_only)
     return rp ? awv_align_ranges_bounded(e, &pen, rp, n, align_bounds, nullptr, vout, sink, user)
               : awv_align_pairs_bounded(e, &pen, ap, n, align_bounds, nullptr, vout, sink, user);
@@ -746,6 +793,8 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   const std::optional<double> div = divergence_bound();
   if (bounded_run && div && !(*div >= 0.0 && *div < 1.0)) throw std::invalid_argument("max_divergence: need 0 <= max_divergence < 1");
   std::vector<BoundStats> bst(S);  // per slot: written by its sink calls (which never overlap) and its submitter thread
+  const bool clipping = clip() && !call.score_only;
+  std::vector<ClipStats> cst(S);   // likewise
   auto worker = [&](size_t s) {
     awv_engine* e = nullptr;
     try {
@@ -794,7 +843,10 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
           const uint8_t* by_div;  // bounded runs: per entry, whether its penalty bound is the one derived from the divergence
           double div;             // the divergence bound (< 0: none)
           BoundStats* bst;
-        } ctx{&batch_cb, rev.data(), idx, &stop, &fail_fn, false, nullptr, -1.0, nullptr};
+          const awv_clip_result* clip;  // clipping runs: per entry of the call, filled before the entry's sink call
+          int64_t clip_min_score;
+          ClipStats* cst;
+        } ctx{&batch_cb, rev.data(), idx, &stop, &fail_fn, false, nullptr, -1.0, nullptr, nullptr, 1, nullptr};
         // one penalty bound per entry: the smaller of with_max_penalty's and the one the divergence bound implies
         std::vector<int32_t> bounds;
         std::vector<uint8_t> by_div;
@@ -822,17 +874,18 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
           Ctx* c = (Ctx*)user;
           if (c->stop->load()) return 1;  // another slot failed: stop here, report nothing
           try {
-            if (c->bst) {  // a bounded run: the batch callback sees the kept entries only
+            if (c->bst || c->clip) {  // a bounded or clipping run: the batch callback sees the kept entries only
               std::vector<awv_result> kres;
               std::vector<uint8_t> krev;
               std::vector<size_t> kidx;
+              std::vector<awv_clip_result> kclip;
               for (int64_t i = 0; i < cnt; ++i) {
                 const awv_result& r = res[i];
-                if (r.status == AWV_ST_ABOVE_BOUND) {
+                if (c->bst && r.status == AWV_ST_ABOVE_BOUND) {
                   ++(c->by_div[first + i] ? c->bst->above_divergence : c->bst->above_penalty);
                   continue;
                 }
-                if (r.status == AWV_ST_COMPLETED && c->div >= 0.0) {  // the exact filter, on the record's counts
+                if (c->bst && r.status == AWV_ST_COMPLETED && c->div >= 0.0) {  // the exact filter, on the record's counts
                   const double edits = (double)r.num_mismatches + (double)r.num_ins + (double)r.num_del;
                   if (!(edits <= c->div * (edits + (double)r.num_matches))) {
                     ++c->bst->above_divergence;
@@ -840,10 +893,33 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
                   }
                 }
                 kres.push_back(r);
+                if (c->clip) {  // a finished pair is delivered as its segment (a failed one as it is: the "empty" result)
+                  const awv_clip_result& cl = c->clip[first + i];
+                  if (r.status == AWV_ST_COMPLETED) {
+                    ++c->cst->pairs;
+                    if (cl.code != AWV_CL_OK || cl.score < c->clip_min_score) {
+                      ++(cl.code != AWV_CL_OK ? c->cst->empty : c->cst->below_min_score);
+                      kres.pop_back();
+                      continue;
+                    }
+                    awv_result& s = kres.back();
+                    s.cigar_off += cl.col_beg;
+                    s.cigar_len = cl.col_end - cl.col_beg;
+                    s.num_matches = cl.num_matches;
+                    s.num_mismatches = cl.num_mismatches;
+                    s.num_ins = cl.num_ins;
+                    s.num_del = cl.num_del;
+                    s.penalty = cl.penalty;
+                    s.score = -cl.penalty;
+                    s.q_end = cl.num_matches + cl.num_mismatches + cl.num_del;
+                    s.t_end = cl.num_matches + cl.num_mismatches + cl.num_ins;
+                  }
+                  kclip.push_back(cl);
+                }
                 krev.push_back(c->rev[first + i]);
                 kidx.push_back(c->idx ? c->idx[first + i] : (size_t)(first + i));
               }
-              (*c->cb)(Batch{0, (int64_t)kres.size(), kres.data(), arena, krev.data(), kidx.data()});
+              (*c->cb)(Batch{0, (int64_t)kres.size(), kres.data(), arena, krev.data(), kidx.data(), c->clip ? kclip.data() : nullptr});
               return 0;
             }
             (*c->cb)(Batch{first, cnt, res, arena, c->rev, c->idx});
@@ -855,8 +931,15 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
           return 0;
         };
         std::vector<awv_verify_result> vr(verify ? (size_t)m : 0);
+        std::vector<awv_clip_result> cr(clipping ? (size_t)std::max<int64_t>(m, 1) : 0);
+        if (clipping) {
+          ctx.clip = cr.data();
+          ctx.clip_min_score = clip_min_score_;
+          ctx.cst = &cst[s];
+        }
         const int rc = engine_call(e, call.score_only, call.max_penalty, pen, ap.data(), m, sink, &ctx, verify ? vr.data() : nullptr,
-                                   ranges_ ? rp.data() : nullptr, bounded_run ? bounds.data() : call.align_bounds);
+                                   ranges_ ? rp.data() : nullptr, bounded_run ? bounds.data() : call.align_bounds, clip_bonus_,
+                                   clipping ? cr.data() : nullptr);
         lap("aligned + sunk");
         awv_stats x{};
         awv_engine_stats(e, &x);
@@ -869,6 +952,11 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
           vst[s].failed += vx.failed;
           vst[s].columns += vx.columns;
           append_verify_failures(vfail[s], vr.data(), m, first, idx, plist, rev.data());
+        }
+        if (clipping && rc == AWV_OK) {
+          awv_clip_stats cx{};
+          awv_engine_clip_stats(e, &cx);
+          cst[s].kernel_ms += cx.kernel_ms;
         }
         if (ctx.failed) return;  // (the error is already recorded)
         if (rc != AWV_OK) {
@@ -899,8 +987,13 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
     verify_failures_.clear();
     verify_stats_ = awv_verify_stats{};
     bound_stats_ = BoundStats{};
+    clip_stats_ = ClipStats{};
   }
   for (size_t s = 0; s < S; ++s) {
+    clip_stats_.pairs += cst[s].pairs;
+    clip_stats_.empty += cst[s].empty;
+    clip_stats_.below_min_score += cst[s].below_min_score;
+    clip_stats_.kernel_ms += cst[s].kernel_ms;
     bound_stats_.pairs += bst[s].pairs;
     bound_stats_.above_penalty += bst[s].above_penalty;
     bound_stats_.above_divergence += bst[s].above_divergence;
@@ -923,7 +1016,7 @@ void AllPairIterator::for_each_with_callback(const Callback& cb) {
     std::lock_guard<std::mutex> g(mu);
     if (first) std::rethrow_exception(first);
     try {
-      for (int64_t i = 0; i < b.n; ++i) cb(result_at(b.pair(i), b.is_rev(i), b.res[i], b.arena, true));
+      for (int64_t i = 0; i < b.n; ++i) cb(result_at(b.pair(i), b.is_rev(i), b.res[i], b.arena, true, b.clip_at(i)));
     } catch (...) {
       first = std::current_exception();
       throw;
@@ -950,7 +1043,7 @@ void AllPairIterator::for_each_paf_batch(const std::function<void(const std::str
         std::string& out = parts[(size_t)t];
         out.reserve((size_t)(hi - lo) * 4096);
         for (int64_t i = lo; i < hi; ++i) {
-          const AlignmentResult a = result_at(b.pair(i), b.is_rev(i), res[i], arena, false);
+          const AlignmentResult a = result_at(b.pair(i), b.is_rev(i), res[i], arena, false, b.clip_at(i));
           const bool ok = res[i].status == AWV_ST_COMPLETED;
           append_paf(out, a, ok ? arena + res[i].cigar_off : nullptr, ok ? res[i].cigar_len : 0, sequences_);
           out.push_back('\n');

@@ -9,7 +9,8 @@
 //   cigar_bytes_to_string, reverse_complement, align_pair's result mapping       src/alignment.rs:25-66,178-190,347-376
 //   AllPairIterator (-p none enumeration, WFA orientation, callback streaming)   src/iterator.rs:12-253
 //   wfa::align_sequences / validate_cigar_alignment                              src/wfa.rs:105-258
-// This build's own: on-device verification of the alignments a run produces (with_verify) and of a PAF file (check_paf).
+// This build's own: on-device verification of the alignments a run produces (with_verify) and of a PAF file (check_paf);
+// alignments clipped to their best-scoring segment on the device (with_clip).
 // Pair planning (mash orientation, sparsifiers, kNN/tree pairs) lives in planner.hpp; the CLI in main.cpp.
 #pragma once
 
@@ -100,6 +101,13 @@ struct PairScore {
 // bound (abandoned by the penalty bound derived from it, or completed and filtered on the record's counts).
 struct BoundStats {
   uint64_t pairs = 0, above_penalty = 0, above_divergence = 0;
+};
+
+// What clipping did to a run (AllPairIterator::with_clip): finished pairs whose op string was clipped, and of them the ones
+// that reached no consumer because the clip is empty, or scores below min_score; kernel_ms: summed clip kernel time.
+struct ClipStats {
+  uint64_t pairs = 0, empty = 0, below_min_score = 0;
+  double kernel_ms = 0.0;
 };
 
 using Callback = std::function<void(AlignmentResult&&)>;  // may throw: first error aborts the run
@@ -197,6 +205,22 @@ class AllPairIterator {  // iterator.rs:12-171
   //   searched under awv_divergence_bound(pen, plen, tlen, d) (a range: its rectangle's lengths), and a completed pair is
   //   kept iff (double)E <= d * (double)columns on its record's counts.  AlignmentParams::max_divergence of the alignment
   //   params means the same; the setter wins.  With both bounds the smaller penalty bound applies.
+  // Every alignment consumer receives each alignment clipped to its best-scoring segment (awv_align_pairs_clipped /
+  // awv_align_ranges_clipped; include/allwave_hip.h has the contract): cigar_bytes is the slice, num_matches,
+  // alignment_length and score (= -penalty, the segment re-scored) are the segment's.  A pair whose clip is empty or scores
+  // below min_score reaches no consumer, like a pair above a bound; a failed pair still gives the "empty" result.
+  // Coordinates follow PAF.  With [qb, qe) the query's range (the whole sequence on a pair list), tb the target range's
+  // start, q_skip / t_skip the bases before the segment and q_len / t_len the bases it consumes:
+  //   forward:  query_start = qb + q_skip, query_end = query_start + q_len
+  //   reverse:  query_end = qe - q_skip, query_start = query_end - q_len     (on the query's FORWARD strand)
+  //   target_start = tb + t_skip, target_end = target_start + t_len
+  // so a clipped '-' line of a whole-sequence pair carries forward-strand query coordinates -- the convention check_paf's
+  // `partial` and parse_paf_ranges read.  The full alignment is what with_verify checks and what the bounds filter on, as
+  // without clipping; scores() ignores the setting.  1 <= match_bonus <= 32767, min_score >= 1.
+  AllPairIterator& with_clip(int match_bonus, int64_t min_score = 1);
+  bool clip() const { return clip_bonus_ > 0; }
+  // of the last run (next(): of the chunks since the list's start), summed over the slots
+  ClipStats last_clip_stats() const { return clip_stats_; }
   AllPairIterator& with_max_penalty(int max_penalty);
   AllPairIterator& with_max_divergence(double max_divergence);
   // of the last run (next(): of the chunks since the list's start), summed over the slots
@@ -246,7 +270,9 @@ class AllPairIterator {  // iterator.rs:12-171
     const uint8_t* arena;
     const uint8_t* rev;  // per entry of the call's pair array
     const size_t* idx;   // pair-list index per entry; nullptr: the entry's own position
+    const awv_clip_result* clip = nullptr;  // a clipping run: per entry its clip; res[] then describes the segment
     size_t pair(int64_t i) const { return idx ? idx[first + i] : (size_t)(first + i); }
+    const awv_clip_result* clip_at(int64_t i) const { return clip ? clip + first + i : nullptr; }
     bool is_rev(int64_t i) const { return rev[first + i] != 0; }
   };
   using BatchCb = std::function<void(const Batch&)>;
@@ -266,7 +292,9 @@ class AllPairIterator {  // iterator.rs:12-171
   void run(size_t first, size_t count, const BatchCb& batch_cb, EngineCall call = {false, -1, nullptr});
   void run(const BatchCb& batch_cb, EngineCall call = {false, -1, nullptr}) { run(0, pairs_.size(), batch_cb, call); }
   // align_pair's result mapping for entry k of the pair list (a range list: in the range's coordinates)
-  AlignmentResult result_at(size_t k, bool is_rev, const awv_result& r, const uint8_t* arena, bool copy_cigar) const;
+  // cl (nullable): the entry's clip, r the segment's record -- the coordinates are shifted by the skips (with_clip)
+  AlignmentResult result_at(size_t k, bool is_rev, const awv_result& r, const uint8_t* arena, bool copy_cigar,
+                            const awv_clip_result* cl = nullptr) const;
   std::shared_ptr<const std::vector<AlignmentRange>> ranges_;  // for_ranges: entry k of pairs_ is this interval pair
   AllPairIterator(const std::vector<Sequence>& sequences, AlignmentParams params, bool enumerate);  // enumerate = false: no pairs
   const std::vector<Sequence>& sequences_;
@@ -280,6 +308,10 @@ class AllPairIterator {  // iterator.rs:12-171
   std::optional<double> max_divergence_;
   std::optional<double> divergence_bound() const { return max_divergence_ ? max_divergence_ : params_.max_divergence; }
   bool bounded() const { return max_penalty_.has_value() || divergence_bound().has_value(); }
+  int clip_bonus_ = 0;  // with_clip (0: off)
+  int64_t clip_min_score_ = 1;
+  ClipStats clip_stats_{};
+  bool drops_pairs() const { return bounded() || clip(); }  // consumers that keep a slot per pair compact what was delivered
   BoundStats bound_stats_{};
   std::vector<VerifyFailure> verify_failures_;
   awv_verify_stats verify_stats_{};
@@ -310,6 +342,7 @@ class AllPairParallelIterator {
   const std::vector<VerifyFailure>& verify_failures() const { return it_.verify_failures(); }
   awv_verify_stats last_verify_stats() const { return it_.last_verify_stats(); }
   BoundStats last_bound_stats() const { return it_.last_bound_stats(); }
+  ClipStats last_clip_stats() const { return it_.last_clip_stats(); }
  private:
   friend class AllPairIterator;
   explicit AllPairParallelIterator(const AllPairIterator& it) : it_(it) {}
@@ -343,6 +376,11 @@ void align_ranges(const std::vector<Sequence>& sequences, const std::vector<Alig
                   const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
                   awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
                   BoundStats* bound_stats = nullptr);
+// the same with every alignment clipped (AllPairIterator::with_clip); clip_stats (nullable) receives what clipping did
+void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
+                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
+                  awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
+                  BoundStats* bound_stats, int clip_match_bonus, int64_t clip_min_score, ClipStats* clip_stats = nullptr);
 
 // ---- mappings in, alignments out: the interval pairs a PAF file names (columns 1-9 of each line) ----
 struct PafRangeLine {

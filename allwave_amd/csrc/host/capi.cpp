@@ -26,25 +26,43 @@ void keep_verify(const awv_verify_stats& st, const std::vector<VerifyFailure>& f
   g_verify_failures = f;
 }
 
+// The options of one run (RunOptions).
 // Bounds on the final alignments: awh_set_bounds leaves them here, per calling thread, for the NEXT alignment hook of that
 // thread, which takes them (they hold for that one call) and leaves its last_bound_stats() for awh_last_bounds.
 thread_local int64_t g_next_max_penalty = -1;
 thread_local double g_next_max_divergence = -1.0;
 thread_local BoundStats g_bound_stats{};
-struct Bounds {
+// Clipping travels the same way: awh_set_clip leaves the match bonus (0: off) and the least score for the NEXT alignment hook
+// of the calling thread, which leaves its last_clip_stats() for awh_last_clip.
+thread_local int g_next_clip_bonus = 0;
+thread_local int64_t g_next_clip_min_score = 1;
+thread_local ClipStats g_clip_stats{};
+struct RunOptions {
   int64_t max_penalty;
   double max_divergence;
+  int clip_bonus;
+  int64_t clip_min_score;
   void apply(AllPairIterator& it) const {
     if (max_penalty >= 0) it.with_max_penalty((int)std::min<int64_t>(max_penalty, INT32_MAX));
     if (max_divergence >= 0.0) it.with_max_divergence(max_divergence);
+    if (clip_bonus != 0) it.with_clip(clip_bonus, clip_min_score);
   }
-  bool any() const { return max_penalty >= 0 || max_divergence >= 0.0; }
+  bool any() const { return max_penalty >= 0 || max_divergence >= 0.0 || clip_bonus != 0; }
 };
-Bounds take_bounds() {
-  const Bounds b{g_next_max_penalty, g_next_max_divergence};
+// what an alignment hook leaves behind of its iterator's bound and clip counters (awh_last_bounds, awh_last_clip)
+template <typename It>
+void keep_stats(const It& it) {
+  g_bound_stats = it.last_bound_stats();
+  g_clip_stats = it.last_clip_stats();
+}
+RunOptions take_run_options() {
+  const RunOptions b{g_next_max_penalty, g_next_max_divergence, g_next_clip_bonus, g_next_clip_min_score};
   g_next_max_penalty = -1;
   g_next_max_divergence = -1.0;
+  g_next_clip_bonus = 0;
+  g_next_clip_min_score = 1;
   g_bound_stats = BoundStats{};
+  g_clip_stats = ClipStats{};
   return b;
 }
 
@@ -120,7 +138,7 @@ int awh_all_pairs_paf_devices(int n, const char* const* ids, const uint8_t* byte
                               const char* sparsification, int orientation, int exclude_self, const int32_t* devices, int n_devices,
                               int64_t min_batch_pairs, int verify, awv_stats* slot_stats, char** out, size_t* out_len, char* err,
                               size_t cap) {
-  const Bounds bounds = take_bounds();
+  const RunOptions opts = take_run_options();
   try {
     const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
     AllPairIterator it = AllPairIterator::with_options(seqs, parse_scores(scores), exclude_self != 0, orientation == 2,
@@ -131,14 +149,14 @@ int awh_all_pairs_paf_devices(int n, const char* const* ids, const uint8_t* byte
     it.with_devices(std::vector<int>(devices, devices + n_devices));
     if (min_batch_pairs > 0) it.with_min_batch_pairs((size_t)min_batch_pairs);
     it.with_verify(verify != 0);
-    bounds.apply(it);
+    opts.apply(it);
     std::string all;
     it.for_each_with_callback([&](AlignmentResult&& r) {  // the reference's own per-record path
       all += alignment_to_paf(r, seqs);
       all.push_back('\n');
     });
     keep_verify(it.last_verify_stats(), it.verify_failures());
-    g_bound_stats = it.last_bound_stats();
+    keep_stats(it);
     if (slot_stats) for (int k = 0; k < n_devices; ++k) slot_stats[k] = it.last_slot_stats()[(size_t)k];
     *out = (char*)malloc(all.size() + 1);
     memcpy(*out, all.c_str(), all.size() + 1);
@@ -166,7 +184,7 @@ int awh_iterate_devices(int n, const char* const* ids, const uint8_t* bytes, con
                         const int32_t* devices, int n_devices, int64_t min_batch_pairs, int64_t shard_rank, int64_t shard_world,
                         int verify_on, awv_stats* slot_stats, char** out, size_t* out_len, size_t* n_records, size_t* late_calls,
                         char* err, size_t cap) {
-  const Bounds bounds = take_bounds();
+  const RunOptions opts = take_run_options();
   if (!devices || n_devices < 1) { set_err(err, cap, "awh_iterate_devices: empty device list"); return -1; }
   size_t seen = 0, late = 0;
   bool thrown = false;
@@ -192,17 +210,17 @@ int awh_iterate_devices(int n, const char* const* ids, const uint8_t* bytes, con
     const std::vector<int> devs(devices, devices + n_devices);
     std::vector<awv_stats> st;
     const bool verify = verify_on != 0;
-    if (mode == 4 && min_batch_pairs <= 0 && !verify && !bounds.any()) {
+    if (mode == 4 && min_batch_pairs <= 0 && !verify && !opts.any()) {
       process_alignments_with_callback(seqs, parse_scores(scores), strat, record, devs);
     } else if (mode == 4) {  // what that overload does, with the batch size of the call and the check
       AllPairIterator it = AllPairIterator::with_options(seqs, parse_scores(scores), true, true, strat);
       it.with_devices(devs).with_verify(verify);
-      bounds.apply(it);
+      opts.apply(it);
       if (min_batch_pairs > 0) it.with_min_batch_pairs((size_t)min_batch_pairs);
       it.for_each_with_callback(record);
       st = it.last_slot_stats();
       keep_verify(it.last_verify_stats(), it.verify_failures());
-      g_bound_stats = it.last_bound_stats();
+      keep_stats(it);
     } else {
       AllPairIterator it0 = AllPairIterator::with_options(seqs, parse_scores(scores), true, orientation == 2,
                                                          resparsify ? SparsificationStrategy{} : strat);
@@ -212,12 +230,12 @@ int awh_iterate_devices(int n, const char* const* ids, const uint8_t* bytes, con
       if (min_batch_pairs > 0) it0.with_min_batch_pairs((size_t)min_batch_pairs);
       if (chunk > 0) it0.with_next_chunk((size_t)chunk);
       it0.with_verify(verify);
-      bounds.apply(it0);
+      opts.apply(it0);
       AllPairIterator it = resparsify ? it0.with_sparsification(strat).with_shard((size_t)shard_rank, (size_t)shard_world) : it0;
-      if (mode == 0) { it.for_each_with_callback(record); st = it.last_slot_stats(); keep_verify(it.last_verify_stats(), it.verify_failures()); g_bound_stats = it.last_bound_stats(); }
-      else if (mode == 1) { while (auto r = it.next()) record(std::move(*r)); st = it.last_slot_stats(); keep_verify(it.last_verify_stats(), it.verify_failures()); g_bound_stats = it.last_bound_stats(); }
-      else if (mode == 2) { auto par = it.into_par_iter(); par.with_threads(threads).for_each_with_callback(record); st = par.last_slot_stats(); keep_verify(par.last_verify_stats(), par.verify_failures()); g_bound_stats = par.last_bound_stats(); }
-      else if (mode == 3) { auto par = it.into_par_iter(); for (auto& r : par.collect()) record(std::move(r)); st = par.last_slot_stats(); keep_verify(par.last_verify_stats(), par.verify_failures()); g_bound_stats = par.last_bound_stats(); }
+      if (mode == 0) { it.for_each_with_callback(record); st = it.last_slot_stats(); keep_verify(it.last_verify_stats(), it.verify_failures()); keep_stats(it); }
+      else if (mode == 1) { while (auto r = it.next()) record(std::move(*r)); st = it.last_slot_stats(); keep_verify(it.last_verify_stats(), it.verify_failures()); keep_stats(it); }
+      else if (mode == 2) { auto par = it.into_par_iter(); par.with_threads(threads).for_each_with_callback(record); st = par.last_slot_stats(); keep_verify(par.last_verify_stats(), par.verify_failures()); keep_stats(par); }
+      else if (mode == 3) { auto par = it.into_par_iter(); for (auto& r : par.collect()) record(std::move(r)); st = par.last_slot_stats(); keep_verify(par.last_verify_stats(), par.verify_failures()); keep_stats(par); }
       else throw std::invalid_argument("awh_iterate_devices: unknown mode");
     }
     if (slot_stats)
@@ -274,7 +292,7 @@ int awh_all_pairs_paf_count_devices(int n, const char* const* ids, const uint8_t
                                     int orientation, const char* sparsification, const int32_t* devices, int n_devices,
                                     int64_t min_batch_pairs, int format_threads, int verify, uint64_t* out_bytes, uint64_t* out_lines,
                                     uint64_t* out_checksum, double* secs, awv_stats* st, awv_stats* slot_stats, char* err, size_t cap) {
-  const Bounds bounds = take_bounds();
+  const RunOptions opts = take_run_options();
   if (!devices || n_devices < 1) { set_err(err, cap, "awh_all_pairs_paf_count_devices: empty device list"); return -1; }
   try {
     const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
@@ -287,7 +305,7 @@ int awh_all_pairs_paf_count_devices(int n, const char* const* ids, const uint8_t
     if (min_batch_pairs > 0) it.with_min_batch_pairs((size_t)min_batch_pairs);
     it.with_threads(format_threads);  // this call's sketching / orientation threads: carried by the iterator, not a process-wide setting
     it.with_verify(verify != 0);
-    bounds.apply(it);
+    opts.apply(it);
     uint64_t nb = 0, nl = 0, sum = 0;
     const auto t0 = std::chrono::steady_clock::now();
     it.for_each_paf_batch([&](const std::string& s) {
@@ -306,7 +324,7 @@ int awh_all_pairs_paf_count_devices(int n, const char* const* ids, const uint8_t
     *out_lines = nl;
     if (out_checksum) *out_checksum = sum;
     keep_verify(it.last_verify_stats(), it.verify_failures());
-    g_bound_stats = it.last_bound_stats();
+    keep_stats(it);
     if (st) *st = it.last_stats();
     if (slot_stats) for (int k = 0; k < n_devices; ++k) slot_stats[k] = it.last_slot_stats()[(size_t)k];
     return 0;
@@ -581,7 +599,7 @@ int awh_check_paf(int n, const char* const* ids, const uint8_t* bytes, const uin
 // list order (malloc'ed).  The verify counters and failures are left for awh_last_verify.
 int awh_align_ranges_paf(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs, const char* scores, const int64_t* ranges,
                          size_t nr, const int32_t* devices, int n_devices, int verify, char** out, size_t* out_len, char* err, size_t cap) {
-  const Bounds bounds = take_bounds();
+  const RunOptions opts = take_run_options();
   try {
     if (!devices || n_devices < 1) throw std::invalid_argument("awh_align_ranges_paf: empty device list");
     const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
@@ -594,11 +612,11 @@ int awh_align_ranges_paf(int n, const char* const* ids, const uint8_t* bytes, co
     }
     AllPairIterator it = AllPairIterator::for_ranges(seqs, rg, parse_scores(scores));
     it.with_devices(std::vector<int>(devices, devices + n_devices)).with_verify(verify != 0);
-    bounds.apply(it);
+    opts.apply(it);
     AllPairParallelIterator par = it.into_par_iter();
     const std::vector<AlignmentResult> res = par.collect();  // (in list order, on any number of slots)
     keep_verify(par.last_verify_stats(), par.verify_failures());
-    g_bound_stats = par.last_bound_stats();
+    keep_stats(par);
     std::string all;
     for (const AlignmentResult& r : res) {
       all += alignment_to_paf(r, seqs);
@@ -662,6 +680,21 @@ void awh_set_bounds(int64_t max_penalty, double max_divergence) {
   g_next_max_penalty = max_penalty;
   g_next_max_divergence = max_divergence;
 }
+// ---- clipping to the best-scoring segment ----
+// The calling thread's NEXT alignment hook runs with_clip(match_bonus, min_score) (match_bonus 0: off); the hooks after it
+// run unclipped again.
+void awh_set_clip(int match_bonus, int64_t min_score) {
+  g_next_clip_bonus = match_bonus;
+  g_next_clip_min_score = min_score;
+}
+// last_clip_stats() of the calling thread's last alignment hook: {pairs, empty, below_min_score} and the kernel time
+void awh_last_clip(uint64_t out[3], double* kernel_ms) {
+  out[0] = g_clip_stats.pairs;
+  out[1] = g_clip_stats.empty;
+  out[2] = g_clip_stats.below_min_score;
+  *kernel_ms = g_clip_stats.kernel_ms;
+}
+
 // last_bound_stats() of the calling thread's last alignment hook: {pairs, above_penalty, above_divergence}
 void awh_last_bounds(uint64_t out[3]) {
   out[0] = g_bound_stats.pairs;

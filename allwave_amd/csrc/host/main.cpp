@@ -50,6 +50,8 @@ struct Args {
   bool partial = false;     // --partial (with --check-paf): lines over a proper interval are checked as that interval pair
   std::string align_paf;    // --align-paf FILE: align the interval pairs that PAF names instead of a planned pair list
   bool have_align_paf = false, have_sparsification = false, have_shard = false;
+  long clip = 0, clip_min_score = 1;  // --clip A: every alignment clipped to its best-scoring segment under the match bonus A
+  bool have_clip = false, have_clip_min_score = false;
 };
 
 [[noreturn]] void die(const std::string& m, int code = 2) {
@@ -225,6 +227,16 @@ int main(int argc, char** argv) {
         die("--max-align-penalty expects a penalty N >= 0");
       a.have_max_align_penalty = true;
     }
+    else if (k == "--clip" || k == "--clip-min-score") {
+      const std::string v = val();
+      char* end = nullptr;
+      const long n = strtol(v.c_str(), &end, 10);
+      const bool bonus = k == "--clip";
+      if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || !end || *end != 0 || n < 1 || (bonus && n > AWV_CLIP_MAX_BONUS))
+        die(bonus ? "--clip expects a match bonus A with 1 <= A <= 32767" : "--clip-min-score expects a score S >= 1");
+      (bonus ? a.clip : a.clip_min_score) = n;
+      (bonus ? a.have_clip : a.have_clip_min_score) = true;
+    }
     else if (k == "--max-divergence") {
       const std::string v = val();
       char* end = nullptr;
@@ -248,10 +260,10 @@ int main(int argc, char** argv) {
       std::cout << "usage: allwave_hip -i in.fa [-o out.paf] [-s m,x,o,e[,o2,e2] | -x ANI] [-p none|auto|random:f|giant:p|tree:n:f:r[:k]]\n"
                    "                   [-t threads] [--wfa-orientation|--wfa-orientation-full|--forward-only] [-k prefixes | -e prefixes] [--mash-matrix]\n"
                    "                   [--device N | --devices LIST] [--shard R/N] [--score-only [--max-penalty N]] [--plan-device N] [--verify]\n"
-                   "                   [--max-align-penalty N] [--max-divergence D]\n"
+                   "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
                    "       allwave_hip -i in.fa --check-paf FILE [-s scores | -x ANI] [--check-optimal] [--partial] [--device N]\n"
                    "       allwave_hip -i in.fa --align-paf FILE [-s scores | -x ANI] [-o out.paf] [--verify] [--score-only] [--device N | --devices LIST]\n"
-                   "                   [--max-align-penalty N] [--max-divergence D]\n"
+                   "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
                    "  --verify         check every alignment on the device before it is written (columns, counts, penalty); the summary\n"
                    "                   line gains `verified N pairs, F failed, K ms`, failures go to stderr, exit status 4 if any\n"
                    "  --check-paf FILE align nothing: check every line of FILE (12 columns + cg:Z:) against in.fa on the device; one line\n"
@@ -273,6 +285,11 @@ int main(int argc, char** argv) {
                    "                   lines, and the summary line gains `A pairs above the bound`\n"
                    "  --max-divergence D  0 <= D < 1: keep the alignments with (#X + #I + #D) <= D * columns; every pair is searched under\n"
                    "                   the penalty bound no such alignment can exceed, completed pairs are filtered on their counts\n"
+                   "  --clip A         clip every alignment to its best-scoring segment on the device (+A per match, minus the penalties):\n"
+                   "                   each PAF line is replaced by its segment's line (coordinates shifted, a '-' line's query coordinates on\n"
+                   "                   the forward strand; columns 10, 11, gi:f: and cg:Z: the segment's) or dropped when nothing scores above 0;\n"
+                   "                   the summary line gains `clipped N pairs, E empty, B below min score, K ms`\n"
+                   "  --clip-min-score S  with --clip: also drop the segments that score below S (default 1)\n"
                    "  --plan-device N  plan on device N: --mash-matrix, the -p pair list and mash orientation (the same output as\n"
                    "                   the host planner; with --shard every rank plans the whole list on its own plan device)\n";
       return 0;
@@ -288,6 +305,10 @@ int main(int argc, char** argv) {
   };
   bound_flag_alone(a.have_max_align_penalty, "--max-align-penalty");
   bound_flag_alone(a.have_max_divergence, "--max-divergence");
+  if (a.have_clip_min_score && !a.have_clip) die("the argument '--clip-min-score' requires '--clip'");
+  if (a.have_clip && a.score_only) die("the argument '--clip' cannot be used with '--score-only'");
+  if (a.have_clip && a.have_check_paf) die("the argument '--clip' cannot be used with '--check-paf'");
+  if (a.have_clip && a.mash_matrix) die("the argument '--clip' cannot be used with '--mash-matrix'");
   if (a.check_optimal && !a.have_check_paf) die("the argument '--check-optimal' requires '--check-paf'");
   if (a.verify && a.score_only) die("the argument '--verify' cannot be used with '--score-only'");
   if (a.verify && a.mash_matrix) die("the argument '--verify' cannot be used with '--mash-matrix'");
@@ -401,6 +422,7 @@ int main(int argc, char** argv) {
     if (a.have_max_align_penalty) it.with_max_penalty((int)a.max_align_penalty);
     if (a.have_max_divergence) it.with_max_divergence(a.max_divergence);
     const bool bounded = a.have_max_align_penalty || a.have_max_divergence;
+    if (a.have_clip) it.with_clip((int)a.clip, (int64_t)a.clip_min_score);
     if (a.forward_only) it.with_orientation(Orientation::ForwardOnly);
     it.with_full_wfa_orientation(a.wfa_orientation_full);
     it.with_devices(devices);
@@ -460,14 +482,19 @@ int main(int argc, char** argv) {
     }
     const BoundStats bs = it.last_bound_stats();
     const size_t above = (size_t)(bs.above_penalty + bs.above_divergence);  // (pairs above a bound get no line)
-    if (done + above != total) die("internal: wrote " + std::to_string(done) + " of " + std::to_string(total) + (a.score_only ? " pairs" : " PAF lines"), 1);
+    const ClipStats cs = it.last_clip_stats();
+    const size_t unclipped = (size_t)(cs.empty + cs.below_min_score);  // (nor do pairs without a clip worth reporting)
+    if (done + above + unclipped != total) die("internal: wrote " + std::to_string(done) + " of " + std::to_string(total) + (a.score_only ? " pairs" : " PAF lines"), 1);
     if (!a.no_progress) {
       const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      char buf[320];
+      char buf[480];
       int w = snprintf(buf, sizeof(buf), "[%.1fs] %zu/%zu (100.0%%) %.1f alignments/sec", secs, done, total, done / std::max(secs, 1e-9));
       if (a.have_align_paf && w > 0 && (size_t)w < sizeof(buf)) w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", %zu bad lines", bad_lines);
       if (bounded && w > 0 && (size_t)w < sizeof(buf)) w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", %zu pairs above the bound", above);
-      if (a.verify) {
+      if (a.have_clip && w > 0 && (size_t)w < sizeof(buf))
+        w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", clipped %llu pairs, %llu empty, %llu below min score, %.2f ms", (unsigned long long)cs.pairs,
+                      (unsigned long long)cs.empty, (unsigned long long)cs.below_min_score, cs.kernel_ms);
+      if (a.verify && w > 0 && (size_t)w < sizeof(buf)) {
         const awv_verify_stats vs = it.last_verify_stats();
         snprintf(buf + w, sizeof(buf) - (size_t)w, ", verified %llu pairs, %zu failed, %.2f ms", (unsigned long long)vs.pairs,
                  it.verify_failures().size(), vs.kernel_ms);

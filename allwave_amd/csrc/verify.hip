@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "planner_device.hpp"  // EngineView, awv_internal_view, awv_internal_fail
+#include "wave_ops.hpp"
 
 namespace awvf {
 
@@ -50,41 +51,11 @@ struct KParams {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-// wave64 inclusive scans on the DPP network
-__device__ __forceinline__ int wave_scan_add(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
-  return v;
-}
-__device__ __forceinline__ int wave_scan_max(int v) {
-  v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x111, 0xf, 0xf, false));
-  v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x112, 0xf, 0xf, false));
-  v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x114, 0xf, 0xf, false));
-  v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x118, 0xf, 0xf, false));
-  v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x142, 0xa, 0xf, false));
-  v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x143, 0xc, 0xf, false));
-  return v;
-}
-// the value of the lane below (wave_shr 1); lane 0 keeps `lane0`
-__device__ __forceinline__ int from_lower_lane(int v, int lane0) { return __builtin_amdgcn_update_dpp(lane0, v, 0x138, 0xf, 0xf, false); }
-
-// 0xff in every byte j of a dword with lo <= j < hi (any lo, hi)
-__device__ __forceinline__ unsigned byte_range_mask(int lo, int hi) {
-  lo = min(max(lo, 0), 4);
-  hi = min(max(hi, 0), 4);
-  const unsigned long long below_hi = (1ull << (8 * hi)) - 1, below_lo = (1ull << (8 * lo)) - 1;
-  return (unsigned)(below_hi & ~below_lo);
-}
-// how many bytes of w equal b
-__device__ __forceinline__ int count_bytes(unsigned w, unsigned b) {
-  const unsigned x = w ^ (b * 0x01010101u);
-  const unsigned nonzero = (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u;
-  return 4 - __popc(nonzero);
-}
+using awvw::byte_range_mask;  // (wave_ops.hpp: the scans and the byte counting shared with clip.hip)
+using awvw::count_bytes;
+using awvw::from_lower_lane;
+using awvw::wave_scan_add;
+using awvw::wave_scan_max;
 
 // 16 bytes of a sequence from position `pos` on, as two 64-bit halves: five aligned dwords, shifted into place.  Dwords
 // that start at or behind the sequence's end are not read; a dword that starts inside it ends at most 3 bytes behind it,
@@ -256,27 +227,7 @@ __global__ __launch_bounds__(64) void awv_verify_kernel(KParams kp) {
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
-template <typename T>
-struct Buf {
-  T* p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t n) {
-    if (n <= cap) return hipSuccess;
-    release();
-    const hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
-    if (e != hipSuccess) {
-      p = nullptr;
-      return e;
-    }
-    cap = n;
-    return hipSuccess;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
+using awvw::Buf;
 
 struct State {
   Buf<awv_pair> d_pairs;

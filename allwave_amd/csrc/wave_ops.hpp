@@ -1,0 +1,102 @@
+// wave_ops.hpp -- what the kernels that scan op bytes (verify.hip, clip.hip) share: wave64 inclusive scans on the DPP network,
+// packed byte counting over a lane's 16 bytes, and the device buffer their host sides keep.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstddef>
+
+namespace awvw {
+
+template <int CTRL, int ROWS>
+__device__ __forceinline__ int dpp32(int ident, int v) {  // lanes without a source (or outside ROWS) get `ident`
+  return __builtin_amdgcn_update_dpp(ident, v, CTRL, ROWS, 0xf, false);
+}
+// 64-bit values travel as two halves
+template <int CTRL, int ROWS>
+__device__ __forceinline__ long long dpp64(long long ident, long long v) {
+  const unsigned lo = (unsigned)dpp32<CTRL, ROWS>((int)(unsigned)(unsigned long long)ident, (int)(unsigned)(unsigned long long)v);
+  const unsigned hi = (unsigned)dpp32<CTRL, ROWS>((int)(unsigned)((unsigned long long)ident >> 32), (int)(unsigned)((unsigned long long)v >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// wave64 inclusive scans: row_shr 1/2/4/8 within the rows of 16, then row_bcast15 / row_bcast31 across them
+__device__ __forceinline__ int wave_scan_add(int v) {
+  v += dpp32<0x111, 0xf>(0, v);
+  v += dpp32<0x112, 0xf>(0, v);
+  v += dpp32<0x114, 0xf>(0, v);
+  v += dpp32<0x118, 0xf>(0, v);
+  v += dpp32<0x142, 0xa>(0, v);
+  v += dpp32<0x143, 0xc>(0, v);
+  return v;
+}
+__device__ __forceinline__ int wave_scan_max(int v) {
+  v = max(v, dpp32<0x111, 0xf>(INT_MIN, v));
+  v = max(v, dpp32<0x112, 0xf>(INT_MIN, v));
+  v = max(v, dpp32<0x114, 0xf>(INT_MIN, v));
+  v = max(v, dpp32<0x118, 0xf>(INT_MIN, v));
+  v = max(v, dpp32<0x142, 0xa>(INT_MIN, v));
+  v = max(v, dpp32<0x143, 0xc>(INT_MIN, v));
+  return v;
+}
+__device__ __forceinline__ long long wave_scan_add(long long v) {
+  v += dpp64<0x111, 0xf>(0, v);
+  v += dpp64<0x112, 0xf>(0, v);
+  v += dpp64<0x114, 0xf>(0, v);
+  v += dpp64<0x118, 0xf>(0, v);
+  v += dpp64<0x142, 0xa>(0, v);
+  v += dpp64<0x143, 0xc>(0, v);
+  return v;
+}
+__device__ __forceinline__ long long wave_scan_min(long long v) {
+  v = min(v, dpp64<0x111, 0xf>(LLONG_MAX, v));
+  v = min(v, dpp64<0x112, 0xf>(LLONG_MAX, v));
+  v = min(v, dpp64<0x114, 0xf>(LLONG_MAX, v));
+  v = min(v, dpp64<0x118, 0xf>(LLONG_MAX, v));
+  v = min(v, dpp64<0x142, 0xa>(LLONG_MAX, v));
+  v = min(v, dpp64<0x143, 0xc>(LLONG_MAX, v));
+  return v;
+}
+// the value of the lane below (wave_shr 1); lane 0 keeps `lane0`
+__device__ __forceinline__ int from_lower_lane(int v, int lane0) { return dpp32<0x138, 0xf>(lane0, v); }
+__device__ __forceinline__ long long from_lower_lane(long long v, long long lane0) { return dpp64<0x138, 0xf>(lane0, v); }
+
+// 0xff in every byte j of a dword with lo <= j < hi (any lo, hi)
+__device__ __forceinline__ unsigned byte_range_mask(int lo, int hi) {
+  lo = min(max(lo, 0), 4);
+  hi = min(max(hi, 0), 4);
+  const unsigned long long below_hi = (1ull << (8 * hi)) - 1, below_lo = (1ull << (8 * lo)) - 1;
+  return (unsigned)(below_hi & ~below_lo);
+}
+// how many bytes of w equal b
+__device__ __forceinline__ int count_bytes(unsigned w, unsigned b) {
+  const unsigned x = w ^ (b * 0x01010101u);
+  const unsigned nonzero = (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u;
+  return 4 - __popc(nonzero);
+}
+
+// a device buffer that only ever grows
+template <typename T>
+struct Buf {
+  T* p = nullptr;
+  size_t cap = 0;
+  hipError_t reserve(size_t n) {
+    if (n <= cap) return hipSuccess;
+    release();
+    const hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
+    if (e != hipSuccess) {
+      p = nullptr;
+      return e;
+    }
+    cap = n;
+    return hipSuccess;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+}  // namespace awvw

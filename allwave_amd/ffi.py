@@ -50,6 +50,12 @@ AWV_VF_X_EQUAL = 5
 AWV_VF_SHORT = 6
 AWV_VF_COUNTS = 7
 AWV_VF_PENALTY = 8
+#: clipping (awv_clip_result.code)
+AWV_CL_OK = 0
+AWV_CL_SKIPPED = 1
+AWV_CL_EMPTY = 2
+AWV_CL_BAD_OP = 3
+AWV_CLIP_MAX_BONUS = 32767
 #: sketch kinds of device pair planning (awv_sketch)
 AWV_SK_CANONICAL = 0
 AWV_SK_FORWARD = 1
@@ -62,7 +68,8 @@ EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine
            "awv_sketch", "awv_sketch_copy", "awv_sketch_pair_counts", "awv_sketch_rows", "awv_sketch_knn", "awv_keep_pairs",
            "awv_align_pairs_verified", "awv_verify_cigars", "awv_verify_one_host", "awv_engine_verify_stats",
            "awv_align_ranges", "awv_align_ranges_verified", "awv_score_ranges", "awv_verify_ranges",
-           "awv_align_pairs_bounded", "awv_align_ranges_bounded", "awv_divergence_bound")
+           "awv_align_pairs_bounded", "awv_align_ranges_bounded", "awv_divergence_bound",
+           "awv_clip_one_host", "awv_clip_cigars", "awv_align_pairs_clipped", "awv_align_ranges_clipped", "awv_engine_clip_stats")
 
 
 class EngineConfig(C.Structure):
@@ -102,6 +109,10 @@ class VerifyStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("pairs", C.c_uint64), ("failed", C.c_uint64), ("columns", C.c_uint64)]
 
 
+class ClipStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("pairs", C.c_uint64), ("empty", C.c_uint64), ("columns", C.c_uint64)]
+
+
 PAIR_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4")])
 #: awv_range_pair: the query interval on the query's forward strand (PAF convention), also with q_revcomp
 RANGE_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4"), ("q_beg", "<i4"), ("q_end", "<i4"),
@@ -111,6 +122,10 @@ RESULT_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4"), ("score", "<i4")
                          ("num_ins", "<i4"), ("num_del", "<i4"), ("q_end", "<i4"), ("t_end", "<i4")])
 #: awv_verify_result
 VERIFY_DTYPE = np.dtype([("code", "<i4"), ("reserved", "<i4"), ("column", "<i8"), ("penalty", "<i8")])
+#: awv_clip_result: the best-scoring segment [col_beg, col_end) of an op string, as a slice description
+CLIP_DTYPE = np.dtype([("code", "<i4"), ("reserved", "<i4"), ("score", "<i8"), ("col_beg", "<u4"), ("col_end", "<u4"),
+                       ("q_skip", "<i4"), ("t_skip", "<i4"), ("num_matches", "<i4"), ("num_mismatches", "<i4"),
+                       ("num_ins", "<i4"), ("num_del", "<i4"), ("penalty", "<i4"), ("reserved2", "<i4")])
 #: awv_score_result
 SCORE_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4")])
 
@@ -163,6 +178,12 @@ def load():
         L.awv_align_ranges_bounded.argtypes = L.awv_align_pairs_bounded.argtypes
         L.awv_divergence_bound.argtypes = [C.POINTER(Penalties), C.c_int32, C.c_int32, C.c_double]
         L.awv_divergence_bound.restype = C.c_int32
+        L.awv_clip_one_host.argtypes = [C.POINTER(Penalties), C.c_int32, C.c_char_p, C.c_int64, C.c_void_p]
+        L.awv_clip_cigars.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.awv_align_pairs_clipped.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, SINK_FN, C.c_void_p]
+        L.awv_align_ranges_clipped.argtypes = L.awv_align_pairs_clipped.argtypes
+        L.awv_engine_clip_stats.argtypes = [C.c_void_p, C.POINTER(ClipStats)]
         _LIB = L
     return _LIB
 
@@ -235,12 +256,12 @@ class Engine:
             ranges = r
         return np.ascontiguousarray(ranges)
 
-    def align_ranges(self, scores, ranges, want_cigars=True, verify=False, max_penalty=None):
+    def align_ranges(self, scores, ranges, want_cigars=True, verify=False, max_penalty=None, clip=None, _sink_hook=None):
         """align_pairs on interval pairs (awv_align_ranges / awv_align_ranges_verified).  ranges: int array [n,7] (q_idx, t_idx,
         q_revcomp, q_beg, q_end, t_beg, t_end) or a RANGE_DTYPE array; the query interval is on the query's forward strand.
         The records' q_end / t_end are consumed lengths, relative to the range.  max_penalty: as for align_pairs
-        (awv_align_ranges_bounded)."""
-        return self._align("awv_align_ranges", scores, self._range_array(ranges), want_cigars, verify, max_penalty)
+        (awv_align_ranges_bounded); clip: as for align_pairs (awv_align_ranges_clipped)."""
+        return self._align("awv_align_ranges", scores, self._range_array(ranges), want_cigars, verify, max_penalty, clip, _sink_hook)
 
     def score_ranges(self, scores, ranges, max_penalty=None):
         """score_pairs on interval pairs (awv_score_ranges).  max_penalty: None, or one bound per range (negative: none)."""
@@ -261,18 +282,23 @@ class Engine:
         """verify_cigars on interval pairs (awv_verify_ranges)."""
         return self._verify("awv_verify_ranges", scores, self._range_array(ranges), results, arena)
 
-    def align_pairs(self, scores, pairs, want_cigars=True, verify=False, max_penalty=None):
+    def align_pairs(self, scores, pairs, want_cigars=True, verify=False, max_penalty=None, clip=None, _sink_hook=None):
         """pairs: int array [n,2] (q,t) or [n,3] (q,t,revcomp), or a PAIR_DTYPE array.
         Returns (results structured array, list of op-byte strings or None); verify=True: every finished pair is checked on
         the device (awv_align_pairs_verified) and a VERIFY_DTYPE array comes back as a third value.
         max_penalty: None = no bound; an int >= 0: one bound for every pair; an array or a list: one bound per pair, a
         negative entry leaving that pair unbounded (awv_align_pairs_bounded).  A pair proved above its bound comes back
-        AWV_ST_ABOVE_BOUND with penalty bound + 1, no CIGAR (None in the list) and zero counts."""
-        return self._align("awv_align_pairs", scores, self._pair_array(pairs), want_cigars, verify, max_penalty)
+        AWV_ST_ABOVE_BOUND with penalty bound + 1, no CIGAR (None in the list) and zero counts.
+        clip: None, or the match bonus a (1 .. 32767): every finished pair's op string is clipped to its best-scoring segment
+        on the device (awv_align_pairs_clipped) and a CLIP_DTYPE array comes back as one more value, after the verify array
+        when there is one.  Records and CIGARs are the unclipped call's: the clip describes a slice.
+        _sink_hook: a test aid, not part of the interface -- with clip, called as _sink_hook(first, n, clips) inside every sink
+        callback, clips being the CLIP_DTYPE array of the whole call as filled so far."""
+        return self._align("awv_align_pairs", scores, self._pair_array(pairs), want_cigars, verify, max_penalty, clip, _sink_hook)
 
-    def _align(self, fn, scores, pairs, want_cigars, verify, max_penalty=None):
-        """awv_align_pairs / awv_align_ranges (`fn`; verify: its _verified variant; max_penalty: its _bounded variant) on a
-        contiguous PAIR_DTYPE / RANGE_DTYPE array."""
+    def _align(self, fn, scores, pairs, want_cigars, verify, max_penalty=None, clip=None, _sink_hook=None):
+        """awv_align_pairs / awv_align_ranges (`fn`; verify: its _verified variant; max_penalty: its _bounded variant; clip: its
+        _clipped variant, which takes the other two as well) on a contiguous PAIR_DTYPE / RANGE_DTYPE array."""
         pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
         bounds = None
         if max_penalty is not None:
@@ -286,8 +312,11 @@ class Engine:
         fn_v = fn + "_verified"
         res = np.zeros(len(pairs), dtype=RESULT_DTYPE)
         cigars = [None] * len(pairs) if want_cigars else None
+        cres = np.zeros(max(len(pairs), 1), dtype=CLIP_DTYPE)[:len(pairs)] if clip is not None else None
 
         def _sink(user, first, n, rptr, arena):
+            if _sink_hook is not None and cres is not None:
+                _sink_hook(int(first), int(n), cres)
             if cigars is not None and arena:
                 r = np.ctypeslib.as_array(C.cast(rptr, C.POINTER(C.c_uint8)), shape=(n * RESULT_DTYPE.itemsize,))
                 r = r.view(RESULT_DTYPE)
@@ -296,7 +325,15 @@ class Engine:
                         cigars[first + i] = C.string_at(arena + int(r["cigar_off"][i]), int(r["cigar_len"][i]))
             return 0
 
-        cb = SINK_FN(_sink) if want_cigars else SINK_FN()
+        cb = SINK_FN(_sink) if want_cigars or (_sink_hook is not None and cres is not None) else SINK_FN()
+        if cres is not None:
+            fn_c = fn + "_clipped"
+            vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)] if verify else None
+            rc = getattr(load(), fn_c)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), None if bounds is None else bounds.ctypes.data,
+                                       int(clip), res.ctypes.data, vres.ctypes.data if verify else None, cres.ctypes.data, cb, None)
+            if rc != AWV_OK:
+                raise EngineError(rc, fn_c)
+            return (res, cigars, vres, cres) if verify else (res, cigars, cres)
         if bounds is not None:
             fn_b = fn + "_bounded"
             vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)] if verify else None
@@ -337,6 +374,31 @@ class Engine:
         if rc != AWV_OK:
             raise EngineError(rc, fn)
         return vres
+
+    def clip_cigars(self, scores, match_bonus, results, arena):
+        """awv_clip_cigars: clips caller-supplied records (a RESULT_DTYPE array whose cigar_off / cigar_len point into `arena`,
+        bytes or a uint8 array) to their best-scoring segments on the device; needs no sequence set.  Returns a CLIP_DTYPE
+        array."""
+        pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+        results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
+        nbytes = int(arena.size)
+        if nbytes == 0:
+            arena = np.zeros(1, dtype=np.uint8)
+        cres = np.zeros(max(len(results), 1), dtype=CLIP_DTYPE)[:len(results)]
+        rc = load().awv_clip_cigars(self._h, C.byref(pen), int(match_bonus), results.ctypes.data, len(results), arena.ctypes.data, nbytes,
+                                    cres.ctypes.data)
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_clip_cigars")
+        return cres
+
+    def clip_stats(self):
+        """awv_engine_clip_stats: kernel_ms, pairs, empty, columns of the last clipping call."""
+        st = ClipStats()
+        rc = load().awv_engine_clip_stats(self._h, C.byref(st))
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_engine_clip_stats")
+        return st
 
     def verify_stats(self):
         """awv_engine_verify_stats: kernel_ms, pairs, failed, columns of the last verifying call."""
@@ -418,6 +480,18 @@ def verify_one_host(scores, pattern, text, cigar, claimed):
                                     out.ctypes.data)
     if rc != AWV_OK:
         raise EngineError(rc, "awv_verify_one_host")
+    return out[0]
+
+
+def clip_one_host(scores, match_bonus, cigar):
+    """awv_clip_one_host: the clipping contract on the host (needs no device; the yardstick the kernel is tested against).
+    Returns one CLIP_DTYPE record."""
+    pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+    cigar = bytes(cigar)
+    out = np.zeros(1, dtype=CLIP_DTYPE)
+    rc = load().awv_clip_one_host(C.byref(pen), int(match_bonus), cigar, len(cigar), out.ctypes.data)
+    if rc != AWV_OK:
+        raise EngineError(rc, "awv_clip_one_host")
     return out[0]
 
 

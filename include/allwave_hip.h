@@ -371,6 +371,69 @@ int awv_align_ranges_bounded(awv_engine* e, const awv_penalties* pen, const awv_
  * INT32_MAX; INT32_MIN for d < 0, NaN, negative lengths or bad penalties. */
 int32_t awv_divergence_bound(const awv_penalties* pen, int32_t plen, int32_t tlen, double d);
 
+/* ---- clipping to the best-scoring segment (csrc/clip.hip, csrc/clip_device.hpp) --------------------------------------------
+ * Every alignment above is global: end to end over the sequences or the intervals, also through flanks that share nothing.
+ * The clip of an op string is the part of it worth reporting.  It is a pure function of the op bytes c[0..n) over M X I D,
+ * the penalties and a match bonus a >= 1; no sequence is read.
+ * The score of a segment [i, j) of columns is a * #M - penalty(c[i..j)), the penalty being the segment re-scored as an op
+ * string of its own by the rule of the verification above: each 'X' adds x, each maximal run of L equal gap ops adds
+ * gap_cost(L) = o1 + L e1 (2-piece: min(o1 + L e1, o2 + L e2)), an 'I' run followed by a 'D' run is two runs.
+ * The clip is the segment of maximal score; among those the one with the smallest end; among those the one with the largest
+ * begin; empty when no segment scores above 0.  A maximal segment begins and ends with an 'M' column (dropping a leading
+ * or trailing 'X' or gap column strictly raises the score), so no gap run is ever cut, and the contract equals this walk:
+ *     S = 0; minS = 0; minI = 0; best = 0; b = e = 0
+ *     for c in 0..n:
+ *         S += a for 'M', -x for 'X', -(gap_cost(L) - gap_cost(L - 1)) for the L-th column of its gap run (gap_cost(0) = 0)
+ *         if S <= minS: minS = S; minI = c + 1                        (a tie moves the minimum: the latest argmin)
+ *         if S - minS > best: best = S - minS; b = minI; e = c + 1    (a tie keeps the best: the first argmax)
+ * The clip is a slice description: records, op bytes and arenas are those of the unclipped call. */
+#define AWV_CL_OK 0       /* the record holds a clip */
+#define AWV_CL_SKIPPED 1  /* status is not AWV_ST_COMPLETED (AWV_ST_ABOVE_BOUND included): nothing to clip; all other fields 0 */
+#define AWV_CL_EMPTY 2    /* no segment scores above 0; all other fields 0 */
+#define AWV_CL_BAD_OP 3   /* a byte that is not M, X, I or D: col_beg = col_end = the smallest such column; all other fields 0 */
+#define AWV_CLIP_MAX_BONUS 32767
+
+typedef struct {
+  int32_t code;            /* AWV_CL_* */
+  int32_t reserved;
+  int64_t score;           /* a * num_matches - penalty, > 0 */
+  uint32_t col_beg, col_end; /* the segment, as a slice [col_beg, col_end) of the op string */
+  int32_t q_skip, t_skip;  /* pattern bases (ops other than 'I') and text bases (ops other than 'D') consumed before col_beg */
+  int32_t num_matches, num_mismatches, num_ins, num_del; /* of the segment */
+  int32_t penalty;         /* the segment re-scored as an op string of its own */
+  int32_t reserved2;
+} awv_clip_result;         /* 56 bytes */
+
+typedef struct {
+  double kernel_ms;  /* HIP-event time of the clip launches of the last clipping call */
+  uint64_t pairs;    /* records handed to the clip (skipped ones included) */
+  uint64_t empty;    /* of them: AWV_CL_EMPTY */
+  uint64_t columns;  /* op bytes of the records not skipped */
+} awv_clip_stats;
+
+/* The contract alone, on the host (needs no device): the yardstick the kernel is tested against, not a fallback -- no product
+ * path calls it.  AWV_ERR_ARG unless 1 <= match_bonus <= AWV_CLIP_MAX_BONUS (every clipping call). */
+int awv_clip_one_host(const awv_penalties* pen, int32_t match_bonus, const uint8_t* cigar, int64_t n, awv_clip_result* out);
+/* Clips records and op bytes the caller supplies, on the device: cout[i] is the clip of
+ * cigar_arena[results[i].cigar_off, + cigar_len) when results[i].status is AWV_ST_COMPLETED, else AWV_CL_SKIPPED.  The arena
+ * goes up in pieces of at most max_arena_bytes.  Reads no sequence: the engine needs no sequence set.  A completed record
+ * whose op bytes lie outside the arena: AWV_ERR_ARG (nothing is read on the device). */
+int awv_clip_cigars(awv_engine* e, const awv_penalties* pen, int32_t match_bonus, const awv_result* results, int64_t n,
+                    const uint8_t* cigar_arena, uint64_t arena_bytes, awv_clip_result* cout /* required */);
+/* awv_align_pairs_bounded / awv_align_ranges_bounded, and every batch's finished pairs clipped on the device, on the engine's
+ * stream, after the optional check and before the batch's CIGARs are copied back (pairs re-run after AWV_ST_CAPACITY
+ * included; also under AWV_F_KEEP_ON_DEVICE).  cout[first .. first + n) is filled before that batch's sink call, as vout is.
+ * Records, op bytes, arena slots, batching and stats are those of the unclipped call, byte for byte: the full op string
+ * still reaches the sink.  max_penalty == NULL: no bound for any pair. */
+int awv_align_pairs_clipped(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
+                            const int32_t* max_penalty /* per pair, nullable; < 0: none */, int32_t match_bonus, awv_result* out,
+                            awv_verify_result* vout /* nullable */, awv_clip_result* cout /* required */, awv_sink sink, void* user);
+int awv_align_ranges_clipped(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n,
+                             const int32_t* max_penalty /* per range, nullable; < 0: none */, int32_t match_bonus, awv_result* out,
+                             awv_verify_result* vout /* nullable */, awv_clip_result* cout /* required */, awv_sink sink, void* user);
+/* The last clipping call (awv_align_*_clipped / awv_clip_cigars) of this engine. */
+int awv_engine_clip_stats(const awv_engine* e, awv_clip_stats* out);
+
 /* ---- device pair planning (csrc/planner.hip) -------------------------------------------------------------------------
  * Integer work over the engine's resident sequence set, on its device and stream; results equal the host planner's
  * (csrc/host/planner.cpp) bit for bit.  Every call but awv_keep_pairs needs a sequence set (else AWV_ERR_STATE); a new set
