@@ -78,6 +78,10 @@ enum { C_M = 0, C_I1 = 1, C_I2 = 2, C_D1 = 3, C_D2 = 4 };
 constexpr int FALLBACK_MIN_SCORE = 250;
 constexpr int FALLBACK_MIN_LENGTH = 100;
 constexpr int STACK_CAP = 48;
+// behind a workgroup's run-length events in HBM: the DFS stack (EV_STACK_WORDS 32-bit words, slack included), then the
+// last-hit table of a twin search's overlap scan ([scope][NCOMP] ints: bialign_overlap)
+constexpr int EV_STACK_WORDS = (STACK_CAP * 32 + 3) / 4 + 16;
+constexpr int EV_TWIN_WORDS = MAX_SCOPE * NCOMP;
 // inside a launch with 32-bit rows, sub-problems of which both lengths are below SUB16_MAX_LEN are searched with 16-bit rows (kp.sub16)
 constexpr int SUB16_MAX_LEN = 32760;  // (the engine's own limit for 16-bit rows: engine.hip)
 // Occupancy target: waves per SIMD (the register budget the kernel is compiled for) and the static
@@ -91,6 +95,7 @@ constexpr int COL_PAD = 576;  // columns of slack either side of a row: whole-wa
 
 // per-pair status (allwave_hip.h AWV_ST_*)
 constexpr int ST_OK = 0, ST_CAPACITY = 1, ST_INTERNAL = 2, ST_MAX_STEPS = 3, ST_ABOVE_BOUND = 4;
+constexpr int ST_TWIN_REDO = 64;  // inside the kernel only: a twin unit gives up sharing and runs both orientations on their own
 
 struct DevPenalties {
   int x, o1, e1, o2, e2, two_piece, scope;  // scope = max(x, o1+e1, o2+e2) + 1  (A.3)
@@ -113,7 +118,12 @@ enum { STAT_CELLS = 0, STAT_EXTEND, STAT_BREAKPOINTS, STAT_BASE, STAT_OVERLAP, S
        // cycles / ticks x 100 MHz (MI355X_MICROARCH.md: the clock under load is not the nominal 2.4 GHz)
        STAT_CLK_CYCLES, STAT_CLK_TICKS,
        STAT_DEEP_CELLS,  // cells computed by deep_phase (passes that also store every I/D row); part of STAT_MULTI_CELLS
-       STAT_N };
+       STAT_N,
+       // twin units, added straight to KParams::stats once per unit (no slot in the workgroup's LDS copy):
+       // units with a twin, searches run shared, searches run per orientation inside twin units, shared searches whose two
+       // breakpoints were not mirrors
+       STAT_TWIN_UNITS = STAT_N, STAT_TWIN_SHARED, STAT_TWIN_SOLO, STAT_TWIN_NONMIRROR,
+       STAT_N_DEV };
 
 #ifdef AWV_PROF
 #define PROF_DRAIN() __builtin_amdgcn_s_waitcnt(0)
@@ -171,6 +181,12 @@ struct KParams {
   // score-only launches with a bound per pair (awv_score_pairs_bounded): nullable; when present pair i's bound is
   // pair_max_penalty[i] (INT_MAX = none) and max_penalty is not read
   const int32_t* pair_max_penalty;
+  // twin units: nullable.  When present `npairs` counts dispatch units: unit u is the entry unit_first[u]
+  // of pair_q / pair_t / ..., aligned together with its swapped entry unit_twin[u] (-1: on its own).  twin_levels: the depth
+  // of the BiWFA recursion down to which a unit's two alignments may share one search (1 = the top level only)
+  const int32_t* unit_first;
+  const int32_t* unit_twin;
+  int twin_levels;
 };
 
 struct RowMeta { int lo, hi; };
@@ -178,7 +194,17 @@ constexpr int K_BIG = 1 << 28;  // an empty row is {K_BIG, -K_BIG}: min/max hull
 #define ROW_EMPTY RowMeta{K_BIG, -K_BIG}
 struct Acc { int hull_lo[NCOMP]; int hull_hi[NCOMP]; int maxak; int oob; int reach; };  // maxak_t: per step of a multi-step pass
 struct Task { int pb, pe, tb, te, cb, ce, score_remaining, known; };  // known: the sub-problem's optimal score (INT_MAX at the top)
+// Twin units: bits 8..9 of Task::cb say whose task it is, bits 16.. its depth below the top (only kept while shared).
+// TM_A = 0: an ordinary pair's tasks are encoded as ever.  A shared task's coordinates are in A's frame.
+constexpr int TM_A = 0, TM_B = 1, TM_SHARED = 2;
+// Twin units exist in the one-wave kernels with 16-bit rows only (config 2's): every other instantiation compiles the twin
+// branches out and keeps the code it had.
+constexpr bool TWIN_BUILD = WG == 64 && !WENC;
+constexpr int TWIN_MAGIC = 0x7477696e;  // never a component: a stale Shared::bp_out cannot pass for the mark
+// the component as the swapped pair names it: I1 <-> D1, I2 <-> D2
+__device__ __forceinline__ int twin_comp(int c) { return c == 0 ? 0 : (c <= 2 ? c + 2 : c - 2); }
 struct Breakpoint { int score, sf, sr, kf, kr, off_f, off_r, comp; };
+static_assert(sizeof(Task) == 32 && sizeof(Breakpoint) == 32, "stack entry / twin record size");
 
 // Scalar-unit arithmetic, spelled out.  Uniform min / max / add chains whose results end up in vector registers anyway (the data
 // of an LDS store, a per-lane select) are otherwise selected as VALU code wholesale: plan_step's hull arithmetic was ~90 vector
@@ -266,7 +292,8 @@ struct Shared {
   int chain_maxak[2][8];  // per direction: [0] the max antidiagonal of a far-apart pass; [t] of step t of a deep pass (TMAX <= 8)
   PassCtx pctx;
   PhaseResult pres;
-  Breakpoint bp_out;  // find_breakpoint_fn's result
+  Breakpoint bp_out;  // find_breakpoint_fn's result; on the way in (kernels built with twin units only): comp == TWIN_MAGIC marks a
+                      // twin search, off_f / off_r then hold the address of its last-hit table (bialign_overlap)
   unsigned long long ext_multi;  // extend probes counted by multi-step passes
   unsigned int win_single, win_multi, win_base, win_base_multi;  // windows processed (diagnostics)
   int ext0[2];
@@ -2820,7 +2847,25 @@ __device__ __forceinline__ void bialign_overlap(const KParams& kp, Shared& sh, c
     }
   }
   if (!any) return;
-  for (int i = tid; i < pn.scope * NCOMP; i += WG) lds.firstk[i] = INT_MAX;
+  // Twin search: the swapped pair's search sees these wavefronts mirrored (k -> -k, I <-> D), so per
+  // candidate score and component it takes the LAST qualifying k where this one takes the first.  Stage 1 records both;
+  // stage 2 replays twice.  The last-hit table lives in HBM (the LDS has no room for it); everything the twin half
+  // needs is read back from LDS here, so that nothing more stays live across the step loop of the search.
+  // (only the one-wave kernels with 16-bit rows are built with it: TWIN_BUILD)
+  const bool twin = TWIN_BUILD && sizeof(OffT) == 2 && uni(sh.bp_out.comp) == TWIN_MAGIC;
+  int* const lastk = twin ? (int*)(uintptr_t)(((unsigned long long)(unsigned)uni(sh.bp_out.off_r) << 32) | (unsigned)uni(sh.bp_out.off_f)) : nullptr;
+  const int score_in = bp.score;
+  for (int i = tid; i < pn.scope * NCOMP; i += WG) {
+    lds.firstk[i] = INT_MAX;
+    if (twin) __hip_atomic_store(&lastk[i], INT_MIN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  // (the table is written and read with device-scope atomics only -- they bypass the CU's vector cache --, so all the ordering
+  // it needs is that a wave's own accesses have been acknowledged before the barrier: a wait, not a fence.  A device-scope
+  // fence here invalidates the CU's vector cache twice per call, for all sixteen waves of the CU: measured, it cost
+  // everything the shared searches saved.)  This argument is for ONE wave per workgroup, where the table's writer and
+  // reader are the same wave and its accesses to one address stay in order; several waves would need a proof of their own.
+  static_assert(!TWIN_BUILD || WG == 64, "the last-hit table's ordering is argued for one wave per workgroup only");
+  if (twin) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   // stage 1: parallel scan of every candidate wavefront pair that passes the row filter (superset of
   // what the sequential search visits: the best score only decreases within a call), 256 columns
@@ -2935,9 +2980,7 @@ __device__ __forceinline__ void bialign_overlap(const KParams& kp, Shared& sh, c
         unpack_raw<OffT>(q1[c], v1);
         decode4<OffT>(v0, c0 + kmin0);
         decode4<OffT>(v1, Cm - c0 - (VEC - 1) + kmin1);
-        int first = VEC;
-#pragma unroll
-        for (int j = VEC - 1; j >= 0; --j) {
+        auto hit = [&](int j) {
           const int col0 = c0 + j;
           const int k0 = col0 + kmin0, k1 = D - k0;
           const int32_t h0 = v0[j] < 0 ? OFF_NULL : v0[j], h1 = v1[VEC - 1 - j] < 0 ? OFF_NULL : v1[VEC - 1 - j];
@@ -2946,14 +2989,28 @@ __device__ __forceinline__ void bialign_overlap(const KParams& kp, Shared& sh, c
             const int kf = fwd ? k0 : k1, hf = fwd ? h0 : h1;
             cond = cond && !((hf - kf) > plen || hf > tlen);
           }
-          if (cond) first = j;
-        }
+          return cond;
+        };
+        int first = VEC;
+#pragma unroll
+        for (int j = VEC - 1; j >= 0; --j)
+          if (hit(j)) first = j;
         const uint64_t mask = __ballot(first < VEC);
         if (mask) {
           const int src = (int)__builtin_ctzll(mask);
           const int fj = __builtin_amdgcn_readlane(first, src);
           if (lane == 0) atomicMin(&lds.firstk[i * NCOMP + c], cbase + src * VEC + fj + kmin0);
-          live &= ~(1u << c);
+          if (!twin) {
+            live &= ~(1u << c);
+          } else {  // the last hit of this chunk; the later chunks are scanned too
+            int last = -1;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j)
+              if (hit(j)) last = j;
+            const int hsrc = 63 - (int)__builtin_clzll(mask);
+            const int lj = __builtin_amdgcn_readlane(last, hsrc);
+            if (lane == 0) __hip_atomic_fetch_max(&lastk[i * NCOMP + c], cbase + hsrc * VEC + lj + kmin0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
         }
       }
     }
@@ -2969,6 +3026,7 @@ __device__ __forceinline__ void bialign_overlap(const KParams& kp, Shared& sh, c
       scan_all(i, si, (w2 ? (1u << C_D2) | (1u << C_I2) : 0u) | (w1 ? (1u << C_D1) | (1u << C_I1) : 0u) | (w0 ? 1u << C_M : 0u));
     }
   }
+  if (twin) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   // stage 2: replay in WFA2's order (per i: D2, I2, D1, I1, M; first k ascending)
   auto apply = [&](int c, int i, int si, int gap_open) {
@@ -2993,6 +3051,68 @@ __device__ __forceinline__ void bialign_overlap(const KParams& kp, Shared& sh, c
       if (s0 + si - pn.o1 < bp.score) { apply(C_D1, i, si, pn.o1); apply(C_I1, i, si, pn.o1); }
       if (s0 + si >= bp.score) continue;
       apply(C_M, i, si, 0);
+    }
+  }
+  if (twin) {
+    // the same replay in the swapped pair's order (its D2, I2, D1, I1, M are our I2, D2, I1, D1, M; its first k ascending
+    // is our last), from the score this call began with.  The record is kept in the swapped pair's frame, in the last 32
+    // bytes of the LDS metadata region; its score always ends equal to bp.score (the kernel checks that).
+    Breakpoint* const rec = reinterpret_cast<Breakpoint*>(reinterpret_cast<unsigned char*>(lds.seq) - sizeof(Breakpoint));
+    int tscore = uni(rec->score) == INT_MIN ? INT_MIN : score_in;  // (void: stays void)
+    // the table is read 64 entries at a time, one per lane (a read per entry would be a memory round trip each, one after the
+    // other); nearly all entries are empty, and the replay walks the table in ascending order
+    int blk = -1, blk_v = INT_MIN;
+    uint64_t blk_hits = 0;
+    auto last_hit = [&](int idx) -> int {
+      if ((idx >> 6) != blk) {
+        blk = idx >> 6;
+        const int j = (blk << 6) + lane;
+        blk_v = j < pn.scope * NCOMP ? __hip_atomic_load(&lastk[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : INT_MIN;
+        blk_hits = __ballot(blk_v != INT_MIN);
+      }
+      if (!((blk_hits >> (idx & 63)) & 1ull)) return INT_MIN;
+      return __builtin_amdgcn_readlane(blk_v, idx & 63);
+    };
+    auto tapply = [&](int c, int i, int si, int gap_open) {
+      if (s0 + si - gap_open >= tscore) return;
+      const int k0 = last_hit(i * NCOMP + c);
+      if (k0 == INT_MIN) return;
+      {  // an entry is a diagonal inside both rows' hulls, or the record is void (the kernel then aligns both entries alone)
+        const RowMeta r0 = uni(meta_load(&lds.ring_meta[(d0 * NCOMP + c) * kp.ring + slot0]));
+        const RowMeta r1 = uni(meta_load(&lds.ring_meta[(d1 * NCOMP + c) * kp.ring + (si & rmask)]));
+        if (k0 < r0.lo || k0 > r0.hi || D - k0 < r1.lo || D - k0 > r1.hi) {
+          tscore = INT_MIN;
+          if (tid == 0) rec->score = INT_MIN;
+          return;
+        }
+      }
+      const int k1 = D - k0;
+      const int32_t h0 = uni(off_load1<OffT>(row_ptr<false, OffT>(kp, ring_mem, d0, c, s0) + (k0 - kmin0), k0));
+      const int32_t h1 = uni(off_load1<OffT>(row_ptr<false, OffT>(kp, ring_mem, d1, c, si) + (k1 - kmin1), k1));
+      tscore = s0 + si - gap_open;
+      if (tid == 0) {
+        const int kf = fwd ? k0 : k1, kr = fwd ? k1 : k0, hf = fwd ? h0 : h1, hr = fwd ? h1 : h0;
+        rec->score = tscore;
+        rec->sf = fwd ? s0 : si;
+        rec->sr = fwd ? si : s0;
+        rec->kf = -kf;
+        rec->kr = -kr;
+        rec->off_f = hf - kf;
+        rec->off_r = hr - kr;
+        rec->comp = twin_comp(c);
+      }
+    };
+    for (int ib = 0; ib < pn.scope; ib += 64) {
+      uint64_t gm = group_mask(ib);
+      while (gm) {
+        const int i = ib + (int)__builtin_ctzll(gm);
+        gm &= gm - 1;
+        const int si = s1 - i;
+        if (P2 && s0 + si - pn.o2 < tscore) { tapply(C_I2, i, si, pn.o2); tapply(C_D2, i, si, pn.o2); }
+        if (s0 + si - pn.o1 < tscore) { tapply(C_I1, i, si, pn.o1); tapply(C_D1, i, si, pn.o1); }
+        if (s0 + si >= tscore) continue;
+        tapply(C_M, i, si, 0);
+      }
     }
   }
   __syncthreads();  // firstk is rewritten by the next call
@@ -3370,6 +3490,331 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
   const unsigned long long clk_c0 = __builtin_amdgcn_s_memtime(), clk_r0 = __builtin_amdgcn_s_memrealtime();
   if (tid < 16) sh.chain_maxak[tid >> 3][tid & 7] = 0;
   __syncthreads();
+  // Twin units are built into the one-wave kernel with 16-bit rows for whole-pair launches; every other instantiation keeps
+  // the pair loop it had, line for line.
+  constexpr bool TWINS = TWIN_BUILD && !RANGES && sizeof(OffT) == 2;
+  if constexpr (TWINS) {
+  for (;;) {
+    if (tid == 0) {
+      sh.cur_pair = (long long)atomicAdd(kp.work_counter, 1ULL);
+      sh.win_single = sh.win_multi = sh.win_base = sh.win_base_multi = 0;
+    }
+    __syncthreads();
+    const long long unit = ((long long)uni((int)(sh.cur_pair >> 32)) << 32) | (unsigned)uni((int)sh.cur_pair);
+    if (unit >= kp.npairs) break;
+    // A dispatch unit is one entry of the pair list, or an entry (q, t) together with its swapped entry (t, q): "A" and "B"
+    long long pair = unit, pair_b = -1;
+    if constexpr (TWINS) {
+      if (kp.unit_first) {
+        pair = uni(kp.unit_first[unit]);
+        pair_b = uni(kp.unit_twin[unit]);
+      }
+    }
+    const int qi = kp.pair_q[pair], ti = kp.pair_t[pair];
+    const int qv = kp.pair_rc[pair] ? 2 : 0;
+    const uint64_t qoff = kp.seq_off[qi], toff = kp.seq_off[ti];
+    int plenT = kp.seq_len[qi], tlenT = kp.seq_len[ti];
+    const uint8_t* Pf = kp.seq[qv] + qoff;
+    const uint8_t* Pr = kp.seq[qv + 1] + qoff;
+    const uint8_t* Tf = kp.seq[0] + toff;
+    const uint8_t* Tr = kp.seq[1] + toff;
+    // 2-bit packed views: usable when both sequences are pure upper-case ACGT (bytes compare verbatim)
+    const int qok = (kp.seq2_ok[qi] >> (qv ? 1 : 0)) & 1, tok = kp.seq2_ok[ti] & 1;
+    gwords_t Pw = nullptr, Tw = nullptr;
+    if (qok && tok && kp.lds_seq_bytes > 0) {
+      Pw = (gwords_t)(uintptr_t)(kp.seq2[qv ? 1 : 0] + kp.seq2_off[qi]);
+      Tw = (gwords_t)(uintptr_t)(kp.seq2[0] + kp.seq2_off[ti]);
+    }
+    int tw_shared = 0, tw_solo = 0, tw_nonmirror = 0;  // searches of a twin unit: shared, per orientation, shared with two different breakpoints
+    // One run of the DFS aligns the unit as planned.  When a twin unit ends other than ST_OK, the orientation that failed
+    // keeps its record -- it ran the plain path's code on the plain path's tree -- and the other one runs again on its own,
+    // from its own top task (todo: bit 0 = A, bit 1 = B still to run alone).
+    int run_mode = TWINS && pair_b >= 0 ? TM_SHARED : TM_A;
+    int todo = 0;
+    for (;;) {
+    const unsigned long long tt0 = PROF_NOW();
+    // `em`, `penalty`, `top` and the sequence pointers are those of the orientation `cur`; the other one's wait in *_o
+    int cur = TM_A;
+    Emit em, em_o;
+    em.cig = kp.score_only ? nullptr : kp.cigar + kp.cigar_off[pair];
+    em.n = 0;
+    em.cnt[0] = em.cnt[1] = em.cnt[2] = em.cnt[3] = 0;
+    em_o = em;
+    if (pair_b >= 0 && !kp.score_only) em_o.cig = kp.cigar + kp.cigar_off[pair_b];
+    int status = ST_OK;
+    int penalty = -1, penalty_o = -1;
+    bool top = true, top_o = true;
+    auto face = [&](int o) {  // (uniform)
+      if (cur == o) return;
+      cur = o;
+      { const uint8_t* x = Pf; Pf = Tf; Tf = x; }
+      { const uint8_t* x = Pr; Pr = Tr; Tr = x; }
+      { const gwords_t x = Pw; Pw = Tw; Tw = x; }
+      { const int x = plenT; plenT = tlenT; tlenT = x; }
+      { const Emit x = em; em = em_o; em_o = x; }
+      { const int x = penalty; penalty = penalty_o; penalty_o = x; }
+      { const bool x = top; top = top_o; top_o = x; }
+    };
+    if (TWINS && run_mode == TM_B) face(TM_B);
+    int sp = 0;
+    if constexpr (RANGES) {
+      // the top-level task is the rectangle the launch names (plenT / tlenT stay the full lengths: the reversed copies are
+      // addressed from the far end)
+      if (tid == 0) {
+        const awvr::Span top = (pair_span_arg, ...)[pair];
+        const bool min_length = max(top.pe - top.pb, top.te - top.tb) <= FALLBACK_MIN_LENGTH;
+        stack[0] = Task{top.pb, top.pe, top.tb, top.te, C_M, C_M, min_length ? 0 : INT_MAX, INT_MAX};
+        sh.error = 0;
+      }
+    } else if (tid == 0) {
+      const bool min_length = max(plenT, tlenT) <= FALLBACK_MIN_LENGTH;
+      stack[0] = Task{0, plenT, 0, tlenT, C_M | (run_mode << 8), C_M, min_length ? 0 : INT_MAX, INT_MAX};
+      sh.error = 0;
+    }
+    sp = 1;
+    __syncthreads();
+    while (sp > 0 && status == ST_OK) {
+      Task t = stack[sp - 1];
+      t.pb = uni(t.pb); t.pe = uni(t.pe); t.tb = uni(t.tb); t.te = uni(t.te);
+      t.cb = uni(t.cb); t.ce = uni(t.ce); t.score_remaining = uni(t.score_remaining); t.known = uni(t.known);
+      --sp;
+      __syncthreads();  // everyone has read the entry before it can be overwritten
+      const int mode = TWINS ? (t.cb >> 8) & 3 : TM_A, depth = TWINS ? t.cb >> 16 : 0;
+      if (TWINS) {
+        t.cb &= 0xff;
+        face(mode == TM_B ? TM_B : TM_A);
+      }
+      const int plen = t.pe - t.pb, tlen = t.te - t.tb;
+      bool split = mode == TM_SHARED && (tlen == 0 || plen == 0 || t.score_remaining <= FALLBACK_MIN_SCORE);
+      Breakpoint bp, bq;  // bq: a shared search's breakpoint for B, in B's frame
+      bool do_base = false;
+      SubCtx cx;
+      if (!split) {
+      if (tlen == 0) {
+        emit_run(em, 'D', plen);
+        if (top) penalty = plen > 0 ? min(pn.o1 + plen * pn.e1, P2 ? pn.o2 + plen * pn.e2 : INT_MAX) : 0;
+        top = false;
+        continue;
+      } else if (plen == 0) {
+        emit_run(em, 'I', tlen);
+        if (top) penalty = min(pn.o1 + tlen * pn.e1, P2 ? pn.o2 + tlen * pn.e2 : INT_MAX);
+        top = false;
+        continue;
+      }
+      cx.plen = plen;
+      cx.tlen = tlen;
+      cx.P[0] = to_global(Pf + t.pb);
+      cx.T[0] = to_global(Tf + t.tb);
+      cx.P[1] = to_global(Pr + (plenT - t.pe));
+      cx.T[1] = to_global(Tr + (tlenT - t.te));
+      cx.kmin[0] = cx.kmin[1] = 0;
+      cx.wcols = 0;
+      cx.Pw = Pw;
+      cx.Tw = Tw;
+      cx.pb_abs = t.pb;
+      cx.tb_abs = t.tb;
+      stage_sequences<OffT>(kp, lds, cx);
+      do_base = t.score_remaining <= FALLBACK_MIN_SCORE;
+      if (!do_base) {
+        int rc = BP_OK;
+        for (int attempt = 0; attempt < AWV_RESTART_ATTEMPTS; ++attempt) {  // (one call site: the search stays inlined)
+          // later attempts: the searches met before the I/D history was being kept -- once more with a wider margin, then step by step
+          if (tid == 0) {  // the search's inputs (find_breakpoint_fn reads them back after a barrier)
+            PassCtx& pc = sh.pctx;
+            pc.ring_mem = (unsigned long long)(uintptr_t)ring_mem;
+            pc.ring_bytes = (unsigned long long)kp.ring_slot_stride;
+            pc.P[0] = (unsigned long long)(uintptr_t)cx.P[0];
+            pc.P[1] = (unsigned long long)(uintptr_t)cx.P[1];
+            pc.T[0] = (unsigned long long)(uintptr_t)cx.T[0];
+            pc.T[1] = (unsigned long long)(uintptr_t)cx.T[1];
+            pc.Pw = (unsigned long long)(uintptr_t)cx.Pw;
+            pc.Tw = (unsigned long long)(uintptr_t)cx.Tw;
+            pc.ring = kp.ring;
+            pc.wcap = kp.wcap;
+            pc.x = pn.x; pc.o1 = pn.o1; pc.e1 = pn.e1; pc.o2 = pn.o2; pc.e2 = pn.e2;
+            pc.lds_meta_bytes = kp.lds_meta_bytes;
+            pc.lds_seq_bytes = kp.lds_seq_bytes;
+            pc.chain_max = kp.chain_max;
+            pc.multi_T = kp.multi_T;
+            pc.deep_passes = kp.deep_passes;
+            pc.max_penalty = kp.pair_max_penalty ? kp.pair_max_penalty[pair] : kp.max_penalty;
+            pc.plen = plen; pc.tlen = tlen;
+            pc.seq_mode = cx.seq_mode; pc.p_w0 = cx.p_w0; pc.t_w0 = cx.t_w0; pc.p_bit = cx.p_bit; pc.t_bit = cx.t_bit;
+            pc.pb_abs = cx.pb_abs; pc.tb_abs = cx.tb_abs;
+            // (a score-only unit needs the shared score alone: no twin search)
+            const unsigned long long tab = (unsigned long long)(uintptr_t)(events + kp.wcap + EV_STACK_WORDS);
+            sh.bp_out.comp = mode == TM_SHARED && !kp.score_only ? TWIN_MAGIC : 0;
+            sh.bp_out.off_f = (int)(unsigned)tab;
+            sh.bp_out.off_r = (int)(unsigned)(tab >> 32);
+            if (mode == TM_SHARED)  // the twin record starts void: a search that never writes it cannot pass a stale one on
+              reinterpret_cast<Breakpoint*>(dyn_smem + kp.lds_meta_bytes - sizeof(Breakpoint))->score = INT_MAX;
+          }
+          __syncthreads();
+          // A launch with 32-bit rows searches the sub-problems that have become short enough with 16-bit rows (kp.sub16): the
+          // same ring arena at half the bytes per row, packed arithmetic, the 16-bit metadata layout inside the same LDS region --
+          // a search leaves nothing behind but its breakpoint.  (The base case stays with the launch's row width.)
+          if constexpr (sizeof(OffT) == 4 && !WENC) {
+            if (kp.sub16 != 0 && max(plen, tlen) < SUB16_MAX_LEN)
+              rc = uni(find_breakpoint_fn<P2, int16_t>((unsigned)(uintptr_t)&sh, (unsigned)(uintptr_t)lds.ring_meta, (unsigned)(uintptr_t)lstats,
+                                                       t.cb, t.ce, t.score_remaining, t.known, attempt | 0x100));  // (0x100: the long reads' margin)
+            else
+              rc = uni(find_breakpoint_fn<P2, OffT>((unsigned)(uintptr_t)&sh, (unsigned)(uintptr_t)lds.ring_meta, (unsigned)(uintptr_t)lstats,
+                                                    t.cb, t.ce, t.score_remaining, t.known, attempt));
+          } else {
+            rc = uni(find_breakpoint_fn<P2, OffT>((unsigned)(uintptr_t)&sh, (unsigned)(uintptr_t)lds.ring_meta, (unsigned)(uintptr_t)lstats,
+                                                  t.cb, t.ce, t.score_remaining, t.known, attempt));
+          }
+          if (rc == BP_OK) {
+            bp.score = uni(sh.bp_out.score); bp.sf = uni(sh.bp_out.sf); bp.sr = uni(sh.bp_out.sr); bp.kf = uni(sh.bp_out.kf);
+            bp.kr = uni(sh.bp_out.kr); bp.off_f = uni(sh.bp_out.off_f); bp.off_r = uni(sh.bp_out.off_r); bp.comp = uni(sh.bp_out.comp);
+            if (mode == TM_SHARED && !kp.score_only) {  // (the record the overlap search kept: the last 32 bytes of the LDS metadata region)
+              const Breakpoint* rec = reinterpret_cast<const Breakpoint*>(dyn_smem + kp.lds_meta_bytes - sizeof(Breakpoint));
+              bq.score = uni(rec->score); bq.sf = uni(rec->sf); bq.sr = uni(rec->sr); bq.kf = uni(rec->kf);
+              bq.off_f = uni(rec->off_f); bq.comp = uni(rec->comp);
+            }
+          }
+          if (rc != BP_RESTART) break;
+          if (tid == 0) lstats[STAT_RESTARTS] += 1;
+        }
+        if (TWINS && pair_b >= 0 && run_mode == TM_SHARED) {
+          if (mode == TM_SHARED) ++tw_shared;
+          else ++tw_solo;
+        }
+        if (rc == BP_END_REACHED) {  // wavefront_bialign_exception -> plain WFA
+          if (mode == TM_SHARED) split = true;
+          else do_base = true;
+        }
+        else if (rc == BP_ABOVE_BOUND) { status = ST_ABOVE_BOUND; break; }
+        else if (rc != BP_OK) { status = rc; break; }
+      }
+      }
+      if (split) {
+        // a shared task that needs no search (an empty half, a base case): each orientation takes it as a task of its own, so
+        // that the code below stays the plain path's
+        if (sp + 2 > STACK_CAP) { status = ST_TWIN_REDO; break; }
+        if (tid == 0) {
+          stack[sp] = Task{t.tb, t.te, t.pb, t.pe, twin_comp(t.cb) | (TM_B << 8), twin_comp(t.ce), t.score_remaining, t.known};
+          stack[sp + 1] = Task{t.pb, t.pe, t.tb, t.te, t.cb | (TM_A << 8), t.ce, t.score_remaining, t.known};
+        }
+        sp += 2;
+        __syncthreads();
+        continue;
+      }
+      if (do_base) {
+        int pen_b = 0;
+        const int rc = base_align<P2, OffT>(kp, sh, lds, cx, hist, hist_rs, events, t.cb, t.ce, em, pen_b, lstats);
+        if (rc != ST_OK) { status = rc; break; }
+        if (top) penalty = pen_b;
+        top = false;
+        continue;
+      }
+      if (kp.score_only) {  // the top level's breakpoint score is the penalty: no sub-problems, no CIGAR
+        penalty = bp.score;
+        if (mode == TM_SHARED) penalty_o = bp.score;  // (the swapped pair's optimal penalty is the same number)
+        break;
+      }
+      const int bh = bp.off_f, bv = bp.off_f - bp.kf;
+      if (mode != TM_SHARED) {
+        if (bh < 0 || bh > tlen || bv < 0 || bv > plen || sp + 2 > STACK_CAP) { status = ST_INTERNAL; break; }
+        if (tid == 0) {
+          const int open_c = bp.comp == C_M ? 0 : ((bp.comp == C_I1 || bp.comp == C_D1) ? kp.pen.o1 : kp.pen.o2);
+          stack[sp] = Task{t.pb + bv, t.pe, t.tb + bh, t.te, bp.comp | (mode << 8), t.ce, bp.sr, bp.sr - open_c};      // right half
+          stack[sp + 1] = Task{t.pb, t.pb + bv, t.tb, t.tb + bh, t.cb | (mode << 8), bp.comp, bp.sf, bp.sf - open_c};  // left half first
+        }
+        sp += 2;
+      } else {
+        // B's breakpoint (in B's frame, where pattern and text have swapped roles) is the mirror image of A's unless a tie
+        // fell the other way.  Mirrors: the halves stay shared.  Otherwise, or below the depth cap: four tasks, each
+        // orientation's two with its own breakpoint -- each orientation still emits left to right.
+        const int qh = bq.off_f, qv2 = bq.off_f - bq.kf;
+        if (bq.score != bp.score || bq.comp < 0 || bq.comp >= NCOMP || (!P2 && (bq.comp == C_I2 || bq.comp == C_D2)) || bh < 0 || bh > tlen || bv < 0 || bv > plen || qh < 0 || qh > plen || qv2 < 0 || qv2 > tlen ||
+            sp + 4 > STACK_CAP) { status = ST_TWIN_REDO; break; }
+        const bool mirror = bq.kf == -bp.kf && qh == bv && bq.comp == twin_comp(bp.comp) && bq.sf == bp.sf && bq.sr == bp.sr;
+        if (!mirror) ++tw_nonmirror;
+        const int open_c = bp.comp == C_M ? 0 : ((bp.comp == C_I1 || bp.comp == C_D1) ? kp.pen.o1 : kp.pen.o2);
+        if (mirror && depth + 1 < kp.twin_levels) {
+          if (tid == 0) {
+            const int tag = (TM_SHARED << 8) | ((depth + 1) << 16);
+            stack[sp] = Task{t.pb + bv, t.pe, t.tb + bh, t.te, bp.comp | tag, t.ce, bp.sr, bp.sr - open_c};
+            stack[sp + 1] = Task{t.pb, t.pb + bv, t.tb, t.tb + bh, t.cb | tag, bp.comp, bp.sf, bp.sf - open_c};
+          }
+          sp += 2;
+        } else {
+          if (tid == 0) {
+            const int open_q = bq.comp == C_M ? 0 : ((bq.comp == C_I1 || bq.comp == C_D1) ? kp.pen.o1 : kp.pen.o2);
+            const int cbq = twin_comp(t.cb), ceq = twin_comp(t.ce);
+            stack[sp] = Task{t.pb + bv, t.pe, t.tb + bh, t.te, bp.comp | (TM_A << 8), t.ce, bp.sr, bp.sr - open_c};
+            stack[sp + 1] = Task{t.tb + qv2, t.te, t.pb + qh, t.pe, bq.comp | (TM_B << 8), ceq, bq.sr, bq.sr - open_q};
+            stack[sp + 2] = Task{t.pb, t.pb + bv, t.tb, t.tb + bh, t.cb | (TM_A << 8), bp.comp, bp.sf, bp.sf - open_c};
+            stack[sp + 3] = Task{t.tb, t.tb + qv2, t.pb, t.pb + qh, cbq | (TM_B << 8), bq.comp, bq.sf, bq.sf - open_q};
+          }
+          sp += 4;
+        }
+        if (top_o) penalty_o = bp.score;
+        top_o = false;
+      }
+      if (top) penalty = bp.score;
+      top = false;
+      __syncthreads();
+    }
+    const int failed_in = cur;
+    if (TWINS) face(TM_A);  // em / penalty: A's, em_o / penalty_o: B's
+    bool write_a = run_mode == TM_A, write_b = run_mode == TM_B;
+    if (TWINS && run_mode == TM_SHARED) {
+      if (status == ST_OK) write_a = write_b = true;
+      else if (status == ST_TWIN_REDO) todo = 3;
+      else if (failed_in == TM_B) { write_b = true; todo = 1; }
+      else { write_a = true; todo = 2; }
+    }
+    // (the closed-form and base-case penalties are exact too; any penalty above the bound reports as such)
+    const int pair_bound = kp.pair_max_penalty ? kp.pair_max_penalty[pair] : kp.max_penalty;
+    if (status == ST_OK && penalty > pair_bound) {  // (a base-case top level has emitted its ops and counts by now: the record reports none)
+      status = ST_ABOVE_BOUND;
+      em.cnt[0] = em.cnt[1] = em.cnt[2] = em.cnt[3] = 0;
+    }
+    if (tid == 0) {
+      auto record = [&](long long pi, const Emit& e, int pen, int qlen) {
+        DevResult r;
+        r.status = status;
+        r.penalty = status == ST_OK ? pen : status == ST_ABOVE_BOUND ? pair_bound + 1 : 0;
+        r.score = -r.penalty;
+        r.cigar_len = status == ST_OK && !kp.score_only ? (uint32_t)e.n : 0u;
+        r.cigar_off = kp.score_only ? 0 : kp.cigar_off[pi];
+        r.num_matches = e.cnt[0];
+        r.num_mismatches = e.cnt[1];
+        r.num_ins = e.cnt[2];
+        r.num_del = e.cnt[3];
+        r.q_end = e.cnt[0] + e.cnt[1] + e.cnt[3];
+        r.t_end = e.cnt[0] + e.cnt[1] + e.cnt[2];
+        kp.results[pi] = r;
+        if (status == ST_OK) {
+          lstats[STAT_ALIGNED_BP] += (unsigned long long)qlen;
+          lstats[STAT_PAIRS] += 1;
+        }
+      };
+      if constexpr (RANGES) {
+        record(pair, em, penalty, (pair_span_arg, ...)[pair].pe - (pair_span_arg, ...)[pair].pb);
+      } else {
+        if (write_a) record(pair, em, penalty, plenT);
+        if (TWINS && write_b) record(pair_b, em_o, penalty_o, tlenT);
+      }
+      PROF_ADD(STAT_T_TOTAL, tt0);
+      lstats[STAT_WIN_SINGLE] += sh.win_single; lstats[STAT_WIN_MULTI] += sh.win_multi; lstats[STAT_WIN_BASE] += sh.win_base; lstats[STAT_WIN_BASE_MULTI] += sh.win_base_multi;
+      sh.win_single = sh.win_multi = sh.win_base = sh.win_base_multi = 0;
+    }
+    __syncthreads();
+    if (!TWINS || !todo) break;
+    run_mode = (todo & 1) ? TM_A : TM_B;
+    todo &= ~(1 << run_mode);
+    }
+    if (TWINS && pair_b >= 0 && tid == 0) {
+      atomicAdd(&kp.stats[STAT_TWIN_UNITS], 1ULL);
+      atomicAdd(&kp.stats[STAT_TWIN_SHARED], (unsigned long long)tw_shared);
+      atomicAdd(&kp.stats[STAT_TWIN_SOLO], (unsigned long long)tw_solo);
+      atomicAdd(&kp.stats[STAT_TWIN_NONMIRROR], (unsigned long long)tw_nonmirror);
+    }
+  }
+  } else {
   for (;;) {
     if (tid == 0) {
       sh.cur_pair = (long long)atomicAdd(kp.work_counter, 1ULL);
@@ -3558,6 +4003,7 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
       }
     }
     __syncthreads();
+  }
   }
   __syncthreads();
   if (tid == 0) {

@@ -53,8 +53,12 @@
 #include <thread>
 #include <vector>
 
+#include "twin_plan.hpp"
+
 namespace {
-constexpr size_t EV_EXTRA = (awv::STACK_CAP * sizeof(awv::Task) + 3) / 4 + 16;  // uint32 words behind the events: the DFS stack
+// uint32 words behind the events: the DFS stack, then the last-hit table of a twin search (biwfa_device.hpp)
+constexpr size_t EV_EXTRA = (size_t)awv::EV_STACK_WORDS;
+static_assert(awv::EV_STACK_WORDS == (awv::STACK_CAP * sizeof(awv::Task) + 3) / 4 + 16, "DFS stack words");
 
 thread_local std::string g_last_error;
 
@@ -155,6 +159,8 @@ struct awv_engine {
   // per-launch buffers
   DevBuf<int32_t> d_pair_q, d_pair_t, d_pair_rc;
   DevBuf<int32_t> d_pair_bound;  // score-only launches with a bound per pair
+  DevBuf<int32_t> d_unit_first, d_unit_twin;  // twin units (twin_plan.hpp): per dispatch unit its entry and its swapped entry
+  uint64_t twin_stats[4] = {0, 0, 0, 0};  // last call: awv_twin_stats
   DevBuf<awvr::Span> d_pair_span;  // range launches: the rectangle of every pair
   DevBuf<uint64_t> d_cigar_off;
   DevBuf<awv::DevResult> d_results;
@@ -341,6 +347,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
   if (int rc = check_penalties(pen, dp)) return rc;
   HIP_TRY(hipSetDevice(e->device));
   e->stats = awv_stats{};
+  for (uint64_t& v : e->twin_stats) v = 0;
   if (npairs == 0) return AWV_OK;
   for (int64_t i = 0; i < npairs; ++i) {
     if (pairs[i].q_idx < 0 || pairs[i].q_idx >= s.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= s.n)
@@ -381,9 +388,10 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
   const int sb_cap = (int)sb;
   const int wb_cap = ((2 * sb_cap + 9 + 2 * COL_PAD) + 63) & ~63;
   // dynamic LDS: metadata region (BiWFA ring metadata, aliased with the base-case table) + sequences
-  auto lds_meta_bytes = [&](size_t meta_elem) {
-    return ((size_t)2 * NCOMP * ring * meta_elem + (size_t)4 * ring * sizeof(int) + (size_t)dp.scope * NCOMP * sizeof(int) + 15) &
-           ~(size_t)15;
+  auto lds_meta_bytes = [&](size_t meta_elem, bool twin_rec) {
+    // (the last 32 bytes: the swapped pair's breakpoint of a twin search, biwfa_device.hpp bialign_overlap)
+    return ((size_t)2 * NCOMP * ring * meta_elem + (size_t)4 * ring * sizeof(int) + (size_t)dp.scope * NCOMP * sizeof(int) +
+            (twin_rec ? sizeof(awv::Breakpoint) : 0) + 15) & ~(size_t)15;
   };
 
 #ifdef AWV_DEBUG_KNOBS
@@ -406,13 +414,16 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       tl = s.len[pairs[gi].t_idx];
     }
   };
-  std::vector<int32_t> hq, ht, hrc, hbound;
+  std::vector<int32_t> hq, ht, hrc, hbound, hufirst, hutwin;
+  // twin units only where the plain alignment or the plain score is asked for: whole pairs, no bound, re-runs allowed
+  const bool twin_ok = max_penalty == INT_MAX && !pair_bound && !spans && !cout &&
+                       !(e->cfg.flags & (AWV_F_NO_TWIN | AWV_F_NO_RERUN));
   std::vector<awvr::Span> hspan;
   std::vector<uint64_t> hoff;
   std::vector<awv_result> hres;
   int64_t first = 0;
   double kernel_ms = 0, h2d_ms = 0, d2h_ms = 0;
-  unsigned long long stat_tot[STAT_N] = {0};
+  unsigned long long stat_tot[STAT_N_DEV] = {0};
   uint64_t launches = 0;
   // With several batches in a call, the sink of batch i (the caller's formatting and output) runs on a
   // helper thread while batch i+1 is carved, launched and copied back.  It is joined before the next
@@ -488,7 +499,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
     if (int rc = e->d_cigar_off.reserve((size_t)n)) return rc;
     if (int rc = e->d_results.reserve((size_t)n)) return rc;
     if (int rc = e->d_cigar.reserve((size_t)arena + 64)) return rc;
-    if (int rc = e->d_counters.reserve(1 + STAT_N)) return rc;
+    if (int rc = e->d_counters.reserve(1 + STAT_N_DEV)) return rc;
     static_assert(sizeof(awv_result) == sizeof(DevResult), "result layout");
     hres.assign((size_t)n, awv_result{});
     // One group of the batch = one kernel flavour: `wide` pairs get a 256-thread workgroup each (four
@@ -546,7 +557,11 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
     // dynamic LDS = ring metadata (16-bit entries with 16-bit rows) + staging of the 2-bit packed
     // sequences: what the largest pair needs, within 160 KB / (16 waves per CU) per workgroup;
     // sub-problems that do not fit read global memory instead
-    const size_t lds_meta = lds_meta_bytes(narrow && !wide_meta ? sizeof(RowMeta16) : sizeof(RowMeta));
+    // twin units only in a group that runs the kernel built with them: one wave per pair, 16-bit rows.  Only
+    // there do the LDS metadata (32 B: the twin record) and the event arena (the last-hit table) grow.
+    const bool twin_here = twin_ok && waves == 1 && width == 0;
+    const size_t ev_extra = EV_EXTRA + (twin_here ? (size_t)awv::EV_TWIN_WORDS : 0);
+    const size_t lds_meta = lds_meta_bytes(narrow && !wide_meta ? sizeof(RowMeta16) : sizeof(RowMeta), twin_here);
     const size_t seq_need = ((((size_t)g_maxlen + 15) / 16 + 2) * 2 + 10) * 4;
     const size_t lds_budget = (size_t)(160 * 1024 / (WAVES_PER_SIMD * 256 / wg)) - STATIC_LDS_RESERVE;
     size_t lds_seq = (e->cfg.flags & AWV_F_NO_PACKED_SEQ) ? 0 : (lds_meta < lds_budget ? std::min(seq_need, lds_budget - lds_meta) : 0);
@@ -557,7 +572,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
     // per-workgroup arenas as a function of the row capacity (columns)
     const size_t budget = e->cfg.max_scratch_bytes > 0 ? (size_t)e->cfg.max_scratch_bytes : (size_t)160 << 30;
     auto per_slot = [&](int wc) {
-      return (size_t)2 * NCOMP * ring * wc * esz + hist_stride + (size_t)(wc + EV_EXTRA) * sizeof(uint32_t);
+      return (size_t)2 * NCOMP * ring * wc * esz + hist_stride + (size_t)(wc + ev_extra) * sizeof(uint32_t);
     };
     // Row capacity of the first attempt.  A wavefront at score s spans at most ~2 s / min(e) diagonals,
     // far fewer than plen + tlen for similar sequences; when full-width rows would not leave room for
@@ -575,7 +590,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
     }
     int wcap = std::min(wcap_full, std::max(std::max(8192, (wcap_full / 2 + 255) & ~255), (2 * g_maxdelta + 4096 + 255) & ~255));
     if (per_slot(wcap) * (size_t)nslots_want > budget) {
-      const size_t fixed = hist_stride + EV_EXTRA * sizeof(uint32_t);
+      const size_t fixed = hist_stride + ev_extra * sizeof(uint32_t);
       const size_t per_col = (size_t)2 * NCOMP * ring * esz + sizeof(uint32_t);
       const size_t share = budget / (size_t)nslots_want;
       long long wc = share > fixed ? (long long)((share - fixed) / per_col) : 0;
@@ -592,7 +607,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
     for (int wc = wcap;;) {
       const int64_t m = (int64_t)hq.size();
       const size_t ring_stride = (size_t)2 * NCOMP * ring * wc * esz;
-      const size_t ev_stride = (size_t)wc + EV_EXTRA;  // run-length events + the DFS stack
+      const size_t ev_stride = (size_t)wc + ev_extra;  // run-length events + the DFS stack
       int nslots = (int)std::min<int64_t>(nslots_g, m);
       {  // keep the per-workgroup arenas inside the scratch budget (default 160 GiB of the 288 GB HBM)
         const size_t fit = std::max<size_t>(1, budget / per_slot(wc));
@@ -663,7 +678,34 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
         if (int rc = e->d_pair_span.reserve((size_t)m)) return rc;
         HIP_TRY(hipMemcpyAsync(e->d_pair_span.p, hspan.data(), (size_t)m * sizeof(awvr::Span), hipMemcpyHostToDevice, e->stream));
       }
-      HIP_TRY(hipMemsetAsync(e->d_counters.p, 0, (1 + STAT_N) * sizeof(unsigned long long), e->stream));
+      // ---- twin units: an entry (q, t) and its swapped entry (t, q) of this launch share their breakpoint searches (DESIGN.md
+      // 4.20).  Entries are in descending cost order and a twin costs what its partner costs, so units ordered by their
+      // summed cost are the twin units in entry order, then the single ones.
+      int64_t nunits = m;
+      if (twin_here) {
+        const awvt::TwinPlan tp = awvt::plan_twins(hq.data(), ht.data(), hrc.data(), (size_t)m);
+        std::vector<size_t> uo(tp.first.size());
+        for (size_t u = 0; u < uo.size(); ++u) uo[u] = u;
+        auto ucost = [&](size_t u) {
+          int ql, tl;
+          pair_lens(first + amap[(size_t)tp.first[u]], ql, tl);
+          const uint64_t c = (uint64_t)((int64_t)ql + tl + 4 * std::llabs((int64_t)ql - tl));
+          return tp.twin[u] >= 0 ? 2 * c : c;
+        };
+        std::stable_sort(uo.begin(), uo.end(), [&](size_t a, size_t b) { return ucost(a) > ucost(b); });
+        hufirst.resize(uo.size());
+        hutwin.resize(uo.size());
+        for (size_t u = 0; u < uo.size(); ++u) {
+          hufirst[u] = tp.first[uo[u]];
+          hutwin[u] = tp.twin[uo[u]];
+        }
+        nunits = (int64_t)uo.size();
+        if (int rc = e->d_unit_first.reserve((size_t)nunits)) return rc;
+        if (int rc = e->d_unit_twin.reserve((size_t)nunits)) return rc;
+        HIP_TRY(hipMemcpyAsync(e->d_unit_first.p, hufirst.data(), (size_t)nunits * 4, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(e->d_unit_twin.p, hutwin.data(), (size_t)nunits * 4, hipMemcpyHostToDevice, e->stream));
+      }
+      HIP_TRY(hipMemsetAsync(e->d_counters.p, 0, (1 + STAT_N_DEV) * sizeof(unsigned long long), e->stream));
       HIP_TRY(hipEventRecord(e->ev1, e->stream));
       HIP_TRY(hipEventSynchronize(e->ev1));
       HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
@@ -680,7 +722,10 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       kp.pair_q = e->d_pair_q.p;
       kp.pair_t = e->d_pair_t.p;
       kp.pair_rc = e->d_pair_rc.p;
-      kp.npairs = m;
+      kp.npairs = nunits;  // dispatch units: entries, or entries with their twins
+      kp.unit_first = twin_here ? e->d_unit_first.p : nullptr;
+      kp.unit_twin = twin_here ? e->d_unit_twin.p : nullptr;
+      kp.twin_levels = (e->cfg.flags & AWV_F_TWIN_TOP_ONLY) ? 1 : INT_MAX;
       kp.pen = dp;
       kp.ring = ring;
       // 32-bit rows: sweeps of at most TMAX32 scores, at most CHAIN_MAX32 of them chained (a lane vector is four registers)
@@ -765,13 +810,13 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       tres.resize((size_t)m);
       HIP_TRY(hipEventRecord(e->ev0, e->stream));
       HIP_TRY(hipMemcpyAsync(tres.data(), e->d_results.p, (size_t)m * sizeof(awv_result), hipMemcpyDeviceToHost, e->stream));
-      unsigned long long hstat[1 + STAT_N];
+      unsigned long long hstat[1 + STAT_N_DEV];
       HIP_TRY(hipMemcpyAsync(hstat, e->d_counters.p, sizeof(hstat), hipMemcpyDeviceToHost, e->stream));
       HIP_TRY(hipEventRecord(e->ev1, e->stream));
       HIP_TRY(hipEventSynchronize(e->ev1));
       HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
       d2h_ms += ms;
-      for (int i = 0; i < STAT_N; ++i) stat_tot[i] += hstat[1 + i];
+      for (int i = 0; i < STAT_N_DEV; ++i) stat_tot[i] += hstat[1 + i];
       // ---- scatter; collect the pairs to re-run with wider rows
       std::vector<int64_t> again;
       for (int64_t i = 0; i < m; ++i) {
@@ -962,6 +1007,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
   e->stats.clock_ticks = stat_tot[STAT_CLK_TICKS];
   e->stats.clock_tick_khz = (uint64_t)e->wall_clock_khz;
   e->stats.deep_cell_steps = stat_tot[STAT_DEEP_CELLS];
+  for (int i = 0; i < 4; ++i) e->twin_stats[i] = stat_tot[STAT_TWIN_UNITS + i];
   return AWV_OK;
 }
 
@@ -1304,6 +1350,12 @@ int align_one_core(awv_engine* e, const awv_penalties* pen, const uint8_t* patte
 }  // namespace
 
 extern "C" {
+
+int awv_twin_stats(const awv_engine* e, uint64_t out[4]) {
+  if (!e || !out) return fail(AWV_ERR_ARG, "twin_stats: null argument");
+  for (int i = 0; i < 4; ++i) out[i] = e->twin_stats[i];
+  return AWV_OK;
+}
 
 int awv_engine_stats(const awv_engine* e, awv_stats* out) {
   if (!e || !out) return fail(AWV_ERR_ARG, "stats: null argument");

@@ -30,6 +30,8 @@ AWV_F_NO_CHAIN = 128
 AWV_F_NO_WIDE16 = 256
 AWV_F_NO_DEEP = 512
 AWV_F_NO_RERUN = 1024
+AWV_F_NO_TWIN = 2048
+AWV_F_TWIN_TOP_ONLY = 4096
 #: WFA orientation (awv_orient_pairs / awv_orient_decide)
 AWV_ORIENT_FORWARD = 0
 AWV_ORIENT_REVERSE = 1
@@ -69,7 +71,8 @@ EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine
            "awv_align_pairs_verified", "awv_verify_cigars", "awv_verify_one_host", "awv_engine_verify_stats",
            "awv_align_ranges", "awv_align_ranges_verified", "awv_score_ranges", "awv_verify_ranges",
            "awv_align_pairs_bounded", "awv_align_ranges_bounded", "awv_divergence_bound",
-           "awv_clip_one_host", "awv_clip_cigars", "awv_align_pairs_clipped", "awv_align_ranges_clipped", "awv_engine_clip_stats")
+           "awv_clip_one_host", "awv_clip_cigars", "awv_align_pairs_clipped", "awv_align_ranges_clipped", "awv_engine_clip_stats",
+           "awv_twin_stats")
 
 
 class EngineConfig(C.Structure):
@@ -157,6 +160,7 @@ def load():
                                     C.c_void_p, C.c_void_p, C.c_size_t]
         L.awv_score_pairs.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         L.awv_engine_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
+        L.awv_twin_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64 * 4)]
         L.awv_score_pairs_bounded.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.awv_orient_pairs.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
         L.awv_orient_decide.argtypes = [C.POINTER(Penalties), C.c_int32, C.c_int32, C.c_int32, C.c_int32]
@@ -466,6 +470,15 @@ class Engine:
         if rc != AWV_OK:
             raise EngineError(rc, "awv_engine_stats")
         return st
+
+    def twin_stats(self):
+        """awv_twin_stats of the last align_pairs call: (twin units, searches run shared, searches run per orientation
+        inside twin units, shared searches whose two breakpoints were not mirrors)."""
+        out = (C.c_uint64 * 4)()
+        rc = load().awv_twin_stats(self._h, C.byref(out))
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_twin_stats")
+        return tuple(int(v) for v in out)
 
 
 def verify_one_host(scores, pattern, text, cigar, claimed):

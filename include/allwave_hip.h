@@ -105,6 +105,9 @@ typedef struct {
 #define AWV_F_NO_CHAIN 128     /* multi-step passes of one sweep only (no chaining of sweeps through registers / LDS) */
 #define AWV_F_NO_DEEP 512      /* the margin zone of a breakpoint search runs step by step (the round-2 path) instead of in passes that store every I/D row */
 #define AWV_F_SINGLE_STEP 64   /* never use multi-step passes (every step stores all five rows; the round-1 kernel path) */
+#define AWV_F_NO_TWIN 2048     /* align every entry of a pair list on its own (default: an entry (q, t) and its swapped entry (t, q) in the same launch
+                                  are aligned as one unit that shares their breakpoint searches) */
+#define AWV_F_TWIN_TOP_ONLY 4096 /* tests and A/B measurements only: such units share their top-level search only (default: every search whose sub-problem is still a mirror image) */
 
 /* penalties as allwave passes them to lib_wfa2 (src/alignment.rs:263-289) */
 typedef struct {
@@ -261,6 +264,10 @@ int awv_orient_decide(const awv_penalties* pen, int32_t lo_f, int32_t hi_f, int3
 int32_t awv_orient_settling_bound(const awv_penalties* pen, int32_t known_is_reverse, int32_t penalty);
 
 int awv_engine_stats(const awv_engine* e, awv_stats* out);
+/* Twin units of the last awv_align_pairs[_verified] or unbounded awv_score_pairs call: out[0] units made of an entry and its swapped entry, out[1] breakpoint
+ * searches run once for both, out[2] searches run per orientation inside such units, out[3] shared searches whose two
+ * breakpoints were not mirror images of each other (a tie that the two orientations break differently). */
+int awv_twin_stats(const awv_engine* e, uint64_t out[4]);
 
 /* ---- verification on the device (csrc/verify.hip, csrc/verify_device.hpp) ---------------------------------------------
  * What the reference's validators check (validation.rs verify_cigar_alignment, validation_simple.rs, wfa.rs
