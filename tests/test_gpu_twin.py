@@ -8,45 +8,12 @@ import pytest
 
 import repeats as R
 import twin_cases as TC
-from util import DEFAULT_2P, PENALTY_SETS, check_against_oracle, mutate, rand_seq
+from util import DEFAULT_2P, PENALTY_SETS, check_against_oracle
 
 pytestmark = pytest.mark.gpu
 
-_SWAP = bytes.maketrans(b"ID", b"DI")
-_RC = bytes.maketrans(b"ACGTacgt", b"TGCATGCA")
-
-
-def rc(s):
-    return bytes(s).translate(_RC)[::-1]
-
-
-def same_records(a, b):
-    ra, ca = a
-    rb, cb = b
-    for name in ra.dtype.names:
-        assert (ra[name] == rb[name]).all(), name
-    assert ca == cb
-
-
-def oracle_records(oracle, seqs, pairs, scores):
-    al = oracle.Aligner(scores)
-    out = []
-    for p in pairs:
-        q = rc(seqs[p[0]]) if len(p) > 2 and p[2] else seqs[p[0]]
-        out.append(al.align(q, seqs[p[1]]))
-    return out
-
-
-def check_records(got, want, seqs, pairs):
-    """Every field of every record and every op byte against the oracle's (penalty, ops)."""
-    res, cigs = got
-    for i, (pen, ops) in enumerate(want):
-        assert res["status"][i] == 0 and res["penalty"][i] == pen and res["score"][i] == -pen, (i, pairs[i])
-        assert cigs[i] == ops and res["cigar_len"][i] == len(ops), (i, pairs[i])
-        c = [ops.count(k) for k in b"MXID"]
-        assert [res["num_matches"][i], res["num_mismatches"][i], res["num_ins"][i], res["num_del"][i]] == c, (i, pairs[i])
-        assert res["q_end"][i] == c[0] + c[1] + c[3] == len(seqs[pairs[i][0]]), (i, pairs[i])
-        assert res["t_end"][i] == c[0] + c[1] + c[2] == len(seqs[pairs[i][1]]), (i, pairs[i])
+_SWAP = TC.SWAP
+rc, same_records, oracle_records, check_records = TC.rc, TC.same_records, TC.oracle_records, TC.check_records
 
 
 @pytest.fixture(scope="module")
@@ -83,14 +50,8 @@ def forms_twins(waves, width):
 
 @pytest.fixture(scope="module")
 def twelve():
-    """12 sequences of 1.2-3 kbp, 3-15 % apart, the first of 1.5 kbp: their 132 directed pairs = 66 twin units; and one
-    more pair, the 1.5 kbp sequence against one of 5 kbp, listed in one direction only."""
-    rng = random.Random("twin-twelve")
-    base = rand_seq(rng, 5000)
-    lens = [1500] + [rng.randint(1200, 3000) for _ in range(11)] + [5000]
-    seqs = [mutate(base[:n], rng.uniform(0.015, 0.075), rng) for n in lens]  # two mutated copies: 3-15 % between them
-    pairs = [(i, j) for i in range(12) for j in range(12) if i != j] + [(0, 12)]
-    return seqs, pairs
+    """twin_cases.twelve: 66 twin units and one single entry."""
+    return TC.twelve()
 
 
 @pytest.mark.parametrize("scores", PENALTY_SETS)
