@@ -10,6 +10,7 @@
 #include "planner_device.hpp"  // (the sketches and scratch of device pair planning, planner.hip)
 #include "verify_device.hpp"   // (the per-batch check of awv_align_pairs_verified, verify.hip)
 #include "clip_device.hpp"     // (the per-batch clip of awv_align_pairs_clipped, clip.hip)
+#include "split_device.hpp"    // (the per-batch split of awv_align_pairs_split, split.hip)
 #include "kernels_awv.hpp"  // (the awv:: kernels themselves are instantiated in kernels_awv.hip -- here only the types)
 #define AWV_NS awv
 #define AWV_WG 64
@@ -171,6 +172,7 @@ struct awv_engine {
   awp::PlanState* plan = nullptr;  // planner.hip: sketches of `seqs` and planning scratch (released with a new set)
   awvf::State* verify = nullptr;   // verify.hip: buffers and stats of the verify launches
   awvc::State* clip = nullptr;     // clip.hip: buffers and stats of the clip launches
+  awvs::State* split = nullptr;    // split.hip: likewise for the split launches
 };
 
 namespace {
@@ -337,10 +339,18 @@ long long worst_case_penalty(const awv::DevPenalties& d, long long n) {
 // coordinates and already validated, instead of the whole of them -- every length below is then the rectangle's
 // cout (nullable; awv_align_pairs_clipped): every batch's op strings are clipped on the device under match_bonus, after the
 // check and before the batch's CIGARs are copied back
+// split (nullable; awv_align_pairs_split): likewise split into all segments of at least split->min_score, into the caller's
+// slot layout (already checked against the slot rule)
+struct SplitOut {
+  int64_t min_score;
+  const uint64_t* seg_first;
+  awv_split_index* iout;
+  awv_clip_result* sout;
+};
 int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
                awv_result* out, awv_sink sink, void* user, bool score_only = false, int max_penalty = INT_MAX,
                const int32_t* pair_bound = nullptr, awv_verify_result* vout = nullptr, const awvr::Span* spans = nullptr,
-               awv_clip_result* cout = nullptr, int32_t match_bonus = 0) {
+               awv_clip_result* cout = nullptr, int32_t match_bonus = 0, const SplitOut* split = nullptr) {
   using namespace awv;
   if (npairs < 0 || (npairs > 0 && !pairs)) return fail(AWV_ERR_ARG, "align_pairs: null pairs");
   DevPenalties dp{};
@@ -947,6 +957,11 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       if (int rc = awvc::clip_batch(e, pen, match_bonus, n, hres.data(), e->d_cigar.p, arena, cout + first)) return rc;
       lap("batch clipped");
     }
+    if (split) {
+      if (int rc = awvs::split_batch(e, pen, match_bonus, split->min_score, n, hres.data(), e->d_cigar.p, arena, split->seg_first + first,
+                                     split->iout + first, split->sout)) return rc;
+      lap("batch split");
+    }
     if (want_cigar) {
       e->h_cigar.resize((size_t)arena + 64);
       lap("host cigar buffer");
@@ -1065,6 +1080,8 @@ void awv_engine_destroy(awv_engine* e) {
   e->verify = nullptr;
   awvc::state_release(e->clip);
   e->clip = nullptr;
+  awvs::state_release(e->split);
+  e->split = nullptr;
   e->seqs.release();
   e->ring_mem.release();
   e->hist_mem.release();
@@ -1178,9 +1195,24 @@ int split_ranges(const SeqSet& s, const awv_range_pair* ranges, int64_t n, std::
       return fail(AWV_ERR_ARG, std::string(who) + ": range " + std::to_string(i) + " names a sequence index or an interval out of range");
   return AWV_OK;
 }
+// what every splitting call refuses before anything is launched, and the slot rule for one entry
+int check_split_args(int32_t match_bonus, const SplitOut& sp, int64_t n) {
+  if (match_bonus < 1 || match_bonus > AWV_CLIP_MAX_BONUS) return fail(AWV_ERR_ARG, "align_split: match_bonus must be in [1, 32767]");
+  if (sp.min_score < 1) return fail(AWV_ERR_ARG, "align_split: min_score must be >= 1");
+  if (!sp.seg_first || (n > 0 && !sp.iout)) return fail(AWV_ERR_ARG, "align_split: null seg_first or iout");
+  for (int64_t i = 0; i < n; ++i)
+    if (sp.seg_first[i + 1] < sp.seg_first[i]) return fail(AWV_ERR_ARG, "align_split: seg_first must ascend");
+  if (n > 0 && sp.seg_first[n] > sp.seg_first[0] && !sp.sout) return fail(AWV_ERR_ARG, "align_split: null sout");
+  return AWV_OK;
+}
+int check_split_slots(const SplitOut& sp, int64_t i, int32_t match_bonus, int64_t shorter) {
+  if (sp.seg_first[i + 1] - sp.seg_first[i] < (uint64_t)awvs::slots(match_bonus, sp.min_score, shorter))
+    return fail(AWV_ERR_ARG, "align_split: entry " + std::to_string(i) + " owns fewer slots than awv_split_slots(a, min_score, min(plen, tlen))");
+  return AWV_OK;
+}
 int align_ranges_core(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, awv_result* out,
                       awv_verify_result* vout, awv_sink sink, void* user, const int32_t* max_penalty = nullptr,
-                      awv_clip_result* cout = nullptr, int32_t match_bonus = 0) {
+                      awv_clip_result* cout = nullptr, int32_t match_bonus = 0, const SplitOut* split = nullptr) {
   if (n < 0 || (n > 0 && !ranges)) return fail(AWV_ERR_ARG, "align_ranges: null ranges");
   if (e->seqs.n == 0 && n > 0) return fail(AWV_ERR_STATE, "align_ranges before set_sequences");
   std::vector<awv_pair> pairs;
@@ -1188,13 +1220,18 @@ int align_ranges_core(awv_engine* e, const awv_penalties* pen, const awv_range_p
   if (int rc = split_ranges(e->seqs, ranges, n, pairs, spans, "align_ranges")) return rc;
   if (vout) awvf::stats_reset(e->verify);
   if (n == 0) return align_core(e, e->seqs, pen, nullptr, 0, out, sink, user);
+  if (split)  // the slot rule over the two interval lengths, before anything is launched
+    for (int64_t i = 0; i < n; ++i) {
+      const awvr::Span& sp = spans[(size_t)i];
+      if (int rc = check_split_slots(*split, i, match_bonus, std::min(sp.pe - sp.pb, sp.te - sp.tb))) return rc;
+    }
   std::vector<int32_t> pb;
   if (max_penalty) {
     pb.resize((size_t)n);
     for (int64_t i = 0; i < n; ++i) pb[(size_t)i] = norm_bound(max_penalty[i]);
   }
   return align_core(e, e->seqs, pen, pairs.data(), n, out, sink, user, false, INT_MAX, max_penalty ? pb.data() : nullptr, vout, spans.data(),
-                    cout, match_bonus);
+                    cout, match_bonus, split);
 }
 // what every clipping call refuses before anything is launched
 int check_clip_args(const awv_clip_result* cout, int32_t match_bonus) {
@@ -1228,6 +1265,43 @@ int awv_align_ranges_clipped(awv_engine* e, const awv_penalties* pen, const awv_
   if (int rc = check_clip_args(cout, match_bonus)) return rc;
   awvc::stats_reset(e->clip);
   AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, out, vout, sink, user, max_penalty, cout, match_bonus);)
+}
+
+int awv_align_pairs_split(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const int32_t* max_penalty,
+                          int32_t match_bonus, int64_t min_score, awv_result* out, awv_verify_result* vout, const uint64_t* seg_first,
+                          awv_split_index* iout, awv_clip_result* sout, awv_sink sink, void* user) {
+  if (!e) return fail(AWV_ERR_ARG, "null engine");
+  if (npairs < 0 || (npairs > 0 && !pairs)) return fail(AWV_ERR_ARG, "align_pairs: null pairs");
+  const SplitOut sp{min_score, seg_first, iout, sout};
+  if (int rc = check_split_args(match_bonus, sp, npairs)) return rc;
+  if (e->seqs.n == 0 && npairs > 0) return fail(AWV_ERR_STATE, "align_pairs before set_sequences");
+  for (int64_t i = 0; i < npairs; ++i) {
+    if (pairs[i].q_idx < 0 || pairs[i].q_idx >= e->seqs.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= e->seqs.n)
+      return fail(AWV_ERR_ARG, "align_pairs: sequence index out of range");
+    if (int rc = check_split_slots(sp, i, match_bonus, std::min(e->seqs.len[pairs[i].q_idx], e->seqs.len[pairs[i].t_idx]))) return rc;
+  }
+  if (vout) awvf::stats_reset(e->verify);
+  awvs::stats_reset(e->split);
+  AWV_GUARDED(
+    std::vector<int32_t> pb;
+    if (max_penalty) {
+      pb.resize((size_t)npairs);
+      for (int64_t i = 0; i < npairs; ++i) pb[(size_t)i] = norm_bound(max_penalty[i]);
+    }
+    return align_core(e, e->seqs, pen, pairs, npairs, out, sink, user, false, INT_MAX, max_penalty && npairs > 0 ? pb.data() : nullptr, vout,
+                      nullptr, nullptr, match_bonus, &sp);
+  )
+}
+
+int awv_align_ranges_split(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const int32_t* max_penalty,
+                           int32_t match_bonus, int64_t min_score, awv_result* out, awv_verify_result* vout, const uint64_t* seg_first,
+                           awv_split_index* iout, awv_clip_result* sout, awv_sink sink, void* user) {
+  if (!e) return fail(AWV_ERR_ARG, "null engine");
+  if (n < 0) return fail(AWV_ERR_ARG, "align_ranges: null ranges");
+  const SplitOut sp{min_score, seg_first, iout, sout};
+  if (int rc = check_split_args(match_bonus, sp, n)) return rc;
+  awvs::stats_reset(e->split);
+  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, out, vout, sink, user, max_penalty, nullptr, match_bonus, &sp);)
 }
 
 int awv_align_pairs_bounded(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const int32_t* max_penalty,
@@ -1386,6 +1460,7 @@ awp::PlanState*& awv_internal_plan(awv_engine* e) { return e->plan; }
 // ---- what verify.hip keeps in an engine, and the arena budget awv_verify_cigars splits its call by (verify_device.hpp) ----
 awvf::State*& awv_internal_verify(awv_engine* e) { return e->verify; }
 awvc::State*& awv_internal_clip(awv_engine* e) { return e->clip; }
+awvs::State*& awv_internal_split(awv_engine* e) { return e->split; }
 uint64_t awv_internal_max_arena(const awv_engine* e) { return e->cfg.max_arena_bytes > 0 ? (uint64_t)e->cfg.max_arena_bytes : (uint64_t)8 << 30; }
 int awv_internal_fail(int code, const std::string& msg) { return fail(code, msg); }
 int awv_internal_check_penalties(const awv_penalties* pen) { return check_penalty_signs(pen); }

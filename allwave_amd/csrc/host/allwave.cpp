@@ -380,6 +380,25 @@ void align_ranges(const std::vector<Sequence>& sequences, const std::vector<Alig
   if (clip_stats) *clip_stats = it.last_clip_stats();
 }
 
+void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
+                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
+                  awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
+                  BoundStats* bound_stats, int clip_match_bonus, int64_t clip_min_score, ClipStats* clip_stats, int split_match_bonus,
+                  int64_t split_min_score, SplitStats* split_stats) {
+  AllPairIterator it = AllPairIterator::for_ranges(sequences, ranges, std::move(params));
+  it.with_devices(devices).with_verify(verify);
+  if (clip_match_bonus != 0) it.with_clip(clip_match_bonus, clip_min_score);
+  if (split_match_bonus != 0) it.with_split(split_match_bonus, split_min_score);
+  if (max_penalty) it.with_max_penalty(*max_penalty);
+  if (max_divergence) it.with_max_divergence(*max_divergence);
+  it.for_each_with_callback(callback);
+  if (failures) *failures = it.verify_failures();
+  if (verify_stats) *verify_stats = it.last_verify_stats();
+  if (bound_stats) *bound_stats = it.last_bound_stats();
+  if (clip_stats) *clip_stats = it.last_clip_stats();
+  if (split_stats) *split_stats = it.last_split_stats();
+}
+
 AllPairIterator::AllPairIterator(const std::vector<Sequence>& sequences, AlignmentParams params)
     : AllPairIterator(sequences, std::move(params), true) {}
 
@@ -537,14 +556,25 @@ AllPairIterator AllPairIterator::with_sparsification(SparsificationStrategy stra
   it.max_divergence_ = max_divergence_;
   it.clip_bonus_ = clip_bonus_;
   it.clip_min_score_ = clip_min_score_;
+  it.split_bonus_ = split_bonus_;
+  it.split_min_score_ = split_min_score_;
   return it;
 }
 AllPairIterator& AllPairIterator::with_verify(bool on) { verify_ = on; return *this; }
 AllPairIterator& AllPairIterator::with_clip(int match_bonus, int64_t min_score) {
   if (match_bonus < 1 || match_bonus > AWV_CLIP_MAX_BONUS) throw std::invalid_argument("with_clip: match_bonus must be in [1, 32767]");
   if (min_score < 1) throw std::invalid_argument("with_clip: min_score must be >= 1");
+  if (split()) throw std::invalid_argument("with_clip: not together with with_split");
   clip_bonus_ = match_bonus;
   clip_min_score_ = min_score;
+  return *this;
+}
+AllPairIterator& AllPairIterator::with_split(int match_bonus, int64_t min_score) {
+  if (match_bonus < 1 || match_bonus > AWV_CLIP_MAX_BONUS) throw std::invalid_argument("with_split: match_bonus must be in [1, 32767]");
+  if (min_score < 1) throw std::invalid_argument("with_split: min_score must be >= 1");
+  if (clip()) throw std::invalid_argument("with_split: not together with with_clip");
+  split_bonus_ = match_bonus;
+  split_min_score_ = min_score;
   return *this;
 }
 AllPairIterator& AllPairIterator::with_max_penalty(int max_penalty) {
@@ -567,14 +597,25 @@ std::optional<AlignmentResult> AllPairIterator::next() {  // iterator.rs:151-171
     const size_t first = next_pos_, cnt = std::min(next_chunk_, pairs_.size() - first);
     std::vector<AlignmentResult> buf(cnt);
     std::vector<uint8_t> have(cnt, 0);  // (a pair above a bound is not delivered: its slot stays empty and is skipped)
+    std::vector<std::vector<AlignmentResult>> more(split() ? cnt : 0);  // a splitting run: a pair's segments after its first
     run(first, cnt, [&](const Batch& b) {  // (every entry has its own slot of buf: no lock)
       for (int64_t i = 0; i < b.n; ++i) {
         const size_t k = b.pair(i);
-        buf[k] = result_at(first + k, b.is_rev(i), b.res[i], b.arena, true, b.clip_at(i));
+        AlignmentResult a = result_at(first + k, b.is_rev(i), b.res[i], b.arena, true, b.clip_at(i));
+        if (have[k]) more[k].push_back(std::move(a));
+        else buf[k] = std::move(a);
         have[k] = 1;
       }
     });
-    if (drops_pairs()) {
+    if (split()) {  // the pairs' segments in pair order, each pair's in column order
+      std::vector<AlignmentResult> flat;
+      for (size_t k = 0; k < cnt; ++k) {
+        if (!have[k]) continue;
+        flat.push_back(std::move(buf[k]));
+        for (auto& a : more[k]) flat.push_back(std::move(a));
+      }
+      buf = std::move(flat);
+    } else if (drops_pairs()) {
       size_t w = 0;
       for (size_t k = 0; k < cnt; ++k)
         if (have[k]) {
@@ -630,14 +671,25 @@ void AllPairParallelIterator::for_each_with_callback(const Callback& cb) {
 std::vector<AlignmentResult> AllPairParallelIterator::collect() {
   std::vector<AlignmentResult> out(it_.pairs_.size());
   std::vector<uint8_t> have(it_.pairs_.size(), 0);
+  std::vector<std::vector<AlignmentResult>> more(it_.split() ? it_.pairs_.size() : 0);  // a splitting run: a pair's segments after its first
   it_.run([&](const AllPairIterator::Batch& b) {  // (every pair has its own slot of `out`: no lock)
     for (int64_t i = 0; i < b.n; ++i) {
       const size_t k = b.pair(i);
-      out[k] = it_.result_at(k, b.is_rev(i), b.res[i], b.arena, true, b.clip_at(i));
+      AlignmentResult a = it_.result_at(k, b.is_rev(i), b.res[i], b.arena, true, b.clip_at(i));
+      if (have[k]) more[k].push_back(std::move(a));
+      else out[k] = std::move(a);
       have[k] = 1;
     }
   });
-  if (it_.drops_pairs()) {  // (pairs above a bound or without a clip are not delivered: the kept ones, in pair-list order)
+  if (it_.split()) {  // the pairs' segments in pair order, each pair's in column order
+    std::vector<AlignmentResult> flat;
+    for (size_t k = 0; k < out.size(); ++k) {
+      if (!have[k]) continue;
+      flat.push_back(std::move(out[k]));
+      for (auto& a : more[k]) flat.push_back(std::move(a));
+    }
+    out = std::move(flat);
+  } else if (it_.drops_pairs()) {  // (pairs above a bound or without a clip are not delivered: the kept ones, in pair-list order)
     size_t w = 0;
     for (size_t k = 0; k < out.size(); ++k)
       if (have[k]) {
@@ -704,9 +756,20 @@ void add_stats(awv_stats& acc, const awv_stats& x, bool same_engine) {
 // rp (nullable): the batch is these n interval pairs -- the same three calls on ranges, `ap` is not read
 // bounds (nullable, alignment calls only): one penalty bound per entry (< 0: none) -- the *_bounded entry points
 // cout (nullable, alignment calls only): the *_clipped entry points under clip_bonus, which take bounds and vout as well
+// sp (nullable, alignment calls only): the *_split entry points, likewise, into the call's own segment storage
+struct SplitCall {
+  int bonus;
+  int64_t min_score;
+  const uint64_t* seg_first;
+  awv_split_index* index;
+  awv_clip_result* seg;
+};
 int engine_call(awv_engine* e, bool score_only, int32_t max_penalty, const awv_penalties& pen, const awv_pair* ap, int64_t n,
                 awv_sink sink, void* user, awv_verify_result* vout, const awv_range_pair* rp = nullptr, const int32_t* align_bounds = nullptr,
-                int clip_bonus = 0, awv_clip_result* cout = nullptr) {
+                int clip_bonus = 0, awv_clip_result* cout = nullptr, const SplitCall* sp = nullptr) {
+  if (sp && !score_only)
+    return rp ? awv_align_ranges_split(e, &pen, rp, n, align_bounds, sp->bonus, sp->min_score, nullptr, vout, sp->seg_first, sp->index, sp->seg, sink, user)
+              : awv_align_pairs_split(e, &pen, ap, n, align_bounds, sp->bonus, sp->min_score, nullptr, vout, sp->seg_first, sp->index, sp->seg, sink, user);
   if (cout && !score_only)
     return rp ? awv_align_ranges_clipped(e, &pen, rp, n, align_bounds, clip_bonus, nullptr, vout, cout, sink, user)
               : awv_align_pairs_clipped(e, &pen, ap, n, align_bounds, clip_bonus, nullptr, vout, cout, sink, user);
@@ -795,6 +858,8 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   std::vector<BoundStats> bst(S);  // per slot: written by its sink calls (which never overlap) and its submitter thread
   const bool clipping = clip() && !call.score_only;
   std::vector<ClipStats> cst(S);   // likewise
+  const bool splitting = split() && !call.score_only;
+  std::vector<SplitStats> sst(S);  // likewise
   auto worker = [&](size_t s) {
     awv_engine* e = nullptr;
     try {
@@ -846,7 +911,9 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
           const awv_clip_result* clip;  // clipping runs: per entry of the call, filled before the entry's sink call
           int64_t clip_min_score;
           ClipStats* cst;
-        } ctx{&batch_cb, rev.data(), idx, &stop, &fail_fn, false, nullptr, -1.0, nullptr, nullptr, 1, nullptr};
+          const SplitCall* sp;  // splitting runs: the call's layout, index and segments, filled before the entry's sink call
+          SplitStats* sst;
+        } ctx{&batch_cb, rev.data(), idx, &stop, &fail_fn, false, nullptr, -1.0, nullptr, nullptr, 1, nullptr, nullptr, nullptr};
         // one penalty bound per entry: the smaller of with_max_penalty's and the one the divergence bound implies
         std::vector<int32_t> bounds;
         std::vector<uint8_t> by_div;
@@ -874,7 +941,7 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
           Ctx* c = (Ctx*)user;
           if (c->stop->load()) return 1;  // another slot failed: stop here, report nothing
           try {
-            if (c->bst || c->clip) {  // a bounded or clipping run: the batch callback sees the kept entries only
+            if (c->bst || c->clip || c->sp) {  // a bounded, clipping or splitting run: the batch callback sees the kept entries only
               std::vector<awv_result> kres;
               std::vector<uint8_t> krev;
               std::vector<size_t> kidx;
@@ -891,6 +958,41 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
                     ++c->bst->above_divergence;
                     continue;
                   }
+                }
+                if (c->sp) {  // a finished pair is delivered as its segments, one entry each (a failed one as it is)
+                  const awv_split_index& ix = c->sp->index[first + i];
+                  if (r.status == AWV_ST_COMPLETED) {
+                    ++c->sst->pairs;
+                    if (ix.code != AWV_CL_OK) {
+                      ++c->sst->empty;
+                      continue;
+                    }
+                    c->sst->segments += (uint64_t)ix.count;
+                  }
+                  const int32_t cnt_seg = r.status == AWV_ST_COMPLETED ? ix.count : 1;
+                  for (int32_t j = 0; j < cnt_seg; ++j) {
+                    kres.push_back(r);
+                    awv_clip_result cl{};
+                    cl.code = AWV_CL_SKIPPED;
+                    if (r.status == AWV_ST_COMPLETED) {
+                      cl = c->sp->seg[c->sp->seg_first[first + i] + (uint64_t)j];
+                      awv_result& s = kres.back();
+                      s.cigar_off += cl.col_beg;
+                      s.cigar_len = cl.col_end - cl.col_beg;
+                      s.num_matches = cl.num_matches;
+                      s.num_mismatches = cl.num_mismatches;
+                      s.num_ins = cl.num_ins;
+                      s.num_del = cl.num_del;
+                      s.penalty = cl.penalty;
+                      s.score = -cl.penalty;
+                      s.q_end = cl.num_matches + cl.num_mismatches + cl.num_del;
+                      s.t_end = cl.num_matches + cl.num_mismatches + cl.num_ins;
+                    }
+                    kclip.push_back(cl);
+                    krev.push_back(c->rev[first + i]);
+                    kidx.push_back(c->idx ? c->idx[first + i] : (size_t)(first + i));
+                  }
+                  continue;
                 }
                 kres.push_back(r);
                 if (c->clip) {  // a finished pair is delivered as its segment (a failed one as it is: the "empty" result)
@@ -919,7 +1021,7 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
                 krev.push_back(c->rev[first + i]);
                 kidx.push_back(c->idx ? c->idx[first + i] : (size_t)(first + i));
               }
-              (*c->cb)(Batch{0, (int64_t)kres.size(), kres.data(), arena, krev.data(), kidx.data(), c->clip ? kclip.data() : nullptr});
+              (*c->cb)(Batch{0, (int64_t)kres.size(), kres.data(), arena, krev.data(), kidx.data(), c->clip || c->sp ? kclip.data() : nullptr});
               return 0;
             }
             (*c->cb)(Batch{first, cnt, res, arena, c->rev, c->idx});
@@ -937,9 +1039,25 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
           ctx.clip_min_score = clip_min_score_;
           ctx.cst = &cst[s];
         }
+        // a splitting run: this call's segment storage, laid out by the engine's own arithmetic over the resident lengths
+        std::vector<uint64_t> seg_first(splitting ? (size_t)m + 1 : 0);
+        std::vector<awv_split_index> six(splitting ? (size_t)std::max<int64_t>(m, 1) : 0);
+        std::vector<awv_clip_result> sseg;
+        SplitCall spc{split_bonus_, split_min_score_, nullptr, nullptr, nullptr};
+        if (splitting) {
+          const int lrc = ranges_ ? awv_split_layout_ranges(e, rp.data(), m, split_bonus_, split_min_score_, seg_first.data())
+                                  : awv_split_layout_pairs(e, ap.data(), m, split_bonus_, split_min_score_, seg_first.data());
+          if (lrc != AWV_OK) throw AlignmentError(std::string("split layout: ") + awv_last_error());
+          sseg.resize((size_t)std::max<uint64_t>(seg_first[(size_t)m], 1));
+          spc.seg_first = seg_first.data();
+          spc.index = six.data();
+          spc.seg = sseg.data();
+          ctx.sp = &spc;
+          ctx.sst = &sst[s];
+        }
         const int rc = engine_call(e, call.score_only, call.max_penalty, pen, ap.data(), m, sink, &ctx, verify ? vr.data() : nullptr,
                                    ranges_ ? rp.data() : nullptr, bounded_run ? bounds.data() : call.align_bounds, clip_bonus_,
-                                   clipping ? cr.data() : nullptr);
+                                   clipping ? cr.data() : nullptr, splitting ? &spc : nullptr);
         lap("aligned + sunk");
         awv_stats x{};
         awv_engine_stats(e, &x);
@@ -957,6 +1075,11 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
           awv_clip_stats cx{};
           awv_engine_clip_stats(e, &cx);
           cst[s].kernel_ms += cx.kernel_ms;
+        }
+        if (splitting && rc == AWV_OK) {
+          awv_split_stats sx{};
+          awv_engine_split_stats(e, &sx);
+          sst[s].kernel_ms += sx.kernel_ms;
         }
         if (ctx.failed) return;  // (the error is already recorded)
         if (rc != AWV_OK) {
@@ -988,8 +1111,13 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
     verify_stats_ = awv_verify_stats{};
     bound_stats_ = BoundStats{};
     clip_stats_ = ClipStats{};
+    split_stats_ = SplitStats{};
   }
   for (size_t s = 0; s < S; ++s) {
+    split_stats_.pairs += sst[s].pairs;
+    split_stats_.segments += sst[s].segments;
+    split_stats_.empty += sst[s].empty;
+    split_stats_.kernel_ms += sst[s].kernel_ms;
     clip_stats_.pairs += cst[s].pairs;
     clip_stats_.empty += cst[s].empty;
     clip_stats_.below_min_score += cst[s].below_min_score;

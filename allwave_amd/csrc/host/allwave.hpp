@@ -110,6 +110,13 @@ struct ClipStats {
   double kernel_ms = 0.0;
 };
 
+// What splitting did to a run (AllPairIterator::with_split): finished pairs whose op string was split, the segments they
+// gave, and the pairs that reached no consumer because no segment scores min_score; kernel_ms: summed split kernel time.
+struct SplitStats {
+  uint64_t pairs = 0, segments = 0, empty = 0;
+  double kernel_ms = 0.0;
+};
+
 using Callback = std::function<void(AlignmentResult&&)>;  // may throw: first error aborts the run
 
 // One interval pair to align globally (awv_range_pair): query[query_start, query_end) -- on the query's FORWARD strand, as PAF
@@ -219,6 +226,14 @@ class AllPairIterator {  // iterator.rs:12-171
   // without clipping; scores() ignores the setting.  1 <= match_bonus <= 32767, min_score >= 1.
   AllPairIterator& with_clip(int match_bonus, int64_t min_score = 1);
   bool clip() const { return clip_bonus_ > 0; }
+  // Every alignment consumer receives one AlignmentResult per segment of each alignment's split (awv_align_pairs_split /
+  // awv_align_ranges_split: every maximal segment that scores at least min_score), in column order within a pair and pair
+  // order across the pairs of a batch; each is what with_clip would give for that segment, coordinates included.  A pair
+  // without a segment reaches no consumer.  Segment storage is allocated per engine call from awv_split_layout_*.  Not
+  // together with with_clip (std::invalid_argument); scores() ignores the setting.
+  AllPairIterator& with_split(int match_bonus, int64_t min_score);
+  bool split() const { return split_bonus_ > 0; }
+  SplitStats last_split_stats() const { return split_stats_; }
   // of the last run (next(): of the chunks since the list's start), summed over the slots
   ClipStats last_clip_stats() const { return clip_stats_; }
   AllPairIterator& with_max_penalty(int max_penalty);
@@ -311,7 +326,10 @@ class AllPairIterator {  // iterator.rs:12-171
   int clip_bonus_ = 0;  // with_clip (0: off)
   int64_t clip_min_score_ = 1;
   ClipStats clip_stats_{};
-  bool drops_pairs() const { return bounded() || clip(); }  // consumers that keep a slot per pair compact what was delivered
+  int split_bonus_ = 0;  // with_split (0: off)
+  int64_t split_min_score_ = 1;
+  SplitStats split_stats_{};
+  bool drops_pairs() const { return bounded() || clip() || split(); }  // consumers that keep a slot per pair compact what was delivered
   BoundStats bound_stats_{};
   std::vector<VerifyFailure> verify_failures_;
   awv_verify_stats verify_stats_{};
@@ -343,6 +361,7 @@ class AllPairParallelIterator {
   awv_verify_stats last_verify_stats() const { return it_.last_verify_stats(); }
   BoundStats last_bound_stats() const { return it_.last_bound_stats(); }
   ClipStats last_clip_stats() const { return it_.last_clip_stats(); }
+  SplitStats last_split_stats() const { return it_.last_split_stats(); }
  private:
   friend class AllPairIterator;
   explicit AllPairParallelIterator(const AllPairIterator& it) : it_(it) {}
@@ -381,6 +400,14 @@ void align_ranges(const std::vector<Sequence>& sequences, const std::vector<Alig
                   const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
                   awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
                   BoundStats* bound_stats, int clip_match_bonus, int64_t clip_min_score, ClipStats* clip_stats = nullptr);
+
+// the same with every alignment split (AllPairIterator::with_split; split_match_bonus 0: off -- then clip_match_bonus 0 is off
+// as well); split_stats (nullable) receives what splitting did
+void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
+                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
+                  awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
+                  BoundStats* bound_stats, int clip_match_bonus, int64_t clip_min_score, ClipStats* clip_stats, int split_match_bonus,
+                  int64_t split_min_score, SplitStats* split_stats = nullptr);
 
 // ---- mappings in, alignments out: the interval pairs a PAF file names (columns 1-9 of each line) ----
 struct PafRangeLine {

@@ -37,26 +37,37 @@ thread_local BoundStats g_bound_stats{};
 thread_local int g_next_clip_bonus = 0;
 thread_local int64_t g_next_clip_min_score = 1;
 thread_local ClipStats g_clip_stats{};
+// And splitting: awh_set_split, awh_last_split.
+thread_local int g_next_split_bonus = 0;
+thread_local int64_t g_next_split_min_score = 1;
+thread_local SplitStats g_split_stats{};
 struct RunOptions {
   int64_t max_penalty;
   double max_divergence;
   int clip_bonus;
   int64_t clip_min_score;
+  int split_bonus;
+  int64_t split_min_score;
   void apply(AllPairIterator& it) const {
     if (max_penalty >= 0) it.with_max_penalty((int)std::min<int64_t>(max_penalty, INT32_MAX));
     if (max_divergence >= 0.0) it.with_max_divergence(max_divergence);
     if (clip_bonus != 0) it.with_clip(clip_bonus, clip_min_score);
+    if (split_bonus != 0) it.with_split(split_bonus, split_min_score);
   }
-  bool any() const { return max_penalty >= 0 || max_divergence >= 0.0 || clip_bonus != 0; }
+  bool any() const { return max_penalty >= 0 || max_divergence >= 0.0 || clip_bonus != 0 || split_bonus != 0; }
 };
 // what an alignment hook leaves behind of its iterator's bound and clip counters (awh_last_bounds, awh_last_clip)
 template <typename It>
 void keep_stats(const It& it) {
   g_bound_stats = it.last_bound_stats();
   g_clip_stats = it.last_clip_stats();
+  g_split_stats = it.last_split_stats();
 }
 RunOptions take_run_options() {
-  const RunOptions b{g_next_max_penalty, g_next_max_divergence, g_next_clip_bonus, g_next_clip_min_score};
+  const RunOptions b{g_next_max_penalty, g_next_max_divergence, g_next_clip_bonus, g_next_clip_min_score, g_next_split_bonus, g_next_split_min_score};
+  g_next_split_bonus = 0;
+  g_next_split_min_score = 1;
+  g_split_stats = SplitStats{};
   g_next_max_penalty = -1;
   g_next_max_divergence = -1.0;
   g_next_clip_bonus = 0;
@@ -686,6 +697,20 @@ void awh_set_bounds(int64_t max_penalty, double max_divergence) {
 void awh_set_clip(int match_bonus, int64_t min_score) {
   g_next_clip_bonus = match_bonus;
   g_next_clip_min_score = min_score;
+}
+// ---- splitting into all good segments ----
+// The calling thread's NEXT alignment hook runs with_split(match_bonus, min_score) (match_bonus 0: off); the hooks after it
+// run unsplit again.
+void awh_set_split(int match_bonus, int64_t min_score) {
+  g_next_split_bonus = match_bonus;
+  g_next_split_min_score = min_score;
+}
+// last_split_stats() of the calling thread's last alignment hook: {pairs, segments, empty} and the kernel time
+void awh_last_split(uint64_t out[3], double* kernel_ms) {
+  out[0] = g_split_stats.pairs;
+  out[1] = g_split_stats.segments;
+  out[2] = g_split_stats.empty;
+  *kernel_ms = g_split_stats.kernel_ms;
 }
 // last_clip_stats() of the calling thread's last alignment hook: {pairs, empty, below_min_score} and the kernel time
 void awh_last_clip(uint64_t out[3], double* kernel_ms) {

@@ -52,6 +52,8 @@ struct Args {
   bool have_align_paf = false, have_sparsification = false, have_shard = false;
   long clip = 0, clip_min_score = 1;  // --clip A: every alignment clipped to its best-scoring segment under the match bonus A
   bool have_clip = false, have_clip_min_score = false;
+  long split = 0, split_min_score = 0;  // --split A --split-min-score S: every alignment split into all its segments that score at least S
+  bool have_split = false, have_split_min_score = false;
 };
 
 [[noreturn]] void die(const std::string& m, int code = 2) {
@@ -227,6 +229,16 @@ int main(int argc, char** argv) {
         die("--max-align-penalty expects a penalty N >= 0");
       a.have_max_align_penalty = true;
     }
+    else if (k == "--split" || k == "--split-min-score") {
+      const std::string v = val();
+      char* end = nullptr;
+      const long n = strtol(v.c_str(), &end, 10);
+      const bool bonus = k == "--split";
+      if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || !end || *end != 0 || n < 1 || (bonus && n > AWV_CLIP_MAX_BONUS))
+        die(bonus ? "--split expects a match bonus A with 1 <= A <= 32767" : "--split-min-score expects a score S >= 1");
+      (bonus ? a.split : a.split_min_score) = n;
+      (bonus ? a.have_split : a.have_split_min_score) = true;
+    }
     else if (k == "--clip" || k == "--clip-min-score") {
       const std::string v = val();
       char* end = nullptr;
@@ -261,9 +273,11 @@ int main(int argc, char** argv) {
                    "                   [-t threads] [--wfa-orientation|--wfa-orientation-full|--forward-only] [-k prefixes | -e prefixes] [--mash-matrix]\n"
                    "                   [--device N | --devices LIST] [--shard R/N] [--score-only [--max-penalty N]] [--plan-device N] [--verify]\n"
                    "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
+                   "                   [--split A --split-min-score S]\n"
                    "       allwave_hip -i in.fa --check-paf FILE [-s scores | -x ANI] [--check-optimal] [--partial] [--device N]\n"
                    "       allwave_hip -i in.fa --align-paf FILE [-s scores | -x ANI] [-o out.paf] [--verify] [--score-only] [--device N | --devices LIST]\n"
                    "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
+                   "                   [--split A --split-min-score S]\n"
                    "  --verify         check every alignment on the device before it is written (columns, counts, penalty); the summary\n"
                    "                   line gains `verified N pairs, F failed, K ms`, failures go to stderr, exit status 4 if any\n"
                    "  --check-paf FILE align nothing: check every line of FILE (12 columns + cg:Z:) against in.fa on the device; one line\n"
@@ -290,6 +304,11 @@ int main(int argc, char** argv) {
                    "                   the forward strand; columns 10, 11, gi:f: and cg:Z: the segment's) or dropped when nothing scores above 0;\n"
                    "                   the summary line gains `clipped N pairs, E empty, B below min score, K ms`\n"
                    "  --clip-min-score S  with --clip: also drop the segments that score below S (default 1)\n"
+                   "  --split A        split every alignment into all its maximal segments that score at least S on the device (+A per match,\n"
+                   "                   minus the penalties; needs --split-min-score S, not with --clip): each PAF line is replaced by its segments'\n"
+                   "                   lines, in column order, or dropped; also with --align-paf, where one input line may give several lines;\n"
+                   "                   the summary line gains `split N pairs into G segments, E without a segment, K ms`\n"
+                   "  --split-min-score S  with --split: the least score of a segment (required: no default can be derived)\n"
                    "  --plan-device N  plan on device N: --mash-matrix, the -p pair list and mash orientation (the same output as\n"
                    "                   the host planner; with --shard every rank plans the whole list on its own plan device)\n";
       return 0;
@@ -306,6 +325,12 @@ int main(int argc, char** argv) {
   bound_flag_alone(a.have_max_align_penalty, "--max-align-penalty");
   bound_flag_alone(a.have_max_divergence, "--max-divergence");
   if (a.have_clip_min_score && !a.have_clip) die("the argument '--clip-min-score' requires '--clip'");
+  if (a.have_split_min_score && !a.have_split) die("the argument '--split-min-score' requires '--split'");
+  if (a.have_split && !a.have_split_min_score) die("the argument '--split' requires '--split-min-score'");
+  if (a.have_split && a.have_clip) die("the argument '--split' cannot be used with '--clip'");
+  if (a.have_split && a.score_only) die("the argument '--split' cannot be used with '--score-only'");
+  if (a.have_split && a.have_check_paf) die("the argument '--split' cannot be used with '--check-paf'");
+  if (a.have_split && a.mash_matrix) die("the argument '--split' cannot be used with '--mash-matrix'");
   if (a.have_clip && a.score_only) die("the argument '--clip' cannot be used with '--score-only'");
   if (a.have_clip && a.have_check_paf) die("the argument '--clip' cannot be used with '--check-paf'");
   if (a.have_clip && a.mash_matrix) die("the argument '--clip' cannot be used with '--mash-matrix'");
@@ -423,6 +448,7 @@ int main(int argc, char** argv) {
     if (a.have_max_divergence) it.with_max_divergence(a.max_divergence);
     const bool bounded = a.have_max_align_penalty || a.have_max_divergence;
     if (a.have_clip) it.with_clip((int)a.clip, (int64_t)a.clip_min_score);
+    if (a.have_split) it.with_split((int)a.split, (int64_t)a.split_min_score);
     if (a.forward_only) it.with_orientation(Orientation::ForwardOnly);
     it.with_full_wfa_orientation(a.wfa_orientation_full);
     it.with_devices(devices);
@@ -484,7 +510,8 @@ int main(int argc, char** argv) {
     const size_t above = (size_t)(bs.above_penalty + bs.above_divergence);  // (pairs above a bound get no line)
     const ClipStats cs = it.last_clip_stats();
     const size_t unclipped = (size_t)(cs.empty + cs.below_min_score);  // (nor do pairs without a clip worth reporting)
-    if (done + above + unclipped != total) die("internal: wrote " + std::to_string(done) + " of " + std::to_string(total) + (a.score_only ? " pairs" : " PAF lines"), 1);
+    const SplitStats ss = it.last_split_stats();  // (a split pair gives one line per segment)
+    if (done + above + unclipped + (size_t)ss.pairs != total + (size_t)ss.segments) die("internal: wrote " + std::to_string(done) + " of " + std::to_string(total) + (a.score_only ? " pairs" : " PAF lines"), 1);
     if (!a.no_progress) {
       const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       char buf[480];
@@ -494,6 +521,9 @@ int main(int argc, char** argv) {
       if (a.have_clip && w > 0 && (size_t)w < sizeof(buf))
         w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", clipped %llu pairs, %llu empty, %llu below min score, %.2f ms", (unsigned long long)cs.pairs,
                       (unsigned long long)cs.empty, (unsigned long long)cs.below_min_score, cs.kernel_ms);
+      if (a.have_split && w > 0 && (size_t)w < sizeof(buf))
+        w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", split %llu pairs into %llu segments, %llu without a segment, %.2f ms", (unsigned long long)ss.pairs,
+                      (unsigned long long)ss.segments, (unsigned long long)ss.empty, ss.kernel_ms);
       if (a.verify && w > 0 && (size_t)w < sizeof(buf)) {
         const awv_verify_stats vs = it.last_verify_stats();
         snprintf(buf + w, sizeof(buf) - (size_t)w, ", verified %llu pairs, %zu failed, %.2f ms", (unsigned long long)vs.pairs,

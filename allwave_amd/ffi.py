@@ -72,7 +72,9 @@ EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine
            "awv_align_ranges", "awv_align_ranges_verified", "awv_score_ranges", "awv_verify_ranges",
            "awv_align_pairs_bounded", "awv_align_ranges_bounded", "awv_divergence_bound",
            "awv_clip_one_host", "awv_clip_cigars", "awv_align_pairs_clipped", "awv_align_ranges_clipped", "awv_engine_clip_stats",
-           "awv_twin_stats")
+           "awv_twin_stats",
+           "awv_split_slots", "awv_split_layout_pairs", "awv_split_layout_ranges", "awv_split_one_host", "awv_split_cigars",
+           "awv_align_pairs_split", "awv_align_ranges_split", "awv_engine_split_stats")
 
 
 class EngineConfig(C.Structure):
@@ -116,6 +118,11 @@ class ClipStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("pairs", C.c_uint64), ("empty", C.c_uint64), ("columns", C.c_uint64)]
 
 
+class SplitStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("pairs", C.c_uint64), ("segments", C.c_uint64), ("empty", C.c_uint64), ("columns", C.c_uint64),
+                ("columns_scanned", C.c_uint64)]
+
+
 PAIR_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4")])
 #: awv_range_pair: the query interval on the query's forward strand (PAF convention), also with q_revcomp
 RANGE_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4"), ("q_beg", "<i4"), ("q_end", "<i4"),
@@ -129,6 +136,8 @@ VERIFY_DTYPE = np.dtype([("code", "<i4"), ("reserved", "<i4"), ("column", "<i8")
 CLIP_DTYPE = np.dtype([("code", "<i4"), ("reserved", "<i4"), ("score", "<i8"), ("col_beg", "<u4"), ("col_end", "<u4"),
                        ("q_skip", "<i4"), ("t_skip", "<i4"), ("num_matches", "<i4"), ("num_mismatches", "<i4"),
                        ("num_ins", "<i4"), ("num_del", "<i4"), ("penalty", "<i4"), ("reserved2", "<i4")])
+#: awv_split_index: what the split found for one record; its segments are CLIP_DTYPE records in the caller's slot region
+SPLIT_INDEX_DTYPE = np.dtype([("code", "<i4"), ("count", "<i4"), ("column", "<i8")])
 #: awv_score_result
 SCORE_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4")])
 
@@ -188,6 +197,18 @@ def load():
                                               C.c_void_p, C.c_void_p, SINK_FN, C.c_void_p]
         L.awv_align_ranges_clipped.argtypes = L.awv_align_pairs_clipped.argtypes
         L.awv_engine_clip_stats.argtypes = [C.c_void_p, C.POINTER(ClipStats)]
+        L.awv_split_slots.argtypes = [C.c_int32, C.c_int64, C.c_int64]
+        L.awv_split_slots.restype = C.c_int64
+        L.awv_split_layout_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p]
+        L.awv_split_layout_ranges.argtypes = L.awv_split_layout_pairs.argtypes
+        L.awv_split_one_host.argtypes = [C.POINTER(Penalties), C.c_int32, C.c_int64, C.c_char_p, C.c_int64, C.c_void_p, C.c_int64,
+                                         C.POINTER(C.c_int64), C.c_void_p]
+        L.awv_split_cigars.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
+        L.awv_align_pairs_split.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, SINK_FN, C.c_void_p]
+        L.awv_align_ranges_split.argtypes = L.awv_align_pairs_split.argtypes
+        L.awv_engine_split_stats.argtypes = [C.c_void_p, C.POINTER(SplitStats)]
         _LIB = L
     return _LIB
 
@@ -260,12 +281,12 @@ class Engine:
             ranges = r
         return np.ascontiguousarray(ranges)
 
-    def align_ranges(self, scores, ranges, want_cigars=True, verify=False, max_penalty=None, clip=None, _sink_hook=None):
+    def align_ranges(self, scores, ranges, want_cigars=True, verify=False, max_penalty=None, clip=None, _sink_hook=None, split=None):
         """align_pairs on interval pairs (awv_align_ranges / awv_align_ranges_verified).  ranges: int array [n,7] (q_idx, t_idx,
         q_revcomp, q_beg, q_end, t_beg, t_end) or a RANGE_DTYPE array; the query interval is on the query's forward strand.
         The records' q_end / t_end are consumed lengths, relative to the range.  max_penalty: as for align_pairs
-        (awv_align_ranges_bounded); clip: as for align_pairs (awv_align_ranges_clipped)."""
-        return self._align("awv_align_ranges", scores, self._range_array(ranges), want_cigars, verify, max_penalty, clip, _sink_hook)
+        (awv_align_ranges_bounded); clip, split: as for align_pairs (awv_align_ranges_clipped, awv_align_ranges_split)."""
+        return self._align("awv_align_ranges", scores, self._range_array(ranges), want_cigars, verify, max_penalty, clip, _sink_hook, split)
 
     def score_ranges(self, scores, ranges, max_penalty=None):
         """score_pairs on interval pairs (awv_score_ranges).  max_penalty: None, or one bound per range (negative: none)."""
@@ -286,7 +307,7 @@ class Engine:
         """verify_cigars on interval pairs (awv_verify_ranges)."""
         return self._verify("awv_verify_ranges", scores, self._range_array(ranges), results, arena)
 
-    def align_pairs(self, scores, pairs, want_cigars=True, verify=False, max_penalty=None, clip=None, _sink_hook=None):
+    def align_pairs(self, scores, pairs, want_cigars=True, verify=False, max_penalty=None, clip=None, _sink_hook=None, split=None):
         """pairs: int array [n,2] (q,t) or [n,3] (q,t,revcomp), or a PAIR_DTYPE array.
         Returns (results structured array, list of op-byte strings or None); verify=True: every finished pair is checked on
         the device (awv_align_pairs_verified) and a VERIFY_DTYPE array comes back as a third value.
@@ -297,10 +318,32 @@ class Engine:
         on the device (awv_align_pairs_clipped) and a CLIP_DTYPE array comes back as one more value, after the verify array
         when there is one.  Records and CIGARs are the unclipped call's: the clip describes a slice.
         _sink_hook: a test aid, not part of the interface -- with clip, called as _sink_hook(first, n, clips) inside every sink
-        callback, clips being the CLIP_DTYPE array of the whole call as filled so far."""
-        return self._align("awv_align_pairs", scores, self._pair_array(pairs), want_cigars, verify, max_penalty, clip, _sink_hook)
+        callback, clips being the CLIP_DTYPE array of the whole call as filled so far.
+        split: None, or (a, min_score): every finished pair's op string is split into all its maximal segments that score at
+        least min_score (awv_align_pairs_split; not together with clip).  One more value comes back, after the verify array
+        when there is one: (index, segments), a SPLIT_INDEX_DTYPE array with one entry per pair and the list of each pair's
+        segments as CLIP_DTYPE arrays, in column order.  With split, _sink_hook is called as _sink_hook(first, n, (index,
+        seg_first, slots)) -- the call's raw storage as filled so far."""
+        return self._align("awv_align_pairs", scores, self._pair_array(pairs), want_cigars, verify, max_penalty, clip, _sink_hook, split)
 
-    def _align(self, fn, scores, pairs, want_cigars, verify, max_penalty=None, clip=None, _sink_hook=None):
+    def split_layout(self, pairs_or_ranges, match_bonus, min_score):
+        """awv_split_layout_pairs / awv_split_layout_ranges: seg_first (uint64, n + 1) for a PAIR_DTYPE / RANGE_DTYPE array (or
+        what align_pairs takes) over the resident set."""
+        arr = pairs_or_ranges if isinstance(pairs_or_ranges, np.ndarray) and pairs_or_ranges.dtype in (PAIR_DTYPE, RANGE_DTYPE) \
+            else self._pair_array(pairs_or_ranges)
+        arr = np.ascontiguousarray(arr)
+        fn = "awv_split_layout_ranges" if arr.dtype == RANGE_DTYPE else "awv_split_layout_pairs"
+        seg_first = np.zeros(len(arr) + 1, dtype=np.uint64)
+        rc = getattr(load(), fn)(self._h, arr.ctypes.data, len(arr), int(match_bonus), int(min_score), seg_first.ctypes.data)
+        if rc != AWV_OK:
+            raise EngineError(rc, fn)
+        return seg_first
+
+    @staticmethod
+    def _segment_lists(index, seg_first, slots):
+        return [slots[int(seg_first[i]):int(seg_first[i]) + int(index["count"][i])].copy() for i in range(len(index))]
+
+    def _align(self, fn, scores, pairs, want_cigars, verify, max_penalty=None, clip=None, _sink_hook=None, split=None):
         """awv_align_pairs / awv_align_ranges (`fn`; verify: its _verified variant; max_penalty: its _bounded variant; clip: its
         _clipped variant, which takes the other two as well) on a contiguous PAIR_DTYPE / RANGE_DTYPE array."""
         pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
@@ -317,10 +360,20 @@ class Engine:
         res = np.zeros(len(pairs), dtype=RESULT_DTYPE)
         cigars = [None] * len(pairs) if want_cigars else None
         cres = np.zeros(max(len(pairs), 1), dtype=CLIP_DTYPE)[:len(pairs)] if clip is not None else None
+        sp = None
+        if split is not None:
+            if clip is not None:
+                raise ValueError("split and clip exclude each other")
+            a, min_score = int(split[0]), int(split[1])
+            seg_first = self.split_layout(pairs, a, min_score)
+            sp = (np.zeros(max(len(pairs), 1), dtype=SPLIT_INDEX_DTYPE)[:len(pairs)], seg_first,
+                  np.zeros(max(int(seg_first[-1]), 1), dtype=CLIP_DTYPE))
 
         def _sink(user, first, n, rptr, arena):
             if _sink_hook is not None and cres is not None:
                 _sink_hook(int(first), int(n), cres)
+            if _sink_hook is not None and sp is not None:
+                _sink_hook(int(first), int(n), sp)
             if cigars is not None and arena:
                 r = np.ctypeslib.as_array(C.cast(rptr, C.POINTER(C.c_uint8)), shape=(n * RESULT_DTYPE.itemsize,))
                 r = r.view(RESULT_DTYPE)
@@ -329,7 +382,17 @@ class Engine:
                         cigars[first + i] = C.string_at(arena + int(r["cigar_off"][i]), int(r["cigar_len"][i]))
             return 0
 
-        cb = SINK_FN(_sink) if want_cigars or (_sink_hook is not None and cres is not None) else SINK_FN()
+        cb = SINK_FN(_sink) if want_cigars or (_sink_hook is not None and (cres is not None or sp is not None)) else SINK_FN()
+        if sp is not None:
+            fn_s = fn + "_split"
+            vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)] if verify else None
+            rc = getattr(load(), fn_s)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), None if bounds is None else bounds.ctypes.data,
+                                       a, min_score, res.ctypes.data, vres.ctypes.data if verify else None, sp[1].ctypes.data,
+                                       sp[0].ctypes.data, sp[2].ctypes.data, cb, None)
+            if rc != AWV_OK:
+                raise EngineError(rc, fn_s)
+            found = (sp[0], self._segment_lists(*sp))
+            return (res, cigars, vres, found) if verify else (res, cigars, found)
         if cres is not None:
             fn_c = fn + "_clipped"
             vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)] if verify else None
@@ -395,6 +458,43 @@ class Engine:
         if rc != AWV_OK:
             raise EngineError(rc, "awv_clip_cigars")
         return cres
+
+    def split_cigars(self, scores, match_bonus, min_score, results, arena, seg_first=None, slots=None):
+        """awv_split_cigars: splits caller-supplied records (as for clip_cigars) into all their segments that score at least
+        min_score, on the device; needs no sequence set.  seg_first (uint64, n + 1; default: what the slot rule requires,
+        awv_split_slots over each cigar_len) and slots (a CLIP_DTYPE array written in place; default: a zeroed one) are the
+        caller's segment storage.  Returns (index, segments): a SPLIT_INDEX_DTYPE array and the list of each record's
+        segments as CLIP_DTYPE arrays."""
+        pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+        results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
+        nbytes = int(arena.size)
+        if nbytes == 0:
+            arena = np.zeros(1, dtype=np.uint8)
+        if seg_first is None:
+            need = [split_slots(match_bonus, min_score, int(r["cigar_len"])) if r["status"] == AWV_ST_COMPLETED else 0 for r in results]
+            seg_first = np.concatenate(([0], np.cumsum(need, dtype=np.uint64))).astype(np.uint64)
+        seg_first = np.ascontiguousarray(seg_first, dtype=np.uint64)
+        if seg_first.shape != (len(results) + 1,):
+            raise ValueError("seg_first: need one entry per record and one more")
+        if slots is None:
+            slots = np.zeros(max(int(seg_first[-1]), 1), dtype=CLIP_DTYPE)
+        if slots.dtype != CLIP_DTYPE or not slots.flags.c_contiguous or len(slots) < int(seg_first.max()):
+            raise ValueError("slots: need a contiguous CLIP_DTYPE array that holds seg_first's regions")
+        index = np.zeros(max(len(results), 1), dtype=SPLIT_INDEX_DTYPE)[:len(results)]
+        rc = load().awv_split_cigars(self._h, C.byref(pen), int(match_bonus), int(min_score), results.ctypes.data, len(results),
+                                     arena.ctypes.data, nbytes, seg_first.ctypes.data, index.ctypes.data, slots.ctypes.data)
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_split_cigars")
+        return index, self._segment_lists(index, seg_first, slots)
+
+    def split_stats(self):
+        """awv_engine_split_stats: kernel_ms, pairs, segments, empty, columns, columns_scanned of the last splitting call."""
+        st = SplitStats()
+        rc = load().awv_engine_split_stats(self._h, C.byref(st))
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_engine_split_stats")
+        return st
 
     def clip_stats(self):
         """awv_engine_clip_stats: kernel_ms, pairs, empty, columns of the last clipping call."""
@@ -506,6 +606,34 @@ def clip_one_host(scores, match_bonus, cigar):
     if rc != AWV_OK:
         raise EngineError(rc, "awv_clip_one_host")
     return out[0]
+
+
+def split_slots(match_bonus, min_score, m):
+    """awv_split_slots: floor(match_bonus * m / min_score), the most segments an op string with m matches can split into.
+    Needs no device."""
+    n = load().awv_split_slots(int(match_bonus), int(min_score), int(m))
+    if n < 0:
+        raise EngineError(AWV_ERR_ARG, "awv_split_slots")
+    return int(n)
+
+
+def split_one_host(scores, match_bonus, min_score, cigar, cap=None):
+    """awv_split_one_host: the splitting contract on the host (needs no device; the yardstick the kernel is tested against).
+    Returns (index record, CLIP_DTYPE array of the segments in column order); cap: the slots to offer (default: the slot
+    rule's bound for a string of this length) -- the segments beyond it are counted, not returned."""
+    pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
+    cigar = bytes(cigar)
+    if cap is None:
+        cap = max(load().awv_split_slots(int(match_bonus), int(min_score), len(cigar)), 0)
+    cap = min(int(cap), len(cigar))  # (a segment holds at least one column)
+    out = np.zeros(max(cap, 1), dtype=CLIP_DTYPE)
+    index = np.zeros(1, dtype=SPLIT_INDEX_DTYPE)
+    count = C.c_int64(0)
+    rc = load().awv_split_one_host(C.byref(pen), int(match_bonus), int(min_score), cigar, len(cigar), out.ctypes.data, cap, C.byref(count),
+                                   index.ctypes.data)
+    if rc != AWV_OK:
+        raise EngineError(rc, "awv_split_one_host")
+    return index[0], out[:min(int(count.value), cap)].copy()
 
 
 def divergence_bound(scores, plen, tlen, d):

@@ -441,6 +441,79 @@ int awv_align_ranges_clipped(awv_engine* e, const awv_penalties* pen, const awv_
 /* The last clipping call (awv_align_*_clipped / awv_clip_cigars) of this engine. */
 int awv_engine_clip_stats(const awv_engine* e, awv_clip_stats* out);
 
+/* ---- splitting into all good segments (csrc/split.hip, csrc/split_device.hpp) ----------------------------------------------
+ * The clip keeps one segment of an op string; the split keeps every maximal one that scores at least min_score (Ruzzo and
+ * Tompa's "all maximal scoring subsequences", with the clip's tie rules inside every interval).  A pure function of the op
+ * bytes c[0..n), the penalties, a match bonus 1 <= a <= AWV_CLIP_MAX_BONUS and a threshold min_score >= 1; no sequence is read:
+ *     segments(lo, hi):
+ *         if hi <= lo: return []
+ *         r = clip(c[lo..hi))                  (the slice re-scored as an op string of its own, the contract above)
+ *         if r is empty or r.score < min_score: return []
+ *         b, e = lo + r.col_beg, lo + r.col_end
+ *         return segments(lo, b) + [[b, e)] + segments(e, hi)
+ *     split(c) = segments(0, n)
+ * No part of an interval scores above that interval's clip, so the pruning at min_score is exact.  The segments are disjoint
+ * and ascending, each begins and ends with an 'M' (no gap run is cut) and scores at least min_score, and what is left between
+ * them holds nothing that does.  When the clip of the whole string scores at least min_score it is one of the segments, the
+ * top-scoring one.  Each segment needs ceil(min_score / a) 'M' columns, so a string with m of them has at most
+ * awv_split_slots(a, min_score, m) = floor(a * m / min_score) segments.
+ * A segment is an awv_clip_result with code AWV_CL_OK: col_beg / col_end are columns of the WHOLE op string, q_skip / t_skip
+ * the bases consumed before col_beg in the whole string; counts, penalty and score are the segment's.
+ * Segment storage is the caller's and its layout is fixed before the call: seg_first holds n + 1 ascending entries, record i
+ * owns sout[seg_first[i] .. seg_first[i + 1]) and its iout[i].count segments lie at the front of that region in ascending
+ * col_beg; the slots behind them are left untouched.  A call is refused with AWV_ERR_ARG, before anything is launched, when a
+ * record owns fewer slots than it may need: the aligning calls need awv_split_slots(a, min_score, min(plen, tlen)) over the
+ * pattern and text lengths (the two interval lengths for ranges), awv_split_cigars needs awv_split_slots(a, min_score,
+ * cigar_len) -- not num_matches, which a caller's record may misstate. */
+typedef struct {
+  int32_t code;    /* AWV_CL_OK: count >= 1 segments; AWV_CL_EMPTY: none reaches min_score; AWV_CL_SKIPPED: status is not
+                      AWV_ST_COMPLETED (AWV_ST_ABOVE_BOUND included); AWV_CL_BAD_OP: as for the clip, count 0 */
+  int32_t count;   /* segments of the record */
+  int64_t column;  /* AWV_CL_BAD_OP: the smallest offending column; -1 for every other code */
+} awv_split_index;   /* 16 bytes */
+
+typedef struct {
+  double kernel_ms;          /* HIP-event time of the split launches of the last splitting call */
+  uint64_t pairs;            /* records handed to the split (skipped ones included) */
+  uint64_t segments;         /* segments written */
+  uint64_t empty;            /* records not skipped that have no segment (AWV_CL_EMPTY) */
+  uint64_t columns;          /* op bytes of the records not skipped */
+  uint64_t columns_scanned;  /* columns of every interval a wave scanned: / columns = the re-scan factor */
+} awv_split_stats;
+
+/* floor(match_bonus * m / min_score), on the host; -1 unless 1 <= match_bonus <= AWV_CLIP_MAX_BONUS, min_score >= 1, m >= 0. */
+int64_t awv_split_slots(int32_t match_bonus, int64_t min_score, int64_t m);
+/* seg_first[0] = 0, seg_first[i + 1] = seg_first[i] + what the aligning calls require for entry i: host arithmetic over the
+ * resident set's lengths.  AWV_ERR_ARG for a bad index or interval, AWV_ERR_STATE without a sequence set. */
+int awv_split_layout_pairs(awv_engine* e, const awv_pair* pairs, int64_t n, int32_t match_bonus, int64_t min_score,
+                           uint64_t* seg_first /* n + 1 */);
+int awv_split_layout_ranges(awv_engine* e, const awv_range_pair* ranges, int64_t n, int32_t match_bonus, int64_t min_score,
+                            uint64_t* seg_first /* n + 1 */);
+/* The contract alone, on the host (needs no device), written as the recursion over the clip's host walk: the yardstick the
+ * kernel is tested against, not a fallback -- no product path calls it.  sout: cap slots; *count: the segments found, of which
+ * min(*count, cap) are written, in ascending col_beg.  index (nullable): the record's awv_split_index. */
+int awv_split_one_host(const awv_penalties* pen, int32_t match_bonus, int64_t min_score, const uint8_t* cigar, int64_t n,
+                       awv_clip_result* sout, int64_t cap, int64_t* count /* required */, awv_split_index* index);
+/* Splits records and op bytes the caller supplies, on the device; staged and pieced as awv_clip_cigars does.  Reads no
+ * sequence: the engine needs no sequence set.  A completed record whose op bytes lie outside the arena: AWV_ERR_ARG. */
+int awv_split_cigars(awv_engine* e, const awv_penalties* pen, int32_t match_bonus, int64_t min_score, const awv_result* results,
+                     int64_t n, const uint8_t* cigar_arena, uint64_t arena_bytes, const uint64_t* seg_first /* n + 1 */,
+                     awv_split_index* iout /* required */, awv_clip_result* sout /* required when any slot exists */);
+/* awv_align_pairs_clipped / awv_align_ranges_clipped with the split in the clip's place: every batch's finished pairs are
+ * split on the device, on the engine's stream, after the optional check and before the batch's CIGARs are copied back;
+ * iout / sout of a batch are filled before that batch's sink call.  Records, op bytes, arena slots, batching and stats are
+ * those of the unsplit call, byte for byte. */
+int awv_align_pairs_split(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
+                          const int32_t* max_penalty /* per pair, nullable; < 0: none */, int32_t match_bonus, int64_t min_score,
+                          awv_result* out, awv_verify_result* vout /* nullable */, const uint64_t* seg_first /* npairs + 1 */,
+                          awv_split_index* iout /* required */, awv_clip_result* sout, awv_sink sink, void* user);
+int awv_align_ranges_split(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n,
+                           const int32_t* max_penalty /* per range, nullable; < 0: none */, int32_t match_bonus, int64_t min_score,
+                           awv_result* out, awv_verify_result* vout /* nullable */, const uint64_t* seg_first /* n + 1 */,
+                           awv_split_index* iout /* required */, awv_clip_result* sout, awv_sink sink, void* user);
+/* The last splitting call (awv_align_*_split / awv_split_cigars) of this engine. */
+int awv_engine_split_stats(const awv_engine* e, awv_split_stats* out);
+
 /* ---- device pair planning (csrc/planner.hip) -------------------------------------------------------------------------
  * Integer work over the engine's resident sequence set, on its device and stream; results equal the host planner's
  * (csrc/host/planner.cpp) bit for bit.  Every call but awv_keep_pairs needs a sequence set (else AWV_ERR_STATE); a new set
