@@ -44,6 +44,7 @@
 #include <limits.h>
 
 #include "range_span.hpp"
+#include "twin_base.hpp"
 
 #ifndef AWV_NS
 #define AWV_NS awv
@@ -187,6 +188,7 @@ struct KParams {
   const int32_t* unit_first;
   const int32_t* unit_twin;
   int twin_levels;
+  int twin_base;  // 1: a base case under a shared task runs its wavefronts once and is backtraced for both orientations
 };
 
 struct RowMeta { int lo, hi; };
@@ -2806,6 +2808,281 @@ __device__ __forceinline__ int base_align(const KParams& kp, Shared& sh, const L
 }
 
 // ---------------------------------------------------------------------------------------------
+// The base case of a twin unit: base_align with a second, mirrored backtrace
+// ---------------------------------------------------------------------------------------------
+// bt_fetch_twin / base_align_twin are bt_fetch / base_align plus the mirror rule of twin_base.hpp.  They are functions of their
+// own, used by the one-wave kernels with 16-bit rows only: folded into base_align behind a compile-time switch they changed the
+// register allocation and the length of the multi-wave and 32-bit kernels, which are to keep the code they had instruction for
+// instruction (the four-wave fault), so those keep base_align's text as it was.  A change to one of the two
+// belongs in the other.
+//
+// bt_fetch with `mirror` set -- uniform --: the cell is one that the swapped pair's backtrace asks for in its own frame, read
+// from this history through the mirror rule.
+template <typename OffT>
+__device__ __forceinline__ int bt_fetch_twin(const KParams& kp, const RowMeta* base_meta, const OffT* hist, int kmin,
+                                             int max_score, int comp, int score, int k, int add, int type, bool mirror) {
+  if (mirror) {
+    const awvb::Cell in_a = awvb::cell_in_a(comp, k);
+    comp = in_a.comp;
+    k = in_a.k;
+  }
+  // the row's metadata and the value are fetched together -- one memory round trip per backtrace step instead of two in series
+  // (a score or diagonal outside what exists reads a valid dummy position and is rejected afterwards)
+  const bool sok = score >= 0 && score <= max_score;
+  const int sr = sok ? score : 0;
+  const RowMeta m = base_meta[sr * NCOMP + comp];
+  int32_t v = (int32_t)hist[((size_t)sr * NCOMP + comp) * (size_t)kp.wb_cap + (size_t)min(max(k - kmin, 0), kp.wb_cap - 1)];
+  if (!sok || k < m.lo || k > m.hi || v < 0) return -1;
+  if (mirror) {
+    v = awvb::offset_in_b(v, k);
+    if (v < 0) return -1;
+  }
+  return ((v + add) << 4) | type;
+}
+
+// base_align with `both` (uniform): false -- base_align as it is; true -- the base case of a twin unit's shared task.  The
+// wavefronts run once, in A's frame; the backtrace and the emission then run twice over the same history, in one loop: for A into
+// `em`, and with `mirror` set for the swapped pair into `em_b`, whose cells bt_fetch_twin reads through the mirror rule.
+template <bool P2, typename OffT>
+__device__ __forceinline__ int base_align_twin(const KParams& kp, Shared& sh, const Lds<OffT>& lds, SubCtx cx, void* hist_mem, rsrc_t hist_rs, uint32_t* events,
+                          int cb, int ce, Emit& em, int& penalty_out, unsigned long long* lstats, Emit& em_b, bool both) {
+  static_assert(TWIN_BUILD && WG == 64 && sizeof(OffT) == 2 && !wenc_of<OffT>(), "the mirrored backtrace is argued for one wave per workgroup and 16-bit rows only");
+  const DevPenalties& pn = kp.pen;
+  const int tid = cold_tid(), lane = tid & 63;
+  const int plen = cx.plen, tlen = cx.tlen;
+  OffT* hist = (OffT*)hist_mem;
+  const RowMeta* base_meta = lds.meta_log;  // HBM log, written by plan_step / finalize_row
+  const int kspan_lo = min(plen, kp.sb_cap), kspan_hi = min(tlen, kp.sb_cap);
+  cx.kmin[0] = -kspan_lo - 4 - COL_PAD;
+  cx.wcols = kspan_lo + kspan_hi + 9 + 2 * COL_PAD;
+  if (cx.wcols > kp.wb_cap) return ST_CAPACITY;
+  const int kmin = cx.kmin[0];
+  // score 0
+  for (int c = tid; c < NCOMP; c += WG) {
+    const RowMeta m0 = (c == cb) ? RowMeta{0, 0} : ROW_EMPTY;
+    meta_store(&lds.ring_meta[c * kp.ring + 0], m0);
+    lds.meta_log[c] = m0;
+  }
+  if (tid == 0) {
+    unsigned it = 0;
+    int v0 = 0;
+    if (cb == C_M) v0 = cx.seq_mode == 2 ? extend_lcp_gw<0>(cx, 0, 0, it) : extend_lcp(cx.P[0], cx.T[0], 0, 0, plen, tlen, it);
+    for (int j = 0; j < 4; ++j) hist[(size_t)cb * kp.wb_cap + (((0 - kmin) & ~3) + j)] = (OffT)(sizeof(OffT) == 2 ? NULL16 : OFF_NULL);
+    hist[(size_t)cb * kp.wb_cap + (0 - kmin)] = (OffT)v0;  // the score-0 row: one cell in a whole lane vector
+    acc_reset(sh.acc[0][0]);
+    acc_reset(sh.acc[1][0]);
+    acc_reset(sh.acc[2][0]);
+  }
+  const unsigned sh_addr = (unsigned)(uintptr_t)&sh, dyn_addr = (unsigned)(uintptr_t)lds.ring_meta;  // LDS addresses
+  if (tid == 0) {  // what base_phase / trim_pass_fn read back (uniform; the barrier below publishes it)
+    PassCtx& pc = sh.pctx;
+    pc.ring_mem = (unsigned long long)(uintptr_t)hist_mem;
+    pc.ring_bytes = (unsigned long long)kp.hist_slot_stride;
+    pc.meta_log = (unsigned long long)(uintptr_t)lds.meta_log;
+    pc.P[0] = pc.P[1] = (unsigned long long)(uintptr_t)cx.P[0];
+    pc.T[0] = pc.T[1] = (unsigned long long)(uintptr_t)cx.T[0];
+    pc.ring = kp.ring;
+    pc.wcap = kp.wcap;
+    pc.wb_cap = kp.wb_cap;
+    pc.sb_cap = kp.sb_cap;
+    pc.end_comp = ce;
+    pc.x = pn.x; pc.o1 = pn.o1; pc.e1 = pn.e1; pc.o2 = pn.o2; pc.e2 = pn.e2;
+    pc.lds_meta_bytes = kp.lds_meta_bytes;
+    pc.plen = plen; pc.tlen = tlen;
+    pc.kmin[0] = pc.kmin[1] = cx.kmin[0];
+    pc.wcols = cx.wcols;
+    pc.seq_mode = cx.seq_mode; pc.p_w0 = cx.p_w0; pc.t_w0 = cx.t_w0; pc.p_bit = cx.p_bit; pc.t_bit = cx.t_bit;
+    sh.ext_multi = 0;
+  }
+  __syncthreads();
+  const int k_end = tlen - plen;
+  int score = 0;
+  unsigned ext_iters = 0;
+  unsigned long long cells = 0;
+  int pass = 0;
+  bool dirty = false;  // some row of this sub-problem was trimmed: later steps mask element by element
+  bool multi_open = kp.multi_T > 0;  // multi-step passes (base_phase) until one is discarded or the capacity bound is near
+  const unsigned long long tb0 = PROF_NOW();
+  for (;;) {
+    // termination (wavefront_termination_end2end): end component reaches (plen, tlen)
+    const RowMeta me = get_meta<OffT>(kp, lds, 0, ce, score);
+    if (k_end >= me.lo && k_end <= me.hi) {
+      const int32_t v = uni(off_load1<OffT>(hist + ((size_t)score * NCOMP + ce) * (size_t)kp.wb_cap + (k_end - kmin), k_end));
+      if (v >= tlen) break;
+    }
+    if (multi_open && !dirty) {
+      if (P2 || pn.e1 == 1) base_phase<P2, OffT, P2 ? 2 : 1, 1>(sh_addr, dyn_addr, score, kp.multi_T, pass);
+      else base_phase<P2, OffT, 2, 1>(sh_addr, dyn_addr, score, kp.multi_T, pass);
+      const int why = uni(sh.pres.why);
+      if (why == MP_ERROR) return uni(sh.error);
+      score = uni(sh.pres.sc);
+      pass += uni(sh.pres.npass);
+      cells += ((unsigned long long)(unsigned)uni((int)(sh.pres.cells >> 32)) << 32) | (unsigned)uni((int)sh.pres.cells);
+      multi_open = false;  // (discarded pass or capacity margin: the rest goes step by step)
+      __syncthreads();     // (sh.pres may be rewritten only after everyone has read it)
+      if (why == MP_MET) break;  // `score` is the first score at which the end cell was reached
+      continue;
+    }
+    ++score;
+    if (score > kp.sb_cap) return ST_CAPACITY;
+    Acc& acc = sh.acc[pass % 3][0];
+    StepPlan pl;
+    plan_step<P2, true, OffT>(kp, lds, 0, score, pl);
+    cells += compute_row<P2, true, OffT>(kp, sh, lds, cx, hist_rs, 0, score, pl, dirty, acc, ext_iters);
+    __syncthreads();
+    if (uni(sh.error)) return uni(sh.error);
+    const bool trim = uni(acc.oob) != 0;
+    dirty = dirty || trim;
+    if (trim) {
+      trim_pass_fn<P2, true, OffT>(sh_addr, 0, score, pl.lo, pl.hi, pass % 3);
+      __syncthreads();
+    }
+    finalize_row<true, OffT>(kp, lds, cx, 0, score, acc, trim);
+    if (tid == 0) acc_reset(sh.acc[(pass + 2) % 3][0]);
+    ++pass;
+  }
+  penalty_out = score;
+  PROF_ADD(STAT_T_BASE_STEPS, tb0);
+  if (tid == 0) {
+    lstats[STAT_CELLS] += cells;
+    lstats[STAT_BASE] += 1;
+  }
+  atomicAdd(&lstats[STAT_EXTEND], (unsigned long long)ext_iters);
+  if (tid == 0) lstats[STAT_EXTEND] += sh.ext_multi;
+  // (a twin unit's shared base case: a second trip for the swapped pair, in its frame; A's history, the metadata log and
+  // `events` stay as they are -- the barrier that ends the emission orders the reuse of `events`)
+  const int trips = both ? 2 : 1;
+  for (int trip = 0; trip < trips; ++trip) {
+  const bool mirror = trip == 1;
+  const awvb::Start bs = awvb::start_in_b(ce, plen, tlen);
+  const int bt_ce = mirror ? bs.comp : ce, bt_k_end = mirror ? bs.k : k_end, bt_plen = mirror ? bs.plen : plen, bt_tlen = mirror ? bs.tlen : tlen;
+  const unsigned long long tb1 = PROF_NOW();
+  // ---- backtrace by wave 0 (candidates fetched by lanes 0..8, packed (offset<<4)|type, max wins)
+  if (tid < 64) {
+    int matrix = bt_ce, sc = score, k = bt_k_end, offset = bt_tlen;
+    int h = offset, v = offset - k;
+    int nev = 0, total = 0;
+    int last_op = -1, last_cnt = 0;
+    int err = 0;
+    auto push = [&](int op, int n) {
+      if (n <= 0) return;
+      if (op == last_op) { last_cnt += n; }
+      else {
+        if (last_op >= 0) { if (lane == 0) events[nev] = ((uint32_t)last_cnt << 2) | (uint32_t)last_op; ++nev; }
+        last_op = op; last_cnt = n;
+      }
+      total += n;
+    };
+    // Candidate `ms` of a state at score s on diagonal kk -- 0: M by a mismatch; 1 / 2: I1 opened / extended; 3 / 4: D1; 5 / 6: I2;
+    // 7 / 8: D2 -- is read from row (comp, cs) at diagonal ck.
+    auto cand_desc = [&](int ms, int s, int kk, int& comp, int& cs, int& ck, int& add, int& type) {
+      const bool open = (ms & 1) != 0, two = ms >= 5, ins = ms == 1 || ms == 2 || ms == 5 || ms == 6;
+      comp = (ms == 0 || open) ? C_M : ms == 2 ? C_I1 : ms == 4 ? C_D1 : ms == 6 ? C_I2 : C_D2;
+      cs = ms == 0 ? s - pn.x : s - (two ? pn.e2 : pn.e1) - (open ? (two ? pn.o2 : pn.o1) : 0);
+      ck = ms == 0 ? kk : ins ? kk - 1 : kk + 1;
+      add = (ms == 0 || ins) ? 1 : 0;
+      type = ms == 0 ? BT_M : ms == 1 ? BT_I1_OPEN : ms == 2 ? BT_I1_EXT : ms == 3 ? BT_D1_OPEN : ms == 4 ? BT_D1_EXT
+           : ms == 5 ? BT_I2_OPEN : ms == 6 ? BT_I2_EXT : ms == 7 ? BT_D2_OPEN : BT_D2_EXT;
+    };
+    // lane j's candidate of the current state as one of those nine (M: all of them, five without the second piece; a gap
+    // component: lane 0 = extended, lane 1 = opened); -1: none
+    auto slot_ms = [&](int mat, int j) {
+      if (mat == C_M) return j <= (P2 ? 8 : 4) ? j : -1;
+      const int ext = mat == C_I1 ? 2 : mat == C_D1 ? 4 : mat == C_I2 ? 6 : 8;
+      return j == 0 ? ext : j == 1 ? ext - 1 : -1;
+    };
+    int guard = 0;
+    while (v > 0 && h > 0 && sc > 0) {
+      if (++guard > 4 * (bt_plen + bt_tlen) + 16) { err = ST_INTERNAL; break; }
+      const int mismatch = sc - pn.x, gap_open1 = sc - pn.o1 - pn.e1, gap_extend1 = sc - pn.e1;
+      const int gap_open2 = sc - pn.o2 - pn.e2, gap_extend2 = sc - pn.e2;
+      // One fetch for all lanes: which row and diagonal a lane reads is arithmetic on its lane number, so the (up to nine)
+      // candidates of a step are ONE pair of vector loads and one wait.  (A branch per lane -- a switch over the lane number with
+      // a fetch in every case -- runs its cases one after the other, each waiting for its own loads: up to nine memory round trips
+      // in series per edit)
+      int cand = -1;
+      {
+        const int ms = lane < 9 ? slot_ms(matrix, lane) : -1;
+        if (ms >= 0) {
+          int comp, cs, ck, add, type;
+          cand_desc(ms, sc, k, comp, cs, ck, add, type);
+          cand = bt_fetch_twin<OffT>(kp, base_meta, hist, kmin, score, comp, cs, ck, add, type, mirror);
+        }
+      }
+      // max over lanes 0..15 on the DPP network (row_shr 1, 2, 4, 8 leave it in lane 15; lanes 9.. hold -1)
+      cand = max(cand, __builtin_amdgcn_update_dpp(-1, cand, 0x111, 0xf, 0xf, false));
+      cand = max(cand, __builtin_amdgcn_update_dpp(-1, cand, 0x112, 0xf, 0xf, false));
+      cand = max(cand, __builtin_amdgcn_update_dpp(-1, cand, 0x114, 0xf, 0xf, false));
+      cand = max(cand, __builtin_amdgcn_update_dpp(-1, cand, 0x118, 0xf, 0xf, false));
+      const int max_all = __builtin_amdgcn_readlane(cand, 15);
+      if (max_all < 0) { err = ST_INTERNAL; break; }
+      if (matrix == C_M) {
+        const int max_offset = max_all >> 4;
+        const int num_matches = offset - max_offset;
+        if (num_matches < 0) { err = ST_INTERNAL; break; }
+        push(0, num_matches);
+        offset = max_offset;
+        v = offset - k;
+        h = offset;
+        if (v <= 0 || h <= 0) break;
+      }
+      const int bt = max_all & 0xF;
+      switch (bt) {
+        case BT_M: sc = mismatch; matrix = C_M; break;
+        case BT_I1_OPEN: sc = gap_open1; matrix = C_M; break;
+        case BT_I1_EXT: sc = gap_extend1; matrix = C_I1; break;
+        case BT_I2_OPEN: sc = gap_open2; matrix = C_M; break;
+        case BT_I2_EXT: sc = gap_extend2; matrix = C_I2; break;
+        case BT_D1_OPEN: sc = gap_open1; matrix = C_M; break;
+        case BT_D1_EXT: sc = gap_extend1; matrix = C_D1; break;
+        case BT_D2_OPEN: sc = gap_open2; matrix = C_M; break;
+        default: sc = gap_extend2; matrix = C_D2; break;
+      }
+      if (bt == BT_M) { push(1, 1); --offset; }
+      else if (bt <= BT_I2_EXT) { push(2, 1); --k; --offset; }
+      else { push(3, 1); ++k; }
+      v = offset - k;
+      h = offset;
+    }
+    if (!err) {
+      if (matrix == C_M) {
+        if (v > 0 && h > 0) {
+          const int nm = min(v, h);
+          push(0, nm);
+          v -= nm;
+          h -= nm;
+        }
+        push(3, v);
+        push(2, h);
+      } else if (v != 0 || h != 0 || sc != 0) {
+        err = ST_INTERNAL;
+      }
+    }
+    if (last_op >= 0) { if (lane == 0) events[nev] = ((uint32_t)last_cnt << 2) | (uint32_t)last_op; ++nev; }
+    if (lane == 0) { sh.nev = nev; sh.bt_total = total; if (err) sh.error = err; }
+  }
+  __syncthreads();
+  PROF_ADD(STAT_T_BACKTRACE, tb1);
+  const unsigned long long tb2 = PROF_NOW();
+  if (uni(sh.error)) return uni(sh.error);
+  // ---- emission: events were produced end -> start
+  const int nev = uni(sh.nev);
+  Emit er = em;  // (by value: both Emits stay in registers)
+  if (mirror) er = em_b;
+  for (int e = nev - 1; e >= 0; --e) {
+    const uint32_t ev = (uint32_t)uni((int)events[e]);
+    const uint32_t opi = ev & 3u;
+    emit_run(er, opi == 0 ? 'M' : opi == 1 ? 'X' : opi == 2 ? 'I' : 'D', (int)(ev >> 2));
+  }
+  if (mirror) em_b = er;
+  else em = er;
+  __syncthreads();  // events / sh.nev are reused by the next trip and by the next base case
+  PROF_ADD(STAT_T_EMIT, tb2);
+  }
+  return ST_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // BiWFA breakpoint search (A.6)
 // ---------------------------------------------------------------------------------------------
 constexpr int BP_OK = 0, BP_END_REACHED = 100, BP_RESTART = 101, BP_ABOVE_BOUND = 102;
@@ -3688,9 +3965,41 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
         else if (rc != BP_OK) { status = rc; break; }
       }
       }
+      bool shared_base = false;
+      if (split && kp.twin_base != 0) {
+        // A shared task that needs no search.  An empty half is a gap run in either orientation -- A's deletion is B's insertion.
+        // A base case runs its wavefronts once, in A's frame, and is backtraced for both orientations; a
+        // score-only unit needs its score alone.
+        if (tlen == 0 || plen == 0) {
+          const int n = max(plen, tlen);
+          const int pen_gap = n > 0 ? min(pn.o1 + n * pn.e1, P2 ? pn.o2 + n * pn.e2 : INT_MAX) : 0;
+          emit_run(em, tlen == 0 ? 'D' : 'I', n);
+          emit_run(em_o, plen == 0 ? 'D' : 'I', n);
+          if (top) penalty = pen_gap;
+          if (top_o) penalty_o = pen_gap;
+          top = top_o = false;
+          continue;
+        }
+        if (t.score_remaining <= FALLBACK_MIN_SCORE) {  // (after BP_END_REACHED the task is staged already)
+          cx.plen = plen;
+          cx.tlen = tlen;
+          cx.P[0] = to_global(Pf + t.pb);
+          cx.T[0] = to_global(Tf + t.tb);
+          cx.P[1] = to_global(Pr + (plenT - t.pe));
+          cx.T[1] = to_global(Tr + (tlenT - t.te));
+          cx.kmin[0] = cx.kmin[1] = 0;
+          cx.wcols = 0;
+          cx.Pw = Pw;
+          cx.Tw = Tw;
+          cx.pb_abs = t.pb;
+          cx.tb_abs = t.tb;
+          stage_sequences<OffT>(kp, lds, cx);
+        }
+        split = false;
+        do_base = shared_base = true;
+      }
       if (split) {
-        // a shared task that needs no search (an empty half, a base case): each orientation takes it as a task of its own, so
-        // that the code below stays the plain path's
+        // (AWV_F_NO_TWIN_BASE) each orientation takes the task as one of its own, so that the code below stays the plain path's
         if (sp + 2 > STACK_CAP) { status = ST_TWIN_REDO; break; }
         if (tid == 0) {
           stack[sp] = Task{t.tb, t.te, t.pb, t.pe, twin_comp(t.cb) | (TM_B << 8), twin_comp(t.ce), t.score_remaining, t.known};
@@ -3702,10 +4011,16 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
       }
       if (do_base) {
         int pen_b = 0;
-        const int rc = base_align<P2, OffT>(kp, sh, lds, cx, hist, hist_rs, events, t.cb, t.ce, em, pen_b, lstats);
-        if (rc != ST_OK) { status = rc; break; }
+        const int rc = base_align_twin<P2, OffT>(kp, sh, lds, cx, hist, hist_rs, events, t.cb, t.ce, em, pen_b, lstats, em_o, shared_base && !kp.score_only);
+        // (whatever goes wrong inside a shared base case ends sharing for the unit: both entries are then aligned alone, with
+        // fresh Emits)
+        if (rc != ST_OK) { status = shared_base ? ST_TWIN_REDO : rc; break; }
         if (top) penalty = pen_b;
         top = false;
+        if (shared_base) {  // (the swapped pair's optimal penalty is the same number)
+          if (top_o) penalty_o = pen_b;
+          top_o = false;
+        }
         continue;
       }
       if (kp.score_only) {  // the top level's breakpoint score is the penalty: no sub-problems, no CIGAR

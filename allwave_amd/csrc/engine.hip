@@ -736,6 +736,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       kp.unit_first = twin_here ? e->d_unit_first.p : nullptr;
       kp.unit_twin = twin_here ? e->d_unit_twin.p : nullptr;
       kp.twin_levels = (e->cfg.flags & AWV_F_TWIN_TOP_ONLY) ? 1 : INT_MAX;
+      kp.twin_base = (e->cfg.flags & AWV_F_NO_TWIN_BASE) ? 0 : 1;
       kp.pen = dp;
       kp.ring = ring;
       // 32-bit rows: sweeps of at most TMAX32 scores, at most CHAIN_MAX32 of them chained (a lane vector is four registers)

@@ -108,6 +108,8 @@ typedef struct {
 #define AWV_F_NO_TWIN 2048     /* align every entry of a pair list on its own (default: an entry (q, t) and its swapped entry (t, q) in the same launch
                                   are aligned as one unit that shares their breakpoint searches) */
 #define AWV_F_TWIN_TOP_ONLY 4096 /* tests and A/B measurements only: such units share their top-level search only (default: every search whose sub-problem is still a mirror image) */
+#define AWV_F_NO_TWIN_BASE 8192 /* tests and A/B measurements only: a base case under a shared search is run once per orientation (default: its wavefronts
+                                   run once and are backtraced for both orientations) */
 
 /* penalties as allwave passes them to lib_wfa2 (src/alignment.rs:263-289) */
 typedef struct {
