@@ -199,7 +199,7 @@ int launch(const awp::EngineView& v, State* st, const awv_penalties& pen, int32_
   kp.npairs = n;
   kp.pen = pen;
   kp.match_bonus = match_bonus;
-  const unsigned grid = (unsigned)std::min<int64_t>(n, (int64_t)st->num_cus * WAVES_PER_CU);
+  const unsigned grid = (unsigned)std::min<int64_t>(n, v.workgroups > 0 ? (int64_t)v.workgroups : (int64_t)st->num_cus * WAVES_PER_CU);
   CL_TRY(hipEventRecord(st->ev0, v.stream));
   hipLaunchKernelGGL(awv_clip_kernel, dim3(grid), dim3(64), 0, v.stream, kp);
   CL_TRY(hipGetLastError());

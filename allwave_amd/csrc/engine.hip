@@ -1450,6 +1450,7 @@ void awv_internal_device_view(awv_engine* e, awp::EngineView* v) {
   v->off = e->seqs.d_off.p;
   v->len = e->seqs.d_len.p;
   v->len_host = e->seqs.len.data();
+  v->workgroups = e->cfg.workgroups;
 }
 int awv_internal_view(awv_engine* e, awp::EngineView* v) {
   if (!e || !v) return fail(AWV_ERR_ARG, "null engine");

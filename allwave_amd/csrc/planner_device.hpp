@@ -31,6 +31,7 @@ struct EngineView {
   const uint64_t* off = nullptr;    // device, n + 1
   const int32_t* len = nullptr;     // device, n
   const int32_t* len_host = nullptr;  // host, n
+  int workgroups = 0;               // awv_engine_config.workgroups: the grid cap of the record kernels (verify / clip / split), 0 = their default
 };
 
 }  // namespace awp

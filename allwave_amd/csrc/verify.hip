@@ -354,7 +354,7 @@ int launch(const awp::EngineView& v, State* st, const awv_penalties& pen, const 
   kp.counters = st->d_counters.p;
   kp.npairs = n;
   kp.pen = pen;
-  const unsigned grid = (unsigned)std::min<int64_t>(n, (int64_t)st->num_cus * WAVES_PER_CU);
+  const unsigned grid = (unsigned)std::min<int64_t>(n, v.workgroups > 0 ? (int64_t)v.workgroups : (int64_t)st->num_cus * WAVES_PER_CU);
   VF_TRY(hipEventRecord(st->ev0, v.stream));
   hipLaunchKernelGGL(awv_verify_kernel, dim3(grid), dim3(64), 0, v.stream, kp);
   VF_TRY(hipGetLastError());

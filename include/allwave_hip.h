@@ -77,7 +77,9 @@ typedef struct awv_engine awv_engine;
 
 typedef struct {
   int32_t device;          /* HIP device ordinal */
-  int32_t workgroups;      /* persistent workgroups = pairs in flight (0 = engine default: 16 per CU) */
+  int32_t workgroups;      /* persistent workgroups = pairs in flight (0 = engine default: 16 per CU); the align kernels open
+                              workgroups / (waves per workgroup) slots, at least one, and the record kernels (verify, clip,
+                              split) launch min(records, workgroups) one-wave workgroups -- 0: min(records, 16 per CU) */
   int64_t max_batch_pairs; /* pairs per launch (0 = default) */
   int64_t max_arena_bytes; /* CIGAR arena budget per launch (0 = default 8 GiB) */
   int32_t flags;           /* AWV_F_* */
