@@ -11,6 +11,7 @@
 #include "verify_device.hpp"   // (the per-batch check of awv_align_pairs_verified, verify.hip)
 #include "clip_device.hpp"     // (the per-batch clip of awv_align_pairs_clipped, clip.hip)
 #include "split_device.hpp"    // (the per-batch split of awv_align_pairs_split, split.hip)
+#include "normalize_device.hpp"  // (the per-batch normalization under awv_engine_set_normalize, normalize.hip)
 #include "kernels_awv.hpp"  // (the awv:: kernels themselves are instantiated in kernels_awv.hip -- here only the types)
 #define AWV_NS awv
 #define AWV_WG 64
@@ -173,6 +174,8 @@ struct awv_engine {
   awvf::State* verify = nullptr;   // verify.hip: buffers and stats of the verify launches
   awvc::State* clip = nullptr;     // clip.hip: buffers and stats of the clip launches
   awvs::State* split = nullptr;    // split.hip: likewise for the split launches
+  awvn::State* normalize = nullptr;  // normalize.hip: likewise for the normalize launches
+  int32_t norm_mode = AWV_NORM_OFF;  // awv_engine_set_normalize: read at the start of every aligning call
 };
 
 namespace {
@@ -358,6 +361,8 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
   HIP_TRY(hipSetDevice(e->device));
   e->stats = awv_stats{};
   for (uint64_t& v : e->twin_stats) v = 0;
+  const int32_t norm = score_only ? AWV_NORM_OFF : e->norm_mode;  // (off: no launch, no allocation, nothing below changes)
+  if (norm != AWV_NORM_OFF) awvn::stats_reset(e->normalize);
   if (npairs == 0) return AWV_OK;
   for (int64_t i = 0; i < npairs; ++i) {
     if (pairs[i].q_idx < 0 || pairs[i].q_idx >= s.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= s.n)
@@ -950,6 +955,11 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
     }
     const bool want_cigar = sink && !score_only && !(e->cfg.flags & AWV_F_KEEP_ON_DEVICE);
     lap("results on host");
+    if (norm != AWV_NORM_OFF) {  // first of the record steps: the check, the clip and the split see the normalized bytes
+      const awvn::SeqView sv{s.n, s.d_seq[0].p, s.d_seq[2].p, s.d_off.p, s.d_len.p};
+      if (int rc = awvn::normalize_batch(e, sv, norm, pairs + first, n, hres.data(), e->d_cigar.p, arena, spans ? spans + first : nullptr)) return rc;
+      lap("batch normalized");
+    }
     if (vout) {  // the groups of a batch overwrite d_results: the batch's records, as gathered in hres, go up once for the check
       if (int rc = awvf::verify_batch(e, pen, pairs + first, n, hres.data(), e->d_cigar.p, arena, vout + first, spans ? spans + first : nullptr)) return rc;
       lap("batch verified");
@@ -1083,6 +1093,8 @@ void awv_engine_destroy(awv_engine* e) {
   e->clip = nullptr;
   awvs::state_release(e->split);
   e->split = nullptr;
+  awvn::state_release(e->normalize);
+  e->normalize = nullptr;
   e->seqs.release();
   e->ring_mem.release();
   e->hist_mem.release();
@@ -1463,6 +1475,8 @@ awp::PlanState*& awv_internal_plan(awv_engine* e) { return e->plan; }
 awvf::State*& awv_internal_verify(awv_engine* e) { return e->verify; }
 awvc::State*& awv_internal_clip(awv_engine* e) { return e->clip; }
 awvs::State*& awv_internal_split(awv_engine* e) { return e->split; }
+awvn::State*& awv_internal_normalize(awv_engine* e) { return e->normalize; }
+int32_t& awv_internal_normalize_mode(awv_engine* e) { return e->norm_mode; }
 uint64_t awv_internal_max_arena(const awv_engine* e) { return e->cfg.max_arena_bytes > 0 ? (uint64_t)e->cfg.max_arena_bytes : (uint64_t)8 << 30; }
 int awv_internal_fail(int code, const std::string& msg) { return fail(code, msg); }
 int awv_internal_check_penalties(const awv_penalties* pen) { return check_penalty_signs(pen); }

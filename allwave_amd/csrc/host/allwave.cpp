@@ -399,6 +399,26 @@ void align_ranges(const std::vector<Sequence>& sequences, const std::vector<Alig
   if (split_stats) *split_stats = it.last_split_stats();
 }
 
+void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
+                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
+                  awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
+                  BoundStats* bound_stats, int clip_match_bonus, int64_t clip_min_score, ClipStats* clip_stats, int split_match_bonus,
+                  int64_t split_min_score, SplitStats* split_stats, int normalize, awv_norm_stats* normalize_stats) {
+  AllPairIterator it = AllPairIterator::for_ranges(sequences, ranges, std::move(params));
+  it.with_devices(devices).with_verify(verify).with_normalize(normalize);
+  if (clip_match_bonus != 0) it.with_clip(clip_match_bonus, clip_min_score);
+  if (split_match_bonus != 0) it.with_split(split_match_bonus, split_min_score);
+  if (max_penalty) it.with_max_penalty(*max_penalty);
+  if (max_divergence) it.with_max_divergence(*max_divergence);
+  it.for_each_with_callback(callback);
+  if (failures) *failures = it.verify_failures();
+  if (verify_stats) *verify_stats = it.last_verify_stats();
+  if (bound_stats) *bound_stats = it.last_bound_stats();
+  if (clip_stats) *clip_stats = it.last_clip_stats();
+  if (split_stats) *split_stats = it.last_split_stats();
+  if (normalize_stats) *normalize_stats = it.last_normalize_stats();
+}
+
 AllPairIterator::AllPairIterator(const std::vector<Sequence>& sequences, AlignmentParams params)
     : AllPairIterator(sequences, std::move(params), true) {}
 
@@ -558,7 +578,14 @@ AllPairIterator AllPairIterator::with_sparsification(SparsificationStrategy stra
   it.clip_min_score_ = clip_min_score_;
   it.split_bonus_ = split_bonus_;
   it.split_min_score_ = split_min_score_;
+  it.normalize_ = normalize_;
   return it;
+}
+AllPairIterator& AllPairIterator::with_normalize(int direction) {
+  if (direction != AWV_NORM_OFF && direction != AWV_NORM_LEFT && direction != AWV_NORM_RIGHT)
+    throw std::invalid_argument("with_normalize: AWV_NORM_OFF, AWV_NORM_LEFT or AWV_NORM_RIGHT");
+  normalize_ = direction;
+  return *this;
 }
 AllPairIterator& AllPairIterator::with_verify(bool on) { verify_ = on; return *this; }
 AllPairIterator& AllPairIterator::with_clip(int match_bonus, int64_t min_score) {
@@ -860,6 +887,8 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   std::vector<ClipStats> cst(S);   // likewise
   const bool splitting = split() && !call.score_only;
   std::vector<SplitStats> sst(S);  // likewise
+  const int normalizing = call.score_only ? AWV_NORM_OFF : normalize_;
+  std::vector<awv_norm_stats> nst(S, awv_norm_stats{});  // per slot: written by its submitter thread only
   auto worker = [&](size_t s) {
     awv_engine* e = nullptr;
     try {
@@ -1055,9 +1084,25 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
           ctx.sp = &spc;
           ctx.sst = &sst[s];
         }
+        // the slot's engine is this thread's until its device lock goes: the mode holds for this call and is off again after it
+        if (normalizing != AWV_NORM_OFF && awv_engine_set_normalize(e, normalizing) != AWV_OK) throw AlignmentError(std::string("normalize: ") + awv_last_error());
         const int rc = engine_call(e, call.score_only, call.max_penalty, pen, ap.data(), m, sink, &ctx, verify ? vr.data() : nullptr,
                                    ranges_ ? rp.data() : nullptr, bounded_run ? bounds.data() : call.align_bounds, clip_bonus_,
                                    clipping ? cr.data() : nullptr, splitting ? &spc : nullptr);
+        if (normalizing != AWV_NORM_OFF) {
+          awv_engine_set_normalize(e, AWV_NORM_OFF);
+          if (rc == AWV_OK) {
+            awv_norm_stats nx{};
+            awv_engine_normalize_stats(e, &nx);
+            nst[s].kernel_ms += nx.kernel_ms;
+            nst[s].pairs += nx.pairs;
+            nst[s].records_moved += nx.records_moved;
+            nst[s].runs += nx.runs;
+            nst[s].runs_moved += nx.runs_moved;
+            nst[s].columns_moved += nx.columns_moved;
+            nst[s].columns += nx.columns;
+          }
+        }
         lap("aligned + sunk");
         awv_stats x{};
         awv_engine_stats(e, &x);
@@ -1112,8 +1157,16 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
     bound_stats_ = BoundStats{};
     clip_stats_ = ClipStats{};
     split_stats_ = SplitStats{};
+    normalize_stats_ = awv_norm_stats{};
   }
   for (size_t s = 0; s < S; ++s) {
+    normalize_stats_.kernel_ms += nst[s].kernel_ms;
+    normalize_stats_.pairs += nst[s].pairs;
+    normalize_stats_.records_moved += nst[s].records_moved;
+    normalize_stats_.runs += nst[s].runs;
+    normalize_stats_.runs_moved += nst[s].runs_moved;
+    normalize_stats_.columns_moved += nst[s].columns_moved;
+    normalize_stats_.columns += nst[s].columns;
     split_stats_.pairs += sst[s].pairs;
     split_stats_.segments += sst[s].segments;
     split_stats_.empty += sst[s].empty;

@@ -236,6 +236,15 @@ class AllPairIterator {  // iterator.rs:12-171
   SplitStats last_split_stats() const { return split_stats_; }
   // of the last run (next(): of the chunks since the list's start), summed over the slots
   ClipStats last_clip_stats() const { return clip_stats_; }
+  // Every alignment consumer receives each alignment with its gap runs at their left- (AWV_NORM_LEFT) or right-normal
+  // (AWV_NORM_RIGHT) place (awv_engine_set_normalize; include/allwave_hip.h has the contract): every slot's engine gets the
+  // mode for its engine calls, under its device's mutex, and is switched off again afterwards.  Normalization comes before the
+  // check, the clip and the split, which then describe the normalized string; records and coordinates are unchanged.
+  // scores() and orientation ignore the setting.  AWV_NORM_OFF: off (the default).
+  AllPairIterator& with_normalize(int direction);
+  int normalize() const { return normalize_; }
+  // of the last run (next(): of the chunks since the list's start), summed over the slots (kernel_ms: summed kernel time)
+  awv_norm_stats last_normalize_stats() const { return normalize_stats_; }
   AllPairIterator& with_max_penalty(int max_penalty);
   AllPairIterator& with_max_divergence(double max_divergence);
   // of the last run (next(): of the chunks since the list's start), summed over the slots
@@ -326,6 +335,8 @@ class AllPairIterator {  // iterator.rs:12-171
   int clip_bonus_ = 0;  // with_clip (0: off)
   int64_t clip_min_score_ = 1;
   ClipStats clip_stats_{};
+  int normalize_ = AWV_NORM_OFF;  // with_normalize
+  awv_norm_stats normalize_stats_{};
   int split_bonus_ = 0;  // with_split (0: off)
   int64_t split_min_score_ = 1;
   SplitStats split_stats_{};
@@ -362,6 +373,7 @@ class AllPairParallelIterator {
   BoundStats last_bound_stats() const { return it_.last_bound_stats(); }
   ClipStats last_clip_stats() const { return it_.last_clip_stats(); }
   SplitStats last_split_stats() const { return it_.last_split_stats(); }
+  awv_norm_stats last_normalize_stats() const { return it_.last_normalize_stats(); }
  private:
   friend class AllPairIterator;
   explicit AllPairParallelIterator(const AllPairIterator& it) : it_(it) {}
@@ -408,6 +420,13 @@ void align_ranges(const std::vector<Sequence>& sequences, const std::vector<Alig
                   awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
                   BoundStats* bound_stats, int clip_match_bonus, int64_t clip_min_score, ClipStats* clip_stats, int split_match_bonus,
                   int64_t split_min_score, SplitStats* split_stats = nullptr);
+// the same with every alignment normalized first (AllPairIterator::with_normalize; AWV_NORM_OFF: off); normalize_stats
+// (nullable) receives what normalization did
+void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
+                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
+                  awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
+                  BoundStats* bound_stats, int clip_match_bonus, int64_t clip_min_score, ClipStats* clip_stats, int split_match_bonus,
+                  int64_t split_min_score, SplitStats* split_stats, int normalize, awv_norm_stats* normalize_stats = nullptr);
 
 // ---- mappings in, alignments out: the interval pairs a PAF file names (columns 1-9 of each line) ----
 struct PafRangeLine {

@@ -41,6 +41,9 @@ thread_local ClipStats g_clip_stats{};
 thread_local int g_next_split_bonus = 0;
 thread_local int64_t g_next_split_min_score = 1;
 thread_local SplitStats g_split_stats{};
+// And normalization: awh_set_normalize (AWV_NORM_*; 0: off), awh_last_normalize.
+thread_local int g_next_normalize = AWV_NORM_OFF;
+thread_local awv_norm_stats g_norm_stats{};
 struct RunOptions {
   int64_t max_penalty;
   double max_divergence;
@@ -48,13 +51,15 @@ struct RunOptions {
   int64_t clip_min_score;
   int split_bonus;
   int64_t split_min_score;
+  int normalize;
   void apply(AllPairIterator& it) const {
+    if (normalize != AWV_NORM_OFF) it.with_normalize(normalize);
     if (max_penalty >= 0) it.with_max_penalty((int)std::min<int64_t>(max_penalty, INT32_MAX));
     if (max_divergence >= 0.0) it.with_max_divergence(max_divergence);
     if (clip_bonus != 0) it.with_clip(clip_bonus, clip_min_score);
     if (split_bonus != 0) it.with_split(split_bonus, split_min_score);
   }
-  bool any() const { return max_penalty >= 0 || max_divergence >= 0.0 || clip_bonus != 0 || split_bonus != 0; }
+  bool any() const { return max_penalty >= 0 || max_divergence >= 0.0 || clip_bonus != 0 || split_bonus != 0 || normalize != AWV_NORM_OFF; }
 };
 // what an alignment hook leaves behind of its iterator's bound and clip counters (awh_last_bounds, awh_last_clip)
 template <typename It>
@@ -62,9 +67,12 @@ void keep_stats(const It& it) {
   g_bound_stats = it.last_bound_stats();
   g_clip_stats = it.last_clip_stats();
   g_split_stats = it.last_split_stats();
+  g_norm_stats = it.last_normalize_stats();
 }
 RunOptions take_run_options() {
-  const RunOptions b{g_next_max_penalty, g_next_max_divergence, g_next_clip_bonus, g_next_clip_min_score, g_next_split_bonus, g_next_split_min_score};
+  const RunOptions b{g_next_max_penalty, g_next_max_divergence, g_next_clip_bonus, g_next_clip_min_score, g_next_split_bonus, g_next_split_min_score, g_next_normalize};
+  g_next_normalize = AWV_NORM_OFF;
+  g_norm_stats = awv_norm_stats{};
   g_next_split_bonus = 0;
   g_next_split_min_score = 1;
   g_split_stats = SplitStats{};
@@ -704,6 +712,21 @@ void awh_set_clip(int match_bonus, int64_t min_score) {
 void awh_set_split(int match_bonus, int64_t min_score) {
   g_next_split_bonus = match_bonus;
   g_next_split_min_score = min_score;
+}
+// ---- gap runs at their normal place ----
+// The calling thread's NEXT alignment hook runs with_normalize(direction) (AWV_NORM_LEFT / AWV_NORM_RIGHT; AWV_NORM_OFF: off); the
+// hooks after it run without again.
+void awh_set_normalize(int direction) { g_next_normalize = direction; }
+// last_normalize_stats() of the calling thread's last alignment hook: {pairs, records_moved, runs, runs_moved, columns_moved,
+// columns} and the kernel time
+void awh_last_normalize(uint64_t out[6], double* kernel_ms) {
+  out[0] = g_norm_stats.pairs;
+  out[1] = g_norm_stats.records_moved;
+  out[2] = g_norm_stats.runs;
+  out[3] = g_norm_stats.runs_moved;
+  out[4] = g_norm_stats.columns_moved;
+  out[5] = g_norm_stats.columns;
+  *kernel_ms = g_norm_stats.kernel_ms;
 }
 // last_split_stats() of the calling thread's last alignment hook: {pairs, segments, empty} and the kernel time
 void awh_last_split(uint64_t out[3], double* kernel_ms) {

@@ -54,6 +54,8 @@ struct Args {
   bool have_clip = false, have_clip_min_score = false;
   long split = 0, split_min_score = 0;  // --split A --split-min-score S: every alignment split into all its segments that score at least S
   bool have_split = false, have_split_min_score = false;
+  int normalize = AWV_NORM_OFF;  // --normalize left|right: every alignment's gap runs moved to their left- / right-normal place
+  bool have_normalize = false;
 };
 
 [[noreturn]] void die(const std::string& m, int code = 2) {
@@ -239,6 +241,12 @@ int main(int argc, char** argv) {
       (bonus ? a.split : a.split_min_score) = n;
       (bonus ? a.have_split : a.have_split_min_score) = true;
     }
+    else if (k == "--normalize") {
+      const std::string v = val();
+      if (v != "left" && v != "right") die("--normalize expects left or right");
+      a.normalize = v == "left" ? AWV_NORM_LEFT : AWV_NORM_RIGHT;
+      a.have_normalize = true;
+    }
     else if (k == "--clip" || k == "--clip-min-score") {
       const std::string v = val();
       char* end = nullptr;
@@ -273,11 +281,11 @@ int main(int argc, char** argv) {
                    "                   [-t threads] [--wfa-orientation|--wfa-orientation-full|--forward-only] [-k prefixes | -e prefixes] [--mash-matrix]\n"
                    "                   [--device N | --devices LIST] [--shard R/N] [--score-only [--max-penalty N]] [--plan-device N] [--verify]\n"
                    "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
-                   "                   [--split A --split-min-score S]\n"
+                   "                   [--split A --split-min-score S] [--normalize left|right]\n"
                    "       allwave_hip -i in.fa --check-paf FILE [-s scores | -x ANI] [--check-optimal] [--partial] [--device N]\n"
                    "       allwave_hip -i in.fa --align-paf FILE [-s scores | -x ANI] [-o out.paf] [--verify] [--score-only] [--device N | --devices LIST]\n"
                    "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
-                   "                   [--split A --split-min-score S]\n"
+                   "                   [--split A --split-min-score S] [--normalize left|right]\n"
                    "  --verify         check every alignment on the device before it is written (columns, counts, penalty); the summary\n"
                    "                   line gains `verified N pairs, F failed, K ms`, failures go to stderr, exit status 4 if any\n"
                    "  --check-paf FILE align nothing: check every line of FILE (12 columns + cg:Z:) against in.fa on the device; one line\n"
@@ -309,6 +317,9 @@ int main(int argc, char** argv) {
                    "                   lines, in column order, or dropped; also with --align-paf, where one input line may give several lines;\n"
                    "                   the summary line gains `split N pairs into G segments, E without a segment, K ms`\n"
                    "  --split-min-score S  with --split: the least score of a segment (required: no default can be derived)\n"
+                   "  --normalize left|right  move every alignment's gap runs as far left (right) as they go among co-optimal placements, on\n"
+                   "                   the device, before --verify, --clip and --split see them: only cg:Z: changes; also with --align-paf;\n"
+                   "                   the summary line gains `normalized N pairs, R runs moved, K ms`\n"
                    "  --plan-device N  plan on device N: --mash-matrix, the -p pair list and mash orientation (the same output as\n"
                    "                   the host planner; with --shard every rank plans the whole list on its own plan device)\n";
       return 0;
@@ -334,6 +345,9 @@ int main(int argc, char** argv) {
   if (a.have_clip && a.score_only) die("the argument '--clip' cannot be used with '--score-only'");
   if (a.have_clip && a.have_check_paf) die("the argument '--clip' cannot be used with '--check-paf'");
   if (a.have_clip && a.mash_matrix) die("the argument '--clip' cannot be used with '--mash-matrix'");
+  if (a.have_normalize && a.score_only) die("the argument '--normalize' cannot be used with '--score-only'");
+  if (a.have_normalize && a.have_check_paf) die("the argument '--normalize' cannot be used with '--check-paf'");
+  if (a.have_normalize && a.mash_matrix) die("the argument '--normalize' cannot be used with '--mash-matrix'");
   if (a.check_optimal && !a.have_check_paf) die("the argument '--check-optimal' requires '--check-paf'");
   if (a.verify && a.score_only) die("the argument '--verify' cannot be used with '--score-only'");
   if (a.verify && a.mash_matrix) die("the argument '--verify' cannot be used with '--mash-matrix'");
@@ -449,6 +463,7 @@ int main(int argc, char** argv) {
     const bool bounded = a.have_max_align_penalty || a.have_max_divergence;
     if (a.have_clip) it.with_clip((int)a.clip, (int64_t)a.clip_min_score);
     if (a.have_split) it.with_split((int)a.split, (int64_t)a.split_min_score);
+    if (a.have_normalize) it.with_normalize(a.normalize);
     if (a.forward_only) it.with_orientation(Orientation::ForwardOnly);
     it.with_full_wfa_orientation(a.wfa_orientation_full);
     it.with_devices(devices);
@@ -514,7 +529,7 @@ int main(int argc, char** argv) {
     if (done + above + unclipped + (size_t)ss.pairs != total + (size_t)ss.segments) die("internal: wrote " + std::to_string(done) + " of " + std::to_string(total) + (a.score_only ? " pairs" : " PAF lines"), 1);
     if (!a.no_progress) {
       const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      char buf[480];
+      char buf[640];
       int w = snprintf(buf, sizeof(buf), "[%.1fs] %zu/%zu (100.0%%) %.1f alignments/sec", secs, done, total, done / std::max(secs, 1e-9));
       if (a.have_align_paf && w > 0 && (size_t)w < sizeof(buf)) w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", %zu bad lines", bad_lines);
       if (bounded && w > 0 && (size_t)w < sizeof(buf)) w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", %zu pairs above the bound", above);
@@ -524,6 +539,11 @@ int main(int argc, char** argv) {
       if (a.have_split && w > 0 && (size_t)w < sizeof(buf))
         w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", split %llu pairs into %llu segments, %llu without a segment, %.2f ms", (unsigned long long)ss.pairs,
                       (unsigned long long)ss.segments, (unsigned long long)ss.empty, ss.kernel_ms);
+      if (a.have_normalize && w > 0 && (size_t)w < sizeof(buf)) {
+        const awv_norm_stats ns = it.last_normalize_stats();
+        w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", normalized %llu pairs, %llu runs moved, %.2f ms", (unsigned long long)ns.pairs,
+                      (unsigned long long)ns.runs_moved, ns.kernel_ms);
+      }
       if (a.verify && w > 0 && (size_t)w < sizeof(buf)) {
         const awv_verify_stats vs = it.last_verify_stats();
         snprintf(buf + w, sizeof(buf) - (size_t)w, ", verified %llu pairs, %zu failed, %.2f ms", (unsigned long long)vs.pairs,

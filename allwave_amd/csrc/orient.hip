@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "normalize_device.hpp"  // (awv_internal_normalize_mode)
 #include "planner_device.hpp"  // (EngineView, awv_internal_view, awv_internal_fail)
 
 namespace awo {
@@ -371,7 +372,12 @@ int orient_core(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, 
       op[(size_t)2 * j + 1] = awv_pair{pairs[tail[(size_t)j]].q_idx, pairs[tail[(size_t)j]].t_idx, 1};
     }
     std::vector<awv_result> orr((size_t)2 * m);
-    if (int rc = awv_align_pairs(e, pen, op.data(), 2 * m, orr.data(), nullptr, nullptr)) return rc;
+    int32_t& norm_mode = awv_internal_normalize_mode(e);  // orientation ignores the engine's normalize mode: edit counts do not move
+    const int32_t saved_mode = norm_mode;
+    norm_mode = AWV_NORM_OFF;
+    const int arc = awv_align_pairs(e, pen, op.data(), 2 * m, orr.data(), nullptr, nullptr);
+    norm_mode = saved_mode;
+    if (arc) return arc;
     awv_stats st{};
     awv_engine_stats(e, &st);
     add_stats(total, st);

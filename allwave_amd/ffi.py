@@ -59,6 +59,14 @@ AWV_CL_SKIPPED = 1
 AWV_CL_EMPTY = 2
 AWV_CL_BAD_OP = 3
 AWV_CLIP_MAX_BONUS = 32767
+#: normalization: the engine's mode / a call's direction, and awv_norm_result.code
+AWV_NORM_OFF = 0
+AWV_NORM_LEFT = 1
+AWV_NORM_RIGHT = 2
+AWV_NM_OK = 0
+AWV_NM_SKIPPED = 1
+AWV_NM_BAD_OP = 2
+AWV_NM_LENGTHS = 3
 #: sketch kinds of device pair planning (awv_sketch)
 AWV_SK_CANONICAL = 0
 AWV_SK_FORWARD = 1
@@ -75,7 +83,9 @@ EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine
            "awv_clip_one_host", "awv_clip_cigars", "awv_align_pairs_clipped", "awv_align_ranges_clipped", "awv_engine_clip_stats",
            "awv_twin_stats",
            "awv_split_slots", "awv_split_layout_pairs", "awv_split_layout_ranges", "awv_split_one_host", "awv_split_cigars",
-           "awv_align_pairs_split", "awv_align_ranges_split", "awv_engine_split_stats")
+           "awv_align_pairs_split", "awv_align_ranges_split", "awv_engine_split_stats",
+           "awv_normalize_one_host", "awv_normalize_cigars", "awv_normalize_ranges", "awv_engine_set_normalize",
+           "awv_engine_normalize_stats")
 
 
 class EngineConfig(C.Structure):
@@ -124,6 +134,11 @@ class SplitStats(C.Structure):
                 ("columns_scanned", C.c_uint64)]
 
 
+class NormStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("pairs", C.c_uint64), ("records_moved", C.c_uint64), ("runs", C.c_uint64),
+                ("runs_moved", C.c_uint64), ("columns_moved", C.c_uint64), ("columns", C.c_uint64)]
+
+
 PAIR_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4")])
 #: awv_range_pair: the query interval on the query's forward strand (PAF convention), also with q_revcomp
 RANGE_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4"), ("q_beg", "<i4"), ("q_end", "<i4"),
@@ -139,6 +154,8 @@ CLIP_DTYPE = np.dtype([("code", "<i4"), ("reserved", "<i4"), ("score", "<i8"), (
                        ("num_ins", "<i4"), ("num_del", "<i4"), ("penalty", "<i4"), ("reserved2", "<i4")])
 #: awv_split_index: what the split found for one record; its segments are CLIP_DTYPE records in the caller's slot region
 SPLIT_INDEX_DTYPE = np.dtype([("code", "<i4"), ("count", "<i4"), ("column", "<i8")])
+#: awv_norm_result: what normalization did to one op string (columns_moved: the smallest offending column under AWV_NM_BAD_OP)
+NORM_DTYPE = np.dtype([("code", "<i4"), ("runs_moved", "<i4"), ("columns_moved", "<i8"), ("max_shift", "<i4"), ("reserved", "<i4")])
 #: awv_score_result
 SCORE_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4")])
 
@@ -210,8 +227,23 @@ def load():
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, SINK_FN, C.c_void_p]
         L.awv_align_ranges_split.argtypes = L.awv_align_pairs_split.argtypes
         L.awv_engine_split_stats.argtypes = [C.c_void_p, C.POINTER(SplitStats)]
+        L.awv_normalize_one_host.argtypes = [C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, C.c_int64, C.c_void_p,
+                                             C.c_void_p]
+        L.awv_normalize_cigars.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.awv_normalize_ranges.argtypes = L.awv_normalize_cigars.argtypes
+        L.awv_engine_set_normalize.argtypes = [C.c_void_p, C.c_int32]
+        L.awv_engine_normalize_stats.argtypes = [C.c_void_p, C.POINTER(NormStats)]
         _LIB = L
     return _LIB
+
+
+def norm_mode(normalize):
+    """None / "off" / "left" / "right" (or an AWV_NORM_* value) -> AWV_NORM_*."""
+    modes = {None: AWV_NORM_OFF, "off": AWV_NORM_OFF, "left": AWV_NORM_LEFT, "right": AWV_NORM_RIGHT,
+             AWV_NORM_OFF: AWV_NORM_OFF, AWV_NORM_LEFT: AWV_NORM_LEFT, AWV_NORM_RIGHT: AWV_NORM_RIGHT}
+    if isinstance(normalize, bool) or normalize not in modes:
+        raise ValueError("normalize: None, 'left' or 'right'")
+    return modes[normalize]
 
 
 class EngineError(RuntimeError):
@@ -282,12 +314,14 @@ class Engine:
             ranges = r
         return np.ascontiguousarray(ranges)
 
-    def align_ranges(self, scores, ranges, want_cigars=True, verify=False, max_penalty=None, clip=None, _sink_hook=None, split=None):
+    def align_ranges(self, scores, ranges, want_cigars=True, verify=False, max_penalty=None, clip=None, _sink_hook=None, split=None,
+                     normalize=None):
         """align_pairs on interval pairs (awv_align_ranges / awv_align_ranges_verified).  ranges: int array [n,7] (q_idx, t_idx,
         q_revcomp, q_beg, q_end, t_beg, t_end) or a RANGE_DTYPE array; the query interval is on the query's forward strand.
         The records' q_end / t_end are consumed lengths, relative to the range.  max_penalty: as for align_pairs
-        (awv_align_ranges_bounded); clip, split: as for align_pairs (awv_align_ranges_clipped, awv_align_ranges_split)."""
-        return self._align("awv_align_ranges", scores, self._range_array(ranges), want_cigars, verify, max_penalty, clip, _sink_hook, split)
+        (awv_align_ranges_bounded); clip, split, normalize: as for align_pairs (awv_align_ranges_clipped, awv_align_ranges_split)."""
+        return self._align("awv_align_ranges", scores, self._range_array(ranges), want_cigars, verify, max_penalty, clip, _sink_hook, split,
+                           normalize)
 
     def score_ranges(self, scores, ranges, max_penalty=None):
         """score_pairs on interval pairs (awv_score_ranges).  max_penalty: None, or one bound per range (negative: none)."""
@@ -308,7 +342,8 @@ class Engine:
         """verify_cigars on interval pairs (awv_verify_ranges)."""
         return self._verify("awv_verify_ranges", scores, self._range_array(ranges), results, arena)
 
-    def align_pairs(self, scores, pairs, want_cigars=True, verify=False, max_penalty=None, clip=None, _sink_hook=None, split=None):
+    def align_pairs(self, scores, pairs, want_cigars=True, verify=False, max_penalty=None, clip=None, _sink_hook=None, split=None,
+                    normalize=None):
         """pairs: int array [n,2] (q,t) or [n,3] (q,t,revcomp), or a PAIR_DTYPE array.
         Returns (results structured array, list of op-byte strings or None); verify=True: every finished pair is checked on
         the device (awv_align_pairs_verified) and a VERIFY_DTYPE array comes back as a third value.
@@ -324,8 +359,12 @@ class Engine:
         least min_score (awv_align_pairs_split; not together with clip).  One more value comes back, after the verify array
         when there is one: (index, segments), a SPLIT_INDEX_DTYPE array with one entry per pair and the list of each pair's
         segments as CLIP_DTYPE arrays, in column order.  With split, _sink_hook is called as _sink_hook(first, n, (index,
-        seg_first, slots)) -- the call's raw storage as filled so far."""
-        return self._align("awv_align_pairs", scores, self._pair_array(pairs), want_cigars, verify, max_penalty, clip, _sink_hook, split)
+        seg_first, slots)) -- the call's raw storage as filled so far.
+        normalize: None, "left" or "right": every finished pair's gap runs are moved to their left- (right-) normal place on
+        the device before the check, the clip, the split and the copy back (awv_engine_set_normalize for this call; the
+        engine's mode is off again afterwards).  Records are those of the unnormalized call; normalize_stats() reports."""
+        return self._align("awv_align_pairs", scores, self._pair_array(pairs), want_cigars, verify, max_penalty, clip, _sink_hook, split,
+                           normalize)
 
     def split_layout(self, pairs_or_ranges, match_bonus, min_score):
         """awv_split_layout_pairs / awv_split_layout_ranges: seg_first (uint64, n + 1) for a PAIR_DTYPE / RANGE_DTYPE array (or
@@ -344,7 +383,23 @@ class Engine:
     def _segment_lists(index, seg_first, slots):
         return [slots[int(seg_first[i]):int(seg_first[i]) + int(index["count"][i])].copy() for i in range(len(index))]
 
-    def _align(self, fn, scores, pairs, want_cigars, verify, max_penalty=None, clip=None, _sink_hook=None, split=None):
+    def set_normalize(self, normalize):
+        """awv_engine_set_normalize: the mode every later aligning call of this engine reads (None / "left" / "right")."""
+        rc = load().awv_engine_set_normalize(self._h, norm_mode(normalize))
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_engine_set_normalize")
+
+    def _align(self, fn, scores, pairs, want_cigars, verify, max_penalty=None, clip=None, _sink_hook=None, split=None, normalize=None):
+        """_align_plain under the engine mode `normalize` (None: the mode is left alone)."""
+        if norm_mode(normalize) == AWV_NORM_OFF:
+            return self._align_plain(fn, scores, pairs, want_cigars, verify, max_penalty, clip, _sink_hook, split)
+        self.set_normalize(normalize)
+        try:
+            return self._align_plain(fn, scores, pairs, want_cigars, verify, max_penalty, clip, _sink_hook, split)
+        finally:
+            self.set_normalize(None)
+
+    def _align_plain(self, fn, scores, pairs, want_cigars, verify, max_penalty=None, clip=None, _sink_hook=None, split=None):
         """awv_align_pairs / awv_align_ranges (`fn`; verify: its _verified variant; max_penalty: its _bounded variant; clip: its
         _clipped variant, which takes the other two as well) on a contiguous PAIR_DTYPE / RANGE_DTYPE array."""
         pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
@@ -442,6 +497,39 @@ class Engine:
         if rc != AWV_OK:
             raise EngineError(rc, fn)
         return vres
+
+    def normalize_cigars(self, direction, pairs, results, arena):
+        """awv_normalize_cigars: moves the gap runs of caller-supplied records (a RESULT_DTYPE array whose cigar_off / cigar_len
+        point into `arena`, bytes or a uint8 array) to their left- / right-normal place against the resident sequences, on
+        the device.  Returns (the normalized arena as a new uint8 array, a NORM_DTYPE array)."""
+        return self._normalize("awv_normalize_cigars", direction, self._pair_array(pairs), results, arena)
+
+    def normalize_ranges(self, direction, ranges, results, arena):
+        """normalize_cigars on interval pairs (awv_normalize_ranges)."""
+        return self._normalize("awv_normalize_ranges", direction, self._range_array(ranges), results, arena)
+
+    def _normalize(self, fn, direction, pairs, results, arena):
+        results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+        if results.shape != (len(pairs),):
+            raise ValueError("results: need one record per pair")
+        arena = np.frombuffer(bytes(arena), dtype=np.uint8).copy() if not isinstance(arena, np.ndarray) else np.array(arena, dtype=np.uint8)
+        nbytes = int(arena.size)
+        buf = arena if nbytes else np.zeros(1, dtype=np.uint8)
+        nres = np.zeros(max(len(pairs), 1), dtype=NORM_DTYPE)[:len(pairs)]
+        rc = getattr(load(), fn)(self._h, norm_mode(direction), pairs.ctypes.data, len(pairs), results.ctypes.data, buf.ctypes.data, nbytes,
+                                 nres.ctypes.data)
+        if rc != AWV_OK:
+            raise EngineError(rc, fn)
+        return arena, nres
+
+    def normalize_stats(self):
+        """awv_engine_normalize_stats: kernel_ms, pairs, records_moved, runs, runs_moved, columns_moved, columns of the last
+        normalizing call."""
+        st = NormStats()
+        rc = load().awv_engine_normalize_stats(self._h, C.byref(st))
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_engine_normalize_stats")
+        return st
 
     def clip_cigars(self, scores, match_bonus, results, arena):
         """awv_clip_cigars: clips caller-supplied records (a RESULT_DTYPE array whose cigar_off / cigar_len point into `arena`,
@@ -595,6 +683,19 @@ def verify_one_host(scores, pattern, text, cigar, claimed):
     if rc != AWV_OK:
         raise EngineError(rc, "awv_verify_one_host")
     return out[0]
+
+
+def normalize_one_host(direction, pattern, text, cigar):
+    """awv_normalize_one_host: the normalization contract on the host (needs no device; the yardstick the kernel is tested
+    against).  direction: "left" / "right".  Returns (op bytes, one NORM_DTYPE record); the bytes are the input's on any
+    code but AWV_NM_OK."""
+    pattern, text, cigar = bytes(pattern), bytes(text), bytes(cigar)
+    buf = C.create_string_buffer(max(len(cigar), 1))
+    out = np.zeros(1, dtype=NORM_DTYPE)
+    rc = load().awv_normalize_one_host(norm_mode(direction), pattern, len(pattern), text, len(text), cigar, len(cigar), buf, out.ctypes.data)
+    if rc != AWV_OK:
+        raise EngineError(rc, "awv_normalize_one_host")
+    return buf.raw[:len(cigar)], out[0]
 
 
 def clip_one_host(scores, match_bonus, cigar):

@@ -159,14 +159,28 @@ def _check_split(split, split_min_score, clip):
     return int(split), int(split_min_score)
 
 
-def _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split=None, split_min_score=None):
-    """The bounds, the clipping and the splitting of this thread's next alignment hook, which takes them: every argument is
-    checked before anything is set, and all settings are always written (awh_set_bounds, awh_set_clip, awh_set_split)."""
+def _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split=None, split_min_score=None, normalize=None):
+    """The bounds, the clipping, the splitting and the normalization of this thread's next alignment hook, which takes them:
+    every argument is checked before anything is set, and all settings are always written (awh_set_bounds, awh_set_clip,
+    awh_set_split, awh_set_normalize)."""
     bonus, least = _check_clip(clip, clip_min_score)
     sbonus, sleast = _check_split(split, split_min_score, clip)
+    mode = ffi.norm_mode(normalize)
     _set_bounds(max_penalty, max_divergence)
     load().awh_set_clip(bonus, C.c_int64(least))
     load().awh_set_split(sbonus, C.c_int64(sleast))
+    load().awh_set_normalize(int(mode))
+
+
+def last_normalize():
+    """last_normalize_stats() of this thread's last all_pairs_paf / iterate / all_pairs_paf_count / align_ranges call:
+    dict(pairs, records_moved, runs, runs_moved, columns_moved, columns, kernel_ms), summed over the slots (zeros for a call
+    without normalize)."""
+    out = (C.c_uint64 * 6)()
+    ms = C.c_double(0)
+    load().awh_last_normalize(out, C.byref(ms))
+    return dict(pairs=int(out[0]), records_moved=int(out[1]), runs=int(out[2]), runs_moved=int(out[3]), columns_moved=int(out[4]),
+                columns=int(out[5]), kernel_ms=float(ms.value))
 
 
 def last_split():
@@ -272,7 +286,7 @@ def check_paf(ids, seqs, paf_text, scores, optimal=False, device=0, partial=Fals
 
 
 def align_ranges(ids, seqs, ranges, scores, devices=None, device=0, verify=False, max_penalty=None, max_divergence=None, clip=None,
-                 clip_min_score=None, split=None, split_min_score=None):
+                 clip_min_score=None, split=None, split_min_score=None, normalize=None):
     """allwave::align_ranges + alignment_to_paf: the interval pairs `ranges` -- rows (query_idx, target_idx, is_reverse,
     query_start, query_end, target_start, target_end), the query interval on its forward strand -- aligned globally on the
     engines `devices` names (default: [device]).  Returns the PAF lines in list order: columns 3-4 and 8-9 are the interval,
@@ -287,7 +301,7 @@ def align_ranges(ids, seqs, ranges, scores, devices=None, device=0, verify=False
     n = C.c_size_t(0)
     e = _err()
     rbuf = r if len(r) else np.zeros((1, 7), dtype=np.int64)
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize)
     rc = load().awh_align_ranges_paf(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), scores.encode(),
                                      rbuf.ctypes.data_as(C.c_void_p), C.c_size_t(len(r)), devs, nd, int(bool(verify)), C.byref(out),
                                      C.byref(n), e, _CAP)
@@ -358,7 +372,7 @@ def _device_args(devices):
 
 def all_pairs_paf(ids, seqs, scores, orientation="wfa", exclude_self=True, device=0, sparsification="none", devices=None,
                   min_batch_pairs=0, orientation_full=False, verify=False, max_penalty=None, max_divergence=None, clip=None,
-                  clip_min_score=None, split=None, split_min_score=None):
+                  clip_min_score=None, split=None, split_min_score=None, normalize=None):
     """AllPairIterator + alignment_to_paf per record; returns the list of PAF lines.  `devices`: a list of ordinals (one
     engine per entry, repeats allowed) to spread the pair list over in this call; None = [device].
     `min_batch_pairs` > 0 overrides the smallest batch of a multi-device run (default 16,384).  orientation_full: WFA
@@ -374,13 +388,16 @@ def all_pairs_paf(ids, seqs, scores, orientation="wfa", exclude_self=True, devic
     clip is empty or scores below clip_min_score; last_clip() counts what was left out.
     split (a match bonus) / split_min_score (required with it): every alignment is split into all its maximal segments that
     score at least split_min_score (with_split): each line is replaced by its segments' lines, in column order, or dropped;
-    last_split() counts them.  Not together with clip.  iterate, all_pairs_paf_count and align_ranges take the same two."""
+    last_split() counts them.  Not together with clip.  iterate, all_pairs_paf_count and align_ranges take the same two.
+    normalize ("left" / "right"): every alignment's gap runs are moved to their left- / right-normal place on the device
+    (with_normalize) before the check, the clip and the split; only cg:Z: changes; last_normalize() tells what moved.
+    iterate, all_pairs_paf_count and align_ranges take it too."""
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if devices is None else devices)
     out = C.c_void_p()
     n = C.c_size_t(0)
     e = _err()
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize)
     rc = load().awh_all_pairs_paf_devices(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
                                           scores.encode(), sparsification.encode(), _orient_code(orientation, orientation_full), int(exclude_self),
                                           devs, nd, C.c_int64(int(min_batch_pairs)), int(bool(verify)), None, C.byref(out), C.byref(n), e, _CAP)
@@ -397,7 +414,7 @@ ITER_MODES = {"for_each": 0, "next": 1, "par_for_each": 2, "par_collect": 3, "pr
 def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientation="forward", threads=4, chunk=0,
             resparsify=False, fail_at=-1, device=0, devices=None, min_batch_pairs=0, shard=None, with_stats=False,
             orientation_full=False, verify=False, max_penalty=None, max_divergence=None, clip=None, clip_min_score=None, split=None,
-            split_min_score=None):
+            split_min_score=None, normalize=None):
     """Every consumer of the pair list (iterator.rs:101-253, lib.rs:57-68) through one hook; returns the PAF lines in arrival
     order.  `fail_at` >= 0 makes the callback throw at that record: HostError carries its message.
     `devices`: a list of ordinals (one engine per entry, repeats allowed) to spread the pair list over; None = [device].
@@ -411,7 +428,7 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
     all_pairs_paf -- no consumer is handed a pair above a bound."""
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if devices is None else devices)
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize)
     st = (ffi.Stats * nd)()
     rank, world = shard if shard is not None else (0, 1)
     out = C.c_void_p()
@@ -436,7 +453,7 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
 
 def all_pairs_paf_count(ids, seqs, scores, orientation="forward", device=0, format_threads=8, devices=None, min_batch_pairs=0,
                         sparsification=None, checksum=False, verify=False, max_penalty=None, max_divergence=None, clip=None,
-                        clip_min_score=None, split=None, split_min_score=None):
+                        clip_min_score=None, split=None, split_min_score=None, normalize=None):
     """End to end: upload -> align -> D2H -> format into a counting sink. Returns (bytes, lines, secs, ffi.Stats) for
     every pair on `device`.  `devices`: a list of ordinals (one engine per entry, repeats allowed); the Stats are then
     summed over the slots, and the result gains a fifth element, each slot's Stats (last_slot_stats()), and a sixth, the
@@ -446,7 +463,7 @@ def all_pairs_paf_count(ids, seqs, scores, orientation="forward", device=0, form
     one = devices is None
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if one else devices)
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize)
     nb, nl, secs, ck = C.c_uint64(0), C.c_uint64(0), C.c_double(0), C.c_uint64(0)
     st = ffi.Stats()
     slot = (ffi.Stats * nd)()

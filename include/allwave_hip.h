@@ -79,7 +79,7 @@ typedef struct {
   int32_t device;          /* HIP device ordinal */
   int32_t workgroups;      /* persistent workgroups = pairs in flight (0 = engine default: 16 per CU); the align kernels open
                               workgroups / (waves per workgroup) slots, at least one, and the record kernels (verify, clip,
-                              split) launch min(records, workgroups) one-wave workgroups -- 0: min(records, 16 per CU) */
+                              split, normalize) launch min(records, workgroups) one-wave workgroups -- 0: min(records, 16 per CU) */
   int64_t max_batch_pairs; /* pairs per launch (0 = default) */
   int64_t max_arena_bytes; /* CIGAR arena budget per launch (0 = default 8 GiB) */
   int32_t flags;           /* AWV_F_* */
@@ -517,6 +517,76 @@ int awv_align_ranges_split(awv_engine* e, const awv_penalties* pen, const awv_ra
                            awv_split_index* iout /* required */, awv_clip_result* sout, awv_sink sink, void* user);
 /* The last splitting call (awv_align_*_split / awv_split_cigars) of this engine. */
 int awv_engine_split_stats(const awv_engine* e, awv_split_stats* out);
+
+/* ---- gap runs moved to a canonical place (csrc/normalize.hip, csrc/normalize_device.hpp) ---------------------------------------
+ * Where a gap sits among co-optimal alignments is a tie-break: in a repeat the same indel can lie anywhere along it at the
+ * same penalty.  Normalization moves every gap run as far left as it goes without changing anything else.  It is a pure
+ * function of an op string c[0..n) over M X I D and the two sequences it aligns; no penalties are involved.  'I' consumes the
+ * text, 'D' the pattern; the pattern is the query, or its reverse complement under q_revcomp; bytes compare verbatim; a
+ * range call's pattern and text are its intervals.
+ * One left step: a maximal gap run of type g over columns [c, c + L) consumes bases [p, p + L) of its own sequence (the
+ * pattern for 'D', the text for 'I').  It moves one column left when column c - 1 is 'M', seq[p - 1] == seq[p + L - 1], and
+ * column c - 2 is not also g (a run never comes to rest directly next to a run of its own type): column c - 1 becomes g,
+ * column c + L - 1 becomes 'M' -- still a true match, since seq[p + L - 1] == seq[p - 1] equals the other sequence's base.
+ * The number, order, types and lengths of all runs, the counts and the penalty under any penalties are unchanged: the record
+ * stays valid as it is, only op bytes move.  The left-normal form is the string in which no run can take a step; it is unique.
+ * Closed form: number the gap runs left to right; m_i = the 'M' columns directly before run i in the input; a_i = the largest k
+ * with seq[p_i - j] == seq[p_i + L_i - j] for j = 1..k; run i is linked to run i - 1 when only 'M' columns lie between them.
+ *     s_i = min(a_i, b_i)      b_i = m_i                                              when not linked
+ *                              b_i = m_i + s_(i-1) - (type_i == type_(i-1) ? 1 : 0)   when linked
+ * and the output is the input with columns [c_i - s_i, c_i - s_i + L_i) set to g_i and [c_i - s_i + L_i, c_i + L_i) set to
+ * 'M', for every i (disjoint zones).  The right-normal form is the mirror image:
+ *     right(c, P, T) = reverse(left(reverse(c), reverse(P), reverse(T)))
+ * (a '-' line's query is reverse-complemented: "left in the target's frame" is "right in the query's forward frame").
+ * Checked up front, before any byte of the string is changed; on any code but AWV_NM_OK the string is left untouched.  M / X
+ * truth is not checked: that is the verification's job. */
+#define AWV_NORM_OFF 0
+#define AWV_NORM_LEFT 1
+#define AWV_NORM_RIGHT 2
+#define AWV_NM_OK 0       /* normalized */
+#define AWV_NM_SKIPPED 1  /* status is not AWV_ST_COMPLETED */
+#define AWV_NM_BAD_OP 2   /* a byte outside MXID: columns_moved holds the smallest such column */
+#define AWV_NM_LENGTHS 3  /* the ops do not consume exactly plen and tlen */
+
+typedef struct {
+  int32_t code;          /* AWV_NM_* */
+  int32_t runs_moved;    /* gap runs with s_i > 0 */
+  int64_t columns_moved; /* the sum of s_i (AWV_NM_BAD_OP: the smallest offending column) */
+  int32_t max_shift;     /* the largest s_i */
+  int32_t reserved;
+} awv_norm_result;       /* 24 bytes */
+
+typedef struct {
+  double kernel_ms;        /* HIP-event time of the normalize launches of the last normalizing call */
+  uint64_t pairs;          /* records handed to the step (skipped ones included) */
+  uint64_t records_moved;  /* of them: at least one run moved */
+  uint64_t runs;           /* gap runs of the records normalized */
+  uint64_t runs_moved;
+  uint64_t columns_moved;  /* the sum of all s_i */
+  uint64_t columns;        /* op bytes of the records not skipped */
+} awv_norm_stats;
+
+/* The contract alone, on the host (needs no device): a serial walk, the yardstick the kernel is tested against, not a
+ * fallback -- no product path calls it.  direction: AWV_NORM_LEFT / AWV_NORM_RIGHT.  out_cigar: n bytes, may be `cigar`. */
+int awv_normalize_one_host(int32_t direction, const uint8_t* pattern, int32_t plen, const uint8_t* text, int32_t tlen,
+                           const uint8_t* cigar, int64_t n, uint8_t* out_cigar, awv_norm_result* out);
+/* Normalizes records and op bytes the caller supplies, in place, against the resident sequence set: results[i] claims that
+ * cigar_arena[results[i].cigar_off, + cigar_len) aligns pairs[i] (ranges[i]).  The arena goes up and back in pieces of at most
+ * max_arena_bytes; the op strings of two records must not overlap.  A completed record whose op bytes lie outside the arena:
+ * AWV_ERR_ARG before anything is launched. */
+int awv_normalize_cigars(awv_engine* e, int32_t direction, const awv_pair* pairs, int64_t n, const awv_result* results,
+                         uint8_t* cigar_arena /* in/out */, uint64_t arena_bytes, awv_norm_result* nout /* required */);
+int awv_normalize_ranges(awv_engine* e, int32_t direction, const awv_range_pair* ranges, int64_t n, const awv_result* results,
+                         uint8_t* cigar_arena /* in/out */, uint64_t arena_bytes, awv_norm_result* nout /* required */);
+/* The engine's mode (AWV_NORM_OFF by default), read at the start of every aligning call: awv_align_pairs, awv_align_ranges,
+ * their _verified, _bounded, _clipped and _split forms, and awv_align_one.  When it is on, every batch's finished pairs are
+ * normalized in the batch's arena on the device, on the engine's stream (pairs re-run after AWV_ST_CAPACITY included; also
+ * under AWV_F_KEEP_ON_DEVICE), BEFORE the optional check, clip and split and before the copy back: vout, cout and the
+ * segments describe the normalized string.  Records are byte-identical to the unnormalized call's.  When it is off there is
+ * no launch, no allocation and no change.  Score-only and orientation calls ignore the mode. */
+int awv_engine_set_normalize(awv_engine* e, int32_t mode);
+/* The last normalizing call (an aligning call under a mode, awv_normalize_cigars / _ranges) of this engine. */
+int awv_engine_normalize_stats(const awv_engine* e, awv_norm_stats* out);
 
 /* ---- device pair planning (csrc/planner.hip) -------------------------------------------------------------------------
  * Integer work over the engine's resident sequence set, on its device and stream; results equal the host planner's
