@@ -23,18 +23,13 @@
 
 #include <algorithm>
 #include <climits>
-#include <cstring>
 #include <new>
-#include <numeric>
 #include <string>
 #include <vector>
 
-#include "planner_device.hpp"  // EngineView, awv_internal_fail
-#include "wave_ops.hpp"
+#include "record_pass.hpp"  // the host skeleton of a record pass: RecordPass, pack_piece, AWV_TRY
 
 namespace awvc {
-
-constexpr int WAVES_PER_CU = 16;  // persistent one-wave workgroups per CU: a chunk's walks depend on its scans, other waves fill the wait
 
 struct KParams {
   const awv_result* results;  // cigar_off relative to `arena`
@@ -52,14 +47,7 @@ __global__ __launch_bounds__(64) void awv_clip_kernel(KParams kp) {
   const long long a = kp.match_bonus;
   unsigned long long n_empty = 0, n_columns = 0;  // (uniform)
   for (;;) {
-    unsigned slot_lo = 0, slot_hi = 0;
-    if (lane == 0) {
-      const unsigned long long s = atomicAdd(&kp.counters[0], 1ull);
-      slot_lo = (unsigned)s;
-      slot_hi = (unsigned)(s >> 32);
-    }
-    const unsigned long long slot = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)slot_lo) |
-                                    ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)slot_hi) << 32);
+    const unsigned long long slot = awvw::take_record(kp.counters, lane);
     if (slot >= (unsigned long long)kp.npairs) break;
     const int pair = __builtin_amdgcn_readfirstlane(kp.order[slot]);
     const awv_result rec = kp.results[pair];
@@ -87,24 +75,12 @@ __global__ __launch_bounds__(64) void awv_clip_kernel(KParams kp) {
 
 using awvw::Buf;
 
-struct State {
-  Buf<awv_result> d_results;
-  Buf<int32_t> d_order;
+struct State : awvw::RecordPass {
   Buf<awv_clip_result> d_out;
-  Buf<unsigned long long> d_counters;
-  Buf<uint8_t> d_arena;  // awv_clip_cigars: the caller's op bytes
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int num_cus = 0;
   awv_clip_stats stats{};
   void release() {
-    d_results.release();
-    d_order.release();
+    RecordPass::release();
     d_out.release();
-    d_counters.release();
-    d_arena.release();
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    ev0 = ev1 = nullptr;
   }
 };
 
@@ -120,25 +96,6 @@ void stats_reset(State* s) {
 
 namespace {
 
-#define CL_TRY(expr)                                                                                              \
-  do {                                                                                                            \
-    hipError_t _e = (expr);                                                                                       \
-    if (_e != hipSuccess)                                                                                         \
-      return awv_internal_fail(_e == hipErrorOutOfMemory ? AWV_ERR_OOM : AWV_ERR_HIP,                             \
-                               std::string(#expr) + ": " + hipGetErrorString(_e));                                \
-  } while (0)
-
-#define CL_GUARDED(body)                                                                                          \
-  try {                                                                                                           \
-    body                                                                                                          \
-  } catch (const std::bad_alloc&) {                                                                               \
-    return awv_internal_fail(AWV_ERR_OOM, "host memory exhausted");                                               \
-  } catch (const std::exception& ex) {                                                                            \
-    return awv_internal_fail(AWV_ERR_HIP, std::string("internal error: ") + ex.what());                           \
-  } catch (...) {                                                                                                 \
-    return awv_internal_fail(AWV_ERR_HIP, "internal error: unknown exception");                                   \
-  }
-
 // the engine's sign rules for penalties (re-scoring has no ring to fit, so any size goes), the unused piece of a gap-affine
 // set cleared, and the bonus in range
 int check_args(const awv_penalties* p, int32_t match_bonus, awv_penalties& out) {
@@ -152,44 +109,19 @@ int check_args(const awv_penalties* p, int32_t match_bonus, awv_penalties& out) 
 }
 
 int open_state(awv_engine* e, awp::EngineView& v, State*& st) {
-  awv_internal_device_view(e, &v);  // (the clip reads no sequence: an engine without a set will do, and is no error)
-  CL_TRY(hipSetDevice(v.device));
   State*& slot = awv_internal_clip(e);
   if (!slot) slot = new State();
   st = slot;
-  if (!st->ev0) CL_TRY(hipEventCreate(&st->ev0));
-  if (!st->ev1) CL_TRY(hipEventCreate(&st->ev1));
-  if (st->num_cus == 0) {
-    int cus = 0;
-    CL_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, v.device));
-    st->num_cus = std::max(cus, 1);
-  }
-  return AWV_OK;
+  return st->open(e, v, false);  // (the clip reads no sequence: an engine without a set will do, and is no error)
 }
 
-bool outside(const awv_result& r, uint64_t arena_bytes) {
-  return r.status == AWV_ST_COMPLETED && (r.cigar_off > arena_bytes || (uint64_t)r.cigar_len > arena_bytes - r.cigar_off);
-}
-
-// One launch over n records whose op bytes are on the device already.  Every op string's place in the arena is checked
-// here, on the host: the kernel reads what the records say.
+// One launch over n records whose op bytes are on the device already.
 int launch(const awp::EngineView& v, State* st, const awv_penalties& pen, int32_t match_bonus, int64_t n, const awv_result* results,
            const uint8_t* d_arena, uint64_t arena_bytes, awv_clip_result* cout) {
   if (n == 0) return AWV_OK;
-  if (n > INT32_MAX) return awv_internal_fail(AWV_ERR_ARG, "clip: more than 2^31 - 1 records in one launch");
-  for (int64_t i = 0; i < n; ++i)
-    if (outside(results[i], arena_bytes)) return awv_internal_fail(AWV_ERR_ARG, "clip: a record's op bytes lie outside the CIGAR arena");
-  std::vector<int32_t> order((size_t)n);
-  std::iota(order.begin(), order.end(), 0);
-  auto cols = [&](int32_t i) { return results[i].status == AWV_ST_COMPLETED ? results[i].cigar_len : 0u; };
-  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return cols(a) > cols(b); });
-  CL_TRY(st->d_results.reserve((size_t)n));
-  CL_TRY(st->d_order.reserve((size_t)n));
-  CL_TRY(st->d_out.reserve((size_t)n));
-  CL_TRY(st->d_counters.reserve(4));
-  CL_TRY(hipMemcpyAsync(st->d_results.p, results, (size_t)n * sizeof(awv_result), hipMemcpyHostToDevice, v.stream));
-  CL_TRY(hipMemcpyAsync(st->d_order.p, order.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-  CL_TRY(hipMemsetAsync(st->d_counters.p, 0, 4 * sizeof(unsigned long long), v.stream));
+  if (int rc = st->begin(v, "clip", n, results, arena_bytes)) return rc;
+  AWV_TRY(st->d_out.reserve((size_t)n));
+  if (int rc = st->clear_counters(v, 4)) return rc;
   KParams kp{};
   kp.results = st->d_results.p;
   kp.order = st->d_order.p;
@@ -199,17 +131,13 @@ int launch(const awp::EngineView& v, State* st, const awv_penalties& pen, int32_
   kp.npairs = n;
   kp.pen = pen;
   kp.match_bonus = match_bonus;
-  const unsigned grid = (unsigned)std::min<int64_t>(n, v.workgroups > 0 ? (int64_t)v.workgroups : (int64_t)st->num_cus * WAVES_PER_CU);
-  CL_TRY(hipEventRecord(st->ev0, v.stream));
-  hipLaunchKernelGGL(awv_clip_kernel, dim3(grid), dim3(64), 0, v.stream, kp);
-  CL_TRY(hipGetLastError());
-  CL_TRY(hipEventRecord(st->ev1, v.stream));
+  if (int rc = st->start(v)) return rc;
+  hipLaunchKernelGGL(awv_clip_kernel, dim3(st->grid(v, n)), dim3(64), 0, v.stream, kp);
+  if (int rc = st->stop(v)) return rc;
   unsigned long long hc[4] = {0, 0, 0, 0};
-  CL_TRY(hipMemcpyAsync(cout, st->d_out.p, (size_t)n * sizeof(awv_clip_result), hipMemcpyDeviceToHost, v.stream));
-  CL_TRY(hipMemcpyAsync(hc, st->d_counters.p, sizeof(hc), hipMemcpyDeviceToHost, v.stream));
-  CL_TRY(hipStreamSynchronize(v.stream));
   float ms = 0;
-  CL_TRY(hipEventElapsedTime(&ms, st->ev0, st->ev1));
+  AWV_TRY(hipMemcpyAsync(cout, st->d_out.p, (size_t)n * sizeof(awv_clip_result), hipMemcpyDeviceToHost, v.stream));
+  if (int rc = st->finish(v, hc, 4, ms)) return rc;
   st->stats.kernel_ms += ms;
   st->stats.pairs += (uint64_t)n;
   st->stats.empty += hc[1];
@@ -227,44 +155,18 @@ int clip_cigars_core(awv_engine* e, const awv_penalties* pen_in, int32_t match_b
   st->stats = awv_clip_stats{};
   // before anything goes up: every completed record's op bytes lie inside the caller's arena
   for (int64_t i = 0; i < n_all; ++i)
-    if (outside(results[i], arena_bytes)) return awv_internal_fail(AWV_ERR_ARG, "clip_cigars: a record's op bytes lie outside the CIGAR arena");
-  // pieces of at most max_arena op bytes (one record alone may exceed it) and 2^20 records: the op bytes of a piece are
-  // packed into 16-byte slots of a staging buffer that keep every string's offset modulo 16 (the kernel's addressing is
-  // part of what a caller may want to exercise), so records may share, overlap or leave out parts of the caller's arena
+    if (awvw::outside(results[i], arena_bytes)) return awv_internal_fail(AWV_ERR_ARG, "clip_cigars: a record's op bytes lie outside the CIGAR arena");
+  // in pieces (record_pieces.hpp) that keep every string's offset modulo 16
   std::vector<uint8_t> stage;
   std::vector<awv_result> recs;
   for (int64_t first = 0; first < n_all;) {
-    int64_t n = 0;
-    uint64_t bytes = 0;
-    recs.clear();
-    while (first + n < n_all && n < ((int64_t)1 << 20)) {
-      const awv_result& r = results[first + n];
-      const uint64_t sh = r.cigar_off & 15;
-      const uint64_t need = r.status == AWV_ST_COMPLETED ? (sh + (uint64_t)r.cigar_len + 15) & ~(uint64_t)15 : 0;
-      if (n > 0 && bytes + need > max_arena) break;
-      recs.push_back(r);
-      recs.back().cigar_off = bytes + sh;
-      bytes += need;
-      ++n;
-    }
-    stage.assign((size_t)bytes, 0);
-    for (int64_t i = 0; i < n; ++i) {
-      const awv_result& r = results[first + i];
-      if (r.status == AWV_ST_COMPLETED && r.cigar_len) std::memcpy(stage.data() + recs[(size_t)i].cigar_off, cigar_arena + r.cigar_off, r.cigar_len);
-    }
-    CL_TRY(st->d_arena.reserve((size_t)bytes + 64));
-    if (bytes) CL_TRY(hipMemcpyAsync(st->d_arena.p, stage.data(), (size_t)bytes, hipMemcpyHostToDevice, v.stream));
-    if (int rc = launch(v, st, pen, match_bonus, n, recs.data(), st->d_arena.p, bytes, cout + first)) return rc;
-    first += n;
+    const awvw::Piece pc = awvw::pack_piece(results, n_all, first, cigar_arena, max_arena, true, recs, stage);
+    AWV_TRY(st->d_arena.reserve((size_t)pc.bytes + 64));
+    if (pc.bytes) AWV_TRY(hipMemcpyAsync(st->d_arena.p, stage.data(), (size_t)pc.bytes, hipMemcpyHostToDevice, v.stream));
+    if (int rc = launch(v, st, pen, match_bonus, pc.n, recs.data(), st->d_arena.p, pc.bytes, cout + first)) return rc;
+    first += pc.n;
   }
   return AWV_OK;
-}
-
-int null_engine() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return awv_internal_fail(AWV_ERR_NO_DEVICE, "no HIP device available: liballwave_hip has no CPU fallback");
-  return awv_internal_fail(AWV_ERR_ARG, "null engine");
 }
 
 }  // namespace
@@ -285,10 +187,10 @@ extern "C" {
 
 int awv_clip_cigars(awv_engine* e, const awv_penalties* pen, int32_t match_bonus, const awv_result* results, int64_t n,
                     const uint8_t* cigar_arena, uint64_t arena_bytes, awv_clip_result* cout) {
-  if (!e) return awvc::null_engine();
+  if (!e) return awv_internal_null_engine();
   if (n < 0 || (n > 0 && (!results || !cout))) return awv_internal_fail(AWV_ERR_ARG, "clip_cigars: null argument");
   if (arena_bytes > 0 && !cigar_arena) return awv_internal_fail(AWV_ERR_ARG, "clip_cigars: null arena");
-  CL_GUARDED(return awvc::clip_cigars_core(e, pen, match_bonus, results, n, cigar_arena, arena_bytes, awv_internal_max_arena(e), cout);)
+  AWV_GUARDED(return awvc::clip_cigars_core(e, pen, match_bonus, results, n, cigar_arena, arena_bytes, awv_internal_max_arena(e), cout);)
 }
 
 int awv_clip_one_host(const awv_penalties* pen, int32_t match_bonus, const uint8_t* cigar, int64_t n, awv_clip_result* out) {

@@ -101,12 +101,5 @@ int clip_batch(awv_engine* e, const awv_penalties* pen, int32_t match_bonus, int
 
 }  // namespace awvc
 
-namespace awp {
-struct EngineView;  // planner_device.hpp
-}
-
 // engine.hip
 awvc::State*& awv_internal_clip(awv_engine* e);
-// awv_internal_view (planner_device.hpp) for a caller that needs the device and the stream only: an engine without a
-// sequence set is no failure (the view then names no sequences) and awv_last_error() is left alone
-void awv_internal_device_view(awv_engine* e, awp::EngineView* v);

@@ -10,14 +10,12 @@
 
 namespace awvc {
 
-constexpr int LANE_BYTES = 16;
-constexpr int CHUNK = 64 * LANE_BYTES;
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-using awvw::byte_range_mask;  // (wave_ops.hpp: the scans and the byte counting shared with verify.hip)
+using awvw::byte_range_mask;  // (wave_ops.hpp: the chunk, the scans and the byte counting shared with verify.hip)
+using awvw::CHUNK;
 using awvw::count_bytes;
 using awvw::from_lower_lane;
+using awvw::LANE_BYTES;
+using awvw::u32x4;
 using awvw::wave_scan_add;
 using awvw::wave_scan_max;
 using awvw::wave_scan_min;

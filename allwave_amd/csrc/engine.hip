@@ -5,6 +5,7 @@
 // wavefront arenas sized for 288 GB of HBM, result/CIGAR arenas, one stream.  There is no CPU
 // fallback: without a HIP device every entry point fails with AWV_ERR_NO_DEVICE.
 #include "allwave_hip.h"
+#include "host_errors.hpp"      // (AWV_TRY, AWV_GUARDED: the error plumbing every unit behind the C ABI shares)
 // the device code, once per workgroup size: awv:: one wave per pair (throughput), awvw:: four waves per pair,
 // awvx:: sixteen waves per pair (one pair per CU: the few pairs a large length difference makes enormous)
 #include "planner_device.hpp"  // (the sketches and scratch of device pair planning, planner.hip)
@@ -69,14 +70,7 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess)                                                                      \
-      return fail(_e == hipErrorOutOfMemory ? AWV_ERR_OOM : AWV_ERR_HIP,                       \
-                  std::string(#expr) + ": " + hipGetErrorString(_e));                          \
-  } while (0)
-
+// deliberately not awvw::Buf (wave_ops.hpp): growth slack, a second attempt without it, and an AWV_* code with its own message
 template <typename T>
 struct DevBuf {
   T* p = nullptr;
@@ -237,24 +231,24 @@ int upload_seqset(awv_engine* e, SeqSet& s, int32_t n, const uint8_t* bytes, con
       if (ok) ok2[i] |= (uint8_t)(1 << v);
     }
   }
-  HIP_TRY(hipSetDevice(e->device));
+  AWV_TRY(hipSetDevice(e->device));
   for (int v = 0; v < 2; ++v) {
     if (int rc = s.d_seq2[v].reserve(h2[v].size())) return rc;
-    HIP_TRY(hipMemcpyAsync(s.d_seq2[v].p, h2[v].data(), h2[v].size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    AWV_TRY(hipMemcpyAsync(s.d_seq2[v].p, h2[v].data(), h2[v].size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
   }
   if (int rc = s.d_off2.reserve((size_t)n + 1)) return rc;
   if (int rc = s.d_ok2.reserve(ok2.size())) return rc;
-  HIP_TRY(hipMemcpyAsync(s.d_off2.p, off2.data(), ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(s.d_ok2.p, ok2.data(), ok2.size(), hipMemcpyHostToDevice, e->stream));
+  AWV_TRY(hipMemcpyAsync(s.d_off2.p, off2.data(), ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
+  AWV_TRY(hipMemcpyAsync(s.d_ok2.p, ok2.data(), ok2.size(), hipMemcpyHostToDevice, e->stream));
   for (int v = 0; v < 4; ++v) {
     if (int rc = s.d_seq[v].reserve(s.total)) return rc;
-    HIP_TRY(hipMemcpyAsync(s.d_seq[v].p, h[v].data(), s.total, hipMemcpyHostToDevice, e->stream));
+    AWV_TRY(hipMemcpyAsync(s.d_seq[v].p, h[v].data(), s.total, hipMemcpyHostToDevice, e->stream));
   }
   if (int rc = s.d_off.reserve((size_t)n + 1)) return rc;
   if (int rc = s.d_len.reserve((size_t)std::max(n, 1))) return rc;
-  HIP_TRY(hipMemcpyAsync(s.d_off.p, s.off.data(), ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
-  if (n > 0) HIP_TRY(hipMemcpyAsync(s.d_len.p, s.len.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
+  AWV_TRY(hipMemcpyAsync(s.d_off.p, s.off.data(), ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
+  if (n > 0) AWV_TRY(hipMemcpyAsync(s.d_len.p, s.len.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+  AWV_TRY(hipStreamSynchronize(e->stream));
   s.n = n;
   return AWV_OK;
 }
@@ -358,7 +352,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
   if (npairs < 0 || (npairs > 0 && !pairs)) return fail(AWV_ERR_ARG, "align_pairs: null pairs");
   DevPenalties dp{};
   if (int rc = check_penalties(pen, dp)) return rc;
-  HIP_TRY(hipSetDevice(e->device));
+  AWV_TRY(hipSetDevice(e->device));
   e->stats = awv_stats{};
   for (uint64_t& v : e->twin_stats) v = 0;
   const int32_t norm = score_only ? AWV_NORM_OFF : e->norm_mode;  // (off: no launch, no allocation, nothing below changes)
@@ -676,22 +670,22 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       lap("arenas reserved");
       if (timing) fprintf(stderr, "[awv] ring arena %p (%zu MiB), hist %p, cigar %p\n", (void*)e->ring_mem.p, e->ring_mem.bytes() >> 20, (void*)e->hist_mem.p, (void*)e->d_cigar.p);
       // ---- H2D
-      HIP_TRY(hipEventRecord(e->ev0, e->stream));
-      HIP_TRY(hipMemcpyAsync(e->d_pair_q.p, hq.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-      HIP_TRY(hipMemcpyAsync(e->d_pair_t.p, ht.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-      HIP_TRY(hipMemcpyAsync(e->d_pair_rc.p, hrc.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-      HIP_TRY(hipMemcpyAsync(e->d_cigar_off.p, hoff.data(), (size_t)m * 8, hipMemcpyHostToDevice, e->stream));
+      AWV_TRY(hipEventRecord(e->ev0, e->stream));
+      AWV_TRY(hipMemcpyAsync(e->d_pair_q.p, hq.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
+      AWV_TRY(hipMemcpyAsync(e->d_pair_t.p, ht.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
+      AWV_TRY(hipMemcpyAsync(e->d_pair_rc.p, hrc.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
+      AWV_TRY(hipMemcpyAsync(e->d_cigar_off.p, hoff.data(), (size_t)m * 8, hipMemcpyHostToDevice, e->stream));
       if (pair_bound) {  // (amap: dispatch index -> batch index, kept through the sort, the groups and the re-runs)
         hbound.resize((size_t)m);
         for (int64_t i = 0; i < m; ++i) hbound[(size_t)i] = pair_bound[first + amap[(size_t)i]];
         if (int rc = e->d_pair_bound.reserve((size_t)m)) return rc;
-        HIP_TRY(hipMemcpyAsync(e->d_pair_bound.p, hbound.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
+        AWV_TRY(hipMemcpyAsync(e->d_pair_bound.p, hbound.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
       }
       if (spans) {
         hspan.resize((size_t)m);
         for (int64_t i = 0; i < m; ++i) hspan[(size_t)i] = spans[first + amap[(size_t)i]];
         if (int rc = e->d_pair_span.reserve((size_t)m)) return rc;
-        HIP_TRY(hipMemcpyAsync(e->d_pair_span.p, hspan.data(), (size_t)m * sizeof(awvr::Span), hipMemcpyHostToDevice, e->stream));
+        AWV_TRY(hipMemcpyAsync(e->d_pair_span.p, hspan.data(), (size_t)m * sizeof(awvr::Span), hipMemcpyHostToDevice, e->stream));
       }
       // ---- twin units: an entry (q, t) and its swapped entry (t, q) of this launch share their breakpoint searches (DESIGN.md
       // 4.20).  Entries are in descending cost order and a twin costs what its partner costs, so units ordered by their
@@ -717,13 +711,13 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
         nunits = (int64_t)uo.size();
         if (int rc = e->d_unit_first.reserve((size_t)nunits)) return rc;
         if (int rc = e->d_unit_twin.reserve((size_t)nunits)) return rc;
-        HIP_TRY(hipMemcpyAsync(e->d_unit_first.p, hufirst.data(), (size_t)nunits * 4, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(e->d_unit_twin.p, hutwin.data(), (size_t)nunits * 4, hipMemcpyHostToDevice, e->stream));
+        AWV_TRY(hipMemcpyAsync(e->d_unit_first.p, hufirst.data(), (size_t)nunits * 4, hipMemcpyHostToDevice, e->stream));
+        AWV_TRY(hipMemcpyAsync(e->d_unit_twin.p, hutwin.data(), (size_t)nunits * 4, hipMemcpyHostToDevice, e->stream));
       }
-      HIP_TRY(hipMemsetAsync(e->d_counters.p, 0, (1 + STAT_N_DEV) * sizeof(unsigned long long), e->stream));
-      HIP_TRY(hipEventRecord(e->ev1, e->stream));
-      HIP_TRY(hipEventSynchronize(e->ev1));
-      HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+      AWV_TRY(hipMemsetAsync(e->d_counters.p, 0, (1 + STAT_N_DEV) * sizeof(unsigned long long), e->stream));
+      AWV_TRY(hipEventRecord(e->ev1, e->stream));
+      AWV_TRY(hipEventSynchronize(e->ev1));
+      AWV_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
       h2d_ms += ms;
       // ---- launch
       KParams kp{};
@@ -773,14 +767,14 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       kp.pair_max_penalty = pair_bound ? e->d_pair_bound.p : nullptr;
       const awvr::Span* const d_span = spans ? e->d_pair_span.p : nullptr;  // (range launches: the kernels' two-argument instantiations)
       const bool ranged = spans != nullptr;
-      HIP_TRY(hipEventRecord(e->ev0, e->stream));
+      AWV_TRY(hipEventRecord(e->ev0, e->stream));
       auto launch = [&](auto kern, const auto& kparams) -> int {
-        HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
+        AWV_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
         hipLaunchKernelGGL(kern, dim3(nslots), dim3(wg), dyn_lds, e->stream, kparams);
         return AWV_OK;
       };
       auto launch_ranges = [&](auto kern, const auto& kparams) -> int {
-        HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
+        AWV_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
         hipLaunchKernelGGL(kern, dim3(nslots), dim3(wg), dyn_lds, e->stream, kparams, d_span);
         return AWV_OK;
       };
@@ -788,7 +782,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
       static_assert(sizeof(awvw::KParams) == sizeof(awv::KParams) && sizeof(awvx::KParams) == sizeof(awv::KParams),
                     "same parameter block for every workgroup size");
       if (waves == 1) {
-        HIP_TRY((hipError_t)awv_launch_one_wave(dp.two_piece, narrow ? 1 : 0, d_span, (unsigned)nslots, dyn_lds, e->stream, &kp));
+        AWV_TRY((hipError_t)awv_launch_one_wave(dp.two_piece, narrow ? 1 : 0, d_span, (unsigned)nslots, dyn_lds, e->stream, &kp));
         lrc = AWV_OK;
       } else if (wide_meta) {
         static_assert(sizeof(awvw_m::KParams) == sizeof(awv::KParams) && sizeof(awvx_m::KParams) == sizeof(awv::KParams), "same parameter block");
@@ -813,24 +807,24 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
         else lrc = narrow ? (ranged ? launch_ranges(awvx::biwfa_align_kernel<false, int16_t, const awvr::Span*>, kx) : launch(awvx::biwfa_align_kernel<false, int16_t>, kx)) : (ranged ? launch_ranges(awvx::biwfa_align_kernel<false, int32_t, const awvr::Span*>, kx) : launch(awvx::biwfa_align_kernel<false, int32_t>, kx));
       }
       if (lrc != AWV_OK) return lrc;
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipEventRecord(e->ev1, e->stream));
+      AWV_TRY(hipGetLastError());
+      AWV_TRY(hipEventRecord(e->ev1, e->stream));
       // while the kernel runs: get the host CIGAR buffer's pages in place (0.2 s for config 2's 670 MB)
       if (sink && !score_only && !(e->cfg.flags & AWV_F_KEEP_ON_DEVICE) && e->h_cigar.size() < (size_t)arena + 64) e->h_cigar.resize((size_t)arena + 64);
-      HIP_TRY(hipEventSynchronize(e->ev1));
-      HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+      AWV_TRY(hipEventSynchronize(e->ev1));
+      AWV_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
       kernel_ms += ms;
       ++launches;
       lap("kernel done");
       // ---- D2H (results + counters)
       tres.resize((size_t)m);
-      HIP_TRY(hipEventRecord(e->ev0, e->stream));
-      HIP_TRY(hipMemcpyAsync(tres.data(), e->d_results.p, (size_t)m * sizeof(awv_result), hipMemcpyDeviceToHost, e->stream));
+      AWV_TRY(hipEventRecord(e->ev0, e->stream));
+      AWV_TRY(hipMemcpyAsync(tres.data(), e->d_results.p, (size_t)m * sizeof(awv_result), hipMemcpyDeviceToHost, e->stream));
       unsigned long long hstat[1 + STAT_N_DEV];
-      HIP_TRY(hipMemcpyAsync(hstat, e->d_counters.p, sizeof(hstat), hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipEventRecord(e->ev1, e->stream));
-      HIP_TRY(hipEventSynchronize(e->ev1));
-      HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+      AWV_TRY(hipMemcpyAsync(hstat, e->d_counters.p, sizeof(hstat), hipMemcpyDeviceToHost, e->stream));
+      AWV_TRY(hipEventRecord(e->ev1, e->stream));
+      AWV_TRY(hipEventSynchronize(e->ev1));
+      AWV_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
       d2h_ms += ms;
       for (int i = 0; i < STAT_N_DEV; ++i) stat_tot[i] += hstat[1 + i];
       // ---- scatter; collect the pairs to re-run with wider rows
@@ -976,12 +970,12 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
     if (want_cigar) {
       e->h_cigar.resize((size_t)arena + 64);
       lap("host cigar buffer");
-      HIP_TRY(hipEventRecord(e->ev0, e->stream));
-      HIP_TRY(hipMemcpyAsync(e->h_cigar.data(), e->d_cigar.p, (size_t)arena, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipEventRecord(e->ev1, e->stream));
-      HIP_TRY(hipEventSynchronize(e->ev1));
+      AWV_TRY(hipEventRecord(e->ev0, e->stream));
+      AWV_TRY(hipMemcpyAsync(e->h_cigar.data(), e->d_cigar.p, (size_t)arena, hipMemcpyDeviceToHost, e->stream));
+      AWV_TRY(hipEventRecord(e->ev1, e->stream));
+      AWV_TRY(hipEventSynchronize(e->ev1));
       float ms_c = 0;
-      HIP_TRY(hipEventElapsedTime(&ms_c, e->ev0, e->ev1));
+      AWV_TRY(hipEventElapsedTime(&ms_c, e->ev0, e->ev1));
       d2h_ms += ms_c;
     }
     lap("cigars on host");
@@ -1113,19 +1107,6 @@ void awv_engine_destroy(awv_engine* e) {
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
-
-// Nothing C++ may cross the C boundary: a std::bad_alloc / std::length_error out of a host-side container (a caller that hands
-// over billions of pairs, a box short of memory) would otherwise reach the foreign caller as std::terminate -> abort().
-#define AWV_GUARDED(body)                                                                                         \
-  try {                                                                                                           \
-    body                                                                                                          \
-  } catch (const std::bad_alloc&) {                                                                               \
-    return fail(AWV_ERR_OOM, "host memory exhausted");                                                            \
-  } catch (const std::exception& ex) {                                                                            \
-    return fail(AWV_ERR_HIP, std::string("internal error: ") + ex.what());                                        \
-  } catch (...) {                                                                                                 \
-    return fail(AWV_ERR_HIP, "internal error: unknown exception");                                                \
-  }
 
 int awv_engine_set_sequences(awv_engine* e, int32_t n, const uint8_t* concat_bytes, const uint64_t* offsets) {
   if (!e) return fail(AWV_ERR_ARG, "null engine");

@@ -28,18 +28,12 @@
 #include <climits>
 #include <cstring>
 #include <new>
-#include <numeric>
 #include <string>
 #include <vector>
 
-#include "planner_device.hpp"  // EngineView, awv_internal_view, awv_internal_fail
-#include "wave_ops.hpp"
+#include "record_pass.hpp"  // the host skeleton of a record pass: RecordPass, pack_piece, scatter_back, AWV_TRY
 
 namespace awvn {
-
-constexpr int LANE_BYTES = 16;
-constexpr int CHUNK = 64 * LANE_BYTES;
-constexpr int WAVES_PER_CU = 16;  // persistent one-wave workgroups per CU, as for verify and clip
 
 struct KParams {
   const uint8_t* fwd;
@@ -57,13 +51,15 @@ struct KParams {
   int mirror;                 // 0: left, 1: right
 };
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 using awvw::byte_range_mask;
+using awvw::CHUNK;
 using awvw::count_bytes;
 using awvw::from_lower_lane;
+using awvw::LANE_BYTES;
+using awvw::u32x4;
 using awvw::wave_scan_add;
 using awvw::wave_scan_max;
+using awvw::wave_sum_i64;
 
 __device__ __forceinline__ unsigned byte_at(const u32x4& w, int j) {  // byte j of a lane's 16, j in a register
   const int k = j >> 2;
@@ -71,25 +67,12 @@ __device__ __forceinline__ unsigned byte_at(const u32x4& w, int j) {  // byte j 
   return (d >> (8 * (j & 3))) & 0xffu;
 }
 
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(64) void awv_normalize_kernel(KParams kp) {
   const int lane = threadIdx.x;
   const bool mirror = kp.mirror != 0;
   unsigned long long t_records = 0, t_runs = 0, t_runs_moved = 0, t_cols_moved = 0, t_columns = 0;  // (uniform)
   for (;;) {
-    unsigned slot_lo = 0, slot_hi = 0;
-    if (lane == 0) {
-      const unsigned long long s = atomicAdd(&kp.counters[0], 1ull);
-      slot_lo = (unsigned)s;
-      slot_hi = (unsigned)(s >> 32);
-    }
-    const unsigned long long slot = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)slot_lo) |
-                                    ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)slot_hi) << 32);
+    const unsigned long long slot = awvw::take_record(kp.counters, lane);
     if (slot >= (unsigned long long)kp.npairs) break;
     const int pair = __builtin_amdgcn_readfirstlane(kp.order[slot]);
     const awv_result rec = kp.results[pair];
@@ -344,29 +327,17 @@ __global__ __launch_bounds__(64) void awv_normalize_kernel(KParams kp) {
 
 using awvw::Buf;
 
-struct State {
+struct State : awvw::RecordPass {
   Buf<awv_pair> d_pairs;
   Buf<Span> d_spans;
-  Buf<awv_result> d_results;
-  Buf<int32_t> d_order;
   Buf<awv_norm_result> d_out;
-  Buf<unsigned long long> d_counters;
-  Buf<uint8_t> d_arena;  // awv_normalize_cigars: the caller's op bytes
   std::vector<awv_norm_result> h_out;  // a batch's records, which an aligning call does not hand out
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int num_cus = 0;
   awv_norm_stats stats{};
   void release() {
+    RecordPass::release();
     d_pairs.release();
     d_spans.release();
-    d_results.release();
-    d_order.release();
     d_out.release();
-    d_counters.release();
-    d_arena.release();
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    ev0 = ev1 = nullptr;
   }
 };
 
@@ -382,25 +353,6 @@ void stats_reset(State* s) {
 
 namespace {
 
-#define NM_TRY(expr)                                                                                              \
-  do {                                                                                                            \
-    hipError_t _e = (expr);                                                                                       \
-    if (_e != hipSuccess)                                                                                         \
-      return awv_internal_fail(_e == hipErrorOutOfMemory ? AWV_ERR_OOM : AWV_ERR_HIP,                             \
-                               std::string(#expr) + ": " + hipGetErrorString(_e));                                \
-  } while (0)
-
-#define NM_GUARDED(body)                                                                                          \
-  try {                                                                                                           \
-    body                                                                                                          \
-  } catch (const std::bad_alloc&) {                                                                               \
-    return awv_internal_fail(AWV_ERR_OOM, "host memory exhausted");                                               \
-  } catch (const std::exception& ex) {                                                                            \
-    return awv_internal_fail(AWV_ERR_HIP, std::string("internal error: ") + ex.what());                           \
-  } catch (...) {                                                                                                 \
-    return awv_internal_fail(AWV_ERR_HIP, "internal error: unknown exception");                                   \
-  }
-
 int check_direction(int32_t direction) {
   if (direction != AWV_NORM_LEFT && direction != AWV_NORM_RIGHT)
     return awv_internal_fail(AWV_ERR_ARG, "normalize: direction must be AWV_NORM_LEFT or AWV_NORM_RIGHT");
@@ -408,57 +360,29 @@ int check_direction(int32_t direction) {
 }
 
 int open_state(awv_engine* e, awp::EngineView& v, State*& st, bool need_set) {
-  if (need_set) {
-    if (int rc = awv_internal_view(e, &v)) return rc;
-  } else {
-    awv_internal_device_view(e, &v);
-  }
-  NM_TRY(hipSetDevice(v.device));
   State*& slot = awv_internal_normalize(e);
   if (!slot) slot = new State();
   st = slot;
-  if (!st->ev0) NM_TRY(hipEventCreate(&st->ev0));
-  if (!st->ev1) NM_TRY(hipEventCreate(&st->ev1));
-  if (st->num_cus == 0) {
-    int cus = 0;
-    NM_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, v.device));
-    st->num_cus = std::max(cus, 1);
-  }
-  return AWV_OK;
+  return st->open(e, v, need_set);
 }
 
-bool outside(const awv_result& r, uint64_t arena_bytes) {
-  return r.status == AWV_ST_COMPLETED && (r.cigar_off > arena_bytes || (uint64_t)r.cigar_len > arena_bytes - r.cigar_off);
-}
-
-// One launch over n records whose op bytes are on the device already.  Every index and every op string's place in the arena
-// is checked here, on the host: the kernel reads and writes where the records say.
+// One launch over n records whose op bytes are on the device already.  Every index is checked here, on the host, as
+// RecordPass::begin checks every op string's place in the arena: the kernel reads and writes where the records say.
 int launch(const awp::EngineView& v, const SeqView& seqs, State* st, int32_t direction, const awv_pair* pairs, int64_t n, const awv_result* results,
            uint8_t* d_arena, uint64_t arena_bytes, awv_norm_result* nout, const Span* spans) {
   if (n == 0) return AWV_OK;
-  if (n > INT32_MAX) return awv_internal_fail(AWV_ERR_ARG, "normalize: more than 2^31 - 1 records in one launch");
-  for (int64_t i = 0; i < n; ++i) {
+  for (int64_t i = 0; i < n; ++i)
     if (pairs[i].q_idx < 0 || pairs[i].q_idx >= seqs.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= seqs.n)
       return awv_internal_fail(AWV_ERR_ARG, "normalize: sequence index out of range");
-    if (outside(results[i], arena_bytes)) return awv_internal_fail(AWV_ERR_ARG, "normalize: a record's op bytes lie outside the CIGAR arena");
-  }
-  std::vector<int32_t> order((size_t)n);
-  std::iota(order.begin(), order.end(), 0);
-  auto cols = [&](int32_t i) { return results[i].status == AWV_ST_COMPLETED ? results[i].cigar_len : 0u; };
-  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return cols(a) > cols(b); });
-  NM_TRY(st->d_pairs.reserve((size_t)n));
-  NM_TRY(st->d_results.reserve((size_t)n));
-  NM_TRY(st->d_order.reserve((size_t)n));
-  NM_TRY(st->d_out.reserve((size_t)n));
-  NM_TRY(st->d_counters.reserve(8));
-  NM_TRY(hipMemcpyAsync(st->d_pairs.p, pairs, (size_t)n * sizeof(awv_pair), hipMemcpyHostToDevice, v.stream));
+  if (int rc = st->begin(v, "normalize", n, results, arena_bytes)) return rc;
+  AWV_TRY(st->d_pairs.reserve((size_t)n));
+  AWV_TRY(st->d_out.reserve((size_t)n));
+  AWV_TRY(hipMemcpyAsync(st->d_pairs.p, pairs, (size_t)n * sizeof(awv_pair), hipMemcpyHostToDevice, v.stream));
   if (spans) {
-    NM_TRY(st->d_spans.reserve((size_t)n));
-    NM_TRY(hipMemcpyAsync(st->d_spans.p, spans, (size_t)n * sizeof(Span), hipMemcpyHostToDevice, v.stream));
+    AWV_TRY(st->d_spans.reserve((size_t)n));
+    AWV_TRY(hipMemcpyAsync(st->d_spans.p, spans, (size_t)n * sizeof(Span), hipMemcpyHostToDevice, v.stream));
   }
-  NM_TRY(hipMemcpyAsync(st->d_results.p, results, (size_t)n * sizeof(awv_result), hipMemcpyHostToDevice, v.stream));
-  NM_TRY(hipMemcpyAsync(st->d_order.p, order.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-  NM_TRY(hipMemsetAsync(st->d_counters.p, 0, 8 * sizeof(unsigned long long), v.stream));
+  if (int rc = st->clear_counters(v, 8)) return rc;
   KParams kp{};
   kp.fwd = seqs.fwd;
   kp.rc = seqs.rc;
@@ -473,17 +397,13 @@ int launch(const awp::EngineView& v, const SeqView& seqs, State* st, int32_t dir
   kp.counters = st->d_counters.p;
   kp.npairs = n;
   kp.mirror = direction == AWV_NORM_RIGHT ? 1 : 0;
-  const unsigned grid = (unsigned)std::min<int64_t>(n, v.workgroups > 0 ? (int64_t)v.workgroups : (int64_t)st->num_cus * WAVES_PER_CU);
-  NM_TRY(hipEventRecord(st->ev0, v.stream));
-  hipLaunchKernelGGL(awv_normalize_kernel, dim3(grid), dim3(64), 0, v.stream, kp);
-  NM_TRY(hipGetLastError());
-  NM_TRY(hipEventRecord(st->ev1, v.stream));
+  if (int rc = st->start(v)) return rc;
+  hipLaunchKernelGGL(awv_normalize_kernel, dim3(st->grid(v, n)), dim3(64), 0, v.stream, kp);
+  if (int rc = st->stop(v)) return rc;
   unsigned long long hc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  NM_TRY(hipMemcpyAsync(nout, st->d_out.p, (size_t)n * sizeof(awv_norm_result), hipMemcpyDeviceToHost, v.stream));
-  NM_TRY(hipMemcpyAsync(hc, st->d_counters.p, sizeof(hc), hipMemcpyDeviceToHost, v.stream));
-  NM_TRY(hipStreamSynchronize(v.stream));
   float ms = 0;
-  NM_TRY(hipEventElapsedTime(&ms, st->ev0, st->ev1));
+  AWV_TRY(hipMemcpyAsync(nout, st->d_out.p, (size_t)n * sizeof(awv_norm_result), hipMemcpyDeviceToHost, v.stream));
+  if (int rc = st->finish(v, hc, 8, ms)) return rc;
   st->stats.kernel_ms += ms;
   st->stats.pairs += (uint64_t)n;
   st->stats.records_moved += hc[1];
@@ -517,54 +437,25 @@ int normalize_cigars_core(awv_engine* e, int32_t direction, const awv_pair* pair
   for (int64_t i = 0; i < npairs; ++i) {
     if (pairs[i].q_idx < 0 || pairs[i].q_idx >= v.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= v.n)
       return awv_internal_fail(AWV_ERR_ARG, "normalize_cigars: sequence index out of range");
-    if (outside(results[i], arena_bytes)) return awv_internal_fail(AWV_ERR_ARG, "normalize_cigars: a record's op bytes lie outside the CIGAR arena");
+    if (awvw::outside(results[i], arena_bytes)) return awv_internal_fail(AWV_ERR_ARG, "normalize_cigars: a record's op bytes lie outside the CIGAR arena");
   }
-  // pieces of at most max_arena op bytes (one record alone may exceed it) and 2^20 records: the op bytes of a piece are
-  // packed into 16-byte slots of a staging buffer that keep every string's offset modulo 16 (the kernel's addressing is
-  // part of what a caller may want to exercise); a piece comes back whole and every string returns to its place
+  // in pieces (record_pieces.hpp) that keep every string's offset modulo 16; a piece comes back whole and every string
+  // returns to its place
   std::vector<uint8_t> stage;
   std::vector<awv_result> recs;
   for (int64_t first = 0; first < npairs;) {
-    int64_t n = 0;
-    uint64_t bytes = 0;
-    recs.clear();
-    while (first + n < npairs && n < ((int64_t)1 << 20)) {
-      const awv_result& r = results[first + n];
-      const uint64_t sh = r.cigar_off & 15;
-      const uint64_t need = r.status == AWV_ST_COMPLETED ? (sh + (uint64_t)r.cigar_len + 15) & ~(uint64_t)15 : 0;
-      if (n > 0 && bytes + need > max_arena) break;
-      recs.push_back(r);
-      recs.back().cigar_off = bytes + sh;
-      bytes += need;
-      ++n;
+    const awvw::Piece pc = awvw::pack_piece(results, npairs, first, cigar_arena, max_arena, true, recs, stage);
+    AWV_TRY(st->d_arena.reserve((size_t)pc.bytes + 64));
+    if (pc.bytes) AWV_TRY(hipMemcpyAsync(st->d_arena.p, stage.data(), (size_t)pc.bytes, hipMemcpyHostToDevice, v.stream));
+    if (int rc = launch(v, seqs, st, direction, pairs + first, pc.n, recs.data(), st->d_arena.p, pc.bytes, nout + first, ranges ? spans.data() + first : nullptr)) return rc;
+    if (pc.bytes) {
+      AWV_TRY(hipMemcpyAsync(stage.data(), st->d_arena.p, (size_t)pc.bytes, hipMemcpyDeviceToHost, v.stream));
+      AWV_TRY(hipStreamSynchronize(v.stream));
     }
-    stage.assign((size_t)bytes, 0);
-    for (int64_t i = 0; i < n; ++i) {
-      const awv_result& r = results[first + i];
-      if (r.status == AWV_ST_COMPLETED && r.cigar_len) std::memcpy(stage.data() + recs[(size_t)i].cigar_off, cigar_arena + r.cigar_off, r.cigar_len);
-    }
-    NM_TRY(st->d_arena.reserve((size_t)bytes + 64));
-    if (bytes) NM_TRY(hipMemcpyAsync(st->d_arena.p, stage.data(), (size_t)bytes, hipMemcpyHostToDevice, v.stream));
-    if (int rc = launch(v, seqs, st, direction, pairs + first, n, recs.data(), st->d_arena.p, bytes, nout + first, ranges ? spans.data() + first : nullptr)) return rc;
-    if (bytes) {
-      NM_TRY(hipMemcpyAsync(stage.data(), st->d_arena.p, (size_t)bytes, hipMemcpyDeviceToHost, v.stream));
-      NM_TRY(hipStreamSynchronize(v.stream));
-    }
-    for (int64_t i = 0; i < n; ++i) {
-      const awv_result& r = results[first + i];
-      if (r.status == AWV_ST_COMPLETED && r.cigar_len && nout[first + i].code == AWV_NM_OK)
-        std::memcpy(cigar_arena + r.cigar_off, stage.data() + recs[(size_t)i].cigar_off, r.cigar_len);
-    }
-    first += n;
+    awvw::scatter_back(results + first, nout + first, pc.n, recs, stage, cigar_arena);
+    first += pc.n;
   }
   return AWV_OK;
-}
-
-int null_engine() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return awv_internal_fail(AWV_ERR_NO_DEVICE, "no HIP device available: liballwave_hip has no CPU fallback");
-  return awv_internal_fail(AWV_ERR_ARG, "null engine");
 }
 
 }  // namespace
@@ -585,18 +476,18 @@ extern "C" {
 
 int awv_normalize_cigars(awv_engine* e, int32_t direction, const awv_pair* pairs, int64_t n, const awv_result* results, uint8_t* cigar_arena,
                          uint64_t arena_bytes, awv_norm_result* nout) {
-  if (!e) return awvn::null_engine();
+  if (!e) return awv_internal_null_engine();
   if (n < 0 || (n > 0 && (!pairs || !results || !nout))) return awv_internal_fail(AWV_ERR_ARG, "normalize_cigars: null argument");
   if (arena_bytes > 0 && !cigar_arena) return awv_internal_fail(AWV_ERR_ARG, "normalize_cigars: null arena");
-  NM_GUARDED(return awvn::normalize_cigars_core(e, direction, pairs, n, results, cigar_arena, arena_bytes, awv_internal_max_arena(e), nout, nullptr);)
+  AWV_GUARDED(return awvn::normalize_cigars_core(e, direction, pairs, n, results, cigar_arena, arena_bytes, awv_internal_max_arena(e), nout, nullptr);)
 }
 
 int awv_normalize_ranges(awv_engine* e, int32_t direction, const awv_range_pair* ranges, int64_t n, const awv_result* results, uint8_t* cigar_arena,
                          uint64_t arena_bytes, awv_norm_result* nout) {
-  if (!e) return awvn::null_engine();
+  if (!e) return awv_internal_null_engine();
   if (n < 0 || (n > 0 && (!ranges || !results || !nout))) return awv_internal_fail(AWV_ERR_ARG, "normalize_ranges: null argument");
   if (arena_bytes > 0 && !cigar_arena) return awv_internal_fail(AWV_ERR_ARG, "normalize_ranges: null arena");
-  NM_GUARDED(return awvn::normalize_cigars_core(e, direction, nullptr, n, results, cigar_arena, arena_bytes, awv_internal_max_arena(e), nout, ranges);)
+  AWV_GUARDED(return awvn::normalize_cigars_core(e, direction, nullptr, n, results, cigar_arena, arena_bytes, awv_internal_max_arena(e), nout, ranges);)
 }
 
 int awv_normalize_one_host(int32_t direction, const uint8_t* pattern, int32_t plen, const uint8_t* text, int32_t tlen, const uint8_t* cigar,

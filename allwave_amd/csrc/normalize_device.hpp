@@ -135,11 +135,6 @@ int normalize_batch(awv_engine* e, const SeqView& seqs, int32_t direction, const
 
 }  // namespace awvn
 
-namespace awp {
-struct EngineView;  // planner_device.hpp
-}
-
 // engine.hip
-void awv_internal_device_view(awv_engine* e, awp::EngineView* v);  // (as in clip_device.hpp: the device and the stream, no set needed)
 awvn::State*& awv_internal_normalize(awv_engine* e);
 int32_t& awv_internal_normalize_mode(awv_engine* e);

@@ -159,13 +159,6 @@ __global__ __launch_bounds__(ROUND_WG) void orient_round_kernel(RoundParams p) {
 
 namespace {
 
-#define OR_TRY(expr)                                                                                                 \
-  do {                                                                                                               \
-    const hipError_t _e = (expr);                                                                                    \
-    if (_e != hipSuccess)                                                                                            \
-      return awv_internal_fail(_e == hipErrorOutOfMemory ? AWV_ERR_OOM : AWV_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 // device allocations of one call, freed whichever way it ends
 struct Scratch {
   std::vector<void*> blocks;
@@ -223,18 +216,18 @@ int race(awv_engine* e, const awp::EngineView& v, const awv_penalties* pen, cons
   awv_score_result* d_res;
   unsigned int* d_counts;
   for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 3; ++b) OR_TRY(sc.get(&d_act[a][b], (size_t)n));
-  OR_TRY(sc.get(&d_lo, (size_t)2 * n));
-  OR_TRY(sc.get(&d_hi, (size_t)2 * n));
-  OR_TRY(sc.get(&d_bound, (size_t)n));
-  OR_TRY(sc.get(&d_base, (size_t)n));
-  OR_TRY(sc.get(&d_west, (size_t)n));
-  OR_TRY(sc.get(&d_dec, (size_t)n));
-  OR_TRY(sc.get(&d_rounds, (size_t)n));
-  OR_TRY(sc.get(&d_ent_id, (size_t)2 * n));
-  OR_TRY(sc.get(&d_ent_bound, (size_t)2 * n));
-  OR_TRY(sc.get(&d_res, (size_t)2 * n));
-  OR_TRY(sc.get(&d_counts, 2));
+    for (int b = 0; b < 3; ++b) AWV_TRY(sc.get(&d_act[a][b], (size_t)n));
+  AWV_TRY(sc.get(&d_lo, (size_t)2 * n));
+  AWV_TRY(sc.get(&d_hi, (size_t)2 * n));
+  AWV_TRY(sc.get(&d_bound, (size_t)n));
+  AWV_TRY(sc.get(&d_base, (size_t)n));
+  AWV_TRY(sc.get(&d_west, (size_t)n));
+  AWV_TRY(sc.get(&d_dec, (size_t)n));
+  AWV_TRY(sc.get(&d_rounds, (size_t)n));
+  AWV_TRY(sc.get(&d_ent_id, (size_t)2 * n));
+  AWV_TRY(sc.get(&d_ent_bound, (size_t)2 * n));
+  AWV_TRY(sc.get(&d_res, (size_t)2 * n));
+  AWV_TRY(sc.get(&d_counts, 2));
   // round 0: both strands under the first bound, of every pair worth racing (the others stay undecided: the caller aligns
   // them in full)
   std::vector<int32_t> h_pair, h_ent, h_mask, h_bound((size_t)n, 0), h_base((size_t)n, 0), h_west((size_t)n, 0);
@@ -258,18 +251,18 @@ int race(awv_engine* e, const awp::EngineView& v, const awv_penalties* pen, cons
     ++n_act;
   }
   if (n_act > 0) {
-    OR_TRY(hipMemcpyAsync(d_act[0][0], h_pair.data(), (size_t)n_act * 4, hipMemcpyHostToDevice, v.stream));
-    OR_TRY(hipMemcpyAsync(d_act[0][1], h_ent.data(), (size_t)n_act * 4, hipMemcpyHostToDevice, v.stream));
-    OR_TRY(hipMemcpyAsync(d_act[0][2], h_mask.data(), (size_t)n_act * 4, hipMemcpyHostToDevice, v.stream));
+    AWV_TRY(hipMemcpyAsync(d_act[0][0], h_pair.data(), (size_t)n_act * 4, hipMemcpyHostToDevice, v.stream));
+    AWV_TRY(hipMemcpyAsync(d_act[0][1], h_ent.data(), (size_t)n_act * 4, hipMemcpyHostToDevice, v.stream));
+    AWV_TRY(hipMemcpyAsync(d_act[0][2], h_mask.data(), (size_t)n_act * 4, hipMemcpyHostToDevice, v.stream));
   }
-  OR_TRY(hipMemcpyAsync(d_bound, h_bound.data(), (size_t)n * 4, hipMemcpyHostToDevice, v.stream));
-  OR_TRY(hipMemcpyAsync(d_base, h_base.data(), (size_t)n * 4, hipMemcpyHostToDevice, v.stream));
-  OR_TRY(hipMemcpyAsync(d_west, h_west.data(), (size_t)n * 4, hipMemcpyHostToDevice, v.stream));
-  OR_TRY(hipMemsetAsync(d_lo, 0, (size_t)2 * n * 4, v.stream));
-  OR_TRY(hipMemsetD32Async((hipDeviceptr_t)d_hi, HI_NONE, (size_t)2 * n, v.stream));
-  OR_TRY(hipMemsetD32Async((hipDeviceptr_t)d_dec, AWV_ORIENT_UNDECIDED, (size_t)n, v.stream));
-  OR_TRY(hipMemsetAsync(d_rounds, 0, (size_t)n * 4, v.stream));
-  OR_TRY(hipStreamSynchronize(v.stream));
+  AWV_TRY(hipMemcpyAsync(d_bound, h_bound.data(), (size_t)n * 4, hipMemcpyHostToDevice, v.stream));
+  AWV_TRY(hipMemcpyAsync(d_base, h_base.data(), (size_t)n * 4, hipMemcpyHostToDevice, v.stream));
+  AWV_TRY(hipMemcpyAsync(d_west, h_west.data(), (size_t)n * 4, hipMemcpyHostToDevice, v.stream));
+  AWV_TRY(hipMemsetAsync(d_lo, 0, (size_t)2 * n * 4, v.stream));
+  AWV_TRY(hipMemsetD32Async((hipDeviceptr_t)d_hi, HI_NONE, (size_t)2 * n, v.stream));
+  AWV_TRY(hipMemsetD32Async((hipDeviceptr_t)d_dec, AWV_ORIENT_UNDECIDED, (size_t)n, v.stream));
+  AWV_TRY(hipMemsetAsync(d_rounds, 0, (size_t)n * 4, v.stream));
+  AWV_TRY(hipStreamSynchronize(v.stream));
   int64_t n_ent = 2 * n_act;
   std::vector<awv_pair> ep;
   std::vector<awv_score_result> res;
@@ -284,8 +277,8 @@ int race(awv_engine* e, const awp::EngineView& v, const awv_penalties* pen, cons
     awv_stats st{};
     awv_engine_stats(e, &st);
     add_stats(total, st);
-    OR_TRY(hipMemcpyAsync(d_res, res.data(), (size_t)n_ent * sizeof(awv_score_result), hipMemcpyHostToDevice, v.stream));
-    OR_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned int), v.stream));
+    AWV_TRY(hipMemcpyAsync(d_res, res.data(), (size_t)n_ent * sizeof(awv_score_result), hipMemcpyHostToDevice, v.stream));
+    AWV_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned int), v.stream));
     RoundParams rp{};
     rp.rule = rule;
     rp.n_act = (int)n_act;
@@ -307,29 +300,29 @@ int race(awv_engine* e, const awp::EngineView& v, const awv_penalties* pen, cons
     rp.ent_bound = d_ent_bound;
     rp.counts = d_counts;
     hipLaunchKernelGGL(orient_round_kernel, dim3((unsigned)((n_act + ROUND_WG - 1) / ROUND_WG)), dim3(ROUND_WG), 0, v.stream, rp);
-    OR_TRY(hipGetLastError());
+    AWV_TRY(hipGetLastError());
     unsigned int counts[2] = {0, 0};
-    OR_TRY(hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, v.stream));
-    OR_TRY(hipStreamSynchronize(v.stream));
+    AWV_TRY(hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, v.stream));
+    AWV_TRY(hipStreamSynchronize(v.stream));
     if ((int64_t)counts[0] > n_act || (int64_t)counts[1] > 2 * (int64_t)counts[0])
       return awv_internal_fail(AWV_ERR_HIP, "orient_pairs: inconsistent round counts");
     n_act = counts[0];
     n_ent = counts[1];
     if (n_ent > 0) {
-      OR_TRY(hipMemcpyAsync(ent_id.data(), d_ent_id, (size_t)n_ent * 4, hipMemcpyDeviceToHost, v.stream));
-      OR_TRY(hipMemcpyAsync(ent_bound.data(), d_ent_bound, (size_t)n_ent * 4, hipMemcpyDeviceToHost, v.stream));
-      OR_TRY(hipStreamSynchronize(v.stream));
+      AWV_TRY(hipMemcpyAsync(ent_id.data(), d_ent_id, (size_t)n_ent * 4, hipMemcpyDeviceToHost, v.stream));
+      AWV_TRY(hipMemcpyAsync(ent_bound.data(), d_ent_bound, (size_t)n_ent * 4, hipMemcpyDeviceToHost, v.stream));
+      AWV_TRY(hipStreamSynchronize(v.stream));
     }
   }
   decision.resize((size_t)n);
   rounds.resize((size_t)n);
   lo.resize((size_t)2 * n);
   hi.resize((size_t)2 * n);
-  OR_TRY(hipMemcpyAsync(decision.data(), d_dec, (size_t)n * 4, hipMemcpyDeviceToHost, v.stream));
-  OR_TRY(hipMemcpyAsync(rounds.data(), d_rounds, (size_t)n * 4, hipMemcpyDeviceToHost, v.stream));
-  OR_TRY(hipMemcpyAsync(lo.data(), d_lo, (size_t)2 * n * 4, hipMemcpyDeviceToHost, v.stream));
-  OR_TRY(hipMemcpyAsync(hi.data(), d_hi, (size_t)2 * n * 4, hipMemcpyDeviceToHost, v.stream));
-  OR_TRY(hipStreamSynchronize(v.stream));
+  AWV_TRY(hipMemcpyAsync(decision.data(), d_dec, (size_t)n * 4, hipMemcpyDeviceToHost, v.stream));
+  AWV_TRY(hipMemcpyAsync(rounds.data(), d_rounds, (size_t)n * 4, hipMemcpyDeviceToHost, v.stream));
+  AWV_TRY(hipMemcpyAsync(lo.data(), d_lo, (size_t)2 * n * 4, hipMemcpyDeviceToHost, v.stream));
+  AWV_TRY(hipMemcpyAsync(hi.data(), d_hi, (size_t)2 * n * 4, hipMemcpyDeviceToHost, v.stream));
+  AWV_TRY(hipStreamSynchronize(v.stream));
   return AWV_OK;
 }
 
@@ -342,7 +335,7 @@ int orient_core(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, 
   for (int64_t i = 0; i < n; ++i)
     if (pairs[i].q_idx < 0 || pairs[i].q_idx >= v.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= v.n)
       return awv_internal_fail(AWV_ERR_ARG, "orient_pairs: sequence index out of range");
-  OR_TRY(hipSetDevice(v.device));
+  AWV_TRY(hipSetDevice(v.device));
   awv_stats total{};
   std::vector<int32_t> decision, lo, hi, rounds;
   const bool raced = n > 0 && !(flags & AWV_ORIENT_FULL) && awo::race_pays(rule);
@@ -406,23 +399,10 @@ extern "C" {
 
 int awv_orient_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, int32_t flags,
                      awv_orient_result* out) {
-  if (!e) {  // (without a GPU there is no engine to pass: say so, as awv_engine_create does)
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-      return awv_internal_fail(AWV_ERR_NO_DEVICE, "no HIP device available: liballwave_hip has no CPU fallback");
-    return awv_internal_fail(AWV_ERR_ARG, "null engine");
-  }
+  if (!e) return awv_internal_null_engine();
   if (npairs < 0 || (npairs > 0 && (!pairs || !out))) return awv_internal_fail(AWV_ERR_ARG, "orient_pairs: null pairs or out");
   if (flags & ~AWV_ORIENT_FULL) return awv_internal_fail(AWV_ERR_ARG, "orient_pairs: unknown flag");
-  try {
-    return orient_core(e, pen, pairs, npairs, flags, out);
-  } catch (const std::bad_alloc&) {
-    return awv_internal_fail(AWV_ERR_OOM, "host memory exhausted");
-  } catch (const std::exception& ex) {
-    return awv_internal_fail(AWV_ERR_HIP, std::string("internal error: ") + ex.what());
-  } catch (...) {
-    return awv_internal_fail(AWV_ERR_HIP, "internal error: unknown exception");
-  }
+  AWV_GUARDED(return orient_core(e, pen, pairs, npairs, flags, out);)
 }
 
 int awv_orient_decide(const awv_penalties* pen, int32_t lo_f, int32_t hi_f, int32_t lo_r, int32_t hi_r) {

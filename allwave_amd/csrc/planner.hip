@@ -19,6 +19,7 @@
 
 #include "allwave_hip.h"
 #include "planner_device.hpp"
+#include "wave_ops.hpp"
 
 namespace awp {
 
@@ -340,26 +341,7 @@ __global__ __launch_bounds__(256) void awp_keep_kernel(const uint8_t* __restrict
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-template <typename T>
-struct Buf {  // device buffer that grows
-  T* p = nullptr;
-  size_t cap = 0;
-  hipError_t reserve(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const hipError_t e = hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T));
-    if (e == hipSuccess) cap = std::max<size_t>(n, 1);
-    else p = nullptr;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
+using awvw::Buf;  // (wave_ops.hpp: the device buffer that only ever grows)
 
 struct SketchSet {
   bool built = false;
@@ -410,38 +392,11 @@ using namespace awp;
 
 namespace {
 
-#define PL_TRY(expr)                                                                                             \
-  do {                                                                                                           \
-    const hipError_t _e = (expr);                                                                                \
-    if (_e != hipSuccess)                                                                                        \
-      return awv_internal_fail(_e == hipErrorOutOfMemory ? AWV_ERR_OOM : AWV_ERR_HIP,                            \
-                               std::string(#expr) + ": " + hipGetErrorString(_e));                               \
-  } while (0)
-
-#define PL_GUARDED(body)                                                                                         \
-  try {                                                                                                          \
-    body                                                                                                         \
-  } catch (const std::bad_alloc&) {                                                                              \
-    return awv_internal_fail(AWV_ERR_OOM, "host memory exhausted");                                              \
-  } catch (const std::exception& ex) {                                                                           \
-    return awv_internal_fail(AWV_ERR_HIP, std::string("internal error: ") + ex.what());                          \
-  } catch (...) {                                                                                                \
-    return awv_internal_fail(AWV_ERR_HIP, "internal error: unknown exception");                                  \
-  }
-
-// a null engine: without a GPU there is none to pass, so say that first (as awv_engine_create does)
-int null_engine() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return awv_internal_fail(AWV_ERR_NO_DEVICE, "no HIP device available: liballwave_hip has no CPU fallback");
-  return awv_internal_fail(AWV_ERR_ARG, "null engine");
-}
-
 // the engine's view and plan state, the device made current
 int open(awv_engine* e, EngineView& v, PlanState*& ps) {
-  if (!e) return null_engine();
+  if (!e) return awv_internal_null_engine();
   if (int rc = awv_internal_view(e, &v)) return rc;
-  PL_TRY(hipSetDevice(v.device));
+  AWV_TRY(hipSetDevice(v.device));
   PlanState*& slot = awv_internal_plan(e);
   if (!slot) slot = new PlanState();
   ps = slot;
@@ -470,17 +425,17 @@ int sketch_core(awv_engine* e, int kind, int k, int s, uint32_t* sizes) {
   sk.slot.assign((size_t)n + 1, 0);
   for (int i = 0; i < n; ++i) sk.slot[i + 1] = sk.slot[i] + (uint64_t)std::min<int64_t>(s, std::max<int64_t>(0, (int64_t)v.len_host[i] - k + 1));
   sk.cnt.assign((size_t)n, 0);
-  PL_TRY(sk.d_hash.reserve(sk.slot[n]));
-  PL_TRY(sk.d_slot.reserve((size_t)n + 1));
-  PL_TRY(sk.d_cnt.reserve((size_t)n));
-  PL_TRY(hipMemcpyAsync(sk.d_slot.p, sk.slot.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, v.stream));
+  AWV_TRY(sk.d_hash.reserve(sk.slot[n]));
+  AWV_TRY(sk.d_slot.reserve((size_t)n + 1));
+  AWV_TRY(sk.d_cnt.reserve((size_t)n));
+  AWV_TRY(hipMemcpyAsync(sk.d_slot.p, sk.slot.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, v.stream));
   const size_t lds = (size_t)(2 * s + SK_TILE) * 8 + SK_TILE + 64;
-  PL_TRY(hipFuncSetAttribute((const void*)awp_sketch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  AWV_TRY(hipFuncSetAttribute((const void*)awp_sketch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(awp_sketch_kernel, dim3(n), dim3(SK_WG), lds, v.stream, kind == AWV_SK_REVCOMP ? v.rc : v.fwd, v.off, v.len,
                      (const uint64_t*)sk.d_slot.p, k, s, kind == AWV_SK_CANONICAL ? 1 : 0, sk.d_hash.p, sk.d_cnt.p);
-  PL_TRY(hipGetLastError());
-  PL_TRY(hipMemcpyAsync(sk.cnt.data(), sk.d_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, v.stream));
-  PL_TRY(hipStreamSynchronize(v.stream));
+  AWV_TRY(hipGetLastError());
+  AWV_TRY(hipMemcpyAsync(sk.cnt.data(), sk.d_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, v.stream));
+  AWV_TRY(hipStreamSynchronize(v.stream));
   sk.built = true;
   if (sizes) std::memcpy(sizes, sk.cnt.data(), (size_t)n * 4);
   return AWV_OK;
@@ -498,8 +453,8 @@ int sketch_copy_core(awv_engine* e, int kind, uint64_t* offsets, uint64_t* hashe
   if (offsets) std::memcpy(offsets, o.data(), o.size() * 8);
   if (hashes) {
     for (int i = 0; i < n; ++i)
-      if (sk->cnt[i]) PL_TRY(hipMemcpyAsync(hashes + o[i], sk->d_hash.p + sk->slot[i], (size_t)sk->cnt[i] * 8, hipMemcpyDeviceToHost, v.stream));
-    PL_TRY(hipStreamSynchronize(v.stream));
+      if (sk->cnt[i]) AWV_TRY(hipMemcpyAsync(hashes + o[i], sk->d_hash.p + sk->slot[i], (size_t)sk->cnt[i] * 8, hipMemcpyDeviceToHost, v.stream));
+    AWV_TRY(hipStreamSynchronize(v.stream));
   }
   return AWV_OK;
 }
@@ -512,11 +467,11 @@ size_t max_cnt(const SketchSet& sk) {
 
 int rows_launch(const EngineView& v, const SketchSet& a, const SketchSet& b, int row0, int nrows, uint16_t* d_out) {
   const size_t lds = std::max<size_t>(max_cnt(a), 1) * 8;
-  PL_TRY(hipFuncSetAttribute((const void*)awp_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  AWV_TRY(hipFuncSetAttribute((const void*)awp_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(awp_rows_kernel, dim3(nrows, (v.n + ROW_COLS - 1) / ROW_COLS), dim3(ROW_WG), lds, v.stream,
                      (const uint64_t*)a.d_hash.p, (const uint64_t*)a.d_slot.p, (const uint32_t*)a.d_cnt.p, (const uint64_t*)b.d_hash.p,
                      (const uint64_t*)b.d_slot.p, (const uint32_t*)b.d_cnt.p, row0, v.n, d_out);
-  PL_TRY(hipGetLastError());
+  AWV_TRY(hipGetLastError());
   return AWV_OK;
 }
 
@@ -528,10 +483,10 @@ int rows_core(awv_engine* e, int kind, int row0, int nrows, uint16_t* out) {
   if (int rc = built_sketch(ps, kind, sk)) return rc;
   if (!out || row0 < 0 || nrows < 0 || (int64_t)row0 + nrows > v.n) return awv_internal_fail(AWV_ERR_ARG, "sketch_rows: rows out of range");
   if (nrows == 0) return AWV_OK;
-  PL_TRY(ps->d_counts.reserve((size_t)nrows * v.n));
+  AWV_TRY(ps->d_counts.reserve((size_t)nrows * v.n));
   if (int rc = rows_launch(v, *sk, *sk, row0, nrows, ps->d_counts.p)) return rc;
-  PL_TRY(hipMemcpyAsync(out, ps->d_counts.p, (size_t)nrows * v.n * 2, hipMemcpyDeviceToHost, v.stream));
-  PL_TRY(hipStreamSynchronize(v.stream));
+  AWV_TRY(hipMemcpyAsync(out, ps->d_counts.p, (size_t)nrows * v.n * 2, hipMemcpyDeviceToHost, v.stream));
+  AWV_TRY(hipStreamSynchronize(v.stream));
   return AWV_OK;
 }
 
@@ -566,24 +521,24 @@ int pair_counts_core(awv_engine* e, int kind_a, int kind_b, const int32_t* a, co
     }
   seg_first.push_back(npairs);
   const size_t nseg = seg_a.size();
-  PL_TRY(ps->d_i32a.reserve(nseg));
-  PL_TRY(ps->d_i64.reserve(nseg + 1));
-  PL_TRY(ps->d_i32b.reserve((size_t)npairs));
-  PL_TRY(ps->d_u32.reserve((size_t)npairs));
-  PL_TRY(ps->d_counts.reserve((size_t)npairs));
-  PL_TRY(hipMemcpyAsync(ps->d_i32a.p, seg_a.data(), nseg * 4, hipMemcpyHostToDevice, v.stream));
-  PL_TRY(hipMemcpyAsync(ps->d_i64.p, seg_first.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, v.stream));
-  PL_TRY(hipMemcpyAsync(ps->d_i32b.p, b, (size_t)npairs * 4, hipMemcpyHostToDevice, v.stream));
-  PL_TRY(hipMemcpyAsync(ps->d_u32.p, order.data(), (size_t)npairs * 4, hipMemcpyHostToDevice, v.stream));
+  AWV_TRY(ps->d_i32a.reserve(nseg));
+  AWV_TRY(ps->d_i64.reserve(nseg + 1));
+  AWV_TRY(ps->d_i32b.reserve((size_t)npairs));
+  AWV_TRY(ps->d_u32.reserve((size_t)npairs));
+  AWV_TRY(ps->d_counts.reserve((size_t)npairs));
+  AWV_TRY(hipMemcpyAsync(ps->d_i32a.p, seg_a.data(), nseg * 4, hipMemcpyHostToDevice, v.stream));
+  AWV_TRY(hipMemcpyAsync(ps->d_i64.p, seg_first.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, v.stream));
+  AWV_TRY(hipMemcpyAsync(ps->d_i32b.p, b, (size_t)npairs * 4, hipMemcpyHostToDevice, v.stream));
+  AWV_TRY(hipMemcpyAsync(ps->d_u32.p, order.data(), (size_t)npairs * 4, hipMemcpyHostToDevice, v.stream));
   const size_t lds = std::max<size_t>(max_cnt(*sa), 1) * 8;
-  PL_TRY(hipFuncSetAttribute((const void*)awp_pair_counts_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  AWV_TRY(hipFuncSetAttribute((const void*)awp_pair_counts_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(awp_pair_counts_kernel, dim3((unsigned)nseg), dim3(ROW_WG), lds, v.stream, (const uint64_t*)sa->d_hash.p,
                      (const uint64_t*)sa->d_slot.p, (const uint32_t*)sa->d_cnt.p, (const uint64_t*)sb->d_hash.p,
                      (const uint64_t*)sb->d_slot.p, (const uint32_t*)sb->d_cnt.p, (const int32_t*)ps->d_i32a.p,
                      (const int64_t*)ps->d_i64.p, (const int32_t*)ps->d_i32b.p, (const uint32_t*)ps->d_u32.p, ps->d_counts.p);
-  PL_TRY(hipGetLastError());
-  PL_TRY(hipMemcpyAsync(out, ps->d_counts.p, (size_t)npairs * 2, hipMemcpyDeviceToHost, v.stream));
-  PL_TRY(hipStreamSynchronize(v.stream));
+  AWV_TRY(hipGetLastError());
+  AWV_TRY(hipMemcpyAsync(out, ps->d_counts.p, (size_t)npairs * 2, hipMemcpyDeviceToHost, v.stream));
+  AWV_TRY(hipStreamSynchronize(v.stream));
   return AWV_OK;
 }
 
@@ -600,25 +555,25 @@ int knn_core(awv_engine* e, int kind, int kn, int kf, int32_t* near_out, int32_t
   if (kn + kf == 0 || n == 0) return AWV_OK;
   // rows in blocks whose counts take at most 128 MiB
   const int R = (int)std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)64 << 20) / n));
-  PL_TRY(ps->d_counts.reserve((size_t)R * n));
-  PL_TRY(ps->d_near.reserve((size_t)n * std::max(kn, 1)));
-  PL_TRY(ps->d_far.reserve((size_t)n * std::max(kf, 1)));
+  AWV_TRY(ps->d_counts.reserve((size_t)R * n));
+  AWV_TRY(ps->d_near.reserve((size_t)n * std::max(kn, 1)));
+  AWV_TRY(ps->d_far.reserve((size_t)n * std::max(kf, 1)));
   for (int r0 = 0; r0 < n; r0 += R) {
     const int nr = std::min(R, n - r0);
     if (int rc = rows_launch(v, *sk, *sk, r0, nr, ps->d_counts.p)) return rc;
     hipLaunchKernelGGL(awp_knn_kernel, dim3((nr + KNN_WG / 64 - 1) / (KNN_WG / 64)), dim3(KNN_WG), 0, v.stream,
                        (const uint16_t*)ps->d_counts.p, (const uint32_t*)sk->d_cnt.p, r0, nr, n, kn, kf, ps->d_near.p, ps->d_far.p);
-    PL_TRY(hipGetLastError());
+    AWV_TRY(hipGetLastError());
   }
-  if (kn) PL_TRY(hipMemcpyAsync(near_out, ps->d_near.p, (size_t)n * kn * 4, hipMemcpyDeviceToHost, v.stream));
-  if (kf) PL_TRY(hipMemcpyAsync(far_out, ps->d_far.p, (size_t)n * kf * 4, hipMemcpyDeviceToHost, v.stream));
-  PL_TRY(hipStreamSynchronize(v.stream));
+  if (kn) AWV_TRY(hipMemcpyAsync(near_out, ps->d_near.p, (size_t)n * kn * 4, hipMemcpyDeviceToHost, v.stream));
+  if (kf) AWV_TRY(hipMemcpyAsync(far_out, ps->d_far.p, (size_t)n * kf * 4, hipMemcpyDeviceToHost, v.stream));
+  AWV_TRY(hipStreamSynchronize(v.stream));
   return AWV_OK;
 }
 
 int keep_core(awv_engine* e, int n, const uint8_t* id_bytes, const uint64_t* id_off, uint64_t threshold, int keep_all, int include_diag,
               uint32_t* bitmap) {
-  if (!e) return null_engine();
+  if (!e) return awv_internal_null_engine();
   EngineView v;
   {
     const int rc = awv_internal_view(e, &v);  // (the keep test reads no sequence: an engine without a set will do)
@@ -629,24 +584,24 @@ int keep_core(awv_engine* e, int n, const uint8_t* id_bytes, const uint64_t* id_
   for (int i = 0; i < n; ++i)
     if (id_off[i + 1] < id_off[i] || id_off[i + 1] - id_off[i] > (1u << 20)) return awv_internal_fail(AWV_ERR_ARG, "keep_pairs: bad id offsets");
   if (id_off[n] > 0 && !id_bytes) return awv_internal_fail(AWV_ERR_ARG, "keep_pairs: null id bytes");
-  PL_TRY(hipSetDevice(v.device));
+  AWV_TRY(hipSetDevice(v.device));
   PlanState*& slot = awv_internal_plan(e);
   if (!slot) slot = new PlanState();
   PlanState* ps = slot;
   const int words = (n + 31) / 32;
   const size_t nw = (size_t)n * words;
-  PL_TRY(ps->d_bytes.reserve((size_t)id_off[n] - id_off[0] + 1));
-  PL_TRY(ps->d_u64.reserve((size_t)n + 1));
-  PL_TRY(ps->d_u32.reserve(nw));
+  AWV_TRY(ps->d_bytes.reserve((size_t)id_off[n] - id_off[0] + 1));
+  AWV_TRY(ps->d_u64.reserve((size_t)n + 1));
+  AWV_TRY(ps->d_u32.reserve(nw));
   std::vector<uint64_t> off((size_t)n + 1);
   for (int i = 0; i <= n; ++i) off[i] = id_off[i] - id_off[0];
-  if (off[n]) PL_TRY(hipMemcpyAsync(ps->d_bytes.p, id_bytes + id_off[0], (size_t)off[n], hipMemcpyHostToDevice, v.stream));
-  PL_TRY(hipMemcpyAsync(ps->d_u64.p, off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, v.stream));
+  if (off[n]) AWV_TRY(hipMemcpyAsync(ps->d_bytes.p, id_bytes + id_off[0], (size_t)off[n], hipMemcpyHostToDevice, v.stream));
+  AWV_TRY(hipMemcpyAsync(ps->d_u64.p, off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, v.stream));
   hipLaunchKernelGGL(awp_keep_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, v.stream, (const uint8_t*)ps->d_bytes.p,
                      (const uint64_t*)ps->d_u64.p, n, words, threshold, keep_all, include_diag, ps->d_u32.p);
-  PL_TRY(hipGetLastError());
-  PL_TRY(hipMemcpyAsync(bitmap, ps->d_u32.p, nw * 4, hipMemcpyDeviceToHost, v.stream));
-  PL_TRY(hipStreamSynchronize(v.stream));
+  AWV_TRY(hipGetLastError());
+  AWV_TRY(hipMemcpyAsync(bitmap, ps->d_u32.p, nw * 4, hipMemcpyDeviceToHost, v.stream));
+  AWV_TRY(hipStreamSynchronize(v.stream));
   return AWV_OK;
 }
 
@@ -655,29 +610,29 @@ int keep_core(awv_engine* e, int n, const uint8_t* id_bytes, const uint64_t* id_
 extern "C" {
 
 int awv_sketch(awv_engine* e, int32_t kind, int32_t k, int32_t s, uint32_t* sizes) {
-  PL_GUARDED(return sketch_core(e, kind, k, s, sizes);)
+  AWV_GUARDED(return sketch_core(e, kind, k, s, sizes);)
 }
 
 int awv_sketch_copy(awv_engine* e, int32_t kind, uint64_t* offsets, uint64_t* hashes) {
-  PL_GUARDED(return sketch_copy_core(e, kind, offsets, hashes);)
+  AWV_GUARDED(return sketch_copy_core(e, kind, offsets, hashes);)
 }
 
 int awv_sketch_pair_counts(awv_engine* e, int32_t kind_a, int32_t kind_b, const int32_t* a, const int32_t* b, int64_t npairs,
                            uint16_t* inter) {
-  PL_GUARDED(return pair_counts_core(e, kind_a, kind_b, a, b, npairs, inter);)
+  AWV_GUARDED(return pair_counts_core(e, kind_a, kind_b, a, b, npairs, inter);)
 }
 
 int awv_sketch_rows(awv_engine* e, int32_t kind, int32_t row0, int32_t nrows, uint16_t* inter) {
-  PL_GUARDED(return rows_core(e, kind, row0, nrows, inter);)
+  AWV_GUARDED(return rows_core(e, kind, row0, nrows, inter);)
 }
 
 int awv_sketch_knn(awv_engine* e, int32_t kind, int32_t k_nearest, int32_t k_farthest, int32_t* nearest, int32_t* farthest) {
-  PL_GUARDED(return knn_core(e, kind, k_nearest, k_farthest, nearest, farthest);)
+  AWV_GUARDED(return knn_core(e, kind, k_nearest, k_farthest, nearest, farthest);)
 }
 
 int awv_keep_pairs(awv_engine* e, int32_t n, const uint8_t* id_bytes, const uint64_t* id_offsets, uint64_t threshold, int32_t keep_all,
                    int32_t include_diag, uint32_t* bitmap) {
-  PL_GUARDED(return keep_core(e, n, id_bytes, id_offsets, threshold, keep_all, include_diag, bitmap);)
+  AWV_GUARDED(return keep_core(e, n, id_bytes, id_offsets, threshold, keep_all, include_diag, bitmap);)
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "allwave_hip.h"
+#include "host_errors.hpp"  // AWV_TRY, AWV_GUARDED, awv_internal_fail, awv_internal_null_engine
 
 struct awv_engine;
 
@@ -38,6 +39,8 @@ struct EngineView {
 
 // engine.hip
 int awv_internal_view(awv_engine* e, awp::EngineView* v);  // AWV_ERR_STATE without a sequence set
+// the same for a caller that needs the device and the stream only: an engine without a sequence set is no failure (the view
+// then names no sequences) and awv_last_error() is left alone
+void awv_internal_device_view(awv_engine* e, awp::EngineView* v);
 awp::PlanState*& awv_internal_plan(awv_engine* e);
-int awv_internal_fail(int code, const std::string& msg);   // records awv_last_error(), returns code
 int awv_internal_check_penalties(const awv_penalties* pen);  // the engine's sign rules for a penalty set (not the ring's size limit): AWV_OK or awv_align_pairs' error

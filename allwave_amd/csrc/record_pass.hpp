@@ -1,0 +1,109 @@
+// record_pass.hpp -- the host skeleton of a record pass: a kernel with one wave per alignment record,
+// persistent waves taking records, longest op string first, from a cursor (awvw::take_record, wave_ops.hpp).  verify.hip,
+// clip.hip, split.hip and normalize.hip each keep a State that derives from RecordPass next to the buffers and stats only
+// that pass has; a launch is begin(), the pass's own uploads, clear_counters(), KParams, start(), the kernel, stop(),
+// the pass's own copy-backs, finish().
+#pragma once
+
+#include <algorithm>
+#include <climits>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "planner_device.hpp"  // EngineView, awv_internal_view, AWV_TRY
+#include "record_pieces.hpp"   // outside
+#include "wave_ops.hpp"        // Buf
+
+namespace awvw {
+
+constexpr int WAVES_PER_CU = 16;  // persistent one-wave workgroups per CU: what a chunk does depends on its scans and loads, other waves fill the wait
+
+struct RecordPass {
+  Buf<awv_result> d_results;
+  Buf<int32_t> d_order;
+  Buf<unsigned long long> d_counters;  // [0] the cursor, [1..] the pass's own
+  Buf<uint8_t> d_arena;                // awv_*_cigars: a piece of the caller's op bytes
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  int num_cus = 0;
+
+  void release() {
+    d_results.release();
+    d_order.release();
+    d_counters.release();
+    d_arena.release();
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    ev0 = ev1 = nullptr;
+  }
+
+  // the engine's view, its device made current, the events and the CU count.  need_set: the pass reads sequences, so an
+  // engine without a set is AWV_ERR_STATE; else the view of such an engine names no sequences and that is no error
+  int open(awv_engine* e, awp::EngineView& v, bool need_set) {
+    if (need_set) {
+      if (int rc = awv_internal_view(e, &v)) return rc;
+    } else {
+      awv_internal_device_view(e, &v);
+    }
+    AWV_TRY(hipSetDevice(v.device));
+    if (!ev0) AWV_TRY(hipEventCreate(&ev0));
+    if (!ev1) AWV_TRY(hipEventCreate(&ev1));
+    if (num_cus == 0) {
+      int cus = 0;
+      AWV_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, v.device));
+      num_cus = std::max(cus, 1);
+    }
+    return AWV_OK;
+  }
+
+  // n > 0 records whose op bytes are on the device already.  Every op string's place in the arena is checked here, on the
+  // host: the kernel reads what the records say.  Then the records and their dispatch order go up.
+  int begin(const awp::EngineView& v, const char* name, int64_t n, const awv_result* results, uint64_t arena_bytes) {
+    if (n > INT32_MAX) return awv_internal_fail(AWV_ERR_ARG, std::string(name) + ": more than 2^31 - 1 records in one launch");
+    for (int64_t i = 0; i < n; ++i)
+      if (outside(results[i], arena_bytes)) return awv_internal_fail(AWV_ERR_ARG, std::string(name) + ": a record's op bytes lie outside the CIGAR arena");
+    std::vector<int32_t> order((size_t)n);
+    std::iota(order.begin(), order.end(), 0);
+    auto cols = [&](int32_t i) { return results[i].status == AWV_ST_COMPLETED ? results[i].cigar_len : 0u; };
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return cols(a) > cols(b); });
+    AWV_TRY(d_results.reserve((size_t)n));
+    AWV_TRY(d_order.reserve((size_t)n));
+    AWV_TRY(hipMemcpyAsync(d_results.p, results, (size_t)n * sizeof(awv_result), hipMemcpyHostToDevice, v.stream));
+    AWV_TRY(hipMemcpyAsync(d_order.p, order.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
+    return AWV_OK;
+  }
+
+  // one-wave workgroups: awv_engine_config.workgroups, or WAVES_PER_CU per CU, and never more than records
+  unsigned grid(const awp::EngineView& v, int64_t n) const {
+    return (unsigned)std::min<int64_t>(n, v.workgroups > 0 ? (int64_t)v.workgroups : (int64_t)num_cus * WAVES_PER_CU);
+  }
+
+  // behind every upload, the pass's own included, as each pass did on its own: d_counters is a State's last allocation and
+  // the memset the stream's last operation before the kernel's bracket
+  int clear_counters(const awp::EngineView& v, int n_counters) {
+    AWV_TRY(d_counters.reserve((size_t)n_counters));
+    AWV_TRY(hipMemsetAsync(d_counters.p, 0, (size_t)n_counters * sizeof(unsigned long long), v.stream));
+    return AWV_OK;
+  }
+
+  // the bracket around the kernel launch
+  int start(const awp::EngineView& v) {
+    AWV_TRY(hipEventRecord(ev0, v.stream));
+    return AWV_OK;
+  }
+  int stop(const awp::EngineView& v) {
+    AWV_TRY(hipGetLastError());
+    AWV_TRY(hipEventRecord(ev1, v.stream));
+    return AWV_OK;
+  }
+
+  // behind the pass's own copy-backs: the counters come back to hc[0 .. n_counters), the stream is waited for, ms is the kernel's time
+  int finish(const awp::EngineView& v, unsigned long long* hc, int n_counters, float& ms) {
+    AWV_TRY(hipMemcpyAsync(hc, d_counters.p, (size_t)n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost, v.stream));
+    AWV_TRY(hipStreamSynchronize(v.stream));
+    AWV_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+    return AWV_OK;
+  }
+};
+
+}  // namespace awvw

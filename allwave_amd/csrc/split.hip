@@ -18,16 +18,13 @@
 #include <algorithm>
 #include <cstring>
 #include <new>
-#include <numeric>
 #include <string>
 #include <vector>
 
-#include "planner_device.hpp"  // EngineView, awv_internal_fail, awv_internal_view
 #include "range_span.hpp"
+#include "record_pass.hpp"  // the host skeleton of a record pass: RecordPass, pack_piece, AWV_TRY
 
 namespace awvs {
-
-constexpr int WAVES_PER_CU = 16;  // as clip.hip
 
 struct KParams {
   const awv_result* results;    // cigar_off relative to `arena`
@@ -59,13 +56,7 @@ __global__ __launch_bounds__(64) void awv_split_kernel(KParams kp) {
   const long long a = kp.match_bonus;
   unsigned long long n_empty = 0, n_columns = 0, n_segments = 0, n_scanned = 0, n_overflow = 0;  // (uniform)
   for (;;) {
-    unsigned slot_lo = 0, slot_hi = 0;
-    if (lane == 0) {
-      const unsigned long long s = atomicAdd(&kp.counters[0], 1ull);
-      slot_lo = (unsigned)s;
-      slot_hi = (unsigned)(s >> 32);
-    }
-    const unsigned long long slot = (unsigned long long)uniform(slot_lo) | ((unsigned long long)uniform(slot_hi) << 32);
+    const unsigned long long slot = awvw::take_record(kp.counters, lane);
     if (slot >= (unsigned long long)kp.npairs) break;
     const int pair = __builtin_amdgcn_readfirstlane(kp.order[slot]);
     const awv_result rec = kp.results[pair];
@@ -137,30 +128,18 @@ __global__ __launch_bounds__(64) void awv_split_kernel(KParams kp) {
 
 using awvw::Buf;
 
-struct State {
-  Buf<awv_result> d_results;
-  Buf<int32_t> d_order;
+struct State : awvw::RecordPass {
   Buf<uint64_t> d_seg_first;
   Buf<awv_clip_result> d_seg;
   Buf<Interval> d_stack;
   Buf<awv_split_index> d_index;
-  Buf<unsigned long long> d_counters;
-  Buf<uint8_t> d_arena;  // awv_split_cigars: the caller's op bytes
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int num_cus = 0;
   awv_split_stats stats{};
   void release() {
-    d_results.release();
-    d_order.release();
+    RecordPass::release();
     d_seg_first.release();
     d_seg.release();
     d_stack.release();
     d_index.release();
-    d_counters.release();
-    d_arena.release();
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    ev0 = ev1 = nullptr;
   }
 };
 
@@ -176,25 +155,6 @@ void stats_reset(State* s) {
 
 namespace {
 
-#define SP_TRY(expr)                                                                                              \
-  do {                                                                                                            \
-    hipError_t _e = (expr);                                                                                       \
-    if (_e != hipSuccess)                                                                                         \
-      return awv_internal_fail(_e == hipErrorOutOfMemory ? AWV_ERR_OOM : AWV_ERR_HIP,                             \
-                               std::string(#expr) + ": " + hipGetErrorString(_e));                                \
-  } while (0)
-
-#define SP_GUARDED(body)                                                                                          \
-  try {                                                                                                           \
-    body                                                                                                          \
-  } catch (const std::bad_alloc&) {                                                                               \
-    return awv_internal_fail(AWV_ERR_OOM, "host memory exhausted");                                               \
-  } catch (const std::exception& ex) {                                                                            \
-    return awv_internal_fail(AWV_ERR_HIP, std::string("internal error: ") + ex.what());                           \
-  } catch (...) {                                                                                                 \
-    return awv_internal_fail(AWV_ERR_HIP, "internal error: unknown exception");                                   \
-  }
-
 // the clip's rules for penalties and bonus, and the threshold
 int check_args(const awv_penalties* p, int32_t match_bonus, int64_t min_score, awv_penalties& out) {
   if (int rc = awv_internal_check_penalties(p)) return rc;
@@ -208,23 +168,10 @@ int check_args(const awv_penalties* p, int32_t match_bonus, int64_t min_score, a
 }
 
 int open_state(awv_engine* e, awp::EngineView& v, State*& st) {
-  awv_internal_device_view(e, &v);  // (the split reads no sequence: an engine without a set will do)
-  SP_TRY(hipSetDevice(v.device));
   State*& slot = awv_internal_split(e);
   if (!slot) slot = new State();
   st = slot;
-  if (!st->ev0) SP_TRY(hipEventCreate(&st->ev0));
-  if (!st->ev1) SP_TRY(hipEventCreate(&st->ev1));
-  if (st->num_cus == 0) {
-    int cus = 0;
-    SP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, v.device));
-    st->num_cus = std::max(cus, 1);
-  }
-  return AWV_OK;
-}
-
-bool outside(const awv_result& r, uint64_t arena_bytes) {
-  return r.status == AWV_ST_COMPLETED && (r.cigar_off > arena_bytes || (uint64_t)r.cigar_len > arena_bytes - r.cigar_off);
+  return st->open(e, v, false);  // (the split reads no sequence: an engine without a set will do)
 }
 
 bool ascending(const uint64_t* seg_first, int64_t n) {
@@ -233,34 +180,23 @@ bool ascending(const uint64_t* seg_first, int64_t n) {
   return true;
 }
 
-// One launch over n records whose op bytes are on the device already.  The op strings' places in the arena are checked here,
-// on the host; the slot regions are the caller's layout, whatever rule it was checked by -- the kernel stays inside them.
-// Record i's segments go to sout[seg_first[i] ..), sorted; slots behind them are not written.
+// One launch over n records whose op bytes are on the device already.  The slot regions are the caller's layout, whatever
+// rule it was checked by -- the kernel stays inside them.  Record i's segments go to sout[seg_first[i] ..), sorted; slots
+// behind them are not written.
 int launch(const awp::EngineView& v, State* st, const awv_penalties& pen, int32_t match_bonus, int64_t min_score, int64_t n, const awv_result* results,
            const uint8_t* d_arena, uint64_t arena_bytes, const uint64_t* seg_first, awv_split_index* iout, awv_clip_result* sout) {
   if (n == 0) return AWV_OK;
-  if (n > INT32_MAX) return awv_internal_fail(AWV_ERR_ARG, "split: more than 2^31 - 1 records in one launch");
   if (!ascending(seg_first, n)) return awv_internal_fail(AWV_ERR_ARG, "split: seg_first must ascend");
-  for (int64_t i = 0; i < n; ++i)
-    if (outside(results[i], arena_bytes)) return awv_internal_fail(AWV_ERR_ARG, "split: a record's op bytes lie outside the CIGAR arena");
-  std::vector<int32_t> order((size_t)n);
-  std::iota(order.begin(), order.end(), 0);
-  auto cols = [&](int32_t i) { return results[i].status == AWV_ST_COMPLETED ? results[i].cigar_len : 0u; };
-  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return cols(a) > cols(b); });
+  if (int rc = st->begin(v, "split", n, results, arena_bytes)) return rc;
   std::vector<uint64_t> rel((size_t)n + 1);
   for (int64_t i = 0; i <= n; ++i) rel[(size_t)i] = seg_first[i] - seg_first[0];
   const uint64_t total = rel[(size_t)n];
-  SP_TRY(st->d_results.reserve((size_t)n));
-  SP_TRY(st->d_order.reserve((size_t)n));
-  SP_TRY(st->d_seg_first.reserve((size_t)n + 1));
-  SP_TRY(st->d_index.reserve((size_t)n));
-  SP_TRY(st->d_seg.reserve((size_t)total + 1));
-  SP_TRY(st->d_stack.reserve((size_t)total + (size_t)n));
-  SP_TRY(st->d_counters.reserve(8));
-  SP_TRY(hipMemcpyAsync(st->d_results.p, results, (size_t)n * sizeof(awv_result), hipMemcpyHostToDevice, v.stream));
-  SP_TRY(hipMemcpyAsync(st->d_order.p, order.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-  SP_TRY(hipMemcpyAsync(st->d_seg_first.p, rel.data(), ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, v.stream));
-  SP_TRY(hipMemsetAsync(st->d_counters.p, 0, 8 * sizeof(unsigned long long), v.stream));
+  AWV_TRY(st->d_seg_first.reserve((size_t)n + 1));
+  AWV_TRY(st->d_index.reserve((size_t)n));
+  AWV_TRY(st->d_seg.reserve((size_t)total + 1));
+  AWV_TRY(st->d_stack.reserve((size_t)total + (size_t)n));
+  AWV_TRY(hipMemcpyAsync(st->d_seg_first.p, rel.data(), ((size_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, v.stream));
+  if (int rc = st->clear_counters(v, 8)) return rc;
   KParams kp{};
   kp.results = st->d_results.p;
   kp.order = st->d_order.p;
@@ -274,16 +210,14 @@ int launch(const awp::EngineView& v, State* st, const awv_penalties& pen, int32_
   kp.min_score = min_score;
   kp.pen = pen;
   kp.match_bonus = match_bonus;
-  const unsigned grid = (unsigned)std::min<int64_t>(n, v.workgroups > 0 ? (int64_t)v.workgroups : (int64_t)st->num_cus * WAVES_PER_CU);
-  SP_TRY(hipEventRecord(st->ev0, v.stream));
-  hipLaunchKernelGGL(awv_split_kernel, dim3(grid), dim3(64), 0, v.stream, kp);
-  SP_TRY(hipGetLastError());
-  SP_TRY(hipEventRecord(st->ev1, v.stream));
+  if (int rc = st->start(v)) return rc;
+  hipLaunchKernelGGL(awv_split_kernel, dim3(st->grid(v, n)), dim3(64), 0, v.stream, kp);
+  if (int rc = st->stop(v)) return rc;
   unsigned long long hc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   std::vector<awv_split_index> hix((size_t)n);
-  SP_TRY(hipMemcpyAsync(hix.data(), st->d_index.p, (size_t)n * sizeof(awv_split_index), hipMemcpyDeviceToHost, v.stream));
-  SP_TRY(hipMemcpyAsync(hc, st->d_counters.p, sizeof(hc), hipMemcpyDeviceToHost, v.stream));
-  SP_TRY(hipStreamSynchronize(v.stream));
+  float ms = 0;
+  AWV_TRY(hipMemcpyAsync(hix.data(), st->d_index.p, (size_t)n * sizeof(awv_split_index), hipMemcpyDeviceToHost, v.stream));
+  if (int rc = st->finish(v, hc, 8, ms)) return rc;
   if (hc[5] != 0) return awv_internal_fail(AWV_ERR_HIP, "split: internal error: a record found more segments than its slots hold");
   // the slot region as far as it is used: the index says where the last segment lies
   uint64_t used = 0;
@@ -291,8 +225,8 @@ int launch(const awp::EngineView& v, State* st, const awv_penalties& pen, int32_
     if (hix[(size_t)i].count > 0) used = std::max(used, rel[(size_t)i] + (uint64_t)hix[(size_t)i].count);
   std::vector<awv_clip_result> hseg((size_t)used);
   if (used) {
-    SP_TRY(hipMemcpyAsync(hseg.data(), st->d_seg.p, (size_t)used * sizeof(awv_clip_result), hipMemcpyDeviceToHost, v.stream));
-    SP_TRY(hipStreamSynchronize(v.stream));
+    AWV_TRY(hipMemcpyAsync(hseg.data(), st->d_seg.p, (size_t)used * sizeof(awv_clip_result), hipMemcpyDeviceToHost, v.stream));
+    AWV_TRY(hipStreamSynchronize(v.stream));
   }
   for (int64_t i = 0; i < n; ++i) {
     const int32_t c = hix[(size_t)i].count;
@@ -303,8 +237,6 @@ int launch(const awp::EngineView& v, State* st, const awv_penalties& pen, int32_
     }
     iout[i] = hix[(size_t)i];
   }
-  float ms = 0;
-  SP_TRY(hipEventElapsedTime(&ms, st->ev0, st->ev1));
   st->stats.kernel_ms += ms;
   st->stats.pairs += (uint64_t)n;
   st->stats.empty += hc[1];
@@ -323,7 +255,7 @@ int split_cigars_core(awv_engine* e, const awv_penalties* pen_in, int32_t match_
   // region holds what an op string of its length may need
   if (!ascending(seg_first, n_all)) return awv_internal_fail(AWV_ERR_ARG, "split_cigars: seg_first must ascend");
   for (int64_t i = 0; i < n_all; ++i) {
-    if (outside(results[i], arena_bytes)) return awv_internal_fail(AWV_ERR_ARG, "split_cigars: a record's op bytes lie outside the CIGAR arena");
+    if (awvw::outside(results[i], arena_bytes)) return awv_internal_fail(AWV_ERR_ARG, "split_cigars: a record's op bytes lie outside the CIGAR arena");
     const int64_t need = results[i].status == AWV_ST_COMPLETED ? slots(match_bonus, min_score, (int64_t)results[i].cigar_len) : 0;
     if (seg_first[i + 1] - seg_first[i] < (uint64_t)need)
       return awv_internal_fail(AWV_ERR_ARG, "split_cigars: record " + std::to_string(i) + " owns fewer slots than awv_split_slots(a, min_score, cigar_len)");
@@ -333,42 +265,17 @@ int split_cigars_core(awv_engine* e, const awv_penalties* pen_in, int32_t match_
   State* st = nullptr;
   if (int rc = open_state(e, v, st)) return rc;
   st->stats = awv_split_stats{};
-  // pieces as in awv_clip_cigars: at most max_arena op bytes (one record alone may exceed it) and 2^20 records, the op bytes
-  // packed into 16-byte slots of a staging buffer that keep every string's offset modulo 16
+  // in pieces (record_pieces.hpp) that keep every string's offset modulo 16
   std::vector<uint8_t> stage;
   std::vector<awv_result> recs;
   for (int64_t first = 0; first < n_all;) {
-    int64_t n = 0;
-    uint64_t bytes = 0;
-    recs.clear();
-    while (first + n < n_all && n < ((int64_t)1 << 20)) {
-      const awv_result& r = results[first + n];
-      const uint64_t sh = r.cigar_off & 15;
-      const uint64_t need = r.status == AWV_ST_COMPLETED ? (sh + (uint64_t)r.cigar_len + 15) & ~(uint64_t)15 : 0;
-      if (n > 0 && bytes + need > max_arena) break;
-      recs.push_back(r);
-      recs.back().cigar_off = bytes + sh;
-      bytes += need;
-      ++n;
-    }
-    stage.assign((size_t)bytes, 0);
-    for (int64_t i = 0; i < n; ++i) {
-      const awv_result& r = results[first + i];
-      if (r.status == AWV_ST_COMPLETED && r.cigar_len) std::memcpy(stage.data() + recs[(size_t)i].cigar_off, cigar_arena + r.cigar_off, r.cigar_len);
-    }
-    SP_TRY(st->d_arena.reserve((size_t)bytes + 64));
-    if (bytes) SP_TRY(hipMemcpyAsync(st->d_arena.p, stage.data(), (size_t)bytes, hipMemcpyHostToDevice, v.stream));
-    if (int rc = launch(v, st, pen, match_bonus, min_score, n, recs.data(), st->d_arena.p, bytes, seg_first + first, iout + first, sout)) return rc;
-    first += n;
+    const awvw::Piece pc = awvw::pack_piece(results, n_all, first, cigar_arena, max_arena, true, recs, stage);
+    AWV_TRY(st->d_arena.reserve((size_t)pc.bytes + 64));
+    if (pc.bytes) AWV_TRY(hipMemcpyAsync(st->d_arena.p, stage.data(), (size_t)pc.bytes, hipMemcpyHostToDevice, v.stream));
+    if (int rc = launch(v, st, pen, match_bonus, min_score, pc.n, recs.data(), st->d_arena.p, pc.bytes, seg_first + first, iout + first, sout)) return rc;
+    first += pc.n;
   }
   return AWV_OK;
-}
-
-int null_engine() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return awv_internal_fail(AWV_ERR_NO_DEVICE, "no HIP device available: liballwave_hip has no CPU fallback");
-  return awv_internal_fail(AWV_ERR_ARG, "null engine");
 }
 
 // seg_first from the (pattern, text) lengths of each entry
@@ -409,7 +316,7 @@ int awv_split_layout_pairs(awv_engine* e, const awv_pair* pairs, int64_t n, int3
   awp::EngineView v;
   if (n > 0)
     if (int rc = awv_internal_view(e, &v)) return rc;
-  SP_GUARDED(return awvs::layout(n, match_bonus, min_score, seg_first, [&](int64_t i, int64_t& pl, int64_t& tl) {
+  AWV_GUARDED(return awvs::layout(n, match_bonus, min_score, seg_first, [&](int64_t i, int64_t& pl, int64_t& tl) {
     if (pairs[i].q_idx < 0 || pairs[i].q_idx >= v.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= v.n) return false;
     pl = v.len_host[pairs[i].q_idx];
     tl = v.len_host[pairs[i].t_idx];
@@ -423,7 +330,7 @@ int awv_split_layout_ranges(awv_engine* e, const awv_range_pair* ranges, int64_t
   awp::EngineView v;
   if (n > 0)
     if (int rc = awv_internal_view(e, &v)) return rc;
-  SP_GUARDED(return awvs::layout(n, match_bonus, min_score, seg_first, [&](int64_t i, int64_t& pl, int64_t& tl) {
+  AWV_GUARDED(return awvs::layout(n, match_bonus, min_score, seg_first, [&](int64_t i, int64_t& pl, int64_t& tl) {
     awv_pair p;
     awvr::Span s;
     if (!awvr::split_range(v.len_host, v.n, ranges[i], p, s)) return false;
@@ -439,7 +346,7 @@ int awv_split_one_host(const awv_penalties* pen, int32_t match_bonus, int64_t mi
   if (int rc = awvs::check_args(pen, match_bonus, min_score, p)) return rc;
   if (!count || cap < 0 || (cap > 0 && !sout) || n < 0 || n > (int64_t)UINT32_MAX || (n > 0 && !cigar))
     return awv_internal_fail(AWV_ERR_ARG, "split_one_host: bad argument");
-  SP_GUARDED(
+  AWV_GUARDED(
     std::vector<awvs::Interval> stack((size_t)std::min<int64_t>(awvs::slots(match_bonus, min_score, n), n) + 1);
     const awv_split_index ix = awvs::split_one(p, match_bonus, min_score, cigar, n, sout, cap, stack.data());
     *count = ix.count;
@@ -450,10 +357,10 @@ int awv_split_one_host(const awv_penalties* pen, int32_t match_bonus, int64_t mi
 
 int awv_split_cigars(awv_engine* e, const awv_penalties* pen, int32_t match_bonus, int64_t min_score, const awv_result* results, int64_t n,
                      const uint8_t* cigar_arena, uint64_t arena_bytes, const uint64_t* seg_first, awv_split_index* iout, awv_clip_result* sout) {
-  if (!e) return awvs::null_engine();
+  if (!e) return awv_internal_null_engine();
   if (n < 0 || !seg_first || (n > 0 && (!results || !iout))) return awv_internal_fail(AWV_ERR_ARG, "split_cigars: null argument");
   if (arena_bytes > 0 && !cigar_arena) return awv_internal_fail(AWV_ERR_ARG, "split_cigars: null arena");
-  SP_GUARDED(return awvs::split_cigars_core(e, pen, match_bonus, min_score, results, n, cigar_arena, arena_bytes, awv_internal_max_arena(e), seg_first,
+  AWV_GUARDED(return awvs::split_cigars_core(e, pen, match_bonus, min_score, results, n, cigar_arena, arena_bytes, awv_internal_max_arena(e), seg_first,
                                             iout, sout);)
 }
 

@@ -18,20 +18,13 @@
 
 #include <algorithm>
 #include <climits>
-#include <cstring>
 #include <new>
-#include <numeric>
 #include <string>
 #include <vector>
 
-#include "planner_device.hpp"  // EngineView, awv_internal_view, awv_internal_fail
-#include "wave_ops.hpp"
+#include "record_pass.hpp"  // the host skeleton of a record pass: RecordPass, pack_piece, AWV_TRY
 
 namespace awvf {
-
-constexpr int LANE_BYTES = 16;
-constexpr int CHUNK = 64 * LANE_BYTES;
-constexpr int WAVES_PER_CU = 16;  // persistent one-wave workgroups per CU: the loads of a chunk depend on its scan, other waves fill the wait
 
 struct KParams {
   const uint8_t* fwd;       // the engine's forward copies
@@ -49,13 +42,15 @@ struct KParams {
   awv_penalties pen;
 };
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-using awvw::byte_range_mask;  // (wave_ops.hpp: the scans and the byte counting shared with clip.hip)
+using awvw::byte_range_mask;  // (wave_ops.hpp: the chunk, the scans and the byte counting shared with clip.hip)
+using awvw::CHUNK;
 using awvw::count_bytes;
 using awvw::from_lower_lane;
+using awvw::LANE_BYTES;
+using awvw::u32x4;
 using awvw::wave_scan_add;
 using awvw::wave_scan_max;
+using awvw::wave_sum_i64;
 
 // 16 bytes of a sequence from position `pos` on, as two 64-bit halves: five aligned dwords, shifted into place.  Dwords
 // that start at or behind the sequence's end are not read; a dword that starts inside it ends at most 3 bytes behind it,
@@ -75,24 +70,11 @@ __device__ __forceinline__ void load16(const uint8_t* seq, int len, int pos, uns
   hi = (unsigned long long)x[2] | ((unsigned long long)x[3] << 32);
 }
 
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(64) void awv_verify_kernel(KParams kp) {
   const int lane = threadIdx.x;
   unsigned long long n_failed = 0, n_columns = 0;  // (uniform)
   for (;;) {
-    unsigned slot_lo = 0, slot_hi = 0;
-    if (lane == 0) {
-      const unsigned long long s = atomicAdd(&kp.counters[0], 1ull);
-      slot_lo = (unsigned)s;
-      slot_hi = (unsigned)(s >> 32);
-    }
-    const unsigned long long slot = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)slot_lo) |
-                                    ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)slot_hi) << 32);
+    const unsigned long long slot = awvw::take_record(kp.counters, lane);
     if (slot >= (unsigned long long)kp.npairs) break;
     const int pair = __builtin_amdgcn_readfirstlane(kp.order[slot]);
     const awv_result claimed = kp.results[pair];
@@ -229,28 +211,16 @@ __global__ __launch_bounds__(64) void awv_verify_kernel(KParams kp) {
 
 using awvw::Buf;
 
-struct State {
+struct State : awvw::RecordPass {
   Buf<awv_pair> d_pairs;
   Buf<Span> d_spans;
-  Buf<awv_result> d_results;
-  Buf<int32_t> d_order;
   Buf<awv_verify_result> d_out;
-  Buf<unsigned long long> d_counters;
-  Buf<uint8_t> d_arena;  // awv_verify_cigars: the caller's op bytes
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int num_cus = 0;
   awv_verify_stats stats{};
   void release() {
+    RecordPass::release();
     d_pairs.release();
     d_spans.release();
-    d_results.release();
-    d_order.release();
     d_out.release();
-    d_counters.release();
-    d_arena.release();
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    ev0 = ev1 = nullptr;
   }
 };
 
@@ -266,25 +236,6 @@ void stats_reset(State* s) {
 
 namespace {
 
-#define VF_TRY(expr)                                                                                              \
-  do {                                                                                                            \
-    hipError_t _e = (expr);                                                                                       \
-    if (_e != hipSuccess)                                                                                         \
-      return awv_internal_fail(_e == hipErrorOutOfMemory ? AWV_ERR_OOM : AWV_ERR_HIP,                             \
-                               std::string(#expr) + ": " + hipGetErrorString(_e));                                \
-  } while (0)
-
-#define VF_GUARDED(body)                                                                                          \
-  try {                                                                                                           \
-    body                                                                                                          \
-  } catch (const std::bad_alloc&) {                                                                               \
-    return awv_internal_fail(AWV_ERR_OOM, "host memory exhausted");                                               \
-  } catch (const std::exception& ex) {                                                                            \
-    return awv_internal_fail(AWV_ERR_HIP, std::string("internal error: ") + ex.what());                           \
-  } catch (...) {                                                                                                 \
-    return awv_internal_fail(AWV_ERR_HIP, "internal error: unknown exception");                                   \
-  }
-
 // the engine's own sign rules for penalties (engine.hip; re-scoring has no ring to fit, so any size goes), then the unused piece of a gap-affine set cleared
 int check_penalties(const awv_penalties* p, awv_penalties& out) {
   if (int rc = awv_internal_check_penalties(p)) return rc;
@@ -295,51 +246,29 @@ int check_penalties(const awv_penalties* p, awv_penalties& out) {
 }
 
 int open_state(awv_engine* e, awp::EngineView& v, State*& st) {
-  if (int rc = awv_internal_view(e, &v)) return rc;
-  VF_TRY(hipSetDevice(v.device));
   State*& slot = awv_internal_verify(e);
   if (!slot) slot = new State();
   st = slot;
-  if (!st->ev0) VF_TRY(hipEventCreate(&st->ev0));
-  if (!st->ev1) VF_TRY(hipEventCreate(&st->ev1));
-  if (st->num_cus == 0) {
-    int cus = 0;
-    VF_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, v.device));
-    st->num_cus = std::max(cus, 1);
-  }
-  return AWV_OK;
+  return st->open(e, v, true);
 }
 
-// One launch over n pairs whose op bytes are on the device already.  Every index and every op string's place in the arena
-// is checked here, on the host: the kernel reads what the records say.
+// One launch over n pairs whose op bytes are on the device already.  Every index is checked here, on the host, as
+// RecordPass::begin checks every op string's place in the arena: the kernel reads what the records say.
 int launch(const awp::EngineView& v, State* st, const awv_penalties& pen, const awv_pair* pairs, int64_t n, const awv_result* results,
            const uint8_t* d_arena, uint64_t arena_bytes, awv_verify_result* vout, const Span* spans = nullptr) {
   if (n == 0) return AWV_OK;
-  if (n > INT32_MAX) return awv_internal_fail(AWV_ERR_ARG, "verify: more than 2^31 - 1 pairs in one launch");
-  for (int64_t i = 0; i < n; ++i) {
+  for (int64_t i = 0; i < n; ++i)
     if (pairs[i].q_idx < 0 || pairs[i].q_idx >= v.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= v.n)
       return awv_internal_fail(AWV_ERR_ARG, "verify: sequence index out of range");
-    if (results[i].status == AWV_ST_COMPLETED &&
-        (results[i].cigar_off > arena_bytes || (uint64_t)results[i].cigar_len > arena_bytes - results[i].cigar_off))
-      return awv_internal_fail(AWV_ERR_ARG, "verify: a record's op bytes lie outside the CIGAR arena");
-  }
-  std::vector<int32_t> order((size_t)n);
-  std::iota(order.begin(), order.end(), 0);
-  auto cols = [&](int32_t i) { return results[i].status == AWV_ST_COMPLETED ? results[i].cigar_len : 0u; };
-  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return cols(a) > cols(b); });
-  VF_TRY(st->d_pairs.reserve((size_t)n));
-  VF_TRY(st->d_results.reserve((size_t)n));
-  VF_TRY(st->d_order.reserve((size_t)n));
-  VF_TRY(st->d_out.reserve((size_t)n));
-  VF_TRY(st->d_counters.reserve(4));
-  VF_TRY(hipMemcpyAsync(st->d_pairs.p, pairs, (size_t)n * sizeof(awv_pair), hipMemcpyHostToDevice, v.stream));
+  if (int rc = st->begin(v, "verify", n, results, arena_bytes)) return rc;
+  AWV_TRY(st->d_pairs.reserve((size_t)n));
+  AWV_TRY(st->d_out.reserve((size_t)n));
+  AWV_TRY(hipMemcpyAsync(st->d_pairs.p, pairs, (size_t)n * sizeof(awv_pair), hipMemcpyHostToDevice, v.stream));
   if (spans) {
-    VF_TRY(st->d_spans.reserve((size_t)n));
-    VF_TRY(hipMemcpyAsync(st->d_spans.p, spans, (size_t)n * sizeof(Span), hipMemcpyHostToDevice, v.stream));
+    AWV_TRY(st->d_spans.reserve((size_t)n));
+    AWV_TRY(hipMemcpyAsync(st->d_spans.p, spans, (size_t)n * sizeof(Span), hipMemcpyHostToDevice, v.stream));
   }
-  VF_TRY(hipMemcpyAsync(st->d_results.p, results, (size_t)n * sizeof(awv_result), hipMemcpyHostToDevice, v.stream));
-  VF_TRY(hipMemcpyAsync(st->d_order.p, order.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, v.stream));
-  VF_TRY(hipMemsetAsync(st->d_counters.p, 0, 4 * sizeof(unsigned long long), v.stream));
+  if (int rc = st->clear_counters(v, 4)) return rc;
   KParams kp{};
   kp.fwd = v.fwd;
   kp.rc = v.rc;
@@ -354,17 +283,13 @@ int launch(const awp::EngineView& v, State* st, const awv_penalties& pen, const 
   kp.counters = st->d_counters.p;
   kp.npairs = n;
   kp.pen = pen;
-  const unsigned grid = (unsigned)std::min<int64_t>(n, v.workgroups > 0 ? (int64_t)v.workgroups : (int64_t)st->num_cus * WAVES_PER_CU);
-  VF_TRY(hipEventRecord(st->ev0, v.stream));
-  hipLaunchKernelGGL(awv_verify_kernel, dim3(grid), dim3(64), 0, v.stream, kp);
-  VF_TRY(hipGetLastError());
-  VF_TRY(hipEventRecord(st->ev1, v.stream));
+  if (int rc = st->start(v)) return rc;
+  hipLaunchKernelGGL(awv_verify_kernel, dim3(st->grid(v, n)), dim3(64), 0, v.stream, kp);
+  if (int rc = st->stop(v)) return rc;
   unsigned long long hc[4] = {0, 0, 0, 0};
-  VF_TRY(hipMemcpyAsync(vout, st->d_out.p, (size_t)n * sizeof(awv_verify_result), hipMemcpyDeviceToHost, v.stream));
-  VF_TRY(hipMemcpyAsync(hc, st->d_counters.p, sizeof(hc), hipMemcpyDeviceToHost, v.stream));
-  VF_TRY(hipStreamSynchronize(v.stream));
   float ms = 0;
-  VF_TRY(hipEventElapsedTime(&ms, st->ev0, st->ev1));
+  AWV_TRY(hipMemcpyAsync(vout, st->d_out.p, (size_t)n * sizeof(awv_verify_result), hipMemcpyDeviceToHost, v.stream));
+  if (int rc = st->finish(v, hc, 4, ms)) return rc;
   st->stats.kernel_ms += ms;
   st->stats.pairs += (uint64_t)n;
   st->stats.failed += hc[1];
@@ -394,44 +319,18 @@ int verify_cigars_core(awv_engine* e, const awv_penalties* pen_in, const awv_pai
   }
   // before anything goes up: every completed record's op bytes lie inside the caller's arena
   for (int64_t i = 0; i < npairs; ++i)
-    if (results[i].status == AWV_ST_COMPLETED &&
-        (results[i].cigar_off > arena_bytes || (uint64_t)results[i].cigar_len > arena_bytes - results[i].cigar_off))
-      return awv_internal_fail(AWV_ERR_ARG, "verify_cigars: a record's op bytes lie outside the CIGAR arena");
-  // pieces of at most max_arena op bytes (one record alone may exceed it) and 2^20 pairs: the op bytes of a piece are packed
-  // into 16-byte slots of a staging buffer, so records may share, overlap or leave out parts of the caller's arena
+    if (awvw::outside(results[i], arena_bytes)) return awv_internal_fail(AWV_ERR_ARG, "verify_cigars: a record's op bytes lie outside the CIGAR arena");
+  // in pieces (record_pieces.hpp); this pass alone packs every string at the start of its slot
   std::vector<uint8_t> stage;
   std::vector<awv_result> recs;
   for (int64_t first = 0; first < npairs;) {
-    int64_t n = 0;
-    uint64_t bytes = 0;
-    recs.clear();
-    while (first + n < npairs && n < ((int64_t)1 << 20)) {
-      const awv_result& r = results[first + n];
-      const uint64_t need = r.status == AWV_ST_COMPLETED ? ((uint64_t)r.cigar_len + 15) & ~(uint64_t)15 : 0;
-      if (n > 0 && bytes + need > max_arena) break;
-      recs.push_back(r);
-      recs.back().cigar_off = bytes;
-      bytes += need;
-      ++n;
-    }
-    stage.assign((size_t)bytes, 0);
-    for (int64_t i = 0; i < n; ++i) {
-      const awv_result& r = results[first + i];
-      if (r.status == AWV_ST_COMPLETED && r.cigar_len) std::memcpy(stage.data() + recs[(size_t)i].cigar_off, cigar_arena + r.cigar_off, r.cigar_len);
-    }
-    VF_TRY(st->d_arena.reserve((size_t)bytes + 64));
-    if (bytes) VF_TRY(hipMemcpyAsync(st->d_arena.p, stage.data(), (size_t)bytes, hipMemcpyHostToDevice, v.stream));
-    if (int rc = launch(v, st, pen, pairs + first, n, recs.data(), st->d_arena.p, bytes, vout + first, ranges ? spans.data() + first : nullptr)) return rc;
-    first += n;
+    const awvw::Piece pc = awvw::pack_piece(results, npairs, first, cigar_arena, max_arena, false, recs, stage);
+    AWV_TRY(st->d_arena.reserve((size_t)pc.bytes + 64));
+    if (pc.bytes) AWV_TRY(hipMemcpyAsync(st->d_arena.p, stage.data(), (size_t)pc.bytes, hipMemcpyHostToDevice, v.stream));
+    if (int rc = launch(v, st, pen, pairs + first, pc.n, recs.data(), st->d_arena.p, pc.bytes, vout + first, ranges ? spans.data() + first : nullptr)) return rc;
+    first += pc.n;
   }
   return AWV_OK;
-}
-
-int null_engine() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return awv_internal_fail(AWV_ERR_NO_DEVICE, "no HIP device available: liballwave_hip has no CPU fallback");
-  return awv_internal_fail(AWV_ERR_ARG, "null engine");
 }
 
 }  // namespace
@@ -452,18 +351,18 @@ extern "C" {
 
 int awv_verify_cigars(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const awv_result* results,
                       const uint8_t* cigar_arena, uint64_t arena_bytes, awv_verify_result* vout) {
-  if (!e) return awvf::null_engine();
+  if (!e) return awv_internal_null_engine();
   if (npairs < 0 || (npairs > 0 && (!pairs || !results || !vout))) return awv_internal_fail(AWV_ERR_ARG, "verify_cigars: null argument");
   if (arena_bytes > 0 && !cigar_arena) return awv_internal_fail(AWV_ERR_ARG, "verify_cigars: null arena");
-  VF_GUARDED(return awvf::verify_cigars_core(e, pen, pairs, npairs, results, cigar_arena, arena_bytes, awv_internal_max_arena(e), vout);)
+  AWV_GUARDED(return awvf::verify_cigars_core(e, pen, pairs, npairs, results, cigar_arena, arena_bytes, awv_internal_max_arena(e), vout);)
 }
 
 int awv_verify_ranges(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const awv_result* results,
                       const uint8_t* cigar_arena, uint64_t arena_bytes, awv_verify_result* vout) {
-  if (!e) return awvf::null_engine();
+  if (!e) return awv_internal_null_engine();
   if (n < 0 || (n > 0 && (!ranges || !results || !vout))) return awv_internal_fail(AWV_ERR_ARG, "verify_ranges: null argument");
   if (arena_bytes > 0 && !cigar_arena) return awv_internal_fail(AWV_ERR_ARG, "verify_ranges: null arena");
-  VF_GUARDED(return awvf::verify_cigars_core(e, pen, nullptr, n, results, cigar_arena, arena_bytes, awv_internal_max_arena(e), vout, ranges);)
+  AWV_GUARDED(return awvf::verify_cigars_core(e, pen, nullptr, n, results, cigar_arena, arena_bytes, awv_internal_max_arena(e), vout, ranges);)
 }
 
 int awv_verify_one_host(const awv_penalties* pen, const uint8_t* pattern, int32_t plen, const uint8_t* text, int32_t tlen,

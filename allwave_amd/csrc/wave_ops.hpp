@@ -1,5 +1,6 @@
-// wave_ops.hpp -- what the kernels that scan op bytes (verify.hip, clip.hip) share: wave64 inclusive scans on the DPP network,
-// packed byte counting over a lane's 16 bytes, and the device buffer their host sides keep.
+// wave_ops.hpp -- what the record kernels (verify.hip, clip.hip, split.hip, normalize.hip) share on the device: the take of
+// the next record from the cursor, the chunk a wave reads (64 lanes x 16 op bytes), wave64 inclusive scans on the DPP network
+// and packed byte counting over a lane's 16 bytes; and the device buffer their host sides keep (record_pass.hpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,6 +9,30 @@
 #include <cstddef>
 
 namespace awvw {
+
+constexpr int LANE_BYTES = 16;
+constexpr int CHUNK = 64 * LANE_BYTES;  // the op bytes a wave takes per iteration, one aligned 16-byte load per lane
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// The next dispatch slot, uniform across the wave: lane 0 advances the 64-bit cursor counters[0].  A kernel's persistent
+// waves call it at the top of their loop and leave when the slot is npairs or more.
+__device__ __forceinline__ unsigned long long take_record(unsigned long long* counters, int lane) {
+  unsigned slot_lo = 0, slot_hi = 0;
+  if (lane == 0) {
+    const unsigned long long s = atomicAdd(&counters[0], 1ull);
+    slot_lo = (unsigned)s;
+    slot_hi = (unsigned)(s >> 32);
+  }
+  return (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)slot_lo) |
+         ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)slot_hi) << 32);
+}
+
+__device__ __forceinline__ long long wave_sum_i64(long long v) {  // in every lane
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
 
 template <int CTRL, int ROWS>
 __device__ __forceinline__ int dpp32(int ident, int v) {  // lanes without a source (or outside ROWS) get `ident`

@@ -216,6 +216,39 @@ def test_default_grid_takes_several_records_per_wave(hip_lib):
         e.close()
 
 
+def test_record_passes_share_their_checks(engines):
+    """What every record pass checks before anything goes up, through each pass's own entry point: three
+    20-column records back to back, the arena handed over one byte short of the last one."""
+    from allwave_amd import ffi
+    e = engines("NO_ARENA_PROBE")
+    seq = b"ACGTTGCAAC" * 2
+    e.set_sequences([seq] * 2)
+    pairs = [(0, 1, 0)] * 3
+    recs = np.zeros(3, dtype=ffi.RESULT_DTYPE)
+    recs["cigar_len"] = 20
+    recs["cigar_off"] = [0, 20, 40]
+    arena = b"M" * 59  # record 2 ends at byte 60
+    passes = {
+        "verify_cigars": (lambda r, n=3: e.verify_cigars(DEFAULT_2P, pairs[:n], r, arena)["code"], e.verify_stats, ffi.AWV_VF_SKIPPED),
+        "clip_cigars": (lambda r, n=3: e.clip_cigars(DEFAULT_2P, 1, r, arena)["code"], e.clip_stats, ffi.AWV_CL_SKIPPED),
+        "split_cigars": (lambda r, n=3: e.split_cigars(DEFAULT_2P, 1, 1, r, arena)[0]["code"], e.split_stats, ffi.AWV_CL_SKIPPED),
+        "normalize_cigars": (lambda r, n=3: e.normalize_cigars("left", pairs[:n], r, arena)[1]["code"], e.normalize_stats, ffi.AWV_NM_SKIPPED),
+    }
+    for name, (call, stats, skipped) in passes.items():
+        with pytest.raises(ffi.EngineError) as err:
+            call(recs)
+        msg = ffi.load().awv_last_error().decode()
+        assert err.value.code == ffi.AWV_ERR_ARG and msg.startswith(name + ":") and "outside the CIGAR arena" in msg, (name, err.value.code, msg)
+        put_off = recs.copy()
+        put_off["status"][2] = ffi.AWV_ST_CAPACITY
+        codes = call(put_off)
+        assert codes[2] == skipped and skipped not in codes[:2], (name, codes)
+        assert stats().pairs == 3, name
+        assert len(call(recs[:0], 0)) == 0, name
+        st = stats()
+        assert all(getattr(st, f) == 0 for f, _ in st._fields_), (name, [(f, getattr(st, f)) for f, _ in st._fields_])
+
+
 # ---- the align kernels --------------------------------------------------------------------------------------------------------
 
 FLAVOURS = {"one-wave": ("ONE_WAVE", "NO_TWIN"), "four-waves": ("FOUR_WAVES",), "one-wave-int32": ("ONE_WAVE", "FORCE_INT32"),
