@@ -351,72 +351,21 @@ void align_ranges(const std::vector<Sequence>& sequences, const std::vector<Alig
   if (verify_stats) *verify_stats = it.last_verify_stats();
 }
 
-void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
-                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
-                  awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
-                  BoundStats* bound_stats) {
-  AllPairIterator it = AllPairIterator::for_ranges(sequences, ranges, std::move(params));
-  it.with_devices(devices).with_verify(verify);
+void RunOptions::apply(AllPairIterator& it) const {
+  if (normalize != AWV_NORM_OFF) it.with_normalize(normalize);
   if (max_penalty) it.with_max_penalty(*max_penalty);
   if (max_divergence) it.with_max_divergence(*max_divergence);
-  it.for_each_with_callback(callback);
-  if (failures) *failures = it.verify_failures();
-  if (verify_stats) *verify_stats = it.last_verify_stats();
-  if (bound_stats) *bound_stats = it.last_bound_stats();
-}
-
-void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
-                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
-                  awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
-                  BoundStats* bound_stats, int clip_match_bonus, int64_t clip_min_score, ClipStats* clip_stats) {
-  AllPairIterator it = AllPairIterator::for_ranges(sequences, ranges, std::move(params));
-  it.with_devices(devices).with_verify(verify).with_clip(clip_match_bonus, clip_min_score);
-  if (max_penalty) it.with_max_penalty(*max_penalty);
-  if (max_divergence) it.with_max_divergence(*max_divergence);
-  it.for_each_with_callback(callback);
-  if (failures) *failures = it.verify_failures();
-  if (verify_stats) *verify_stats = it.last_verify_stats();
-  if (bound_stats) *bound_stats = it.last_bound_stats();
-  if (clip_stats) *clip_stats = it.last_clip_stats();
-}
-
-void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
-                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
-                  awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
-                  BoundStats* bound_stats, int clip_match_bonus, int64_t clip_min_score, ClipStats* clip_stats, int split_match_bonus,
-                  int64_t split_min_score, SplitStats* split_stats) {
-  AllPairIterator it = AllPairIterator::for_ranges(sequences, ranges, std::move(params));
-  it.with_devices(devices).with_verify(verify);
   if (clip_match_bonus != 0) it.with_clip(clip_match_bonus, clip_min_score);
   if (split_match_bonus != 0) it.with_split(split_match_bonus, split_min_score);
-  if (max_penalty) it.with_max_penalty(*max_penalty);
-  if (max_divergence) it.with_max_divergence(*max_divergence);
-  it.for_each_with_callback(callback);
-  if (failures) *failures = it.verify_failures();
-  if (verify_stats) *verify_stats = it.last_verify_stats();
-  if (bound_stats) *bound_stats = it.last_bound_stats();
-  if (clip_stats) *clip_stats = it.last_clip_stats();
-  if (split_stats) *split_stats = it.last_split_stats();
 }
 
 void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
-                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
-                  awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
-                  BoundStats* bound_stats, int clip_match_bonus, int64_t clip_min_score, ClipStats* clip_stats, int split_match_bonus,
-                  int64_t split_min_score, SplitStats* split_stats, int normalize, awv_norm_stats* normalize_stats) {
+                  const Callback& callback, const std::vector<int>& devices, bool verify, const RunOptions& options, RunReport* report) {
   AllPairIterator it = AllPairIterator::for_ranges(sequences, ranges, std::move(params));
-  it.with_devices(devices).with_verify(verify).with_normalize(normalize);
-  if (clip_match_bonus != 0) it.with_clip(clip_match_bonus, clip_min_score);
-  if (split_match_bonus != 0) it.with_split(split_match_bonus, split_min_score);
-  if (max_penalty) it.with_max_penalty(*max_penalty);
-  if (max_divergence) it.with_max_divergence(*max_divergence);
+  it.with_devices(devices).with_verify(verify);
+  options.apply(it);
   it.for_each_with_callback(callback);
-  if (failures) *failures = it.verify_failures();
-  if (verify_stats) *verify_stats = it.last_verify_stats();
-  if (bound_stats) *bound_stats = it.last_bound_stats();
-  if (clip_stats) *clip_stats = it.last_clip_stats();
-  if (split_stats) *split_stats = it.last_split_stats();
-  if (normalize_stats) *normalize_stats = it.last_normalize_stats();
+  if (report) *report = it.last_report();
 }
 
 AllPairIterator::AllPairIterator(const std::vector<Sequence>& sequences, AlignmentParams params)
@@ -618,41 +567,36 @@ AllPairIterator& AllPairIterator::with_next_chunk(size_t n) { next_chunk_ = std:
 AllPairIterator& AllPairIterator::with_threads(int t) { threads_ = t; return *this; }
 AllPairParallelIterator AllPairIterator::into_par_iter() const { return AllPairParallelIterator(*this); }
 
+std::vector<AlignmentResult> AllPairIterator::collect_ordered(size_t first, size_t cnt) {
+  std::vector<AlignmentResult> buf(cnt);
+  std::vector<uint8_t> have(cnt, 0);  // (a pair the run drops is not delivered: its slot stays empty and is skipped)
+  std::vector<std::vector<AlignmentResult>> more(split() ? cnt : 0);  // a splitting run: a pair's segments after its first
+  run(first, cnt, [&](const Batch& b) {  // (every pair has its own slot of buf: no lock)
+    for (int64_t i = 0; i < b.n; ++i) {
+      const size_t k = b.pair(i);
+      AlignmentResult a = result_at(first + k, b.is_rev(i), b.res[i], b.arena, true, b.clip_at(i));
+      if (have[k]) more[k].push_back(std::move(a));
+      else buf[k] = std::move(a);
+      have[k] = 1;
+    }
+  });
+  if (!drops_pairs()) return buf;
+  std::vector<AlignmentResult> kept;  // the delivered pairs in pair-list order, each pair's segments in column order
+  for (size_t k = 0; k < cnt; ++k) {
+    if (!have[k]) continue;
+    kept.push_back(std::move(buf[k]));
+    if (split())
+      for (auto& a : more[k]) kept.push_back(std::move(a));
+  }
+  return kept;
+}
+
 std::optional<AlignmentResult> AllPairIterator::next() {  // iterator.rs:151-171
   if (next_buf_pos_ >= next_buf_.size()) {
     if (next_pos_ >= pairs_.size()) return std::nullopt;
-    const size_t first = next_pos_, cnt = std::min(next_chunk_, pairs_.size() - first);
-    std::vector<AlignmentResult> buf(cnt);
-    std::vector<uint8_t> have(cnt, 0);  // (a pair above a bound is not delivered: its slot stays empty and is skipped)
-    std::vector<std::vector<AlignmentResult>> more(split() ? cnt : 0);  // a splitting run: a pair's segments after its first
-    run(first, cnt, [&](const Batch& b) {  // (every entry has its own slot of buf: no lock)
-      for (int64_t i = 0; i < b.n; ++i) {
-        const size_t k = b.pair(i);
-        AlignmentResult a = result_at(first + k, b.is_rev(i), b.res[i], b.arena, true, b.clip_at(i));
-        if (have[k]) more[k].push_back(std::move(a));
-        else buf[k] = std::move(a);
-        have[k] = 1;
-      }
-    });
-    if (split()) {  // the pairs' segments in pair order, each pair's in column order
-      std::vector<AlignmentResult> flat;
-      for (size_t k = 0; k < cnt; ++k) {
-        if (!have[k]) continue;
-        flat.push_back(std::move(buf[k]));
-        for (auto& a : more[k]) flat.push_back(std::move(a));
-      }
-      buf = std::move(flat);
-    } else if (drops_pairs()) {
-      size_t w = 0;
-      for (size_t k = 0; k < cnt; ++k)
-        if (have[k]) {
-          if (w != k) buf[w] = std::move(buf[k]);
-          ++w;
-        }
-      buf.resize(w);
-    }
+    const size_t cnt = std::min(next_chunk_, pairs_.size() - next_pos_);
     // (only a run that returned moves the position on: after an error the next call runs the same chunk again)
-    next_buf_ = std::move(buf);
+    next_buf_ = collect_ordered(next_pos_, cnt);
     next_buf_pos_ = 0;
     next_pos_ += cnt;
     if (next_buf_.empty()) return next();  // (a chunk of dropped pairs only: on to the next one)
@@ -695,38 +639,7 @@ void AllPairParallelIterator::for_each_with_callback(const Callback& cb) {
   });
 }
 
-std::vector<AlignmentResult> AllPairParallelIterator::collect() {
-  std::vector<AlignmentResult> out(it_.pairs_.size());
-  std::vector<uint8_t> have(it_.pairs_.size(), 0);
-  std::vector<std::vector<AlignmentResult>> more(it_.split() ? it_.pairs_.size() : 0);  // a splitting run: a pair's segments after its first
-  it_.run([&](const AllPairIterator::Batch& b) {  // (every pair has its own slot of `out`: no lock)
-    for (int64_t i = 0; i < b.n; ++i) {
-      const size_t k = b.pair(i);
-      AlignmentResult a = it_.result_at(k, b.is_rev(i), b.res[i], b.arena, true, b.clip_at(i));
-      if (have[k]) more[k].push_back(std::move(a));
-      else out[k] = std::move(a);
-      have[k] = 1;
-    }
-  });
-  if (it_.split()) {  // the pairs' segments in pair order, each pair's in column order
-    std::vector<AlignmentResult> flat;
-    for (size_t k = 0; k < out.size(); ++k) {
-      if (!have[k]) continue;
-      flat.push_back(std::move(out[k]));
-      for (auto& a : more[k]) flat.push_back(std::move(a));
-    }
-    out = std::move(flat);
-  } else if (it_.drops_pairs()) {  // (pairs above a bound or without a clip are not delivered: the kept ones, in pair-list order)
-    size_t w = 0;
-    for (size_t k = 0; k < out.size(); ++k)
-      if (have[k]) {
-        if (w != k) out[w] = std::move(out[k]);
-        ++w;
-      }
-    out.resize(w);
-  }
-  return out;
-}
+std::vector<AlignmentResult> AllPairParallelIterator::collect() { return it_.collect_ordered(0, it_.pairs_.size()); }
 
 void process_alignments_with_callback(const std::vector<Sequence>& sequences, AlignmentParams params,
                                       SparsificationStrategy sparsification, const Callback& callback) {  // lib.rs:57-68
@@ -778,38 +691,91 @@ void add_stats(awv_stats& acc, const awv_stats& x, bool same_engine) {
   acc.deep_cell_steps += x.deep_cell_steps;
 }
 
-// one batch's engine call: awv_align_pairs (awv_align_pairs_verified when `vout` is given), or awv_score_pairs under
-// max_penalty (< 0: no bound) with its results handed to the sink in one call (status and penalty, no arena)
-// rp (nullable): the batch is these n interval pairs -- the same three calls on ranges, `ap` is not read
-// bounds (nullable, alignment calls only): one penalty bound per entry (< 0: none) -- the *_bounded entry points
-// cout (nullable, alignment calls only): the *_clipped entry points under clip_bonus, which take bounds and vout as well
-// sp (nullable, alignment calls only): the *_split entry points, likewise, into the call's own segment storage
-struct SplitCall {
-  int bonus;
-  int64_t min_score;
-  const uint64_t* seg_first;
-  awv_split_index* index;
-  awv_clip_result* seg;
+// the other counters of a run, one sum per kind
+void add(awv_verify_stats& acc, const awv_verify_stats& x) {
+  acc.kernel_ms += x.kernel_ms;
+  acc.pairs += x.pairs;
+  acc.failed += x.failed;
+  acc.columns += x.columns;
+}
+void add(BoundStats& acc, const BoundStats& x) {
+  acc.pairs += x.pairs;
+  acc.above_penalty += x.above_penalty;
+  acc.above_divergence += x.above_divergence;
+}
+void add(ClipStats& acc, const ClipStats& x) {
+  acc.pairs += x.pairs;
+  acc.empty += x.empty;
+  acc.below_min_score += x.below_min_score;
+  acc.kernel_ms += x.kernel_ms;
+}
+void add(SplitStats& acc, const SplitStats& x) {
+  acc.pairs += x.pairs;
+  acc.segments += x.segments;
+  acc.empty += x.empty;
+  acc.kernel_ms += x.kernel_ms;
+}
+void add(awv_norm_stats& acc, const awv_norm_stats& x) {
+  acc.kernel_ms += x.kernel_ms;
+  acc.pairs += x.pairs;
+  acc.records_moved += x.records_moved;
+  acc.runs += x.runs;
+  acc.runs_moved += x.runs_moved;
+  acc.columns_moved += x.columns_moved;
+  acc.columns += x.columns;
+}
+void add(RunReport& acc, const RunReport& x) {
+  acc.verify_failures.insert(acc.verify_failures.end(), x.verify_failures.begin(), x.verify_failures.end());
+  add(acc.verify_stats, x.verify_stats);
+  add(acc.bound_stats, x.bound_stats);
+  add(acc.clip_stats, x.clip_stats);
+  add(acc.split_stats, x.split_stats);
+  add(acc.normalize_stats, x.normalize_stats);
+}
+
+// One batch's engine call, by name.  ranges (nullable): the batch is these n interval pairs, `pairs` is not read.  Alignment
+// calls only: verify (nullable), bounds (nullable: one penalty bound per entry, < 0: none), clip (nullable: the clips, under
+// clip_bonus), seg_first (nullable: the split under split_bonus / split_min_score, into index and seg).
+struct EngineRequest {
+  bool score_only = false;
+  int32_t max_penalty = -1;  // the score call's bound (< 0: none)
+  const awv_penalties* pen = nullptr;
+  const awv_pair* pairs = nullptr;
+  const awv_range_pair* ranges = nullptr;
+  int64_t n = 0;
+  awv_verify_result* verify = nullptr;
+  const int32_t* bounds = nullptr;
+  int clip_bonus = 0;
+  awv_clip_result* clip = nullptr;
+  int split_bonus = 0;
+  int64_t split_min_score = 1;
+  const uint64_t* seg_first = nullptr;
+  awv_split_index* index = nullptr;
+  awv_clip_result* seg = nullptr;
 };
-int engine_call(awv_engine* e, bool score_only, int32_t max_penalty, const awv_penalties& pen, const awv_pair* ap, int64_t n,
-                awv_sink sink, void* user, awv_verify_result* vout, const awv_range_pair* rp = nullptr, const int32_t* align_bounds = nullptr,
-                int clip_bonus = 0, awv_clip_result* cout = nullptr, const SplitCall* sp = nullptr) {
-  if (sp && !score_only)
-    return rp ? awv_align_ranges_split(e, &pen, rp, n, align_bounds, sp->bonus, sp->min_score, nullptr, vout, sp->seg_first, sp->index, sp->seg, sink, user)
-              : awv_align_pairs_split(e, &pen, ap, n, align_bounds, sp->bonus, sp->min_score, nullptr, vout, sp->seg_first, sp->index, sp->seg, sink, user);
-  if (cout && !score_only)
-    return rp ? awv_align_ranges_clipped(e, &pen, rp, n, align_bounds, clip_bonus, nullptr, vout, cout, sink, user)
-              : awv_align_pairs_clipped(e, &pen, ap, n, align_bounds, clip_bonus, nullptr, vout, cout, sink, user);
-  if (align_bounds && !score_only)
-    return rp ? awv_align_ranges_bounded(e, &pen, rp, n, align_bounds, nullptr, vout, sink, user)
-              : awv_align_pairs_bounded(e, &pen, ap, n, align_bounds, nullptr, vout, sink, user);
-  if (rp && !score_only) return vout ? awv_align_ranges_verified(e, &pen, rp, n, nullptr, vout, sink, user) : awv_align_ranges(e, &pen, rp, n, nullptr, sink, user);
-  if (!score_only && vout) return awv_align_pairs_verified(e, &pen, ap, n, nullptr, vout, sink, user);
-  if (!score_only) return awv_align_pairs(e, &pen, ap, n, nullptr, sink, user);
+
+// The entry point a request names: the split, else the clip, else the bounded call, else the verified or the plain one, each
+// on pairs or on ranges (they differ in which engine counters they reset); or awv_score_pairs / awv_score_ranges with the
+// results handed to the sink in one call (status and penalty, no arena).
+int engine_call(awv_engine* e, const EngineRequest& q, awv_sink sink, void* user) {
+  const awv_penalties* pen = q.pen;
+  const int64_t n = q.n;
+  if (q.seg_first && !q.score_only)
+    return q.ranges ? awv_align_ranges_split(e, pen, q.ranges, n, q.bounds, q.split_bonus, q.split_min_score, nullptr, q.verify, q.seg_first, q.index, q.seg, sink, user)
+                    : awv_align_pairs_split(e, pen, q.pairs, n, q.bounds, q.split_bonus, q.split_min_score, nullptr, q.verify, q.seg_first, q.index, q.seg, sink, user);
+  if (q.clip && !q.score_only)
+    return q.ranges ? awv_align_ranges_clipped(e, pen, q.ranges, n, q.bounds, q.clip_bonus, nullptr, q.verify, q.clip, sink, user)
+                    : awv_align_pairs_clipped(e, pen, q.pairs, n, q.bounds, q.clip_bonus, nullptr, q.verify, q.clip, sink, user);
+  if (q.bounds && !q.score_only)
+    return q.ranges ? awv_align_ranges_bounded(e, pen, q.ranges, n, q.bounds, nullptr, q.verify, sink, user)
+                    : awv_align_pairs_bounded(e, pen, q.pairs, n, q.bounds, nullptr, q.verify, sink, user);
+  if (q.ranges && !q.score_only) return q.verify ? awv_align_ranges_verified(e, pen, q.ranges, n, nullptr, q.verify, sink, user) : awv_align_ranges(e, pen, q.ranges, n, nullptr, sink, user);
+  if (!q.score_only && q.verify) return awv_align_pairs_verified(e, pen, q.pairs, n, nullptr, q.verify, sink, user);
+  if (!q.score_only) return awv_align_pairs(e, pen, q.pairs, n, nullptr, sink, user);
   std::vector<awv_score_result> sr((size_t)n);
-  std::vector<int32_t> bounds(rp && max_penalty >= 0 ? (size_t)n : 0, max_penalty);
-  const int rc = rp ? awv_score_ranges(e, &pen, rp, n, bounds.empty() ? nullptr : bounds.data(), sr.data())
-                    : awv_score_pairs(e, &pen, ap, n, max_penalty, sr.data());
+  std::vector<int32_t> bounds(q.ranges && q.max_penalty >= 0 ? (size_t)n : 0, q.max_penalty);
+  const int rc = q.ranges ? awv_score_ranges(e, pen, q.ranges, n, bounds.empty() ? nullptr : bounds.data(), sr.data())
+                          : awv_score_pairs(e, pen, q.pairs, n, q.max_penalty, sr.data());
   if (rc != AWV_OK || n == 0) return rc;
   std::vector<awv_result> res((size_t)n);
   for (int64_t i = 0; i < n; ++i) {
@@ -821,6 +787,198 @@ int engine_call(awv_engine* e, bool score_only, int32_t max_penalty, const awv_p
 }
 }  // namespace
 
+// What one slot of a run counts: written by its submitter thread and its sink calls (which never overlap) only.
+struct AllPairIterator::SlotTotals {
+  awv_stats engine{};
+  RunReport report;
+};
+
+// What the slots of one run share.  The settings hold for alignment calls only: a score-only run has none of them.
+struct AllPairIterator::RunState {
+  size_t first = 0, count = 0;
+  const std::pair<size_t, size_t>* plist = nullptr;  // pairs_.data() + first
+  const BatchCb* batch_cb = nullptr;
+  EngineCall call{false, -1};
+  std::vector<std::vector<size_t>> batches;  // pair indices (relative to `first`) of each batch; one slot's single batch: empty, the whole range
+  std::vector<uint8_t> mash_rev;             // mash orientation of the whole range, computed up front
+  bool verify = false, bounded = false, clipping = false, splitting = false;
+  int normalizing = AWV_NORM_OFF;
+  std::optional<double> div;  // the divergence bound of a bounded run
+  awv_penalties pen{}, open{};
+  std::vector<SlotTotals> totals;
+  // the first error -- an engine's or a batch callback's -- wins: every slot takes no new batch and stops at its next sink call
+  std::mutex mu;  // guards err (and run()'s start barrier)
+  std::exception_ptr err;
+  std::atomic<bool> stop{false};
+  void fail(std::exception_ptr e) {
+    std::lock_guard<std::mutex> g(mu);
+    if (!err) err = e;
+    stop.store(true);
+  }
+  bool timing = false;  // diagnostic (AWH_TIMING): a one-slot run's stage times on stderr
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  void lap(const char* what) const {
+    if (timing) fprintf(stderr, "[awh] %-18s %.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  }
+};
+
+// One batch made ready for its engine call: the arrays the call reads and writes, which this object owns, the request that
+// names them and the delivery rule over them (delivery.hpp).
+struct AllPairIterator::PreparedBatch {
+  const size_t* idx = nullptr;  // pair-list index (relative to the run's range) per entry; nullptr: the entry's own position
+  int64_t m = 0;
+  std::vector<awv_pair> ap;
+  std::vector<uint8_t> rev;
+  std::vector<awv_range_pair> rp;
+  std::vector<int32_t> bounds;  // one penalty bound per entry: the smaller of with_max_penalty's and the one the divergence bound implies
+  std::vector<uint8_t> by_div;
+  std::vector<awv_verify_result> vr;
+  std::vector<awv_clip_result> cr;
+  // a splitting run: this call's segment storage, laid out by the engine's own arithmetic over the resident lengths
+  std::vector<uint64_t> seg_first;
+  std::vector<awv_split_index> six;
+  std::vector<awv_clip_result> sseg;
+  EngineRequest request;
+  Delivery delivery;
+};
+
+AllPairIterator::PreparedBatch AllPairIterator::prepare_batch(const RunState& rs, awv_engine* e, size_t b, SlotTotals& totals) const {
+  PreparedBatch pb;
+  const bool whole = devices_.size() == 1;  // one slot: one batch, the whole range in list order
+  const size_t* idx = pb.idx = whole ? nullptr : rs.batches[b].data();
+  const int64_t m = pb.m = (int64_t)(whole ? rs.count : rs.batches[b].size());
+  auto at = [&](int64_t i) { return idx ? idx[i] : (size_t)i; };
+  pb.ap.resize((size_t)m);
+  pb.rev.assign((size_t)m, 0);
+  for (int64_t i = 0; i < m; ++i) pb.ap[i] = awv_pair{(int32_t)rs.plist[at(i)].first, (int32_t)rs.plist[at(i)].second, 0};
+  if (ranges_) {
+    pb.rp.resize((size_t)m);
+    for (int64_t i = 0; i < m; ++i) {
+      const AlignmentRange& g = (*ranges_)[rs.first + at(i)];
+      pb.rev[i] = g.is_reverse ? 1 : 0;
+      pb.rp[i] = awv_range_pair{pb.ap[i].q_idx, pb.ap[i].t_idx, pb.rev[i], (int32_t)g.query_start, (int32_t)g.query_end, (int32_t)g.target_start, (int32_t)g.target_end};
+    }
+  } else if (orientation_ == Orientation::Mash) {
+    for (int64_t i = 0; i < m; ++i) pb.rev[i] = rs.mash_rev[at(i)];
+  } else if (orientation_ == Orientation::Wfa) {
+    orient_wfa(e, rs.open, pb.ap.data(), m, full_wfa_orientation_, pb.rev.data());
+  }
+  for (int64_t i = 0; i < m; ++i) pb.ap[i].q_revcomp = pb.rev[i];
+  rs.lap("pairs oriented");
+  EngineRequest& q = pb.request;
+  Delivery& d = pb.delivery;
+  q.score_only = rs.call.score_only;
+  q.max_penalty = rs.call.max_penalty;
+  q.pen = &rs.pen;
+  q.pairs = pb.ap.data();
+  q.ranges = ranges_ ? pb.rp.data() : nullptr;
+  q.n = m;
+  d.rev = pb.rev.data();
+  d.idx = idx;
+  if (rs.bounded) {
+    pb.bounds.assign((size_t)m, max_penalty_ ? (int32_t)*max_penalty_ : -1);
+    pb.by_div.assign((size_t)m, 0);
+    for (int64_t i = 0; rs.div && i < m; ++i) {
+      const int32_t ql = ranges_ ? pb.rp[i].q_end - pb.rp[i].q_beg : (int32_t)sequences_[rs.plist[at(i)].first].seq.size();
+      const int32_t tl = ranges_ ? pb.rp[i].t_end - pb.rp[i].t_beg : (int32_t)sequences_[rs.plist[at(i)].second].seq.size();
+      const int32_t db = awv_divergence_bound(&rs.pen, ql, tl, *rs.div);
+      if (db == INT32_MIN) throw AlignmentError(std::string("max_divergence: ") + awv_last_error());
+      if (db >= 0 && (pb.bounds[(size_t)i] < 0 || db < pb.bounds[(size_t)i])) {
+        pb.bounds[(size_t)i] = db;
+        pb.by_div[(size_t)i] = 1;
+      }
+    }
+    q.bounds = pb.bounds.data();
+    d.by_div = pb.by_div.data();
+    d.div = rs.div ? *rs.div : -1.0;
+    d.bounds = &totals.report.bound_stats;
+    d.bounds->pairs += (uint64_t)m;
+  }
+  if (rs.verify) {
+    pb.vr.resize((size_t)m);
+    q.verify = pb.vr.data();
+  }
+  if (rs.clipping) {
+    pb.cr.resize((size_t)std::max<int64_t>(m, 1));
+    q.clip_bonus = clip_bonus_;
+    q.clip = pb.cr.data();
+    d.clip = pb.cr.data();
+    d.min_score = clip_min_score_;
+    d.clips = &totals.report.clip_stats;
+  }
+  if (rs.splitting) {
+    pb.seg_first.resize((size_t)m + 1);
+    pb.six.resize((size_t)std::max<int64_t>(m, 1));
+    const int lrc = ranges_ ? awv_split_layout_ranges(e, pb.rp.data(), m, split_bonus_, split_min_score_, pb.seg_first.data())
+                            : awv_split_layout_pairs(e, pb.ap.data(), m, split_bonus_, split_min_score_, pb.seg_first.data());
+    if (lrc != AWV_OK) throw AlignmentError(std::string("split layout: ") + awv_last_error());
+    pb.sseg.resize((size_t)std::max<uint64_t>(pb.seg_first[(size_t)m], 1));
+    q.split_bonus = split_bonus_;
+    q.split_min_score = split_min_score_;
+    q.seg_first = d.seg_first = pb.seg_first.data();
+    q.index = pb.six.data();
+    d.index = pb.six.data();
+    q.seg = pb.sseg.data();
+    d.seg = pb.sseg.data();
+    d.splits = &totals.report.split_stats;
+  }
+  return pb;
+}
+
+// The engine's sink of every alignment and score call of a run: the batch callback sees the call's entries as they are --
+// no copy, no per-entry vector -- or, in a run that filters, the ones delivery.hpp's rule keeps.
+struct AllPairIterator::SinkCtx {
+  RunState* rs;
+  const Delivery* d;
+  bool failed;
+};
+int AllPairIterator::batch_sink(void* user, int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena) {
+  SinkCtx* c = (SinkCtx*)user;
+  if (c->rs->stop.load()) return 1;  // another slot failed: stop here, report nothing
+  try {
+    if (c->d->filters()) {
+      const Delivered k = deliver(*c->d, first, cnt, res);
+      (*c->rs->batch_cb)(Batch{0, (int64_t)k.res.size(), k.res.data(), arena, k.rev.data(), k.idx.data(), k.clip.empty() ? nullptr : k.clip.data()});
+    } else {
+      (*c->rs->batch_cb)(Batch{first, cnt, res, arena, c->d->rev, c->d->idx});
+    }
+  } catch (...) {
+    c->rs->fail(std::current_exception());  // recorded now, and every slot stops at its next sink call
+    c->failed = true;
+    return 1;
+  }
+  return 0;
+}
+
+// What a slot's totals take from its engine after one call: awv_engine_stats always, the kernel times and the verify
+// failures only from a call that returned AWV_OK.
+void AllPairIterator::take_call_totals(const RunState& rs, const PreparedBatch& pb, awv_engine* e, bool ok, SlotTotals& t) {
+  if (rs.normalizing != AWV_NORM_OFF && ok) {
+    awv_norm_stats nx{};
+    awv_engine_normalize_stats(e, &nx);
+    add(t.report.normalize_stats, nx);
+  }
+  awv_stats x{};
+  awv_engine_stats(e, &x);
+  add_stats(t.engine, x, true);
+  if (rs.verify && ok) {
+    awv_verify_stats vx{};
+    awv_engine_verify_stats(e, &vx);
+    add(t.report.verify_stats, vx);
+    append_verify_failures(t.report.verify_failures, pb.vr.data(), pb.m, rs.first, pb.idx, rs.plist, pb.rev.data());
+  }
+  if (rs.clipping && ok) {
+    awv_clip_stats cx{};
+    awv_engine_clip_stats(e, &cx);
+    t.report.clip_stats.kernel_ms += cx.kernel_ms;
+  }
+  if (rs.splitting && ok) {
+    awv_split_stats sx{};
+    awv_engine_split_stats(e, &sx);
+    t.report.split_stats.kernel_ms += sx.kernel_ms;
+  }
+}
+
 // The run's pairs go to its slots in batches.  One slot: one batch, the whole range in list order, on the calling thread.
 // Several slots: planner::device_batches over the predicted costs, one submitter thread per slot.  Every slot creates its
 // engine and uploads the sequences; only when all have done so (a failure there ends the run before any launch) does slot
@@ -830,24 +988,20 @@ int engine_call(awv_engine* e, bool score_only, int32_t max_penalty, const awv_p
 // call; it is rethrown here once every thread has ended.
 void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, EngineCall call) {
   if (first > pairs_.size() || count > pairs_.size() - first) throw AlignmentError("pair range out of bounds");
-  const std::pair<size_t, size_t>* plist = pairs_.data() + first;
   const size_t S = devices_.size();
+  RunState rs;
+  rs.first = first;
+  rs.count = count;
+  rs.plist = pairs_.data() + first;
+  rs.batch_cb = &batch_cb;
+  rs.call = call;
 #ifdef AWV_DEBUG_KNOBS
-  const bool timing = S == 1 && getenv("AWH_TIMING") != nullptr;  // diagnostic: a one-slot run's stage times on stderr
-#else
-  const bool timing = false;
+  rs.timing = S == 1 && getenv("AWH_TIMING") != nullptr;
 #endif
-  const auto tr0 = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (timing) fprintf(stderr, "[awh] %-18s %.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count());
-  };
-  // pair indices (relative to `first`) of each batch; one slot's single batch needs none (Batch::idx == nullptr)
-  const std::vector<std::vector<size_t>> batches =
-      S > 1 ? planner::device_batches(pair_costs(sequences_, plist, count, params_, ranges_ ? ranges_->data() + first : nullptr), S, min_batch_pairs_)
-            : std::vector<std::vector<size_t>>(1);
-  std::vector<uint8_t> mash_rev;
+  rs.batches = S > 1 ? planner::device_batches(pair_costs(sequences_, rs.plist, count, params_, ranges_ ? ranges_->data() + first : nullptr), S, min_batch_pairs_)
+                     : std::vector<std::vector<size_t>>(1);
   if (orientation_ == Orientation::Mash && !ranges_)  // alignment.rs:69-94 (host threads: the CLI's -t)
-    mash_rev = planner::orient_pairs_mash(sequences_, plist, count, threads_ > 0 ? threads_ : planner::host_threads(), plan_device_);
+    rs.mash_rev = planner::orient_pairs_mash(sequences_, rs.plist, count, threads_ > 0 ? threads_ : planner::host_threads(), plan_device_);
   // slot number of every entry on its device, and how many slots each device has in this run
   std::map<int, int> per_device;
   std::vector<int> slot_no(S);
@@ -859,333 +1013,78 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   std::vector<std::unique_lock<std::mutex>> locks;
   for (const auto& o : order) locks.emplace_back(*slot_mutex(o.first.first, o.first.second));
 
-  std::mutex mu;  // guards err and the start barrier
-  std::condition_variable cv;
+  rs.verify = verify_ && !call.score_only;
+  rs.bounded = bounded() && !call.score_only;
+  rs.clipping = clip() && !call.score_only;
+  rs.splitting = split() && !call.score_only;
+  rs.normalizing = call.score_only ? AWV_NORM_OFF : normalize_;
+  rs.div = divergence_bound();
+  rs.pen = to_penalties(params_);
+  rs.open = to_penalties(orientation_params_);
+  if (rs.bounded && rs.div && !(*rs.div >= 0.0 && *rs.div < 1.0)) throw std::invalid_argument("max_divergence: need 0 <= max_divergence < 1");
+  rs.totals.resize(S);
+  std::condition_variable cv;  // the start barrier, under rs.mu
   size_t ready = 0;
   bool aborted = false;  // a submitter thread could not be started: nobody waits for the whole set at the barrier
-  std::exception_ptr err;
-  std::atomic<bool> stop{false};
   std::atomic<size_t> cursor{S};
-  auto fail = [&](std::exception_ptr e) {
-    std::lock_guard<std::mutex> g(mu);
-    if (!err) err = e;
-    stop.store(true);
-  };
-  const std::function<void(std::exception_ptr)> fail_fn = fail;
-  std::vector<awv_stats> st(S, awv_stats{});
-  const bool verify = verify_ && !call.score_only;
-  std::vector<awv_verify_stats> vst(S, awv_verify_stats{});  // per slot: written by its submitter thread only
-  std::vector<std::vector<VerifyFailure>> vfail(S);
-  const awv_penalties pen = to_penalties(params_), open = to_penalties(orientation_params_);
-  // bounds on the final alignments (with_max_penalty / with_max_divergence): per batch one penalty bound per entry, and the
-  // pairs above a bound taken out of what the batch callback sees
-  const bool bounded_run = bounded() && !call.score_only;
-  const std::optional<double> div = divergence_bound();
-  if (bounded_run && div && !(*div >= 0.0 && *div < 1.0)) throw std::invalid_argument("max_divergence: need 0 <= max_divergence < 1");
-  std::vector<BoundStats> bst(S);  // per slot: written by its sink calls (which never overlap) and its submitter thread
-  const bool clipping = clip() && !call.score_only;
-  std::vector<ClipStats> cst(S);   // likewise
-  const bool splitting = split() && !call.score_only;
-  std::vector<SplitStats> sst(S);  // likewise
-  const int normalizing = call.score_only ? AWV_NORM_OFF : normalize_;
-  std::vector<awv_norm_stats> nst(S, awv_norm_stats{});  // per slot: written by its submitter thread only
   auto worker = [&](size_t s) {
     awv_engine* e = nullptr;
     try {
       e = slot_engine(devices_[s], slot_no[s], per_device.at(devices_[s]));
-      lap("engine created");
+      rs.lap("engine created");
       upload(e, sequences_);
-      lap("sequences uploaded");
+      rs.lap("sequences uploaded");
     } catch (...) {
-      fail(std::current_exception());
+      rs.fail(std::current_exception());
     }
     {
-      std::unique_lock<std::mutex> g(mu);
+      std::unique_lock<std::mutex> g(rs.mu);
       if (++ready == S) cv.notify_all();
       else cv.wait(g, [&] { return ready == S || aborted; });
     }
-    if (stop.load()) return;
+    if (rs.stop.load()) return;
     try {
-      for (size_t b = s; b < batches.size() && !stop.load(); b = cursor.fetch_add(1)) {
-        const size_t* idx = S > 1 ? batches[b].data() : nullptr;
-        const int64_t m = (int64_t)(S > 1 ? batches[b].size() : count);
-        auto at = [&](int64_t i) { return idx ? idx[i] : (size_t)i; };
-        std::vector<awv_pair> ap((size_t)m);
-        std::vector<uint8_t> rev((size_t)m, 0);
-        for (int64_t i = 0; i < m; ++i) ap[i] = awv_pair{(int32_t)plist[at(i)].first, (int32_t)plist[at(i)].second, 0};
-        std::vector<awv_range_pair> rp(ranges_ ? (size_t)m : 0);
-        if (ranges_) {
-          for (int64_t i = 0; i < m; ++i) {
-            const AlignmentRange& g = (*ranges_)[first + at(i)];
-            rev[i] = g.is_reverse ? 1 : 0;
-            rp[i] = awv_range_pair{ap[i].q_idx, ap[i].t_idx, rev[i], (int32_t)g.query_start, (int32_t)g.query_end, (int32_t)g.target_start, (int32_t)g.target_end};
-          }
-        } else if (orientation_ == Orientation::Mash) {
-          for (int64_t i = 0; i < m; ++i) rev[i] = mash_rev[at(i)];
-        } else if (orientation_ == Orientation::Wfa) {
-          orient_wfa(e, open, ap.data(), m, full_wfa_orientation_, rev.data());
-        }
-        for (int64_t i = 0; i < m; ++i) ap[i].q_revcomp = rev[i];
-        lap("pairs oriented");
-        struct Ctx {
-          const BatchCb* cb;
-          const uint8_t* rev;
-          const size_t* idx;
-          std::atomic<bool>* stop;
-          const std::function<void(std::exception_ptr)>* fail;
-          bool failed;
-          const uint8_t* by_div;  // bounded runs: per entry, whether its penalty bound is the one derived from the divergence
-          double div;             // the divergence bound (< 0: none)
-          BoundStats* bst;
-          const awv_clip_result* clip;  // clipping runs: per entry of the call, filled before the entry's sink call
-          int64_t clip_min_score;
-          ClipStats* cst;
-          const SplitCall* sp;  // splitting runs: the call's layout, index and segments, filled before the entry's sink call
-          SplitStats* sst;
-        } ctx{&batch_cb, rev.data(), idx, &stop, &fail_fn, false, nullptr, -1.0, nullptr, nullptr, 1, nullptr, nullptr, nullptr};
-        // one penalty bound per entry: the smaller of with_max_penalty's and the one the divergence bound implies
-        std::vector<int32_t> bounds;
-        std::vector<uint8_t> by_div;
-        if (bounded_run) {
-          bounds.assign((size_t)m, max_penalty_ ? (int32_t)*max_penalty_ : -1);
-          by_div.assign((size_t)m, 0);
-          if (div) {
-            for (int64_t i = 0; i < m; ++i) {
-              const int32_t ql = ranges_ ? rp[i].q_end - rp[i].q_beg : (int32_t)sequences_[plist[at(i)].first].seq.size();
-              const int32_t tl = ranges_ ? rp[i].t_end - rp[i].t_beg : (int32_t)sequences_[plist[at(i)].second].seq.size();
-              const int32_t db = awv_divergence_bound(&pen, ql, tl, *div);
-              if (db == INT32_MIN) throw AlignmentError(std::string("max_divergence: ") + awv_last_error());
-              if (db >= 0 && (bounds[(size_t)i] < 0 || db < bounds[(size_t)i])) {
-                bounds[(size_t)i] = db;
-                by_div[(size_t)i] = 1;
-              }
-            }
-          }
-          ctx.by_div = by_div.data();
-          ctx.div = div ? *div : -1.0;
-          ctx.bst = &bst[s];
-          bst[s].pairs += (uint64_t)m;
-        }
-        auto sink = [](void* user, int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena) -> int {
-          Ctx* c = (Ctx*)user;
-          if (c->stop->load()) return 1;  // another slot failed: stop here, report nothing
-          try {
-            if (c->bst || c->clip || c->sp) {  // a bounded, clipping or splitting run: the batch callback sees the kept entries only
-              std::vector<awv_result> kres;
-              std::vector<uint8_t> krev;
-              std::vector<size_t> kidx;
-              std::vector<awv_clip_result> kclip;
-              for (int64_t i = 0; i < cnt; ++i) {
-                const awv_result& r = res[i];
-                if (c->bst && r.status == AWV_ST_ABOVE_BOUND) {
-                  ++(c->by_div[first + i] ? c->bst->above_divergence : c->bst->above_penalty);
-                  continue;
-                }
-                if (c->bst && r.status == AWV_ST_COMPLETED && c->div >= 0.0) {  // the exact filter, on the record's counts
-                  const double edits = (double)r.num_mismatches + (double)r.num_ins + (double)r.num_del;
-                  if (!(edits <= c->div * (edits + (double)r.num_matches))) {
-                    ++c->bst->above_divergence;
-                    continue;
-                  }
-                }
-                if (c->sp) {  // a finished pair is delivered as its segments, one entry each (a failed one as it is)
-                  const awv_split_index& ix = c->sp->index[first + i];
-                  if (r.status == AWV_ST_COMPLETED) {
-                    ++c->sst->pairs;
-                    if (ix.code != AWV_CL_OK) {
-                      ++c->sst->empty;
-                      continue;
-                    }
-                    c->sst->segments += (uint64_t)ix.count;
-                  }
-                  const int32_t cnt_seg = r.status == AWV_ST_COMPLETED ? ix.count : 1;
-                  for (int32_t j = 0; j < cnt_seg; ++j) {
-                    kres.push_back(r);
-                    awv_clip_result cl{};
-                    cl.code = AWV_CL_SKIPPED;
-                    if (r.status == AWV_ST_COMPLETED) {
-                      cl = c->sp->seg[c->sp->seg_first[first + i] + (uint64_t)j];
-                      awv_result& s = kres.back();
-                      s.cigar_off += cl.col_beg;
-                      s.cigar_len = cl.col_end - cl.col_beg;
-                      s.num_matches = cl.num_matches;
-                      s.num_mismatches = cl.num_mismatches;
-                      s.num_ins = cl.num_ins;
-                      s.num_del = cl.num_del;
-                      s.penalty = cl.penalty;
-                      s.score = -cl.penalty;
-                      s.q_end = cl.num_matches + cl.num_mismatches + cl.num_del;
-                      s.t_end = cl.num_matches + cl.num_mismatches + cl.num_ins;
-                    }
-                    kclip.push_back(cl);
-                    krev.push_back(c->rev[first + i]);
-                    kidx.push_back(c->idx ? c->idx[first + i] : (size_t)(first + i));
-                  }
-                  continue;
-                }
-                kres.push_back(r);
-                if (c->clip) {  // a finished pair is delivered as its segment (a failed one as it is: the "empty" result)
-                  const awv_clip_result& cl = c->clip[first + i];
-                  if (r.status == AWV_ST_COMPLETED) {
-                    ++c->cst->pairs;
-                    if (cl.code != AWV_CL_OK || cl.score < c->clip_min_score) {
-                      ++(cl.code != AWV_CL_OK ? c->cst->empty : c->cst->below_min_score);
-                      kres.pop_back();
-                      continue;
-                    }
-                    awv_result& s = kres.back();
-                    s.cigar_off += cl.col_beg;
-                    s.cigar_len = cl.col_end - cl.col_beg;
-                    s.num_matches = cl.num_matches;
-                    s.num_mismatches = cl.num_mismatches;
-                    s.num_ins = cl.num_ins;
-                    s.num_del = cl.num_del;
-                    s.penalty = cl.penalty;
-                    s.score = -cl.penalty;
-                    s.q_end = cl.num_matches + cl.num_mismatches + cl.num_del;
-                    s.t_end = cl.num_matches + cl.num_mismatches + cl.num_ins;
-                  }
-                  kclip.push_back(cl);
-                }
-                krev.push_back(c->rev[first + i]);
-                kidx.push_back(c->idx ? c->idx[first + i] : (size_t)(first + i));
-              }
-              (*c->cb)(Batch{0, (int64_t)kres.size(), kres.data(), arena, krev.data(), kidx.data(), c->clip || c->sp ? kclip.data() : nullptr});
-              return 0;
-            }
-            (*c->cb)(Batch{first, cnt, res, arena, c->rev, c->idx});
-          } catch (...) {
-            (*c->fail)(std::current_exception());  // recorded now, and every slot stops at its next sink call
-            c->failed = true;
-            return 1;
-          }
-          return 0;
-        };
-        std::vector<awv_verify_result> vr(verify ? (size_t)m : 0);
-        std::vector<awv_clip_result> cr(clipping ? (size_t)std::max<int64_t>(m, 1) : 0);
-        if (clipping) {
-          ctx.clip = cr.data();
-          ctx.clip_min_score = clip_min_score_;
-          ctx.cst = &cst[s];
-        }
-        // a splitting run: this call's segment storage, laid out by the engine's own arithmetic over the resident lengths
-        std::vector<uint64_t> seg_first(splitting ? (size_t)m + 1 : 0);
-        std::vector<awv_split_index> six(splitting ? (size_t)std::max<int64_t>(m, 1) : 0);
-        std::vector<awv_clip_result> sseg;
-        SplitCall spc{split_bonus_, split_min_score_, nullptr, nullptr, nullptr};
-        if (splitting) {
-          const int lrc = ranges_ ? awv_split_layout_ranges(e, rp.data(), m, split_bonus_, split_min_score_, seg_first.data())
-                                  : awv_split_layout_pairs(e, ap.data(), m, split_bonus_, split_min_score_, seg_first.data());
-          if (lrc != AWV_OK) throw AlignmentError(std::string("split layout: ") + awv_last_error());
-          sseg.resize((size_t)std::max<uint64_t>(seg_first[(size_t)m], 1));
-          spc.seg_first = seg_first.data();
-          spc.index = six.data();
-          spc.seg = sseg.data();
-          ctx.sp = &spc;
-          ctx.sst = &sst[s];
-        }
+      for (size_t b = s; b < rs.batches.size() && !rs.stop.load(); b = cursor.fetch_add(1)) {
+        const PreparedBatch pb = prepare_batch(rs, e, b, rs.totals[s]);
+        SinkCtx ctx{&rs, &pb.delivery, false};
         // the slot's engine is this thread's until its device lock goes: the mode holds for this call and is off again after it
-        if (normalizing != AWV_NORM_OFF && awv_engine_set_normalize(e, normalizing) != AWV_OK) throw AlignmentError(std::string("normalize: ") + awv_last_error());
-        const int rc = engine_call(e, call.score_only, call.max_penalty, pen, ap.data(), m, sink, &ctx, verify ? vr.data() : nullptr,
-                                   ranges_ ? rp.data() : nullptr, bounded_run ? bounds.data() : call.align_bounds, clip_bonus_,
-                                   clipping ? cr.data() : nullptr, splitting ? &spc : nullptr);
-        if (normalizing != AWV_NORM_OFF) {
-          awv_engine_set_normalize(e, AWV_NORM_OFF);
-          if (rc == AWV_OK) {
-            awv_norm_stats nx{};
-            awv_engine_normalize_stats(e, &nx);
-            nst[s].kernel_ms += nx.kernel_ms;
-            nst[s].pairs += nx.pairs;
-            nst[s].records_moved += nx.records_moved;
-            nst[s].runs += nx.runs;
-            nst[s].runs_moved += nx.runs_moved;
-            nst[s].columns_moved += nx.columns_moved;
-            nst[s].columns += nx.columns;
-          }
-        }
-        lap("aligned + sunk");
-        awv_stats x{};
-        awv_engine_stats(e, &x);
-        add_stats(st[s], x, true);
-        if (verify && rc == AWV_OK) {
-          awv_verify_stats vx{};
-          awv_engine_verify_stats(e, &vx);
-          vst[s].kernel_ms += vx.kernel_ms;
-          vst[s].pairs += vx.pairs;
-          vst[s].failed += vx.failed;
-          vst[s].columns += vx.columns;
-          append_verify_failures(vfail[s], vr.data(), m, first, idx, plist, rev.data());
-        }
-        if (clipping && rc == AWV_OK) {
-          awv_clip_stats cx{};
-          awv_engine_clip_stats(e, &cx);
-          cst[s].kernel_ms += cx.kernel_ms;
-        }
-        if (splitting && rc == AWV_OK) {
-          awv_split_stats sx{};
-          awv_engine_split_stats(e, &sx);
-          sst[s].kernel_ms += sx.kernel_ms;
-        }
+        if (rs.normalizing != AWV_NORM_OFF && awv_engine_set_normalize(e, rs.normalizing) != AWV_OK) throw AlignmentError(std::string("normalize: ") + awv_last_error());
+        const int rc = engine_call(e, pb.request, batch_sink, &ctx);
+        if (rs.normalizing != AWV_NORM_OFF) awv_engine_set_normalize(e, AWV_NORM_OFF);
+        rs.lap("aligned + sunk");
+        take_call_totals(rs, pb, e, rc == AWV_OK, rs.totals[s]);
         if (ctx.failed) return;  // (the error is already recorded)
         if (rc != AWV_OK) {
-          if (rc == AWV_ERR_SINK && stop.load()) return;  // stopped by another slot's error, which is the one reported
+          if (rc == AWV_ERR_SINK && rs.stop.load()) return;  // stopped by another slot's error, which is the one reported
           throw AlignmentError(std::string("align_pairs: ") + awv_last_error());
         }
       }
     } catch (...) {
-      fail(std::current_exception());
+      rs.fail(std::current_exception());
     }
   };
   std::vector<std::thread> th;
   try {
     for (size_t s = 1; s < S; ++s) th.emplace_back(worker, s);
   } catch (...) {
-    fail(std::current_exception());
-    std::lock_guard<std::mutex> g(mu);
+    rs.fail(std::current_exception());
+    std::lock_guard<std::mutex> g(rs.mu);
     aborted = true;
     cv.notify_all();
   }
   if (th.size() == S - 1) worker(0);
   for (auto& t : th) t.join();
   locks.clear();
-  slot_stats_ = st;
+  slot_stats_.clear();
   stats_ = awv_stats{};
-  for (const auto& x : st) add_stats(stats_, x, false);
-  if (first == 0) {  // a run from the list's start begins anew; a later range (next()'s chunks) adds to it
-    verify_failures_.clear();
-    verify_stats_ = awv_verify_stats{};
-    bound_stats_ = BoundStats{};
-    clip_stats_ = ClipStats{};
-    split_stats_ = SplitStats{};
-    normalize_stats_ = awv_norm_stats{};
+  if (first == 0) report_ = RunReport{};  // a run from the list's start begins anew; a later range (next()'s chunks) adds to it
+  for (const SlotTotals& t : rs.totals) {
+    slot_stats_.push_back(t.engine);
+    add_stats(stats_, t.engine, false);
+    add(report_, t.report);
   }
-  for (size_t s = 0; s < S; ++s) {
-    normalize_stats_.kernel_ms += nst[s].kernel_ms;
-    normalize_stats_.pairs += nst[s].pairs;
-    normalize_stats_.records_moved += nst[s].records_moved;
-    normalize_stats_.runs += nst[s].runs;
-    normalize_stats_.runs_moved += nst[s].runs_moved;
-    normalize_stats_.columns_moved += nst[s].columns_moved;
-    normalize_stats_.columns += nst[s].columns;
-    split_stats_.pairs += sst[s].pairs;
-    split_stats_.segments += sst[s].segments;
-    split_stats_.empty += sst[s].empty;
-    split_stats_.kernel_ms += sst[s].kernel_ms;
-    clip_stats_.pairs += cst[s].pairs;
-    clip_stats_.empty += cst[s].empty;
-    clip_stats_.below_min_score += cst[s].below_min_score;
-    clip_stats_.kernel_ms += cst[s].kernel_ms;
-    bound_stats_.pairs += bst[s].pairs;
-    bound_stats_.above_penalty += bst[s].above_penalty;
-    bound_stats_.above_divergence += bst[s].above_divergence;
-    verify_stats_.kernel_ms += vst[s].kernel_ms;
-    verify_stats_.pairs += vst[s].pairs;
-    verify_stats_.failed += vst[s].failed;
-    verify_stats_.columns += vst[s].columns;
-    verify_failures_.insert(verify_failures_.end(), vfail[s].begin(), vfail[s].end());
-  }
-  sort_verify_failures(verify_failures_);
-  if (err) std::rethrow_exception(err);
+  sort_verify_failures(report_.verify_failures);
+  if (rs.err) std::rethrow_exception(rs.err);
 }
 
 void AllPairIterator::for_each_with_callback(const Callback& cb) {
@@ -1259,7 +1158,7 @@ std::vector<PairScore> AllPairIterator::scores(std::optional<int> max_penalty) {
       p.status = b.res[i].status;
       p.penalty = b.res[i].penalty;
     }
-  }, EngineCall{true, max_penalty ? *max_penalty : -1, nullptr});
+  }, EngineCall{true, max_penalty ? *max_penalty : -1});
   return out;
 }
 

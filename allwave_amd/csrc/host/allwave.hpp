@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "allwave_hip.h"
+#include "delivery.hpp"  // BoundStats, ClipStats, SplitStats; the delivery rule of a filtering run
 
 namespace allwave {
 
@@ -96,27 +97,6 @@ struct PairScore {
   int32_t status = AWV_ST_COMPLETED;
 };
 
-// What the bounds of a run left out (AllPairIterator::with_max_penalty / with_max_divergence): pairs aligned under a bound,
-// and of them the ones dropped because their penalty is above the penalty bound, or their divergence above the divergence
-// bound (abandoned by the penalty bound derived from it, or completed and filtered on the record's counts).
-struct BoundStats {
-  uint64_t pairs = 0, above_penalty = 0, above_divergence = 0;
-};
-
-// What clipping did to a run (AllPairIterator::with_clip): finished pairs whose op string was clipped, and of them the ones
-// that reached no consumer because the clip is empty, or scores below min_score; kernel_ms: summed clip kernel time.
-struct ClipStats {
-  uint64_t pairs = 0, empty = 0, below_min_score = 0;
-  double kernel_ms = 0.0;
-};
-
-// What splitting did to a run (AllPairIterator::with_split): finished pairs whose op string was split, the segments they
-// gave, and the pairs that reached no consumer because no segment scores min_score; kernel_ms: summed split kernel time.
-struct SplitStats {
-  uint64_t pairs = 0, segments = 0, empty = 0;
-  double kernel_ms = 0.0;
-};
-
 using Callback = std::function<void(AlignmentResult&&)>;  // may throw: first error aborts the run
 
 // One interval pair to align globally (awv_range_pair): query[query_start, query_end) -- on the query's FORWARD strand, as PAF
@@ -160,6 +140,32 @@ void release_engines();
 int visible_device_count();
 
 class AllPairParallelIterator;
+class AllPairIterator;
+
+// The options of one run that filter or rewrite what it delivers, in one place: AllPairIterator::with_max_penalty,
+// with_max_divergence (std::nullopt: no bound), with_clip and with_split (match bonus 0: off), with_normalize (AWV_NORM_OFF: off).
+struct RunOptions {
+  std::optional<int> max_penalty;
+  std::optional<double> max_divergence;
+  int clip_match_bonus = 0;
+  int64_t clip_min_score = 1;
+  int split_match_bonus = 0;
+  int64_t split_min_score = 1;
+  int normalize = AWV_NORM_OFF;
+  void apply(AllPairIterator& it) const;  // the with_* calls of what is set; they throw std::invalid_argument as documented there
+  bool any() const { return max_penalty || max_divergence || clip_match_bonus != 0 || split_match_bonus != 0 || normalize != AWV_NORM_OFF; }
+};
+
+// What a run leaves behind besides its results (AllPairIterator::last_report): the failed checks sorted by pair-list index,
+// and every counter summed over the slots (kernel_ms: summed kernel time).
+struct RunReport {
+  std::vector<VerifyFailure> verify_failures;
+  awv_verify_stats verify_stats{};
+  BoundStats bound_stats{};
+  ClipStats clip_stats{};
+  SplitStats split_stats{};
+  awv_norm_stats normalize_stats{};
+};
 
 class AllPairIterator {  // iterator.rs:12-171
  public:
@@ -233,9 +239,9 @@ class AllPairIterator {  // iterator.rs:12-171
   // together with with_clip (std::invalid_argument); scores() ignores the setting.
   AllPairIterator& with_split(int match_bonus, int64_t min_score);
   bool split() const { return split_bonus_ > 0; }
-  SplitStats last_split_stats() const { return split_stats_; }
+  SplitStats last_split_stats() const { return report_.split_stats; }
   // of the last run (next(): of the chunks since the list's start), summed over the slots
-  ClipStats last_clip_stats() const { return clip_stats_; }
+  ClipStats last_clip_stats() const { return report_.clip_stats; }
   // Every alignment consumer receives each alignment with its gap runs at their left- (AWV_NORM_LEFT) or right-normal
   // (AWV_NORM_RIGHT) place (awv_engine_set_normalize; include/allwave_hip.h has the contract): every slot's engine gets the
   // mode for its engine calls, under its device's mutex, and is switched off again afterwards.  Normalization comes before the
@@ -244,15 +250,16 @@ class AllPairIterator {  // iterator.rs:12-171
   AllPairIterator& with_normalize(int direction);
   int normalize() const { return normalize_; }
   // of the last run (next(): of the chunks since the list's start), summed over the slots (kernel_ms: summed kernel time)
-  awv_norm_stats last_normalize_stats() const { return normalize_stats_; }
+  awv_norm_stats last_normalize_stats() const { return report_.normalize_stats; }
   AllPairIterator& with_max_penalty(int max_penalty);
   AllPairIterator& with_max_divergence(double max_divergence);
   // of the last run (next(): of the chunks since the list's start), summed over the slots
-  BoundStats last_bound_stats() const { return bound_stats_; }
+  BoundStats last_bound_stats() const { return report_.bound_stats; }
   // of the last run (next(): of the chunks since the list's start): the failed pairs sorted by pair-list index, and the
   // verify counters summed over the slots (kernel_ms: summed kernel time)
-  const std::vector<VerifyFailure>& verify_failures() const { return verify_failures_; }
-  awv_verify_stats last_verify_stats() const { return verify_stats_; }
+  const std::vector<VerifyFailure>& verify_failures() const { return report_.verify_failures; }
+  awv_verify_stats last_verify_stats() const { return report_.verify_stats; }
+  const RunReport& last_report() const { return report_; }  // all of the last_*_stats() and verify_failures() in one
   AllPairIterator& with_device(int device);  // = with_devices({device})
   // Aligns the pair list on several engines at once, one "slot" per entry: an ordinal may appear more than once, and each
   // occurrence is an engine of its own (stream, arenas; the slots of one device split its default scratch budget).  With
@@ -300,21 +307,30 @@ class AllPairIterator {  // iterator.rs:12-171
     bool is_rev(int64_t i) const { return rev[first + i] != 0; }
   };
   using BatchCb = std::function<void(const Batch&)>;
-  // The engine call a run makes per batch: awv_align_pairs, or awv_score_pairs under max_penalty (< 0: no bound; one sink
-  // call per batch, results carry status and penalty, no arena).  align_bounds (nullable, alignment calls): one bound per
-  // entry of the batch (< 0: none) -- the call is then awv_align_pairs_bounded / awv_align_ranges_bounded; run() fills it in
-  // per batch from with_max_penalty / with_max_divergence.
+  // The engine call a run makes per batch: an alignment call, or awv_score_pairs under max_penalty (< 0: no bound; one sink
+  // call per batch, results carry status and penalty, no arena).
   struct EngineCall {
     bool score_only;
     int32_t max_penalty;
-    const int32_t* align_bounds;
   };
   // pairs_[first, first + count) on the with_devices slots; batch indices are relative to `first`.  Per batch: orientation,
   // one engine call, the batch callback, the counters.  One slot: one batch, the whole range in list order, on the calling
   // thread.  With several slots, batch callbacks of different slots run concurrently: consumers that call user code
   // serialise it.
-  void run(size_t first, size_t count, const BatchCb& batch_cb, EngineCall call = {false, -1, nullptr});
-  void run(const BatchCb& batch_cb, EngineCall call = {false, -1, nullptr}) { run(0, pairs_.size(), batch_cb, call); }
+  void run(size_t first, size_t count, const BatchCb& batch_cb, EngineCall call = {false, -1});
+  void run(const BatchCb& batch_cb, EngineCall call = {false, -1}) { run(0, pairs_.size(), batch_cb, call); }
+  // run()'s steps (allwave.cpp): what the slots of one run share and what each of them counts; one batch made ready for its
+  // engine call; the engine's sink, which hands a call's results to the batch callback; the counters taken after a call
+  struct RunState;
+  struct SlotTotals;
+  struct PreparedBatch;
+  struct SinkCtx;
+  PreparedBatch prepare_batch(const RunState& rs, awv_engine* e, size_t b, SlotTotals& totals) const;
+  static int batch_sink(void* user, int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena);
+  static void take_call_totals(const RunState& rs, const PreparedBatch& pb, awv_engine* e, bool ok, SlotTotals& totals);
+  // run(first, count) into one result per delivered entry, in pair-list order: a pair's segments in column order (with_split),
+  // the pairs a run drops left out
+  std::vector<AlignmentResult> collect_ordered(size_t first, size_t count);
   // align_pair's result mapping for entry k of the pair list (a range list: in the range's coordinates)
   // cl (nullable): the entry's clip, r the segment's record -- the coordinates are shifted by the skips (with_clip)
   AlignmentResult result_at(size_t k, bool is_rev, const awv_result& r, const uint8_t* arena, bool copy_cigar,
@@ -334,16 +350,11 @@ class AllPairIterator {  // iterator.rs:12-171
   bool bounded() const { return max_penalty_.has_value() || divergence_bound().has_value(); }
   int clip_bonus_ = 0;  // with_clip (0: off)
   int64_t clip_min_score_ = 1;
-  ClipStats clip_stats_{};
   int normalize_ = AWV_NORM_OFF;  // with_normalize
-  awv_norm_stats normalize_stats_{};
   int split_bonus_ = 0;  // with_split (0: off)
   int64_t split_min_score_ = 1;
-  SplitStats split_stats_{};
   bool drops_pairs() const { return bounded() || clip() || split(); }  // consumers that keep a slot per pair compact what was delivered
-  BoundStats bound_stats_{};
-  std::vector<VerifyFailure> verify_failures_;
-  awv_verify_stats verify_stats_{};
+  RunReport report_;
   std::vector<int> devices_{0};
   size_t min_batch_pairs_ = 16384;
   int threads_ = 0;
@@ -374,6 +385,7 @@ class AllPairParallelIterator {
   ClipStats last_clip_stats() const { return it_.last_clip_stats(); }
   SplitStats last_split_stats() const { return it_.last_split_stats(); }
   awv_norm_stats last_normalize_stats() const { return it_.last_normalize_stats(); }
+  const RunReport& last_report() const { return it_.last_report(); }
  private:
   friend class AllPairIterator;
   explicit AllPairParallelIterator(const AllPairIterator& it) : it_(it) {}
@@ -401,32 +413,11 @@ AlignmentResult range_alignment_result(const AlignmentRange& range, const awv_re
 void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
                   const Callback& callback, const std::vector<int>& devices = {0}, bool verify = false,
                   std::vector<VerifyFailure>* failures = nullptr, awv_verify_stats* verify_stats = nullptr);
-// the same under bounds (AllPairIterator::with_max_penalty / with_max_divergence; std::nullopt: none): a range above a bound
-// gives no callback; bound_stats (nullable) receives what was left out
+// the same under `options` (a range above a bound, or without a clip or a segment worth reporting, gives no callback; a split
+// range gives one per segment); report (nullable) receives what the run left behind
 void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
-                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
-                  awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
-                  BoundStats* bound_stats = nullptr);
-// the same with every alignment clipped (AllPairIterator::with_clip); clip_stats (nullable) receives what clipping did
-void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
-                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
-                  awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
-                  BoundStats* bound_stats, int clip_match_bonus, int64_t clip_min_score, ClipStats* clip_stats = nullptr);
-
-// the same with every alignment split (AllPairIterator::with_split; split_match_bonus 0: off -- then clip_match_bonus 0 is off
-// as well); split_stats (nullable) receives what splitting did
-void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
-                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
-                  awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
-                  BoundStats* bound_stats, int clip_match_bonus, int64_t clip_min_score, ClipStats* clip_stats, int split_match_bonus,
-                  int64_t split_min_score, SplitStats* split_stats = nullptr);
-// the same with every alignment normalized first (AllPairIterator::with_normalize; AWV_NORM_OFF: off); normalize_stats
-// (nullable) receives what normalization did
-void align_ranges(const std::vector<Sequence>& sequences, const std::vector<AlignmentRange>& ranges, AlignmentParams params,
-                  const Callback& callback, const std::vector<int>& devices, bool verify, std::vector<VerifyFailure>* failures,
-                  awv_verify_stats* verify_stats, std::optional<int> max_penalty, std::optional<double> max_divergence,
-                  BoundStats* bound_stats, int clip_match_bonus, int64_t clip_min_score, ClipStats* clip_stats, int split_match_bonus,
-                  int64_t split_min_score, SplitStats* split_stats, int normalize, awv_norm_stats* normalize_stats = nullptr);
+                  const Callback& callback, const std::vector<int>& devices, bool verify, const RunOptions& options,
+                  RunReport* report = nullptr);
 
 // ---- mappings in, alignments out: the interval pairs a PAF file names (columns 1-9 of each line) ----
 struct PafRangeLine {

@@ -17,72 +17,29 @@ namespace {
 void set_err(char* err, size_t cap, const std::string& m) {
   if (err && cap) snprintf(err, cap, "%s", m.c_str());
 }
-// On-device verification: the alignment hooks below take `verify` (AllPairIterator::with_verify) and leave their verify
-// counters and failures here, per calling thread, for awh_last_verify.
-thread_local awv_verify_stats g_verify_stats{};
-thread_local std::vector<VerifyFailure> g_verify_failures;
-void keep_verify(const awv_verify_stats& st, const std::vector<VerifyFailure>& f) {
-  g_verify_stats = st;
-  g_verify_failures = f;
-}
-
-// The options of one run (RunOptions).
-// Bounds on the final alignments: awh_set_bounds leaves them here, per calling thread, for the NEXT alignment hook of that
-// thread, which takes them (they hold for that one call) and leaves its last_bound_stats() for awh_last_bounds.
-thread_local int64_t g_next_max_penalty = -1;
-thread_local double g_next_max_divergence = -1.0;
-thread_local BoundStats g_bound_stats{};
-// Clipping travels the same way: awh_set_clip leaves the match bonus (0: off) and the least score for the NEXT alignment hook
-// of the calling thread, which leaves its last_clip_stats() for awh_last_clip.
-thread_local int g_next_clip_bonus = 0;
-thread_local int64_t g_next_clip_min_score = 1;
-thread_local ClipStats g_clip_stats{};
-// And splitting: awh_set_split, awh_last_split.
-thread_local int g_next_split_bonus = 0;
-thread_local int64_t g_next_split_min_score = 1;
-thread_local SplitStats g_split_stats{};
-// And normalization: awh_set_normalize (AWV_NORM_*; 0: off), awh_last_normalize.
-thread_local int g_next_normalize = AWV_NORM_OFF;
-thread_local awv_norm_stats g_norm_stats{};
-struct RunOptions {
-  int64_t max_penalty;
-  double max_divergence;
-  int clip_bonus;
-  int64_t clip_min_score;
-  int split_bonus;
-  int64_t split_min_score;
-  int normalize;
-  void apply(AllPairIterator& it) const {
-    if (normalize != AWV_NORM_OFF) it.with_normalize(normalize);
-    if (max_penalty >= 0) it.with_max_penalty((int)std::min<int64_t>(max_penalty, INT32_MAX));
-    if (max_divergence >= 0.0) it.with_max_divergence(max_divergence);
-    if (clip_bonus != 0) it.with_clip(clip_bonus, clip_min_score);
-    if (split_bonus != 0) it.with_split(split_bonus, split_min_score);
-  }
-  bool any() const { return max_penalty >= 0 || max_divergence >= 0.0 || clip_bonus != 0 || split_bonus != 0 || normalize != AWV_NORM_OFF; }
-};
-// what an alignment hook leaves behind of its iterator's bound and clip counters (awh_last_bounds, awh_last_clip)
+// What the calling thread's last alignment hook left behind, its iterator's last_report(): the verify counters and failures
+// for awh_last_verify, the other counters for awh_last_bounds, awh_last_clip, awh_last_split and awh_last_normalize.
+thread_local RunReport g_report;
 template <typename It>
-void keep_stats(const It& it) {
-  g_bound_stats = it.last_bound_stats();
-  g_clip_stats = it.last_clip_stats();
-  g_split_stats = it.last_split_stats();
-  g_norm_stats = it.last_normalize_stats();
+void keep(const It& it) {
+  g_report = it.last_report();
 }
+// The options of the calling thread's NEXT alignment hook: awh_set_bounds, awh_set_clip, awh_set_split and awh_set_normalize
+// leave them here; the hook takes them (they hold for that one call) and starts the counters they go with afresh.
+thread_local RunOptions g_next;
 RunOptions take_run_options() {
-  const RunOptions b{g_next_max_penalty, g_next_max_divergence, g_next_clip_bonus, g_next_clip_min_score, g_next_split_bonus, g_next_split_min_score, g_next_normalize};
-  g_next_normalize = AWV_NORM_OFF;
-  g_norm_stats = awv_norm_stats{};
-  g_next_split_bonus = 0;
-  g_next_split_min_score = 1;
-  g_split_stats = SplitStats{};
-  g_next_max_penalty = -1;
-  g_next_max_divergence = -1.0;
-  g_next_clip_bonus = 0;
-  g_next_clip_min_score = 1;
-  g_bound_stats = BoundStats{};
-  g_clip_stats = ClipStats{};
-  return b;
+  const RunOptions o = g_next;
+  g_next = RunOptions{};
+  g_report.bound_stats = BoundStats{};
+  g_report.clip_stats = ClipStats{};
+  g_report.split_stats = SplitStats{};
+  g_report.normalize_stats = awv_norm_stats{};
+  return o;
+}
+// the hooks' orientation code on an iterator: 0 forward, 1 WFA, 2 mash, 3 WFA by two full alignments per pair
+void set_orientation(AllPairIterator& it, int orientation) {
+  it.with_orientation(orientation == 0 ? Orientation::ForwardOnly : (orientation == 1 || orientation == 3) ? Orientation::Wfa : Orientation::Mash);
+  it.with_full_wfa_orientation(orientation == 3);
 }
 
 std::vector<Sequence> make_seqs(int n, const char* const* ids, const uint8_t* bytes, const uint64_t* offs) {
@@ -162,8 +119,7 @@ int awh_all_pairs_paf_devices(int n, const char* const* ids, const uint8_t* byte
     const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
     AllPairIterator it = AllPairIterator::with_options(seqs, parse_scores(scores), exclude_self != 0, orientation == 2,
                                                       SparsificationStrategy::parse(sparsification ? sparsification : "none"));
-    it.with_orientation(orientation == 0 ? Orientation::ForwardOnly : (orientation == 1 || orientation == 3) ? Orientation::Wfa : Orientation::Mash);
-    it.with_full_wfa_orientation(orientation == 3);
+    set_orientation(it, orientation);
     if (!devices || n_devices < 1) throw std::invalid_argument("awh_all_pairs_paf: empty device list");
     it.with_devices(std::vector<int>(devices, devices + n_devices));
     if (min_batch_pairs > 0) it.with_min_batch_pairs((size_t)min_batch_pairs);
@@ -174,8 +130,7 @@ int awh_all_pairs_paf_devices(int n, const char* const* ids, const uint8_t* byte
       all += alignment_to_paf(r, seqs);
       all.push_back('\n');
     });
-    keep_verify(it.last_verify_stats(), it.verify_failures());
-    keep_stats(it);
+    keep(it);
     if (slot_stats) for (int k = 0; k < n_devices; ++k) slot_stats[k] = it.last_slot_stats()[(size_t)k];
     *out = (char*)malloc(all.size() + 1);
     memcpy(*out, all.c_str(), all.size() + 1);
@@ -210,7 +165,6 @@ int awh_iterate_devices(int n, const char* const* ids, const uint8_t* bytes, con
   try {
     const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
     const SparsificationStrategy strat = SparsificationStrategy::parse(sparsification ? sparsification : "none");
-    const Orientation orient = orientation == 0 ? Orientation::ForwardOnly : (orientation == 1 || orientation == 3) ? Orientation::Wfa : Orientation::Mash;
     std::mutex mu;
     std::string all;
     auto record = [&](AlignmentResult&& r) {
@@ -238,23 +192,22 @@ int awh_iterate_devices(int n, const char* const* ids, const uint8_t* bytes, con
       if (min_batch_pairs > 0) it.with_min_batch_pairs((size_t)min_batch_pairs);
       it.for_each_with_callback(record);
       st = it.last_slot_stats();
-      keep_verify(it.last_verify_stats(), it.verify_failures());
-      keep_stats(it);
+      keep(it);
     } else {
       AllPairIterator it0 = AllPairIterator::with_options(seqs, parse_scores(scores), true, orientation == 2,
                                                          resparsify ? SparsificationStrategy{} : strat);
-      it0.with_orientation(orient).with_devices(devs);
-      it0.with_full_wfa_orientation(orientation == 3);
+      set_orientation(it0, orientation);
+      it0.with_devices(devs);
       if (shard_world > 1) it0.with_shard((size_t)shard_rank, (size_t)shard_world);
       if (min_batch_pairs > 0) it0.with_min_batch_pairs((size_t)min_batch_pairs);
       if (chunk > 0) it0.with_next_chunk((size_t)chunk);
       it0.with_verify(verify);
       opts.apply(it0);
       AllPairIterator it = resparsify ? it0.with_sparsification(strat).with_shard((size_t)shard_rank, (size_t)shard_world) : it0;
-      if (mode == 0) { it.for_each_with_callback(record); st = it.last_slot_stats(); keep_verify(it.last_verify_stats(), it.verify_failures()); keep_stats(it); }
-      else if (mode == 1) { while (auto r = it.next()) record(std::move(*r)); st = it.last_slot_stats(); keep_verify(it.last_verify_stats(), it.verify_failures()); keep_stats(it); }
-      else if (mode == 2) { auto par = it.into_par_iter(); par.with_threads(threads).for_each_with_callback(record); st = par.last_slot_stats(); keep_verify(par.last_verify_stats(), par.verify_failures()); keep_stats(par); }
-      else if (mode == 3) { auto par = it.into_par_iter(); for (auto& r : par.collect()) record(std::move(r)); st = par.last_slot_stats(); keep_verify(par.last_verify_stats(), par.verify_failures()); keep_stats(par); }
+      if (mode == 0) { it.for_each_with_callback(record); st = it.last_slot_stats(); keep(it); }
+      else if (mode == 1) { while (auto r = it.next()) record(std::move(*r)); st = it.last_slot_stats(); keep(it); }
+      else if (mode == 2) { auto par = it.into_par_iter(); par.with_threads(threads).for_each_with_callback(record); st = par.last_slot_stats(); keep(par); }
+      else if (mode == 3) { auto par = it.into_par_iter(); for (auto& r : par.collect()) record(std::move(r)); st = par.last_slot_stats(); keep(par); }
       else throw std::invalid_argument("awh_iterate_devices: unknown mode");
     }
     if (slot_stats)
@@ -284,8 +237,7 @@ int awh_all_pairs_scores(int n, const char* const* ids, const uint8_t* bytes, co
     const std::vector<Sequence> seqs = make_seqs(n, ids, bytes, offs);
     AllPairIterator it = AllPairIterator::with_options(seqs, parse_scores(scores), true, orientation == 2,
                                                       SparsificationStrategy::parse(sparsification ? sparsification : "none"));
-    it.with_orientation(orientation == 0 ? Orientation::ForwardOnly : (orientation == 1 || orientation == 3) ? Orientation::Wfa : Orientation::Mash);
-    it.with_full_wfa_orientation(orientation == 3);
+    set_orientation(it, orientation);
     it.with_devices(std::vector<int>(devices, devices + n_devices));
     if (shard_world > 1) it.with_shard((size_t)shard_rank, (size_t)shard_world);
     if (max_penalty > INT32_MAX) max_penalty = -1;  // (no pair can score that much: no bound)
@@ -318,9 +270,8 @@ int awh_all_pairs_paf_count_devices(int n, const char* const* ids, const uint8_t
     AllPairIterator it = sparsification ? AllPairIterator::with_options(seqs, parse_scores(scores), true, false,
                                                                        SparsificationStrategy::parse(sparsification))
                                         : AllPairIterator(seqs, parse_scores(scores));
-    it.with_orientation(orientation == 0 ? Orientation::ForwardOnly : (orientation == 1 || orientation == 3) ? Orientation::Wfa : Orientation::Mash)
-        .with_devices(std::vector<int>(devices, devices + n_devices));
-    it.with_full_wfa_orientation(orientation == 3);
+    set_orientation(it, orientation);
+    it.with_devices(std::vector<int>(devices, devices + n_devices));
     if (min_batch_pairs > 0) it.with_min_batch_pairs((size_t)min_batch_pairs);
     it.with_threads(format_threads);  // this call's sketching / orientation threads: carried by the iterator, not a process-wide setting
     it.with_verify(verify != 0);
@@ -342,8 +293,7 @@ int awh_all_pairs_paf_count_devices(int n, const char* const* ids, const uint8_t
     *out_bytes = nb;
     *out_lines = nl;
     if (out_checksum) *out_checksum = sum;
-    keep_verify(it.last_verify_stats(), it.verify_failures());
-    keep_stats(it);
+    keep(it);
     if (st) *st = it.last_stats();
     if (slot_stats) for (int k = 0; k < n_devices; ++k) slot_stats[k] = it.last_slot_stats()[(size_t)k];
     return 0;
@@ -561,7 +511,8 @@ int awh_verify_failure_path(int n, const char* const* ids, const int64_t* pairs,
     append_verify_failures(all, vr.data(), (int64_t)(hi - lo), first, ix.data(), plist.data(), rev + lo);
   }
   sort_verify_failures(all);
-  keep_verify(st, all);
+  g_report.verify_stats = st;
+  g_report.verify_failures = all;
   std::string text;
   const int status = report_verify_failures(all, seqs, text);
   snprintf(report, cap, "%s", text.c_str());
@@ -571,16 +522,16 @@ int awh_verify_failure_path(int n, const char* const* ids, const int64_t* pairs,
 // what the calling thread's last alignment hook left: last_verify_stats() and verify_failures() as malloc'ed int64 records of seven (pair-list
 // index, query_idx, target_idx, is_reverse, code, column, penalty)
 int awh_last_verify(awv_verify_stats* st, int64_t** out, size_t* n) {
-  *st = g_verify_stats;
-  *out = (int64_t*)malloc(sizeof(int64_t) * 7 * (g_verify_failures.size() + 1));
+  *st = g_report.verify_stats;
+  *out = (int64_t*)malloc(sizeof(int64_t) * 7 * (g_report.verify_failures.size() + 1));
   if (!*out) return -1;
-  for (size_t i = 0; i < g_verify_failures.size(); ++i) {
-    const VerifyFailure& f = g_verify_failures[i];
+  for (size_t i = 0; i < g_report.verify_failures.size(); ++i) {
+    const VerifyFailure& f = g_report.verify_failures[i];
     int64_t* o = *out + 7 * i;
     o[0] = (int64_t)f.index; o[1] = (int64_t)f.query_idx; o[2] = (int64_t)f.target_idx; o[3] = f.is_reverse ? 1 : 0;
     o[4] = f.code; o[5] = f.column; o[6] = f.penalty;
   }
-  *n = g_verify_failures.size();
+  *n = g_report.verify_failures.size();
   return 0;
 }
 
@@ -634,8 +585,7 @@ int awh_align_ranges_paf(int n, const char* const* ids, const uint8_t* bytes, co
     opts.apply(it);
     AllPairParallelIterator par = it.into_par_iter();
     const std::vector<AlignmentResult> res = par.collect();  // (in list order, on any number of slots)
-    keep_verify(par.last_verify_stats(), par.verify_failures());
-    keep_stats(par);
+    keep(par);
     std::string all;
     for (const AlignmentResult& r : res) {
       all += alignment_to_paf(r, seqs);
@@ -696,58 +646,58 @@ int awh_parse_paf_ranges(int n, const char* const* ids, const int64_t* lens, con
 // awh_align_ranges_paf) runs under AllPairIterator::with_max_penalty(max_penalty) (< 0: none) and
 // with_max_divergence(max_divergence) (< 0: none); the hooks after it run unbounded again.
 void awh_set_bounds(int64_t max_penalty, double max_divergence) {
-  g_next_max_penalty = max_penalty;
-  g_next_max_divergence = max_divergence;
+  g_next.max_penalty = max_penalty >= 0 ? std::optional<int>((int)std::min<int64_t>(max_penalty, INT32_MAX)) : std::nullopt;
+  g_next.max_divergence = max_divergence >= 0.0 ? std::optional<double>(max_divergence) : std::nullopt;
 }
 // ---- clipping to the best-scoring segment ----
 // The calling thread's NEXT alignment hook runs with_clip(match_bonus, min_score) (match_bonus 0: off); the hooks after it
 // run unclipped again.
 void awh_set_clip(int match_bonus, int64_t min_score) {
-  g_next_clip_bonus = match_bonus;
-  g_next_clip_min_score = min_score;
+  g_next.clip_match_bonus = match_bonus;
+  g_next.clip_min_score = min_score;
 }
 // ---- splitting into all good segments ----
 // The calling thread's NEXT alignment hook runs with_split(match_bonus, min_score) (match_bonus 0: off); the hooks after it
 // run unsplit again.
 void awh_set_split(int match_bonus, int64_t min_score) {
-  g_next_split_bonus = match_bonus;
-  g_next_split_min_score = min_score;
+  g_next.split_match_bonus = match_bonus;
+  g_next.split_min_score = min_score;
 }
 // ---- gap runs at their normal place ----
 // The calling thread's NEXT alignment hook runs with_normalize(direction) (AWV_NORM_LEFT / AWV_NORM_RIGHT; AWV_NORM_OFF: off); the
 // hooks after it run without again.
-void awh_set_normalize(int direction) { g_next_normalize = direction; }
+void awh_set_normalize(int direction) { g_next.normalize = direction; }
 // last_normalize_stats() of the calling thread's last alignment hook: {pairs, records_moved, runs, runs_moved, columns_moved,
 // columns} and the kernel time
 void awh_last_normalize(uint64_t out[6], double* kernel_ms) {
-  out[0] = g_norm_stats.pairs;
-  out[1] = g_norm_stats.records_moved;
-  out[2] = g_norm_stats.runs;
-  out[3] = g_norm_stats.runs_moved;
-  out[4] = g_norm_stats.columns_moved;
-  out[5] = g_norm_stats.columns;
-  *kernel_ms = g_norm_stats.kernel_ms;
+  out[0] = g_report.normalize_stats.pairs;
+  out[1] = g_report.normalize_stats.records_moved;
+  out[2] = g_report.normalize_stats.runs;
+  out[3] = g_report.normalize_stats.runs_moved;
+  out[4] = g_report.normalize_stats.columns_moved;
+  out[5] = g_report.normalize_stats.columns;
+  *kernel_ms = g_report.normalize_stats.kernel_ms;
 }
 // last_split_stats() of the calling thread's last alignment hook: {pairs, segments, empty} and the kernel time
 void awh_last_split(uint64_t out[3], double* kernel_ms) {
-  out[0] = g_split_stats.pairs;
-  out[1] = g_split_stats.segments;
-  out[2] = g_split_stats.empty;
-  *kernel_ms = g_split_stats.kernel_ms;
+  out[0] = g_report.split_stats.pairs;
+  out[1] = g_report.split_stats.segments;
+  out[2] = g_report.split_stats.empty;
+  *kernel_ms = g_report.split_stats.kernel_ms;
 }
 // last_clip_stats() of the calling thread's last alignment hook: {pairs, empty, below_min_score} and the kernel time
 void awh_last_clip(uint64_t out[3], double* kernel_ms) {
-  out[0] = g_clip_stats.pairs;
-  out[1] = g_clip_stats.empty;
-  out[2] = g_clip_stats.below_min_score;
-  *kernel_ms = g_clip_stats.kernel_ms;
+  out[0] = g_report.clip_stats.pairs;
+  out[1] = g_report.clip_stats.empty;
+  out[2] = g_report.clip_stats.below_min_score;
+  *kernel_ms = g_report.clip_stats.kernel_ms;
 }
 
 // last_bound_stats() of the calling thread's last alignment hook: {pairs, above_penalty, above_divergence}
 void awh_last_bounds(uint64_t out[3]) {
-  out[0] = g_bound_stats.pairs;
-  out[1] = g_bound_stats.above_penalty;
-  out[2] = g_bound_stats.above_divergence;
+  out[0] = g_report.bound_stats.pairs;
+  out[1] = g_report.bound_stats.above_penalty;
+  out[2] = g_report.bound_stats.above_divergence;
 }
 
 void awh_free(void* p) { free(p); }
