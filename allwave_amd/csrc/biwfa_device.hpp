@@ -55,8 +55,8 @@
 namespace AWV_NS {
 
 constexpr int WG = AWV_WG;  // threads per workgroup = per sequence pair (64 or 256)
-// Accepted penalties: scope = max(x, o1+e1, o2+e2) + 1 <= MAX_SCOPE (engine.hip check_penalties).  The ring of score rows is
-// the power of two >= scope + 2 + multi_T * chain_max - 1 (align_core), so it reaches MAX_RING = 256 rows: e.g. (0,5,121,1),
+// Accepted penalties: scope = max(x, o1+e1, o2+e2) + 1 <= MAX_SCOPE (batch_plan.hpp plan_penalties).  The ring of score rows is
+// the power of two >= scope + 2 + multi_T * chain_max - 1 (plan_penalties), so it reaches MAX_RING = 256 rows: e.g. (0,5,121,1),
 // (0,125,3,1) or (0,5,8,2,124,1).  Nothing on the device is sized by it; the ring arena and the LDS row metadata follow kp.ring.
 constexpr int MAX_SCOPE = 126;
 constexpr int MAX_RING = 256;

@@ -56,11 +56,15 @@
 #include <thread>
 #include <vector>
 
+#include "batch_plan.hpp"
 #include "twin_plan.hpp"
 
 namespace {
-// uint32 words behind the events: the DFS stack, then the last-hit table of a twin search (biwfa_device.hpp)
-constexpr size_t EV_EXTRA = (size_t)awv::EV_STACK_WORDS;
+// the device constants batch_plan.hpp's rules are written over (biwfa_device.hpp)
+const awvb::Limits LIMITS = {awv::TMAX, awv::TMAX32, awv::CHAIN_MAX, awv::MAX_RING, awv::MAX_SCOPE, awv::NCOMP, awv::COL_PAD,
+                             awv::FALLBACK_MIN_SCORE, awv::FALLBACK_MIN_LENGTH, awv::WAVES_PER_SIMD, awv::STATIC_LDS_RESERVE,
+                             (size_t)awv::EV_STACK_WORDS, (size_t)awv::EV_TWIN_WORDS, sizeof(awv::RowMeta), sizeof(awv::RowMeta16),
+                             sizeof(awv::Breakpoint)};
 static_assert(awv::EV_STACK_WORDS == (awv::STACK_CAP * sizeof(awv::Task) + 3) / 4 + 16, "DFS stack words");
 
 thread_local std::string g_last_error;
@@ -163,6 +167,14 @@ struct awv_engine {
   DevBuf<uint8_t> d_cigar;
   DevBuf<unsigned long long> d_counters;  // [0] work cursor, [1..] stats
   std::vector<uint8_t> h_cigar;
+  // host sides of a launch's uploads and of its read-back: kept with the engine, like h_cigar, so that the copies of every call
+  // start from / land in the same host memory (fresh allocations per call cost the runtime tens of milliseconds now and then)
+  struct HostStage {
+    std::vector<int32_t> hq, ht, hrc, hbound, hufirst, hutwin;
+    std::vector<uint64_t> hoff;
+    std::vector<awvr::Span> hspan;
+    std::vector<awv_result> tres;
+  } stage;
   awv_stats stats{};
   awp::PlanState* plan = nullptr;  // planner.hip: sketches of `seqs` and planning scratch (released with a new set)
   awvf::State* verify = nullptr;   // verify.hip: buffers and stats of the verify launches
@@ -253,29 +265,12 @@ int upload_seqset(awv_engine* e, SeqSet& s, int32_t n, const uint8_t* bytes, con
   return AWV_OK;
 }
 
-// what makes a penalty set meaningful at all (the verify check re-scores under any such set: awv_internal_check_penalties)
+// what makes a penalty set meaningful at all (the verify check re-scores under any such set: awv_internal_check_penalties); what
+// the alignment kernels can run is batch_plan.hpp's plan_penalties
 int check_penalty_signs(const awv_penalties* p) {
-  if (!p) return fail(AWV_ERR_ARG, "penalties: null");
-  if (p->match != 0) return fail(AWV_ERR_PENALTIES, "match score must be 0 (WFA2 penalty transformation is out of scope)");
-  if (p->mismatch <= 0 || p->gap_open1 < 0 || p->gap_ext1 <= 0) return fail(AWV_ERR_PENALTIES, "need x > 0, o >= 0, e > 0");
-  if (p->two_piece && (p->gap_open2 < 0 || p->gap_ext2 <= 0)) return fail(AWV_ERR_PENALTIES, "need o2 >= 0, e2 > 0");
-  return AWV_OK;
-}
-
-// and what the alignment kernels can run: the score ring holds max(x, o1 + e1, o2 + e2) + 1 rows
-int check_penalties(const awv_penalties* p, awv::DevPenalties& d) {
-  if (int rc = check_penalty_signs(p)) return rc;
-  d.x = p->mismatch;
-  d.o1 = p->gap_open1;
-  d.e1 = p->gap_ext1;
-  d.two_piece = p->two_piece ? 1 : 0;
-  d.o2 = d.two_piece ? p->gap_open2 : p->gap_open1;
-  d.e2 = d.two_piece ? p->gap_ext2 : p->gap_ext1;
-  int scope = std::max(d.x, d.o1 + d.e1);
-  if (d.two_piece) scope = std::max(scope, d.o2 + d.e2);
-  d.scope = scope + 1;
-  if (d.scope > awv::MAX_SCOPE) return fail(AWV_ERR_PENALTIES, "penalties too large: max(x, o1+e1, o2+e2) must be < 126");
-  return AWV_OK;
+  std::string msg;
+  const int rc = awvb::check_signs(p, msg);
+  return rc == AWV_OK ? rc : fail(rc, msg);
 }
 
 // ---- arena placement --------------------------------------------------------------------------
@@ -317,697 +312,561 @@ __global__ __launch_bounds__(64, 4) void arena_probe_kernel(unsigned char* arena
   if (acc == 0x12345678u) sink[0] = acc;
 }
 
-// worst-case penalty of an end-to-end alignment of two sequences of length <= n
-long long worst_case_penalty(const awv::DevPenalties& d, long long n) {
-  auto gap = [&](long long l) {
-    long long g = d.o1 + l * d.e1;
-    if (d.two_piece) g = std::min(g, (long long)d.o2 + l * d.e2);
-    return g;
-  };
-  return std::min(2 * gap(n), n * (long long)d.x + gap(n));
-}
-
-// score_only: awv_score_pairs -- the top-level search's score only, no CIGAR arena (so max_arena_bytes does not cut batches);
-// max_penalty: that call's bound (INT_MAX = none); pair_bound (nullable): pair i's own bound instead (INT_MAX = none).  A full
-// alignment may carry bounds too (awv_align_pairs_bounded): they stop the pair's top-level search, nothing below it
-// vout (nullable; awv_align_pairs_verified, on the engine's own sequence set): every batch's records and op bytes are checked
-// on the device before the batch's CIGARs are copied back
-// spans (nullable; the awv_*_ranges calls): pair i aligns the rectangle spans[i] of its two sequences, in pattern / text
-// coordinates and already validated, instead of the whole of them -- every length below is then the rectangle's
-// cout (nullable; awv_align_pairs_clipped): every batch's op strings are clipped on the device under match_bonus, after the
-// check and before the batch's CIGARs are copied back
-// split (nullable; awv_align_pairs_split): likewise split into all segments of at least split->min_score, into the caller's
-// slot layout (already checked against the slot rule)
+// ---- an aligning call: batch_plan.hpp decides, the stages below carry it out ----
 struct SplitOut {
   int64_t min_score;
   const uint64_t* seg_first;
   awv_split_index* iout;
   awv_clip_result* sout;
 };
-int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
-               awv_result* out, awv_sink sink, void* user, bool score_only = false, int max_penalty = INT_MAX,
-               const int32_t* pair_bound = nullptr, awv_verify_result* vout = nullptr, const awvr::Span* spans = nullptr,
-               awv_clip_result* cout = nullptr, int32_t match_bonus = 0, const SplitOut* split = nullptr) {
-  using namespace awv;
-  if (npairs < 0 || (npairs > 0 && !pairs)) return fail(AWV_ERR_ARG, "align_pairs: null pairs");
-  DevPenalties dp{};
-  if (int rc = check_penalties(pen, dp)) return rc;
-  AWV_TRY(hipSetDevice(e->device));
-  e->stats = awv_stats{};
-  for (uint64_t& v : e->twin_stats) v = 0;
-  const int32_t norm = score_only ? AWV_NORM_OFF : e->norm_mode;  // (off: no launch, no allocation, nothing below changes)
-  if (norm != AWV_NORM_OFF) awvn::stats_reset(e->normalize);
-  if (npairs == 0) return AWV_OK;
-  for (int64_t i = 0; i < npairs; ++i) {
-    if (pairs[i].q_idx < 0 || pairs[i].q_idx >= s.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= s.n)
-      return fail(AWV_ERR_ARG, "align_pairs: sequence index out of range");
-  }
-  // multi-step passes (biwfa_device.hpp, compute_rows_multi): T steps per pass, T <= the nearest M source
-  // (so that every M row a pass reads was written by an earlier pass); instantiated for the I/D depths
-  // of the reference's presets (2-piece: e1 = 2 / e2 = 1; gap-affine: e = 1 or 2)
-  int multi_T = std::min(std::min(dp.x, dp.o1 + dp.e1), awv::TMAX);
-  if (dp.two_piece) multi_T = std::min(multi_T, dp.o2 + dp.e2);
-  if (dp.two_piece ? (dp.e1 != 2 || dp.e2 != 1) : (dp.e1 != 1 && dp.e1 != 2)) multi_T = 0;
-  if (multi_T < 2 || (e->cfg.flags & AWV_F_SINGLE_STEP)) multi_T = 0;
-  // chained sweeps (compute_rows_multi, CHAIN): the previous one / two sweeps' M rows are this sweep's sources 5 and 10
-  // scores back -- only with x = TMAX and o1 + e1 = 2 TMAX (the default scores); the third source must still come from
-  // earlier passes: TMAX * chain_max <= o2 + e2
-  int chain_max = 1;
-  if (multi_T == awv::TMAX && dp.two_piece && dp.x == awv::TMAX && dp.o1 + dp.e1 == 2 * awv::TMAX && !(e->cfg.flags & AWV_F_NO_CHAIN))
-    chain_max = std::max(1, std::min(awv::CHAIN_MAX, (dp.o2 + dp.e2) / awv::TMAX));
-  int ring = 4;
-  while (ring < dp.scope + 2 + (multi_T > 0 ? multi_T * chain_max - 1 : 0)) ring *= 2;
-  if (ring > awv::MAX_RING) return fail(AWV_ERR_PENALTIES, "ring of " + std::to_string(ring) + " rows exceeds MAX_RING");  // (unreachable: MAX_SCOPE)
-  const int64_t max_batch = e->cfg.max_batch_pairs > 0 ? e->cfg.max_batch_pairs : (int64_t)1 << 20;
-  uint64_t max_arena = e->cfg.max_arena_bytes > 0 ? (uint64_t)e->cfg.max_arena_bytes : (uint64_t)8 << 30;
-  // Experiment knobs read from the environment exist only in a -DAWV_DEBUG_KNOBS build; the product library's
-  // behaviour depends on its arguments alone.
-#ifdef AWV_DEBUG_KNOBS
-  if (const char* env = getenv("AWV_MAX_ARENA_MB")) max_arena = std::max<uint64_t>(1, (uint64_t)atoll(env)) << 20;
-  const bool inline_sink = getenv("AWV_INLINE_SINK") != nullptr;  // every sink on the calling thread
-#else
-  const bool inline_sink = false;
-#endif
-  // base-case capacities: score_remaining <= 250 or both lengths <= 100
-  // A sub-problem that ends in an indel component pays that gap's open on top of the
-  // score_remaining its parent hands down (the reverse aligner starts with the open pre-paid).
-  const long long sb = std::max<long long>(FALLBACK_MIN_SCORE + std::max(dp.o1, dp.o2),
-                                           worst_case_penalty(dp, FALLBACK_MIN_LENGTH));
-  if (sb > 4000) return fail(AWV_ERR_PENALTIES, "penalties too large for the base-case history");
-  const int sb_cap = (int)sb;
-  const int wb_cap = ((2 * sb_cap + 9 + 2 * COL_PAD) + 63) & ~63;
-  // dynamic LDS: metadata region (BiWFA ring metadata, aliased with the base-case table) + sequences
-  auto lds_meta_bytes = [&](size_t meta_elem, bool twin_rec) {
-    // (the last 32 bytes: the swapped pair's breakpoint of a twin search, biwfa_device.hpp bialign_overlap)
-    return ((size_t)2 * NCOMP * ring * meta_elem + (size_t)4 * ring * sizeof(int) + (size_t)dp.scope * NCOMP * sizeof(int) +
-            (twin_rec ? sizeof(awv::Breakpoint) : 0) + 15) & ~(size_t)15;
-  };
+// What one call asks for; every aligning entry point of the C ABI fills one.
+struct AlignRequest {
+  const awv_pair* pairs = nullptr;
+  int64_t npairs = 0;
+  awv_result* out = nullptr;
+  awv_sink sink = nullptr;
+  void* user = nullptr;
+  // awv_score_pairs: the top-level search's score only, no CIGAR arena (so max_arena_bytes does not cut batches)
+  bool score_only = false;
+  // the call's bound (INT_MAX = none), or pair i's own bound instead (nullable; INT_MAX = none).  A full alignment may carry
+  // bounds too (awv_align_pairs_bounded): they stop the pair's top-level search, nothing below it
+  int max_penalty = INT_MAX;
+  const int32_t* pair_bound = nullptr;
+  // (nullable; awv_align_pairs_verified, on the engine's own sequence set): every batch's records and op bytes are checked on
+  // the device before the batch's CIGARs are copied back
+  awv_verify_result* vout = nullptr;
+  // (nullable; the awv_*_ranges calls): pair i aligns the rectangle spans[i] of its two sequences, in pattern / text
+  // coordinates and already validated, instead of the whole of them -- every length of the plan is then the rectangle's
+  const awvr::Span* spans = nullptr;
+  // (nullable; awv_align_pairs_clipped): every batch's op strings are clipped on the device under match_bonus, after the check
+  // and before the batch's CIGARs are copied back
+  awv_clip_result* cout = nullptr;
+  int32_t match_bonus = 0;
+  // (nullable; awv_align_pairs_split): likewise split into all segments of at least split->min_score, into the caller's slot
+  // layout (already checked against the slot rule)
+  const SplitOut* split = nullptr;
+};
 
-#ifdef AWV_DEBUG_KNOBS
-  const bool timing = getenv("AWV_TIMING") != nullptr;  // diagnostic: host-side stage times on stderr
-#else
-  const bool timing = false;
-#endif
-  const auto tl0 = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (timing) fprintf(stderr, "[awv] %-22s %.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - tl0).count());
-  };
-  // the (pattern, text) lengths pair gi of the call is aligned over: what cost order, kernel flavour, row width, row capacity and
-  // the CIGAR arena are decided by
-  auto pair_lens = [&](int64_t gi, int& ql, int& tl) {
-    if (spans) {
-      ql = spans[gi].pe - spans[gi].pb;
-      tl = spans[gi].te - spans[gi].tb;
-    } else {
-      ql = s.len[pairs[gi].q_idx];
-      tl = s.len[pairs[gi].t_idx];
-    }
-  };
-  std::vector<int32_t> hq, ht, hrc, hbound, hufirst, hutwin;
-  // twin units only where the plain alignment or the plain score is asked for: whole pairs, no bound, re-runs allowed
-  const bool twin_ok = max_penalty == INT_MAX && !pair_bound && !spans && !cout &&
-                       !(e->cfg.flags & (AWV_F_NO_TWIN | AWV_F_NO_RERUN));
-  std::vector<awvr::Span> hspan;
-  std::vector<uint64_t> hoff;
-  std::vector<awv_result> hres;
-  int64_t first = 0;
-  double kernel_ms = 0, h2d_ms = 0, d2h_ms = 0;
-  unsigned long long stat_tot[STAT_N_DEV] = {0};
-  uint64_t launches = 0;
-  // With several batches in a call, the sink of batch i (the caller's formatting and output) runs on a
-  // helper thread while batch i+1 is carved, launched and copied back.  It is joined before the next
-  // sink starts: sinks never overlap, come in batch order, and a batch's result / CIGAR buffers stay
-  // untouched until its sink has returned.  The last batch's sink runs on the calling thread.
-  struct SinkRunner {
-    std::thread th;
-    int rc = 0;
-    std::vector<awv_result> res;
-    std::vector<uint8_t> cig;
-    int wait() {
-      if (th.joinable()) th.join();
-      const int r = rc;
-      rc = 0;
-      return r;
-    }
-    ~SinkRunner() { if (th.joinable()) th.join(); }
-  } runner;
-  while (first < npairs) {
-    // ---- carve a batch
-    int64_t n = 0;
-    uint64_t arena = 0;
-    int maxsum = 0, maxlen = 0;
-    hq.clear(); ht.clear(); hrc.clear(); hoff.clear();
-    while (first + n < npairs && n < max_batch) {
-      const awv_pair& p = pairs[first + n];
-      int ql, tl;
-      pair_lens(first + n, ql, tl);
-      const uint64_t need = score_only ? 0 : ((uint64_t)ql + (uint64_t)tl + 7) & ~(uint64_t)7;
-      if (n > 0 && arena + need > max_arena) break;
-      hq.push_back(p.q_idx);
-      ht.push_back(p.t_idx);
-      hrc.push_back(p.q_revcomp ? 1 : 0);
-      hoff.push_back(arena);
-      arena += need;
-      maxsum = std::max(maxsum, ql + tl);
-      maxlen = std::max(maxlen, std::max(ql, tl));
-      ++n;
-    }
-    // Dispatch order: workgroups take pairs from a shared cursor, so the most expensive pairs go
-    // first (longest-processing-time-first; the work of a pair grows with the square of its score,
-    // estimated here from the lengths and the gap a length difference forces).  Results and CIGARs
-    // keep their caller-order slots through the index map.  Equal-cost batches keep caller order.
-    std::vector<int64_t> amap;  // dispatch index -> batch index (empty = identity)
-    bool skewed = false;  // the most expensive pair costs several times the median one
-    {
-      std::vector<int64_t> order((size_t)n);
-      std::vector<uint64_t> cost((size_t)n);
-      bool uniform = true;
-      for (int64_t i = 0; i < n; ++i) {
-        order[(size_t)i] = i;
-        int ql, tl;
-        pair_lens(first + i, ql, tl);
-        cost[(size_t)i] = (uint64_t)((int64_t)ql + tl + 4 * std::llabs((int64_t)ql - tl));
-        uniform = uniform && cost[(size_t)i] == cost[0];
-      }
-      if (!uniform) {
-        std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return cost[(size_t)a] > cost[(size_t)b]; });
-        std::vector<int32_t> q2((size_t)n), t2((size_t)n), rc2((size_t)n);
-        std::vector<uint64_t> off2((size_t)n);
-        for (int64_t i = 0; i < n; ++i) {
-          const size_t o = (size_t)order[(size_t)i];
-          q2[(size_t)i] = hq[o]; t2[(size_t)i] = ht[o]; rc2[(size_t)i] = hrc[o]; off2[(size_t)i] = hoff[o];
-        }
-        hq.swap(q2); ht.swap(t2); hrc.swap(rc2); hoff.swap(off2);
-        skewed = cost[(size_t)order[0]] >= 3 * cost[(size_t)order[(size_t)n / 2]];
-        amap.swap(order);
-      }
-    }
-    if (int rc = e->d_pair_q.reserve((size_t)n)) return rc;
-    if (int rc = e->d_pair_t.reserve((size_t)n)) return rc;
-    if (int rc = e->d_pair_rc.reserve((size_t)n)) return rc;
-    if (int rc = e->d_cigar_off.reserve((size_t)n)) return rc;
-    if (int rc = e->d_results.reserve((size_t)n)) return rc;
-    if (int rc = e->d_cigar.reserve((size_t)arena + 64)) return rc;
-    if (int rc = e->d_counters.reserve(1 + STAT_N_DEV)) return rc;
-    static_assert(sizeof(awv_result) == sizeof(DevResult), "result layout");
-    hres.assign((size_t)n, awv_result{});
-    // One group of the batch = one kernel flavour: `wide` pairs get a 256-thread workgroup each (four
-    // waves deal a row's windows among themselves), the others one wave each.
-    auto run_group = [&](std::vector<int32_t> hq, std::vector<int32_t> ht, std::vector<int32_t> hrc, std::vector<uint64_t> hoff,
-                         std::vector<int64_t> amap, int waves, int width, int g_maxsum, int g_maxlen, bool reserve_only) -> int {
-    // width: 0 = 16-bit rows (both lengths < 32760), 1 = 32-bit rows, 2 = 16-bit rows holding min(h, v) with 32-bit
-    // row metadata (AWV_WIDE16: only the shorter length < 32760)
-    const bool narrow = width != 1, wide_meta = width == 2;
-    if (hq.empty()) return AWV_OK;
-    // 16-bit wavefront rows whenever every offset fits (halves the HBM/L2 traffic of the rings): the caller
-    // groups pairs by row width, so one long sequence no longer drags a whole batch to 32-bit rows
-    const size_t esz = narrow ? 2 : 4;
-    // Row offsets inside a workgroup's ring arena are 32-bit and its buffer descriptor holds at most 2^31 - 1 bytes
-    // (row_off, make_rsrc in biwfa_device.hpp): a row past 2 GiB would read 0 and lose its writes.  So no attempt, the first
-    // or a re-run, uses rows wider than wc_2g columns: with 32-bit rows 838,656 at ring 64, 419,328 at ring 128 and 209,664
-    // at ring 256; with 16-bit rows 1,677,568 at ring 64 and 838,656 at ring 128.
-    const int wc_2g = (int)(((size_t)INT32_MAX / ((size_t)2 * NCOMP * ring * esz)) & ~(size_t)255);
-    {
-      // A pair whose length difference alone cannot fit such rows ends CAPACITY here, before any launch (the kernel would
-      // find out only after a long search).  The two searches meet on one diagonal, and a row of wc columns reaches at
-      // most half + COL_PAD - 2 diagonals beyond its search's origin on either side: find_breakpoint clips its diagonal
-      // range to half = (wc - 2 COL_PAD - 9 - 256) / 2 on each side, and the capacity test of compute_row keeps 257 / 262
-      // columns at the row's ends.  So the searches span at most 2 half + 2 COL_PAD diagonals between them.
-      const long long span = 2 * (((long long)wc_2g - 2 * COL_PAD - 9 - 256) / 2) + 2 * COL_PAD;
-      if (amap.empty()) {
-        amap.resize(hq.size());
-        for (size_t i = 0; i < hq.size(); ++i) amap[i] = (int64_t)i;
-      }
-      size_t k = 0;
-      g_maxsum = g_maxlen = 0;
-      for (size_t i = 0; i < hq.size(); ++i) {
-        int ql, tl;
-        pair_lens(first + amap[i], ql, tl);
-        if (ql > 0 && tl > 0 && std::llabs((long long)ql - tl) > span) {
-          awv_result r{};
-          r.status = AWV_ST_CAPACITY;
-          r.cigar_off = hoff[i];
-          hres[(size_t)amap[i]] = r;
-          continue;
-        }
-        amap[k] = amap[i];
-        hq[k] = hq[i]; ht[k] = ht[i]; hrc[k] = hrc[i]; hoff[k] = hoff[i];
-        g_maxsum = std::max(g_maxsum, ql + tl);
-        g_maxlen = std::max(g_maxlen, std::max(ql, tl));
-        ++k;
-      }
-      hq.resize(k); ht.resize(k); hrc.resize(k); hoff.resize(k); amap.resize(k);
-      if (k == 0) return AWV_OK;
-    }
-    const int wg = 64 * waves;
-    const int nslots_g = e->cfg.workgroups > 0 ? std::max(1, e->cfg.workgroups / (wg / 64)) : (WAVES_PER_SIMD * 256 / wg) * e->num_cus;
-    const int wcap_full = ((g_maxsum + 9 + 256 + 2 * COL_PAD) + 255) & ~255;
-    const int nslots_want = (int)std::min<int64_t>(nslots_g, (int64_t)hq.size());
-    // dynamic LDS = ring metadata (16-bit entries with 16-bit rows) + staging of the 2-bit packed
-    // sequences: what the largest pair needs, within 160 KB / (16 waves per CU) per workgroup;
-    // sub-problems that do not fit read global memory instead
-    // twin units only in a group that runs the kernel built with them: one wave per pair, 16-bit rows.  Only
-    // there do the LDS metadata (32 B: the twin record) and the event arena (the last-hit table) grow.
-    const bool twin_here = twin_ok && waves == 1 && width == 0;
-    const size_t ev_extra = EV_EXTRA + (twin_here ? (size_t)awv::EV_TWIN_WORDS : 0);
-    const size_t lds_meta = lds_meta_bytes(narrow && !wide_meta ? sizeof(RowMeta16) : sizeof(RowMeta), twin_here);
-    const size_t seq_need = ((((size_t)g_maxlen + 15) / 16 + 2) * 2 + 10) * 4;
-    const size_t lds_budget = (size_t)(160 * 1024 / (WAVES_PER_SIMD * 256 / wg)) - STATIC_LDS_RESERVE;
-    size_t lds_seq = (e->cfg.flags & AWV_F_NO_PACKED_SEQ) ? 0 : (lds_meta < lds_budget ? std::min(seq_need, lds_budget - lds_meta) : 0);
-    lds_seq &= ~(size_t)15;
-    const size_t dyn_lds = lds_meta + lds_seq;
-    const size_t hist_rows = ((size_t)(sb_cap + 1) * NCOMP * wb_cap * esz + 63) & ~(size_t)63;
-    const size_t hist_stride = hist_rows + (((size_t)(sb_cap + 1) * NCOMP * sizeof(RowMeta) + 63) & ~(size_t)63);
-    // per-workgroup arenas as a function of the row capacity (columns)
-    const size_t budget = e->cfg.max_scratch_bytes > 0 ? (size_t)e->cfg.max_scratch_bytes : (size_t)160 << 30;
-    auto per_slot = [&](int wc) {
-      return (size_t)2 * NCOMP * ring * wc * esz + hist_stride + (size_t)(wc + ev_extra) * sizeof(uint32_t);
-    };
-    // Row capacity of the first attempt.  A wavefront at score s spans at most ~2 s / min(e) diagonals,
-    // far fewer than plen + tlen for similar sequences; when full-width rows would not leave room for
-    // every workgroup's arenas (long sequences), start with the widest rows that do and re-run only
-    // the pairs whose wavefronts outgrow them (status CAPACITY) with wider rows.
-    // Half-width rows (at least 8192 columns) already hold every pair whose optimal score is below
-    // about a quarter of plen + tlen; they halve the arenas (allocating -- and the driver clearing --
-    // tens of GB is the largest fixed cost of a call) and only unusually divergent pairs are re-run.
-    // (a length difference forces a gap that long: the rows must span it in both directions)
-    int g_maxdelta = 0;
-    for (size_t i = 0; i < hq.size(); ++i) {
-      int ql, tl;
-      pair_lens(first + amap[i], ql, tl);
-      g_maxdelta = std::max(g_maxdelta, std::abs(ql - tl));
-    }
-    int wcap = std::min(wcap_full, std::max(std::max(8192, (wcap_full / 2 + 255) & ~255), (2 * g_maxdelta + 4096 + 255) & ~255));
-    if (per_slot(wcap) * (size_t)nslots_want > budget) {
-      const size_t fixed = hist_stride + ev_extra * sizeof(uint32_t);
-      const size_t per_col = (size_t)2 * NCOMP * ring * esz + sizeof(uint32_t);
-      const size_t share = budget / (size_t)nslots_want;
-      long long wc = share > fixed ? (long long)((share - fixed) / per_col) : 0;
-      wc = std::max<long long>(wc & ~255LL, 8192);
-      wcap = (int)std::min<long long>(wcap, wc);
-    }
-    // (diagnostic / test hook: a narrower first attempt, so that the CAPACITY re-run path can be exercised on short sequences)
-    if (e->cfg.first_row_cols > 0) wcap = std::min(wcap, std::max(2048, (e->cfg.first_row_cols + 255) & ~255));
-    wcap = std::min(wcap, wc_2g);
-    const int wc_last = std::min(wcap_full, wc_2g);  // the widest rows a re-run may use
-    // ---- attempts: the whole batch at row capacity `wcap`, then only the pairs that outgrew it
-    std::vector<awv_result> tres;
-    float ms = 0;
-    for (int wc = wcap;;) {
-      const int64_t m = (int64_t)hq.size();
-      const size_t ring_stride = (size_t)2 * NCOMP * ring * wc * esz;
-      const size_t ev_stride = (size_t)wc + ev_extra;  // run-length events + the DFS stack
-      int nslots = (int)std::min<int64_t>(nslots_g, m);
-      {  // keep the per-workgroup arenas inside the scratch budget (default 160 GiB of the 288 GB HBM)
-        const size_t fit = std::max<size_t>(1, budget / per_slot(wc));
-        if ((size_t)nslots > fit) nslots = (int)fit;
-      }
-      if (ring_stride * nslots > e->ring_mem.cap) {  // the ring arena grows: choose where it lies (see arena_probe_kernel)
-        const size_t want = ring_stride * (size_t)nslots + ((size_t)64 << 20);
-        size_t free_b = 0, total_b = 0;
-        e->ring_mem.release();
-        (void)hipMemGetInfo(&free_b, &total_b);
-        int ncand = (e->cfg.flags & AWV_F_NO_ARENA_PROBE) ? 1 : 4;
-        while (ncand > 1 && (size_t)ncand * want > free_b / 10 * 8) --ncand;  // all candidates are alive at once
-        const bool probe_ok = ncand > 1 && want >= ((size_t)1 << 30) && esz == 2 && ring_stride >= (size_t)2 * 5 * 32 * 4096 &&
-                              (size_t)wc * esz >= 4096;
-        if (!probe_ok) ncand = 1;
-        uint8_t* cand[4] = {nullptr, nullptr, nullptr, nullptr};
-        float cms[4] = {0, 0, 0, 0};
-        int best = -1;
-        for (int c = 0; c < ncand; ++c) {
-          if (hipMalloc((void**)&cand[c], want) != hipSuccess) { cand[c] = nullptr; (void)hipGetLastError(); break; }
-          if (ncand == 1) { best = 0; break; }
-          float tbest = 1e30f;
-          hipError_t perr = hipSuccess;
-          for (int rep = 0; rep < 2 && perr == hipSuccess; ++rep) {
-            float pms = 0;
-            if ((perr = hipEventRecord(e->ev0, e->stream)) != hipSuccess) break;
-            hipLaunchKernelGGL(arena_probe_kernel, dim3(nslots), dim3(64), 0, e->stream, cand[c], ring_stride, (int)((size_t)wc * esz), 24,
-                               std::min(1400, wc - 2048), e->d_counters.p);
-            if ((perr = hipEventRecord(e->ev1, e->stream)) != hipSuccess) break;
-            if ((perr = hipEventSynchronize(e->ev1)) != hipSuccess) break;
-            if ((perr = hipEventElapsedTime(&pms, e->ev0, e->ev1)) != hipSuccess) break;
-            tbest = std::min(tbest, pms);
-          }
-          if (perr != hipSuccess) {  // nothing may stay allocated behind an error return
-            for (int k = 0; k < 4; ++k)
-              if (cand[k]) (void)hipFree(cand[k]);
-            return fail(AWV_ERR_HIP, std::string("ring arena probe: ") + hipGetErrorString(perr));
-          }
-          cms[c] = tbest;
-          if (best < 0 || tbest < cms[best]) best = c;
-          if (timing) fprintf(stderr, "[awv] ring arena candidate %d at %p: %.2f ms\n", c, (void*)cand[c], tbest);
-        }
-        if (best < 0) return fail(AWV_ERR_OOM, "hipMalloc " + std::to_string(want) + " bytes for the ring arena failed");
-        for (int c = 0; c < 4; ++c)
-          if (c != best && cand[c]) (void)hipFree(cand[c]);
-        e->ring_mem.adopt(cand[best], want);
-      }
-      if (int rc = e->hist_mem.reserve(hist_stride * nslots)) return rc;
-      if (int rc = e->ev_mem.reserve(ev_stride * nslots)) return rc;
-      if (reserve_only) return AWV_OK;  // (first pass over the groups: one allocation covers them all)
-      lap("arenas reserved");
-      if (timing) fprintf(stderr, "[awv] ring arena %p (%zu MiB), hist %p, cigar %p\n", (void*)e->ring_mem.p, e->ring_mem.bytes() >> 20, (void*)e->hist_mem.p, (void*)e->d_cigar.p);
-      // ---- H2D
-      AWV_TRY(hipEventRecord(e->ev0, e->stream));
-      AWV_TRY(hipMemcpyAsync(e->d_pair_q.p, hq.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-      AWV_TRY(hipMemcpyAsync(e->d_pair_t.p, ht.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-      AWV_TRY(hipMemcpyAsync(e->d_pair_rc.p, hrc.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-      AWV_TRY(hipMemcpyAsync(e->d_cigar_off.p, hoff.data(), (size_t)m * 8, hipMemcpyHostToDevice, e->stream));
-      if (pair_bound) {  // (amap: dispatch index -> batch index, kept through the sort, the groups and the re-runs)
-        hbound.resize((size_t)m);
-        for (int64_t i = 0; i < m; ++i) hbound[(size_t)i] = pair_bound[first + amap[(size_t)i]];
-        if (int rc = e->d_pair_bound.reserve((size_t)m)) return rc;
-        AWV_TRY(hipMemcpyAsync(e->d_pair_bound.p, hbound.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-      }
-      if (spans) {
-        hspan.resize((size_t)m);
-        for (int64_t i = 0; i < m; ++i) hspan[(size_t)i] = spans[first + amap[(size_t)i]];
-        if (int rc = e->d_pair_span.reserve((size_t)m)) return rc;
-        AWV_TRY(hipMemcpyAsync(e->d_pair_span.p, hspan.data(), (size_t)m * sizeof(awvr::Span), hipMemcpyHostToDevice, e->stream));
-      }
-      // ---- twin units: an entry (q, t) and its swapped entry (t, q) of this launch share their breakpoint searches (DESIGN.md
-      // 4.20).  Entries are in descending cost order and a twin costs what its partner costs, so units ordered by their
-      // summed cost are the twin units in entry order, then the single ones.
-      int64_t nunits = m;
-      if (twin_here) {
-        const awvt::TwinPlan tp = awvt::plan_twins(hq.data(), ht.data(), hrc.data(), (size_t)m);
-        std::vector<size_t> uo(tp.first.size());
-        for (size_t u = 0; u < uo.size(); ++u) uo[u] = u;
-        auto ucost = [&](size_t u) {
-          int ql, tl;
-          pair_lens(first + amap[(size_t)tp.first[u]], ql, tl);
-          const uint64_t c = (uint64_t)((int64_t)ql + tl + 4 * std::llabs((int64_t)ql - tl));
-          return tp.twin[u] >= 0 ? 2 * c : c;
-        };
-        std::stable_sort(uo.begin(), uo.end(), [&](size_t a, size_t b) { return ucost(a) > ucost(b); });
-        hufirst.resize(uo.size());
-        hutwin.resize(uo.size());
-        for (size_t u = 0; u < uo.size(); ++u) {
-          hufirst[u] = tp.first[uo[u]];
-          hutwin[u] = tp.twin[uo[u]];
-        }
-        nunits = (int64_t)uo.size();
-        if (int rc = e->d_unit_first.reserve((size_t)nunits)) return rc;
-        if (int rc = e->d_unit_twin.reserve((size_t)nunits)) return rc;
-        AWV_TRY(hipMemcpyAsync(e->d_unit_first.p, hufirst.data(), (size_t)nunits * 4, hipMemcpyHostToDevice, e->stream));
-        AWV_TRY(hipMemcpyAsync(e->d_unit_twin.p, hutwin.data(), (size_t)nunits * 4, hipMemcpyHostToDevice, e->stream));
-      }
-      AWV_TRY(hipMemsetAsync(e->d_counters.p, 0, (1 + STAT_N_DEV) * sizeof(unsigned long long), e->stream));
-      AWV_TRY(hipEventRecord(e->ev1, e->stream));
-      AWV_TRY(hipEventSynchronize(e->ev1));
-      AWV_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-      h2d_ms += ms;
-      // ---- launch
-      KParams kp{};
-      for (int v = 0; v < 4; ++v) kp.seq[v] = s.d_seq[v].p;
-      kp.seq_off = s.d_off.p;
-      kp.seq_len = s.d_len.p;
-      kp.seq2[0] = s.d_seq2[0].p;
-      kp.seq2[1] = s.d_seq2[1].p;
-      kp.seq2_off = s.d_off2.p;
-      kp.seq2_ok = s.d_ok2.p;
-      kp.pair_q = e->d_pair_q.p;
-      kp.pair_t = e->d_pair_t.p;
-      kp.pair_rc = e->d_pair_rc.p;
-      kp.npairs = nunits;  // dispatch units: entries, or entries with their twins
-      kp.unit_first = twin_here ? e->d_unit_first.p : nullptr;
-      kp.unit_twin = twin_here ? e->d_unit_twin.p : nullptr;
-      kp.twin_levels = (e->cfg.flags & AWV_F_TWIN_TOP_ONLY) ? 1 : INT_MAX;
-      kp.twin_base = (e->cfg.flags & AWV_F_NO_TWIN_BASE) ? 0 : 1;
-      kp.pen = dp;
-      kp.ring = ring;
-      // 32-bit rows: sweeps of at most TMAX32 scores, at most CHAIN_MAX32 of them chained (a lane vector is four registers)
-      kp.multi_T = narrow ? multi_T : (std::min(multi_T, awv::TMAX32) >= 2 ? std::min(multi_T, awv::TMAX32) : 0);
-      kp.deep_passes = (kp.multi_T > 0 && !(e->cfg.flags & AWV_F_NO_DEEP)) ? 1 : 0;
-      kp.sub16 = (e->cfg.flags & AWV_F_FORCE_INT32) ? 0 : 1;  // (the pin means 32-bit rows throughout)
-      // (32-bit rows: two sweeps chained through registers, a third when the kernel finds room for its chain rows in LDS -- the
-      // kernel caps what it is offered: biwfa_device.hpp, multi_phase's lds_chain)
-      kp.chain_max = narrow ? chain_max : (awv::TMAX32 == awv::TMAX ? std::min(chain_max, 3) : 1);
-      kp.wcap = wc;
-      kp.ring_mem = e->ring_mem.p;
-      kp.ring_slot_stride = ring_stride;
-      kp.lds_meta_bytes = (int)lds_meta;
-      kp.lds_seq_bytes = (int)lds_seq;
-      kp.sb_cap = sb_cap;
-      kp.wb_cap = wb_cap;
-      kp.hist_mem = e->hist_mem.p;
-      kp.hist_slot_stride = hist_stride;
-      kp.hist_meta_offset = hist_rows;
-      kp.ev_mem = e->ev_mem.p;
-      kp.ev_slot_stride = ev_stride;
-      kp.cigar = e->d_cigar.p;
-      kp.cigar_off = e->d_cigar_off.p;
-      kp.results = e->d_results.p;
-      kp.work_counter = e->d_counters.p;
-      kp.stats = e->d_counters.p + 1;
-      kp.score_only = score_only ? 1 : 0;
-      kp.max_penalty = max_penalty;
-      kp.pair_max_penalty = pair_bound ? e->d_pair_bound.p : nullptr;
-      const awvr::Span* const d_span = spans ? e->d_pair_span.p : nullptr;  // (range launches: the kernels' two-argument instantiations)
-      const bool ranged = spans != nullptr;
-      AWV_TRY(hipEventRecord(e->ev0, e->stream));
-      auto launch = [&](auto kern, const auto& kparams) -> int {
-        AWV_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
-        hipLaunchKernelGGL(kern, dim3(nslots), dim3(wg), dyn_lds, e->stream, kparams);
-        return AWV_OK;
-      };
-      auto launch_ranges = [&](auto kern, const auto& kparams) -> int {
-        AWV_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
-        hipLaunchKernelGGL(kern, dim3(nslots), dim3(wg), dyn_lds, e->stream, kparams, d_span);
-        return AWV_OK;
-      };
-      int lrc;
-      static_assert(sizeof(awvw::KParams) == sizeof(awv::KParams) && sizeof(awvx::KParams) == sizeof(awv::KParams),
-                    "same parameter block for every workgroup size");
-      if (waves == 1) {
-        AWV_TRY((hipError_t)awv_launch_one_wave(dp.two_piece, narrow ? 1 : 0, d_span, (unsigned)nslots, dyn_lds, e->stream, &kp));
-        lrc = AWV_OK;
-      } else if (wide_meta) {
-        static_assert(sizeof(awvw_m::KParams) == sizeof(awv::KParams) && sizeof(awvx_m::KParams) == sizeof(awv::KParams), "same parameter block");
-        if (waves == 4) {
-          awvw_m::KParams kw;
-          std::memcpy(&kw, &kp, sizeof(kw));
-          lrc = dp.two_piece ? (ranged ? launch_ranges(awvw_m::biwfa_align_kernel<true, int16_t, const awvr::Span*>, kw) : launch(awvw_m::biwfa_align_kernel<true, int16_t>, kw)) : (ranged ? launch_ranges(awvw_m::biwfa_align_kernel<false, int16_t, const awvr::Span*>, kw) : launch(awvw_m::biwfa_align_kernel<false, int16_t>, kw));
-        } else {
-          awvx_m::KParams kx;
-          std::memcpy(&kx, &kp, sizeof(kx));
-          lrc = dp.two_piece ? (ranged ? launch_ranges(awvx_m::biwfa_align_kernel<true, int16_t, const awvr::Span*>, kx) : launch(awvx_m::biwfa_align_kernel<true, int16_t>, kx)) : (ranged ? launch_ranges(awvx_m::biwfa_align_kernel<false, int16_t, const awvr::Span*>, kx) : launch(awvx_m::biwfa_align_kernel<false, int16_t>, kx));
-        }
-      } else if (waves == 4) {
-        awvw::KParams kw;
-        std::memcpy(&kw, &kp, sizeof(kw));
-        if (dp.two_piece) lrc = narrow ? (ranged ? launch_ranges(awvw::biwfa_align_kernel<true, int16_t, const awvr::Span*>, kw) : launch(awvw::biwfa_align_kernel<true, int16_t>, kw)) : (ranged ? launch_ranges(awvw::biwfa_align_kernel<true, int32_t, const awvr::Span*>, kw) : launch(awvw::biwfa_align_kernel<true, int32_t>, kw));
-        else lrc = narrow ? (ranged ? launch_ranges(awvw::biwfa_align_kernel<false, int16_t, const awvr::Span*>, kw) : launch(awvw::biwfa_align_kernel<false, int16_t>, kw)) : (ranged ? launch_ranges(awvw::biwfa_align_kernel<false, int32_t, const awvr::Span*>, kw) : launch(awvw::biwfa_align_kernel<false, int32_t>, kw));
-      } else {
-        awvx::KParams kx;
-        std::memcpy(&kx, &kp, sizeof(kx));
-        if (dp.two_piece) lrc = narrow ? (ranged ? launch_ranges(awvx::biwfa_align_kernel<true, int16_t, const awvr::Span*>, kx) : launch(awvx::biwfa_align_kernel<true, int16_t>, kx)) : (ranged ? launch_ranges(awvx::biwfa_align_kernel<true, int32_t, const awvr::Span*>, kx) : launch(awvx::biwfa_align_kernel<true, int32_t>, kx));
-        else lrc = narrow ? (ranged ? launch_ranges(awvx::biwfa_align_kernel<false, int16_t, const awvr::Span*>, kx) : launch(awvx::biwfa_align_kernel<false, int16_t>, kx)) : (ranged ? launch_ranges(awvx::biwfa_align_kernel<false, int32_t, const awvr::Span*>, kx) : launch(awvx::biwfa_align_kernel<false, int32_t>, kx));
-      }
-      if (lrc != AWV_OK) return lrc;
-      AWV_TRY(hipGetLastError());
-      AWV_TRY(hipEventRecord(e->ev1, e->stream));
-      // while the kernel runs: get the host CIGAR buffer's pages in place (0.2 s for config 2's 670 MB)
-      if (sink && !score_only && !(e->cfg.flags & AWV_F_KEEP_ON_DEVICE) && e->h_cigar.size() < (size_t)arena + 64) e->h_cigar.resize((size_t)arena + 64);
-      AWV_TRY(hipEventSynchronize(e->ev1));
-      AWV_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-      kernel_ms += ms;
-      ++launches;
-      lap("kernel done");
-      // ---- D2H (results + counters)
-      tres.resize((size_t)m);
-      AWV_TRY(hipEventRecord(e->ev0, e->stream));
-      AWV_TRY(hipMemcpyAsync(tres.data(), e->d_results.p, (size_t)m * sizeof(awv_result), hipMemcpyDeviceToHost, e->stream));
-      unsigned long long hstat[1 + STAT_N_DEV];
-      AWV_TRY(hipMemcpyAsync(hstat, e->d_counters.p, sizeof(hstat), hipMemcpyDeviceToHost, e->stream));
-      AWV_TRY(hipEventRecord(e->ev1, e->stream));
-      AWV_TRY(hipEventSynchronize(e->ev1));
-      AWV_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-      d2h_ms += ms;
-      for (int i = 0; i < STAT_N_DEV; ++i) stat_tot[i] += hstat[1 + i];
-      // ---- scatter; collect the pairs to re-run with wider rows
-      std::vector<int64_t> again;
-      for (int64_t i = 0; i < m; ++i) {
-        const int64_t bi = amap.empty() ? i : amap[(size_t)i];
-        hres[(size_t)bi] = tres[(size_t)i];
-        if (tres[(size_t)i].status == AWV_ST_CAPACITY && wc < wc_last && !(e->cfg.flags & AWV_F_NO_RERUN)) again.push_back(i);
-      }
-      if (again.empty()) break;
-      std::vector<int32_t> q2, t2, rc2;
-      std::vector<uint64_t> off2;
-      std::vector<int64_t> map2;
-      for (int64_t i : again) {
-        q2.push_back(hq[(size_t)i]);
-        t2.push_back(ht[(size_t)i]);
-        rc2.push_back(hrc[(size_t)i]);
-        off2.push_back(hoff[(size_t)i]);
-        map2.push_back(amap.empty() ? i : amap[(size_t)i]);
-      }
-      hq.swap(q2); ht.swap(t2); hrc.swap(rc2); hoff.swap(off2); amap.swap(map2);
-      wc = (int)std::min<long long>(wc_last, 4LL * wc);
-    }
-    return AWV_OK;
-    };
-    {
-      // One group = one kernel flavour x one row width.  Flavour: all of a small batch goes four waves per pair
-      // (latency), and so do pairs of long sequences (rows tens of windows wide; measured +17 % on 100 kbp
-      // pairs) and pairs a length difference makes expensive -- pair by pair, so that the short pairs of a
-      // mixed set (config 5) keep the throughput flavour.  Row width: 16-bit rows when both lengths fit.
-      const bool never_wide = (e->cfg.flags & AWV_F_ONE_WAVE) != 0;
-      // (a batch of uneven pairs that fits the machine about once is bound by its longest pairs, not by throughput)
-      const bool all_wide = !never_wide && ((e->cfg.flags & AWV_F_FOUR_WAVES) || n <= (int64_t)(WAVES_PER_SIMD * e->num_cus) ||
-                                            (skewed && n <= (int64_t)(4 * WAVES_PER_SIMD * e->num_cus)));
-      constexpr int NG = 9;  // group = flavour (0 one wave, 1 four, 2 sixteen) * 3 + row width (0: 16-bit, 1: 32-bit, 2: 16-bit min(h, v) rows)
-      std::vector<int32_t> q[NG], t[NG], rc[NG];
-      std::vector<uint64_t> off[NG];
-      std::vector<int64_t> map[NG];
-      int gsum[NG] = {0}, glen[NG] = {0};
-      // sixteen waves per pair only pay while such pairs are too few to fill the machine four waves at a time
-      // (dispatch index -> the pair's index in the call)
-      auto lens_at = [&](int64_t i, int& ql, int& tl) { pair_lens(first + (amap.empty() ? i : amap[(size_t)i]), ql, tl); };
-      int64_t n_huge = 0;
-      for (int64_t i = 0; i < n; ++i) {
-        int ql, tl;
-        lens_at(i, ql, tl);
-        n_huge += std::abs(ql - tl) >= 16384;
-      }
-      const bool use_sixteen = !never_wide && !(e->cfg.flags & AWV_F_FOUR_WAVES) && n_huge > 0 && n_huge <= (int64_t)e->num_cus;
-      const bool force32 = (e->cfg.flags & AWV_F_FORCE_INT32) != 0;
-      const bool no_wide16 = (e->cfg.flags & AWV_F_NO_WIDE16) != 0;
-      std::vector<uint8_t> fl((size_t)n);
-      int64_t n_one = 0, n_four = 0;
-      for (int64_t i = 0; i < n; ++i) {
-        int ql, tl;
-        lens_at(i, ql, tl);
-        const int dl = std::abs(ql - tl);
-        int f = (all_wide || (!never_wide && (dl >= 4096 || std::max(ql, tl) >= 32760))) ? 1 : 0;
-        if (use_sixteen && dl >= 16384) f = 2;  // a forced gap that long: rows hundreds of windows wide
-#ifdef AWV_DEBUG_KNOBS
-        if (getenv("AWV_FORCE_SIXTEEN") && std::max(ql, tl) >= atoi(getenv("AWV_FORCE_SIXTEEN"))) f = 2;  // experiment: sixteen waves per pair for sequences at least that long
-#endif
-        fl[(size_t)i] = (uint8_t)f;
-        n_one += f == 0;
-        n_four += f == 1;
-      }
-      // One-wave pairs that cannot fill the machine even once, next to pairs that go four waves anyway, are bound by their
-      // most expensive pair on a single wave while most of the machine idles: when their costs are uneven they go four
-      // waves too (config 5: 3,315 such pairs, 2.9 s at 61 % of the CUs busy).  (Pairs come in descending cost order.)
-      if (!never_wide && n_one > 0 && n_four > 0 && n_one <= (int64_t)(WAVES_PER_SIMD * 256 / 64) * e->num_cus) {
-        auto cost_of = [&](int64_t i) {
-          int ql, tl;
-          lens_at(i, ql, tl);
-          return (uint64_t)((int64_t)ql + tl + 4 * std::llabs((int64_t)ql - tl));
-        };
-        int64_t first_one = -1, seen = 0, median_one = -1;
-        for (int64_t i = 0; i < n && median_one < 0; ++i) {
-          if (fl[(size_t)i] != 0) continue;
-          if (first_one < 0) first_one = i;
-          if (seen++ == n_one / 2) median_one = i;
-        }
-        if (2 * cost_of(first_one) >= 3 * cost_of(median_one))  // (work grows with the square of this length measure: 1.5 x = more than twice the work)
-          for (int64_t i = 0; i < n; ++i)
-            if (fl[(size_t)i] == 0) fl[(size_t)i] = 1;
-      }
-      for (int64_t i = 0; i < n; ++i) {
-        int ql, tl;
-        lens_at(i, ql, tl);
-        const int f = fl[(size_t)i];
-        // row width: every stored value must fit 16 bits -- text offsets (both lengths short), or min(h, v) when only
-        // the shorter sequence is (the kernels for that exist in the four- and sixteen-wave flavours)
-        int w = force32 || std::max(ql, tl) >= 32760 ? 1 : 0;
-        if (w == 1 && !force32 && !no_wide16 && f >= 1 && std::min(ql, tl) < 32760) w = 2;
-        const int g = f * 3 + w;
-        q[g].push_back(hq[(size_t)i]); t[g].push_back(ht[(size_t)i]); rc[g].push_back(hrc[(size_t)i]); off[g].push_back(hoff[(size_t)i]);
-        map[g].push_back(amap.empty() ? i : amap[(size_t)i]);
-        gsum[g] = std::max(gsum[g], ql + tl);
-        glen[g] = std::max(glen[g], std::max(ql, tl));
-      }
-      static const int waves_of[3] = {1, 4, 16};
-      // the arenas are sized for the most demanding group first: growing them between two groups would
-      // mean a free followed by a large allocation, which the driver can take seconds over
-      {  // (reserve in descending order of estimated ring demand; DevBuf::reserve only ever grows)
-        std::pair<size_t, int> demand[NG];
-        for (int g = 0; g < NG; ++g) {
-          demand[g] = {0, g};
-          if (q[g].empty()) continue;
-          const int wv = waves_of[g / 3];
-          const int wgx = 64 * wv;
-          const int64_t slots = std::min<int64_t>((WAVES_PER_SIMD * 256 / wgx) * e->num_cus, (int64_t)q[g].size());
-          demand[g].first = (size_t)slots * (size_t)gsum[g] * ((g % 3) == 1 ? 4 : 2);
-        }
-        std::sort(demand, demand + NG, [](const std::pair<size_t, int>& a, const std::pair<size_t, int>& b) { return a.first > b.first; });
-        for (int k = 0; k < NG; ++k) {
-          const int g = demand[k].second;
-          if (q[g].empty()) continue;
-          if (int rcg = run_group(q[g], t[g], rc[g], off[g], map[g], waves_of[g / 3], g % 3, gsum[g], glen[g], true)) return rcg;
-        }
-      }
-      for (int g = NG - 1; g >= 0; --g)
-        if (int rcg = run_group(std::move(q[g]), std::move(t[g]), std::move(rc[g]), std::move(off[g]), std::move(map[g]), waves_of[g / 3], g % 3, gsum[g], glen[g], false)) return rcg;
-    }
-    const bool want_cigar = sink && !score_only && !(e->cfg.flags & AWV_F_KEEP_ON_DEVICE);
-    lap("results on host");
-    if (norm != AWV_NORM_OFF) {  // first of the record steps: the check, the clip and the split see the normalized bytes
-      const awvn::SeqView sv{s.n, s.d_seq[0].p, s.d_seq[2].p, s.d_off.p, s.d_len.p};
-      if (int rc = awvn::normalize_batch(e, sv, norm, pairs + first, n, hres.data(), e->d_cigar.p, arena, spans ? spans + first : nullptr)) return rc;
-      lap("batch normalized");
-    }
-    if (vout) {  // the groups of a batch overwrite d_results: the batch's records, as gathered in hres, go up once for the check
-      if (int rc = awvf::verify_batch(e, pen, pairs + first, n, hres.data(), e->d_cigar.p, arena, vout + first, spans ? spans + first : nullptr)) return rc;
-      lap("batch verified");
-    }
-    if (cout) {
-      if (int rc = awvc::clip_batch(e, pen, match_bonus, n, hres.data(), e->d_cigar.p, arena, cout + first)) return rc;
-      lap("batch clipped");
-    }
-    if (split) {
-      if (int rc = awvs::split_batch(e, pen, match_bonus, split->min_score, n, hres.data(), e->d_cigar.p, arena, split->seg_first + first,
-                                     split->iout + first, split->sout)) return rc;
-      lap("batch split");
-    }
-    if (want_cigar) {
-      e->h_cigar.resize((size_t)arena + 64);
-      lap("host cigar buffer");
-      AWV_TRY(hipEventRecord(e->ev0, e->stream));
-      AWV_TRY(hipMemcpyAsync(e->h_cigar.data(), e->d_cigar.p, (size_t)arena, hipMemcpyDeviceToHost, e->stream));
-      AWV_TRY(hipEventRecord(e->ev1, e->stream));
-      AWV_TRY(hipEventSynchronize(e->ev1));
-      float ms_c = 0;
-      AWV_TRY(hipEventElapsedTime(&ms_c, e->ev0, e->ev1));
-      d2h_ms += ms_c;
-    }
-    lap("cigars on host");
-    if (out) std::memcpy(out + first, hres.data(), (size_t)n * sizeof(awv_result));
-    if (sink) {
-      if (const int prc = runner.wait()) return fail(AWV_ERR_SINK, "sink callback returned " + std::to_string(prc));
-      if (first + n >= npairs || inline_sink) {  // the last (or only) batch: on the calling thread
-        const int rc = sink(user, first, n, hres.data(), want_cigar ? e->h_cigar.data() : nullptr);
-        if (rc != 0) return fail(AWV_ERR_SINK, "sink callback returned " + std::to_string(rc));
-        lap("sink returned");
-      } else {  // hand the batch's buffers to the helper thread and go on with the next batch
-        runner.res.swap(hres);
-        runner.cig.swap(e->h_cigar);
-        const awv_result* rp = runner.res.data();
-        const uint8_t* cp = want_cigar ? runner.cig.data() : nullptr;
-        const int64_t f0 = first, n0 = n;
-        SinkRunner* rn = &runner;
-        try {
-          runner.th = std::thread([rn, sink, user, f0, n0, rp, cp]() { rn->rc = sink(user, f0, n0, rp, cp); });
-          lap("sink handed off");
-        } catch (const std::exception&) {  // no thread to be had: this sink runs here, nothing may cross the C boundary
-          const int rc = sink(user, f0, n0, rp, cp);
-          if (rc != 0) return fail(AWV_ERR_SINK, "sink callback returned " + std::to_string(rc));
-        }
-      }
-    }
-    first += n;
+// With several batches in a call, the sink of batch i (the caller's formatting and output) runs on a
+// helper thread while batch i+1 is carved, launched and copied back.  It is joined before the next
+// sink starts: sinks never overlap, come in batch order, and a batch's result / CIGAR buffers stay
+// untouched until its sink has returned.  The last batch's sink runs on the calling thread.
+struct SinkRunner {
+  std::thread th;
+  int rc = 0;
+  std::vector<awv_result> res;
+  std::vector<uint8_t> cig;
+  int wait() {
+    if (th.joinable()) th.join();
+    const int r = rc;
+    rc = 0;
+    return r;
   }
-  e->stats.kernel_ms = kernel_ms;
-  e->stats.h2d_ms = h2d_ms;
-  e->stats.d2h_ms = d2h_ms;
-  e->stats.launches = launches;
+  ~SinkRunner() { if (th.joinable()) th.join(); }
+};
+
+// Everything one call carries from stage to stage.
+struct AlignCall {
+  awv_engine* e;
+  SeqSet& s;
+  const awv_penalties* pen;
+  const AlignRequest& rq;
+  awvb::PenaltyPlan pp;
+  awvb::Config cfg;
+  int32_t norm = AWV_NORM_OFF;
+  bool twin_ok = false;
+  int64_t max_batch = 0;
+  uint64_t max_arena = 0;
+  // experiment knobs (read_knobs)
+  bool inline_sink = false, timing = false;
+  int force_sixteen_len = INT_MAX;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  // the batch in hand: pairs [first, first + n) of the call, `arena` bytes of CIGARs, results in caller order
+  int64_t first = 0, n = 0;
+  uint64_t arena = 0;
+  std::vector<awvb::Entry> entries;
+  std::vector<awv_result> hres;
+  double kernel_ms = 0, h2d_ms = 0, d2h_ms = 0;
+  unsigned long long stat_tot[awv::STAT_N_DEV] = {0};
+  uint64_t launches = 0;
+  SinkRunner runner;
+  bool want_cigar() const { return rq.sink && !rq.score_only && !(e->cfg.flags & AWV_F_KEEP_ON_DEVICE); }
+  void lap(const char* what) const {  // diagnostic: host-side stage times on stderr
+    if (timing) fprintf(stderr, "[awv] %-22s %.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  }
+};
+
+// Experiment knobs read from the environment exist only in a -DAWV_DEBUG_KNOBS build; the product library's
+// behaviour depends on its arguments alone.
+void read_knobs(AlignCall& c) {
+#ifdef AWV_DEBUG_KNOBS
+  if (const char* env = getenv("AWV_MAX_ARENA_MB")) c.max_arena = std::max<uint64_t>(1, (uint64_t)atoll(env)) << 20;
+  c.inline_sink = getenv("AWV_INLINE_SINK") != nullptr;  // every sink on the calling thread
+  c.timing = getenv("AWV_TIMING") != nullptr;
+  if (const char* env = getenv("AWV_FORCE_SIXTEEN")) c.force_sixteen_len = atoi(env);  // experiment: sixteen waves per pair for sequences at least that long
+#else
+  (void)c;
+#endif
+}
+
+// the two events around a stretch of stream work: its milliseconds are added to `acc`
+int timer_wait(AlignCall& c, double& acc) {
+  float ms = 0;
+  AWV_TRY(hipEventSynchronize(c.e->ev1));
+  AWV_TRY(hipEventElapsedTime(&ms, c.e->ev0, c.e->ev1));
+  acc += ms;
+  return AWV_OK;
+}
+int timer_stop(AlignCall& c, double& acc) {
+  AWV_TRY(hipEventRecord(c.e->ev1, c.e->stream));
+  return timer_wait(c, acc);
+}
+
+// ---- per batch: carve, order, buffers ----
+// (the (pattern, text) lengths a pair is aligned over decide cost order, kernel flavour, row width, row capacity and the CIGAR arena)
+bool carve_and_order(AlignCall& c) {
+  const AlignRequest& rq = c.rq;
+  const awvb::Carve cv = awvb::carve_batch(
+      [&](int64_t gi, int32_t& ql, int32_t& tl) {
+        if (rq.spans) {
+          ql = rq.spans[gi].pe - rq.spans[gi].pb;
+          tl = rq.spans[gi].te - rq.spans[gi].tb;
+        } else {
+          ql = c.s.len[rq.pairs[gi].q_idx];
+          tl = c.s.len[rq.pairs[gi].t_idx];
+        }
+      },
+      c.first, rq.npairs, c.max_batch, c.max_arena, rq.score_only, c.entries);
+  c.n = cv.n;
+  c.arena = cv.arena;
+  for (awvb::Entry& en : c.entries) {
+    const awv_pair& p = rq.pairs[c.first + en.batch_index];
+    en.q = p.q_idx;
+    en.t = p.t_idx;
+    en.rc = p.q_revcomp ? 1 : 0;
+  }
+  return awvb::order_by_cost(c.entries);  // results and CIGARs keep their caller-order slots through Entry::batch_index
+}
+
+int reserve_batch_buffers(AlignCall& c) {
+  awv_engine* e = c.e;
+  const size_t n = (size_t)c.n;
+  if (int rc = e->d_pair_q.reserve(n)) return rc;
+  if (int rc = e->d_pair_t.reserve(n)) return rc;
+  if (int rc = e->d_pair_rc.reserve(n)) return rc;
+  if (int rc = e->d_cigar_off.reserve(n)) return rc;
+  if (int rc = e->d_results.reserve(n)) return rc;
+  if (int rc = e->d_cigar.reserve((size_t)c.arena + 64)) return rc;
+  if (int rc = e->d_counters.reserve(1 + awv::STAT_N_DEV)) return rc;
+  static_assert(sizeof(awv_result) == sizeof(awv::DevResult), "result layout");
+  c.hres.assign(n, awv_result{});
+  return AWV_OK;
+}
+
+// the pairs of a group whose length difference alone rules out rows within the 2 GiB limit end CAPACITY before any launch
+void drop_beyond_span(AlignCall& c, std::vector<awvb::Entry>& ge, int width) {
+  const long long span = awvb::capacity_span(LIMITS, awvb::wc_2g(LIMITS, c.pp.ring, width));
+  size_t k = 0;
+  for (size_t i = 0; i < ge.size(); ++i) {
+    const awvb::Entry en = ge[i];
+    if (awvb::beyond_span(en.ql, en.tl, span)) {
+      awv_result r{};
+      r.status = AWV_ST_CAPACITY;
+      r.cigar_off = en.off;
+      c.hres[(size_t)en.batch_index] = r;
+      continue;
+    }
+    ge[k++] = en;
+  }
+  ge.resize(k);
+}
+
+// ---- arenas ----
+// The ring arena grows: choose where it lies (see arena_probe_kernel).
+int choose_ring_arena(AlignCall& c, const awvb::RowPlan& rp, int wc, int nslots) {
+  awv_engine* e = c.e;
+  const size_t ring_stride = rp.ring_stride(wc);
+  const size_t want = ring_stride * (size_t)nslots + ((size_t)64 << 20);
+  size_t free_b = 0, total_b = 0;
+  e->ring_mem.release();
+  (void)hipMemGetInfo(&free_b, &total_b);
+  int ncand = (e->cfg.flags & AWV_F_NO_ARENA_PROBE) ? 1 : 4;
+  while (ncand > 1 && (size_t)ncand * want > free_b / 10 * 8) --ncand;  // all candidates are alive at once
+  const bool probe_ok = ncand > 1 && want >= ((size_t)1 << 30) && rp.esz == 2 && ring_stride >= (size_t)2 * 5 * 32 * 4096 &&
+                        (size_t)wc * rp.esz >= 4096;
+  if (!probe_ok) ncand = 1;
+  uint8_t* cand[4] = {nullptr, nullptr, nullptr, nullptr};
+  float cms[4] = {0, 0, 0, 0};
+  int best = -1;
+  for (int k = 0; k < ncand; ++k) {
+    if (hipMalloc((void**)&cand[k], want) != hipSuccess) { cand[k] = nullptr; (void)hipGetLastError(); break; }
+    if (ncand == 1) { best = 0; break; }
+    float tbest = 1e30f;
+    hipError_t perr = hipSuccess;
+    for (int rep = 0; rep < 2 && perr == hipSuccess; ++rep) {
+      float pms = 0;
+      if ((perr = hipEventRecord(e->ev0, e->stream)) != hipSuccess) break;
+      hipLaunchKernelGGL(arena_probe_kernel, dim3(nslots), dim3(64), 0, e->stream, cand[k], ring_stride, (int)((size_t)wc * rp.esz), 24,
+                         std::min(1400, wc - 2048), e->d_counters.p);
+      if ((perr = hipEventRecord(e->ev1, e->stream)) != hipSuccess) break;
+      if ((perr = hipEventSynchronize(e->ev1)) != hipSuccess) break;
+      if ((perr = hipEventElapsedTime(&pms, e->ev0, e->ev1)) != hipSuccess) break;
+      tbest = std::min(tbest, pms);
+    }
+    if (perr != hipSuccess) {  // nothing may stay allocated behind an error return
+      for (int j = 0; j < 4; ++j)
+        if (cand[j]) (void)hipFree(cand[j]);
+      return fail(AWV_ERR_HIP, std::string("ring arena probe: ") + hipGetErrorString(perr));
+    }
+    cms[k] = tbest;
+    if (best < 0 || tbest < cms[best]) best = k;
+    if (c.timing) fprintf(stderr, "[awv] ring arena candidate %d at %p: %.2f ms\n", k, (void*)cand[k], tbest);
+  }
+  if (best < 0) return fail(AWV_ERR_OOM, "hipMalloc " + std::to_string(want) + " bytes for the ring arena failed");
+  for (int k = 0; k < 4; ++k)
+    if (k != best && cand[k]) (void)hipFree(cand[k]);
+  e->ring_mem.adopt(cand[best], want);
+  return AWV_OK;
+}
+
+// the per-workgroup arenas of an attempt of `nslots` workgroups at row capacity wc (DevBuf::reserve only ever grows)
+int ensure_arenas(AlignCall& c, const awvb::RowPlan& rp, int wc, int nslots) {
+  awv_engine* e = c.e;
+  if (rp.ring_stride(wc) * nslots > e->ring_mem.cap)
+    if (int rc = choose_ring_arena(c, rp, wc, nslots)) return rc;
+  if (int rc = e->hist_mem.reserve(rp.hist_stride * nslots)) return rc;
+  if (int rc = e->ev_mem.reserve(rp.ev_stride(wc) * nslots)) return rc;
+  return AWV_OK;
+}
+
+// ---- one attempt of a group: upload, launch, read back ----
+// Twin units: an entry (q, t) and its swapped entry (t, q) of this launch share their breakpoint searches.
+// Entries are in descending cost order and a twin costs what its partner costs, so units ordered by their summed cost are the
+// twin units in entry order, then the single ones.
+int upload_twin_units(AlignCall& c, const std::vector<awvb::Entry>& ge, int64_t& nunits) {
+  awv_engine* e = c.e;
+  awv_engine::HostStage& st = e->stage;
+  const awvt::TwinPlan tp = awvt::plan_twins(st.hq.data(), st.ht.data(), st.hrc.data(), ge.size());
+  std::vector<size_t> uo(tp.first.size());
+  for (size_t u = 0; u < uo.size(); ++u) uo[u] = u;
+  auto ucost = [&](size_t u) {
+    const awvb::Entry& en = ge[(size_t)tp.first[u]];
+    const uint64_t cost = awvb::pair_cost(en.ql, en.tl);
+    return tp.twin[u] >= 0 ? 2 * cost : cost;
+  };
+  std::stable_sort(uo.begin(), uo.end(), [&](size_t a, size_t b) { return ucost(a) > ucost(b); });
+  st.hufirst.resize(uo.size());
+  st.hutwin.resize(uo.size());
+  for (size_t u = 0; u < uo.size(); ++u) {
+    st.hufirst[u] = tp.first[uo[u]];
+    st.hutwin[u] = tp.twin[uo[u]];
+  }
+  nunits = (int64_t)uo.size();
+  if (int rc = e->d_unit_first.reserve((size_t)nunits)) return rc;
+  if (int rc = e->d_unit_twin.reserve((size_t)nunits)) return rc;
+  AWV_TRY(hipMemcpyAsync(e->d_unit_first.p, st.hufirst.data(), (size_t)nunits * 4, hipMemcpyHostToDevice, e->stream));
+  AWV_TRY(hipMemcpyAsync(e->d_unit_twin.p, st.hutwin.data(), (size_t)nunits * 4, hipMemcpyHostToDevice, e->stream));
+  return AWV_OK;
+}
+
+// the group's entries, split into the device's arrays; nunits: the launch's dispatch units (entries, or entries with their twins)
+int upload_group(AlignCall& c, const std::vector<awvb::Entry>& ge, const awvb::RowPlan& rp, int64_t& nunits) {
+  awv_engine* e = c.e;
+  awv_engine::HostStage& st = e->stage;
+  const AlignRequest& rq = c.rq;
+  const size_t m = ge.size();
+  st.hq.resize(m); st.ht.resize(m); st.hrc.resize(m); st.hoff.resize(m);
+  for (size_t i = 0; i < m; ++i) {
+    st.hq[i] = ge[i].q; st.ht[i] = ge[i].t; st.hrc[i] = ge[i].rc; st.hoff[i] = ge[i].off;
+  }
+  AWV_TRY(hipEventRecord(e->ev0, e->stream));
+  AWV_TRY(hipMemcpyAsync(e->d_pair_q.p, st.hq.data(), m * 4, hipMemcpyHostToDevice, e->stream));
+  AWV_TRY(hipMemcpyAsync(e->d_pair_t.p, st.ht.data(), m * 4, hipMemcpyHostToDevice, e->stream));
+  AWV_TRY(hipMemcpyAsync(e->d_pair_rc.p, st.hrc.data(), m * 4, hipMemcpyHostToDevice, e->stream));
+  AWV_TRY(hipMemcpyAsync(e->d_cigar_off.p, st.hoff.data(), m * 8, hipMemcpyHostToDevice, e->stream));
+  if (rq.pair_bound) {
+    st.hbound.resize(m);
+    for (size_t i = 0; i < m; ++i) st.hbound[i] = rq.pair_bound[c.first + ge[i].batch_index];
+    if (int rc = e->d_pair_bound.reserve(m)) return rc;
+    AWV_TRY(hipMemcpyAsync(e->d_pair_bound.p, st.hbound.data(), m * 4, hipMemcpyHostToDevice, e->stream));
+  }
+  if (rq.spans) {
+    st.hspan.resize(m);
+    for (size_t i = 0; i < m; ++i) st.hspan[i] = rq.spans[c.first + ge[i].batch_index];
+    if (int rc = e->d_pair_span.reserve(m)) return rc;
+    AWV_TRY(hipMemcpyAsync(e->d_pair_span.p, st.hspan.data(), m * sizeof(awvr::Span), hipMemcpyHostToDevice, e->stream));
+  }
+  nunits = (int64_t)m;
+  if (rp.twin_here)
+    if (int rc = upload_twin_units(c, ge, nunits)) return rc;
+  AWV_TRY(hipMemsetAsync(e->d_counters.p, 0, (1 + awv::STAT_N_DEV) * sizeof(unsigned long long), e->stream));
+  return timer_stop(c, c.h2d_ms);
+}
+
+awv::KParams fill_kparams(const AlignCall& c, const awvb::RowPlan& rp, int wc, int64_t nunits) {
+  const awv_engine* e = c.e;
+  const SeqSet& s = c.s;
+  const bool narrow = rp.width != 1;
+  awv::KParams kp{};
+  for (int v = 0; v < 4; ++v) kp.seq[v] = s.d_seq[v].p;
+  kp.seq_off = s.d_off.p;
+  kp.seq_len = s.d_len.p;
+  kp.seq2[0] = s.d_seq2[0].p;
+  kp.seq2[1] = s.d_seq2[1].p;
+  kp.seq2_off = s.d_off2.p;
+  kp.seq2_ok = s.d_ok2.p;
+  kp.pair_q = e->d_pair_q.p;
+  kp.pair_t = e->d_pair_t.p;
+  kp.pair_rc = e->d_pair_rc.p;
+  kp.npairs = nunits;
+  kp.unit_first = rp.twin_here ? e->d_unit_first.p : nullptr;
+  kp.unit_twin = rp.twin_here ? e->d_unit_twin.p : nullptr;
+  kp.twin_levels = (e->cfg.flags & AWV_F_TWIN_TOP_ONLY) ? 1 : INT_MAX;
+  kp.twin_base = (e->cfg.flags & AWV_F_NO_TWIN_BASE) ? 0 : 1;
+  kp.pen = awv::DevPenalties{c.pp.x, c.pp.o1, c.pp.e1, c.pp.o2, c.pp.e2, c.pp.two_piece, c.pp.scope};
+  kp.ring = c.pp.ring;
+  // 32-bit rows: sweeps of at most TMAX32 scores, at most CHAIN_MAX32 of them chained (a lane vector is four registers)
+  kp.multi_T = narrow ? c.pp.multi_T : (std::min(c.pp.multi_T, awv::TMAX32) >= 2 ? std::min(c.pp.multi_T, awv::TMAX32) : 0);
+  kp.deep_passes = (kp.multi_T > 0 && !(e->cfg.flags & AWV_F_NO_DEEP)) ? 1 : 0;
+  kp.sub16 = (e->cfg.flags & AWV_F_FORCE_INT32) ? 0 : 1;  // (the pin means 32-bit rows throughout)
+  // (32-bit rows: two sweeps chained through registers, a third when the kernel finds room for its chain rows in LDS -- the
+  // kernel caps what it is offered: biwfa_device.hpp, multi_phase's lds_chain)
+  kp.chain_max = narrow ? c.pp.chain_max : (awv::TMAX32 == awv::TMAX ? std::min(c.pp.chain_max, 3) : 1);
+  kp.wcap = wc;
+  kp.ring_mem = e->ring_mem.p;
+  kp.ring_slot_stride = rp.ring_stride(wc);
+  kp.lds_meta_bytes = (int)rp.lds_meta;
+  kp.lds_seq_bytes = (int)rp.lds_seq;
+  kp.sb_cap = c.pp.sb_cap;
+  kp.wb_cap = c.pp.wb_cap;
+  kp.hist_mem = e->hist_mem.p;
+  kp.hist_slot_stride = rp.hist_stride;
+  kp.hist_meta_offset = rp.hist_rows;
+  kp.ev_mem = e->ev_mem.p;
+  kp.ev_slot_stride = rp.ev_stride(wc);
+  kp.cigar = e->d_cigar.p;
+  kp.cigar_off = e->d_cigar_off.p;
+  kp.results = e->d_results.p;
+  kp.work_counter = e->d_counters.p;
+  kp.stats = e->d_counters.p + 1;
+  kp.score_only = c.rq.score_only ? 1 : 0;
+  kp.max_penalty = c.rq.max_penalty;
+  kp.pair_max_penalty = c.rq.pair_bound ? e->d_pair_bound.p : nullptr;
+  return kp;
+}
+
+// The kernel of a multi-wave flavour: NS names one inclusion of biwfa_device.hpp; the choice runs over 2-piece x row type x
+// ranged (range launches: the kernels' two-argument instantiations).  The AWV_WIDE16 inclusions hold only their 16-bit kernels.
+// (kernels_awv.hip has the same choice for the one-wave flavour.)
+struct LaunchShape {
+  unsigned grid;
+  int wg;
+  size_t dyn_lds;
+  hipStream_t stream;
+  bool two_piece, narrow;
+  const awvr::Span* d_span;
+};
+#define AWV_KERNELS_OF(NS)                                                                   \
+  struct NS##_kernels {                                                                      \
+    typedef NS::KParams KParams;                                                             \
+    static constexpr bool only16 = NS::WENC;                                                 \
+    template <bool P2, typename OffT, typename... S>                                         \
+    static auto kernel() { return &NS::biwfa_align_kernel<P2, OffT, S...>; }                \
+  }
+AWV_KERNELS_OF(awvw);
+AWV_KERNELS_OF(awvx);
+AWV_KERNELS_OF(awvw_m);
+AWV_KERNELS_OF(awvx_m);
+#undef AWV_KERNELS_OF
+template <typename K, typename KP, typename... PairSpan>
+int launch_kernel(K kern, const LaunchShape& l, const KP& kparams, PairSpan... pair_span) {
+  AWV_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.dyn_lds));
+  hipLaunchKernelGGL(kern, dim3(l.grid), dim3(l.wg), l.dyn_lds, l.stream, kparams, pair_span...);
+  return AWV_OK;
+}
+template <typename NS, bool P2, typename OffT>
+int launch_ranged(const LaunchShape& l, const typename NS::KParams& k) {
+  if (l.d_span) return launch_kernel(NS::template kernel<P2, OffT, const awvr::Span*>(), l, k, l.d_span);
+  return launch_kernel(NS::template kernel<P2, OffT>(), l, k);
+}
+template <typename NS, bool P2>
+int launch_rows(const LaunchShape& l, const typename NS::KParams& k) {
+  if constexpr (NS::only16) return launch_ranged<NS, P2, int16_t>(l, k);
+  else return l.narrow ? launch_ranged<NS, P2, int16_t>(l, k) : launch_ranged<NS, P2, int32_t>(l, k);
+}
+template <typename NS>
+int launch_flavour(const LaunchShape& l, const awv::KParams& kp) {
+  static_assert(sizeof(typename NS::KParams) == sizeof(awv::KParams), "same parameter block for every workgroup size");
+  typename NS::KParams k;
+  std::memcpy(&k, &kp, sizeof(k));
+  return l.two_piece ? launch_rows<NS, true>(l, k) : launch_rows<NS, false>(l, k);
+}
+
+int launch_group(AlignCall& c, const awvb::RowPlan& rp, const awv::KParams& kp, int nslots) {
+  awv_engine* e = c.e;
+  const LaunchShape l{(unsigned)nslots, rp.wg, rp.dyn_lds, e->stream, kp.pen.two_piece != 0, rp.width != 1, c.rq.spans ? e->d_pair_span.p : nullptr};
+  AWV_TRY(hipEventRecord(e->ev0, e->stream));
+  if (rp.waves == 1) AWV_TRY((hipError_t)awv_launch_one_wave(l.two_piece, l.narrow ? 1 : 0, l.d_span, l.grid, l.dyn_lds, l.stream, &kp));
+  else if (int rc = rp.width == 2 ? (rp.waves == 4 ? launch_flavour<awvw_m_kernels>(l, kp) : launch_flavour<awvx_m_kernels>(l, kp))
+                                  : (rp.waves == 4 ? launch_flavour<awvw_kernels>(l, kp) : launch_flavour<awvx_kernels>(l, kp)))
+    return rc;
+  AWV_TRY(hipGetLastError());
+  AWV_TRY(hipEventRecord(e->ev1, e->stream));
+  // while the kernel runs: get the host CIGAR buffer's pages in place (0.2 s for config 2's 670 MB)
+  if (c.want_cigar() && e->h_cigar.size() < (size_t)c.arena + 64) e->h_cigar.resize((size_t)c.arena + 64);
+  if (int rc = timer_wait(c, c.kernel_ms)) return rc;
+  ++c.launches;
+  c.lap("kernel done");
+  return AWV_OK;
+}
+
+// D2H of the attempt's results and counters; every result goes to its caller-order slot
+int read_back(AlignCall& c, const std::vector<awvb::Entry>& ge) {
+  awv_engine* e = c.e;
+  awv_engine::HostStage& st = e->stage;
+  const size_t m = ge.size();
+  st.tres.resize(m);
+  AWV_TRY(hipEventRecord(e->ev0, e->stream));
+  AWV_TRY(hipMemcpyAsync(st.tres.data(), e->d_results.p, m * sizeof(awv_result), hipMemcpyDeviceToHost, e->stream));
+  unsigned long long hstat[1 + awv::STAT_N_DEV];
+  AWV_TRY(hipMemcpyAsync(hstat, e->d_counters.p, sizeof(hstat), hipMemcpyDeviceToHost, e->stream));
+  if (int rc = timer_stop(c, c.d2h_ms)) return rc;
+  for (int i = 0; i < awv::STAT_N_DEV; ++i) c.stat_tot[i] += hstat[1 + i];
+  for (size_t i = 0; i < m; ++i) c.hres[(size_t)ge[i].batch_index] = st.tres[i];
+  return AWV_OK;
+}
+
+// keeps the pairs to re-run with wider rows: those that outgrew rows narrower than the widest a re-run may use
+void select_reruns(const AlignCall& c, std::vector<awvb::Entry>& ge, bool wider_rows_left) {
+  const awv_engine::HostStage& st = c.e->stage;
+  size_t k = 0;
+  if (wider_rows_left && !(c.e->cfg.flags & AWV_F_NO_RERUN))
+    for (size_t i = 0; i < ge.size(); ++i)
+      if (st.tres[i].status == AWV_ST_CAPACITY) ge[k++] = ge[i];
+  ge.resize(k);
+}
+
+// One group of the batch = one kernel flavour x one row width.  Attempts: the whole group at row capacity rp.wcap, then only
+// the pairs that outgrew it.
+int run_group(AlignCall& c, std::vector<awvb::Entry>& ge, const awvb::RowPlan& rp) {
+  for (int wc = rp.wcap; !ge.empty(); wc = rp.next_wc(wc)) {
+    const int nslots = rp.slots(wc, (int64_t)ge.size());
+    if (int rc = ensure_arenas(c, rp, wc, nslots)) return rc;
+    c.lap("arenas reserved");
+    if (c.timing) fprintf(stderr, "[awv] ring arena %p (%zu MiB), hist %p, cigar %p\n", (void*)c.e->ring_mem.p, c.e->ring_mem.bytes() >> 20, (void*)c.e->hist_mem.p, (void*)c.e->d_cigar.p);
+    int64_t nunits = 0;
+    if (int rc = upload_group(c, ge, rp, nunits)) return rc;
+    if (int rc = launch_group(c, rp, fill_kparams(c, rp, wc, nunits), nslots)) return rc;
+    if (int rc = read_back(c, ge)) return rc;
+    select_reruns(c, ge, wc < rp.wc_last);
+  }
+  return AWV_OK;
+}
+
+// The batch's pairs go to their groups; the arenas are reserved for the most demanding group first (one allocation covers
+// them all); the groups run from the sixteen-wave flavour down.
+int run_groups(AlignCall& c, bool skewed) {
+  const awvb::GroupPlan gp = awvb::assign_groups(LIMITS, c.cfg, c.entries, skewed, c.force_sixteen_len);
+  std::vector<awvb::Entry> ge[awvb::NG];
+  for (int g = 0; g < awvb::NG; ++g) ge[g].reserve(gp.count[g]);
+  for (size_t i = 0; i < c.entries.size(); ++i) ge[gp.group[i]].push_back(c.entries[i]);
+  awvb::RowPlan rp[awvb::NG];
+  for (int k = 0; k < awvb::NG; ++k) {
+    const int g = gp.demand_order[k];
+    drop_beyond_span(c, ge[g], awvb::width_of(g));
+    if (ge[g].empty()) continue;
+    rp[g] = awvb::plan_rows(LIMITS, c.cfg, c.pp, ge[g], awvb::waves_of(g), awvb::width_of(g), c.twin_ok);
+    if (int rc = ensure_arenas(c, rp[g], rp[g].wcap, rp[g].slots(rp[g].wcap, (int64_t)ge[g].size()))) return rc;
+  }
+  for (int g = awvb::NG - 1; g >= 0; --g)
+    if (int rc = run_group(c, ge[g], rp[g])) return rc;
+  return AWV_OK;
+}
+
+// ---- after the groups: record steps, copy-back, delivery ----
+// normalize first: the check, the clip and the split see the normalized bytes.  (The groups of a batch overwrite d_results: the
+// batch's records, as gathered in hres, go up once per step.)
+int run_record_steps(AlignCall& c) {
+  awv_engine* e = c.e;
+  const AlignRequest& rq = c.rq;
+  const SeqSet& s = c.s;
+  const int64_t first = c.first, n = c.n;
+  const uint64_t arena = c.arena;
+  std::vector<awv_result>& hres = c.hres;
+  if (c.norm != AWV_NORM_OFF) {
+    const awvn::SeqView sv{s.n, s.d_seq[0].p, s.d_seq[2].p, s.d_off.p, s.d_len.p};
+    if (int rc = awvn::normalize_batch(e, sv, c.norm, rq.pairs + first, n, hres.data(), e->d_cigar.p, arena, rq.spans ? rq.spans + first : nullptr)) return rc;
+    c.lap("batch normalized");
+  }
+  if (rq.vout) {
+    if (int rc = awvf::verify_batch(e, c.pen, rq.pairs + first, n, hres.data(), e->d_cigar.p, arena, rq.vout + first, rq.spans ? rq.spans + first : nullptr)) return rc;
+    c.lap("batch verified");
+  }
+  if (rq.cout) {
+    if (int rc = awvc::clip_batch(e, c.pen, rq.match_bonus, n, hres.data(), e->d_cigar.p, arena, rq.cout + first)) return rc;
+    c.lap("batch clipped");
+  }
+  if (rq.split) {
+    if (int rc = awvs::split_batch(e, c.pen, rq.match_bonus, rq.split->min_score, n, hres.data(), e->d_cigar.p, arena, rq.split->seg_first + first,
+                                   rq.split->iout + first, rq.split->sout)) return rc;
+    c.lap("batch split");
+  }
+  return AWV_OK;
+}
+
+int copy_cigars_back(AlignCall& c) {
+  awv_engine* e = c.e;
+  if (c.want_cigar()) {
+    e->h_cigar.resize((size_t)c.arena + 64);
+    c.lap("host cigar buffer");
+    AWV_TRY(hipEventRecord(e->ev0, e->stream));
+    AWV_TRY(hipMemcpyAsync(e->h_cigar.data(), e->d_cigar.p, (size_t)c.arena, hipMemcpyDeviceToHost, e->stream));
+    if (int rc = timer_stop(c, c.d2h_ms)) return rc;
+  }
+  c.lap("cigars on host");
+  return AWV_OK;
+}
+
+// the batch's results to the caller's array and to the sink (SinkRunner)
+int deliver(AlignCall& c) {
+  const AlignRequest& rq = c.rq;
+  if (rq.out) std::memcpy(rq.out + c.first, c.hres.data(), (size_t)c.n * sizeof(awv_result));
+  if (!rq.sink) return AWV_OK;
+  const bool want_cigar = c.want_cigar();
+  const awv_sink sink = rq.sink;
+  void* const user = rq.user;
+  if (const int prc = c.runner.wait()) return fail(AWV_ERR_SINK, "sink callback returned " + std::to_string(prc));
+  if (c.first + c.n >= rq.npairs || c.inline_sink) {  // the last (or only) batch: on the calling thread
+    const int rc = sink(user, c.first, c.n, c.hres.data(), want_cigar ? c.e->h_cigar.data() : nullptr);
+    if (rc != 0) return fail(AWV_ERR_SINK, "sink callback returned " + std::to_string(rc));
+    c.lap("sink returned");
+    return AWV_OK;
+  }
+  // hand the batch's buffers to the helper thread and go on with the next batch
+  c.runner.res.swap(c.hres);
+  c.runner.cig.swap(c.e->h_cigar);
+  const awv_result* rp = c.runner.res.data();
+  const uint8_t* cp = want_cigar ? c.runner.cig.data() : nullptr;
+  const int64_t f0 = c.first, n0 = c.n;
+  SinkRunner* rn = &c.runner;
+  try {
+    c.runner.th = std::thread([rn, sink, user, f0, n0, rp, cp]() { rn->rc = sink(user, f0, n0, rp, cp); });
+    c.lap("sink handed off");
+  } catch (const std::exception&) {  // no thread to be had: this sink runs here, nothing may cross the C boundary
+    const int rc = sink(user, f0, n0, rp, cp);
+    if (rc != 0) return fail(AWV_ERR_SINK, "sink callback returned " + std::to_string(rc));
+  }
+  return AWV_OK;
+}
+
+void publish_stats(AlignCall& c) {
+  using namespace awv;
+  awv_engine* e = c.e;
+  const unsigned long long* stat_tot = c.stat_tot;
+  e->stats.kernel_ms = c.kernel_ms;
+  e->stats.h2d_ms = c.h2d_ms;
+  e->stats.d2h_ms = c.d2h_ms;
+  e->stats.launches = c.launches;
   e->stats.cell_steps = stat_tot[STAT_CELLS];
   e->stats.extend_steps = stat_tot[STAT_EXTEND];
   e->stats.n_breakpoints = stat_tot[STAT_BREAKPOINTS];
@@ -1028,7 +887,68 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const awv_pai
   e->stats.clock_tick_khz = (uint64_t)e->wall_clock_khz;
   e->stats.deep_cell_steps = stat_tot[STAT_DEEP_CELLS];
   for (int i = 0; i < 4; ++i) e->twin_stats[i] = stat_tot[STAT_TWIN_UNITS + i];
+}
+
+int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const AlignRequest& rq) {
+  // ---- validate; the penalty plan
+  if (rq.npairs < 0 || (rq.npairs > 0 && !rq.pairs)) return fail(AWV_ERR_ARG, "align_pairs: null pairs");
+  AlignCall c{e, s, pen, rq};
+  c.pp = awvb::plan_penalties(LIMITS, pen, e->cfg.flags);
+  if (c.pp.code != AWV_OK && !c.pp.late) return fail(c.pp.code, c.pp.message);
+  AWV_TRY(hipSetDevice(e->device));
+  e->stats = awv_stats{};
+  for (uint64_t& v : e->twin_stats) v = 0;
+  c.norm = rq.score_only ? AWV_NORM_OFF : e->norm_mode;  // (off: no launch, no allocation, nothing below changes)
+  if (c.norm != AWV_NORM_OFF) awvn::stats_reset(e->normalize);
+  if (rq.npairs == 0) return AWV_OK;
+  for (int64_t i = 0; i < rq.npairs; ++i) {
+    if (rq.pairs[i].q_idx < 0 || rq.pairs[i].q_idx >= s.n || rq.pairs[i].t_idx < 0 || rq.pairs[i].t_idx >= s.n)
+      return fail(AWV_ERR_ARG, "align_pairs: sequence index out of range");
+  }
+  if (c.pp.code != AWV_OK) return fail(c.pp.code, c.pp.message);
+  c.cfg = awvb::Config{e->cfg.flags, e->num_cus, e->cfg.workgroups, (int64_t)e->cfg.max_scratch_bytes, e->cfg.first_row_cols};
+  c.max_batch = e->cfg.max_batch_pairs > 0 ? e->cfg.max_batch_pairs : (int64_t)1 << 20;
+  c.max_arena = e->cfg.max_arena_bytes > 0 ? (uint64_t)e->cfg.max_arena_bytes : (uint64_t)8 << 30;
+  // twin units only where the plain alignment or the plain score is asked for: whole pairs, no bound, re-runs allowed
+  c.twin_ok = rq.max_penalty == INT_MAX && !rq.pair_bound && !rq.spans && !rq.cout && !(e->cfg.flags & (AWV_F_NO_TWIN | AWV_F_NO_RERUN));
+  read_knobs(c);
+  // ---- batch by batch
+  for (; c.first < rq.npairs; c.first += c.n) {
+    const bool skewed = carve_and_order(c);
+    if (int rc = reserve_batch_buffers(c)) return rc;
+    if (int rc = run_groups(c, skewed)) return rc;
+    c.lap("results on host");
+    if (int rc = run_record_steps(c)) return rc;
+    if (int rc = copy_cigars_back(c)) return rc;
+    if (int rc = deliver(c)) return rc;
+  }
+  publish_stats(c);
   return AWV_OK;
+}
+
+// ---- what the entry points share ----
+int require_sequences(const awv_engine* e, int64_t n, const char* who) {
+  if (e->seqs.n == 0 && n > 0) return fail(AWV_ERR_STATE, std::string(who) + " before set_sequences");
+  return AWV_OK;
+}
+// (a bound of 2^30 or more cannot be met by any pair the engine accepts: it is no bound)
+int32_t norm_bound(int32_t b) { return b < 0 || b >= (1 << 30) ? INT_MAX : b; }
+// a caller's nullable array of n bounds as align_core takes them: normalized, in `store`; no array (or no pairs) stays null
+const int32_t* normalized_bounds(const int32_t* bounds, int64_t n, std::vector<int32_t>& store) {
+  if (!bounds || n <= 0) return nullptr;
+  store.resize((size_t)n);
+  for (int64_t i = 0; i < n; ++i) store[(size_t)i] = norm_bound(bounds[i]);
+  return store.data();
+}
+// the request of a plain full alignment; the other entry points set what they add
+AlignRequest full_request(const awv_pair* pairs, int64_t npairs, awv_result* out, awv_sink sink, void* user) {
+  AlignRequest rq;
+  rq.pairs = pairs;
+  rq.npairs = npairs;
+  rq.out = out;
+  rq.sink = sink;
+  rq.user = user;
+  return rq;
 }
 
 }  // namespace
@@ -1118,46 +1038,39 @@ int awv_engine_set_sequences(awv_engine* e, int32_t n, const uint8_t* concat_byt
 int awv_align_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, awv_result* out,
                     awv_sink sink, void* user) {
   if (!e) return fail(AWV_ERR_ARG, "null engine");
-  if (e->seqs.n == 0 && npairs > 0) return fail(AWV_ERR_STATE, "align_pairs before set_sequences");
-  AWV_GUARDED(return align_core(e, e->seqs, pen, pairs, npairs, out, sink, user);)
+  if (int rc = require_sequences(e, npairs, "align_pairs")) return rc;
+  AWV_GUARDED(return align_core(e, e->seqs, pen, full_request(pairs, npairs, out, sink, user));)
 }
 
 int awv_align_pairs_verified(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, awv_result* out,
                              awv_verify_result* vout, awv_sink sink, void* user) {
   if (!e) return fail(AWV_ERR_ARG, "null engine");
   if (!vout) return fail(AWV_ERR_ARG, "align_pairs_verified: null vout");
-  if (e->seqs.n == 0 && npairs > 0) return fail(AWV_ERR_STATE, "align_pairs before set_sequences");
+  if (int rc = require_sequences(e, npairs, "align_pairs")) return rc;
   awvf::stats_reset(e->verify);  // the call's batches add to them (a call without pairs launches nothing: its stats are empty)
-  AWV_GUARDED(return align_core(e, e->seqs, pen, pairs, npairs, out, sink, user, false, INT_MAX, nullptr, vout);)
+  AlignRequest rq = full_request(pairs, npairs, out, sink, user);
+  rq.vout = vout;
+  AWV_GUARDED(return align_core(e, e->seqs, pen, rq);)
 }
 
 namespace {
-// (a bound of 2^30 or more cannot be met by any pair the engine accepts: it is no bound)
-int32_t norm_bound(int32_t b) { return b < 0 || b >= (1 << 30) ? INT_MAX : b; }
-
-// awv_score_pairs / awv_score_pairs_bounded: one bound for the call (pair_bound == nullptr), or one per pair
-int score_core(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, int32_t max_penalty,
-               const int32_t* pair_bound, awv_score_result* out, const awvr::Span* spans = nullptr) {
-  if (!e) {  // (without a GPU there is no engine to pass: say so, as awv_engine_create does)
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(AWV_ERR_NO_DEVICE, "no HIP device available: liballwave_hip has no CPU fallback");
-    return fail(AWV_ERR_ARG, "null engine");
-  }
+// awv_score_pairs / awv_score_pairs_bounded / awv_score_ranges.  rq: the pairs (and rectangles) and the bounds as the caller
+// gave them -- one for the call (max_penalty), or one per pair (pair_bound).
+int score_core(awv_engine* e, const awv_penalties* pen, AlignRequest rq, awv_score_result* out) {
+  if (!e) return awv_internal_null_engine();  // (without a GPU there is no engine to pass: say so, as awv_engine_create does)
   if (!out) return fail(AWV_ERR_ARG, "score_pairs: null out");
-  if (npairs < 0) return fail(AWV_ERR_ARG, "score_pairs: npairs < 0");
-  if (e->seqs.n == 0 && npairs > 0) return fail(AWV_ERR_STATE, "score_pairs before set_sequences");
-  auto norm = norm_bound;
+  if (rq.npairs < 0) return fail(AWV_ERR_ARG, "score_pairs: npairs < 0");
+  if (int rc = require_sequences(e, rq.npairs, "score_pairs")) return rc;
   AWV_GUARDED(
-    std::vector<awv_result> res((size_t)npairs);
+    std::vector<awv_result> res((size_t)rq.npairs);
     std::vector<int32_t> pb;
-    if (pair_bound) {
-      pb.resize((size_t)npairs);
-      for (int64_t i = 0; i < npairs; ++i) pb[(size_t)i] = norm(pair_bound[i]);
-    }
-    const int rc = align_core(e, e->seqs, pen, pairs, npairs, res.data(), nullptr, nullptr, true, norm(max_penalty),
-                              pair_bound ? pb.data() : nullptr, nullptr, spans);
+    rq.out = res.data();
+    rq.score_only = true;
+    rq.max_penalty = norm_bound(rq.max_penalty);
+    rq.pair_bound = normalized_bounds(rq.pair_bound, rq.npairs, pb);
+    const int rc = align_core(e, e->seqs, pen, rq);
     if (rc != AWV_OK) return rc;
-    for (int64_t i = 0; i < npairs; ++i) {
+    for (int64_t i = 0; i < rq.npairs; ++i) {
       out[i].status = res[(size_t)i].status;
       out[i].penalty = res[(size_t)i].penalty;
     }
@@ -1168,13 +1081,18 @@ int score_core(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, i
 
 int awv_score_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, int32_t max_penalty,
                     awv_score_result* out) {
-  return score_core(e, pen, pairs, npairs, max_penalty, nullptr, out);
+  AlignRequest rq = full_request(pairs, npairs, nullptr, nullptr, nullptr);
+  rq.max_penalty = max_penalty;
+  return score_core(e, pen, rq, out);
 }
 
 int awv_score_pairs_bounded(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
                             const int32_t* max_penalty, awv_score_result* out) {
   if (e && npairs > 0 && !max_penalty) return fail(AWV_ERR_ARG, "score_pairs_bounded: null max_penalty");
-  return score_core(e, pen, pairs, npairs, -1, max_penalty, out);
+  AlignRequest rq = full_request(pairs, npairs, nullptr, nullptr, nullptr);
+  rq.max_penalty = -1;
+  rq.pair_bound = max_penalty;
+  return score_core(e, pen, rq, out);
 }
 
 // ---- ranges: the same calls over sub-intervals of the resident sequences.  Each range becomes the pair and the rectangle
@@ -1204,28 +1122,26 @@ int check_split_slots(const SplitOut& sp, int64_t i, int32_t match_bonus, int64_
     return fail(AWV_ERR_ARG, "align_split: entry " + std::to_string(i) + " owns fewer slots than awv_split_slots(a, min_score, min(plen, tlen))");
   return AWV_OK;
 }
-int align_ranges_core(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, awv_result* out,
-                      awv_verify_result* vout, awv_sink sink, void* user, const int32_t* max_penalty = nullptr,
-                      awv_clip_result* cout = nullptr, int32_t match_bonus = 0, const SplitOut* split = nullptr) {
+// rq: everything but the pairs and rectangles, which the ranges become; rq.pair_bound as the caller gave it (nullable)
+int align_ranges_core(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, AlignRequest rq) {
   if (n < 0 || (n > 0 && !ranges)) return fail(AWV_ERR_ARG, "align_ranges: null ranges");
-  if (e->seqs.n == 0 && n > 0) return fail(AWV_ERR_STATE, "align_ranges before set_sequences");
+  if (int rc = require_sequences(e, n, "align_ranges")) return rc;
   std::vector<awv_pair> pairs;
   std::vector<awvr::Span> spans;
   if (int rc = split_ranges(e->seqs, ranges, n, pairs, spans, "align_ranges")) return rc;
-  if (vout) awvf::stats_reset(e->verify);
-  if (n == 0) return align_core(e, e->seqs, pen, nullptr, 0, out, sink, user);
-  if (split)  // the slot rule over the two interval lengths, before anything is launched
+  if (rq.vout) awvf::stats_reset(e->verify);
+  if (n == 0) return align_core(e, e->seqs, pen, full_request(nullptr, 0, rq.out, rq.sink, rq.user));
+  if (rq.split)  // the slot rule over the two interval lengths, before anything is launched
     for (int64_t i = 0; i < n; ++i) {
       const awvr::Span& sp = spans[(size_t)i];
-      if (int rc = check_split_slots(*split, i, match_bonus, std::min(sp.pe - sp.pb, sp.te - sp.tb))) return rc;
+      if (int rc = check_split_slots(*rq.split, i, rq.match_bonus, std::min(sp.pe - sp.pb, sp.te - sp.tb))) return rc;
     }
   std::vector<int32_t> pb;
-  if (max_penalty) {
-    pb.resize((size_t)n);
-    for (int64_t i = 0; i < n; ++i) pb[(size_t)i] = norm_bound(max_penalty[i]);
-  }
-  return align_core(e, e->seqs, pen, pairs.data(), n, out, sink, user, false, INT_MAX, max_penalty ? pb.data() : nullptr, vout, spans.data(),
-                    cout, match_bonus, split);
+  rq.pairs = pairs.data();
+  rq.npairs = n;
+  rq.spans = spans.data();
+  rq.pair_bound = normalized_bounds(rq.pair_bound, n, pb);
+  return align_core(e, e->seqs, pen, rq);
 }
 // what every clipping call refuses before anything is launched
 int check_clip_args(const awv_clip_result* cout, int32_t match_bonus) {
@@ -1239,17 +1155,17 @@ int awv_align_pairs_clipped(awv_engine* e, const awv_penalties* pen, const awv_p
                             int32_t match_bonus, awv_result* out, awv_verify_result* vout, awv_clip_result* cout, awv_sink sink, void* user) {
   if (!e) return fail(AWV_ERR_ARG, "null engine");
   if (int rc = check_clip_args(cout, match_bonus)) return rc;
-  if (e->seqs.n == 0 && npairs > 0) return fail(AWV_ERR_STATE, "align_pairs before set_sequences");
+  if (int rc = require_sequences(e, npairs, "align_pairs")) return rc;
   if (vout) awvf::stats_reset(e->verify);
   awvc::stats_reset(e->clip);
   AWV_GUARDED(
     std::vector<int32_t> pb;
-    if (max_penalty) {
-      pb.resize((size_t)std::max<int64_t>(npairs, 0));
-      for (int64_t i = 0; i < npairs; ++i) pb[(size_t)i] = norm_bound(max_penalty[i]);
-    }
-    return align_core(e, e->seqs, pen, pairs, npairs, out, sink, user, false, INT_MAX, max_penalty && npairs > 0 ? pb.data() : nullptr, vout,
-                      nullptr, cout, match_bonus);
+    AlignRequest rq = full_request(pairs, npairs, out, sink, user);
+    rq.pair_bound = normalized_bounds(max_penalty, npairs, pb);
+    rq.vout = vout;
+    rq.cout = cout;
+    rq.match_bonus = match_bonus;
+    return align_core(e, e->seqs, pen, rq);
   )
 }
 
@@ -1258,7 +1174,12 @@ int awv_align_ranges_clipped(awv_engine* e, const awv_penalties* pen, const awv_
   if (!e) return fail(AWV_ERR_ARG, "null engine");
   if (int rc = check_clip_args(cout, match_bonus)) return rc;
   awvc::stats_reset(e->clip);
-  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, out, vout, sink, user, max_penalty, cout, match_bonus);)
+  AlignRequest rq = full_request(nullptr, 0, out, sink, user);
+  rq.pair_bound = max_penalty;
+  rq.vout = vout;
+  rq.cout = cout;
+  rq.match_bonus = match_bonus;
+  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, rq);)
 }
 
 int awv_align_pairs_split(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const int32_t* max_penalty,
@@ -1268,7 +1189,7 @@ int awv_align_pairs_split(awv_engine* e, const awv_penalties* pen, const awv_pai
   if (npairs < 0 || (npairs > 0 && !pairs)) return fail(AWV_ERR_ARG, "align_pairs: null pairs");
   const SplitOut sp{min_score, seg_first, iout, sout};
   if (int rc = check_split_args(match_bonus, sp, npairs)) return rc;
-  if (e->seqs.n == 0 && npairs > 0) return fail(AWV_ERR_STATE, "align_pairs before set_sequences");
+  if (int rc = require_sequences(e, npairs, "align_pairs")) return rc;
   for (int64_t i = 0; i < npairs; ++i) {
     if (pairs[i].q_idx < 0 || pairs[i].q_idx >= e->seqs.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= e->seqs.n)
       return fail(AWV_ERR_ARG, "align_pairs: sequence index out of range");
@@ -1278,12 +1199,12 @@ int awv_align_pairs_split(awv_engine* e, const awv_penalties* pen, const awv_pai
   awvs::stats_reset(e->split);
   AWV_GUARDED(
     std::vector<int32_t> pb;
-    if (max_penalty) {
-      pb.resize((size_t)npairs);
-      for (int64_t i = 0; i < npairs; ++i) pb[(size_t)i] = norm_bound(max_penalty[i]);
-    }
-    return align_core(e, e->seqs, pen, pairs, npairs, out, sink, user, false, INT_MAX, max_penalty && npairs > 0 ? pb.data() : nullptr, vout,
-                      nullptr, nullptr, match_bonus, &sp);
+    AlignRequest rq = full_request(pairs, npairs, out, sink, user);
+    rq.pair_bound = normalized_bounds(max_penalty, npairs, pb);
+    rq.vout = vout;
+    rq.match_bonus = match_bonus;
+    rq.split = &sp;
+    return align_core(e, e->seqs, pen, rq);
   )
 }
 
@@ -1295,26 +1216,36 @@ int awv_align_ranges_split(awv_engine* e, const awv_penalties* pen, const awv_ra
   const SplitOut sp{min_score, seg_first, iout, sout};
   if (int rc = check_split_args(match_bonus, sp, n)) return rc;
   awvs::stats_reset(e->split);
-  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, out, vout, sink, user, max_penalty, nullptr, match_bonus, &sp);)
+  AlignRequest rq = full_request(nullptr, 0, out, sink, user);
+  rq.pair_bound = max_penalty;
+  rq.vout = vout;
+  rq.match_bonus = match_bonus;
+  rq.split = &sp;
+  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, rq);)
 }
 
 int awv_align_pairs_bounded(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const int32_t* max_penalty,
                             awv_result* out, awv_verify_result* vout, awv_sink sink, void* user) {
   if (!e) return fail(AWV_ERR_ARG, "null engine");
   if (npairs > 0 && !max_penalty) return fail(AWV_ERR_ARG, "align_pairs_bounded: null max_penalty");
-  if (e->seqs.n == 0 && npairs > 0) return fail(AWV_ERR_STATE, "align_pairs before set_sequences");
+  if (int rc = require_sequences(e, npairs, "align_pairs")) return rc;
   if (vout) awvf::stats_reset(e->verify);
   AWV_GUARDED(
-    std::vector<int32_t> pb((size_t)std::max<int64_t>(npairs, 0));
-    for (int64_t i = 0; i < npairs; ++i) pb[(size_t)i] = norm_bound(max_penalty[i]);
-    return align_core(e, e->seqs, pen, pairs, npairs, out, sink, user, false, INT_MAX, npairs > 0 ? pb.data() : nullptr, vout);
+    std::vector<int32_t> pb;
+    AlignRequest rq = full_request(pairs, npairs, out, sink, user);
+    rq.pair_bound = normalized_bounds(max_penalty, npairs, pb);
+    rq.vout = vout;
+    return align_core(e, e->seqs, pen, rq);
   )
 }
 
 int awv_align_ranges_bounded(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const int32_t* max_penalty,
                              awv_result* out, awv_verify_result* vout, awv_sink sink, void* user) {
   if (!e) return fail(AWV_ERR_ARG, "null engine");
-  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, out, vout, sink, user, max_penalty);)
+  AlignRequest rq = full_request(nullptr, 0, out, sink, user);
+  rq.pair_bound = max_penalty;
+  rq.vout = vout;
+  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, rq);)
 }
 
 int32_t awv_divergence_bound(const awv_penalties* pen, int32_t plen, int32_t tlen, double d) {
@@ -1337,27 +1268,33 @@ int32_t awv_divergence_bound(const awv_penalties* pen, int32_t plen, int32_t tle
 int awv_align_ranges(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, awv_result* out,
                      awv_sink sink, void* user) {
   if (!e) return fail(AWV_ERR_ARG, "null engine");
-  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, out, nullptr, sink, user);)
+  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, full_request(nullptr, 0, out, sink, user));)
 }
 
 int awv_align_ranges_verified(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, awv_result* out,
                               awv_verify_result* vout, awv_sink sink, void* user) {
   if (!e) return fail(AWV_ERR_ARG, "null engine");
   if (!vout) return fail(AWV_ERR_ARG, "align_ranges_verified: null vout");
-  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, out, vout, sink, user);)
+  AlignRequest rq = full_request(nullptr, 0, out, sink, user);
+  rq.vout = vout;
+  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, rq);)
 }
 
 int awv_score_ranges(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const int32_t* max_penalty,
                      awv_score_result* out) {
-  if (!e) return score_core(nullptr, pen, nullptr, 0, -1, nullptr, out);  // (says which: no device, or a null engine)
+  if (!e) return awv_internal_null_engine();  // (says which: no device, or a null engine)
   if (!out) return fail(AWV_ERR_ARG, "score_ranges: null out");
   if (n < 0 || (n > 0 && !ranges)) return fail(AWV_ERR_ARG, "score_ranges: null ranges");
-  if (e->seqs.n == 0 && n > 0) return fail(AWV_ERR_STATE, "score_ranges before set_sequences");
+  if (int rc = require_sequences(e, n, "score_ranges")) return rc;
   AWV_GUARDED(
     std::vector<awv_pair> pairs;
     std::vector<awvr::Span> spans;
     if (int rc = split_ranges(e->seqs, ranges, n, pairs, spans, "score_ranges")) return rc;
-    return score_core(e, pen, pairs.data(), n, -1, max_penalty, out, spans.data());
+    AlignRequest rq = full_request(pairs.data(), n, nullptr, nullptr, nullptr);
+    rq.max_penalty = -1;
+    rq.pair_bound = max_penalty;
+    rq.spans = spans.data();
+    return score_core(e, pen, rq, out);
   )
 }
 
@@ -1410,7 +1347,7 @@ int align_one_core(awv_engine* e, const awv_penalties* pen, const uint8_t* patte
     const awv_pair p{0, 1, 0};
     OneSink os{cigar_buf, cigar_cap, AWV_OK};
     e->cfg.flags &= ~AWV_F_KEEP_ON_DEVICE;
-    rc = align_core(e, sc.tmp, pen, &p, 1, result, one_sink, &os);
+    rc = align_core(e, sc.tmp, pen, full_request(&p, 1, result, one_sink, &os));
     if (rc == AWV_ERR_SINK && os.rc != AWV_OK) rc = fail(os.rc, "align_one: cigar buffer too small");
   }
   return rc;

@@ -1,8 +1,8 @@
 """The penalty space the kernels are run over, and a restatement of what the engine derives from a penalty set.
 
-The kernels are compiled once; every penalty-dependent choice is made at run time by the host, in `check_penalties` and
-at the top of `align_core` (allwave_amd/csrc/engine.hip).  `derive` restates that derivation line by line so that the
-tests can (i) check that the named sets below reach every derived class -- ring depth, steps per multi-step pass, chained
+The kernels are compiled once; every penalty-dependent choice is made at run time by the host, in `plan_penalties`
+(allwave_amd/csrc/batch_plan.hpp; engine.hip's `align_core` calls it first).  `derive` restates that derivation line by line so
+that the tests can (o) compare it field for field with the header's own output (tests/test_batch_plan_cpu.py), (i) check that the named sets below reach every derived class -- ring depth, steps per multi-step pass, chained
 sweeps, base-case history bound, 2-piece shape -- on both sides of every boundary, and (ii) check the restatement against
 what the engine reports (awv_stats.multi_cell_steps, AWV_ERR_PENALTIES).
 
@@ -12,14 +12,14 @@ Scores are given the way the reference passes them: (match, x, o, e) for gap-aff
 from collections import namedtuple
 
 # allwave_amd/csrc/biwfa_device.hpp
-MAX_SCOPE = 126            # check_penalties: scope + 2 <= 128
+MAX_SCOPE = 126            # plan_penalties: scope + 2 <= 128
 MAX_RING = 256             # the deepest ring an accepted set can need (scope 126 plus a chained pass)
 TMAX = 5                   # AWV_TMAX: steps per sweep
 TMAX32 = 5                 # AWV_TMAX32: steps per sweep with 32-bit rows
 CHAIN_MAX = 3              # AWV_CHAIN_MAX: sweeps a pass may chain
 FALLBACK_MIN_SCORE = 250   # base case when score_remaining <= 250 ...
 FALLBACK_MIN_LENGTH = 100  # ... or both lengths <= 100
-MAX_SB = 4000              # align_core: the base-case history is sized for scores up to 4000
+MAX_SB = 4000              # plan_penalties: the base-case history is sized for scores up to 4000
 NCOMP = 5                  # M, I1, I2, D1, D2 rows per direction
 
 # flags of include/allwave_hip.h that change the derivation
@@ -34,7 +34,7 @@ def _pieces(scores):
     if len(s) == 6:
         return s[0], s[1], s[2], s[3], s[4], s[5], True
     if len(s) == 4:
-        return s[0], s[1], s[2], s[3], s[2], s[3], False   # gap-affine: piece 2 = piece 1 (engine.hip check_penalties)
+        return s[0], s[1], s[2], s[3], s[2], s[3], False   # gap-affine: piece 2 = piece 1 (batch_plan.hpp plan_penalties)
     raise ValueError("expected 4 or 6 scores, got %d" % len(s))
 
 
@@ -45,13 +45,13 @@ def gap(scores, n):
 
 
 def derive(scores, flags=0):
-    """What the engine derives from a penalty set (allwave_amd/csrc/engine.hip, check_penalties and align_core)."""
+    """What the engine derives from a penalty set (allwave_amd/csrc/batch_plan.hpp, plan_penalties)."""
     m, x, o1, e1, o2, e2, two_piece = _pieces(scores)
 
     def out(accepted, reason, scope=0, multi_T=0, multi_T32=0, chain_max=1, ring=0, sb=0):
         return Derived(accepted, reason, two_piece, x, o1, e1, o2, e2, scope, multi_T, multi_T32, chain_max, ring, sb)
 
-    # check_penalties
+    # check_signs, then the scope
     if m != 0:
         return out(False, "match != 0")
     if x <= 0 or o1 < 0 or e1 <= 0:
@@ -61,7 +61,7 @@ def derive(scores, flags=0):
     scope = max(x, o1 + e1, o2 + e2) + 1
     if scope > MAX_SCOPE:
         return out(False, "scope", scope)
-    # align_core: multi-step passes, T <= the nearest M source, only for the instantiated I/D depths
+    # multi-step passes, T <= the nearest M source, only for the instantiated I/D depths
     multi_T = min(x, o1 + e1, TMAX)
     if two_piece:
         multi_T = min(multi_T, o2 + e2)
@@ -80,7 +80,7 @@ def derive(scores, flags=0):
     n = FALLBACK_MIN_LENGTH
     worst = min(2 * gap(scores, n), n * x + gap(scores, n))
     sb = max(FALLBACK_MIN_SCORE + max(o1, o2), worst)
-    # 32-bit rows: sweeps of at most TMAX32 steps (the run_group launch parameters)
+    # 32-bit rows: sweeps of at most TMAX32 steps (engine.hip fill_kparams)
     multi_T32 = min(multi_T, TMAX32) if min(multi_T, TMAX32) >= 2 else 0
     if sb > MAX_SB:
         return out(False, "sb", scope, multi_T, multi_T32, chain_max, ring, sb)

@@ -4,7 +4,7 @@ and termination as the kernels.
 
 For every pair: status 0; penalty == gotoh_penalty_banded(..., bound=penalty) (a penalty above the optimum makes the DP
 find a lower one, a penalty below it makes the DP return more); the CIGAR is valid and re-scores to the penalty; the
-M/X/I/D counts and q_end / t_end are the CIGAR's.  The paths are those of the routing in align_core (engine.hip, the
+M/X/I/D counts and q_end / t_end are the CIGAR's.  The paths are those of the routing in assign_groups (batch_plan.hpp, the
 NG = 9 group table): one wave with 16-bit rows and multi-step passes, four and sixteen waves, 32-bit rows, wide16 rows,
 chains through LDS, 16-bit sub-searches inside 32-bit launches, in-place packed, staged and raw-byte probes, reverse
 complements and restarted searches; where the engine's counters can show that a path ran, the test asserts it.  The DP
