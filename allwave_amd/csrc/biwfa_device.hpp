@@ -45,6 +45,7 @@
 
 #include "range_span.hpp"
 #include "twin_base.hpp"
+#include "row_reuse.hpp"
 
 #ifndef AWV_NS
 #define AWV_NS awv
@@ -124,6 +125,9 @@ enum { STAT_CELLS = 0, STAT_EXTEND, STAT_BREAKPOINTS, STAT_BASE, STAT_OVERLAP, S
        // units with a twin, searches run shared, searches run per orientation inside twin units, shared searches whose two
        // breakpoints were not mirrors
        STAT_TWIN_UNITS = STAT_N, STAT_TWIN_SHARED, STAT_TWIN_SOLO, STAT_TWIN_NONMIRROR,
+       // row reuse, added to KParams::stats by the search that took rows from the archive: the cell-steps of
+       // those rows (part of STAT_CELLS and STAT_MULTI_CELLS all the same), and the searches
+       STAT_REUSE_CELLS, STAT_REUSE_SEARCHES,
        STAT_N_DEV };
 
 #ifdef AWV_PROF
@@ -190,6 +194,11 @@ struct KParams {
   int twin_levels;
   int twin_base;  // 1: a base case under a shared task runs its wavefronts once and is backtraced for both orientations
 };
+// Row archives (row_reuse.hpp).  KParams stays as it is -- a longer one would move the second kernel argument of
+// the range kernels -- so the launch's archive descriptor lies behind the counters, at KParams::stats[STAT_N_DEV ..]: the
+// arena (0: the launch keeps no archives), the bytes per workgroup slot, passes | T << 32, and the I/D rows per pass; a slot
+// is laid out as awvrr::make_layout(passes, T, nid).  Only the one-wave kernels with 16-bit rows look at it.
+constexpr int RR_DESC_WORDS = 4;
 
 struct RowMeta { int lo, hi; };
 constexpr int K_BIG = 1 << 28;  // an empty row is {K_BIG, -K_BIG}: min/max hulls ignore it for free
@@ -2190,6 +2199,430 @@ __device__ __attribute__((noinline)) void multi_phase(unsigned sh_addr, unsigned
     deep_phase<P2, OffT, E1, E2>(sh_addr, dyn_addr, sc, fmax, rmax, Tn, pass, npass, (unsigned)cells, (unsigned)(cells >> 32));
 }
 
+// Row reuse (row_reuse.hpp), built into the one-wave kernels with 16-bit rows for whole-pair launches only:
+// a top-level search (RR_RECORD) copies the rows of its full-length far-apart passes into the workgroup's archive as they
+// become official; the forward search of its left child (RR_FWD) and the reverse search of its right child (RR_REV) -- same
+// origin, same begin component, prefixes of the same sequences -- take whole passes of that direction from the archive for
+// as long as the archived rows lie inside the child's box and the child's own pass decisions land on the archive's pass
+// boundaries, and then copy the rows the next pass reads into the child's ring.  Every decision of the phase sees the
+// numbers the skipped computation would have produced (the pass's maximum antidiagonal, its cell count), so margins, chains,
+// restarts and the hand-over to deep_phase are multi_phase's.
+//
+// The phase itself (multi_phase_reuse) is multi_phase's text with four calls added; all the work is in the functions below,
+// never inlined, and the search's reuse state waits in LDS while a pass runs -- in Lds::firstk, which only the overlap search
+// of phase 2 uses: the window loops of compute_rows_multi take the whole register file, and whatever else is alive across
+// them is spilled around them (scratch/spill_audit.py).  The kernel writes words 0..5 before it calls the search.
+constexpr int RR_RECORD = 0x1000, RR_FWD = 0x2000, RR_REV = 0x4000;
+enum { RRS_ARCH_LO = 0, RRS_ARCH_HI, RRS_PASSES, RRS_T, RRS_NID,
+       RRS_PART,   // in: RR_RECORD / RR_FWD / RR_REV / 0; from rr_begin on: 1 while this search archives its passes, else 0
+       RRS_COV,    // the direction this search takes from the archive (-1: none, or no longer)
+       RRS_N,      // passes archived so far (recording) / passes the archive holds (taking)
+       RRS_KMIN,   // the archived search's column origin in direction RRS_COV
+       RRS_BOX,    // 4 words, recording: the running maxima behind P_BOXH / P_BOXV, per direction
+       RRS_SKIP = RRS_BOX + 4,  // the direction whose rows the running pass takes from the archive (-1: none) ...
+       RRS_MAXAK,  // ... that archived pass's maximum antidiagonal ...
+       RRS_CELLS,  // ... and its cell-steps
+       RRS_WORDS };
+static_assert(RRS_WORDS == 16, "the kernel asks for scope * NCOMP >= RRS_WORDS words of Lds::firstk");
+typedef __attribute__((address_space(1))) unsigned char* garch_t;
+
+// what the functions below read of the running search: rebuilt from Shared::pctx and the state words, like multi_phase's own
+template <typename OffT>
+struct RrEnv {
+  typedef typename MetaTraits<OffT>::Stored MetaStored;
+  Shared* sh;
+  KParams kp;
+  int plen, tlen, kmin[2], wcols;
+  MetaStored* ring_meta;
+  int* st;
+  garch_t ring, arch;
+  awvrr::Layout al;
+  __device__ __forceinline__ __attribute__((address_space(1))) int* word(size_t byte_off) const { return (__attribute__((address_space(1))) int*)(arch + byte_off); }
+  __device__ __forceinline__ int load(size_t byte_off) const { return uni(__hip_atomic_load((int*)word(byte_off), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); }
+  __device__ __forceinline__ garch_t ring_row(int dir, int comp, int score) const { return ring + (unsigned)row_off<false, OffT>(kp, dir, comp, score); }
+};
+template <bool P2, typename OffT>
+__device__ __forceinline__ RrEnv<OffT> rr_env(unsigned sh_addr, unsigned dyn_addr) {
+  static_assert(WG == 64 && sizeof(OffT) == 2 && !wenc_of<OffT>(), "row archives: one wave per workgroup, 16-bit text offsets");
+  RrEnv<OffT> e;
+  e.sh = (Shared*)__builtin_assume_aligned((Shared*)(lds_shared_ptr)(uintptr_t)uni((int)sh_addr), 8);
+  unsigned char* dyn_smem = (unsigned char*)__builtin_assume_aligned((unsigned char*)(lds_bytes_ptr)(uintptr_t)uni((int)dyn_addr), 16);
+  const PassCtx& pc = e.sh->pctx;
+  auto uni64 = [](unsigned long long v) { return ((unsigned long long)(unsigned)uni((int)(v >> 32)) << 32) | (unsigned)uni((int)v); };
+  e.kp = KParams{};
+  e.kp.ring = uni(pc.ring);
+  e.kp.wcap = uni(pc.wcap);
+  e.kp.pen.x = uni(pc.x);
+  e.kp.pen.o1 = uni(pc.o1);
+  e.kp.pen.e1 = uni(pc.e1);
+  e.kp.pen.o2 = uni(pc.o2);
+  e.kp.pen.e2 = uni(pc.e2);
+  e.kp.pen.two_piece = P2 ? 1 : 0;
+  e.kp.pen.scope = max(e.kp.pen.x, max(e.kp.pen.o1 + e.kp.pen.e1, P2 ? e.kp.pen.o2 + e.kp.pen.e2 : 0)) + 1;
+  e.plen = uni(pc.plen);
+  e.tlen = uni(pc.tlen);
+  e.kmin[0] = uni(pc.kmin[0]);
+  e.kmin[1] = uni(pc.kmin[1]);
+  e.wcols = uni(pc.wcols);
+  e.ring_meta = reinterpret_cast<typename RrEnv<OffT>::MetaStored*>(dyn_smem);
+  e.st = reinterpret_cast<int*>(e.ring_meta + 2 * NCOMP * e.kp.ring) + 4 * e.kp.ring;  // Lds::firstk
+  e.ring = (garch_t)(uintptr_t)uni64(pc.ring_mem);
+  e.arch = (garch_t)(uintptr_t)(((unsigned long long)(unsigned)uni(e.st[RRS_ARCH_HI]) << 32) | (unsigned)uni(e.st[RRS_ARCH_LO]));
+  e.al = awvrr::make_layout(uni(e.st[RRS_PASSES]), uni(e.st[RRS_T]), uni(e.st[RRS_NID]));
+  return e;
+}
+
+// When the phase begins (score 0): what this search's part is.  t_full: the length of a full pass under the launch's scores.
+template <bool P2, typename OffT, int E1, int E2>
+__device__ __attribute__((noinline)) void rr_begin(unsigned sh_addr, unsigned dyn_addr, int s0_v, int t_full_v) {
+  constexpr int NID = 2 * E1 + (P2 ? 2 * E2 : 0);
+  const RrEnv<OffT> e = rr_env<P2, OffT>(sh_addr, dyn_addr);
+  const int part = uni(e.st[RRS_PART]);
+  const bool usable = e.arch != nullptr && uni(s0_v) == 0 && e.al.passes > 0 && e.al.nid == NID && e.al.T == uni(t_full_v);
+  const bool rec = usable && (part & RR_RECORD) != 0;
+  int cov = !usable || rec ? -1 : (part & RR_FWD) ? 0 : (part & RR_REV) ? 1 : -1;
+  int n = 0, kmin = 0;
+  if (rec && threadIdx.x == 0) {  // (the archive is void: the kernel set H_NPASS = 0 before this attempt of the search)
+    *e.word(awvrr::H_KMIN0 * 4) = e.kmin[0];
+    *e.word(awvrr::H_KMIN1 * 4) = e.kmin[1];
+  }
+  if (cov >= 0) {
+    n = e.load(awvrr::H_NPASS * 4);
+    kmin = e.load((cov ? awvrr::H_KMIN1 : awvrr::H_KMIN0) * 4);
+    if (n <= 0) cov = -1;
+  }
+  if (threadIdx.x == 0) {
+    e.st[RRS_PART] = rec ? 1 : 0;
+    e.st[RRS_COV] = cov;
+    e.st[RRS_N] = n;
+    e.st[RRS_KMIN] = kmin;
+    e.st[RRS_BOX] = e.st[RRS_BOX + 1] = e.st[RRS_BOX + 2] = e.st[RRS_BOX + 3] = 0;
+    e.st[RRS_SKIP] = -1;
+    e.st[RRS_MAXAK] = e.st[RRS_CELLS] = 0;
+  }
+  __syncthreads();
+}
+
+// The hand-over from taking to computing at score sc, a pass boundary of the archive (every pass so far was taken from it):
+// what the next pass reads of the scores behind it goes into the ring, in this search's columns -- the M rows of the last
+// scope - 1 scores with the hulls of all their components, and the I/D rows the last archived pass left in memory.  A cell
+// outside its row's hull is NULL, as a computed row has it.
+template <bool P2, typename OffT, int E1, int E2>
+__device__ __forceinline__ void rr_hand_over(const RrEnv<OffT>& e, int dirc, int sc) {
+  constexpr int NID = 2 * E1 + (P2 ? 2 * E2 : 0);
+  const awvrr::Layout& al = e.al;
+  const int kminC = dirc ? e.kmin[1] : e.kmin[0], kminA = uni(e.st[RRS_KMIN]);
+  const int fc = awvrr::first_col(al, kminA);
+  const int lane = threadIdx.x & 63, rmask = e.kp.ring - 1;
+  typename RrEnv<OffT>::MetaStored* const meta = e.ring_meta + (size_t)dirc * NCOMP * e.kp.ring;
+  auto put_row = [&](int comp, int score, int apass, int arow) {
+    const int w = e.load(al.meta_off() + al.meta_index(dirc, score, C_M) * 4);  // the M hull of the archived score: the row's stored extent
+    const RowMeta m{(int)(short)(w & 0xffff), (int)(short)(w >> 16)};
+    if (m.lo > m.hi) return;
+    if (m.lo - kminC < 256 + 1 || m.hi - kminC + 256 + 4 + 2 > e.wcols) {  // (compute_rows_multi's test, for the row it would have written)
+      e.sh->error = ST_CAPACITY;
+      return;
+    }
+    const __attribute__((address_space(1))) short* src = (const __attribute__((address_space(1))) short*)(e.arch + al.row_off(dirc, apass, arow));
+    garch_t dst = e.ring_row(dirc, comp, score);
+    const int c_hi = (m.hi - kminC) | 3;
+    for (int c = ((m.lo - kminC) & ~3) + 4 * lane; c <= c_hi; c += 256) {
+      unsigned short v[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = c + j + kminC;
+        v[j] = (k >= m.lo && k <= m.hi) ? (unsigned short)src[k - kminA - fc] : (unsigned short)NULL16;
+      }
+      typedef unsigned int u32x2r __attribute__((ext_vector_type(2)));
+      u32x2r w2;
+      w2[0] = (unsigned)v[0] | ((unsigned)v[1] << 16);
+      w2[1] = (unsigned)v[2] | ((unsigned)v[3] << 16);
+      *(__attribute__((address_space(1))) u32x2r*)(dst + (size_t)c * 2) = w2;
+    }
+  };
+  if (sc > 0) {
+    const int lastp = sc / al.T - 1;
+    for (int s = max(1, sc + 1 - (e.kp.pen.scope - 1)); s <= sc; ++s) {
+      if (lane < NCOMP)
+        *reinterpret_cast<int*>(&meta[lane * e.kp.ring + (s & rmask)]) = __hip_atomic_load((int*)e.word(al.meta_off() + al.meta_index(dirc, s, lane) * 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      put_row(C_M, s, awvrr::pass_of(al, s), awvrr::row_of(al, s));
+    }
+    for (int q = 0; q < NID; ++q) {
+      int qc, qs;
+      multi_source<P2, E1, E2>(e.kp.pen, sc, q, qc, qs);
+      if (qs >= 1) put_row(qc, qs, lastp, awvrr::id_row(al, E1, E2, qc, sc - qs));
+    }
+  }
+  if (threadIdx.x == 0) {
+    e.st[RRS_COV] = -1;
+    e.st[RRS_SKIP] = -1;
+  }
+  __syncthreads();  // the hulls are in LDS and the rows in memory before the pass plans and loads
+}
+
+// Before a pass of T scores from score sc, while this search takes a direction from the archive: the pass is taken when it is
+// archived, inside the box, and the archive's own pass; else the search computes from here on.
+template <bool P2, typename OffT, int E1, int E2>
+__device__ __attribute__((noinline)) void rr_before_pass(unsigned sh_addr, unsigned dyn_addr, int sc_v, int T_v) {
+  const RrEnv<OffT> e = rr_env<P2, OffT>(sh_addr, dyn_addr);
+  const int sc = uni(sc_v), T = uni(T_v), cov = uni(e.st[RRS_COV]);
+  if (cov < 0) return;
+  int take = awvrr::pass_for(e.al, uni(e.st[RRS_N]), sc, T);
+  if (take >= 0) {
+    const size_t tb = e.al.table_off() + e.al.table_index(cov, take) * 4;
+    if (!awvrr::box_ok(e.load(tb + awvrr::P_BOXH * 4), e.load(tb + awvrr::P_BOXV * 4), e.plen, e.tlen)) take = -1;
+    else {
+      const int maxak = e.load(tb + awvrr::P_MAXAK * 4), nc = e.load(tb + awvrr::P_CELLS * 4);
+      if (threadIdx.x == 0) {
+        e.st[RRS_SKIP] = cov;
+        e.st[RRS_MAXAK] = maxak;
+        e.st[RRS_CELLS] = nc;
+        // (this workgroup's own counters: the kernel adds them to the launch's when it ends)
+        __attribute__((address_space(1))) unsigned long long* const rc = (__attribute__((address_space(1))) unsigned long long*)(e.arch + awvrr::H_RCELLS * 4);
+        *rc = __hip_atomic_load((unsigned long long*)rc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + (unsigned long long)nc;
+        if (take == 0) *e.word(awvrr::H_RSEARCH * 4) = __hip_atomic_load((int*)e.word(awvrr::H_RSEARCH * 4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+      }
+      __syncthreads();
+    }
+  }
+  if (take < 0) rr_hand_over<P2, OffT, E1, E2>(e, cov, sc);
+}
+
+// When the phase ends while a direction is still taken from the archive: whoever goes on from sc computes.
+template <bool P2, typename OffT, int E1, int E2>
+__device__ __attribute__((noinline)) void rr_end(unsigned sh_addr, unsigned dyn_addr, int sc_v) {
+  const RrEnv<OffT> e = rr_env<P2, OffT>(sh_addr, dyn_addr);
+  const int cov = uni(e.st[RRS_COV]);
+  if (cov >= 0) rr_hand_over<P2, OffT, E1, E2>(e, cov, uni(sc_v));
+}
+
+// After a pass of T scores from score sc has become official, while this search archives: into the archive with its rows, as
+// long as the passes are the full-length ones from score 0 on and the hulls fit the archive's rows.  The first pass that is
+// not closes the archive for this search.  P0 / P1: the pass's maximum antidiagonals, nc0 / nc1 its cell-steps, arun0 / arun1
+// the search's maximum antidiagonals so far, per direction.
+template <bool P2, typename OffT, int E1, int E2>
+__device__ __attribute__((noinline)) void rr_after_pass(unsigned sh_addr, unsigned dyn_addr, int sc_v, int T_v, int P0_v, int P1_v, int nc0_v, int nc1_v,
+                                                        int arun0_v, int arun1_v) {
+  constexpr int NID = 2 * E1 + (P2 ? 2 * E2 : 0);
+  const RrEnv<OffT> e = rr_env<P2, OffT>(sh_addr, dyn_addr);
+  if (uni(e.st[RRS_PART]) == 0) return;
+  const awvrr::Layout& al = e.al;
+  const int sc = uni(sc_v), T = uni(T_v), n = uni(e.st[RRS_N]);
+  const int lane = threadIdx.x & 63, rmask = e.kp.ring - 1;
+  bool ok = n < al.passes && T == al.T && sc == n * al.T;
+  int hmax[2] = {-K_BIG, -K_BIG}, lmin[2] = {K_BIG, K_BIG};
+#pragma unroll
+  for (int d = 0; d < 2; ++d) {
+    typename RrEnv<OffT>::MetaStored* const meta = e.ring_meta + (size_t)d * NCOMP * e.kp.ring;
+    for (int t = 0; t < T && ok; ++t) {
+      const RowMeta m = uni(meta_load(&meta[C_M * e.kp.ring + ((sc + 1 + t) & rmask)]));
+      if (!awvrr::hull_fits(al, m.lo, m.hi)) ok = false;
+      if (m.lo <= m.hi) { hmax[d] = max(hmax[d], m.hi); lmin[d] = min(lmin[d], m.lo); }
+    }
+  }
+  if (!ok) {
+    if (threadIdx.x == 0) e.st[RRS_PART] = 0;
+    __syncthreads();
+    return;
+  }
+#pragma unroll
+  for (int d = 0; d < 2; ++d) {
+    typename RrEnv<OffT>::MetaStored* const meta = e.ring_meta + (size_t)d * NCOMP * e.kp.ring;
+    const int kminD = d ? e.kmin[1] : e.kmin[0];
+    const int fc = awvrr::first_col(al, kminD);
+    for (int r = 0; r < T + NID; ++r) {
+      int comp = C_M, score = sc + 1 + r;
+      if (r >= T) multi_source<P2, E1, E2>(e.kp.pen, sc + T, r - T, comp, score);
+      if (score < 1) continue;
+      if (r < T && lane < NCOMP)
+        *e.word(al.meta_off() + al.meta_index(d, score, lane) * 4) = *reinterpret_cast<const int*>(&meta[lane * e.kp.ring + (score & rmask)]);
+      const RowMeta m = uni(meta_load(&meta[C_M * e.kp.ring + (score & rmask)]));
+      if (m.lo > m.hi) continue;
+      typedef unsigned int u32x2r __attribute__((ext_vector_type(2)));
+      const garch_t src = e.ring_row(d, comp, score);
+      garch_t dst = e.arch + al.row_off(d, n, r);
+      const int c_hi = (m.hi - kminD) | 3;
+      for (int c = ((m.lo - kminD) & ~3) + 4 * lane; c <= c_hi; c += 256)
+        *(__attribute__((address_space(1))) u32x2r*)(dst + (size_t)(c - fc) * 2) = *(const __attribute__((address_space(1))) u32x2r*)(src + (size_t)c * 2);
+    }
+    const int ar = uni(d ? arun1_v : arun0_v);
+    int boxh = uni(e.st[RRS_BOX + 2 * d]), boxv = uni(e.st[RRS_BOX + 2 * d + 1]);
+    if (hmax[d] >= lmin[d]) {
+      boxh = max(boxh, ar + hmax[d]);
+      boxv = max(boxv, ar - lmin[d]);
+    }
+    if (lane == 0) {
+      e.st[RRS_BOX + 2 * d] = boxh;
+      e.st[RRS_BOX + 2 * d + 1] = boxv;
+      const size_t tb = al.table_off() + al.table_index(d, n) * 4;
+      *e.word(tb + awvrr::P_MAXAK * 4) = uni(d ? P1_v : P0_v);
+      *e.word(tb + awvrr::P_CELLS * 4) = uni(d ? nc1_v : nc0_v);
+      *e.word(tb + awvrr::P_BOXH * 4) = boxh;
+      *e.word(tb + awvrr::P_BOXV * 4) = boxv;
+    }
+  }
+  if (lane == 0) {
+    e.st[RRS_N] = n + 1;
+    *e.word(awvrr::H_NPASS * 4) = n + 1;
+  }
+  __syncthreads();
+}
+
+// multi_phase with a row archive: multi_phase's text, line for line, plus the calls of rr_begin, rr_before_pass, rr_after_pass and
+// rr_end and the archived numbers of a direction that was not computed.  A function of its own: multi_phase's text and code stay
+// as they are for every other kernel (DESIGN.md 4.28 records what a shared body cost).
+template <bool P2, typename OffT, int E1, int E2, bool CHAIN>
+__device__ __attribute__((noinline)) void multi_phase_reuse(unsigned sh_addr, unsigned dyn_addr, int s0_v, int fmax_v, int rmax_v, int Tn_v, int pass_v, int deep_v) {
+  Shared& sh = *(Shared*)__builtin_assume_aligned((Shared*)(lds_shared_ptr)(uintptr_t)uni((int)sh_addr), 8);
+  unsigned char* dyn_smem = (unsigned char*)__builtin_assume_aligned((unsigned char*)(lds_bytes_ptr)(uintptr_t)uni((int)dyn_addr), 16);
+  const int Tn = uni(Tn_v);
+  int sc = uni(s0_v);  // both directions stand at the same score when the phase begins and after every pass
+  int fmax = uni(fmax_v), rmax = uni(rmax_v), pass = uni(pass_v);
+  const PassCtx& pc = sh.pctx;
+  KParams kp{};
+  kp.ring = uni(pc.ring);
+  kp.wcap = uni(pc.wcap);
+  kp.pen.x = uni(pc.x);
+  kp.pen.o1 = uni(pc.o1);
+  kp.pen.e1 = uni(pc.e1);
+  kp.pen.o2 = uni(pc.o2);
+  kp.pen.e2 = uni(pc.e2);
+  kp.pen.two_piece = P2 ? 1 : 0;
+  kp.pen.scope = max(kp.pen.x, max(kp.pen.o1 + kp.pen.e1, P2 ? kp.pen.o2 + kp.pen.e2 : 0)) + 1;
+  kp.lds_meta_bytes = uni(pc.lds_meta_bytes);
+  auto uni64 = [](unsigned long long v) { return ((unsigned long long)(unsigned)uni((int)(v >> 32)) << 32) | (unsigned)uni((int)v); };
+  SubCtx cx;
+  cx.plen = uni(pc.plen);
+  cx.tlen = uni(pc.tlen);
+  cx.kmin[0] = uni(pc.kmin[0]);
+  cx.kmin[1] = uni(pc.kmin[1]);
+  cx.wcols = uni(pc.wcols);
+  cx.seq_mode = uni(pc.seq_mode);
+  cx.p_w0 = uni(pc.p_w0);
+  cx.t_w0 = uni(pc.t_w0);
+  cx.p_bit = uni(pc.p_bit);
+  cx.t_bit = uni(pc.t_bit);
+  cx.P[0] = (gseq_t)(uintptr_t)uni64(pc.P[0]);
+  cx.P[1] = (gseq_t)(uintptr_t)uni64(pc.P[1]);
+  cx.T[0] = (gseq_t)(uintptr_t)uni64(pc.T[0]);
+  cx.T[1] = (gseq_t)(uintptr_t)uni64(pc.T[1]);
+  cx.Pw = nullptr;
+  cx.Tw = nullptr;
+  cx.pb_abs = cx.tb_abs = 0;
+  Lds<OffT> lds;
+  typedef typename MetaTraits<OffT>::Stored MetaStored;
+  lds.ring_meta = reinterpret_cast<MetaStored*>(dyn_smem);
+  lds.bi_A = reinterpret_cast<int*>(lds.ring_meta + 2 * NCOMP * kp.ring);
+  lds.bi_oob = lds.bi_A + 2 * kp.ring;
+  lds.firstk = lds.bi_oob + 2 * kp.ring;
+  lds.seq = reinterpret_cast<uint32_t*>(dyn_smem + kp.lds_meta_bytes);
+  lds.meta_log = nullptr;
+  const rsrc_t rs = make_rsrc((void*)(uintptr_t)uni64(pc.ring_mem), (size_t)uni64(pc.ring_bytes));
+  const int rmask = kp.ring - 1;
+  const int max_antidiagonal = cx.plen + cx.tlen - 1;
+  const int arun_start = fmax + rmax;
+  int arun0 = fmax, arun1 = rmax;  // max antidiagonal over every row computed so far, per direction
+  int nsteps = 0, npass = 0, why = MP_MARGIN;
+  unsigned long long cells = 0;
+  unsigned ext_iters = 0;
+  // 32-bit rows: a third chained sweep when the staging region of the packed sequences can hold the chain rows (compute_rows_multi, LCH)
+  const bool lds_chain = CHAIN && sizeof(OffT) == 4 && cx.seq_mode != 1 &&
+                         uni(pc.lds_seq_bytes) >= (WG / 64) * TMAX32 * 64 * 16;
+  const int margin_shift = (uni(deep_v) >> 8) & 3;  // a restarted search: the margin times four (find_breakpoint)
+  const bool long_reads = (uni(deep_v) & 0x400) != 0;  // a 16-bit search of a launch with 32-bit rows: those reads' margin factor
+  const int chain_cap = CHAIN ? min(max(uni(pc.chain_max), 1), sizeof(OffT) == 2 ? CHAIN_MAX : (lds_chain ? 3 : CHAIN_MAX32)) : 1;
+  int* const rrs = lds.firstk;  // the search's reuse state (RRS_*)
+  rr_begin<P2, OffT, E1, E2>(sh_addr, dyn_addr, sc, chain_cap > 1 ? TMAX * chain_cap : Tn);
+  for (;;) {
+    if (sc >= uni(pc.score_cap)) { why = MP_BOUND; break; }  // (score-only bound: no pass from this score on, no deep_phase)
+    // Start keeping every I/D row well before the furthest points can meet: the margin is several times what
+    // the two searches advance while `scope` more rows (and one more pass) are computed.  The longest chain
+    // whose own length still fits in front of that margin is taken.
+    const int grow = nsteps > 0 ? (arun0 + arun1 - arun_start) / nsteps : 0;
+    int nh = 0;
+    for (int c = chain_cap; c >= 1; --c) {
+      const int T = c > 1 ? TMAX * c : Tn;
+      // (32-bit rows = long sequences with long exact runs: the searches advance in larger bursts, 2.0 x instead of 1.5 x -- config 4:
+      // 9.91 s and 4.9 k restarted searches against 10.31 s and 26 k)
+      const int mul4 = (sizeof(OffT) == 2 && !long_reads) ? MARGIN_MUL4 : MARGIN_MUL4 + 2;
+      if (arun0 + arun1 < max_antidiagonal - ((MARGIN_BASE + mul4 * (kp.pen.scope + T) * max(grow, 8) / 4) << margin_shift)) { nh = c; break; }
+    }
+    if (nh == 0) { why = MP_MARGIN; break; }
+    const int T = nh > 1 ? TMAX * nh : Tn;
+    const int aslot = pass % 3;
+    int nc0 = 0, nc1 = 0;
+    if (uni(rrs[RRS_COV]) >= 0) rr_before_pass<P2, OffT, E1, E2>(sh_addr, dyn_addr, sc, T);
+    // (a real loop over the direction: one copy of the pass code; per-direction values are picked by
+    // selects, never by indexing a register array with the run-time `dir`)
+#pragma nounroll
+    for (int dir = 0; dir < 2; ++dir) {
+      if (uni(rrs[RRS_SKIP]) == dir) continue;  // this direction's rows are the archive's
+      MultiPlan mp;
+      const unsigned long long tpl = PROF_NOW();
+      plan_multi<P2, OffT, E1, E2, false>(kp, lds, cx, dir, sc, T, nh, mp);
+      mp.lds_chain = lds_chain ? 1 : 0;
+      PROF_ADD_L(STAT_T_CR_REDUCE, tpl);  // (diagnostic build: the passes' planning is booked under "reduce")
+      Acc& acc = dir ? sh.acc[aslot][1] : sh.acc[aslot][0];
+      const int nc = compute_rows_multi<P2, OffT, E1, E2, false, CHAIN>(kp, sh, lds, cx, rs, dir, sc, mp, acc, dir ? sh.chain_maxak[1] : sh.chain_maxak[0], ext_iters);
+      if (dir) nc1 = nc; else nc0 = nc;
+    }
+    __syncthreads();
+    if (uni(sh.error)) { why = MP_ERROR; break; }
+    if (uni(sh.acc[aslot][0].oob) != 0 || uni(sh.acc[aslot][1].oob) != 0) { why = MP_DISCARD; break; }  // the pass assumed untrimmed rows
+    const int rr_skip = uni(rrs[RRS_SKIP]);  // (the direction that was not computed: its pass's cell-steps and maximum as archived)
+    if (rr_skip == 0) nc0 = uni(rrs[RRS_CELLS]);
+    if (rr_skip == 1) nc1 = uni(rrs[RRS_CELLS]);
+    cells += (unsigned long long)(nc0 + nc1);
+    // The pass's rows become official.  WFA2's phase-1 order is forward, test, reverse, test per score (A.6), but
+    // the running maxima only grow: some test inside the pass holds exactly when the one after its last score
+    // does -- so one maximum per direction over the whole pass decides it, and no per-score reduction is
+    // needed.  (No per-score entries -- bi_A / bi_oob -- are written for a far-apart pass's scores: their only reader, the
+    // overlap search of phase 2, looks at the last `scope` scores of either side, all of which lie at or above `deep_since`
+    // (deep_ok), i.e. past every far-apart pass; a ring slot is rewritten by the deep pass or step that next lands on it.)
+    const int P0 = rr_skip == 0 ? uni(rrs[RRS_MAXAK]) : uni(sh.chain_maxak[0][0]), P1 = rr_skip == 1 ? uni(rrs[RRS_MAXAK]) : uni(sh.chain_maxak[1][0]);
+    arun0 = max(arun0, P0);
+    arun1 = max(arun1, P1);
+    fmax = max(fmax, P0);
+    rmax = max(rmax, P1);
+    const bool met = fmax + rmax >= max_antidiagonal;
+    if (uni(rrs[RRS_PART]) != 0) rr_after_pass<P2, OffT, E1, E2>(sh_addr, dyn_addr, sc, T, P0, P1, nc0, nc1, arun0, arun1);
+    __syncthreads();  // everyone has read the pass's maxima
+    if (threadIdx.x < 16) sh.chain_maxak[threadIdx.x >> 3][threadIdx.x & 7] = 0;
+    if (threadIdx.x == 0) { acc_reset(sh.acc[(pass + 2) % 3][0]); acc_reset(sh.acc[(pass + 2) % 3][1]); }
+    __syncthreads();  // ... and they are clear before the next pass adds to them
+    ++pass;
+    ++npass;
+    nsteps += T;
+    sc += T;
+    if (met) { why = MP_MET; break; }
+  }
+  if (uni(rrs[RRS_COV]) >= 0) rr_end<P2, OffT, E1, E2>(sh_addr, dyn_addr, sc);
+  __syncthreads();  // every thread is past its last look at the accumulators
+  if (threadIdx.x == 0) {
+    PhaseResult& pr = sh.pres;
+    pr.why = why;
+    pr.sc = sc;
+    pr.sf = pr.sr = sc;
+    pr.last_fwd = 0;
+    pr.deep_from = sc;
+    pr.fmax = fmax;
+    pr.rmax = rmax;
+    pr.npass = npass;
+    pr.cells = cells;
+    pr.deep_cells = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { acc_reset(sh.acc[i][0]); acc_reset(sh.acc[i][1]); }  // whatever the caller's pass counter says next, its slot is clean
+  }
+  if (threadIdx.x < 16) sh.chain_maxak[threadIdx.x >> 3][threadIdx.x & 7] = 0;
+  atomicAdd(&sh.ext_multi, (unsigned long long)ext_iters);
+  __syncthreads();
+  // The margin is reached: the rest of phase 1 runs in passes that store every I/D row (deep_phase), called from HERE -- a call
+  // site of its own in find_breakpoint_fn cost that function's step-by-step loop register spills (config 5's forced-gap pairs,
+  // which live in that loop: +24 %); its result record replaces the one above and carries the far-apart passes' counts along.
+  if ((uni(deep_v) & 1) != 0 && why == MP_MARGIN)
+    deep_phase<P2, OffT, E1, E2>(sh_addr, dyn_addr, sc, fmax, rmax, Tn, pass, npass, (unsigned)cells, (unsigned)(cells >> 32));
+}
+
 // The rest of phase 1 in passes (round 3).  From the safety margin on, every I/D row has to be in memory -- the overlap search
 // of phase 2 reads those of the last `scope` scores -- and round 2 went step by step there: 80 % of all step-by-step window-steps
 // of config 2 lay in that zone (profiles/r03/zones.json).  deep_phase runs it in single sweeps of T scores that keep the I/D
@@ -3659,6 +4092,272 @@ __device__ __forceinline__ int find_breakpoint(const KParams& kp, Shared& sh, co
   return rc;
 }
 
+// find_breakpoint for a kernel that keeps row archives: the same search, line for line, whose far-apart phase is
+// multi_phase_reuse.  (The kernel has written the search's part into Lds::firstk, which nothing touches before phase 2.)
+template <bool P2, typename OffT>
+__device__ __forceinline__ int find_breakpoint_reuse(const KParams& kp, Shared& sh, const Lds<OffT>& lds, SubCtx cx, void* ring_mem, rsrc_t ring_rs, int cb, int ce,
+                               int score_remaining, int known_score, int attempt, Breakpoint& bp, unsigned long long* lstats) {
+  const DevPenalties& pn = kp.pen;
+  const int tid = cold_tid();
+  const int plen = cx.plen, tlen = cx.tlen;
+  const int rmask = kp.ring - 1;
+  // column spaces: forward kmin, reverse kmin mirrored on chunk boundaries (C == 63 mod 64)
+  {
+    long long bound = (long long)score_remaining + 2LL * pn.scope + 16;
+    // the diagonal range is also clipped to what a row can hold; a wavefront that outgrows it is
+    // detected in compute_row (ST_CAPACITY) and the pair is re-run by the host with wider rows
+    const long long half = (kp.wcap - 2 * COL_PAD - 9 - 256) / 2;
+    bound = min(bound, half);
+    const int blo = (int)min((long long)plen, bound), bhi = (int)min((long long)tlen, bound);
+    const int need = -blo - 4 - COL_PAD;
+    cx.kmin[0] = need;
+    const int D = tlen - plen;
+    const int c0 = D - need - need;
+    const int adj = ((255 - c0) % 256 + 256) % 256;  // mirror on whole 256-column chunks
+    cx.kmin[1] = need - adj;
+    cx.wcols = blo + bhi + 9 + adj + 2 * COL_PAD;
+    if (cx.wcols > kp.wcap) return ST_CAPACITY;
+  }
+  const unsigned sh_addr = (unsigned)(uintptr_t)&sh, dyn_addr = (unsigned)(uintptr_t)lds.ring_meta;  // LDS addresses (low half of the flat ones)
+  if (tid == 0) {  // what multi_phase / trim_pass_fn read back (uniform; the barrier below publishes it)
+    PassCtx& pc = sh.pctx;
+    pc.ring_mem = (unsigned long long)(uintptr_t)ring_mem;
+    pc.ring_bytes = (unsigned long long)kp.ring_slot_stride;
+    pc.P[0] = (unsigned long long)(uintptr_t)cx.P[0];
+    pc.P[1] = (unsigned long long)(uintptr_t)cx.P[1];
+    pc.T[0] = (unsigned long long)(uintptr_t)cx.T[0];
+    pc.T[1] = (unsigned long long)(uintptr_t)cx.T[1];
+    pc.ring = kp.ring;
+    pc.wcap = kp.wcap;
+    pc.x = pn.x; pc.o1 = pn.o1; pc.e1 = pn.e1; pc.o2 = pn.o2; pc.e2 = pn.e2;
+    pc.lds_meta_bytes = kp.lds_meta_bytes;
+    pc.chain_max = kp.chain_max;
+    pc.plen = plen; pc.tlen = tlen;
+    pc.kmin[0] = cx.kmin[0]; pc.kmin[1] = cx.kmin[1];
+    pc.wcols = cx.wcols;
+    pc.seq_mode = cx.seq_mode; pc.p_w0 = cx.p_w0; pc.t_w0 = cx.t_w0; pc.p_bit = cx.p_bit; pc.t_bit = cx.t_bit;
+    // both directions at score s: every breakpoint still to be found costs at least 2 s - (scope - 1) - gap_opening (the
+    // inequality of the bound, below), so from the first s at which that exceeds the bound phase 1 plans no further pass
+    const long long gap_open_max = P2 ? max(pn.o1, pn.o2) : pn.o1;
+    pc.score_cap = kp.max_penalty == INT_MAX ? INT_MAX : (int)min((long long)INT_MAX, ((long long)kp.max_penalty + pn.scope - 1 + gap_open_max) / 2 + 1);
+    sh.ext_multi = 0;
+  }
+  // score-0 wavefronts (wavefront_unialign_init by begin component)
+  for (int i = tid; i < 2 * NCOMP; i += WG) {
+    const int dir = i / NCOMP, c = i % NCOMP;
+    const int begin = dir == 0 ? cb : ce;
+    meta_store(&lds.ring_meta[(dir * NCOMP + c) * kp.ring + 0], (c == begin) ? RowMeta{0, 0} : ROW_EMPTY);
+  }
+  if (tid == 0 || tid == (WG > 64 ? 64 : 1)) {
+    const int dir = tid ? 1 : 0;
+    const int begin = dir == 0 ? cb : ce;
+    unsigned it = 0;
+    int v0 = 0;
+    if (begin == C_M)
+      v0 = cx.seq_mode == 2 ? (dir ? extend_lcp_gw<1>(cx, 0, 0, it) : extend_lcp_gw<0>(cx, 0, 0, it))
+                            : extend_lcp(dir ? cx.P[1] : cx.P[0], dir ? cx.T[1] : cx.T[0], 0, 0, plen, tlen, it);
+    {  // the score-0 row: one cell, stored as a whole lane vector like every other row
+      const int col = 0 - (dir ? cx.kmin[1] : cx.kmin[0]);
+      OffT* row = row_ptr<false, OffT>(kp, ring_mem, dir, begin, 0);
+      for (int j = 0; j < 4; ++j) row[(col & ~3) + j] = (OffT)(sizeof(OffT) == 2 ? NULL16 : OFF_NULL);
+      row[col] = (OffT)v0;
+    }
+    sh.ext0[dir] = v0;
+    lds.bi_A[(dir) * kp.ring + (0)] = (begin == C_M) ? 2 * v0 : 0;
+    lds.bi_oob[(dir) * kp.ring + (0)] = 0;
+    acc_reset(sh.acc[0][dir]);
+    acc_reset(sh.acc[1][dir]);
+    acc_reset(sh.acc[2][dir]);
+  }
+  __syncthreads();
+  if (cb == C_M && ce == C_M && plen == tlen && (uni(sh.ext0[0]) >= tlen || uni(sh.ext0[1]) >= tlen)) return BP_END_REACHED;
+  const int max_antidiagonal = plen + tlen - 1;
+  int sc[2] = {0, 0};    // official scores (forward, reverse)
+  int comp[2] = {0, 0};  // computed scores (may run one ahead: speculative row)
+  int fmax = uni(lds.bi_A[(0) * kp.ring + (0)]), rmax = uni(lds.bi_A[(1) * kp.ring + (0)]);
+  bp.score = INT_MAX;
+  unsigned ext_iters = 0;
+  unsigned long long cells = 0, multi_cells = 0, deep_cells = 0;
+  int pass = 0;
+  const long long max_steps = ((long long)pn.o1 + pn.o2 + 2LL * (pn.e1 + pn.e2) + pn.x) * ((long long)plen + tlen + 4) + 1024;
+  long long steps = 0;
+  int rc = BP_OK;
+  // Score-only bound B (kp.max_penalty, INT_MAX = none).  Every breakpoint the search can still find pairs a score >= sc[0] of
+  // one side with one >= sc[1] - (scope - 1) of the other, minus at most one gap open -- the inequality phase 2's termination
+  // tests rely on.  So the search starts as if a breakpoint of score B + 1 were known: phase 2 then accepts only breakpoints
+  // <= B and ends as soon as none can remain, and phase 1 (which finds none) ends once both sides stand at pctx.score_cap.
+  // A breakpoint <= B, once found, lets the search run to its normal end (exact).  (Bound values are read back from LDS
+  // where they are needed: nothing extra stays live in the step loop.)
+  if (kp.max_penalty != INT_MAX) bp.score = kp.max_penalty + 1;
+  const int gap_opening = P2 ? max(pn.o1, pn.o2) : pn.o1;
+  bool last_fwd = false;
+  // A sub-problem handed down by a parent's breakpoint has a known optimal score: its share of the
+  // parent's optimal alignment (the forward / reverse score at the breakpoint) minus the gap open of
+  // the breakpoint's component -- in the child that boundary gap is pre-paid at its begin or end, while
+  // both of the parent's searches had paid for entering it.  A cheaper way through the child would make
+  // the parent's alignment cheaper too.  WFA2 keeps searching until no better overlap is possible but
+  // only ever replaces the breakpoint by a strictly better one, so once that score is reached the rest
+  // of the search cannot change the result and is skipped.
+  const bool known_optimum = known_score != INT_MAX;
+  bool dirty[2] = {false, false};  // per direction: some row was trimmed, later steps mask element by element
+  // Multi-step passes (compute_rows_multi) while the searches are far apart; step by step -- every I/D
+  // row kept, as the overlap search needs them -- from a safe margin before they can meet.
+  // attempt 0: the margins of multi_phase; 1 (the furthest points met inside a far-apart pass): once more with four times the
+  // margin; 2 (again): step by step throughout
+  const bool force_single = (attempt & 0xff) >= AWV_RESTART_ATTEMPTS - 1;
+  // (bits 8, 9 = log2 of the margin's multiplier, bit 10 = the margin factor of long reads although the rows are 16-bit)
+  const int deep_arg = kp.deep_passes | ((attempt & 0xff) == 1 && !force_single ? 0x200 : 0) | ((attempt & 0x100) ? 0x400 : 0);
+  const int multi_T = (!force_single && plen + tlen > AWV_MIN_PASS_LEN) ? kp.multi_T : 0;  // 0: step by step throughout
+  bool deep_on = multi_T == 0;     // every step stores its I/D rows
+  int deep_since[2] = {deep_on ? 0 : INT_MAX, deep_on ? 0 : INT_MAX};  // first score from which all I/D rows are in HBM
+  // the overlap search of (d0, s0) against d1 reads the I/D rows of s0 and of scores s1 - scope + 1 .. s1
+  auto deep_ok = [&](int d0, int s0, int d1, int s1) {
+    const int lo_need = max(s1 - (pn.scope - 1), 1);
+    return (s0 == 0 || deep_since[d0] <= s0) && (s1 == 0 || deep_since[d1] <= lo_need);
+  };
+  int phase = 1;
+  // One loop for both phases (A.6).  Each iteration first makes sure the next forward and the next
+  // reverse wavefront exist (one fused pass, one barrier), then runs WFA2's bookkeeping for it.
+  for (;;) {
+    if (phase == 1 && fmax + rmax >= max_antidiagonal) phase = 2;
+    {
+      Acc* a = sh.acc[pass % 3];
+      int plo[2] = {1, 1}, phi[2] = {0, 0};
+      bool need[2];
+      const unsigned long long tp0 = PROF_NOW();
+      if (!deep_on && (dirty[0] || dirty[1])) {
+        deep_on = true;
+        deep_since[0] = comp[0] + 1;
+        deep_since[1] = comp[1] + 1;
+      }
+      if (!deep_on && phase == 1 && comp[0] == sc[0] && comp[1] == sc[1] && sc[0] == sc[1]) {
+        // ---- the far-apart phase: all multi-step passes of this search in one call (multi_phase), from score 0 on (sources
+        // of negative scores are empty rows to plan_multi)
+        // (chained sweeps only where the scores allow them: 2-piece with x = TMAX and o1 + e1 = 2 TMAX, the default set)
+        if (P2) multi_phase_reuse<P2, OffT, 2, 1, P2>(sh_addr, dyn_addr, sc[0], fmax, rmax, multi_T, pass, deep_arg);
+        else if (pn.e1 == 1) multi_phase_reuse<P2, OffT, 1, 1, false>(sh_addr, dyn_addr, sc[0], fmax, rmax, multi_T, pass, deep_arg);
+        else multi_phase_reuse<P2, OffT, 2, 1, false>(sh_addr, dyn_addr, sc[0], fmax, rmax, multi_T, pass, deep_arg);
+        PROF_ADD(STAT_T_BI_COMPUTE, tp0);
+        const int why = uni(sh.pres.why);
+        if (why == MP_ERROR) { rc = uni(sh.error); break; }
+        if (why == MP_MET) { rc = BP_RESTART; break; }
+        // the far-apart passes and (from the margin on) the passes that store every I/D row, in one call: both directions are
+        // COMPUTED through pres.sc; the official scores may stand below it when phase 1 ended inside the last pass (the rows
+        // beyond them are the ones phase 2 asks for next)
+        steps += (long long)(uni(sh.pres.sc) - sc[0]);
+        comp[0] = comp[1] = uni(sh.pres.sc);
+        sc[0] = uni(sh.pres.sf);
+        sc[1] = uni(sh.pres.sr);
+        last_fwd = uni(sh.pres.last_fwd) != 0;
+        fmax = uni(sh.pres.fmax);
+        rmax = uni(sh.pres.rmax);
+        pass += uni(sh.pres.npass);
+        {
+          const unsigned long long c = ((unsigned long long)(unsigned)uni((int)(sh.pres.cells >> 32)) << 32) | (unsigned)uni((int)sh.pres.cells);
+          const unsigned long long dc = ((unsigned long long)(unsigned)uni((int)(sh.pres.deep_cells >> 32)) << 32) | (unsigned)uni((int)sh.pres.deep_cells);
+          cells += c;
+          multi_cells += c;
+          deep_cells += dc;
+        }
+        deep_on = true;  // from here on every row of every component goes to HBM
+        deep_since[0] = deep_since[1] = uni(sh.pres.deep_from) + 1;
+        __syncthreads();  // (sh.pres may be rewritten by the next search only after everyone has read it)
+        continue;
+      } else {
+#pragma unroll
+      for (int dir = 0; dir < 2; ++dir) {  // unrolled: every per-direction array keeps constant indices
+        need[dir] = comp[dir] == sc[dir];
+        if (need[dir]) {
+          StepPlan pl;
+          plan_step<P2, false, OffT>(kp, lds, dir, sc[dir] + 1, pl);
+          cells += compute_row<P2, false, OffT>(kp, sh, lds, cx, ring_rs, dir, sc[dir] + 1, pl, dirty[dir], a[dir], ext_iters);
+          plo[dir] = pl.lo;
+          phi[dir] = pl.hi;
+        }
+      }
+#ifdef AWV_DIAG
+      // diagnostic build: step-by-step window-steps by zone, reported through awv_stats.prof[9..13]
+      // ([9] sub-problems without passes, [10] before the passes can start, [11] margin zone of phase 1, [12] phase 2, [13] trimmed rows)
+      if (tid == 0) {
+        const int zone = (dirty[0] || dirty[1]) ? 4 : multi_T == 0 ? 0 : phase == 2 ? 3 : (sc[0] + 1 - (pn.scope - 1) >= 1) ? 2 : 1;
+        unsigned nw = 0;
+        if (need[0] && plo[0] <= phi[0]) nw += (unsigned)((phi[0] - plo[0] + 4) / 248 + 1);
+        if (need[1] && plo[1] <= phi[1]) nw += (unsigned)((phi[1] - plo[1] + 4) / 248 + 1);
+        lstats[STAT_T_CR_LOAD + zone] += nw;
+      }
+#endif
+      if (need[0] || need[1]) {
+        PROF_ADD(STAT_T_BI_COMPUTE, tp0);
+        PROF_INC(STAT_N_PASSES);
+        const unsigned long long tp1 = PROF_NOW();
+        __syncthreads();
+        PROF_ADD(STAT_T_BI_BARRIER, tp1);
+        const unsigned long long tp2 = PROF_NOW();
+        if (uni(sh.error)) { rc = uni(sh.error); break; }
+        const bool trim0 = need[0] && uni(a[0].oob) != 0, trim1 = need[1] && uni(a[1].oob) != 0;
+        dirty[0] = dirty[0] || trim0;
+        dirty[1] = dirty[1] || trim1;
+        if (trim0 || trim1) {
+          if (trim0) trim_pass_fn<P2, false, OffT>(sh_addr, 0, sc[0] + 1, plo[0], phi[0], pass % 3);
+          if (trim1) trim_pass_fn<P2, false, OffT>(sh_addr, 1, sc[1] + 1, plo[1], phi[1], pass % 3);
+          __syncthreads();
+        }
+        if (need[0]) { finalize_row<false, OffT>(kp, lds, cx, 0, sc[0] + 1, a[0], trim0); comp[0] = sc[0] + 1; }
+        if (need[1]) { finalize_row<false, OffT>(kp, lds, cx, 1, sc[1] + 1, a[1], trim1); comp[1] = sc[1] + 1; }
+        if (tid == 0) { acc_reset(sh.acc[(pass + 2) % 3][0]); acc_reset(sh.acc[(pass + 2) % 3][1]); }
+        ++pass;
+        PROF_ADD(STAT_T_BI_FINALIZE, tp2);
+      }
+      }
+    }
+    if (phase == 1) {
+      // phase 1: until the furthest points can collide
+      ++sc[0];
+      fmax = max(fmax, uni(lds.bi_A[0 * kp.ring + (sc[0] & rmask)]));
+      last_fwd = true;
+      if (fmax + rmax >= max_antidiagonal) { phase = 2; continue; }
+      ++sc[1];
+      rmax = max(rmax, uni(lds.bi_A[1 * kp.ring + (sc[1] & rmask)]));
+      last_fwd = false;
+      if (sc[1] >= uni(sh.pctx.score_cap)) { rc = BP_ABOVE_BOUND; break; }  // (sc[0] == sc[1]: every breakpoint left is above the bound)
+    } else {
+      // phase 2: until no better overlap is possible
+      if (last_fwd) {
+        const int min_sr = (sc[1] > pn.scope - 1) ? sc[1] - (pn.scope - 1) : 0;
+        if (sc[0] + min_sr - gap_opening >= bp.score) break;
+        if (!deep_ok(0, sc[0], 1, sc[1])) { rc = BP_RESTART; break; }
+        const unsigned long long to0 = PROF_NOW();
+        bialign_overlap<P2, OffT>(kp, sh, lds, cx, ring_mem, ring_rs, 0, sc[0], sc[1], true, bp, lstats);
+        PROF_ADD(STAT_T_OVERLAP, to0);
+        if (known_optimum && bp.score == known_score) break;
+        ++sc[1];
+      }
+      const int min_sf = (sc[0] > pn.scope - 1) ? sc[0] - (pn.scope - 1) : 0;
+      if (min_sf + sc[1] - gap_opening >= bp.score) break;
+      if (!deep_ok(1, sc[1], 0, sc[0])) { rc = BP_RESTART; break; }
+      const unsigned long long to1 = PROF_NOW();
+      bialign_overlap<P2, OffT>(kp, sh, lds, cx, ring_mem, ring_rs, 1, sc[1], sc[0], false, bp, lstats);
+      PROF_ADD(STAT_T_OVERLAP, to1);
+      if (known_optimum && bp.score == known_score) break;
+      ++sc[0];
+      last_fwd = true;
+    }
+    if (++steps > max_steps) { rc = ST_MAX_STEPS; break; }
+  }
+  if (tid == 0) {
+    lstats[STAT_CELLS] += cells;
+    lstats[STAT_MULTI_CELLS] += multi_cells;
+    lstats[STAT_DEEP_CELLS] += deep_cells;
+    lstats[STAT_BREAKPOINTS] += 1;
+  }
+  atomicAdd(&lstats[STAT_EXTEND], (unsigned long long)ext_iters);
+  if (tid == 0) lstats[STAT_EXTEND] += sh.ext_multi;
+  if (rc == BP_OK && bp.score > uni(sh.pctx.max_penalty)) rc = BP_ABOVE_BOUND;  // (the bound's phase 2 found no breakpoint <= B)
+  __syncthreads();  // LDS metadata is rewritten by the next sub-problem
+  if (rc == BP_OK && bp.score == INT_MAX) rc = ST_INTERNAL;
+  return rc;
+}
+
 // The breakpoint search as a function of its own (never inlined): the DFS loop, the base case and the CIGAR
 // emission keep their state out of its register file, and edits on either side stop perturbing the
 // other's allocation (the step-by-step loop inside is full: an inlined change elsewhere in the kernel
@@ -3730,6 +4429,74 @@ __device__ __attribute__((noinline)) int find_breakpoint_fn(unsigned sh_addr, un
   return rc;
 }
 
+
+// find_breakpoint_fn for a kernel that keeps row archives: the same function around find_breakpoint_reuse.
+template <bool P2, typename OffT>
+__device__ __attribute__((noinline)) int find_breakpoint_fn_reuse(unsigned sh_addr, unsigned dyn_addr, unsigned lstats_addr, int cb_v, int ce_v,
+                                                            int score_remaining_v, int known_v, int attempt_v) {
+  Shared& sh = *(Shared*)__builtin_assume_aligned((Shared*)(__attribute__((address_space(3))) Shared*)(uintptr_t)uni((int)sh_addr), 8);
+  unsigned char* dyn_smem = (unsigned char*)__builtin_assume_aligned((unsigned char*)(__attribute__((address_space(3))) unsigned char*)(uintptr_t)uni((int)dyn_addr), 16);
+  unsigned long long* lstats = (unsigned long long*)__builtin_assume_aligned((unsigned long long*)(__attribute__((address_space(3))) unsigned long long*)(uintptr_t)uni((int)lstats_addr), 8);
+  const int cb = uni(cb_v), ce = uni(ce_v), score_remaining = uni(score_remaining_v), known = uni(known_v);
+  const int attempt = uni(attempt_v);  // bits 0..7: the attempt, bit 8: a 16-bit search inside a launch with 32-bit rows
+  const PassCtx& pc = sh.pctx;
+  auto uni64 = [](unsigned long long v) { return ((unsigned long long)(unsigned)uni((int)(v >> 32)) << 32) | (unsigned)uni((int)v); };
+  KParams kp{};
+  kp.ring = uni(pc.ring);
+  kp.wcap = uni(pc.wcap);
+  kp.pen.x = uni(pc.x);
+  kp.pen.o1 = uni(pc.o1);
+  kp.pen.e1 = uni(pc.e1);
+  kp.pen.o2 = uni(pc.o2);
+  kp.pen.e2 = uni(pc.e2);
+  kp.pen.two_piece = P2 ? 1 : 0;
+  kp.pen.scope = max(kp.pen.x, max(kp.pen.o1 + kp.pen.e1, P2 ? kp.pen.o2 + kp.pen.e2 : 0)) + 1;
+  kp.lds_meta_bytes = uni(pc.lds_meta_bytes);
+  kp.lds_seq_bytes = uni(pc.lds_seq_bytes);
+  kp.chain_max = uni(pc.chain_max);
+  kp.multi_T = uni(pc.multi_T);
+  kp.deep_passes = uni(pc.deep_passes);
+  // The bound is the pair's: only its top-level search carries it.  The top-level task is the one that arrives without a score
+  // handed down (score_remaining == INT_MAX: a child's is its share of the parent's breakpoint score).  A sub-problem's penalty
+  // never exceeds the pair's, and a bound left on it would only change its pass planning.
+  kp.max_penalty = score_remaining == INT_MAX ? uni(pc.max_penalty) : INT_MAX;
+  kp.ring_slot_stride = (size_t)uni64(pc.ring_bytes);
+  SubCtx cx;
+  cx.plen = uni(pc.plen);
+  cx.tlen = uni(pc.tlen);
+  cx.kmin[0] = cx.kmin[1] = 0;
+  cx.wcols = 0;
+  cx.seq_mode = uni(pc.seq_mode);
+  cx.p_w0 = uni(pc.p_w0);
+  cx.t_w0 = uni(pc.t_w0);
+  cx.p_bit = uni(pc.p_bit);
+  cx.t_bit = uni(pc.t_bit);
+  cx.P[0] = (gseq_t)(uintptr_t)uni64(pc.P[0]);
+  cx.P[1] = (gseq_t)(uintptr_t)uni64(pc.P[1]);
+  cx.T[0] = (gseq_t)(uintptr_t)uni64(pc.T[0]);
+  cx.T[1] = (gseq_t)(uintptr_t)uni64(pc.T[1]);
+  cx.Pw = (gwords_t)(uintptr_t)uni64(pc.Pw);
+  cx.Tw = (gwords_t)(uintptr_t)uni64(pc.Tw);
+  cx.pb_abs = uni(pc.pb_abs);
+  cx.tb_abs = uni(pc.tb_abs);
+  Lds<OffT> lds;
+  typedef typename MetaTraits<OffT>::Stored MetaStored;
+  lds.ring_meta = reinterpret_cast<MetaStored*>(dyn_smem);
+  lds.bi_A = reinterpret_cast<int*>(lds.ring_meta + 2 * NCOMP * kp.ring);
+  lds.bi_oob = lds.bi_A + 2 * kp.ring;
+  lds.firstk = lds.bi_oob + 2 * kp.ring;
+  lds.seq = reinterpret_cast<uint32_t*>(dyn_smem + kp.lds_meta_bytes);
+  lds.meta_log = nullptr;
+  void* ring_mem = (void*)(__attribute__((address_space(1))) char*)(uintptr_t)uni64(pc.ring_mem);  // (a global pointer, not a generic one: the row probes stay global_load)
+  const rsrc_t ring_rs = make_rsrc(ring_mem, kp.ring_slot_stride);
+  __syncthreads();  // everyone has read pctx before the search rewrites parts of it
+  Breakpoint bp;
+  const int rc = find_breakpoint_reuse<P2, OffT>(kp, sh, lds, cx, ring_mem, ring_rs, cb, ce, score_remaining, known, attempt, bp, lstats);
+  if (threadIdx.x == 0) sh.bp_out = bp;
+  __syncthreads();
+  return rc;
+}
+
 // ---------------------------------------------------------------------------------------------
 // The kernel: persistent workgroups, one pair at a time, DFS over the BiWFA recursion
 // ---------------------------------------------------------------------------------------------
@@ -3771,6 +4538,12 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
   // the pair loop it had, line for line.
   constexpr bool TWINS = TWIN_BUILD && !RANGES && sizeof(OffT) == 2;
   if constexpr (TWINS) {
+  // Row reuse: this workgroup's archive of its running top-level search's rows; null when the launch keeps none
+  // (AWV_F_NO_ROW_REUSE, a bound, a score-only call, no room): every search then goes through find_breakpoint_fn as ever.
+  const unsigned long long rr_mem = kp.stats[STAT_N_DEV], rr_stride = kp.stats[STAT_N_DEV + 1], rr_pt = kp.stats[STAT_N_DEV + 2];
+  const int rr_passes = uni((int)(unsigned)rr_pt), rr_T = uni((int)(rr_pt >> 32)), rr_nid = uni((int)kp.stats[STAT_N_DEV + 3]);
+  int* const rr_hdr = rr_mem != 0 && rr_passes > 0 && pn.scope * NCOMP >= RRS_WORDS ? (int*)((char*)(uintptr_t)rr_mem + (size_t)blockIdx.x * (size_t)rr_stride) : nullptr;
+  if (rr_hdr != nullptr && tid < awvrr::H_WORDS) rr_hdr[tid] = 0;
   for (;;) {
     if (tid == 0) {
       sh.cur_pair = (long long)atomicAdd(kp.work_counter, 1ULL);
@@ -3833,6 +4606,9 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
       { const bool x = top; top = top_o; top_o = x; }
     };
     if (TWINS && run_mode == TM_B) face(TM_B);
+    // the top-level search's breakpoint and frame once it is known: the two tasks it hands down are the ones that may take
+    // rows from the archive.  Void (rr_bv < 0) at the start of every run of the DFS: no archive outlives its item.
+    int rr_bv = -1, rr_bh = -1, rr_comp = 0, rr_mode = TM_A;
     int sp = 0;
     if constexpr (RANGES) {
       // the top-level task is the rectangle the launch names (plenT / tlenT stay the full lengths: the reversed copies are
@@ -3937,6 +4713,28 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
             else
               rc = uni(find_breakpoint_fn<P2, OffT>((unsigned)(uintptr_t)&sh, (unsigned)(uintptr_t)lds.ring_meta, (unsigned)(uintptr_t)lstats,
                                                     t.cb, t.ce, t.score_remaining, t.known, attempt));
+          } else if (rr_hdr != nullptr) {
+            // the top-level search keeps its rows; a task it handed down, still in its frame (a shared unit's tasks are in A's),
+            // takes the forward rows when it is the left half and the reverse rows when it is the right half
+            int part = 0;
+            if (t.score_remaining == INT_MAX) part = RR_RECORD;
+            else if (rr_bv >= 0 && (mode == rr_mode || (rr_mode == TM_SHARED && mode == TM_A))) {
+              if (t.pb == 0 && t.tb == 0 && t.pe == rr_bv && t.te == rr_bh && t.cb == C_M && t.ce == rr_comp) part = RR_FWD;
+              else if (t.pb == rr_bv && t.tb == rr_bh && t.pe == plenT && t.te == tlenT && t.cb == rr_comp && t.ce == C_M) part = RR_REV;
+            }
+            if (tid == 0) {  // the search's reuse state (RRS_*: Lds::firstk, untouched until phase 2); a recording search voids the archive
+              const unsigned long long ra = (unsigned long long)(uintptr_t)rr_hdr;
+              lds.firstk[RRS_ARCH_LO] = (int)(unsigned)ra;
+              lds.firstk[RRS_ARCH_HI] = (int)(unsigned)(ra >> 32);
+              lds.firstk[RRS_PASSES] = rr_passes;
+              lds.firstk[RRS_T] = rr_T;
+              lds.firstk[RRS_NID] = rr_nid;
+              lds.firstk[RRS_PART] = part;
+              if (part == RR_RECORD) rr_hdr[awvrr::H_NPASS] = 0;
+            }
+            __syncthreads();
+            rc = uni(find_breakpoint_fn_reuse<P2, OffT>((unsigned)(uintptr_t)&sh, (unsigned)(uintptr_t)lds.ring_meta, (unsigned)(uintptr_t)lstats,
+                                                        t.cb, t.ce, t.score_remaining, t.known, attempt));
           } else {
             rc = uni(find_breakpoint_fn<P2, OffT>((unsigned)(uintptr_t)&sh, (unsigned)(uintptr_t)lds.ring_meta, (unsigned)(uintptr_t)lstats,
                                                   t.cb, t.ce, t.score_remaining, t.known, attempt));
@@ -4029,6 +4827,7 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
         break;
       }
       const int bh = bp.off_f, bv = bp.off_f - bp.kf;
+      if (rr_hdr != nullptr && t.score_remaining == INT_MAX) { rr_bv = bv; rr_bh = bh; rr_comp = bp.comp; rr_mode = mode; }
       if (mode != TM_SHARED) {
         if (bh < 0 || bh > tlen || bv < 0 || bv > plen || sp + 2 > STACK_CAP) { status = ST_INTERNAL; break; }
         if (tid == 0) {
@@ -4128,6 +4927,12 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
       atomicAdd(&kp.stats[STAT_TWIN_SOLO], (unsigned long long)tw_solo);
       atomicAdd(&kp.stats[STAT_TWIN_NONMIRROR], (unsigned long long)tw_nonmirror);
     }
+  }
+  if (rr_hdr != nullptr && tid == 0) {  // what this workgroup's searches took from its archive (rr_before_pass counts there)
+    const unsigned long long rcells = __hip_atomic_load((unsigned long long*)(rr_hdr + awvrr::H_RCELLS), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int rsearch = __hip_atomic_load(rr_hdr + awvrr::H_RSEARCH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (rcells) atomicAdd(&kp.stats[STAT_REUSE_CELLS], rcells);
+    if (rsearch) atomicAdd(&kp.stats[STAT_REUSE_SEARCHES], (unsigned long long)rsearch);
   }
   } else {
   for (;;) {

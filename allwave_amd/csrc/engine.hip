@@ -58,6 +58,7 @@
 
 #include "batch_plan.hpp"
 #include "twin_plan.hpp"
+#include "row_reuse.hpp"
 
 namespace {
 // the device constants batch_plan.hpp's rules are written over (biwfa_device.hpp)
@@ -156,6 +157,7 @@ struct awv_engine {
   // scratch arenas (per persistent workgroup)
   DevBuf<uint8_t> ring_mem, hist_mem;
   DevBuf<uint32_t> ev_mem;
+  DevBuf<uint8_t> reuse_mem;  // row archives of the top-level searches (row_reuse.hpp); reserved after every other arena
   // per-launch buffers
   DevBuf<int32_t> d_pair_q, d_pair_t, d_pair_rc;
   DevBuf<int32_t> d_pair_bound;  // score-only launches with a bound per pair
@@ -174,6 +176,7 @@ struct awv_engine {
     std::vector<uint64_t> hoff;
     std::vector<awvr::Span> hspan;
     std::vector<awv_result> tres;
+    unsigned long long hreuse[4] = {0, 0, 0, 0};
   } stage;
   awv_stats stats{};
   awp::PlanState* plan = nullptr;  // planner.hip: sketches of `seqs` and planning scratch (released with a new set)
@@ -389,6 +392,7 @@ struct AlignCall {
   double kernel_ms = 0, h2d_ms = 0, d2h_ms = 0;
   unsigned long long stat_tot[awv::STAT_N_DEV] = {0};
   uint64_t launches = 0;
+  awvrr::Layout reuse{0, 0, 0, 0};  // the running group's row archives (passes == 0: none)
   SinkRunner runner;
   bool want_cigar() const { return rq.sink && !rq.score_only && !(e->cfg.flags & AWV_F_KEEP_ON_DEVICE); }
   void lap(const char* what) const {  // diagnostic: host-side stage times on stderr
@@ -457,7 +461,7 @@ int reserve_batch_buffers(AlignCall& c) {
   if (int rc = e->d_cigar_off.reserve(n)) return rc;
   if (int rc = e->d_results.reserve(n)) return rc;
   if (int rc = e->d_cigar.reserve((size_t)c.arena + 64)) return rc;
-  if (int rc = e->d_counters.reserve(1 + awv::STAT_N_DEV)) return rc;
+  if (int rc = e->d_counters.reserve(1 + awv::STAT_N_DEV + awv::RR_DESC_WORDS)) return rc;  // (behind the counters: the row archives' descriptor)
   static_assert(sizeof(awv_result) == sizeof(awv::DevResult), "result layout");
   c.hres.assign(n, awv_result{});
   return AWV_OK;
@@ -539,6 +543,37 @@ int ensure_arenas(AlignCall& c, const awvb::RowPlan& rp, int wc, int nslots) {
   return AWV_OK;
 }
 
+// The row archives of an attempt: only the one-wave kernels with 16-bit rows keep them, for whole pairs aligned
+// in full, and only in what the scratch budget leaves after the arenas above.  No archive is no error: the kernel then
+// computes every row.
+void plan_row_archives(AlignCall& c, const std::vector<awvb::Entry>& ge, const awvb::RowPlan& rp, int wc, int nslots) {
+  awv_engine* e = c.e;
+  c.reuse = awvrr::Layout{0, 0, 0, 0};
+  const AlignRequest& rq = c.rq;
+  if (rp.waves != 1 || rp.width != 0 || (e->cfg.flags & AWV_F_NO_ROW_REUSE) || rq.spans || rq.score_only || rq.pair_bound ||
+      rq.max_penalty != INT_MAX || c.pp.multi_T <= 0)
+    return;
+  int maxsum = 0;
+  for (const awvb::Entry& p : ge) maxsum = std::max(maxsum, p.ql + p.tl);
+  const int chain = std::min(std::max(c.pp.chain_max, 1), awv::CHAIN_MAX);
+  const int T = chain > 1 ? awv::TMAX * chain : c.pp.multi_T;
+  const int nid = 2 * c.pp.e1 + (c.pp.two_piece ? 2 * c.pp.e2 : 0);
+  const size_t used = rp.per_slot(wc) * (size_t)nslots;
+  const int passes = awvrr::plan_passes(maxsum, T, nid, nslots, rp.budget > used ? rp.budget - used : 0);
+  if (passes == 0) {
+    c.lap("row archives: none (no room, or pairs too short)");
+    return;
+  }
+  const awvrr::Layout l = awvrr::make_layout(passes, T, nid);
+  if (e->reuse_mem.reserve(l.bytes() * (size_t)nslots) != AWV_OK) {  // (awv_stats.prof[13] then stays 0 for the launch)
+    (void)hipGetLastError();
+    c.lap("row archives: none (allocation failed)");
+    return;
+  }
+  c.reuse = l;
+  if (c.timing) fprintf(stderr, "[awv] row archives: %d passes of %d scores, %zu MiB for %d workgroups\n", passes, T, (l.bytes() * (size_t)nslots) >> 20, nslots);
+}
+
 // ---- one attempt of a group: upload, launch, read back ----
 // Twin units: an entry (q, t) and its swapped entry (t, q) of this launch share their breakpoint searches.
 // Entries are in descending cost order and a twin costs what its partner costs, so units ordered by their summed cost are the
@@ -599,7 +634,14 @@ int upload_group(AlignCall& c, const std::vector<awvb::Entry>& ge, const awvb::R
   nunits = (int64_t)m;
   if (rp.twin_here)
     if (int rc = upload_twin_units(c, ge, nunits)) return rc;
-  AWV_TRY(hipMemsetAsync(e->d_counters.p, 0, (1 + awv::STAT_N_DEV) * sizeof(unsigned long long), e->stream));
+  AWV_TRY(hipMemsetAsync(e->d_counters.p, 0, (1 + awv::STAT_N_DEV + awv::RR_DESC_WORDS) * sizeof(unsigned long long), e->stream));
+  if (c.reuse.passes > 0) {  // the launch's row archives (biwfa_device.hpp, RR_DESC_WORDS)
+    st.hreuse[0] = (unsigned long long)(uintptr_t)e->reuse_mem.p;
+    st.hreuse[1] = (unsigned long long)c.reuse.bytes();
+    st.hreuse[2] = (unsigned long long)(unsigned)c.reuse.passes | ((unsigned long long)(unsigned)c.reuse.T << 32);
+    st.hreuse[3] = (unsigned long long)c.reuse.nid;
+    AWV_TRY(hipMemcpyAsync(e->d_counters.p + 1 + awv::STAT_N_DEV, st.hreuse, sizeof(st.hreuse), hipMemcpyHostToDevice, e->stream));
+  }
   return timer_stop(c, c.h2d_ms);
 }
 
@@ -752,6 +794,7 @@ int run_group(AlignCall& c, std::vector<awvb::Entry>& ge, const awvb::RowPlan& r
   for (int wc = rp.wcap; !ge.empty(); wc = rp.next_wc(wc)) {
     const int nslots = rp.slots(wc, (int64_t)ge.size());
     if (int rc = ensure_arenas(c, rp, wc, nslots)) return rc;
+    plan_row_archives(c, ge, rp, wc, nslots);
     c.lap("arenas reserved");
     if (c.timing) fprintf(stderr, "[awv] ring arena %p (%zu MiB), hist %p, cigar %p\n", (void*)c.e->ring_mem.p, c.e->ring_mem.bytes() >> 20, (void*)c.e->hist_mem.p, (void*)c.e->d_cigar.p);
     int64_t nunits = 0;
@@ -874,7 +917,7 @@ void publish_stats(AlignCall& c) {
   e->stats.overlap_scans = stat_tot[STAT_OVERLAP];
   e->stats.aligned_bp = stat_tot[STAT_ALIGNED_BP];
   e->stats.pairs_completed = stat_tot[STAT_PAIRS];
-  e->stats.scratch_bytes = e->ring_mem.bytes() + e->hist_mem.bytes() + e->ev_mem.bytes();
+  e->stats.scratch_bytes = e->ring_mem.bytes() + e->hist_mem.bytes() + e->ev_mem.bytes() + e->reuse_mem.bytes();
   for (int i = 0; i < 14; ++i) e->stats.prof[i] = stat_tot[STAT_T_TOTAL + i];
   e->stats.restarts = stat_tot[STAT_RESTARTS];
   e->stats.multi_cell_steps = stat_tot[STAT_MULTI_CELLS];
@@ -887,6 +930,12 @@ void publish_stats(AlignCall& c) {
   e->stats.clock_tick_khz = (uint64_t)e->wall_clock_khz;
   e->stats.deep_cell_steps = stat_tot[STAT_DEEP_CELLS];
   for (int i = 0; i < 4; ++i) e->twin_stats[i] = stat_tot[STAT_TWIN_UNITS + i];
+#if !defined(AWV_PROF) && !defined(AWV_DIAG)
+  // row reuse: the product build stamps no cycles and counts no zones, so two of the slots that only the diagnostic builds fill carry
+  // the cell-steps taken from a row archive (they are counted in cell_steps and multi_cell_steps too) and the searches that took some
+  e->stats.prof[12] = stat_tot[STAT_REUSE_CELLS];
+  e->stats.prof[13] = stat_tot[STAT_REUSE_SEARCHES];
+#endif
 }
 
 int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const AlignRequest& rq) {
@@ -1013,6 +1062,7 @@ void awv_engine_destroy(awv_engine* e) {
   e->ring_mem.release();
   e->hist_mem.release();
   e->ev_mem.release();
+  e->reuse_mem.release();
   e->d_pair_q.release();
   e->d_pair_t.release();
   e->d_pair_rc.release();

@@ -112,6 +112,9 @@ typedef struct {
 #define AWV_F_TWIN_TOP_ONLY 4096 /* tests and A/B measurements only: such units share their top-level search only (default: every search whose sub-problem is still a mirror image) */
 #define AWV_F_NO_TWIN_BASE 8192 /* tests and A/B measurements only: a base case under a shared search is run once per orientation (default: its wavefronts
                                    run once and are backtraced for both orientations) */
+#define AWV_F_NO_ROW_REUSE 16384 /* tests and A/B measurements only: every breakpoint search computes all of its rows (default: in the one-wave kernels with
+                                    16-bit rows the two searches below a pair's top-level search take the rows they share with it from an archive it keeps;
+                                    awv_stats.prof[12] / prof[13] then count the cell-steps taken and the searches that took some) */
 
 /* penalties as allwave passes them to lib_wfa2 (src/alignment.rs:263-289) */
 typedef struct {
