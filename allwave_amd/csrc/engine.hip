@@ -13,6 +13,7 @@
 #include "clip_device.hpp"     // (the per-batch clip of awv_align_pairs_clipped, clip.hip)
 #include "split_device.hpp"    // (the per-batch split of awv_align_pairs_split, split.hip)
 #include "normalize_device.hpp"  // (the per-batch normalization under awv_engine_set_normalize, normalize.hip)
+#include "encode_device.hpp"   // (the per-batch run-length text of awv_align_pairs_encoded, encode.hip)
 #include "kernels_awv.hpp"  // (the awv:: kernels themselves are instantiated in kernels_awv.hip -- here only the types)
 #define AWV_NS awv
 #define AWV_WG 64
@@ -184,6 +185,7 @@ struct awv_engine {
   awvc::State* clip = nullptr;     // clip.hip: buffers and stats of the clip launches
   awvs::State* split = nullptr;    // split.hip: likewise for the split launches
   awvn::State* normalize = nullptr;  // normalize.hip: likewise for the normalize launches
+  awve::State* encode = nullptr;   // encode.hip: likewise for the encode launches, and the text arena of the batch in hand
   int32_t norm_mode = AWV_NORM_OFF;  // awv_engine_set_normalize: read at the start of every aligning call
 };
 
@@ -348,6 +350,9 @@ struct AlignRequest {
   // (nullable; awv_align_pairs_split): likewise split into all segments of at least split->min_score, into the caller's slot
   // layout (already checked against the slot rule)
   const SplitOut* split = nullptr;
+  // (nullable; awv_align_pairs_encoded): every batch's op strings -- their clips under match_bonus > 0 -- become run-length text
+  // on the device, last of the record steps; the text is copied back and handed to the sink in the op bytes' place
+  awv_cigar_text* tout = nullptr;
 };
 
 // With several batches in a call, the sink of batch i (the caller's formatting and output) runs on a
@@ -387,6 +392,7 @@ struct AlignCall {
   // the batch in hand: pairs [first, first + n) of the call, `arena` bytes of CIGARs, results in caller order
   int64_t first = 0, n = 0;
   uint64_t arena = 0;
+  uint64_t text_bytes = 0;  // an encoded call: the batch's text arena
   std::vector<awvb::Entry> entries;
   std::vector<awv_result> hres;
   double kernel_ms = 0, h2d_ms = 0, d2h_ms = 0;
@@ -755,7 +761,7 @@ int launch_group(AlignCall& c, const awvb::RowPlan& rp, const awv::KParams& kp, 
   AWV_TRY(hipGetLastError());
   AWV_TRY(hipEventRecord(e->ev1, e->stream));
   // while the kernel runs: get the host CIGAR buffer's pages in place (0.2 s for config 2's 670 MB)
-  if (c.want_cigar() && e->h_cigar.size() < (size_t)c.arena + 64) e->h_cigar.resize((size_t)c.arena + 64);
+  if (c.want_cigar() && !c.rq.tout && e->h_cigar.size() < (size_t)c.arena + 64) e->h_cigar.resize((size_t)c.arena + 64);
   if (int rc = timer_wait(c, c.kernel_ms)) return rc;
   ++c.launches;
   c.lap("kernel done");
@@ -827,7 +833,8 @@ int run_groups(AlignCall& c, bool skewed) {
 }
 
 // ---- after the groups: record steps, copy-back, delivery ----
-// normalize first: the check, the clip and the split see the normalized bytes.  (The groups of a batch overwrite d_results: the
+// normalize first: the check, the clip and the split see the normalized bytes; the text last: it is of the normalized string, and
+// of the clip where there is one.  (The groups of a batch overwrite d_results: the
 // batch's records, as gathered in hres, go up once per step.)
 int run_record_steps(AlignCall& c) {
   awv_engine* e = c.e;
@@ -854,16 +861,23 @@ int run_record_steps(AlignCall& c) {
                                    rq.split->iout + first, rq.split->sout)) return rc;
     c.lap("batch split");
   }
+  if (rq.tout) {
+    if (int rc = awve::encode_batch(e, n, hres.data(), e->d_cigar.p, arena, rq.cout ? rq.cout + first : nullptr, rq.tout + first, &c.text_bytes)) return rc;
+    c.lap("batch encoded");
+  }
   return AWV_OK;
 }
 
 int copy_cigars_back(AlignCall& c) {
   awv_engine* e = c.e;
   if (c.want_cigar()) {
-    e->h_cigar.resize((size_t)c.arena + 64);
+    // an encoded call: the batch's text in the op bytes' place, in the same host buffer
+    const uint8_t* src = c.rq.tout ? awve::batch_text(e) : e->d_cigar.p;
+    const size_t bytes = (size_t)(c.rq.tout ? c.text_bytes : c.arena);
+    e->h_cigar.resize(bytes + 64);
     c.lap("host cigar buffer");
     AWV_TRY(hipEventRecord(e->ev0, e->stream));
-    AWV_TRY(hipMemcpyAsync(e->h_cigar.data(), e->d_cigar.p, (size_t)c.arena, hipMemcpyDeviceToHost, e->stream));
+    if (bytes) AWV_TRY(hipMemcpyAsync(e->h_cigar.data(), src, bytes, hipMemcpyDeviceToHost, e->stream));
     if (int rc = timer_stop(c, c.d2h_ms)) return rc;
   }
   c.lap("cigars on host");
@@ -1058,6 +1072,8 @@ void awv_engine_destroy(awv_engine* e) {
   e->split = nullptr;
   awvn::state_release(e->normalize);
   e->normalize = nullptr;
+  awve::state_release(e->encode);
+  e->encode = nullptr;
   e->seqs.release();
   e->ring_mem.release();
   e->hist_mem.release();
@@ -1229,6 +1245,55 @@ int awv_align_ranges_clipped(awv_engine* e, const awv_penalties* pen, const awv_
   rq.vout = vout;
   rq.cout = cout;
   rq.match_bonus = match_bonus;
+  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, rq);)
+}
+
+namespace {
+// what every encoding call refuses before anything is launched; match_bonus == 0: no clip, cout is not read
+int check_encode_args(const awv_cigar_text* tout, awv_clip_result*& cout, int32_t match_bonus) {
+  if (!tout) return fail(AWV_ERR_ARG, "align_encoded: null tout");
+  if (match_bonus == 0) {
+    cout = nullptr;
+    return AWV_OK;
+  }
+  return check_clip_args(cout, match_bonus);
+}
+}  // namespace
+
+int awv_align_pairs_encoded(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const int32_t* max_penalty,
+                            int32_t match_bonus, awv_result* out, awv_verify_result* vout, awv_clip_result* cout, awv_cigar_text* tout,
+                            awv_sink sink, void* user) {
+  if (!e) return fail(AWV_ERR_ARG, "null engine");
+  if (int rc = check_encode_args(tout, cout, match_bonus)) return rc;
+  if (int rc = require_sequences(e, npairs, "align_pairs")) return rc;
+  if (vout) awvf::stats_reset(e->verify);
+  if (cout) awvc::stats_reset(e->clip);
+  awve::stats_reset(e->encode);
+  AWV_GUARDED(
+    std::vector<int32_t> pb;
+    AlignRequest rq = full_request(pairs, npairs, out, sink, user);
+    rq.pair_bound = normalized_bounds(max_penalty, npairs, pb);
+    rq.vout = vout;
+    rq.cout = cout;
+    rq.match_bonus = match_bonus;
+    rq.tout = tout;
+    return align_core(e, e->seqs, pen, rq);
+  )
+}
+
+int awv_align_ranges_encoded(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const int32_t* max_penalty,
+                             int32_t match_bonus, awv_result* out, awv_verify_result* vout, awv_clip_result* cout, awv_cigar_text* tout,
+                             awv_sink sink, void* user) {
+  if (!e) return fail(AWV_ERR_ARG, "null engine");
+  if (int rc = check_encode_args(tout, cout, match_bonus)) return rc;
+  if (cout) awvc::stats_reset(e->clip);
+  awve::stats_reset(e->encode);
+  AlignRequest rq = full_request(nullptr, 0, out, sink, user);
+  rq.pair_bound = max_penalty;
+  rq.vout = vout;
+  rq.cout = cout;
+  rq.match_bonus = match_bonus;
+  rq.tout = tout;
   AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, rq);)
 }
 
@@ -1444,6 +1509,7 @@ awvf::State*& awv_internal_verify(awv_engine* e) { return e->verify; }
 awvc::State*& awv_internal_clip(awv_engine* e) { return e->clip; }
 awvs::State*& awv_internal_split(awv_engine* e) { return e->split; }
 awvn::State*& awv_internal_normalize(awv_engine* e) { return e->normalize; }
+awve::State*& awv_internal_encode(awv_engine* e) { return e->encode; }
 int32_t& awv_internal_normalize_mode(awv_engine* e) { return e->norm_mode; }
 uint64_t awv_internal_max_arena(const awv_engine* e) { return e->cfg.max_arena_bytes > 0 ? (uint64_t)e->cfg.max_arena_bytes : (uint64_t)8 << 30; }
 int awv_internal_fail(int code, const std::string& msg) { return fail(code, msg); }

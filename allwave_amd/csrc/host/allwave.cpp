@@ -165,8 +165,8 @@ std::vector<uint8_t> reverse_complement(const std::vector<uint8_t>& seq) {  // a
   return out;
 }
 
-void append_paf(std::string& out, const AlignmentResult& r, const uint8_t* ops, size_t nops,
-                const std::vector<Sequence>& sequences) {  // lib.rs:71-112
+// the line up to and including "cg:Z:"
+static void append_paf_head(std::string& out, const AlignmentResult& r, const std::vector<Sequence>& sequences) {  // lib.rs:71-112
   const Sequence& q = sequences[r.query_idx];
   const Sequence& t = sequences[r.target_idx];
   const size_t qa = r.query_end - r.query_start, ta = r.target_end - r.target_start;
@@ -188,7 +188,16 @@ void append_paf(std::string& out, const AlignmentResult& r, const uint8_t* ops, 
   snprintf(buf, sizeof(buf), "%.6f", identity);
   out += buf;
   out += "\tcg:Z:";
+}
+
+void append_paf(std::string& out, const AlignmentResult& r, const uint8_t* ops, size_t nops, const std::vector<Sequence>& sequences) {
+  append_paf_head(out, r, sequences);
   append_cigar(out, ops, nops);
+}
+
+void append_paf_text(std::string& out, const AlignmentResult& r, const uint8_t* text, size_t ntext, const std::vector<Sequence>& sequences) {
+  append_paf_head(out, r, sequences);
+  out.append((const char*)text, ntext);
 }
 
 std::string alignment_to_paf(const AlignmentResult& r, const std::vector<Sequence>& sequences) {
@@ -353,6 +362,7 @@ void align_ranges(const std::vector<Sequence>& sequences, const std::vector<Alig
 
 void RunOptions::apply(AllPairIterator& it) const {
   if (normalize != AWV_NORM_OFF) it.with_normalize(normalize);
+  if (device_cigar) it.with_device_cigar(true);
   if (max_penalty) it.with_max_penalty(*max_penalty);
   if (max_divergence) it.with_max_divergence(*max_divergence);
   if (clip_match_bonus != 0) it.with_clip(clip_match_bonus, clip_min_score);
@@ -528,7 +538,13 @@ AllPairIterator AllPairIterator::with_sparsification(SparsificationStrategy stra
   it.split_bonus_ = split_bonus_;
   it.split_min_score_ = split_min_score_;
   it.normalize_ = normalize_;
+  it.device_cigar_ = device_cigar_;
   return it;
+}
+AllPairIterator& AllPairIterator::with_device_cigar(bool on) {
+  if (on && split()) throw std::invalid_argument("with_device_cigar: not together with with_split");
+  device_cigar_ = on;
+  return *this;
 }
 AllPairIterator& AllPairIterator::with_normalize(int direction) {
   if (direction != AWV_NORM_OFF && direction != AWV_NORM_LEFT && direction != AWV_NORM_RIGHT)
@@ -549,6 +565,7 @@ AllPairIterator& AllPairIterator::with_split(int match_bonus, int64_t min_score)
   if (match_bonus < 1 || match_bonus > AWV_CLIP_MAX_BONUS) throw std::invalid_argument("with_split: match_bonus must be in [1, 32767]");
   if (min_score < 1) throw std::invalid_argument("with_split: min_score must be >= 1");
   if (clip()) throw std::invalid_argument("with_split: not together with with_clip");
+  if (device_cigar_) throw std::invalid_argument("with_split: not together with with_device_cigar");
   split_bonus_ = match_bonus;
   split_min_score_ = min_score;
   return *this;
@@ -724,6 +741,13 @@ void add(awv_norm_stats& acc, const awv_norm_stats& x) {
   acc.columns_moved += x.columns_moved;
   acc.columns += x.columns;
 }
+void add(awv_encode_stats& acc, const awv_encode_stats& x) {
+  acc.kernel_ms += x.kernel_ms;
+  acc.pairs += x.pairs;
+  acc.runs += x.runs;
+  acc.text_bytes += x.text_bytes;
+  acc.columns += x.columns;
+}
 void add(RunReport& acc, const RunReport& x) {
   acc.verify_failures.insert(acc.verify_failures.end(), x.verify_failures.begin(), x.verify_failures.end());
   add(acc.verify_stats, x.verify_stats);
@@ -731,11 +755,13 @@ void add(RunReport& acc, const RunReport& x) {
   add(acc.clip_stats, x.clip_stats);
   add(acc.split_stats, x.split_stats);
   add(acc.normalize_stats, x.normalize_stats);
+  add(acc.encode_stats, x.encode_stats);
 }
 
 // One batch's engine call, by name.  ranges (nullable): the batch is these n interval pairs, `pairs` is not read.  Alignment
 // calls only: verify (nullable), bounds (nullable: one penalty bound per entry, < 0: none), clip (nullable: the clips, under
-// clip_bonus), seg_first (nullable: the split under split_bonus / split_min_score, into index and seg).
+// clip_bonus), seg_first (nullable: the split under split_bonus / split_min_score, into index and seg), text (nullable: the
+// texts of the call's _encoded form -- not with a split).
 struct EngineRequest {
   bool score_only = false;
   int32_t max_penalty = -1;  // the score call's bound (< 0: none)
@@ -752,14 +778,18 @@ struct EngineRequest {
   const uint64_t* seg_first = nullptr;
   awv_split_index* index = nullptr;
   awv_clip_result* seg = nullptr;
+  awv_cigar_text* text = nullptr;
 };
 
-// The entry point a request names: the split, else the clip, else the bounded call, else the verified or the plain one, each
+// The entry point a request names: the encoded call (which takes the bounds, the check and the clip), else the split, else the clip, else the bounded call, else the verified or the plain one, each
 // on pairs or on ranges (they differ in which engine counters they reset); or awv_score_pairs / awv_score_ranges with the
 // results handed to the sink in one call (status and penalty, no arena).
 int engine_call(awv_engine* e, const EngineRequest& q, awv_sink sink, void* user) {
   const awv_penalties* pen = q.pen;
   const int64_t n = q.n;
+  if (q.text && !q.score_only)
+    return q.ranges ? awv_align_ranges_encoded(e, pen, q.ranges, n, q.bounds, q.clip ? q.clip_bonus : 0, nullptr, q.verify, q.clip, q.text, sink, user)
+                    : awv_align_pairs_encoded(e, pen, q.pairs, n, q.bounds, q.clip ? q.clip_bonus : 0, nullptr, q.verify, q.clip, q.text, sink, user);
   if (q.seg_first && !q.score_only)
     return q.ranges ? awv_align_ranges_split(e, pen, q.ranges, n, q.bounds, q.split_bonus, q.split_min_score, nullptr, q.verify, q.seg_first, q.index, q.seg, sink, user)
                     : awv_align_pairs_split(e, pen, q.pairs, n, q.bounds, q.split_bonus, q.split_min_score, nullptr, q.verify, q.seg_first, q.index, q.seg, sink, user);
@@ -798,10 +828,10 @@ struct AllPairIterator::RunState {
   size_t first = 0, count = 0;
   const std::pair<size_t, size_t>* plist = nullptr;  // pairs_.data() + first
   const BatchCb* batch_cb = nullptr;
-  EngineCall call{false, -1};
+  EngineCall call{false, -1, false};
   std::vector<std::vector<size_t>> batches;  // pair indices (relative to `first`) of each batch; one slot's single batch: empty, the whole range
   std::vector<uint8_t> mash_rev;             // mash orientation of the whole range, computed up front
-  bool verify = false, bounded = false, clipping = false, splitting = false;
+  bool verify = false, bounded = false, clipping = false, splitting = false, encoding = false;
   int normalizing = AWV_NORM_OFF;
   std::optional<double> div;  // the divergence bound of a bounded run
   awv_penalties pen{}, open{};
@@ -834,6 +864,7 @@ struct AllPairIterator::PreparedBatch {
   std::vector<uint8_t> by_div;
   std::vector<awv_verify_result> vr;
   std::vector<awv_clip_result> cr;
+  std::vector<awv_cigar_text> tx;
   // a splitting run: this call's segment storage, laid out by the engine's own arithmetic over the resident lengths
   std::vector<uint64_t> seg_first;
   std::vector<awv_split_index> six;
@@ -922,6 +953,11 @@ AllPairIterator::PreparedBatch AllPairIterator::prepare_batch(const RunState& rs
     d.seg = pb.sseg.data();
     d.splits = &totals.report.split_stats;
   }
+  if (rs.encoding) {
+    pb.tx.resize((size_t)std::max<int64_t>(m, 1));
+    q.text = pb.tx.data();
+    d.text = pb.tx.data();
+  }
   return pb;
 }
 
@@ -938,9 +974,10 @@ int AllPairIterator::batch_sink(void* user, int64_t first, int64_t cnt, const aw
   try {
     if (c->d->filters()) {
       const Delivered k = deliver(*c->d, first, cnt, res);
-      (*c->rs->batch_cb)(Batch{0, (int64_t)k.res.size(), k.res.data(), arena, k.rev.data(), k.idx.data(), k.clip.empty() ? nullptr : k.clip.data()});
+      (*c->rs->batch_cb)(Batch{0, (int64_t)k.res.size(), k.res.data(), arena, k.rev.data(), k.idx.data(), k.clip.empty() ? nullptr : k.clip.data(),
+                               k.text.empty() ? nullptr : k.text.data()});
     } else {
-      (*c->rs->batch_cb)(Batch{first, cnt, res, arena, c->d->rev, c->d->idx});
+      (*c->rs->batch_cb)(Batch{first, cnt, res, arena, c->d->rev, c->d->idx, nullptr, c->d->text});
     }
   } catch (...) {
     c->rs->fail(std::current_exception());  // recorded now, and every slot stops at its next sink call
@@ -957,6 +994,11 @@ void AllPairIterator::take_call_totals(const RunState& rs, const PreparedBatch& 
     awv_norm_stats nx{};
     awv_engine_normalize_stats(e, &nx);
     add(t.report.normalize_stats, nx);
+  }
+  if (rs.encoding && ok) {
+    awv_encode_stats ex{};
+    awv_engine_encode_stats(e, &ex);
+    add(t.report.encode_stats, ex);
   }
   awv_stats x{};
   awv_engine_stats(e, &x);
@@ -1017,6 +1059,7 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   rs.bounded = bounded() && !call.score_only;
   rs.clipping = clip() && !call.score_only;
   rs.splitting = split() && !call.score_only;
+  rs.encoding = call.encode && !call.score_only;
   rs.normalizing = call.score_only ? AWV_NORM_OFF : normalize_;
   rs.div = divergence_bound();
   rs.pen = to_penalties(params_);
@@ -1125,7 +1168,8 @@ void AllPairIterator::for_each_paf_batch(const std::function<void(const std::str
         for (int64_t i = lo; i < hi; ++i) {
           const AlignmentResult a = result_at(b.pair(i), b.is_rev(i), res[i], arena, false, b.clip_at(i));
           const bool ok = res[i].status == AWV_ST_COMPLETED;
-          append_paf(out, a, ok ? arena + res[i].cigar_off : nullptr, ok ? res[i].cigar_len : 0, sequences_);
+          if (const awv_cigar_text* tx = b.text_at(i)) append_paf_text(out, a, tx->len ? arena + tx->off : nullptr, tx->len, sequences_);
+          else append_paf(out, a, ok ? arena + res[i].cigar_off : nullptr, ok ? res[i].cigar_len : 0, sequences_);
           out.push_back('\n');
         }
       });
@@ -1142,7 +1186,7 @@ void AllPairIterator::for_each_paf_batch(const std::function<void(const std::str
       first = std::current_exception();
       throw;
     }
-  });
+  }, EngineCall{false, -1, device_cigar_});
 }
 
 std::vector<PairScore> AllPairIterator::scores(std::optional<int> max_penalty) {
@@ -1158,7 +1202,7 @@ std::vector<PairScore> AllPairIterator::scores(std::optional<int> max_penalty) {
       p.status = b.res[i].status;
       p.penalty = b.res[i].penalty;
     }
-  }, EngineCall{true, max_penalty ? *max_penalty : -1});
+  }, EngineCall{true, max_penalty ? *max_penalty : -1, false});
   return out;
 }
 

@@ -79,6 +79,9 @@ std::vector<uint8_t> reverse_complement(const std::vector<uint8_t>& seq);
 std::string alignment_to_paf(const AlignmentResult& r, const std::vector<Sequence>& sequences);
 void append_paf(std::string& out, const AlignmentResult& r, const uint8_t* ops, size_t nops,
                 const std::vector<Sequence>& sequences);
+// the same line from the CIGAR's ready run-length text (awv_cigar_text: made on the device) instead of its op bytes
+void append_paf_text(std::string& out, const AlignmentResult& r, const uint8_t* text, size_t ntext,
+                     const std::vector<Sequence>& sequences);
 
 // Orientation of the query before the final alignment (alignment.rs:35-39).
 enum class Orientation {
@@ -143,7 +146,8 @@ class AllPairParallelIterator;
 class AllPairIterator;
 
 // The options of one run that filter or rewrite what it delivers, in one place: AllPairIterator::with_max_penalty,
-// with_max_divergence (std::nullopt: no bound), with_clip and with_split (match bonus 0: off), with_normalize (AWV_NORM_OFF: off).
+// with_max_divergence (std::nullopt: no bound), with_clip and with_split (match bonus 0: off), with_normalize (AWV_NORM_OFF: off),
+// with_device_cigar.
 struct RunOptions {
   std::optional<int> max_penalty;
   std::optional<double> max_divergence;
@@ -152,8 +156,9 @@ struct RunOptions {
   int split_match_bonus = 0;
   int64_t split_min_score = 1;
   int normalize = AWV_NORM_OFF;
+  bool device_cigar = false;
   void apply(AllPairIterator& it) const;  // the with_* calls of what is set; they throw std::invalid_argument as documented there
-  bool any() const { return max_penalty || max_divergence || clip_match_bonus != 0 || split_match_bonus != 0 || normalize != AWV_NORM_OFF; }
+  bool any() const { return max_penalty || max_divergence || clip_match_bonus != 0 || split_match_bonus != 0 || normalize != AWV_NORM_OFF || device_cigar; }
 };
 
 // What a run leaves behind besides its results (AllPairIterator::last_report): the failed checks sorted by pair-list index,
@@ -165,6 +170,7 @@ struct RunReport {
   ClipStats clip_stats{};
   SplitStats split_stats{};
   awv_norm_stats normalize_stats{};
+  awv_encode_stats encode_stats{};
 };
 
 class AllPairIterator {  // iterator.rs:12-171
@@ -251,6 +257,15 @@ class AllPairIterator {  // iterator.rs:12-171
   int normalize() const { return normalize_; }
   // of the last run (next(): of the chunks since the list's start), summed over the slots (kernel_ms: summed kernel time)
   awv_norm_stats last_normalize_stats() const { return report_.normalize_stats; }
+  // for_each_paf_batch takes every CIGAR's run-length text from the device (awv_align_pairs_encoded / awv_align_ranges_encoded;
+  // include/allwave_hip.h has the contract): each batch's op strings -- normalized, and clipped, when those are set -- are
+  // encoded on the device, the text comes back in the op bytes' place and goes into the PAF lines as it is.  The lines are
+  // byte-identical to those of a run without the setting.  The consumers that hand out cigar_bytes (for_each_with_callback,
+  // next, into_par_iter, collect) and scores() ignore it.  Not together with with_split (std::invalid_argument).
+  AllPairIterator& with_device_cigar(bool on);
+  bool device_cigar() const { return device_cigar_; }
+  // of the last run, summed over the slots (kernel_ms: summed kernel time)
+  awv_encode_stats last_encode_stats() const { return report_.encode_stats; }
   AllPairIterator& with_max_penalty(int max_penalty);
   AllPairIterator& with_max_divergence(double max_divergence);
   // of the last run (next(): of the chunks since the list's start), summed over the slots
@@ -302,23 +317,26 @@ class AllPairIterator {  // iterator.rs:12-171
     const uint8_t* rev;  // per entry of the call's pair array
     const size_t* idx;   // pair-list index per entry; nullptr: the entry's own position
     const awv_clip_result* clip = nullptr;  // a clipping run: per entry its clip; res[] then describes the segment
+    const awv_cigar_text* text = nullptr;   // an encoding run: per entry its text; `arena` is then the call's text arena
+    const awv_cigar_text* text_at(int64_t i) const { return text ? text + first + i : nullptr; }
     size_t pair(int64_t i) const { return idx ? idx[first + i] : (size_t)(first + i); }
     const awv_clip_result* clip_at(int64_t i) const { return clip ? clip + first + i : nullptr; }
     bool is_rev(int64_t i) const { return rev[first + i] != 0; }
   };
   using BatchCb = std::function<void(const Batch&)>;
   // The engine call a run makes per batch: an alignment call, or awv_score_pairs under max_penalty (< 0: no bound; one sink
-  // call per batch, results carry status and penalty, no arena).
+  // call per batch, results carry status and penalty, no arena); encode: the alignment call's _encoded form (with_device_cigar).
   struct EngineCall {
     bool score_only;
     int32_t max_penalty;
+    bool encode;
   };
   // pairs_[first, first + count) on the with_devices slots; batch indices are relative to `first`.  Per batch: orientation,
   // one engine call, the batch callback, the counters.  One slot: one batch, the whole range in list order, on the calling
   // thread.  With several slots, batch callbacks of different slots run concurrently: consumers that call user code
   // serialise it.
-  void run(size_t first, size_t count, const BatchCb& batch_cb, EngineCall call = {false, -1});
-  void run(const BatchCb& batch_cb, EngineCall call = {false, -1}) { run(0, pairs_.size(), batch_cb, call); }
+  void run(size_t first, size_t count, const BatchCb& batch_cb, EngineCall call = {false, -1, false});
+  void run(const BatchCb& batch_cb, EngineCall call = {false, -1, false}) { run(0, pairs_.size(), batch_cb, call); }
   // run()'s steps (allwave.cpp): what the slots of one run share and what each of them counts; one batch made ready for its
   // engine call; the engine's sink, which hands a call's results to the batch callback; the counters taken after a call
   struct RunState;
@@ -351,6 +369,7 @@ class AllPairIterator {  // iterator.rs:12-171
   int clip_bonus_ = 0;  // with_clip (0: off)
   int64_t clip_min_score_ = 1;
   int normalize_ = AWV_NORM_OFF;  // with_normalize
+  bool device_cigar_ = false;     // with_device_cigar
   int split_bonus_ = 0;  // with_split (0: off)
   int64_t split_min_score_ = 1;
   bool drops_pairs() const { return bounded() || clip() || split(); }  // consumers that keep a slot per pair compact what was delivered
@@ -385,6 +404,7 @@ class AllPairParallelIterator {
   ClipStats last_clip_stats() const { return it_.last_clip_stats(); }
   SplitStats last_split_stats() const { return it_.last_split_stats(); }
   awv_norm_stats last_normalize_stats() const { return it_.last_normalize_stats(); }
+  awv_encode_stats last_encode_stats() const { return it_.last_encode_stats(); }
   const RunReport& last_report() const { return it_.last_report(); }
  private:
   friend class AllPairIterator;

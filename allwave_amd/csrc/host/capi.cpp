@@ -18,13 +18,14 @@ void set_err(char* err, size_t cap, const std::string& m) {
   if (err && cap) snprintf(err, cap, "%s", m.c_str());
 }
 // What the calling thread's last alignment hook left behind, its iterator's last_report(): the verify counters and failures
-// for awh_last_verify, the other counters for awh_last_bounds, awh_last_clip, awh_last_split and awh_last_normalize.
+// for awh_last_verify, the other counters for awh_last_bounds, awh_last_clip, awh_last_split, awh_last_normalize and awh_last_encode.
 thread_local RunReport g_report;
 template <typename It>
 void keep(const It& it) {
   g_report = it.last_report();
 }
-// The options of the calling thread's NEXT alignment hook: awh_set_bounds, awh_set_clip, awh_set_split and awh_set_normalize
+// The options of the calling thread's NEXT alignment hook: awh_set_bounds, awh_set_clip, awh_set_split, awh_set_normalize and
+// awh_set_device_cigar
 // leave them here; the hook takes them (they hold for that one call) and starts the counters they go with afresh.
 thread_local RunOptions g_next;
 RunOptions take_run_options() {
@@ -34,6 +35,7 @@ RunOptions take_run_options() {
   g_report.clip_stats = ClipStats{};
   g_report.split_stats = SplitStats{};
   g_report.normalize_stats = awv_norm_stats{};
+  g_report.encode_stats = awv_encode_stats{};
   return o;
 }
 // the hooks' orientation code on an iterator: 0 forward, 1 WFA, 2 mash, 3 WFA by two full alignments per pair
@@ -126,10 +128,14 @@ int awh_all_pairs_paf_devices(int n, const char* const* ids, const uint8_t* byte
     it.with_verify(verify != 0);
     opts.apply(it);
     std::string all;
-    it.for_each_with_callback([&](AlignmentResult&& r) {  // the reference's own per-record path
-      all += alignment_to_paf(r, seqs);
-      all.push_back('\n');
-    });
+    if (opts.device_cigar) {  // the consumer that takes the device's text: whole formatted batches
+      it.for_each_paf_batch([&](const std::string& chunk) { all += chunk; });
+    } else {
+      it.for_each_with_callback([&](AlignmentResult&& r) {  // the reference's own per-record path
+        all += alignment_to_paf(r, seqs);
+        all.push_back('\n');
+      });
+    }
     keep(it);
     if (slot_stats) for (int k = 0; k < n_devices; ++k) slot_stats[k] = it.last_slot_stats()[(size_t)k];
     *out = (char*)malloc(all.size() + 1);
@@ -583,13 +589,18 @@ int awh_align_ranges_paf(int n, const char* const* ids, const uint8_t* bytes, co
     AllPairIterator it = AllPairIterator::for_ranges(seqs, rg, parse_scores(scores));
     it.with_devices(std::vector<int>(devices, devices + n_devices)).with_verify(verify != 0);
     opts.apply(it);
-    AllPairParallelIterator par = it.into_par_iter();
-    const std::vector<AlignmentResult> res = par.collect();  // (in list order, on any number of slots)
-    keep(par);
     std::string all;
-    for (const AlignmentResult& r : res) {
-      all += alignment_to_paf(r, seqs);
-      all.push_back('\n');
+    if (opts.device_cigar) {  // the consumer that takes the device's text (in list order on one slot, in batch order on several)
+      it.for_each_paf_batch([&](const std::string& chunk) { all += chunk; });
+      keep(it);
+    } else {
+      AllPairParallelIterator par = it.into_par_iter();
+      const std::vector<AlignmentResult> res = par.collect();  // (in list order, on any number of slots)
+      keep(par);
+      for (const AlignmentResult& r : res) {
+        all += alignment_to_paf(r, seqs);
+        all.push_back('\n');
+      }
     }
     *out = (char*)malloc(all.size() + 1);
     if (!*out) throw std::bad_alloc();
@@ -667,6 +678,18 @@ void awh_set_split(int match_bonus, int64_t min_score) {
 // The calling thread's NEXT alignment hook runs with_normalize(direction) (AWV_NORM_LEFT / AWV_NORM_RIGHT; AWV_NORM_OFF: off); the
 // hooks after it run without again.
 void awh_set_normalize(int direction) { g_next.normalize = direction; }
+// The calling thread's NEXT alignment hook runs with_device_cigar(on).  The hooks that format PAF (awh_all_pairs_paf_devices,
+// awh_all_pairs_paf_count_devices, awh_align_ranges_paf) then go through for_each_paf_batch; awh_iterate_devices' consumers hand
+// out op bytes and ignore it.
+void awh_set_device_cigar(int on) { g_next.device_cigar = on != 0; }
+// last_encode_stats() of the calling thread's last alignment hook: {pairs, runs, text_bytes, columns} and the summed kernel time
+void awh_last_encode(uint64_t out[4], double* kernel_ms) {
+  out[0] = g_report.encode_stats.pairs;
+  out[1] = g_report.encode_stats.runs;
+  out[2] = g_report.encode_stats.text_bytes;
+  out[3] = g_report.encode_stats.columns;
+  *kernel_ms = g_report.encode_stats.kernel_ms;
+}
 // last_normalize_stats() of the calling thread's last alignment hook: {pairs, records_moved, runs, runs_moved, columns_moved,
 // columns} and the kernel time
 void awh_last_normalize(uint64_t out[6], double* kernel_ms) {

@@ -67,17 +67,20 @@ struct Delivery {
   const awv_split_index* index = nullptr;
   const awv_clip_result* seg = nullptr;
   SplitStats* splits = nullptr;
+  // an encoding run (text != nullptr): the entry's run-length text in the sink call's text arena -- of the clip in a clipping run
+  const awv_cigar_text* text = nullptr;
 
   bool filters() const { return bounds || clips || splits; }  // false: every entry is delivered as it is, nothing is copied
 };
 
 // What one sink call delivers: the kept records, their strands and pair-list indices and, in a clipping or splitting run,
-// their clips (else empty).
+// their clips (else empty) and, in an encoding run, their texts (else empty).
 struct Delivered {
   std::vector<awv_result> res;
   std::vector<uint8_t> rev;
   std::vector<size_t> idx;
   std::vector<awv_clip_result> clip;
+  std::vector<awv_cigar_text> text;
 };
 
 // The rule, entry by entry in call order, for a run that filters(); counts into the Delivery's stats.
@@ -88,6 +91,7 @@ inline Delivered deliver(const Delivery& d, int64_t first, int64_t cnt, const aw
     out.rev.push_back(d.rev[e]);
     out.idx.push_back(d.idx ? d.idx[e] : (size_t)e);
     if (cl) out.clip.push_back(*cl);
+    if (d.text) out.text.push_back(d.text[e]);
   };
   for (int64_t i = 0; i < cnt; ++i) {
     const awv_result& r = res[i];

@@ -56,6 +56,7 @@ struct Args {
   bool have_split = false, have_split_min_score = false;
   int normalize = AWV_NORM_OFF;  // --normalize left|right: every alignment's gap runs moved to their left- / right-normal place
   bool have_normalize = false;
+  bool device_cigar = false;  // --device-cigar: the run-length text behind cg:Z: is made on the device
 };
 
 [[noreturn]] void die(const std::string& m, int code = 2) {
@@ -247,6 +248,7 @@ int main(int argc, char** argv) {
       a.normalize = v == "left" ? AWV_NORM_LEFT : AWV_NORM_RIGHT;
       a.have_normalize = true;
     }
+    else if (k == "--device-cigar") a.device_cigar = true;
     else if (k == "--clip" || k == "--clip-min-score") {
       const std::string v = val();
       char* end = nullptr;
@@ -281,11 +283,11 @@ int main(int argc, char** argv) {
                    "                   [-t threads] [--wfa-orientation|--wfa-orientation-full|--forward-only] [-k prefixes | -e prefixes] [--mash-matrix]\n"
                    "                   [--device N | --devices LIST] [--shard R/N] [--score-only [--max-penalty N]] [--plan-device N] [--verify]\n"
                    "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
-                   "                   [--split A --split-min-score S] [--normalize left|right]\n"
+                   "                   [--split A --split-min-score S] [--normalize left|right] [--device-cigar]\n"
                    "       allwave_hip -i in.fa --check-paf FILE [-s scores | -x ANI] [--check-optimal] [--partial] [--device N]\n"
                    "       allwave_hip -i in.fa --align-paf FILE [-s scores | -x ANI] [-o out.paf] [--verify] [--score-only] [--device N | --devices LIST]\n"
                    "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
-                   "                   [--split A --split-min-score S] [--normalize left|right]\n"
+                   "                   [--split A --split-min-score S] [--normalize left|right] [--device-cigar]\n"
                    "  --verify         check every alignment on the device before it is written (columns, counts, penalty); the summary\n"
                    "                   line gains `verified N pairs, F failed, K ms`, failures go to stderr, exit status 4 if any\n"
                    "  --check-paf FILE align nothing: check every line of FILE (12 columns + cg:Z:) against in.fa on the device; one line\n"
@@ -320,6 +322,9 @@ int main(int argc, char** argv) {
                    "  --normalize left|right  move every alignment's gap runs as far left (right) as they go among co-optimal placements, on\n"
                    "                   the device, before --verify, --clip and --split see them: only cg:Z: changes; also with --align-paf;\n"
                    "                   the summary line gains `normalized N pairs, R runs moved, K ms`\n"
+                   "  --device-cigar   make the run-length text behind cg:Z: on the device, after --normalize, --verify and --clip, and copy it\n"
+                   "                   back in place of the op bytes: the PAF is byte-identical; also with --align-paf; not with --split; the\n"
+                   "                   summary line gains `encoded N pairs, R runs, B text bytes, K ms`\n"
                    "  --plan-device N  plan on device N: --mash-matrix, the -p pair list and mash orientation (the same output as\n"
                    "                   the host planner; with --shard every rank plans the whole list on its own plan device)\n";
       return 0;
@@ -348,6 +353,10 @@ int main(int argc, char** argv) {
   if (a.have_normalize && a.score_only) die("the argument '--normalize' cannot be used with '--score-only'");
   if (a.have_normalize && a.have_check_paf) die("the argument '--normalize' cannot be used with '--check-paf'");
   if (a.have_normalize && a.mash_matrix) die("the argument '--normalize' cannot be used with '--mash-matrix'");
+  if (a.device_cigar && a.have_split) die("the argument '--device-cigar' cannot be used with '--split'");
+  if (a.device_cigar && a.score_only) die("the argument '--device-cigar' cannot be used with '--score-only'");
+  if (a.device_cigar && a.have_check_paf) die("the argument '--device-cigar' cannot be used with '--check-paf'");
+  if (a.device_cigar && a.mash_matrix) die("the argument '--device-cigar' cannot be used with '--mash-matrix'");
   if (a.check_optimal && !a.have_check_paf) die("the argument '--check-optimal' requires '--check-paf'");
   if (a.verify && a.score_only) die("the argument '--verify' cannot be used with '--score-only'");
   if (a.verify && a.mash_matrix) die("the argument '--verify' cannot be used with '--mash-matrix'");
@@ -464,6 +473,7 @@ int main(int argc, char** argv) {
     if (a.have_clip) it.with_clip((int)a.clip, (int64_t)a.clip_min_score);
     if (a.have_split) it.with_split((int)a.split, (int64_t)a.split_min_score);
     if (a.have_normalize) it.with_normalize(a.normalize);
+    it.with_device_cigar(a.device_cigar);
     if (a.forward_only) it.with_orientation(Orientation::ForwardOnly);
     it.with_full_wfa_orientation(a.wfa_orientation_full);
     it.with_devices(devices);
@@ -543,6 +553,11 @@ int main(int argc, char** argv) {
         const awv_norm_stats ns = it.last_normalize_stats();
         w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", normalized %llu pairs, %llu runs moved, %.2f ms", (unsigned long long)ns.pairs,
                       (unsigned long long)ns.runs_moved, ns.kernel_ms);
+      }
+      if (a.device_cigar && w > 0 && (size_t)w < sizeof(buf)) {
+        const awv_encode_stats es = it.last_encode_stats();
+        w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", encoded %llu pairs, %llu runs, %llu text bytes, %.2f ms", (unsigned long long)es.pairs,
+                      (unsigned long long)es.runs, (unsigned long long)es.text_bytes, es.kernel_ms);
       }
       if (a.verify && w > 0 && (size_t)w < sizeof(buf)) {
         const awv_verify_stats vs = it.last_verify_stats();

@@ -86,7 +86,8 @@ EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine
            "awv_split_slots", "awv_split_layout_pairs", "awv_split_layout_ranges", "awv_split_one_host", "awv_split_cigars",
            "awv_align_pairs_split", "awv_align_ranges_split", "awv_engine_split_stats",
            "awv_normalize_one_host", "awv_normalize_cigars", "awv_normalize_ranges", "awv_engine_set_normalize",
-           "awv_engine_normalize_stats")
+           "awv_engine_normalize_stats",
+           "awv_encode_one_host", "awv_encode_cigars", "awv_align_pairs_encoded", "awv_align_ranges_encoded", "awv_engine_encode_stats")
 
 
 class EngineConfig(C.Structure):
@@ -140,6 +141,10 @@ class NormStats(C.Structure):
                 ("runs_moved", C.c_uint64), ("columns_moved", C.c_uint64), ("columns", C.c_uint64)]
 
 
+class EncodeStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("pairs", C.c_uint64), ("runs", C.c_uint64), ("text_bytes", C.c_uint64), ("columns", C.c_uint64)]
+
+
 PAIR_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4")])
 #: awv_range_pair: the query interval on the query's forward strand (PAF convention), also with q_revcomp
 RANGE_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4"), ("q_beg", "<i4"), ("q_end", "<i4"),
@@ -157,6 +162,8 @@ CLIP_DTYPE = np.dtype([("code", "<i4"), ("reserved", "<i4"), ("score", "<i8"), (
 SPLIT_INDEX_DTYPE = np.dtype([("code", "<i4"), ("count", "<i4"), ("column", "<i8")])
 #: awv_norm_result: what normalization did to one op string (columns_moved: the smallest offending column under AWV_NM_BAD_OP)
 NORM_DTYPE = np.dtype([("code", "<i4"), ("runs_moved", "<i4"), ("columns_moved", "<i8"), ("max_shift", "<i4"), ("reserved", "<i4")])
+#: awv_cigar_text: where a record's run-length text lies in its call's or batch's text arena, and its run count
+CIGAR_TEXT_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("runs", "<u4")])
 #: awv_score_result
 SCORE_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4")])
 
@@ -234,6 +241,13 @@ def load():
         L.awv_normalize_ranges.argtypes = L.awv_normalize_cigars.argtypes
         L.awv_engine_set_normalize.argtypes = [C.c_void_p, C.c_int32]
         L.awv_engine_normalize_stats.argtypes = [C.c_void_p, C.POINTER(NormStats)]
+        L.awv_encode_one_host.argtypes = [C.c_char_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.awv_encode_cigars.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                        C.POINTER(C.c_uint64)]
+        L.awv_align_pairs_encoded.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, SINK_FN, C.c_void_p]
+        L.awv_align_ranges_encoded.argtypes = L.awv_align_pairs_encoded.argtypes
+        L.awv_engine_encode_stats.argtypes = [C.c_void_p, C.POINTER(EncodeStats)]
         _LIB = L
     return _LIB
 
@@ -316,13 +330,14 @@ class Engine:
         return np.ascontiguousarray(ranges)
 
     def align_ranges(self, scores, ranges, want_cigars=True, verify=False, max_penalty=None, clip=None, _sink_hook=None, split=None,
-                     normalize=None):
+                     normalize=None, encode=False):
         """align_pairs on interval pairs (awv_align_ranges / awv_align_ranges_verified).  ranges: int array [n,7] (q_idx, t_idx,
         q_revcomp, q_beg, q_end, t_beg, t_end) or a RANGE_DTYPE array; the query interval is on the query's forward strand.
         The records' q_end / t_end are consumed lengths, relative to the range.  max_penalty: as for align_pairs
-        (awv_align_ranges_bounded); clip, split, normalize: as for align_pairs (awv_align_ranges_clipped, awv_align_ranges_split)."""
+        (awv_align_ranges_bounded); clip, split, normalize, encode: as for align_pairs (awv_align_ranges_clipped,
+        awv_align_ranges_split, awv_align_ranges_encoded)."""
         return self._align("awv_align_ranges", scores, self._range_array(ranges), want_cigars, verify, max_penalty, clip, _sink_hook, split,
-                           normalize)
+                           normalize, encode)
 
     def score_ranges(self, scores, ranges, max_penalty=None):
         """score_pairs on interval pairs (awv_score_ranges).  max_penalty: None, or one bound per range (negative: none)."""
@@ -344,7 +359,7 @@ class Engine:
         return self._verify("awv_verify_ranges", scores, self._range_array(ranges), results, arena)
 
     def align_pairs(self, scores, pairs, want_cigars=True, verify=False, max_penalty=None, clip=None, _sink_hook=None, split=None,
-                    normalize=None):
+                    normalize=None, encode=False):
         """pairs: int array [n,2] (q,t) or [n,3] (q,t,revcomp), or a PAIR_DTYPE array.
         Returns (results structured array, list of op-byte strings or None); verify=True: every finished pair is checked on
         the device (awv_align_pairs_verified) and a VERIFY_DTYPE array comes back as a third value.
@@ -363,9 +378,15 @@ class Engine:
         seg_first, slots)) -- the call's raw storage as filled so far.
         normalize: None, "left" or "right": every finished pair's gap runs are moved to their left- (right-) normal place on
         the device before the check, the clip, the split and the copy back (awv_engine_set_normalize for this call; the
-        engine's mode is off again afterwards).  Records are those of the unnormalized call; normalize_stats() reports."""
+        engine's mode is off again afterwards).  Records are those of the unnormalized call; normalize_stats() reports.
+        encode=True: every finished pair's op string -- normalized, and clipped to its segment, when those are asked for -- is
+        turned into its run-length text on the device (awv_align_pairs_encoded; not together with split), and the text comes
+        back in the op bytes' place: the second value is the list of texts (bytes; b"" for a pair that is not completed or has
+        no clip; None throughout without want_cigars or under AWV_F_KEEP_ON_DEVICE), and one more value comes last, the
+        CIGAR_TEXT_DTYPE array (offsets relative to each batch's text arena).  Records, the verify and the clip arrays are the
+        call's without encode; encode_stats() reports."""
         return self._align("awv_align_pairs", scores, self._pair_array(pairs), want_cigars, verify, max_penalty, clip, _sink_hook, split,
-                           normalize)
+                           normalize, encode)
 
     def split_layout(self, pairs_or_ranges, match_bonus, min_score):
         """awv_split_layout_pairs / awv_split_layout_ranges: seg_first (uint64, n + 1) for a PAIR_DTYPE / RANGE_DTYPE array (or
@@ -390,17 +411,18 @@ class Engine:
         if rc != AWV_OK:
             raise EngineError(rc, "awv_engine_set_normalize")
 
-    def _align(self, fn, scores, pairs, want_cigars, verify, max_penalty=None, clip=None, _sink_hook=None, split=None, normalize=None):
+    def _align(self, fn, scores, pairs, want_cigars, verify, max_penalty=None, clip=None, _sink_hook=None, split=None, normalize=None,
+               encode=False):
         """_align_plain under the engine mode `normalize` (None: the mode is left alone)."""
         if norm_mode(normalize) == AWV_NORM_OFF:
-            return self._align_plain(fn, scores, pairs, want_cigars, verify, max_penalty, clip, _sink_hook, split)
+            return self._align_plain(fn, scores, pairs, want_cigars, verify, max_penalty, clip, _sink_hook, split, encode)
         self.set_normalize(normalize)
         try:
-            return self._align_plain(fn, scores, pairs, want_cigars, verify, max_penalty, clip, _sink_hook, split)
+            return self._align_plain(fn, scores, pairs, want_cigars, verify, max_penalty, clip, _sink_hook, split, encode)
         finally:
             self.set_normalize(None)
 
-    def _align_plain(self, fn, scores, pairs, want_cigars, verify, max_penalty=None, clip=None, _sink_hook=None, split=None):
+    def _align_plain(self, fn, scores, pairs, want_cigars, verify, max_penalty=None, clip=None, _sink_hook=None, split=None, encode=False):
         """awv_align_pairs / awv_align_ranges (`fn`; verify: its _verified variant; max_penalty: its _bounded variant; clip: its
         _clipped variant, which takes the other two as well) on a contiguous PAIR_DTYPE / RANGE_DTYPE array."""
         pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
@@ -418,6 +440,9 @@ class Engine:
         cigars = [None] * len(pairs) if want_cigars else None
         cres = np.zeros(max(len(pairs), 1), dtype=CLIP_DTYPE)[:len(pairs)] if clip is not None else None
         sp = None
+        tres = np.zeros(max(len(pairs), 1), dtype=CIGAR_TEXT_DTYPE)[:len(pairs)] if encode else None
+        if encode and split is not None:
+            raise ValueError("encode and split exclude each other")
         if split is not None:
             if clip is not None:
                 raise ValueError("split and clip exclude each other")
@@ -431,7 +456,10 @@ class Engine:
                 _sink_hook(int(first), int(n), cres)
             if _sink_hook is not None and sp is not None:
                 _sink_hook(int(first), int(n), sp)
-            if cigars is not None and arena:
+            if cigars is not None and arena and tres is not None:  # the arena is the batch's text arena
+                for i in range(first, first + n):
+                    cigars[i] = C.string_at(arena + int(tres["off"][i]), int(tres["len"][i]))
+            elif cigars is not None and arena:
                 r = np.ctypeslib.as_array(C.cast(rptr, C.POINTER(C.c_uint8)), shape=(n * RESULT_DTYPE.itemsize,))
                 r = r.view(RESULT_DTYPE)
                 for i in range(n):
@@ -450,6 +478,15 @@ class Engine:
                 raise EngineError(rc, fn_s)
             found = (sp[0], self._segment_lists(*sp))
             return (res, cigars, vres, found) if verify else (res, cigars, found)
+        if tres is not None:
+            fn_e = fn + "_encoded"
+            vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)] if verify else None
+            rc = getattr(load(), fn_e)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), None if bounds is None else bounds.ctypes.data,
+                                       0 if clip is None else int(clip), res.ctypes.data, vres.ctypes.data if verify else None,
+                                       None if cres is None else cres.ctypes.data, tres.ctypes.data, cb, None)
+            if rc != AWV_OK:
+                raise EngineError(rc, fn_e)
+            return (res, cigars) + ((vres,) if verify else ()) + ((cres,) if cres is not None else ()) + (tres,)
         if cres is not None:
             fn_c = fn + "_clipped"
             vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)] if verify else None
@@ -522,6 +559,51 @@ class Engine:
         if rc != AWV_OK:
             raise EngineError(rc, fn)
         return arena, nres
+
+    def encode_cigars(self, results, arena, slices=None, want_text=True, text_cap=None):
+        """awv_encode_cigars: the run-length texts of caller-supplied records (a RESULT_DTYPE array whose cigar_off / cigar_len
+        point into `arena`, bytes or a uint8 array), made on the device; needs no sequence set.  slices: None, or an [n, 2]
+        array of (col_beg, col_end) -- record i is encoded over those columns of its string.  Returns (texts, tout, text_bytes):
+        the text arena as a uint8 array, a CIGAR_TEXT_DTYPE array and the arena's size.  want_text=False is the measuring call
+        (text_buf == NULL, text_cap == 0) and gives texts None; text_cap: the buffer's size (default: measured first, so that it
+        fits) -- a buffer smaller than text_bytes is left untouched and comes back as it was, filled with 0xff."""
+        results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
+        nbytes = int(arena.size)
+        if nbytes == 0:
+            arena = np.zeros(1, dtype=np.uint8)
+        sl = None
+        if slices is not None:
+            sl = np.ascontiguousarray(np.asarray(slices, dtype=np.uint32).reshape(-1, 2))
+            if sl.shape != (len(results), 2):
+                raise ValueError("slices: need one (col_beg, col_end) per record")
+            sl = sl if len(sl) else np.zeros((1, 2), dtype=np.uint32)
+        tout = np.zeros(max(len(results), 1), dtype=CIGAR_TEXT_DTYPE)[:len(results)]
+        total = C.c_uint64(0)
+
+        def call(buf, cap):
+            rc = load().awv_encode_cigars(self._h, results.ctypes.data, len(results), arena.ctypes.data, nbytes, None if sl is None else sl.ctypes.data,
+                                          tout.ctypes.data, None if buf is None else buf.ctypes.data, cap, C.byref(total))
+            if rc != AWV_OK:
+                raise EngineError(rc, "awv_encode_cigars")
+
+        if not want_text:
+            call(None, 0)
+            return None, tout, int(total.value)
+        if text_cap is None:
+            call(None, 0)
+            text_cap = int(total.value)
+        text = np.full(max(int(text_cap), 1), 0xff, dtype=np.uint8)
+        call(text, int(text_cap))
+        return text[:int(text_cap)], tout, int(total.value)
+
+    def encode_stats(self):
+        """awv_engine_encode_stats: kernel_ms, pairs, runs, text_bytes, columns of the last encoding call."""
+        st = EncodeStats()
+        rc = load().awv_engine_encode_stats(self._h, C.byref(st))
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_engine_encode_stats")
+        return st
 
     def normalize_stats(self):
         """awv_engine_normalize_stats: kernel_ms, pairs, records_moved, runs, runs_moved, columns_moved, columns of the last
@@ -697,6 +779,21 @@ def normalize_one_host(direction, pattern, text, cigar):
     if rc != AWV_OK:
         raise EngineError(rc, "awv_normalize_one_host")
     return buf.raw[:len(cigar)], out[0]
+
+
+def encode_one_host(cigar, cap=None):
+    """awv_encode_one_host: the run-length text of an op string on the host (needs no device; the yardstick the kernels are
+    tested against).  Returns (text, one CIGAR_TEXT_DTYPE record); cap: the buffer's size (default: enough) -- with a buffer
+    smaller than the text, the text is b"" and the record still holds its length and run count."""
+    cigar = bytes(cigar)
+    size = 2 * len(cigar) if cap is None else int(cap)
+    buf = C.create_string_buffer(max(size, 1))
+    out = np.zeros(1, dtype=CIGAR_TEXT_DTYPE)
+    rc = load().awv_encode_one_host(cigar, len(cigar), buf, size, out.ctypes.data)
+    if rc != AWV_OK:
+        raise EngineError(rc, "awv_encode_one_host")
+    n = int(out[0]["len"])
+    return (buf.raw[:n] if n <= size else b""), out[0]
 
 
 def clip_one_host(scores, match_bonus, cigar):

@@ -79,7 +79,7 @@ typedef struct {
   int32_t device;          /* HIP device ordinal */
   int32_t workgroups;      /* persistent workgroups = pairs in flight (0 = engine default: 16 per CU); the align kernels open
                               workgroups / (waves per workgroup) slots, at least one, and the record kernels (verify, clip,
-                              split, normalize) launch min(records, workgroups) one-wave workgroups -- 0: min(records, 16 per CU) */
+                              split, normalize, encode) launch min(records, workgroups) one-wave workgroups -- 0: min(records, 16 per CU) */
   int64_t max_batch_pairs; /* pairs per launch (0 = default) */
   int64_t max_arena_bytes; /* CIGAR arena budget per launch (0 = default 8 GiB) */
   int32_t flags;           /* AWV_F_* */
@@ -582,7 +582,7 @@ int awv_normalize_cigars(awv_engine* e, int32_t direction, const awv_pair* pairs
 int awv_normalize_ranges(awv_engine* e, int32_t direction, const awv_range_pair* ranges, int64_t n, const awv_result* results,
                          uint8_t* cigar_arena /* in/out */, uint64_t arena_bytes, awv_norm_result* nout /* required */);
 /* The engine's mode (AWV_NORM_OFF by default), read at the start of every aligning call: awv_align_pairs, awv_align_ranges,
- * their _verified, _bounded, _clipped and _split forms, and awv_align_one.  When it is on, every batch's finished pairs are
+ * their _verified, _bounded, _clipped, _split and _encoded forms, and awv_align_one.  When it is on, every batch's finished pairs are
  * normalized in the batch's arena on the device, on the engine's stream (pairs re-run after AWV_ST_CAPACITY included; also
  * under AWV_F_KEEP_ON_DEVICE), BEFORE the optional check, clip and split and before the copy back: vout, cout and the
  * segments describe the normalized string.  Records are byte-identical to the unnormalized call's.  When it is off there is
@@ -590,6 +590,61 @@ int awv_normalize_ranges(awv_engine* e, int32_t direction, const awv_range_pair*
 int awv_engine_set_normalize(awv_engine* e, int32_t mode);
 /* The last normalizing call (an aligning call under a mode, awv_normalize_cigars / _ranges) of this engine. */
 int awv_engine_normalize_stats(const awv_engine* e, awv_norm_stats* out);
+
+/* ---- run-length CIGAR text made on the device (csrc/encode.hip, csrc/encode_device.hpp) ---------------------------------------
+ * The engine keeps a CIGAR as one op byte per column; what a PAF line carries behind cg:Z: is its run-length text.  The text of
+ * an op string c[0..n) is exactly what the reference's cigar_bytes_to_string (src/alignment.rs:347-376) returns: every maximal
+ * run of equal bytes becomes its length in decimal followed by one character, 'M' -> '=', 'X' -> 'X', 'I' -> 'D', 'D' -> 'I'
+ * (the gap letters swap), any other byte -> '?'.  An empty string has empty text.  A slice [col_beg, col_end) of a string is
+ * encoded as an op string of its own, so a slice that begins or ends inside a run cuts that run.  A record whose status is not
+ * AWV_ST_COMPLETED (AWV_ST_ABOVE_BOUND included) has empty text.  A pure function of the op bytes: no sequence, no penalties.
+ * Layout: the texts of a call's (or a batch's) records lie in one text arena, dense and in record order -- off[0] = 0 and
+ * off[i + 1] = off[i] + len[i] -- so one contiguous copy of exactly the text bytes brings them home, and the layout does not
+ * depend on the order the device worked in.  A string or slice holds at most 2^31 - 1 columns (AWV_ERR_ARG beyond). */
+typedef struct {
+  uint64_t off;   /* of the record's text in the text arena */
+  uint32_t len;   /* characters */
+  uint32_t runs;  /* maximal runs = letters in the text */
+} awv_cigar_text; /* 16 bytes */
+
+typedef struct {
+  double kernel_ms;     /* HIP-event time of the encode launches (measure, scan, emit) of the last encoding call */
+  uint64_t pairs;       /* records handed to the step (the ones without text included) */
+  uint64_t runs;        /* runs encoded */
+  uint64_t text_bytes;  /* characters of all texts */
+  uint64_t columns;     /* op bytes of the strings and slices encoded */
+} awv_encode_stats;
+
+/* The contract alone, on the host (needs no device): a serial walk, the yardstick the kernels are tested against, not a
+ * fallback -- no product path calls it.  out->off is 0; the text is written to out_buf only when out->len <= cap. */
+int awv_encode_one_host(const uint8_t* cigar, int64_t n, uint8_t* out_buf, uint64_t cap, awv_cigar_text* out /* required */);
+/* Encodes records and op bytes the caller supplies, on the device; staged and pieced as awv_clip_cigars does, the offsets
+ * running on from piece to piece.  slices (nullable): 2 n entries, record i is encoded over its columns [slices[2 i],
+ * slices[2 i + 1]).  Reads no sequence: the engine needs no sequence set.  tout[0..n) and *text_bytes (the arena's size) are always
+ * filled; the text is written to text_buf only when *text_bytes <= text_cap -- all of it or nothing -- so text_buf == NULL with
+ * text_cap == 0 is the measuring call.  AWV_ERR_ARG, before anything is launched, for a completed record whose op bytes lie
+ * outside the arena and for a slice with col_beg > col_end or col_end > cigar_len. */
+int awv_encode_cigars(awv_engine* e, const awv_result* results, int64_t n, const uint8_t* cigar_arena, uint64_t arena_bytes,
+                      const uint32_t* slices /* nullable */, awv_cigar_text* tout /* required */, uint8_t* text_buf, uint64_t text_cap,
+                      uint64_t* text_bytes /* required */);
+/* awv_align_pairs_clipped / awv_align_ranges_clipped with every batch's finished pairs encoded on the device, on the engine's
+ * stream, last of the per-batch steps (after normalization, the optional check and the optional clip: the text is of the
+ * normalized string under a mode).  match_bonus == 0: no clip, cout is not read and the text is the whole string's;
+ * match_bonus >= 1: cout is required and the text is the clip's slice [col_beg, col_end), empty when the clip's code is not
+ * AWV_CL_OK.  Records, vout and cout are the unencoded call's, byte for byte: cigar_off / cigar_len still describe the op
+ * bytes, which stay on the device and are NOT copied back.  The sink is called as always, but its cigar_arena argument is the
+ * batch's text arena, and tout[first .. first + n) is filled before the call, relative to that arena.  Under
+ * AWV_F_KEEP_ON_DEVICE the step runs and tout is filled, but no text is copied (the sink's arena is NULL). */
+int awv_align_pairs_encoded(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
+                            const int32_t* max_penalty /* per pair, nullable; < 0: none */, int32_t match_bonus, awv_result* out,
+                            awv_verify_result* vout /* nullable */, awv_clip_result* cout /* nullable when match_bonus == 0 */,
+                            awv_cigar_text* tout /* required */, awv_sink sink, void* user);
+int awv_align_ranges_encoded(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n,
+                             const int32_t* max_penalty /* per range, nullable; < 0: none */, int32_t match_bonus, awv_result* out,
+                             awv_verify_result* vout /* nullable */, awv_clip_result* cout /* nullable when match_bonus == 0 */,
+                             awv_cigar_text* tout /* required */, awv_sink sink, void* user);
+/* The last encoding call (awv_align_*_encoded / awv_encode_cigars) of this engine. */
+int awv_engine_encode_stats(const awv_engine* e, awv_encode_stats* out);
 
 /* ---- device pair planning (csrc/planner.hip) -------------------------------------------------------------------------
  * Integer work over the engine's resident sequence set, on its device and stream; results equal the host planner's
