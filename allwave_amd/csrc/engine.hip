@@ -14,6 +14,7 @@
 #include "split_device.hpp"    // (the per-batch split of awv_align_pairs_split, split.hip)
 #include "normalize_device.hpp"  // (the per-batch normalization under awv_engine_set_normalize, normalize.hip)
 #include "encode_device.hpp"   // (the per-batch run-length text of awv_align_pairs_encoded, encode.hip)
+#include "cs_device.hpp"       // (the per-batch cs text of awv_align_pairs_cs, cs.hip)
 #include "kernels_awv.hpp"  // (the awv:: kernels themselves are instantiated in kernels_awv.hip -- here only the types)
 #define AWV_NS awv
 #define AWV_WG 64
@@ -170,6 +171,7 @@ struct awv_engine {
   DevBuf<uint8_t> d_cigar;
   DevBuf<unsigned long long> d_counters;  // [0] work cursor, [1..] stats
   std::vector<uint8_t> h_cigar;
+  std::vector<uint8_t> h_cs;  // a cs call: the batch's cs text, next to h_cigar and handed on like it
   // host sides of a launch's uploads and of its read-back: kept with the engine, like h_cigar, so that the copies of every call
   // start from / land in the same host memory (fresh allocations per call cost the runtime tens of milliseconds now and then)
   struct HostStage {
@@ -186,6 +188,7 @@ struct awv_engine {
   awvs::State* split = nullptr;    // split.hip: likewise for the split launches
   awvn::State* normalize = nullptr;  // normalize.hip: likewise for the normalize launches
   awve::State* encode = nullptr;   // encode.hip: likewise for the encode launches, and the text arena of the batch in hand
+  awvx::State* cs = nullptr;       // cs.hip: likewise for the cs launches, and the cs arena of the batch in hand
   int32_t norm_mode = AWV_NORM_OFF;  // awv_engine_set_normalize: read at the start of every aligning call
 };
 
@@ -353,6 +356,11 @@ struct AlignRequest {
   // (nullable; awv_align_pairs_encoded): every batch's op strings -- their clips under match_bonus > 0 -- become run-length text
   // on the device, last of the record steps; the text is copied back and handed to the sink in the op bytes' place
   awv_cigar_text* tout = nullptr;
+  // (nullable; awv_align_pairs_cs): every batch's op strings -- their clips under match_bonus > 0 -- become cs text on the device,
+  // after the run-length text; it is copied to a host buffer of its own and handed to cs_sink, which stands in sink's place
+  awv_cs_text* csout = nullptr;
+  int32_t cs_mode = 0;
+  awv_cs_sink cs_sink = nullptr;
 };
 
 // With several batches in a call, the sink of batch i (the caller's formatting and output) runs on a
@@ -363,7 +371,7 @@ struct SinkRunner {
   std::thread th;
   int rc = 0;
   std::vector<awv_result> res;
-  std::vector<uint8_t> cig;
+  std::vector<uint8_t> cig, cs;
   int wait() {
     if (th.joinable()) th.join();
     const int r = rc;
@@ -393,6 +401,7 @@ struct AlignCall {
   int64_t first = 0, n = 0;
   uint64_t arena = 0;
   uint64_t text_bytes = 0;  // an encoded call: the batch's text arena
+  uint64_t cs_bytes = 0;    // a cs call: the batch's cs arena
   std::vector<awvb::Entry> entries;
   std::vector<awv_result> hres;
   double kernel_ms = 0, h2d_ms = 0, d2h_ms = 0;
@@ -400,7 +409,7 @@ struct AlignCall {
   uint64_t launches = 0;
   awvrr::Layout reuse{0, 0, 0, 0};  // the running group's row archives (passes == 0: none)
   SinkRunner runner;
-  bool want_cigar() const { return rq.sink && !rq.score_only && !(e->cfg.flags & AWV_F_KEEP_ON_DEVICE); }
+  bool want_cigar() const { return (rq.sink || rq.cs_sink) && !rq.score_only && !(e->cfg.flags & AWV_F_KEEP_ON_DEVICE); }
   void lap(const char* what) const {  // diagnostic: host-side stage times on stderr
     if (timing) fprintf(stderr, "[awv] %-22s %.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
   }
@@ -865,6 +874,11 @@ int run_record_steps(AlignCall& c) {
     if (int rc = awve::encode_batch(e, n, hres.data(), e->d_cigar.p, arena, rq.cout ? rq.cout + first : nullptr, rq.tout + first, &c.text_bytes)) return rc;
     c.lap("batch encoded");
   }
+  if (rq.csout) {
+    if (int rc = awvx::cs_batch(e, rq.cs_mode, rq.pairs + first, n, hres.data(), e->d_cigar.p, arena, rq.cout ? rq.cout + first : nullptr,
+                                rq.spans ? rq.spans + first : nullptr, rq.csout + first, &c.cs_bytes)) return rc;
+    c.lap("batch cs");
+  }
   return AWV_OK;
 }
 
@@ -878,6 +892,10 @@ int copy_cigars_back(AlignCall& c) {
     c.lap("host cigar buffer");
     AWV_TRY(hipEventRecord(e->ev0, e->stream));
     if (bytes) AWV_TRY(hipMemcpyAsync(e->h_cigar.data(), src, bytes, hipMemcpyDeviceToHost, e->stream));
+    if (c.rq.csout) {  // (inside the same bracket: one wait for both copies)
+      e->h_cs.resize((size_t)c.cs_bytes + 64);
+      if (c.cs_bytes) AWV_TRY(hipMemcpyAsync(e->h_cs.data(), awvx::batch_text(e), (size_t)c.cs_bytes, hipMemcpyDeviceToHost, e->stream));
+    }
     if (int rc = timer_stop(c, c.d2h_ms)) return rc;
   }
   c.lap("cigars on host");
@@ -888,13 +906,18 @@ int copy_cigars_back(AlignCall& c) {
 int deliver(AlignCall& c) {
   const AlignRequest& rq = c.rq;
   if (rq.out) std::memcpy(rq.out + c.first, c.hres.data(), (size_t)c.n * sizeof(awv_result));
-  if (!rq.sink) return AWV_OK;
+  if (!rq.sink && !rq.cs_sink) return AWV_OK;
   const bool want_cigar = c.want_cigar();
-  const awv_sink sink = rq.sink;
+  // a cs call's sink also takes the batch's cs arena
+  const awv_sink plain = rq.sink;
+  const awv_cs_sink with_cs = rq.cs_sink;
+  const auto sink = [plain, with_cs](void* u, int64_t f, int64_t m, const awv_result* r, const uint8_t* cig, const uint8_t* cs) {
+    return with_cs ? with_cs(u, f, m, r, cig, cs) : plain(u, f, m, r, cig);
+  };
   void* const user = rq.user;
   if (const int prc = c.runner.wait()) return fail(AWV_ERR_SINK, "sink callback returned " + std::to_string(prc));
   if (c.first + c.n >= rq.npairs || c.inline_sink) {  // the last (or only) batch: on the calling thread
-    const int rc = sink(user, c.first, c.n, c.hres.data(), want_cigar ? c.e->h_cigar.data() : nullptr);
+    const int rc = sink(user, c.first, c.n, c.hres.data(), want_cigar ? c.e->h_cigar.data() : nullptr, want_cigar && with_cs ? c.e->h_cs.data() : nullptr);
     if (rc != 0) return fail(AWV_ERR_SINK, "sink callback returned " + std::to_string(rc));
     c.lap("sink returned");
     return AWV_OK;
@@ -902,15 +925,17 @@ int deliver(AlignCall& c) {
   // hand the batch's buffers to the helper thread and go on with the next batch
   c.runner.res.swap(c.hres);
   c.runner.cig.swap(c.e->h_cigar);
+  c.runner.cs.swap(c.e->h_cs);
   const awv_result* rp = c.runner.res.data();
   const uint8_t* cp = want_cigar ? c.runner.cig.data() : nullptr;
+  const uint8_t* xp = want_cigar && with_cs ? c.runner.cs.data() : nullptr;
   const int64_t f0 = c.first, n0 = c.n;
   SinkRunner* rn = &c.runner;
   try {
-    c.runner.th = std::thread([rn, sink, user, f0, n0, rp, cp]() { rn->rc = sink(user, f0, n0, rp, cp); });
+    c.runner.th = std::thread([rn, sink, user, f0, n0, rp, cp, xp]() { rn->rc = sink(user, f0, n0, rp, cp, xp); });
     c.lap("sink handed off");
   } catch (const std::exception&) {  // no thread to be had: this sink runs here, nothing may cross the C boundary
-    const int rc = sink(user, f0, n0, rp, cp);
+    const int rc = sink(user, f0, n0, rp, cp, xp);
     if (rc != 0) return fail(AWV_ERR_SINK, "sink callback returned " + std::to_string(rc));
   }
   return AWV_OK;
@@ -1074,6 +1099,8 @@ void awv_engine_destroy(awv_engine* e) {
   e->normalize = nullptr;
   awve::state_release(e->encode);
   e->encode = nullptr;
+  awvx::state_release(e->cs);
+  e->cs = nullptr;
   e->seqs.release();
   e->ring_mem.release();
   e->hist_mem.release();
@@ -1297,6 +1324,62 @@ int awv_align_ranges_encoded(awv_engine* e, const awv_penalties* pen, const awv_
   AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, rq);)
 }
 
+namespace {
+// what every cs call refuses before anything is launched; match_bonus == 0: no clip, cout is not read
+int check_cs_args(int32_t cs_mode, const awv_cs_text* csout, awv_clip_result*& cout, int32_t match_bonus) {
+  if (!awvx::mode_ok(cs_mode)) return fail(AWV_ERR_ARG, "align_cs: cs_mode must be AWV_CS_SHORT or AWV_CS_LONG");
+  if (!csout) return fail(AWV_ERR_ARG, "align_cs: null csout");
+  if (match_bonus == 0) {
+    cout = nullptr;
+    return AWV_OK;
+  }
+  return check_clip_args(cout, match_bonus);
+}
+// the encoded call's request plus the cs step; the sink that takes both arenas stands in the plain sink's place
+void cs_request(AlignRequest& rq, const int32_t* bounds, int32_t match_bonus, awv_verify_result* vout, awv_clip_result* cout, awv_cigar_text* tout,
+                int32_t cs_mode, awv_cs_text* csout, awv_cs_sink sink) {
+  rq.pair_bound = bounds;
+  rq.vout = vout;
+  rq.cout = cout;
+  rq.match_bonus = match_bonus;
+  rq.tout = tout;
+  rq.cs_mode = cs_mode;
+  rq.csout = csout;
+  rq.cs_sink = sink;
+}
+}  // namespace
+
+int awv_align_pairs_cs(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const int32_t* max_penalty, int32_t match_bonus,
+                       awv_result* out, awv_verify_result* vout, awv_clip_result* cout, awv_cigar_text* tout, int32_t cs_mode, awv_cs_text* csout,
+                       awv_cs_sink sink, void* user) {
+  if (!e) return fail(AWV_ERR_ARG, "null engine");
+  if (int rc = check_cs_args(cs_mode, csout, cout, match_bonus)) return rc;
+  if (int rc = require_sequences(e, npairs, "align_pairs")) return rc;
+  if (vout) awvf::stats_reset(e->verify);
+  if (cout) awvc::stats_reset(e->clip);
+  if (tout) awve::stats_reset(e->encode);
+  awvx::stats_reset(e->cs);
+  AWV_GUARDED(
+    std::vector<int32_t> pb;
+    AlignRequest rq = full_request(pairs, npairs, out, nullptr, user);
+    cs_request(rq, normalized_bounds(max_penalty, npairs, pb), match_bonus, vout, cout, tout, cs_mode, csout, sink);
+    return align_core(e, e->seqs, pen, rq);
+  )
+}
+
+int awv_align_ranges_cs(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const int32_t* max_penalty, int32_t match_bonus,
+                        awv_result* out, awv_verify_result* vout, awv_clip_result* cout, awv_cigar_text* tout, int32_t cs_mode, awv_cs_text* csout,
+                        awv_cs_sink sink, void* user) {
+  if (!e) return fail(AWV_ERR_ARG, "null engine");
+  if (int rc = check_cs_args(cs_mode, csout, cout, match_bonus)) return rc;
+  if (cout) awvc::stats_reset(e->clip);
+  if (tout) awve::stats_reset(e->encode);
+  awvx::stats_reset(e->cs);
+  AlignRequest rq = full_request(nullptr, 0, out, nullptr, user);
+  cs_request(rq, max_penalty, match_bonus, vout, cout, tout, cs_mode, csout, sink);
+  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, rq);)
+}
+
 int awv_align_pairs_split(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const int32_t* max_penalty,
                           int32_t match_bonus, int64_t min_score, awv_result* out, awv_verify_result* vout, const uint64_t* seg_first,
                           awv_split_index* iout, awv_clip_result* sout, awv_sink sink, void* user) {
@@ -1510,6 +1593,7 @@ awvc::State*& awv_internal_clip(awv_engine* e) { return e->clip; }
 awvs::State*& awv_internal_split(awv_engine* e) { return e->split; }
 awvn::State*& awv_internal_normalize(awv_engine* e) { return e->normalize; }
 awve::State*& awv_internal_encode(awv_engine* e) { return e->encode; }
+awvx::State*& awv_internal_cs(awv_engine* e) { return e->cs; }
 int32_t& awv_internal_normalize_mode(awv_engine* e) { return e->norm_mode; }
 uint64_t awv_internal_max_arena(const awv_engine* e) { return e->cfg.max_arena_bytes > 0 ? (uint64_t)e->cfg.max_arena_bytes : (uint64_t)8 << 30; }
 int awv_internal_fail(int code, const std::string& msg) { return fail(code, msg); }

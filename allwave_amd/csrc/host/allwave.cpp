@@ -363,6 +363,7 @@ void align_ranges(const std::vector<Sequence>& sequences, const std::vector<Alig
 void RunOptions::apply(AllPairIterator& it) const {
   if (normalize != AWV_NORM_OFF) it.with_normalize(normalize);
   if (device_cigar) it.with_device_cigar(true);
+  if (cs != 0) it.with_cs(cs);
   if (max_penalty) it.with_max_penalty(*max_penalty);
   if (max_divergence) it.with_max_divergence(*max_divergence);
   if (clip_match_bonus != 0) it.with_clip(clip_match_bonus, clip_min_score);
@@ -539,11 +540,18 @@ AllPairIterator AllPairIterator::with_sparsification(SparsificationStrategy stra
   it.split_min_score_ = split_min_score_;
   it.normalize_ = normalize_;
   it.device_cigar_ = device_cigar_;
+  it.cs_ = cs_;
   return it;
 }
 AllPairIterator& AllPairIterator::with_device_cigar(bool on) {
   if (on && split()) throw std::invalid_argument("with_device_cigar: not together with with_split");
   device_cigar_ = on;
+  return *this;
+}
+AllPairIterator& AllPairIterator::with_cs(int mode) {
+  if (mode != 0 && mode != AWV_CS_SHORT && mode != AWV_CS_LONG) throw std::invalid_argument("with_cs: 0, AWV_CS_SHORT or AWV_CS_LONG");
+  if (mode != 0 && split()) throw std::invalid_argument("with_cs: not together with with_split");
+  cs_ = mode;
   return *this;
 }
 AllPairIterator& AllPairIterator::with_normalize(int direction) {
@@ -566,6 +574,7 @@ AllPairIterator& AllPairIterator::with_split(int match_bonus, int64_t min_score)
   if (min_score < 1) throw std::invalid_argument("with_split: min_score must be >= 1");
   if (clip()) throw std::invalid_argument("with_split: not together with with_clip");
   if (device_cigar_) throw std::invalid_argument("with_split: not together with with_device_cigar");
+  if (cs_ != 0) throw std::invalid_argument("with_split: not together with with_cs");
   split_bonus_ = match_bonus;
   split_min_score_ = min_score;
   return *this;
@@ -748,6 +757,13 @@ void add(awv_encode_stats& acc, const awv_encode_stats& x) {
   acc.text_bytes += x.text_bytes;
   acc.columns += x.columns;
 }
+void add(awv_cs_stats& acc, const awv_cs_stats& x) {
+  acc.kernel_ms += x.kernel_ms;
+  acc.pairs += x.pairs;
+  acc.failed += x.failed;
+  acc.text_bytes += x.text_bytes;
+  acc.columns += x.columns;
+}
 void add(RunReport& acc, const RunReport& x) {
   acc.verify_failures.insert(acc.verify_failures.end(), x.verify_failures.begin(), x.verify_failures.end());
   add(acc.verify_stats, x.verify_stats);
@@ -756,12 +772,14 @@ void add(RunReport& acc, const RunReport& x) {
   add(acc.split_stats, x.split_stats);
   add(acc.normalize_stats, x.normalize_stats);
   add(acc.encode_stats, x.encode_stats);
+  add(acc.cs_stats, x.cs_stats);
 }
 
 // One batch's engine call, by name.  ranges (nullable): the batch is these n interval pairs, `pairs` is not read.  Alignment
 // calls only: verify (nullable), bounds (nullable: one penalty bound per entry, < 0: none), clip (nullable: the clips, under
 // clip_bonus), seg_first (nullable: the split under split_bonus / split_min_score, into index and seg), text (nullable: the
-// texts of the call's _encoded form -- not with a split).
+// texts of the call's _encoded form -- not with a split), cs (nullable: the cs texts of the call's _cs form under cs_mode, which
+// takes the text too -- not with a split).
 struct EngineRequest {
   bool score_only = false;
   int32_t max_penalty = -1;  // the score call's bound (< 0: none)
@@ -779,14 +797,19 @@ struct EngineRequest {
   awv_split_index* index = nullptr;
   awv_clip_result* seg = nullptr;
   awv_cigar_text* text = nullptr;
+  int cs_mode = 0;
+  awv_cs_text* cs = nullptr;
 };
 
-// The entry point a request names: the encoded call (which takes the bounds, the check and the clip), else the split, else the clip, else the bounded call, else the verified or the plain one, each
+// The entry point a request names: the cs call (which takes all the encoded call does, and cs_sink as its sink), else the encoded call (which takes the bounds, the check and the clip), else the split, else the clip, else the bounded call, else the verified or the plain one, each
 // on pairs or on ranges (they differ in which engine counters they reset); or awv_score_pairs / awv_score_ranges with the
 // results handed to the sink in one call (status and penalty, no arena).
-int engine_call(awv_engine* e, const EngineRequest& q, awv_sink sink, void* user) {
+int engine_call(awv_engine* e, const EngineRequest& q, awv_sink sink, awv_cs_sink cs_sink, void* user) {
   const awv_penalties* pen = q.pen;
   const int64_t n = q.n;
+  if (q.cs && !q.score_only)
+    return q.ranges ? awv_align_ranges_cs(e, pen, q.ranges, n, q.bounds, q.clip ? q.clip_bonus : 0, nullptr, q.verify, q.clip, q.text, q.cs_mode, q.cs, cs_sink, user)
+                    : awv_align_pairs_cs(e, pen, q.pairs, n, q.bounds, q.clip ? q.clip_bonus : 0, nullptr, q.verify, q.clip, q.text, q.cs_mode, q.cs, cs_sink, user);
   if (q.text && !q.score_only)
     return q.ranges ? awv_align_ranges_encoded(e, pen, q.ranges, n, q.bounds, q.clip ? q.clip_bonus : 0, nullptr, q.verify, q.clip, q.text, sink, user)
                     : awv_align_pairs_encoded(e, pen, q.pairs, n, q.bounds, q.clip ? q.clip_bonus : 0, nullptr, q.verify, q.clip, q.text, sink, user);
@@ -828,10 +851,11 @@ struct AllPairIterator::RunState {
   size_t first = 0, count = 0;
   const std::pair<size_t, size_t>* plist = nullptr;  // pairs_.data() + first
   const BatchCb* batch_cb = nullptr;
-  EngineCall call{false, -1, false};
+  EngineCall call{false, -1, false, 0};
   std::vector<std::vector<size_t>> batches;  // pair indices (relative to `first`) of each batch; one slot's single batch: empty, the whole range
   std::vector<uint8_t> mash_rev;             // mash orientation of the whole range, computed up front
   bool verify = false, bounded = false, clipping = false, splitting = false, encoding = false;
+  int cs = 0;  // the cs mode of the run's alignment calls (0: none)
   int normalizing = AWV_NORM_OFF;
   std::optional<double> div;  // the divergence bound of a bounded run
   awv_penalties pen{}, open{};
@@ -865,6 +889,7 @@ struct AllPairIterator::PreparedBatch {
   std::vector<awv_verify_result> vr;
   std::vector<awv_clip_result> cr;
   std::vector<awv_cigar_text> tx;
+  std::vector<awv_cs_text> cx;
   // a splitting run: this call's segment storage, laid out by the engine's own arithmetic over the resident lengths
   std::vector<uint64_t> seg_first;
   std::vector<awv_split_index> six;
@@ -958,6 +983,12 @@ AllPairIterator::PreparedBatch AllPairIterator::prepare_batch(const RunState& rs
     q.text = pb.tx.data();
     d.text = pb.tx.data();
   }
+  if (rs.cs != 0) {
+    pb.cx.resize((size_t)std::max<int64_t>(m, 1));
+    q.cs_mode = rs.cs;
+    q.cs = pb.cx.data();
+    d.cs = pb.cx.data();
+  }
   return pb;
 }
 
@@ -969,15 +1000,19 @@ struct AllPairIterator::SinkCtx {
   bool failed;
 };
 int AllPairIterator::batch_sink(void* user, int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena) {
+  return batch_cs_sink(user, first, cnt, res, arena, nullptr);
+}
+// (the sink of a cs call: the same, with the call's cs arena)
+int AllPairIterator::batch_cs_sink(void* user, int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena, const uint8_t* cs_arena) {
   SinkCtx* c = (SinkCtx*)user;
   if (c->rs->stop.load()) return 1;  // another slot failed: stop here, report nothing
   try {
     if (c->d->filters()) {
       const Delivered k = deliver(*c->d, first, cnt, res);
       (*c->rs->batch_cb)(Batch{0, (int64_t)k.res.size(), k.res.data(), arena, k.rev.data(), k.idx.data(), k.clip.empty() ? nullptr : k.clip.data(),
-                               k.text.empty() ? nullptr : k.text.data()});
+                               k.text.empty() ? nullptr : k.text.data(), k.cs.empty() ? nullptr : k.cs.data(), cs_arena});
     } else {
-      (*c->rs->batch_cb)(Batch{first, cnt, res, arena, c->d->rev, c->d->idx, nullptr, c->d->text});
+      (*c->rs->batch_cb)(Batch{first, cnt, res, arena, c->d->rev, c->d->idx, nullptr, c->d->text, c->d->cs, cs_arena});
     }
   } catch (...) {
     c->rs->fail(std::current_exception());  // recorded now, and every slot stops at its next sink call
@@ -999,6 +1034,11 @@ void AllPairIterator::take_call_totals(const RunState& rs, const PreparedBatch& 
     awv_encode_stats ex{};
     awv_engine_encode_stats(e, &ex);
     add(t.report.encode_stats, ex);
+  }
+  if (rs.cs != 0 && ok) {
+    awv_cs_stats cx{};
+    awv_engine_cs_stats(e, &cx);
+    add(t.report.cs_stats, cx);
   }
   awv_stats x{};
   awv_engine_stats(e, &x);
@@ -1060,6 +1100,7 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   rs.clipping = clip() && !call.score_only;
   rs.splitting = split() && !call.score_only;
   rs.encoding = call.encode && !call.score_only;
+  rs.cs = call.score_only ? 0 : call.cs;
   rs.normalizing = call.score_only ? AWV_NORM_OFF : normalize_;
   rs.div = divergence_bound();
   rs.pen = to_penalties(params_);
@@ -1092,7 +1133,7 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
         SinkCtx ctx{&rs, &pb.delivery, false};
         // the slot's engine is this thread's until its device lock goes: the mode holds for this call and is off again after it
         if (rs.normalizing != AWV_NORM_OFF && awv_engine_set_normalize(e, rs.normalizing) != AWV_OK) throw AlignmentError(std::string("normalize: ") + awv_last_error());
-        const int rc = engine_call(e, pb.request, batch_sink, &ctx);
+        const int rc = engine_call(e, pb.request, batch_sink, batch_cs_sink, &ctx);
         if (rs.normalizing != AWV_NORM_OFF) awv_engine_set_normalize(e, AWV_NORM_OFF);
         rs.lap("aligned + sunk");
         take_call_totals(rs, pb, e, rc == AWV_OK, rs.totals[s]);
@@ -1170,6 +1211,10 @@ void AllPairIterator::for_each_paf_batch(const std::function<void(const std::str
           const bool ok = res[i].status == AWV_ST_COMPLETED;
           if (const awv_cigar_text* tx = b.text_at(i)) append_paf_text(out, a, tx->len ? arena + tx->off : nullptr, tx->len, sequences_);
           else append_paf(out, a, ok ? arena + res[i].cigar_off : nullptr, ok ? res[i].cigar_len : 0, sequences_);
+          if (const awv_cs_text* cx = b.cs_at(i)) {
+            out += "\tcs:Z:";
+            if (cx->len) out.append((const char*)b.cs_arena + cx->off, cx->len);
+          }
           out.push_back('\n');
         }
       });
@@ -1186,7 +1231,7 @@ void AllPairIterator::for_each_paf_batch(const std::function<void(const std::str
       first = std::current_exception();
       throw;
     }
-  }, EngineCall{false, -1, device_cigar_});
+  }, EngineCall{false, -1, device_cigar_, cs_});
 }
 
 std::vector<PairScore> AllPairIterator::scores(std::optional<int> max_penalty) {
@@ -1202,7 +1247,7 @@ std::vector<PairScore> AllPairIterator::scores(std::optional<int> max_penalty) {
       p.status = b.res[i].status;
       p.penalty = b.res[i].penalty;
     }
-  }, EngineCall{true, max_penalty ? *max_penalty : -1, false});
+  }, EngineCall{true, max_penalty ? *max_penalty : -1, false, 0});
   return out;
 }
 

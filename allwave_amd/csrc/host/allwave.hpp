@@ -147,7 +147,7 @@ class AllPairIterator;
 
 // The options of one run that filter or rewrite what it delivers, in one place: AllPairIterator::with_max_penalty,
 // with_max_divergence (std::nullopt: no bound), with_clip and with_split (match bonus 0: off), with_normalize (AWV_NORM_OFF: off),
-// with_device_cigar.
+// with_device_cigar, with_cs (0: off).
 struct RunOptions {
   std::optional<int> max_penalty;
   std::optional<double> max_divergence;
@@ -157,8 +157,9 @@ struct RunOptions {
   int64_t split_min_score = 1;
   int normalize = AWV_NORM_OFF;
   bool device_cigar = false;
+  int cs = 0;
   void apply(AllPairIterator& it) const;  // the with_* calls of what is set; they throw std::invalid_argument as documented there
-  bool any() const { return max_penalty || max_divergence || clip_match_bonus != 0 || split_match_bonus != 0 || normalize != AWV_NORM_OFF || device_cigar; }
+  bool any() const { return max_penalty || max_divergence || clip_match_bonus != 0 || split_match_bonus != 0 || normalize != AWV_NORM_OFF || device_cigar || cs != 0; }
 };
 
 // What a run leaves behind besides its results (AllPairIterator::last_report): the failed checks sorted by pair-list index,
@@ -171,6 +172,7 @@ struct RunReport {
   SplitStats split_stats{};
   awv_norm_stats normalize_stats{};
   awv_encode_stats encode_stats{};
+  awv_cs_stats cs_stats{};
 };
 
 class AllPairIterator {  // iterator.rs:12-171
@@ -266,6 +268,16 @@ class AllPairIterator {  // iterator.rs:12-171
   bool device_cigar() const { return device_cigar_; }
   // of the last run, summed over the slots (kernel_ms: summed kernel time)
   awv_encode_stats last_encode_stats() const { return report_.encode_stats; }
+  // for_each_paf_batch appends minimap2's cs difference string to every line, "\tcs:Z:<text>" after the cg:Z: field
+  // (AWV_CS_SHORT / AWV_CS_LONG; 0: off; awv_align_pairs_cs / awv_align_ranges_cs, include/allwave_hip.h has the contract): the
+  // text is made on the device from each batch's op strings -- normalized, and clipped, when those are set -- and the resident
+  // sequences, and copied back next to the CIGARs.  The line up to the tag is the line without the setting.  The consumers that
+  // hand out AlignmentResults (for_each_with_callback, next, into_par_iter, collect) and scores() ignore it.  Not together with
+  // with_split (std::invalid_argument).
+  AllPairIterator& with_cs(int mode);
+  int cs() const { return cs_; }
+  // of the last run, summed over the slots (kernel_ms: summed kernel time)
+  awv_cs_stats last_cs_stats() const { return report_.cs_stats; }
   AllPairIterator& with_max_penalty(int max_penalty);
   AllPairIterator& with_max_divergence(double max_divergence);
   // of the last run (next(): of the chunks since the list's start), summed over the slots
@@ -319,24 +331,29 @@ class AllPairIterator {  // iterator.rs:12-171
     const awv_clip_result* clip = nullptr;  // a clipping run: per entry its clip; res[] then describes the segment
     const awv_cigar_text* text = nullptr;   // an encoding run: per entry its text; `arena` is then the call's text arena
     const awv_cigar_text* text_at(int64_t i) const { return text ? text + first + i : nullptr; }
+    const awv_cs_text* cs = nullptr;        // a cs run: per entry its cs text, in the call's cs arena
+    const uint8_t* cs_arena = nullptr;
+    const awv_cs_text* cs_at(int64_t i) const { return cs ? cs + first + i : nullptr; }
     size_t pair(int64_t i) const { return idx ? idx[first + i] : (size_t)(first + i); }
     const awv_clip_result* clip_at(int64_t i) const { return clip ? clip + first + i : nullptr; }
     bool is_rev(int64_t i) const { return rev[first + i] != 0; }
   };
   using BatchCb = std::function<void(const Batch&)>;
   // The engine call a run makes per batch: an alignment call, or awv_score_pairs under max_penalty (< 0: no bound; one sink
-  // call per batch, results carry status and penalty, no arena); encode: the alignment call's _encoded form (with_device_cigar).
+  // call per batch, results carry status and penalty, no arena); encode: the alignment call's _encoded form (with_device_cigar);
+  // cs: its _cs form under that mode (with_cs), which takes the encoding too.
   struct EngineCall {
     bool score_only;
     int32_t max_penalty;
     bool encode;
+    int cs;
   };
   // pairs_[first, first + count) on the with_devices slots; batch indices are relative to `first`.  Per batch: orientation,
   // one engine call, the batch callback, the counters.  One slot: one batch, the whole range in list order, on the calling
   // thread.  With several slots, batch callbacks of different slots run concurrently: consumers that call user code
   // serialise it.
-  void run(size_t first, size_t count, const BatchCb& batch_cb, EngineCall call = {false, -1, false});
-  void run(const BatchCb& batch_cb, EngineCall call = {false, -1, false}) { run(0, pairs_.size(), batch_cb, call); }
+  void run(size_t first, size_t count, const BatchCb& batch_cb, EngineCall call = {false, -1, false, 0});
+  void run(const BatchCb& batch_cb, EngineCall call = {false, -1, false, 0}) { run(0, pairs_.size(), batch_cb, call); }
   // run()'s steps (allwave.cpp): what the slots of one run share and what each of them counts; one batch made ready for its
   // engine call; the engine's sink, which hands a call's results to the batch callback; the counters taken after a call
   struct RunState;
@@ -345,6 +362,7 @@ class AllPairIterator {  // iterator.rs:12-171
   struct SinkCtx;
   PreparedBatch prepare_batch(const RunState& rs, awv_engine* e, size_t b, SlotTotals& totals) const;
   static int batch_sink(void* user, int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena);
+  static int batch_cs_sink(void* user, int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena, const uint8_t* cs_arena);
   static void take_call_totals(const RunState& rs, const PreparedBatch& pb, awv_engine* e, bool ok, SlotTotals& totals);
   // run(first, count) into one result per delivered entry, in pair-list order: a pair's segments in column order (with_split),
   // the pairs a run drops left out
@@ -370,6 +388,7 @@ class AllPairIterator {  // iterator.rs:12-171
   int64_t clip_min_score_ = 1;
   int normalize_ = AWV_NORM_OFF;  // with_normalize
   bool device_cigar_ = false;     // with_device_cigar
+  int cs_ = 0;                    // with_cs (0: off)
   int split_bonus_ = 0;  // with_split (0: off)
   int64_t split_min_score_ = 1;
   bool drops_pairs() const { return bounded() || clip() || split(); }  // consumers that keep a slot per pair compact what was delivered
@@ -405,6 +424,7 @@ class AllPairParallelIterator {
   SplitStats last_split_stats() const { return it_.last_split_stats(); }
   awv_norm_stats last_normalize_stats() const { return it_.last_normalize_stats(); }
   awv_encode_stats last_encode_stats() const { return it_.last_encode_stats(); }
+  awv_cs_stats last_cs_stats() const { return it_.last_cs_stats(); }
   const RunReport& last_report() const { return it_.last_report(); }
  private:
   friend class AllPairIterator;

@@ -18,14 +18,14 @@ void set_err(char* err, size_t cap, const std::string& m) {
   if (err && cap) snprintf(err, cap, "%s", m.c_str());
 }
 // What the calling thread's last alignment hook left behind, its iterator's last_report(): the verify counters and failures
-// for awh_last_verify, the other counters for awh_last_bounds, awh_last_clip, awh_last_split, awh_last_normalize and awh_last_encode.
+// for awh_last_verify, the other counters for awh_last_bounds, awh_last_clip, awh_last_split, awh_last_normalize, awh_last_encode and awh_last_cs.
 thread_local RunReport g_report;
 template <typename It>
 void keep(const It& it) {
   g_report = it.last_report();
 }
 // The options of the calling thread's NEXT alignment hook: awh_set_bounds, awh_set_clip, awh_set_split, awh_set_normalize and
-// awh_set_device_cigar
+// awh_set_device_cigar, awh_set_cs
 // leave them here; the hook takes them (they hold for that one call) and starts the counters they go with afresh.
 thread_local RunOptions g_next;
 RunOptions take_run_options() {
@@ -36,6 +36,7 @@ RunOptions take_run_options() {
   g_report.split_stats = SplitStats{};
   g_report.normalize_stats = awv_norm_stats{};
   g_report.encode_stats = awv_encode_stats{};
+  g_report.cs_stats = awv_cs_stats{};
   return o;
 }
 // the hooks' orientation code on an iterator: 0 forward, 1 WFA, 2 mash, 3 WFA by two full alignments per pair
@@ -128,7 +129,7 @@ int awh_all_pairs_paf_devices(int n, const char* const* ids, const uint8_t* byte
     it.with_verify(verify != 0);
     opts.apply(it);
     std::string all;
-    if (opts.device_cigar) {  // the consumer that takes the device's text: whole formatted batches
+    if (opts.device_cigar || opts.cs != 0) {  // the consumer that takes the device's text: whole formatted batches
       it.for_each_paf_batch([&](const std::string& chunk) { all += chunk; });
     } else {
       it.for_each_with_callback([&](AlignmentResult&& r) {  // the reference's own per-record path
@@ -590,7 +591,7 @@ int awh_align_ranges_paf(int n, const char* const* ids, const uint8_t* bytes, co
     it.with_devices(std::vector<int>(devices, devices + n_devices)).with_verify(verify != 0);
     opts.apply(it);
     std::string all;
-    if (opts.device_cigar) {  // the consumer that takes the device's text (in list order on one slot, in batch order on several)
+    if (opts.device_cigar || opts.cs != 0) {  // the consumer that takes the device's text (in list order on one slot, in batch order on several)
       it.for_each_paf_batch([&](const std::string& chunk) { all += chunk; });
       keep(it);
     } else {
@@ -682,6 +683,17 @@ void awh_set_normalize(int direction) { g_next.normalize = direction; }
 // awh_all_pairs_paf_count_devices, awh_align_ranges_paf) then go through for_each_paf_batch; awh_iterate_devices' consumers hand
 // out op bytes and ignore it.
 void awh_set_device_cigar(int on) { g_next.device_cigar = on != 0; }
+// The calling thread's NEXT alignment hook runs with_cs(mode) (AWV_CS_SHORT / AWV_CS_LONG; 0: off).  The hooks that format PAF then
+// go through for_each_paf_batch, as under awh_set_device_cigar; awh_iterate_devices' consumers ignore it.
+void awh_set_cs(int mode) { g_next.cs = mode; }
+// last_cs_stats() of the calling thread's last alignment hook: {pairs, failed, text_bytes, columns} and the summed kernel time
+void awh_last_cs(uint64_t out[4], double* kernel_ms) {
+  out[0] = g_report.cs_stats.pairs;
+  out[1] = g_report.cs_stats.failed;
+  out[2] = g_report.cs_stats.text_bytes;
+  out[3] = g_report.cs_stats.columns;
+  *kernel_ms = g_report.cs_stats.kernel_ms;
+}
 // last_encode_stats() of the calling thread's last alignment hook: {pairs, runs, text_bytes, columns} and the summed kernel time
 void awh_last_encode(uint64_t out[4], double* kernel_ms) {
   out[0] = g_report.encode_stats.pairs;

@@ -69,18 +69,21 @@ struct Delivery {
   SplitStats* splits = nullptr;
   // an encoding run (text != nullptr): the entry's run-length text in the sink call's text arena -- of the clip in a clipping run
   const awv_cigar_text* text = nullptr;
+  // a cs run (cs != nullptr): the entry's cs text in the sink call's cs arena -- of the clip in a clipping run
+  const awv_cs_text* cs = nullptr;
 
   bool filters() const { return bounds || clips || splits; }  // false: every entry is delivered as it is, nothing is copied
 };
 
 // What one sink call delivers: the kept records, their strands and pair-list indices and, in a clipping or splitting run,
-// their clips (else empty) and, in an encoding run, their texts (else empty).
+// their clips (else empty), in an encoding run their texts (else empty) and, in a cs run, their cs texts (else empty).
 struct Delivered {
   std::vector<awv_result> res;
   std::vector<uint8_t> rev;
   std::vector<size_t> idx;
   std::vector<awv_clip_result> clip;
   std::vector<awv_cigar_text> text;
+  std::vector<awv_cs_text> cs;
 };
 
 // The rule, entry by entry in call order, for a run that filters(); counts into the Delivery's stats.
@@ -92,6 +95,7 @@ inline Delivered deliver(const Delivery& d, int64_t first, int64_t cnt, const aw
     out.idx.push_back(d.idx ? d.idx[e] : (size_t)e);
     if (cl) out.clip.push_back(*cl);
     if (d.text) out.text.push_back(d.text[e]);
+    if (d.cs) out.cs.push_back(d.cs[e]);
   };
   for (int64_t i = 0; i < cnt; ++i) {
     const awv_result& r = res[i];

@@ -57,6 +57,7 @@ struct Args {
   int normalize = AWV_NORM_OFF;  // --normalize left|right: every alignment's gap runs moved to their left- / right-normal place
   bool have_normalize = false;
   bool device_cigar = false;  // --device-cigar: the run-length text behind cg:Z: is made on the device
+  int cs = 0;                 // --cs short|long: every line gains minimap2's cs:Z: tag, made on the device (0: off)
 };
 
 [[noreturn]] void die(const std::string& m, int code = 2) {
@@ -249,6 +250,11 @@ int main(int argc, char** argv) {
       a.have_normalize = true;
     }
     else if (k == "--device-cigar") a.device_cigar = true;
+    else if (k == "--cs") {
+      const std::string v = val();
+      if (v != "short" && v != "long") die("--cs expects short or long");
+      a.cs = v == "short" ? AWV_CS_SHORT : AWV_CS_LONG;
+    }
     else if (k == "--clip" || k == "--clip-min-score") {
       const std::string v = val();
       char* end = nullptr;
@@ -283,11 +289,11 @@ int main(int argc, char** argv) {
                    "                   [-t threads] [--wfa-orientation|--wfa-orientation-full|--forward-only] [-k prefixes | -e prefixes] [--mash-matrix]\n"
                    "                   [--device N | --devices LIST] [--shard R/N] [--score-only [--max-penalty N]] [--plan-device N] [--verify]\n"
                    "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
-                   "                   [--split A --split-min-score S] [--normalize left|right] [--device-cigar]\n"
+                   "                   [--split A --split-min-score S] [--normalize left|right] [--device-cigar] [--cs short|long]\n"
                    "       allwave_hip -i in.fa --check-paf FILE [-s scores | -x ANI] [--check-optimal] [--partial] [--device N]\n"
                    "       allwave_hip -i in.fa --align-paf FILE [-s scores | -x ANI] [-o out.paf] [--verify] [--score-only] [--device N | --devices LIST]\n"
                    "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
-                   "                   [--split A --split-min-score S] [--normalize left|right] [--device-cigar]\n"
+                   "                   [--split A --split-min-score S] [--normalize left|right] [--device-cigar] [--cs short|long]\n"
                    "  --verify         check every alignment on the device before it is written (columns, counts, penalty); the summary\n"
                    "                   line gains `verified N pairs, F failed, K ms`, failures go to stderr, exit status 4 if any\n"
                    "  --check-paf FILE align nothing: check every line of FILE (12 columns + cg:Z:) against in.fa on the device; one line\n"
@@ -325,6 +331,10 @@ int main(int argc, char** argv) {
                    "  --device-cigar   make the run-length text behind cg:Z: on the device, after --normalize, --verify and --clip, and copy it\n"
                    "                   back in place of the op bytes: the PAF is byte-identical; also with --align-paf; not with --split; the\n"
                    "                   summary line gains `encoded N pairs, R runs, B text bytes, K ms`\n"
+                   "  --cs short|long  append minimap2's cs difference string to every line (cs:Z:, after cg:Z:), made on the device after\n"
+                   "                   --normalize, --verify, --clip and --device-cigar from the op string and the sequences: short writes\n"
+                   "                   :N for N matches, long =BASES; also with --align-paf; not with --split; the summary line gains\n"
+                   "                   `cs N pairs, F failed, B text bytes, K ms`\n"
                    "  --plan-device N  plan on device N: --mash-matrix, the -p pair list and mash orientation (the same output as\n"
                    "                   the host planner; with --shard every rank plans the whole list on its own plan device)\n";
       return 0;
@@ -357,6 +367,10 @@ int main(int argc, char** argv) {
   if (a.device_cigar && a.score_only) die("the argument '--device-cigar' cannot be used with '--score-only'");
   if (a.device_cigar && a.have_check_paf) die("the argument '--device-cigar' cannot be used with '--check-paf'");
   if (a.device_cigar && a.mash_matrix) die("the argument '--device-cigar' cannot be used with '--mash-matrix'");
+  if (a.cs != 0 && a.have_split) die("the argument '--cs' cannot be used with '--split'");
+  if (a.cs != 0 && a.score_only) die("the argument '--cs' cannot be used with '--score-only'");
+  if (a.cs != 0 && a.have_check_paf) die("the argument '--cs' cannot be used with '--check-paf'");
+  if (a.cs != 0 && a.mash_matrix) die("the argument '--cs' cannot be used with '--mash-matrix'");
   if (a.check_optimal && !a.have_check_paf) die("the argument '--check-optimal' requires '--check-paf'");
   if (a.verify && a.score_only) die("the argument '--verify' cannot be used with '--score-only'");
   if (a.verify && a.mash_matrix) die("the argument '--verify' cannot be used with '--mash-matrix'");
@@ -474,6 +488,7 @@ int main(int argc, char** argv) {
     if (a.have_split) it.with_split((int)a.split, (int64_t)a.split_min_score);
     if (a.have_normalize) it.with_normalize(a.normalize);
     it.with_device_cigar(a.device_cigar);
+    it.with_cs(a.cs);
     if (a.forward_only) it.with_orientation(Orientation::ForwardOnly);
     it.with_full_wfa_orientation(a.wfa_orientation_full);
     it.with_devices(devices);
@@ -558,6 +573,11 @@ int main(int argc, char** argv) {
         const awv_encode_stats es = it.last_encode_stats();
         w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", encoded %llu pairs, %llu runs, %llu text bytes, %.2f ms", (unsigned long long)es.pairs,
                       (unsigned long long)es.runs, (unsigned long long)es.text_bytes, es.kernel_ms);
+      }
+      if (a.cs != 0 && w > 0 && (size_t)w < sizeof(buf)) {
+        const awv_cs_stats xs = it.last_cs_stats();
+        w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", cs %llu pairs, %llu failed, %llu text bytes, %.2f ms", (unsigned long long)xs.pairs,
+                      (unsigned long long)xs.failed, (unsigned long long)xs.text_bytes, xs.kernel_ms);
       }
       if (a.verify && w > 0 && (size_t)w < sizeof(buf)) {
         const awv_verify_stats vs = it.last_verify_stats();

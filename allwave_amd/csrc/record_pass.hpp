@@ -1,6 +1,6 @@
 // record_pass.hpp -- the host skeleton of a record pass: a kernel with one wave per alignment record,
 // persistent waves taking records, longest op string first, from a cursor (awvw::take_record, wave_ops.hpp).  verify.hip,
-// clip.hip, split.hip, normalize.hip and encode.hip each keep a State that derives from RecordPass next to the buffers and stats only
+// clip.hip, split.hip, normalize.hip, encode.hip and cs.hip each keep a State that derives from RecordPass next to the buffers and stats only
 // that pass has; a launch is begin(), the pass's own uploads, clear_counters(), KParams, start(), the kernel, stop(),
 // the pass's own copy-backs, finish().
 #pragma once

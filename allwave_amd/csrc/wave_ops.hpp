@@ -1,4 +1,4 @@
-// wave_ops.hpp -- what the record kernels (verify.hip, clip.hip, split.hip, normalize.hip, encode.hip) share on the device: the take of
+// wave_ops.hpp -- what the record kernels (verify.hip, clip.hip, split.hip, normalize.hip, encode.hip, cs.hip) share on the device: the take of
 // the next record from the cursor, the chunk a wave reads (64 lanes x 16 op bytes), wave64 inclusive scans on the DPP network
 // and packed byte counting over a lane's 16 bytes; and the device buffer their host sides keep (record_pass.hpp).
 #pragma once

@@ -68,6 +68,13 @@ AWV_NM_OK = 0
 AWV_NM_SKIPPED = 1
 AWV_NM_BAD_OP = 2
 AWV_NM_LENGTHS = 3
+#: the cs difference string: a call's mode, and awv_cs_text.code
+AWV_CS_SHORT = 1
+AWV_CS_LONG = 2
+AWV_CST_OK = 0
+AWV_CST_SKIPPED = 1
+AWV_CST_BAD_OP = 2
+AWV_CST_LENGTHS = 3
 #: sketch kinds of device pair planning (awv_sketch)
 AWV_SK_CANONICAL = 0
 AWV_SK_FORWARD = 1
@@ -87,7 +94,8 @@ EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine
            "awv_align_pairs_split", "awv_align_ranges_split", "awv_engine_split_stats",
            "awv_normalize_one_host", "awv_normalize_cigars", "awv_normalize_ranges", "awv_engine_set_normalize",
            "awv_engine_normalize_stats",
-           "awv_encode_one_host", "awv_encode_cigars", "awv_align_pairs_encoded", "awv_align_ranges_encoded", "awv_engine_encode_stats")
+           "awv_encode_one_host", "awv_encode_cigars", "awv_align_pairs_encoded", "awv_align_ranges_encoded", "awv_engine_encode_stats",
+           "awv_cs_one_host", "awv_cs_cigars", "awv_cs_ranges", "awv_align_pairs_cs", "awv_align_ranges_cs", "awv_engine_cs_stats")
 
 
 class EngineConfig(C.Structure):
@@ -145,6 +153,10 @@ class EncodeStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("pairs", C.c_uint64), ("runs", C.c_uint64), ("text_bytes", C.c_uint64), ("columns", C.c_uint64)]
 
 
+class CsStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("pairs", C.c_uint64), ("failed", C.c_uint64), ("text_bytes", C.c_uint64), ("columns", C.c_uint64)]
+
+
 PAIR_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4")])
 #: awv_range_pair: the query interval on the query's forward strand (PAF convention), also with q_revcomp
 RANGE_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4"), ("q_beg", "<i4"), ("q_end", "<i4"),
@@ -164,6 +176,10 @@ SPLIT_INDEX_DTYPE = np.dtype([("code", "<i4"), ("count", "<i4"), ("column", "<i8
 NORM_DTYPE = np.dtype([("code", "<i4"), ("runs_moved", "<i4"), ("columns_moved", "<i8"), ("max_shift", "<i4"), ("reserved", "<i4")])
 #: awv_cigar_text: where a record's run-length text lies in its call's or batch's text arena, and its run count
 CIGAR_TEXT_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("runs", "<u4")])
+#: awv_cs_text: where a record's cs text lies in its call's or batch's cs arena, and its code
+CS_TEXT_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("code", "<i4")])
+#: awv_cs_slice: columns [col_beg, col_end) of an op string, and the bases consumed before col_beg (the fields of a clip)
+CS_SLICE_DTYPE = np.dtype([("col_beg", "<u4"), ("col_end", "<u4"), ("q_skip", "<i4"), ("t_skip", "<i4")])
 #: awv_score_result
 SCORE_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4")])
 
@@ -172,6 +188,8 @@ ORIENT_DTYPE = np.dtype([("is_reverse", "<i4"), ("how", "<i4"), ("lo_f", "<i4"),
                          ("edits_f", "<u8"), ("edits_r", "<u8"), ("rounds", "<i4"), ("reserved", "<i4")])
 
 SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p)
+#: awv_cs_sink: the sink of a cs call also takes the batch's cs arena
+CS_SINK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p)
 
 _LIB = None
 
@@ -248,8 +266,25 @@ def load():
                                               C.c_void_p, C.c_void_p, C.c_void_p, SINK_FN, C.c_void_p]
         L.awv_align_ranges_encoded.argtypes = L.awv_align_pairs_encoded.argtypes
         L.awv_engine_encode_stats.argtypes = [C.c_void_p, C.POINTER(EncodeStats)]
+        L.awv_cs_one_host.argtypes = [C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, C.c_int32, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                      C.c_void_p]
+        L.awv_cs_cigars.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_uint64, C.POINTER(C.c_uint64)]
+        L.awv_cs_ranges.argtypes = L.awv_cs_cigars.argtypes
+        L.awv_align_pairs_cs.argtypes = [C.c_void_p, C.POINTER(Penalties), C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, CS_SINK_FN, C.c_void_p]
+        L.awv_align_ranges_cs.argtypes = L.awv_align_pairs_cs.argtypes
+        L.awv_engine_cs_stats.argtypes = [C.c_void_p, C.POINTER(CsStats)]
         _LIB = L
     return _LIB
+
+
+def cs_mode(cs):
+    """None / "short" / "long" (or an AWV_CS_* value) -> 0 (off) / AWV_CS_SHORT / AWV_CS_LONG."""
+    modes = {None: 0, "short": AWV_CS_SHORT, "long": AWV_CS_LONG, AWV_CS_SHORT: AWV_CS_SHORT, AWV_CS_LONG: AWV_CS_LONG}
+    if isinstance(cs, bool) or cs not in modes:
+        raise ValueError("cs: None, 'short' or 'long', not %r" % (cs,))
+    return modes[cs]
 
 
 def norm_mode(normalize):
@@ -330,14 +365,14 @@ class Engine:
         return np.ascontiguousarray(ranges)
 
     def align_ranges(self, scores, ranges, want_cigars=True, verify=False, max_penalty=None, clip=None, _sink_hook=None, split=None,
-                     normalize=None, encode=False):
+                     normalize=None, encode=False, cs=None):
         """align_pairs on interval pairs (awv_align_ranges / awv_align_ranges_verified).  ranges: int array [n,7] (q_idx, t_idx,
         q_revcomp, q_beg, q_end, t_beg, t_end) or a RANGE_DTYPE array; the query interval is on the query's forward strand.
         The records' q_end / t_end are consumed lengths, relative to the range.  max_penalty: as for align_pairs
         (awv_align_ranges_bounded); clip, split, normalize, encode: as for align_pairs (awv_align_ranges_clipped,
-        awv_align_ranges_split, awv_align_ranges_encoded)."""
+        awv_align_ranges_split, awv_align_ranges_encoded); cs: as for align_pairs (awv_align_ranges_cs)."""
         return self._align("awv_align_ranges", scores, self._range_array(ranges), want_cigars, verify, max_penalty, clip, _sink_hook, split,
-                           normalize, encode)
+                           normalize, encode, cs)
 
     def score_ranges(self, scores, ranges, max_penalty=None):
         """score_pairs on interval pairs (awv_score_ranges).  max_penalty: None, or one bound per range (negative: none)."""
@@ -359,7 +394,7 @@ class Engine:
         return self._verify("awv_verify_ranges", scores, self._range_array(ranges), results, arena)
 
     def align_pairs(self, scores, pairs, want_cigars=True, verify=False, max_penalty=None, clip=None, _sink_hook=None, split=None,
-                    normalize=None, encode=False):
+                    normalize=None, encode=False, cs=None):
         """pairs: int array [n,2] (q,t) or [n,3] (q,t,revcomp), or a PAIR_DTYPE array.
         Returns (results structured array, list of op-byte strings or None); verify=True: every finished pair is checked on
         the device (awv_align_pairs_verified) and a VERIFY_DTYPE array comes back as a third value.
@@ -384,9 +419,14 @@ class Engine:
         back in the op bytes' place: the second value is the list of texts (bytes; b"" for a pair that is not completed or has
         no clip; None throughout without want_cigars or under AWV_F_KEEP_ON_DEVICE), and one more value comes last, the
         CIGAR_TEXT_DTYPE array (offsets relative to each batch's text arena).  Records, the verify and the clip arrays are the
-        call's without encode; encode_stats() reports."""
+        call's without encode; encode_stats() reports.
+        cs="short" / "long": every finished pair's cs difference string -- of the normalized string, and of the clip's segment,
+        when those are asked for -- is made on the device (awv_align_pairs_cs; not together with split).  One more value comes
+        back, last of all: (texts, csout), the list of cs texts (bytes; b"" for a pair without one; None without want_cigars or
+        under AWV_F_KEEP_ON_DEVICE) and the CS_TEXT_DTYPE array (offsets relative to each batch's cs arena).  Everything else
+        is the call's without cs; cs_stats() reports."""
         return self._align("awv_align_pairs", scores, self._pair_array(pairs), want_cigars, verify, max_penalty, clip, _sink_hook, split,
-                           normalize, encode)
+                           normalize, encode, cs)
 
     def split_layout(self, pairs_or_ranges, match_bonus, min_score):
         """awv_split_layout_pairs / awv_split_layout_ranges: seg_first (uint64, n + 1) for a PAIR_DTYPE / RANGE_DTYPE array (or
@@ -412,17 +452,17 @@ class Engine:
             raise EngineError(rc, "awv_engine_set_normalize")
 
     def _align(self, fn, scores, pairs, want_cigars, verify, max_penalty=None, clip=None, _sink_hook=None, split=None, normalize=None,
-               encode=False):
+               encode=False, cs=None):
         """_align_plain under the engine mode `normalize` (None: the mode is left alone)."""
         if norm_mode(normalize) == AWV_NORM_OFF:
-            return self._align_plain(fn, scores, pairs, want_cigars, verify, max_penalty, clip, _sink_hook, split, encode)
+            return self._align_plain(fn, scores, pairs, want_cigars, verify, max_penalty, clip, _sink_hook, split, encode, cs)
         self.set_normalize(normalize)
         try:
-            return self._align_plain(fn, scores, pairs, want_cigars, verify, max_penalty, clip, _sink_hook, split, encode)
+            return self._align_plain(fn, scores, pairs, want_cigars, verify, max_penalty, clip, _sink_hook, split, encode, cs)
         finally:
             self.set_normalize(None)
 
-    def _align_plain(self, fn, scores, pairs, want_cigars, verify, max_penalty=None, clip=None, _sink_hook=None, split=None, encode=False):
+    def _align_plain(self, fn, scores, pairs, want_cigars, verify, max_penalty=None, clip=None, _sink_hook=None, split=None, encode=False, cs=None):
         """awv_align_pairs / awv_align_ranges (`fn`; verify: its _verified variant; max_penalty: its _bounded variant; clip: its
         _clipped variant, which takes the other two as well) on a contiguous PAIR_DTYPE / RANGE_DTYPE array."""
         pen = scores if isinstance(scores, Penalties) else Penalties.from_scores(scores)
@@ -443,6 +483,11 @@ class Engine:
         tres = np.zeros(max(len(pairs), 1), dtype=CIGAR_TEXT_DTYPE)[:len(pairs)] if encode else None
         if encode and split is not None:
             raise ValueError("encode and split exclude each other")
+        mode = cs_mode(cs)
+        if mode and split is not None:
+            raise ValueError("cs and split exclude each other")
+        csres = np.zeros(max(len(pairs), 1), dtype=CS_TEXT_DTYPE)[:len(pairs)] if mode else None
+        cs_texts = [None] * len(pairs) if mode and want_cigars else None
         if split is not None:
             if clip is not None:
                 raise ValueError("split and clip exclude each other")
@@ -467,6 +512,24 @@ class Engine:
                         cigars[first + i] = C.string_at(arena + int(r["cigar_off"][i]), int(r["cigar_len"][i]))
             return 0
 
+        def _cs_sink(user, first, n, rptr, arena, cs_arena):
+            if cs_texts is not None and cs_arena:
+                for i in range(first, first + n):
+                    cs_texts[i] = C.string_at(cs_arena + int(csres["off"][i]), int(csres["len"][i]))
+            return _sink(user, first, n, rptr, arena)
+
+        if mode:
+            fn_x = fn + "_cs"
+            cb = CS_SINK_FN(_cs_sink) if want_cigars or (_sink_hook is not None and cres is not None) else CS_SINK_FN()
+            vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)] if verify else None
+            rc = getattr(load(), fn_x)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), None if bounds is None else bounds.ctypes.data,
+                                       0 if clip is None else int(clip), res.ctypes.data, vres.ctypes.data if verify else None,
+                                       None if cres is None else cres.ctypes.data, None if tres is None else tres.ctypes.data, mode,
+                                       csres.ctypes.data, cb, None)
+            if rc != AWV_OK:
+                raise EngineError(rc, fn_x)
+            return (res, cigars) + ((vres,) if verify else ()) + ((cres,) if cres is not None else ()) + ((tres,) if tres is not None else ()) + \
+                ((cs_texts, csres),)
         cb = SINK_FN(_sink) if want_cigars or (_sink_hook is not None and (cres is not None or sp is not None)) else SINK_FN()
         if sp is not None:
             fn_s = fn + "_split"
@@ -596,6 +659,68 @@ class Engine:
         text = np.full(max(int(text_cap), 1), 0xff, dtype=np.uint8)
         call(text, int(text_cap))
         return text[:int(text_cap)], tout, int(total.value)
+
+    def cs_cigars(self, cs, pairs, results, arena, slices=None, want_text=True, text_cap=None):
+        """awv_cs_cigars: the cs texts ("short" / "long") of caller-supplied records (a RESULT_DTYPE array whose cigar_off /
+        cigar_len point into `arena`, bytes or a uint8 array) against the resident sequences, made on the device.  slices: None,
+        or a CS_SLICE_DTYPE array (or [n, 4] integers: col_beg, col_end, q_skip, t_skip).  Returns (texts, csout, text_bytes):
+        the cs arena as a uint8 array, a CS_TEXT_DTYPE array and the arena's size.  want_text=False is the measuring call
+        (text_buf == NULL, text_cap == 0) and gives texts None; text_cap: the buffer's size (default: measured first, so that it
+        fits) -- a buffer smaller than text_bytes is left untouched and comes back as it was, filled with 0xff."""
+        return self._cs("awv_cs_cigars", cs, self._pair_array(pairs), results, arena, slices, want_text, text_cap)
+
+    def cs_ranges(self, cs, ranges, results, arena, slices=None, want_text=True, text_cap=None):
+        """cs_cigars on interval pairs (awv_cs_ranges)."""
+        return self._cs("awv_cs_ranges", cs, self._range_array(ranges), results, arena, slices, want_text, text_cap)
+
+    def _cs(self, fn, cs, pairs, results, arena, slices, want_text, text_cap):
+        mode = cs if isinstance(cs, int) and not isinstance(cs, bool) else cs_mode(cs)  # (an integer goes through as it is: the library refuses a bad one)
+        results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+        if results.shape != (len(pairs),):
+            raise ValueError("results: need one record per pair")
+        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
+        nbytes = int(arena.size)
+        if nbytes == 0:
+            arena = np.zeros(1, dtype=np.uint8)
+        sl = None
+        if slices is not None:
+            if isinstance(slices, np.ndarray) and slices.dtype == CS_SLICE_DTYPE:
+                sl = np.ascontiguousarray(slices)
+            else:
+                raw = np.asarray(slices, dtype=np.int64).reshape(-1, 4)
+                sl = np.zeros(len(raw), dtype=CS_SLICE_DTYPE)
+                for k, name in enumerate(("col_beg", "col_end", "q_skip", "t_skip")):
+                    sl[name] = raw[:, k]
+            if sl.shape != (len(results),):
+                raise ValueError("slices: need one slice per record")
+            sl = sl if len(sl) else np.zeros(1, dtype=CS_SLICE_DTYPE)
+        csout = np.zeros(max(len(results), 1), dtype=CS_TEXT_DTYPE)[:len(results)]
+        total = C.c_uint64(0)
+
+        def call(buf, cap):
+            rc = getattr(load(), fn)(self._h, mode, pairs.ctypes.data, len(pairs), results.ctypes.data, arena.ctypes.data, nbytes,
+                                     None if sl is None else sl.ctypes.data, csout.ctypes.data, None if buf is None else buf.ctypes.data, cap,
+                                     C.byref(total))
+            if rc != AWV_OK:
+                raise EngineError(rc, fn)
+
+        if not want_text:
+            call(None, 0)
+            return None, csout, int(total.value)
+        if text_cap is None:
+            call(None, 0)
+            text_cap = int(total.value)
+        text = np.full(max(int(text_cap), 1), 0xff, dtype=np.uint8)
+        call(text, int(text_cap))
+        return text[:int(text_cap)], csout, int(total.value)
+
+    def cs_stats(self):
+        """awv_engine_cs_stats: kernel_ms, pairs, failed, text_bytes, columns of the last cs call."""
+        st = CsStats()
+        rc = load().awv_engine_cs_stats(self._h, C.byref(st))
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_engine_cs_stats")
+        return st
 
     def encode_stats(self):
         """awv_engine_encode_stats: kernel_ms, pairs, runs, text_bytes, columns of the last encoding call."""
@@ -792,6 +917,27 @@ def encode_one_host(cigar, cap=None):
     rc = load().awv_encode_one_host(cigar, len(cigar), buf, size, out.ctypes.data)
     if rc != AWV_OK:
         raise EngineError(rc, "awv_encode_one_host")
+    n = int(out[0]["len"])
+    return (buf.raw[:n] if n <= size else b""), out[0]
+
+
+def cs_one_host(cs, pattern, text, cigar, slice=None, cap=None):
+    """awv_cs_one_host: the cs text ("short" / "long") of an op string over `pattern` and `text` on the host (needs no device;
+    the yardstick the kernels are tested against).  slice: None, or (col_beg, col_end, q_skip, t_skip).  Returns (text, one
+    CS_TEXT_DTYPE record); cap: the buffer's size (default: enough) -- with a buffer too small for the text nothing is written
+    and the text comes back empty, the record still says how long it is."""
+    pattern, text, cigar = bytes(pattern), bytes(text), bytes(cigar)
+    size = 3 * len(cigar) + 16 if cap is None else int(cap)
+    buf = C.create_string_buffer(max(size, 1))
+    out = np.zeros(1, dtype=CS_TEXT_DTYPE)
+    sl = None
+    if slice is not None:
+        sl = np.zeros(1, dtype=CS_SLICE_DTYPE)
+        sl[0] = tuple(int(v) for v in slice)
+    rc = load().awv_cs_one_host(cs_mode(cs), pattern, len(pattern), text, len(text), cigar, len(cigar), None if sl is None else sl.ctypes.data, buf, size,
+                                out.ctypes.data)
+    if rc != AWV_OK:
+        raise EngineError(rc, "awv_cs_one_host")
     n = int(out[0]["len"])
     return (buf.raw[:n] if n <= size else b""), out[0]
 

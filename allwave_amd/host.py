@@ -159,20 +159,35 @@ def _check_split(split, split_min_score, clip):
     return int(split), int(split_min_score)
 
 
-def _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split=None, split_min_score=None, normalize=None, device_cigar=False):
-    """The bounds, the clipping, the splitting, the normalization and the device-side CIGAR text of this thread's next alignment
-    hook, which takes them: every argument is checked before anything is set, and all settings are always written
-    (awh_set_bounds, awh_set_clip, awh_set_split, awh_set_normalize, awh_set_device_cigar)."""
+def _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split=None, split_min_score=None, normalize=None, device_cigar=False,
+                     cs=None):
+    """The bounds, the clipping, the splitting, the normalization, the device-side CIGAR text and the cs tag of this thread's next
+    alignment hook, which takes them: every argument is checked before anything is set, and all settings are always written
+    (awh_set_bounds, awh_set_clip, awh_set_split, awh_set_normalize, awh_set_device_cigar, awh_set_cs)."""
     bonus, least = _check_clip(clip, clip_min_score)
     sbonus, sleast = _check_split(split, split_min_score, clip)
     mode = ffi.norm_mode(normalize)
     if device_cigar and sbonus:
         raise ValueError("device_cigar and split exclude each other")
+    cs_mode = ffi.cs_mode(cs)
+    if cs_mode and sbonus:
+        raise ValueError("cs and split exclude each other")
     _set_bounds(max_penalty, max_divergence)
     load().awh_set_clip(bonus, C.c_int64(least))
     load().awh_set_split(sbonus, C.c_int64(sleast))
     load().awh_set_normalize(int(mode))
     load().awh_set_device_cigar(int(bool(device_cigar)))
+    load().awh_set_cs(int(cs_mode))
+
+
+def last_cs():
+    """last_cs_stats() of this thread's last all_pairs_paf / all_pairs_paf_count / align_ranges call: dict(pairs, failed,
+    text_bytes, columns, kernel_ms), summed over the slots (zeros for a call without cs, and for iterate, whose consumers hand
+    out alignment records)."""
+    out = (C.c_uint64 * 4)()
+    ms = C.c_double(0)
+    load().awh_last_cs(out, C.byref(ms))
+    return dict(pairs=int(out[0]), failed=int(out[1]), text_bytes=int(out[2]), columns=int(out[3]), kernel_ms=float(ms.value))
 
 
 def last_encode():
@@ -299,14 +314,15 @@ def check_paf(ids, seqs, paf_text, scores, optimal=False, device=0, partial=Fals
 
 
 def align_ranges(ids, seqs, ranges, scores, devices=None, device=0, verify=False, max_penalty=None, max_divergence=None, clip=None,
-                 clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False):
+                 clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None):
     """allwave::align_ranges + alignment_to_paf: the interval pairs `ranges` -- rows (query_idx, target_idx, is_reverse,
     query_start, query_end, target_start, target_end), the query interval on its forward strand -- aligned globally on the
     engines `devices` names (default: [device]).  Returns the PAF lines in list order: columns 3-4 and 8-9 are the interval,
     2 and 7 the full lengths; a failed range prints its starts twice and an empty cg.  verify=True: every range is checked on
     the device; last_verify() then holds the counters and the failures (index = list index).  max_penalty / max_divergence: as
     for all_pairs_paf (the divergence bound's penalty bound comes from the rectangle's lengths); a range above a bound gives
-    no line.  device_cigar: as for all_pairs_paf -- the same lines (in list order on one slot, in batch order on several)."""
+    no line.  device_cigar: as for all_pairs_paf -- the same lines (in list order on one slot, in batch order on several).
+    cs: as for all_pairs_paf."""
     cids, data, offs = _seq_args(ids, seqs)
     r = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1, 7))
     devs, nd = _device_args([device] if devices is None else devices)
@@ -314,7 +330,7 @@ def align_ranges(ids, seqs, ranges, scores, devices=None, device=0, verify=False
     n = C.c_size_t(0)
     e = _err()
     rbuf = r if len(r) else np.zeros((1, 7), dtype=np.int64)
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs)
     rc = load().awh_align_ranges_paf(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), scores.encode(),
                                      rbuf.ctypes.data_as(C.c_void_p), C.c_size_t(len(r)), devs, nd, int(bool(verify)), C.byref(out),
                                      C.byref(n), e, _CAP)
@@ -385,7 +401,7 @@ def _device_args(devices):
 
 def all_pairs_paf(ids, seqs, scores, orientation="wfa", exclude_self=True, device=0, sparsification="none", devices=None,
                   min_batch_pairs=0, orientation_full=False, verify=False, max_penalty=None, max_divergence=None, clip=None,
-                  clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False):
+                  clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None):
     """AllPairIterator + alignment_to_paf per record; returns the list of PAF lines.  `devices`: a list of ordinals (one
     engine per entry, repeats allowed) to spread the pair list over in this call; None = [device].
     `min_batch_pairs` > 0 overrides the smallest batch of a multi-device run (default 16,384).  orientation_full: WFA
@@ -408,13 +424,17 @@ def all_pairs_paf(ids, seqs, scores, orientation="wfa", exclude_self=True, devic
     device_cigar: the run-length text behind cg:Z: is made on the device (with_device_cigar) and the lines are formatted a
     batch at a time from it (for_each_paf_batch) instead of record by record from the op bytes: the same lines, byte for byte;
     last_encode() tells what was encoded.  Not together with split.  all_pairs_paf_count and align_ranges take it too;
-    iterate accepts and ignores it (its consumers hand out op bytes)."""
+    iterate accepts and ignores it (its consumers hand out op bytes).
+    cs ("short" / "long"): every line gains minimap2's cs difference string, "\tcs:Z:<text>" after the cg:Z: field, made on the
+    device (with_cs) from the op string -- normalized, and clipped, when those are set -- and the resident sequences; the line
+    up to the tag is the line without it; last_cs() tells what was written.  Not together with split.  all_pairs_paf_count and
+    align_ranges take it too; iterate accepts and ignores it."""
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if devices is None else devices)
     out = C.c_void_p()
     n = C.c_size_t(0)
     e = _err()
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs)
     rc = load().awh_all_pairs_paf_devices(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
                                           scores.encode(), sparsification.encode(), _orient_code(orientation, orientation_full), int(exclude_self),
                                           devs, nd, C.c_int64(int(min_batch_pairs)), int(bool(verify)), None, C.byref(out), C.byref(n), e, _CAP)
@@ -431,7 +451,7 @@ ITER_MODES = {"for_each": 0, "next": 1, "par_for_each": 2, "par_collect": 3, "pr
 def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientation="forward", threads=4, chunk=0,
             resparsify=False, fail_at=-1, device=0, devices=None, min_batch_pairs=0, shard=None, with_stats=False,
             orientation_full=False, verify=False, max_penalty=None, max_divergence=None, clip=None, clip_min_score=None, split=None,
-            split_min_score=None, normalize=None, device_cigar=False):
+            split_min_score=None, normalize=None, device_cigar=False, cs=None):
     """Every consumer of the pair list (iterator.rs:101-253, lib.rs:57-68) through one hook; returns the PAF lines in arrival
     order.  `fail_at` >= 0 makes the callback throw at that record: HostError carries its message.
     `devices`: a list of ordinals (one engine per entry, repeats allowed) to spread the pair list over; None = [device].
@@ -442,11 +462,11 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
     fail_at, each of those fails with a message of its own: "callback failed again, ...").  orientation_full: WFA
     orientation by two full alignments for every pair instead of bounded scores (the same strands).  verify: with_verify on the
     iterator, whichever consumer `mode` names; last_verify() tells the outcome.  max_penalty / max_divergence: as for
-    all_pairs_paf -- no consumer is handed a pair above a bound.  device_cigar: accepted and ignored -- every consumer here
-    hands out op bytes."""
+    all_pairs_paf -- no consumer is handed a pair above a bound.  device_cigar, cs: accepted and ignored -- every consumer here
+    hands out alignment records with their op bytes."""
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if devices is None else devices)
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs)
     st = (ffi.Stats * nd)()
     rank, world = shard if shard is not None else (0, 1)
     out = C.c_void_p()
@@ -471,18 +491,19 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
 
 def all_pairs_paf_count(ids, seqs, scores, orientation="forward", device=0, format_threads=8, devices=None, min_batch_pairs=0,
                         sparsification=None, checksum=False, verify=False, max_penalty=None, max_divergence=None, clip=None,
-                        clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False):
+                        clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None):
     """End to end: upload -> align -> D2H -> format into a counting sink. Returns (bytes, lines, secs, ffi.Stats) for
     every pair on `device`.  `devices`: a list of ordinals (one engine per entry, repeats allowed); the Stats are then
     summed over the slots, and the result gains a fifth element, each slot's Stats (last_slot_stats()), and a sixth, the
     sum of the lines' FNV-1a hashes when `checksum` (order-independent; else None).  With devices, `sparsification` plans
     the pair list (default: every pair).  verify: with_verify on the iterator; last_verify() tells the outcome.
     max_penalty / max_divergence: as for all_pairs_paf (the lines counted are the kept pairs').  device_cigar: as for
-    all_pairs_paf; the Stats' d2h_ms then covers the text copy in the op bytes' place."""
+    all_pairs_paf; the Stats' d2h_ms then covers the text copy in the op bytes' place.  cs: as for all_pairs_paf; d2h_ms covers
+    the cs text's copy too."""
     one = devices is None
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if one else devices)
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs)
     nb, nl, secs, ck = C.c_uint64(0), C.c_uint64(0), C.c_double(0), C.c_uint64(0)
     st = ffi.Stats()
     slot = (ffi.Stats * nd)()

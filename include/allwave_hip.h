@@ -79,7 +79,7 @@ typedef struct {
   int32_t device;          /* HIP device ordinal */
   int32_t workgroups;      /* persistent workgroups = pairs in flight (0 = engine default: 16 per CU); the align kernels open
                               workgroups / (waves per workgroup) slots, at least one, and the record kernels (verify, clip,
-                              split, normalize, encode) launch min(records, workgroups) one-wave workgroups -- 0: min(records, 16 per CU) */
+                              split, normalize, encode, cs) launch min(records, workgroups) one-wave workgroups -- 0: min(records, 16 per CU) */
   int64_t max_batch_pairs; /* pairs per launch (0 = default) */
   int64_t max_arena_bytes; /* CIGAR arena budget per launch (0 = default 8 GiB) */
   int32_t flags;           /* AWV_F_* */
@@ -582,7 +582,7 @@ int awv_normalize_cigars(awv_engine* e, int32_t direction, const awv_pair* pairs
 int awv_normalize_ranges(awv_engine* e, int32_t direction, const awv_range_pair* ranges, int64_t n, const awv_result* results,
                          uint8_t* cigar_arena /* in/out */, uint64_t arena_bytes, awv_norm_result* nout /* required */);
 /* The engine's mode (AWV_NORM_OFF by default), read at the start of every aligning call: awv_align_pairs, awv_align_ranges,
- * their _verified, _bounded, _clipped, _split and _encoded forms, and awv_align_one.  When it is on, every batch's finished pairs are
+ * their _verified, _bounded, _clipped, _split, _encoded and _cs forms, and awv_align_one.  When it is on, every batch's finished pairs are
  * normalized in the batch's arena on the device, on the engine's stream (pairs re-run after AWV_ST_CAPACITY included; also
  * under AWV_F_KEEP_ON_DEVICE), BEFORE the optional check, clip and split and before the copy back: vout, cout and the
  * segments describe the normalized string.  Records are byte-identical to the unnormalized call's.  When it is off there is
@@ -645,6 +645,95 @@ int awv_align_ranges_encoded(awv_engine* e, const awv_penalties* pen, const awv_
                              awv_cigar_text* tout /* required */, awv_sink sink, void* user);
 /* The last encoding call (awv_align_*_encoded / awv_encode_cigars) of this engine. */
 int awv_engine_encode_stats(const awv_engine* e, awv_encode_stats* out);
+
+/* ---- minimap2's cs difference string made on the device (csrc/cs.hip, csrc/cs_device.hpp) --------------------------------------
+ * The text behind a PAF line's cs:Z: tag says what the differing bases are.  The inputs are an op string c[0..n) over M X I D and
+ * the two sequences it aligns: the pattern is the query, or its reverse complement when q_revcomp is set, the text is the target;
+ * for a range call they are the two intervals, exactly as verification and normalization see them.  No penalties are involved.
+ * Let p and t be the pattern and text positions consumed so far, lower(b) = b + 32 for 'A'..'Z' and b otherwise, upper its inverse
+ * on 'a'..'z'.  The maximal runs of equal op bytes, left to right:
+ *     a run of L 'M'    AWV_CS_SHORT: ':' + L in decimal    AWV_CS_LONG: '=' + upper(text[t .. t + L))    p and t advance by L
+ *     each 'X' column   '*' + lower(text[t]) + lower(pattern[p])   (target base first)                    both by 1
+ *     a run of L 'I'    '-' + lower(text[t .. t + L))       ('I' consumes the text)                       t by L
+ *     a run of L 'D'    '+' + lower(pattern[p .. p + L))    ('D' consumes the pattern)                    p by L
+ * An 'I' run directly followed by a 'D' run is two items.  Whether an 'M' column's bases are equal or an 'X' column's differ is
+ * not checked (that is verification's job); the '=' bases are always the text's.  Known answer (minimap2's manual): the text
+ * CGATCGATAAATAGAGTAGGAATAGCA, the pattern CGATCGAATAGAGTAGGTCGAATTGCA and the ops 6M 3I 10M 3D 4M 1X 3M give
+ * ":6-ata:10+gtc:4*at:3" and "=CGATCG-ata=AATAGAGTAG+gtc=GAAT*at=GCA".
+ * A slice is an op string of its own, columns [col_beg, col_end) of the record's, that starts at p = q_skip, t = t_skip (the
+ * fields of an awv_clip_result): a slice that cuts a run cuts that item, and nothing before col_beg is read.
+ * Layout: the texts of a call's (or a batch's) records lie in one cs arena, dense and in record order -- off[0] = 0 and
+ * off[i + 1] = off[i] + len[i] -- like the run-length text arena.  A string or slice holds at most 2^30 columns (AWV_ERR_ARG beyond,
+ * before anything is launched); a column gives at most 3 characters, so len fits 32 bits. */
+#define AWV_CS_SHORT 1
+#define AWV_CS_LONG 2
+#define AWV_CST_OK 0       /* the record has a text (empty for an empty string) */
+#define AWV_CST_SKIPPED 1  /* status is not AWV_ST_COMPLETED (AWV_ST_ABOVE_BOUND included), or, in a clipping call, the clip's code is not AWV_CL_OK */
+#define AWV_CST_BAD_OP 2   /* a byte outside MXID */
+#define AWV_CST_LENGTHS 3  /* q_skip + the pattern bases the string consumes > plen, or the same for the text */
+typedef struct {
+  uint64_t off;  /* of the record's text in the cs arena */
+  uint32_t len;  /* characters; 0 for every code but AWV_CST_OK */
+  int32_t code;  /* AWV_CST_* */
+} awv_cs_text; /* 16 bytes */
+
+typedef struct {
+  uint32_t col_beg, col_end; /* the slice [col_beg, col_end) of the op string */
+  int32_t q_skip, t_skip;    /* pattern and text bases consumed before col_beg */
+} awv_cs_slice; /* 16 bytes */
+
+typedef struct {
+  double kernel_ms;     /* HIP-event time of the cs launches (measure, scan, emit) of the last cs call */
+  uint64_t pairs;       /* records handed to the step (the ones without text included) */
+  uint64_t failed;      /* of them: code other than AWV_CST_OK / AWV_CST_SKIPPED */
+  uint64_t text_bytes;  /* characters of all texts */
+  uint64_t columns;     /* op bytes of the strings and slices walked */
+} awv_cs_stats; /* 40 bytes */
+
+/* The sink of a cs call: awv_sink's arguments, and the batch's cs arena (valid only during the call, like cigar_arena). */
+typedef int (*awv_cs_sink)(void* user, int64_t first, int64_t n, const awv_result* results, const uint8_t* cigar_arena,
+                           const uint8_t* cs_arena);
+
+/* The contract alone, on the host (needs no device): a serial walk, the yardstick the kernels are tested against, not a
+ * fallback -- no product path calls it.  mode: AWV_CS_SHORT / AWV_CS_LONG.  slice (nullable): the whole string from p = t = 0.
+ * out->off is 0; the text is written to out_buf only when out->code is AWV_CST_OK and out->len <= cap. */
+int awv_cs_one_host(int32_t mode, const uint8_t* pattern, int32_t plen, const uint8_t* text, int32_t tlen, const uint8_t* cigar,
+                    int64_t n, const awv_cs_slice* slice /* nullable */, uint8_t* out_buf, uint64_t cap,
+                    awv_cs_text* out /* required */);
+/* The cs texts of records and op bytes the caller supplies, on the device, against the resident sequence set (AWV_ERR_STATE
+ * without one): results[i] claims that cigar_arena[results[i].cigar_off, + cigar_len) aligns pairs[i] (ranges[i]).  Staged and
+ * pieced as awv_encode_cigars does, the offsets running on from piece to piece.  slices (nullable): n entries.  csout[0..n) and
+ * *text_bytes (the arena's size) are always filled; the text is written to text_buf only when *text_bytes <= text_cap -- all of
+ * it or nothing -- so text_buf == NULL with text_cap == 0 is the measuring call.  AWV_ERR_ARG, before anything is launched, for a
+ * mode other than the two, a completed record whose op bytes lie outside the arena, and a slice with col_beg > col_end,
+ * col_end > cigar_len or a negative skip. */
+int awv_cs_cigars(awv_engine* e, int32_t mode, const awv_pair* pairs, int64_t n, const awv_result* results,
+                  const uint8_t* cigar_arena, uint64_t arena_bytes, const awv_cs_slice* slices /* nullable */,
+                  awv_cs_text* csout /* required */, uint8_t* text_buf, uint64_t text_cap, uint64_t* text_bytes /* required */);
+int awv_cs_ranges(awv_engine* e, int32_t mode, const awv_range_pair* ranges, int64_t n, const awv_result* results,
+                  const uint8_t* cigar_arena, uint64_t arena_bytes, const awv_cs_slice* slices /* nullable */,
+                  awv_cs_text* csout /* required */, uint8_t* text_buf, uint64_t text_cap, uint64_t* text_bytes /* required */);
+/* awv_align_pairs_encoded / awv_align_ranges_encoded (tout nullable here) with the cs text of every batch's finished pairs made
+ * on the device, on the engine's stream, last of the per-batch steps: after normalization, the optional check, the optional clip
+ * and the optional run-length text, so the cs text is of the normalized string under a mode.  match_bonus == 0: no clip;
+ * match_bonus >= 1: cout is required and the slice is the clip's, with its q_skip / t_skip (AWV_CST_SKIPPED when the clip's code
+ * is not AWV_CL_OK).  tout == NULL: the sink's cigar_arena is the op bytes, as in awv_align_pairs_clipped; non-null: it is the
+ * batch's run-length text arena, as in awv_align_pairs_encoded.  Records, vout, cout and tout are those calls', byte for byte.
+ * csout[first .. first + n) is filled before that batch's sink call, relative to the batch's cs arena, which is copied to a
+ * host buffer of its own and is the sink's cs_arena.  Under AWV_F_KEEP_ON_DEVICE the step runs and csout is filled, but nothing
+ * is copied (both of the sink's arenas are NULL). */
+int awv_align_pairs_cs(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
+                       const int32_t* max_penalty /* per pair, nullable; < 0: none */, int32_t match_bonus, awv_result* out,
+                       awv_verify_result* vout /* nullable */, awv_clip_result* cout /* nullable when match_bonus == 0 */,
+                       awv_cigar_text* tout /* nullable */, int32_t cs_mode, awv_cs_text* csout /* required */, awv_cs_sink sink,
+                       void* user);
+int awv_align_ranges_cs(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n,
+                        const int32_t* max_penalty /* per range, nullable; < 0: none */, int32_t match_bonus, awv_result* out,
+                        awv_verify_result* vout /* nullable */, awv_clip_result* cout /* nullable when match_bonus == 0 */,
+                        awv_cigar_text* tout /* nullable */, int32_t cs_mode, awv_cs_text* csout /* required */, awv_cs_sink sink,
+                        void* user);
+/* The last cs call (awv_align_*_cs / awv_cs_cigars / awv_cs_ranges) of this engine. */
+int awv_engine_cs_stats(const awv_engine* e, awv_cs_stats* out);
 
 /* ---- device pair planning (csrc/planner.hip) -------------------------------------------------------------------------
  * Integer work over the engine's resident sequence set, on its device and stream; results equal the host planner's
