@@ -84,15 +84,8 @@ struct State : awvw::RecordPass {
   }
 };
 
-void state_release(State* s) {
-  if (!s) return;
-  s->release();
-  delete s;
-}
-
-void stats_reset(State* s) {
-  if (s) s->stats = awv_clip_stats{};
-}
+void state_release(State* s) { awvw::release_pass(s); }
+void stats_reset(State* s) { awvw::reset_stats(s); }
 
 namespace {
 
@@ -108,12 +101,8 @@ int check_args(const awv_penalties* p, int32_t match_bonus, awv_penalties& out) 
   return AWV_OK;
 }
 
-int open_state(awv_engine* e, awp::EngineView& v, State*& st) {
-  State*& slot = awv_internal_clip(e);
-  if (!slot) slot = new State();
-  st = slot;
-  return st->open(e, v, false);  // (the clip reads no sequence: an engine without a set will do, and is no error)
-}
+// (the clip reads no sequence: an engine without a set will do, and is no error)
+int open_state(awv_engine* e, awp::EngineView& v, State*& st) { return awvw::open_pass(awv_internal_clip(e), e, v, st, false); }
 
 // One launch over n records whose op bytes are on the device already.
 int launch(const awp::EngineView& v, State* st, const awv_penalties& pen, int32_t match_bonus, int64_t n, const awv_result* results,

@@ -2,11 +2,9 @@
 // awv_engine_cs_stats (include/allwave_hip.h).  What the cs text of an op string is is cs_device.hpp; this file gets the kernels to
 // the same bytes.
 //
-// encode.hip's shape with verify.hip's sequence walk: one wave per record, persistent waves taking records (longest op string
-// first) from a cursor, and three steps on the stream because the size of the output depends on the data:
-//   1. measure: every record's text length and code (awv_cs_text.len / .code);
-//   2. scan: one workgroup's exclusive scan over `len` in record order gives every record its place (.off) in a dense cs arena;
-//   3. emit: the same walk again, now writing every item's characters at its place.
+// A text pass (text_pass.hpp) with verify.hip's sequence walk: one wave per record, persistent waves taking records (longest op
+// string first) from a cursor, and measure, scan and emit on the stream.  measure writes every record's text length and code
+// (awv_cs_text.len / .code).
 // The walk takes a string in chunks of 64 lanes x 16 op bytes, one aligned 16-byte load per lane.  A column's pattern position
 // is the number of ops other than 'I' before it, its text position the number other than 'D': a lane counts both over its bytes,
 // one packed add-scan over the lanes (16 bits each: a chunk holds 1,024 columns) and a carry from chunk to chunk place the lane,
@@ -14,22 +12,20 @@
 // consecutive pattern and 16 consecutive text bytes: five aligned dwords each, shifted into place.
 // Who owns which characters: an 'X' column its three; a gap column its base, and the sign too when it starts its run (its op
 // differs from the one before it); in long mode an 'M' column likewise.  In short mode an 'M' run's ":N" belongs to the lane that
-// holds the break that ends the run, as a run does in encode.hip -- where the run began is the last break before it, among the
-// lane's own bytes, else from a max-scan over the lanes' last breaks, else the carry -- and the string's last run is written
-// when the chunks are done.  A second add-scan over the lanes' character counts gives every lane its text offset.
+// holds the break that ends the run (text_pass.hpp's run ownership), and the string's last run is written when the chunks are
+// done.  A second add-scan over the lanes' character counts gives every lane its text offset.
 // The text is stored byte by byte, straight to global memory, as encode.hip stores its text.
 #include "cs_device.hpp"
 
 #include <algorithm>
 #include <climits>
-#include <cstring>
 #include <new>
 #include <string>
 #include <vector>
 
-#include "record_pass.hpp"  // the host skeleton of a record pass: RecordPass, pack_piece, AWV_TRY
+#include "text_pass.hpp"  // the host skeleton and the device walk of a text pass: TextPass, lane_runs, text_dest, AWV_TRY
 
-namespace awvx {
+namespace awvcs {
 
 struct KParams {
   const uint8_t* fwd;         // the engine's forward copies
@@ -42,24 +38,16 @@ struct KParams {
   const int32_t* order;       // dispatch slot -> record
   const uint8_t* arena;       // 16-byte aligned, readable up to the 16-byte boundary behind every op string
   awv_cs_text* out;           // measure writes len and code, the scan off, emit reads all three
-  uint8_t* text;              // emit: the launch's cs arena, text_bytes of it; text[0] is the character at offset text_base
-  unsigned long long text_base, text_bytes;
+  awvw::TextArena text;       // emit: where the launch's cs text goes
   unsigned long long* counters;  // [0] this kernel's cursor; measure: [1] failed records, [2] columns
   long long npairs;
 };
 
+using awvw::byte_at;
 using awvw::CHUNK;
-using awvw::from_lower_lane;
 using awvw::LANE_BYTES;
 using awvw::u32x4;
 using awvw::wave_scan_add;
-using awvw::wave_scan_max;
-
-__device__ __forceinline__ unsigned byte_at(const u32x4& w, int j) {  // byte j of a lane's 16, j in a register
-  const int k = j >> 2;
-  const unsigned d = k == 0 ? w[0] : k == 1 ? w[1] : k == 2 ? w[2] : w[3];
-  return (d >> (8 * (j & 3))) & 0xffu;
-}
 
 // 16 bytes of a sequence of `len` bytes from position `pos` on: five aligned dwords, shifted into place.  Dwords that start at or
 // behind the sequence's end are not read (their bytes are 0); a dword that starts inside it ends at most 3 bytes behind it, inside
@@ -108,17 +96,16 @@ __global__ __launch_bounds__(64) void awv_cs_kernel(KParams kp) {
       }
       continue;
     }
-    // emit: the record's characters are dst[0 .. room), inside the cs arena by the scan -- checked all the same, so that nothing is
-    // ever stored outside the buffer.  Only a record that measure found sound is walked again: its positions stay inside the two
-    // sequences (load16 clamps all the same).
+    // emit: only a record that measure found sound is walked again: its positions stay inside the two sequences (load16 clamps all
+    // the same)
     uint8_t* dst = nullptr;
     unsigned room = 0;
     if (EMIT) {
       const awv_cs_text t = kp.out[pair];
-      if (t.code == AWV_CST_OK && t.off >= kp.text_base && t.off - kp.text_base <= kp.text_bytes &&
-          (unsigned long long)t.len <= kp.text_bytes - (t.off - kp.text_base)) {
-        dst = kp.text + (t.off - kp.text_base);
-        room = t.len;
+      if (t.code == AWV_CST_OK) {
+        const awvw::TextDest d = awvw::text_dest(kp.text, t.off, t.len);
+        dst = d.dst;
+        room = d.room;
       }
       if (room == 0) continue;
     }
@@ -128,45 +115,36 @@ __global__ __launch_bounds__(64) void awv_cs_kernel(KParams kp) {
     const uint8_t* const ops = kp.arena + (rec.cigar_off & ~(uint64_t)15);  // op byte c is ops[sh + c]
     const long long span = sh + n;
 
-    int cq = 0, ct = 0;     // bases consumed before the chunk (uniform, like everything carried)
-    long long c_start = 0;  // the column the run in progress began at
-    unsigned c_prev = 0;    // the op before the chunk's first column
-    unsigned c_text = 0;    // characters of the columns and ended 'M' runs of the chunks before
+    int cq = 0, ct = 0;  // bases consumed before the chunk (uniform, like everything carried)
+    awvw::RunCarry carry;
+    unsigned c_text = 0;  // characters of the columns and ended 'M' runs of the chunks before
     bool bad = false;
     for (long long base = 0; base < span; base += CHUNK) {
-      const long long b0 = base + lane * LANE_BYTES;
-      const int jlo = (int)min(max((long long)sh - b0, 0ll), (long long)LANE_BYTES), jhi = (int)min(max(span - b0, 0ll), (long long)LANE_BYTES);  // this lane's bytes [jlo, jhi) are columns
-      u32x4 w = {0u, 0u, 0u, 0u};
-      if (b0 < span) w = *(const u32x4*)(ops + b0);
-      // the op before this lane's first byte: the lower lane's last byte, the chunk's carry in lane 0 (column 0 has none: it is no break)
-      const unsigned prev = (unsigned)from_lower_lane((int)w[3], (int)(c_prev << 24)) >> 24;
-      unsigned valid = 0, brk = 0, m_m = 0, m_x = 0, m_i = 0, m_d = 0;  // bit j: byte j is a column / one > 0 whose op differs from the one before it / an 'M', ...
-      unsigned pv = prev;
+      const awvw::LaneRuns r = awvw::lane_runs(ops, sh, span, base, lane, carry);
+      const long long b0 = r.b0;
+      const u32x4 w = r.w;
+      const unsigned brk = r.brk;
+      const unsigned valid = ((1u << r.jhi) - 1u) & ~((1u << r.jlo) - 1u);  // bit j: byte j is a column
+      unsigned m_m = 0, m_x = 0, m_i = 0, m_d = 0;                          // ... an 'M', ...
 #pragma unroll
       for (int j = 0; j < LANE_BYTES; ++j) {
         const unsigned op = (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
-        if (j >= jlo && j < jhi) {
-          valid |= 1u << j;
-          if (op != pv && b0 + j > sh) brk |= 1u << j;
-          pv = op;
-          m_m |= (unsigned)(op == 'M') << j;
-          m_x |= (unsigned)(op == 'X') << j;
-          m_i |= (unsigned)(op == 'I') << j;
-          m_d |= (unsigned)(op == 'D') << j;
-        }
+        m_m |= (unsigned)(op == 'M') << j;
+        m_x |= (unsigned)(op == 'X') << j;
+        m_i |= (unsigned)(op == 'I') << j;
+        m_d |= (unsigned)(op == 'D') << j;
       }
+      m_m &= valid;
+      m_x &= valid;
+      m_i &= valid;
+      m_d &= valid;
       const unsigned gaps = m_i | m_d;
       const unsigned starts = brk | (b0 <= sh && sh < b0 + LANE_BYTES ? 1u << (int)(sh - b0) : 0u);  // columns that begin a run: the breaks and column 0
       const unsigned takes_p = valid & ~m_i, takes_t = valid & ~m_d;
       const bool lane_bad = (valid & ~(m_m | m_x | gaps)) != 0;
 
-      const int key = brk != 0 ? lane * LANE_BYTES + (31 - __builtin_clz(brk)) : -1;  // the lane's last break, as a byte position in the chunk
-      const int kin = wave_scan_max(key);
-      const int kex = from_lower_lane(kin, -1);
-      const long long rs0 = kex >= 0 ? base + kex - sh : c_start;  // the run this lane begins in started here
-
       // short mode: the breaks of this lane that end an 'M' run
-      const unsigned end_m = LONG ? 0u : brk & ((m_m << 1) | (prev == 'M' ? 1u : 0u));
+      const unsigned end_m = LONG ? 0u : brk & ((m_m << 1) | (r.prev == 'M' ? 1u : 0u));
       int chars = 3 * __popc(m_x);
       if (LONG) {
         chars += __popc(valid & ~m_x) + __popc(starts & ~m_x);
@@ -174,9 +152,7 @@ __global__ __launch_bounds__(64) void awv_cs_kernel(KParams kp) {
         chars += __popc(gaps) + __popc(starts & gaps);
         for (unsigned m = end_m; m != 0; m &= m - 1) {
           const int j = __builtin_ctz(m);
-          const unsigned lower_brk = brk & ((1u << j) - 1u);
-          const long long start = lower_brk != 0 ? b0 + (31 - __builtin_clz(lower_brk)) - sh : rs0;
-          chars += (int)match_chars((unsigned)(b0 + j - sh - start));
+          chars += (int)match_chars((unsigned)(b0 + j - sh - awvw::run_start_before(r, sh, j)));
         }
       }
       const int counts = __popc(takes_p) | (__popc(takes_t) << 16);  // (a chunk holds 1,024 columns: the sums fit 16 bits each)
@@ -193,9 +169,7 @@ __global__ __launch_bounds__(64) void awv_cs_kernel(KParams kp) {
             const unsigned bit = 1u << j, below = bit - 1u;
             const unsigned op = byte_at(w, j);
             if (!LONG && (end_m & bit) != 0) {
-              const unsigned lower_brk = brk & below;
-              const long long start = lower_brk != 0 ? b0 + (31 - __builtin_clz(lower_brk)) - sh : rs0;
-              const unsigned len = (unsigned)(b0 + j - sh - start), nc = match_chars(len);
+              const unsigned len = (unsigned)(b0 + j - sh - awvw::run_start_before(r, sh, j)), nc = match_chars(len);
               if (at + nc <= room) put_match(dst + at, len);
               at += nc;
             }
@@ -212,10 +186,7 @@ __global__ __launch_bounds__(64) void awv_cs_kernel(KParams kp) {
         }
       }
 
-      const int last_lane = (int)min(63ll, (span - 1 - base) >> 4);  // the lane that holds the chunk's last column
-      c_prev = (unsigned)__builtin_amdgcn_readlane((int)pv, last_lane);
-      const int kall = __builtin_amdgcn_readlane(kin, 63);
-      if (kall >= 0) c_start = base + kall - sh;
+      awvw::carry_on(carry, r, sh, span, base);
       const int tot = __builtin_amdgcn_readlane(s_pos, 63);
       cq += tot & 0xffff;
       ct += tot >> 16;
@@ -223,8 +194,8 @@ __global__ __launch_bounds__(64) void awv_cs_kernel(KParams kp) {
       bad = bad || __ballot(lane_bad) != 0;
     }
     // short mode: an 'M' run that ends with the string
-    const unsigned last_len = (unsigned)(n - c_start);
-    const unsigned last_nc = !LONG && c_prev == 'M' ? match_chars(last_len) : 0u;
+    const unsigned last_len = (unsigned)(n - carry.start);
+    const unsigned last_nc = !LONG && carry.prev == 'M' ? match_chars(last_len) : 0u;
     if (EMIT) {
       if (lane == 0 && last_nc != 0 && c_text + last_nc <= room) put_match(dst + c_text, last_len);
     } else {
@@ -240,74 +211,33 @@ __global__ __launch_bounds__(64) void awv_cs_kernel(KParams kp) {
   }
 }
 
-// Step 2 (encode.hip's scan, over awv_cs_text): out[i].off = base + the sum of out[0 .. i).len, in record order; *total = base + the
-// sum of them all.  One workgroup of sixteen waves takes the records in tiles of 1,024.
-constexpr int SCAN_THREADS = 1024;
-__global__ __launch_bounds__(SCAN_THREADS) void awv_cs_scan_kernel(awv_cs_text* out, long long n, unsigned long long base, unsigned long long* total) {
-  __shared__ unsigned long long wave_sum[SCAN_THREADS / 64];
-  const int tid = threadIdx.x, wave = tid >> 6;
-  unsigned long long carry = base;
-  for (long long tile = 0; tile < n; tile += SCAN_THREADS) {
-    const long long i = tile + tid;
-    const unsigned long long len = i < n ? (unsigned long long)out[i].len : 0ull;
-    const unsigned long long inc = (unsigned long long)wave_scan_add((long long)len);
-    if ((tid & 63) == 63) wave_sum[wave] = inc;
-    __syncthreads();
-    unsigned long long before = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_THREADS / 64; ++k) {
-      const unsigned long long s = wave_sum[k];
-      if (k < wave) before += s;
-      all += s;
-    }
-    if (i < n) out[i].off = carry + before + inc - len;
-    carry += all;
-    __syncthreads();
-  }
-  if (tid == 0) *total = carry;
-}
-
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
 using awvw::Buf;
 
-constexpr int N_COUNTERS = 16;  // [0..2] the measure kernel's, [4] the scan's total, [8] the emit kernel's cursor
-
-struct State : awvw::RecordPass {
+struct State : awvw::TextPass {
   Buf<awv_pair> d_pairs;
   Buf<Span> d_spans;
   Buf<awv_cs_text> d_out;
-  Buf<uint8_t> d_text;             // the cs arena of the launch in hand
   std::vector<awv_result> h_recs;  // a batch's records with their slices applied
   std::vector<Span> h_spans;       // and their rectangles
   awv_cs_stats stats{};
   void release() {
-    RecordPass::release();
+    TextPass::release();
     d_pairs.release();
     d_spans.release();
     d_out.release();
-    d_text.release();
   }
 };
 
-void state_release(State* s) {
-  if (!s) return;
-  s->release();
-  delete s;
-}
-
-void stats_reset(State* s) {
-  if (s) s->stats = awv_cs_stats{};
-}
+void state_release(State* s) { awvw::release_pass(s); }
+void stats_reset(State* s) { awvw::reset_stats(s); }
 
 namespace {
 
-int open_state(awv_engine* e, awp::EngineView& v, State*& st) {
-  State*& slot = awv_internal_cs(e);
-  if (!slot) slot = new State();
-  st = slot;
-  return st->open(e, v, true);
-}
+constexpr const char* TOO_LONG = "cs: an op string of more than 2^30 columns";  // what fits awv_cs_text.len
+
+int open_state(awv_engine* e, awp::EngineView& v, State*& st) { return awvw::open_pass(awv_internal_cs(e), e, v, st, true); }
 
 void launch_kernel(bool emit, int32_t mode, unsigned grid, hipStream_t stream, const KParams& kp) {
   if (emit) {
@@ -317,14 +247,6 @@ void launch_kernel(bool emit, int32_t mode, unsigned grid, hipStream_t stream, c
     if (mode == AWV_CS_LONG) hipLaunchKernelGGL((awv_cs_kernel<false, true>), dim3(grid), dim3(64), 0, stream, kp);
     else hipLaunchKernelGGL((awv_cs_kernel<false, false>), dim3(grid), dim3(64), 0, stream, kp);
   }
-}
-
-// what fits awv_cs_text.len: refused before anything is launched
-int check_lengths(const awv_result* recs, int64_t n) {
-  for (int64_t i = 0; i < n; ++i)
-    if (recs[i].status == AWV_ST_COMPLETED && (int64_t)recs[i].cigar_len > MAX_COLUMNS)
-      return awv_internal_fail(AWV_ERR_ARG, "cs: an op string of more than 2^30 columns");
-  return AWV_OK;
 }
 
 // One launch over n records whose op bytes are on the device already; a record's slice has been applied to it and to its
@@ -349,7 +271,6 @@ int launch(const awp::EngineView& v, State* st, int32_t mode, const awv_pair* pa
   AWV_TRY(st->d_out.reserve((size_t)n));
   AWV_TRY(hipMemcpyAsync(st->d_pairs.p, pairs, (size_t)n * sizeof(awv_pair), hipMemcpyHostToDevice, v.stream));
   AWV_TRY(hipMemcpyAsync(st->d_spans.p, spans, (size_t)n * sizeof(Span), hipMemcpyHostToDevice, v.stream));
-  if (int rc = st->clear_counters(v, N_COUNTERS)) return rc;
   KParams kp{};
   kp.fwd = v.fwd;
   kp.rc = v.rc;
@@ -360,41 +281,20 @@ int launch(const awp::EngineView& v, State* st, int32_t mode, const awv_pair* pa
   kp.order = st->d_order.p;
   kp.arena = d_arena;
   kp.out = st->d_out.p;
-  kp.counters = st->d_counters.p;
   kp.npairs = n;
-  const unsigned grid = st->grid(v, n);
-  if (int rc = st->start(v)) return rc;
-  launch_kernel(false, mode, grid, v.stream, kp);
-  hipLaunchKernelGGL(awv_cs_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, v.stream, st->d_out.p, (long long)n, (unsigned long long)text_base,
-                     st->d_counters.p + 4);
-  if (int rc = st->stop(v)) return rc;
-  // the arena's size: all the host waits for before the text buffer is sized
-  unsigned long long total = 0;
-  float ms = 0, ms_emit = 0;
-  AWV_TRY(hipMemcpyAsync(&total, st->d_counters.p + 4, sizeof(total), hipMemcpyDeviceToHost, v.stream));
-  AWV_TRY(hipStreamSynchronize(v.stream));
-  AWV_TRY(hipEventElapsedTime(&ms, st->ev0, st->ev1));
-  const uint64_t bytes = total - text_base;
-  const bool emit = want_text && bytes > 0;
-  if (emit) {
-    AWV_TRY(st->d_text.reserve((size_t)bytes + 64));
-    kp.text = st->d_text.p;
-    kp.text_base = text_base;
-    kp.text_bytes = bytes;
-    kp.counters = st->d_counters.p + 8;
-    if (int rc = st->start(v)) return rc;
-    launch_kernel(true, mode, grid, v.stream, kp);
-    if (int rc = st->stop(v)) return rc;
-  }
-  unsigned long long hc[4] = {0, 0, 0, 0};
-  AWV_TRY(hipMemcpyAsync(csout, st->d_out.p, (size_t)n * sizeof(awv_cs_text), hipMemcpyDeviceToHost, v.stream));
-  if (int rc = st->finish(v, hc, 4, ms_emit)) return rc;
-  st->stats.kernel_ms += ms + (emit ? ms_emit : 0.f);
+  awvw::TextLaunch done;
+  const auto run = [&](bool emit, unsigned grid, unsigned long long* counters, const awvw::TextArena& text) {
+    kp.counters = counters;
+    kp.text = text;
+    launch_kernel(emit, mode, grid, v.stream, kp);
+  };
+  if (int rc = st->measure_scan_emit(v, n, st->d_out.p, text_base, want_text, csout, run, done)) return rc;
+  st->stats.kernel_ms += done.kernel_ms;
   st->stats.pairs += (uint64_t)n;
-  st->stats.failed += hc[1];
-  st->stats.columns += hc[2];
-  st->stats.text_bytes += bytes;
-  *text_end = total;
+  st->stats.failed += done.hc[1];
+  st->stats.columns += done.hc[2];
+  st->stats.text_bytes += done.bytes;
+  *text_end = done.end;
   return AWV_OK;
 }
 
@@ -439,31 +339,11 @@ int cs_cigars_core(awv_engine* e, int32_t mode, const awv_pair* pairs, const awv
     for (int64_t i = 0; i < n_all; ++i) apply_slice(sliced[(size_t)i], spans[(size_t)i], slices[i]);
     results = sliced.data();
   }
-  if (int rc = check_lengths(results, n_all)) return rc;
-  // in pieces (record_pieces.hpp) that keep every string's offset modulo 16; the offsets run on from piece to piece.  A piece's
-  // text is kept here while the text so far fits the caller's buffer, which is written at the end, all of it or none.
-  std::vector<uint8_t> stage, text;
-  std::vector<awv_result> recs;
-  uint64_t at = 0;
-  bool fits = text_buf != nullptr;
-  for (int64_t first = 0; first < n_all;) {
-    const awvw::Piece pc = awvw::pack_piece(results, n_all, first, cigar_arena, max_arena, true, recs, stage);
-    AWV_TRY(st->d_arena.reserve((size_t)pc.bytes + 64));
-    if (pc.bytes) AWV_TRY(hipMemcpyAsync(st->d_arena.p, stage.data(), (size_t)pc.bytes, hipMemcpyHostToDevice, v.stream));
-    uint64_t end = at;
-    if (int rc = launch(v, st, mode, pairs + first, spans.data() + first, pc.n, recs.data(), st->d_arena.p, pc.bytes, at, fits, csout + first, &end)) return rc;
-    fits = fits && end <= text_cap;
-    if (fits && end > at) {
-      text.resize((size_t)end);
-      AWV_TRY(hipMemcpyAsync(text.data() + at, st->d_text.p, (size_t)(end - at), hipMemcpyDeviceToHost, v.stream));
-      AWV_TRY(hipStreamSynchronize(v.stream));
-    }
-    at = end;
-    first += pc.n;
-  }
-  *text_bytes = at;
-  if (fits && at > 0) std::memcpy(text_buf, text.data(), (size_t)at);
-  return AWV_OK;
+  if (int rc = awvw::check_lengths(results, n_all, MAX_COLUMNS, TOO_LONG)) return rc;
+  return st->in_pieces(v, results, n_all, cigar_arena, max_arena, text_buf, text_cap, text_bytes,
+                       [&](int64_t first, int64_t n, const awv_result* recs, uint64_t bytes, uint64_t text_base, bool want_text, uint64_t* text_end) {
+                         return launch(v, st, mode, pairs + first, spans.data() + first, n, recs, st->d_arena.p, bytes, text_base, want_text, csout + first, text_end);
+                       });
 }
 
 int check_call_args(const char* name, int64_t n, const void* who, const awv_result* results, const uint8_t* cigar_arena, uint64_t arena_bytes,
@@ -492,7 +372,7 @@ int cs_batch(awv_engine* e, int32_t mode, const awv_pair* pairs, int64_t n, cons
     }
     results = st->h_recs.data();
   }
-  if (int rc = check_lengths(results, n)) return rc;
+  if (int rc = awvw::check_lengths(results, n, MAX_COLUMNS, TOO_LONG)) return rc;
   return launch(v, st, mode, pairs, st->h_spans.data(), n, results, d_arena, arena_bytes, 0, true, csout, text_bytes);
 }
 
@@ -501,13 +381,13 @@ const uint8_t* batch_text(awv_engine* e) {
   return st ? st->d_text.p : nullptr;
 }
 
-}  // namespace awvx
+}  // namespace awvcs
 
 extern "C" {
 
 int awv_cs_one_host(int32_t mode, const uint8_t* pattern, int32_t plen, const uint8_t* text, int32_t tlen, const uint8_t* cigar, int64_t n,
                     const awv_cs_slice* slice, uint8_t* out_buf, uint64_t cap, awv_cs_text* out) {
-  if (!out || !awvx::mode_ok(mode) || plen < 0 || tlen < 0 || n < 0 || (plen > 0 && !pattern) || (tlen > 0 && !text) || (n > 0 && !cigar) ||
+  if (!out || !awvcs::mode_ok(mode) || plen < 0 || tlen < 0 || n < 0 || (plen > 0 && !pattern) || (tlen > 0 && !text) || (n > 0 && !cigar) ||
       (cap > 0 && !out_buf))
     return awv_internal_fail(AWV_ERR_ARG, "cs_one_host: bad argument");
   int64_t beg = 0, end = n, q_skip = 0, t_skip = 0;
@@ -519,31 +399,31 @@ int awv_cs_one_host(int32_t mode, const uint8_t* pattern, int32_t plen, const ui
     q_skip = slice->q_skip;
     t_skip = slice->t_skip;
   }
-  if (end - beg > awvx::MAX_COLUMNS) return awv_internal_fail(AWV_ERR_ARG, "cs_one_host: an op string of more than 2^30 columns");
-  *out = awvx::cs_one(mode, pattern, plen, text, tlen, cigar + beg, end - beg, q_skip, t_skip, out_buf, cap);
+  if (end - beg > awvcs::MAX_COLUMNS) return awv_internal_fail(AWV_ERR_ARG, "cs_one_host: an op string of more than 2^30 columns");
+  *out = awvcs::cs_one(mode, pattern, plen, text, tlen, cigar + beg, end - beg, q_skip, t_skip, out_buf, cap);
   return AWV_OK;
 }
 
 int awv_cs_cigars(awv_engine* e, int32_t mode, const awv_pair* pairs, int64_t n, const awv_result* results, const uint8_t* cigar_arena,
                   uint64_t arena_bytes, const awv_cs_slice* slices, awv_cs_text* csout, uint8_t* text_buf, uint64_t text_cap, uint64_t* text_bytes) {
   if (!e) return awv_internal_null_engine();
-  if (int rc = awvx::check_call_args("cs_cigars", n, pairs, results, cigar_arena, arena_bytes, csout, text_buf, text_cap, text_bytes)) return rc;
-  AWV_GUARDED(return awvx::cs_cigars_core(e, mode, pairs, nullptr, n, results, cigar_arena, arena_bytes, slices, awv_internal_max_arena(e), csout, text_buf,
+  if (int rc = awvcs::check_call_args("cs_cigars", n, pairs, results, cigar_arena, arena_bytes, csout, text_buf, text_cap, text_bytes)) return rc;
+  AWV_GUARDED(return awvcs::cs_cigars_core(e, mode, pairs, nullptr, n, results, cigar_arena, arena_bytes, slices, awv_internal_max_arena(e), csout, text_buf,
                                           text_cap, text_bytes);)
 }
 
 int awv_cs_ranges(awv_engine* e, int32_t mode, const awv_range_pair* ranges, int64_t n, const awv_result* results, const uint8_t* cigar_arena,
                   uint64_t arena_bytes, const awv_cs_slice* slices, awv_cs_text* csout, uint8_t* text_buf, uint64_t text_cap, uint64_t* text_bytes) {
   if (!e) return awv_internal_null_engine();
-  if (int rc = awvx::check_call_args("cs_ranges", n, ranges, results, cigar_arena, arena_bytes, csout, text_buf, text_cap, text_bytes)) return rc;
+  if (int rc = awvcs::check_call_args("cs_ranges", n, ranges, results, cigar_arena, arena_bytes, csout, text_buf, text_cap, text_bytes)) return rc;
   static const awv_range_pair none{};
-  AWV_GUARDED(return awvx::cs_cigars_core(e, mode, nullptr, n > 0 ? ranges : &none, n, results, cigar_arena, arena_bytes, slices, awv_internal_max_arena(e), csout,
+  AWV_GUARDED(return awvcs::cs_cigars_core(e, mode, nullptr, n > 0 ? ranges : &none, n, results, cigar_arena, arena_bytes, slices, awv_internal_max_arena(e), csout,
                                           text_buf, text_cap, text_bytes);)
 }
 
 int awv_engine_cs_stats(const awv_engine* e, awv_cs_stats* out) {
   if (!e || !out) return awv_internal_fail(AWV_ERR_ARG, "cs_stats: null argument");
-  const awvx::State* st = awv_internal_cs(const_cast<awv_engine*>(e));
+  const awvcs::State* st = awv_internal_cs(const_cast<awv_engine*>(e));
   *out = st ? st->stats : awv_cs_stats{};
   return AWV_OK;
 }

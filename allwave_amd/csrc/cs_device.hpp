@@ -19,11 +19,12 @@
 #include <cstdint>
 
 #include "allwave_hip.h"
+#include "encode_device.hpp"  // digits
 #include "range_span.hpp"
 
 struct awv_engine;
 
-namespace awvx {
+namespace awvcs {
 
 constexpr int64_t MAX_COLUMNS = (int64_t)1 << 30;  // of one string or slice: its text (at most three characters a column) then fits awv_cs_text.len
 
@@ -32,11 +33,8 @@ __host__ __device__ inline bool is_op(uint32_t op) { return op == 'M' || op == '
 __host__ __device__ inline uint32_t lower(uint32_t b) { return b >= 'A' && b <= 'Z' ? b + 32u : b; }
 __host__ __device__ inline uint32_t upper(uint32_t b) { return b >= 'a' && b <= 'z' ? b - 32u : b; }
 
-// decimal digits of a run length (>= 1, <= MAX_COLUMNS)
-__host__ __device__ inline int digits(uint32_t len) {
-  return len < 10u ? 1 : len < 100u ? 2 : len < 1000u ? 3 : len < 10000u ? 4 : len < 100000u ? 5 : len < 1000000u ? 6 : len < 10000000u ? 7 : len < 100000000u ? 8
-       : len < 1000000000u ? 9 : 10;
-}
+using awve::digits;  // decimal digits of a run length (>= 1, <= MAX_COLUMNS)
+
 // the characters of a short-mode 'M' run: ':' and its length
 __host__ __device__ inline uint32_t match_chars(uint32_t len) { return (uint32_t)digits(len) + 1u; }
 // writes them at dst
@@ -155,8 +153,8 @@ int cs_batch(awv_engine* e, int32_t mode, const awv_pair* pairs, int64_t n, cons
              const awv_clip_result* clips, const Span* spans, awv_cs_text* csout, uint64_t* text_bytes);
 const uint8_t* batch_text(awv_engine* e);  // the last cs_batch's text, on the device
 
-}  // namespace awvx
+}  // namespace awvcs
 
 // engine.hip
-awvx::State*& awv_internal_cs(awv_engine* e);
+awvcs::State*& awv_internal_cs(awv_engine* e);
 uint64_t awv_internal_max_arena(const awv_engine* e);  // the CIGAR arena budget of a launch: awv_cs_cigars cuts its call by it

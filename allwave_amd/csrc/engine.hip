@@ -7,7 +7,11 @@
 #include "allwave_hip.h"
 #include "host_errors.hpp"      // (AWV_TRY, AWV_GUARDED: the error plumbing every unit behind the C ABI shares)
 // the device code, once per workgroup size: awv:: one wave per pair (throughput), awvw:: four waves per pair,
-// awvx:: sixteen waves per pair (one pair per CU: the few pairs a large length difference makes enormous)
+// awvx:: sixteen waves per pair (one pair per CU: the few pairs a large length difference makes enormous).  These three
+// names and awvw_m / awvx_m below belong to biwfa_device.hpp's instantiations, whose types (KParams, ...) are defined anew in
+// each: no other header included here may open one of them.  The passes' hooks live in awp (planner), awo (orient), awvf
+// (verify), awvc (clip), awvs (split), awvn (normalize), awve (encode) and awvcs (cs); awvw is also wave_ops.hpp's name in the
+// passes' own units, which this unit does not include.
 #include "planner_device.hpp"  // (the sketches and scratch of device pair planning, planner.hip)
 #include "verify_device.hpp"   // (the per-batch check of awv_align_pairs_verified, verify.hip)
 #include "clip_device.hpp"     // (the per-batch clip of awv_align_pairs_clipped, clip.hip)
@@ -188,7 +192,7 @@ struct awv_engine {
   awvs::State* split = nullptr;    // split.hip: likewise for the split launches
   awvn::State* normalize = nullptr;  // normalize.hip: likewise for the normalize launches
   awve::State* encode = nullptr;   // encode.hip: likewise for the encode launches, and the text arena of the batch in hand
-  awvx::State* cs = nullptr;       // cs.hip: likewise for the cs launches, and the cs arena of the batch in hand
+  awvcs::State* cs = nullptr;      // cs.hip: likewise for the cs launches, and the cs arena of the batch in hand
   int32_t norm_mode = AWV_NORM_OFF;  // awv_engine_set_normalize: read at the start of every aligning call
 };
 
@@ -875,7 +879,7 @@ int run_record_steps(AlignCall& c) {
     c.lap("batch encoded");
   }
   if (rq.csout) {
-    if (int rc = awvx::cs_batch(e, rq.cs_mode, rq.pairs + first, n, hres.data(), e->d_cigar.p, arena, rq.cout ? rq.cout + first : nullptr,
+    if (int rc = awvcs::cs_batch(e, rq.cs_mode, rq.pairs + first, n, hres.data(), e->d_cigar.p, arena, rq.cout ? rq.cout + first : nullptr,
                                 rq.spans ? rq.spans + first : nullptr, rq.csout + first, &c.cs_bytes)) return rc;
     c.lap("batch cs");
   }
@@ -894,7 +898,7 @@ int copy_cigars_back(AlignCall& c) {
     if (bytes) AWV_TRY(hipMemcpyAsync(e->h_cigar.data(), src, bytes, hipMemcpyDeviceToHost, e->stream));
     if (c.rq.csout) {  // (inside the same bracket: one wait for both copies)
       e->h_cs.resize((size_t)c.cs_bytes + 64);
-      if (c.cs_bytes) AWV_TRY(hipMemcpyAsync(e->h_cs.data(), awvx::batch_text(e), (size_t)c.cs_bytes, hipMemcpyDeviceToHost, e->stream));
+      if (c.cs_bytes) AWV_TRY(hipMemcpyAsync(e->h_cs.data(), awvcs::batch_text(e), (size_t)c.cs_bytes, hipMemcpyDeviceToHost, e->stream));
     }
     if (int rc = timer_stop(c, c.d2h_ms)) return rc;
   }
@@ -1099,7 +1103,7 @@ void awv_engine_destroy(awv_engine* e) {
   e->normalize = nullptr;
   awve::state_release(e->encode);
   e->encode = nullptr;
-  awvx::state_release(e->cs);
+  awvcs::state_release(e->cs);
   e->cs = nullptr;
   e->seqs.release();
   e->ring_mem.release();
@@ -1327,7 +1331,7 @@ int awv_align_ranges_encoded(awv_engine* e, const awv_penalties* pen, const awv_
 namespace {
 // what every cs call refuses before anything is launched; match_bonus == 0: no clip, cout is not read
 int check_cs_args(int32_t cs_mode, const awv_cs_text* csout, awv_clip_result*& cout, int32_t match_bonus) {
-  if (!awvx::mode_ok(cs_mode)) return fail(AWV_ERR_ARG, "align_cs: cs_mode must be AWV_CS_SHORT or AWV_CS_LONG");
+  if (!awvcs::mode_ok(cs_mode)) return fail(AWV_ERR_ARG, "align_cs: cs_mode must be AWV_CS_SHORT or AWV_CS_LONG");
   if (!csout) return fail(AWV_ERR_ARG, "align_cs: null csout");
   if (match_bonus == 0) {
     cout = nullptr;
@@ -1358,7 +1362,7 @@ int awv_align_pairs_cs(awv_engine* e, const awv_penalties* pen, const awv_pair* 
   if (vout) awvf::stats_reset(e->verify);
   if (cout) awvc::stats_reset(e->clip);
   if (tout) awve::stats_reset(e->encode);
-  awvx::stats_reset(e->cs);
+  awvcs::stats_reset(e->cs);
   AWV_GUARDED(
     std::vector<int32_t> pb;
     AlignRequest rq = full_request(pairs, npairs, out, nullptr, user);
@@ -1374,7 +1378,7 @@ int awv_align_ranges_cs(awv_engine* e, const awv_penalties* pen, const awv_range
   if (int rc = check_cs_args(cs_mode, csout, cout, match_bonus)) return rc;
   if (cout) awvc::stats_reset(e->clip);
   if (tout) awve::stats_reset(e->encode);
-  awvx::stats_reset(e->cs);
+  awvcs::stats_reset(e->cs);
   AlignRequest rq = full_request(nullptr, 0, out, nullptr, user);
   cs_request(rq, max_penalty, match_bonus, vout, cout, tout, cs_mode, csout, sink);
   AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, rq);)
@@ -1593,7 +1597,7 @@ awvc::State*& awv_internal_clip(awv_engine* e) { return e->clip; }
 awvs::State*& awv_internal_split(awv_engine* e) { return e->split; }
 awvn::State*& awv_internal_normalize(awv_engine* e) { return e->normalize; }
 awve::State*& awv_internal_encode(awv_engine* e) { return e->encode; }
-awvx::State*& awv_internal_cs(awv_engine* e) { return e->cs; }
+awvcs::State*& awv_internal_cs(awv_engine* e) { return e->cs; }
 int32_t& awv_internal_normalize_mode(awv_engine* e) { return e->norm_mode; }
 uint64_t awv_internal_max_arena(const awv_engine* e) { return e->cfg.max_arena_bytes > 0 ? (uint64_t)e->cfg.max_arena_bytes : (uint64_t)8 << 30; }
 int awv_internal_fail(int code, const std::string& msg) { return fail(code, msg); }

@@ -51,6 +51,7 @@ struct KParams {
   int mirror;                 // 0: left, 1: right
 };
 
+using awvw::byte_at;
 using awvw::byte_range_mask;
 using awvw::CHUNK;
 using awvw::count_bytes;
@@ -60,12 +61,6 @@ using awvw::u32x4;
 using awvw::wave_scan_add;
 using awvw::wave_scan_max;
 using awvw::wave_sum_i64;
-
-__device__ __forceinline__ unsigned byte_at(const u32x4& w, int j) {  // byte j of a lane's 16, j in a register
-  const int k = j >> 2;
-  const unsigned d = k == 0 ? w[0] : k == 1 ? w[1] : k == 2 ? w[2] : w[3];
-  return (d >> (8 * (j & 3))) & 0xffu;
-}
 
 __global__ __launch_bounds__(64) void awv_normalize_kernel(KParams kp) {
   const int lane = threadIdx.x;
@@ -341,15 +336,8 @@ struct State : awvw::RecordPass {
   }
 };
 
-void state_release(State* s) {
-  if (!s) return;
-  s->release();
-  delete s;
-}
-
-void stats_reset(State* s) {
-  if (s) s->stats = awv_norm_stats{};
-}
+void state_release(State* s) { awvw::release_pass(s); }
+void stats_reset(State* s) { awvw::reset_stats(s); }
 
 namespace {
 
@@ -359,12 +347,7 @@ int check_direction(int32_t direction) {
   return AWV_OK;
 }
 
-int open_state(awv_engine* e, awp::EngineView& v, State*& st, bool need_set) {
-  State*& slot = awv_internal_normalize(e);
-  if (!slot) slot = new State();
-  st = slot;
-  return st->open(e, v, need_set);
-}
+int open_state(awv_engine* e, awp::EngineView& v, State*& st, bool need_set) { return awvw::open_pass(awv_internal_normalize(e), e, v, st, need_set); }
 
 // One launch over n records whose op bytes are on the device already.  Every index is checked here, on the host, as
 // RecordPass::begin checks every op string's place in the arena: the kernel reads and writes where the records say.

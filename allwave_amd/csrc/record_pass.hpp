@@ -1,8 +1,9 @@
 // record_pass.hpp -- the host skeleton of a record pass: a kernel with one wave per alignment record,
 // persistent waves taking records, longest op string first, from a cursor (awvw::take_record, wave_ops.hpp).  verify.hip,
-// clip.hip, split.hip, normalize.hip, encode.hip and cs.hip each keep a State that derives from RecordPass next to the buffers and stats only
-// that pass has; a launch is begin(), the pass's own uploads, clear_counters(), KParams, start(), the kernel, stop(),
-// the pass's own copy-backs, finish().
+// clip.hip, split.hip and normalize.hip (namespaces awvf, awvc, awvs, awvn) each keep a State that derives from RecordPass next
+// to the buffers and stats only that pass has; a launch is begin(), the pass's own uploads, clear_counters(), KParams, start(),
+// the kernel, stop(), the pass's own copy-backs, finish().  encode.hip and cs.hip (awve, awvcs) write text whose size depends on
+// the data: their State derives from TextPass (text_pass.hpp), which puts measure, scan and emit on the stream with these parts.
 #pragma once
 
 #include <algorithm>
@@ -105,5 +106,24 @@ struct RecordPass {
     return AWV_OK;
   }
 };
+
+// What stands around every pass's State (a RecordPass with the pass's `stats`), once: the engine keeps one per pass in a slot of
+// its own (engine.hip's awv_internal_*), made on first use; the functions a pass's *_device.hpp declares are one line each on these.
+template <typename State>
+int open_pass(State*& slot, awv_engine* e, awp::EngineView& v, State*& st, bool need_set) {
+  if (!slot) slot = new State();
+  st = slot;
+  return st->open(e, v, need_set);
+}
+template <typename State>
+void release_pass(State* s) {  // frees the buffers and the object itself (nullptr: nothing)
+  if (!s) return;
+  s->release();
+  delete s;
+}
+template <typename State>
+void reset_stats(State* s) {  // (nullptr: nothing)
+  if (s) s->stats = decltype(s->stats){};
+}
 
 }  // namespace awvw

@@ -143,15 +143,8 @@ struct State : awvw::RecordPass {
   }
 };
 
-void state_release(State* s) {
-  if (!s) return;
-  s->release();
-  delete s;
-}
-
-void stats_reset(State* s) {
-  if (s) s->stats = awv_split_stats{};
-}
+void state_release(State* s) { awvw::release_pass(s); }
+void stats_reset(State* s) { awvw::reset_stats(s); }
 
 namespace {
 
@@ -167,12 +160,8 @@ int check_args(const awv_penalties* p, int32_t match_bonus, int64_t min_score, a
   return AWV_OK;
 }
 
-int open_state(awv_engine* e, awp::EngineView& v, State*& st) {
-  State*& slot = awv_internal_split(e);
-  if (!slot) slot = new State();
-  st = slot;
-  return st->open(e, v, false);  // (the split reads no sequence: an engine without a set will do)
-}
+// (the split reads no sequence: an engine without a set will do)
+int open_state(awv_engine* e, awp::EngineView& v, State*& st) { return awvw::open_pass(awv_internal_split(e), e, v, st, false); }
 
 bool ascending(const uint64_t* seg_first, int64_t n) {
   for (int64_t i = 0; i < n; ++i)

@@ -224,15 +224,8 @@ struct State : awvw::RecordPass {
   }
 };
 
-void state_release(State* s) {
-  if (!s) return;
-  s->release();
-  delete s;
-}
-
-void stats_reset(State* s) {
-  if (s) s->stats = awv_verify_stats{};
-}
+void state_release(State* s) { awvw::release_pass(s); }
+void stats_reset(State* s) { awvw::reset_stats(s); }
 
 namespace {
 
@@ -245,12 +238,7 @@ int check_penalties(const awv_penalties* p, awv_penalties& out) {
   return AWV_OK;
 }
 
-int open_state(awv_engine* e, awp::EngineView& v, State*& st) {
-  State*& slot = awv_internal_verify(e);
-  if (!slot) slot = new State();
-  st = slot;
-  return st->open(e, v, true);
-}
+int open_state(awv_engine* e, awp::EngineView& v, State*& st) { return awvw::open_pass(awv_internal_verify(e), e, v, st, true); }
 
 // One launch over n pairs whose op bytes are on the device already.  Every index is checked here, on the host, as
 // RecordPass::begin checks every op string's place in the arena: the kernel reads what the records say.

@@ -1,6 +1,8 @@
-// wave_ops.hpp -- what the record kernels (verify.hip, clip.hip, split.hip, normalize.hip, encode.hip, cs.hip) share on the device: the take of
-// the next record from the cursor, the chunk a wave reads (64 lanes x 16 op bytes), wave64 inclusive scans on the DPP network
-// and packed byte counting over a lane's 16 bytes; and the device buffer their host sides keep (record_pass.hpp).
+// wave_ops.hpp -- what the record kernels (verify.hip, clip.hip, split.hip, normalize.hip, encode.hip, cs.hip: namespaces awvf,
+// awvc, awvs, awvn, awve, awvcs) share on the device, in namespace awvw: the take of the next record from the cursor, the chunk a
+// wave reads (64 lanes x 16 op bytes), wave64 inclusive scans on the DPP network, one byte of a lane's 16 and packed byte
+// counting over them; and the device buffer their host sides keep (record_pass.hpp).  What only the two text passes share on
+// the device is text_pass.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -86,6 +88,13 @@ __device__ __forceinline__ long long wave_scan_min(long long v) {
 // the value of the lane below (wave_shr 1); lane 0 keeps `lane0`
 __device__ __forceinline__ int from_lower_lane(int v, int lane0) { return dpp32<0x138, 0xf>(lane0, v); }
 __device__ __forceinline__ long long from_lower_lane(long long v, long long lane0) { return dpp64<0x138, 0xf>(lane0, v); }
+
+// byte j of a lane's 16, j in a register
+__device__ __forceinline__ unsigned byte_at(const u32x4& w, int j) {
+  const int k = j >> 2;
+  const unsigned d = k == 0 ? w[0] : k == 1 ? w[1] : k == 2 ? w[2] : w[3];
+  return (d >> (8 * (j & 3))) & 0xffu;
+}
 
 // 0xff in every byte j of a dword with lo <= j < hi (any lo, hi)
 __device__ __forceinline__ unsigned byte_range_mask(int lo, int hi) {

@@ -631,10 +631,6 @@ class Engine:
         (text_buf == NULL, text_cap == 0) and gives texts None; text_cap: the buffer's size (default: measured first, so that it
         fits) -- a buffer smaller than text_bytes is left untouched and comes back as it was, filled with 0xff."""
         results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
-        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
-        nbytes = int(arena.size)
-        if nbytes == 0:
-            arena = np.zeros(1, dtype=np.uint8)
         sl = None
         if slices is not None:
             sl = np.ascontiguousarray(np.asarray(slices, dtype=np.uint32).reshape(-1, 2))
@@ -642,23 +638,33 @@ class Engine:
                 raise ValueError("slices: need one (col_beg, col_end) per record")
             sl = sl if len(sl) else np.zeros((1, 2), dtype=np.uint32)
         tout = np.zeros(max(len(results), 1), dtype=CIGAR_TEXT_DTYPE)[:len(results)]
+        return self._text_call("awv_encode_cigars", (results.ctypes.data, len(results)), arena, sl, tout, want_text, text_cap)
+
+    def _text_call(self, fn, head, arena, sl, out, want_text, text_cap):
+        """The text calls awv_encode_cigars / awv_cs_cigars / awv_cs_ranges (`fn`): their arguments are the engine, `head`, the
+        arena (bytes or a uint8 array) and its size, the slices (`sl`: an array, or None), the per-record array `out`, the text
+        buffer and its size, and where the text's size goes.  Returns (texts, out, text_bytes) as encode_cigars documents."""
+        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
+        nbytes = int(arena.size)
+        if nbytes == 0:
+            arena = np.zeros(1, dtype=np.uint8)
         total = C.c_uint64(0)
 
         def call(buf, cap):
-            rc = load().awv_encode_cigars(self._h, results.ctypes.data, len(results), arena.ctypes.data, nbytes, None if sl is None else sl.ctypes.data,
-                                          tout.ctypes.data, None if buf is None else buf.ctypes.data, cap, C.byref(total))
+            rc = getattr(load(), fn)(self._h, *head, arena.ctypes.data, nbytes, None if sl is None else sl.ctypes.data, out.ctypes.data,
+                                     None if buf is None else buf.ctypes.data, cap, C.byref(total))
             if rc != AWV_OK:
-                raise EngineError(rc, "awv_encode_cigars")
+                raise EngineError(rc, fn)
 
         if not want_text:
             call(None, 0)
-            return None, tout, int(total.value)
+            return None, out, int(total.value)
         if text_cap is None:
             call(None, 0)
             text_cap = int(total.value)
         text = np.full(max(int(text_cap), 1), 0xff, dtype=np.uint8)
         call(text, int(text_cap))
-        return text[:int(text_cap)], tout, int(total.value)
+        return text[:int(text_cap)], out, int(total.value)
 
     def cs_cigars(self, cs, pairs, results, arena, slices=None, want_text=True, text_cap=None):
         """awv_cs_cigars: the cs texts ("short" / "long") of caller-supplied records (a RESULT_DTYPE array whose cigar_off /
@@ -678,10 +684,6 @@ class Engine:
         results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
         if results.shape != (len(pairs),):
             raise ValueError("results: need one record per pair")
-        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
-        nbytes = int(arena.size)
-        if nbytes == 0:
-            arena = np.zeros(1, dtype=np.uint8)
         sl = None
         if slices is not None:
             if isinstance(slices, np.ndarray) and slices.dtype == CS_SLICE_DTYPE:
@@ -695,49 +697,28 @@ class Engine:
                 raise ValueError("slices: need one slice per record")
             sl = sl if len(sl) else np.zeros(1, dtype=CS_SLICE_DTYPE)
         csout = np.zeros(max(len(results), 1), dtype=CS_TEXT_DTYPE)[:len(results)]
-        total = C.c_uint64(0)
+        return self._text_call(fn, (mode, pairs.ctypes.data, len(pairs), results.ctypes.data), arena, sl, csout, want_text, text_cap)
 
-        def call(buf, cap):
-            rc = getattr(load(), fn)(self._h, mode, pairs.ctypes.data, len(pairs), results.ctypes.data, arena.ctypes.data, nbytes,
-                                     None if sl is None else sl.ctypes.data, csout.ctypes.data, None if buf is None else buf.ctypes.data, cap,
-                                     C.byref(total))
-            if rc != AWV_OK:
-                raise EngineError(rc, fn)
-
-        if not want_text:
-            call(None, 0)
-            return None, csout, int(total.value)
-        if text_cap is None:
-            call(None, 0)
-            text_cap = int(total.value)
-        text = np.full(max(int(text_cap), 1), 0xff, dtype=np.uint8)
-        call(text, int(text_cap))
-        return text[:int(text_cap)], csout, int(total.value)
+    def _stats(self, fn_name, cls):
+        """One of the awv_engine_*_stats getters: the engine's `cls` record."""
+        st = cls()
+        rc = getattr(load(), fn_name)(self._h, C.byref(st))
+        if rc != AWV_OK:
+            raise EngineError(rc, fn_name)
+        return st
 
     def cs_stats(self):
         """awv_engine_cs_stats: kernel_ms, pairs, failed, text_bytes, columns of the last cs call."""
-        st = CsStats()
-        rc = load().awv_engine_cs_stats(self._h, C.byref(st))
-        if rc != AWV_OK:
-            raise EngineError(rc, "awv_engine_cs_stats")
-        return st
+        return self._stats("awv_engine_cs_stats", CsStats)
 
     def encode_stats(self):
         """awv_engine_encode_stats: kernel_ms, pairs, runs, text_bytes, columns of the last encoding call."""
-        st = EncodeStats()
-        rc = load().awv_engine_encode_stats(self._h, C.byref(st))
-        if rc != AWV_OK:
-            raise EngineError(rc, "awv_engine_encode_stats")
-        return st
+        return self._stats("awv_engine_encode_stats", EncodeStats)
 
     def normalize_stats(self):
         """awv_engine_normalize_stats: kernel_ms, pairs, records_moved, runs, runs_moved, columns_moved, columns of the last
         normalizing call."""
-        st = NormStats()
-        rc = load().awv_engine_normalize_stats(self._h, C.byref(st))
-        if rc != AWV_OK:
-            raise EngineError(rc, "awv_engine_normalize_stats")
-        return st
+        return self._stats("awv_engine_normalize_stats", NormStats)
 
     def clip_cigars(self, scores, match_bonus, results, arena):
         """awv_clip_cigars: clips caller-supplied records (a RESULT_DTYPE array whose cigar_off / cigar_len point into `arena`,
@@ -787,27 +768,15 @@ class Engine:
 
     def split_stats(self):
         """awv_engine_split_stats: kernel_ms, pairs, segments, empty, columns, columns_scanned of the last splitting call."""
-        st = SplitStats()
-        rc = load().awv_engine_split_stats(self._h, C.byref(st))
-        if rc != AWV_OK:
-            raise EngineError(rc, "awv_engine_split_stats")
-        return st
+        return self._stats("awv_engine_split_stats", SplitStats)
 
     def clip_stats(self):
         """awv_engine_clip_stats: kernel_ms, pairs, empty, columns of the last clipping call."""
-        st = ClipStats()
-        rc = load().awv_engine_clip_stats(self._h, C.byref(st))
-        if rc != AWV_OK:
-            raise EngineError(rc, "awv_engine_clip_stats")
-        return st
+        return self._stats("awv_engine_clip_stats", ClipStats)
 
     def verify_stats(self):
         """awv_engine_verify_stats: kernel_ms, pairs, failed, columns of the last verifying call."""
-        st = VerifyStats()
-        rc = load().awv_engine_verify_stats(self._h, C.byref(st))
-        if rc != AWV_OK:
-            raise EngineError(rc, "awv_engine_verify_stats")
-        return st
+        return self._stats("awv_engine_verify_stats", VerifyStats)
 
     def score_pairs(self, scores, pairs, max_penalty=None):
         """Score-only alignment (awv_score_pairs): the optimal penalty of every pair, no CIGAR.  pairs as for align_pairs.
@@ -862,11 +831,7 @@ class Engine:
         return res[0], buf.raw[:int(res[0]["cigar_len"])]
 
     def stats(self):
-        st = Stats()
-        rc = load().awv_engine_stats(self._h, C.byref(st))
-        if rc != AWV_OK:
-            raise EngineError(rc, "awv_engine_stats")
-        return st
+        return self._stats("awv_engine_stats", Stats)
 
     def twin_stats(self):
         """awv_twin_stats of the last align_pairs call: (twin units, searches run shared, searches run per orientation

@@ -34,18 +34,18 @@ int main() {
     rec.status = AWV_ST_COMPLETED;
     rec.cigar_len = (uint32_t)ops.size();
     const awv_cs_slice sl{(uint32_t)beg, (uint32_t)end, (int32_t)q_skip, (int32_t)t_skip};
-    const bool ok = awvx::mode_ok((int32_t)mode) && awvx::slice_ok(rec, sl);
-    awv_cs_text t = awvx::make_text(0, 0, AWV_CST_SKIPPED);
+    const bool ok = awvcs::mode_ok((int32_t)mode) && awvcs::slice_ok(rec, sl);
+    awv_cs_text t = awvcs::make_text(0, 0, AWV_CST_SKIPPED);
     std::vector<uint8_t> out((size_t)cap, 0xee);
     if (ok) {
-      awvx::Span sp{0, (int32_t)pattern.size(), 0, (int32_t)text.size()};
-      awvx::apply_slice(rec, sp, sl);
+      awvcs::Span sp{0, (int32_t)pattern.size(), 0, (int32_t)text.size()};
+      awvcs::apply_slice(rec, sp, sl);
       // exact-size copies of what the record and the rectangle name (a rectangle of negative length names nothing)
       const std::vector<uint8_t> c(ops.begin() + (long)rec.cigar_off, ops.begin() + (long)rec.cigar_off + rec.cigar_len);
       const int plen = sp.pe - sp.pb, tlen = sp.te - sp.tb;
       const std::vector<uint8_t> p(pattern.begin() + (plen > 0 ? sp.pb : 0), pattern.begin() + (plen > 0 ? sp.pe : 0));
       const std::vector<uint8_t> x(text.begin() + (tlen > 0 ? sp.tb : 0), text.begin() + (tlen > 0 ? sp.te : 0));
-      t = awvx::cs_one((int32_t)mode, p.data(), plen, x.data(), tlen, c.data(), (int64_t)c.size(), 0, 0, out.empty() ? nullptr : out.data(), (uint64_t)cap);
+      t = awvcs::cs_one((int32_t)mode, p.data(), plen, x.data(), tlen, c.data(), (int64_t)c.size(), 0, 0, out.empty() ? nullptr : out.data(), (uint64_t)cap);
     }
     bool written = false;
     for (uint8_t b : out) written = written || b != 0xee;

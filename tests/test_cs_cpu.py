@@ -182,7 +182,7 @@ def test_exports_struct_sizes_and_constants(hip_lib):
     assert hip_lib.awv_abi_version() == 3 and "#define AWV_ABI_VERSION 3" in hdr
     assert not any(n.endswith("_cs") and "split" in n for n in ffi.EXPORTS)  # the split has no cs form
     blob = open(ffi.LIB_PATH, "rb").read()
-    assert b"awv_cs_kernel" in blob and b"awv_cs_scan_kernel" in blob  # native kernels, in the gfx950 code object
+    assert b"awv_cs_kernel" in blob and b"awv_text_scan_kernelI11awv_cs_text" in blob  # native kernels, in the gfx950 code object
     # a null engine is refused before anything else is read: "no device" where there is none (the yardstick needs none), else a bad argument
     total = C.c_uint64(0)
     for fn in (hip_lib.awv_cs_cigars, hip_lib.awv_cs_ranges):

@@ -131,7 +131,7 @@ def test_exports_struct_sizes_and_constants(hip_lib):
     assert hip_lib.awv_abi_version() == 3 and "#define AWV_ABI_VERSION 3" in hdr
     assert not any(n.endswith("_encoded") and "split" in n for n in ffi.EXPORTS)  # the split has no encoded form
     blob = open(ffi.LIB_PATH, "rb").read()
-    assert b"awv_encode_kernel" in blob and b"awv_encode_scan_kernel" in blob  # native kernels, in the gfx950 code object
+    assert b"awv_encode_kernel" in blob and b"awv_text_scan_kernelI14awv_cigar_text" in blob  # native kernels, in the gfx950 code object
     # a null engine is refused before anything else is read: "no device" where there is none (the yardstick needs none), else a bad argument
     total = C.c_uint64(0)
     assert hip_lib.awv_encode_cigars(None, None, 0, None, 0, None, None, None, 0, C.byref(total)) in (ffi.AWV_ERR_NO_DEVICE, ffi.AWV_ERR_ARG)

@@ -77,6 +77,28 @@ def test_cs_cigars_in_several_pieces(hip_lib, cases):
         e.close()
 
 
+@pytest.mark.parametrize("mode", X.MODES)
+def test_cs_cigars_all_of_the_text_or_none_across_pieces(hip_lib, cases, mode):
+    """More than ten pieces and a buffer that the text outgrows at the last piece, halfway or at the first: csout and text_bytes
+    are the fitting call's, and not one byte of the buffer is written."""
+    from allwave_amd import ffi
+    _, seqs, pairs, recs, arena, _ = cases
+    e = ffi.Engine(device=0, flags=ffi.AWV_F_NO_ARENA_PROBE, max_arena_bytes=200000)
+    try:
+        assert len(arena) > 10 * 200000
+        e.set_sequences(seqs)
+        full, cs0, total0 = e.cs_cigars(mode, pairs, recs, arena)
+        assert len(full) == total0 > 2
+        for cap in (total0 - 1, total0 // 2, 1):
+            buf, csout, total = e.cs_cigars(mode, pairs, recs, arena, text_cap=cap)
+            assert len(buf) == cap and (buf == 0xff).all() and csout.tobytes() == cs0.tobytes() and total == total0, cap
+        buf, csout, total = e.cs_cigars(mode, pairs, recs, arena, text_cap=total0 + 9)
+        assert bytes(buf[:total0]) == bytes(full) and (buf[total0:] == 0xff).all() and len(buf) == total0 + 9
+        assert csout.tobytes() == cs0.tobytes() and total == total0
+    finally:
+        e.close()
+
+
 @pytest.fixture(scope="module")
 def alignment_engine(hip_lib):
     """An engine whose resident set is the 300 random alignments: sequence 2 k is alignment k's pattern, 2 k + 1 its text."""

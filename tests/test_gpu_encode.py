@@ -65,6 +65,26 @@ def test_encode_cigars_in_several_pieces(hip_lib, cases):
         e.close()
 
 
+def test_encode_cigars_all_of_the_text_or_none_across_pieces(hip_lib, cases):
+    """More than ten pieces and a buffer that the text outgrows at the last piece, halfway or at the first: tout and text_bytes are
+    the fitting call's, and not one byte of the buffer is written."""
+    from allwave_amd import ffi
+    _, recs, arena, _ = cases
+    e = ffi.Engine(device=0, flags=ffi.AWV_F_NO_ARENA_PROBE, max_arena_bytes=200000)
+    try:
+        assert len(arena) > 10 * 200000
+        full, tout0, total0 = e.encode_cigars(recs, arena)
+        assert len(full) == total0 > 2
+        for cap in (total0 - 1, total0 // 2, 1):
+            buf, tout, total = e.encode_cigars(recs, arena, text_cap=cap)
+            assert len(buf) == cap and (buf == 0xff).all() and tout.tobytes() == tout0.tobytes() and total == total0, cap
+        buf, tout, total = e.encode_cigars(recs, arena, text_cap=total0 + 9)
+        assert bytes(buf[:total0]) == bytes(full) and (buf[total0:] == 0xff).all() and len(buf) == total0 + 9
+        assert tout.tobytes() == tout0.tobytes() and total == total0
+    finally:
+        e.close()
+
+
 @pytest.fixture(scope="module")
 def bare_engine(hip_lib):
     from allwave_amd import ffi
