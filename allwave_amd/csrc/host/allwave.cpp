@@ -364,6 +364,7 @@ void RunOptions::apply(AllPairIterator& it) const {
   if (normalize != AWV_NORM_OFF) it.with_normalize(normalize);
   if (device_cigar) it.with_device_cigar(true);
   if (cs != 0) it.with_cs(cs);
+  if (coverage != 0) it.with_coverage(coverage);
   if (max_penalty) it.with_max_penalty(*max_penalty);
   if (max_divergence) it.with_max_divergence(*max_divergence);
   if (clip_match_bonus != 0) it.with_clip(clip_match_bonus, clip_min_score);
@@ -541,6 +542,7 @@ AllPairIterator AllPairIterator::with_sparsification(SparsificationStrategy stra
   it.normalize_ = normalize_;
   it.device_cigar_ = device_cigar_;
   it.cs_ = cs_;
+  it.coverage_ = coverage_;
   return it;
 }
 AllPairIterator& AllPairIterator::with_device_cigar(bool on) {
@@ -552,6 +554,11 @@ AllPairIterator& AllPairIterator::with_cs(int mode) {
   if (mode != 0 && mode != AWV_CS_SHORT && mode != AWV_CS_LONG) throw std::invalid_argument("with_cs: 0, AWV_CS_SHORT or AWV_CS_LONG");
   if (mode != 0 && split()) throw std::invalid_argument("with_cs: not together with with_split");
   cs_ = mode;
+  return *this;
+}
+AllPairIterator& AllPairIterator::with_coverage(int roles) {
+  if (roles < 0 || roles > AWV_COV_BOTH) throw std::invalid_argument("with_coverage: 0, AWV_COV_TARGET, AWV_COV_QUERY or AWV_COV_BOTH");
+  coverage_ = roles;
   return *this;
 }
 AllPairIterator& AllPairIterator::with_normalize(int direction) {
@@ -764,6 +771,14 @@ void add(awv_cs_stats& acc, const awv_cs_stats& x) {
   acc.text_bytes += x.text_bytes;
   acc.columns += x.columns;
 }
+void add(awv_cov_stats& acc, const awv_cov_stats& x) {
+  acc.kernel_ms += x.kernel_ms;
+  acc.items += x.items;
+  acc.failed += x.failed;
+  acc.columns += x.columns;
+  acc.boundaries += x.boundaries;
+  acc.reads += x.reads;
+}
 void add(RunReport& acc, const RunReport& x) {
   acc.verify_failures.insert(acc.verify_failures.end(), x.verify_failures.begin(), x.verify_failures.end());
   add(acc.verify_stats, x.verify_stats);
@@ -773,6 +788,7 @@ void add(RunReport& acc, const RunReport& x) {
   add(acc.normalize_stats, x.normalize_stats);
   add(acc.encode_stats, x.encode_stats);
   add(acc.cs_stats, x.cs_stats);
+  add(acc.coverage_stats, x.coverage_stats);
 }
 
 // One batch's engine call, by name.  ranges (nullable): the batch is these n interval pairs, `pairs` is not read.  Alignment
@@ -844,6 +860,7 @@ int engine_call(awv_engine* e, const EngineRequest& q, awv_sink sink, awv_cs_sin
 struct AllPairIterator::SlotTotals {
   awv_stats engine{};
   RunReport report;
+  std::vector<uint32_t> cov_aligned, cov_matched;  // a coverage run: the slot's tracks, read when its batches are done
 };
 
 // What the slots of one run share.  The settings hold for alignment calls only: a score-only run has none of them.
@@ -856,6 +873,8 @@ struct AllPairIterator::RunState {
   std::vector<uint8_t> mash_rev;             // mash orientation of the whole range, computed up front
   bool verify = false, bounded = false, clipping = false, splitting = false, encoding = false;
   int cs = 0;  // the cs mode of the run's alignment calls (0: none)
+  int coverage = 0;  // the roles of a run that accumulates the per-base depth (0: none)
+  uint64_t n_bases = 0;  // the sum of the sequences' lengths
   int normalizing = AWV_NORM_OFF;
   std::optional<double> div;  // the divergence bound of a bounded run
   awv_penalties pen{}, open{};
@@ -1102,6 +1121,8 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   rs.encoding = call.encode && !call.score_only;
   rs.cs = call.score_only ? 0 : call.cs;
   rs.normalizing = call.score_only ? AWV_NORM_OFF : normalize_;
+  rs.coverage = call.score_only ? 0 : coverage_;
+  for (const Sequence& q : sequences_) rs.n_bases += q.seq.size();
   rs.div = divergence_bound();
   rs.pen = to_penalties(params_);
   rs.open = to_penalties(orientation_params_);
@@ -1118,6 +1139,8 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
       rs.lap("engine created");
       upload(e, sequences_);
       rs.lap("sequences uploaded");
+      // (a new set ended whatever coverage the engine had: the slot's depth starts from zero with every run)
+      if (rs.coverage != 0 && awv_engine_coverage_begin(e, rs.coverage, clip_min_score_) != AWV_OK) throw AlignmentError(std::string("coverage: ") + awv_last_error());
     } catch (...) {
       rs.fail(std::current_exception());
     }
@@ -1143,9 +1166,19 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
           throw AlignmentError(std::string("align_pairs: ") + awv_last_error());
         }
       }
+      if (rs.coverage != 0 && !rs.stop.load()) {  // the slot's depth, and what it cost
+        SlotTotals& t = rs.totals[s];
+        t.cov_aligned.assign((size_t)rs.n_bases, 0);
+        t.cov_matched.assign((size_t)rs.n_bases, 0);
+        if (awv_engine_coverage_read(e, t.cov_aligned.data(), t.cov_matched.data(), rs.n_bases) != AWV_OK) throw AlignmentError(std::string("coverage: ") + awv_last_error());
+        awv_cov_stats cx{};
+        awv_engine_coverage_stats(e, &cx);
+        add(t.report.coverage_stats, cx);
+      }
     } catch (...) {
       rs.fail(std::current_exception());
     }
+    if (e && rs.coverage != 0) awv_engine_coverage_begin(e, 0, 0);  // the accumulators go with the run
   };
   std::vector<std::thread> th;
   try {
@@ -1162,10 +1195,21 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   slot_stats_.clear();
   stats_ = awv_stats{};
   if (first == 0) report_ = RunReport{};  // a run from the list's start begins anew; a later range (next()'s chunks) adds to it
+  if (first == 0 && !call.score_only) cov_ = Coverage{};
+  if (rs.coverage != 0 && cov_.offsets.empty()) {
+    cov_.offsets.assign(sequences_.size() + 1, 0);
+    for (size_t i = 0; i < sequences_.size(); ++i) cov_.offsets[i + 1] = cov_.offsets[i] + sequences_[i].seq.size();
+    cov_.aligned.assign((size_t)rs.n_bases, 0);
+    cov_.matched.assign((size_t)rs.n_bases, 0);
+  }
   for (const SlotTotals& t : rs.totals) {
     slot_stats_.push_back(t.engine);
     add_stats(stats_, t.engine, false);
     add(report_, t.report);
+    for (size_t i = 0; i < t.cov_aligned.size(); ++i) {  // the slots' depths add up to the one-engine result
+      cov_.aligned[i] += t.cov_aligned[i];
+      cov_.matched[i] += t.cov_matched[i];
+    }
   }
   sort_verify_failures(report_.verify_failures);
   if (rs.err) std::rethrow_exception(rs.err);

@@ -147,7 +147,7 @@ class AllPairIterator;
 
 // The options of one run that filter or rewrite what it delivers, in one place: AllPairIterator::with_max_penalty,
 // with_max_divergence (std::nullopt: no bound), with_clip and with_split (match bonus 0: off), with_normalize (AWV_NORM_OFF: off),
-// with_device_cigar, with_cs (0: off).
+// with_device_cigar, with_cs (0: off), with_coverage (0: off).
 struct RunOptions {
   std::optional<int> max_penalty;
   std::optional<double> max_divergence;
@@ -158,8 +158,9 @@ struct RunOptions {
   int normalize = AWV_NORM_OFF;
   bool device_cigar = false;
   int cs = 0;
+  int coverage = 0;
   void apply(AllPairIterator& it) const;  // the with_* calls of what is set; they throw std::invalid_argument as documented there
-  bool any() const { return max_penalty || max_divergence || clip_match_bonus != 0 || split_match_bonus != 0 || normalize != AWV_NORM_OFF || device_cigar || cs != 0; }
+  bool any() const { return max_penalty || max_divergence || clip_match_bonus != 0 || split_match_bonus != 0 || normalize != AWV_NORM_OFF || device_cigar || cs != 0 || coverage != 0; }
 };
 
 // What a run leaves behind besides its results (AllPairIterator::last_report): the failed checks sorted by pair-list index,
@@ -173,6 +174,14 @@ struct RunReport {
   awv_norm_stats normalize_stats{};
   awv_encode_stats encode_stats{};
   awv_cs_stats cs_stats{};
+  awv_cov_stats coverage_stats{};
+};
+
+// The per-base depth a run with with_coverage leaves behind (AllPairIterator::last_coverage): sequence s owns entries
+// [offsets[s], offsets[s + 1]) of both tracks, one per forward-strand base.  Empty without the setting.
+struct Coverage {
+  std::vector<uint64_t> offsets;
+  std::vector<uint32_t> aligned, matched;
 };
 
 class AllPairIterator {  // iterator.rs:12-171
@@ -278,6 +287,17 @@ class AllPairIterator {  // iterator.rs:12-171
   int cs() const { return cs_; }
   // of the last run, summed over the slots (kernel_ms: summed kernel time)
   awv_cs_stats last_cs_stats() const { return report_.cs_stats; }
+  // Every alignment consumer also accumulates the per-base depth of what the engine aligned (awv_engine_coverage_begin;
+  // include/allwave_hip.h has the contract): roles is AWV_COV_TARGET, AWV_COV_QUERY or AWV_COV_BOTH, 0: off.  Every slot's engine
+  // begins at a run's start -- with with_clip's min_score as its clip_min_score -- and is read at the run's end; the slots' arrays
+  // are summed on the host, so several devices, and one ordinal given twice, give the one-engine result exactly.  What counts is
+  // what the contract says: with_clip's slices that reach min_score, with_split's segments, else every completed record, after
+  // with_normalize; the strand alignments of WFA orientation do not count, nor does scores().  (A completed pair that only
+  // with_max_divergence's host-side test drops has been aligned under its bound, and counts.)  Results, lines and the other
+  // counters are those of the run without the setting.  next() accumulates since the list's start, like the report.
+  AllPairIterator& with_coverage(int roles);
+  int coverage() const { return coverage_; }
+  const Coverage& last_coverage() const { return cov_; }
   AllPairIterator& with_max_penalty(int max_penalty);
   AllPairIterator& with_max_divergence(double max_divergence);
   // of the last run (next(): of the chunks since the list's start), summed over the slots
@@ -389,6 +409,8 @@ class AllPairIterator {  // iterator.rs:12-171
   int normalize_ = AWV_NORM_OFF;  // with_normalize
   bool device_cigar_ = false;     // with_device_cigar
   int cs_ = 0;                    // with_cs (0: off)
+  int coverage_ = 0;              // with_coverage (0: off)
+  Coverage cov_;                  // of the last run (next(): since the list's start)
   int split_bonus_ = 0;  // with_split (0: off)
   int64_t split_min_score_ = 1;
   bool drops_pairs() const { return bounded() || clip() || split(); }  // consumers that keep a slot per pair compact what was delivered
@@ -425,6 +447,7 @@ class AllPairParallelIterator {
   awv_norm_stats last_normalize_stats() const { return it_.last_normalize_stats(); }
   awv_encode_stats last_encode_stats() const { return it_.last_encode_stats(); }
   awv_cs_stats last_cs_stats() const { return it_.last_cs_stats(); }
+  const Coverage& last_coverage() const { return it_.last_coverage(); }
   const RunReport& last_report() const { return it_.last_report(); }
  private:
   friend class AllPairIterator;

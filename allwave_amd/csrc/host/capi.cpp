@@ -20,12 +20,14 @@ void set_err(char* err, size_t cap, const std::string& m) {
 // What the calling thread's last alignment hook left behind, its iterator's last_report(): the verify counters and failures
 // for awh_last_verify, the other counters for awh_last_bounds, awh_last_clip, awh_last_split, awh_last_normalize, awh_last_encode and awh_last_cs.
 thread_local RunReport g_report;
+thread_local Coverage g_coverage;  // and its last_coverage(), for awh_last_coverage
 template <typename It>
 void keep(const It& it) {
   g_report = it.last_report();
+  g_coverage = it.last_coverage();
 }
 // The options of the calling thread's NEXT alignment hook: awh_set_bounds, awh_set_clip, awh_set_split, awh_set_normalize and
-// awh_set_device_cigar, awh_set_cs
+// awh_set_device_cigar, awh_set_cs, awh_set_coverage
 // leave them here; the hook takes them (they hold for that one call) and starts the counters they go with afresh.
 thread_local RunOptions g_next;
 RunOptions take_run_options() {
@@ -37,6 +39,8 @@ RunOptions take_run_options() {
   g_report.normalize_stats = awv_norm_stats{};
   g_report.encode_stats = awv_encode_stats{};
   g_report.cs_stats = awv_cs_stats{};
+  g_report.coverage_stats = awv_cov_stats{};
+  g_coverage = Coverage{};
   return o;
 }
 // the hooks' orientation code on an iterator: 0 forward, 1 WFA, 2 mash, 3 WFA by two full alignments per pair
@@ -693,6 +697,31 @@ void awh_last_cs(uint64_t out[4], double* kernel_ms) {
   out[2] = g_report.cs_stats.text_bytes;
   out[3] = g_report.cs_stats.columns;
   *kernel_ms = g_report.cs_stats.kernel_ms;
+}
+// ---- per-base depth ----
+// The calling thread's NEXT alignment hook runs with_coverage(roles) (AWV_COV_*; 0: off); the hooks after it run without again.
+void awh_set_coverage(int roles) { g_next.coverage = roles; }
+// last_coverage() of the calling thread's last alignment hook.  *n_offsets is the number of sequences + 1, or 0 for a call without
+// coverage; the three arrays are malloc'd copies (awh_free each), offsets[*n_offsets - 1] entries per track.  stats:
+// {items, failed, columns, boundaries, reads} and the summed kernel time.  Returns -1 when memory runs out.
+int awh_last_coverage(uint64_t** offsets, size_t* n_offsets, uint32_t** aligned, uint32_t** matched, uint64_t stats[5], double* kernel_ms) {
+  const awv_cov_stats& cs = g_report.coverage_stats;
+  stats[0] = cs.items; stats[1] = cs.failed; stats[2] = cs.columns; stats[3] = cs.boundaries; stats[4] = cs.reads;
+  *kernel_ms = cs.kernel_ms;
+  *n_offsets = g_coverage.offsets.size();
+  const size_t nb = g_coverage.aligned.size();
+  *offsets = (uint64_t*)malloc(std::max<size_t>(*n_offsets, 1) * sizeof(uint64_t));
+  *aligned = (uint32_t*)malloc(std::max<size_t>(nb, 1) * sizeof(uint32_t));
+  *matched = (uint32_t*)malloc(std::max<size_t>(nb, 1) * sizeof(uint32_t));
+  if (!*offsets || !*aligned || !*matched) {
+    free(*offsets); free(*aligned); free(*matched);
+    *offsets = nullptr; *aligned = *matched = nullptr; *n_offsets = 0;
+    return -1;
+  }
+  if (*n_offsets) memcpy(*offsets, g_coverage.offsets.data(), *n_offsets * sizeof(uint64_t));
+  if (nb) memcpy(*aligned, g_coverage.aligned.data(), nb * sizeof(uint32_t));
+  if (nb) memcpy(*matched, g_coverage.matched.data(), nb * sizeof(uint32_t));
+  return 0;
 }
 // last_encode_stats() of the calling thread's last alignment hook: {pairs, runs, text_bytes, columns} and the summed kernel time
 void awh_last_encode(uint64_t out[4], double* kernel_ms) {

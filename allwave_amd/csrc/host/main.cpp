@@ -58,6 +58,10 @@ struct Args {
   bool have_normalize = false;
   bool device_cigar = false;  // --device-cigar: the run-length text behind cg:Z: is made on the device
   int cs = 0;                 // --cs short|long: every line gains minimap2's cs:Z: tag, made on the device (0: off)
+  std::string coverage;       // --coverage FILE: the per-base depth of what was aligned, accumulated on the device
+  bool have_coverage = false;
+  int coverage_of = AWV_COV_BOTH;  // --coverage-of target|query|both
+  bool have_coverage_of = false;
 };
 
 [[noreturn]] void die(const std::string& m, int code = 2) {
@@ -255,6 +259,17 @@ int main(int argc, char** argv) {
       if (v != "short" && v != "long") die("--cs expects short or long");
       a.cs = v == "short" ? AWV_CS_SHORT : AWV_CS_LONG;
     }
+    else if (k == "--coverage") {
+      a.coverage = val();
+      if (a.coverage.empty()) die("--coverage expects a file name");
+      a.have_coverage = true;
+    }
+    else if (k == "--coverage-of") {
+      const std::string v = val();
+      if (v != "target" && v != "query" && v != "both") die("--coverage-of expects target, query or both");
+      a.coverage_of = v == "target" ? AWV_COV_TARGET : v == "query" ? AWV_COV_QUERY : AWV_COV_BOTH;
+      a.have_coverage_of = true;
+    }
     else if (k == "--clip" || k == "--clip-min-score") {
       const std::string v = val();
       char* end = nullptr;
@@ -290,10 +305,12 @@ int main(int argc, char** argv) {
                    "                   [--device N | --devices LIST] [--shard R/N] [--score-only [--max-penalty N]] [--plan-device N] [--verify]\n"
                    "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
                    "                   [--split A --split-min-score S] [--normalize left|right] [--device-cigar] [--cs short|long]\n"
+                   "                   [--coverage FILE [--coverage-of target|query|both]]\n"
                    "       allwave_hip -i in.fa --check-paf FILE [-s scores | -x ANI] [--check-optimal] [--partial] [--device N]\n"
                    "       allwave_hip -i in.fa --align-paf FILE [-s scores | -x ANI] [-o out.paf] [--verify] [--score-only] [--device N | --devices LIST]\n"
                    "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
                    "                   [--split A --split-min-score S] [--normalize left|right] [--device-cigar] [--cs short|long]\n"
+                   "                   [--coverage FILE [--coverage-of target|query|both]]\n"
                    "  --verify         check every alignment on the device before it is written (columns, counts, penalty); the summary\n"
                    "                   line gains `verified N pairs, F failed, K ms`, failures go to stderr, exit status 4 if any\n"
                    "  --check-paf FILE align nothing: check every line of FILE (12 columns + cg:Z:) against in.fa on the device; one line\n"
@@ -335,6 +352,14 @@ int main(int argc, char** argv) {
                    "                   --normalize, --verify, --clip and --device-cigar from the op string and the sequences: short writes\n"
                    "                   :N for N matches, long =BASES; also with --align-paf; not with --split; the summary line gains\n"
                    "                   `cs N pairs, F failed, B text bytes, K ms`\n"
+                   "  --coverage FILE  accumulate on the device, for every base of every sequence, in how many of the run's alignments it is\n"
+                   "                   aligned (= or X) and in how many it matches, and write FILE: one line name<TAB>beg<TAB>end<TAB>aligned<TAB>\n"
+                   "                   matched per maximal interval on which both are constant, every sequence end to end, in input order; what\n"
+                   "                   counts is what is written (the clip under --clip, every segment under --split, after --normalize); the\n"
+                   "                   PAF is byte-identical; also with --align-paf; not with --score-only, --check-paf or --mash-matrix; under\n"
+                   "                   --shard every process writes the depth of its own shard to its own FILE (add the files up by\n"
+                   "                   position); the summary line gains `coverage I items, B boundaries, K ms`\n"
+                   "  --coverage-of target|query|both  whose bases an aligned column counts for (default both)\n"
                    "  --plan-device N  plan on device N: --mash-matrix, the -p pair list and mash orientation (the same output as\n"
                    "                   the host planner; with --shard every rank plans the whole list on its own plan device)\n";
       return 0;
@@ -371,6 +396,10 @@ int main(int argc, char** argv) {
   if (a.cs != 0 && a.score_only) die("the argument '--cs' cannot be used with '--score-only'");
   if (a.cs != 0 && a.have_check_paf) die("the argument '--cs' cannot be used with '--check-paf'");
   if (a.cs != 0 && a.mash_matrix) die("the argument '--cs' cannot be used with '--mash-matrix'");
+  if (a.have_coverage_of && !a.have_coverage) die("the argument '--coverage-of' requires '--coverage'");
+  if (a.have_coverage && a.score_only) die("the argument '--coverage' cannot be used with '--score-only'");
+  if (a.have_coverage && a.have_check_paf) die("the argument '--coverage' cannot be used with '--check-paf'");
+  if (a.have_coverage && a.mash_matrix) die("the argument '--coverage' cannot be used with '--mash-matrix'");
   if (a.check_optimal && !a.have_check_paf) die("the argument '--check-optimal' requires '--check-paf'");
   if (a.verify && a.score_only) die("the argument '--verify' cannot be used with '--score-only'");
   if (a.verify && a.mash_matrix) die("the argument '--verify' cannot be used with '--mash-matrix'");
@@ -489,6 +518,7 @@ int main(int argc, char** argv) {
     if (a.have_normalize) it.with_normalize(a.normalize);
     it.with_device_cigar(a.device_cigar);
     it.with_cs(a.cs);
+    if (a.have_coverage) it.with_coverage(a.coverage_of);
     if (a.forward_only) it.with_orientation(Orientation::ForwardOnly);
     it.with_full_wfa_orientation(a.wfa_orientation_full);
     it.with_devices(devices);
@@ -546,6 +576,28 @@ int main(int argc, char** argv) {
       fout.close();
       if (fout.fail()) die("write error on the PAF output (close)", 1);
     }
+    if (a.have_coverage) {  // name, beg, end, aligned, matched per maximal interval on which both tracks are constant
+      const Coverage& cv = it.last_coverage();
+      std::ofstream cout_(a.coverage, std::ios::binary);
+      if (!cout_) die("cannot create " + a.coverage, 1);
+      std::string buf;
+      for (size_t s = 0; s < sequences.size(); ++s) {
+        const size_t len = sequences[s].seq.size();
+        const uint32_t* al = cv.aligned.data() + cv.offsets[s];
+        const uint32_t* ma = cv.matched.data() + cv.offsets[s];
+        for (size_t beg = 0, p = 1; p <= len; ++p) {
+          if (p < len && al[p] == al[beg] && ma[p] == ma[beg]) continue;
+          buf += sequences[s].id + '\t' + std::to_string(beg) + '\t' + std::to_string(p) + '\t' + std::to_string(al[beg]) + '\t' + std::to_string(ma[beg]) + '\n';
+          beg = p;
+        }
+        if (buf.size() >= (1u << 20) || s + 1 == sequences.size()) {
+          cout_.write(buf.data(), (std::streamsize)buf.size());
+          buf.clear();
+        }
+      }
+      cout_.close();
+      if (cout_.fail()) die("write error on the coverage output", 1);
+    }
     const BoundStats bs = it.last_bound_stats();
     const size_t above = (size_t)(bs.above_penalty + bs.above_divergence);  // (pairs above a bound get no line)
     const ClipStats cs = it.last_clip_stats();
@@ -578,6 +630,11 @@ int main(int argc, char** argv) {
         const awv_cs_stats xs = it.last_cs_stats();
         w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", cs %llu pairs, %llu failed, %llu text bytes, %.2f ms", (unsigned long long)xs.pairs,
                       (unsigned long long)xs.failed, (unsigned long long)xs.text_bytes, xs.kernel_ms);
+      }
+      if (a.have_coverage && w > 0 && (size_t)w < sizeof(buf)) {
+        const awv_cov_stats vs = it.last_report().coverage_stats;
+        w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", coverage %llu items, %llu boundaries, %.2f ms", (unsigned long long)vs.items,
+                      (unsigned long long)vs.boundaries, vs.kernel_ms);
       }
       if (a.verify && w > 0 && (size_t)w < sizeof(buf)) {
         const awv_verify_stats vs = it.last_verify_stats();

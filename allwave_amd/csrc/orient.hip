@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "coverage_device.hpp"   // (awv_internal_coverage_paused)
 #include "normalize_device.hpp"  // (awv_internal_normalize_mode)
 #include "planner_device.hpp"  // (EngineView, awv_internal_view, awv_internal_fail)
 
@@ -368,7 +369,11 @@ int orient_core(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, 
     int32_t& norm_mode = awv_internal_normalize_mode(e);  // orientation ignores the engine's normalize mode: edit counts do not move
     const int32_t saved_mode = norm_mode;
     norm_mode = AWV_NORM_OFF;
+    bool& cov_paused = awv_internal_coverage_paused(e);  // nor do these strand alignments count towards the depth: only final ones do
+    const bool saved_paused = cov_paused;
+    cov_paused = true;
     const int arc = awv_align_pairs(e, pen, op.data(), 2 * m, orr.data(), nullptr, nullptr);
+    cov_paused = saved_paused;
     norm_mode = saved_mode;
     if (arc) return arc;
     awv_stats st{};

@@ -75,6 +75,14 @@ AWV_CST_OK = 0
 AWV_CST_SKIPPED = 1
 AWV_CST_BAD_OP = 2
 AWV_CST_LENGTHS = 3
+#: per-base depth: the roles whose tracks a column is added to, and awv_cov_item.code
+AWV_COV_TARGET = 1
+AWV_COV_QUERY = 2
+AWV_COV_BOTH = 3
+AWV_CV_OK = 0
+AWV_CV_SKIPPED = 1
+AWV_CV_BAD_OP = 2
+AWV_CV_LENGTHS = 3
 #: sketch kinds of device pair planning (awv_sketch)
 AWV_SK_CANONICAL = 0
 AWV_SK_FORWARD = 1
@@ -95,7 +103,9 @@ EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine
            "awv_normalize_one_host", "awv_normalize_cigars", "awv_normalize_ranges", "awv_engine_set_normalize",
            "awv_engine_normalize_stats",
            "awv_encode_one_host", "awv_encode_cigars", "awv_align_pairs_encoded", "awv_align_ranges_encoded", "awv_engine_encode_stats",
-           "awv_cs_one_host", "awv_cs_cigars", "awv_cs_ranges", "awv_align_pairs_cs", "awv_align_ranges_cs", "awv_engine_cs_stats")
+           "awv_cs_one_host", "awv_cs_cigars", "awv_cs_ranges", "awv_align_pairs_cs", "awv_align_ranges_cs", "awv_engine_cs_stats",
+           "awv_coverage_one_host", "awv_engine_coverage_begin", "awv_engine_coverage_read", "awv_coverage_cigars", "awv_coverage_ranges",
+           "awv_engine_coverage_stats")
 
 
 class EngineConfig(C.Structure):
@@ -157,6 +167,11 @@ class CsStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("pairs", C.c_uint64), ("failed", C.c_uint64), ("text_bytes", C.c_uint64), ("columns", C.c_uint64)]
 
 
+class CovStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("items", C.c_uint64), ("failed", C.c_uint64), ("columns", C.c_uint64), ("boundaries", C.c_uint64),
+                ("reads", C.c_uint64)]
+
+
 PAIR_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4")])
 #: awv_range_pair: the query interval on the query's forward strand (PAF convention), also with q_revcomp
 RANGE_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4"), ("q_beg", "<i4"), ("q_end", "<i4"),
@@ -180,6 +195,8 @@ CIGAR_TEXT_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("runs", "<u4")])
 CS_TEXT_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("code", "<i4")])
 #: awv_cs_slice: columns [col_beg, col_end) of an op string, and the bases consumed before col_beg (the fields of a clip)
 CS_SLICE_DTYPE = np.dtype([("col_beg", "<u4"), ("col_end", "<u4"), ("q_skip", "<i4"), ("t_skip", "<i4")])
+#: awv_cov_item: what one item added to the depth tracks
+COV_ITEM_DTYPE = np.dtype([("code", "<i4"), ("aligned_cols", "<u4"), ("matched_cols", "<u4"), ("boundaries", "<u4")])
 #: awv_score_result
 SCORE_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4")])
 
@@ -275,8 +292,24 @@ def load():
                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, CS_SINK_FN, C.c_void_p]
         L.awv_align_ranges_cs.argtypes = L.awv_align_pairs_cs.argtypes
         L.awv_engine_cs_stats.argtypes = [C.c_void_p, C.POINTER(CsStats)]
+        L.awv_coverage_one_host.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.awv_engine_coverage_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int64]
+        L.awv_engine_coverage_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.awv_coverage_cigars.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.awv_coverage_ranges.argtypes = L.awv_coverage_cigars.argtypes
+        L.awv_engine_coverage_stats.argtypes = [C.c_void_p, C.POINTER(CovStats)]
         _LIB = L
     return _LIB
+
+
+def coverage_roles(coverage):
+    """None / "target" / "query" / "both" (or an AWV_COV_* value) -> 0 (off) / AWV_COV_*."""
+    roles = {None: 0, "target": AWV_COV_TARGET, "query": AWV_COV_QUERY, "both": AWV_COV_BOTH,
+             AWV_COV_TARGET: AWV_COV_TARGET, AWV_COV_QUERY: AWV_COV_QUERY, AWV_COV_BOTH: AWV_COV_BOTH}
+    if isinstance(coverage, bool) or coverage not in roles:
+        raise ValueError("coverage: None, 'target', 'query' or 'both', not %r" % (coverage,))
+    return roles[coverage]
 
 
 def cs_mode(cs):
@@ -339,6 +372,7 @@ class Engine:
         if rc != AWV_OK:
             raise EngineError(rc, "awv_engine_set_sequences")
         self.nseq = n
+        self._seq_offsets = offs.astype(np.int64)
 
     @staticmethod
     def _pair_array(pairs):
@@ -679,25 +713,81 @@ class Engine:
         """cs_cigars on interval pairs (awv_cs_ranges)."""
         return self._cs("awv_cs_ranges", cs, self._range_array(ranges), results, arena, slices, want_text, text_cap)
 
+    @staticmethod
+    def _slice_array(slices, n):
+        """None, a CS_SLICE_DTYPE array or [n, 4] integers (col_beg, col_end, q_skip, t_skip) -> None or a contiguous CS_SLICE_DTYPE array."""
+        if slices is None:
+            return None
+        if isinstance(slices, np.ndarray) and slices.dtype == CS_SLICE_DTYPE:
+            sl = np.ascontiguousarray(slices)
+        else:
+            raw = np.asarray(slices, dtype=np.int64).reshape(-1, 4)
+            sl = np.zeros(len(raw), dtype=CS_SLICE_DTYPE)
+            for k, name in enumerate(("col_beg", "col_end", "q_skip", "t_skip")):
+                sl[name] = raw[:, k]
+        if sl.shape != (n,):
+            raise ValueError("slices: need one slice per record")
+        return sl if len(sl) else np.zeros(1, dtype=CS_SLICE_DTYPE)
+
     def _cs(self, fn, cs, pairs, results, arena, slices, want_text, text_cap):
         mode = cs if isinstance(cs, int) and not isinstance(cs, bool) else cs_mode(cs)  # (an integer goes through as it is: the library refuses a bad one)
         results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
         if results.shape != (len(pairs),):
             raise ValueError("results: need one record per pair")
-        sl = None
-        if slices is not None:
-            if isinstance(slices, np.ndarray) and slices.dtype == CS_SLICE_DTYPE:
-                sl = np.ascontiguousarray(slices)
-            else:
-                raw = np.asarray(slices, dtype=np.int64).reshape(-1, 4)
-                sl = np.zeros(len(raw), dtype=CS_SLICE_DTYPE)
-                for k, name in enumerate(("col_beg", "col_end", "q_skip", "t_skip")):
-                    sl[name] = raw[:, k]
-            if sl.shape != (len(results),):
-                raise ValueError("slices: need one slice per record")
-            sl = sl if len(sl) else np.zeros(1, dtype=CS_SLICE_DTYPE)
+        sl = self._slice_array(slices, len(results))
         csout = np.zeros(max(len(results), 1), dtype=CS_TEXT_DTYPE)[:len(results)]
         return self._text_call(fn, (mode, pairs.ctypes.data, len(pairs), results.ctypes.data), arena, sl, csout, want_text, text_cap)
+
+    def coverage_begin(self, roles="both", clip_min_score=0):
+        """awv_engine_coverage_begin: from now on every aligning call of this engine adds its contributing alignments to two
+        per-base depth tracks on the device.  roles: "target", "query", "both" (or an AWV_COV_* mask); None or 0 ends coverage
+        and frees the accumulators, as set_sequences does.  clip_min_score: the least score of a clip that contributes."""
+        r = roles if isinstance(roles, int) and not isinstance(roles, bool) else coverage_roles(roles)  # (an integer goes through as it is)
+        rc = load().awv_engine_coverage_begin(self._h, r, int(clip_min_score))
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_engine_coverage_begin")
+
+    def coverage_read(self):
+        """awv_engine_coverage_read: the depth so far, as (offsets, aligned, matched) -- sequence s owns entries
+        [offsets[s], offsets[s + 1]) of the two uint32 arrays, one per forward-strand base.  Accumulation goes on afterwards."""
+        offs = getattr(self, "_seq_offsets", np.zeros(1, dtype=np.int64))
+        total = int(offs[-1])
+        aligned = np.zeros(max(total, 1), dtype=np.uint32)
+        matched = np.zeros(max(total, 1), dtype=np.uint32)
+        rc = load().awv_engine_coverage_read(self._h, aligned.ctypes.data, matched.ctypes.data, total)
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_engine_coverage_read")
+        return offs.copy(), aligned[:total], matched[:total]
+
+    def coverage_cigars(self, pairs, results, arena, slices=None):
+        """awv_coverage_cigars: adds caller-supplied records (a RESULT_DTYPE array whose cigar_off / cigar_len point into
+        `arena`, bytes or a uint8 array) to the engine's depth tracks, on the device.  slices: as for cs_cigars.  Returns a
+        COV_ITEM_DTYPE array."""
+        return self._coverage("awv_coverage_cigars", self._pair_array(pairs), results, arena, slices)
+
+    def coverage_ranges(self, ranges, results, arena, slices=None):
+        """coverage_cigars on interval pairs (awv_coverage_ranges)."""
+        return self._coverage("awv_coverage_ranges", self._range_array(ranges), results, arena, slices)
+
+    def _coverage(self, fn, pairs, results, arena, slices):
+        results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+        if results.shape != (len(pairs),):
+            raise ValueError("results: need one record per pair")
+        sl = self._slice_array(slices, len(results))
+        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
+        nbytes = int(arena.size)
+        if nbytes == 0:
+            arena = np.zeros(1, dtype=np.uint8)
+        items = np.zeros(max(len(results), 1), dtype=COV_ITEM_DTYPE)[:len(results)]
+        rc = getattr(load(), fn)(self._h, pairs.ctypes.data, len(pairs), results.ctypes.data, arena.ctypes.data, nbytes,
+                                 None if sl is None else sl.ctypes.data, items.ctypes.data)
+        if rc != AWV_OK:
+            raise EngineError(rc, fn)
+        return items
+
+    def coverage_stats(self):
+        """awv_engine_coverage_stats: kernel_ms, items, failed, columns, boundaries, reads since coverage_begin."""
+        return self._stats("awv_engine_coverage_stats", CovStats)
 
     def _stats(self, fn_name, cls):
         """One of the awv_engine_*_stats getters: the engine's `cls` record."""
@@ -905,6 +995,37 @@ def cs_one_host(cs, pattern, text, cigar, slice=None, cap=None):
         raise EngineError(rc, "awv_cs_one_host")
     n = int(out[0]["len"])
     return (buf.raw[:n] if n <= size else b""), out[0]
+
+
+def coverage_one_host(roles, q_revcomp, qlen, tlen, cigar, span=None, slice=None, q_tracks=None, t_tracks=None):
+    """awv_coverage_one_host: adds one item to per-base depth tracks on the host (needs no device; the yardstick the kernel is
+    tested against).  roles: "target" / "query" / "both" (or an AWV_COV_* mask); span: None (the whole of both sequences) or
+    (pb, pe, tb, te) in pattern / text coordinates; slice: None, or (col_beg, col_end, q_skip, t_skip).  q_tracks / t_tracks:
+    (aligned, matched) pairs of contiguous uint32 arrays with qlen / tlen entries, added to in place (None: new zeroed ones;
+    the same pair may be passed for both, for a sequence aligned with itself).  Returns (one COV_ITEM_DTYPE record, q_tracks,
+    t_tracks)."""
+    cigar = bytes(cigar)
+    r = roles if isinstance(roles, int) and not isinstance(roles, bool) else coverage_roles(roles)
+    pb, pe, tb, te = (0, qlen, 0, tlen) if span is None else (int(v) for v in span)
+    if q_tracks is None:
+        q_tracks = (np.zeros(qlen, dtype=np.uint32), np.zeros(qlen, dtype=np.uint32))
+    if t_tracks is None:
+        t_tracks = (np.zeros(tlen, dtype=np.uint32), np.zeros(tlen, dtype=np.uint32))
+    for tr, ln in ((q_tracks, qlen), (t_tracks, tlen)):
+        for a in tr:
+            if not (isinstance(a, np.ndarray) and a.dtype == np.uint32 and a.flags["C_CONTIGUOUS"] and a.shape == (ln,)):
+                raise ValueError("tracks: contiguous uint32 arrays with one entry per base")
+    sl = None
+    if slice is not None:
+        sl = np.zeros(1, dtype=CS_SLICE_DTYPE)
+        sl[0] = tuple(int(v) for v in slice)
+    out = np.zeros(1, dtype=COV_ITEM_DTYPE)
+    rc = load().awv_coverage_one_host(r, int(bool(q_revcomp)), qlen, tlen, pb, pe, tb, te, cigar, len(cigar), None if sl is None else sl.ctypes.data,
+                                      q_tracks[0].ctypes.data, q_tracks[1].ctypes.data, t_tracks[0].ctypes.data, t_tracks[1].ctypes.data,
+                                      out.ctypes.data)
+    if rc != AWV_OK:
+        raise EngineError(rc, "awv_coverage_one_host")
+    return out[0], q_tracks, t_tracks
 
 
 def clip_one_host(scores, match_bonus, cigar):

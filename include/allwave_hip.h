@@ -79,7 +79,7 @@ typedef struct {
   int32_t device;          /* HIP device ordinal */
   int32_t workgroups;      /* persistent workgroups = pairs in flight (0 = engine default: 16 per CU); the align kernels open
                               workgroups / (waves per workgroup) slots, at least one, and the record kernels (verify, clip,
-                              split, normalize, encode, cs) launch min(records, workgroups) one-wave workgroups -- 0: min(records, 16 per CU) */
+                              split, normalize, encode, cs, coverage) launch min(records, workgroups) one-wave workgroups -- 0: min(records, 16 per CU) */
   int64_t max_batch_pairs; /* pairs per launch (0 = default) */
   int64_t max_arena_bytes; /* CIGAR arena budget per launch (0 = default 8 GiB) */
   int32_t flags;           /* AWV_F_* */
@@ -734,6 +734,76 @@ int awv_align_ranges_cs(awv_engine* e, const awv_penalties* pen, const awv_range
                         void* user);
 /* The last cs call (awv_align_*_cs / awv_cs_cigars / awv_cs_ranges) of this engine. */
 int awv_engine_cs_stats(const awv_engine* e, awv_cs_stats* out);
+
+/* ---- per-base alignment depth accumulated on the device (csrc/coverage.hip, csrc/coverage_device.hpp) ---------------------------
+ * For every base of every resident sequence: in how many alignments is it aligned, and in how many does it match?  Two tracks of
+ * uint32 per forward-strand position: aligned[s][p] counts the contributing columns that are 'M' or 'X' and consume base p of
+ * sequence s, matched[s][p] the 'M' columns among them.  A pure function of the items, exact and independent of their order.
+ * An item is an op string c[0..n) over M X I D with its rectangle (pattern [pb, pe) against text [tb, te), the pattern's
+ * coordinates those of the reverse-complement copy for a q_revcomp pair) and the skips q_skip, t_skip of a slice: exactly what
+ * the cs text is made from.  Column k sits at pattern position x = pb + q_skip + #(ops other than 'I' before k) and at text
+ * position y = tb + t_skip + #(ops other than 'D' before k).  The target's base is y; the query's forward-strand base is x for
+ * a forward pair and len[q] - 1 - x for a q_revcomp pair.  roles says whose tracks a column is added to.
+ * What contributes in an aligning call: without clip or split a record with status AWV_ST_COMPLETED, whole; in a clipping call
+ * the clip's slice when its code is AWV_CL_OK and its score >= clip_min_score; in a splitting call every segment; nothing else
+ * (failed records, records above the bound, empty clips, score-only and orientation calls).  The walk comes after normalization.
+ * An item is all or nothing: one whose code is not AWV_CV_OK adds to no counter anywhere, and nothing is ever stored outside a
+ * sequence's own slots, whatever the bytes say.  A string or slice holds at most 2^30 columns; an engine accumulates at most
+ * 2^31 - 1 items between awv_engine_coverage_begin calls, so no depth can wrap (AWV_ERR_ARG beyond, before anything is launched). */
+#define AWV_COV_TARGET 1
+#define AWV_COV_QUERY 2
+#define AWV_COV_BOTH 3
+#define AWV_CV_OK 0       /* the item was added */
+#define AWV_CV_SKIPPED 1  /* status is not AWV_ST_COMPLETED */
+#define AWV_CV_BAD_OP 2   /* a byte outside MXID */
+#define AWV_CV_LENGTHS 3  /* q_skip + the pattern bases the string consumes > the pattern interval, or the same for the text */
+typedef struct {
+  int32_t code;           /* AWV_CV_* */
+  uint32_t aligned_cols;  /* 'M' and 'X' columns; the three counts are 0 for every code but AWV_CV_OK */
+  uint32_t matched_cols;  /* 'M' columns */
+  uint32_t boundaries;    /* 2 x (maximal runs of aligned columns + maximal runs of 'M'): the adds one role costs */
+} awv_cov_item; /* 16 bytes */
+
+typedef struct {
+  double kernel_ms;     /* HIP-event time of the coverage launches (the read-out scans included) since awv_engine_coverage_begin */
+  uint64_t items;       /* items handed to the pass since then (skipped ones included) */
+  uint64_t failed;      /* of them: code other than AWV_CV_OK / AWV_CV_SKIPPED */
+  uint64_t columns;     /* op bytes of the strings and slices walked */
+  uint64_t boundaries;  /* adds made: the items' boundaries, once per role */
+  uint64_t reads;       /* awv_engine_coverage_read calls */
+} awv_cov_stats; /* 48 bytes */
+
+/* The contract alone, on the host (needs no device): a per-column walk, the yardstick the kernel is tested against, not a
+ * fallback -- no product path calls it.  qlen / tlen: the two sequences' lengths; the rectangle in pattern / text coordinates;
+ * slice (nullable): the whole string, no skips.  q_aligned / q_matched: the query's tracks, qlen entries; t_aligned / t_matched:
+ * the target's, tlen entries (for a self pair the same arrays may be passed twice); a null track is not kept.  Adds 1 per
+ * contributing column, and nothing unless out->code is AWV_CV_OK. */
+int awv_coverage_one_host(int32_t roles, int32_t q_revcomp, int32_t qlen, int32_t tlen, int32_t pb, int32_t pe, int32_t tb,
+                          int32_t te, const uint8_t* cigar, int64_t n, const awv_cs_slice* slice /* nullable */,
+                          uint32_t* q_aligned, uint32_t* q_matched, uint32_t* t_aligned, uint32_t* t_matched,
+                          awv_cov_item* out /* required */);
+/* Begins accumulation over the resident sequence set (AWV_ERR_STATE without one): allocates and zeroes the accumulators, two
+ * difference tracks of len[s] + 1 slots per sequence.  From then on every aligning call of the engine -- awv_align_pairs and
+ * awv_align_ranges in all their forms -- adds each batch's contributing items on the device, on the engine's stream, after the
+ * clip / split step; records, op bytes, texts and stats of those calls are unchanged.  roles: AWV_COV_* (1..3); roles == 0 ends
+ * coverage and frees the memory, and so does awv_engine_set_sequences.  clip_min_score: the threshold of clipping calls. */
+int awv_engine_coverage_begin(awv_engine* e, int32_t roles, int64_t clip_min_score);
+/* The depth so far: a segmented scan of the difference slots into separate buffers, copied back; the sequences concatenated in
+ * set order.  The accumulators stay as they are: accumulation goes on after a read.  n_bases must be the sum of the lengths
+ * (AWV_ERR_ARG); either pointer may be null.  AWV_ERR_STATE before begin.  A sequence whose scan does not end on 0 is a bug,
+ * never an input error: AWV_ERR_HIP. */
+int awv_engine_coverage_read(awv_engine* e, uint32_t* aligned, uint32_t* matched, uint64_t n_bases);
+/* Accumulates records and op bytes the caller supplies into the engine's accumulators: results[i] claims that
+ * cigar_arena[results[i].cigar_off, + cigar_len) aligns pairs[i] (ranges[i]).  Staged and pieced as awv_cs_cigars does; slices
+ * (nullable): n entries; items[0..n) is filled.  AWV_ERR_STATE before begin; AWV_ERR_ARG, before anything is launched, for what
+ * awv_cs_cigars refuses. */
+int awv_coverage_cigars(awv_engine* e, const awv_pair* pairs, int64_t n, const awv_result* results, const uint8_t* cigar_arena,
+                        uint64_t arena_bytes, const awv_cs_slice* slices /* nullable */, awv_cov_item* items /* required */);
+int awv_coverage_ranges(awv_engine* e, const awv_range_pair* ranges, int64_t n, const awv_result* results,
+                        const uint8_t* cigar_arena, uint64_t arena_bytes, const awv_cs_slice* slices /* nullable */,
+                        awv_cov_item* items /* required */);
+/* Since the last awv_engine_coverage_begin of this engine (all zero before one). */
+int awv_engine_coverage_stats(const awv_engine* e, awv_cov_stats* out);
 
 /* ---- device pair planning (csrc/planner.hip) -------------------------------------------------------------------------
  * Integer work over the engine's resident sequence set, on its device and stream; results equal the host planner's
