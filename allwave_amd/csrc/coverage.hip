@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "batch_items.hpp"  // contributing_items, whole_span
 #include "record_pass.hpp"  // RecordPass, open_pass, Buf, pack_piece, AWV_TRY
 
 namespace awvcov {
@@ -252,9 +253,7 @@ struct State : awvw::RecordPass {
   Buf<uint64_t> d_cov_off;
   Buf<uint32_t> d_acc_a, d_acc_m;      // the difference tracks: n_bases + nseq slots each
   Buf<uint32_t> d_depth_a, d_depth_m;  // a read's depths: n_bases each
-  std::vector<awv_pair> h_pairs;       // a batch's items
-  std::vector<awv_result> h_recs;      // their records with the slices applied
-  std::vector<Span> h_spans;           // and their rectangles
+  awvw::BatchItems items;              // a batch's items (batch_items.hpp)
   std::vector<awv_cov_item> h_items;
   int32_t roles = 0;  // 0: no coverage
   int64_t clip_min_score = 0;
@@ -355,8 +354,7 @@ int launch(const awp::EngineView& v, State* st, const awv_pair* pairs, const Spa
   return AWV_OK;
 }
 
-// the whole of both sequences: the rectangle of a pair call's record
-Span whole_span(const awp::EngineView& v, const awv_pair& p) { return Span{0, v.len_host[p.q_idx], 0, v.len_host[p.t_idx]}; }
+using awvw::whole_span;
 
 // ranges (nullable; awv_coverage_ranges): the call is on ranges[0..n_all) -- `pairs` is not read
 int coverage_cigars_core(awv_engine* e, const awv_pair* pairs, const awv_range_pair* ranges, int64_t n_all, const awv_result* results,
@@ -476,33 +474,8 @@ int coverage_batch(awv_engine* e, const awv_pair* pairs, int64_t n, const awv_re
   awp::EngineView v;
   State* st = nullptr;
   if (int rc = open_active(e, "coverage_batch", v, st)) return rc;
-  const auto span_of = [&](int64_t i) { return spans ? spans[i] : whole_span(v, pairs[i]); };  // (the indices: checked by the aligning call)
-  const auto slice_of = [](const awv_clip_result& c) { return awv_cs_slice{c.col_beg, c.col_end, c.q_skip, c.t_skip}; };
-  st->h_pairs.clear();
-  st->h_recs.clear();
-  st->h_spans.clear();
-  const auto push = [&](int64_t i, const awv_cs_slice* sl) {
-    st->h_pairs.push_back(pairs[i]);
-    st->h_recs.push_back(results[i]);
-    st->h_spans.push_back(span_of(i));
-    if (sl) awvcs::apply_slice(st->h_recs.back(), st->h_spans.back(), *sl);
-  };
-  for (int64_t i = 0; i < n; ++i) {
-    if (results[i].status != AWV_ST_COMPLETED) continue;  // failed, above the bound: nothing
-    if (iout) {  // every segment of the split is an item
-      if (iout[i].code != AWV_CL_OK) continue;
-      for (int32_t k = 0; k < iout[i].count; ++k) {
-        const awv_cs_slice sl = slice_of(sout[seg_first[i] + (uint64_t)k]);
-        if (awvcs::slice_ok(results[i], sl)) push(i, &sl);
-      }
-    } else if (clips) {  // the clip's segment, when it scores enough
-      const awv_cs_slice sl = slice_of(clips[i]);
-      if (clips[i].code == AWV_CL_OK && clips[i].score >= st->clip_min_score && awvcs::slice_ok(results[i], sl)) push(i, &sl);
-    } else {
-      push(i, nullptr);
-    }
-  }
-  return launch(v, st, st->h_pairs.data(), st->h_spans.data(), (int64_t)st->h_pairs.size(), st->h_recs.data(), d_arena, arena_bytes, nullptr);
+  awvw::contributing_items(v, pairs, n, results, clips, st->clip_min_score, seg_first, iout, sout, spans, st->items);
+  return launch(v, st, st->items.pairs.data(), st->items.spans.data(), (int64_t)st->items.pairs.size(), st->items.recs.data(), d_arena, arena_bytes, nullptr);
 }
 
 }  // namespace awvcov

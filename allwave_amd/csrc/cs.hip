@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "seq_load.hpp"   // load16
 #include "text_pass.hpp"  // the host skeleton and the device walk of a text pass: TextPass, lane_runs, text_dest, AWV_TRY
 
 namespace awvcs {
@@ -46,25 +47,9 @@ struct KParams {
 using awvw::byte_at;
 using awvw::CHUNK;
 using awvw::LANE_BYTES;
+using awvw::load16;
 using awvw::u32x4;
 using awvw::wave_scan_add;
-
-// 16 bytes of a sequence of `len` bytes from position `pos` on: five aligned dwords, shifted into place.  Dwords that start at or
-// behind the sequence's end are not read (their bytes are 0); a dword that starts inside it ends at most 3 bytes behind it, inside
-// the engine's padding.
-static_assert(awp::SEQ_PAD_BYTES >= 3, "load16 reads whole dwords that start inside a sequence: the layout must pad every sequence by 3 bytes or more");
-__device__ __forceinline__ u32x4 load16(const uint8_t* seq, int len, int pos) {
-  const uintptr_t addr = (uintptr_t)seq + (uintptr_t)pos, end = (uintptr_t)seq + (uintptr_t)max(len, 0);
-  const unsigned* a = (const unsigned*)(addr & ~(uintptr_t)3);
-  const unsigned s = (unsigned)(addr & 3);
-  unsigned d[5];
-#pragma unroll
-  for (int k = 0; k < 5; ++k) d[k] = (uintptr_t)(a + k) < end ? a[k] : 0u;
-  u32x4 x;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) x[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], s);
-  return x;
-}
 
 __device__ __forceinline__ void put(uint8_t* dst, unsigned room, unsigned& at, unsigned ch) {  // never outside the record's own characters
   if (at < room) dst[at] = (uint8_t)ch;

@@ -83,6 +83,16 @@ AWV_CV_OK = 0
 AWV_CV_SKIPPED = 1
 AWV_CV_BAD_OP = 2
 AWV_CV_LENGTHS = 3
+#: the allele table: awv_variant.type, awv_var_item.code and the hash (base and modulus are part of the contract)
+AWV_VAR_SNV = 0
+AWV_VAR_DEL = 1
+AWV_VAR_INS = 2
+AWV_VAR_HASH_BASE = 0x1b873593a5c1f2e7
+AWV_VAR_HASH_MOD = (1 << 61) - 1
+AWV_VR_OK = 0
+AWV_VR_SKIPPED = 1
+AWV_VR_BAD_OP = 2
+AWV_VR_LENGTHS = 3
 #: sketch kinds of device pair planning (awv_sketch)
 AWV_SK_CANONICAL = 0
 AWV_SK_FORWARD = 1
@@ -105,7 +115,8 @@ EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine
            "awv_encode_one_host", "awv_encode_cigars", "awv_align_pairs_encoded", "awv_align_ranges_encoded", "awv_engine_encode_stats",
            "awv_cs_one_host", "awv_cs_cigars", "awv_cs_ranges", "awv_align_pairs_cs", "awv_align_ranges_cs", "awv_engine_cs_stats",
            "awv_coverage_one_host", "awv_engine_coverage_begin", "awv_engine_coverage_read", "awv_coverage_cigars", "awv_coverage_ranges",
-           "awv_engine_coverage_stats")
+           "awv_engine_coverage_stats",
+           "awv_variants_one_host", "awv_variants_fold_host")
 
 
 class EngineConfig(C.Structure):
@@ -197,6 +208,11 @@ CS_TEXT_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("code", "<i4")])
 CS_SLICE_DTYPE = np.dtype([("col_beg", "<u4"), ("col_end", "<u4"), ("q_skip", "<i4"), ("t_skip", "<i4")])
 #: awv_cov_item: what one item added to the depth tracks
 COV_ITEM_DTYPE = np.dtype([("code", "<i4"), ("aligned_cols", "<u4"), ("matched_cols", "<u4"), ("boundaries", "<u4")])
+#: awv_variant: one row of the allele table (or one event: count 1), 40 bytes
+VARIANT_DTYPE = np.dtype([("t_idx", "<i4"), ("pos", "<i4"), ("type", "<i4"), ("len", "<i4"), ("hash", "<u8"), ("rep", "<u8"), ("count", "<u4"),
+                          ("reserved", "<u4")])
+#: awv_var_item: the code and the events of one item
+VAR_ITEM_DTYPE = np.dtype([("code", "<i4"), ("snv", "<u4"), ("ins", "<u4"), ("del", "<u4")])
 #: awv_score_result
 SCORE_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4")])
 
@@ -299,6 +315,9 @@ def load():
         L.awv_coverage_cigars.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.awv_coverage_ranges.argtypes = L.awv_coverage_cigars.argtypes
         L.awv_engine_coverage_stats.argtypes = [C.c_void_p, C.POINTER(CovStats)]
+        L.awv_variants_one_host.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
+        L.awv_variants_fold_host.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         _LIB = L
     return _LIB
 
@@ -1026,6 +1045,40 @@ def coverage_one_host(roles, q_revcomp, qlen, tlen, cigar, span=None, slice=None
     if rc != AWV_OK:
         raise EngineError(rc, "awv_coverage_one_host")
     return out[0], q_tracks, t_tracks
+
+
+def variants_one_host(q_idx, t_idx, q_revcomp, pattern, tlen, cigar, span=None, slice=None):
+    """awv_variants_one_host: the events of one item, in column order, on the host (needs no device; the yardstick the kernel is
+    tested against).  pattern: the aligned copy of the query (its reverse complement for a q_revcomp pair); span: None (the
+    whole of both sequences) or (pb, pe, tb, te); slice: None, or (col_beg, col_end, q_skip, t_skip).  Returns (one
+    VAR_ITEM_DTYPE record, a VARIANT_DTYPE array of count-1 events)."""
+    cigar, pattern = bytes(cigar), bytes(pattern)
+    qlen = len(pattern)
+    pb, pe, tb, te = (0, qlen, 0, tlen) if span is None else (int(v) for v in span)
+    sl = None
+    if slice is not None:
+        sl = np.zeros(1, dtype=CS_SLICE_DTYPE)
+        sl[0] = tuple(int(v) for v in slice)
+    out = np.zeros(1, dtype=VAR_ITEM_DTYPE)
+    cap = len(cigar) + 1
+    events = np.zeros(cap, dtype=VARIANT_DTYPE)
+    n = C.c_uint64(0)
+    rc = load().awv_variants_one_host(int(q_idx), int(t_idx), int(bool(q_revcomp)), pattern, qlen, int(tlen), pb, pe, tb, te, cigar, len(cigar),
+                                      None if sl is None else sl.ctypes.data, events.ctypes.data, cap, C.byref(n), out.ctypes.data)
+    if rc != AWV_OK:
+        raise EngineError(rc, "awv_variants_one_host")
+    return out[0], events[:int(n.value)]
+
+
+def variants_fold_host(rows):
+    """awv_variants_fold_host: events or rows (VARIANT_DTYPE) sorted by key and reduced (sum of count, min of rep); a new array."""
+    rows = np.array(rows, dtype=VARIANT_DTYPE, copy=True).reshape(-1)
+    buf = rows if len(rows) else np.zeros(1, dtype=VARIANT_DTYPE)
+    n = C.c_uint64(0)
+    rc = load().awv_variants_fold_host(buf.ctypes.data, len(rows), C.byref(n))
+    if rc != AWV_OK:
+        raise EngineError(rc, "awv_variants_fold_host")
+    return rows[:int(n.value)].copy()
 
 
 def clip_one_host(scores, match_bonus, cigar):

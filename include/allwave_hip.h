@@ -805,6 +805,60 @@ int awv_coverage_ranges(awv_engine* e, const awv_range_pair* ranges, int64_t n, 
 /* Since the last awv_engine_coverage_begin of this engine (all zero before one). */
 int awv_engine_coverage_stats(const awv_engine* e, awv_cov_stats* out);
 
+/* ---- the alleles of all alignments per target site (csrc/variants.hip, csrc/variants_device.hpp) --------------------------------
+ * At this site of this sequence, which alleles do the other sequences carry, and how many carry each?  A keyed table: distinct
+ * (site, allele) rows with a support count, deduplicated across records, batches and calls.  This section is the contract and
+ * its host yardsticks; the hash, its combine and the key order are __host__ __device__ in variants_device.hpp.
+ * A pure function of the contributing items, exact and independent of their order.
+ * An item is exactly the coverage pass's item: an op string c[0..n) over M X I D with its rectangle (pattern [pb, pe) against
+ * text [tb, te)), the skips of a slice, and the pair's q_idx, t_idx and q_revcomp; the pattern is the reverse-complement copy for
+ * a q_revcomp pair, so allele bases are in target orientation.  Column k sits at pattern position x and text position y as above.
+ * What contributes of an aligning call is the coverage rule, word for word (whole completed records, a clip's slice that reaches
+ * clip_min_score, every split segment, after normalization); a slice that cuts a run cuts the event, as in cs.
+ * The events of an item, left to right:
+ *   each 'X' column               AWV_VAR_SNV  pos = y                        len 1  allele: the pattern base
+ *   each maximal 'I' run of L     AWV_VAR_DEL  pos = y of its first column    len L  no allele ('I' consumes the text, cs's '-')
+ *   each maximal 'D' run of L     AWV_VAR_INS  pos = y, the target base the   len L  allele: pattern[p, p + L)
+ *                                              insertion precedes (tlen is allowed)  ('D' consumes the pattern, cs's '+')
+ * An 'I' run directly followed by a 'D' run is two events.  Whether an 'X' column's bases really differ is not judged, as in cs.
+ * Allele identity is (len, hash): hash runs over the upper-cased allele bytes modulo 2^61 - 1 with the base AWV_VAR_HASH_BASE:
+ * h(empty) = 0, h(s.c) = (h(s) * B + upper(c)) mod (2^61 - 1), hence h(a.b) = (h(a) * B^|b| + h(b)) mod (2^61 - 1); a deletion has
+ * hash 0.  The constant is part of the contract: tables of several devices are merged by key.  Two different insertions of equal
+ * length at one site are told apart by this hash and nothing else.
+ * Row key: (t_idx, pos, type, len, hash); the table is sorted ascending by it.  Row value: count, the number of contributing items
+ * that carry the event, and rep, the smallest (uint64)q_idx << 32 | q_revcomp << 31 | p_beg over those items, p_beg the event's
+ * first pattern position in the aligned copy's coordinates: the allele's bytes can be read from rep.  Sum and min: the table does
+ * not depend on the order of items, batches, engines or devices.
+ * An item is all or nothing: one whose code is not AWV_VR_OK adds no event.  A string or slice holds at most 2^30 columns, and
+ * a table takes at most 2^31 - 1 items, so no count can wrap. */
+#define AWV_VAR_SNV 0
+#define AWV_VAR_DEL 1
+#define AWV_VAR_INS 2
+#define AWV_VAR_HASH_BASE 1983613069137408743ull /* B = 0x1b873593a5c1f2e7, below 2^61 - 1 */
+#define AWV_VR_OK 0       /* the item's events were appended */
+#define AWV_VR_SKIPPED 1  /* status is not AWV_ST_COMPLETED */
+#define AWV_VR_BAD_OP 2   /* a byte outside MXID */
+#define AWV_VR_LENGTHS 3  /* q_skip + the pattern bases the string consumes > the pattern interval, or the same for the text */
+typedef struct {
+  int32_t t_idx, pos, type, len; /* type: AWV_VAR_* */
+  uint64_t hash, rep;
+  uint32_t count, reserved;      /* reserved: 0 */
+} awv_variant; /* 40 bytes */
+typedef struct {
+  int32_t code;           /* AWV_VR_* */
+  uint32_t snv, ins, del; /* events of each type; 0 for every code but AWV_VR_OK */
+} awv_var_item; /* 16 bytes */
+/* The contract alone, on the host (needs no device): yardsticks for kernels to be tested against, not fallbacks -- no product
+ * path of the engine calls them.  awv_variants_one_host is the serial per-column walk of one item into events with count 1, in column
+ * order: pattern is the aligned copy of the query (qlen bytes), the rectangle and the slice as in awv_coverage_one_host; at most
+ * cap events are written to `events` (nullable with cap 0), *n_events is their number whatever cap is, and nothing is written
+ * unless out->code is AWV_VR_OK.  awv_variants_fold_host sorts rows[0..n) -- events or rows -- by key and reduces equal keys
+ * (sum of count, min of rep) in place; *n_rows is the number of distinct rows left at the front. */
+int awv_variants_one_host(int32_t q_idx, int32_t t_idx, int32_t q_revcomp, const uint8_t* pattern, int32_t qlen, int32_t tlen,
+                          int32_t pb, int32_t pe, int32_t tb, int32_t te, const uint8_t* cigar, int64_t n,
+                          const awv_cs_slice* slice /* nullable */, awv_variant* events, uint64_t cap, uint64_t* n_events,
+                          awv_var_item* out /* required */);
+int awv_variants_fold_host(awv_variant* rows, uint64_t n, uint64_t* n_rows);
 /* ---- device pair planning (csrc/planner.hip) -------------------------------------------------------------------------
  * Integer work over the engine's resident sequence set, on its device and stream; results equal the host planner's
  * (csrc/host/planner.cpp) bit for bit.  Every call but awv_keep_pairs needs a sequence set (else AWV_ERR_STATE); a new set
