@@ -992,8 +992,7 @@ void publish_stats(AlignCall& c) {
 }
 
 int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const AlignRequest& rq) {
-  // ---- validate; the penalty plan
-  if (rq.npairs < 0 || (rq.npairs > 0 && !rq.pairs)) return fail(AWV_ERR_ARG, "align_pairs: null pairs");
+  // ---- the penalty plan (the list, the pair indices and the slot rule are checked, and the steps' counters reset, by align_call)
   AlignCall c{e, s, pen, rq};
   c.pp = awvb::plan_penalties(LIMITS, pen, e->cfg.flags);
   if (c.pp.code != AWV_OK && !c.pp.late) return fail(c.pp.code, c.pp.message);
@@ -1001,12 +1000,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const AlignRe
   e->stats = awv_stats{};
   for (uint64_t& v : e->twin_stats) v = 0;
   c.norm = rq.score_only ? AWV_NORM_OFF : e->norm_mode;  // (off: no launch, no allocation, nothing below changes)
-  if (c.norm != AWV_NORM_OFF) awvn::stats_reset(e->normalize);
   if (rq.npairs == 0) return AWV_OK;
-  for (int64_t i = 0; i < rq.npairs; ++i) {
-    if (rq.pairs[i].q_idx < 0 || rq.pairs[i].q_idx >= s.n || rq.pairs[i].t_idx < 0 || rq.pairs[i].t_idx >= s.n)
-      return fail(AWV_ERR_ARG, "align_pairs: sequence index out of range");
-  }
   if (c.pp.code != AWV_OK) return fail(c.pp.code, c.pp.message);
   c.cfg = awvb::Config{e->cfg.flags, e->num_cus, e->cfg.workgroups, (int64_t)e->cfg.max_scratch_bytes, e->cfg.first_row_cols};
   c.max_batch = e->cfg.max_batch_pairs > 0 ? e->cfg.max_batch_pairs : (int64_t)1 << 20;
@@ -1028,7 +1022,7 @@ int align_core(awv_engine* e, SeqSet& s, const awv_penalties* pen, const AlignRe
   return AWV_OK;
 }
 
-// ---- what the entry points share ----
+// ---- what the entry points share (the table of forms and the order of the checks) ----
 int require_sequences(const awv_engine* e, int64_t n, const char* who) {
   if (e->seqs.n == 0 && n > 0) return fail(AWV_ERR_STATE, std::string(who) + " before set_sequences");
   return AWV_OK;
@@ -1042,15 +1036,169 @@ const int32_t* normalized_bounds(const int32_t* bounds, int64_t n, std::vector<i
   for (int64_t i = 0; i < n; ++i) store[(size_t)i] = norm_bound(bounds[i]);
   return store.data();
 }
-// the request of a plain full alignment; the other entry points set what they add
-AlignRequest full_request(const awv_pair* pairs, int64_t npairs, awv_result* out, awv_sink sink, void* user) {
+// Each range becomes the pair and the rectangle (pattern / text coordinates) align_core works on
+int split_ranges(const SeqSet& s, const awv_range_pair* ranges, int64_t n, std::vector<awv_pair>& pairs, std::vector<awvr::Span>& spans,
+                 const char* who) {
+  pairs.resize((size_t)n);
+  spans.resize((size_t)n);
+  for (int64_t i = 0; i < n; ++i)
+    if (!awvr::split_range(s.len.data(), s.n, ranges[i], pairs[(size_t)i], spans[(size_t)i]))
+      return fail(AWV_ERR_ARG, std::string(who) + ": range " + std::to_string(i) + " names a sequence index or an interval out of range");
+  return AWV_OK;
+}
+// what every clipping call refuses before anything is launched
+int check_clip_args(const awv_clip_result* cout, int32_t match_bonus) {
+  if (!cout) return fail(AWV_ERR_ARG, "align_clipped: null cout");
+  if (match_bonus < 1 || match_bonus > AWV_CLIP_MAX_BONUS) return fail(AWV_ERR_ARG, "align_clipped: match_bonus must be in [1, 32767]");
+  return AWV_OK;
+}
+// what every encoding call refuses; match_bonus == 0: no clip, cout is not read
+int check_encode_args(const awv_cigar_text* tout, awv_clip_result*& cout, int32_t match_bonus) {
+  if (!tout) return fail(AWV_ERR_ARG, "align_encoded: null tout");
+  if (match_bonus == 0) {
+    cout = nullptr;
+    return AWV_OK;
+  }
+  return check_clip_args(cout, match_bonus);
+}
+// what every cs call refuses; match_bonus == 0: no clip, cout is not read
+int check_cs_args(int32_t cs_mode, const awv_cs_text* csout, awv_clip_result*& cout, int32_t match_bonus) {
+  if (!awvcs::mode_ok(cs_mode)) return fail(AWV_ERR_ARG, "align_cs: cs_mode must be AWV_CS_SHORT or AWV_CS_LONG");
+  if (!csout) return fail(AWV_ERR_ARG, "align_cs: null csout");
+  if (match_bonus == 0) {
+    cout = nullptr;
+    return AWV_OK;
+  }
+  return check_clip_args(cout, match_bonus);
+}
+// what every splitting call refuses, and the slot rule for one entry
+int check_split_args(int32_t match_bonus, const SplitOut& sp, int64_t n) {
+  if (match_bonus < 1 || match_bonus > AWV_CLIP_MAX_BONUS) return fail(AWV_ERR_ARG, "align_split: match_bonus must be in [1, 32767]");
+  if (sp.min_score < 1) return fail(AWV_ERR_ARG, "align_split: min_score must be >= 1");
+  if (!sp.seg_first || (n > 0 && !sp.iout)) return fail(AWV_ERR_ARG, "align_split: null seg_first or iout");
+  for (int64_t i = 0; i < n; ++i)
+    if (sp.seg_first[i + 1] < sp.seg_first[i]) return fail(AWV_ERR_ARG, "align_split: seg_first must ascend");
+  if (n > 0 && sp.seg_first[n] > sp.seg_first[0] && !sp.sout) return fail(AWV_ERR_ARG, "align_split: null sout");
+  return AWV_OK;
+}
+int check_split_slots(const SplitOut& sp, int64_t i, int32_t match_bonus, int64_t shorter) {
+  if (sp.seg_first[i + 1] - sp.seg_first[i] < (uint64_t)awvs::slots(match_bonus, sp.min_score, shorter))
+    return fail(AWV_ERR_ARG, "align_split: entry " + std::to_string(i) + " owns fewer slots than awv_split_slots(a, min_score, min(plen, tlen))");
+  return AWV_OK;
+}
+
+// The request's outputs exactly as the caller gave them; the pairs and rectangles are align_call's to set
+AlignRequest request(awv_result* out, awv_sink sink, void* user, const int32_t* bounds = nullptr, awv_verify_result* vout = nullptr,
+                     int32_t match_bonus = 0, awv_clip_result* cout = nullptr, awv_cigar_text* tout = nullptr) {
   AlignRequest rq;
-  rq.pairs = pairs;
-  rq.npairs = npairs;
   rq.out = out;
   rq.sink = sink;
   rq.user = user;
+  rq.pair_bound = bounds;
+  rq.vout = vout;
+  rq.match_bonus = match_bonus;
+  rq.cout = cout;
+  rq.tout = tout;
   return rq;
+}
+// the encoded call's request plus the cs step; the sink that takes both arenas stands in the plain sink's place
+AlignRequest cs_request(AlignRequest rq, int32_t cs_mode, awv_cs_text* csout, awv_cs_sink sink) {
+  rq.cs_mode = cs_mode;
+  rq.csout = csout;
+  rq.cs_sink = sink;
+  return rq;
+}
+// the bounded call's request plus the split step; sp outlives the call
+AlignRequest split_request(AlignRequest rq, const SplitOut& sp) {
+  rq.split = &sp;
+  return rq;
+}
+// The list a call works on -- pairs, or ranges -- and the name its messages carry
+struct Subject {
+  const awv_pair* pairs;
+  const awv_range_pair* ranges;
+  bool by_range;
+  int64_t n;
+  const char* who;
+};
+Subject over_pairs(const awv_pair* pairs, int64_t n, const char* who = "align_pairs") { return {pairs, nullptr, false, n, who}; }
+Subject over_ranges(const awv_range_pair* ranges, int64_t n, const char* who = "align_ranges") { return {nullptr, ranges, true, n, who}; }
+// What a form requires of its arguments beyond the list, and the name its own messages carry
+enum : unsigned { NEED_VOUT = 1, NEED_BOUNDS = 2, NEED_CLIP = 4, NEED_SPLIT = 8, NEED_TEXT = 16, NEED_CS = 32 };
+struct Form {
+  const char* name;
+  unsigned needs;
+};
+
+// The one path from an entry point to align_core.  Every check comes before anything is launched or reset, in this order: the
+// engine, the form's own arguments, the list, the sequence set, the ranges, the pair indices, the slot rule.  An accepted call
+// resets the counters of the steps it asks for and of no other.
+int align_call(awv_engine* e, const awv_penalties* pen, const Subject& sub, AlignRequest rq, const Form& form) {
+  if (!e) return fail(AWV_ERR_ARG, "null engine");
+  const int64_t n = sub.n;
+  if ((form.needs & NEED_VOUT) && !rq.vout) return fail(AWV_ERR_ARG, std::string(form.name) + ": null vout");
+  if ((form.needs & NEED_BOUNDS) && n > 0 && !rq.pair_bound) return fail(AWV_ERR_ARG, std::string(form.name) + ": null max_penalty");
+  if (form.needs & NEED_CLIP)
+    if (int rc = check_clip_args(rq.cout, rq.match_bonus)) return rc;
+  if (form.needs & NEED_TEXT)
+    if (int rc = check_encode_args(rq.tout, rq.cout, rq.match_bonus)) return rc;
+  if (form.needs & NEED_CS)
+    if (int rc = check_cs_args(rq.cs_mode, rq.csout, rq.cout, rq.match_bonus)) return rc;
+  if (form.needs & NEED_SPLIT)
+    if (int rc = check_split_args(rq.match_bonus, *rq.split, n)) return rc;
+  if (n < 0 || (n > 0 && !(sub.by_range ? (const void*)sub.ranges : (const void*)sub.pairs)))
+    return fail(AWV_ERR_ARG, sub.by_range ? std::string(sub.who) + ": null ranges" : std::string("align_pairs: null pairs"));
+  if (int rc = require_sequences(e, n, sub.who)) return rc;
+  AWV_GUARDED(
+    const SeqSet& s = e->seqs;
+    std::vector<awv_pair> pairs;
+    std::vector<awvr::Span> spans;
+    std::vector<int32_t> pb;
+    rq.pairs = sub.pairs;
+    rq.npairs = n;
+    if (sub.by_range) {
+      if (int rc = split_ranges(s, sub.ranges, n, pairs, spans, sub.who)) return rc;
+      rq.pairs = pairs.data();
+      rq.spans = n > 0 ? spans.data() : nullptr;
+    }
+    for (int64_t i = 0; i < n; ++i) {
+      const awv_pair& p = rq.pairs[i];
+      if (p.q_idx < 0 || p.q_idx >= s.n || p.t_idx < 0 || p.t_idx >= s.n) return fail(AWV_ERR_ARG, "align_pairs: sequence index out of range");
+      if (!rq.split) continue;  // the slot rule over the two lengths the pair aligns: the intervals', or the sequences'
+      const int64_t shorter = rq.spans ? std::min(rq.spans[i].pe - rq.spans[i].pb, rq.spans[i].te - rq.spans[i].tb)
+                                       : std::min(s.len[p.q_idx], s.len[p.t_idx]);
+      if (int rc = check_split_slots(*rq.split, i, rq.match_bonus, shorter)) return rc;
+    }
+    // the call's batches add to them (a call without pairs launches nothing: its stats are empty)
+    if (rq.vout) awvf::stats_reset(e->verify);
+    if (rq.cout) awvc::stats_reset(e->clip);
+    if (rq.split) awvs::stats_reset(e->split);
+    if (rq.tout) awve::stats_reset(e->encode);
+    if (rq.csout) awvcs::stats_reset(e->cs);
+    if (!rq.score_only && e->norm_mode != AWV_NORM_OFF) awvn::stats_reset(e->normalize);
+    rq.max_penalty = norm_bound(rq.max_penalty);
+    rq.pair_bound = normalized_bounds(rq.pair_bound, n, pb);
+    return align_core(e, e->seqs, pen, rq);
+  )
+}
+// awv_score_pairs / awv_score_pairs_bounded / awv_score_ranges.  rq: the bounds as the caller gave them -- one for the call
+// (max_penalty), or one per pair (pair_bound).
+int score_core(awv_engine* e, const awv_penalties* pen, const Subject& sub, AlignRequest rq, awv_score_result* out, const Form& form) {
+  if (!e) return awv_internal_null_engine();  // (without a GPU there is no engine to pass: say so, as awv_engine_create does)
+  if (!out) return fail(AWV_ERR_ARG, std::string(sub.who) + ": null out");
+  if (sub.n < 0) return fail(AWV_ERR_ARG, sub.by_range ? "score_ranges: null ranges" : "score_pairs: npairs < 0");
+  AWV_GUARDED(
+    std::vector<awv_result> res((size_t)sub.n);
+    rq.out = res.data();
+    rq.score_only = true;
+    const int rc = align_call(e, pen, sub, rq, form);
+    if (rc != AWV_OK) return rc;
+    for (int64_t i = 0; i < sub.n; ++i) {
+      out[i].status = res[(size_t)i].status;
+      out[i].penalty = res[(size_t)i].penalty;
+    }
+    return AWV_OK;
+  )
 }
 
 }  // namespace
@@ -1147,322 +1295,86 @@ int awv_engine_set_sequences(awv_engine* e, int32_t n, const uint8_t* concat_byt
   AWV_GUARDED(return upload_seqset(e, e->seqs, n, concat_bytes, offsets);)
 }
 
+// ---- the aligning calls: each fills the request from its arguments, names what its form requires, and takes the one path.
+// The _ranges forms are the same calls over sub-intervals of the resident sequences.
 int awv_align_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, awv_result* out,
                     awv_sink sink, void* user) {
-  if (!e) return fail(AWV_ERR_ARG, "null engine");
-  if (int rc = require_sequences(e, npairs, "align_pairs")) return rc;
-  AWV_GUARDED(return align_core(e, e->seqs, pen, full_request(pairs, npairs, out, sink, user));)
+  return align_call(e, pen, over_pairs(pairs, npairs), request(out, sink, user), {"align_pairs", 0});
+}
+
+int awv_align_ranges(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, awv_result* out,
+                     awv_sink sink, void* user) {
+  return align_call(e, pen, over_ranges(ranges, n), request(out, sink, user), {"align_ranges", 0});
 }
 
 int awv_align_pairs_verified(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, awv_result* out,
                              awv_verify_result* vout, awv_sink sink, void* user) {
-  if (!e) return fail(AWV_ERR_ARG, "null engine");
-  if (!vout) return fail(AWV_ERR_ARG, "align_pairs_verified: null vout");
-  if (int rc = require_sequences(e, npairs, "align_pairs")) return rc;
-  awvf::stats_reset(e->verify);  // the call's batches add to them (a call without pairs launches nothing: its stats are empty)
-  AlignRequest rq = full_request(pairs, npairs, out, sink, user);
-  rq.vout = vout;
-  AWV_GUARDED(return align_core(e, e->seqs, pen, rq);)
+  return align_call(e, pen, over_pairs(pairs, npairs), request(out, sink, user, nullptr, vout), {"align_pairs_verified", NEED_VOUT});
 }
 
-namespace {
-// awv_score_pairs / awv_score_pairs_bounded / awv_score_ranges.  rq: the pairs (and rectangles) and the bounds as the caller
-// gave them -- one for the call (max_penalty), or one per pair (pair_bound).
-int score_core(awv_engine* e, const awv_penalties* pen, AlignRequest rq, awv_score_result* out) {
-  if (!e) return awv_internal_null_engine();  // (without a GPU there is no engine to pass: say so, as awv_engine_create does)
-  if (!out) return fail(AWV_ERR_ARG, "score_pairs: null out");
-  if (rq.npairs < 0) return fail(AWV_ERR_ARG, "score_pairs: npairs < 0");
-  if (int rc = require_sequences(e, rq.npairs, "score_pairs")) return rc;
-  AWV_GUARDED(
-    std::vector<awv_result> res((size_t)rq.npairs);
-    std::vector<int32_t> pb;
-    rq.out = res.data();
-    rq.score_only = true;
-    rq.max_penalty = norm_bound(rq.max_penalty);
-    rq.pair_bound = normalized_bounds(rq.pair_bound, rq.npairs, pb);
-    const int rc = align_core(e, e->seqs, pen, rq);
-    if (rc != AWV_OK) return rc;
-    for (int64_t i = 0; i < rq.npairs; ++i) {
-      out[i].status = res[(size_t)i].status;
-      out[i].penalty = res[(size_t)i].penalty;
-    }
-    return AWV_OK;
-  )
-}
-}  // namespace
-
-int awv_score_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, int32_t max_penalty,
-                    awv_score_result* out) {
-  AlignRequest rq = full_request(pairs, npairs, nullptr, nullptr, nullptr);
-  rq.max_penalty = max_penalty;
-  return score_core(e, pen, rq, out);
+int awv_align_ranges_verified(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, awv_result* out,
+                              awv_verify_result* vout, awv_sink sink, void* user) {
+  return align_call(e, pen, over_ranges(ranges, n), request(out, sink, user, nullptr, vout), {"align_ranges_verified", NEED_VOUT});
 }
 
-int awv_score_pairs_bounded(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
-                            const int32_t* max_penalty, awv_score_result* out) {
-  if (e && npairs > 0 && !max_penalty) return fail(AWV_ERR_ARG, "score_pairs_bounded: null max_penalty");
-  AlignRequest rq = full_request(pairs, npairs, nullptr, nullptr, nullptr);
-  rq.max_penalty = -1;
-  rq.pair_bound = max_penalty;
-  return score_core(e, pen, rq, out);
+int awv_align_pairs_bounded(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const int32_t* max_penalty,
+                            awv_result* out, awv_verify_result* vout, awv_sink sink, void* user) {
+  return align_call(e, pen, over_pairs(pairs, npairs), request(out, sink, user, max_penalty, vout), {"align_pairs_bounded", NEED_BOUNDS});
 }
 
-// ---- ranges: the same calls over sub-intervals of the resident sequences.  Each range becomes the pair and the rectangle
-// (pattern / text coordinates) align_core works on; nothing is launched when one of them is invalid.
-namespace {
-int split_ranges(const SeqSet& s, const awv_range_pair* ranges, int64_t n, std::vector<awv_pair>& pairs, std::vector<awvr::Span>& spans,
-                 const char* who) {
-  pairs.resize((size_t)n);
-  spans.resize((size_t)n);
-  for (int64_t i = 0; i < n; ++i)
-    if (!awvr::split_range(s.len.data(), s.n, ranges[i], pairs[(size_t)i], spans[(size_t)i]))
-      return fail(AWV_ERR_ARG, std::string(who) + ": range " + std::to_string(i) + " names a sequence index or an interval out of range");
-  return AWV_OK;
+int awv_align_ranges_bounded(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const int32_t* max_penalty,
+                             awv_result* out, awv_verify_result* vout, awv_sink sink, void* user) {
+  return align_call(e, pen, over_ranges(ranges, n), request(out, sink, user, max_penalty, vout), {"align_ranges_bounded", 0});
 }
-// what every splitting call refuses before anything is launched, and the slot rule for one entry
-int check_split_args(int32_t match_bonus, const SplitOut& sp, int64_t n) {
-  if (match_bonus < 1 || match_bonus > AWV_CLIP_MAX_BONUS) return fail(AWV_ERR_ARG, "align_split: match_bonus must be in [1, 32767]");
-  if (sp.min_score < 1) return fail(AWV_ERR_ARG, "align_split: min_score must be >= 1");
-  if (!sp.seg_first || (n > 0 && !sp.iout)) return fail(AWV_ERR_ARG, "align_split: null seg_first or iout");
-  for (int64_t i = 0; i < n; ++i)
-    if (sp.seg_first[i + 1] < sp.seg_first[i]) return fail(AWV_ERR_ARG, "align_split: seg_first must ascend");
-  if (n > 0 && sp.seg_first[n] > sp.seg_first[0] && !sp.sout) return fail(AWV_ERR_ARG, "align_split: null sout");
-  return AWV_OK;
-}
-int check_split_slots(const SplitOut& sp, int64_t i, int32_t match_bonus, int64_t shorter) {
-  if (sp.seg_first[i + 1] - sp.seg_first[i] < (uint64_t)awvs::slots(match_bonus, sp.min_score, shorter))
-    return fail(AWV_ERR_ARG, "align_split: entry " + std::to_string(i) + " owns fewer slots than awv_split_slots(a, min_score, min(plen, tlen))");
-  return AWV_OK;
-}
-// rq: everything but the pairs and rectangles, which the ranges become; rq.pair_bound as the caller gave it (nullable)
-int align_ranges_core(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, AlignRequest rq) {
-  if (n < 0 || (n > 0 && !ranges)) return fail(AWV_ERR_ARG, "align_ranges: null ranges");
-  if (int rc = require_sequences(e, n, "align_ranges")) return rc;
-  std::vector<awv_pair> pairs;
-  std::vector<awvr::Span> spans;
-  if (int rc = split_ranges(e->seqs, ranges, n, pairs, spans, "align_ranges")) return rc;
-  if (rq.vout) awvf::stats_reset(e->verify);
-  if (n == 0) return align_core(e, e->seqs, pen, full_request(nullptr, 0, rq.out, rq.sink, rq.user));
-  if (rq.split)  // the slot rule over the two interval lengths, before anything is launched
-    for (int64_t i = 0; i < n; ++i) {
-      const awvr::Span& sp = spans[(size_t)i];
-      if (int rc = check_split_slots(*rq.split, i, rq.match_bonus, std::min(sp.pe - sp.pb, sp.te - sp.tb))) return rc;
-    }
-  std::vector<int32_t> pb;
-  rq.pairs = pairs.data();
-  rq.npairs = n;
-  rq.spans = spans.data();
-  rq.pair_bound = normalized_bounds(rq.pair_bound, n, pb);
-  return align_core(e, e->seqs, pen, rq);
-}
-// what every clipping call refuses before anything is launched
-int check_clip_args(const awv_clip_result* cout, int32_t match_bonus) {
-  if (!cout) return fail(AWV_ERR_ARG, "align_clipped: null cout");
-  if (match_bonus < 1 || match_bonus > AWV_CLIP_MAX_BONUS) return fail(AWV_ERR_ARG, "align_clipped: match_bonus must be in [1, 32767]");
-  return AWV_OK;
-}
-}  // namespace
 
 int awv_align_pairs_clipped(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const int32_t* max_penalty,
                             int32_t match_bonus, awv_result* out, awv_verify_result* vout, awv_clip_result* cout, awv_sink sink, void* user) {
-  if (!e) return fail(AWV_ERR_ARG, "null engine");
-  if (int rc = check_clip_args(cout, match_bonus)) return rc;
-  if (int rc = require_sequences(e, npairs, "align_pairs")) return rc;
-  if (vout) awvf::stats_reset(e->verify);
-  awvc::stats_reset(e->clip);
-  AWV_GUARDED(
-    std::vector<int32_t> pb;
-    AlignRequest rq = full_request(pairs, npairs, out, sink, user);
-    rq.pair_bound = normalized_bounds(max_penalty, npairs, pb);
-    rq.vout = vout;
-    rq.cout = cout;
-    rq.match_bonus = match_bonus;
-    return align_core(e, e->seqs, pen, rq);
-  )
+  return align_call(e, pen, over_pairs(pairs, npairs), request(out, sink, user, max_penalty, vout, match_bonus, cout), {"align_pairs_clipped", NEED_CLIP});
 }
 
 int awv_align_ranges_clipped(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const int32_t* max_penalty,
                              int32_t match_bonus, awv_result* out, awv_verify_result* vout, awv_clip_result* cout, awv_sink sink, void* user) {
-  if (!e) return fail(AWV_ERR_ARG, "null engine");
-  if (int rc = check_clip_args(cout, match_bonus)) return rc;
-  awvc::stats_reset(e->clip);
-  AlignRequest rq = full_request(nullptr, 0, out, sink, user);
-  rq.pair_bound = max_penalty;
-  rq.vout = vout;
-  rq.cout = cout;
-  rq.match_bonus = match_bonus;
-  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, rq);)
+  return align_call(e, pen, over_ranges(ranges, n), request(out, sink, user, max_penalty, vout, match_bonus, cout), {"align_ranges_clipped", NEED_CLIP});
 }
-
-namespace {
-// what every encoding call refuses before anything is launched; match_bonus == 0: no clip, cout is not read
-int check_encode_args(const awv_cigar_text* tout, awv_clip_result*& cout, int32_t match_bonus) {
-  if (!tout) return fail(AWV_ERR_ARG, "align_encoded: null tout");
-  if (match_bonus == 0) {
-    cout = nullptr;
-    return AWV_OK;
-  }
-  return check_clip_args(cout, match_bonus);
-}
-}  // namespace
 
 int awv_align_pairs_encoded(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const int32_t* max_penalty,
                             int32_t match_bonus, awv_result* out, awv_verify_result* vout, awv_clip_result* cout, awv_cigar_text* tout,
                             awv_sink sink, void* user) {
-  if (!e) return fail(AWV_ERR_ARG, "null engine");
-  if (int rc = check_encode_args(tout, cout, match_bonus)) return rc;
-  if (int rc = require_sequences(e, npairs, "align_pairs")) return rc;
-  if (vout) awvf::stats_reset(e->verify);
-  if (cout) awvc::stats_reset(e->clip);
-  awve::stats_reset(e->encode);
-  AWV_GUARDED(
-    std::vector<int32_t> pb;
-    AlignRequest rq = full_request(pairs, npairs, out, sink, user);
-    rq.pair_bound = normalized_bounds(max_penalty, npairs, pb);
-    rq.vout = vout;
-    rq.cout = cout;
-    rq.match_bonus = match_bonus;
-    rq.tout = tout;
-    return align_core(e, e->seqs, pen, rq);
-  )
+  return align_call(e, pen, over_pairs(pairs, npairs), request(out, sink, user, max_penalty, vout, match_bonus, cout, tout), {"align_pairs_encoded", NEED_TEXT});
 }
 
 int awv_align_ranges_encoded(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const int32_t* max_penalty,
                              int32_t match_bonus, awv_result* out, awv_verify_result* vout, awv_clip_result* cout, awv_cigar_text* tout,
                              awv_sink sink, void* user) {
-  if (!e) return fail(AWV_ERR_ARG, "null engine");
-  if (int rc = check_encode_args(tout, cout, match_bonus)) return rc;
-  if (cout) awvc::stats_reset(e->clip);
-  awve::stats_reset(e->encode);
-  AlignRequest rq = full_request(nullptr, 0, out, sink, user);
-  rq.pair_bound = max_penalty;
-  rq.vout = vout;
-  rq.cout = cout;
-  rq.match_bonus = match_bonus;
-  rq.tout = tout;
-  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, rq);)
+  return align_call(e, pen, over_ranges(ranges, n), request(out, sink, user, max_penalty, vout, match_bonus, cout, tout), {"align_ranges_encoded", NEED_TEXT});
 }
-
-namespace {
-// what every cs call refuses before anything is launched; match_bonus == 0: no clip, cout is not read
-int check_cs_args(int32_t cs_mode, const awv_cs_text* csout, awv_clip_result*& cout, int32_t match_bonus) {
-  if (!awvcs::mode_ok(cs_mode)) return fail(AWV_ERR_ARG, "align_cs: cs_mode must be AWV_CS_SHORT or AWV_CS_LONG");
-  if (!csout) return fail(AWV_ERR_ARG, "align_cs: null csout");
-  if (match_bonus == 0) {
-    cout = nullptr;
-    return AWV_OK;
-  }
-  return check_clip_args(cout, match_bonus);
-}
-// the encoded call's request plus the cs step; the sink that takes both arenas stands in the plain sink's place
-void cs_request(AlignRequest& rq, const int32_t* bounds, int32_t match_bonus, awv_verify_result* vout, awv_clip_result* cout, awv_cigar_text* tout,
-                int32_t cs_mode, awv_cs_text* csout, awv_cs_sink sink) {
-  rq.pair_bound = bounds;
-  rq.vout = vout;
-  rq.cout = cout;
-  rq.match_bonus = match_bonus;
-  rq.tout = tout;
-  rq.cs_mode = cs_mode;
-  rq.csout = csout;
-  rq.cs_sink = sink;
-}
-}  // namespace
 
 int awv_align_pairs_cs(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const int32_t* max_penalty, int32_t match_bonus,
                        awv_result* out, awv_verify_result* vout, awv_clip_result* cout, awv_cigar_text* tout, int32_t cs_mode, awv_cs_text* csout,
                        awv_cs_sink sink, void* user) {
-  if (!e) return fail(AWV_ERR_ARG, "null engine");
-  if (int rc = check_cs_args(cs_mode, csout, cout, match_bonus)) return rc;
-  if (int rc = require_sequences(e, npairs, "align_pairs")) return rc;
-  if (vout) awvf::stats_reset(e->verify);
-  if (cout) awvc::stats_reset(e->clip);
-  if (tout) awve::stats_reset(e->encode);
-  awvcs::stats_reset(e->cs);
-  AWV_GUARDED(
-    std::vector<int32_t> pb;
-    AlignRequest rq = full_request(pairs, npairs, out, nullptr, user);
-    cs_request(rq, normalized_bounds(max_penalty, npairs, pb), match_bonus, vout, cout, tout, cs_mode, csout, sink);
-    return align_core(e, e->seqs, pen, rq);
-  )
+  return align_call(e, pen, over_pairs(pairs, npairs), cs_request(request(out, nullptr, user, max_penalty, vout, match_bonus, cout, tout), cs_mode, csout, sink),
+                    {"align_pairs_cs", NEED_CS});
 }
 
 int awv_align_ranges_cs(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const int32_t* max_penalty, int32_t match_bonus,
                         awv_result* out, awv_verify_result* vout, awv_clip_result* cout, awv_cigar_text* tout, int32_t cs_mode, awv_cs_text* csout,
                         awv_cs_sink sink, void* user) {
-  if (!e) return fail(AWV_ERR_ARG, "null engine");
-  if (int rc = check_cs_args(cs_mode, csout, cout, match_bonus)) return rc;
-  if (cout) awvc::stats_reset(e->clip);
-  if (tout) awve::stats_reset(e->encode);
-  awvcs::stats_reset(e->cs);
-  AlignRequest rq = full_request(nullptr, 0, out, nullptr, user);
-  cs_request(rq, max_penalty, match_bonus, vout, cout, tout, cs_mode, csout, sink);
-  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, rq);)
+  return align_call(e, pen, over_ranges(ranges, n), cs_request(request(out, nullptr, user, max_penalty, vout, match_bonus, cout, tout), cs_mode, csout, sink),
+                    {"align_ranges_cs", NEED_CS});
 }
 
 int awv_align_pairs_split(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const int32_t* max_penalty,
                           int32_t match_bonus, int64_t min_score, awv_result* out, awv_verify_result* vout, const uint64_t* seg_first,
                           awv_split_index* iout, awv_clip_result* sout, awv_sink sink, void* user) {
-  if (!e) return fail(AWV_ERR_ARG, "null engine");
-  if (npairs < 0 || (npairs > 0 && !pairs)) return fail(AWV_ERR_ARG, "align_pairs: null pairs");
   const SplitOut sp{min_score, seg_first, iout, sout};
-  if (int rc = check_split_args(match_bonus, sp, npairs)) return rc;
-  if (int rc = require_sequences(e, npairs, "align_pairs")) return rc;
-  for (int64_t i = 0; i < npairs; ++i) {
-    if (pairs[i].q_idx < 0 || pairs[i].q_idx >= e->seqs.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= e->seqs.n)
-      return fail(AWV_ERR_ARG, "align_pairs: sequence index out of range");
-    if (int rc = check_split_slots(sp, i, match_bonus, std::min(e->seqs.len[pairs[i].q_idx], e->seqs.len[pairs[i].t_idx]))) return rc;
-  }
-  if (vout) awvf::stats_reset(e->verify);
-  awvs::stats_reset(e->split);
-  AWV_GUARDED(
-    std::vector<int32_t> pb;
-    AlignRequest rq = full_request(pairs, npairs, out, sink, user);
-    rq.pair_bound = normalized_bounds(max_penalty, npairs, pb);
-    rq.vout = vout;
-    rq.match_bonus = match_bonus;
-    rq.split = &sp;
-    return align_core(e, e->seqs, pen, rq);
-  )
+  return align_call(e, pen, over_pairs(pairs, npairs), split_request(request(out, sink, user, max_penalty, vout, match_bonus), sp), {"align_pairs_split", NEED_SPLIT});
 }
 
 int awv_align_ranges_split(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const int32_t* max_penalty,
                            int32_t match_bonus, int64_t min_score, awv_result* out, awv_verify_result* vout, const uint64_t* seg_first,
                            awv_split_index* iout, awv_clip_result* sout, awv_sink sink, void* user) {
-  if (!e) return fail(AWV_ERR_ARG, "null engine");
-  if (n < 0) return fail(AWV_ERR_ARG, "align_ranges: null ranges");
   const SplitOut sp{min_score, seg_first, iout, sout};
-  if (int rc = check_split_args(match_bonus, sp, n)) return rc;
-  awvs::stats_reset(e->split);
-  AlignRequest rq = full_request(nullptr, 0, out, sink, user);
-  rq.pair_bound = max_penalty;
-  rq.vout = vout;
-  rq.match_bonus = match_bonus;
-  rq.split = &sp;
-  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, rq);)
-}
-
-int awv_align_pairs_bounded(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, const int32_t* max_penalty,
-                            awv_result* out, awv_verify_result* vout, awv_sink sink, void* user) {
-  if (!e) return fail(AWV_ERR_ARG, "null engine");
-  if (npairs > 0 && !max_penalty) return fail(AWV_ERR_ARG, "align_pairs_bounded: null max_penalty");
-  if (int rc = require_sequences(e, npairs, "align_pairs")) return rc;
-  if (vout) awvf::stats_reset(e->verify);
-  AWV_GUARDED(
-    std::vector<int32_t> pb;
-    AlignRequest rq = full_request(pairs, npairs, out, sink, user);
-    rq.pair_bound = normalized_bounds(max_penalty, npairs, pb);
-    rq.vout = vout;
-    return align_core(e, e->seqs, pen, rq);
-  )
-}
-
-int awv_align_ranges_bounded(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const int32_t* max_penalty,
-                             awv_result* out, awv_verify_result* vout, awv_sink sink, void* user) {
-  if (!e) return fail(AWV_ERR_ARG, "null engine");
-  AlignRequest rq = full_request(nullptr, 0, out, sink, user);
-  rq.pair_bound = max_penalty;
-  rq.vout = vout;
-  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, rq);)
+  return align_call(e, pen, over_ranges(ranges, n), split_request(request(out, sink, user, max_penalty, vout, match_bonus), sp), {"align_ranges_split", NEED_SPLIT});
 }
 
 int32_t awv_divergence_bound(const awv_penalties* pen, int32_t plen, int32_t tlen, double d) {
@@ -1482,37 +1394,22 @@ int32_t awv_divergence_bound(const awv_penalties* pen, int32_t plen, int32_t tle
   return B > (double)INT32_MAX ? -1 : (int32_t)B;
 }
 
-int awv_align_ranges(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, awv_result* out,
-                     awv_sink sink, void* user) {
-  if (!e) return fail(AWV_ERR_ARG, "null engine");
-  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, full_request(nullptr, 0, out, sink, user));)
+// ---- the score calls: score_core converts the results and takes the same path
+int awv_score_pairs(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs, int32_t max_penalty,
+                    awv_score_result* out) {
+  AlignRequest rq;
+  rq.max_penalty = max_penalty;
+  return score_core(e, pen, over_pairs(pairs, npairs, "score_pairs"), rq, out, {"score_pairs", 0});
 }
 
-int awv_align_ranges_verified(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, awv_result* out,
-                              awv_verify_result* vout, awv_sink sink, void* user) {
-  if (!e) return fail(AWV_ERR_ARG, "null engine");
-  if (!vout) return fail(AWV_ERR_ARG, "align_ranges_verified: null vout");
-  AlignRequest rq = full_request(nullptr, 0, out, sink, user);
-  rq.vout = vout;
-  AWV_GUARDED(return align_ranges_core(e, pen, ranges, n, rq);)
+int awv_score_pairs_bounded(awv_engine* e, const awv_penalties* pen, const awv_pair* pairs, int64_t npairs,
+                            const int32_t* max_penalty, awv_score_result* out) {
+  return score_core(e, pen, over_pairs(pairs, npairs, "score_pairs"), request(nullptr, nullptr, nullptr, max_penalty), out, {"score_pairs_bounded", NEED_BOUNDS});
 }
 
 int awv_score_ranges(awv_engine* e, const awv_penalties* pen, const awv_range_pair* ranges, int64_t n, const int32_t* max_penalty,
                      awv_score_result* out) {
-  if (!e) return awv_internal_null_engine();  // (says which: no device, or a null engine)
-  if (!out) return fail(AWV_ERR_ARG, "score_ranges: null out");
-  if (n < 0 || (n > 0 && !ranges)) return fail(AWV_ERR_ARG, "score_ranges: null ranges");
-  if (int rc = require_sequences(e, n, "score_ranges")) return rc;
-  AWV_GUARDED(
-    std::vector<awv_pair> pairs;
-    std::vector<awvr::Span> spans;
-    if (int rc = split_ranges(e->seqs, ranges, n, pairs, spans, "score_ranges")) return rc;
-    AlignRequest rq = full_request(pairs.data(), n, nullptr, nullptr, nullptr);
-    rq.max_penalty = -1;
-    rq.pair_bound = max_penalty;
-    rq.spans = spans.data();
-    return score_core(e, pen, rq, out);
-  )
+  return score_core(e, pen, over_ranges(ranges, n, "score_ranges"), request(nullptr, nullptr, nullptr, max_penalty), out, {"score_ranges", 0});
 }
 
 namespace {
@@ -1564,7 +1461,11 @@ int align_one_core(awv_engine* e, const awv_penalties* pen, const uint8_t* patte
     const awv_pair p{0, 1, 0};
     OneSink os{cigar_buf, cigar_cap, AWV_OK};
     e->cfg.flags &= ~AWV_F_KEEP_ON_DEVICE;
-    rc = align_core(e, sc.tmp, pen, full_request(&p, 1, result, one_sink, &os));
+    AlignRequest rq = request(result, one_sink, &os);
+    rq.pairs = &p;
+    rq.npairs = 1;
+    if (e->norm_mode != AWV_NORM_OFF) awvn::stats_reset(e->normalize);  // (the one call that does not come through align_call)
+    rc = align_core(e, sc.tmp, pen, rq);
     if (rc == AWV_ERR_SINK && os.rc != AWV_OK) rc = fail(os.rc, "align_one: cigar buffer too small");
   }
   return rc;

@@ -818,7 +818,8 @@ struct EngineRequest {
 };
 
 // The entry point a request names: the cs call (which takes all the encoded call does, and cs_sink as its sink), else the encoded call (which takes the bounds, the check and the clip), else the split, else the clip, else the bounded call, else the verified or the plain one, each
-// on pairs or on ranges (they differ in which engine counters they reset); or awv_score_pairs / awv_score_ranges with the
+// on pairs or on ranges (all follow one rule: a call resets the counters of the steps it asks for and of no other);
+// or awv_score_pairs / awv_score_ranges with the
 // results handed to the sink in one call (status and penalty, no arena).
 int engine_call(awv_engine* e, const EngineRequest& q, awv_sink sink, awv_cs_sink cs_sink, void* user) {
   const awv_penalties* pen = q.pen;

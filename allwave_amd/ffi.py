@@ -528,7 +528,6 @@ class Engine:
             if bounds.shape != (len(pairs),):
                 raise ValueError("max_penalty: need one bound per pair")
             bounds = bounds if len(bounds) else np.zeros(1, dtype=np.int32)
-        fn_v = fn + "_verified"
         res = np.zeros(len(pairs), dtype=RESULT_DTYPE)
         cigars = [None] * len(pairs) if want_cigars else None
         cres = np.zeros(max(len(pairs), 1), dtype=CLIP_DTYPE)[:len(pairs)] if clip is not None else None
@@ -571,64 +570,32 @@ class Engine:
                     cs_texts[i] = C.string_at(cs_arena + int(csres["off"][i]), int(csres["len"][i]))
             return _sink(user, first, n, rptr, arena)
 
+        ptr = lambda arr: None if arr is None else arr.ctypes.data
+        vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)] if verify else None  # (a required vout is one also for an empty list)
+        bonus = 0 if clip is None else int(clip)
+        # the richest form the request names, and what that form takes between the list and the sink
         if mode:
-            fn_x = fn + "_cs"
-            cb = CS_SINK_FN(_cs_sink) if want_cigars or (_sink_hook is not None and cres is not None) else CS_SINK_FN()
-            vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)] if verify else None
-            rc = getattr(load(), fn_x)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), None if bounds is None else bounds.ctypes.data,
-                                       0 if clip is None else int(clip), res.ctypes.data, vres.ctypes.data if verify else None,
-                                       None if cres is None else cres.ctypes.data, None if tres is None else tres.ctypes.data, mode,
-                                       csres.ctypes.data, cb, None)
-            if rc != AWV_OK:
-                raise EngineError(rc, fn_x)
-            return (res, cigars) + ((vres,) if verify else ()) + ((cres,) if cres is not None else ()) + ((tres,) if tres is not None else ()) + \
-                ((cs_texts, csres),)
-        cb = SINK_FN(_sink) if want_cigars or (_sink_hook is not None and (cres is not None or sp is not None)) else SINK_FN()
-        if sp is not None:
-            fn_s = fn + "_split"
-            vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)] if verify else None
-            rc = getattr(load(), fn_s)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), None if bounds is None else bounds.ctypes.data,
-                                       a, min_score, res.ctypes.data, vres.ctypes.data if verify else None, sp[1].ctypes.data,
-                                       sp[0].ctypes.data, sp[2].ctypes.data, cb, None)
-            if rc != AWV_OK:
-                raise EngineError(rc, fn_s)
-            found = (sp[0], self._segment_lists(*sp))
-            return (res, cigars, vres, found) if verify else (res, cigars, found)
-        if tres is not None:
-            fn_e = fn + "_encoded"
-            vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)] if verify else None
-            rc = getattr(load(), fn_e)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), None if bounds is None else bounds.ctypes.data,
-                                       0 if clip is None else int(clip), res.ctypes.data, vres.ctypes.data if verify else None,
-                                       None if cres is None else cres.ctypes.data, tres.ctypes.data, cb, None)
-            if rc != AWV_OK:
-                raise EngineError(rc, fn_e)
-            return (res, cigars) + ((vres,) if verify else ()) + ((cres,) if cres is not None else ()) + (tres,)
-        if cres is not None:
-            fn_c = fn + "_clipped"
-            vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)] if verify else None
-            rc = getattr(load(), fn_c)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), None if bounds is None else bounds.ctypes.data,
-                                       int(clip), res.ctypes.data, vres.ctypes.data if verify else None, cres.ctypes.data, cb, None)
-            if rc != AWV_OK:
-                raise EngineError(rc, fn_c)
-            return (res, cigars, vres, cres) if verify else (res, cigars, cres)
-        if bounds is not None:
-            fn_b = fn + "_bounded"
-            vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)] if verify else None
-            rc = getattr(load(), fn_b)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), bounds.ctypes.data, res.ctypes.data,
-                                       vres.ctypes.data if verify else None, cb, None)
-            if rc != AWV_OK:
-                raise EngineError(rc, fn_b)
-            return (res, cigars, vres) if verify else (res, cigars)
-        if verify:
-            vres = np.zeros(max(len(pairs), 1), dtype=VERIFY_DTYPE)[:len(pairs)]  # (vout is required, also for an empty list)
-            rc = getattr(load(), fn_v)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), res.ctypes.data, vres.ctypes.data, cb, None)
-            if rc != AWV_OK:
-                raise EngineError(rc, fn_v)
-            return res, cigars, vres
-        rc = getattr(load(), fn)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), res.ctypes.data, cb, None)
+            suffix, args = "_cs", (ptr(bounds), bonus, ptr(res), ptr(vres), ptr(cres), ptr(tres), mode, ptr(csres))
+        elif sp is not None:
+            suffix, args = "_split", (ptr(bounds), a, min_score, ptr(res), ptr(vres), ptr(sp[1]), ptr(sp[0]), ptr(sp[2]))
+        elif tres is not None:
+            suffix, args = "_encoded", (ptr(bounds), bonus, ptr(res), ptr(vres), ptr(cres), ptr(tres))
+        elif cres is not None:
+            suffix, args = "_clipped", (ptr(bounds), bonus, ptr(res), ptr(vres), ptr(cres))
+        elif bounds is not None:
+            suffix, args = "_bounded", (ptr(bounds), ptr(res), ptr(vres))
+        elif verify:
+            suffix, args = "_verified", (ptr(res), ptr(vres))
+        else:
+            suffix, args = "", (ptr(res),)
+        sink_fn, sink = (CS_SINK_FN, _cs_sink) if mode else (SINK_FN, _sink)
+        cb = sink_fn(sink) if want_cigars or (_sink_hook is not None and (cres is not None or sp is not None)) else sink_fn()
+        rc = getattr(load(), fn + suffix)(self._h, C.byref(pen), pairs.ctypes.data, len(pairs), *args, cb, None)
         if rc != AWV_OK:
-            raise EngineError(rc, fn)
-        return res, cigars
+            raise EngineError(rc, fn + suffix)
+        found = None if sp is None else (sp[0], self._segment_lists(*sp))
+        texts = (cs_texts, csres) if mode else None
+        return (res, cigars) + tuple(x for x in (vres, cres, found, tres, texts) if x is not None)
 
     def verify_cigars(self, scores, pairs, results, arena):
         """awv_verify_cigars: checks caller-supplied records (a RESULT_DTYPE array whose cigar_off / cigar_len point into
