@@ -365,6 +365,7 @@ void RunOptions::apply(AllPairIterator& it) const {
   if (device_cigar) it.with_device_cigar(true);
   if (cs != 0) it.with_cs(cs);
   if (coverage != 0) it.with_coverage(coverage);
+  if (variants) it.with_variants(true);
   if (max_penalty) it.with_max_penalty(*max_penalty);
   if (max_divergence) it.with_max_divergence(*max_divergence);
   if (clip_match_bonus != 0) it.with_clip(clip_match_bonus, clip_min_score);
@@ -543,6 +544,7 @@ AllPairIterator AllPairIterator::with_sparsification(SparsificationStrategy stra
   it.device_cigar_ = device_cigar_;
   it.cs_ = cs_;
   it.coverage_ = coverage_;
+  it.variants_ = variants_;
   return it;
 }
 AllPairIterator& AllPairIterator::with_device_cigar(bool on) {
@@ -779,6 +781,18 @@ void add(awv_cov_stats& acc, const awv_cov_stats& x) {
   acc.boundaries += x.boundaries;
   acc.reads += x.reads;
 }
+void add(awv_variants_stats& acc, const awv_variants_stats& x) {  // (rows: set behind the merge)
+  acc.kernel_ms += x.kernel_ms;
+  acc.fold_ms += x.fold_ms;
+  acc.items += x.items;
+  acc.failed += x.failed;
+  acc.columns += x.columns;
+  acc.snv += x.snv;
+  acc.ins += x.ins;
+  acc.del += x.del;
+  acc.folds += x.folds;
+  acc.capacity_rows += x.capacity_rows;
+}
 void add(RunReport& acc, const RunReport& x) {
   acc.verify_failures.insert(acc.verify_failures.end(), x.verify_failures.begin(), x.verify_failures.end());
   add(acc.verify_stats, x.verify_stats);
@@ -789,6 +803,7 @@ void add(RunReport& acc, const RunReport& x) {
   add(acc.encode_stats, x.encode_stats);
   add(acc.cs_stats, x.cs_stats);
   add(acc.coverage_stats, x.coverage_stats);
+  add(acc.variants_stats, x.variants_stats);
 }
 
 // One batch's engine call, by name.  ranges (nullable): the batch is these n interval pairs, `pairs` is not read.  Alignment
@@ -862,6 +877,7 @@ struct AllPairIterator::SlotTotals {
   awv_stats engine{};
   RunReport report;
   std::vector<uint32_t> cov_aligned, cov_matched;  // a coverage run: the slot's tracks, read when its batches are done
+  std::vector<awv_variant> var_rows;                // a variants run: the slot's folded table, likewise
 };
 
 // What the slots of one run share.  The settings hold for alignment calls only: a score-only run has none of them.
@@ -875,6 +891,7 @@ struct AllPairIterator::RunState {
   bool verify = false, bounded = false, clipping = false, splitting = false, encoding = false;
   int cs = 0;  // the cs mode of the run's alignment calls (0: none)
   int coverage = 0;  // the roles of a run that accumulates the per-base depth (0: none)
+  bool variants = false;  // a run that tallies the allele table
   uint64_t n_bases = 0;  // the sum of the sequences' lengths
   int normalizing = AWV_NORM_OFF;
   std::optional<double> div;  // the divergence bound of a bounded run
@@ -1123,6 +1140,7 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   rs.cs = call.score_only ? 0 : call.cs;
   rs.normalizing = call.score_only ? AWV_NORM_OFF : normalize_;
   rs.coverage = call.score_only ? 0 : coverage_;
+  rs.variants = variants_ && !call.score_only;
   for (const Sequence& q : sequences_) rs.n_bases += q.seq.size();
   rs.div = divergence_bound();
   rs.pen = to_penalties(params_);
@@ -1142,6 +1160,7 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
       rs.lap("sequences uploaded");
       // (a new set ended whatever coverage the engine had: the slot's depth starts from zero with every run)
       if (rs.coverage != 0 && awv_engine_coverage_begin(e, rs.coverage, clip_min_score_) != AWV_OK) throw AlignmentError(std::string("coverage: ") + awv_last_error());
+      if (rs.variants && awv_engine_variants_begin(e, clip_min_score_, 0) != AWV_OK) throw AlignmentError(std::string("variants: ") + awv_last_error());
     } catch (...) {
       rs.fail(std::current_exception());
     }
@@ -1176,10 +1195,21 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
         awv_engine_coverage_stats(e, &cx);
         add(t.report.coverage_stats, cx);
       }
+      if (rs.variants && !rs.stop.load()) {  // the slot's table, and what it cost
+        SlotTotals& t = rs.totals[s];
+        uint64_t n_rows = 0;
+        if (awv_engine_variants_read(e, nullptr, 0, &n_rows) != AWV_OK) throw AlignmentError(std::string("variants: ") + awv_last_error());
+        t.var_rows.resize((size_t)n_rows);
+        if (n_rows && awv_engine_variants_read(e, t.var_rows.data(), n_rows, &n_rows) != AWV_OK) throw AlignmentError(std::string("variants: ") + awv_last_error());
+        awv_variants_stats vx{};
+        awv_engine_variants_stats(e, &vx);
+        add(t.report.variants_stats, vx);
+      }
     } catch (...) {
       rs.fail(std::current_exception());
     }
     if (e && rs.coverage != 0) awv_engine_coverage_begin(e, 0, 0);  // the accumulators go with the run
+    if (e && rs.variants) awv_engine_variants_end(e);               // and so does the table
   };
   std::vector<std::thread> th;
   try {
@@ -1197,6 +1227,7 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   stats_ = awv_stats{};
   if (first == 0) report_ = RunReport{};  // a run from the list's start begins anew; a later range (next()'s chunks) adds to it
   if (first == 0 && !call.score_only) cov_ = Coverage{};
+  if (first == 0 && !call.score_only) var_.clear();
   if (rs.coverage != 0 && cov_.offsets.empty()) {
     cov_.offsets.assign(sequences_.size() + 1, 0);
     for (size_t i = 0; i < sequences_.size(); ++i) cov_.offsets[i + 1] = cov_.offsets[i] + sequences_[i].seq.size();
@@ -1211,6 +1242,13 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
       cov_.aligned[i] += t.cov_aligned[i];
       cov_.matched[i] += t.cov_matched[i];
     }
+  }
+  if (rs.variants) {  // the slots' tables (and, for next()'s chunks, the table so far) merge by key: sum and min
+    for (const SlotTotals& t : rs.totals) var_.insert(var_.end(), t.var_rows.begin(), t.var_rows.end());
+    uint64_t left = var_.size();
+    if (awv_variants_fold_host(var_.data(), var_.size(), &left) != AWV_OK) throw AlignmentError(std::string("variants: ") + awv_last_error());
+    var_.resize((size_t)left);
+    report_.variants_stats.rows = left;
   }
   sort_verify_failures(report_.verify_failures);
   if (rs.err) std::rethrow_exception(rs.err);

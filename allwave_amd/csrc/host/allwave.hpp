@@ -147,7 +147,7 @@ class AllPairIterator;
 
 // The options of one run that filter or rewrite what it delivers, in one place: AllPairIterator::with_max_penalty,
 // with_max_divergence (std::nullopt: no bound), with_clip and with_split (match bonus 0: off), with_normalize (AWV_NORM_OFF: off),
-// with_device_cigar, with_cs (0: off), with_coverage (0: off).
+// with_device_cigar, with_cs (0: off), with_coverage (0: off), with_variants.
 struct RunOptions {
   std::optional<int> max_penalty;
   std::optional<double> max_divergence;
@@ -159,8 +159,9 @@ struct RunOptions {
   bool device_cigar = false;
   int cs = 0;
   int coverage = 0;
+  bool variants = false;
   void apply(AllPairIterator& it) const;  // the with_* calls of what is set; they throw std::invalid_argument as documented there
-  bool any() const { return max_penalty || max_divergence || clip_match_bonus != 0 || split_match_bonus != 0 || normalize != AWV_NORM_OFF || device_cigar || cs != 0 || coverage != 0; }
+  bool any() const { return max_penalty || max_divergence || clip_match_bonus != 0 || split_match_bonus != 0 || normalize != AWV_NORM_OFF || device_cigar || cs != 0 || coverage != 0 || variants; }
 };
 
 // What a run leaves behind besides its results (AllPairIterator::last_report): the failed checks sorted by pair-list index,
@@ -175,6 +176,7 @@ struct RunReport {
   awv_encode_stats encode_stats{};
   awv_cs_stats cs_stats{};
   awv_cov_stats coverage_stats{};
+  awv_variants_stats variants_stats{};  // rows: of the merged table; folds: the engines' folds
 };
 
 // The per-base depth a run with with_coverage leaves behind (AllPairIterator::last_coverage): sequence s owns entries
@@ -298,6 +300,17 @@ class AllPairIterator {  // iterator.rs:12-171
   AllPairIterator& with_coverage(int roles);
   int coverage() const { return coverage_; }
   const Coverage& last_coverage() const { return cov_; }
+  // Every alignment consumer also tallies the per-site allele table of what the engine aligned (awv_engine_variants_begin;
+  // include/allwave_hip.h has the contract).  Every slot's engine keeps a table of its own; the slots' tables are concatenated and
+  // folded on the host (awv_variants_fold_host: sum and min), so several devices, or one ordinal given twice, give the
+  // one-engine table exactly.  Clipping runs count the clips that reach clip_min_score.  last_variants(): the table of the last
+  // run, in key order (next(): since the list's start); empty without the setting.
+  AllPairIterator& with_variants(bool on) {
+    variants_ = on;
+    return *this;
+  }
+  bool variants() const { return variants_; }
+  const std::vector<awv_variant>& last_variants() const { return var_; }
   AllPairIterator& with_max_penalty(int max_penalty);
   AllPairIterator& with_max_divergence(double max_divergence);
   // of the last run (next(): of the chunks since the list's start), summed over the slots
@@ -411,6 +424,8 @@ class AllPairIterator {  // iterator.rs:12-171
   int cs_ = 0;                    // with_cs (0: off)
   int coverage_ = 0;              // with_coverage (0: off)
   Coverage cov_;                  // of the last run (next(): since the list's start)
+  bool variants_ = false;         // with_variants
+  std::vector<awv_variant> var_;  // the allele table of the last run (next(): since the list's start)
   int split_bonus_ = 0;  // with_split (0: off)
   int64_t split_min_score_ = 1;
   bool drops_pairs() const { return bounded() || clip() || split(); }  // consumers that keep a slot per pair compact what was delivered
@@ -448,6 +463,7 @@ class AllPairParallelIterator {
   awv_encode_stats last_encode_stats() const { return it_.last_encode_stats(); }
   awv_cs_stats last_cs_stats() const { return it_.last_cs_stats(); }
   const Coverage& last_coverage() const { return it_.last_coverage(); }
+  const std::vector<awv_variant>& last_variants() const { return it_.last_variants(); }
   const RunReport& last_report() const { return it_.last_report(); }
  private:
   friend class AllPairIterator;

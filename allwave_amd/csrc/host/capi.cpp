@@ -21,10 +21,12 @@ void set_err(char* err, size_t cap, const std::string& m) {
 // for awh_last_verify, the other counters for awh_last_bounds, awh_last_clip, awh_last_split, awh_last_normalize, awh_last_encode and awh_last_cs.
 thread_local RunReport g_report;
 thread_local Coverage g_coverage;  // and its last_coverage(), for awh_last_coverage
+thread_local std::vector<awv_variant> g_variants;  // and its last_variants(), for awh_last_variants
 template <typename It>
 void keep(const It& it) {
   g_report = it.last_report();
   g_coverage = it.last_coverage();
+  g_variants = it.last_variants();
 }
 // The options of the calling thread's NEXT alignment hook: awh_set_bounds, awh_set_clip, awh_set_split, awh_set_normalize and
 // awh_set_device_cigar, awh_set_cs, awh_set_coverage
@@ -41,6 +43,8 @@ RunOptions take_run_options() {
   g_report.cs_stats = awv_cs_stats{};
   g_report.coverage_stats = awv_cov_stats{};
   g_coverage = Coverage{};
+  g_report.variants_stats = awv_variants_stats{};
+  g_variants.clear();
   return o;
 }
 // the hooks' orientation code on an iterator: 0 forward, 1 WFA, 2 mash, 3 WFA by two full alignments per pair
@@ -721,6 +725,22 @@ int awh_last_coverage(uint64_t** offsets, size_t* n_offsets, uint32_t** aligned,
   if (*n_offsets) memcpy(*offsets, g_coverage.offsets.data(), *n_offsets * sizeof(uint64_t));
   if (nb) memcpy(*aligned, g_coverage.aligned.data(), nb * sizeof(uint32_t));
   if (nb) memcpy(*matched, g_coverage.matched.data(), nb * sizeof(uint32_t));
+  return 0;
+}
+// ---- the per-site allele table ----
+// The calling thread's NEXT alignment hook runs with_variants(on != 0); the hooks after it run without again.
+void awh_set_variants(int on) { g_next.variants = on != 0; }
+// last_variants() of the calling thread's last alignment hook: *rows is a malloc'd copy of the *n_rows rows (awh_free), stats the
+// run's awv_variants_stats summed over the slots.  Returns -1 when memory runs out.
+int awh_last_variants(awv_variant** rows, size_t* n_rows, awv_variants_stats* stats) {
+  *stats = g_report.variants_stats;
+  *n_rows = g_variants.size();
+  *rows = (awv_variant*)malloc(std::max<size_t>(*n_rows, 1) * sizeof(awv_variant));
+  if (!*rows) {
+    *n_rows = 0;
+    return -1;
+  }
+  if (*n_rows) memcpy(*rows, g_variants.data(), *n_rows * sizeof(awv_variant));
   return 0;
 }
 // last_encode_stats() of the calling thread's last alignment hook: {pairs, runs, text_bytes, columns} and the summed kernel time

@@ -62,6 +62,10 @@ struct Args {
   bool have_coverage = false;
   int coverage_of = AWV_COV_BOTH;  // --coverage-of target|query|both
   bool have_coverage_of = false;
+  std::string variants;       // --variants FILE: the per-site allele table of what was aligned, tallied on the device
+  bool have_variants = false;
+  long variants_min_count = 1;  // --variants-min-count N: rows with a smaller count are not written
+  bool have_variants_min_count = false;
 };
 
 [[noreturn]] void die(const std::string& m, int code = 2) {
@@ -259,6 +263,19 @@ int main(int argc, char** argv) {
       if (v != "short" && v != "long") die("--cs expects short or long");
       a.cs = v == "short" ? AWV_CS_SHORT : AWV_CS_LONG;
     }
+    else if (k == "--variants") {
+      a.variants = val();
+      if (a.variants.empty()) die("--variants expects a file name");
+      a.have_variants = true;
+    }
+    else if (k == "--variants-min-count") {
+      const std::string v = val();
+      char* end = nullptr;
+      a.variants_min_count = strtol(v.c_str(), &end, 10);
+      if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || !end || *end != 0 || a.variants_min_count < 1)
+        die("--variants-min-count expects a count N >= 1");
+      a.have_variants_min_count = true;
+    }
     else if (k == "--coverage") {
       a.coverage = val();
       if (a.coverage.empty()) die("--coverage expects a file name");
@@ -305,12 +322,12 @@ int main(int argc, char** argv) {
                    "                   [--device N | --devices LIST] [--shard R/N] [--score-only [--max-penalty N]] [--plan-device N] [--verify]\n"
                    "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
                    "                   [--split A --split-min-score S] [--normalize left|right] [--device-cigar] [--cs short|long]\n"
-                   "                   [--coverage FILE [--coverage-of target|query|both]]\n"
+                   "                   [--coverage FILE [--coverage-of target|query|both]] [--variants FILE [--variants-min-count N]]\n"
                    "       allwave_hip -i in.fa --check-paf FILE [-s scores | -x ANI] [--check-optimal] [--partial] [--device N]\n"
                    "       allwave_hip -i in.fa --align-paf FILE [-s scores | -x ANI] [-o out.paf] [--verify] [--score-only] [--device N | --devices LIST]\n"
                    "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
                    "                   [--split A --split-min-score S] [--normalize left|right] [--device-cigar] [--cs short|long]\n"
-                   "                   [--coverage FILE [--coverage-of target|query|both]]\n"
+                   "                   [--coverage FILE [--coverage-of target|query|both]] [--variants FILE [--variants-min-count N]]\n"
                    "  --verify         check every alignment on the device before it is written (columns, counts, penalty); the summary\n"
                    "                   line gains `verified N pairs, F failed, K ms`, failures go to stderr, exit status 4 if any\n"
                    "  --check-paf FILE align nothing: check every line of FILE (12 columns + cg:Z:) against in.fa on the device; one line\n"
@@ -360,6 +377,14 @@ int main(int argc, char** argv) {
                    "                   --shard every process writes the depth of its own shard to its own FILE (add the files up by\n"
                    "                   position); the summary line gains `coverage I items, B boundaries, K ms`\n"
                    "  --coverage-of target|query|both  whose bases an aligned column counts for (default both)\n"
+                   "  --variants FILE  tally on the device, per site of every target, which alleles the run's alignments carry and how many\n"
+                   "                   carry each, and write FILE: one line tname<TAB>pos<TAB>snv|del|ins<TAB>len<TAB>ref<TAB>alt<TAB>count per\n"
+                   "                   distinct (site, allele), sorted by target, position, type, length; ref: the target's bases (. for an\n"
+                   "                   insertion), alt: the query's (. for a deletion), upper case; what counts is what is written, as for\n"
+                   "                   --coverage; --normalize left makes indel sites canonical across queries; the PAF is byte-identical;\n"
+                   "                   also with --align-paf; not with --score-only, --check-paf or --mash-matrix; under --shard every\n"
+                   "                   process writes its own shard's table; the summary line gains `variants I items, E events, R rows, K ms`\n"
+                   "  --variants-min-count N  write only rows that N or more alignments carry (default 1)\n"
                    "  --plan-device N  plan on device N: --mash-matrix, the -p pair list and mash orientation (the same output as\n"
                    "                   the host planner; with --shard every rank plans the whole list on its own plan device)\n";
       return 0;
@@ -397,6 +422,10 @@ int main(int argc, char** argv) {
   if (a.cs != 0 && a.have_check_paf) die("the argument '--cs' cannot be used with '--check-paf'");
   if (a.cs != 0 && a.mash_matrix) die("the argument '--cs' cannot be used with '--mash-matrix'");
   if (a.have_coverage_of && !a.have_coverage) die("the argument '--coverage-of' requires '--coverage'");
+  if (a.have_variants_min_count && !a.have_variants) die("the argument '--variants-min-count' requires '--variants'");
+  if (a.have_variants && a.score_only) die("the argument '--variants' cannot be used with '--score-only'");
+  if (a.have_variants && a.have_check_paf) die("the argument '--variants' cannot be used with '--check-paf'");
+  if (a.have_variants && a.mash_matrix) die("the argument '--variants' cannot be used with '--mash-matrix'");
   if (a.have_coverage && a.score_only) die("the argument '--coverage' cannot be used with '--score-only'");
   if (a.have_coverage && a.have_check_paf) die("the argument '--coverage' cannot be used with '--check-paf'");
   if (a.have_coverage && a.mash_matrix) die("the argument '--coverage' cannot be used with '--mash-matrix'");
@@ -519,6 +548,7 @@ int main(int argc, char** argv) {
     it.with_device_cigar(a.device_cigar);
     it.with_cs(a.cs);
     if (a.have_coverage) it.with_coverage(a.coverage_of);
+    it.with_variants(a.have_variants);
     if (a.forward_only) it.with_orientation(Orientation::ForwardOnly);
     it.with_full_wfa_orientation(a.wfa_orientation_full);
     it.with_devices(devices);
@@ -598,6 +628,45 @@ int main(int argc, char** argv) {
       cout_.close();
       if (cout_.fail()) die("write error on the coverage output", 1);
     }
+    if (a.have_variants) {  // tname, pos, type, len, ref, alt, count per row of the table, in key order
+      std::ofstream vout(a.variants, std::ios::binary);
+      if (!vout) die("cannot create " + a.variants, 1);
+      static const char* const type_names[3] = {"snv", "del", "ins"};
+      const auto upper = [](uint8_t c) { return (char)(c >= 'a' && c <= 'z' ? c - 32 : c); };
+      const auto comp = [](uint8_t c) {  // the engine's reverse complement: ACGT in either case, anything else N
+        switch (c) {
+          case 'A': case 'a': return 'T';
+          case 'C': case 'c': return 'G';
+          case 'G': case 'g': return 'C';
+          case 'T': case 't': return 'A';
+          default: return 'N';
+        }
+      };
+      std::string buf;
+      const std::vector<awv_variant>& rows = it.last_variants();
+      for (size_t k = 0; k < rows.size(); ++k) {
+        const awv_variant& r = rows[k];
+        if ((long)r.count >= a.variants_min_count) {
+          const std::vector<uint8_t>& tseq = sequences[(size_t)r.t_idx].seq;
+          const std::vector<uint8_t>& qseq = sequences[(size_t)(r.rep >> 32)].seq;
+          const bool rev = ((r.rep >> 31) & 1) != 0;
+          const size_t p_beg = (size_t)(r.rep & 0x7fffffffu), len = (size_t)r.len;
+          std::string ref, alt;
+          if (r.type != AWV_VAR_INS)
+            for (size_t i = 0; i < len && (size_t)r.pos + i < tseq.size(); ++i) ref += upper(tseq[(size_t)r.pos + i]);
+          if (r.type != AWV_VAR_DEL)
+            for (size_t i = 0; i < len && p_beg + i < qseq.size(); ++i) alt += rev ? comp(qseq[qseq.size() - 1 - (p_beg + i)]) : upper(qseq[p_beg + i]);
+          buf += sequences[(size_t)r.t_idx].id + '\t' + std::to_string(r.pos) + '\t' + type_names[r.type >= 0 && r.type < 3 ? r.type : 0] + '\t' +
+                 std::to_string(r.len) + '\t' + (r.type != AWV_VAR_INS ? ref : ".") + '\t' + (r.type != AWV_VAR_DEL ? alt : ".") + '\t' + std::to_string(r.count) + '\n';
+        }
+        if (buf.size() >= (1u << 20) || k + 1 == rows.size()) {
+          vout.write(buf.data(), (std::streamsize)buf.size());
+          buf.clear();
+        }
+      }
+      vout.close();
+      if (vout.fail()) die("write error on the variants output", 1);
+    }
     const BoundStats bs = it.last_bound_stats();
     const size_t above = (size_t)(bs.above_penalty + bs.above_divergence);  // (pairs above a bound get no line)
     const ClipStats cs = it.last_clip_stats();
@@ -635,6 +704,11 @@ int main(int argc, char** argv) {
         const awv_cov_stats vs = it.last_report().coverage_stats;
         w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", coverage %llu items, %llu boundaries, %.2f ms", (unsigned long long)vs.items,
                       (unsigned long long)vs.boundaries, vs.kernel_ms);
+      }
+      if (a.have_variants && w > 0 && (size_t)w < sizeof(buf)) {
+        const awv_variants_stats vs = it.last_report().variants_stats;
+        w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", variants %llu items, %llu events, %llu rows, %.2f ms", (unsigned long long)vs.items,
+                      (unsigned long long)(vs.snv + vs.ins + vs.del), (unsigned long long)vs.rows, vs.kernel_ms + vs.fold_ms);
       }
       if (a.verify && w > 0 && (size_t)w < sizeof(buf)) {
         const awv_verify_stats vs = it.last_verify_stats();

@@ -152,6 +152,91 @@ inline awv_var_item var_one(int32_t q_idx, int32_t t_idx, bool revcomp, const ui
   return make_item(AWV_VR_OK, snv, ins, del);
 }
 
+// ---- the walk in lanes and chunks (variants.hip's kernel; tests/variants_walk_driver.cpp runs the same functions serially) --------
+// The kernel takes a string in chunks of 64 lanes x 16 op bytes (text_pass.hpp).  What is new relative to the cs walk stands here
+// on plain values: the allele hash of a 'D' run that crosses lanes or chunks, which events a lane owns and in which order, and a
+// run's pos / p_beg from the positions at its end.
+
+// The segmented hash scan's element: of a stretch of columns, the hash and B^length of the 'D' bytes behind its last column other
+// than 'D' (`reset`: it holds one; else the stretch lies wholly inside a run and is a pass-through).
+struct HashSeg {
+  uint64_t h, pw;
+  uint32_t reset;
+};
+__host__ __device__ inline HashSeg seg_identity() { return HashSeg{0, 1, 0u}; }
+// a then b; associative, with seg_identity() on both sides
+__host__ __device__ inline HashSeg seg_combine(const HashSeg& a, const HashSeg& b) {
+  if (b.reset) return b;
+  return HashSeg{hash_combine(a.h, b.h, b.pw), mulmod61(a.pw, b.pw), a.reset};
+}
+// the hash of the 'D' run in progress behind a stretch, `carry` the one in progress before it
+__host__ __device__ inline uint64_t seg_behind(uint64_t carry, const HashSeg& s) { return s.reset ? s.h : hash_combine(carry, s.h, s.pw); }
+
+// A lane's 16 bytes as masks (bit j: byte j), all inside `valid`, the bytes that are columns -- a contiguous range.
+struct LaneCols {
+  uint32_t valid, x, i, d;  // ... an 'X', an 'I', a 'D'
+  uint32_t brk;             // a column > 0 whose op differs from the one before it
+  uint32_t prev_i, prev_d;  // 1: the op before the lane's first byte is an 'I' / a 'D'
+};
+__host__ __device__ inline int popc32(uint32_t m) { return __builtin_popcount(m); }
+__host__ __device__ inline int top_bit(uint32_t m) { return 31 - __builtin_clz(m); }  // m != 0
+// the breaks that end an 'I' run / a 'D' run: the lane that holds the break owns the run's event
+__host__ __device__ inline uint32_t ends_i(const LaneCols& c) { return c.brk & ((c.i << 1) | c.prev_i); }
+__host__ __device__ inline uint32_t ends_d(const LaneCols& c) { return c.brk & ((c.d << 1) | c.prev_d); }
+__host__ __device__ inline uint32_t lane_event_count(const LaneCols& c) { return (uint32_t)(popc32(c.x) + popc32(ends_i(c)) + popc32(ends_d(c))); }
+// the 'D' columns at the lane's upper end: their run goes on into the next lane (or ends with the string)
+__host__ __device__ inline uint32_t tail_d(const LaneCols& c) {
+  const uint32_t other = c.valid & ~c.d;
+  return other == 0 ? c.d : c.d & ~(((uint32_t)2 << top_bit(other)) - 1u);
+}
+// the lane's element of the scan; byte(k): the k-th of the pattern bytes the lane's columns consume
+template <typename Byte>
+__host__ __device__ inline HashSeg lane_seg(const LaneCols& c, Byte&& byte) {
+  const uint32_t tail = tail_d(c), takes_p = c.valid & ~c.i;
+  uint64_t h = 0;
+  for (uint32_t m = tail; m != 0; m &= m - 1) h = hash_push(h, byte(popc32(takes_p & ((m & (0u - m)) - 1u))));  // at most 16 trips: a 16-bit mask
+  return HashSeg{h, hash_pow((uint64_t)popc32(tail)), (uint32_t)((c.valid & ~tail) != 0)};
+}
+// a gap run's event from the positions (x, y) behind its last column and its length
+__host__ __device__ inline awv_variant gap_event(int32_t q_idx, int32_t t_idx, bool revcomp, bool is_d, int64_t x, int64_t y, int64_t len, uint64_t hash) {
+  return is_d ? make_event(t_idx, y, AWV_VAR_INS, len, hash, make_rep(q_idx, revcomp, x - len))
+              : make_event(t_idx, y - len, AWV_VAR_DEL, len, 0, make_rep(q_idx, revcomp, x));
+}
+// The lane's events in order, each handed to put(event): ascending by byte; at a break the run that ends there, then the byte's own
+// SNV.  col0: the column of byte 0 (may be negative); rs0: the column at which the run the lane begins in started; (x0, y0): the
+// positions at the lane's first column; in_h: the hash of the 'D' run in progress before the lane (seg_behind of the lower lanes).
+template <typename Byte, typename Put>
+__host__ __device__ inline void lane_events(const LaneCols& c, int32_t q_idx, int32_t t_idx, bool revcomp, int64_t col0, int64_t rs0, int64_t x0, int64_t y0,
+                                            uint64_t in_h, Byte&& byte, Put&& put) {
+  const uint32_t e_i = ends_i(c), e_d = ends_d(c), takes_p = c.valid & ~c.i, takes_t = c.valid & ~c.d;
+  const uint32_t head_d = c.d & ~tail_d(c);  // the 'D' columns whose run ends inside the lane
+  uint64_t h = 0;     // of the 'D' run in progress, its bytes in this lane
+  uint32_t cnt = 0;   // how many they are
+  bool begun = false; // the run began inside the lane
+  for (uint32_t m = c.x | e_i | e_d | head_d; m != 0; m &= m - 1) {  // at most 16 trips: a 16-bit mask
+    const uint32_t bit = m & (0u - m), below = bit - 1u;
+    const int j = top_bit(bit);
+    const int kp = popc32(takes_p & below);
+    const int64_t x = x0 + kp, y = y0 + popc32(takes_t & below);
+    if ((e_i | e_d) & bit) {
+      const uint32_t lower = c.brk & below;
+      const int64_t len = col0 + j - (lower != 0 ? col0 + top_bit(lower) : rs0);
+      const bool is_d = (e_d & bit) != 0;
+      put(gap_event(q_idx, t_idx, revcomp, is_d, x, y, len, is_d ? (begun ? h : hash_combine(in_h, h, hash_pow(cnt))) : 0));
+    }
+    if (c.x & bit) put(make_event(t_idx, y, AWV_VAR_SNV, 1, hash_push(0, byte(kp)), make_rep(q_idx, revcomp, x)));
+    if (head_d & bit) {
+      if (c.brk & bit) {
+        h = 0;
+        cnt = 0;
+        begun = true;
+      }
+      h = hash_push(h, byte(kp));
+      ++cnt;
+    }
+  }
+}
+
 // The fold as the host does it (the yardstick, and the merge of several engines' tables): rows[0 .. n) sorted by key, equal keys
 // reduced to one row (sum of count, min of rep), compacted to the front; returns the number of rows left.
 inline uint64_t fold_rows(awv_variant* rows, uint64_t n) {
@@ -168,4 +253,24 @@ inline uint64_t fold_rows(awv_variant* rows, uint64_t n) {
   return w;
 }
 
+struct State;                  // variants.hip: the accumulated table, the pass's device buffers and the stats since begin
+void state_release(State* s);  // frees them and the object itself (nullptr: nothing)
+bool active(const State* s);   // between awv_engine_variants_begin and the end of its table
+
+// engine.hip's hook: one batch of an aligning call, on the engine's stream, after the clip / split step; the arguments are
+// awvcov::coverage_batch's, the items awvw::contributing_items' under the begin's clip_min_score.  Appends the batch's events to the table.
+int variants_batch(awv_engine* e, const awv_pair* pairs, int64_t n, const awv_result* results, const uint8_t* d_arena, uint64_t arena_bytes,
+                   const awv_clip_result* clips, const uint64_t* seg_first, const awv_split_index* iout, const awv_clip_result* sout, const Span* spans);
+
+// variants_fold.hip: the fold on the device.  d_rows[0 .. n), events or rows in any order, become fold_rows' rows in place, on
+// `stream`; *n_out is their number and *ms gains the HIP-event time.  The scratch only ever grows.
+struct FoldScratch;
+FoldScratch* fold_scratch_new();
+void fold_scratch_release(FoldScratch* fs);  // (nullptr: nothing)
+constexpr uint64_t MAX_FOLD_ROWS = (uint64_t)1 << 31;  // the sort's permutation is 32 bits wide
+int fold_device(hipStream_t stream, FoldScratch* fs, awv_variant* d_rows, uint64_t n, uint64_t* n_out, float* ms);
+
 }  // namespace awvvar
+
+// engine.hip
+awvvar::State*& awv_internal_variants(awv_engine* e);

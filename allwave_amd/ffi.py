@@ -93,6 +93,10 @@ AWV_VR_OK = 0
 AWV_VR_SKIPPED = 1
 AWV_VR_BAD_OP = 2
 AWV_VR_LENGTHS = 3
+#: `fold` of awv_variants_cigars: the unfolded events, the call's folded table, or into the engine's table
+AWV_VTAB_EVENTS = 0
+AWV_VTAB_FOLDED = 1
+AWV_VTAB_ACCUMULATE = 2
 #: sketch kinds of device pair planning (awv_sketch)
 AWV_SK_CANONICAL = 0
 AWV_SK_FORWARD = 1
@@ -116,7 +120,8 @@ EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine
            "awv_cs_one_host", "awv_cs_cigars", "awv_cs_ranges", "awv_align_pairs_cs", "awv_align_ranges_cs", "awv_engine_cs_stats",
            "awv_coverage_one_host", "awv_engine_coverage_begin", "awv_engine_coverage_read", "awv_coverage_cigars", "awv_coverage_ranges",
            "awv_engine_coverage_stats",
-           "awv_variants_one_host", "awv_variants_fold_host")
+           "awv_variants_one_host", "awv_variants_fold_host", "awv_engine_variants_begin", "awv_engine_variants_end", "awv_engine_variants_read", "awv_engine_variants_stats",
+           "awv_variants_cigars", "awv_variants_ranges", "awv_variants_fold")
 
 
 class EngineConfig(C.Structure):
@@ -176,6 +181,11 @@ class EncodeStats(C.Structure):
 
 class CsStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("pairs", C.c_uint64), ("failed", C.c_uint64), ("text_bytes", C.c_uint64), ("columns", C.c_uint64)]
+
+
+class VariantsStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("fold_ms", C.c_double), ("items", C.c_uint64), ("failed", C.c_uint64), ("columns", C.c_uint64),
+                ("snv", C.c_uint64), ("ins", C.c_uint64), ("del_", C.c_uint64), ("rows", C.c_uint64), ("folds", C.c_uint64), ("capacity_rows", C.c_uint64)]
 
 
 class CovStats(C.Structure):
@@ -318,6 +328,14 @@ def load():
         L.awv_variants_one_host.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                             C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
         L.awv_variants_fold_host.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.awv_engine_variants_begin.argtypes = [C.c_void_p, C.c_int64, C.c_uint64]
+        L.awv_engine_variants_end.argtypes = [C.c_void_p]
+        L.awv_engine_variants_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.awv_engine_variants_stats.argtypes = [C.c_void_p, C.POINTER(VariantsStats)]
+        L.awv_variants_cigars.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_uint64, C.POINTER(C.c_uint64)]
+        L.awv_variants_ranges.argtypes = L.awv_variants_cigars.argtypes
+        L.awv_variants_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         _LIB = L
     return _LIB
 
@@ -353,6 +371,16 @@ class EngineError(RuntimeError):
         msg = load().awv_last_error()
         super().__init__("%s failed with %d: %s" % (where, code, (msg or b"").decode(errors="replace")))
         self.code = code
+
+
+class RowsDoNotFit(Exception):
+    """variants_read / variants_cigars / variants_ranges with a `cap` smaller than the table: nothing was written; n_rows is
+    what it takes (and items, for the calls on records, what the pass made of them)."""
+
+    def __init__(self, n_rows, items=None):
+        super().__init__("%d rows do not fit the buffer" % n_rows)
+        self.n_rows = int(n_rows)
+        self.items = items
 
 
 class Engine:
@@ -774,6 +802,96 @@ class Engine:
     def coverage_stats(self):
         """awv_engine_coverage_stats: kernel_ms, items, failed, columns, boundaries, reads since coverage_begin."""
         return self._stats("awv_engine_coverage_stats", CovStats)
+
+    def variants_begin(self, clip_min_score=0, reserve_rows=0):
+        """awv_engine_variants_begin: from now on every aligning call of this engine appends its contributing alignments' (site,
+        allele) events to a table on the device.  reserve_rows: the row buffer's first size (0: the default)."""
+        rc = load().awv_engine_variants_begin(self._h, int(clip_min_score), int(reserve_rows))
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_engine_variants_begin")
+
+    def variants_end(self):
+        """awv_engine_variants_end: ends the table and frees its buffer; later aligning calls append nothing."""
+        rc = load().awv_engine_variants_end(self._h)
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_engine_variants_end")
+
+    def variants_read(self, cap=None):
+        """awv_engine_variants_read: the folded table so far, a VARIANT_DTYPE array in key order.  cap: the rows the buffer holds
+        (None: measured first, by a read without a buffer -- a fold of its own); when the table is larger nothing is written and
+        RowsDoNotFit is raised."""
+        n = C.c_uint64(0)
+        if cap is None:
+            rc = load().awv_engine_variants_read(self._h, None, 0, C.byref(n))
+            if rc != AWV_OK:
+                raise EngineError(rc, "awv_engine_variants_read")
+            cap = n.value
+        rows = np.zeros(max(int(cap), 1), dtype=VARIANT_DTYPE)
+        rc = load().awv_engine_variants_read(self._h, rows.ctypes.data, int(cap), C.byref(n))
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_engine_variants_read")
+        if n.value > int(cap):
+            raise RowsDoNotFit(n.value)
+        return rows[:n.value].copy()
+
+    def variants_stats(self):
+        """awv_engine_variants_stats: kernel_ms, fold_ms, items, failed, columns, snv, ins, del_, rows, folds, capacity_rows since variants_begin."""
+        return self._stats("awv_engine_variants_stats", VariantsStats)
+
+    def variants_cigars(self, pairs, results, arena, slices=None, fold=AWV_VTAB_EVENTS, cap=None):
+        """awv_variants_cigars: the events of caller-supplied records (a RESULT_DTYPE array whose cigar_off / cigar_len point
+        into `arena`, bytes or a uint8 array) against the resident set, on the device.  fold: AWV_VTAB_EVENTS (the count-1 events
+        in record order, then column order), AWV_VTAB_FOLDED (the call's table) or AWV_VTAB_ACCUMULATE (into the engine's table).
+        Returns (a VAR_ITEM_DTYPE array, a VARIANT_DTYPE array); under AWV_VTAB_ACCUMULATE the second entry is the number of
+        events appended.  cap: the rows the buffer holds (None: one row per column of the records, which no item exceeds, so the
+        pass runs once); when there are more rows nothing is written and RowsDoNotFit is raised."""
+        return self._variants("awv_variants_cigars", self._pair_array(pairs), results, arena, slices, fold, cap)
+
+    def variants_ranges(self, ranges, results, arena, slices=None, fold=AWV_VTAB_EVENTS, cap=None):
+        """variants_cigars on interval pairs (awv_variants_ranges)."""
+        return self._variants("awv_variants_ranges", self._range_array(ranges), results, arena, slices, fold, cap)
+
+    def _variants(self, fn, pairs, results, arena, slices, fold, cap):
+        results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+        if results.shape != (len(pairs),):
+            raise ValueError("results: need one record per pair")
+        sl = self._slice_array(slices, len(results))
+        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
+        nbytes = int(arena.size)
+        if nbytes == 0:
+            arena = np.zeros(1, dtype=np.uint8)
+        items = np.zeros(max(len(results), 1), dtype=VAR_ITEM_DTYPE)[:len(results)]
+        n = C.c_uint64(0)
+
+        def call(rows, room):
+            rc = getattr(load(), fn)(self._h, pairs.ctypes.data, len(pairs), results.ctypes.data, arena.ctypes.data, nbytes,
+                                     None if sl is None else sl.ctypes.data, int(fold), items.ctypes.data, None if rows is None else rows.ctypes.data, room,
+                                     C.byref(n))
+            if rc != AWV_OK:
+                raise EngineError(rc, fn)
+
+        if fold == AWV_VTAB_ACCUMULATE:
+            call(None, 0)
+            return items, int(n.value)
+        if cap is None:  # an event takes a column or more
+            done = results["status"] == 0
+            width = results["cigar_len"].astype(np.int64) if sl is None else np.minimum(sl["col_end"].astype(np.int64) - sl["col_beg"].astype(np.int64), results["cigar_len"].astype(np.int64))
+            cap = int(np.maximum(width, 0)[done].sum())
+        rows = np.zeros(max(int(cap), 1), dtype=VARIANT_DTYPE)
+        call(rows, int(cap))
+        if n.value > int(cap):
+            raise RowsDoNotFit(n.value, items)
+        return items, rows[:n.value].copy()
+
+    def variants_fold(self, rows):
+        """awv_variants_fold: events or rows (VARIANT_DTYPE) sorted by key and reduced on the device; a new array."""
+        rows = np.array(rows, dtype=VARIANT_DTYPE, copy=True).reshape(-1)
+        buf = rows if len(rows) else np.zeros(1, dtype=VARIANT_DTYPE)
+        n = C.c_uint64(0)
+        rc = load().awv_variants_fold(self._h, buf.ctypes.data, len(rows), C.byref(n))
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_variants_fold")
+        return rows[:n.value].copy()
 
     def _stats(self, fn_name, cls):
         """One of the awv_engine_*_stats getters: the engine's `cls` record."""

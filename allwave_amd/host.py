@@ -160,10 +160,11 @@ def _check_split(split, split_min_score, clip):
 
 
 def _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split=None, split_min_score=None, normalize=None, device_cigar=False,
-                     cs=None, coverage=None):
+                     cs=None, coverage=None, variants=False):
     """The bounds, the clipping, the splitting, the normalization, the device-side CIGAR text and the cs tag of this thread's next
     alignment hook, which takes them: every argument is checked before anything is set, and all settings are always written
-    (awh_set_bounds, awh_set_clip, awh_set_split, awh_set_normalize, awh_set_device_cigar, awh_set_cs, awh_set_coverage)."""
+    (awh_set_bounds, awh_set_clip, awh_set_split, awh_set_normalize, awh_set_device_cigar, awh_set_cs, awh_set_coverage,
+    awh_set_variants)."""
     bonus, least = _check_clip(clip, clip_min_score)
     sbonus, sleast = _check_split(split, split_min_score, clip)
     mode = ffi.norm_mode(normalize)
@@ -182,6 +183,7 @@ def _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split=No
     load().awh_set_device_cigar(int(bool(device_cigar)))
     load().awh_set_cs(int(cs_mode))
     load().awh_set_coverage(int(roles))
+    load().awh_set_variants(int(bool(variants)))
 
 
 def last_coverage():
@@ -208,6 +210,26 @@ def last_coverage():
             L.awh_free(C.cast(p, C.c_void_p))
     return dict(offsets=offsets, aligned=aligned, matched=matched, items=int(st[0]), failed=int(st[1]), columns=int(st[2]),
                 boundaries=int(st[3]), reads=int(st[4]), kernel_ms=float(ms.value))
+
+
+def last_variants():
+    """last_variants() of this thread's last all_pairs_paf / all_pairs_paf_count / iterate / align_ranges call with variants=True:
+    dict(rows, stats) -- rows the per-site allele table (ffi.VARIANT_DTYPE, in key order), the slots' tables merged by key (sum of
+    count, min of rep), so several devices give the one-engine table exactly; stats an ffi.VariantsStats summed over the slots
+    (rows: of the merged table).  rows is empty for a call without variants."""
+    rows = C.c_void_p()
+    n = C.c_size_t(0)
+    st = ffi.VariantsStats()
+    L = load()
+    L.awh_last_variants.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    if L.awh_last_variants(C.byref(rows), C.byref(n), C.byref(st)) != 0:
+        raise HostError("out of memory")
+    try:
+        nbytes = n.value * ffi.VARIANT_DTYPE.itemsize
+        out = np.frombuffer(C.string_at(rows, nbytes), dtype=ffi.VARIANT_DTYPE).copy() if nbytes else np.zeros(0, dtype=ffi.VARIANT_DTYPE)
+    finally:
+        L.awh_free(rows)
+    return dict(rows=out, stats=st)
 
 
 def last_cs():
@@ -344,7 +366,7 @@ def check_paf(ids, seqs, paf_text, scores, optimal=False, device=0, partial=Fals
 
 
 def align_ranges(ids, seqs, ranges, scores, devices=None, device=0, verify=False, max_penalty=None, max_divergence=None, clip=None,
-                 clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None):
+                 clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False):
     """allwave::align_ranges + alignment_to_paf: the interval pairs `ranges` -- rows (query_idx, target_idx, is_reverse,
     query_start, query_end, target_start, target_end), the query interval on its forward strand -- aligned globally on the
     engines `devices` names (default: [device]).  Returns the PAF lines in list order: columns 3-4 and 8-9 are the interval,
@@ -360,7 +382,7 @@ def align_ranges(ids, seqs, ranges, scores, devices=None, device=0, verify=False
     n = C.c_size_t(0)
     e = _err()
     rbuf = r if len(r) else np.zeros((1, 7), dtype=np.int64)
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants)
     rc = load().awh_align_ranges_paf(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), scores.encode(),
                                      rbuf.ctypes.data_as(C.c_void_p), C.c_size_t(len(r)), devs, nd, int(bool(verify)), C.byref(out),
                                      C.byref(n), e, _CAP)
@@ -431,7 +453,7 @@ def _device_args(devices):
 
 def all_pairs_paf(ids, seqs, scores, orientation="wfa", exclude_self=True, device=0, sparsification="none", devices=None,
                   min_batch_pairs=0, orientation_full=False, verify=False, max_penalty=None, max_divergence=None, clip=None,
-                  clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None):
+                  clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False):
     """AllPairIterator + alignment_to_paf per record; returns the list of PAF lines.  `devices`: a list of ordinals (one
     engine per entry, repeats allowed) to spread the pair list over in this call; None = [device].
     `min_batch_pairs` > 0 overrides the smallest batch of a multi-device run (default 16,384).  orientation_full: WFA
@@ -460,14 +482,15 @@ def all_pairs_paf(ids, seqs, scores, orientation="wfa", exclude_self=True, devic
     up to the tag is the line without it; last_cs() tells what was written.  Not together with split.
     coverage ("target" / "query" / "both"): the run also accumulates, on the device, the per-base depth of what it aligned
     (with_coverage: per base of every sequence, in how many alignments it is aligned and in how many it matches); the lines are
-    those of the run without it, and last_coverage() returns the two tracks.  iterate and align_ranges take it too.  all_pairs_paf_count and
+    those of the run without it, and last_coverage() returns the two tracks.  variants=True: the run also tallies, on the device, the
+    per-site allele table of what it aligned (with_variants; last_variants() returns it).  iterate and align_ranges take it too.  all_pairs_paf_count and
     align_ranges take it too; iterate accepts and ignores it."""
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if devices is None else devices)
     out = C.c_void_p()
     n = C.c_size_t(0)
     e = _err()
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants)
     rc = load().awh_all_pairs_paf_devices(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
                                           scores.encode(), sparsification.encode(), _orient_code(orientation, orientation_full), int(exclude_self),
                                           devs, nd, C.c_int64(int(min_batch_pairs)), int(bool(verify)), None, C.byref(out), C.byref(n), e, _CAP)
@@ -484,7 +507,7 @@ ITER_MODES = {"for_each": 0, "next": 1, "par_for_each": 2, "par_collect": 3, "pr
 def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientation="forward", threads=4, chunk=0,
             resparsify=False, fail_at=-1, device=0, devices=None, min_batch_pairs=0, shard=None, with_stats=False,
             orientation_full=False, verify=False, max_penalty=None, max_divergence=None, clip=None, clip_min_score=None, split=None,
-            split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None):
+            split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False):
     """Every consumer of the pair list (iterator.rs:101-253, lib.rs:57-68) through one hook; returns the PAF lines in arrival
     order.  `fail_at` >= 0 makes the callback throw at that record: HostError carries its message.
     `devices`: a list of ordinals (one engine per entry, repeats allowed) to spread the pair list over; None = [device].
@@ -499,7 +522,7 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
     hands out alignment records with their op bytes."""
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if devices is None else devices)
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants)
     st = (ffi.Stats * nd)()
     rank, world = shard if shard is not None else (0, 1)
     out = C.c_void_p()
@@ -524,7 +547,7 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
 
 def all_pairs_paf_count(ids, seqs, scores, orientation="forward", device=0, format_threads=8, devices=None, min_batch_pairs=0,
                         sparsification=None, checksum=False, verify=False, max_penalty=None, max_divergence=None, clip=None,
-                        clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None):
+                        clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False):
     """End to end: upload -> align -> D2H -> format into a counting sink. Returns (bytes, lines, secs, ffi.Stats) for
     every pair on `device`.  `devices`: a list of ordinals (one engine per entry, repeats allowed); the Stats are then
     summed over the slots, and the result gains a fifth element, each slot's Stats (last_slot_stats()), and a sixth, the
@@ -536,7 +559,7 @@ def all_pairs_paf_count(ids, seqs, scores, orientation="forward", device=0, form
     one = devices is None
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if one else devices)
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants)
     nb, nl, secs, ck = C.c_uint64(0), C.c_uint64(0), C.c_double(0), C.c_uint64(0)
     st = ffi.Stats()
     slot = (ffi.Stats * nd)()

@@ -808,7 +808,8 @@ int awv_engine_coverage_stats(const awv_engine* e, awv_cov_stats* out);
 /* ---- the alleles of all alignments per target site (csrc/variants.hip, csrc/variants_device.hpp) --------------------------------
  * At this site of this sequence, which alleles do the other sequences carry, and how many carry each?  A keyed table: distinct
  * (site, allele) rows with a support count, deduplicated across records, batches and calls.  This section is the contract and
- * its host yardsticks; the hash, its combine and the key order are __host__ __device__ in variants_device.hpp.
+ * its host yardsticks; the device pass is declared behind them.  The hash, its combine and the key order are __host__ __device__
+ * in variants_device.hpp.
  * A pure function of the contributing items, exact and independent of their order.
  * An item is exactly the coverage pass's item: an op string c[0..n) over M X I D with its rectangle (pattern [pb, pe) against
  * text [tb, te)), the skips of a slice, and the pair's q_idx, t_idx and q_revcomp; the pattern is the reverse-complement copy for
@@ -859,6 +860,56 @@ int awv_variants_one_host(int32_t q_idx, int32_t t_idx, int32_t q_revcomp, const
                           const awv_cs_slice* slice /* nullable */, awv_variant* events, uint64_t cap, uint64_t* n_events,
                           awv_var_item* out /* required */);
 int awv_variants_fold_host(awv_variant* rows, uint64_t n, uint64_t* n_rows);
+
+/* The device pass (csrc/variants.hip: the events of every item, one wave per item; csrc/variants_fold.hip: the fold, a stable
+ * radix sort by key and one reduction of equal keys).  Events and rows are awv_variants_one_host's and awv_variants_fold_host's,
+ * byte for byte. */
+#define AWV_VTAB_EVENTS 0     /* `fold` of awv_variants_cigars: the items' unfolded events, in record order, then column order */
+#define AWV_VTAB_FOLDED 1     /* the folded table of the call */
+#define AWV_VTAB_ACCUMULATE 2 /* the events go to the engine's table (AWV_ERR_STATE before awv_engine_variants_begin); no row comes back */
+typedef struct {
+  double kernel_ms;  /* HIP-event time of the event kernels (measure, scan, emit) since awv_engine_variants_begin */
+  double fold_ms;    /* and of the folds */
+  uint64_t items;    /* items handed to the pass since then (skipped ones included) */
+  uint64_t failed;   /* of them: code other than AWV_VR_OK / AWV_VR_SKIPPED */
+  uint64_t columns;  /* op bytes of the strings and slices walked */
+  uint64_t snv, ins, del; /* events of each type */
+  uint64_t rows;     /* rows of the engine's table after its last fold */
+  uint64_t folds;    /* folds of the engine's table: those that made room, and one per read */
+  uint64_t capacity_rows; /* the size of the engine's row buffer; it only grows between two begins, so this is its peak */
+} awv_variants_stats; /* 88 bytes */
+/* Begins a table over the resident sequence set (AWV_ERR_STATE without one): a device buffer of reserve_rows rows (0: a default).
+ * From then on every aligning call of the engine -- awv_align_pairs and awv_align_ranges in all their forms -- appends each batch's
+ * events on the device, on the engine's stream, after the clip / split step; records, op bytes, texts and stats of those calls are
+ * unchanged.  When a batch's events would pass the buffer's end the table is folded in place, and doubled if it is then still
+ * more than half full; a failed allocation is AWV_ERR_OOM and leaves the table as it was.  clip_min_score: the threshold of
+ * clipping calls.  A begin ends the table before it, and so does awv_engine_set_sequences.  At most 2^31 - 1 items between two
+ * begins (AWV_ERR_ARG beyond, before anything is launched). */
+int awv_engine_variants_begin(awv_engine* e, int64_t clip_min_score, uint64_t reserve_rows);
+/* Ends the table and frees its buffer (nothing to end: AWV_OK); the stats stay readable until the next begin. */
+int awv_engine_variants_end(awv_engine* e);
+/* The table so far: folds, then copies.  *n_rows is the number of rows whatever cap is; they are written to rows only when
+ * *n_rows <= cap -- all of them or none -- so rows == NULL with cap == 0 is the measuring call.  Accumulation goes on after a
+ * read.  AWV_ERR_STATE before begin. */
+int awv_engine_variants_read(awv_engine* e, awv_variant* rows, uint64_t cap, uint64_t* n_rows /* required */);
+/* Since the last awv_engine_variants_begin of this engine (since its creation before one); awv_variants_cigars / _ranges add
+ * to items, failed, columns, the events and kernel_ms under every `fold`. */
+int awv_engine_variants_stats(const awv_engine* e, awv_variants_stats* out);
+/* The events of records and op bytes the caller supplies, on the device, against the resident sequence set: results[i] claims that
+ * cigar_arena[results[i].cigar_off, + cigar_len) aligns pairs[i] (ranges[i]).  Staged and pieced as awv_cs_cigars does; slices
+ * (nullable): n entries; items[0..n) is filled.  fold: AWV_VTAB_*.  *n_rows is the number of rows (under AWV_VTAB_ACCUMULATE: of
+ * events appended) whatever cap is; rows is written only when *n_rows <= cap, all or none.  AWV_ERR_ARG, before anything is
+ * launched, for what awv_cs_cigars refuses. */
+int awv_variants_cigars(awv_engine* e, const awv_pair* pairs, int64_t n, const awv_result* results, const uint8_t* cigar_arena,
+                        uint64_t arena_bytes, const awv_cs_slice* slices /* nullable */, int32_t fold,
+                        awv_var_item* items /* required */, awv_variant* rows, uint64_t cap, uint64_t* n_rows /* required */);
+int awv_variants_ranges(awv_engine* e, const awv_range_pair* ranges, int64_t n, const awv_result* results,
+                        const uint8_t* cigar_arena, uint64_t arena_bytes, const awv_cs_slice* slices /* nullable */, int32_t fold,
+                        awv_var_item* items /* required */, awv_variant* rows, uint64_t cap, uint64_t* n_rows /* required */);
+/* The device fold on the caller's rows: rows[0..n), n < 2^31, events or rows in any order and with any field values (the order is
+ * awv_variants_fold_host's: the four 32-bit fields as signed numbers, the hash as an unsigned 64-bit word), become
+ * awv_variants_fold_host's rows in place; *n_rows is their number.  Needs no sequence set. */
+int awv_variants_fold(awv_engine* e, awv_variant* rows, uint64_t n, uint64_t* n_rows /* required */);
 /* ---- device pair planning (csrc/planner.hip) -------------------------------------------------------------------------
  * Integer work over the engine's resident sequence set, on its device and stream; results equal the host planner's
  * (csrc/host/planner.cpp) bit for bit.  Every call but awv_keep_pairs needs a sequence set (else AWV_ERR_STATE); a new set
