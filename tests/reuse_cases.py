@@ -454,3 +454,260 @@ def bounds_for(want, every):
     """Per-pair bounds from the oracle's penalties: P // 2 for every `every`-th entry (abandoned mid-search whenever P > 0),
     -1 -- no bound -- for the others."""
     return np.asarray([pen // 2 if k % every == every - 1 else -1 for k, (pen, _) in enumerate(want)], dtype=np.int32)
+
+
+# ---- the five newer record passes: normalize.hip, encode.hip, cs.hip, coverage.hip, variants.hip ---------------------------------
+# They take records in the scan kernels' order and carry more from chunk to chunk: the run carry (the column the run in progress
+# began at, the op before the chunk), the characters, runs and events so far, the bases consumed, the hash of the 'D' run in
+# progress, lane-local counts and a lane-local "bad byte seen", the class of the column before the chunk, and normalize's link
+# state.  The lists above serve them as they are; the lists below add what they lack: adjacencies chosen for that state.
+
+DIGITS = (9, 10, 99, 100, 999, 1000)  # run lengths at which the text of a run gains a digit
+
+#: (kind of A, kind of B, B begins on a 16-byte boundary): the trap groups of pass-I / pass-D.  coverage.hip's carried class reaches
+#: a record's first column only in lane 0's byte 0 -- at any other offset the byte before column 0 is masked out.
+_PASS_GROUPS = [("gap_tail", "gap_head", False), ("many_runs", "one_run", False), ("pos_tail", "digits", True), ("plain", "x_first", False),
+                ("many_runs", "one_event", False), ("revcomp", "forward", False), ("badlast", "plain", False), ("overrun", "plain", False),
+                ("bad3", "plain", False), ("all_gaps", "plain", False)]
+
+
+def _pass_record(kind, rng, n, g, k):
+    """A record of the lists above, or one of the kinds only these lists have (k: which of the digit thresholds)."""
+    if kind == "many_runs":    # runs of 1 .. 3 columns of every op: a long text, many runs, many events
+        ops = bytearray()
+        while len(ops) < n:
+            ops += bytes([rng.choice(b"MXMIMD")]) * rng.randint(1, 3)
+        ops = bytes(ops[:n])
+    elif kind == "one_run":
+        ops = b"M" * n
+    elif kind == "one_event":  # its only event is its last column
+        ops = b"M" * (n - 1) + b"X"
+    elif kind == "x_first":    # its first column reads both sequences' first bases
+        ops = (b"X" + _plain(rng, n))[:n]
+    elif kind == "digits":     # its first run is an 'M' run of a digit threshold (the largest that fits, else all of it)
+        fit = [d for d in DIGITS if d < n]
+        d = DIGITS[k % len(DIGITS)] if DIGITS[k % len(DIGITS)] < n else fit[-1] if fit else n
+        ops = (b"M" * d + b"X" + _plain(rng, n))[:n]
+    else:
+        return _record(kind, rng, n, g)
+    p, t = V.build_from_ops(rng, ops)
+    return ScanRec(kind, ops, 0, p, t, 0)
+
+
+def _decreasing_list(rng, groups, make):
+    """Records from 5,000 columns down to 1, the groups in rotation, stored back to back: make(kind, n, instance) is a record of n
+    columns.  A group whose B begins on a 16-byte boundary shortens its A by up to 15 columns to get there."""
+    out = []
+    n, k, off = 5000, 0, 0
+    while n >= 1:
+        a, b, aligned = groups[k % len(groups)]
+        k += 1
+        if a in ("bad3", "overrun") and n < 12:
+            continue
+        if aligned:
+            if n <= 16:
+                continue
+            n -= (off + n) % 16
+        for kind in (a, b):
+            if n < 1:
+                break
+            out.append(make(kind, n, k // len(groups)))
+            assert len(out[-1].ops) == n, (kind, n)
+            off += n
+            n -= rng.randint(1, 55) if n > 100 else rng.randint(1, 3)
+    return out
+
+
+def _pass_list(seed, g):
+    rng = random.Random("reuse/pass/%s" % seed)
+    return _decreasing_list(rng, _PASS_GROUPS, lambda kind, n, k: _pass_record(kind, rng, n, g, k))
+
+
+# normalize.hip moves a gap run only through bases that repeat, which verify_cases.build_from_ops' random sequences almost never
+# offer: these records lie in a homopolymer.  Every 'M' is A over A and every run is free to go as far as its bound allows, unless
+# an 'X' (A over C) or a column of G stands in its way.
+
+def _hp_content(rng, n):
+    """n columns: 'M' runs of 5 .. 40 with gap runs of 1 .. 3 between them."""
+    ops = bytearray()
+    while len(ops) < n:
+        ops += b"M" * rng.randint(5, 40) + bytes([rng.choice(b"ID")]) * rng.randint(1, 3)
+    return bytes(ops[:n])
+
+
+def _hp_pair(ops, other=()):
+    """(pattern, text) of the homopolymer under `ops`; the columns in `other`, all 'M', hold G."""
+    p, t = bytearray(), bytearray()
+    for c, op in enumerate(ops):
+        b = ord("G") if c in other else ord("A")
+        if op != ord("I"):
+            p.append(b)
+        if op != ord("D"):
+            t.append(ord("C") if op == ord("X") else b)
+    return bytes(p), bytes(t)
+
+
+#: the trap groups of norm-left (and, mirrored, of norm-right)
+_NORM_GROUPS = [("n_tail_unmoved", "n_head_moves", False), ("n_tail_moved", "n_head_blocked", False), ("n_gap_tail", "n_gap_head_other", False),
+                ("n_moves_many", "n_blocked", False)]
+HEAD_M = (1, 2, 17, 70, 300, 1030)  # the 'M' columns before the first run of n_head_moves: inside a lane, over lanes, over a chunk
+
+
+def _norm_record(kind, rng, n, g, k):
+    """A homopolymer record of n columns; g: the gap op of its trap."""
+    o = b"D" if g == b"I" else b"I"
+    other = ()
+    if kind == "n_tail_unmoved":    # the last gap run stands behind an 'X' and does not move; 1 .. 3 'M' columns end the string
+        ops = (_hp_content(rng, n) + b"X" + g * rng.randint(1, 5) + b"M" * rng.randint(1, 3))[-n:]
+    elif kind == "n_head_moves":    # M^m g^L: the run goes to column 0
+        L = rng.randint(1, 4)
+        m = max(min(HEAD_M[k % len(HEAD_M)], n - L), 0)
+        ops = (b"M" * m + g * L + b"X" + _hp_content(rng, n))[:n]
+    elif kind == "n_tail_moved":    # the last gap run moves 40 columns or more; two 'M' columns end the string
+        ops = (_hp_content(rng, n) + b"M" * 40 + g * rng.randint(1, 5) + b"MM")[-n:]
+    elif kind == "n_head_blocked":  # M^m g^L with a G d columns before the run: it moves by d
+        m, L = rng.randint(4, 40), rng.randint(1, 4)
+        ops = (b"M" * m + g * L + b"X" + _hp_content(rng, n))[:n]
+        other = (m - 1 - rng.randint(0, 3),)
+        if other[0] >= n or ops[other[0]] != ord("M"):
+            other = ()
+    elif kind == "n_gap_tail":      # ends inside a gap run
+        ops = (_hp_content(rng, n) + g * (1100 if n >= 1300 else rng.randint(1, 30)))[-n:]
+    elif kind == "n_gap_head_other":  # begins with a run of the other gap op
+        ops = (o * rng.randint(1, 30) + b"M" + _hp_content(rng, n))[:n]
+    elif kind == "n_moves_many":
+        ops = _hp_content(rng, n)
+    elif kind == "n_blocked":       # every gap run stands behind an 'X': nothing moves
+        ops = bytearray()
+        while len(ops) < n:
+            ops += b"M" * rng.randint(5, 40) + b"X" + bytes([rng.choice(b"ID")]) * rng.randint(1, 3)
+        ops = bytes(ops[:n])
+    else:
+        raise ValueError(kind)
+    p, t = _hp_pair(ops, other)
+    return ScanRec(kind, ops, 0, p, t, 0)
+
+
+def _norm_list(seed):
+    rng = random.Random("reuse/norm/%s" % seed)
+    return _decreasing_list(rng, _NORM_GROUPS, lambda kind, n, k: _norm_record(kind, rng, n, b"ID"[k % 2:][:1], k))
+
+
+def mirrored(rec):
+    """The record as a right-normalizing wave walks it: the reversed op string over the reversed sequences."""
+    return rec._replace(ops=rec.ops[::-1], pattern=rec.pattern[::-1], text=rec.text[::-1])
+
+
+_PASS = {}
+
+
+def pass_lists():
+    """{name: [ScanRec]}, built once and never changed: the lists of the five newer passes.  norm-right is a list of its own,
+    mirrored: a right-normalizing wave walks a string from its end, so there A's "end" is its column 0."""
+    if not _PASS:
+        _PASS["pass-I"] = _pass_list("I", b"I")
+        _PASS["pass-D"] = _pass_list("D", b"D")
+        _PASS["norm-left"] = _norm_list("left")
+        _PASS["norm-right"] = [mirrored(r) for r in _norm_list("right")]
+    return _PASS
+
+
+def all_lists():
+    """The scan lists and the pass lists."""
+    out = dict(scan_lists())
+    out.update(pass_lists())
+    return out
+
+
+def offsets_of(recs):
+    """Where each record's op string begins in the back-to-back arena."""
+    return [int(v) for v in np.concatenate(([0], np.cumsum([len(r.ops) for r in recs])))[:-1]]
+
+
+# ---- what the five passes must give: the host yardsticks, record by record ---------------------------------------------------------
+
+def range_geometry(seqs, ranges):
+    """Per range (aligned copy of the whole query, (pb, pe, tb, te) in its coordinates): a q_revcomp range's interval, given on the
+    forward strand, seen from the reverse complement."""
+    out = []
+    for q, t, rc, qb, qe, tb, te in (tuple(int(v) for v in r) for r in ranges):
+        ql = len(seqs[q])
+        out.append((V.revcomp(seqs[q]), (ql - qe, ql - qb, tb, te)) if rc else (seqs[q], (qb, qe, tb, te)))
+    return out
+
+
+def encode_want(ffi, recs):
+    """(awv_cigar_text array, text bytes) of a list: offsets in record order."""
+    out = np.zeros(len(recs), dtype=ffi.CIGAR_TEXT_DTYPE)
+    text = bytearray()
+    for k, r in enumerate(recs):
+        out[k]["off"] = len(text)
+        if r.status == 0 and r.ops:
+            t, rec = ffi.encode_one_host(r.ops)
+            out[k]["len"], out[k]["runs"] = rec["len"], rec["runs"]
+            assert len(t) == int(rec["len"])
+            text += t
+    return out, bytes(text)
+
+
+def cs_want(ffi, mode, recs):
+    """(awv_cs_text array, text bytes) of a list."""
+    out = np.zeros(len(recs), dtype=ffi.CS_TEXT_DTYPE)
+    text = bytearray()
+    for k, r in enumerate(recs):
+        out[k]["off"] = len(text)
+        if r.status != 0:
+            out[k]["code"] = ffi.AWV_CST_SKIPPED
+            continue
+        t, rec = ffi.cs_one_host(mode, r.pattern, r.text, r.ops)
+        out[k]["len"], out[k]["code"] = rec["len"], rec["code"]
+        assert len(t) == int(rec["len"])
+        text += t
+    return out, bytes(text)
+
+
+def coverage_want(ffi, roles, recs, seqs, geometry=None):
+    """(awv_cov_item array, aligned, matched) of a list whose record k is the pair (2 k, 2 k + 1) of `seqs`: the tracks of all
+    sequences in set order.  geometry: range_geometry's, for a list of ranges."""
+    items = np.zeros(len(recs), dtype=ffi.COV_ITEM_DTYPE)
+    aligned, matched = [], []
+    for k, r in enumerate(recs):
+        ql, tl = len(seqs[2 * k]), len(seqs[2 * k + 1])
+        qt = (np.zeros(ql, dtype=np.uint32), np.zeros(ql, dtype=np.uint32))
+        tt = (np.zeros(tl, dtype=np.uint32), np.zeros(tl, dtype=np.uint32))
+        if r.status != 0:
+            items[k]["code"] = ffi.AWV_CV_SKIPPED
+        else:
+            items[k], _, _ = ffi.coverage_one_host(roles, r.rc, ql, tl, r.ops, span=None if geometry is None else geometry[k][1], q_tracks=qt, t_tracks=tt)
+        aligned += [qt[0], tt[0]]
+        matched += [qt[1], tt[1]]
+    return items, np.concatenate(aligned), np.concatenate(matched)
+
+
+def variants_want(ffi, recs, seqs, geometry=None):
+    """(awv_var_item array, [events of record k]) of a list whose record k is the pair (2 k, 2 k + 1) of `seqs`."""
+    items = np.zeros(len(recs), dtype=ffi.VAR_ITEM_DTYPE)
+    events = []
+    for k, r in enumerate(recs):
+        if r.status != 0:
+            items[k]["code"] = ffi.AWV_VR_SKIPPED
+            events.append(np.zeros(0, dtype=ffi.VARIANT_DTYPE))
+            continue
+        pattern, span = (r.pattern, None) if geometry is None else geometry[k]
+        items[k], ev = ffi.variants_one_host(2 * k, 2 * k + 1, r.rc, pattern, len(seqs[2 * k + 1]), r.ops, span=span)
+        events.append(ev)
+    return items, events
+
+
+def normalize_want(ffi, direction, recs, tail=b""):
+    """(the arena afterwards, awv_norm_result array) of a list stored back to back with `tail` behind the last string."""
+    out = np.zeros(len(recs), dtype=ffi.NORM_DTYPE)
+    arena = bytearray()
+    for k, r in enumerate(recs):
+        if r.status != 0:
+            out[k]["code"] = ffi.AWV_NM_SKIPPED
+            arena += r.ops
+        else:
+            ops, out[k] = ffi.normalize_one_host(direction, r.pattern, r.text, r.ops)
+            arena += ops
+    return bytes(arena + tail), out

@@ -218,7 +218,7 @@ def test_default_grid_takes_several_records_per_wave(hip_lib):
 
 def test_record_passes_share_their_checks(engines):
     """What every record pass checks before anything goes up, through each pass's own entry point: three
-    20-column records back to back, the arena handed over one byte short of the last one."""
+    20-column records back to back, the arena handed over one byte short of the last one.  The eight caller-supplied passes."""
     from allwave_amd import ffi
     e = engines("NO_ARENA_PROBE")
     seq = b"ACGTTGCAAC" * 2
@@ -228,11 +228,36 @@ def test_record_passes_share_their_checks(engines):
     recs["cigar_len"] = 20
     recs["cigar_off"] = [0, 20, 40]
     arena = b"M" * 59  # record 2 ends at byte 60
+    NO_RUN = -1
+
+    class ItemStats:
+        """The stats of coverage and variants, which count since their begin and call a record an item: `pairs` is `items`; not
+        among the fields that an empty call leaves zero: what begin itself sets."""
+        def __init__(self, st, set_by_begin=()):
+            self.st, self.pairs = st, st.items
+            self._fields_ = [f for f in st._fields_ if f[0] not in set_by_begin]
+
+        def __getattr__(self, f):
+            return getattr(self.st, f)
+
+    def coverage(r, n):  # (a begin of its own: the stats count from there)
+        e.coverage_begin("both")
+        return e.coverage_cigars(pairs[:n], r, arena)["code"]
+
+    def variants(r, n):
+        e.variants_begin()
+        return e.variants_cigars(pairs[:n], r, arena)[0]["code"]
+
     passes = {
         "verify_cigars": (lambda r, n=3: e.verify_cigars(DEFAULT_2P, pairs[:n], r, arena)["code"], e.verify_stats, ffi.AWV_VF_SKIPPED),
         "clip_cigars": (lambda r, n=3: e.clip_cigars(DEFAULT_2P, 1, r, arena)["code"], e.clip_stats, ffi.AWV_CL_SKIPPED),
         "split_cigars": (lambda r, n=3: e.split_cigars(DEFAULT_2P, 1, 1, r, arena)[0]["code"], e.split_stats, ffi.AWV_CL_SKIPPED),
         "normalize_cigars": (lambda r, n=3: e.normalize_cigars("left", pairs[:n], r, arena)[1]["code"], e.normalize_stats, ffi.AWV_NM_SKIPPED),
+        # (a text has no code: a record that was put off has no run, a completed one of 20 'M' columns has one)
+        "encode_cigars": (lambda r, n=3: np.where(e.encode_cigars(r, arena)[1]["runs"] == 0, NO_RUN, 0), e.encode_stats, NO_RUN),
+        "cs_cigars": (lambda r, n=3: e.cs_cigars("short", pairs[:n], r, arena)[1]["code"], e.cs_stats, ffi.AWV_CST_SKIPPED),
+        "coverage_cigars": (lambda r, n=3: coverage(r, n), lambda: ItemStats(e.coverage_stats()), ffi.AWV_CV_SKIPPED),
+        "variants_cigars": (lambda r, n=3: variants(r, n), lambda: ItemStats(e.variants_stats(), ("capacity_rows",)), ffi.AWV_VR_SKIPPED),
     }
     for name, (call, stats, skipped) in passes.items():
         with pytest.raises(ffi.EngineError) as err:
