@@ -21,6 +21,7 @@
 #include "cs_device.hpp"       // (the per-batch cs text of awv_align_pairs_cs, cs.hip)
 #include "coverage_device.hpp" // (the per-batch depth accumulation under awv_engine_coverage_begin, coverage.hip)
 #include "variants_device.hpp" // (the per-batch allele events under awv_engine_variants_begin, variants.hip)
+#include "lift_device.hpp"     // (the per-batch lifts under awv_engine_lift_begin, lift.hip)
 #include "kernels_awv.hpp"  // (the awv:: kernels themselves are instantiated in kernels_awv.hip -- here only the types)
 #define AWV_NS awv
 #define AWV_WG 64
@@ -198,6 +199,7 @@ struct awv_engine {
   awvcov::State* cov = nullptr;    // coverage.hip: the depth accumulators between awv_engine_coverage_begin and its end, and the launches' buffers
   bool cov_paused = false;         // (orient.hip: the strand alignments inside an orientation call do not count -- for the depth and for the allele table)
   awvvar::State* var = nullptr;    // variants.hip: the allele table between awv_engine_variants_begin and its end, and the launches' buffers
+  awvl::State* lift = nullptr;     // lift.hip: the regions and rows between awv_engine_lift_begin and its end, and the launches' buffers
   int32_t norm_mode = AWV_NORM_OFF;  // awv_engine_set_normalize: read at the start of every aligning call
 };
 
@@ -892,6 +894,12 @@ int run_record_steps(AlignCall& c) {
                                         rq.split ? rq.split->sout : nullptr, rq.spans ? rq.spans + first : nullptr)) return rc;
     c.lap("batch variants");
   }
+  if (awvl::active(e->lift) && !e->cov_paused && !rq.score_only && &s == &e->seqs) {
+    if (int rc = awvl::lift_batch(e, rq.pairs + first, n, hres.data(), e->d_cigar.p, arena, rq.cout ? rq.cout + first : nullptr,
+                                  rq.split ? rq.split->seg_first + first : nullptr, rq.split ? rq.split->iout + first : nullptr,
+                                  rq.split ? rq.split->sout : nullptr, rq.spans ? rq.spans + first : nullptr)) return rc;
+    c.lap("batch lifted");
+  }
   if (rq.tout) {
     if (int rc = awve::encode_batch(e, n, hres.data(), e->d_cigar.p, arena, rq.cout ? rq.cout + first : nullptr, rq.tout + first, &c.text_bytes)) return rc;
     c.lap("batch encoded");
@@ -1275,6 +1283,8 @@ void awv_engine_destroy(awv_engine* e) {
   e->cov = nullptr;
   awvvar::state_release(e->var);
   e->var = nullptr;
+  awvl::state_release(e->lift);
+  e->lift = nullptr;
   e->seqs.release();
   e->ring_mem.release();
   e->hist_mem.release();
@@ -1304,6 +1314,8 @@ int awv_engine_set_sequences(awv_engine* e, int32_t n, const uint8_t* concat_byt
   e->cov = nullptr;
   awvvar::state_release(e->var);  // (and so does the allele table)
   e->var = nullptr;
+  awvl::state_release(e->lift);   // (and the lift table)
+  e->lift = nullptr;
   AWV_GUARDED(return upload_seqset(e, e->seqs, n, concat_bytes, offsets);)
 }
 
@@ -1528,6 +1540,7 @@ awve::State*& awv_internal_encode(awv_engine* e) { return e->encode; }
 awvcs::State*& awv_internal_cs(awv_engine* e) { return e->cs; }
 awvcov::State*& awv_internal_coverage(awv_engine* e) { return e->cov; }
 awvvar::State*& awv_internal_variants(awv_engine* e) { return e->var; }
+awvl::State*& awv_internal_lift(awv_engine* e) { return e->lift; }
 bool& awv_internal_coverage_paused(awv_engine* e) { return e->cov_paused; }
 int32_t& awv_internal_normalize_mode(awv_engine* e) { return e->norm_mode; }
 uint64_t awv_internal_max_arena(const awv_engine* e) { return e->cfg.max_arena_bytes > 0 ? (uint64_t)e->cfg.max_arena_bytes : (uint64_t)8 << 30; }

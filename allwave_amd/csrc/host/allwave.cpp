@@ -366,6 +366,7 @@ void RunOptions::apply(AllPairIterator& it) const {
   if (cs != 0) it.with_cs(cs);
   if (coverage != 0) it.with_coverage(coverage);
   if (variants) it.with_variants(true);
+  if (liftover_from != 0) it.with_liftover(liftover, liftover_from);
   if (max_penalty) it.with_max_penalty(*max_penalty);
   if (max_divergence) it.with_max_divergence(*max_divergence);
   if (clip_match_bonus != 0) it.with_clip(clip_match_bonus, clip_min_score);
@@ -545,6 +546,8 @@ AllPairIterator AllPairIterator::with_sparsification(SparsificationStrategy stra
   it.cs_ = cs_;
   it.coverage_ = coverage_;
   it.variants_ = variants_;
+  it.lift_from_ = lift_from_;
+  it.lift_regions_ = lift_regions_;
   return it;
 }
 AllPairIterator& AllPairIterator::with_device_cigar(bool on) {
@@ -561,6 +564,15 @@ AllPairIterator& AllPairIterator::with_cs(int mode) {
 AllPairIterator& AllPairIterator::with_coverage(int roles) {
   if (roles < 0 || roles > AWV_COV_BOTH) throw std::invalid_argument("with_coverage: 0, AWV_COV_TARGET, AWV_COV_QUERY or AWV_COV_BOTH");
   coverage_ = roles;
+  return *this;
+}
+AllPairIterator& AllPairIterator::with_liftover(std::vector<awv_region> regions, int from) {
+  if (from < 0 || from > AWV_LIFT_FROM_BOTH) throw std::invalid_argument("with_liftover: 0, AWV_LIFT_FROM_TARGET, AWV_LIFT_FROM_QUERY or AWV_LIFT_FROM_BOTH");
+  for (const awv_region& g : regions)
+    if (g.seq < 0 || (size_t)g.seq >= sequences_.size() || g.beg < 0 || g.beg >= g.end || (size_t)g.end > sequences_[(size_t)g.seq].seq.size())
+      throw std::invalid_argument("with_liftover: a region names a sequence out of range, or an interval that is empty or outside its sequence");
+  lift_from_ = from;
+  lift_regions_ = from != 0 ? std::move(regions) : std::vector<awv_region>{};
   return *this;
 }
 AllPairIterator& AllPairIterator::with_normalize(int direction) {
@@ -793,6 +805,25 @@ void add(awv_variants_stats& acc, const awv_variants_stats& x) {  // (rows: set 
   acc.folds += x.folds;
   acc.capacity_rows += x.capacity_rows;
 }
+void add(awv_lift_stats& acc, const awv_lift_stats& x) {
+  acc.kernel_ms += x.kernel_ms;
+  acc.records += x.records;
+  acc.columns += x.columns;
+  acc.queries += x.queries;
+  acc.ok += x.ok;
+  acc.skipped += x.skipped;
+  acc.bad_op += x.bad_op;
+  acc.lengths += x.lengths;
+  acc.unaligned += x.unaligned;
+  acc.outside += x.outside;
+}
+// the table's order: all twelve fields of a row in their order, region first
+bool lift_row_less(const awv_lift_row& a, const awv_lift_row& b) {
+  static_assert(sizeof(awv_lift_row) == 12 * sizeof(int32_t), "awv_lift_row is twelve 32-bit fields");
+  const int32_t* const u = &a.region;
+  const int32_t* const w = &b.region;
+  return std::lexicographical_compare(u, u + 12, w, w + 12);
+}
 void add(RunReport& acc, const RunReport& x) {
   acc.verify_failures.insert(acc.verify_failures.end(), x.verify_failures.begin(), x.verify_failures.end());
   add(acc.verify_stats, x.verify_stats);
@@ -804,6 +835,7 @@ void add(RunReport& acc, const RunReport& x) {
   add(acc.cs_stats, x.cs_stats);
   add(acc.coverage_stats, x.coverage_stats);
   add(acc.variants_stats, x.variants_stats);
+  add(acc.lift_stats, x.lift_stats);
 }
 
 // One batch's engine call, by name.  ranges (nullable): the batch is these n interval pairs, `pairs` is not read.  Alignment
@@ -878,6 +910,7 @@ struct AllPairIterator::SlotTotals {
   RunReport report;
   std::vector<uint32_t> cov_aligned, cov_matched;  // a coverage run: the slot's tracks, read when its batches are done
   std::vector<awv_variant> var_rows;                // a variants run: the slot's folded table, likewise
+  std::vector<awv_lift_row> lift_rows;              // a liftover run: the slot's rows, likewise
 };
 
 // What the slots of one run share.  The settings hold for alignment calls only: a score-only run has none of them.
@@ -892,6 +925,7 @@ struct AllPairIterator::RunState {
   int cs = 0;  // the cs mode of the run's alignment calls (0: none)
   int coverage = 0;  // the roles of a run that accumulates the per-base depth (0: none)
   bool variants = false;  // a run that tallies the allele table
+  int liftover = 0;  // the side mask of a run that lifts regions (0: none)
   uint64_t n_bases = 0;  // the sum of the sequences' lengths
   int normalizing = AWV_NORM_OFF;
   std::optional<double> div;  // the divergence bound of a bounded run
@@ -1141,6 +1175,7 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   rs.normalizing = call.score_only ? AWV_NORM_OFF : normalize_;
   rs.coverage = call.score_only ? 0 : coverage_;
   rs.variants = variants_ && !call.score_only;
+  rs.liftover = call.score_only ? 0 : lift_from_;
   for (const Sequence& q : sequences_) rs.n_bases += q.seq.size();
   rs.div = divergence_bound();
   rs.pen = to_penalties(params_);
@@ -1161,6 +1196,8 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
       // (a new set ended whatever coverage the engine had: the slot's depth starts from zero with every run)
       if (rs.coverage != 0 && awv_engine_coverage_begin(e, rs.coverage, clip_min_score_) != AWV_OK) throw AlignmentError(std::string("coverage: ") + awv_last_error());
       if (rs.variants && awv_engine_variants_begin(e, clip_min_score_, 0) != AWV_OK) throw AlignmentError(std::string("variants: ") + awv_last_error());
+      if (rs.liftover != 0 && awv_engine_lift_begin(e, lift_regions_.data(), (int64_t)lift_regions_.size(), rs.liftover, clip_min_score_) != AWV_OK)
+        throw AlignmentError(std::string("liftover: ") + awv_last_error());
     } catch (...) {
       rs.fail(std::current_exception());
     }
@@ -1205,9 +1242,20 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
         awv_engine_variants_stats(e, &vx);
         add(t.report.variants_stats, vx);
       }
+      if (rs.liftover != 0 && !rs.stop.load()) {  // the slot's rows, and what they cost
+        SlotTotals& t = rs.totals[s];
+        uint64_t n_rows = 0;
+        if (awv_engine_lift_read(e, nullptr, 0, &n_rows) != AWV_OK) throw AlignmentError(std::string("liftover: ") + awv_last_error());
+        t.lift_rows.resize((size_t)n_rows);
+        if (n_rows && awv_engine_lift_read(e, t.lift_rows.data(), n_rows, &n_rows) != AWV_OK) throw AlignmentError(std::string("liftover: ") + awv_last_error());
+        awv_lift_stats lx{};
+        awv_engine_lift_stats(e, &lx);
+        add(t.report.lift_stats, lx);
+      }
     } catch (...) {
       rs.fail(std::current_exception());
     }
+    if (e && rs.liftover != 0) awv_engine_lift_begin(e, nullptr, 0, 0, 0);  // the table goes with the run
     if (e && rs.coverage != 0) awv_engine_coverage_begin(e, 0, 0);  // the accumulators go with the run
     if (e && rs.variants) awv_engine_variants_end(e);               // and so does the table
   };
@@ -1228,6 +1276,7 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   if (first == 0) report_ = RunReport{};  // a run from the list's start begins anew; a later range (next()'s chunks) adds to it
   if (first == 0 && !call.score_only) cov_ = Coverage{};
   if (first == 0 && !call.score_only) var_.clear();
+  if (first == 0 && !call.score_only) lift_.clear();
   if (rs.coverage != 0 && cov_.offsets.empty()) {
     cov_.offsets.assign(sequences_.size() + 1, 0);
     for (size_t i = 0; i < sequences_.size(); ++i) cov_.offsets[i + 1] = cov_.offsets[i] + sequences_[i].seq.size();
@@ -1249,6 +1298,10 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
     if (awv_variants_fold_host(var_.data(), var_.size(), &left) != AWV_OK) throw AlignmentError(std::string("variants: ") + awv_last_error());
     var_.resize((size_t)left);
     report_.variants_stats.rows = left;
+  }
+  if (rs.liftover != 0) {  // the slots' rows (and, for next()'s chunks, the rows so far) merge by concatenating and sorting
+    for (const SlotTotals& t : rs.totals) lift_.insert(lift_.end(), t.lift_rows.begin(), t.lift_rows.end());
+    std::sort(lift_.begin(), lift_.end(), lift_row_less);
   }
   sort_verify_failures(report_.verify_failures);
   if (rs.err) std::rethrow_exception(rs.err);

@@ -147,7 +147,7 @@ class AllPairIterator;
 
 // The options of one run that filter or rewrite what it delivers, in one place: AllPairIterator::with_max_penalty,
 // with_max_divergence (std::nullopt: no bound), with_clip and with_split (match bonus 0: off), with_normalize (AWV_NORM_OFF: off),
-// with_device_cigar, with_cs (0: off), with_coverage (0: off), with_variants.
+// with_device_cigar, with_cs (0: off), with_coverage (0: off), with_variants, with_liftover (liftover_from 0: off).
 struct RunOptions {
   std::optional<int> max_penalty;
   std::optional<double> max_divergence;
@@ -160,8 +160,10 @@ struct RunOptions {
   int cs = 0;
   int coverage = 0;
   bool variants = false;
+  std::vector<awv_region> liftover;  // with liftover_from: the regions lifted through the run's alignments
+  int liftover_from = 0;             // AWV_LIFT_FROM_TARGET, AWV_LIFT_FROM_QUERY or AWV_LIFT_FROM_BOTH; 0: off
   void apply(AllPairIterator& it) const;  // the with_* calls of what is set; they throw std::invalid_argument as documented there
-  bool any() const { return max_penalty || max_divergence || clip_match_bonus != 0 || split_match_bonus != 0 || normalize != AWV_NORM_OFF || device_cigar || cs != 0 || coverage != 0 || variants; }
+  bool any() const { return max_penalty || max_divergence || clip_match_bonus != 0 || split_match_bonus != 0 || normalize != AWV_NORM_OFF || device_cigar || cs != 0 || coverage != 0 || variants || liftover_from != 0; }
 };
 
 // What a run leaves behind besides its results (AllPairIterator::last_report): the failed checks sorted by pair-list index,
@@ -177,6 +179,7 @@ struct RunReport {
   awv_cs_stats cs_stats{};
   awv_cov_stats coverage_stats{};
   awv_variants_stats variants_stats{};  // rows: of the merged table; folds: the engines' folds
+  awv_lift_stats lift_stats{};
 };
 
 // The per-base depth a run with with_coverage leaves behind (AllPairIterator::last_coverage): sequence s owns entries
@@ -311,6 +314,17 @@ class AllPairIterator {  // iterator.rs:12-171
   }
   bool variants() const { return variants_; }
   const std::vector<awv_variant>& last_variants() const { return var_; }
+  // Every alignment consumer also lifts `regions` (forward strand, any order; they may overlap, nest and repeat) through what the
+  // engine aligned (awv_engine_lift_begin; include/allwave_hip.h has the contract): regions on an alignment's target under
+  // AWV_LIFT_FROM_TARGET, on its query under AWV_LIFT_FROM_QUERY, both under AWV_LIFT_FROM_BOTH; from 0: off.  Every slot's
+  // engine keeps a table of its own; the slots' rows are concatenated and sorted on the host, so several devices, or one ordinal
+  // given twice, give the one-engine table exactly.  What an alignment contributes is the coverage rule.  last_liftover(): the
+  // table of the last run, in the rows' order (next(): since the list's start); empty without the setting.
+  // std::invalid_argument for a mask other than these and for a region outside its sequence.
+  AllPairIterator& with_liftover(std::vector<awv_region> regions, int from);
+  int liftover_from() const { return lift_from_; }
+  const std::vector<awv_region>& liftover_regions() const { return lift_regions_; }
+  const std::vector<awv_lift_row>& last_liftover() const { return lift_; }
   AllPairIterator& with_max_penalty(int max_penalty);
   AllPairIterator& with_max_divergence(double max_divergence);
   // of the last run (next(): of the chunks since the list's start), summed over the slots
@@ -426,6 +440,9 @@ class AllPairIterator {  // iterator.rs:12-171
   Coverage cov_;                  // of the last run (next(): since the list's start)
   bool variants_ = false;         // with_variants
   std::vector<awv_variant> var_;  // the allele table of the last run (next(): since the list's start)
+  int lift_from_ = 0;                     // with_liftover (0: off)
+  std::vector<awv_region> lift_regions_;  // its regions
+  std::vector<awv_lift_row> lift_;        // the lifted rows of the last run (next(): since the list's start)
   int split_bonus_ = 0;  // with_split (0: off)
   int64_t split_min_score_ = 1;
   bool drops_pairs() const { return bounded() || clip() || split(); }  // consumers that keep a slot per pair compact what was delivered
@@ -464,6 +481,7 @@ class AllPairParallelIterator {
   awv_cs_stats last_cs_stats() const { return it_.last_cs_stats(); }
   const Coverage& last_coverage() const { return it_.last_coverage(); }
   const std::vector<awv_variant>& last_variants() const { return it_.last_variants(); }
+  const std::vector<awv_lift_row>& last_liftover() const { return it_.last_liftover(); }
   const RunReport& last_report() const { return it_.last_report(); }
  private:
   friend class AllPairIterator;

@@ -22,14 +22,16 @@ void set_err(char* err, size_t cap, const std::string& m) {
 thread_local RunReport g_report;
 thread_local Coverage g_coverage;  // and its last_coverage(), for awh_last_coverage
 thread_local std::vector<awv_variant> g_variants;  // and its last_variants(), for awh_last_variants
+thread_local std::vector<awv_lift_row> g_liftover;  // and its last_liftover(), for awh_last_liftover
 template <typename It>
 void keep(const It& it) {
   g_report = it.last_report();
   g_coverage = it.last_coverage();
   g_variants = it.last_variants();
+  g_liftover = it.last_liftover();
 }
 // The options of the calling thread's NEXT alignment hook: awh_set_bounds, awh_set_clip, awh_set_split, awh_set_normalize and
-// awh_set_device_cigar, awh_set_cs, awh_set_coverage
+// awh_set_device_cigar, awh_set_cs, awh_set_coverage, awh_set_variants, awh_set_liftover
 // leave them here; the hook takes them (they hold for that one call) and starts the counters they go with afresh.
 thread_local RunOptions g_next;
 RunOptions take_run_options() {
@@ -45,6 +47,8 @@ RunOptions take_run_options() {
   g_coverage = Coverage{};
   g_report.variants_stats = awv_variants_stats{};
   g_variants.clear();
+  g_report.lift_stats = awv_lift_stats{};
+  g_liftover.clear();
   return o;
 }
 // the hooks' orientation code on an iterator: 0 forward, 1 WFA, 2 mash, 3 WFA by two full alignments per pair
@@ -741,6 +745,26 @@ int awh_last_variants(awv_variant** rows, size_t* n_rows, awv_variants_stats* st
     return -1;
   }
   if (*n_rows) memcpy(*rows, g_variants.data(), *n_rows * sizeof(awv_variant));
+  return 0;
+}
+// ---- regions lifted through the alignments ----
+// The calling thread's NEXT alignment hook runs with_liftover(regions[0 .. n), from) (AWV_LIFT_FROM_*; 0: off); the hooks after it
+// run without again.
+void awh_set_liftover(const awv_region* regions, size_t n, int from) {
+  g_next.liftover.assign(regions, regions + (regions ? n : 0));
+  g_next.liftover_from = from;
+}
+// last_liftover() of the calling thread's last alignment hook: *rows is a malloc'd copy of the *n_rows rows (awh_free), stats the
+// run's awv_lift_stats summed over the slots.  Returns -1 when memory runs out.
+int awh_last_liftover(awv_lift_row** rows, size_t* n_rows, awv_lift_stats* stats) {
+  *stats = g_report.lift_stats;
+  *n_rows = g_liftover.size();
+  *rows = (awv_lift_row*)malloc(std::max<size_t>(*n_rows, 1) * sizeof(awv_lift_row));
+  if (!*rows) {
+    *n_rows = 0;
+    return -1;
+  }
+  if (*n_rows) memcpy(*rows, g_liftover.data(), *n_rows * sizeof(awv_lift_row));
   return 0;
 }
 // last_encode_stats() of the calling thread's last alignment hook: {pairs, runs, text_bytes, columns} and the summed kernel time

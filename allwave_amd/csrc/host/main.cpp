@@ -22,6 +22,7 @@
 #include <stdexcept>
 
 #include "allwave.hpp"
+#include "bed.hpp"
 #include "planner.hpp"
 
 using namespace allwave;
@@ -66,6 +67,10 @@ struct Args {
   bool have_variants = false;
   long variants_min_count = 1;  // --variants-min-count N: rows with a smaller count are not written
   bool have_variants_min_count = false;
+  std::string liftover;       // --liftover BED: the regions lifted through what was aligned, on the device
+  std::string liftover_out;   // --liftover-out FILE: one line per lifted region and alignment
+  bool have_liftover = false, have_liftover_out = false, have_liftover_from = false;
+  int liftover_from = AWV_LIFT_FROM_TARGET;  // --liftover-from target|query|both
 };
 
 [[noreturn]] void die(const std::string& m, int code = 2) {
@@ -276,6 +281,22 @@ int main(int argc, char** argv) {
         die("--variants-min-count expects a count N >= 1");
       a.have_variants_min_count = true;
     }
+    else if (k == "--liftover") {
+      a.liftover = val();
+      if (a.liftover.empty()) die("--liftover expects a BED file name");
+      a.have_liftover = true;
+    }
+    else if (k == "--liftover-out") {
+      a.liftover_out = val();
+      if (a.liftover_out.empty()) die("--liftover-out expects a file name");
+      a.have_liftover_out = true;
+    }
+    else if (k == "--liftover-from") {
+      const std::string v = val();
+      if (v != "target" && v != "query" && v != "both") die("--liftover-from expects target, query or both");
+      a.liftover_from = v == "target" ? AWV_LIFT_FROM_TARGET : v == "query" ? AWV_LIFT_FROM_QUERY : AWV_LIFT_FROM_BOTH;
+      a.have_liftover_from = true;
+    }
     else if (k == "--coverage") {
       a.coverage = val();
       if (a.coverage.empty()) die("--coverage expects a file name");
@@ -323,11 +344,13 @@ int main(int argc, char** argv) {
                    "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
                    "                   [--split A --split-min-score S] [--normalize left|right] [--device-cigar] [--cs short|long]\n"
                    "                   [--coverage FILE [--coverage-of target|query|both]] [--variants FILE [--variants-min-count N]]\n"
+                   "                   [--liftover BED --liftover-out FILE [--liftover-from target|query|both]]\n"
                    "       allwave_hip -i in.fa --check-paf FILE [-s scores | -x ANI] [--check-optimal] [--partial] [--device N]\n"
                    "       allwave_hip -i in.fa --align-paf FILE [-s scores | -x ANI] [-o out.paf] [--verify] [--score-only] [--device N | --devices LIST]\n"
                    "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
                    "                   [--split A --split-min-score S] [--normalize left|right] [--device-cigar] [--cs short|long]\n"
                    "                   [--coverage FILE [--coverage-of target|query|both]] [--variants FILE [--variants-min-count N]]\n"
+                   "                   [--liftover BED --liftover-out FILE [--liftover-from target|query|both]]\n"
                    "  --verify         check every alignment on the device before it is written (columns, counts, penalty); the summary\n"
                    "                   line gains `verified N pairs, F failed, K ms`, failures go to stderr, exit status 4 if any\n"
                    "  --check-paf FILE align nothing: check every line of FILE (12 columns + cg:Z:) against in.fa on the device; one line\n"
@@ -385,6 +408,15 @@ int main(int argc, char** argv) {
                    "                   also with --align-paf; not with --score-only, --check-paf or --mash-matrix; under --shard every\n"
                    "                   process writes its own shard's table; the summary line gains `variants I items, E events, R rows, K ms`\n"
                    "  --variants-min-count N  write only rows that N or more alignments carry (default 1)\n"
+                   "  --liftover BED   lift the regions of BED (name<TAB>beg<TAB>end[<TAB>label], names as in in.fa; a bad line is reported on\n"
+                   "                   stderr as `line class` and gives no region) through the run's alignments on the device, to every sequence\n"
+                   "                   their sequence was aligned with: the aligned core of a region, from its first aligned base to its last;\n"
+                   "                   --liftover-out FILE gets one line src_name<TAB>src_beg<TAB>src_end<TAB>label<TAB>dst_name<TAB>dst_beg<TAB>\n"
+                   "                   dst_end<TAB>strand<TAB>matches<TAB>mismatches<TAB>ins<TAB>del per region and alignment that has one, sorted\n"
+                   "                   by region, then pair; what counts is what is written, as for --coverage; the PAF is byte-identical; also\n"
+                   "                   with --align-paf; not with --score-only, --check-paf or --mash-matrix; under --shard every process writes\n"
+                   "                   its own shard's file; the summary line gains `lifted Q queries, R rows, U unaligned, K ms`\n"
+                   "  --liftover-from target|query|both  the side of an alignment a region is looked for on (default target)\n"
                    "  --plan-device N  plan on device N: --mash-matrix, the -p pair list and mash orientation (the same output as\n"
                    "                   the host planner; with --shard every rank plans the whole list on its own plan device)\n";
       return 0;
@@ -426,6 +458,11 @@ int main(int argc, char** argv) {
   if (a.have_variants && a.score_only) die("the argument '--variants' cannot be used with '--score-only'");
   if (a.have_variants && a.have_check_paf) die("the argument '--variants' cannot be used with '--check-paf'");
   if (a.have_variants && a.mash_matrix) die("the argument '--variants' cannot be used with '--mash-matrix'");
+  if (a.have_liftover != a.have_liftover_out) die("the arguments '--liftover' and '--liftover-out' require each other");
+  if (a.have_liftover_from && !a.have_liftover) die("the argument '--liftover-from' requires '--liftover'");
+  if (a.have_liftover && a.score_only) die("the argument '--liftover' cannot be used with '--score-only'");
+  if (a.have_liftover && a.have_check_paf) die("the argument '--liftover' cannot be used with '--check-paf'");
+  if (a.have_liftover && a.mash_matrix) die("the argument '--liftover' cannot be used with '--mash-matrix'");
   if (a.have_coverage && a.score_only) die("the argument '--coverage' cannot be used with '--score-only'");
   if (a.have_coverage && a.have_check_paf) die("the argument '--coverage' cannot be used with '--check-paf'");
   if (a.have_coverage && a.mash_matrix) die("the argument '--coverage' cannot be used with '--mash-matrix'");
@@ -549,6 +586,22 @@ int main(int argc, char** argv) {
     it.with_cs(a.cs);
     if (a.have_coverage) it.with_coverage(a.coverage_of);
     it.with_variants(a.have_variants);
+    BedRegions bed;
+    if (a.have_liftover) {  // (bad lines reported here and left out)
+      std::ifstream fin(a.liftover, std::ios::binary);
+      if (!fin) die("cannot open " + a.liftover, 1);
+      std::stringstream ss;
+      ss << fin.rdbuf();
+      std::vector<std::string> names;
+      std::vector<size_t> lens;
+      for (const Sequence& q : sequences) {
+        names.push_back(q.id);
+        lens.push_back(q.seq.size());
+      }
+      bed = parse_bed_regions(names, lens, ss.str());
+      for (const BedLine& l : bed.bad) std::cerr << l.line << ' ' << l.cls << "\n";
+      it.with_liftover(bed.regions, a.liftover_from);
+    }
     if (a.forward_only) it.with_orientation(Orientation::ForwardOnly);
     it.with_full_wfa_orientation(a.wfa_orientation_full);
     it.with_devices(devices);
@@ -667,6 +720,27 @@ int main(int argc, char** argv) {
       vout.close();
       if (vout.fail()) die("write error on the variants output", 1);
     }
+    if (a.have_liftover) {  // one line per row of the table, in its order
+      std::ofstream lout(a.liftover_out, std::ios::binary);
+      if (!lout) die("cannot create " + a.liftover_out, 1);
+      std::string buf;
+      const std::vector<awv_lift_row>& rows = it.last_liftover();
+      for (size_t k = 0; k < rows.size(); ++k) {
+        const awv_lift_row& r = rows[k];
+        const bool from_q = (r.flags & AWV_LIFT_ROW_FROM_QUERY) != 0;
+        const Sequence& src = sequences[(size_t)(from_q ? r.q_idx : r.t_idx)];
+        const Sequence& dst = sequences[(size_t)(from_q ? r.t_idx : r.q_idx)];
+        buf += src.id + '\t' + std::to_string(r.src_beg) + '\t' + std::to_string(r.src_end) + '\t' + bed.labels[(size_t)r.region] + '\t' + dst.id + '\t' +
+               std::to_string(r.dst_beg) + '\t' + std::to_string(r.dst_end) + '\t' + ((r.flags & AWV_LIFT_ROW_REVCOMP) ? '-' : '+') + '\t' +
+               std::to_string(r.num_matches) + '\t' + std::to_string(r.num_mismatches) + '\t' + std::to_string(r.num_ins) + '\t' + std::to_string(r.num_del) + '\n';
+        if (buf.size() >= (1u << 20) || k + 1 == rows.size()) {
+          lout.write(buf.data(), (std::streamsize)buf.size());
+          buf.clear();
+        }
+      }
+      lout.close();
+      if (lout.fail()) die("write error on the liftover output", 1);
+    }
     const BoundStats bs = it.last_bound_stats();
     const size_t above = (size_t)(bs.above_penalty + bs.above_divergence);  // (pairs above a bound get no line)
     const ClipStats cs = it.last_clip_stats();
@@ -675,7 +749,7 @@ int main(int argc, char** argv) {
     if (done + above + unclipped + (size_t)ss.pairs != total + (size_t)ss.segments) die("internal: wrote " + std::to_string(done) + " of " + std::to_string(total) + (a.score_only ? " pairs" : " PAF lines"), 1);
     if (!a.no_progress) {
       const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      char buf[640];
+      char buf[768];
       int w = snprintf(buf, sizeof(buf), "[%.1fs] %zu/%zu (100.0%%) %.1f alignments/sec", secs, done, total, done / std::max(secs, 1e-9));
       if (a.have_align_paf && w > 0 && (size_t)w < sizeof(buf)) w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", %zu bad lines", bad_lines);
       if (bounded && w > 0 && (size_t)w < sizeof(buf)) w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", %zu pairs above the bound", above);
@@ -709,6 +783,11 @@ int main(int argc, char** argv) {
         const awv_variants_stats vs = it.last_report().variants_stats;
         w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", variants %llu items, %llu events, %llu rows, %.2f ms", (unsigned long long)vs.items,
                       (unsigned long long)(vs.snv + vs.ins + vs.del), (unsigned long long)vs.rows, vs.kernel_ms + vs.fold_ms);
+      }
+      if (a.have_liftover && w > 0 && (size_t)w < sizeof(buf)) {
+        const awv_lift_stats ls = it.last_report().lift_stats;
+        w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", lifted %llu queries, %zu rows, %llu unaligned, %.2f ms", (unsigned long long)ls.queries,
+                      it.last_liftover().size(), (unsigned long long)ls.unaligned, ls.kernel_ms);
       }
       if (a.verify && w > 0 && (size_t)w < sizeof(buf)) {
         const awv_verify_stats vs = it.last_verify_stats();

@@ -97,6 +97,18 @@ AWV_VR_LENGTHS = 3
 AWV_VTAB_EVENTS = 0
 AWV_VTAB_FOLDED = 1
 AWV_VTAB_ACCUMULATE = 2
+#: liftover: the side a region lies on (a mask of both for lift_begin), awv_lift_result.code and awv_lift_row.flags
+AWV_LIFT_FROM_TARGET = 1
+AWV_LIFT_FROM_QUERY = 2
+AWV_LIFT_FROM_BOTH = 3
+AWV_LF_OK = 0
+AWV_LF_SKIPPED = 1
+AWV_LF_BAD_OP = 2
+AWV_LF_LENGTHS = 3
+AWV_LF_UNALIGNED = 4
+AWV_LF_OUTSIDE = 5
+AWV_LIFT_ROW_REVCOMP = 1
+AWV_LIFT_ROW_FROM_QUERY = 2
 #: sketch kinds of device pair planning (awv_sketch)
 AWV_SK_CANONICAL = 0
 AWV_SK_FORWARD = 1
@@ -121,7 +133,8 @@ EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine
            "awv_coverage_one_host", "awv_engine_coverage_begin", "awv_engine_coverage_read", "awv_coverage_cigars", "awv_coverage_ranges",
            "awv_engine_coverage_stats",
            "awv_variants_one_host", "awv_variants_fold_host", "awv_engine_variants_begin", "awv_engine_variants_end", "awv_engine_variants_read", "awv_engine_variants_stats",
-           "awv_variants_cigars", "awv_variants_ranges", "awv_variants_fold")
+           "awv_variants_cigars", "awv_variants_ranges", "awv_variants_fold",
+           "awv_lift_one_host", "awv_lift_cigars", "awv_lift_ranges", "awv_engine_lift_begin", "awv_engine_lift_read", "awv_engine_lift_stats")
 
 
 class EngineConfig(C.Structure):
@@ -193,6 +206,11 @@ class CovStats(C.Structure):
                 ("reads", C.c_uint64)]
 
 
+class LiftStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("records", C.c_uint64), ("columns", C.c_uint64), ("queries", C.c_uint64), ("ok", C.c_uint64),
+                ("skipped", C.c_uint64), ("bad_op", C.c_uint64), ("lengths", C.c_uint64), ("unaligned", C.c_uint64), ("outside", C.c_uint64)]
+
+
 PAIR_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4")])
 #: awv_range_pair: the query interval on the query's forward strand (PAF convention), also with q_revcomp
 RANGE_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4"), ("q_beg", "<i4"), ("q_end", "<i4"),
@@ -223,6 +241,18 @@ VARIANT_DTYPE = np.dtype([("t_idx", "<i4"), ("pos", "<i4"), ("type", "<i4"), ("l
                           ("reserved", "<u4")])
 #: awv_var_item: the code and the events of one item
 VAR_ITEM_DTYPE = np.dtype([("code", "<i4"), ("snv", "<u4"), ("ins", "<u4"), ("del", "<u4")])
+#: awv_lift_query: [beg, end) on the forward strand of record `record`'s target (from 1) or query (from 2)
+LIFT_QUERY_DTYPE = np.dtype([("record", "<i8"), ("from", "<i4"), ("beg", "<i4"), ("end", "<i4"), ("reserved", "<i4")])
+#: awv_lift_result: the code, the aligned core as a slice of the record's op string, the two intervals and the slice's op counts
+LIFT_DTYPE = np.dtype([("code", "<i4"), ("reserved", "<i4"), ("col_beg", "<u4"), ("col_end", "<u4"), ("q_skip", "<i4"), ("t_skip", "<i4"),
+                       ("src_beg", "<i4"), ("src_end", "<i4"), ("dst_beg", "<i4"), ("dst_end", "<i4"), ("num_matches", "<i4"),
+                       ("num_mismatches", "<i4"), ("num_ins", "<i4"), ("num_del", "<i4")])
+#: awv_region: [beg, end) of resident sequence seq, forward strand
+REGION_DTYPE = np.dtype([("seq", "<i4"), ("beg", "<i4"), ("end", "<i4")])
+#: awv_lift_row: one region lifted through one alignment; the table is sorted by all fields in this order
+LIFT_ROW_DTYPE = np.dtype([("region", "<i4"), ("q_idx", "<i4"), ("t_idx", "<i4"), ("flags", "<i4"), ("src_beg", "<i4"), ("src_end", "<i4"),
+                           ("dst_beg", "<i4"), ("dst_end", "<i4"), ("num_matches", "<i4"), ("num_mismatches", "<i4"), ("num_ins", "<i4"),
+                           ("num_del", "<i4")])
 #: awv_score_result
 SCORE_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4")])
 
@@ -336,8 +366,38 @@ def load():
                                           C.c_uint64, C.POINTER(C.c_uint64)]
         L.awv_variants_ranges.argtypes = L.awv_variants_cigars.argtypes
         L.awv_variants_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.awv_lift_one_host.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int64,
+                                        C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        L.awv_lift_cigars.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.awv_lift_ranges.argtypes = L.awv_lift_cigars.argtypes
+        L.awv_engine_lift_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64]
+        L.awv_engine_lift_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.awv_engine_lift_stats.argtypes = [C.c_void_p, C.POINTER(LiftStats)]
         _LIB = L
     return _LIB
+
+
+def lift_from(side):
+    """None / "target" / "query" / "both" (or an AWV_LIFT_FROM_* value) -> 0 (off) / AWV_LIFT_FROM_*."""
+    sides = {None: 0, "target": AWV_LIFT_FROM_TARGET, "query": AWV_LIFT_FROM_QUERY, "both": AWV_LIFT_FROM_BOTH,
+             AWV_LIFT_FROM_TARGET: AWV_LIFT_FROM_TARGET, AWV_LIFT_FROM_QUERY: AWV_LIFT_FROM_QUERY, AWV_LIFT_FROM_BOTH: AWV_LIFT_FROM_BOTH}
+    if isinstance(side, bool) or side not in sides:
+        raise ValueError("liftover side: None, 'target', 'query' or 'both', not %r" % (side,))
+    return sides[side]
+
+
+def _struct_array(rows, dtype, what):
+    """A contiguous array of `dtype` from one, or from rows of its fields in order."""
+    if isinstance(rows, np.ndarray) and rows.dtype == dtype:
+        return np.ascontiguousarray(rows)
+    out = np.zeros(len(rows), dtype=dtype)
+    names = [n for n in dtype.names if n != "reserved"]
+    for k, row in enumerate(rows):
+        if len(row) != len(names):
+            raise ValueError("%s: %d fields per entry (%s)" % (what, len(names), ", ".join(names)))
+        for name, val in zip(names, row):
+            out[k][name] = val if not isinstance(val, str) else lift_from(val)
+    return out
 
 
 def coverage_roles(coverage):
@@ -803,6 +863,72 @@ class Engine:
         """awv_engine_coverage_stats: kernel_ms, items, failed, columns, boundaries, reads since coverage_begin."""
         return self._stats("awv_engine_coverage_stats", CovStats)
 
+    def lift_cigars(self, pairs, results, arena, queries, slices=None):
+        """awv_lift_cigars: lifts intervals through caller-supplied records (a RESULT_DTYPE array whose cigar_off / cigar_len point
+        into `arena`, bytes or a uint8 array), on the device.  queries: a LIFT_QUERY_DTYPE array, or (record, from, beg, end) rows
+        with from "target" / "query" (or AWV_LIFT_FROM_*), in any order.  slices: as for cs_cigars.  Returns a LIFT_DTYPE array, entry
+        j the answer to query j."""
+        return self._lift("awv_lift_cigars", self._pair_array(pairs), results, arena, queries, slices)
+
+    def lift_ranges(self, ranges, results, arena, queries, slices=None):
+        """lift_cigars on interval pairs (awv_lift_ranges)."""
+        return self._lift("awv_lift_ranges", self._range_array(ranges), results, arena, queries, slices)
+
+    def _lift(self, fn, pairs, results, arena, queries, slices):
+        results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+        if results.shape != (len(pairs),):
+            raise ValueError("results: need one record per pair")
+        sl = self._slice_array(slices, len(results))
+        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
+        nbytes = int(arena.size)
+        if nbytes == 0:
+            arena = np.zeros(1, dtype=np.uint8)
+        q = _struct_array(queries, LIFT_QUERY_DTYPE, "queries")
+        nq = len(q)
+        if nq == 0:
+            q = np.zeros(1, dtype=LIFT_QUERY_DTYPE)
+        lout = np.zeros(max(nq, 1), dtype=LIFT_DTYPE)[:nq]
+        rc = getattr(load(), fn)(self._h, pairs.ctypes.data, len(pairs), results.ctypes.data, arena.ctypes.data, nbytes,
+                                 None if sl is None else sl.ctypes.data, q.ctypes.data, nq, lout.ctypes.data)
+        if rc != AWV_OK:
+            raise EngineError(rc, fn)
+        return lout
+
+    def lift_begin(self, regions, from_="target", clip_min_score=0):
+        """awv_engine_lift_begin: from now on every aligning call of this engine lifts `regions` (a REGION_DTYPE array or (seq, beg,
+        end) rows, forward strand) through its contributing alignments, on the device, and appends the lifted ones to a table.
+        from_: the side the regions lie on, "target", "query", "both" (or an AWV_LIFT_FROM_* mask); None or 0 ends the table, as
+        set_sequences does.  clip_min_score: the least score of a clip that contributes."""
+        mask = from_ if isinstance(from_, int) and not isinstance(from_, bool) else lift_from(from_)  # (an integer goes through as it is)
+        g = _struct_array(regions if regions is not None else [], REGION_DTYPE, "regions")
+        n = len(g)
+        if n == 0:
+            g = np.zeros(1, dtype=REGION_DTYPE)
+        rc = load().awv_engine_lift_begin(self._h, g.ctypes.data, n, mask, int(clip_min_score))
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_engine_lift_begin")
+
+    def lift_read(self, cap=None):
+        """awv_engine_lift_read: the table so far, a LIFT_ROW_DTYPE array sorted by all its fields, region first.  cap: the rows
+        the buffer holds (None: measured first); when the table is larger nothing is written and RowsDoNotFit is raised."""
+        n = C.c_uint64(0)
+        if cap is None:
+            rc = load().awv_engine_lift_read(self._h, None, 0, C.byref(n))
+            if rc != AWV_OK:
+                raise EngineError(rc, "awv_engine_lift_read")
+            cap = n.value
+        rows = np.zeros(max(int(cap), 1), dtype=LIFT_ROW_DTYPE)
+        rc = load().awv_engine_lift_read(self._h, rows.ctypes.data, int(cap), C.byref(n))
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_engine_lift_read")
+        if n.value > int(cap):
+            raise RowsDoNotFit(n.value)
+        return rows[:n.value].copy()
+
+    def lift_stats(self):
+        """awv_engine_lift_stats: kernel_ms, records, columns, queries and the queries per code since lift_begin."""
+        return self._stats("awv_engine_lift_stats", LiftStats)
+
     def variants_begin(self, clip_min_score=0, reserve_rows=0):
         """awv_engine_variants_begin: from now on every aligning call of this engine appends its contributing alignments' (site,
         allele) events to a table on the device.  reserve_rows: the row buffer's first size (0: the default)."""
@@ -1130,6 +1256,26 @@ def coverage_one_host(roles, q_revcomp, qlen, tlen, cigar, span=None, slice=None
     if rc != AWV_OK:
         raise EngineError(rc, "awv_coverage_one_host")
     return out[0], q_tracks, t_tracks
+
+
+def lift_one_host(from_, q_revcomp, qlen, tlen, cigar, beg, end, span=None, slice=None):
+    """awv_lift_one_host: [beg, end) of the source's forward strand lifted through one item, on the host (needs no device; the
+    yardstick the kernel is tested against).  from_: "target" / "query" (or AWV_LIFT_FROM_*); span: None (the whole of both
+    sequences) or (pb, pe, tb, te) in pattern / text coordinates; slice: None, or (col_beg, col_end, q_skip, t_skip).  Returns one
+    LIFT_DTYPE record."""
+    cigar = bytes(cigar)
+    f = from_ if isinstance(from_, int) and not isinstance(from_, bool) else lift_from(from_)
+    pb, pe, tb, te = (0, qlen, 0, tlen) if span is None else (int(v) for v in span)
+    sl = None
+    if slice is not None:
+        sl = np.zeros(1, dtype=CS_SLICE_DTYPE)
+        sl[0] = tuple(int(v) for v in slice)
+    out = np.zeros(1, dtype=LIFT_DTYPE)
+    rc = load().awv_lift_one_host(f, int(bool(q_revcomp)), qlen, tlen, pb, pe, tb, te, cigar, len(cigar), None if sl is None else sl.ctypes.data,
+                                  int(beg), int(end), out.ctypes.data)
+    if rc != AWV_OK:
+        raise EngineError(rc, "awv_lift_one_host")
+    return out[0]
 
 
 def variants_one_host(q_idx, t_idx, q_revcomp, pattern, tlen, cigar, span=None, slice=None):

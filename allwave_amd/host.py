@@ -160,11 +160,11 @@ def _check_split(split, split_min_score, clip):
 
 
 def _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split=None, split_min_score=None, normalize=None, device_cigar=False,
-                     cs=None, coverage=None, variants=False):
+                     cs=None, coverage=None, variants=False, liftover=None, liftover_from=None, ids=None):
     """The bounds, the clipping, the splitting, the normalization, the device-side CIGAR text and the cs tag of this thread's next
     alignment hook, which takes them: every argument is checked before anything is set, and all settings are always written
     (awh_set_bounds, awh_set_clip, awh_set_split, awh_set_normalize, awh_set_device_cigar, awh_set_cs, awh_set_coverage,
-    awh_set_variants)."""
+    awh_set_variants, awh_set_liftover)."""
     bonus, least = _check_clip(clip, clip_min_score)
     sbonus, sleast = _check_split(split, split_min_score, clip)
     mode = ffi.norm_mode(normalize)
@@ -176,6 +176,7 @@ def _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split=No
     roles = ffi.coverage_roles(coverage) if coverage is None or isinstance(coverage, str) else None
     if roles is None:
         raise ValueError("coverage: None, 'target', 'query' or 'both', not %r" % (coverage,))
+    regions, side = _check_liftover(liftover, liftover_from, ids)
     _set_bounds(max_penalty, max_divergence)
     load().awh_set_clip(bonus, C.c_int64(least))
     load().awh_set_split(sbonus, C.c_int64(sleast))
@@ -184,6 +185,55 @@ def _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split=No
     load().awh_set_cs(int(cs_mode))
     load().awh_set_coverage(int(roles))
     load().awh_set_variants(int(bool(variants)))
+    load().awh_set_liftover.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
+    load().awh_set_liftover(regions.ctypes.data if len(regions) else None, len(regions), int(side))
+
+
+def _check_liftover(liftover, liftover_from, ids):
+    """(an ffi.REGION_DTYPE array, the AWV_LIFT_FROM_* mask) of liftover= / liftover_from=: liftover is None (off), an
+    ffi.REGION_DTYPE array or (seq, beg, end) rows, seq an index or one of `ids`; liftover_from "target" (the default), "query" or
+    "both"."""
+    if liftover is None:
+        if liftover_from is not None:
+            raise ValueError("liftover_from requires liftover")
+        return np.zeros(0, dtype=ffi.REGION_DTYPE), 0
+    side = ffi.lift_from("target" if liftover_from is None else liftover_from) if liftover_from is None or isinstance(liftover_from, str) else 0
+    if not side:
+        raise ValueError("liftover_from: 'target', 'query' or 'both', not %r" % (liftover_from,))
+    if isinstance(liftover, np.ndarray) and liftover.dtype == ffi.REGION_DTYPE:
+        return np.ascontiguousarray(liftover), side
+    where = {name: k for k, name in enumerate(ids or [])}
+    out = np.zeros(len(liftover), dtype=ffi.REGION_DTYPE)
+    for k, row in enumerate(liftover):
+        if len(row) != 3:
+            raise ValueError("liftover: (seq, beg, end) rows")
+        seq = row[0]
+        if isinstance(seq, (str, bytes)):
+            if seq not in where:
+                raise ValueError("liftover: no sequence named %r" % (seq,))
+            seq = where[seq]
+        out[k] = (int(seq), int(row[1]), int(row[2]))
+    return out, side
+
+
+def last_liftover():
+    """last_liftover() of this thread's last all_pairs_paf / all_pairs_paf_count / iterate / align_ranges call with liftover=...:
+    dict(rows, stats) -- rows the lifted regions (ffi.LIFT_ROW_DTYPE, sorted by all fields, region first), the slots' rows
+    concatenated and sorted, so several devices give the one-engine table exactly; stats an ffi.LiftStats summed over the slots.
+    rows is empty for a call without liftover."""
+    rows = C.c_void_p()
+    n = C.c_size_t(0)
+    st = ffi.LiftStats()
+    L = load()
+    L.awh_last_liftover.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    if L.awh_last_liftover(C.byref(rows), C.byref(n), C.byref(st)) != 0:
+        raise HostError("out of memory")
+    try:
+        nbytes = n.value * ffi.LIFT_ROW_DTYPE.itemsize
+        out = np.frombuffer(C.string_at(rows, nbytes), dtype=ffi.LIFT_ROW_DTYPE).copy() if nbytes else np.zeros(0, dtype=ffi.LIFT_ROW_DTYPE)
+    finally:
+        L.awh_free(rows)
+    return dict(rows=out, stats=st)
 
 
 def last_coverage():
@@ -366,7 +416,7 @@ def check_paf(ids, seqs, paf_text, scores, optimal=False, device=0, partial=Fals
 
 
 def align_ranges(ids, seqs, ranges, scores, devices=None, device=0, verify=False, max_penalty=None, max_divergence=None, clip=None,
-                 clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False):
+                 clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False, liftover=None, liftover_from=None):
     """allwave::align_ranges + alignment_to_paf: the interval pairs `ranges` -- rows (query_idx, target_idx, is_reverse,
     query_start, query_end, target_start, target_end), the query interval on its forward strand -- aligned globally on the
     engines `devices` names (default: [device]).  Returns the PAF lines in list order: columns 3-4 and 8-9 are the interval,
@@ -382,7 +432,7 @@ def align_ranges(ids, seqs, ranges, scores, devices=None, device=0, verify=False
     n = C.c_size_t(0)
     e = _err()
     rbuf = r if len(r) else np.zeros((1, 7), dtype=np.int64)
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants, liftover, liftover_from, ids)
     rc = load().awh_align_ranges_paf(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), scores.encode(),
                                      rbuf.ctypes.data_as(C.c_void_p), C.c_size_t(len(r)), devs, nd, int(bool(verify)), C.byref(out),
                                      C.byref(n), e, _CAP)
@@ -453,7 +503,7 @@ def _device_args(devices):
 
 def all_pairs_paf(ids, seqs, scores, orientation="wfa", exclude_self=True, device=0, sparsification="none", devices=None,
                   min_batch_pairs=0, orientation_full=False, verify=False, max_penalty=None, max_divergence=None, clip=None,
-                  clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False):
+                  clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False, liftover=None, liftover_from=None):
     """AllPairIterator + alignment_to_paf per record; returns the list of PAF lines.  `devices`: a list of ordinals (one
     engine per entry, repeats allowed) to spread the pair list over in this call; None = [device].
     `min_batch_pairs` > 0 overrides the smallest batch of a multi-device run (default 16,384).  orientation_full: WFA
@@ -483,14 +533,16 @@ def all_pairs_paf(ids, seqs, scores, orientation="wfa", exclude_self=True, devic
     coverage ("target" / "query" / "both"): the run also accumulates, on the device, the per-base depth of what it aligned
     (with_coverage: per base of every sequence, in how many alignments it is aligned and in how many it matches); the lines are
     those of the run without it, and last_coverage() returns the two tracks.  variants=True: the run also tallies, on the device, the
-    per-site allele table of what it aligned (with_variants; last_variants() returns it).  iterate and align_ranges take it too.  all_pairs_paf_count and
+    per-site allele table of what it aligned (with_variants; last_variants() returns it).  liftover= ((seq, beg, end) rows, seq an
+    index or an id, forward strand) with liftover_from= ("target", the default, "query" or "both"): the run also lifts those regions,
+    on the device, through what it aligned (with_liftover; last_liftover() returns the rows).  iterate and align_ranges take it too.  all_pairs_paf_count and
     align_ranges take it too; iterate accepts and ignores it."""
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if devices is None else devices)
     out = C.c_void_p()
     n = C.c_size_t(0)
     e = _err()
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants, liftover, liftover_from, ids)
     rc = load().awh_all_pairs_paf_devices(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
                                           scores.encode(), sparsification.encode(), _orient_code(orientation, orientation_full), int(exclude_self),
                                           devs, nd, C.c_int64(int(min_batch_pairs)), int(bool(verify)), None, C.byref(out), C.byref(n), e, _CAP)
@@ -507,7 +559,7 @@ ITER_MODES = {"for_each": 0, "next": 1, "par_for_each": 2, "par_collect": 3, "pr
 def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientation="forward", threads=4, chunk=0,
             resparsify=False, fail_at=-1, device=0, devices=None, min_batch_pairs=0, shard=None, with_stats=False,
             orientation_full=False, verify=False, max_penalty=None, max_divergence=None, clip=None, clip_min_score=None, split=None,
-            split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False):
+            split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False, liftover=None, liftover_from=None):
     """Every consumer of the pair list (iterator.rs:101-253, lib.rs:57-68) through one hook; returns the PAF lines in arrival
     order.  `fail_at` >= 0 makes the callback throw at that record: HostError carries its message.
     `devices`: a list of ordinals (one engine per entry, repeats allowed) to spread the pair list over; None = [device].
@@ -522,7 +574,7 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
     hands out alignment records with their op bytes."""
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if devices is None else devices)
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants, liftover, liftover_from, ids)
     st = (ffi.Stats * nd)()
     rank, world = shard if shard is not None else (0, 1)
     out = C.c_void_p()
@@ -547,7 +599,7 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
 
 def all_pairs_paf_count(ids, seqs, scores, orientation="forward", device=0, format_threads=8, devices=None, min_batch_pairs=0,
                         sparsification=None, checksum=False, verify=False, max_penalty=None, max_divergence=None, clip=None,
-                        clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False):
+                        clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False, liftover=None, liftover_from=None):
     """End to end: upload -> align -> D2H -> format into a counting sink. Returns (bytes, lines, secs, ffi.Stats) for
     every pair on `device`.  `devices`: a list of ordinals (one engine per entry, repeats allowed); the Stats are then
     summed over the slots, and the result gains a fifth element, each slot's Stats (last_slot_stats()), and a sixth, the
@@ -559,7 +611,7 @@ def all_pairs_paf_count(ids, seqs, scores, orientation="forward", device=0, form
     one = devices is None
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if one else devices)
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants, liftover, liftover_from, ids)
     nb, nl, secs, ck = C.c_uint64(0), C.c_uint64(0), C.c_double(0), C.c_uint64(0)
     st = ffi.Stats()
     slot = (ffi.Stats * nd)()

@@ -910,6 +910,113 @@ int awv_variants_ranges(awv_engine* e, const awv_range_pair* ranges, int64_t n, 
  * awv_variants_fold_host's: the four 32-bit fields as signed numbers, the hash as an unsigned 64-bit word), become
  * awv_variants_fold_host's rows in place; *n_rows is their number.  Needs no sequence set. */
 int awv_variants_fold(awv_engine* e, awv_variant* rows, uint64_t n, uint64_t* n_rows /* required */);
+
+/* ---- regions lifted through alignments on the device (csrc/lift.hip, csrc/lift_device.hpp) --------------------------------------
+ * This interval of sequence A: where is it on a sequence A was aligned with, and how well does it align there?  The one answer
+ * that crosses sequences; the rule is __host__ __device__ in lift_device.hpp.  A pure function of the op bytes, the rectangle and
+ * the interval: no penalties are involved and no sequence bytes are read.
+ * An item is exactly the coverage pass's item: an op string c[0..n) over M X I D ('I' consumes the text only, 'D' the pattern
+ * only, 'M' and 'X' both) with its rectangle (pattern [pb, pe) against text [tb, te), the pattern the reverse-complement copy for
+ * a q_revcomp pair) and the skips of a slice.  Column k sits at pattern position x = pb + q_skip + #(ops other than 'I' before k)
+ * and at text position y = tb + t_skip + #(ops other than 'D' before k).
+ * A lift query names a side and a half-open interval [a, b) on the source sequence's forward strand.  AWV_LIFT_FROM_TARGET: the
+ * source is the text, the destination the pattern; AWV_LIFT_FROM_QUERY: the reverse.  For a q_revcomp pair a query-side position
+ * f is pattern position len[q] - 1 - f, so [a, b) becomes [len - b, len - a), and reported query intervals are turned back the
+ * same way.  srcpos(k) is column k's source position, defined for the columns that consume the source; the item's source span is
+ * [s0, s0 + S), s0 the source position of column 0 and S the source bases the string consumes.  The lift is the aligned core:
+ *     col_beg = the smallest k with c[k] in {M, X} and srcpos(k) >= a     (n when there is none)
+ *     col_end = 1 + the largest k with c[k] in {M, X} and srcpos(k) < b   (0 when there is none)
+ * The interval does not meet the span: AWV_LF_OUTSIDE.  It does and col_beg >= col_end (it lies in a gap): AWV_LF_UNALIGNED.
+ * Otherwise AWV_LF_OK, and the slice [col_beg, col_end) begins and ends on an 'M' / 'X' column: gap runs of either kind strictly
+ * inside it belong to it, gap columns at its edges do not, and an interval reaching beyond the span is cut to it by the same rule.
+ * AWV_LF_SKIPPED, AWV_LF_BAD_OP and AWV_LF_LENGTHS are coverage's codes and hold for the whole item: every query of such an item
+ * carries the item's code, whatever its own columns look like.
+ * Known answers (the ops of minimap2's cs example, 6M 3I 10M 3D 4M 1X 3M, whole sequences, a forward pair):
+ *     from target [4, 12)   OK, slice [4, 12), target [4, 12), query [4, 9), 5 M and 3 I
+ *     from target [6, 9)    AWV_LF_UNALIGNED
+ *     from target [7, 10)   OK, slice [9, 10), target [9, 10), query [6, 7)
+ *     from query [15, 20)   OK, slice [18, 23), query [15, 20), target [18, 20), 2 M and 3 D
+ * A string or slice holds at most 2^30 columns, a call fewer than 2^30 queries (AWV_ERR_ARG otherwise, before anything is launched). */
+#define AWV_LIFT_FROM_TARGET 1
+#define AWV_LIFT_FROM_QUERY 2
+#define AWV_LIFT_FROM_BOTH 3 /* a from_mask of awv_engine_lift_begin only */
+#define AWV_LF_OK 0        /* the interval has an aligned core: the slice and the two intervals are filled */
+#define AWV_LF_SKIPPED 1   /* status is not AWV_ST_COMPLETED */
+#define AWV_LF_BAD_OP 2    /* a byte outside MXID anywhere in the string or slice */
+#define AWV_LF_LENGTHS 3   /* the string consumes more than its rectangle */
+#define AWV_LF_UNALIGNED 4 /* the interval meets the item's source span but holds no aligned column there */
+#define AWV_LF_OUTSIDE 5   /* the interval does not meet the item's source span */
+#define AWV_LIFT_ROW_REVCOMP 1    /* awv_lift_row.flags: the pair is q_revcomp */
+#define AWV_LIFT_ROW_FROM_QUERY 2 /* the region lies on the query (src is the query, dst the target) */
+typedef struct {
+  int64_t record;   /* of the call's records */
+  int32_t from;     /* AWV_LIFT_FROM_TARGET / AWV_LIFT_FROM_QUERY */
+  int32_t beg, end; /* [beg, end) on the source sequence's forward strand */
+  int32_t reserved; /* not read */
+} awv_lift_query; /* 24 bytes */
+typedef struct {
+  int32_t code;              /* AWV_LF_*; every other field is 0 unless it is AWV_LF_OK */
+  int32_t reserved;          /* 0 */
+  uint32_t col_beg, col_end; /* with the skips exactly an awv_cs_slice of the record's op string: counted from the string's */
+  int32_t q_skip, t_skip;    /* start, the item's own slice included */
+  int32_t src_beg, src_end;  /* the source and destination intervals the slice covers, forward strand, sequence coordinates */
+  int32_t dst_beg, dst_end;
+  int32_t num_matches, num_mismatches, num_ins, num_del; /* the slice's 'M', 'X', 'I', 'D' bytes (as in awv_clip_result) */
+} awv_lift_result; /* 56 bytes */
+typedef struct {
+  int32_t seq, beg, end; /* [beg, end) of resident sequence seq, forward strand */
+} awv_region; /* 12 bytes */
+typedef struct {
+  int32_t region;             /* index into the begin's regions */
+  int32_t q_idx, t_idx;       /* the alignment the row comes from */
+  int32_t flags;              /* AWV_LIFT_ROW_* */
+  int32_t src_beg, src_end;   /* on the region's sequence */
+  int32_t dst_beg, dst_end;   /* on the other sequence of the pair */
+  int32_t num_matches, num_mismatches, num_ins, num_del;
+} awv_lift_row; /* 48 bytes */
+typedef struct {
+  double kernel_ms;   /* HIP-event time of the lift launches since awv_engine_lift_begin (since the engine's creation before one) */
+  uint64_t records;   /* records walked: the ones with a query, each once per launch */
+  uint64_t columns;   /* their op bytes, each once however many queries a record has */
+  uint64_t queries;
+  uint64_t ok, skipped, bad_op, lengths, unaligned, outside; /* queries that ended with each code */
+} awv_lift_stats; /* 80 bytes */
+
+/* The contract alone, on the host (needs no device): a serial per-column walk, the yardstick the kernel is tested against, not a
+ * fallback -- no product path calls it.  The rectangle and the slice as in awv_coverage_one_host; [beg, end) on the source's
+ * forward strand, 0 <= beg < end <= the source sequence's length (AWV_ERR_ARG otherwise). */
+int awv_lift_one_host(int32_t from, int32_t q_revcomp, int32_t qlen, int32_t tlen, int32_t pb, int32_t pe, int32_t tb, int32_t te,
+                      const uint8_t* cigar, int64_t n, const awv_cs_slice* slice /* nullable */, int32_t beg, int32_t end,
+                      awv_lift_result* out /* required */);
+/* Lifts intervals through records and op bytes the caller supplies, on the device: results[i] claims that
+ * cigar_arena[results[i].cigar_off, + cigar_len) aligns pairs[i] (ranges[i]).  The engine needs a sequence set for the lengths
+ * only (AWV_ERR_STATE without one).  Queries come in any order and reach any number of records; lout[j] answers queries[j].  One
+ * wave walks a record's op string once and answers all of its queries in that walk; a record without a query is not walked.
+ * Staged and pieced as awv_coverage_cigars does; slices (nullable): n entries.  AWV_ERR_ARG, before anything is launched, for
+ * what awv_cs_cigars refuses, a record index outside [0, n), a `from` other than the two sides, beg >= end, beg < 0 and an end
+ * above the source sequence's length. */
+int awv_lift_cigars(awv_engine* e, const awv_pair* pairs, int64_t n, const awv_result* results, const uint8_t* cigar_arena,
+                    uint64_t arena_bytes, const awv_cs_slice* slices /* nullable */, const awv_lift_query* queries, int64_t nq,
+                    awv_lift_result* lout /* required when nq > 0 */);
+int awv_lift_ranges(awv_engine* e, const awv_range_pair* ranges, int64_t n, const awv_result* results, const uint8_t* cigar_arena,
+                    uint64_t arena_bytes, const awv_cs_slice* slices /* nullable */, const awv_lift_query* queries, int64_t nq,
+                    awv_lift_result* lout /* required when nq > 0 */);
+/* Begins a table over the resident sequence set (AWV_ERR_STATE without one).  regions[0..n_regions): forward strand, in any
+ * order; they may overlap, nest and repeat (AWV_ERR_ARG for a sequence index out of range or an interval that is empty or outside
+ * its sequence).  From then on every aligning call of the engine -- awv_align_pairs and awv_align_ranges in all their forms --
+ * lifts, per batch, on the device and on the engine's stream, after normalization and the clip / split step: every region through
+ * every contributing item (the coverage rule, word for word) that overlaps it, regions on an item's target under
+ * AWV_LIFT_FROM_TARGET, on its query under AWV_LIFT_FROM_QUERY.  The AWV_LF_OK results are appended to the table as rows, on the
+ * host; records, op bytes, texts and stats of those calls are unchanged.  from_mask == 0 ends the table (the stats stay
+ * readable), and so does awv_engine_set_sequences.  clip_min_score: the threshold of clipping calls. */
+int awv_engine_lift_begin(awv_engine* e, const awv_region* regions, int64_t n_regions, int32_t from_mask, int64_t clip_min_score);
+/* The table so far, sorted ascending by all fields in their order (region first; as signed numbers): it does not depend on the
+ * order of batches, and tables of several engines merge by concatenating and sorting.  *n_rows is the number of rows whatever
+ * cap is; they are written only when *n_rows <= cap, all or none, so rows == NULL with cap == 0 is the measuring call.
+ * AWV_ERR_STATE before begin. */
+int awv_engine_lift_read(awv_engine* e, awv_lift_row* rows, uint64_t cap, uint64_t* n_rows /* required */);
+/* Since the last awv_engine_lift_begin of this engine (since its creation before one); awv_lift_cigars / _ranges add to it. */
+int awv_engine_lift_stats(const awv_engine* e, awv_lift_stats* out);
 /* ---- device pair planning (csrc/planner.hip) -------------------------------------------------------------------------
  * Integer work over the engine's resident sequence set, on its device and stream; results equal the host planner's
  * (csrc/host/planner.cpp) bit for bit.  Every call but awv_keep_pairs needs a sequence set (else AWV_ERR_STATE); a new set
