@@ -22,6 +22,7 @@
 #include "coverage_device.hpp" // (the per-batch depth accumulation under awv_engine_coverage_begin, coverage.hip)
 #include "variants_device.hpp" // (the per-batch allele events under awv_engine_variants_begin, variants.hip)
 #include "lift_device.hpp"     // (the per-batch lifts under awv_engine_lift_begin, lift.hip)
+#include "msa_device.hpp"      // (the buffers of awv_msa_cigars / awv_msa_ranges, msa.hip)
 #include "kernels_awv.hpp"  // (the awv:: kernels themselves are instantiated in kernels_awv.hip -- here only the types)
 #define AWV_NS awv
 #define AWV_WG 64
@@ -200,6 +201,7 @@ struct awv_engine {
   bool cov_paused = false;         // (orient.hip: the strand alignments inside an orientation call do not count -- for the depth and for the allele table)
   awvvar::State* var = nullptr;    // variants.hip: the allele table between awv_engine_variants_begin and its end, and the launches' buffers
   awvl::State* lift = nullptr;     // lift.hip: the regions and rows between awv_engine_lift_begin and its end, and the launches' buffers
+  awvmsa::State* msa = nullptr;    // msa.hip: the launches' buffers and the last call's stats
   int32_t norm_mode = AWV_NORM_OFF;  // awv_engine_set_normalize: read at the start of every aligning call
 };
 
@@ -1285,6 +1287,8 @@ void awv_engine_destroy(awv_engine* e) {
   e->var = nullptr;
   awvl::state_release(e->lift);
   e->lift = nullptr;
+  awvmsa::state_release(e->msa);
+  e->msa = nullptr;
   e->seqs.release();
   e->ring_mem.release();
   e->hist_mem.release();
@@ -1541,6 +1545,7 @@ awvcs::State*& awv_internal_cs(awv_engine* e) { return e->cs; }
 awvcov::State*& awv_internal_coverage(awv_engine* e) { return e->cov; }
 awvvar::State*& awv_internal_variants(awv_engine* e) { return e->var; }
 awvl::State*& awv_internal_lift(awv_engine* e) { return e->lift; }
+awvmsa::State*& awv_internal_msa(awv_engine* e) { return e->msa; }
 bool& awv_internal_coverage_paused(awv_engine* e) { return e->cov_paused; }
 int32_t& awv_internal_normalize_mode(awv_engine* e) { return e->norm_mode; }
 uint64_t awv_internal_max_arena(const awv_engine* e) { return e->cfg.max_arena_bytes > 0 ? (uint64_t)e->cfg.max_arena_bytes : (uint64_t)8 << 30; }

@@ -11,6 +11,8 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <numeric>
+#include <tuple>
 #include <chrono>
 #include <condition_variable>
 #include <dlfcn.h>
@@ -367,6 +369,7 @@ void RunOptions::apply(AllPairIterator& it) const {
   if (coverage != 0) it.with_coverage(coverage);
   if (variants) it.with_variants(true);
   if (liftover_from != 0) it.with_liftover(liftover, liftover_from);
+  if (msa) it.with_msa(msa_targets, msa_max_bytes);
   if (max_penalty) it.with_max_penalty(*max_penalty);
   if (max_divergence) it.with_max_divergence(*max_divergence);
   if (clip_match_bonus != 0) it.with_clip(clip_match_bonus, clip_min_score);
@@ -548,6 +551,9 @@ AllPairIterator AllPairIterator::with_sparsification(SparsificationStrategy stra
   it.variants_ = variants_;
   it.lift_from_ = lift_from_;
   it.lift_regions_ = lift_regions_;
+  it.msa_ = msa_;
+  it.msa_targets_ = msa_targets_;
+  it.msa_max_bytes_ = msa_max_bytes_;
   return it;
 }
 AllPairIterator& AllPairIterator::with_device_cigar(bool on) {
@@ -573,6 +579,20 @@ AllPairIterator& AllPairIterator::with_liftover(std::vector<awv_region> regions,
       throw std::invalid_argument("with_liftover: a region names a sequence out of range, or an interval that is empty or outside its sequence");
   lift_from_ = from;
   lift_regions_ = from != 0 ? std::move(regions) : std::vector<awv_region>{};
+  return *this;
+}
+AllPairIterator& AllPairIterator::with_msa(std::vector<int> targets, uint64_t max_bytes) {
+  if (max_bytes == 0) throw std::invalid_argument("with_msa: max_bytes must be positive");
+  std::vector<uint8_t> seen(sequences_.size(), 0);
+  for (int t : targets) {
+    if (t < 0 || (size_t)t >= sequences_.size()) throw std::invalid_argument("with_msa: a target names a sequence out of range");
+    if (seen[(size_t)t]++) throw std::invalid_argument("with_msa: a target is named twice");
+  }
+  if (targets.empty())
+    for (size_t t = 0; t < sequences_.size(); ++t) targets.push_back((int)t);
+  msa_ = true;
+  msa_targets_ = std::move(targets);
+  msa_max_bytes_ = max_bytes;
   return *this;
 }
 AllPairIterator& AllPairIterator::with_normalize(int direction) {
@@ -911,6 +931,7 @@ struct AllPairIterator::SlotTotals {
   std::vector<uint32_t> cov_aligned, cov_matched;  // a coverage run: the slot's tracks, read when its batches are done
   std::vector<awv_variant> var_rows;                // a variants run: the slot's folded table, likewise
   std::vector<awv_lift_row> lift_rows;              // a liftover run: the slot's rows, likewise
+  MsaStore msa;                                     // an msa run: what the slot's sink calls kept
 };
 
 // What the slots of one run share.  The settings hold for alignment calls only: a score-only run has none of them.
@@ -926,6 +947,8 @@ struct AllPairIterator::RunState {
   int coverage = 0;  // the roles of a run that accumulates the per-base depth (0: none)
   bool variants = false;  // a run that tallies the allele table
   int liftover = 0;  // the side mask of a run that lifts regions (0: none)
+  const AllPairIterator* msa = nullptr;  // a run that keeps items for the multiple alignments (nullptr: none)
+  std::vector<uint8_t> msa_chosen;        // per sequence: it is one of the targets
   uint64_t n_bases = 0;  // the sum of the sequences' lengths
   int normalizing = AWV_NORM_OFF;
   std::optional<double> div;  // the divergence bound of a bounded run
@@ -1069,6 +1092,7 @@ struct AllPairIterator::SinkCtx {
   RunState* rs;
   const Delivery* d;
   bool failed;
+  SlotTotals* totals;
 };
 int AllPairIterator::batch_sink(void* user, int64_t first, int64_t cnt, const awv_result* res, const uint8_t* arena) {
   return batch_cs_sink(user, first, cnt, res, arena, nullptr);
@@ -1080,10 +1104,14 @@ int AllPairIterator::batch_cs_sink(void* user, int64_t first, int64_t cnt, const
   try {
     if (c->d->filters()) {
       const Delivered k = deliver(*c->d, first, cnt, res);
-      (*c->rs->batch_cb)(Batch{0, (int64_t)k.res.size(), k.res.data(), arena, k.rev.data(), k.idx.data(), k.clip.empty() ? nullptr : k.clip.data(),
-                               k.text.empty() ? nullptr : k.text.data(), k.cs.empty() ? nullptr : k.cs.data(), cs_arena});
+      const Batch b{0, (int64_t)k.res.size(), k.res.data(), arena, k.rev.data(), k.idx.data(), k.clip.empty() ? nullptr : k.clip.data(),
+                    k.text.empty() ? nullptr : k.text.data(), k.cs.empty() ? nullptr : k.cs.data(), cs_arena};
+      if (c->rs->msa) c->rs->msa->keep_msa(*c->rs, b, c->totals->msa);
+      (*c->rs->batch_cb)(b);
     } else {
-      (*c->rs->batch_cb)(Batch{first, cnt, res, arena, c->d->rev, c->d->idx, nullptr, c->d->text, c->d->cs, cs_arena});
+      const Batch b{first, cnt, res, arena, c->d->rev, c->d->idx, nullptr, c->d->text, c->d->cs, cs_arena};
+      if (c->rs->msa) c->rs->msa->keep_msa(*c->rs, b, c->totals->msa);
+      (*c->rs->batch_cb)(b);
     }
   } catch (...) {
     c->rs->fail(std::current_exception());  // recorded now, and every slot stops at its next sink call
@@ -1091,6 +1119,104 @@ int AllPairIterator::batch_cs_sink(void* user, int64_t first, int64_t cnt, const
     return 1;
   }
   return 0;
+}
+
+// What the sink keeps of a delivered batch for the multiple alignments: batch_items.hpp's rule on what the batch delivered -- a
+// completed record as it reaches the consumer is a whole record, a clip's slice that scored enough or one split segment -- for the
+// chosen targets only: pair, span, slice and op bytes.  Beyond the bound only the size is counted.
+void AllPairIterator::keep_msa(const RunState& rs, const Batch& b, MsaStore& st) const {
+  for (int64_t i = 0; i < b.n; ++i) {
+    const awv_result& r = b.res[i];
+    if (r.status != AWV_ST_COMPLETED) continue;
+    const size_t pi = b.pair(i);
+    const size_t q = rs.plist[pi].first, t = rs.plist[pi].second;
+    if (!rs.msa_chosen[t]) continue;
+    const int32_t qlen = (int32_t)sequences_[q].seq.size(), tlen = (int32_t)sequences_[t].seq.size();
+    const int32_t rev = b.is_rev(i) ? 1 : 0;
+    MsaKept k{};
+    if (ranges_) {
+      const AlignmentRange& g = (*ranges_)[rs.first + pi];
+      k.range = awv_range_pair{(int32_t)q, (int32_t)t, rev, (int32_t)g.query_start, (int32_t)g.query_end, (int32_t)g.target_start, (int32_t)g.target_end};
+    } else {
+      k.range = awv_range_pair{(int32_t)q, (int32_t)t, rev, 0, qlen, 0, tlen};
+    }
+    const awv_clip_result* cl = b.clip_at(i);
+    k.q_skip = cl ? cl->q_skip : 0;
+    k.t_skip = cl ? cl->t_skip : 0;
+    k.col_beg = cl ? cl->col_beg : 0u;
+    k.pattern_beg = (rev ? qlen - k.range.q_end : k.range.q_beg) + k.q_skip;
+    k.len = r.cigar_len;
+    k.off = st.ops.size();
+    st.need += r.cigar_len;
+    if (st.need > msa_max_bytes_) continue;
+    st.ops.insert(st.ops.end(), b.arena + r.cigar_off, b.arena + r.cigar_off + r.cigar_len);
+    st.kept.push_back(k);
+  }
+}
+
+// The run's one awv_msa_ranges call, on engine e (which holds the run's sequences): the kept items in the rows' order, measured
+// first; the blocks and their row names are left in msa_blocks_.
+awv_msa_stats AllPairIterator::build_msa(awv_engine* e) {
+  const auto bound = [&](const char* what, uint64_t need) {
+    return AlignmentError(std::string("msa: ") + what + " need " + std::to_string(need) + " bytes, more than msa_max_bytes = " + std::to_string(msa_max_bytes_));
+  };
+  msa_blocks_.clear();
+  const MsaStore& st = msa_store_;
+  if (st.need > msa_max_bytes_) throw bound("the kept op bytes", st.need);
+  std::vector<size_t> order(st.kept.size());
+  std::iota(order.begin(), order.end(), (size_t)0);
+  const auto key = [&](size_t i) {
+    const MsaKept& k = st.kept[i];
+    return std::make_tuple(k.range.q_idx, k.range.q_revcomp, k.pattern_beg, k.col_beg, k.range.t_idx, k.range.t_beg + k.t_skip, k.len);
+  };
+  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return key(a) < key(b); });
+  const int64_t n = (int64_t)order.size(), nt = (int64_t)msa_targets_.size();
+  std::vector<awv_range_pair> ranges((size_t)n);
+  std::vector<awv_result> recs((size_t)n);
+  std::vector<awv_cs_slice> slices((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    const MsaKept& k = st.kept[order[(size_t)i]];
+    ranges[(size_t)i] = k.range;
+    recs[(size_t)i] = awv_result{};
+    recs[(size_t)i].status = AWV_ST_COMPLETED;
+    recs[(size_t)i].cigar_off = k.off;
+    recs[(size_t)i].cigar_len = k.len;
+    slices[(size_t)i] = awv_cs_slice{0u, k.len, k.q_skip, k.t_skip};
+  }
+  std::vector<int32_t> targets(msa_targets_.begin(), msa_targets_.end());
+  std::vector<awv_msa_item> items((size_t)std::max<int64_t>(n, 1));
+  std::vector<awv_msa_target> tgts((size_t)std::max<int64_t>(nt, 1));
+  uint64_t bytes = 0;
+  const uint8_t none = 0;
+  const uint8_t* const ops = st.ops.empty() ? &none : st.ops.data();
+  if (awv_msa_ranges(e, ranges.data(), n, recs.data(), ops, st.ops.size(), slices.data(), targets.data(), nt, items.data(), tgts.data(), nullptr, 0, &bytes) != AWV_OK)
+    throw AlignmentError(std::string("msa: ") + awv_last_error());
+  if (bytes > msa_max_bytes_) throw bound("the blocks", bytes);
+  std::vector<uint8_t> buf((size_t)std::max<uint64_t>(bytes, 1));
+  if (awv_msa_ranges(e, ranges.data(), n, recs.data(), ops, st.ops.size(), slices.data(), targets.data(), nt, items.data(), tgts.data(), buf.data(), bytes, &bytes) != AWV_OK)
+    throw AlignmentError(std::string("msa: ") + awv_last_error());
+  msa_blocks_.resize((size_t)nt);
+  for (int64_t j = 0; j < nt; ++j) {
+    MsaBlock& blk = msa_blocks_[(size_t)j];
+    blk.t_idx = tgts[(size_t)j].t_idx;
+    blk.rows = tgts[(size_t)j].rows;
+    blk.width = tgts[(size_t)j].width;
+    blk.names.assign((size_t)blk.rows, std::string());
+    blk.names[0] = sequences_[(size_t)blk.t_idx].id;
+    blk.bytes.assign(buf.begin() + (ptrdiff_t)tgts[(size_t)j].off, buf.begin() + (ptrdiff_t)(tgts[(size_t)j].off + (uint64_t)blk.rows * (uint64_t)blk.width));
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    const awv_msa_item& it = items[(size_t)i];
+    if (it.code != AWV_MS_OK || it.row <= 0) continue;
+    const MsaKept& k = st.kept[order[(size_t)i]];
+    const int64_t qlen = (int64_t)sequences_[(size_t)k.range.q_idx].seq.size(), x0 = k.pattern_beg, x1 = x0 + (int64_t)it.bases;
+    const int64_t fb = k.range.q_revcomp ? qlen - x1 : x0, fe = k.range.q_revcomp ? qlen - x0 : x1;
+    msa_blocks_[(size_t)it.target].names[(size_t)it.row] =
+        sequences_[(size_t)k.range.q_idx].id + "/" + std::to_string(fb) + "-" + std::to_string(fe) + (k.range.q_revcomp ? "-" : "+");
+  }
+  awv_msa_stats ms{};
+  awv_engine_msa_stats(e, &ms);
+  return ms;
 }
 
 // What a slot's totals take from its engine after one call: awv_engine_stats always, the kernel times and the verify
@@ -1176,6 +1302,12 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   rs.coverage = call.score_only ? 0 : coverage_;
   rs.variants = variants_ && !call.score_only;
   rs.liftover = call.score_only ? 0 : lift_from_;
+  if (msa_ && !call.score_only) {
+    if (call.encode) throw std::invalid_argument("with_msa: not together with with_device_cigar (the sink then carries text, not op bytes)");
+    rs.msa = this;
+    rs.msa_chosen.assign(sequences_.size(), 0);
+    for (int t : msa_targets_) rs.msa_chosen[(size_t)t] = 1;
+  }
   for (const Sequence& q : sequences_) rs.n_bases += q.seq.size();
   rs.div = divergence_bound();
   rs.pen = to_penalties(params_);
@@ -1210,7 +1342,7 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
     try {
       for (size_t b = s; b < rs.batches.size() && !rs.stop.load(); b = cursor.fetch_add(1)) {
         const PreparedBatch pb = prepare_batch(rs, e, b, rs.totals[s]);
-        SinkCtx ctx{&rs, &pb.delivery, false};
+        SinkCtx ctx{&rs, &pb.delivery, false, &rs.totals[s]};
         // the slot's engine is this thread's until its device lock goes: the mode holds for this call and is off again after it
         if (rs.normalizing != AWV_NORM_OFF && awv_engine_set_normalize(e, rs.normalizing) != AWV_OK) throw AlignmentError(std::string("normalize: ") + awv_last_error());
         const int rc = engine_call(e, pb.request, batch_sink, batch_cs_sink, &ctx);
@@ -1270,6 +1402,26 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   }
   if (th.size() == S - 1) worker(0);
   for (auto& t : th) t.join();
+  awv_msa_stats msa_stats{};
+  if (rs.msa) {  // the slots' items (and, for next()'s chunks, the items so far) in one call on the run's first device, still under its lock
+    if (first == 0) msa_store_ = MsaStore{};
+    for (SlotTotals& t : rs.totals) {
+      for (MsaKept k : t.msa.kept) {
+        k.off += msa_store_.ops.size();
+        msa_store_.kept.push_back(k);
+      }
+      msa_store_.need += t.msa.need;
+      if (msa_store_.need <= msa_max_bytes_) msa_store_.ops.insert(msa_store_.ops.end(), t.msa.ops.begin(), t.msa.ops.end());
+      t.msa = MsaStore{};
+    }
+    if (!rs.err) {
+      try {
+        msa_stats = build_msa(slot_engine(devices_[0], slot_no[0], per_device.at(devices_[0])));
+      } catch (...) {
+        rs.fail(std::current_exception());
+      }
+    }
+  }
   locks.clear();
   slot_stats_.clear();
   stats_ = awv_stats{};
@@ -1277,6 +1429,7 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
   if (first == 0 && !call.score_only) cov_ = Coverage{};
   if (first == 0 && !call.score_only) var_.clear();
   if (first == 0 && !call.score_only) lift_.clear();
+  if (!call.score_only && !rs.msa) msa_blocks_.clear();
   if (rs.coverage != 0 && cov_.offsets.empty()) {
     cov_.offsets.assign(sequences_.size() + 1, 0);
     for (size_t i = 0; i < sequences_.size(); ++i) cov_.offsets[i + 1] = cov_.offsets[i] + sequences_[i].seq.size();
@@ -1303,6 +1456,7 @@ void AllPairIterator::run(size_t first, size_t count, const BatchCb& batch_cb, E
     for (const SlotTotals& t : rs.totals) lift_.insert(lift_.end(), t.lift_rows.begin(), t.lift_rows.end());
     std::sort(lift_.begin(), lift_.end(), lift_row_less);
   }
+  if (rs.msa) report_.msa_stats = msa_stats;
   sort_verify_failures(report_.verify_failures);
   if (rs.err) std::rethrow_exception(rs.err);
 }

@@ -147,7 +147,8 @@ class AllPairIterator;
 
 // The options of one run that filter or rewrite what it delivers, in one place: AllPairIterator::with_max_penalty,
 // with_max_divergence (std::nullopt: no bound), with_clip and with_split (match bonus 0: off), with_normalize (AWV_NORM_OFF: off),
-// with_device_cigar, with_cs (0: off), with_coverage (0: off), with_variants, with_liftover (liftover_from 0: off).
+// with_device_cigar, with_cs (0: off), with_coverage (0: off), with_variants, with_liftover (liftover_from 0: off),
+// with_msa (msa false: off).
 struct RunOptions {
   std::optional<int> max_penalty;
   std::optional<double> max_divergence;
@@ -162,8 +163,11 @@ struct RunOptions {
   bool variants = false;
   std::vector<awv_region> liftover;  // with liftover_from: the regions lifted through the run's alignments
   int liftover_from = 0;             // AWV_LIFT_FROM_TARGET, AWV_LIFT_FROM_QUERY or AWV_LIFT_FROM_BOTH; 0: off
+  bool msa = false;                  // with msa_targets (empty: every sequence) and msa_max_bytes: the multiple alignments built from the run's alignments
+  std::vector<int> msa_targets;
+  uint64_t msa_max_bytes = (uint64_t)1 << 30;
   void apply(AllPairIterator& it) const;  // the with_* calls of what is set; they throw std::invalid_argument as documented there
-  bool any() const { return max_penalty || max_divergence || clip_match_bonus != 0 || split_match_bonus != 0 || normalize != AWV_NORM_OFF || device_cigar || cs != 0 || coverage != 0 || variants || liftover_from != 0; }
+  bool any() const { return max_penalty || max_divergence || clip_match_bonus != 0 || split_match_bonus != 0 || normalize != AWV_NORM_OFF || device_cigar || cs != 0 || coverage != 0 || variants || liftover_from != 0 || msa; }
 };
 
 // What a run leaves behind besides its results (AllPairIterator::last_report): the failed checks sorted by pair-list index,
@@ -180,6 +184,16 @@ struct RunReport {
   awv_cov_stats coverage_stats{};
   awv_variants_stats variants_stats{};  // rows: of the merged table; folds: the engines' folds
   awv_lift_stats lift_stats{};
+  awv_msa_stats msa_stats{};  // of the run's one awv_msa_ranges call
+};
+
+// One target's multiple alignment of a run with with_msa (AllPairIterator::last_msa): rows x width bytes, row-major; names[0] is the
+// target's name, names[r] of an item's row `qname/qbeg-qend` and the strand sign, the query interval on the forward strand.
+struct MsaBlock {
+  int t_idx = 0;
+  int64_t rows = 0, width = 0;
+  std::vector<std::string> names;
+  std::vector<uint8_t> bytes;
 };
 
 // The per-base depth a run with with_coverage leaves behind (AllPairIterator::last_coverage): sequence s owns entries
@@ -325,6 +339,19 @@ class AllPairIterator {  // iterator.rs:12-171
   int liftover_from() const { return lift_from_; }
   const std::vector<awv_region>& liftover_regions() const { return lift_regions_; }
   const std::vector<awv_lift_row>& last_liftover() const { return lift_; }
+  // Every alignment consumer also lays every sequence out against each of `targets` (distinct sequence indices; empty: every
+  // sequence) as a target-anchored multiple alignment, on the device (awv_msa_ranges; include/allwave_hip.h has the contract).  The
+  // batch sink keeps, on the host, what the run delivered for the chosen targets -- whole completed records, a clip's slice that
+  // reaches clip_min_score, every split segment, after normalization: pair, span, slice and op bytes -- and after the run makes one
+  // call on the run's first device, so several devices, or one ordinal given twice, give the one-engine blocks exactly.  The rows
+  // of a target are ordered by (q_idx, q_revcomp, pattern begin, column begin).  The kept op bytes and the arena of blocks are each
+  // bounded by max_bytes: beyond it the run's alignments are delivered as always, and then the run fails with an AlignmentError
+  // that names the bound and the size needed.  Not together with with_device_cigar (the sink then carries text, not op bytes).
+  // std::invalid_argument for a target out of range or named twice, and for max_bytes == 0.
+  AllPairIterator& with_msa(std::vector<int> targets, uint64_t max_bytes = (uint64_t)1 << 30);
+  AllPairIterator& without_msa() { msa_ = false; msa_targets_.clear(); return *this; }
+  bool msa() const { return msa_; }
+  const std::vector<MsaBlock>& last_msa() const { return msa_blocks_; }
   AllPairIterator& with_max_penalty(int max_penalty);
   AllPairIterator& with_max_divergence(double max_divergence);
   // of the last run (next(): of the chunks since the list's start), summed over the slots
@@ -443,6 +470,25 @@ class AllPairIterator {  // iterator.rs:12-171
   int lift_from_ = 0;                     // with_liftover (0: off)
   std::vector<awv_region> lift_regions_;  // its regions
   std::vector<awv_lift_row> lift_;        // the lifted rows of the last run (next(): since the list's start)
+  // with_msa: what the sink keeps of an item, the kept op bytes, what they would take without the bound, and the last run's blocks
+  struct MsaKept {
+    awv_range_pair range;
+    int32_t q_skip, t_skip, pattern_beg;
+    uint32_t col_beg, len;
+    uint64_t off;  // of the item's op bytes
+  };
+  struct MsaStore {
+    std::vector<MsaKept> kept;
+    std::vector<uint8_t> ops;
+    uint64_t need = 0;
+  };
+  bool msa_ = false;
+  std::vector<int> msa_targets_;
+  uint64_t msa_max_bytes_ = (uint64_t)1 << 30;
+  MsaStore msa_store_;                 // of the last run (next(): since the list's start)
+  std::vector<MsaBlock> msa_blocks_;
+  void keep_msa(const RunState& rs, const Batch& b, MsaStore& st) const;
+  awv_msa_stats build_msa(awv_engine* e);
   int split_bonus_ = 0;  // with_split (0: off)
   int64_t split_min_score_ = 1;
   bool drops_pairs() const { return bounded() || clip() || split(); }  // consumers that keep a slot per pair compact what was delivered
@@ -482,6 +528,7 @@ class AllPairParallelIterator {
   const Coverage& last_coverage() const { return it_.last_coverage(); }
   const std::vector<awv_variant>& last_variants() const { return it_.last_variants(); }
   const std::vector<awv_lift_row>& last_liftover() const { return it_.last_liftover(); }
+  const std::vector<MsaBlock>& last_msa() const { return it_.last_msa(); }
   const RunReport& last_report() const { return it_.last_report(); }
  private:
   friend class AllPairIterator;

@@ -23,15 +23,17 @@ thread_local RunReport g_report;
 thread_local Coverage g_coverage;  // and its last_coverage(), for awh_last_coverage
 thread_local std::vector<awv_variant> g_variants;  // and its last_variants(), for awh_last_variants
 thread_local std::vector<awv_lift_row> g_liftover;  // and its last_liftover(), for awh_last_liftover
+thread_local std::vector<MsaBlock> g_msa;           // and its last_msa(), for awh_last_msa_block
 template <typename It>
 void keep(const It& it) {
   g_report = it.last_report();
   g_coverage = it.last_coverage();
   g_variants = it.last_variants();
   g_liftover = it.last_liftover();
+  g_msa = it.last_msa();
 }
 // The options of the calling thread's NEXT alignment hook: awh_set_bounds, awh_set_clip, awh_set_split, awh_set_normalize and
-// awh_set_device_cigar, awh_set_cs, awh_set_coverage, awh_set_variants, awh_set_liftover
+// awh_set_device_cigar, awh_set_cs, awh_set_coverage, awh_set_variants, awh_set_liftover, awh_set_msa
 // leave them here; the hook takes them (they hold for that one call) and starts the counters they go with afresh.
 thread_local RunOptions g_next;
 RunOptions take_run_options() {
@@ -49,6 +51,8 @@ RunOptions take_run_options() {
   g_variants.clear();
   g_report.lift_stats = awv_lift_stats{};
   g_liftover.clear();
+  g_report.msa_stats = awv_msa_stats{};
+  g_msa.clear();
   return o;
 }
 // the hooks' orientation code on an iterator: 0 forward, 1 WFA, 2 mash, 3 WFA by two full alignments per pair
@@ -765,6 +769,43 @@ int awh_last_liftover(awv_lift_row** rows, size_t* n_rows, awv_lift_stats* stats
     return -1;
   }
   if (*n_rows) memcpy(*rows, g_liftover.data(), *n_rows * sizeof(awv_lift_row));
+  return 0;
+}
+// ---- target-anchored multiple alignments ----
+// The calling thread's NEXT alignment hook runs with_msa(targets[0 .. n), max_bytes) (n == 0: every sequence; max_bytes == 0: the
+// default bound) when on != 0; the hooks after it run without again.
+void awh_set_msa(int on, const int* targets, size_t n, uint64_t max_bytes) {
+  g_next.msa = on != 0;
+  g_next.msa_targets.assign(targets, targets + (targets && on ? n : 0));
+  g_next.msa_max_bytes = max_bytes ? max_bytes : (uint64_t)1 << 30;
+}
+// last_msa() of the calling thread's last alignment hook: the number of blocks and the call's awv_msa_stats
+size_t awh_last_msa(awv_msa_stats* stats) {
+  *stats = g_report.msa_stats;
+  return g_msa.size();
+}
+// Block j of it: *names is a malloc'd copy of the rows' names, one per line, *bytes one of the rows * width bytes (awh_free both).
+// Returns -1 when j is out of range or memory runs out.
+int awh_last_msa_block(size_t j, int* t_idx, int64_t* rows, int64_t* width, char** names, size_t* names_len, uint8_t** bytes) {
+  if (j >= g_msa.size()) return -1;
+  const MsaBlock& b = g_msa[j];
+  std::string all;
+  for (const std::string& nm : b.names) all += nm + "\n";
+  *t_idx = b.t_idx;
+  *rows = b.rows;
+  *width = b.width;
+  *names_len = all.size();
+  *names = (char*)malloc(std::max<size_t>(all.size(), 1));
+  *bytes = (uint8_t*)malloc(std::max<size_t>(b.bytes.size(), 1));
+  if (!*names || !*bytes) {
+    free(*names);
+    free(*bytes);
+    *names = nullptr;
+    *bytes = nullptr;
+    return -1;
+  }
+  memcpy(*names, all.data(), all.size());
+  if (!b.bytes.empty()) memcpy(*bytes, b.bytes.data(), b.bytes.size());
   return 0;
 }
 // last_encode_stats() of the calling thread's last alignment hook: {pairs, runs, text_bytes, columns} and the summed kernel time

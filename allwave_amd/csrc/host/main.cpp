@@ -71,6 +71,10 @@ struct Args {
   std::string liftover_out;   // --liftover-out FILE: one line per lifted region and alignment
   bool have_liftover = false, have_liftover_out = false, have_liftover_from = false;
   int liftover_from = AWV_LIFT_FROM_TARGET;  // --liftover-from target|query|both
+  std::string msa;                        // --msa FILE: the targets' multiple alignments as aligned FASTA ({}: the target's index)
+  std::vector<std::string> msa_targets;   // --msa-target NAME (repeatable), or all
+  unsigned long long msa_max_bytes = 1ull << 30;  // --msa-max-bytes N
+  bool have_msa = false, have_msa_max_bytes = false;
 };
 
 [[noreturn]] void die(const std::string& m, int code = 2) {
@@ -281,6 +285,23 @@ int main(int argc, char** argv) {
         die("--variants-min-count expects a count N >= 1");
       a.have_variants_min_count = true;
     }
+    else if (k == "--msa") {
+      a.msa = val();
+      if (a.msa.empty()) die("--msa expects a file name");
+      a.have_msa = true;
+    }
+    else if (k == "--msa-target") {
+      const std::string v = val();
+      if (v.empty()) die("--msa-target expects a sequence name, or all");
+      a.msa_targets.push_back(v);
+    }
+    else if (k == "--msa-max-bytes") {
+      char* end = nullptr;
+      const std::string v = val();
+      a.msa_max_bytes = strtoull(v.c_str(), &end, 10);
+      if (v.empty() || *end != '\0' || v[0] == '-' || a.msa_max_bytes < 1) die("--msa-max-bytes expects a number of bytes N >= 1");
+      a.have_msa_max_bytes = true;
+    }
     else if (k == "--liftover") {
       a.liftover = val();
       if (a.liftover.empty()) die("--liftover expects a BED file name");
@@ -345,12 +366,14 @@ int main(int argc, char** argv) {
                    "                   [--split A --split-min-score S] [--normalize left|right] [--device-cigar] [--cs short|long]\n"
                    "                   [--coverage FILE [--coverage-of target|query|both]] [--variants FILE [--variants-min-count N]]\n"
                    "                   [--liftover BED --liftover-out FILE [--liftover-from target|query|both]]\n"
+                   "                   [--msa FILE --msa-target NAME|all ... [--msa-max-bytes N]]\n"
                    "       allwave_hip -i in.fa --check-paf FILE [-s scores | -x ANI] [--check-optimal] [--partial] [--device N]\n"
                    "       allwave_hip -i in.fa --align-paf FILE [-s scores | -x ANI] [-o out.paf] [--verify] [--score-only] [--device N | --devices LIST]\n"
                    "                   [--max-align-penalty N] [--max-divergence D] [--clip A [--clip-min-score S]]\n"
                    "                   [--split A --split-min-score S] [--normalize left|right] [--device-cigar] [--cs short|long]\n"
                    "                   [--coverage FILE [--coverage-of target|query|both]] [--variants FILE [--variants-min-count N]]\n"
                    "                   [--liftover BED --liftover-out FILE [--liftover-from target|query|both]]\n"
+                   "                   [--msa FILE --msa-target NAME|all ... [--msa-max-bytes N]]\n"
                    "  --verify         check every alignment on the device before it is written (columns, counts, penalty); the summary\n"
                    "                   line gains `verified N pairs, F failed, K ms`, failures go to stderr, exit status 4 if any\n"
                    "  --check-paf FILE align nothing: check every line of FILE (12 columns + cg:Z:) against in.fa on the device; one line\n"
@@ -417,6 +440,17 @@ int main(int argc, char** argv) {
                    "                   with --align-paf; not with --score-only, --check-paf or --mash-matrix; under --shard every process writes\n"
                    "                   its own shard's file; the summary line gains `lifted Q queries, R rows, U unaligned, K ms`\n"
                    "  --liftover-from target|query|both  the side of an alignment a region is looked for on (default target)\n"
+                   "  --msa FILE       lay every aligned sequence out against the targets named by --msa-target NAME (repeatable, names as in\n"
+                   "                   in.fa; or all) as target-anchored multiple alignments, on the device, from the run's alignments: aligned\n"
+                   "                   FASTA, `>` and the target's name for the first row, then `>qname/qbeg-qend` and the strand sign per\n"
+                   "                   alignment of the target (the query interval on the forward strand), sorted by query, strand and\n"
+                   "                   position; insertions are left-justified; with more than one target FILE must contain {}, which is\n"
+                   "                   replaced by the target's 0-based index in in.fa; what counts is what is written, as for --coverage; the\n"
+                   "                   PAF is byte-identical; also with --align-paf; not with --score-only, --check-paf, --mash-matrix or\n"
+                   "                   --device-cigar; under --shard every process writes its own shard's file; the summary line gains\n"
+                   "                   `msa T targets, R rows, B bytes, K ms`\n"
+                   "  --msa-max-bytes N  the bound of the kept op bytes and of the blocks, each (default 2^30): beyond it the run's alignments\n"
+                   "                   are written as always and the run then fails, naming the bound and the size needed\n"
                    "  --plan-device N  plan on device N: --mash-matrix, the -p pair list and mash orientation (the same output as\n"
                    "                   the host planner; with --shard every rank plans the whole list on its own plan device)\n";
       return 0;
@@ -458,6 +492,13 @@ int main(int argc, char** argv) {
   if (a.have_variants && a.score_only) die("the argument '--variants' cannot be used with '--score-only'");
   if (a.have_variants && a.have_check_paf) die("the argument '--variants' cannot be used with '--check-paf'");
   if (a.have_variants && a.mash_matrix) die("the argument '--variants' cannot be used with '--mash-matrix'");
+  if (a.have_msa && a.msa_targets.empty()) die("the argument '--msa' requires '--msa-target'");
+  if (!a.have_msa && !a.msa_targets.empty()) die("the argument '--msa-target' requires '--msa'");
+  if (a.have_msa_max_bytes && !a.have_msa) die("the argument '--msa-max-bytes' requires '--msa'");
+  if (a.have_msa && a.score_only) die("the argument '--msa' cannot be used with '--score-only'");
+  if (a.have_msa && a.have_check_paf) die("the argument '--msa' cannot be used with '--check-paf'");
+  if (a.have_msa && a.mash_matrix) die("the argument '--msa' cannot be used with '--mash-matrix'");
+  if (a.have_msa && a.device_cigar) die("the argument '--msa' cannot be used with '--device-cigar' (the sink then carries text, not op bytes)");
   if (a.have_liftover != a.have_liftover_out) die("the arguments '--liftover' and '--liftover-out' require each other");
   if (a.have_liftover_from && !a.have_liftover) die("the argument '--liftover-from' requires '--liftover'");
   if (a.have_liftover && a.score_only) die("the argument '--liftover' cannot be used with '--score-only'");
@@ -602,6 +643,20 @@ int main(int argc, char** argv) {
       for (const BedLine& l : bed.bad) std::cerr << l.line << ' ' << l.cls << "\n";
       it.with_liftover(bed.regions, a.liftover_from);
     }
+    std::vector<int> msa_idx;  // the targets' indices in in.fa, in the order they were named
+    if (a.have_msa) {
+      const bool all = a.msa_targets.size() == 1 && a.msa_targets[0] == "all";
+      for (size_t i = 0; all && i < sequences.size(); ++i) msa_idx.push_back((int)i);
+      for (size_t k = 0; !all && k < a.msa_targets.size(); ++k) {
+        size_t i = 0;
+        while (i < sequences.size() && sequences[i].id != a.msa_targets[k]) ++i;
+        if (i == sequences.size()) die("--msa-target: no sequence named '" + a.msa_targets[k] + "' in " + a.input);
+        if (std::find(msa_idx.begin(), msa_idx.end(), (int)i) != msa_idx.end()) die("--msa-target: '" + a.msa_targets[k] + "' is named twice");
+        msa_idx.push_back((int)i);
+      }
+      if (msa_idx.size() > 1 && a.msa.find("{}") == std::string::npos) die("--msa: with more than one target the file name must contain {}");
+      it.with_msa(msa_idx, a.msa_max_bytes);
+    }
     if (a.forward_only) it.with_orientation(Orientation::ForwardOnly);
     it.with_full_wfa_orientation(a.wfa_orientation_full);
     it.with_devices(devices);
@@ -741,6 +796,24 @@ int main(int argc, char** argv) {
       lout.close();
       if (lout.fail()) die("write error on the liftover output", 1);
     }
+    uint64_t msa_rows = 0;
+    if (a.have_msa) {  // one aligned FASTA per target
+      for (const MsaBlock& b : it.last_msa()) {
+        std::string name = a.msa;
+        const size_t at = name.find("{}");
+        if (at != std::string::npos) name.replace(at, 2, std::to_string(b.t_idx));
+        std::ofstream mout(name, std::ios::binary);
+        if (!mout) die("cannot create " + name, 1);
+        for (int64_t r = 0; r < b.rows; ++r) {
+          mout << '>' << b.names[(size_t)r] << '\n';
+          mout.write((const char*)b.bytes.data() + r * b.width, (std::streamsize)b.width);
+          mout << '\n';
+        }
+        mout.close();
+        if (mout.fail()) die("write error on the msa output", 1);
+        msa_rows += (uint64_t)b.rows;
+      }
+    }
     const BoundStats bs = it.last_bound_stats();
     const size_t above = (size_t)(bs.above_penalty + bs.above_divergence);  // (pairs above a bound get no line)
     const ClipStats cs = it.last_clip_stats();
@@ -749,7 +822,7 @@ int main(int argc, char** argv) {
     if (done + above + unclipped + (size_t)ss.pairs != total + (size_t)ss.segments) die("internal: wrote " + std::to_string(done) + " of " + std::to_string(total) + (a.score_only ? " pairs" : " PAF lines"), 1);
     if (!a.no_progress) {
       const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      char buf[768];
+      char buf[896];
       int w = snprintf(buf, sizeof(buf), "[%.1fs] %zu/%zu (100.0%%) %.1f alignments/sec", secs, done, total, done / std::max(secs, 1e-9));
       if (a.have_align_paf && w > 0 && (size_t)w < sizeof(buf)) w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", %zu bad lines", bad_lines);
       if (bounded && w > 0 && (size_t)w < sizeof(buf)) w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", %zu pairs above the bound", above);
@@ -788,6 +861,11 @@ int main(int argc, char** argv) {
         const awv_lift_stats ls = it.last_report().lift_stats;
         w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", lifted %llu queries, %zu rows, %llu unaligned, %.2f ms", (unsigned long long)ls.queries,
                       it.last_liftover().size(), (unsigned long long)ls.unaligned, ls.kernel_ms);
+      }
+      if (a.have_msa && w > 0 && (size_t)w < sizeof(buf)) {
+        const awv_msa_stats ms = it.last_report().msa_stats;
+        w += snprintf(buf + w, sizeof(buf) - (size_t)w, ", msa %zu targets, %llu rows, %llu bytes, %.2f ms", it.last_msa().size(), (unsigned long long)msa_rows,
+                      (unsigned long long)ms.bytes, ms.width_ms + ms.scan_ms + ms.emit_ms);
       }
       if (a.verify && w > 0 && (size_t)w < sizeof(buf)) {
         const awv_verify_stats vs = it.last_verify_stats();

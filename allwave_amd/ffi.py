@@ -109,6 +109,12 @@ AWV_LF_UNALIGNED = 4
 AWV_LF_OUTSIDE = 5
 AWV_LIFT_ROW_REVCOMP = 1
 AWV_LIFT_ROW_FROM_QUERY = 2
+#: awv_msa_item.code
+AWV_MS_OK = 0
+AWV_MS_SKIPPED = 1
+AWV_MS_BAD_OP = 2
+AWV_MS_LENGTHS = 3
+AWV_MS_NOT_CHOSEN = 4
 #: sketch kinds of device pair planning (awv_sketch)
 AWV_SK_CANONICAL = 0
 AWV_SK_FORWARD = 1
@@ -134,7 +140,8 @@ EXPORTS = ("awv_abi_version", "awv_last_error", "awv_engine_create", "awv_engine
            "awv_engine_coverage_stats",
            "awv_variants_one_host", "awv_variants_fold_host", "awv_engine_variants_begin", "awv_engine_variants_end", "awv_engine_variants_read", "awv_engine_variants_stats",
            "awv_variants_cigars", "awv_variants_ranges", "awv_variants_fold",
-           "awv_lift_one_host", "awv_lift_cigars", "awv_lift_ranges", "awv_engine_lift_begin", "awv_engine_lift_read", "awv_engine_lift_stats")
+           "awv_lift_one_host", "awv_lift_cigars", "awv_lift_ranges", "awv_engine_lift_begin", "awv_engine_lift_read", "awv_engine_lift_stats",
+           "awv_msa_host", "awv_msa_cigars", "awv_msa_ranges", "awv_engine_msa_stats")
 
 
 class EngineConfig(C.Structure):
@@ -211,6 +218,11 @@ class LiftStats(C.Structure):
                 ("skipped", C.c_uint64), ("bad_op", C.c_uint64), ("lengths", C.c_uint64), ("unaligned", C.c_uint64), ("outside", C.c_uint64)]
 
 
+class MsaStats(C.Structure):
+    _fields_ = [("width_ms", C.c_double), ("scan_ms", C.c_double), ("emit_ms", C.c_double), ("items", C.c_uint64), ("failed", C.c_uint64),
+                ("columns", C.c_uint64), ("runs", C.c_uint64), ("bases", C.c_uint64), ("bytes", C.c_uint64)]
+
+
 PAIR_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4")])
 #: awv_range_pair: the query interval on the query's forward strand (PAF convention), also with q_revcomp
 RANGE_DTYPE = np.dtype([("q_idx", "<i4"), ("t_idx", "<i4"), ("q_revcomp", "<i4"), ("q_beg", "<i4"), ("q_end", "<i4"),
@@ -253,6 +265,11 @@ REGION_DTYPE = np.dtype([("seq", "<i4"), ("beg", "<i4"), ("end", "<i4")])
 LIFT_ROW_DTYPE = np.dtype([("region", "<i4"), ("q_idx", "<i4"), ("t_idx", "<i4"), ("flags", "<i4"), ("src_beg", "<i4"), ("src_end", "<i4"),
                            ("dst_beg", "<i4"), ("dst_end", "<i4"), ("num_matches", "<i4"), ("num_mismatches", "<i4"), ("num_ins", "<i4"),
                            ("num_del", "<i4")])
+#: awv_msa_item: the code, the index into the call's targets (-1: not chosen), the row within the block (0: none), the bases placed
+#: and the first and one-past-last non-gap column of the row
+MSA_ITEM_DTYPE = np.dtype([("code", "<i4"), ("target", "<i4"), ("row", "<i4"), ("bases", "<u4"), ("col_beg", "<i8"), ("col_end", "<i8")])
+#: awv_msa_target: the block of target t_idx is rows x width bytes at byte `off` of the arena
+MSA_TARGET_DTYPE = np.dtype([("t_idx", "<i4"), ("rows", "<i4"), ("width", "<i8"), ("off", "<u8")])
 #: awv_score_result
 SCORE_DTYPE = np.dtype([("status", "<i4"), ("penalty", "<i4")])
 
@@ -373,6 +390,12 @@ def load():
         L.awv_engine_lift_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64]
         L.awv_engine_lift_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.awv_engine_lift_stats.argtypes = [C.c_void_p, C.POINTER(LiftStats)]
+        L.awv_msa_host.argtypes = [C.c_char_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.awv_msa_cigars.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.awv_msa_ranges.argtypes = L.awv_msa_cigars.argtypes
+        L.awv_engine_msa_stats.argtypes = [C.c_void_p, C.POINTER(MsaStats)]
         _LIB = L
     return _LIB
 
@@ -863,6 +886,57 @@ class Engine:
         """awv_engine_coverage_stats: kernel_ms, items, failed, columns, boundaries, reads since coverage_begin."""
         return self._stats("awv_engine_coverage_stats", CovStats)
 
+    def msa_cigars(self, pairs, results, arena, targets, slices=None, want_blocks=True, cap=None):
+        """awv_msa_cigars: the target-anchored multiple alignments of `targets` (distinct sequence indices) from caller-supplied
+        records (a RESULT_DTYPE array whose cigar_off / cigar_len point into `arena`, bytes or a uint8 array), on the device.
+        slices: as for cs_cigars.  Returns (items, tgts, buf, msa_bytes): a MSA_ITEM_DTYPE array, a MSA_TARGET_DTYPE array, the
+        arena of blocks as a uint8 array (target j's block is buf[off : off + rows * width].reshape(rows, width)) and its size.
+        want_blocks=False is the measuring call (buf == NULL, cap == 0) and gives buf None; cap: the buffer's size (default:
+        measured first, so that it fits) -- a buffer smaller than msa_bytes is left untouched and comes back filled with 0xff."""
+        return self._msa("awv_msa_cigars", self._pair_array(pairs), results, arena, targets, slices, want_blocks, cap)
+
+    def msa_ranges(self, ranges, results, arena, targets, slices=None, want_blocks=True, cap=None):
+        """msa_cigars on interval pairs (awv_msa_ranges)."""
+        return self._msa("awv_msa_ranges", self._range_array(ranges), results, arena, targets, slices, want_blocks, cap)
+
+    def _msa(self, fn, pairs, results, arena, targets, slices, want_blocks, cap):
+        results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
+        if results.shape != (len(pairs),):
+            raise ValueError("results: need one record per pair")
+        sl = self._slice_array(slices, len(results))
+        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
+        nbytes = int(arena.size)
+        if nbytes == 0:
+            arena = np.zeros(1, dtype=np.uint8)
+        tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+        nt = len(tg)
+        if nt == 0:
+            tg = np.zeros(1, dtype=np.int32)
+        items = np.zeros(max(len(results), 1), dtype=MSA_ITEM_DTYPE)[:len(results)]
+        tgts = np.zeros(max(nt, 1), dtype=MSA_TARGET_DTYPE)[:nt]
+        size = C.c_uint64(0)
+
+        def call(buf, cap_):
+            rc = getattr(load(), fn)(self._h, pairs.ctypes.data, len(pairs), results.ctypes.data, arena.ctypes.data, nbytes,
+                                     None if sl is None else sl.ctypes.data, tg.ctypes.data, nt, items.ctypes.data, tgts.ctypes.data,
+                                     None if buf is None else buf.ctypes.data, cap_, C.byref(size))
+            if rc != AWV_OK:
+                raise EngineError(rc, fn)
+
+        if not want_blocks:
+            call(None, 0)
+            return items, tgts, None, int(size.value)
+        if cap is None:
+            call(None, 0)
+            cap = int(size.value)
+        buf = np.full(max(int(cap), 1), 0xff, dtype=np.uint8)
+        call(buf, int(cap))
+        return items, tgts, buf[:int(cap)], int(size.value)
+
+    def msa_stats(self):
+        """awv_engine_msa_stats: width_ms, scan_ms, emit_ms, items, failed, columns, runs, bases, bytes of the last msa_* call."""
+        return self._stats("awv_engine_msa_stats", MsaStats)
+
     def lift_cigars(self, pairs, results, arena, queries, slices=None):
         """awv_lift_cigars: lifts intervals through caller-supplied records (a RESULT_DTYPE array whose cigar_off / cigar_len point
         into `arena`, bytes or a uint8 array), on the device.  queries: a LIFT_QUERY_DTYPE array, or (record, from, beg, end) rows
@@ -1256,6 +1330,46 @@ def coverage_one_host(roles, q_revcomp, qlen, tlen, cigar, span=None, slice=None
     if rc != AWV_OK:
         raise EngineError(rc, "awv_coverage_one_host")
     return out[0], q_tracks, t_tracks
+
+
+def msa_host(text, items, want_block=True):
+    """awv_msa_host: one target's multiple alignment on the host (needs no device; the yardstick the kernels are tested
+    against).  text: the target's bytes; items: (pattern, ops, span, slice) per item -- pattern the aligned copy of the query (its
+    reverse complement for a q_revcomp pair), ops the op bytes (None: a record that is not completed), span None (the whole of
+    both sequences) or (pb, pe, tb, te), slice None or (col_beg, col_end, q_skip, t_skip).  Returns (ins, width, codes, block):
+    the widths of the len + 1 slots, W, the items' codes and the block as a 2-D uint8 array (None with want_block=False)."""
+    text = bytes(text)
+    n = len(items)
+    pats = [bytes(it[0]) for it in items]
+    ops = [None if it[1] is None else bytes(it[1]) for it in items]
+    parr = (C.c_char_p * max(n, 1))(*pats)
+    carr = (C.c_char_p * max(n, 1))(*[o if o is not None else b"" for o in ops])
+    plens = np.array([len(p) for p in pats] + [0], dtype=np.int32)
+    clens = np.array([-1 if o is None else len(o) for o in ops] + [0], dtype=np.int64)
+    rects = np.zeros((max(n, 1), 4), dtype=np.int32)
+    any_slice = any(it[3] is not None for it in items)
+    sl = np.zeros(max(n, 1), dtype=CS_SLICE_DTYPE)
+    for k, it in enumerate(items):
+        rects[k] = (0, len(pats[k]), 0, len(text)) if it[2] is None else tuple(int(v) for v in it[2])
+        sl[k] = (0, max(int(clens[k]), 0), 0, 0) if it[3] is None else tuple(int(v) for v in it[3])
+    ins = np.zeros(len(text) + 1, dtype=np.uint32)
+    codes = np.zeros(max(n, 1), dtype=np.int32)
+    width, size = C.c_int64(0), C.c_uint64(0)
+
+    def call(block, cap):
+        rc = load().awv_msa_host(text, len(text), n, C.cast(parr, C.c_void_p), plens.ctypes.data, rects.ctypes.data, C.cast(carr, C.c_void_p),
+                                 clens.ctypes.data, sl.ctypes.data if any_slice else None, ins.ctypes.data, C.byref(width), codes.ctypes.data,
+                                 None if block is None else block.ctypes.data, cap, C.byref(size))
+        if rc != AWV_OK:
+            raise EngineError(rc, "awv_msa_host")
+
+    call(None, 0)
+    if not want_block:
+        return ins, int(width.value), codes[:n], None
+    block = np.zeros(max(int(size.value), 1), dtype=np.uint8)
+    call(block, int(size.value))
+    rows = int(size.value) // int(width.value) if width.value else 1 + int((codes[:n] == AWV_MS_OK).sum())
+    return ins, int(width.value), codes[:n], block[:int(size.value)].reshape(rows, int(width.value))
 
 
 def lift_one_host(from_, q_revcomp, qlen, tlen, cigar, beg, end, span=None, slice=None):

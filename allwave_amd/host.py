@@ -160,11 +160,11 @@ def _check_split(split, split_min_score, clip):
 
 
 def _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split=None, split_min_score=None, normalize=None, device_cigar=False,
-                     cs=None, coverage=None, variants=False, liftover=None, liftover_from=None, ids=None):
+                     cs=None, coverage=None, variants=False, liftover=None, liftover_from=None, ids=None, msa_targets=None, msa_max_bytes=None):
     """The bounds, the clipping, the splitting, the normalization, the device-side CIGAR text and the cs tag of this thread's next
     alignment hook, which takes them: every argument is checked before anything is set, and all settings are always written
     (awh_set_bounds, awh_set_clip, awh_set_split, awh_set_normalize, awh_set_device_cigar, awh_set_cs, awh_set_coverage,
-    awh_set_variants, awh_set_liftover)."""
+    awh_set_variants, awh_set_liftover, awh_set_msa)."""
     bonus, least = _check_clip(clip, clip_min_score)
     sbonus, sleast = _check_split(split, split_min_score, clip)
     mode = ffi.norm_mode(normalize)
@@ -177,6 +177,7 @@ def _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split=No
     if roles is None:
         raise ValueError("coverage: None, 'target', 'query' or 'both', not %r" % (coverage,))
     regions, side = _check_liftover(liftover, liftover_from, ids)
+    msa_on, targets, bound = _check_msa(msa_targets, msa_max_bytes, ids, device_cigar)
     _set_bounds(max_penalty, max_divergence)
     load().awh_set_clip(bonus, C.c_int64(least))
     load().awh_set_split(sbonus, C.c_int64(sleast))
@@ -187,6 +188,75 @@ def _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split=No
     load().awh_set_variants(int(bool(variants)))
     load().awh_set_liftover.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
     load().awh_set_liftover(regions.ctypes.data if len(regions) else None, len(regions), int(side))
+    load().awh_set_msa.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_uint64]
+    load().awh_set_msa(int(msa_on), targets.ctypes.data if len(targets) else None, len(targets), int(bound))
+
+
+def _check_msa(msa_targets, msa_max_bytes, ids, device_cigar):
+    """(on, an int32 array of target indices -- empty: every sequence --, the bound or 0 for the default) of msa_targets= /
+    msa_max_bytes=: msa_targets is None (off), "all" or an empty list (every sequence), or a list of indices or ids."""
+    if msa_targets is None:
+        if msa_max_bytes is not None:
+            raise ValueError("msa_max_bytes requires msa_targets")
+        return False, np.zeros(0, dtype=np.int32), 0
+    if device_cigar:
+        raise ValueError("msa_targets: not together with device_cigar (the sink then carries text, not op bytes)")
+    if msa_max_bytes is not None and (isinstance(msa_max_bytes, bool) or int(msa_max_bytes) < 1):
+        raise ValueError("msa_max_bytes: a positive number of bytes, not %r" % (msa_max_bytes,))
+    if isinstance(msa_targets, str) and msa_targets == "all":
+        msa_targets = []
+    if isinstance(msa_targets, (str, bytes)):
+        raise ValueError("msa_targets: 'all' or a list of indices or ids, not %r" % (msa_targets,))
+    where = {name: k for k, name in enumerate(ids or [])}
+    out = []
+    for t in msa_targets:
+        if isinstance(t, (str, bytes)):
+            if t not in where:
+                raise ValueError("msa_targets: no sequence named %r" % (t,))
+            t = where[t]
+        t = int(t)
+        if t < 0 or t >= len(ids or []) or t in out:
+            raise ValueError("msa_targets: index %d is out of range or named twice" % t)
+        out.append(t)
+    return True, np.array(out, dtype=np.int32), 0 if msa_max_bytes is None else int(msa_max_bytes)
+
+
+def last_msa():
+    """last_msa() of this thread's last all_pairs_paf / all_pairs_paf_count / iterate / align_ranges call with msa_targets=...:
+    {target index: (names, block)} -- block the target's multiple alignment as a 2-D uint8 array (rows x width, '-' for a gap), names
+    the rows' names: the target's id for row 0, `qname/qbeg-qend` and the strand sign for an item's row.  Built in one device call
+    after the run, so several devices give the one-engine blocks exactly.  Empty for a call without msa_targets.
+    last_msa.stats is not kept: last_msa_stats() returns the call's ffi.MsaStats."""
+    return _last_msa()[0]
+
+
+def last_msa_stats():
+    """The ffi.MsaStats of the awv_msa_ranges call behind last_msa()."""
+    return _last_msa(blocks=False)[1]
+
+
+def _last_msa(blocks=True):
+    L = load()
+    st = ffi.MsaStats()
+    L.awh_last_msa.argtypes = [C.c_void_p]
+    L.awh_last_msa.restype = C.c_size_t
+    L.awh_last_msa_block.argtypes = [C.c_size_t] + [C.c_void_p] * 6
+    n = L.awh_last_msa(C.byref(st))
+    out = {}
+    for j in range(n if blocks else 0):
+        t, rows, width, nlen = C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_size_t(0)
+        names, data = C.c_void_p(), C.c_void_p()
+        if L.awh_last_msa_block(j, C.byref(t), C.byref(rows), C.byref(width), C.byref(names), C.byref(nlen), C.byref(data)) != 0:
+            raise HostError("out of memory")
+        try:
+            nm = C.string_at(names, nlen.value).decode().split("\n")[:-1]
+            nbytes = rows.value * width.value
+            blk = np.frombuffer(C.string_at(data, nbytes), dtype=np.uint8).copy() if nbytes else np.zeros(0, dtype=np.uint8)
+        finally:
+            L.awh_free(names)
+            L.awh_free(data)
+        out[t.value] = (nm, blk.reshape(rows.value, width.value))
+    return out, st
 
 
 def _check_liftover(liftover, liftover_from, ids):
@@ -416,7 +486,7 @@ def check_paf(ids, seqs, paf_text, scores, optimal=False, device=0, partial=Fals
 
 
 def align_ranges(ids, seqs, ranges, scores, devices=None, device=0, verify=False, max_penalty=None, max_divergence=None, clip=None,
-                 clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False, liftover=None, liftover_from=None):
+                 clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False, liftover=None, liftover_from=None, msa_targets=None, msa_max_bytes=None):
     """allwave::align_ranges + alignment_to_paf: the interval pairs `ranges` -- rows (query_idx, target_idx, is_reverse,
     query_start, query_end, target_start, target_end), the query interval on its forward strand -- aligned globally on the
     engines `devices` names (default: [device]).  Returns the PAF lines in list order: columns 3-4 and 8-9 are the interval,
@@ -432,7 +502,7 @@ def align_ranges(ids, seqs, ranges, scores, devices=None, device=0, verify=False
     n = C.c_size_t(0)
     e = _err()
     rbuf = r if len(r) else np.zeros((1, 7), dtype=np.int64)
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants, liftover, liftover_from, ids)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants, liftover, liftover_from, ids, msa_targets, msa_max_bytes)
     rc = load().awh_align_ranges_paf(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p), scores.encode(),
                                      rbuf.ctypes.data_as(C.c_void_p), C.c_size_t(len(r)), devs, nd, int(bool(verify)), C.byref(out),
                                      C.byref(n), e, _CAP)
@@ -503,7 +573,7 @@ def _device_args(devices):
 
 def all_pairs_paf(ids, seqs, scores, orientation="wfa", exclude_self=True, device=0, sparsification="none", devices=None,
                   min_batch_pairs=0, orientation_full=False, verify=False, max_penalty=None, max_divergence=None, clip=None,
-                  clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False, liftover=None, liftover_from=None):
+                  clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False, liftover=None, liftover_from=None, msa_targets=None, msa_max_bytes=None):
     """AllPairIterator + alignment_to_paf per record; returns the list of PAF lines.  `devices`: a list of ordinals (one
     engine per entry, repeats allowed) to spread the pair list over in this call; None = [device].
     `min_batch_pairs` > 0 overrides the smallest batch of a multi-device run (default 16,384).  orientation_full: WFA
@@ -535,14 +605,16 @@ def all_pairs_paf(ids, seqs, scores, orientation="wfa", exclude_self=True, devic
     those of the run without it, and last_coverage() returns the two tracks.  variants=True: the run also tallies, on the device, the
     per-site allele table of what it aligned (with_variants; last_variants() returns it).  liftover= ((seq, beg, end) rows, seq an
     index or an id, forward strand) with liftover_from= ("target", the default, "query" or "both"): the run also lifts those regions,
-    on the device, through what it aligned (with_liftover; last_liftover() returns the rows).  iterate and align_ranges take it too.  all_pairs_paf_count and
+    on the device, through what it aligned (with_liftover; last_liftover() returns the rows).  msa_targets= ("all", or a list of
+    indices or ids) with msa_max_bytes= (default 2^30): the run also lays every sequence out against each target as a multiple
+    alignment, on the device, after the run (with_msa; last_msa() returns {target: (names, block)}); not with device_cigar.  iterate and align_ranges take them too.  all_pairs_paf_count and
     align_ranges take it too; iterate accepts and ignores it."""
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if devices is None else devices)
     out = C.c_void_p()
     n = C.c_size_t(0)
     e = _err()
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants, liftover, liftover_from, ids)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants, liftover, liftover_from, ids, msa_targets, msa_max_bytes)
     rc = load().awh_all_pairs_paf_devices(len(ids), cids, data.ctypes.data_as(C.c_void_p), offs.ctypes.data_as(C.c_void_p),
                                           scores.encode(), sparsification.encode(), _orient_code(orientation, orientation_full), int(exclude_self),
                                           devs, nd, C.c_int64(int(min_batch_pairs)), int(bool(verify)), None, C.byref(out), C.byref(n), e, _CAP)
@@ -559,7 +631,7 @@ ITER_MODES = {"for_each": 0, "next": 1, "par_for_each": 2, "par_collect": 3, "pr
 def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientation="forward", threads=4, chunk=0,
             resparsify=False, fail_at=-1, device=0, devices=None, min_batch_pairs=0, shard=None, with_stats=False,
             orientation_full=False, verify=False, max_penalty=None, max_divergence=None, clip=None, clip_min_score=None, split=None,
-            split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False, liftover=None, liftover_from=None):
+            split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False, liftover=None, liftover_from=None, msa_targets=None, msa_max_bytes=None):
     """Every consumer of the pair list (iterator.rs:101-253, lib.rs:57-68) through one hook; returns the PAF lines in arrival
     order.  `fail_at` >= 0 makes the callback throw at that record: HostError carries its message.
     `devices`: a list of ordinals (one engine per entry, repeats allowed) to spread the pair list over; None = [device].
@@ -574,7 +646,7 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
     hands out alignment records with their op bytes."""
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if devices is None else devices)
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants, liftover, liftover_from, ids)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants, liftover, liftover_from, ids, msa_targets, msa_max_bytes)
     st = (ffi.Stats * nd)()
     rank, world = shard if shard is not None else (0, 1)
     out = C.c_void_p()
@@ -599,7 +671,7 @@ def iterate(ids, seqs, scores, mode="for_each", sparsification="none", orientati
 
 def all_pairs_paf_count(ids, seqs, scores, orientation="forward", device=0, format_threads=8, devices=None, min_batch_pairs=0,
                         sparsification=None, checksum=False, verify=False, max_penalty=None, max_divergence=None, clip=None,
-                        clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False, liftover=None, liftover_from=None):
+                        clip_min_score=None, split=None, split_min_score=None, normalize=None, device_cigar=False, cs=None, coverage=None, variants=False, liftover=None, liftover_from=None, msa_targets=None, msa_max_bytes=None):
     """End to end: upload -> align -> D2H -> format into a counting sink. Returns (bytes, lines, secs, ffi.Stats) for
     every pair on `device`.  `devices`: a list of ordinals (one engine per entry, repeats allowed); the Stats are then
     summed over the slots, and the result gains a fifth element, each slot's Stats (last_slot_stats()), and a sixth, the
@@ -611,7 +683,7 @@ def all_pairs_paf_count(ids, seqs, scores, orientation="forward", device=0, form
     one = devices is None
     cids, data, offs = _seq_args(ids, seqs)
     devs, nd = _device_args([device] if one else devices)
-    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants, liftover, liftover_from, ids)
+    _set_run_options(max_penalty, max_divergence, clip, clip_min_score, split, split_min_score, normalize, device_cigar, cs, coverage, variants, liftover, liftover_from, ids, msa_targets, msa_max_bytes)
     nb, nl, secs, ck = C.c_uint64(0), C.c_uint64(0), C.c_double(0), C.c_uint64(0)
     st = ffi.Stats()
     slot = (ffi.Stats * nd)()

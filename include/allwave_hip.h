@@ -1017,6 +1017,90 @@ int awv_engine_lift_begin(awv_engine* e, const awv_region* regions, int64_t n_re
 int awv_engine_lift_read(awv_engine* e, awv_lift_row* rows, uint64_t cap, uint64_t* n_rows /* required */);
 /* Since the last awv_engine_lift_begin of this engine (since its creation before one); awv_lift_cigars / _ranges add to it. */
 int awv_engine_lift_stats(const awv_engine* e, awv_lift_stats* out);
+
+/* ---- target-anchored multiple alignments on the device (csrc/msa.hip, csrc/msa_device.hpp) ------------------------------------
+ * Every sequence laid out against one of them: a star multiple alignment anchored on a target, as a dense block of bytes.  The
+ * rule is __host__ __device__ in msa_device.hpp.  A pure function of the items and the two sequences: no penalties are involved,
+ * and nothing depends on the order of the items apart from the order of the rows.
+ * An item is exactly the coverage pass's item: an op string c[0..n) over M X I D ('I' consumes the text only, 'D' the pattern
+ * only, 'M' and 'X' both) with its rectangle (pattern [pb, pe) against text [tb, te), the pattern the reverse-complement copy for
+ * a q_revcomp pair) and the skips of a slice.  Column k sits at pattern position x = pb + q_skip + #(ops other than 'I' before k)
+ * and at text position y = tb + t_skip + #(ops other than 'D' before k).
+ * The codes are coverage's, and AWV_MS_NOT_CHOSEN: the item's t_idx is not among the call's targets; such an item is not walked,
+ * whatever its record says.  An item is all or nothing: one whose code is not AWV_MS_OK widens no slot and gets no row, whatever
+ * bytes precede the bad one.
+ * Widths.  A chosen target s of L bases has L + 1 slots: slot p is the gap before base p, slot L the one behind the last base.
+ * ins[s][p] is the maximum, over the AWV_MS_OK items with t_idx == s, of the number of the item's 'D' columns at text position p.
+ * In one string those columns are one run (any other op advances y); a slice that cuts a run counts only its own columns.
+ * Columns.  col[s][p] = p + the sum of ins[s][r] for r <= p, in 64 bits.  Base p (p < L) sits in column col[p], slot p's insertion
+ * columns are [col[p] - ins[p], col[p]), and the block is W = col[L] columns wide.
+ * Rows.  A target's block is rows x W bytes, row-major, filled with '-'.  Row 0 is the target: upper(text[p]) at col[p].  Then one
+ * row per AWV_MS_OK item of that target, in the call's item order: an 'M' or 'X' column at (x, y) puts upper(pattern[x]) at
+ * col[y]; a 'D' column that is the j-th (from 0) of its run within the item, at slot y, puts upper(pattern[x]) at
+ * col[y] - ins[y] + j (insertions are left-justified and not aligned among themselves); an 'I' column leaves the fill, and so does
+ * everything outside the item's target span.
+ * Known answer (minimap2's cs example): text CGATCGATAAATAGAGTAGGAATAGCA, pattern CGATCGAATAGAGTAGGTCGAATTGCA, ops
+ * 6M 3I 10M 3D 4M 1X 3M, alone on its target: W = 30, row 0 CGATCGATAAATAGAGTAG---GAATAGCA, row 1 CGATCG---AATAGAGTAGGTCGAATTGCA.
+ * A string or slice holds at most 2^30 columns (AWV_ERR_ARG otherwise, before anything is launched). */
+#define AWV_MS_OK 0         /* the item widened its target's slots and has a row */
+#define AWV_MS_SKIPPED 1    /* status is not AWV_ST_COMPLETED */
+#define AWV_MS_BAD_OP 2     /* a byte outside MXID */
+#define AWV_MS_LENGTHS 3    /* q_skip + the pattern bases the string consumes > the pattern interval, or the same for the text */
+#define AWV_MS_NOT_CHOSEN 4 /* t_idx is not among the call's targets: the item was not walked */
+typedef struct {
+  int32_t code;             /* AWV_MS_*; every field below but `target` is 0 unless it is AWV_MS_OK */
+  int32_t target;           /* index into the call's targets; -1 for AWV_MS_NOT_CHOSEN */
+  int32_t row;              /* the item's row within its target's block (>= 1); 0 when it has none */
+  uint32_t bases;           /* bases placed: the item's 'M', 'X' and 'D' columns */
+  int64_t col_beg, col_end; /* the first and one past the last non-gap column of the row; 0, 0 for a row without a base */
+} awv_msa_item; /* 32 bytes */
+typedef struct {
+  int32_t t_idx;  /* the target's sequence index */
+  int32_t rows;   /* 1 + its AWV_MS_OK items */
+  int64_t width;  /* W */
+  uint64_t off;   /* the block begins at this byte of the arena and holds rows * width bytes */
+} awv_msa_target; /* 24 bytes */
+typedef struct {
+  double width_ms;  /* HIP-event time of the width launches of the last awv_msa_* call */
+  double scan_ms;   /* ... of the segmented scan and the items' column intervals */
+  double emit_ms;   /* ... of the fill, the targets' rows and the emit launches (0 for a measuring call) */
+  uint64_t items;   /* items of the call, the ones not chosen included */
+  uint64_t failed;  /* of them: AWV_MS_BAD_OP and AWV_MS_LENGTHS */
+  uint64_t columns; /* op bytes walked by the width launches, each once however often it is read */
+  uint64_t runs;    /* 'D' runs of the AWV_MS_OK items: one atomic maximum each */
+  uint64_t bases;   /* bases placed in the items' rows (counted by the width launches: also in a measuring call) */
+  uint64_t bytes;   /* *msa_bytes */
+} awv_msa_stats; /* 72 bytes */
+
+/* The contract alone, on the host (needs no device): the serial per-column walk of ONE target's items, the yardstick the kernels
+ * are tested against, not a fallback -- no product path calls it.  text[0..tlen): the target.  Item i: patterns[i][0..plens[i]) is
+ * the aligned copy of its query (the reverse complement for a q_revcomp pair), rects[4 i .. 4 i + 4) = pb, pe, tb, te in pattern /
+ * text coordinates, cigars[i][0..cigar_lens[i]) the op string (cigar_lens[i] < 0: a record that is not completed,
+ * AWV_MS_SKIPPED), slices (nullable) n entries.  Writes ins[0..tlen], *width, codes[0..n) and *block_bytes = rows * width always;
+ * block[0..*block_bytes) only when *block_bytes <= cap. */
+int awv_msa_host(const uint8_t* text, int32_t tlen, int64_t n, const uint8_t* const* patterns, const int32_t* plens, const int32_t* rects,
+                 const uint8_t* const* cigars, const int64_t* cigar_lens, const awv_cs_slice* slices /* nullable */, uint32_t* ins,
+                 int64_t* width, int32_t* codes, uint8_t* block /* nullable when cap == 0 */, uint64_t cap, uint64_t* block_bytes);
+/* Builds the blocks of targets[0..nt) (distinct sequence indices) from records and op bytes the caller supplies, on the device:
+ * results[i] claims that cigar_arena[results[i].cigar_off, + cigar_len) aligns pairs[i] (ranges[i]).  Needs a sequence set
+ * (AWV_ERR_STATE without one).  items[i] answers item i; tgts[j] describes targets[j]; the blocks lie in one arena in `targets`
+ * order, tgts[0].off = 0 and tgts[j + 1].off = tgts[j].off + rows[j] * width[j].  *msa_bytes is the arena's size, always filled;
+ * buf[0..*msa_bytes) is written only when *msa_bytes <= cap, all of it or nothing, so buf == NULL with cap == 0 is the measuring
+ * call (items and tgts are filled all the same).  A target without items gets a block of one row and width L.
+ * Three steps on the engine's stream: a width kernel (a record pass: every item walked twice in one launch, the second walk one
+ * no-return atomic maximum per 'D' run), a segmented scan of the slots into 64-bit columns, and -- when the arena fits -- a fill
+ * with '-', the targets' rows and an emit kernel (the same walk, one byte store per base).  Staged and pieced as
+ * awv_coverage_cigars does under awv_engine_config.max_arena_bytes; the pieces go up once for the widths and once for the rows.
+ * slices (nullable): n entries.  AWV_ERR_ARG, before anything is launched, for what awv_cs_cigars refuses, a target index
+ * outside the set and a repeated target. */
+int awv_msa_cigars(awv_engine* e, const awv_pair* pairs, int64_t n, const awv_result* results, const uint8_t* cigar_arena,
+                   uint64_t arena_bytes, const awv_cs_slice* slices /* nullable */, const int32_t* targets, int64_t nt,
+                   awv_msa_item* items, awv_msa_target* tgts, uint8_t* buf, uint64_t cap, uint64_t* msa_bytes /* required */);
+int awv_msa_ranges(awv_engine* e, const awv_range_pair* ranges, int64_t n, const awv_result* results, const uint8_t* cigar_arena,
+                   uint64_t arena_bytes, const awv_cs_slice* slices /* nullable */, const int32_t* targets, int64_t nt,
+                   awv_msa_item* items, awv_msa_target* tgts, uint8_t* buf, uint64_t cap, uint64_t* msa_bytes /* required */);
+/* Of the engine's last awv_msa_cigars / awv_msa_ranges call (zeros before one). */
+int awv_engine_msa_stats(const awv_engine* e, awv_msa_stats* out);
 /* ---- device pair planning (csrc/planner.hip) -------------------------------------------------------------------------
  * Integer work over the engine's resident sequence set, on its device and stream; results equal the host planner's
  * (csrc/host/planner.cpp) bit for bit.  Every call but awv_keep_pairs needs a sequence set (else AWV_ERR_STATE); a new set
