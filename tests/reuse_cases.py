@@ -711,3 +711,204 @@ def normalize_want(ffi, direction, recs, tail=b""):
             ops, out[k] = ffi.normalize_one_host(direction, r.pattern, r.text, r.ops)
             arena += ops
     return bytes(arena + tail), out
+
+
+# ---- the ninth and tenth record passes: lift.hip, msa.hip ---------------------------------------------------------------------------
+# They take records in the scan kernels' order too.  msa.hip's width and emit kernels carry the bases consumed (cq, ct), one past the
+# last column so far that is no 'D' (run0) and whether the column before the chunk is a 'D' (prev_d); lift.hip carries the four op
+# counts of the chunks before (tm, tx, ti, td), the answer behind the last aligned column so far (last_a) and the probe cursors
+# (pp), and leaves five arrays in LDS.  The lists above serve both as they are.  What they trap here:
+#   gap_tail -> gap_head (main-D, pass-D: 'D')   run0: B's leading 'D' run would begin at A's last column that is no 'D' -- it comes
+#                                                out too narrow, or not at all; (main-I, pass-I: 'I') last_a: a query that ends inside
+#                                                B's leading run of text-only columns would end at A's last aligned column
+#   all_gaps -> plain                            prev_d: A ends in 'D', B begins with another op -- where B begins on a 16-byte
+#                                                boundary (lift_msa_inputs puts it there) a carried bit counts a run that is none
+#   any record with columns -> any with a base   cq / ct, the four counts: B would be walked from where A ended
+#   the record with 200 queries -> the next      pp: B's probes would be behind the cursor and never answered
+# lift.hip dispatches only records that have a query: its processing order at one workgroup is the list order restricted to them.
+
+FROM_TARGET, FROM_QUERY = 1, 2   # AWV_LIFT_FROM_*
+LIFT_SIDES = (FROM_TARGET, FROM_QUERY)
+HEAVY = (130, 70)                # the queries of a record that has many: from the target, from the query
+
+
+def lift_msa_inputs(recs):
+    """(sequences, pairs [n, 3], RESULT_DTYPE records, arena) of a scan list for lift.hip and msa.hip: record k is the pair (2 k,
+    2 k + 1), the strings back to back -- but a record that begins with an op other than 'D' behind one that ends in 'D' begins on
+    the next 16-byte boundary, where alone msa.hip's carried prev_d can reach its first column (the bytes between hold 'D')."""
+    from allwave_amd import ffi
+    out = np.zeros(len(recs), dtype=ffi.RESULT_DTYPE)
+    arena = bytearray()
+    seqs, pairs = [], []
+    for k, r in enumerate(recs):
+        if k and recs[k - 1].ops[-1:] == b"D" and r.ops and r.ops[:1] != b"D":
+            arena += b"D" * (-len(arena) % 16)
+        out[k]["status"], out[k]["cigar_off"], out[k]["cigar_len"] = r.status, len(arena), len(r.ops)
+        arena += r.ops
+        seqs += [V.revcomp(r.pattern) if r.rc else r.pattern, r.text]
+        pairs.append((2 * k, 2 * k + 1, r.rc))
+    return seqs, np.asarray(pairs, dtype=np.int32).reshape(-1, 3), out, bytes(arena)
+
+
+def has_query(k):
+    """Every third record gets no query, and lift.hip does not dispatch it (the second of three: the key-0 list's SKIPPED records
+    are every third from index 2 on and keep theirs)."""
+    return k % 3 != 1
+
+
+def sound(r):
+    """Whether both passes walk the record as a sound one (awvcs::whole_code's rule) where it is the pair of its own sequences."""
+    return (r.status == 0 and all(b in b"MXID" for b in r.ops) and len(r.ops) - r.ops.count(b"I") <= len(r.pattern)
+            and len(r.ops) - r.ops.count(b"D") <= len(r.text))
+
+
+def heavy_records(recs):
+    """The records that get HEAVY queries: the first one, and the last one with a query that has two chunks wherever it begins
+    (1,040 columns or more) and a sound record as the next one with a query -- which has fewer columns.  A list without such a
+    record has the first one only."""
+    ks = [k for k in range(len(recs)) if has_query(k)]
+    two = [a for a, b in zip(ks, ks[1:]) if recs[a].status == 0 and len(recs[a].ops) >= CHUNK + 16 and sound(recs[b])]
+    return sorted({0, two[-1]} if two else {0})
+
+
+def lift_side(r, frm, qlen, tlen, span):
+    """(s0, used, length, gap) of a record seen from one side, in the item's own coordinates: where its source bases begin, how
+    many its string consumes, the source sequence's length, and the gap op that consumes the source alone."""
+    pb, pe, tb, te = span
+    if frm == FROM_TARGET:
+        return tb, len(r.ops) - r.ops.count(b"D"), tlen, b"I"
+    return pb, len(r.ops) - r.ops.count(b"I"), qlen, b"D"
+
+
+def lift_queries(recs, seqs, seed, geometry=None):
+    """[(record, from, beg, end)], deterministic, for a list whose record k is the pair (2 k, 2 k + 1) of `seqs` (geometry:
+    range_geometry's, for a list of ranges), intervals on the source's forward strand.  From both sides of every record that gets
+    any: the first base, the first few, the last base, the whole source interval, an interval that ends inside the leading run of
+    source-only columns and one that begins inside the trailing one (where the record has them), and two random ones.  Every third
+    record gets NO query: lift.hip does not dispatch it, so the processing order at one workgroup is the list order restricted to
+    the records with a query.  heavy_records get HEAVY more: 100 from the target with both ends at source offsets 100 .. 900
+    (one chunk answers 200 probes, 64 a step) or, in a record of more than two chunks, 1,100 .. 1,800 (the second chunk does),
+    the others anywhere -- some stay pending into the chunks behind.  A record without a base on a side gets no query there."""
+    rng = random.Random("reuse/lift/%s" % seed)
+    heavy = heavy_records(recs)
+    out = []
+    for k, r in enumerate(recs):
+        if not has_query(k):
+            continue
+        qlen, tlen = len(seqs[2 * k]), len(seqs[2 * k + 1])
+        span = (0, qlen, 0, tlen) if geometry is None else geometry[k][1]
+        for frm in LIFT_SIDES:
+            s0, u, length, gap = lift_side(r, frm, qlen, tlen, span)
+            head, tail = len(r.ops) - len(r.ops.lstrip(gap)), len(r.ops) - len(r.ops.rstrip(gap))
+            item = [(s0, s0 + 1), (s0, s0 + min(4, max(u, 1))), (s0 + u - 1, s0 + u), (s0, s0 + u)]
+            if head:
+                item.append((s0, s0 + (head + 1) // 2))
+            if tail:
+                item.append((s0 + u - (tail + 1) // 2, s0 + u + 2))
+            for _ in range(2):
+                b = rng.randint(max(s0 - 3, 0), s0 + u + 2)
+                item.append((b, b + rng.choice([1, 2, 5, 40, 3000])))
+            if k in heavy:
+                lo, hi = (1100, 1800) if len(r.ops) > 2 * CHUNK + 16 else (min(100, u // 3), min(900, u))
+                for j in range(HEAVY[frm - 1]):
+                    if frm == FROM_TARGET and j < 100:
+                        b = s0 + rng.randint(lo, hi)
+                        item.append((b, min(b + rng.randint(1, 60), s0 + max(hi, 1))))
+                    else:
+                        b = rng.randint(max(s0 - 3, 0), s0 + u + 2)
+                        item.append((b, b + rng.choice([1, 7, 300, 3000])))
+            for a, b in item:
+                a, b = max(a, 0), min(b, length)
+                if a < b:
+                    out.append((k, frm) + ((qlen - b, qlen - a) if frm == FROM_QUERY and r.rc else (a, b)))
+    return out
+
+
+def lift_want(ffi, recs, queries, seqs, geometry=None):
+    """The LIFT_DTYPE array of a list's queries: ffi.lift_one_host, the yardstick, one call per query (a record that is not
+    completed: SKIPPED)."""
+    out = np.zeros(len(queries), dtype=ffi.LIFT_DTYPE)
+    for j, (k, frm, beg, end) in enumerate(queries):
+        r = recs[k]
+        if r.status != 0:
+            out[j]["code"] = ffi.AWV_LF_SKIPPED
+            continue
+        out[j] = ffi.lift_one_host(frm, r.rc, len(seqs[2 * k]), len(seqs[2 * k + 1]), r.ops, beg, end, span=None if geometry is None else geometry[k][1])
+    return out
+
+
+def lift_walked(recs, queries):
+    """(records, columns) a launch walks: the completed records that have a query, each once."""
+    done = sorted({q[0] for q in queries if recs[q[0]].status == 0})
+    return len(done), sum(len(recs[k].ops) for k in done)
+
+
+def msa_layout(recs, seqs, shared, seed=0):
+    """(sequences, pairs [n, 3], targets) of a list in one of two layouts.  own targets: record k is the pair (2 k, 2 k + 1) and the
+    targets are all odd sequences -- every block has one item.  shared targets: three sequences S are appended to the set, each as
+    long as the list's longest op string or longer, and record k is the pair (2 k, S[k mod 3]): a string may be shorter than its
+    rectangle, so every well-formed string whose own query holds it stays sound, about a third of the list's items lie on each
+    target from slot 0 on, the atomic maximum has contention and an item's row depends on widths other waves decided."""
+    n = len(recs)
+    if not shared:
+        return list(seqs), np.asarray([(2 * k, 2 * k + 1, r.rc) for k, r in enumerate(recs)], dtype=np.int32).reshape(-1, 3), list(range(1, 2 * n, 2))
+    rng = random.Random("reuse/msa/shared/%s" % seed)
+    longest = max([len(r.ops) for r in recs] + [1])
+    extra = [rand_seq(rng, longest + d) for d in (0, 7, 31)]
+    pairs = np.asarray([(2 * k, 2 * n + k % 3, r.rc) for k, r in enumerate(recs)], dtype=np.int32).reshape(-1, 3)
+    return list(seqs) + extra, pairs, [2 * n, 2 * n + 1, 2 * n + 2]
+
+
+def msa_items(recs, pairs, geometry=None):
+    """The records as msa_cases.msa_of's items."""
+    return [(int(p[0]), int(p[1]), int(p[2]), r.ops, None if geometry is None else geometry[k][1], None, r.status) for k, (r, p) in enumerate(zip(recs, pairs))]
+
+
+def msa_want(seqs, targets, items):
+    """msa_cases.msa_of's answer to one call, with what the GPU tests compare byte for byte: `item_array` (MSA_ITEM_DTYPE),
+    `target_array` (MSA_TARGET_DTYPE) and `arena`, the blocks one behind the other."""
+    import msa_cases as M
+    from allwave_amd import ffi
+    w = M.msa_of(seqs, list(targets), items)
+    w["item_array"] = np.array(w["items"], dtype=ffi.MSA_ITEM_DTYPE) if items else np.zeros(0, dtype=ffi.MSA_ITEM_DTYPE)
+    w["target_array"] = np.array(w["targets"], dtype=ffi.MSA_TARGET_DTYPE) if targets else np.zeros(0, dtype=ffi.MSA_TARGET_DTYPE)
+    w["arena"] = M.arena_of(w["blocks"])
+    return w
+
+
+def msa_host_of(ffi, seqs, s, items):
+    """ffi.msa_host, the C yardstick, on the items of target s: (ins, width, codes, block)."""
+    mine = [(V.revcomp(seqs[q]) if rev else bytes(seqs[q]), None if status != 0 else ops, span, sl) for q, t, rev, ops, span, sl, status in items if t == s]
+    return ffi.msa_host(seqs[s], mine)
+
+
+# the launch geometry of msa.hip's scan and target kernels: tiles of 1,024 slots, trips of 64 x 256 = 16,384 bases
+
+GEOMETRY_LENS = (1023, 1024, 2047, 2048, 16500)  # len + 1 = 1,024, 1,025, 2,048, 2,049; one target longer than a trip
+GEOMETRY_SLOTS = (0, 1023, 1024, 2047, 2048, 16383, 16384)
+
+
+def geometry_slots(length):
+    """The slots of a target of that length that get 'D' runs: those of GEOMETRY_SLOTS that exist, len - 1 and len."""
+    return sorted({s for s in GEOMETRY_SLOTS if s <= length} | {length - 1, length})
+
+
+def geometry_set(seed=0):
+    """(sequences, ranges [n, 7], op strings, msa_of's items, targets) for awv_msa_ranges: five targets of GEOMETRY_LENS bases
+    (sequences 0 .. 4) and four queries of 96 bases; at every slot of geometry_slots two items (a third at slot 0) with 'D' runs of
+    different widths, M^a D^w M^b of a few dozen columns placed by tb = slot - a, every other one on the reverse strand."""
+    rng = random.Random("reuse/msa/geometry/%s" % seed)
+    seqs = [rand_seq(rng, n) for n in GEOMETRY_LENS] + [rand_seq(rng, 96) for _ in range(4)]
+    ranges, strings, items = [], [], []
+    for t, length in enumerate(GEOMETRY_LENS):
+        for i, slot in enumerate(geometry_slots(length)):
+            for w in ((1 + i % 3, 4 + i % 4) + ((9,) if slot == 0 else ())):
+                a, b = min(slot, rng.randint(3, 20)), min(length - slot, rng.randint(1, 20))
+                ops = b"M" * a + b"D" * w + b"M" * b
+                q, rev = len(GEOMETRY_LENS) + len(items) % 4, len(items) % 2
+                qb = rng.randint(0, 96 - (a + w + b))
+                ranges.append((q, t, rev, qb, qb + a + w + b, slot - a, slot + b))
+                pb = 96 - (qb + a + w + b) if rev else qb
+                items.append((q, t, rev, ops, (pb, pb + a + w + b, slot - a, slot + b), None, 0))
+                strings.append(ops)
+    return seqs, np.asarray(ranges, dtype=np.int32), strings, items, list(range(len(GEOMETRY_LENS)))
