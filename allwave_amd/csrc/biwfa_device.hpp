@@ -126,8 +126,9 @@ enum { STAT_CELLS = 0, STAT_EXTEND, STAT_BREAKPOINTS, STAT_BASE, STAT_OVERLAP, S
        // breakpoints were not mirrors
        STAT_TWIN_UNITS = STAT_N, STAT_TWIN_SHARED, STAT_TWIN_SOLO, STAT_TWIN_NONMIRROR,
        // row reuse, added to KParams::stats by the search that took rows from the archive: the cell-steps of
-       // those rows (part of STAT_CELLS and STAT_MULTI_CELLS all the same), and the searches
-       STAT_REUSE_CELLS, STAT_REUSE_SEARCHES,
+       // those rows (part of STAT_CELLS and STAT_MULTI_CELLS all the same), and the searches -- of the two searches right below
+       // the top-level one; then the same two numbers for the searches further down
+       STAT_REUSE_CELLS, STAT_REUSE_SEARCHES, STAT_REUSE_DEEP_CELLS, STAT_REUSE_DEEP_SEARCHES,
        STAT_N_DEV };
 
 #ifdef AWV_PROF
@@ -196,7 +197,8 @@ struct KParams {
 };
 // Row archives (row_reuse.hpp).  KParams stays as it is -- a longer one would move the second kernel argument of
 // the range kernels -- so the launch's archive descriptor lies behind the counters, at KParams::stats[STAT_N_DEV ..]: the
-// arena (0: the launch keeps no archives), the bytes per workgroup slot, passes | T << 32, and the I/D rows per pass; a slot
+// arena (0: the launch keeps no archives), the bytes per workgroup slot, passes | T << 32, and the I/D rows per pass | who takes
+// (awvrr::LV_*) << 32; a slot
 // is laid out as awvrr::make_layout(passes, T, nid).  Only the one-wave kernels with 16-bit rows look at it.
 constexpr int RR_DESC_WORDS = 4;
 
@@ -208,6 +210,7 @@ struct Task { int pb, pe, tb, te, cb, ce, score_remaining, known; };  // known: 
 // Twin units: bits 8..9 of Task::cb say whose task it is, bits 16.. its depth below the top (only kept while shared).
 // TM_A = 0: an ordinary pair's tasks are encoded as ever.  A shared task's coordinates are in A's frame.
 constexpr int TM_A = 0, TM_B = 1, TM_SHARED = 2;
+static_assert(TM_A == awvrr::FR_A && TM_B == awvrr::FR_B && TM_SHARED == awvrr::FR_SHARED, "row_reuse.hpp names the same frames");
 // Twin units exist in the one-wave kernels with 16-bit rows only (config 2's): every other instantiation compiles the twin
 // branches out and keeps the code it had.
 constexpr bool TWIN_BUILD = WG == 64 && !WENC;
@@ -4542,6 +4545,7 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
   // (AWV_F_NO_ROW_REUSE, a bound, a score-only call, no room): every search then goes through find_breakpoint_fn as ever.
   const unsigned long long rr_mem = kp.stats[STAT_N_DEV], rr_stride = kp.stats[STAT_N_DEV + 1], rr_pt = kp.stats[STAT_N_DEV + 2];
   const int rr_passes = uni((int)(unsigned)rr_pt), rr_T = uni((int)(rr_pt >> 32)), rr_nid = uni((int)kp.stats[STAT_N_DEV + 3]);
+  const int rr_levels = uni((int)(kp.stats[STAT_N_DEV + 3] >> 32));  // awvrr::LV_ALL, or LV_ONE (AWV_F_ROW_REUSE_LEVEL1)
   int* const rr_hdr = rr_mem != 0 && rr_passes > 0 && pn.scope * NCOMP >= RRS_WORDS ? (int*)((char*)(uintptr_t)rr_mem + (size_t)blockIdx.x * (size_t)rr_stride) : nullptr;
   if (rr_hdr != nullptr && tid < awvrr::H_WORDS) rr_hdr[tid] = 0;
   for (;;) {
@@ -4714,13 +4718,17 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
               rc = uni(find_breakpoint_fn<P2, OffT>((unsigned)(uintptr_t)&sh, (unsigned)(uintptr_t)lds.ring_meta, (unsigned)(uintptr_t)lstats,
                                                     t.cb, t.ce, t.score_remaining, t.known, attempt));
           } else if (rr_hdr != nullptr) {
-            // the top-level search keeps its rows; a task it handed down, still in its frame (a shared unit's tasks are in A's),
-            // takes the forward rows when it is the left half and the reverse rows when it is the right half
+            // the top-level search keeps its rows; a task below it, still in its frame (a shared unit's tasks are in A's), takes
+            // the forward rows when it begins at the top-level search's origin in M -- the left half, and the left half of that,
+            // and so on down -- and the reverse rows when it ends at its end in M (awvrr::take_dir)
             int part = 0;
+            bool below_one = false;  // a taker below level 1: what it takes is counted apart as well
             if (t.score_remaining == INT_MAX) part = RR_RECORD;
-            else if (rr_bv >= 0 && (mode == rr_mode || (rr_mode == TM_SHARED && mode == TM_A))) {
-              if (t.pb == 0 && t.tb == 0 && t.pe == rr_bv && t.te == rr_bh && t.cb == C_M && t.ce == rr_comp) part = RR_FWD;
-              else if (t.pb == rr_bv && t.tb == rr_bh && t.pe == plenT && t.te == tlenT && t.cb == rr_comp && t.ce == C_M) part = RR_REV;
+            else if (rr_bv >= 0 && awvrr::frame_ok(rr_mode, mode)) {
+              bool level1;
+              const int tdir = awvrr::take_dir(awvrr::RootId{plenT, tlenT, rr_bv, rr_bh, rr_comp}, awvrr::TaskId{t.pb, t.pe, t.tb, t.te, t.cb, t.ce}, rr_levels, &level1);
+              part = tdir == 0 ? RR_FWD : tdir == 1 ? RR_REV : 0;
+              below_one = tdir >= 0 && !level1;
             }
             if (tid == 0) {  // the search's reuse state (RRS_*: Lds::firstk, untouched until phase 2); a recording search voids the archive
               const unsigned long long ra = (unsigned long long)(uintptr_t)rr_hdr;
@@ -4731,10 +4739,27 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
               lds.firstk[RRS_NID] = rr_nid;
               lds.firstk[RRS_PART] = part;
               if (part == RR_RECORD) rr_hdr[awvrr::H_NPASS] = 0;
+              // (kept in the archive's header, not in a register: nothing more stays alive across the search.  A mark in RRS_PART
+              // with rr_before_pass adding to H_DCELLS itself would be shorter, but rr_before_pass and the search functions keep
+              // the parent's code this way, and the dozen header accesses are per search, not per pass)
+              rr_hdr[awvrr::H_DNOW] = below_one ? 1 : 0;
+              if (below_one) {
+                *(unsigned long long*)(rr_hdr + awvrr::H_DMARK) = __hip_atomic_load((unsigned long long*)(rr_hdr + awvrr::H_RCELLS), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                rr_hdr[awvrr::H_DSMARK] = __hip_atomic_load(rr_hdr + awvrr::H_RSEARCH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              }
             }
             __syncthreads();
             rc = uni(find_breakpoint_fn_reuse<P2, OffT>((unsigned)(uintptr_t)&sh, (unsigned)(uintptr_t)lds.ring_meta, (unsigned)(uintptr_t)lstats,
                                                         t.cb, t.ce, t.score_remaining, t.known, attempt));
+            if (tid == 0 && __hip_atomic_load(rr_hdr + awvrr::H_DNOW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+              const unsigned long long now = __hip_atomic_load((unsigned long long*)(rr_hdr + awvrr::H_RCELLS), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              const unsigned long long mark = __hip_atomic_load((unsigned long long*)(rr_hdr + awvrr::H_DMARK), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              const unsigned long long dc = __hip_atomic_load((unsigned long long*)(rr_hdr + awvrr::H_DCELLS), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              *(unsigned long long*)(rr_hdr + awvrr::H_DCELLS) = dc + (now - mark);
+              const int snow = __hip_atomic_load(rr_hdr + awvrr::H_RSEARCH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              const int smark = __hip_atomic_load(rr_hdr + awvrr::H_DSMARK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              rr_hdr[awvrr::H_DSEARCH] = __hip_atomic_load(rr_hdr + awvrr::H_DSEARCH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + (snow - smark);
+            }
           } else {
             rc = uni(find_breakpoint_fn<P2, OffT>((unsigned)(uintptr_t)&sh, (unsigned)(uintptr_t)lds.ring_meta, (unsigned)(uintptr_t)lstats,
                                                   t.cb, t.ce, t.score_remaining, t.known, attempt));
@@ -4931,8 +4956,13 @@ __global__ __launch_bounds__(WG, WAVES_PER_SIMD) void biwfa_align_kernel(KParams
   if (rr_hdr != nullptr && tid == 0) {  // what this workgroup's searches took from its archive (rr_before_pass counts there)
     const unsigned long long rcells = __hip_atomic_load((unsigned long long*)(rr_hdr + awvrr::H_RCELLS), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int rsearch = __hip_atomic_load(rr_hdr + awvrr::H_RSEARCH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (rcells) atomicAdd(&kp.stats[STAT_REUSE_CELLS], rcells);
-    if (rsearch) atomicAdd(&kp.stats[STAT_REUSE_SEARCHES], (unsigned long long)rsearch);
+    // (the header counts every taker; the launch's counters keep the two level-1 searches and the ones below them apart)
+    const unsigned long long dcells = __hip_atomic_load((unsigned long long*)(rr_hdr + awvrr::H_DCELLS), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int dsearch = __hip_atomic_load(rr_hdr + awvrr::H_DSEARCH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (rcells - dcells) atomicAdd(&kp.stats[STAT_REUSE_CELLS], rcells - dcells);
+    if (rsearch - dsearch) atomicAdd(&kp.stats[STAT_REUSE_SEARCHES], (unsigned long long)(rsearch - dsearch));
+    if (dcells) atomicAdd(&kp.stats[STAT_REUSE_DEEP_CELLS], dcells);
+    if (dsearch) atomicAdd(&kp.stats[STAT_REUSE_DEEP_SEARCHES], (unsigned long long)dsearch);
   }
   } else {
   for (;;) {

@@ -667,7 +667,7 @@ int upload_group(AlignCall& c, const std::vector<awvb::Entry>& ge, const awvb::R
     st.hreuse[0] = (unsigned long long)(uintptr_t)e->reuse_mem.p;
     st.hreuse[1] = (unsigned long long)c.reuse.bytes();
     st.hreuse[2] = (unsigned long long)(unsigned)c.reuse.passes | ((unsigned long long)(unsigned)c.reuse.T << 32);
-    st.hreuse[3] = (unsigned long long)c.reuse.nid;
+    st.hreuse[3] = (unsigned long long)c.reuse.nid | ((unsigned long long)((e->cfg.flags & AWV_F_ROW_REUSE_LEVEL1) ? awvrr::LV_ONE : awvrr::LV_ALL) << 32);
     AWV_TRY(hipMemcpyAsync(e->d_counters.p + 1 + awv::STAT_N_DEV, st.hreuse, sizeof(st.hreuse), hipMemcpyHostToDevice, e->stream));
   }
   return timer_stop(c, c.h2d_ms);
@@ -1006,6 +1006,9 @@ void publish_stats(AlignCall& c) {
   // the cell-steps taken from a row archive (they are counted in cell_steps and multi_cell_steps too) and the searches that took some
   e->stats.prof[12] = stat_tot[STAT_REUSE_CELLS];
   e->stats.prof[13] = stat_tot[STAT_REUSE_SEARCHES];
+  // ([12] / [13]: by the two searches right below a top-level search; [10] / [11]: by the searches further down)
+  e->stats.prof[10] = stat_tot[STAT_REUSE_DEEP_CELLS];
+  e->stats.prof[11] = stat_tot[STAT_REUSE_DEEP_SEARCHES];
 #endif
 }
 

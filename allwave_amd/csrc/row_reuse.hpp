@@ -1,6 +1,7 @@
 // row_reuse.hpp -- the arithmetic of the row archive: a top-level breakpoint search keeps the rows of its
-// far-apart passes, and the two level-1 searches that run in its frame -- the left child's forward search, the right child's
-// reverse search -- take them back instead of computing them again.
+// far-apart passes, and the searches below it that run in its frame and share a corner with it -- the forward search of the
+// left child, of that child's left child and so on; the reverse search of the right child and of its chain of right children --
+// take them back instead of computing them again (take_dir).
 //
 // A child's search starts at the parent's origin over prefixes of the parent's sequences, so as long as a parent row lies
 // inside the child's box (no cell beyond the child's pattern or text end) the child computes that very row, component by
@@ -8,7 +9,7 @@
 // pass of the archive a pass of the child may take, and the column shift between the two searches' rows.
 //
 // Plain C++ with no HIP types, usable from host and device code, so that it can be built and tested on its own
-// (tests/row_reuse_driver.cpp).
+// (tests/row_reuse_driver.cpp, tests/row_reuse_levels_driver.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -28,6 +29,11 @@ enum { H_NPASS = 0,   // passes archived by the running top-level search (both d
        H_KMIN1 = 2,
        H_RCELLS = 4,  // words 4 and 5, one 64-bit count: cell-steps this workgroup took from its archive during the launch
        H_RSEARCH = 6, // searches that took some
+       H_DCELLS = 8,  // words 8 and 9, one 64-bit count: the part of H_RCELLS that searches below level 1 took
+       H_DMARK = 10,  // words 10 and 11: H_RCELLS as it stood when the running search below level 1 began
+       H_DNOW = 12,   // 1 while such a search runs
+       H_DSMARK = 13, // H_RSEARCH as it stood when it began
+       H_DSEARCH = 14, // the part of H_RSEARCH that is searches below level 1
        H_WORDS = 16 };
 // per pass and direction: 32-bit words of the pass table
 enum { P_MAXAK = 0,   // the pass's maximum antidiagonal 2h - k
@@ -86,6 +92,32 @@ AWVRR_HD int pass_for(const Layout& l, int npass, int sc, int Tc) {
   if (Tc != l.T || sc < 0 || sc % l.T != 0) return -1;
   const int p = sc / l.T;
   return p < npass && p < l.passes ? p : -1;
+}
+
+// Whose rows an archive holds, and who may take them.  A search's forward rows depend on its origin corner, its begin
+// component and the sequences from that corner on, and on nothing else; its reverse rows on its end corner and its end
+// component in the same way.  The top-level search runs from (0, 0) to (plen, tlen) with M at either end, so every task below
+// it, in its frame, that begins at (0, 0) in M computes the archive's forward rows for as long as they lie inside its box (the
+// left half, the left half's left half, ...), and every task that ends at (plen, tlen) in M its reverse rows.  Where the
+// task's other end lies decides only which half it is: the level-1 rule asks for it, the general rule does not.
+// Coordinates in the unit's frame; component 0 is M.
+struct RootId { int plen, tlen, bv, bh, bcomp; };  // the recorded search: its lengths, its breakpoint's pattern / text offset and component
+struct TaskId { int pb, pe, tb, te, cb, ce; };
+constexpr int LV_ALL = 0, LV_ONE = 1;  // who takes: every task with the archive's corner and component / the two level-1 tasks only
+// The frame rule.  A twin unit's shared search runs in A's frame and so do its shared tasks and A's own; B's own tasks (after a
+// four-way split, or when B runs alone) have pattern and text swapped.  A task takes only from an archive recorded in its own
+// frame: the same frame, or A's task under a shared top-level search.  (The kernel's TM_A / TM_B / TM_SHARED.)
+constexpr int FR_A = 0, FR_B = 1, FR_SHARED = 2;
+AWVRR_HD bool frame_ok(int root_frame, int task_frame) { return task_frame == root_frame || (root_frame == FR_SHARED && task_frame == FR_A); }
+// the direction `t` takes from the root's archive (0 forward, 1 reverse; -1: none); *level1: it is one of the root's two halves
+AWVRR_HD int take_dir(const RootId& r, const TaskId& t, int levels, bool* level1) {
+  const bool fwd = t.pb == 0 && t.tb == 0 && t.cb == 0, rev = t.pe == r.plen && t.te == r.tlen && t.ce == 0;
+  *level1 = true;
+  if (fwd && t.pe == r.bv && t.te == r.bh && t.ce == r.bcomp) return 0;
+  if (rev && t.pb == r.bv && t.tb == r.bh && t.cb == r.bcomp) return 1;
+  *level1 = false;
+  if (levels == LV_ONE) return -1;
+  return fwd ? 0 : rev ? 1 : -1;
 }
 
 // ---- host side: how many passes a launch's archives hold ----------------------------------------------------------------

@@ -34,6 +34,7 @@ AWV_F_NO_TWIN = 2048
 AWV_F_TWIN_TOP_ONLY = 4096
 AWV_F_NO_TWIN_BASE = 8192
 AWV_F_NO_ROW_REUSE = 16384
+AWV_F_ROW_REUSE_LEVEL1 = 32768
 #: WFA orientation (awv_orient_pairs / awv_orient_decide)
 AWV_ORIENT_FORWARD = 0
 AWV_ORIENT_REVERSE = 1

@@ -115,6 +115,9 @@ typedef struct {
 #define AWV_F_NO_ROW_REUSE 16384 /* tests and A/B measurements only: every breakpoint search computes all of its rows (default: in the one-wave kernels with
                                     16-bit rows the two searches below a pair's top-level search take the rows they share with it from an archive it keeps;
                                     awv_stats.prof[12] / prof[13] then count the cell-steps taken and the searches that took some) */
+#define AWV_F_ROW_REUSE_LEVEL1 32768 /* tests and A/B measurements only: only the two searches right below a pair's top-level search take rows from its
+                                        archive (default: every search below it that shares its origin or its end, however deep; awv_stats.prof[10] /
+                                        prof[11] count the cell-steps and the searches of those further down, prof[12] / prof[13] stay the two's own) */
 
 /* penalties as allwave passes them to lib_wfa2 (src/alignment.rs:263-289) */
 typedef struct {
@@ -171,7 +174,9 @@ typedef struct {
   /* shader-clock cycles summed over workgroups; only filled by the -DAWV_PROF diagnostic build:
    * [0] total, [1] step compute, [2] step barrier wait, [3] step finalize, [4] overlap search,
    * [5] base-case steps, [6] backtrace, [7] CIGAR emission, [8] number of fused step passes,
-   * [9..13] inside the step: row loads, DP arithmetic, extend, stores, reductions */
+   * [9..13] inside the step: row loads, DP arithmetic, extend, stores, reductions.
+   * The product build stamps nothing; there [12] / [13] are the cell-steps taken from row archives by the two searches right below
+   * a top-level search and those searches, [10] / [11] the same for the searches further down (AWV_F_ROW_REUSE_LEVEL1) */
   uint64_t prof[14];
   uint64_t restarts;          /* breakpoint searches run again step by step (multi-step passes met too early) */
   uint64_t multi_cell_steps;  /* cells computed by multi-step passes (I/D rows kept in registers) */
