@@ -50,8 +50,8 @@ HIP_UNITS = (("engine.hip", HIP_FLAGS), ("kernels_awv.hip", HIP_FLAGS_AWV), ("pl
              ("cs.hip", HIP_FLAGS), ("coverage.hip", HIP_FLAGS), ("variants.hip", HIP_FLAGS), ("variants_fold.hip", HIP_FLAGS),
              ("lift.hip", HIP_FLAGS), ("msa.hip", HIP_FLAGS))
 HIP_SOURCES = [os.path.join(CSRC, f) for f in ("engine.hip", "kernels_awv.hip", "kernels_awv.hpp", "biwfa_device.hpp", "range_span.hpp", "batch_plan.hpp", "twin_plan.hpp", "twin_base.hpp", "row_reuse.hpp", "planner.hip",
-                                               "planner_device.hpp", "orient.hip", "orient_device.hpp", "verify.hip", "verify_device.hpp", "clip.hip", "clip_device.hpp", "clip_scan.hpp", "split.hip", "split_device.hpp", "normalize.hip", "normalize_device.hpp", "encode.hip", "encode_device.hpp", "cs.hip", "cs_device.hpp", "coverage.hip", "coverage_device.hpp", "variants.hip", "variants_fold.hip", "variants_device.hpp", "lift.hip", "lift_device.hpp", "msa.hip", "msa_device.hpp", "batch_items.hpp", "seq_load.hpp", "wave_ops.hpp",
-                                               "host_errors.hpp", "record_pass.hpp", "record_pieces.hpp", "text_pass.hpp")] + [ABI_HEADER]
+                                               "planner_device.hpp", "orient.hip", "orient_device.hpp", "verify.hip", "verify_device.hpp", "clip.hip", "clip_device.hpp", "clip_scan.hpp", "split.hip", "split_device.hpp", "normalize.hip", "normalize_device.hpp", "encode.hip", "encode_device.hpp", "cs.hip", "cs_device.hpp", "cs_slice.hpp", "coverage.hip", "coverage_device.hpp", "variants.hip", "variants_fold.hip", "variants_device.hpp", "lift.hip", "lift_device.hpp", "msa.hip", "msa_device.hpp", "batch_items.hpp", "seq_load.hpp", "wave_ops.hpp",
+                                               "host_errors.hpp", "item_call.hpp", "record_pass.hpp", "record_pieces.hpp", "text_pass.hpp")] + [ABI_HEADER]
 
 
 def _host_sources():

@@ -1,12 +1,13 @@
-// batch_items.hpp -- which items one batch of an aligning call contributes to the passes that sum over alignments (coverage.hip; a pass
-// that tallies variants_device.hpp's table takes the same items), once: whole completed records; in a clipping call the clip's slice when it scores enough; in a splitting call
-// every segment; nothing of failed records or records above the bound.  Pure host code.
+// batch_items.hpp -- which items one batch of an aligning call contributes to the passes that sum over alignments (coverage.hip,
+// variants.hip, lift.hip), once: whole completed records; in a clipping call the clip's slice when it scores enough; in a
+// splitting call every segment; nothing of failed records or records above the bound.  Pure host code.
 #pragma once
 
 #include <cstdint>
 #include <vector>
 
-#include "cs_device.hpp"       // slice_ok, apply_slice, Span
+#include "cs_slice.hpp"        // slice_ok, apply_slice
+#include "item_call.hpp"       // whole_span, Span
 #include "planner_device.hpp"  // EngineView
 
 namespace awvw {
@@ -16,9 +17,6 @@ struct BatchItems {
   std::vector<awv_result> recs;  // their records with the slices applied
   std::vector<awvr::Span> spans; // and their rectangles
 };
-
-// the whole of both sequences: the rectangle of a pair call's record
-inline awvr::Span whole_span(const awp::EngineView& v, const awv_pair& p) { return awvr::Span{0, v.len_host[p.q_idx], 0, v.len_host[p.t_idx]}; }
 
 // `pairs`, `results`: the batch's n entries (host; the indices were checked by the aligning call); clips (nullable): the batch's
 // clips; seg_first / iout / sout (nullable): the call's split layout, seg_first and iout already offset to the batch; spans
@@ -33,7 +31,7 @@ inline void contributing_items(const awp::EngineView& v, const awv_pair* pairs, 
   const auto push = [&](int64_t i, const awv_cs_slice* sl) {
     out.pairs.push_back(pairs[i]);
     out.recs.push_back(results[i]);
-    out.spans.push_back(spans ? spans[i] : whole_span(v, pairs[i]));
+    out.spans.push_back(spans ? spans[i] : whole_span(v.len_host, pairs[i]));
     if (sl) awvcs::apply_slice(out.recs.back(), out.spans.back(), *sl);
   };
   for (int64_t i = 0; i < n; ++i) {

@@ -2,9 +2,10 @@
 // awv_coverage_cigars / awv_coverage_ranges and awv_coverage_one_host (include/allwave_hip.h).  What an item adds is
 // coverage_device.hpp; this file gets the kernels to the same numbers.
 //
-// A record pass (record_pass.hpp) with cs.hip's walk: one wave per item, persistent waves taking items (longest op string first)
-// from a cursor, a string in chunks of 64 lanes x 16 op bytes, one aligned 16-byte load per lane.  It is the first pass whose
-// output is indexed by sequence coordinate and summed over items, batches and calls, so it only ever adds.
+// A record pass (record_pass.hpp) with the op-mask walk of wave_ops.hpp (lane_op_masks): one wave per item, persistent waves
+// taking items (longest op string first) from a cursor, a string in chunks of 64 lanes x 16 op bytes, one aligned 16-byte load
+// per lane.  It is the first pass whose output is indexed by sequence coordinate and summed over items, batches and calls, so it
+// only ever adds.
 // The accumulators are difference arrays: per track and sequence len + 1 uint32 slots (slot len is the interval end), laid out by
 // cov_off.  A maximal run of aligned columns covers one interval of the target and one of the query: +1 at the interval's begin,
 // -1 at its end, modulo 2^32; likewise a maximal 'M' run in the matched track.  A lane sees a boundary where a column's class
@@ -24,8 +25,8 @@
 #include <string>
 #include <vector>
 
-#include "batch_items.hpp"  // contributing_items, whole_span
-#include "record_pass.hpp"  // RecordPass, open_pass, Buf, pack_piece, AWV_TRY
+#include "batch_items.hpp"  // contributing_items
+#include "record_pass.hpp"  // RecordPass, open_pass, open_active, each_piece, resolve_call, Buf, AWV_TRY
 
 namespace awvcov {
 
@@ -47,53 +48,30 @@ struct KParams {
 
 using awvw::CHUNK;
 using awvw::from_lower_lane;
-using awvw::LANE_BYTES;
-using awvw::u32x4;
 using awvw::wave_scan_add;
 using awvw::wave_sum_i64;
 
-// One lane's 16 op bytes of a chunk as masks over its columns.  Op byte c of the string is ops[sh + c].
-struct LaneOps {
-  unsigned valid;       // bit j: byte j is a column
-  unsigned m, a, i, d;  // ... an 'M'; an 'M' or 'X'; an 'I'; a 'D'
-  unsigned top;         // the classes of the lane's last byte (bit 0: aligned, bit 1: matched): what the next lane's first column follows
-  unsigned last;        // the classes of the lane's last column (0: it has none)
+// What coverage makes of a lane's masks (awvw::OpMasks): its two classes of columns, aligned ('M' or 'X') and matched ('M').
+struct LaneClasses {
+  unsigned a;     // bit j: column j is aligned (o.m: it is matched)
+  unsigned top;   // the classes of the lane's last byte (bit 0: aligned, bit 1: matched): what the next lane's first column follows
+  unsigned last;  // the classes of the lane's last column (0: it has none)
 };
-
-__device__ __forceinline__ LaneOps lane_ops(const uint8_t* ops, int sh, long long span, long long base, int lane) {
-  const long long b0 = base + lane * LANE_BYTES;
-  const int jlo = (int)min(max((long long)sh - b0, 0ll), (long long)LANE_BYTES);
-  const int jhi = (int)min(max(span - b0, 0ll), (long long)LANE_BYTES);
-  u32x4 w = u32x4{0u, 0u, 0u, 0u};
-  if (b0 < span) w = *(const u32x4*)(ops + b0);
-  LaneOps o;
-  o.valid = jhi > jlo ? ((1u << jhi) - 1u) & ~((1u << jlo) - 1u) : 0u;
-  unsigned m_m = 0, m_x = 0, m_i = 0, m_d = 0;
-#pragma unroll
-  for (int j = 0; j < LANE_BYTES; ++j) {
-    const unsigned op = (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
-    m_m |= (unsigned)(op == 'M') << j;
-    m_x |= (unsigned)(op == 'X') << j;
-    m_i |= (unsigned)(op == 'I') << j;
-    m_d |= (unsigned)(op == 'D') << j;
-  }
-  o.m = m_m & o.valid;
-  o.a = (m_m | m_x) & o.valid;
-  o.i = m_i & o.valid;
-  o.d = m_d & o.valid;
-  o.top = ((o.a >> 15) & 1u) | (((o.m >> 15) & 1u) << 1);
-  const int jl = max(jhi - 1, 0);
-  o.last = o.valid != 0 ? ((o.a >> jl) & 1u) | (((o.m >> jl) & 1u) << 1) : 0u;
-  return o;
+__device__ __forceinline__ LaneClasses classes_of(const awvw::OpMasks& o) {
+  LaneClasses c;
+  c.a = o.m | o.x;
+  c.top = ((c.a >> 15) & 1u) | (((o.m >> 15) & 1u) << 1);
+  const int jl = 31 - __clz((int)(o.valid | 1u));
+  c.last = o.valid != 0 ? ((c.a >> jl) & 1u) | (((o.m >> jl) & 1u) << 1) : 0u;
+  return c;
 }
 
 // the columns of a lane whose class bit differs from the one of the column before them (prev: before the lane's first byte)
 __device__ __forceinline__ unsigned boundaries_of(unsigned cls, unsigned prev, unsigned valid) { return (cls ^ ((cls << 1) | prev)) & valid; }
 
 // the classes of the chunk's last column: what the next chunk's first column follows, and what closes the string
-__device__ __forceinline__ unsigned chunk_last(const LaneOps& o, long long span, long long base) {
-  const int last_lane = (int)min(63ll, (span - 1 - base) >> 4);
-  return (unsigned)__builtin_amdgcn_readlane((int)o.last, last_lane);
+__device__ __forceinline__ unsigned chunk_last(const LaneClasses& c, long long span, long long base) {
+  return (unsigned)__builtin_amdgcn_readlane((int)c.last, awvw::last_column_lane(span, base));
 }
 
 // one add into a difference track: slot `slot` of sequence `seq`, never outside the sequence's own slots
@@ -136,13 +114,14 @@ __global__ __launch_bounds__(64) void awv_coverage_kernel(KParams kp) {
     unsigned prev = 0;  // the classes of the column before the chunk (uniform)
     unsigned long long l_cols = 0, l_pos = 0, l_rest = 0;  // aligned | matched << 32; pattern bases | text bases << 32; boundaries | bad bytes << 32
     for (long long base = 0; base < span; base += CHUNK) {
-      const LaneOps o = lane_ops(ops, sh, span, base, lane);
-      const unsigned pb = (unsigned)from_lower_lane((int)o.top, (int)prev);
-      const unsigned ba = boundaries_of(o.a, pb & 1u, o.valid), bm = boundaries_of(o.m, pb >> 1, o.valid);
-      l_cols += (unsigned long long)__popc(o.a) | ((unsigned long long)__popc(o.m) << 32);
+      const awvw::OpMasks o = awvw::lane_op_masks(ops, sh, span, base, lane);
+      const LaneClasses c = classes_of(o);
+      const unsigned pb = (unsigned)from_lower_lane((int)c.top, (int)prev);
+      const unsigned ba = boundaries_of(c.a, pb & 1u, o.valid), bm = boundaries_of(o.m, pb >> 1, o.valid);
+      l_cols += (unsigned long long)__popc(c.a) | ((unsigned long long)__popc(o.m) << 32);
       l_pos += (unsigned long long)__popc(o.valid & ~o.i) | ((unsigned long long)__popc(o.valid & ~o.d) << 32);
-      l_rest += (unsigned long long)(__popc(ba) + __popc(bm)) | ((unsigned long long)__popc(o.valid & ~(o.a | o.i | o.d)) << 32);
-      prev = chunk_last(o, span, base);
+      l_rest += (unsigned long long)(__popc(ba) + __popc(bm)) | ((unsigned long long)__popc(o.valid & ~(o.m | o.x | o.i | o.d)) << 32);
+      prev = chunk_last(c, span, base);
     }
     const unsigned long long cols = (unsigned long long)wave_sum_i64((long long)l_cols), pos = (unsigned long long)wave_sum_i64((long long)l_pos),
                              rest = (unsigned long long)wave_sum_i64((long long)l_rest);
@@ -161,25 +140,23 @@ __global__ __launch_bounds__(64) void awv_coverage_kernel(KParams kp) {
     int cq = 0, ct = 0;  // bases consumed before the chunk (uniform)
     prev = 0;
     for (long long base = 0; base < span; base += CHUNK) {
-      const LaneOps o = lane_ops(ops, sh, span, base, lane);
-      const unsigned pb = (unsigned)from_lower_lane((int)o.top, (int)prev);
-      const unsigned ba = boundaries_of(o.a, pb & 1u, o.valid), bm = boundaries_of(o.m, pb >> 1, o.valid);
+      const awvw::OpMasks o = awvw::lane_op_masks(ops, sh, span, base, lane);
+      const LaneClasses c = classes_of(o);
+      const unsigned pb = (unsigned)from_lower_lane((int)c.top, (int)prev);
+      const unsigned ba = boundaries_of(c.a, pb & 1u, o.valid), bm = boundaries_of(o.m, pb >> 1, o.valid);
       const unsigned takes_p = o.valid & ~o.i, takes_t = o.valid & ~o.d;
-      const int counts = __popc(takes_p) | (__popc(takes_t) << 16);  // (a chunk holds 1,024 columns: the sums fit 16 bits each)
-      const int s_pos = wave_scan_add(counts);
-      const int ex = s_pos - counts;
-      const long long x0 = (long long)sp.pb + cq + (ex & 0xffff), y0 = (long long)sp.tb + ct + (ex >> 16);
+      const awvw::ConsumedScan pos = awvw::consumed_scan(o);
+      const long long x0 = (long long)sp.pb + cq + (pos.ex & 0xffff), y0 = (long long)sp.tb + ct + (pos.ex >> 16);
       for (unsigned b = ba | bm; b != 0; b &= b - 1) {
         const int j = __builtin_ctz(b);
         const unsigned bit = 1u << j, below = bit - 1u;
         const long long x = x0 + __popc(takes_p & below), y = y0 + __popc(takes_t & below);
-        if (ba & bit) add_boundary(kp.acc_a, kp, pr, qlen, tlen, x, y, (o.a & bit) ? 1u : 0u - 1u);
+        if (ba & bit) add_boundary(kp.acc_a, kp, pr, qlen, tlen, x, y, (c.a & bit) ? 1u : 0u - 1u);
         if (bm & bit) add_boundary(kp.acc_m, kp, pr, qlen, tlen, x, y, (o.m & bit) ? 1u : 0u - 1u);
       }
-      const int tot = __builtin_amdgcn_readlane(s_pos, 63);
-      cq += tot & 0xffff;
-      ct += tot >> 16;
-      prev = chunk_last(o, span, base);
+      cq += pos.tot & 0xffff;
+      ct += pos.tot >> 16;
+      prev = chunk_last(c, span, base);
     }
     if (lane == 0) {  // a run that ends with the string
       const long long x = (long long)sp.pb + cq, y = (long long)sp.tb + ct;
@@ -282,20 +259,11 @@ bool active(const State* s) { return s && s->roles != 0; }
 
 namespace {
 
-// what fits awv_cov_item's counts: refused before anything is launched
-int check_lengths(const awv_result* recs, int64_t n) {
-  for (int64_t i = 0; i < n; ++i)
-    if (recs[i].status == AWV_ST_COMPLETED && (int64_t)recs[i].cigar_len > MAX_COLUMNS)
-      return awv_internal_fail(AWV_ERR_ARG, "coverage: an op string of more than 2^30 columns");
-  return AWV_OK;
-}
+constexpr const char* TOO_LONG = "coverage: an op string of more than 2^30 columns";  // what fits awv_cov_item's counts
 
 int open_state(awv_engine* e, awp::EngineView& v, State*& st) { return awvw::open_pass(awv_internal_coverage(e), e, v, st, true); }
 // the state of an engine that accumulates
-int open_active(awv_engine* e, const char* who, awp::EngineView& v, State*& st) {
-  if (!active(awv_internal_coverage(e))) return awv_internal_fail(AWV_ERR_STATE, std::string(who) + " before awv_engine_coverage_begin");
-  return open_state(e, v, st);
-}
+int open_active(awv_engine* e, const char* who, awp::EngineView& v, State*& st) { return awvw::open_active(awv_internal_coverage(e), who, "coverage", e, v, st); }
 
 // One launch over n items whose op bytes are on the device already; an item's slice has been applied to its record and to its
 // rectangle.  Every index and rectangle is checked here, on the host: the kernel reads what the items say.  items (host,
@@ -305,15 +273,8 @@ int launch(const awp::EngineView& v, State* st, const awv_pair* pairs, const Spa
   if (n == 0) return AWV_OK;
   if (v.n != st->nseq) return awv_internal_fail(AWV_ERR_STATE, "coverage: the sequence set changed since awv_engine_coverage_begin");
   if ((int64_t)st->stats.items + n > MAX_ITEMS) return awv_internal_fail(AWV_ERR_ARG, "coverage: more than 2^31 - 1 items since awv_engine_coverage_begin");
-  for (int64_t i = 0; i < n; ++i) {
-    if (pairs[i].q_idx < 0 || pairs[i].q_idx >= v.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= v.n)
-      return awv_internal_fail(AWV_ERR_ARG, "coverage: sequence index out of range");
-    const Span& sp = spans[i];
-    if (sp.pb < 0 || sp.tb < 0 || sp.pe > v.len_host[pairs[i].q_idx] || sp.te > v.len_host[pairs[i].t_idx] || (int64_t)sp.pb > (int64_t)sp.pe + 1 ||
-        (int64_t)sp.tb > (int64_t)sp.te + 1)
-      return awv_internal_fail(AWV_ERR_ARG, "coverage: an interval outside its sequence");
-  }
-  if (int rc = check_lengths(recs, n)) return rc;
+  if (int rc = awvw::check_rectangles(v, "coverage", pairs, spans, n)) return rc;
+  if (int rc = awvw::check_lengths(recs, n, MAX_COLUMNS, TOO_LONG)) return rc;
   if (int rc = st->begin(v, "coverage", n, recs, arena_bytes)) return rc;
   AWV_TRY(st->d_pairs.reserve((size_t)n));
   AWV_TRY(st->d_spans.reserve((size_t)n));
@@ -354,63 +315,20 @@ int launch(const awp::EngineView& v, State* st, const awv_pair* pairs, const Spa
   return AWV_OK;
 }
 
-using awvw::whole_span;
-
 // ranges (nullable; awv_coverage_ranges): the call is on ranges[0..n_all) -- `pairs` is not read
 int coverage_cigars_core(awv_engine* e, const awv_pair* pairs, const awv_range_pair* ranges, int64_t n_all, const awv_result* results,
                          const uint8_t* cigar_arena, uint64_t arena_bytes, const awv_cs_slice* slices, uint64_t max_arena, awv_cov_item* items) {
+  const char* const who = ranges ? "coverage_ranges" : "coverage_cigars";
   awp::EngineView v;
   State* st = nullptr;
-  if (int rc = open_active(e, ranges ? "coverage_ranges" : "coverage_cigars", v, st)) return rc;
-  // before anything goes up: every rectangle inside its sequences, every completed record's op bytes inside the caller's arena,
-  // every slice inside its string
-  std::vector<awv_pair> rpairs;
-  std::vector<Span> spans((size_t)n_all);
-  if (ranges) {
-    rpairs.resize((size_t)n_all);
-    for (int64_t i = 0; i < n_all; ++i)
-      if (!awvr::split_range(v.len_host, v.n, ranges[i], rpairs[(size_t)i], spans[(size_t)i]))
-        return awv_internal_fail(AWV_ERR_ARG, "coverage_ranges: range " + std::to_string(i) + " names a sequence index or an interval out of range");
-    pairs = rpairs.data();
-  } else {
-    for (int64_t i = 0; i < n_all; ++i) {
-      if (pairs[i].q_idx < 0 || pairs[i].q_idx >= v.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= v.n)
-        return awv_internal_fail(AWV_ERR_ARG, "coverage_cigars: sequence index out of range");
-      spans[(size_t)i] = whole_span(v, pairs[i]);
-    }
-  }
-  for (int64_t i = 0; i < n_all; ++i) {
-    if (awvw::outside(results[i], arena_bytes)) return awv_internal_fail(AWV_ERR_ARG, "coverage_cigars: a record's op bytes lie outside the CIGAR arena");
-    if (slices && !awvcs::slice_ok(results[i], slices[i]))
-      return awv_internal_fail(AWV_ERR_ARG, "coverage_cigars: slice " + std::to_string(i) + " does not lie inside its op string, or skips a negative number of bases");
-  }
-  // a slice is an op string of its own: the records that go up name the slices
-  std::vector<awv_result> sliced;
-  if (slices) {
-    sliced.assign(results, results + n_all);
-    for (int64_t i = 0; i < n_all; ++i) awvcs::apply_slice(sliced[(size_t)i], spans[(size_t)i], slices[i]);
-    results = sliced.data();
-  }
-  if (int rc = check_lengths(results, n_all)) return rc;
+  if (int rc = open_active(e, who, v, st)) return rc;
+  awvw::ItemCall call;
+  if (int rc = awvw::resolve_call(call, v, who, pairs, ranges, n_all, results, arena_bytes, slices)) return rc;
+  if (int rc = awvw::check_lengths(call.recs, n_all, MAX_COLUMNS, TOO_LONG)) return rc;
   if ((int64_t)st->stats.items + n_all > MAX_ITEMS) return awv_internal_fail(AWV_ERR_ARG, "coverage: more than 2^31 - 1 items since awv_engine_coverage_begin");
-  // in pieces (record_pieces.hpp) that keep every string's offset modulo 16
-  std::vector<uint8_t> stage;
-  std::vector<awv_result> recs;
-  for (int64_t first = 0; first < n_all;) {
-    const awvw::Piece pc = awvw::pack_piece(results, n_all, first, cigar_arena, max_arena, true, recs, stage);
-    AWV_TRY(st->d_arena.reserve((size_t)pc.bytes + 64));
-    if (pc.bytes) AWV_TRY(hipMemcpyAsync(st->d_arena.p, stage.data(), (size_t)pc.bytes, hipMemcpyHostToDevice, v.stream));
-    if (int rc = launch(v, st, pairs + first, spans.data() + first, pc.n, recs.data(), st->d_arena.p, pc.bytes, items + first)) return rc;
-    first += pc.n;
-  }
-  return AWV_OK;
-}
-
-int check_call_args(const char* name, int64_t n, const void* who, const awv_result* results, const uint8_t* cigar_arena, uint64_t arena_bytes,
-                    const awv_cov_item* items) {
-  if (n < 0 || (n > 0 && (!who || !results || !items))) return awv_internal_fail(AWV_ERR_ARG, std::string(name) + ": null argument");
-  if (arena_bytes > 0 && !cigar_arena) return awv_internal_fail(AWV_ERR_ARG, std::string(name) + ": null arena");
-  return AWV_OK;
+  return st->each_piece(v, call.recs, n_all, cigar_arena, max_arena, [&](int64_t first, int64_t n, const awv_result* recs, uint64_t bytes) {
+    return launch(v, st, call.pairs + first, call.spans.data() + first, n, recs, st->d_arena.p, bytes, items + first);
+  });
 }
 
 int begin_core(awv_engine* e, int32_t roles, int64_t clip_min_score) {
@@ -487,18 +405,10 @@ int awv_coverage_one_host(int32_t roles, int32_t q_revcomp, int32_t qlen, int32_
                           awv_cov_item* out) {
   if (!out || !awvcov::roles_ok(roles) || qlen < 0 || tlen < 0 || n < 0 || (n > 0 && !cigar))
     return awv_internal_fail(AWV_ERR_ARG, "coverage_one_host: bad argument");
-  if (pb < 0 || pb > pe || pe > qlen || tb < 0 || tb > te || te > tlen) return awv_internal_fail(AWV_ERR_ARG, "coverage_one_host: an interval outside its sequence");
-  int64_t beg = 0, end = n, q_skip = 0, t_skip = 0;
-  if (slice) {
-    if (slice->col_beg > slice->col_end || (int64_t)slice->col_end > n || slice->q_skip < 0 || slice->t_skip < 0)
-      return awv_internal_fail(AWV_ERR_ARG, "coverage_one_host: the slice does not lie inside the op string, or skips a negative number of bases");
-    beg = slice->col_beg;
-    end = slice->col_end;
-    q_skip = slice->q_skip;
-    t_skip = slice->t_skip;
-  }
-  if (end - beg > awvcov::MAX_COLUMNS) return awv_internal_fail(AWV_ERR_ARG, "coverage_one_host: an op string of more than 2^30 columns");
-  *out = awvcov::cov_one(roles, q_revcomp != 0, qlen, tlen, awvcov::Span{pb, pe, tb, te}, cigar + beg, end - beg, q_skip, t_skip, q_aligned, q_matched,
+  if (int rc = awvw::check_host_rectangle("coverage_one_host", qlen, tlen, pb, pe, tb, te)) return rc;
+  awvw::HostSlice sl;
+  if (int rc = awvw::check_host_slice("coverage_one_host", slice, n, awvcov::MAX_COLUMNS, sl)) return rc;
+  *out = awvcov::cov_one(roles, q_revcomp != 0, qlen, tlen, awvcov::Span{pb, pe, tb, te}, cigar + sl.beg, sl.end - sl.beg, sl.q_skip, sl.t_skip, q_aligned, q_matched,
                          t_aligned, t_matched);
   return AWV_OK;
 }
@@ -516,14 +426,14 @@ int awv_engine_coverage_read(awv_engine* e, uint32_t* aligned, uint32_t* matched
 int awv_coverage_cigars(awv_engine* e, const awv_pair* pairs, int64_t n, const awv_result* results, const uint8_t* cigar_arena, uint64_t arena_bytes,
                         const awv_cs_slice* slices, awv_cov_item* items) {
   if (!e) return awv_internal_null_engine();
-  if (int rc = awvcov::check_call_args("coverage_cigars", n, pairs, results, cigar_arena, arena_bytes, items)) return rc;
+  if (int rc = awvw::check_call_args("coverage_cigars", n, pairs, results, n <= 0 || items, cigar_arena, arena_bytes)) return rc;
   AWV_GUARDED(return awvcov::coverage_cigars_core(e, pairs, nullptr, n, results, cigar_arena, arena_bytes, slices, awv_internal_max_arena(e), items);)
 }
 
 int awv_coverage_ranges(awv_engine* e, const awv_range_pair* ranges, int64_t n, const awv_result* results, const uint8_t* cigar_arena, uint64_t arena_bytes,
                         const awv_cs_slice* slices, awv_cov_item* items) {
   if (!e) return awv_internal_null_engine();
-  if (int rc = awvcov::check_call_args("coverage_ranges", n, ranges, results, cigar_arena, arena_bytes, items)) return rc;
+  if (int rc = awvw::check_call_args("coverage_ranges", n, ranges, results, n <= 0 || items, cigar_arena, arena_bytes)) return rc;
   static const awv_range_pair none{};
   AWV_GUARDED(return awvcov::coverage_cigars_core(e, nullptr, n > 0 ? ranges : &none, n, results, cigar_arena, arena_bytes, slices, awv_internal_max_arena(e), items);)
 }

@@ -24,7 +24,7 @@
 #include <vector>
 
 #include "seq_load.hpp"   // load16
-#include "text_pass.hpp"  // the host skeleton and the device walk of a text pass: TextPass, lane_runs, text_dest, AWV_TRY
+#include "text_pass.hpp"  // the host skeleton and the device walk of a text pass: TextPass, lane_runs, text_dest, AWV_TRY; resolve_call below it
 
 namespace awvcs {
 
@@ -109,20 +109,11 @@ __global__ __launch_bounds__(64) void awv_cs_kernel(KParams kp) {
       const long long b0 = r.b0;
       const u32x4 w = r.w;
       const unsigned brk = r.brk;
-      const unsigned valid = ((1u << r.jhi) - 1u) & ~((1u << r.jlo) - 1u);  // bit j: byte j is a column
-      unsigned m_m = 0, m_x = 0, m_i = 0, m_d = 0;                          // ... an 'M', ...
+      awvw::OpMasks o = awvw::window_masks(r.jlo, r.jhi);  // (awvw::op_masks, written out: see there)
 #pragma unroll
-      for (int j = 0; j < LANE_BYTES; ++j) {
-        const unsigned op = (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
-        m_m |= (unsigned)(op == 'M') << j;
-        m_x |= (unsigned)(op == 'X') << j;
-        m_i |= (unsigned)(op == 'I') << j;
-        m_d |= (unsigned)(op == 'D') << j;
-      }
-      m_m &= valid;
-      m_x &= valid;
-      m_i &= valid;
-      m_d &= valid;
+      for (int j = 0; j < LANE_BYTES; ++j) awvw::add_op(o, w, j);
+      awvw::cut_to_window(o);
+      const unsigned valid = o.valid, m_m = o.m, m_x = o.x, m_i = o.i, m_d = o.d;
       const unsigned gaps = m_i | m_d;
       const unsigned starts = brk | (b0 <= sh && sh < b0 + LANE_BYTES ? 1u << (int)(sh - b0) : 0u);  // columns that begin a run: the breaks and column 0
       const unsigned takes_p = valid & ~m_i, takes_t = valid & ~m_d;
@@ -140,14 +131,12 @@ __global__ __launch_bounds__(64) void awv_cs_kernel(KParams kp) {
           chars += (int)match_chars((unsigned)(b0 + j - sh - awvw::run_start_before(r, sh, j)));
         }
       }
-      const int counts = __popc(takes_p) | (__popc(takes_t) << 16);  // (a chunk holds 1,024 columns: the sums fit 16 bits each)
-      const int s_pos = wave_scan_add(counts);
+      const awvw::ConsumedScan pos = awvw::consumed_scan(o);
       const int s_ch = wave_scan_add(chars);
       if (EMIT) {
         const unsigned active = LONG ? valid : valid & ~m_m;  // the columns that own characters (an ended 'M' run's go with the column that ends it)
         if (active != 0) {
-          const int ex = s_pos - counts;
-          const u32x4 pb16 = load16(pattern, plen, cq + (ex & 0xffff)), tb16 = load16(text, tlen, ct + (ex >> 16));
+          const u32x4 pb16 = load16(pattern, plen, cq + (pos.ex & 0xffff)), tb16 = load16(text, tlen, ct + (pos.ex >> 16));
           unsigned at = c_text + (unsigned)(s_ch - chars);
           for (unsigned m = active; m != 0; m &= m - 1) {
             const int j = __builtin_ctz(m);
@@ -172,9 +161,8 @@ __global__ __launch_bounds__(64) void awv_cs_kernel(KParams kp) {
       }
 
       awvw::carry_on(carry, r, sh, span, base);
-      const int tot = __builtin_amdgcn_readlane(s_pos, 63);
-      cq += tot & 0xffff;
-      ct += tot >> 16;
+      cq += pos.tot & 0xffff;
+      ct += pos.tot >> 16;
       c_text += (unsigned)__builtin_amdgcn_readlane(s_ch, 63);
       bad = bad || __ballot(lane_bad) != 0;
     }
@@ -242,14 +230,7 @@ int launch(const awp::EngineView& v, State* st, int32_t mode, const awv_pair* pa
            const uint8_t* d_arena, uint64_t arena_bytes, uint64_t text_base, bool want_text, awv_cs_text* csout, uint64_t* text_end) {
   *text_end = text_base;
   if (n == 0) return AWV_OK;
-  for (int64_t i = 0; i < n; ++i) {
-    if (pairs[i].q_idx < 0 || pairs[i].q_idx >= v.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= v.n)
-      return awv_internal_fail(AWV_ERR_ARG, "cs: sequence index out of range");
-    const Span& sp = spans[i];
-    if (sp.pb < 0 || sp.tb < 0 || sp.pe > v.len_host[pairs[i].q_idx] || sp.te > v.len_host[pairs[i].t_idx] || (int64_t)sp.pb > (int64_t)sp.pe + 1 ||
-        (int64_t)sp.tb > (int64_t)sp.te + 1)
-      return awv_internal_fail(AWV_ERR_ARG, "cs: an interval outside its sequence");
-  }
+  if (int rc = awvw::check_rectangles(v, "cs", pairs, spans, n)) return rc;
   if (int rc = st->begin(v, "cs", n, recs, arena_bytes)) return rc;
   AWV_TRY(st->d_pairs.reserve((size_t)n));
   AWV_TRY(st->d_spans.reserve((size_t)n));
@@ -283,9 +264,6 @@ int launch(const awp::EngineView& v, State* st, int32_t mode, const awv_pair* pa
   return AWV_OK;
 }
 
-// the whole of both sequences: the rectangle of a pair call's record
-Span whole_span(const awp::EngineView& v, const awv_pair& p) { return Span{0, v.len_host[p.q_idx], 0, v.len_host[p.t_idx]}; }
-
 // ranges (nullable; awv_cs_ranges): the call is on ranges[0..n_all) -- `pairs` is not read
 int cs_cigars_core(awv_engine* e, int32_t mode, const awv_pair* pairs, const awv_range_pair* ranges, int64_t n_all, const awv_result* results,
                    const uint8_t* cigar_arena, uint64_t arena_bytes, const awv_cs_slice* slices, uint64_t max_arena, awv_cs_text* csout, uint8_t* text_buf,
@@ -295,46 +273,20 @@ int cs_cigars_core(awv_engine* e, int32_t mode, const awv_pair* pairs, const awv
   State* st = nullptr;
   if (int rc = open_state(e, v, st)) return rc;
   st->stats = awv_cs_stats{};
-  // before anything goes up: every rectangle inside its sequences, every completed record's op bytes inside the caller's arena,
-  // every slice inside its string
-  std::vector<awv_pair> rpairs;
-  std::vector<Span> spans((size_t)n_all);
-  if (ranges) {
-    rpairs.resize((size_t)n_all);
-    for (int64_t i = 0; i < n_all; ++i)
-      if (!awvr::split_range(v.len_host, v.n, ranges[i], rpairs[(size_t)i], spans[(size_t)i]))
-        return awv_internal_fail(AWV_ERR_ARG, "cs_ranges: range " + std::to_string(i) + " names a sequence index or an interval out of range");
-    pairs = rpairs.data();
-  } else {
-    for (int64_t i = 0; i < n_all; ++i) {
-      if (pairs[i].q_idx < 0 || pairs[i].q_idx >= v.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= v.n)
-        return awv_internal_fail(AWV_ERR_ARG, "cs_cigars: sequence index out of range");
-      spans[(size_t)i] = whole_span(v, pairs[i]);
-    }
-  }
-  for (int64_t i = 0; i < n_all; ++i) {
-    if (awvw::outside(results[i], arena_bytes)) return awv_internal_fail(AWV_ERR_ARG, "cs_cigars: a record's op bytes lie outside the CIGAR arena");
-    if (slices && !slice_ok(results[i], slices[i]))
-      return awv_internal_fail(AWV_ERR_ARG, "cs_cigars: slice " + std::to_string(i) + " does not lie inside its op string, or skips a negative number of bases");
-  }
-  // a slice is an op string of its own: the records that go up name the slices
-  std::vector<awv_result> sliced;
-  if (slices) {
-    sliced.assign(results, results + n_all);
-    for (int64_t i = 0; i < n_all; ++i) apply_slice(sliced[(size_t)i], spans[(size_t)i], slices[i]);
-    results = sliced.data();
-  }
-  if (int rc = awvw::check_lengths(results, n_all, MAX_COLUMNS, TOO_LONG)) return rc;
-  return st->in_pieces(v, results, n_all, cigar_arena, max_arena, text_buf, text_cap, text_bytes,
+  awvw::ItemCall call;
+  if (int rc = awvw::resolve_call(call, v, ranges ? "cs_ranges" : "cs_cigars", pairs, ranges, n_all, results, arena_bytes, slices)) return rc;
+  if (int rc = awvw::check_lengths(call.recs, n_all, MAX_COLUMNS, TOO_LONG)) return rc;
+  return st->in_pieces(v, call.recs, n_all, cigar_arena, max_arena, text_buf, text_cap, text_bytes,
                        [&](int64_t first, int64_t n, const awv_result* recs, uint64_t bytes, uint64_t text_base, bool want_text, uint64_t* text_end) {
-                         return launch(v, st, mode, pairs + first, spans.data() + first, n, recs, st->d_arena.p, bytes, text_base, want_text, csout + first, text_end);
+                         return launch(v, st, mode, call.pairs + first, call.spans.data() + first, n, recs, st->d_arena.p, bytes, text_base, want_text, csout + first,
+                                       text_end);
                        });
 }
 
-int check_call_args(const char* name, int64_t n, const void* who, const awv_result* results, const uint8_t* cigar_arena, uint64_t arena_bytes,
-                    const awv_cs_text* csout, const uint8_t* text_buf, uint64_t text_cap, const uint64_t* text_bytes) {
-  if (n < 0 || !text_bytes || (n > 0 && (!who || !results || !csout))) return awv_internal_fail(AWV_ERR_ARG, std::string(name) + ": null argument");
-  if (arena_bytes > 0 && !cigar_arena) return awv_internal_fail(AWV_ERR_ARG, std::string(name) + ": null arena");
+// list: the pairs or ranges
+int check_args(const char* name, int64_t n, const void* list, const awv_result* results, const uint8_t* cigar_arena, uint64_t arena_bytes, const awv_cs_text* csout,
+               const uint8_t* text_buf, uint64_t text_cap, const uint64_t* text_bytes) {
+  if (int rc = awvw::check_call_args(name, n, list, results, text_bytes && (n <= 0 || csout), cigar_arena, arena_bytes)) return rc;
   if (text_cap > 0 && !text_buf) return awv_internal_fail(AWV_ERR_ARG, std::string(name) + ": null text buffer");
   return AWV_OK;
 }
@@ -347,7 +299,7 @@ int cs_batch(awv_engine* e, int32_t mode, const awv_pair* pairs, int64_t n, cons
   State* st = nullptr;
   if (int rc = open_state(e, v, st)) return rc;
   st->h_spans.resize((size_t)n);
-  for (int64_t i = 0; i < n; ++i) st->h_spans[(size_t)i] = spans ? spans[i] : whole_span(v, pairs[i]);  // (the indices: checked by the aligning call)
+  for (int64_t i = 0; i < n; ++i) st->h_spans[(size_t)i] = spans ? spans[i] : awvw::whole_span(v.len_host, pairs[i]);  // (the indices: checked by the aligning call)
   if (clips) {  // the clip's segment is the slice; a record without one has no text
     st->h_recs.assign(results, results + n);
     for (int64_t i = 0; i < n; ++i) {
@@ -375,24 +327,16 @@ int awv_cs_one_host(int32_t mode, const uint8_t* pattern, int32_t plen, const ui
   if (!out || !awvcs::mode_ok(mode) || plen < 0 || tlen < 0 || n < 0 || (plen > 0 && !pattern) || (tlen > 0 && !text) || (n > 0 && !cigar) ||
       (cap > 0 && !out_buf))
     return awv_internal_fail(AWV_ERR_ARG, "cs_one_host: bad argument");
-  int64_t beg = 0, end = n, q_skip = 0, t_skip = 0;
-  if (slice) {
-    if (slice->col_beg > slice->col_end || (int64_t)slice->col_end > n || slice->q_skip < 0 || slice->t_skip < 0)
-      return awv_internal_fail(AWV_ERR_ARG, "cs_one_host: the slice does not lie inside the op string, or skips a negative number of bases");
-    beg = slice->col_beg;
-    end = slice->col_end;
-    q_skip = slice->q_skip;
-    t_skip = slice->t_skip;
-  }
-  if (end - beg > awvcs::MAX_COLUMNS) return awv_internal_fail(AWV_ERR_ARG, "cs_one_host: an op string of more than 2^30 columns");
-  *out = awvcs::cs_one(mode, pattern, plen, text, tlen, cigar + beg, end - beg, q_skip, t_skip, out_buf, cap);
+  awvw::HostSlice sl;
+  if (int rc = awvw::check_host_slice("cs_one_host", slice, n, awvcs::MAX_COLUMNS, sl)) return rc;
+  *out = awvcs::cs_one(mode, pattern, plen, text, tlen, cigar + sl.beg, sl.end - sl.beg, sl.q_skip, sl.t_skip, out_buf, cap);
   return AWV_OK;
 }
 
 int awv_cs_cigars(awv_engine* e, int32_t mode, const awv_pair* pairs, int64_t n, const awv_result* results, const uint8_t* cigar_arena,
                   uint64_t arena_bytes, const awv_cs_slice* slices, awv_cs_text* csout, uint8_t* text_buf, uint64_t text_cap, uint64_t* text_bytes) {
   if (!e) return awv_internal_null_engine();
-  if (int rc = awvcs::check_call_args("cs_cigars", n, pairs, results, cigar_arena, arena_bytes, csout, text_buf, text_cap, text_bytes)) return rc;
+  if (int rc = awvcs::check_args("cs_cigars", n, pairs, results, cigar_arena, arena_bytes, csout, text_buf, text_cap, text_bytes)) return rc;
   AWV_GUARDED(return awvcs::cs_cigars_core(e, mode, pairs, nullptr, n, results, cigar_arena, arena_bytes, slices, awv_internal_max_arena(e), csout, text_buf,
                                           text_cap, text_bytes);)
 }
@@ -400,7 +344,7 @@ int awv_cs_cigars(awv_engine* e, int32_t mode, const awv_pair* pairs, int64_t n,
 int awv_cs_ranges(awv_engine* e, int32_t mode, const awv_range_pair* ranges, int64_t n, const awv_result* results, const uint8_t* cigar_arena,
                   uint64_t arena_bytes, const awv_cs_slice* slices, awv_cs_text* csout, uint8_t* text_buf, uint64_t text_cap, uint64_t* text_bytes) {
   if (!e) return awv_internal_null_engine();
-  if (int rc = awvcs::check_call_args("cs_ranges", n, ranges, results, cigar_arena, arena_bytes, csout, text_buf, text_cap, text_bytes)) return rc;
+  if (int rc = awvcs::check_args("cs_ranges", n, ranges, results, cigar_arena, arena_bytes, csout, text_buf, text_cap, text_bytes)) return rc;
   static const awv_range_pair none{};
   AWV_GUARDED(return awvcs::cs_cigars_core(e, mode, nullptr, n > 0 ? ranges : &none, n, results, cigar_arena, arena_bytes, slices, awv_internal_max_arena(e), csout,
                                           text_buf, text_cap, text_bytes);)

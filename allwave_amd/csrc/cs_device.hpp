@@ -20,6 +20,7 @@
 
 #include "allwave_hip.h"
 #include "encode_device.hpp"  // digits
+#include "cs_slice.hpp"       // slice_ok, apply_slice
 #include "range_span.hpp"
 
 struct awv_engine;
@@ -115,22 +116,6 @@ __host__ __device__ inline awv_cs_text cs_one(int32_t mode, const uint8_t* patte
     }
   }
   return make_text(0, len, AWV_CST_OK);
-}
-
-// a slice that lies inside a record's op string and skips no negative number of bases (a record that is not completed has no
-// string: any columns will do)
-inline bool slice_ok(const awv_result& r, const awv_cs_slice& s) {
-  if (s.q_skip < 0 || s.t_skip < 0) return false;
-  return r.status != AWV_ST_COMPLETED || (s.col_beg <= s.col_end && s.col_end <= r.cigar_len);
-}
-// A slice is an op string of its own: the record as the kernels take it names the slice's bytes, and the rectangle begins behind
-// the skips (a skip beyond its sequence leaves a rectangle of negative length: AWV_CST_LENGTHS).
-inline void apply_slice(awv_result& r, awvr::Span& sp, const awv_cs_slice& s) {
-  if (r.status != AWV_ST_COMPLETED) return;
-  r.cigar_off += s.col_beg;
-  r.cigar_len = s.col_end - s.col_beg;
-  sp.pb = (int32_t)std::min<int64_t>((int64_t)sp.pb + s.q_skip, (int64_t)sp.pe + 1);
-  sp.tb = (int32_t)std::min<int64_t>((int64_t)sp.tb + s.t_skip, (int64_t)sp.te + 1);
 }
 
 // A record without a clip has no text (AWV_CST_SKIPPED): the kernels take it as one that is not completed.

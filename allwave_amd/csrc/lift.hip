@@ -2,9 +2,10 @@
 // _stats and awv_lift_one_host (include/allwave_hip.h).  What the lift of one interval is stands in lift_device.hpp; this file gets
 // the kernel to the same results.
 //
-// A record pass (record_pass.hpp) with cs.hip's walk: persistent one-wave workgroups take records -- not queries --, longest op
-// string first, from a cursor; a string goes by in chunks of 64 lanes x 16 op bytes, one aligned 16-byte load per lane.  Only
-// records that have a query are dispatched, and a record is walked once however many queries it has.
+// A record pass (record_pass.hpp) with the op-mask walk of wave_ops.hpp (lane_op_masks): persistent one-wave workgroups take
+// records -- not queries --, longest op string first, from a cursor; a string goes by in chunks of 64 lanes x 16 op bytes, one
+// aligned 16-byte load per lane.  Only records that have a query are dispatched, and a record is walked once however many queries
+// it has.
 // The host turns a record's queries into probes.  A probe is a source offset r (counted from the item's first source base) and
 // asks for the first aligned ('M' / 'X') column whose source offset is r or more: a query's begin wants that column, its end the
 // aligned column before it.  Both are the same search, and its answer is monotone in r, so a record's probes are sorted by r, per
@@ -29,8 +30,8 @@
 #include <string>
 #include <vector>
 
-#include "batch_items.hpp"  // contributing_items, whole_span
-#include "record_pass.hpp"  // RecordPass, open_pass, Buf, pack_piece, AWV_TRY
+#include "batch_items.hpp"  // contributing_items
+#include "record_pass.hpp"  // RecordPass, open_pass, open_active, each_piece, resolve_call, Buf, AWV_TRY
 
 namespace awvl {
 
@@ -66,39 +67,8 @@ struct KParams {
 using awvw::CHUNK;
 using awvw::from_lower_lane;
 using awvw::LANE_BYTES;
-using awvw::u32x4;
 using awvw::wave_scan_add;
 using awvw::wave_scan_max;
-
-// One lane's 16 op bytes of a chunk as masks over its columns.  Op byte c of the string is ops[sh + c].
-struct LaneOps {
-  unsigned valid;       // bit j: byte j is a column
-  unsigned m, x, i, d;  // ... an 'M', an 'X', an 'I', a 'D'
-};
-
-__device__ __forceinline__ LaneOps lane_ops(const uint8_t* ops, int sh, long long span, long long base, int lane) {
-  const long long b0 = base + lane * LANE_BYTES;
-  const int jlo = (int)min(max((long long)sh - b0, 0ll), (long long)LANE_BYTES);
-  const int jhi = (int)min(max(span - b0, 0ll), (long long)LANE_BYTES);
-  u32x4 w = u32x4{0u, 0u, 0u, 0u};
-  if (b0 < span) w = *(const u32x4*)(ops + b0);
-  LaneOps o;
-  o.valid = jhi > jlo ? ((1u << jhi) - 1u) & ~((1u << jlo) - 1u) : 0u;
-  unsigned m_m = 0, m_x = 0, m_i = 0, m_d = 0;
-#pragma unroll
-  for (int j = 0; j < LANE_BYTES; ++j) {
-    const unsigned op = (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
-    m_m |= (unsigned)(op == 'M') << j;
-    m_x |= (unsigned)(op == 'X') << j;
-    m_i |= (unsigned)(op == 'I') << j;
-    m_d |= (unsigned)(op == 'D') << j;
-  }
-  o.m = m_m & o.valid;
-  o.x = m_x & o.valid;
-  o.i = m_i & o.valid;
-  o.d = m_d & o.valid;
-  return o;
-}
 
 // the columns of a lane below bit j
 __device__ __forceinline__ unsigned below(int j) { return (1u << j) - 1u; }
@@ -158,7 +128,7 @@ __global__ __launch_bounds__(64) void awv_lift_kernel(KParams kp) {
       Prefix last_a{0u, 0u, 0u, 0u, 0u};          // behind the last aligned column so far (col 0: there is none) (uniform)
       unsigned bad = 0;                           // (lane-local)
       for (long long base = 0; base < span; base += CHUNK) {
-        const LaneOps o = lane_ops(ops, sh, span, base, lane);
+        const awvw::OpMasks o = awvw::lane_op_masks(ops, sh, span, base, lane);
         bad |= o.valid & ~(o.m | o.x | o.i | o.d);
         const unsigned al = o.m | o.x;
         const long long cnt = (long long)((unsigned long long)__popc(o.m) | ((unsigned long long)__popc(o.x) << 16) | ((unsigned long long)__popc(o.i) << 32) |
@@ -344,14 +314,11 @@ bool active(const State* s) { return s && s->from_mask != 0; }
 
 namespace {
 
-// what the kernel's 32-bit columns and counts hold: refused before anything is launched
-int check_lengths(const awv_result* recs, int64_t n) {
-  for (int64_t i = 0; i < n; ++i)
-    if (recs[i].status == AWV_ST_COMPLETED && (int64_t)recs[i].cigar_len > MAX_COLUMNS) return awv_internal_fail(AWV_ERR_ARG, "lift: an op string of more than 2^30 columns");
-  return AWV_OK;
-}
+constexpr const char* TOO_LONG = "lift: an op string of more than 2^30 columns";  // what the kernel's 32-bit columns and counts hold
 
 int open_state(awv_engine* e, awp::EngineView& v, State*& st) { return awvw::open_pass(awv_internal_lift(e), e, v, st, true); }
+// the state of an engine that keeps a table
+int open_active(awv_engine* e, const char* who, awp::EngineView& v, State*& st) { return awvw::open_active(awv_internal_lift(e), who, "lift", e, v, st); }
 
 // One launch over the records, of n, that hq[0 .. nq) (sorted by rec) name; their op bytes are on the device already, and a
 // record's slice has been applied to it and to its rectangle (bases, nullable: what the slices were).  Every index, rectangle and
@@ -377,11 +344,9 @@ int launch(const awp::EngineView& v, State* st, const awv_pair* pairs, const Spa
   for (int64_t k = 0; k < nq;) {
     const int64_t i = hq[k].rec;
     if (i < 0 || i >= n || (k > 0 && i < hq[k - 1].rec)) return awv_internal_fail(AWV_ERR_ARG, "lift: a query's record is out of range");
-    if (pairs[i].q_idx < 0 || pairs[i].q_idx >= v.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= v.n) return awv_internal_fail(AWV_ERR_ARG, "lift: sequence index out of range");
+    if (int rc = awvw::check_rectangles(v, "lift", pairs + i, spans + i, 1)) return rc;
     const Span& sp = spans[i];
     const int64_t qlen = v.len_host[pairs[i].q_idx], tlen = v.len_host[pairs[i].t_idx];
-    if (sp.pb < 0 || sp.tb < 0 || sp.pe > qlen || sp.te > tlen || (int64_t)sp.pb > (int64_t)sp.pe + 1 || (int64_t)sp.tb > (int64_t)sp.te + 1)
-      return awv_internal_fail(AWV_ERR_ARG, "lift: an interval outside its sequence");
     int64_t k1 = k;
     keys[0].clear();
     keys[1].clear();
@@ -420,7 +385,7 @@ int launch(const awp::EngineView& v, State* st, const awv_pair* pairs, const Spa
     k = k1;
   }
   const int64_t m = (int64_t)crecs.size();
-  if (int rc = check_lengths(crecs.data(), m)) return rc;
+  if (int rc = awvw::check_lengths(crecs.data(), m, MAX_COLUMNS, TOO_LONG)) return rc;
   if (int rc = st->begin(v, "lift", m, crecs.data(), arena_bytes)) return rc;
   AWV_TRY(st->d_pairs.reserve((size_t)m));
   AWV_TRY(st->d_spans.reserve((size_t)m));
@@ -471,8 +436,6 @@ int launch(const awp::EngineView& v, State* st, const awv_pair* pairs, const Spa
   return AWV_OK;
 }
 
-using awvw::whole_span;
-
 // ranges (nullable; awv_lift_ranges): the call is on ranges[0..n_all) -- `pairs` is not read
 int lift_cigars_core(awv_engine* e, const awv_pair* pairs, const awv_range_pair* ranges, int64_t n_all, const awv_result* results, const uint8_t* cigar_arena,
                      uint64_t arena_bytes, const awv_cs_slice* slices, uint64_t max_arena, const awv_lift_query* queries, int64_t nq, awv_lift_result* lout) {
@@ -480,28 +443,11 @@ int lift_cigars_core(awv_engine* e, const awv_pair* pairs, const awv_range_pair*
   awp::EngineView v;
   State* st = nullptr;
   if (int rc = open_state(e, v, st)) return rc;
-  // before anything goes up: every rectangle inside its sequences, every completed record's op bytes inside the caller's arena,
-  // every slice inside its string, every query on a record of the call and inside its source sequence
-  std::vector<awv_pair> rpairs;
-  std::vector<Span> spans((size_t)n_all);
-  if (ranges) {
-    rpairs.resize((size_t)n_all);
-    for (int64_t i = 0; i < n_all; ++i)
-      if (!awvr::split_range(v.len_host, v.n, ranges[i], rpairs[(size_t)i], spans[(size_t)i]))
-        return awv_internal_fail(AWV_ERR_ARG, "lift_ranges: range " + std::to_string(i) + " names a sequence index or an interval out of range");
-    pairs = rpairs.data();
-  } else {
-    for (int64_t i = 0; i < n_all; ++i) {
-      if (pairs[i].q_idx < 0 || pairs[i].q_idx >= v.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= v.n)
-        return awv_internal_fail(AWV_ERR_ARG, "lift_cigars: sequence index out of range");
-      spans[(size_t)i] = whole_span(v, pairs[i]);
-    }
-  }
-  for (int64_t i = 0; i < n_all; ++i) {
-    if (awvw::outside(results[i], arena_bytes)) return awv_internal_fail(AWV_ERR_ARG, std::string(who) + ": a record's op bytes lie outside the CIGAR arena");
-    if (slices && !awvcs::slice_ok(results[i], slices[i]))
-      return awv_internal_fail(AWV_ERR_ARG, std::string(who) + ": slice " + std::to_string(i) + " does not lie inside its op string, or skips a negative number of bases");
-  }
+  // before anything goes up: the call's own checks (item_call.hpp), then every query on a record of the call and inside its
+  // source sequence
+  awvw::ItemCall call;
+  if (int rc = awvw::resolve_call(call, v, who, pairs, ranges, n_all, results, arena_bytes, slices)) return rc;
+  pairs = call.pairs;
   if (nq > MAX_QUERIES) return awv_internal_fail(AWV_ERR_ARG, std::string(who) + ": 2^30 queries or more");
   for (int64_t j = 0; j < nq; ++j) {
     const awv_lift_query& q = queries[j];
@@ -525,48 +471,31 @@ int lift_cigars_core(awv_engine* e, const awv_pair* pairs, const awv_range_pair*
     if (k == 0 || q.record != queries[by_rec[(size_t)k - 1]].record) {
       const int64_t i = q.record;
       cpairs.push_back(pairs[i]);
-      cspans.push_back(spans[(size_t)i]);
-      crecs.push_back(results[i]);
-      cbases.push_back(awv_cs_slice{0u, 0u, 0, 0});
-      if (slices) {
-        awvcs::apply_slice(crecs.back(), cspans.back(), slices[i]);
-        if (results[i].status == AWV_ST_COMPLETED) cbases.back() = slices[i];
-      }
+      cspans.push_back(call.spans[(size_t)i]);
+      crecs.push_back(call.recs[i]);
+      cbases.push_back(slices && results[i].status == AWV_ST_COMPLETED ? slices[i] : awv_cs_slice{0u, 0u, 0, 0});
     }
     hq[(size_t)k] = HostQuery{(int64_t)crecs.size() - 1, q.from, q.beg, q.end, by_rec[(size_t)k]};
   }
   const int64_t m = (int64_t)crecs.size();
-  if (int rc = check_lengths(crecs.data(), m)) return rc;
-  // in pieces (record_pieces.hpp) that keep every string's offset modulo 16
-  std::vector<uint8_t> stage;
-  std::vector<awv_result> recs;
+  if (int rc = awvw::check_lengths(crecs.data(), m, MAX_COLUMNS, TOO_LONG)) return rc;
+  // in pieces, a piece's queries re-based to its first record
   std::vector<awv_lift_result> out;
   std::vector<HostQuery> piece_q;
   int64_t k = 0;
-  for (int64_t first = 0; first < m;) {
-    const awvw::Piece pc = awvw::pack_piece(crecs.data(), m, first, cigar_arena, max_arena, true, recs, stage);
+  return st->each_piece(v, crecs.data(), m, cigar_arena, max_arena, [&](int64_t first, int64_t n, const awv_result* recs, uint64_t bytes) {
     piece_q.clear();
-    for (; k < nq && hq[(size_t)k].rec < first + pc.n; ++k) {
+    for (; k < nq && hq[(size_t)k].rec < first + n; ++k) {
       piece_q.push_back(hq[(size_t)k]);
       piece_q.back().rec -= first;
     }
     out.resize(piece_q.size());
-    AWV_TRY(st->d_arena.reserve((size_t)pc.bytes + 64));
-    if (pc.bytes) AWV_TRY(hipMemcpyAsync(st->d_arena.p, stage.data(), (size_t)pc.bytes, hipMemcpyHostToDevice, v.stream));
-    if (int rc = launch(v, st, cpairs.data() + first, cspans.data() + first, cbases.data() + first, pc.n, recs.data(), st->d_arena.p, pc.bytes, piece_q.data(),
-                        (int64_t)piece_q.size(), out.data()))
+    if (int rc = launch(v, st, cpairs.data() + first, cspans.data() + first, cbases.data() + first, n, recs, st->d_arena.p, bytes, piece_q.data(), (int64_t)piece_q.size(),
+                        out.data()))
       return rc;
     for (size_t t = 0; t < piece_q.size(); ++t) lout[piece_q[t].tag] = out[t];
-    first += pc.n;
-  }
-  return AWV_OK;
-}
-
-int check_call_args(const char* name, int64_t n, const void* who, const awv_result* results, const uint8_t* cigar_arena, uint64_t arena_bytes,
-                    const awv_lift_query* queries, int64_t nq, const awv_lift_result* lout) {
-  if (n < 0 || nq < 0 || (n > 0 && (!who || !results)) || (nq > 0 && (!queries || !lout))) return awv_internal_fail(AWV_ERR_ARG, std::string(name) + ": null argument");
-  if (arena_bytes > 0 && !cigar_arena) return awv_internal_fail(AWV_ERR_ARG, std::string(name) + ": null arena");
-  return AWV_OK;
+    return (int)AWV_OK;
+  });
 }
 
 int begin_core(awv_engine* e, const awv_region* regions, int64_t n_regions, int32_t from_mask, int64_t clip_min_score) {
@@ -606,10 +535,9 @@ int begin_core(awv_engine* e, const awv_region* regions, int64_t n_regions, int3
 }
 
 int read_core(awv_engine* e, awv_lift_row* rows, uint64_t cap, uint64_t* n_rows) {
-  State* st = awv_internal_lift(e);
-  if (!active(st)) return awv_internal_fail(AWV_ERR_STATE, "lift_read before awv_engine_lift_begin");
   awp::EngineView v;
-  if (int rc = open_state(e, v, st)) return rc;
+  State* st = nullptr;
+  if (int rc = open_active(e, "lift_read", v, st)) return rc;
   std::sort(st->rows.begin(), st->rows.end(), row_less);
   *n_rows = (uint64_t)st->rows.size();
   if (*n_rows <= cap && rows && *n_rows) std::copy(st->rows.begin(), st->rows.end(), rows);
@@ -633,10 +561,9 @@ void match_regions(const State* st, int64_t item, int32_t from, int32_t seq, int
 
 int lift_batch(awv_engine* e, const awv_pair* pairs, int64_t n, const awv_result* results, const uint8_t* d_arena, uint64_t arena_bytes,
                const awv_clip_result* clips, const uint64_t* seg_first, const awv_split_index* iout, const awv_clip_result* sout, const Span* spans) {
-  State* st = awv_internal_lift(e);
-  if (!active(st)) return awv_internal_fail(AWV_ERR_STATE, "lift_batch before awv_engine_lift_begin");
   awp::EngineView v;
-  if (int rc = open_state(e, v, st)) return rc;
+  State* st = nullptr;
+  if (int rc = open_active(e, "lift_batch", v, st)) return rc;
   if (v.n != st->nseq) return awv_internal_fail(AWV_ERR_STATE, "lift: the sequence set changed since awv_engine_lift_begin");
   awvw::contributing_items(v, pairs, n, results, clips, st->clip_min_score, seg_first, iout, sout, spans, st->items);
   const awvw::BatchItems& it = st->items;
@@ -672,16 +599,12 @@ extern "C" {
 int awv_lift_one_host(int32_t from, int32_t q_revcomp, int32_t qlen, int32_t tlen, int32_t pb, int32_t pe, int32_t tb, int32_t te, const uint8_t* cigar, int64_t n,
                       const awv_cs_slice* slice, int32_t beg, int32_t end, awv_lift_result* out) {
   if (!out || !awvl::from_ok(from) || qlen < 0 || tlen < 0 || n < 0 || (n > 0 && !cigar)) return awv_internal_fail(AWV_ERR_ARG, "lift_one_host: bad argument");
-  if (pb < 0 || pb > pe || pe > qlen || tb < 0 || tb > te || te > tlen) return awv_internal_fail(AWV_ERR_ARG, "lift_one_host: an interval outside its sequence");
+  if (int rc = awvw::check_host_rectangle("lift_one_host", qlen, tlen, pb, pe, tb, te)) return rc;
   if (beg < 0 || beg >= end || end > (from == AWV_LIFT_FROM_TARGET ? tlen : qlen))
     return awv_internal_fail(AWV_ERR_ARG, "lift_one_host: the interval is empty or outside its source sequence");
-  awv_cs_slice base{0u, (uint32_t)n, 0, 0};
-  if (slice) {
-    if (slice->col_beg > slice->col_end || (int64_t)slice->col_end > n || slice->q_skip < 0 || slice->t_skip < 0)
-      return awv_internal_fail(AWV_ERR_ARG, "lift_one_host: the slice does not lie inside the op string, or skips a negative number of bases");
-    base = *slice;
-  }
-  if ((int64_t)base.col_end - base.col_beg > awvl::MAX_COLUMNS) return awv_internal_fail(AWV_ERR_ARG, "lift_one_host: an op string of more than 2^30 columns");
+  awvw::HostSlice sl;
+  if (int rc = awvw::check_host_slice("lift_one_host", slice, n, awvl::MAX_COLUMNS, sl)) return rc;
+  const awv_cs_slice base{(uint32_t)sl.beg, (uint32_t)sl.end, (int32_t)sl.q_skip, (int32_t)sl.t_skip};
   awvl::Span sp{pb, pe, tb, te};
   sp.pb = (int32_t)std::min<int64_t>((int64_t)sp.pb + base.q_skip, (int64_t)sp.pe + 1);  // (awvcs::apply_slice's rectangle)
   sp.tb = (int32_t)std::min<int64_t>((int64_t)sp.tb + base.t_skip, (int64_t)sp.te + 1);
@@ -692,14 +615,14 @@ int awv_lift_one_host(int32_t from, int32_t q_revcomp, int32_t qlen, int32_t tle
 int awv_lift_cigars(awv_engine* e, const awv_pair* pairs, int64_t n, const awv_result* results, const uint8_t* cigar_arena, uint64_t arena_bytes,
                     const awv_cs_slice* slices, const awv_lift_query* queries, int64_t nq, awv_lift_result* lout) {
   if (!e) return awv_internal_null_engine();
-  if (int rc = awvl::check_call_args("lift_cigars", n, pairs, results, cigar_arena, arena_bytes, queries, nq, lout)) return rc;
+  if (int rc = awvw::check_call_args("lift_cigars", n, pairs, results, nq >= 0 && (nq == 0 || (queries && lout)), cigar_arena, arena_bytes)) return rc;
   AWV_GUARDED(return awvl::lift_cigars_core(e, pairs, nullptr, n, results, cigar_arena, arena_bytes, slices, awv_internal_max_arena(e), queries, nq, lout);)
 }
 
 int awv_lift_ranges(awv_engine* e, const awv_range_pair* ranges, int64_t n, const awv_result* results, const uint8_t* cigar_arena, uint64_t arena_bytes,
                     const awv_cs_slice* slices, const awv_lift_query* queries, int64_t nq, awv_lift_result* lout) {
   if (!e) return awv_internal_null_engine();
-  if (int rc = awvl::check_call_args("lift_ranges", n, ranges, results, cigar_arena, arena_bytes, queries, nq, lout)) return rc;
+  if (int rc = awvw::check_call_args("lift_ranges", n, ranges, results, nq >= 0 && (nq == 0 || (queries && lout)), cigar_arena, arena_bytes)) return rc;
   static const awv_range_pair none{};
   AWV_GUARDED(return awvl::lift_cigars_core(e, nullptr, n > 0 ? ranges : &none, n, results, cigar_arena, arena_bytes, slices, awv_internal_max_arena(e), queries, nq, lout);)
 }

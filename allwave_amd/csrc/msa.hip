@@ -22,8 +22,7 @@
 #include <string>
 #include <vector>
 
-#include "batch_items.hpp"  // whole_span
-#include "record_pass.hpp"  // RecordPass, open_pass, Buf, pack_piece, AWV_TRY
+#include "record_pass.hpp"  // RecordPass, open_pass, each_piece, resolve_call, Buf, AWV_TRY
 
 namespace awvmsa {
 
@@ -53,89 +52,51 @@ struct KParams {
 using awvw::CHUNK;
 using awvw::from_lower_lane;
 using awvw::LANE_BYTES;
-using awvw::u32x4;
 using awvw::wave_scan_add;
 using awvw::wave_scan_max;
+using awvw::wave_max_i64;
+using awvw::wave_min_i64;
 using awvw::wave_sum_i64;
 
-__device__ __forceinline__ long long wave_min_i64(long long v) {  // in every lane
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m, 64));
-  return v;
-}
-__device__ __forceinline__ long long wave_max_i64(long long v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m, 64));
-  return v;
-}
-
-// One lane's 16 op bytes of a chunk as masks over its columns.  Op byte c of the string is ops[sh + c].
-struct LaneOps {
-  unsigned valid;    // bit j: byte j is a column
-  unsigned a, i, d;  // ... an 'M' or 'X'; an 'I'; a 'D'
-  int k0;            // the string column of byte 0 (negative in the first lane of a string that begins inside its 16 bytes)
-};
-
-__device__ __forceinline__ LaneOps lane_ops(const uint8_t* ops, int sh, long long span, long long base, int lane) {
-  const long long b0 = base + lane * LANE_BYTES;
-  const int jlo = (int)min(max((long long)sh - b0, 0ll), (long long)LANE_BYTES);
-  const int jhi = (int)min(max(span - b0, 0ll), (long long)LANE_BYTES);
-  u32x4 w = u32x4{0u, 0u, 0u, 0u};
-  if (b0 < span) w = *(const u32x4*)(ops + b0);
-  LaneOps o;
-  o.valid = jhi > jlo ? ((1u << jhi) - 1u) & ~((1u << jlo) - 1u) : 0u;
-  unsigned m_a = 0, m_i = 0, m_d = 0;
-#pragma unroll
-  for (int j = 0; j < LANE_BYTES; ++j) {
-    const unsigned op = (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
-    m_a |= (unsigned)(op == 'M' || op == 'X') << j;
-    m_i |= (unsigned)(op == 'I') << j;
-    m_d |= (unsigned)(op == 'D') << j;
-  }
-  o.a = m_a & o.valid;
-  o.i = m_i & o.valid;
-  o.d = m_d & o.valid;
-  o.k0 = (int)(b0 - sh);
-  return o;
-}
+// the string column of a lane's byte 0
+__device__ __forceinline__ int lane_k0(int sh, long long base, int lane) { return (int)(base + lane * LANE_BYTES - sh); }
 
 // What a chunk's scans give a lane (all under full EXEC, from values computed right before them).
 struct ChunkScan {
-  long long x0, y0;  // the pattern and text positions of the lane's byte 0
+  int k0;            // the string column of the lane's byte 0 (negative in the first lane of a string that begins inside its 16 bytes)
+  long long x0, y0;  // the pattern and text positions of that byte
   int start;         // the string column where the 'D' run going on at the lane's byte 0 began: one past the last column below the lane that is no 'D'
   unsigned ends;     // the lane's columns that end a 'D' run: no 'D', behind one
   int tot, inc_last; // (uniform) the chunk's consumed bases, packed; one past the chunk's last column that is no 'D', or INT_MIN
 };
-// cq, ct: bases consumed before the chunk; run0: the run start carried into the chunk; prev_d: the column before the chunk is a 'D'
-__device__ __forceinline__ ChunkScan chunk_scan(const LaneOps& o, long long xb, long long yb, int cq, int ct, int run0, unsigned prev_d) {
-  const unsigned takes_p = o.valid & ~o.i, takes_t = o.valid & ~o.d;
-  const int counts = __popc(takes_p) | (__popc(takes_t) << 16);  // (a chunk holds 1,024 columns: the sums fit 16 bits each)
-  const int mine = takes_t != 0 ? o.k0 + (31 - __clz((int)takes_t)) + 1 : INT_MIN;
+// k0: lane_k0; cq, ct: bases consumed before the chunk; run0: the run start carried into the chunk; prev_d: the column before the chunk is a 'D'
+__device__ __forceinline__ ChunkScan chunk_scan(const awvw::OpMasks& o, int k0, long long xb, long long yb, int cq, int ct, int run0, unsigned prev_d) {
+  const unsigned takes_t = o.valid & ~o.d;
+  const int mine = takes_t != 0 ? k0 + (31 - __clz((int)takes_t)) + 1 : INT_MIN;
   const int top = (int)((o.d >> 15) & 1u);
-  const int s_pos = wave_scan_add(counts);
+  const awvw::ConsumedScan pos = awvw::consumed_scan(o);
   const int s_run = wave_scan_max(mine);
   const int below_run = from_lower_lane(s_run, INT_MIN);
   const unsigned pbit = (unsigned)from_lower_lane(top, (int)prev_d);
   ChunkScan c;
-  const int ex = s_pos - counts;
-  c.x0 = xb + cq + (ex & 0xffff);
-  c.y0 = yb + ct + (ex >> 16);
+  c.k0 = k0;
+  c.x0 = xb + cq + (pos.ex & 0xffff);
+  c.y0 = yb + ct + (pos.ex >> 16);
   c.start = max(below_run, run0);
   c.ends = takes_t & ((o.d << 1) | pbit);
-  c.tot = __builtin_amdgcn_readlane(s_pos, 63);
+  c.tot = pos.tot;
   c.inc_last = __builtin_amdgcn_readlane(s_run, 63);
   return c;
 }
 // the start of the 'D' run that ends at, or holds, the lane's byte j
-__device__ __forceinline__ int run_start(const LaneOps& o, const ChunkScan& c, int j) {
+__device__ __forceinline__ int run_start(const awvw::OpMasks& o, const ChunkScan& c, int j) {
   const unsigned nd = o.valid & ~o.d & ((1u << j) - 1u);
-  return nd != 0 ? o.k0 + (31 - __clz((int)nd)) + 1 : c.start;
+  return nd != 0 ? c.k0 + (31 - __clz((int)nd)) + 1 : c.start;
 }
 // whether the chunk's last column is a 'D': what the next chunk's first column follows, and what closes the string
-__device__ __forceinline__ unsigned chunk_last_d(const LaneOps& o, long long span, long long base) {
+__device__ __forceinline__ unsigned chunk_last_d(const awvw::OpMasks& o, long long span, long long base) {
   const long long lastb = min(span - 1 - base, (long long)CHUNK - 1);
-  const int last_lane = (int)(lastb >> 4);
-  return ((unsigned)__builtin_amdgcn_readlane((int)o.d, last_lane) >> (int)(lastb & 15)) & 1u;
+  return ((unsigned)__builtin_amdgcn_readlane((int)o.d, awvw::last_column_lane(span, base)) >> (int)(lastb & 15)) & 1u;
 }
 
 // one maximum into a target's slots: never outside the target's own len + 1
@@ -184,14 +145,15 @@ __global__ __launch_bounds__(64) void awv_msa_width_kernel(KParams kp) {
     unsigned long long l_pos = 0, l_bad = 0;  // pattern bases | text bases << 32; bad bytes
     long long l_first = LLONG_MAX, l_last = -1;  // the first and last column other than 'I', each << 1 | it is a 'D'
     for (long long base = 0; base < span; base += CHUNK) {
-      const LaneOps o = lane_ops(ops, sh, span, base, lane);
+      const awvw::OpMasks o = awvw::lane_op_masks(ops, sh, span, base, lane);
+      const int k0 = lane_k0(sh, base, lane);
       const unsigned takes_p = o.valid & ~o.i;
       l_pos += (unsigned long long)__popc(takes_p) | ((unsigned long long)__popc(o.valid & ~o.d) << 32);
-      l_bad += (unsigned long long)__popc(o.valid & ~(o.a | o.i | o.d));
+      l_bad += (unsigned long long)__popc(o.valid & ~(o.m | o.x | o.i | o.d));
       if (takes_p != 0) {
         const int jf = __builtin_ctz(takes_p), jl = 31 - __clz((int)takes_p);
-        l_first = min(l_first, ((long long)(o.k0 + jf) << 1) | (long long)((o.d >> jf) & 1u));
-        l_last = max(l_last, ((long long)(o.k0 + jl) << 1) | (long long)((o.d >> jl) & 1u));
+        l_first = min(l_first, ((long long)(k0 + jf) << 1) | (long long)((o.d >> jf) & 1u));
+        l_last = max(l_last, ((long long)(k0 + jl) << 1) | (long long)((o.d >> jl) & 1u));
       }
     }
     const unsigned long long pos = (unsigned long long)wave_sum_i64((long long)l_pos), bad = (unsigned long long)wave_sum_i64((long long)l_bad);
@@ -213,13 +175,13 @@ __global__ __launch_bounds__(64) void awv_msa_width_kernel(KParams kp) {
     unsigned l_runs = 0;
     int l_last_run = 0;  // the run that column kl is the last of, in the lane that closes it
     for (long long base = 0; base < span; base += CHUNK) {
-      const LaneOps o = lane_ops(ops, sh, span, base, lane);
-      const ChunkScan c = chunk_scan(o, sp.pb, sp.tb, cq, ct, run0, prev_d);
+      const awvw::OpMasks o = awvw::lane_op_masks(ops, sh, span, base, lane);
+      const ChunkScan c = chunk_scan(o, lane_k0(sh, base, lane), sp.pb, sp.tb, cq, ct, run0, prev_d);
       const unsigned takes_t = o.valid & ~o.d;
       for (unsigned b = c.ends; b != 0; b &= b - 1) {
         const int j = __builtin_ctz(b);
         const long long y = c.y0 + __popc(takes_t & ((1u << j) - 1u));
-        const int k = o.k0 + j, run = k - run_start(o, c, j);
+        const int k = c.k0 + j, run = k - run_start(o, c, j);
         widen_slot(kp, target, tlen, y, run);
         ++l_runs;
         if ((long long)k == kl + 1) l_last_run = run;
@@ -279,8 +241,8 @@ __global__ __launch_bounds__(64) void awv_msa_emit_kernel(KParams kp) {
     int cq = 0, ct = 0, run0 = 0;
     unsigned prev_d = 0;
     for (long long base = 0; base < span; base += CHUNK) {
-      const LaneOps o = lane_ops(ops, sh, span, base, lane);
-      const ChunkScan c = chunk_scan(o, sp.pb, sp.tb, cq, ct, run0, prev_d);
+      const awvw::OpMasks o = awvw::lane_op_masks(ops, sh, span, base, lane);
+      const ChunkScan c = chunk_scan(o, lane_k0(sh, base, lane), sp.pb, sp.tb, cq, ct, run0, prev_d);
       const unsigned takes_p = o.valid & ~o.i, takes_t = o.valid & ~o.d;
       for (unsigned b = takes_p; b != 0; b &= b - 1) {
         const int j = __builtin_ctz(b);
@@ -288,7 +250,7 @@ __global__ __launch_bounds__(64) void awv_msa_emit_kernel(KParams kp) {
         const long long x = c.x0 + __popc(takes_p & below), y = c.y0 + __popc(takes_t & below);
         const bool is_d = (o.d >> j) & 1u;
         if (!base_ok(x, qlen) || !slot_ok(y, tlen) || (!is_d && y >= tlen)) continue;
-        const long long at = is_d ? ins_column((long long)col[y], ins[y], (o.k0 + j) - run_start(o, c, j)) : (long long)col[y];
+        const long long at = is_d ? ins_column((long long)col[y], ins[y], (c.k0 + j) - run_start(o, c, j)) : (long long)col[y];
         if (at >= 0 && at < W) row[at] = (uint8_t)awvcs::upper(pattern[x]);
       }
       cq += c.tot & 0xffff;
@@ -402,8 +364,6 @@ void state_release(State* s) { awvw::release_pass(s); }
 
 namespace {
 
-using awvw::whole_span;
-
 template <typename T>
 int upload(const awp::EngineView& v, Buf<T>& b, const T* src, size_t n) {
   AWV_TRY(b.reserve(std::max<size_t>(n, 1)));
@@ -466,36 +426,11 @@ int msa_core(awv_engine* e, const awv_pair* pairs, const awv_range_pair* ranges,
     tmap[(size_t)targets[j]] = (int32_t)j;
     slot_off[(size_t)j + 1] = slot_off[(size_t)j] + (uint64_t)v.len_host[targets[j]] + 1;
   }
-  std::vector<awv_pair> rpairs;
-  std::vector<Span> spans((size_t)n_all);
-  if (ranges) {
-    rpairs.resize((size_t)n_all);
-    for (int64_t i = 0; i < n_all; ++i)
-      if (!awvr::split_range(v.len_host, v.n, ranges[i], rpairs[(size_t)i], spans[(size_t)i]))
-        return awv_internal_fail(AWV_ERR_ARG, "msa_ranges: range " + std::to_string(i) + " names a sequence index or an interval out of range");
-    pairs = rpairs.data();
-  } else {
-    for (int64_t i = 0; i < n_all; ++i) {
-      if (pairs[i].q_idx < 0 || pairs[i].q_idx >= v.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= v.n)
-        return awv_internal_fail(AWV_ERR_ARG, "msa_cigars: sequence index out of range");
-      spans[(size_t)i] = whole_span(v, pairs[i]);
-    }
-  }
-  for (int64_t i = 0; i < n_all; ++i) {
-    if (awvw::outside(results[i], arena_bytes)) return awv_internal_fail(AWV_ERR_ARG, std::string(who) + ": a record's op bytes lie outside the CIGAR arena");
-    if (slices && !awvcs::slice_ok(results[i], slices[i]))
-      return awv_internal_fail(AWV_ERR_ARG, std::string(who) + ": slice " + std::to_string(i) + " does not lie inside its op string, or skips a negative number of bases");
-  }
-  // a slice is an op string of its own: the records that go up name the slices
-  std::vector<awv_result> sliced;
-  if (slices) {
-    sliced.assign(results, results + n_all);
-    for (int64_t i = 0; i < n_all; ++i) awvcs::apply_slice(sliced[(size_t)i], spans[(size_t)i], slices[i]);
-    results = sliced.data();
-  }
-  for (int64_t i = 0; i < n_all; ++i)
-    if (results[i].status == AWV_ST_COMPLETED && (int64_t)results[i].cigar_len > MAX_COLUMNS)
-      return awv_internal_fail(AWV_ERR_ARG, std::string(who) + ": an op string of more than 2^30 columns");
+  awvw::ItemCall call;
+  if (int rc = awvw::resolve_call(call, v, who, pairs, ranges, n_all, results, arena_bytes, slices)) return rc;
+  if (awvw::first_too_long(call.recs, n_all, MAX_COLUMNS) >= 0) return awv_internal_fail(AWV_ERR_ARG, std::string(who) + ": an op string of more than 2^30 columns");
+  pairs = call.pairs;
+  results = call.recs;
 
   // the call's tables
   const uint64_t slots = slot_off[(size_t)nt];
@@ -503,7 +438,7 @@ int msa_core(awv_engine* e, const awv_pair* pairs, const awv_range_pair* ranges,
   if (int rc = upload(v, st->d_targets, targets, (size_t)nt)) return rc;
   if (int rc = upload(v, st->d_slot_off, slot_off.data(), slot_off.size())) return rc;
   if (int rc = upload(v, st->d_pairs, pairs, (size_t)n_all)) return rc;
-  if (int rc = upload(v, st->d_spans, spans.data(), (size_t)n_all)) return rc;
+  if (int rc = upload(v, st->d_spans, call.spans.data(), (size_t)n_all)) return rc;
   AWV_TRY(st->d_out.reserve(std::max<size_t>((size_t)n_all, 1)));
   AWV_TRY(st->d_ends.reserve(std::max<size_t>((size_t)n_all, 1)));
   AWV_TRY(st->d_ins.reserve(std::max<size_t>((size_t)slots, 1)));
@@ -512,23 +447,19 @@ int msa_core(awv_engine* e, const awv_pair* pairs, const awv_range_pair* ranges,
   if (slots) AWV_TRY(hipMemsetAsync(st->d_ins.p, 0, (size_t)slots * sizeof(uint32_t), v.stream));
   if (n_all) AWV_TRY(hipMemsetAsync(st->d_ends.p, 0, (size_t)n_all * sizeof(Ends), v.stream));
 
-  // (1) the widths, in pieces (record_pieces.hpp) that keep every string's offset modulo 16
-  std::vector<uint8_t> stage;
-  std::vector<awv_result> recs;
-  for (int64_t first = 0; first < n_all;) {
-    const awvw::Piece pc = awvw::pack_piece(results, n_all, first, cigar_arena, max_arena, true, recs, stage);
-    AWV_TRY(st->d_arena.reserve((size_t)pc.bytes + 64));
-    if (pc.bytes) AWV_TRY(hipMemcpyAsync(st->d_arena.p, stage.data(), (size_t)pc.bytes, hipMemcpyHostToDevice, v.stream));
+  // (1) the widths, in pieces
+  const auto widen = [&](int64_t first, int64_t n, const awv_result* recs, uint64_t bytes) {
     unsigned long long hc[COUNTERS] = {0, 0, 0, 0, 0};
     float ms = 0;
-    if (int rc = launch(v, st, false, first, pc.n, recs.data(), pc.bytes, hc, ms)) return rc;
+    if (int rc = launch(v, st, false, first, n, recs, bytes, hc, ms)) return rc;
     st->stats.width_ms += ms;
     st->stats.failed += hc[1];
     st->stats.columns += hc[2];
     st->stats.runs += hc[3];
     st->stats.bases += hc[4];
-    first += pc.n;
-  }
+    return (int)AWV_OK;
+  };
+  if (int rc = st->each_piece(v, results, n_all, cigar_arena, max_arena, widen)) return rc;
   st->stats.items = (uint64_t)n_all;
 
   // (2) the columns, one width per target and the items' column intervals
@@ -592,27 +523,23 @@ int msa_core(awv_engine* e, const awv_pair* pairs, const awv_range_pair* ranges,
     AWV_TRY(hipEventElapsedTime(&ms, st->ev0, st->ev1));
     st->stats.emit_ms += ms;
   }
-  for (int64_t first = 0; first < n_all;) {
-    const awvw::Piece pc = awvw::pack_piece(results, n_all, first, cigar_arena, max_arena, true, recs, stage);
-    if (pc.bytes) AWV_TRY(hipMemcpyAsync(st->d_arena.p, stage.data(), (size_t)pc.bytes, hipMemcpyHostToDevice, v.stream));
+  const auto emit = [&](int64_t first, int64_t n, const awv_result* recs, uint64_t piece_bytes) {  // (the same pieces: d_arena holds each already)
     unsigned long long hc[COUNTERS] = {0, 0, 0, 0, 0};
     float ms = 0;
-    if (int rc = launch(v, st, true, first, pc.n, recs.data(), pc.bytes, hc, ms)) return rc;
+    if (int rc = launch(v, st, true, first, n, recs, piece_bytes, hc, ms)) return rc;
     st->stats.emit_ms += ms;
-    first += pc.n;
-  }
+    return (int)AWV_OK;
+  };
+  if (int rc = st->each_piece(v, results, n_all, cigar_arena, max_arena, emit)) return rc;
   AWV_TRY(hipMemcpyAsync(buf, st->d_buf.p, (size_t)bytes, hipMemcpyDeviceToHost, v.stream));
   AWV_TRY(hipStreamSynchronize(v.stream));
   return AWV_OK;
 }
 
-int check_call_args(const char* name, int64_t n, const void* who, const awv_result* results, const uint8_t* cigar_arena, uint64_t arena_bytes,
-                    const int32_t* targets, int64_t nt, const awv_msa_item* items, const awv_msa_target* tgts, const uint8_t* buf, uint64_t cap,
-                    const uint64_t* msa_bytes) {
-  if (n < 0 || nt < 0 || !msa_bytes || (n > 0 && (!who || !results || !items)) || (nt > 0 && (!targets || !tgts)) || (cap > 0 && !buf))
-    return awv_internal_fail(AWV_ERR_ARG, std::string(name) + ": null argument");
-  if (arena_bytes > 0 && !cigar_arena) return awv_internal_fail(AWV_ERR_ARG, std::string(name) + ": null arena");
-  return AWV_OK;
+// an awv_msa_cigars / awv_msa_ranges call's own outputs and counts
+bool outputs_ok(int64_t n, const int32_t* targets, int64_t nt, const awv_msa_item* items, const awv_msa_target* tgts, const uint8_t* buf, uint64_t cap,
+                const uint64_t* msa_bytes) {
+  return nt >= 0 && msa_bytes && (n <= 0 || items) && (nt == 0 || (targets && tgts)) && (cap == 0 || buf);
 }
 
 }  // namespace
@@ -657,7 +584,7 @@ int awv_msa_cigars(awv_engine* e, const awv_pair* pairs, int64_t n, const awv_re
                    const awv_cs_slice* slices, const int32_t* targets, int64_t nt, awv_msa_item* items, awv_msa_target* tgts, uint8_t* buf, uint64_t cap,
                    uint64_t* msa_bytes) {
   if (!e) return awv_internal_null_engine();
-  if (int rc = awvmsa::check_call_args("msa_cigars", n, pairs, results, cigar_arena, arena_bytes, targets, nt, items, tgts, buf, cap, msa_bytes)) return rc;
+  if (int rc = awvw::check_call_args("msa_cigars", n, pairs, results, awvmsa::outputs_ok(n, targets, nt, items, tgts, buf, cap, msa_bytes), cigar_arena, arena_bytes)) return rc;
   AWV_GUARDED(return awvmsa::msa_core(e, pairs, nullptr, n, results, cigar_arena, arena_bytes, slices, awv_internal_max_arena(e), targets, nt, items, tgts, buf,
                                       cap, msa_bytes);)
 }
@@ -666,7 +593,7 @@ int awv_msa_ranges(awv_engine* e, const awv_range_pair* ranges, int64_t n, const
                    const awv_cs_slice* slices, const int32_t* targets, int64_t nt, awv_msa_item* items, awv_msa_target* tgts, uint8_t* buf, uint64_t cap,
                    uint64_t* msa_bytes) {
   if (!e) return awv_internal_null_engine();
-  if (int rc = awvmsa::check_call_args("msa_ranges", n, ranges, results, cigar_arena, arena_bytes, targets, nt, items, tgts, buf, cap, msa_bytes)) return rc;
+  if (int rc = awvw::check_call_args("msa_ranges", n, ranges, results, awvmsa::outputs_ok(n, targets, nt, items, tgts, buf, cap, msa_bytes), cigar_arena, arena_bytes)) return rc;
   static const awv_range_pair none{};
   AWV_GUARDED(return awvmsa::msa_core(e, nullptr, n > 0 ? ranges : &none, n, results, cigar_arena, arena_bytes, slices, awv_internal_max_arena(e), targets, nt,
                                       items, tgts, buf, cap, msa_bytes);)

@@ -1,5 +1,5 @@
-// record_pieces.hpp -- how a call on caller-supplied records (awv_verify_cigars, awv_clip_cigars, awv_split_cigars,
-// awv_normalize_cigars, awv_encode_cigars, awv_cs_cigars) is cut into launches: pure host code, no HIP, so a CPU program can run it (tests/record_pieces_driver.cpp).
+// record_pieces.hpp -- how a call on caller-supplied records (the awv_*_cigars / _ranges entry points of all ten record passes) is
+// cut into launches: pure host code, no HIP, so a CPU program can run it (tests/record_pieces_driver.cpp).
 //
 // A piece holds at most max_arena op bytes (one record alone may exceed that) and at most max_records records.  The op bytes
 // of a piece are packed into 16-byte slots of a staging buffer, so records may share, overlap or leave out parts of the

@@ -1,5 +1,6 @@
 // text_pass.hpp -- what a text pass shares on top of record_pass.hpp: a record pass whose output's size depends
-// on the data, so that it takes three steps on the stream.  encode.hip (awv_cigar_text) and cs.hip (awv_cs_text) are the two.
+// on the data, so that it takes three steps on the stream.  encode.hip (awv_cigar_text) and cs.hip (awv_cs_text) are the two;
+// variants.hip, whose rows are placed the same way, takes the walk by runs and the scan kernel from here.
 //   1. measure: the pass's kernel walks every record and writes its text length (Text.len, and the pass's own 32-bit field);
 //   2. scan: awv_text_scan_kernel's exclusive scan over `len` in record order gives every record its place (Text.off) in a dense
 //      text arena and the arena's size, the only thing the host waits for before it sizes the text buffer;
@@ -88,8 +89,7 @@ __device__ __forceinline__ long long run_start_before(const LaneRuns& r, int sh,
 
 // at the end of a chunk: the op of its last column and the chunk's last break go on to the next
 __device__ __forceinline__ void carry_on(RunCarry& c, const LaneRuns& r, int sh, long long span, long long base) {
-  const int last_lane = (int)min(63ll, (span - 1 - base) >> 4);  // the lane that holds the chunk's last column
-  c.prev = (unsigned)__builtin_amdgcn_readlane((int)r.last, last_lane);
+  c.prev = (unsigned)__builtin_amdgcn_readlane((int)r.last, last_column_lane(span, base));
   const int kall = __builtin_amdgcn_readlane(r.kin, 63);
   if (kall >= 0) c.start = base + kall - sh;
 }
@@ -125,13 +125,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void awv_text_scan_kernel(Text* out, 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
 constexpr int TEXT_COUNTERS = 16;  // [0..2] the measure kernel's (cursor and the pass's two), [4] the scan's total, [8] the emit kernel's cursor
-
-// what fits Text.len: refused before anything is launched
-inline int check_lengths(const awv_result* recs, int64_t n, int64_t max_columns, const char* message) {
-  for (int64_t i = 0; i < n; ++i)
-    if (recs[i].status == AWV_ST_COMPLETED && (int64_t)recs[i].cigar_len > max_columns) return awv_internal_fail(AWV_ERR_ARG, message);
-  return AWV_OK;
-}
 
 struct TextLaunch {              // what one measure_scan_emit did
   uint64_t end = 0;              // the records' texts take [text_base, end) of the call's arena
@@ -180,23 +173,18 @@ struct TextPass : RecordPass {
     return AWV_OK;
   }
 
-  // awv_*_cigars: the call in pieces (record_pieces.hpp) that keep every string's offset modulo 16; the offsets run on from piece
-  // to piece.  launch_piece(first, n, recs, arena_bytes, text_base, want_text, &end) is the pass's launch over records
-  // [first, first + n), whose op bytes are in d_arena.  A piece's text is kept here while the text so far fits the caller's buffer,
-  // which is written at the end, all of it or none.
+  // awv_*_cigars: the call in pieces (each_piece); the offsets run on from piece to piece.  launch_piece(first, n, recs,
+  // arena_bytes, text_base, want_text, &end) is the pass's launch over records [first, first + n), whose op bytes are in d_arena.
+  // A piece's text is kept here while the text so far fits the caller's buffer, which is written at the end, all of it or none.
   template <typename LaunchPiece>
   int in_pieces(const awp::EngineView& v, const awv_result* results, int64_t n_all, const uint8_t* cigar_arena, uint64_t max_arena, uint8_t* text_buf,
                 uint64_t text_cap, uint64_t* text_bytes, LaunchPiece&& launch_piece) {
-    std::vector<uint8_t> stage, text;
-    std::vector<awv_result> recs;
+    std::vector<uint8_t> text;
     uint64_t at = 0;
     bool fits = text_buf != nullptr;
-    for (int64_t first = 0; first < n_all;) {
-      const Piece pc = pack_piece(results, n_all, first, cigar_arena, max_arena, true, recs, stage);
-      AWV_TRY(d_arena.reserve((size_t)pc.bytes + 64));
-      if (pc.bytes) AWV_TRY(hipMemcpyAsync(d_arena.p, stage.data(), (size_t)pc.bytes, hipMemcpyHostToDevice, v.stream));
+    const auto piece = [&](int64_t first, int64_t n, const awv_result* recs, uint64_t bytes) {
       uint64_t end = at;
-      if (int rc = launch_piece(first, pc.n, recs.data(), pc.bytes, at, fits, &end)) return rc;
+      if (int rc = launch_piece(first, n, recs, bytes, at, fits, &end)) return rc;
       fits = fits && end <= text_cap;
       if (fits && end > at) {
         text.resize((size_t)end);
@@ -204,8 +192,9 @@ struct TextPass : RecordPass {
         AWV_TRY(hipStreamSynchronize(v.stream));
       }
       at = end;
-      first += pc.n;
-    }
+      return (int)AWV_OK;
+    };
+    if (int rc = each_piece(v, results, n_all, cigar_arena, max_arena, piece)) return rc;
     *text_bytes = at;
     if (fits && at > 0) std::memcpy(text_buf, text.data(), (size_t)at);
     return AWV_OK;

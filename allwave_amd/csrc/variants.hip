@@ -9,7 +9,7 @@
 // walks the sound items again and writes count-1 rows in column order: awv_variants_one_host's rows, byte for byte.
 // Who owns which event: an 'X' column its SNV; the lane that holds the break that ends a gap run the run's event, before the
 // break byte's own SNV; lane 0 the string's last run, behind the chunks.  A lane's first row is a wave add-scan of the lanes'
-// event counts plus a uniform carry.  A column's pattern and text position are cs.hip's packed add-scan; a run's pos / p_beg are
+// event counts plus a uniform carry.  A column's pattern and text position are the packed add-scan of wave_ops.hpp (consumed_scan); a run's pos / p_beg are
 // the positions at its end minus its length.  The allele hash of a 'D' run is a segmented wave scan of HashSeg elements over the
 // lanes (a lane wholly inside a run is a pass-through) and one uniform hash carried from chunk to chunk.
 // Hang discipline: every loop's trip count is a host-validated length or a 16-bit mask; scans, readlane and
@@ -22,9 +22,9 @@
 #include <string>
 #include <vector>
 
-#include "batch_items.hpp"  // contributing_items, whole_span
+#include "batch_items.hpp"  // contributing_items
 #include "seq_load.hpp"     // load16
-#include "text_pass.hpp"    // lane_runs, run_start_before's carry, awv_text_scan_kernel, TEXT_COUNTERS; record_pass.hpp below it
+#include "text_pass.hpp"    // lane_runs, run_start_before's carry, awv_text_scan_kernel, TEXT_COUNTERS; record_pass.hpp below it: each_piece, resolve_call
 
 namespace awvvar {
 
@@ -146,38 +146,30 @@ __global__ __launch_bounds__(64) void awv_variants_kernel(KParams kp) {
     bool l_bad = false;
     for (long long base = 0; base < span; base += CHUNK) {  // ceil(span / 1,024) trips: span <= 2^30 + 15 by the host's check
       const awvw::LaneRuns r = awvw::lane_runs(ops, sh, span, base, lane, carry);
-      const u32x4 w = r.w;
-      LaneCols c;
-      c.valid = ((1u << r.jhi) - 1u) & ~((1u << r.jlo) - 1u);
-      unsigned m_m = 0, m_x = 0, m_i = 0, m_d = 0;
+      awvw::OpMasks o = awvw::window_masks(r.jlo, r.jhi);  // (awvw::op_masks, written out: see there)
 #pragma unroll
-      for (int j = 0; j < LANE_BYTES; ++j) {
-        const unsigned op = (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
-        m_m |= (unsigned)(op == 'M') << j;
-        m_x |= (unsigned)(op == 'X') << j;
-        m_i |= (unsigned)(op == 'I') << j;
-        m_d |= (unsigned)(op == 'D') << j;
-      }
-      c.x = m_x & c.valid;
-      c.i = m_i & c.valid;
-      c.d = m_d & c.valid;
+      for (int j = 0; j < LANE_BYTES; ++j) awvw::add_op(o, r.w, j);
+      awvw::cut_to_window(o);
+      LaneCols c;
+      c.valid = o.valid;
+      c.x = o.x;
+      c.i = o.i;
+      c.d = o.d;
       c.brk = r.brk;
       c.prev_i = r.prev == 'I';
       c.prev_d = r.prev == 'D';
       const unsigned takes_p = c.valid & ~c.i, takes_t = c.valid & ~c.d;
       if (!EMIT) {
-        l_bad = l_bad || (c.valid & ~(m_m | m_x | m_i | m_d)) != 0;
+        l_bad = l_bad || (o.valid & ~(o.m | o.x | o.i | o.d)) != 0;
         l_pos += (unsigned long long)__popc(takes_p) | ((unsigned long long)__popc(takes_t) << 32);
         l_snv += (unsigned long long)__popc(c.x);
         l_gap += (unsigned long long)__popc(ends_d(c)) | ((unsigned long long)__popc(ends_i(c)) << 32);
       } else {
-        const int counts = __popc(takes_p) | (__popc(takes_t) << 16);  // (a chunk holds 1,024 columns: the sums fit 16 bits each)
-        const int s_pos = wave_scan_add(counts);
-        const int ex = s_pos - counts;
+        const awvw::ConsumedScan pos = awvw::consumed_scan(o);
         const int cnt = (int)lane_event_count(c);
         const int s_ev = wave_scan_add(cnt);
         u32x4 pb16 = u32x4{0u, 0u, 0u, 0u};
-        if ((c.x | c.d) != 0) pb16 = load16(pattern, plen, cq + (ex & 0xffff));
+        if ((c.x | c.d) != 0) pb16 = load16(pattern, plen, cq + (pos.ex & 0xffff));
         const auto byte = [&](int k) { return byte_at(pb16, k); };
         uint64_t in_h = hcarry;  // (a chunk without a 'D': only its first column can end the run in progress)
         if (__ballot(c.d != 0) != 0) {  // (uniform)
@@ -194,12 +186,11 @@ __global__ __launch_bounds__(64) void awv_variants_kernel(KParams kp) {
         }
         if (cnt != 0) {
           unsigned at = c_ev + (unsigned)(s_ev - cnt);
-          lane_events(c, pr.q_idx, pr.t_idx, pr.q_revcomp != 0, r.b0 - sh, r.rs0, (int64_t)sp.pb + cq + (ex & 0xffff), (int64_t)sp.tb + ct + (ex >> 16), in_h, byte,
+          lane_events(c, pr.q_idx, pr.t_idx, pr.q_revcomp != 0, r.b0 - sh, r.rs0, (int64_t)sp.pb + cq + (pos.ex & 0xffff), (int64_t)sp.tb + ct + (pos.ex >> 16), in_h, byte,
                       [&](const awv_variant& ev) { put(at, ev); });
         }
-        const int tot = __builtin_amdgcn_readlane(s_pos, 63);
-        cq += tot & 0xffff;
-        ct += tot >> 16;
+        cq += pos.tot & 0xffff;
+        ct += pos.tot >> 16;
         c_ev += (unsigned)__builtin_amdgcn_readlane(s_ev, 63);
       }
       awvw::carry_on(carry, r, sh, span, base);
@@ -271,14 +262,15 @@ bool active(const State* s) { return s && s->on; }
 
 namespace {
 
+constexpr const char* TOO_LONG = "variants: an op string of more than 2^30 columns";
+
 int open_state(awv_engine* e, awp::EngineView& v, State*& st, bool need_set = true) {
   if (int rc = awvw::open_pass(awv_internal_variants(e), e, v, st, need_set)) return rc;
   if (!st->fs) st->fs = fold_scratch_new();
   return AWV_OK;
 }
-int open_active(awv_engine* e, const char* who, awp::EngineView& v, State*& st) {
-  if (!active(awv_internal_variants(e))) return awv_internal_fail(AWV_ERR_STATE, std::string(who) + " before awv_engine_variants_begin");
-  if (int rc = open_state(e, v, st)) return rc;
+int open_active(awv_engine* e, const char* who, awp::EngineView& v, State*& st) {  // (an engine that accumulates has its fold scratch: begin made it)
+  if (int rc = awvw::open_active(awv_internal_variants(e), who, "variants", e, v, st)) return rc;
   if (v.n != st->nseq) return awv_internal_fail(AWV_ERR_STATE, "variants: the sequence set changed since awv_engine_variants_begin");
   return AWV_OK;
 }
@@ -343,15 +335,8 @@ int copy_out(const awp::EngineView& v, const Table& tb, awv_variant* rows, uint6
 int launch(const awp::EngineView& v, State* st, Table& tb, bool may_fold, const awv_pair* pairs, const Span* spans, int64_t n, const awv_result* recs,
            const uint8_t* d_arena, uint64_t arena_bytes, awv_var_item* items) {
   if (n == 0) return AWV_OK;
-  for (int64_t i = 0; i < n; ++i) {
-    if (pairs[i].q_idx < 0 || pairs[i].q_idx >= v.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= v.n)
-      return awv_internal_fail(AWV_ERR_ARG, "variants: sequence index out of range");
-    const Span& sp = spans[i];
-    if (sp.pb < 0 || sp.tb < 0 || sp.pe > v.len_host[pairs[i].q_idx] || sp.te > v.len_host[pairs[i].t_idx] || (int64_t)sp.pb > (int64_t)sp.pe + 1 ||
-        (int64_t)sp.tb > (int64_t)sp.te + 1)
-      return awv_internal_fail(AWV_ERR_ARG, "variants: an interval outside its sequence");
-  }
-  if (int rc = awvw::check_lengths(recs, n, MAX_COLUMNS, "variants: an op string of more than 2^30 columns")) return rc;
+  if (int rc = awvw::check_rectangles(v, "variants", pairs, spans, n)) return rc;
+  if (int rc = awvw::check_lengths(recs, n, MAX_COLUMNS, TOO_LONG)) return rc;
   if (int rc = st->begin(v, "variants", n, recs, arena_bytes)) return rc;
   AWV_TRY(st->d_pairs.reserve((size_t)n));
   AWV_TRY(st->d_spans.reserve((size_t)n));
@@ -428,50 +413,17 @@ int variants_cigars_core(awv_engine* e, const awv_pair* pairs, const awv_range_p
   awp::EngineView v;
   State* st = nullptr;
   if (int rc = fold == AWV_VTAB_ACCUMULATE ? open_active(e, who, v, st) : open_state(e, v, st)) return rc;
-  // before anything goes up: every rectangle inside its sequences, every completed record's op bytes inside the caller's arena,
-  // every slice inside its string
-  std::vector<awv_pair> rpairs;
-  std::vector<Span> spans((size_t)n_all);
-  if (ranges) {
-    rpairs.resize((size_t)n_all);
-    for (int64_t i = 0; i < n_all; ++i)
-      if (!awvr::split_range(v.len_host, v.n, ranges[i], rpairs[(size_t)i], spans[(size_t)i]))
-        return awv_internal_fail(AWV_ERR_ARG, "variants_ranges: range " + std::to_string(i) + " names a sequence index or an interval out of range");
-    pairs = rpairs.data();
-  } else {
-    for (int64_t i = 0; i < n_all; ++i) {
-      if (pairs[i].q_idx < 0 || pairs[i].q_idx >= v.n || pairs[i].t_idx < 0 || pairs[i].t_idx >= v.n)
-        return awv_internal_fail(AWV_ERR_ARG, "variants_cigars: sequence index out of range");
-      spans[(size_t)i] = awvw::whole_span(v, pairs[i]);
-    }
-  }
-  for (int64_t i = 0; i < n_all; ++i) {
-    if (awvw::outside(results[i], arena_bytes)) return awv_internal_fail(AWV_ERR_ARG, std::string(who) + ": a record's op bytes lie outside the CIGAR arena");
-    if (slices && !awvcs::slice_ok(results[i], slices[i]))
-      return awv_internal_fail(AWV_ERR_ARG, std::string(who) + ": slice " + std::to_string(i) + " does not lie inside its op string, or skips a negative number of bases");
-  }
-  // a slice is an op string of its own: the records that go up name the slices
-  std::vector<awv_result> sliced;
-  if (slices) {
-    sliced.assign(results, results + n_all);
-    for (int64_t i = 0; i < n_all; ++i) awvcs::apply_slice(sliced[(size_t)i], spans[(size_t)i], slices[i]);
-    results = sliced.data();
-  }
-  if (int rc = awvw::check_lengths(results, n_all, MAX_COLUMNS, "variants: an op string of more than 2^30 columns")) return rc;
+  awvw::ItemCall call;
+  if (int rc = awvw::resolve_call(call, v, who, pairs, ranges, n_all, results, arena_bytes, slices)) return rc;
+  if (int rc = awvw::check_lengths(call.recs, n_all, MAX_COLUMNS, TOO_LONG)) return rc;
   if (int rc = too_many_items(st, n_all)) return rc;
   Table& tb = fold == AWV_VTAB_ACCUMULATE ? st->acc : st->call;
   if (fold != AWV_VTAB_ACCUMULATE) tb.n = 0;
   const uint64_t events_before = st->stats.snv + st->stats.ins + st->stats.del;
-  // in pieces (record_pieces.hpp) that keep every string's offset modulo 16; pack_piece takes one record or more, so `first` advances
-  std::vector<uint8_t> stage;
-  std::vector<awv_result> recs;
-  for (int64_t first = 0; first < n_all;) {
-    const awvw::Piece pc = awvw::pack_piece(results, n_all, first, cigar_arena, max_arena, true, recs, stage);
-    AWV_TRY(st->d_arena.reserve((size_t)pc.bytes + 64));
-    if (pc.bytes) AWV_TRY(hipMemcpyAsync(st->d_arena.p, stage.data(), (size_t)pc.bytes, hipMemcpyHostToDevice, v.stream));
-    if (int rc = launch(v, st, tb, fold != AWV_VTAB_EVENTS, pairs + first, spans.data() + first, pc.n, recs.data(), st->d_arena.p, pc.bytes, items + first)) return rc;
-    first += pc.n;
-  }
+  const auto piece = [&](int64_t first, int64_t n, const awv_result* recs, uint64_t bytes) {
+    return launch(v, st, tb, fold != AWV_VTAB_EVENTS, call.pairs + first, call.spans.data() + first, n, recs, st->d_arena.p, bytes, items + first);
+  };
+  if (int rc = st->each_piece(v, call.recs, n_all, cigar_arena, max_arena, piece)) return rc;
   if (fold == AWV_VTAB_ACCUMULATE) {
     *n_rows = st->stats.snv + st->stats.ins + st->stats.del - events_before;
     return AWV_OK;
@@ -481,10 +433,10 @@ int variants_cigars_core(awv_engine* e, const awv_pair* pairs, const awv_range_p
   return copy_out(v, tb, rows, cap, n_rows);
 }
 
-int check_call_args(const char* name, int64_t n, const void* who, const awv_result* results, const uint8_t* cigar_arena, uint64_t arena_bytes,
-                    const awv_var_item* items, const awv_variant* rows, uint64_t cap, const uint64_t* n_rows) {
-  if (n < 0 || !n_rows || (n > 0 && (!who || !results || !items))) return awv_internal_fail(AWV_ERR_ARG, std::string(name) + ": null argument");
-  if (arena_bytes > 0 && !cigar_arena) return awv_internal_fail(AWV_ERR_ARG, std::string(name) + ": null arena");
+// list: the pairs or ranges
+int check_args(const char* name, int64_t n, const void* list, const awv_result* results, const uint8_t* cigar_arena, uint64_t arena_bytes,
+               const awv_var_item* items, const awv_variant* rows, uint64_t cap, const uint64_t* n_rows) {
+  if (int rc = awvw::check_call_args(name, n, list, results, n_rows && (n <= 0 || items), cigar_arena, arena_bytes)) return rc;
   if (cap > 0 && !rows) return awv_internal_fail(AWV_ERR_ARG, std::string(name) + ": null row buffer");
   return AWV_OK;
 }
@@ -550,18 +502,10 @@ int awv_variants_one_host(int32_t q_idx, int32_t t_idx, int32_t q_revcomp, const
                           awv_var_item* out) {
   if (!out || !n_events || q_idx < 0 || t_idx < 0 || qlen < 0 || tlen < 0 || n < 0 || (qlen > 0 && !pattern) || (n > 0 && !cigar) || (cap > 0 && !events))
     return awv_internal_fail(AWV_ERR_ARG, "variants_one_host: bad argument");
-  if (pb < 0 || pb > pe || pe > qlen || tb < 0 || tb > te || te > tlen) return awv_internal_fail(AWV_ERR_ARG, "variants_one_host: an interval outside its sequence");
-  int64_t beg = 0, end = n, q_skip = 0, t_skip = 0;
-  if (slice) {
-    if (slice->col_beg > slice->col_end || (int64_t)slice->col_end > n || slice->q_skip < 0 || slice->t_skip < 0)
-      return awv_internal_fail(AWV_ERR_ARG, "variants_one_host: the slice does not lie inside the op string, or skips a negative number of bases");
-    beg = slice->col_beg;
-    end = slice->col_end;
-    q_skip = slice->q_skip;
-    t_skip = slice->t_skip;
-  }
-  if (end - beg > awvvar::MAX_COLUMNS) return awv_internal_fail(AWV_ERR_ARG, "variants_one_host: an op string of more than 2^30 columns");
-  *out = awvvar::var_one(q_idx, t_idx, q_revcomp != 0, pattern, awvvar::Span{pb, pe, tb, te}, cigar + beg, end - beg, q_skip, t_skip, events, cap, n_events);
+  if (int rc = awvw::check_host_rectangle("variants_one_host", qlen, tlen, pb, pe, tb, te)) return rc;
+  awvw::HostSlice sl;
+  if (int rc = awvw::check_host_slice("variants_one_host", slice, n, awvvar::MAX_COLUMNS, sl)) return rc;
+  *out = awvvar::var_one(q_idx, t_idx, q_revcomp != 0, pattern, awvvar::Span{pb, pe, tb, te}, cigar + sl.beg, sl.end - sl.beg, sl.q_skip, sl.t_skip, events, cap, n_events);
   return AWV_OK;
 }
 
@@ -601,7 +545,7 @@ int awv_engine_variants_stats(const awv_engine* e, awv_variants_stats* out) {
 int awv_variants_cigars(awv_engine* e, const awv_pair* pairs, int64_t n, const awv_result* results, const uint8_t* cigar_arena, uint64_t arena_bytes,
                         const awv_cs_slice* slices, int32_t fold, awv_var_item* items, awv_variant* rows, uint64_t cap, uint64_t* n_rows) {
   if (!e) return awv_internal_null_engine();
-  if (int rc = awvvar::check_call_args("variants_cigars", n, pairs, results, cigar_arena, arena_bytes, items, rows, cap, n_rows)) return rc;
+  if (int rc = awvvar::check_args("variants_cigars", n, pairs, results, cigar_arena, arena_bytes, items, rows, cap, n_rows)) return rc;
   AWV_GUARDED(return awvvar::variants_cigars_core(e, pairs, nullptr, n, results, cigar_arena, arena_bytes, slices, awv_internal_max_arena(e), fold, items, rows,
                                                   cap, n_rows);)
 }
@@ -609,7 +553,7 @@ int awv_variants_cigars(awv_engine* e, const awv_pair* pairs, int64_t n, const a
 int awv_variants_ranges(awv_engine* e, const awv_range_pair* ranges, int64_t n, const awv_result* results, const uint8_t* cigar_arena, uint64_t arena_bytes,
                         const awv_cs_slice* slices, int32_t fold, awv_var_item* items, awv_variant* rows, uint64_t cap, uint64_t* n_rows) {
   if (!e) return awv_internal_null_engine();
-  if (int rc = awvvar::check_call_args("variants_ranges", n, ranges, results, cigar_arena, arena_bytes, items, rows, cap, n_rows)) return rc;
+  if (int rc = awvvar::check_args("variants_ranges", n, ranges, results, cigar_arena, arena_bytes, items, rows, cap, n_rows)) return rc;
   static const awv_range_pair none{};
   AWV_GUARDED(return awvvar::variants_cigars_core(e, nullptr, n > 0 ? ranges : &none, n, results, cigar_arena, arena_bytes, slices, awv_internal_max_arena(e), fold,
                                                   items, rows, cap, n_rows);)

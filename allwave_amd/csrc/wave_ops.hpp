@@ -1,8 +1,10 @@
-// wave_ops.hpp -- what the record kernels (verify.hip, clip.hip, split.hip, normalize.hip, encode.hip, cs.hip: namespaces awvf,
-// awvc, awvs, awvn, awve, awvcs) share on the device, in namespace awvw: the take of the next record from the cursor, the chunk a
-// wave reads (64 lanes x 16 op bytes), wave64 inclusive scans on the DPP network, one byte of a lane's 16 and packed byte
-// counting over them; and the device buffer their host sides keep (record_pass.hpp).  What only the two text passes share on
-// the device is text_pass.hpp.
+// wave_ops.hpp -- what the kernels of the ten record passes (verify.hip, clip.hip, split.hip, normalize.hip, encode.hip, cs.hip,
+// coverage.hip, variants.hip, lift.hip, msa.hip: namespaces awvf, awvc, awvs, awvn, awve, awvcs, awvcov, awvvar, awvl, awvmsa) share on
+// the device, in namespace awvw: the take of the next record from the cursor, the chunk a wave reads (64 lanes x 16 op bytes),
+// wave64 reductions and inclusive scans on the DPP network, one byte of a lane's 16 and packed byte counting over them, a lane's
+// 16 op bytes as bit masks with the packed scan of the bases they consume (cs.hip and the four passes made after it); and the
+// device buffer their host sides keep (record_pass.hpp).  What only the passes that look at runs share on the device is
+// text_pass.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -33,6 +35,16 @@ __device__ __forceinline__ unsigned long long take_record(unsigned long long* co
 __device__ __forceinline__ long long wave_sum_i64(long long v) {  // in every lane
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+__device__ __forceinline__ long long wave_min_i64(long long v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m, 64));
+  return v;
+}
+__device__ __forceinline__ long long wave_max_i64(long long v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m, 64));
   return v;
 }
 
@@ -108,6 +120,62 @@ __device__ __forceinline__ int count_bytes(unsigned w, unsigned b) {
   const unsigned x = w ^ (b * 0x01010101u);
   const unsigned nonzero = (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u;
   return 4 - __popc(nonzero);
+}
+
+// One lane's 16 op bytes of a chunk as masks over its columns.  Op byte c of the string is ops[sh + c]; a pass's bad-byte test is
+// valid & ~(m | x | i | d).
+struct OpMasks {
+  unsigned valid;       // bit j: byte j is a column
+  unsigned m, x, i, d;  // ... an 'M', an 'X', an 'I', a 'D' (cut to valid)
+};
+// The three steps that build them: the window [jlo, jhi) of the lane's bytes that are columns (0 <= jlo, jhi <= 16; none when
+// jhi <= jlo), every byte's op, the cut to the window.
+__device__ __forceinline__ OpMasks window_masks(int jlo, int jhi) { return OpMasks{((1u << jhi) - 1u) & ~((1u << jlo) - 1u), 0u, 0u, 0u, 0u}; }
+__device__ __forceinline__ void add_op(OpMasks& o, const u32x4& w, int j) {
+  const unsigned op = (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
+  o.m |= (unsigned)(op == 'M') << j;
+  o.x |= (unsigned)(op == 'X') << j;
+  o.i |= (unsigned)(op == 'I') << j;
+  o.d |= (unsigned)(op == 'D') << j;
+}
+__device__ __forceinline__ void cut_to_window(OpMasks& o) {
+  o.m &= o.valid;
+  o.x &= o.valid;
+  o.i &= o.valid;
+  o.d &= o.valid;
+}
+// from the lane's bytes w.  cs.hip and variants.hip, which have the bytes from text_pass.hpp's lane_runs, write these four lines in
+// their chunk loop instead of calling this: compiled with the call, the four cs kernels take 75 to 87 VGPRs (5 or 6 waves per
+// SIMD) in place of 57 to 62 (8), and with the loop in the kernel they take what they took (observed).
+__device__ __forceinline__ OpMasks op_masks(const u32x4& w, int jlo, int jhi) {
+  OpMasks o = window_masks(jlo, jhi);
+#pragma unroll
+  for (int j = 0; j < LANE_BYTES; ++j) add_op(o, w, j);
+  cut_to_window(o);
+  return o;
+}
+// the window and the aligned load first: lane `lane` of the chunk at `base` of a string that takes bytes [sh, span)
+__device__ __forceinline__ OpMasks lane_op_masks(const uint8_t* ops, int sh, long long span, long long base, int lane) {
+  const long long b0 = base + lane * LANE_BYTES;
+  const int jlo = (int)min(max((long long)sh - b0, 0ll), (long long)LANE_BYTES);
+  const int jhi = (int)min(max(span - b0, 0ll), (long long)LANE_BYTES);
+  u32x4 w = u32x4{0u, 0u, 0u, 0u};
+  if (b0 < span) w = *(const u32x4*)(ops + b0);
+  return op_masks(w, jlo, jhi);
+}
+// the lane that holds the chunk's last column
+__device__ __forceinline__ int last_column_lane(long long span, long long base) { return (int)min(63ll, (span - 1 - base) >> 4); }
+
+// The bases a chunk's columns consume, packed: pattern bases (every column but an 'I') in the low 16 bits, text bases (every
+// column but a 'D') in the high ones -- a chunk holds 1,024 columns, so the sums fit 16 bits each.  One add-scan over the lanes.
+struct ConsumedScan {
+  int ex;   // by the lanes below this one
+  int tot;  // by the whole chunk (uniform)
+};
+__device__ __forceinline__ ConsumedScan consumed_scan(const OpMasks& o) {
+  const int counts = __popc(o.valid & ~o.i) | (__popc(o.valid & ~o.d) << 16);
+  const int s_pos = wave_scan_add(counts);
+  return ConsumedScan{s_pos - counts, __builtin_amdgcn_readlane(s_pos, 63)};
 }
 
 // a device buffer that only ever grows

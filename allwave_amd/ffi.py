@@ -770,16 +770,12 @@ class Engine:
                 raise ValueError("slices: need one (col_beg, col_end) per record")
             sl = sl if len(sl) else np.zeros((1, 2), dtype=np.uint32)
         tout = np.zeros(max(len(results), 1), dtype=CIGAR_TEXT_DTYPE)[:len(results)]
-        return self._text_call("awv_encode_cigars", (results.ctypes.data, len(results)), arena, sl, tout, want_text, text_cap)
+        return self._text_call("awv_encode_cigars", (results.ctypes.data, len(results)), *self._arena_array(arena), sl, tout, want_text, text_cap)
 
-    def _text_call(self, fn, head, arena, sl, out, want_text, text_cap):
+    def _text_call(self, fn, head, arena, nbytes, sl, out, want_text, text_cap):
         """The text calls awv_encode_cigars / awv_cs_cigars / awv_cs_ranges (`fn`): their arguments are the engine, `head`, the
-        arena (bytes or a uint8 array) and its size, the slices (`sl`: an array, or None), the per-record array `out`, the text
+        arena and its size (as _arena_array gives them), the slices (`sl`: an array, or None), the per-record array `out`, the text
         buffer and its size, and where the text's size goes.  Returns (texts, out, text_bytes) as encode_cigars documents."""
-        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
-        nbytes = int(arena.size)
-        if nbytes == 0:
-            arena = np.zeros(1, dtype=np.uint8)
         total = C.c_uint64(0)
 
         def call(buf, cap):
@@ -827,14 +823,27 @@ class Engine:
             raise ValueError("slices: need one slice per record")
         return sl if len(sl) else np.zeros(1, dtype=CS_SLICE_DTYPE)
 
-    def _cs(self, fn, cs, pairs, results, arena, slices, want_text, text_cap):
-        mode = cs if isinstance(cs, int) and not isinstance(cs, bool) else cs_mode(cs)  # (an integer goes through as it is: the library refuses a bad one)
+    @staticmethod
+    def _arena_array(arena):
+        """bytes or a uint8 array -> (a contiguous uint8 array, its size); an empty arena is a one-byte stand-in of size 0."""
+        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
+        nbytes = int(arena.size)
+        return (arena if nbytes else np.zeros(1, dtype=np.uint8)), nbytes
+
+    def _item_call(self, pairs, results, arena, slices):
+        """The opening of every call on caller-supplied records with slices (cs, coverage, variants, lift, msa; `pairs`: the pair
+        or range array) -> (the records as a RESULT_DTYPE array, one per pair; the slices as _slice_array gives them; the arena
+        and its size as _arena_array gives them)."""
         results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
         if results.shape != (len(pairs),):
             raise ValueError("results: need one record per pair")
-        sl = self._slice_array(slices, len(results))
+        return (results, self._slice_array(slices, len(results))) + self._arena_array(arena)
+
+    def _cs(self, fn, cs, pairs, results, arena, slices, want_text, text_cap):
+        mode = cs if isinstance(cs, int) and not isinstance(cs, bool) else cs_mode(cs)  # (an integer goes through as it is: the library refuses a bad one)
+        results, sl, arena, nbytes = self._item_call(pairs, results, arena, slices)
         csout = np.zeros(max(len(results), 1), dtype=CS_TEXT_DTYPE)[:len(results)]
-        return self._text_call(fn, (mode, pairs.ctypes.data, len(pairs), results.ctypes.data), arena, sl, csout, want_text, text_cap)
+        return self._text_call(fn, (mode, pairs.ctypes.data, len(pairs), results.ctypes.data), arena, nbytes, sl, csout, want_text, text_cap)
 
     def coverage_begin(self, roles="both", clip_min_score=0):
         """awv_engine_coverage_begin: from now on every aligning call of this engine adds its contributing alignments to two
@@ -868,14 +877,7 @@ class Engine:
         return self._coverage("awv_coverage_ranges", self._range_array(ranges), results, arena, slices)
 
     def _coverage(self, fn, pairs, results, arena, slices):
-        results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
-        if results.shape != (len(pairs),):
-            raise ValueError("results: need one record per pair")
-        sl = self._slice_array(slices, len(results))
-        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
-        nbytes = int(arena.size)
-        if nbytes == 0:
-            arena = np.zeros(1, dtype=np.uint8)
+        results, sl, arena, nbytes = self._item_call(pairs, results, arena, slices)
         items = np.zeros(max(len(results), 1), dtype=COV_ITEM_DTYPE)[:len(results)]
         rc = getattr(load(), fn)(self._h, pairs.ctypes.data, len(pairs), results.ctypes.data, arena.ctypes.data, nbytes,
                                  None if sl is None else sl.ctypes.data, items.ctypes.data)
@@ -901,14 +903,7 @@ class Engine:
         return self._msa("awv_msa_ranges", self._range_array(ranges), results, arena, targets, slices, want_blocks, cap)
 
     def _msa(self, fn, pairs, results, arena, targets, slices, want_blocks, cap):
-        results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
-        if results.shape != (len(pairs),):
-            raise ValueError("results: need one record per pair")
-        sl = self._slice_array(slices, len(results))
-        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
-        nbytes = int(arena.size)
-        if nbytes == 0:
-            arena = np.zeros(1, dtype=np.uint8)
+        results, sl, arena, nbytes = self._item_call(pairs, results, arena, slices)
         tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
         nt = len(tg)
         if nt == 0:
@@ -950,14 +945,7 @@ class Engine:
         return self._lift("awv_lift_ranges", self._range_array(ranges), results, arena, queries, slices)
 
     def _lift(self, fn, pairs, results, arena, queries, slices):
-        results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
-        if results.shape != (len(pairs),):
-            raise ValueError("results: need one record per pair")
-        sl = self._slice_array(slices, len(results))
-        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
-        nbytes = int(arena.size)
-        if nbytes == 0:
-            arena = np.zeros(1, dtype=np.uint8)
+        results, sl, arena, nbytes = self._item_call(pairs, results, arena, slices)
         q = _struct_array(queries, LIFT_QUERY_DTYPE, "queries")
         nq = len(q)
         if nq == 0:
@@ -1053,14 +1041,7 @@ class Engine:
         return self._variants("awv_variants_ranges", self._range_array(ranges), results, arena, slices, fold, cap)
 
     def _variants(self, fn, pairs, results, arena, slices, fold, cap):
-        results = np.ascontiguousarray(results, dtype=RESULT_DTYPE)
-        if results.shape != (len(pairs),):
-            raise ValueError("results: need one record per pair")
-        sl = self._slice_array(slices, len(results))
-        arena = np.frombuffer(bytes(arena), dtype=np.uint8) if not isinstance(arena, np.ndarray) else np.ascontiguousarray(arena, dtype=np.uint8)
-        nbytes = int(arena.size)
-        if nbytes == 0:
-            arena = np.zeros(1, dtype=np.uint8)
+        results, sl, arena, nbytes = self._item_call(pairs, results, arena, slices)
         items = np.zeros(max(len(results), 1), dtype=VAR_ITEM_DTYPE)[:len(results)]
         n = C.c_uint64(0)
 
